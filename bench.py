@@ -33,6 +33,11 @@ Prints ONE JSON line on rank 0 (fields: see the driver contract) including
                   the last profiled run (named by file: they are NOT measured in this process, so `traffic` is null)
   "cpu_baseline": the CPU oracle's tile loops (oracle/attention_oracle.py, a restatement of the reference's
                   src/fa1/torch/impl.py) timed on this host on a bounded sample of the same workload.
+
+`--dump-outputs DIR` writes what the LAST timed step returned on rank 0 (o and lse of the forward, dq / dk / dv of the
+backward) as DIR/<name>.npy in float32, so that two builds run with the same arguments (hence the same seeded inputs)
+can be compared output for output.  Above DUMP_BYTES in all, every array is cut to the same fixed, seeded sample of
+its rows (one row = one (b,h) unit's query or key position).
 """
 import argparse
 import json
@@ -52,6 +57,7 @@ PEAK_TFLOPS = {"bf16": 2500.0, "fp16": 2500.0, "fp32": 157.3}  # dense MFMA peak
 PEAK_HBM_GBPS = 8000.0
 DT = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
 TRAFFIC_FILES = ("r03_traffic.json", "r02_traffic.json")   # newest first; PMC passes of this command (tools/collect_traffic.py)
+DUMP_BYTES = 64 * 10 ** 6                                    # --dump-outputs: all .npy files together, headers included
 
 
 def alg_flops(bh, n, d, causal, direction):
@@ -98,6 +104,31 @@ def cpu_baseline(n, d, dtype, causal, budget_s):
     }
 
 
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """Write every tensor of `arrays` (name -> tensor, all with the same leading (BH, N) dims) as out_dir/<name>.npy in
+    float32.  When they exceed `budget` together, each is flattened to (BH * N, ...) and all of them keep the same rows:
+    a sorted sample drawn from a fixed seed, so it depends on the shapes alone.  Returns a summary for the JSON line."""
+    import numpy as np
+
+    lead = next(iter(arrays.values())).shape[:2]
+    assert all(t.shape[:2] == lead for t in arrays.values()), {k: tuple(t.shape) for k, t in arrays.items()}
+    rows = lead[0] * lead[1]
+    header = 1024                                   # np.save writes a 128-byte header for these shapes; generous
+    row_bytes = sum(t.numel() // rows * 4 for t in arrays.values())
+    keep = min(rows, (budget - header * len(arrays)) // row_bytes)
+    assert keep > 0, "budget too small for one row"
+    idx = None
+    if keep < rows:
+        idx = torch.randperm(rows, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if idx is not None:
+            t = t.reshape(rows, *t.shape[2:]).index_select(0, idx.to(t.device))
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+    return {"dir": out_dir, "rows": keep, "of_rows": rows, "arrays": sorted(arrays)}
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -123,7 +154,13 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="plumbing rehearsal without a GPU: gloo, CPU tensors, a placeholder step (no attention is "
                          "computed, value is null); exercises the launcher, the sharding, the barriers and the gather")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned on rank 0 (o, lse, dq, dk, dv) as "
+                         "DIR/<name>.npy in float32; a fixed, seeded sample of rows when they exceed 64 MB in all")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def spawn_ranks(args, argv):
@@ -255,7 +292,7 @@ def main(argv=None):
             q_.grad = k_.grad = v_.grad = None
             o = q_ + k_ + v_
             torch.autograd.backward(o, do_)
-            return o
+            return o, None
         ext = None
     else:
         import flashattention_lab_cuda as ext
@@ -263,9 +300,9 @@ def main(argv=None):
 
         def run(q_, k_, v_, do_):
             q_.grad = k_.grad = v_.grad = None
-            o, _ = fa2_cuda(q_, k_, v_, args.causal, scale, spec)
+            o, lse = fa2_cuda(q_, k_, v_, args.causal, scale, spec)
             torch.autograd.backward(o, do_)
-            return o
+            return o, lse
 
     def step():
         return run(q, k, v, do)
@@ -274,18 +311,18 @@ def main(argv=None):
         if dist is not None:
             dist.barrier(device_ids=None if dry else [local_rank])
 
-    # ---- settle + warm-up: the SAME loop as the timed one (the previous step's `o` stays alive across the call, as a
+    # ---- settle + warm-up: the SAME loop as the timed one (the previous step's `o`, `lse` stay alive across the call, as a
     # training loop's activations would), so the caching allocator is in its periodic state before the clock starts
-    o = None
+    o = lse = None
     settle_steps = 0
     t_settle = time.perf_counter()
     while not dry and time.perf_counter() - t_settle < args.settle_seconds:
-        o = step()
+        o, lse = step()
         settle_steps += 1
         if settle_steps % 8 == 0:
             sync()
     for _ in range(args.warmup):
-        o = step()
+        o, lse = step()
     sync()
     ev = None
     if not dry:
@@ -298,7 +335,7 @@ def main(argv=None):
     for i in range(args.steps):
         if ev is not None:
             ev[i][0].record()
-        o = step()
+        o, lse = step()
         if ev is not None:
             ev[i][1].record()
     sync()
@@ -319,12 +356,18 @@ def main(argv=None):
         allocator["reserved_GiB"] = round(torch.cuda.memory_reserved(dev) / 2 ** 30, 3)
         allocator["shim_workspace_GiB"] = round(ext.workspace_stats()["bytes"] / 2 ** 30, 3)
 
+    # ---- the last timed step's outputs, before the profiling pass below replaces them
+    dump = None
+    if args.dump_outputs and rank == 0:
+        last = {"o": o, "lse": lse, "dq": q.grad, "dk": k.grad, "dv": v.grad}
+        dump = dump_outputs(args.dump_outputs, {name: t for name, t in last.items() if t is not None})
+
     # ---- per-kernel durations (HIP events on the launch stream, inside the library), separate untimed pass
     prof, prof_steps = {}, min(args.steps, 50)
     if ext is not None:
         ext.profile_enable(True)
         for _ in range(prof_steps):
-            o = step()
+            o, lse = step()
         sync()
         prof = ext.profile_report()
         ext.profile_enable(False)
@@ -348,7 +391,7 @@ def main(argv=None):
         if rank == 0:
             q2, k2, v2, do2 = shards[1]
             q2, k2, v2 = (t.requires_grad_(True) for t in (q2, k2, v2))
-            o2 = run(q2, k2, v2, do2)
+            o2, _ = run(q2, k2, v2, do2)
             sync()
             diffs = [(f[chk_lo:chk_hi].float() - t_.detach().float()).abs().max().item()
                      for f, t_ in zip(full, (o2, q2.grad, k2.grad, v2.grad))]
@@ -455,6 +498,8 @@ def main(argv=None):
             "gather_check": gather_check,
             "roofline": roof, "cpu_baseline": cpu,
         }
+        if dump is not None:
+            line["dump_outputs"] = dump
         if dry:
             line["dry_run"] = True
         if line["inconsistent"]:

@@ -27,6 +27,15 @@ def _line(r):
     return json.loads(lines[0])
 
 
+def _bench_module():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
 def test_self_launch_two_ranks_weak_scaling():
     r = _run("--gpus", "2", "--dry-run", "--steps", "2", "--warmup", "1")
     assert r.returncode == 0, r.stderr[-2000:]
@@ -52,13 +61,9 @@ def test_self_launch_strong_scaling_ragged_split():
 def test_global_tensors_do_not_depend_on_who_draws_them():
     """Unit u of the global problem has the same values whichever rank draws it (per-block seeded draws): slices drawn with
     different bounds agree where they overlap."""
-    import importlib.util
-
     import torch
 
-    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
-    bench = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(bench)
+    bench = _bench_module()
     a = bench.draw_shards(200, 8, 4, torch.float32, torch.device("cpu"), 3, [(0, 200)])[0]
     b = bench.draw_shards(200, 8, 4, torch.float32, torch.device("cpu"), 3, [(50, 130), (190, 200)])
     for t in range(4):
@@ -83,3 +88,54 @@ def test_under_a_launcher_no_second_spawn():
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r)
     assert d["n_gpus"] == 1 and d["gather_ms"] is None
+
+
+def test_dump_outputs_is_reproducible(tmp_path):
+    """--dump-outputs DIR writes the last timed step's outputs as float32 .npy files, the same ones on every run with the
+    same arguments (the inputs come from fixed seeds), and --steps is the number of timed steps in the JSON line."""
+    import numpy as np
+
+    runs = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        r = _run("--dry-run", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out))
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _line(r)
+        assert d["steps"] == 3 and d["dump_outputs"]["dir"] == str(out)
+        runs.append({p.name: np.load(p) for p in sorted(out.glob("*.npy"))})
+    assert sorted(runs[0]) == ["dk.npy", "dq.npy", "dv.npy", "o.npy"]      # the dry-run placeholder has no lse
+    bh, n, dh = 4, 64, 16                                                  # the dry run's clamped workload
+    for name, a in runs[0].items():
+        assert a.dtype == np.float32 and a.shape == (bh, n, dh) and np.isfinite(a).all(), name
+        assert np.array_equal(a, runs[1][name]), name
+
+
+def test_dump_outputs_samples_the_same_rows_within_the_budget(tmp_path):
+    import numpy as np
+    import torch
+
+    bench = _bench_module()
+    g = torch.Generator().manual_seed(5)
+    arrays = {"o": torch.randn((6, 50, 8), generator=g).to(torch.bfloat16), "lse": torch.randn((6, 50), generator=g),
+              "dq": torch.randn((6, 50, 8), generator=g).to(torch.bfloat16)}
+    budget = 8192
+    info = bench.dump_outputs(str(tmp_path / "a"), arrays, budget=budget)
+    bench.dump_outputs(str(tmp_path / "b"), arrays, budget=budget)
+    assert info["of_rows"] == 300 and 0 < info["rows"] < 300
+    assert sum(p.stat().st_size for p in (tmp_path / "a").glob("*.npy")) <= budget
+    o, lse, dq = (np.load(tmp_path / "a" / f"{k}.npy") for k in ("o", "lse", "dq"))
+    assert o.dtype == lse.dtype == dq.dtype == np.float32
+    assert o.shape == dq.shape == (info["rows"], 8) and lse.shape == (info["rows"],)
+    # every array keeps the same rows of the flattened (BH * N) axis, exactly (bf16 -> float32 is exact)
+    flat_o = arrays["o"].float().reshape(300, 8).numpy()
+    rows = [int(np.flatnonzero((flat_o == r).all(axis=1))[0]) for r in o]
+    assert rows == sorted(set(rows))
+    assert np.array_equal(lse, arrays["lse"].reshape(300).numpy()[rows])
+    assert np.array_equal(dq, arrays["dq"].float().reshape(300, 8).numpy()[rows])
+    for k in ("o", "lse", "dq"):
+        assert np.array_equal(np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")), k
+
+
+def test_steps_below_one_are_refused():
+    r = _run("--dry-run", "--steps", "0", "--warmup", "0")
+    assert r.returncode != 0 and "--steps" in r.stderr
