@@ -113,6 +113,9 @@ bool use_mfma_bwd(int dtype, int64_t n, int64_t d, double s, std::initializer_li
 // function the forward evaluated.  It holds wherever the 16-bit MFMA kernels serve the call (f16 / bf16 tensors, head dims that
 // are multiples of 8 up to 256): Q, K and V then go through OCP e4m3 with one scale per 64-row block, as the reference's wiring
 // has it (csrc/fa3/fa3_fwd.cu:196-208) — at d = 128 on the e4m3 MFMA kernel, elsewhere as a round trip ahead of the 16-bit kernels.
+// V~ is the same in both: where the all-e4m3 kernel runs (fa::fp8_v_pow2) every row of the forward and the backward's round trip
+// use power-of-two V scales, elsewhere absmax / 448 ones.  What the backward does NOT reproduce is the e4m3 rounding of P in that
+// kernel: it recomputes P exactly from lse (straight-through over the 8-bit P, as over the rounding of Q, K and V).
 bool fp8_path(int dtype, int64_t n, int64_t d, double s, const void* q, const void* k, const void* v, const void* o) {
     return fa::fwd_mfma_supported(dtype, d) && fa::bwd_mfma_supported(dtype, d) && scale_ok(s) && g_mode.load() != FA_MODE_F32_GENERIC &&
            slab_ok(n, d) && aligned16({q, k, v, o});

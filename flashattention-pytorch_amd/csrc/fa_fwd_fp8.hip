@@ -19,7 +19,17 @@ namespace fa {
 
 constexpr float kE4M3Max = 448.f;
 
-// one workgroup = one 64-row block of one (b,h) of one tensor (blockIdx.z: 0 = q, 1 = k)
+// x / scl rounded once, then to e4m3 (round to nearest even, as the pair conversion does): the reference's quantise step
+// (src/fa3/torch/impl.py: x / scale, scale = absmax / 448) and the oracle's model.  Not x * (448 / absmax): e4m3 keeps 3
+// mantissa bits, so 16-bit inputs often land exactly halfway between two e4m3 values, and a reciprocal that is an ulp off
+// then rounds those the other way — one e4m3 step, up to 3.6 % of the block's absmax on the element.
+template <bool HI>
+__device__ __forceinline__ int cvt_pk_e4m3_div(float a, float b, float scl, int old) {
+    return __builtin_amdgcn_cvt_pk_fp8_f32(__fdiv_rn(a, scl), __fdiv_rn(b, scl), old, HI);
+}
+
+// one workgroup = one 64-row block of one (b,h) of one tensor (blockIdx.x = bh * nb + block, blockIdx.z: 0 = q, 1 = k; BH is
+// folded into x, as in the attention kernels, because gridDim.y stops at 65535)
 // OUT16 = false: write e4m3 bytes + scales (forward).  OUT16 = true: write the DEQUANTISED values back as 16-bit
 // tensors (backward: the gradient is taken of the function the forward actually evaluated, i.e. with the
 // quantised Q and K, which is also what the reference's fa3_backward does, csrc/fa3/fa3_bwd.cu:134-146).
@@ -58,7 +68,7 @@ __global__ __launch_bounds__(256) void fp8_quant_kernel(const uint16_t* __restri
     const uint16_t* src = blockIdx.z == 0 ? q : k;
     uint8_t* dst = blockIdx.z == 0 ? q8 : k8;
     float* sc = blockIdx.z == 0 ? sq : sk;
-    const int bh = blockIdx.y, blk = blockIdx.x, row0 = blk * 64;
+    const int bh = blockIdx.x / nb, blk = blockIdx.x - bh * nb, row0 = blk * 64;
     const size_t base = (size_t)bh * n * D;
     float xf[PER][8];
     float amax = 0.f;
@@ -87,17 +97,16 @@ __global__ __launch_bounds__(256) void fp8_quant_kernel(const uint16_t* __restri
     __syncthreads();
     amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     amax = fmaxf(amax, 1e-6f);                       // eps of block_absmax_scale
-    const float inv = kE4M3Max / amax;
-    const float scl = amax / kE4M3Max;
+    const float scl = __fdiv_rn(amax, kE4M3Max);
     if (!OUT16 && threadIdx.x == 0) sc[(size_t)bh * nb + blk] = scl;
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
         const int c = threadIdx.x + 256 * i, row = row0 + c / CPR, ch = c % CPR;
         int w0 = 0, w1 = 0;
-        w0 = __builtin_amdgcn_cvt_pk_fp8_f32(xf[i][0] * inv, xf[i][1] * inv, w0, false);
-        w0 = __builtin_amdgcn_cvt_pk_fp8_f32(xf[i][2] * inv, xf[i][3] * inv, w0, true);
-        w1 = __builtin_amdgcn_cvt_pk_fp8_f32(xf[i][4] * inv, xf[i][5] * inv, w1, false);
-        w1 = __builtin_amdgcn_cvt_pk_fp8_f32(xf[i][6] * inv, xf[i][7] * inv, w1, true);
+        w0 = cvt_pk_e4m3_div<false>(xf[i][0], xf[i][1], scl, w0);
+        w0 = cvt_pk_e4m3_div<true>(xf[i][2], xf[i][3], scl, w0);
+        w1 = cvt_pk_e4m3_div<false>(xf[i][4], xf[i][5], scl, w1);
+        w1 = cvt_pk_e4m3_div<true>(xf[i][6], xf[i][7], scl, w1);
         if (!OUT16) {
             if (row >= n) continue;
             u32x2 o2 = {(unsigned)w0, (unsigned)w1};
@@ -129,17 +138,29 @@ __global__ __launch_bounds__(256) void fp8_quant_kernel(const uint16_t* __restri
 // src/fa3/torch/impl.py:123-131) — with a real 8-bit rounding in place of its fp16 no-op.  ROT (Q and K, power-of-two
 // head dims: src/fa3/torch/impl.py:60-61 skips the others too): rotate, quantise, and rotate back, so that the round-tripped
 // tensors live in the original basis and any kernel can consume them: (Q~ R^T)(K~ R^T)^T = Q~ K~^T.
+// POW2 (V where the all-e4m3 kernel runs, fp8_v_pow2): the scale rounded up to a power of two, 2^e >= absmax / 448, exactly as
+// fp8_quant_v_kernel computes it, so that the round trip yields the V~ that kernel multiplies with.
 // Serves: fa3_forward(fp8) for head dims without an e4m3 MFMA kernel (then the 16-bit kernels run on Q~, K~, V~), the V of the
-// d = 128 kernel's bf16 P.V variant, and fa3_backward(fp8) at every head dim (it differentiates the function the forward evaluated).
+// d = 128 kernels' 16-bit P.V, and fa3_backward(fp8) at every head dim (it differentiates the function the forward evaluated).
 struct Fp8RtArgs {
     const uint16_t* src[3];
     uint16_t* dst[3];
     int rot[3];
+    int pow2[3];
 };
+
+// smallest power of two 2^e with amax / 2^e <= 448 (exponent arithmetic on the f32 bits: exact), e clamped to [-126, 126]
+__device__ __forceinline__ int pow2_scale_exp(float amax) {
+    int e = (int)((__float_as_uint(amax / kE4M3Max) >> 23) & 0xff) - 127;
+    if (__uint_as_float((unsigned)(e + 127) << 23) * kE4M3Max < amax) ++e;
+    return max(-126, min(126, e));
+}
+// one workgroup = one 64-row block: blockIdx.x = bh * nbl + block (BH folded into x: gridDim.y stops at 65535), nbl = the blocks
+// per (b,h) this launch covers (ceil(n / 64), or fewer: the leading rows only)
 template <typename Tag, int MAXI>               // MAXI: 16-byte chunks per thread = ceil(64 rows x d / 8 chunks / 256 threads): 1, 2, 4, 8
-__global__ __launch_bounds__(256) void fp8_roundtrip_kernel(Fp8RtArgs a, int n, int d) {
+__global__ __launch_bounds__(256) void fp8_roundtrip_kernel(Fp8RtArgs a, int n, int d, int nbl) {
     __shared__ float red[4];
-    const int z = blockIdx.z, bh = blockIdx.y, row0 = blockIdx.x * 64;
+    const int z = blockIdx.z, bh = blockIdx.x / nbl, row0 = (blockIdx.x - bh * nbl) * 64;
     const uint16_t* src = a.src[z];
     uint16_t* dst = a.dst[z];
     const bool rot = a.rot[z] != 0;             // the host sets it only for power-of-two d: a row is then cpr <= 32 consecutive lanes
@@ -180,16 +201,17 @@ __global__ __launch_bounds__(256) void fp8_roundtrip_kernel(Fp8RtArgs a, int n, 
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = amax;
     __syncthreads();
     amax = fmaxf(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])), 1e-6f);   // eps of block_absmax_scale
-    const float inv = kE4M3Max / amax, scl = amax / kE4M3Max;
+    float scl = __fdiv_rn(amax, kE4M3Max);
+    if (a.pow2[z]) scl = __uint_as_float((unsigned)(127 + pow2_scale_exp(amax)) << 23);   // (x / 2^e is exact)
     typedef float f32x2_t __attribute__((ext_vector_type(2)));
 #pragma unroll
     for (int i = 0; i < MAXI; ++i) {
         const int c = threadIdx.x + 256 * i, row = row0 + c / cpr, ch = c % cpr;
         int w0 = 0, w1 = 0;
-        w0 = __builtin_amdgcn_cvt_pk_fp8_f32(xf[i][0] * inv, xf[i][1] * inv, w0, false);
-        w0 = __builtin_amdgcn_cvt_pk_fp8_f32(xf[i][2] * inv, xf[i][3] * inv, w0, true);
-        w1 = __builtin_amdgcn_cvt_pk_fp8_f32(xf[i][4] * inv, xf[i][5] * inv, w1, false);
-        w1 = __builtin_amdgcn_cvt_pk_fp8_f32(xf[i][6] * inv, xf[i][7] * inv, w1, true);
+        w0 = cvt_pk_e4m3_div<false>(xf[i][0], xf[i][1], scl, w0);
+        w0 = cvt_pk_e4m3_div<true>(xf[i][2], xf[i][3], scl, w0);
+        w1 = cvt_pk_e4m3_div<false>(xf[i][4], xf[i][5], scl, w1);
+        w1 = cvt_pk_e4m3_div<true>(xf[i][6], xf[i][7], scl, w1);
         const f32x2_t a0 = __builtin_amdgcn_cvt_pk_f32_fp8(w0, false), a1 = __builtin_amdgcn_cvt_pk_f32_fp8(w0, true);
         const f32x2_t a2 = __builtin_amdgcn_cvt_pk_f32_fp8(w1, false), a3 = __builtin_amdgcn_cvt_pk_f32_fp8(w1, true);
         float y[8] = {a0[0] * scl, a0[1] * scl, a1[0] * scl, a1[1] * scl, a2[0] * scl, a2[1] * scl, a3[0] * scl, a3[1] * scl};
@@ -396,14 +418,15 @@ __global__ __launch_bounds__(512, 2) void fwd_fp8_kernel(const uint8_t* __restri
 //     row: harmless from a few dozen keys on, up to 6 % of |v| on a row that sees two.  Rows that short exist only in the FIRST
 //     query tile under the causal mask (every later tile's rows see >= 256 keys) and on problems of N <= 256: those run on the
 //     kernel above with its 16-bit P (launch_fp8_t), so that o stays what the backward — which recomputes P exactly from lse —
-//     differentiates (the delta = rowsum(dO o) it takes from the forward's o otherwise puts the same 6 % into dQ).
+//     differentiates (the delta = rowsum(dO o) it takes from the forward's o otherwise puts the same 6 % into dQ).  Their V~ is
+//     the power-of-two-scaled one all the same (fp8_v_pow2), so one V~ serves every row and the backward.
 template <typename Tag>
 __global__ __launch_bounds__(256) void fp8_quant_v_kernel(const uint16_t* __restrict__ v, uint8_t* __restrict__ v8t,
                                                           int* __restrict__ svexp, int n, int nb, int ntile) {
     constexpr int D = 128, CPR = D / 8, PER = (64 * CPR) / 256;
     __shared__ float red[4];
     __shared__ __attribute__((aligned(16))) uint8_t tr[D * 64];   // [d row][permuted key position]
-    const int bh = blockIdx.y, blk = blockIdx.x, row0 = blk * 64;
+    const int bh = blockIdx.x / nb, blk = blockIdx.x - bh * nb, row0 = blk * 64;   // BH folded into x (gridDim.y <= 65535)
     const size_t base = (size_t)bh * n * D;
     float xf[PER][8];
     float amax = 0.f;
@@ -422,10 +445,7 @@ __global__ __launch_bounds__(256) void fp8_quant_v_kernel(const uint16_t* __rest
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = amax;
     __syncthreads();
     amax = fmaxf(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])), 1e-6f);
-    // smallest power of two 2^e with amax / 2^e <= 448 (exponent arithmetic on the f32 bits: exact)
-    int e = (int)((__float_as_uint(amax / kE4M3Max) >> 23) & 0xff) - 127;
-    if (__uint_as_float((unsigned)(e + 127) << 23) * kE4M3Max < amax) ++e;
-    e = max(-126, min(126, e));
+    const int e = pow2_scale_exp(amax);
     const float inv = __uint_as_float((unsigned)(127 - e) << 23);   // 2^-e
     if (threadIdx.x == 0) svexp[(size_t)bh * nb + blk] = e + 127;   // E8M0
 #pragma unroll
@@ -624,6 +644,11 @@ __global__ __launch_bounds__(512, 2) void fwd_fp8v_kernel(const uint8_t* __restr
 
 bool fwd_fp8_supported(int dtype, int64_t d) { return (dtype == 1 || dtype == 2) && d == 128; }
 
+// Does the fp8 path use power-of-two V scales?  Exactly when the all-e4m3 kernel runs (d = 128, option fp8_pv != 1, N > 256).
+// ONE rule for every row of the forward — the rows that kernel serves, and the first query tile that the 16-bit P.V kernel serves
+// under the causal mask — and for fa3_backward's round trip of V, so that forward and backward see the same V~.
+bool fp8_v_pow2(int dtype, int64_t n, int64_t d) { return fwd_fp8_supported(dtype, d) && option(OPT_FP8_PV) != 1 && n > 256; }
+
 // workspace: [q8: BH*N*D bytes][k8: BH*N*D bytes][pad][sq: BH*nb floats][sk: BH*nb floats][svexp: BH*nb ints][pad]
 //            [v8t: BH * ntile * 128 * 128 bytes], nb = ceil(N/64), ntile = ceil(N/128)
 struct Fp8Ws { uint8_t *q8, *k8, *v8t; float *sq, *sk; int* svexp; size_t bytes; };
@@ -646,31 +671,33 @@ size_t fwd_fp8_workspace_bytes(int64_t bh, int64_t n, int64_t d) { return fp8_ws
 
 // Q and K -> e4m3 bytes + scales; then the all-e4m3 kernel (V quantised transposed) or, with option fp8_pv = 1, the kernel with
 // the 16-bit P.V on the round-tripped V (`vslab`: room for one 16-bit tensor).  Under the causal mask the first query tile, and
-// problems of N <= 256 altogether, take the 16-bit P.V in either case (see the comment above fp8_quant_v_kernel).
+// problems of N <= 256 altogether, take the 16-bit P.V in either case (see the comment above fp8_quant_v_kernel), on a V~ with
+// the scales fp8_v_pow2 gives all rows.
 template <typename Tag>
 static hipError_t launch_fp8_t(const FwdArgs& a, void* ws, void* vslab, hipStream_t st) {
     constexpr int D = 128;
     const int nb = (int)((a.n + 63) / 64), ntile = (int)((a.n + 127) / 128);
     const int nqt = (int)((a.n + 255) / 256);
     const Fp8Ws L = fp8_ws_layout(ws, a.bh, a.n, D);
-    const bool pv16 = option(OPT_FP8_PV) == 1 || a.n <= 256;
+    const bool pv16 = !fp8_v_pow2(a.dtype, a.n, D);
     const int nqt16 = pv16 ? nqt : (a.causal ? 1 : 0);          // query tiles on the 16-bit P.V kernel (the first ones)
     const int64_t vrows = pv16 ? a.n : (a.causal ? (a.n < 256 ? a.n : 256) : 0);   // rows of V they read
     {
         ProfScope ps(K_FP8_QUANT, st);
         if (option(OPT_FP8_ROT) == 2)   // option fp8_rot = 2: quantise without the incoherent rotation (A/B, tests)
-            hipLaunchKernelGGL((fp8_quant_kernel<Tag, D, false, false>), dim3(nb, (unsigned)a.bh, 2), dim3(256), 0, st, (const uint16_t*)a.q,
+            hipLaunchKernelGGL((fp8_quant_kernel<Tag, D, false, false>), dim3((unsigned)(nb * a.bh), 1, 2), dim3(256), 0, st, (const uint16_t*)a.q,
                                (const uint16_t*)a.k, L.q8, L.k8, L.sq, L.sk, (int)a.n, nb);
         else
-            hipLaunchKernelGGL((fp8_quant_kernel<Tag, D, false, true>), dim3(nb, (unsigned)a.bh, 2), dim3(256), 0, st, (const uint16_t*)a.q,
+            hipLaunchKernelGGL((fp8_quant_kernel<Tag, D, false, true>), dim3((unsigned)(nb * a.bh), 1, 2), dim3(256), 0, st, (const uint16_t*)a.q,
                                (const uint16_t*)a.k, L.q8, L.k8, L.sq, L.sk, (int)a.n, nb);
         if (!pv16)
-            hipLaunchKernelGGL(fp8_quant_v_kernel<Tag>, dim3(nb, (unsigned)a.bh), dim3(256), 0, st, (const uint16_t*)a.v, L.v8t, L.svexp,
+            hipLaunchKernelGGL(fp8_quant_v_kernel<Tag>, dim3((unsigned)(nb * a.bh)), dim3(256), 0, st, (const uint16_t*)a.v, L.v8t, L.svexp,
                                (int)a.n, nb, ntile);
-        if (vrows > 0) {   // V~ (the first `vrows` rows of every (b,h)) for the 16-bit P.V kernel
+        if (vrows > 0) {   // V~ (the first `vrows` rows of every (b,h)) for the 16-bit P.V kernel, with the scales of fp8_v_pow2
             Fp8RtArgs r{};
-            r.src[0] = (const uint16_t*)a.v; r.dst[0] = (uint16_t*)vslab; r.rot[0] = 0;
-            hipLaunchKernelGGL((fp8_roundtrip_kernel<Tag, 4>), dim3((unsigned)((vrows + 63) / 64), (unsigned)a.bh, 1), dim3(256), 0, st, r, (int)a.n, D);
+            r.src[0] = (const uint16_t*)a.v; r.dst[0] = (uint16_t*)vslab; r.rot[0] = 0; r.pow2[0] = pv16 ? 0 : 1;
+            const int nbl = (int)((vrows + 63) / 64);
+            hipLaunchKernelGGL((fp8_roundtrip_kernel<Tag, 4>), dim3((unsigned)(nbl * a.bh), 1, 1), dim3(256), 0, st, r, (int)a.n, D, nbl);
         }
     }
     hipError_t e = hipGetLastError();
@@ -707,9 +734,11 @@ static hipError_t launch_fp8_t(const FwdArgs& a, void* ws, void* vslab, hipStrea
 }
 
 // q, k, v -> their e4m3 round trips as 16-bit tensors qt, kt, vt (a null source is skipped).  Q and K are rotated around the
-// quantisation when the head dim is a power of two (option fp8_rot = 2: never), V never is.
+// quantisation when the head dim is a power of two (option fp8_rot = 2: never), V never is; V takes power-of-two scales where
+// fp8_v_pow2 says the forward's V~ has them.
 hipError_t launch_fp8_roundtrip(const void* q, const void* k, const void* v, void* qt, void* kt, void* vt, int64_t bh, int64_t n,
                                 int64_t d, int dtype, hipStream_t st) {
+    const bool vpow2 = fp8_v_pow2(dtype, n, d);
     const int nb = (int)((n + 63) / 64);
     const bool rot = option(OPT_FP8_ROT) != 2 && (d & (d - 1)) == 0;
     Fp8RtArgs a{};
@@ -717,10 +746,14 @@ hipError_t launch_fp8_roundtrip(const void* q, const void* k, const void* v, voi
     const void* srcs[3] = {q, k, v};
     void* dsts[3] = {qt, kt, vt};
     for (int i = 0; i < 3; ++i)
-        if (srcs[i]) { a.src[cnt] = (const uint16_t*)srcs[i]; a.dst[cnt] = (uint16_t*)dsts[i]; a.rot[cnt] = (i < 2 && rot) ? 1 : 0; ++cnt; }
+        if (srcs[i]) {
+            a.src[cnt] = (const uint16_t*)srcs[i]; a.dst[cnt] = (uint16_t*)dsts[i];
+            a.rot[cnt] = (i < 2 && rot) ? 1 : 0; a.pow2[cnt] = (i == 2 && vpow2) ? 1 : 0;
+            ++cnt;
+        }
     if (!cnt || bh <= 0 || n <= 0) return hipSuccess;
     ProfScope ps(K_FP8_QUANT, st);
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(nb, (unsigned)bh, cnt), dim3(256), 0, st, a, (int)n, (int)d); };
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)(nb * bh), 1, cnt), dim3(256), 0, st, a, (int)n, (int)d, nb); };
     if (dtype == 2) { if (d <= 32) go(fp8_roundtrip_kernel<bf16_tag, 1>); else if (d <= 64) go(fp8_roundtrip_kernel<bf16_tag, 2>); else if (d <= 128) go(fp8_roundtrip_kernel<bf16_tag, 4>); else go(fp8_roundtrip_kernel<bf16_tag, 8>); }
     else { if (d <= 32) go(fp8_roundtrip_kernel<f16_tag, 1>); else if (d <= 64) go(fp8_roundtrip_kernel<f16_tag, 2>); else if (d <= 128) go(fp8_roundtrip_kernel<f16_tag, 4>); else go(fp8_roundtrip_kernel<f16_tag, 8>); }
     return hipGetLastError();

@@ -96,6 +96,7 @@ hipError_t launch_bwd_dq_w4(const BwdArgs& a, float* nlse, float* ndelta, hipStr
 
 // FA3-style fp8 forward (fa_fwd_fp8.hip): Q/K quantised to e4m3 per 64-row block, S on the fp8 MFMA
 bool fwd_fp8_supported(int dtype, int64_t d);
+bool fp8_v_pow2(int dtype, int64_t n, int64_t d);   // V~ with power-of-two block scales (forward and backward alike)
 // workspace: fwd_fp8_workspace_bytes; vslab: room for one 16-bit (bh, n, d) tensor (the round-tripped V of the 16-bit P.V kernel)
 hipError_t launch_fwd_fp8(const FwdArgs& a, void* workspace, void* vslab, hipStream_t st);
 size_t fwd_fp8_workspace_bytes(int64_t bh, int64_t n, int64_t d);

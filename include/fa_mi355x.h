@@ -81,11 +81,15 @@ int fa2_backward(const void* q, const void* k, const void* v, const void* o, con
                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* --- FlashAttention-3 (replaces csrc/fa3/fa3_fwd.cu:172, csrc/fa3/fa3_bwd.cu:104).
- * fp8 != 0: where the e4m3 kernel exists (f16/bf16 tensors, d = 128) Q and K are quantised to OCP e4m3 with one
- * scale per (bh, 64-row block) and QK^T runs on the fp8 MFMA; V, P and all accumulation stay 16/32-bit, and the
- * forward needs a workspace (fa3_forward_workspace_bytes, 0 when the kernel does not apply).  Other shapes take the
- * regular 16/32-bit path.  The fp8 backward differentiates the function the forward evaluated (attention of the
- * e4m3-round-tripped Q, K; cf. csrc/fa3/fa3_bwd.cu:134-146) and needs fa3_backward_workspace_bytes. */
+ * fp8 != 0 (f16/bf16 tensors, head dims that are multiples of 8 up to 256): Q, K and V go through OCP e4m3 with one
+ * scale per (bh, 64-row block); Q and K are rotated (sign + Hadamard) around the quantisation at power-of-two head dims.
+ * d = 128: QK^T runs on the e4m3 MFMA; for N > 256 (unless option fp8_pv = 1) P.V does too, with P rounded to e4m3 and
+ * V scaled by powers of two; otherwise P stays 16-bit and V has absmax / 448 scales.  Under the causal mask the first
+ * 256 query rows always take the 16-bit P, on the same V~ as the other rows.  Other head dims: the round-tripped Q~, K~,
+ * V~ feed the 16-bit kernels.  Accumulation is fp32 throughout.  The forward needs fa3_forward_workspace_bytes.
+ * fp32 tensors take the regular path.  The fp8 backward differentiates attention of the same Q~, K~, V~ (cf.
+ * csrc/fa3/fa3_bwd.cu:134-146) with P recomputed exactly (straight-through over the e4m3 P) and needs
+ * fa3_backward_workspace_bytes. */
 int fa3_forward(const void* q, const void* k, const void* v, void* o, float* lse,
                 int64_t bh, int64_t n, int64_t d, int dtype,
                 int causal, double softmax_scale, int64_t br, int64_t bc, int64_t stages, int fp8,

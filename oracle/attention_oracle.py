@@ -302,16 +302,19 @@ def fp8_roundtrip(q, k, v, block_q, block_k, rotate: bool = True, quantize_v: bo
 
 
 def fp8_attention(q, k, v, causal, softmax_scale, block_q, block_k, rotate: bool = True, quantize_v: bool = True,
-                  p_e4m3: bool = False):
+                  p_e4m3: bool = False, v_pow2: Optional[bool] = None):
     """Attention with Q, K and V quantised to e4m3 per row block; the numerical model of the HIP `fa3_forward(fp8=True)` path.
     p_e4m3=False: P and the accumulation in fp32 — the path whose P.V product is 16-bit (every head dim but 128, and option
     fp8_pv = 1 there).  p_e4m3=True: the all-e4m3 kernel (d = 128 default): V with a power-of-two block scale and the
     probabilities p = exp(s - rowmax) rounded to e4m3 in the P.V product, the row sum (and lse) from the unrounded p.  (The
     kernel rounds p relative to a running maximum that may lag the true one by up to 2^8, so its roundings differ from these
     element by element; the model has the same error statistics, not the same bits.)
+    v_pow2: V's block scales rounded up to powers of two; None = p_e4m3.  v_pow2=True with p_e4m3=False models the rows the
+    16-bit P.V kernel serves where the all-e4m3 kernel serves the others (the first query tile under the causal mask).
     This is this repo's model of the reference's INTENT (its own fp8 branch models no 8-bit rounding and its rotation is not
-    orthogonal: SURVEY D6, D7) — fp8 parity is not pinned by a reference fixture."""
-    qd, kd, vd = fp8_roundtrip(q, k, v, block_q, block_k, rotate, quantize_v, v_pow2=p_e4m3)
+    orthogonal: SURVEY D6, D7).  It is held to the reference's fixtures at the reference's per-element fp8 bar by
+    tests/test_fp8_model_cpu.py."""
+    qd, kd, vd = fp8_roundtrip(q, k, v, block_q, block_k, rotate, quantize_v, v_pow2=p_e4m3 if v_pow2 is None else v_pow2)
     if not p_e4m3:
         o, lse = exact_attention(qd, kd, vd, causal, softmax_scale)
         return o.to(v.dtype), lse
@@ -326,10 +329,13 @@ def fp8_attention(q, k, v, causal, softmax_scale, block_q, block_k, rotate: bool
     return o.float().to(v.dtype), lse
 
 
-def fp8_attention_backward(q, k, v, dout, causal, softmax_scale, block_q, block_k, rotate: bool = True, quantize_v: bool = True):
+def fp8_attention_backward(q, k, v, dout, causal, softmax_scale, block_q, block_k, rotate: bool = True, quantize_v: bool = True,
+                           v_pow2: bool = False):
     """(dq, dk, dv, o, lse) of the function `fp8_attention` evaluates, taken at the round-tripped tensors and handed to q, k, v
-    themselves (straight-through over the rounding), as the reference's fa3_backward does (csrc/fa3/fa3_bwd.cu:134-146)."""
-    qd, kd, vd = fp8_roundtrip(q, k, v, block_q, block_k, rotate, quantize_v)
+    themselves (straight-through over the rounding), as the reference's fa3_backward does (csrc/fa3/fa3_bwd.cu:134-146).
+    v_pow2: V~ with power-of-two block scales, as the library's backward uses where the all-e4m3 forward kernel ran (d = 128,
+    N > 256, option fp8_pv != 1).  P is exact either way (straight-through over the e4m3 P of that kernel)."""
+    qd, kd, vd = fp8_roundtrip(q, k, v, block_q, block_k, rotate, quantize_v, v_pow2=v_pow2)
     return exact_attention_backward(qd, kd, vd, dout, causal, softmax_scale, math_dtype=torch.float64)
 
 
