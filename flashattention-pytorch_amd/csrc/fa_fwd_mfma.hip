@@ -346,18 +346,46 @@ hipError_t set_trace_buffer(void* p) { return hipMemcpyToSymbol(HIP_SYMBOL(g_tra
 // Staggered ("ping-pong") forward: the DEFAULT at d = 128 with 128-key tiles (1.95 ms against 2.14 for the lock-step kernel
 // above at B8 H32 N4096, bitwise the same results; profiles/r01_tile_sweep.md); also built with 64-key tiles (fwd_stag = 1).  The two waves that share a SIMD run the same program; with
 // one barrier per tile they stay in lock step, so their MFMA phases collide and their softmax (VALU) phases collide, and
-// the tile time is close to the SUM of the two.  Here every 64-key tile is split in two halves separated by barriers,
+// the tile time is close to the SUM of the two.  Here every tile is split in two halves separated by barriers,
 //     M_t = [ O^T += V^T P^T (tile t-1) ; S^T = K Q^T (tile t) ]      matrix pipe
 //     V_t = [ online softmax of tile t, O rescale, pack P ]           vector pipe
 // and waves 4..7 run half a tile behind waves 0..3, so at any time one wave of a SIMD is in M and the other in V.
 // A wave that is alone on the matrix pipe gets no latency cover from its partner, so the M phase is hand timed: LDS
 // operand reads from inline asm three MFMAs ahead (a 4-slot ring, the first slots filled before the barrier), counted
-// lgkmcnt waits fused to each MFMA, P.V and S accumulation chains interleaved.  K and V are triple buffered with the
-// LDS-DMA issued two tiles ahead at even global half-steps g = 2u (K(u+2), V(u+1)) and counted vmcnt waits, so a
-// transfer has four half-steps to land.
+// lgkmcnt waits fused to each MFMA, P.V and S accumulation chains interleaved.
+// 64-key tiles: K and V triple buffered, the LDS-DMA issued two tiles ahead at even global half-steps g = 2u (K(u+2),
+// V(u+1)) with counted vmcnt waits, so a transfer has four half-steps to land.
+// 128-key tiles (KA, the default): K triple and V double buffered, 5 x 32 KiB = the whole 160 KiB of the CU.  Every wave
+// issues 8 DMA pieces from INSIDE its own matrix phase M_u (one piece in the gap after a chosen MFMA, fwdsched::kDmaStep):
+// waves 0..3 the tile V(u), waves 4..7 the tile K(u+2); a wave waits for its pieces (vmcnt(0)) at the barrier that ends its
+// next vector phase.  Global half-step g, wave half s (0: waves 0..3, 1: waves 4..7); M_t of half s runs in g = 2t + s:
+//     tile    buffer   issued by / in      landed + barrier     first read                   last read
+//     K(t)    t % 3    half 1, g = 2t - 3   end of g = 2t - 2    g = 2t - 1 (half 0, ahead     g = 2t + 1 (half 1, M_t)
+//                                                                 of the barrier that starts M_t)
+//     V(t)    t % 2    half 0, g = 2t       end of g = 2t + 1    g = 2t + 2 (half 0, M_{t+1})  g = 2t + 3 (half 1, M_{t+1})
+// (K(0), K(1): the prologue.)  The next writer of K(t)'s buffer, K(t+3), is issued in g = 2t + 3, and that of V(t)'s,
+// V(t+2), in g = 2t + 4: both after the last read and its barrier.  Because V(t) lands only at the barrier that starts
+// M_{t+1}, the steps whose operands are requested ahead of that barrier are S steps (Map, LEAD); the order inside every
+// accumulation chain is the one of the two-buffer form, so the results are bitwise the same.  Tiles past the workgroup's
+// last (the causal tail, the dummy S of the last M phase) are requested at an offset the range check rejects: zeros, no
+// traffic.  The two-buffer form of round 3 (K(u+1), V(u) as one block at the head of every even half-step) stays
+// selectable for the A/B: fwd_stag = 4.
 // W2: one counted operand wait per TWO MFMAs (an even step also waits for the next step's operand, an odd step issues none), as
 // the backward stream kernels do: one instruction less per two steps on an issue port that is 80 % busy (option fwd_w2).
-template <typename Tag, int D, bool CAUSAL, int KB, bool PAD = false, int RD = 4, bool W2 = false>
+namespace fwdsched {
+// tools/gen_fwd_schedule.py (tests/test_fwd_schedule_cpu.py keeps the two in step): a piece goes where the gap's operand
+// request is one ds_read_b128 (an S step) or none, at every ring depth; spread evenly over those gaps
+// generated by tools/gen_fwd_schedule.py: the step at whose head DMA piece p is issued
+constexpr int kDmaStepS[8] = {2, 6, 10, 14, 18, 22, 26, 30};    // M_0: S(0) only, 32 steps
+constexpr int kDmaStepPS[8] = {3, 11, 17, 25, 31, 39, 45, 62};   // M_t: P.V(t-1) ; S(t), 64 steps
+// end of generated table
+constexpr int piece_at(bool pv, int j) {   // DMA piece issued at the head of step j, or -1
+    for (int p = 0; p < 8; ++p)
+        if ((pv ? kDmaStepPS[p] : kDmaStepS[p]) == j) return p;
+    return -1;
+}
+}  // namespace fwdsched
+template <typename Tag, int D, bool CAUSAL, int KB, bool PAD = false, int RD = 4, bool W2 = false, bool KA = false>
 __global__ __launch_bounds__(512, 2) void fwd_mfma_stag_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                                const uint16_t* __restrict__ v, uint16_t* __restrict__ o,
                                                                float* __restrict__ lse, int n, int nqt, float c_log2,
@@ -368,11 +396,14 @@ __global__ __launch_bounds__(512, 2) void fwd_mfma_stag_kernel(const uint16_t* _
     constexpr int BM = 256, BN = 32 * KB, NKS = D / 16, NDV = D / 32;
     constexpr int TILE_BYTES = BN * D * 2;
     // 64-key tiles: K and V triple buffered, DMA two tiles ahead.  128-key tiles (160 KB of LDS do not hold six of them):
-    // double buffered, DMA one tile ahead, which is as much time because the phases are twice as long.
+    // KA: K triple, V double buffered, DMA inside the matrix phases (header comment); otherwise (fwd_stag = 4) both double
+    // buffered, DMA one tile ahead, which is as much time because the phases are twice as long.
+    static_assert(!KA || (KB == 4 && D == 128), "the in-stream DMA schedule is laid out for 128-key tiles at d = 128");
     constexpr int NBUF = KB == 4 ? 2 : 3;
-    extern __shared__ __attribute__((aligned(16))) char smem[];  // [K x NBUF | V x NBUF]: tile t in buffer t % NBUF
+    constexpr int NBK = KA ? 3 : NBUF, NBV = NBUF;
+    extern __shared__ __attribute__((aligned(16))) char smem[];  // [K x NBK | V x NBV]: tile t in buffer t % NBK / t % NBV
     char* Kbuf = smem;
-    char* Vbuf = smem + NBUF * TILE_BYTES;
+    char* Vbuf = smem + NBK * TILE_BYTES;
 
     const int L = xcd_remap(blockIdx.x, gridDim.x);
     const int bh = L / nqt;
@@ -415,6 +446,22 @@ __global__ __launch_bounds__(512, 2) void fwd_mfma_stag_kernel(const uint16_t* _
             dma_stage_tile<D, BN, 8>(v_rs, Vbuf + (u & 1) * TILE_BYTES, u * BN, dma_voff, w, DR);
         }
     };
+    // KA: the tile a wave issues in its matrix phase M_u, V(u) (waves 0..3) or K(u+2) (waves 4..7), four waves per tile:
+    // wave w & 3 takes the pieces (w & 3) + 4 p, p = 0 .. 7 (dma_voff is the same for w and w & 3: RPP * 4 = 16 rows).
+    // Tiles from the workgroup's T-th on are requested at kOobOff: zeros, no traffic (ablation flag 4: every tile).
+    rsrc_s_t dma_rs;
+    unsigned dma_dst = 0;
+    int dma_soff = 0, dma_vo = 0;
+    auto dma_set = [&](int u, int T_) {
+        const int tile = u + 2 * stag;
+        const bool live = tile < T_ && !(dbg & 4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dma_rs[i] = stag ? k_rs[i] : v_rs[i];
+        dma_dst = lds_addr_of(stag ? Kbuf + (tile % 3) * TILE_BYTES : Vbuf + (tile & 1) * TILE_BYTES) + (w & 3) * 1024;
+        dma_soff = __builtin_amdgcn_readfirstlane(live ? (tile * BN + 4 * (w & 3)) * 2 * DR : 0);
+        dma_vo = live ? dma_voff : kOobOff;
+    };
+    auto dma_piece = [&](int p) { dma16_issue(dma_rs, dma_dst + 4096 * p, dma_vo, dma_soff + p * 32 * DR); };
 
     f32x16 oacc[NDV];
 #pragma unroll
@@ -532,16 +579,24 @@ __global__ __launch_bounds__(512, 2) void fwd_mfma_stag_kernel(const uint16_t* _
         // accumulator run at about half rate (tools/ubench/overlap.hip) — so P.V steps (NDV chains) and S steps (KB
         // chains) alternate, and consecutive S steps alternate between the key blocks.
         // step j -> (is_pv, index): P.V index p = (kb, s2, dvb) with dvb fastest; S index i = (ks, kb) with kb fastest.
+        // KA: the first LEAD = RD - 1 steps are S steps (their K operands are requested ahead of the barrier, before which
+        // V(t-1) has not landed), then P.V and S alternate, P.V first; the chains' own orders are unchanged.
+        constexpr int LEAD = (KA && NPV != 0 && NS != 0) ? (RD - 1 < NS ? RD - 1 : NS) : 0;
+        constexpr int M2 = NPV < NS - LEAD ? NPV : NS - LEAD;   // P.V / S pairs after the lead
         struct Map {
-            static constexpr bool is_pv(int j) { return NS == 0 || (NPV != 0 && (j < 2 * (NPV < NS ? NPV : NS) ? (j & 1) == 0 : NPV > NS)); }
+            static constexpr bool is_pv(int j) {
+                return NS == 0 || (NPV != 0 && j >= LEAD && (j - LEAD < 2 * M2 ? ((j - LEAD) & 1) == 0 : NPV > NS - LEAD));
+            }
             static constexpr int idx(int j) {
-                constexpr int m = NPV < NS ? NPV : NS;
-                return (NPV == 0 || NS == 0) ? j : (j < 2 * m ? j / 2 : j - m);
+                if (NPV == 0 || NS == 0 || j < LEAD) return j;
+                const int jj = j - LEAD;
+                if (jj < 2 * M2) return (jj & 1) == 0 ? jj / 2 : LEAD + jj / 2;
+                return NPV > NS - LEAD ? jj - M2 : LEAD + jj - M2;
             }
         };
         // this phase's buffers folded into the lane addresses once; everything else is an immediate offset
         if constexpr (WHICH == 0) {
-            const unsigned vsel = (t % NBUF) * TILE_BYTES, ksel = ((t + (PV ? 1 : 0)) % NBUF) * TILE_BYTES;
+            const unsigned vsel = (t % NBV) * TILE_BYTES, ksel = ((t + (PV ? 1 : 0)) % NBK) * TILE_BYTES;
 #pragma unroll
             for (int ks = 0; ks < NKS; ++ks) kq[ks] = (ka0 + ksel) ^ (32u * ks);
 #pragma unroll
@@ -564,6 +619,10 @@ __global__ __launch_bounds__(512, 2) void fwd_mfma_stag_kernel(const uint16_t* _
         auto step = [&](auto jc) {
             constexpr int j = decltype(jc)::value, x = Map::idx(j);
             fetch(std::integral_constant<int, j + RD - 1>{});
+            if constexpr (KA) {   // this step's LDS-DMA piece, if any (fwdsched::kDmaStep)
+                constexpr int pc = fwdsched::piece_at(PV, j);
+                if constexpr (pc >= 0) dma_piece(pc);
+            }
             __builtin_amdgcn_sched_barrier(0);
             // LDS instructions issued after the operand this step waits for: its own, or (W2, even steps) the next step's;
             // W2's odd steps issue no wait: the even step before them has covered their operand
@@ -620,37 +679,80 @@ __global__ __launch_bounds__(512, 2) void fwd_mfma_stag_kernel(const uint16_t* _
         stamp();
     };
     if ((dbg & 256) && stag) __builtin_amdgcn_s_setprio(1);   // A/B: one static priority for the younger half, no per-phase flips (guide, two waves per SIMD, item 4)
-    dma_stage_tile<D, BN, 8>(k_rs, Kbuf, 0, dma_voff, w, DR);
-    if (NBUF == 3) {
-        dma_stage_tile<D, BN, 8>(k_rs, Kbuf + TILE_BYTES, BN, dma_voff, w, DR);
-        dma_stage_tile<D, BN, 8>(v_rs, Vbuf, 0, dma_voff, w, DR);
+    if constexpr (KA) {
+        // K(0), K(1) by every wave; then the half-steps as in the header comment's table.  A wave waits for its own pieces at
+        // the barrier that ends its vector phase (they were issued in the matrix phase before it); every wave passes the
+        // same 2T + 2 barriers, the causal tail and the idle first half-step of waves 4..7 as feed-only half-steps.
+        auto end_half_ka = [&](bool wait) {
+            stamp();
+            if (wait) dma_wait_all();
+            __syncthreads();
+            stamp();
+        };
+        dma_stage_tile<D, BN, 8>(k_rs, Kbuf, 0, dma_voff, w, DR);
+        if (BN < nk) dma_stage_tile<D, BN, 8>(k_rs, Kbuf + TILE_BYTES, BN, dma_voff, w, DR);
+        dma_wait_all();
+        __syncthreads();
+        int g = 0;
+        if (stag) { end_half_ka(false); g = 1; }              // second half idles through half-step 0
+        dma_set(0, T);
+        do_M(std::false_type{}, std::true_type{}, std::integral_constant<int, 0>{}, 0);
+        do_M(std::false_type{}, std::true_type{}, std::integral_constant<int, 1>{}, 0);         // M_0 = S(0), issues tile 0 / 2
+        end_half_ka(false); ++g;
+        for (int t = 0; t < Tw; ++t) {
+            do_softmax(t);                                    // V_t
+            do_M(std::true_type{}, std::true_type{}, std::integral_constant<int, 0>{}, t);      // S operands of M_{t+1}: K(t+1) landed a half-step ago
+            dma_set(t + 1, T);
+            end_half_ka(true); ++g;
+            do_M(std::true_type{}, std::true_type{}, std::integral_constant<int, 1>{}, t);      // M_{t+1} = P.V(t) ; S(t+1)
+            end_half_ka(false); ++g;
+        }
+        for (; g < 2 * T + 2; ++g) {                          // feed-only half-steps (causal tail)
+            const int l = g - stag;
+            if (!(l & 1)) {
+                dma_set(l >> 1, T);
+#pragma unroll
+                for (int p = 0; p < 8; ++p) dma_piece(p);
+            }
+            end_half_ka(l & 1);
+        }
+    } else {
+        dma_stage_tile<D, BN, 8>(k_rs, Kbuf, 0, dma_voff, w, DR);
+        if (NBUF == 3) {
+            dma_stage_tile<D, BN, 8>(k_rs, Kbuf + TILE_BYTES, BN, dma_voff, w, DR);
+            dma_stage_tile<D, BN, 8>(v_rs, Vbuf, 0, dma_voff, w, DR);
+        }
+        dma_wait_all();
+        __syncthreads();
+        int g = 0;
+        if (stag) { issue(0); end_half(0); g = 1; }               // second half idles through half-step 0
+        if (!(g & 1)) issue(g >> 1);
+        do_M(std::false_type{}, std::true_type{}, std::integral_constant<int, 0>{}, 0);
+        do_M(std::false_type{}, std::true_type{}, std::integral_constant<int, 1>{}, 0);             // M_0 = S(0)
+        end_half(g); ++g;
+        for (int t = 0; t < Tw; ++t) {
+            if (!(g & 1)) issue(g >> 1);
+            do_softmax(t);                                        // V_t
+            // first operands of M_{t+1} ahead of the barrier — with three buffers both tiles landed a step ago; with two the
+            // tiles are only guaranteed after this barrier, so the requests follow it
+            if (NBUF == 3) do_M(std::true_type{}, std::true_type{}, std::integral_constant<int, 0>{}, t);
+            end_half(g); ++g;
+            if (!(g & 1)) issue(g >> 1);
+            if (NBUF != 3) do_M(std::true_type{}, std::true_type{}, std::integral_constant<int, 0>{}, t);
+            do_M(std::true_type{}, std::true_type{}, std::integral_constant<int, 1>{}, t);          // M_{t+1} = P.V(t) ; S(t+1)  (after the last tile S is unused:
+                                                                  // one code path keeps the accumulators in place)
+            end_half(g); ++g;
+        }
+        for (; g < 2 * T + 2; ++g) {                              // feed-only half-steps (causal tail, idle half)
+            if (!(g & 1)) issue(g >> 1);
+            end_half(g);
+        }
     }
+    // nothing of this workgroup may still be writing LDS when the epilogue stages O in the K buffers (or the next workgroup
+    // takes the CU): every wave waits for its own DMA, the barrier for everybody's (the last pieces of waves 4..7 and, with
+    // 64-key tiles, the last issue are still in flight after the last half-step's barrier)
     dma_wait_all();
-    __syncthreads();
-    int g = 0;
-    if (stag) { issue(0); end_half(0); g = 1; }               // second half idles through half-step 0
-    if (!(g & 1)) issue(g >> 1);
-    do_M(std::false_type{}, std::true_type{}, std::integral_constant<int, 0>{}, 0);
-    do_M(std::false_type{}, std::true_type{}, std::integral_constant<int, 1>{}, 0);             // M_0 = S(0)
-    end_half(g); ++g;
-    for (int t = 0; t < Tw; ++t) {
-        if (!(g & 1)) issue(g >> 1);
-        do_softmax(t);                                        // V_t
-        // first operands of M_{t+1} ahead of the barrier — with three buffers both tiles landed a step ago; with two the
-        // tiles are only guaranteed after this barrier, so the requests follow it
-        if (NBUF == 3) do_M(std::true_type{}, std::true_type{}, std::integral_constant<int, 0>{}, t);
-        end_half(g); ++g;
-        if (!(g & 1)) issue(g >> 1);
-        if (NBUF != 3) do_M(std::true_type{}, std::true_type{}, std::integral_constant<int, 0>{}, t);
-        do_M(std::true_type{}, std::true_type{}, std::integral_constant<int, 1>{}, t);          // M_{t+1} = P.V(t) ; S(t+1)  (after the last tile S is unused:
-                                                              // one code path keeps the accumulators in place)
-        end_half(g); ++g;
-    }
-    for (; g < 2 * T + 2; ++g) {                              // feed-only half-steps (causal tail, idle half)
-        if (!(g & 1)) issue(g >> 1);
-        end_half(g);
-    }
-    dma_wait_all();   // nothing of this workgroup may still be writing LDS when the next one takes the CU
+    if (KA || NBUF == 3) __syncthreads();
     if (tron && lane == 0) trace[(w >> 2) * 2048] = tri;
 
     // ---- epilogue.  Every wave is past the last barrier and nothing writes LDS any more: the K / V buffers are dead and each
@@ -712,10 +814,13 @@ static hipError_t launch_fwd_t(const FwdArgs& a, hipStream_t st, bool want_stag 
                            (const uint16_t*)a.v, (uint16_t*)a.o, a.lse, (int)a.n, nqt, c, a.scale, last_arg);
         return hipGetLastError();
     };
-    // staggered schedule (fwd_mfma_stag_kernel): d = 128, 64-key tiles (three buffers each) or 128-key tiles (two)
+    // staggered schedule (fwd_mfma_stag_kernel): d = 128, 64-key tiles (three buffers each) or 128-key tiles (K three, V two;
+    // fwd_stag = 4: two each, the round-3 schedule)
     if constexpr ((D == 128 || D == 64) && (KB == 2 || KB == 4)) {
         if (want_stag) {
-            smem = (size_t)2 * (KB == 4 ? 2 : 3) * (32 * KB) * D * 2;
+            constexpr bool ka_ok = D == 128 && KB == 4;
+            const bool ka = ka_ok && option(OPT_FWD_STAG) != 4;
+            smem = (size_t)(ka ? 5 : 2 * (KB == 4 ? 2 : 3)) * (32 * KB) * D * 2;
             last_arg = (int)a.d | ((option(OPT_FWD_STAG) != 0 ? option(OPT_FWD_ABL) : 0) << 16);   // debug flags only with an explicit fwd_stag
             auto launch_s = [&](auto kern) -> hipError_t {
                 hipError_t e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
@@ -724,11 +829,16 @@ static hipError_t launch_fwd_t(const FwdArgs& a, hipStream_t st, bool want_stag 
                                    (const uint16_t*)a.v, (uint16_t*)a.o, a.lse, (int)a.n, nqt, c, a.scale, last_arg, (int)(a.nk > 0 ? a.nk : a.n));
                 return hipGetLastError();
             };
-            if constexpr (D == 128 && KB == 4 && !PAD) {   // operand ring depth (option fwd_rd: 4, 6, 8; 0 = default)
-                const int rd = option(OPT_FWD_RD);
-                if (option(OPT_FWD_W2) == 1) return a.causal ? launch_s(fwd_mfma_stag_kernel<Tag, D, true, KB, PAD, 6, true>) : launch_s(fwd_mfma_stag_kernel<Tag, D, false, KB, PAD, 6, true>);
-                if (rd == 6) return a.causal ? launch_s(fwd_mfma_stag_kernel<Tag, D, true, KB, PAD, 6>) : launch_s(fwd_mfma_stag_kernel<Tag, D, false, KB, PAD, 6>);
-                if (rd == 8) return a.causal ? launch_s(fwd_mfma_stag_kernel<Tag, D, true, KB, PAD, 8>) : launch_s(fwd_mfma_stag_kernel<Tag, D, false, KB, PAD, 8>);
+            if constexpr (ka_ok) {
+                if (ka) {
+                    if constexpr (!PAD) {   // operand ring depth (option fwd_rd: 4, 6, 8; 0 = default)
+                        const int rd = option(OPT_FWD_RD);
+                        if (option(OPT_FWD_W2) == 1) return a.causal ? launch_s(fwd_mfma_stag_kernel<Tag, D, true, KB, PAD, 6, true, true>) : launch_s(fwd_mfma_stag_kernel<Tag, D, false, KB, PAD, 6, true, true>);
+                        if (rd == 6) return a.causal ? launch_s(fwd_mfma_stag_kernel<Tag, D, true, KB, PAD, 6, false, true>) : launch_s(fwd_mfma_stag_kernel<Tag, D, false, KB, PAD, 6, false, true>);
+                        if (rd == 8) return a.causal ? launch_s(fwd_mfma_stag_kernel<Tag, D, true, KB, PAD, 8, false, true>) : launch_s(fwd_mfma_stag_kernel<Tag, D, false, KB, PAD, 8, false, true>);
+                    }
+                    return a.causal ? launch_s(fwd_mfma_stag_kernel<Tag, D, true, KB, PAD, 4, false, true>) : launch_s(fwd_mfma_stag_kernel<Tag, D, false, KB, PAD, 4, false, true>);
+                }
             }
             return a.causal ? launch_s(fwd_mfma_stag_kernel<Tag, D, true, KB, PAD>) : launch_s(fwd_mfma_stag_kernel<Tag, D, false, KB, PAD>);
         }
@@ -811,15 +921,17 @@ static hipError_t launch_fwd_kb(const FwdArgs& a, hipStream_t st) {
     const int kb = fwd_kb_override();
     // Schedule at d = 128: the staggered kernel with 128-key tiles is the default (-9 % non-causal, -2 ... -10 % causal
     // against lock step, profiles/r01_tile_sweep.md; bitwise the same results, it performs the same operations in the
-    // same order).  Option fwd_stag: 1 = staggered with 64-key tiles, 2 = lock step, 3 = staggered with 128-key tiles.
+    // same order).  Option fwd_stag: 1 = staggered with 64-key tiles, 2 = lock step, 3 = staggered with 128-key tiles,
+    // 4 = as the default, with the round-3 two-buffer schedule of the staggered kernel (A/B).
     const int so = option(OPT_FWD_STAG);
+    const bool so_default = so == 0 || so == 4;
     const bool other_sweep = kb || option(OPT_FWD_RS) || option(OPT_FWD_EAGER) || option(OPT_FWD_HS) || option(OPT_FWD_TPW) || option(OPT_FWD_ABL);
     // Under the causal mask the staggered kernel (one tile per workgroup, heaviest first) pays only on long rows: the lock-step
     // kernel with its heavy + light tile pairs is ahead by 15 - 27 % at N = 1024, 5 - 25 % at N = 2048, 3 - 10 % at N = 4096 below
     // about 3000 row tiles, and behind by 3 - 6 % from there on (256 x 4096, N >= 8192: profiles/r02_small_launches.md §5).
     // Without the mask the two are level at N = 1024 and the lock-step kernel is 8 - 10 % ahead at N = 512.
     const bool short_rows = a.causal ? !(a.n >= 8192 || (a.n >= 4096 && a.bh * ((a.n + 255) / 256) >= 3072)) : a.n < 1024;
-    if ((D == 128 && (so == 3 || (so == 0 && !other_sweep && !short_rows))) || (D == 64 && so == 3)) return launch_fwd_t<Tag, D, 4>(a, st, true);
+    if ((D == 128 && (so == 3 || (so_default && !other_sweep && !short_rows))) || (D == 64 && so == 3)) return launch_fwd_t<Tag, D, 4>(a, st, true);
     const bool stag = D == 128 && so == 1;
     if (stag) return launch_fwd_t<Tag, D, 2>(a, st, true);
     if (kb == 1 && D == 128) return launch_fwd_t<Tag, D, (D == 128 ? 1 : 2)>(a, st);
