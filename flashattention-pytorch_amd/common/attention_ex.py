@@ -6,7 +6,9 @@ extended entry points (`fa_ex_forward` / `fa_ex_backward`, include/fa_mi355x.h):
     flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, block_size=128,
                        causal=False, dropout_p=0.0, seed=0, softmax_scale=None) -> o
 
-q: (B, H, Nq, d) or (BH, Nq, d); k, v: (..., Nk, d).  `mask` follows the model's convention — a boolean / 0-1 tensor
+q: (B, H, Nq, d) or (BH, Nq, d); k, v: (B, H_kv, Nk, d) or (B*H_kv, Nk, d).  H_kv < H is grouped-query attention (GQA; H_kv = 1:
+multi-query attention) with H % H_kv == 0: query head h reads K/V head h // (H / H_kv), with no copy of K and V, and the
+gradients of k and v come back in k's and v's shape, summed over each group by the library.  `mask` follows the model's convention — a boolean / 0-1 tensor
 broadcastable to (B, H, Nq, Nk), True / 1 = allowed (`look_ahead_mask_` builds the causal one for Nq != Nk, :176-190;
 `causal=True` is the same mask without materialising it) — and `block_sparse_mask[i, j] == 0` skips tile (i, j) of
 `block_size` x `block_size` (Algorithm 5).  Differentiable (autograd Function; the backward recomputes P and regenerates
@@ -78,8 +80,12 @@ def flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, bloc
     four_d = q.dim() == 4
     if four_d:
         b, h, nq, d = q.shape
-        nk = k.shape[2]
-        q3, k3, v3 = q.reshape(b * h, nq, d), k.reshape(b * h, nk, d), v.reshape(b * h, nk, d)
+        if k.dim() != 4 or k.shape[0] != b or v.shape != k.shape:
+            raise RuntimeError(f"k and v must be (B, H_kv, Nk, d) with q's B; got {tuple(k.shape)}, {tuple(v.shape)}")
+        hkv, nk = k.shape[1], k.shape[2]
+        if hkv == 0 or h % hkv != 0:
+            raise RuntimeError(f"the query heads ({h}) must be a multiple of the K/V heads ({hkv})")
+        q3, k3, v3 = q.reshape(b * h, nq, d), k.reshape(b * hkv, nk, d), v.reshape(b * hkv, nk, d)
     else:
         q3, k3, v3 = q, k, v
         (_, nq, d), nk = q.shape, k.shape[1]

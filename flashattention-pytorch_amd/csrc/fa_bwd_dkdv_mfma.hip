@@ -23,7 +23,7 @@ __global__ __launch_bounds__((D == 256 || W4) ? 256 : 512, D == 256 ? 1 : 2) voi
                                                                const float* __restrict__ nlse,
                                                                const float* __restrict__ ndelta, uint16_t* __restrict__ dk,
                                                                uint16_t* __restrict__ dv, int n, int nkt, float c_log2,
-                                                               float scale, int dr) {
+                                                               float scale, int dr, unsigned kvg /* kv_magic(query heads per K/V head) */) {
     // D = 256: 4 waves (one per SIMD, 512 registers: dK^T and dV^T alone are 256), 128 keys, query tiles of 32 rows
     // W4 (d <= 128): 4 waves = 128 keys per workgroup for launches too small to fill the CUs with 256-key tiles
     constexpr int NW = (D == 256 || W4) ? 4 : 8, BK = 32 * NW, BQ = D == 256 ? 32 : 64, NKS = D / 16, NDB = D / 32;
@@ -53,12 +53,13 @@ __global__ __launch_bounds__((D == 256 || W4) ? 256 : 512, D == 256 ? 1 : 2) voi
     const size_t base = (size_t)bh * n * DR;
     const size_t rbase = (size_t)bh * n;
 
-    const rsrc_s_t k_rs = make_rsrc_s(k + base, (unsigned)n * DR * 2);
+    const size_t kvbase = (size_t)kv_unit(bh, kvg) * n * DR;   // K / V rows (dK / dV: per query head, at base)
+    const rsrc_s_t k_rs = make_rsrc_s(k + kvbase, (unsigned)n * DR * 2);
     const rsrc_s_t q_rs = make_rsrc_s(q + base, (unsigned)n * DR * 2);
     const rsrc_s_t o_rs = make_rsrc_s(dout + base, (unsigned)n * DR * 2);
     const rsrc_s_t l_rs = make_rsrc_s(nlse + rbase, (unsigned)n * 4);
     const rsrc_s_t d_rs = make_rsrc_s(ndelta + rbase, (unsigned)n * 4);
-    const buf_rsrc_t v_rs = make_rsrc(v + base, (unsigned)n * DR * 2);
+    const buf_rsrc_t v_rs = make_rsrc(v + kvbase, (unsigned)n * DR * 2);
     const int dma_voff = dma_lane_voff<D>(lane, w, DR);
     const int dma_voff_b = D == 256 ? dma_lane_voff<D>(lane, w + NW, DR) : 0;
 
@@ -82,7 +83,7 @@ __global__ __launch_bounds__((D == 256 || W4) ? 256 : 512, D == 256 ? 1 : 2) voi
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) vf[ks] = buf_load_frag(v_rs, frag_off(key_, 16 * ks + 8 * h, DR, PAD));
         if (KREG) {
-            const buf_rsrc_t kk_rs = make_rsrc(k + base, (unsigned)n * DR * 2);
+            const buf_rsrc_t kk_rs = make_rsrc(k + kvbase, (unsigned)n * DR * 2);
 #pragma unroll
             for (int ks = 0; ks < NKS; ++ks) kfr[ks] = buf_load_frag(kk_rs, frag_off(key_, 16 * ks + 8 * h, DR, PAD));
         }
@@ -281,7 +282,7 @@ static hipError_t launch_dkdv_t(const BwdArgs& a, const float* nlse, const float
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kern, grid, dim3(64 * NW), smem, st, (const uint16_t*)a.q, (const uint16_t*)a.k,
                            (const uint16_t*)a.v, (const uint16_t*)a.dout, nlse, ndelta, (uint16_t*)a.dk, (uint16_t*)a.dv,
-                           (int)a.n, nkt, c, a.scale, (int)a.d);
+                           (int)a.n, nkt, c, a.scale, (int)a.d, kv_magic(a.kv_group));
         return hipGetLastError();
     };
     if constexpr (D == 64 && !PAD && !W4) {

@@ -235,7 +235,8 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv_w4_kernel(const uint16_t* __r
                                                              const float* __restrict__ ndelta, uint16_t* __restrict__ dk,
                                                              uint16_t* __restrict__ dv, int n, int nkt, float c_log2,
                                                              float scale, int nk /* keys; n = query rows; causal: nk >= n, diagonal at key = row + nk - n */,
-                                                             uint16_t* __restrict__ ds = nullptr, int nqb = 0, int nkb32 = 0 /* DS: tile grid of the dS workspace */) {
+                                                             uint16_t* __restrict__ ds = nullptr, int nqb = 0, int nkb32 = 0 /* DS: tile grid of the dS workspace */,
+                                                             unsigned kvg = 0 /* kv_magic(query heads per K/V head) */) {
     constexpr int D = 128, NKS = 8, NDB = 4, BK = 256, BQ = 32, NBUF = 4, K1R = KR == 3 ? 8 : (KR == 2 ? 4 : 0), RS = KR == 3 ? 8 : (KR == 2 ? 12 : (KR ? 10 : 16));
     // operand groups requested ahead of use (6 MFMAs).  4 live groups x 3 fragments = 12 ring slots; with 16 a request
     // never lands on a fragment the two MFMAs just issued are still reading (hipcc would pad that hazard with an s_nop)
@@ -261,18 +262,19 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv_w4_kernel(const uint16_t* __r
     };
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
-    const size_t base = (size_t)bh * n * D, kvbase = (size_t)bh * nk * D;   // q / dO rows; k / v / dk / dv rows
+    const size_t base = (size_t)bh * n * D, kvbase = (size_t)bh * nk * D;   // q / dO rows; dk / dv rows (per query head)
+    const size_t kvread = (size_t)kv_unit(bh, kvg) * nk * D;                   // k / v rows: the K/V unit of the group
     const size_t rbase = (size_t)bh * n;
     const int coff = nk - n;
     int key0 = 0, kw0 = 0;                       // first key of the current tile / of this wave in it
 
-    const rsrc_s_t k_rs = make_rsrc_s(k + kvbase, (unsigned)nk * D * 2);
+    const rsrc_s_t k_rs = make_rsrc_s(k + kvread, (unsigned)nk * D * 2);
     const rsrc_s_t q_rs = make_rsrc_s(q + base, (unsigned)n * D * 2);
     const rsrc_s_t o_rs = make_rsrc_s(dout + base, (unsigned)n * D * 2);
     const rsrc_s_t l_rs = make_rsrc_s(nlse + rbase, (unsigned)n * 4);
     const rsrc_s_t d_rs = make_rsrc_s(ndelta + rbase, (unsigned)n * 4);
     const rsrc_s_t lr_rs = (w & 1) ? d_rs : l_rs;   // this wave's row-constant source (wave-uniform select)
-    const buf_rsrc_t v_rs = make_rsrc(v + kvbase, (unsigned)nk * D * 2);
+    const buf_rsrc_t v_rs = make_rsrc(v + kvread, (unsigned)nk * D * 2);
     const int dma_voff = dma_lane_voff<D>(lane, w, D);
 
     int qs_first = 0, nblk = 0;                  // first query of the current tile's sweep, 32-query blocks in it
@@ -677,7 +679,7 @@ static hipError_t launch_dkdv_w4_t(const BwdArgs& a, const float* nlse, const fl
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kern, grid, dim3(256), smem, st, (const uint16_t*)a.q, (const uint16_t*)a.k, (const uint16_t*)a.v,
                            (const uint16_t*)a.dout, nlse, ndelta, (uint16_t*)a.dk, (uint16_t*)a.dv, (int)a.n, nkt, c, a.scale, (int)nk,
-                           (uint16_t*)ds, ds_tile_rows(a.n), ds_tile_cols(nk));
+                           (uint16_t*)ds, ds_tile_rows(a.n), ds_tile_cols(nk), kv_magic(a.kv_group));
         return hipGetLastError();
     };
     // K rows in registers: the kernels keep ALL of the wave's K fragments there (KR = 3: 250 - 256 VGPRs, no scratch;

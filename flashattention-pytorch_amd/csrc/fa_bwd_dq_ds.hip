@@ -33,7 +33,7 @@ namespace fa {
 template <typename Tag, bool CAUSAL, int NW>
 __global__ __launch_bounds__(64 * NW, 1) void bwd_dq_ds_kernel(const uint16_t* __restrict__ k, const uint16_t* __restrict__ ds,
                                                            uint16_t* __restrict__ dq, int n, int nk, int nqt, int nqb, int nkb32,
-                                                           float scale) {
+                                                           float scale, unsigned kvg /* kv_magic(query heads per K/V head) */) {
     constexpr int D = 128, NDB = 4, BM = 64 * NW, SK = 32, NBUF = NW == 8 ? 3 : 6, AHEAD = NBUF - 1;
     constexpr int K_BYTES = SK * D * 2;             // 8 KiB: the stage's K rows
     constexpr int DS_W = 2 * 2048;                  // 4 KiB: a wave's two dS tiles of the stage
@@ -53,7 +53,7 @@ __global__ __launch_bounds__(64 * NW, 1) void bwd_dq_ds_kernel(const uint16_t* _
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
     const int coff = nk - n;
-    const size_t kvbase = (size_t)bh * nk * D, base = (size_t)bh * n * D;
+    const size_t kvbase = (size_t)kv_unit(bh, kvg) * nk * D, base = (size_t)bh * n * D;
     const rsrc_s_t k_rs = make_rsrc_s(k + kvbase, (unsigned)nk * D * 2);
     const int k_voff = dma_lane_voff<D>(lane, w, D);
     // dS tile, LDS chunk p = 64 i + lane of piece i holds [r >> 2][s][r & 3][h]: r = 16 i + 4 (lane >> 4) + ((lane >> 1) & 3),
@@ -186,7 +186,7 @@ static hipError_t launch_dq_ds_t(const BwdArgs& a, const void* ds, hipStream_t s
         hipError_t e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kern, grid, dim3(64 * nw), smem, st, (const uint16_t*)a.k, (const uint16_t*)ds, (uint16_t*)a.dq, (int)a.n, (int)nk,
-                           nqt, ds_tile_rows(a.n), ds_tile_cols(nk), a.scale);
+                           nqt, ds_tile_rows(a.n), ds_tile_cols(nk), a.scale, kv_magic(a.kv_group));
         return hipGetLastError();
     };
     if (nw == 4) return a.causal ? launch(bwd_dq_ds_kernel<Tag, true, 4>) : launch(bwd_dq_ds_kernel<Tag, false, 4>);

@@ -27,7 +27,7 @@ __global__ __launch_bounds__((D == 256 || W4) ? 256 : 512, D == 256 ? 1 : 2) voi
                                                              const uint16_t* __restrict__ o, const float* __restrict__ lse,
                                                              float* __restrict__ nlse, float* __restrict__ ndelta,
                                                              uint16_t* __restrict__ dq, int n, int nqt, float c_log2,
-                                                             float scale, int dr) {
+                                                             float scale, int dr, unsigned kvg /* kv_magic(query heads per K/V head) */) {
     const int DR = PAD ? dr : D;   // elements per tensor row (PAD: head dims below the tile width, fa_common.h)
     // D = 256: 4 waves, one per SIMD, with the whole 512-register file each (Q, dO fragments 128 + dQ^T 128 registers)
     // W4 (d <= 128): the same 4-wave shape but TWO workgroups per CU — the two waves of a SIMD then belong to different
@@ -91,8 +91,9 @@ __global__ __launch_bounds__((D == 256 || W4) ? 256 : 512, D == 256 ? 1 : 2) voi
     load_rows(tile_of(0));
 
     // K / V tiles arrive by LDS-DMA (no staging registers); rows >= n read as zero
-    const rsrc_s_t k_rs = make_rsrc_s(k + base, (unsigned)n * DR * 2);
-    const rsrc_s_t v_rs = make_rsrc_s(v + base, (unsigned)n * DR * 2);
+    const size_t kvbase = (size_t)kv_unit(bh, kvg) * n * DR;
+    const rsrc_s_t k_rs = make_rsrc_s(k + kvbase, (unsigned)n * DR * 2);
+    const rsrc_s_t v_rs = make_rsrc_s(v + kvbase, (unsigned)n * DR * 2);
     const int dma_voff = dma_lane_voff<D>(lane, w, DR);
     const int dma_voff_b = D == 256 ? dma_lane_voff<D>(lane, w + NW, DR) : 0;
     auto stage = [&](int buf, int k0) {
@@ -243,7 +244,7 @@ static hipError_t launch_dq_kt(const BwdArgs& a, float* nlse, float* ndelta, hip
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kern, grid, dim3(64 * NW), smem, st, (const uint16_t*)a.q, (const uint16_t*)a.k,
                            (const uint16_t*)a.v, (const uint16_t*)a.dout, (const uint16_t*)a.o, a.lse, nlse, ndelta, (uint16_t*)a.dq, (int)a.n, nqt, c,
-                           a.scale, (int)a.d);
+                           a.scale, (int)a.d, kv_magic(a.kv_group));
         return hipGetLastError();
     };
     auto pick = [&](auto nlf) -> hipError_t {

@@ -187,7 +187,8 @@ __global__ __launch_bounds__(256, 1) void bwd_dq_w4_kernel(const uint16_t* __res
                                                            const uint16_t* __restrict__ o, const float* __restrict__ lse,
                                                            float* __restrict__ nlse, float* __restrict__ ndelta,
                                                            uint16_t* __restrict__ dq, int n, int nqt, float c_log2,
-                                                           float scale, int nk /* keys; n = query rows; causal: nk >= n, diagonal at key = row + nk - n */) {
+                                                           float scale, int nk /* keys; n = query rows; causal: nk >= n, diagonal at key = row + nk - n */,
+                                                           unsigned kvg /* kv_magic(query heads per K/V head) */) {
     constexpr int D = 128, NKS = 8, NDB = 4, BM = 256, BN = 64, NBUF = 4, RS = 8, AHEAD = 3;
     constexpr int KT = BN * D * 2;               // 16 KiB: the K rows of a tile (the V rows follow)
     constexpr int BUF = 2 * KT;                  // K | V
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(256, 1) void bwd_dq_w4_kernel(const uint16_t* __res
         if (CAUSAL ? (i == 0 || grp < nqt - 1 - grp) : (tile_of(i) < nqt)) ntile_wg = i + 1;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
-    const size_t base = (size_t)bh * n * D, kbase = (size_t)bh * nk * D;
+    const size_t base = (size_t)bh * n * D, kbase = (size_t)kv_unit(bh, kvg) * nk * D;
     const int coff = nk - n;
 
     const buf_rsrc_t q_rs = make_rsrc(q + base, (unsigned)n * D * 2);
@@ -548,7 +549,7 @@ static hipError_t launch_dq_w4_t(const BwdArgs& a, float* nlse, float* ndelta, h
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kern, grid, dim3(256), smem, st, (const uint16_t*)a.q, (const uint16_t*)a.k, (const uint16_t*)a.v,
                            (const uint16_t*)a.dout, (const uint16_t*)a.o, a.lse, nlse, ndelta, (uint16_t*)a.dq, (int)a.n, nqt, c,
-                           a.scale, (int)(a.nk > 0 ? a.nk : a.n));
+                           a.scale, (int)(a.nk > 0 ? a.nk : a.n), kv_magic(a.kv_group));
         return hipGetLastError();
     };
     if constexpr (std::is_same<Tag, bf16_tag>::value) {

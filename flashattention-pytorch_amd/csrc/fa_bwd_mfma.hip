@@ -363,14 +363,17 @@ static size_t ds_chunk_bytes() {
     const int mb = option(OPT_DS_CHUNK_MB);
     return mb > 0 ? (size_t)mb << 20 : (size_t)4 << 30;
 }
-static int64_t ds_chunk_units(int64_t bh, int64_t n, int64_t nk = 0) {
+// Grouped (g = kv_group > 1): a chunk is made of whole groups, so that its K/V units start at (b0 / g): the step is rounded down
+// to a multiple of g, and is at least g.
+static int64_t ds_chunk_units(int64_t bh, int64_t n, int64_t nk = 0, int64_t g = 1) {
     const int64_t fit = (int64_t)(ds_chunk_bytes() / ds_workspace_bytes(1, n, nk > 0 ? nk : n));
     if (fit >= bh) return bh;
     if (fit < 1) return 0;
     const int64_t nch = (bh + fit - 1) / fit;
-    return (bh + nch - 1) / nch;   // equal chunks: a short last one would leave CUs idle
+    const int64_t step = (bh + nch - 1) / nch;   // equal chunks: a short last one would leave CUs idle
+    return g > 1 ? (step < g ? g : step - step % g) : step;
 }
-static bool bwd_ds_path(int dtype, int64_t d, int64_t bh, int64_t n, bool causal, bool atomic_variant, int64_t nk = 0) {
+static bool bwd_ds_path(int dtype, int64_t d, int64_t bh, int64_t n, bool causal, bool atomic_variant, int64_t nk = 0, int64_t g = 1) {
     const int dq_opt = option(OPT_DQ), dkdv_opt = option(OPT_DKDV);
     if (atomic_variant || !bwd_dkdv_w4_supported(dtype, d)) return false;
     // a kernel pinned by option (A/B runs of one pass against another) keeps the other pass as it was: only dq = 6 asks for this path
@@ -385,7 +388,7 @@ static bool bwd_ds_path(int dtype, int64_t d, int64_t bh, int64_t n, bool causal
     // 2 500 cycles longer then).  Under the causal mask: rows of 4096 and more always (4 - 9 %), shorter rows from 160 row tiles
     // on (below, the 8-wave / 4-wave dK/dV kernels with 128-key tiles serve the launch better: 64 x 512: 0.063 against 0.079 ms),
     // and while a chunk holds 16 (b,h) units or the whole launch (N = 16384 x 32 units: 8 per chunk, -1 %).
-    if (causal) return (n >= 4096 || bh * ((n + 255) / 256) >= 160) && ds_chunk_units(bh, n, nk) >= (bh < 16 ? bh : 16);
+    if (causal) return (n >= 4096 || bh * ((n + 255) / 256) >= 160) && ds_chunk_units(bh, n, nk, g) >= (bh < 16 ? bh : 16);
     return true;
 }
 size_t bwd_mfma_workspace_bytes(int64_t bh, int64_t n, int64_t d, bool atomic_variant) {
@@ -393,9 +396,9 @@ size_t bwd_mfma_workspace_bytes(int64_t bh, int64_t n, int64_t d, bool atomic_va
 }
 // what the dS hand-over wants on top of that (0 where it does not serve the call): a call whose workspace is smaller runs
 // the recomputing dQ pass instead
-size_t bwd_ds_extra_bytes(int64_t bh, int64_t n, int64_t d, int dtype, bool causal, bool atomic_variant, int64_t nk) {
+size_t bwd_ds_extra_bytes(int64_t bh, int64_t n, int64_t d, int dtype, bool causal, bool atomic_variant, int64_t nk, int64_t kv_group) {
     const int64_t nkk = nk > 0 ? nk : n;
-    return bwd_ds_path(dtype, d, bh, n, causal, atomic_variant, nkk) ? ds_workspace_bytes(ds_chunk_units(bh, n, nkk), n, nkk) : 0;
+    return bwd_ds_path(dtype, d, bh, n, causal, atomic_variant, nkk, kv_group) ? ds_workspace_bytes(ds_chunk_units(bh, n, nkk, kv_group), n, nkk) : 0;
 }
 
 // The hand-over itself: row constants, then per chunk of (b,h) units dK/dV (stores dS) and dQ = scale * dS K.  `a.nk` keys
@@ -412,13 +415,14 @@ static hipError_t run_handover_t(const BwdArgs& a, float* nlse, float* ndelta, v
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const int64_t step = ds_chunk_units(a.bh, a.n, nk);
+    const int64_t step = ds_chunk_units(a.bh, a.n, nk, a.kv_group);   // grouped: whole groups per chunk
     for (int64_t b0 = 0; b0 < a.bh; b0 += step) {
         BwdArgs c = a;
         c.bh = a.bh - b0 < step ? a.bh - b0 : step;
-        const size_t qo = (size_t)b0 * a.n * a.d * 2, ko = (size_t)b0 * nk * a.d * 2;   // query-side / key-side tensors
+        // query-side tensors and the dK / dV outputs (per query head when grouped) / K and V (per K/V unit)
+        const size_t qo = (size_t)b0 * a.n * a.d * 2, ko = (size_t)b0 * nk * a.d * 2, kvo = (size_t)(b0 / a.kv_group) * nk * a.d * 2;
         c.q = (const char*)a.q + qo; c.dout = (const char*)a.dout + qo; c.dq = (char*)a.dq + qo;
-        c.k = (const char*)a.k + ko; c.v = (const char*)a.v + ko; c.dk = (char*)a.dk + ko; c.dv = (char*)a.dv + ko;
+        c.k = (const char*)a.k + kvo; c.v = (const char*)a.v + kvo; c.dk = (char*)a.dk + ko; c.dv = (char*)a.dv + ko;
         if ((e = launch_bwd_dkdv_w4(c, nlse + b0 * a.n, ndelta + b0 * a.n, st, ds)) != hipSuccess) return e;
         if ((e = launch_bwd_dq_ds(c, ds, st)) != hipSuccess) return e;
     }
@@ -437,7 +441,7 @@ static hipError_t launch_bwd_t(const BwdArgs& a, hipStream_t st) {
     float* nlse = reinterpret_cast<float*>(a.workspace);
     float* ndelta = nlse + rows;
     float* dq_acc = reinterpret_cast<float*>(reinterpret_cast<char*>(a.workspace) + row_constants_bytes(a.bh, a.n));
-    const bool fused = a.fused_dq != 0 && !pad;
+    const bool fused = a.fused_dq != 0 && !pad && a.kv_group == 1;
     if (fused && a.workspace_bytes < bwd_mfma_workspace_bytes(a.bh, a.n, a.d, true)) return hipErrorInvalidValue;
     hipError_t e = hipSuccess;
     if (fused) {
@@ -448,8 +452,8 @@ static hipError_t launch_bwd_t(const BwdArgs& a, hipStream_t st) {
     // ndelta = -rowsum(dO * O) on its way (it holds every query row's dO in registers), the dK/dV kernel reads them.
     // d <= 64: a preparation launch makes them (fa_bwd_dq_mfma.hip, PREP).  FA_DKDV=4 selects the 4-wave dK/dV kernel.
     const int dkdv_env = option(OPT_DKDV);
-    const bool split = pad || (!fused && dkdv_env != 4);
-    const size_t ds_extra = pad ? 0 : bwd_ds_extra_bytes(a.bh, a.n, a.d, a.dtype, a.causal != 0, a.fused_dq != 0);
+    const bool split = pad || (!fused && (dkdv_env != 4 || a.kv_group > 1));   // (grouped: the split kernels take the K/V unit)
+    const size_t ds_extra = pad ? 0 : bwd_ds_extra_bytes(a.bh, a.n, a.d, a.dtype, a.causal != 0, fused, 0, a.kv_group);
     if (ds_extra && option(OPT_DQ) == 6 && a.workspace_bytes < bwd_mfma_workspace_bytes(a.bh, a.n, a.d, false) + ds_extra)
         return hipErrorInvalidValue;   // asked for by option: fail rather than fall back
     if (ds_extra && a.workspace_bytes >= bwd_mfma_workspace_bytes(a.bh, a.n, a.d, false) + ds_extra) {

@@ -30,7 +30,7 @@ std::vector<ProfRec> g_prof_recs;
 std::vector<hipEvent_t> g_prof_free;
 hipEvent_t g_prof_open[fa::K_COUNT];
 const char* const kKernelNames[fa::K_COUNT] = {"fwd_f32", "bwd_delta", "bwd_dkdv_f32", "bwd_dq_f32", "fwd_mfma",
-                                               "bwd_mfma", "bwd_dq_cvt", "bwd_dq_mfma", "fp8_quant", "fwd_fp8", "ex_fwd", "ex_bwd"};
+                                               "bwd_mfma", "bwd_dq_cvt", "bwd_dq_mfma", "fp8_quant", "fwd_fp8", "ex_fwd", "ex_bwd", "kv_group_sum"};
 
 hipEvent_t prof_get_event() {
     if (!g_prof_free.empty()) { hipEvent_t e = g_prof_free.back(); g_prof_free.pop_back(); return e; }
@@ -347,58 +347,132 @@ static int ex_check(const char* who, int64_t bh, int64_t nq, int64_t nk, int64_t
     return FA_OK;
 }
 
-int fa_ex_forward(const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t nq, int64_t nk, int64_t d,
-                  int dtype, int causal, double softmax_scale, const uint8_t* mask, int64_t mask_bh_stride,
-                  const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* stream) {
-    int rc = ex_check("fa_ex_forward", bh, nq, nk, d, dtype, softmax_scale, block_mask, br, bc, dropout_p);
+// grouped-query attention: kv_group query heads per K/V head (k and v hold bh / kv_group units)
+static int group_check(const char* who, int64_t bh, int64_t kv_group) {
+    if (kv_group < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: kv_group must be >= 1 (got %lld)", who, (long long)kv_group);
+    if (bh % kv_group != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: BH=%lld is not a multiple of kv_group=%lld", who, (long long)bh, (long long)kv_group);
+    if (kv_group > 1 && bh * kv_group >= ((int64_t)1 << 32))   // (the kernels divide by kv_group with a 32-bit multiplier)
+        return fail(FA_ERR_UNSUPPORTED, "%s: BH * kv_group too large", who);
+    return FA_OK;
+}
+
+static int ex_forward_impl(const char* who, const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t kv_group,
+                           int64_t nq, int64_t nk, int64_t d, int dtype, int causal, double softmax_scale, const uint8_t* mask,
+                           int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p,
+                           uint64_t dropout_seed, void* stream) {
+    int rc = ex_check(who, bh, nq, nk, d, dtype, softmax_scale, block_mask, br, bc, dropout_p);
     if (rc != FA_OK) return rc;
+    if ((rc = group_check(who, bh, kv_group)) != FA_OK) return rc;
     if (bh == 0 || nq == 0) return FA_OK;
-    if (!q || !o || !lse || (nk > 0 && (!k || !v))) return fail(FA_ERR_INVALID_ARGUMENT, "fa_ex_forward: null tensor pointer");
+    if (!q || !o || !lse || (nk > 0 && (!k || !v))) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
     if (nk == 0) {   // no key at all: every row is a row without a visible key, o = 0 and lse = -inf
         hipStream_t st = reinterpret_cast<hipStream_t>(stream);
         hipError_t e = hipMemsetAsync(o, 0, (size_t)bh * nq * d * (dtype == FA_DTYPE_F32 ? 4 : 2), st);
         if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lse), (int)0xFF800000u, (size_t)bh * nq, st);
-        if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "fa_ex_forward: HIP error %d (%s)", (int)e, hipGetErrorString(e));
+        if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
         return FA_OK;
     }
     fa::ExArgs a{q, k, v, o, lse, nullptr, nullptr, nullptr, nullptr, bh, nq, nk, d, dtype, causal ? 1 : 0, (float)softmax_scale,
                  mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, nullptr};
+    a.kv_group = kv_group;
     hipError_t e = fa::launch_ex(a, false, reinterpret_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "fa_ex_forward: HIP error %d (%s)", (int)e, hipGetErrorString(e));
+    if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
     return FA_OK;
+}
+
+static size_t ex_bwd_ws_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype);
+
+static int ex_backward_impl(const char* who, const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse,
+                            void* dq, void* dk, void* dv, int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype,
+                            int causal, double softmax_scale, const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask,
+                            int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+    int rc = ex_check(who, bh, nq, nk, d, dtype, softmax_scale, block_mask, br, bc, dropout_p);
+    if (rc != FA_OK) return rc;
+    if ((rc = group_check(who, bh, kv_group)) != FA_OK) return rc;
+    if (bh == 0 || (nq == 0 && nk == 0)) return FA_OK;
+    if (nq == 0 || nk == 0) {   // one side empty: the gradients of the other side are sums over nothing
+        const size_t es = dtype == FA_DTYPE_F32 ? 4 : 2;
+        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+        hipError_t e = hipSuccess;
+        if (nq == 0) {   // (grouped: dk and dv hold bh / kv_group units)
+            if (!dk || !dv) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+            e = hipMemsetAsync(dk, 0, (size_t)(bh / kv_group) * nk * d * es, st);
+            if (e == hipSuccess) e = hipMemsetAsync(dv, 0, (size_t)(bh / kv_group) * nk * d * es, st);
+        } else {
+            if (!dq) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+            e = hipMemsetAsync(dq, 0, (size_t)bh * nq * d * es, st);
+        }
+        if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
+        return FA_OK;
+    }
+    if (!q || !k || !v || !o || !do_ || !lse || !dq || !dk || !dv) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    const size_t need = ex_bwd_ws_grouped(bh, kv_group, nq, nk, d, dtype);
+    if (!workspace || workspace_bytes < need)
+        return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
+    fa::ExArgs a{q, k, v, const_cast<void*>(o), const_cast<float*>(lse), do_, dq, dk, dv, bh, nq, nk, d, dtype, causal ? 1 : 0,
+                 (float)softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, workspace, workspace_bytes};
+    a.kv_group = kv_group;
+    hipError_t e = fa::launch_ex(a, true, reinterpret_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
+    return FA_OK;
+}
+
+// the grouped minimum: the ungrouped one for bh query units, plus (kv_group > 1) the dK / dV partial slabs in front of it
+static size_t ex_bwd_ws_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {
+    size_t need = fa_ex_backward_workspace_bytes(bh, nq, nk, d, dtype);
+    if (kv_group > 1 && bh > 0 && nq > 0 && nk > 0 && d > 0) need += 2 * fa::kv_partial_bytes(bh, nk, d, dtype);
+    return need;
+}
+
+// the dS room of the hand-over where it serves the call (the plain backward's rule; grouped: sized for chunks of whole groups)
+static size_t ex_bwd_ds_room(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype, int causal, int extras) {
+    if (extras || bh <= 0 || nq <= 0 || nk <= 0 || g_mode.load() == FA_MODE_F32_GENERIC || fa::option(fa::OPT_EX_PATH) == 1 || fa::option(fa::OPT_EX_PATH) == 3) return 0;
+    if (!fa::bwd_mfma_supported(dtype, d)) return 0;
+    if (nq == nk) return fa::bwd_ds_extra_bytes(bh, nq, d, dtype, causal != 0, bwd_atomic_variant(), 0, kv_group);   // the plain backward's own rule
+    if (!fa::nqnk_mfma_supported(dtype, d, bh, nq, nk, causal)) return 0;   // (under the mask: Nk >= Nq)
+    return fa::bwd_ds_extra_bytes(bh, nq, d, dtype, causal != 0, false, nk, kv_group);
+}
+
+int fa_ex_forward(const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t nq, int64_t nk, int64_t d,
+                  int dtype, int causal, double softmax_scale, const uint8_t* mask, int64_t mask_bh_stride,
+                  const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* stream) {
+    return ex_forward_impl("fa_ex_forward", q, k, v, o, lse, bh, 1, nq, nk, d, dtype, causal, softmax_scale, mask, mask_bh_stride,
+                           block_mask, br, bc, dropout_p, dropout_seed, stream);
+}
+
+int fa_ex_forward_grouped(const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t kv_group, int64_t nq,
+                          int64_t nk, int64_t d, int dtype, int causal, double softmax_scale, const uint8_t* mask, int64_t mask_bh_stride,
+                          const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* stream) {
+    return ex_forward_impl("fa_ex_forward_grouped", q, k, v, o, lse, bh, kv_group, nq, nk, d, dtype, causal, softmax_scale, mask,
+                           mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, stream);
 }
 
 int fa_ex_backward(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
                    void* dv, int64_t bh, int64_t nq, int64_t nk, int64_t d, int dtype, int causal, double softmax_scale,
                    const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p,
                    uint64_t dropout_seed, void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = ex_check("fa_ex_backward", bh, nq, nk, d, dtype, softmax_scale, block_mask, br, bc, dropout_p);
-    if (rc != FA_OK) return rc;
-    if (bh == 0 || (nq == 0 && nk == 0)) return FA_OK;
-    if (nq == 0 || nk == 0) {   // one side empty: the gradients of the other side are sums over nothing
-        const size_t es = dtype == FA_DTYPE_F32 ? 4 : 2;
-        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-        hipError_t e = hipSuccess;
-        if (nq == 0) {
-            if (!dk || !dv) return fail(FA_ERR_INVALID_ARGUMENT, "fa_ex_backward: null tensor pointer");
-            e = hipMemsetAsync(dk, 0, (size_t)bh * nk * d * es, st);
-            if (e == hipSuccess) e = hipMemsetAsync(dv, 0, (size_t)bh * nk * d * es, st);
-        } else {
-            if (!dq) return fail(FA_ERR_INVALID_ARGUMENT, "fa_ex_backward: null tensor pointer");
-            e = hipMemsetAsync(dq, 0, (size_t)bh * nq * d * es, st);
-        }
-        if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "fa_ex_backward: HIP error %d (%s)", (int)e, hipGetErrorString(e));
-        return FA_OK;
-    }
-    if (!q || !k || !v || !o || !do_ || !lse || !dq || !dk || !dv) return fail(FA_ERR_INVALID_ARGUMENT, "fa_ex_backward: null tensor pointer");
-    const size_t need = fa_ex_backward_workspace_bytes(bh, nq, nk, d, dtype);
-    if (!workspace || workspace_bytes < need)
-        return fail(FA_ERR_WORKSPACE, "fa_ex_backward: workspace of %zu bytes needed, %zu given", need, workspace_bytes);
-    fa::ExArgs a{q, k, v, const_cast<void*>(o), const_cast<float*>(lse), do_, dq, dk, dv, bh, nq, nk, d, dtype, causal ? 1 : 0,
-                 (float)softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, workspace, workspace_bytes};
-    hipError_t e = fa::launch_ex(a, true, reinterpret_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "fa_ex_backward: HIP error %d (%s)", (int)e, hipGetErrorString(e));
-    return FA_OK;
+    return ex_backward_impl("fa_ex_backward", q, k, v, o, do_, lse, dq, dk, dv, bh, 1, nq, nk, d, dtype, causal, softmax_scale, mask,
+                            mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, workspace, workspace_bytes, stream);
+}
+
+int fa_ex_backward_grouped(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq,
+                           void* dk, void* dv, int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype, int causal,
+                           double softmax_scale, const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br,
+                           int64_t bc, double dropout_p, uint64_t dropout_seed, void* workspace, size_t workspace_bytes, void* stream) {
+    return ex_backward_impl("fa_ex_backward_grouped", q, k, v, o, do_, lse, dq, dk, dv, bh, kv_group, nq, nk, d, dtype, causal,
+                            softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, workspace, workspace_bytes,
+                            stream);
+}
+
+size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {
+    return ex_bwd_ws_grouped(bh, kv_group, nq, nk, d, dtype);
+}
+
+size_t fa_ex_backward_workspace_bytes_fast_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype, int causal,
+                                                   int extras) {
+    return ex_bwd_ws_grouped(bh, kv_group, nq, nk, d, dtype) + ex_bwd_ds_room(bh, kv_group, nq, nk, d, dtype, causal, extras);
 }
 
 size_t fa_ex_backward_workspace_bytes(int64_t bh, int64_t nq, int64_t nk, int64_t d, int dtype) {
@@ -408,12 +482,7 @@ size_t fa_ex_backward_workspace_bytes(int64_t bh, int64_t nq, int64_t nk, int64_
 }
 
 size_t fa_ex_backward_workspace_bytes_fast(int64_t bh, int64_t nq, int64_t nk, int64_t d, int dtype, int causal, int extras) {
-    size_t need = fa_ex_backward_workspace_bytes(bh, nq, nk, d, dtype);
-    if (extras || bh <= 0 || nq <= 0 || nk <= 0 || g_mode.load() == FA_MODE_F32_GENERIC || fa::option(fa::OPT_EX_PATH) == 1 || fa::option(fa::OPT_EX_PATH) == 3) return need;
-    if (!fa::bwd_mfma_supported(dtype, d)) return need;
-    if (nq == nk) return need + fa::bwd_ds_extra_bytes(bh, nq, d, dtype, causal != 0, bwd_atomic_variant());   // the plain backward's own rule
-    if (!fa::nqnk_mfma_supported(dtype, d, bh, nq, nk, causal)) return need;   // (under the mask: Nk >= Nq)
-    return need + fa::bwd_ds_extra_bytes(bh, nq, d, dtype, causal != 0, false, nk);
+    return fa_ex_backward_workspace_bytes(bh, nq, nk, d, dtype) + ex_bwd_ds_room(bh, 1, nq, nk, d, dtype, causal, extras);
 }
 
 size_t fa3_backward_workspace_bytes(int64_t bh, int64_t n, int64_t d, int dtype, int fp8) {

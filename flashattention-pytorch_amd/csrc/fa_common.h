@@ -341,4 +341,9 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
     return base + idx;
 }
 
+// Grouped-query attention: query unit bh reads K/V unit bh / g (g query heads share one K/V head).  The kernels take
+// kvm = kv_magic(g) (fa_kernels.h; 0 = ungrouped) and divide by one scalar multiply-high: no vector register, no division
+// sequence beside the MFMA streams.
+__device__ __forceinline__ int kv_unit(int bh, unsigned kvm) { return kvm ? (int)__umulhi((unsigned)bh, kvm) : bh; }
+
 }  // namespace fa

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(NW * 64) void ex_fwd_kernel(const T* __restrict__ q
     const int ntile = (p.nq + BM - 1) / BM;
     const int bh = blockIdx.x / ntile;
     const int q0 = (blockIdx.x - bh * ntile) * BM;
-    const size_t qbase = (size_t)bh * p.nq * p.d, kbase = (size_t)bh * p.nk * p.d;
+    const size_t qbase = (size_t)bh * p.nq * p.d, kbase = (size_t)kv_unit(bh, p.kvg) * p.nk * p.d;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int lr = lane & 15, lq = lane >> 4;
 
@@ -196,7 +196,8 @@ __global__ __launch_bounds__(NW * 64) void ex_dkdv_kernel(const T* __restrict__ 
     const int ntile = (p.nk + BK - 1) / BK;
     const int bh = blockIdx.x / ntile;
     const int k0 = (blockIdx.x - bh * ntile) * BK;
-    const size_t qbase = (size_t)bh * p.nq * p.d, kbase = (size_t)bh * p.nk * p.d;
+    const size_t qbase = (size_t)bh * p.nq * p.d, kbase = (size_t)kv_unit(bh, p.kvg) * p.nk * p.d;
+    const size_t dkbase = (size_t)bh * p.nk * p.d;   // dK / dV rows: per query head (grouped: the partials kv_group_sum adds up)
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int lr = lane & 15, lq = lane >> 4;
 
@@ -268,8 +269,8 @@ __global__ __launch_bounds__(NW * 64) void ex_dkdv_kernel(const T* __restrict__ 
             for (int t = 0; t < NT; ++t) {
                 const int c = 16 * t + lr;
                 if (c < p.d) {
-                    dk[kbase + (size_t)key * p.d + c] = from_f32<T>(dka[t][i] * p.scale);
-                    dv[kbase + (size_t)key * p.d + c] = from_f32<T>(dva[t][i]);
+                    dk[dkbase + (size_t)key * p.d + c] = from_f32<T>(dka[t][i] * p.scale);
+                    dv[dkbase + (size_t)key * p.d + c] = from_f32<T>(dva[t][i]);
                 }
             }
         }
@@ -292,7 +293,7 @@ __global__ __launch_bounds__(NW * 64) void ex_dq_kernel(const T* __restrict__ q,
     const int ntile = (p.nq + BM - 1) / BM;
     const int bh = blockIdx.x / ntile;
     const int q0 = (blockIdx.x - bh * ntile) * BM;
-    const size_t qbase = (size_t)bh * p.nq * p.d, kbase = (size_t)bh * p.nk * p.d;
+    const size_t qbase = (size_t)bh * p.nq * p.d, kbase = (size_t)kv_unit(bh, p.kvg) * p.nk * p.d;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int lr = lane & 15, lq = lane >> 4;
 
@@ -420,20 +421,29 @@ static hipError_t ex_by_d(const ExArgs& a, bool backward, hipStream_t st) {
     return backward ? ex_bwd_t<T, 256, 2>(a, st) : ex_fwd_t<T, 256, 4>(a, st);
 }
 
-hipError_t launch_ex(const ExArgs& a, bool backward, hipStream_t st) {
+// Grouped-query attention (a.kv_group > 1) reaches every family below except the plain path's exact-f32 kernels (fa_generic.hip):
+// those calls take this file's kernels.  The K/V unit enters the kernels' K/V addresses only; a backward writes per-query-head
+// dK / dV partials that launch_ex adds up.
+static hipError_t launch_ex_one(const ExArgs& a, bool backward, hipStream_t st) {
     const int path = option(OPT_EX_PATH);   // 0: MFMA kernels where they apply, 1: always these, 2: MFMA or fail, 3: MFMA, never the plain kernels
     // no extras at all on a square problem: this IS the plain path — hand it to the tuned kernels (same results contract;
     // the workspace of fa_ex_backward_workspace_bytes covers their row constants)
     const bool plain = (path == 0 || path == 2) && !a.mask && !a.block_mask && a.dropout_p <= 0.0 && a.scale > 0.f;
     if (plain && a.nq == a.nk && (backward ? bwd_mfma_supported(a.dtype, a.d) : fwd_mfma_supported(a.dtype, a.d))) {
-        if (!backward) return launch_fwd_mfma(FwdArgs{a.q, a.k, a.v, a.o, a.lse, a.bh, a.nq, a.d, a.dtype, a.causal, a.scale}, st);
+        if (!backward) {
+            FwdArgs f{a.q, a.k, a.v, a.o, a.lse, a.bh, a.nq, a.d, a.dtype, a.causal, a.scale};
+            f.kv_group = a.kv_group;
+            return launch_fwd_mfma(f, st);
+        }
         // (with a workspace of fa_ex_backward_workspace_bytes_fast the plain backward hands dS over as it does behind fa2_backward)
-        return launch_bwd_mfma(BwdArgs{a.q, a.k, a.v, a.o, a.dout, a.lse, a.dq, a.dk, a.dv, a.bh, a.nq, a.d, a.dtype, a.causal, a.scale,
-                                       a.workspace, a.workspace_bytes > ex_backward_workspace_bytes(a.bh, a.nq) ? a.workspace_bytes : ex_backward_workspace_bytes(a.bh, a.nq), 0}, st);
+        BwdArgs b{a.q, a.k, a.v, a.o, a.dout, a.lse, a.dq, a.dk, a.dv, a.bh, a.nq, a.d, a.dtype, a.causal, a.scale,
+                  a.workspace, a.workspace_bytes > ex_backward_workspace_bytes(a.bh, a.nq) ? a.workspace_bytes : ex_backward_workspace_bytes(a.bh, a.nq), 0};
+        b.kv_group = a.kv_group;
+        return launch_bwd_mfma(b, st);
     }
     // the same for what the 16-bit kernels do not take (fp32 tensors, head dims that are not a multiple of 8): the plain path's
     // exact-f32 kernels (fa_generic.hip: register fragments, 16-byte operand reads — 2.5 x the rate of the kernels below)
-    if ((path == 0) && !a.mask && !a.block_mask && a.dropout_p <= 0.0 && a.nq == a.nk && a.d <= 256 &&
+    if ((path == 0) && a.kv_group == 1 && !a.mask && !a.block_mask && a.dropout_p <= 0.0 && a.nq == a.nk && a.d <= 256 &&
         !(backward ? bwd_mfma_supported(a.dtype, a.d) : fwd_mfma_supported(a.dtype, a.d))) {
         if (!backward) return launch_fwd_generic(FwdArgs{a.q, a.k, a.v, a.o, a.lse, a.bh, a.nq, a.d, a.dtype, a.causal, a.scale}, st);
         return launch_bwd_generic(BwdArgs{a.q, a.k, a.v, a.o, a.dout, a.lse, a.dq, a.dk, a.dv, a.bh, a.nq, a.d, a.dtype, a.causal, a.scale,
@@ -445,17 +455,19 @@ hipError_t launch_ex(const ExArgs& a, bool backward, hipStream_t st) {
         if (!backward) {
             FwdArgs f{a.q, a.k, a.v, a.o, a.lse, a.bh, a.nq, a.d, a.dtype, a.causal, a.scale};
             f.nk = a.nk;
+            f.kv_group = a.kv_group;
             return launch_fwd_nqnk(f, st);
         }
         BwdArgs b{a.q, a.k, a.v, a.o, a.dout, a.lse, a.dq, a.dk, a.dv, a.bh, a.nq, a.d, a.dtype, a.causal, a.scale, a.workspace,
                   ex_backward_workspace_bytes(a.bh, a.nq), 0};
         b.nk = a.nk;
+        b.kv_group = a.kv_group;
         float* nlse = reinterpret_cast<float*>(a.workspace);
         float* ndelta = nlse + (size_t)a.bh * a.nq;
         // with room for the dS tiles behind the row constants the dK/dV kernel hands dS to the dQ product kernel,
         // as the square backward does and by its rule — since round 3 also under the (shifted) causal diagonal
         const size_t base = (ex_backward_workspace_bytes(a.bh, a.nq) + 255) & ~(size_t)255;
-        const size_t extra = bwd_ds_extra_bytes(a.bh, a.nq, a.d, a.dtype, a.causal != 0, false, a.nk);
+        const size_t extra = bwd_ds_extra_bytes(a.bh, a.nq, a.d, a.dtype, a.causal != 0, false, a.nk, a.kv_group);
         if (extra && a.workspace_bytes >= base + extra)
             return launch_bwd_handover(b, nlse, ndelta, reinterpret_cast<char*>(a.workspace) + base, st);
         hipError_t e = launch_bwd_dq_w4(b, nlse, ndelta, st);   // makes the row constants on its way
@@ -469,6 +481,22 @@ hipError_t launch_ex(const ExArgs& a, bool backward, hipStream_t st) {
         case 1: return ex_by_d<__half>(a, backward, st);
         default: return ex_by_d<__hip_bfloat16>(a, backward, st);
     }
+}
+
+hipError_t launch_ex(const ExArgs& a, bool backward, hipStream_t st) {
+    if (!backward || a.kv_group <= 1) return launch_ex_one(a, backward, st);
+    // Grouped backward.  Workspace: [dK partials][dV partials][what the ungrouped call of bh query units takes]; the kernels write
+    // one dK / dV unit per query head into the partials (their indexing and launch geometry as ungrouped), then the group sum.
+    const size_t slab = kv_partial_bytes(a.bh, a.nk, a.d, a.dtype);
+    if (a.workspace_bytes < 2 * slab) return hipErrorInvalidValue;
+    ExArgs g = a;
+    g.dk = a.workspace;
+    g.dv = reinterpret_cast<char*>(a.workspace) + slab;
+    g.workspace = reinterpret_cast<char*>(a.workspace) + 2 * slab;
+    g.workspace_bytes = a.workspace_bytes - 2 * slab;
+    hipError_t e = launch_ex_one(g, true, st);
+    if (e != hipSuccess) return e;
+    return launch_kv_group_sum(g.dk, g.dv, a.dk, a.dv, a.bh / a.kv_group, a.kv_group, a.nk, a.d, a.dtype, st);
 }
 // [-lse/scale | -delta] for the MFMA kernels (the exact kernels keep delta alone in the first half)
 size_t ex_backward_workspace_bytes(int64_t bh, int64_t nq) { return sizeof(float) * 2 * (((size_t)bh * (size_t)nq + 63) & ~(size_t)63) + 256; }

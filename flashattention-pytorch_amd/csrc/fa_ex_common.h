@@ -19,6 +19,7 @@ struct ExParams {
     unsigned nqh;               // ceil(nq / 2): row pairs per (b,h)
     unsigned long long seedmix; // seed * G + G
     float scale;
+    unsigned kvg;          // kv_magic(query heads per K/V head g): K / V rows of unit bh / g (dK / dV: of bh, the per-head partials)
 };
 
 // Dropout generator: ONE splitmix64 value per 2 x 2 quad of (query row, key) elements, 16 uniform bits per element — the
@@ -70,6 +71,7 @@ inline ExParams make_ex_params(const ExArgs& a) {
     p.nqh = (unsigned)((a.nq + 1) / 2);
     p.seedmix = a.seed * 0x9E3779B97F4A7C15ull + 0x9E3779B97F4A7C15ull;
     p.scale = a.scale;
+    p.kvg = kv_magic(a.kv_group);
     return p;
 }
 

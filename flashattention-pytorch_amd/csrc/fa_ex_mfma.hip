@@ -232,7 +232,7 @@ __global__ __launch_bounds__(512, 2) void exm_fwd_kernel(const uint16_t* __restr
     const int q0 = (L - bh * nqt) * BM;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
-    const size_t qbase = (size_t)bh * nq * DR, kbase = (size_t)bh * nk * DR;
+    const size_t qbase = (size_t)bh * nq * DR, kbase = (size_t)kv_unit(bh, p.kvg) * nk * DR;
     const int qrow = q0 + 32 * w + r;
 
     const buf_rsrc_t q_rs = make_rsrc(q + qbase, (unsigned)nq * DR * 2);
@@ -478,7 +478,7 @@ __global__ __launch_bounds__(512, 2) void exm_dkdv_kernel(const uint16_t* __rest
     const int key0 = (L - bh * nkt) * BK;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
-    const size_t qbase = (size_t)bh * nq * DR, kbase = (size_t)bh * nk * DR, rbase = (size_t)bh * nq;
+    const size_t qbase = (size_t)bh * nq * DR, kbase = (size_t)kv_unit(bh, p.kvg) * nk * DR, rbase = (size_t)bh * nq;
     const int kw0 = key0 + 32 * w, key = kw0 + r;
 
     const rsrc_s_t k_rs = make_rsrc_s(k + kbase, (unsigned)nk * DR * 2);
@@ -654,8 +654,9 @@ __global__ __launch_bounds__(512, 2) void exm_dkdv_kernel(const uint16_t* __rest
     }
 
     if (key < nk) {
-        uint16_t* dkrow = dk + kbase + (size_t)key * DR;
-        uint16_t* dvrow = dv + kbase + (size_t)key * DR;
+        // dK / dV rows: per query head (grouped: the partials kv_group_sum adds up)
+        uint16_t* dkrow = dk + ((size_t)bh * nk + key) * DR;
+        uint16_t* dvrow = dv + ((size_t)bh * nk + key) * DR;
 #pragma unroll
         for (int db = 0; db < NDB; ++db)
 #pragma unroll
@@ -687,7 +688,7 @@ __global__ __launch_bounds__(512, 2) void exm_dq_kernel(const uint16_t* __restri
     const int q0 = (L - bh * nqt) * BM;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
-    const size_t qbase = (size_t)bh * nq * DR, kbase = (size_t)bh * nk * DR;
+    const size_t qbase = (size_t)bh * nq * DR, kbase = (size_t)kv_unit(bh, p.kvg) * nk * DR;
     const int qrow = q0 + 32 * w + r;
     const bool live_row = qrow < nq;
 

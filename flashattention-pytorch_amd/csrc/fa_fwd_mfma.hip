@@ -35,7 +35,7 @@ template <typename Tag, int D, bool CAUSAL, int KB, bool RS_MFMA, bool LAZY, boo
 __global__ __launch_bounds__((D == 256 || W4) ? 256 : 512, D == 256 ? 1 : 2) void fwd_mfma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                           const uint16_t* __restrict__ v, uint16_t* __restrict__ o,
                                                           float* __restrict__ lse, int n, int nqt, float c_log2,
-                                                          float scale, int dr) {
+                                                          float scale, int dr, unsigned kvg /* kv_magic(query heads per K/V head) */) {
     const int DR = PAD ? dr : D;   // elements per tensor row (PAD: head dims below the tile width, fa_common.h)
     // D = 256: 4 waves, one per SIMD, with the whole 512-register file each (Q fragments 64 + O^T 128 registers)
     constexpr int NW = (D == 256 || W4) ? 4 : 8, BM = 32 * NW, BN = 32 * KB, NKS = D / 16, NDV = D / 32;   // KB = 32-key blocks per K/V tile
@@ -74,8 +74,10 @@ __global__ __launch_bounds__((D == 256 || W4) ? 256 : 512, D == 256 ? 1 : 2) voi
     load_q(tile_of(0));
 
     // K / V tiles arrive by LDS-DMA (no staging registers); rows >= n read as zero
-    const rsrc_s_t k_rs = make_rsrc_s(k + base, (unsigned)n * DR * 2);
-    const rsrc_s_t v_rs = make_rsrc_s(v + base, (unsigned)n * DR * 2);
+    // (the RS_MFMA sweep form takes no grouped call: its launcher refuses one, and the form keeps its code as it was)
+    const size_t kvbase = RS_MFMA ? base : (size_t)kv_unit(bh, kvg) * n * DR;
+    const rsrc_s_t k_rs = make_rsrc_s(k + kvbase, (unsigned)n * DR * 2);
+    const rsrc_s_t v_rs = make_rsrc_s(v + kvbase, (unsigned)n * DR * 2);
     const int dma_voff = dma_lane_voff<D>(lane, w, DR);
     const int dma_voff_b = D == 256 ? dma_lane_voff<D>(lane, w + NW, DR) : 0;
     auto stage = [&](int buf, int k0) {
@@ -390,7 +392,8 @@ __global__ __launch_bounds__(512, 2) void fwd_mfma_stag_kernel(const uint16_t* _
                                                                const uint16_t* __restrict__ v, uint16_t* __restrict__ o,
                                                                float* __restrict__ lse, int n, int nqt, float c_log2,
                                                                float scale, int dr_dbg /* row length | debug ablation flags (option fwd_abl) << 16 */,
-                                                               int nk /* keys; n = query rows; causal needs nk >= n: the diagonal sits at key = row + nk - n */) {
+                                                               int nk /* keys; n = query rows; causal needs nk >= n: the diagonal sits at key = row + nk - n */,
+                                                               unsigned kvg /* kv_magic(query heads per K/V head) */) {
     const int dbg = dr_dbg >> 16;
     const int DR = PAD ? (dr_dbg & 0xffff) : D;   // elements per tensor row (PAD: head dims below the tile width, fa_common.h)
     constexpr int BM = 256, BN = 32 * KB, NKS = D / 16, NDV = D / 32;
@@ -413,7 +416,7 @@ __global__ __launch_bounds__(512, 2) void fwd_mfma_stag_kernel(const uint16_t* _
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
     const int qrow = q0 + 32 * w + r;
-    const size_t base = (size_t)bh * n * DR, kbase = (size_t)bh * nk * DR;
+    const size_t base = (size_t)bh * n * DR, kbase = (size_t)kv_unit(bh, kvg) * nk * DR;
     const int coff = nk - n;
     // waves 4..7 (the second wave of every SIMD) run one half-step behind (debug flag 64: waves 0..3 lag instead — does the longer
     // matrix phase of the lagging half follow the wave's age or its role?)
@@ -811,7 +814,7 @@ static hipError_t launch_fwd_t(const FwdArgs& a, hipStream_t st, bool want_stag 
         hipError_t e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kern, grid, dim3(64 * NW), smem, st, (const uint16_t*)a.q, (const uint16_t*)a.k,
-                           (const uint16_t*)a.v, (uint16_t*)a.o, a.lse, (int)a.n, nqt, c, a.scale, last_arg);
+                           (const uint16_t*)a.v, (uint16_t*)a.o, a.lse, (int)a.n, nqt, c, a.scale, last_arg, kv_magic(a.kv_group));
         return hipGetLastError();
     };
     // staggered schedule (fwd_mfma_stag_kernel): d = 128, 64-key tiles (three buffers each) or 128-key tiles (K three, V two;
@@ -826,7 +829,8 @@ static hipError_t launch_fwd_t(const FwdArgs& a, hipStream_t st, bool want_stag 
                 hipError_t e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
                 if (e != hipSuccess) return e;
                 hipLaunchKernelGGL(kern, grid, dim3(64 * NW), smem, st, (const uint16_t*)a.q, (const uint16_t*)a.k,
-                                   (const uint16_t*)a.v, (uint16_t*)a.o, a.lse, (int)a.n, nqt, c, a.scale, last_arg, (int)(a.nk > 0 ? a.nk : a.n));
+                                   (const uint16_t*)a.v, (uint16_t*)a.o, a.lse, (int)a.n, nqt, c, a.scale, last_arg, (int)(a.nk > 0 ? a.nk : a.n),
+                                   kv_magic(a.kv_group));
                 return hipGetLastError();
             };
             if constexpr (ka_ok) {
@@ -844,8 +848,10 @@ static hipError_t launch_fwd_t(const FwdArgs& a, hipStream_t st, bool want_stag 
         }
     }
     if constexpr (!PAD && D != 256) {   // sweep variants exist for the 64 / 128 tile widths only
-    if (option(OPT_FWD_RS) != 0)
+    if (option(OPT_FWD_RS) != 0) {
+        if (a.kv_group > 1) return hipErrorInvalidConfiguration;   // (not built for grouped calls)
         return a.causal ? launch(fwd_mfma_kernel<Tag, D, true, KB, true, true, false, 1, PAD>) : launch(fwd_mfma_kernel<Tag, D, false, KB, true, true, false, 1, PAD>);
+    }
     if (option(OPT_FWD_EAGER) != 0)   // rescale every tile (the textbook order), for the A/B
         return a.causal ? launch(fwd_mfma_kernel<Tag, D, true, KB, false, false, false, 1, PAD>) : launch(fwd_mfma_kernel<Tag, D, false, KB, false, false, false, 1, PAD>);
     if (option(OPT_FWD_HS) != 0)
@@ -896,7 +902,7 @@ static hipError_t launch_fwd_w4(const FwdArgs& a, hipStream_t st) {
         hipError_t e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kern, dim3((unsigned)(nqt * a.bh)), dim3(64 * NW), smem, st, (const uint16_t*)a.q, (const uint16_t*)a.k,
-                           (const uint16_t*)a.v, (uint16_t*)a.o, a.lse, (int)a.n, nqt, c, a.scale, (int)a.d);
+                           (const uint16_t*)a.v, (uint16_t*)a.o, a.lse, (int)a.n, nqt, c, a.scale, (int)a.d, kv_magic(a.kv_group));
         return hipGetLastError();
     };
     return a.causal ? launch(fwd_mfma_kernel<Tag, D, true, KB, false, true, false, 1, false, 0, true>)

@@ -6,6 +6,10 @@
 
 namespace fa {
 
+// Grouped-query attention: the multiplier for bh / g as umulhi(bh, m), m = ceil(2^32 / g); 0 for g = 1 (no grouping).  Exact for
+// bh * g < 2^32 (m g = 2^32 + e with e < g: the error bh e / (g 2^32) stays below 1 / g), which the C-ABI layer checks.
+inline unsigned kv_magic(int64_t g) { return g <= 1 ? 0u : (unsigned)((((uint64_t)1 << 32) + (uint64_t)g - 1) / (uint64_t)g); }
+
 struct FwdArgs {
     const void *q, *k, *v;
     void* o;
@@ -15,6 +19,7 @@ struct FwdArgs {
     int causal;
     float scale;
     int64_t nk = 0;   // keys (0: = n, the query rows).  Only the kernels fwd_nqnk_supported() names take nk != n.
+    int64_t kv_group = 1;   // query heads per K/V head: k, v hold bh / kv_group units, query unit bh reads unit bh / kv_group
 };
 
 struct BwdArgs {
@@ -29,12 +34,15 @@ struct BwdArgs {
     size_t workspace_bytes;
     int fused_dq;  // 1: single kernel, dQ by global float atomics; 0: dK/dV kernel + dQ kernel (deterministic)
     int64_t nk = 0;   // keys (0: = n, the query rows).  Only the stream kernels take nk != n (causal: nk >= n).
+    // query heads per K/V head: k and v hold bh / kv_group units, read through unit bh / kv_group; dk and dv then receive the
+    // per-query-head partials (bh units, as ungrouped) that kv_group_sum adds up.  > 1 only with fused_dq = 0.
+    int64_t kv_group = 1;
 };
 
 // Optional per-kernel timing with HIP events recorded on the launch stream (used by bench.py for the
 // roofline figure; off by default, costs nothing when off).
 enum KernelId { K_FWD_F32 = 0, K_BWD_DELTA, K_BWD_DKDV_F32, K_BWD_DQ_F32, K_FWD_MFMA, K_BWD_MFMA, K_BWD_DQ_CVT, K_BWD_DQ_MFMA,
-                K_FP8_QUANT, K_FWD_FP8, K_EX_FWD, K_EX_BWD, K_COUNT };
+                K_FP8_QUANT, K_FWD_FP8, K_EX_FWD, K_EX_BWD, K_KV_GROUP_SUM, K_COUNT };
 void prof_begin(int id, hipStream_t st);
 void prof_end(int id, hipStream_t st);
 struct ProfScope {
@@ -72,7 +80,8 @@ bool bwd_mfma_supported(int dtype, int64_t d);
 hipError_t launch_bwd_mfma(const BwdArgs& a, hipStream_t st);
 size_t bwd_mfma_workspace_bytes(int64_t bh, int64_t n, int64_t d, bool atomic_variant);   // fp32 dQ scratch only for the single-kernel variant
 // bytes the dS hand-over (fa_bwd_dq_ds.hip) wants on top of that; 0 where it does not serve the call
-size_t bwd_ds_extra_bytes(int64_t bh, int64_t n, int64_t d, int dtype, bool causal, bool atomic_variant, int64_t nk = 0);
+// (kv_group > 1: the chunks of query units are whole groups, so the room is sized for the rounded step)
+size_t bwd_ds_extra_bytes(int64_t bh, int64_t n, int64_t d, int dtype, bool causal, bool atomic_variant, int64_t nk = 0, int64_t kv_group = 1);
 // row constants + the chunk loop [dK/dV with dS stores, dQ product]; a.nk keys (0: = a.n), ds: bwd_ds_extra_bytes of room
 hipError_t launch_bwd_handover(const BwdArgs& a, float* nlse, float* ndelta, void* ds, hipStream_t st);
 hipError_t launch_bwd_dkdv_mfma(const BwdArgs& a, const float* nlse, const float* ndelta, hipStream_t st);  // 8-wave dK/dV
@@ -126,10 +135,20 @@ struct ExArgs {
     uint64_t seed;
     void* workspace;              // backward: ex_backward_workspace_bytes
     size_t workspace_bytes = 0;   // what the caller really gave (more than the minimum lets plain calls hand dS over)
+    int64_t kv_group = 1;         // query heads per K/V head: k, v, dk, dv hold bh / kv_group units (grouped-query attention)
 };
 hipError_t launch_ex(const ExArgs& a, bool backward, hipStream_t st);
 bool ex_mfma_supported(const ExArgs& a);
 hipError_t launch_ex_mfma(const ExArgs& a, bool backward, hipStream_t st);
 size_t ex_backward_workspace_bytes(int64_t bh, int64_t nq);
+// the two per-query-head dK / dV partial slabs of a grouped backward (kv_group > 1), each rounded to 256 bytes
+inline size_t kv_partial_bytes(int64_t bh, int64_t nk, int64_t d, int dtype) {
+    return (((size_t)bh * nk * d * (dtype == 0 ? 4 : 2) + 255) & ~(size_t)255);
+}
+
+// Grouped-query attention (fa_kv_group.hip): dk[u] = sum over m = 0 .. g-1 of pk[u g + m] (and dv from pv), accumulated in fp32 in
+// that order and rounded once to the tensor dtype; units of nk * d elements, bh / g of them in dk and dv.
+hipError_t launch_kv_group_sum(const void* pk, const void* pv, void* dk, void* dv, int64_t bh_kv, int64_t g, int64_t nk, int64_t d,
+                               int dtype, hipStream_t st);
 
 }  // namespace fa

@@ -35,6 +35,8 @@ EXPORTED_C_SYMBOLS = (
     "fa_backward_workspace_bytes", "fa_backward_workspace_bytes_fast", "fa3_forward_workspace_bytes", "fa3_backward_workspace_bytes", "fa_last_error", "fa_version",
     "fa_set_kernel_mode", "fa_set_option", "fa_debug_trace_buffer", "fa_device_is_gfx950", "fa_profile_enable", "fa_profile_report",
     "fa_ex_forward", "fa_ex_backward", "fa_ex_backward_workspace_bytes", "fa_ex_backward_workspace_bytes_fast",
+    "fa_ex_forward_grouped", "fa_ex_backward_grouped", "fa_ex_backward_workspace_bytes_grouped",
+    "fa_ex_backward_workspace_bytes_fast_grouped",
 )
 
 
@@ -90,6 +92,16 @@ def _load_library() -> ctypes.CDLL:
     lib.fa_ex_backward_workspace_bytes.restype = sz
     lib.fa_ex_backward_workspace_bytes_fast.argtypes = [i64, i64, i64, i64, ci, ci, ci]
     lib.fa_ex_backward_workspace_bytes_fast.restype = sz
+    # grouped-query attention: the same arguments with kv_group right after bh
+    lib.fa_ex_forward_grouped.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, ci, dbl, vp, i64, vp, i64, i64, dbl, u64, vp]
+    lib.fa_ex_forward_grouped.restype = ci
+    lib.fa_ex_backward_grouped.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, ci, dbl, vp, i64, vp, i64, i64,
+                                           dbl, u64, vp, sz, vp]
+    lib.fa_ex_backward_grouped.restype = ci
+    lib.fa_ex_backward_workspace_bytes_grouped.argtypes = [i64, i64, i64, i64, i64, ci]
+    lib.fa_ex_backward_workspace_bytes_grouped.restype = sz
+    lib.fa_ex_backward_workspace_bytes_fast_grouped.argtypes = [i64, i64, i64, i64, i64, ci, ci, ci]
+    lib.fa_ex_backward_workspace_bytes_fast_grouped.restype = sz
     return lib
 
 
@@ -277,8 +289,11 @@ def _ex_common(who, q, k, v, mask, block_mask, br, bc):
     for t in (q, k, v):
         if not t.is_cuda:
             raise RuntimeError(f"{who}: tensors must be on the GPU (HIP device); there is no CPU path")
-    if q.dim() != 3 or k.dim() != 3 or v.shape != k.shape or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
-        raise RuntimeError(f"{who}: q must be (BH, Nq, d), k and v (BH, Nk, d); got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    # grouped-query attention: k and v may hold fewer units than q, BH / kv_group, query unit u reading K/V unit u // kv_group
+    if (q.dim() != 3 or k.dim() != 3 or v.shape != k.shape or q.shape[2] != k.shape[2] or
+            (k.shape[0] == 0 and q.shape[0] != 0) or (k.shape[0] > 0 and q.shape[0] % k.shape[0] != 0)):
+        raise RuntimeError(f"{who}: q must be (BH, Nq, d), k and v (BH / kv_group, Nk, d); got {tuple(q.shape)}, {tuple(k.shape)}, "
+                           f"{tuple(v.shape)}")
     if q.dtype not in _DTYPE_CODE or k.dtype != q.dtype or v.dtype != q.dtype:
         raise RuntimeError(f"{who}: q, k, v must share a supported dtype")
     bh, nq, d = q.shape
@@ -301,40 +316,54 @@ def _ex_common(who, q, k, v, mask, block_mask, br, bc):
         if tuple(block_mask.shape) != want:
             raise RuntimeError(f"{who}: block_sparse_mask must be {want} for br={br}, bc={bc}, got {tuple(block_mask.shape)}")
         bptr = block_mask.data_ptr()
-    return bh, nq, nk, d, _DTYPE_CODE[q.dtype], mask, mptr, mstride, block_mask, bptr
+    kv_group = bh // k.shape[0] if k.shape[0] > 0 else 1
+    return bh, nq, nk, d, _DTYPE_CODE[q.dtype], mask, mptr, mstride, block_mask, bptr, kv_group
 
 
 def ex_forward(q, k, v, causal, softmax_scale, mask=None, block_mask=None, br=128, bc=128, dropout_p=0.0, seed=0):
     """(o, lse) of attention with Nq != Nk (causal aligned bottom-right), dense mask (0 = masked), block-sparse mask
-    (0 = tile skipped) and dropout; see include/fa_mi355x.h."""
+    (0 = tile skipped) and dropout; see include/fa_mi355x.h.  k and v with BH / g units (g query heads per K/V head) make
+    it grouped-query attention."""
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-    bh, nq, nk, d, code, mask, mptr, mstride, block_mask, bptr = _ex_common("ex_forward", q, k, v, mask, block_mask, br, bc)
+    bh, nq, nk, d, code, mask, mptr, mstride, block_mask, bptr, g = _ex_common("ex_forward", q, k, v, mask, block_mask, br, bc)
     with torch.cuda.device(q.device):
         o = torch.empty_like(q)
         lse = torch.empty((bh, nq), dtype=torch.float32, device=q.device)
-        _check(_lib.fa_ex_forward(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), bh, nq, nk, d, code,
-                                  int(bool(causal)), float(softmax_scale), mptr, mstride, bptr, int(br), int(bc), float(dropout_p),
-                                  int(seed) & (2 ** 64 - 1), _stream_ptr(q.device)))
+        ptrs = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr())
+        rest = (nq, nk, d, code, int(bool(causal)), float(softmax_scale), mptr, mstride, bptr, int(br), int(bc), float(dropout_p),
+                int(seed) & (2 ** 64 - 1), _stream_ptr(q.device))
+        if g > 1:
+            _check(_lib.fa_ex_forward_grouped(*ptrs, bh, g, *rest))
+        else:
+            _check(_lib.fa_ex_forward(*ptrs, bh, *rest))
     return o, lse
 
 
 def ex_backward(q, k, v, o, do_, lse, causal, softmax_scale, mask=None, block_mask=None, br=128, bc=128, dropout_p=0.0, seed=0):
     q, k, v, o, do_, lse = (t.contiguous() for t in (q, k, v, o, do_, lse))
-    bh, nq, nk, d, code, mask, mptr, mstride, block_mask, bptr = _ex_common("ex_backward", q, k, v, mask, block_mask, br, bc)
+    bh, nq, nk, d, code, mask, mptr, mstride, block_mask, bptr, g = _ex_common("ex_backward", q, k, v, mask, block_mask, br, bc)
     if o.shape != q.shape or do_.shape != q.shape or lse.shape != (bh, nq) or lse.dtype != torch.float32:
         raise RuntimeError("ex_backward: o, do must be (BH, Nq, d) and lse (BH, Nq) float32")
     with torch.cuda.device(q.device):
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        small = int(_lib.fa_ex_backward_workspace_bytes(bh, nq, nk, d, code))
         extras = int(mask is not None or block_mask is not None or dropout_p > 0.0)
-        fast = int(_lib.fa_ex_backward_workspace_bytes_fast(bh, nq, nk, d, code, int(bool(causal)), extras))
+        if g > 1:   # (+ the per-query-head dK / dV partials the library sums over each group)
+            small = int(_lib.fa_ex_backward_workspace_bytes_grouped(bh, g, nq, nk, d, code))
+            fast = int(_lib.fa_ex_backward_workspace_bytes_fast_grouped(bh, g, nq, nk, d, code, int(bool(causal)), extras))
+        else:
+            small = int(_lib.fa_ex_backward_workspace_bytes(bh, nq, nk, d, code))
+            fast = int(_lib.fa_ex_backward_workspace_bytes_fast(bh, nq, nk, d, code, int(bool(causal)), extras))
         capturing = torch.cuda.is_current_stream_capturing()
         have = 0 if capturing else _workspaces.capacity(q.device, _stream_ptr(q.device))
         nbytes = plan_backward_workspace(small, fast, have, None if (have >= fast or capturing) else _device_headroom(q.device))
         ws = _workspace(q.device, nbytes)
         nbytes = max(nbytes, 0 if capturing else _workspaces.capacity(q.device, _stream_ptr(q.device)))
-        _check(_lib.fa_ex_backward(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do_.data_ptr(), lse.data_ptr(),
-                                   dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), bh, nq, nk, d, code, int(bool(causal)),
-                                   float(softmax_scale), mptr, mstride, bptr, int(br), int(bc), float(dropout_p),
-                                   int(seed) & (2 ** 64 - 1), ws.data_ptr(), nbytes, _stream_ptr(q.device)))
+        ptrs = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do_.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+                dv.data_ptr())
+        rest = (nq, nk, d, code, int(bool(causal)), float(softmax_scale), mptr, mstride, bptr, int(br), int(bc), float(dropout_p),
+                int(seed) & (2 ** 64 - 1), ws.data_ptr(), nbytes, _stream_ptr(q.device))
+        if g > 1:
+            _check(_lib.fa_ex_backward_grouped(*ptrs, bh, g, *rest))
+        else:
+            _check(_lib.fa_ex_backward(*ptrs, bh, *rest))
     return dq, dk, dv

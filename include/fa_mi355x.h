@@ -140,6 +140,37 @@ size_t fa_ex_backward_workspace_bytes(int64_t bh, int64_t nq, int64_t nk, int64_
  * included, under the causal mask with Nk >= Nq; at most 4 GiB more).  Equals fa_ex_backward_workspace_bytes where that does not apply. */
 size_t fa_ex_backward_workspace_bytes_fast(int64_t bh, int64_t nq, int64_t nk, int64_t d, int dtype, int causal, int extras);
 
+/* --- Grouped-query attention (GQA; MQA at kv_group = BH / B): K and V with fewer heads than Q.  The fa_ex_* calls above with
+ * kv_group = H_q / H_kv right after bh; kv_group = 1 is exactly the fa_ex_* call.
+ *   q, o, do, dq : (BH, Nq, d) with BH = B * H_q      k, v, dk, dv : (BH / kv_group, Nk, d)      lse : (BH, Nq) float32
+ *   query unit u reads K/V unit u / kv_group (= b * H_kv + h / kv_group: heads are b-major); mask_bh_stride, the dropout counter
+ *   and lse stay indexed by the query unit.  kv_group >= 1 and BH % kv_group == 0, else FA_ERR_INVALID_ARGUMENT.
+ * The backward runs the dK/dV kernels with one output per query head into two partial slabs of the workspace and sums each group
+ * into dk and dv (fp32, member 0 first, one rounding): deterministic, the same bits on every run.
+ * Workspace: fa_ex_backward_workspace_bytes_grouped = fa_ex_backward_workspace_bytes for BH query units, plus for kv_group > 1 the
+ * two slabs, 2 * round_up(BH * Nk * d * sizeof(dtype), 256) bytes.  _fast_grouped adds the dS hand-over's room by the rule of
+ * fa_ex_backward_workspace_bytes_fast (chunks of whole groups).  Same kernels as the fa_ex_* calls, with the exception of the
+ * plain path's exact-f32 kernels: square calls of f32 tensors without extras take the extended exact-f32 kernels instead. */
+int fa_ex_forward_grouped(const void* q, const void* k, const void* v, void* o, float* lse,
+                          int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype,
+                          int causal, double softmax_scale,
+                          const uint8_t* mask, int64_t mask_bh_stride,
+                          const uint8_t* block_mask, int64_t br, int64_t bc,
+                          double dropout_p, uint64_t dropout_seed, void* stream);
+
+int fa_ex_backward_grouped(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse,
+                           void* dq, void* dk, void* dv,
+                           int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype,
+                           int causal, double softmax_scale,
+                           const uint8_t* mask, int64_t mask_bh_stride,
+                           const uint8_t* block_mask, int64_t br, int64_t bc,
+                           double dropout_p, uint64_t dropout_seed,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype);
+size_t fa_ex_backward_workspace_bytes_fast_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype,
+                                                   int causal, int extras);
+
 /* --- support entry points (no reference counterpart: the reference allocates inside the callee) --- */
 /* bytes for the CURRENT kernel mode: two float row constants per query row (+ an fp32 dQ scratch of bh*n*d floats in
  * FA_MODE_BWD_ATOMIC only); ask again after changing the mode */

@@ -3,12 +3,19 @@ family (16-bit MFMA kernels, csrc/fa_ex_mfma.hip; exact-f32 kernels, csrc/fa_ex.
 score matrix accounted for (algorithmic FLOPs = 4 / 10 x visible (q, key) pairs x d).
 
     python tools/bench_ex.py [--bh 32] [--nq 2048] [--nk 4096] [--head-dim 128] [--dtype bf16] [--paths default,mfma,exact]
+
+Grouped-query attention (--kv-heads 8,1): B x H_q query heads (--batch, --q-heads, --nq = --nk) against each listed K/V head
+count, causal and not.  Per row: the grouped call (fa_ex_*_grouped), the same call with H_kv = H_q, and the repeat_interleave
+route (K and V expanded by torch, autograd sums their gradients); forward and backward alone for the first two, the whole
+autograd step (flash_attention_ex forward + backward) for all three, and the group-sum kernel's share of the backward.
+
+    python tools/bench_ex.py --kv-heads 8,1 [--batch 8] [--q-heads 32] [--nq 4096] [--head-dim 128]
 """
 import argparse
 import json
 import sys
 
-sys.path.insert(0, "flashattention-pytorch_amd")
+sys.path.insert(0, "flashattention-pytorch_amd")   # (run from the repository root)
 import torch
 import flashattention_lab_cuda as ext
 
@@ -35,7 +42,12 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--paths", default="mfma,exact")
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--kv-heads", default="", help="comma-separated K/V head counts: time grouped-query attention instead")
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--q-heads", type=int, default=32)
     args = ap.parse_args()
+    if args.kv_heads:
+        return bench_gqa(args)
     dt = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[args.dtype]
     bh, nq, nk, d = args.bh, args.nq, args.nk, args.head_dim
     g = torch.Generator(device="cuda").manual_seed(0)
@@ -81,6 +93,53 @@ def main():
     print(json.dumps(dict(shape=dict(bh=bh, nq=nq, nk=nk, d=d, dtype=args.dtype),
                           kernels="mfma: v_mfma_f32_32x32x16 (peak 2500 TFLOP/s); exact: v_mfma_f32_16x16x4_f32 (peak 157 TFLOP/s)",
                           rows=rows), indent=1))
+
+
+def bench_gqa(args):
+    from common.attention_ex import flash_attention_ex
+
+    dt = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[args.dtype]
+    b, hq, n, d = args.batch, args.q_heads, args.nq, args.head_dim
+    scale = d ** -0.5
+    g = torch.Generator(device="cuda").manual_seed(0)
+    q = torch.randn((b * hq, n, d), device="cuda", dtype=dt, generator=g)
+    do = torch.randn((b * hq, n, d), device="cuda", dtype=dt, generator=g)
+    kf, vf = (torch.randn((b * hq, n, d), device="cuda", dtype=dt, generator=g) for _ in range(2))   # H_kv = H_q
+    rows = []
+    for hkv in (int(x) for x in args.kv_heads.split(",")):
+        grp = hq // hkv
+        k, v = kf[: b * hkv].clone(), vf[: b * hkv].clone()
+        for causal in (False, True):
+            row = dict(h_q=hq, h_kv=hkv, causal=causal)
+            for name, kk, vv in (("grouped", k, v), ("ungrouped", kf, vf)):
+                o, lse = ext.ex_forward(q, kk, vv, causal, scale)
+                row[name + "_fwd_ms"] = round(timed(lambda: ext.ex_forward(q, kk, vv, causal, scale), args.iters), 3)
+                row[name + "_bwd_ms"] = round(timed(lambda: ext.ex_backward(q, kk, vv, o, do, lse, causal, scale), args.iters), 3)
+                if name == "grouped":
+                    ext.profile_enable(True)
+                    ext.ex_backward(q, kk, vv, o, do, lse, causal, scale)
+                    torch.cuda.synchronize()
+                    prof = ext.profile_report()
+                    ext.profile_enable(False)
+                    row["kv_group_sum_ms"] = round(prof.get("kv_group_sum", (0, 0.0))[1], 3)
+            leaves = [t.detach().clone().requires_grad_(True) for t in (q, k, v)]
+            full = [t.detach().clone().requires_grad_(True) for t in (kf, vf)]
+
+            def step(route):
+                if route == "grouped":
+                    o = flash_attention_ex(leaves[0], leaves[1], leaves[2], causal=causal, softmax_scale=scale)
+                elif route == "ungrouped":
+                    o = flash_attention_ex(leaves[0], full[0], full[1], causal=causal, softmax_scale=scale)
+                else:   # expand K and V by torch; autograd sums the gradients of each group
+                    o = flash_attention_ex(leaves[0], leaves[1].repeat_interleave(grp, 0), leaves[2].repeat_interleave(grp, 0),
+                                           causal=causal, softmax_scale=scale)
+                o.backward(do)
+
+            for route in ("grouped", "ungrouped", "repeat_interleave"):
+                row[route + "_step_ms"] = round(timed(lambda: step(route), args.iters), 3)
+            rows.append(row)
+            del leaves, full
+    print(json.dumps(dict(shape=dict(batch=b, q_heads=hq, n=n, d=d, dtype=args.dtype), rows=rows), indent=1))
 
 
 if __name__ == "__main__":
