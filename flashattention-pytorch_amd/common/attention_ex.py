@@ -4,19 +4,24 @@
 extended entry points (`fa_ex_forward` / `fa_ex_backward`, include/fa_mi355x.h):
 
     flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, block_size=128,
-                       causal=False, dropout_p=0.0, seed=0, softmax_scale=None) -> o
+                       causal=False, dropout_p=0.0, seed=0, softmax_scale=None, window_size=(-1, -1)) -> o
 
 q: (B, H, Nq, d) or (BH, Nq, d); k, v: (B, H_kv, Nk, d) or (B*H_kv, Nk, d).  H_kv < H is grouped-query attention (GQA; H_kv = 1:
 multi-query attention) with H % H_kv == 0: query head h reads K/V head h // (H / H_kv), with no copy of K and V, and the
 gradients of k and v come back in k's and v's shape, summed over each group by the library.  `mask` follows the model's convention — a boolean / 0-1 tensor
 broadcastable to (B, H, Nq, Nk), True / 1 = allowed (`look_ahead_mask_` builds the causal one for Nq != Nk, :176-190;
 `causal=True` is the same mask without materialising it) — and `block_sparse_mask[i, j] == 0` skips tile (i, j) of
-`block_size` x `block_size` (Algorithm 5).  Differentiable (autograd Function; the backward recomputes P and regenerates
-the dropout mask from the seed).  No CPU path: the tensors must live on the GPU.
+`block_size` x `block_size` (Algorithm 5).  `window_size=(left, right)` is a sliding window (local attention, FlashAttention-2's
+argument) in the causal flag's coordinates: key j is visible to query i only if i + Nk - Nq - left <= j <= i + Nk - Nq + right,
+-1 = unbounded on that side; `causal=True, window_size=(left, -1)` is the usual causal local attention.  It composes with every
+other argument (GQA K/V included), and the kernels visit only the tiles of each row's band (fa_ex_forward_window); a window
+that bounds nothing is the call without one, bit for bit.  Differentiable (autograd Function; the backward recomputes P and
+regenerates the dropout mask from the seed).  No CPU path: the tensors must live on the GPU.
 """
 from __future__ import annotations
 
 import math
+import operator
 
 import torch
 
@@ -55,12 +60,12 @@ def normalize_mask(mask, lead, nq, nk):
 
 class _FlashAttnExFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale, mask, block_mask, br, bc, dropout_p, seed):
+    def forward(ctx, q, k, v, causal, scale, mask, block_mask, br, bc, dropout_p, seed, window):
         import flashattention_lab_cuda as ext
 
-        o, lse = ext.ex_forward(q, k, v, causal, scale, mask, block_mask, br, bc, dropout_p, seed)
+        o, lse = ext.ex_forward(q, k, v, causal, scale, mask, block_mask, br, bc, dropout_p, seed, window=window)
         ctx.save_for_backward(q, k, v, o, lse)
-        ctx.args = (causal, scale, mask, block_mask, br, bc, dropout_p, seed)
+        ctx.args = (causal, scale, mask, block_mask, br, bc, dropout_p, seed, window)
         return o
 
     @staticmethod
@@ -68,13 +73,29 @@ class _FlashAttnExFn(torch.autograd.Function):
         import flashattention_lab_cuda as ext
 
         q, k, v, o, lse = ctx.saved_tensors
-        causal, scale, mask, block_mask, br, bc, dropout_p, seed = ctx.args
-        dq, dk, dv = ext.ex_backward(q, k, v, o, do.contiguous(), lse, causal, scale, mask, block_mask, br, bc, dropout_p, seed)
-        return (dq, dk, dv) + (None,) * 8
+        causal, scale, mask, block_mask, br, bc, dropout_p, seed, window = ctx.args
+        dq, dk, dv = ext.ex_backward(q, k, v, o, do.contiguous(), lse, causal, scale, mask, block_mask, br, bc, dropout_p, seed,
+                                     window=window)
+        return (dq, dk, dv) + (None,) * 9
+
+
+def _window_size(window_size):
+    """(left, right) ints >= -1, with the library's error text (flashattention_lab_cuda.window_arg, fa_capi.hip)."""
+    try:
+        left, right = window_size
+        if isinstance(left, bool) or isinstance(right, bool):
+            raise TypeError
+        left, right = operator.index(left), operator.index(right)
+    except (TypeError, ValueError):
+        raise RuntimeError(f"flash_attention_ex: window_size must be a pair (left, right) of ints, got {window_size!r}") from None
+    if left < -1 or right < -1:
+        raise RuntimeError(f"flash_attention_ex: window ({left}, {right}): each bound must be >= 0, or -1 for unbounded")
+    return left, right
 
 
 def flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, block_size=128, causal=False, dropout_p=0.0,
-                       seed=0, softmax_scale=None):
+                       seed=0, softmax_scale=None, window_size=(-1, -1)):
+    window = _window_size(window_size)
     if not q.is_cuda:
         raise RuntimeError("Inputs must be CUDA tensors")   # as the reference's wrappers (src/fa2/cuda/impl.py:44)
     four_d = q.dim() == 4
@@ -96,5 +117,5 @@ def flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, bloc
     br = bc = int(block_size)
     if block_sparse_mask is not None:
         br, bc = min(br, nq), min(bc, nk)         # Br = min(block_size, q_len), Bc = min(block_size, kv_len)  (:100-101)
-    o = _FlashAttnExFn.apply(q3, k3, v3, bool(causal), scale, m, block_sparse_mask, br, bc, float(dropout_p), int(seed))
+    o = _FlashAttnExFn.apply(q3, k3, v3, bool(causal), scale, m, block_sparse_mask, br, bc, float(dropout_p), int(seed), window)
     return o.reshape(q.shape) if four_d else o

@@ -357,13 +357,28 @@ static int group_check(const char* who, int64_t bh, int64_t kv_group) {
     return FA_OK;
 }
 
+// sliding window (local attention): key j is visible to query i only if j >= i + (Nk - Nq) - wl and j <= i + (Nk - Nq) + wr,
+// -1 = unbounded on that side.  Canonical form (a window that bounds nothing is then exactly the call without one): bounds that
+// cut nothing are dropped, and wr = 0 without the causal mask IS the causal mask.
+static int window_canon(const char* who, int64_t nq, int64_t nk, int& causal, int64_t& wl, int64_t& wr) {
+    if (wl < -1 || wr < -1)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: window (%lld, %lld): each bound must be >= 0, or -1 for unbounded", who,
+                    (long long)wl, (long long)wr);
+    if (wl >= nk - 1) wl = -1;            // the first key is in every row's band
+    if (wr >= nq - 1) wr = -1;            // the last key is in every row's band
+    if (causal && wr >= 0) wr = -1;       // the diagonal bounds more
+    if (!causal && wr == 0) { causal = 1; wr = -1; }
+    return FA_OK;
+}
+
 static int ex_forward_impl(const char* who, const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t kv_group,
-                           int64_t nq, int64_t nk, int64_t d, int dtype, int causal, double softmax_scale, const uint8_t* mask,
-                           int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p,
-                           uint64_t dropout_seed, void* stream) {
+                           int64_t nq, int64_t nk, int64_t d, int dtype, int causal, int64_t wl, int64_t wr, double softmax_scale,
+                           const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc,
+                           double dropout_p, uint64_t dropout_seed, void* stream) {
     int rc = ex_check(who, bh, nq, nk, d, dtype, softmax_scale, block_mask, br, bc, dropout_p);
     if (rc != FA_OK) return rc;
     if ((rc = group_check(who, bh, kv_group)) != FA_OK) return rc;
+    if ((rc = window_canon(who, nq, nk, causal, wl, wr)) != FA_OK) return rc;
     if (bh == 0 || nq == 0) return FA_OK;
     if (!q || !o || !lse || (nk > 0 && (!k || !v))) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
     if (nk == 0) {   // no key at all: every row is a row without a visible key, o = 0 and lse = -inf
@@ -376,6 +391,8 @@ static int ex_forward_impl(const char* who, const void* q, const void* k, const 
     fa::ExArgs a{q, k, v, o, lse, nullptr, nullptr, nullptr, nullptr, bh, nq, nk, d, dtype, causal ? 1 : 0, (float)softmax_scale,
                  mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, nullptr};
     a.kv_group = kv_group;
+    a.window_left = wl;
+    a.window_right = wr;
     hipError_t e = fa::launch_ex(a, false, reinterpret_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
     return FA_OK;
@@ -385,12 +402,13 @@ static size_t ex_bwd_ws_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_
 
 static int ex_backward_impl(const char* who, const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse,
                             void* dq, void* dk, void* dv, int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype,
-                            int causal, double softmax_scale, const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask,
-                            int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* workspace, size_t workspace_bytes,
-                            void* stream) {
+                            int causal, int64_t wl, int64_t wr, double softmax_scale, const uint8_t* mask, int64_t mask_bh_stride,
+                            const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* workspace,
+                            size_t workspace_bytes, void* stream) {
     int rc = ex_check(who, bh, nq, nk, d, dtype, softmax_scale, block_mask, br, bc, dropout_p);
     if (rc != FA_OK) return rc;
     if ((rc = group_check(who, bh, kv_group)) != FA_OK) return rc;
+    if ((rc = window_canon(who, nq, nk, causal, wl, wr)) != FA_OK) return rc;
     if (bh == 0 || (nq == 0 && nk == 0)) return FA_OK;
     if (nq == 0 || nk == 0) {   // one side empty: the gradients of the other side are sums over nothing
         const size_t es = dtype == FA_DTYPE_F32 ? 4 : 2;
@@ -414,6 +432,8 @@ static int ex_backward_impl(const char* who, const void* q, const void* k, const
     fa::ExArgs a{q, k, v, const_cast<void*>(o), const_cast<float*>(lse), do_, dq, dk, dv, bh, nq, nk, d, dtype, causal ? 1 : 0,
                  (float)softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, workspace, workspace_bytes};
     a.kv_group = kv_group;
+    a.window_left = wl;
+    a.window_right = wr;
     hipError_t e = fa::launch_ex(a, true, reinterpret_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
     return FA_OK;
@@ -438,14 +458,14 @@ static size_t ex_bwd_ds_room(int64_t bh, int64_t kv_group, int64_t nq, int64_t n
 int fa_ex_forward(const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t nq, int64_t nk, int64_t d,
                   int dtype, int causal, double softmax_scale, const uint8_t* mask, int64_t mask_bh_stride,
                   const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* stream) {
-    return ex_forward_impl("fa_ex_forward", q, k, v, o, lse, bh, 1, nq, nk, d, dtype, causal, softmax_scale, mask, mask_bh_stride,
+    return ex_forward_impl("fa_ex_forward", q, k, v, o, lse, bh, 1, nq, nk, d, dtype, causal, -1, -1, softmax_scale, mask, mask_bh_stride,
                            block_mask, br, bc, dropout_p, dropout_seed, stream);
 }
 
 int fa_ex_forward_grouped(const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t kv_group, int64_t nq,
                           int64_t nk, int64_t d, int dtype, int causal, double softmax_scale, const uint8_t* mask, int64_t mask_bh_stride,
                           const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* stream) {
-    return ex_forward_impl("fa_ex_forward_grouped", q, k, v, o, lse, bh, kv_group, nq, nk, d, dtype, causal, softmax_scale, mask,
+    return ex_forward_impl("fa_ex_forward_grouped", q, k, v, o, lse, bh, kv_group, nq, nk, d, dtype, causal, -1, -1, softmax_scale, mask,
                            mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, stream);
 }
 
@@ -453,7 +473,7 @@ int fa_ex_backward(const void* q, const void* k, const void* v, const void* o, c
                    void* dv, int64_t bh, int64_t nq, int64_t nk, int64_t d, int dtype, int causal, double softmax_scale,
                    const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p,
                    uint64_t dropout_seed, void* workspace, size_t workspace_bytes, void* stream) {
-    return ex_backward_impl("fa_ex_backward", q, k, v, o, do_, lse, dq, dk, dv, bh, 1, nq, nk, d, dtype, causal, softmax_scale, mask,
+    return ex_backward_impl("fa_ex_backward", q, k, v, o, do_, lse, dq, dk, dv, bh, 1, nq, nk, d, dtype, causal, -1, -1, softmax_scale, mask,
                             mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, workspace, workspace_bytes, stream);
 }
 
@@ -462,8 +482,26 @@ int fa_ex_backward_grouped(const void* q, const void* k, const void* v, const vo
                            double softmax_scale, const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br,
                            int64_t bc, double dropout_p, uint64_t dropout_seed, void* workspace, size_t workspace_bytes, void* stream) {
     return ex_backward_impl("fa_ex_backward_grouped", q, k, v, o, do_, lse, dq, dk, dv, bh, kv_group, nq, nk, d, dtype, causal,
-                            softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, workspace, workspace_bytes,
+                            -1, -1, softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, workspace, workspace_bytes,
                             stream);
+}
+
+int fa_ex_forward_window(const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t kv_group, int64_t nq,
+                         int64_t nk, int64_t d, int dtype, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                         const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p,
+                         uint64_t dropout_seed, void* stream) {
+    return ex_forward_impl("fa_ex_forward_window", q, k, v, o, lse, bh, kv_group, nq, nk, d, dtype, causal, window_left, window_right,
+                           softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, stream);
+}
+
+int fa_ex_backward_window(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq,
+                          void* dk, void* dv, int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype, int causal,
+                          int64_t window_left, int64_t window_right, double softmax_scale, const uint8_t* mask, int64_t mask_bh_stride,
+                          const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    return ex_backward_impl("fa_ex_backward_window", q, k, v, o, do_, lse, dq, dk, dv, bh, kv_group, nq, nk, d, dtype, causal,
+                            window_left, window_right, softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed,
+                            workspace, workspace_bytes, stream);
 }
 
 size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {

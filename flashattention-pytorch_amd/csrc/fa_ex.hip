@@ -7,7 +7,10 @@
 //   * a block-sparse mask [ceil(Nq/br)][ceil(Nk/bc)], 0 = the tile is skipped (Algorithm 5, line 8: :123-125);
 //   * dropout on the attention probabilities, in-kernel: keep where rnd > p, scale 1/(1-p) (src/common/dropout.py:9-15,
 //     flashattention_pytorch.py:85-87), with a counter-based generator so that the backward regenerates the mask from
-//     (seed, b*h, i, j) instead of storing it; `tau` (:134) folds into softmax_scale.
+//     (seed, b*h, i, j) instead of storing it; `tau` (:134) folds into softmax_scale;
+//   * a sliding window (no reference counterpart; FlashAttention-2's window_size): key j is visible to query i only if
+//     i + (Nk - Nq) - wl <= j <= i + (Nk - Nq) + wr (ExParams: wr = 0 under the causal mask, kWinNone when unbounded); the
+//     key (query) tile ranges of every kernel are cut to the band at both ends.
 // Exact-f32 math on the f32-input MFMA (any dtype in, head_dim <= 256), the structure of fa_generic.hip: forward by
 // query tile with online softmax over the visible keys; backward = delta pre-pass + dK/dV kernel + dQ kernel, no
 // atomics.  Rows without any visible key get o = 0, lse = -inf (the reference's softmax of an all -inf row is NaN).
@@ -60,7 +63,7 @@ template <typename T> __device__ __forceinline__ bool ex_quad_ok(int d, const vo
 // sum stays an f32 fma chain).  The P / dS staging areas are wave-private: no workgroup barrier between writing and reading them.
 
 // ---- forward: one workgroup = NW waves = 16 NW query rows of one (b,h); key tiles of 32
-template <typename T, int DP, int NW>
+template <typename T, int DP, int NW, bool WIN>
 __global__ __launch_bounds__(NW * 64) void ex_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                          const T* __restrict__ v, T* __restrict__ o,
                                                          float* __restrict__ lse, ExParams p) {
@@ -85,11 +88,12 @@ __global__ __launch_bounds__(NW * 64) void ex_fwd_kernel(const T* __restrict__ q
     float m[4], l[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) { m[i] = -INFINITY; l[i] = 0.f; }
-    // keys past the last row's diagonal are masked for every row of the tile
-    const int kend = p.causal ? max(0, min(p.nk, q0 + BM + p.coff)) : p.nk;
+    // keys past the last row's diagonal / band are masked for every row of the tile, and keys before the first row's band
+    const int kend = WIN ? max(0, min(p.nk, q0 + BM + p.coff + p.wr)) : (p.causal ? max(0, min(p.nk, q0 + BM + p.coff)) : p.nk);
+    const int kstart = WIN ? (max(0, q0 + p.coff - p.wl) / BN) * BN : 0;   // (wr = 0 under the causal mask)
     float* Pw = Ps + w * 16 * PLD;
 
-    for (int k0 = 0; k0 < kend; k0 += BN) {
+    for (int k0 = kstart; k0 < kend; k0 += BN) {
         if (!ex_tile_live(p, q0, min(q0 + BM, p.nq), k0, min(k0 + BN, p.nk))) continue;   // block-sparse skip (uniform)
         __syncthreads();
         ex_load_tile<T, DP, LD, NTH>(Ks, k + kbase, k0, BN, p.nk, p.d, vec);
@@ -111,8 +115,8 @@ __global__ __launch_bounds__(NW * 64) void ex_fwd_kernel(const T* __restrict__ q
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int row = q0 + w * 16 + lq * 4 + i;
-            float x0 = ex_visible(p, bh, row, key0) ? s0[i] * p.scale : -INFINITY;
-            float x1 = ex_visible(p, bh, row, key1) ? s1[i] * p.scale : -INFINITY;
+            float x0 = ex_visible<WIN>(p, bh, row, key0) ? s0[i] * p.scale : -INFINITY;
+            float x1 = ex_visible<WIN>(p, bh, row, key1) ? s1[i] * p.scale : -INFINITY;
             float mx = fmaxf(x0, x1);
             mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
             mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
@@ -179,7 +183,7 @@ __global__ __launch_bounds__(256) void ex_delta_kernel(const T* __restrict__ o, 
 
 // ---- backward dK/dV: one workgroup = 16 NW keys resident in LDS; loops over 32-row query tiles
 //      dV = P_drop^T dO,  dP = keep/(1-p) * (dO V^T),  dS = P (dP - delta),  dK = scale dS^T Q
-template <typename T, int DP, int NW>
+template <typename T, int DP, int NW, bool WIN>
 __global__ __launch_bounds__(NW * 64) void ex_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                           const T* __restrict__ v, const T* __restrict__ dout,
                                                           const float* __restrict__ lse, const float* __restrict__ delta,
@@ -209,9 +213,11 @@ __global__ __launch_bounds__(NW * 64) void ex_dkdv_kernel(const T* __restrict__ 
     for (int t = 0; t < NT; ++t) { dka[t] = f32x4{0.f, 0.f, 0.f, 0.f}; dva[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     float* Pw = Pt + w * 16 * PLD;
     float* Sw = St + w * 16 * PLD;
-    // rows before the tile's first key's diagonal see none of it: key k0 is visible from row k0 - coff on
-    const int qstart = p.causal ? (max(0, k0 - p.coff) / BQ) * BQ : 0;
-    for (int r0 = qstart; r0 < p.nq; r0 += BQ) {
+    // rows before the tile's first key's diagonal see none of it: key k0 is visible from row k0 - coff - wr on (wr = 0
+    // under the causal mask); with a left bound the tile's last key is visible up to row kl - coff + wl
+    const int qstart = WIN ? (max(0, k0 - p.coff - p.wr) / BQ) * BQ : (p.causal ? (max(0, k0 - p.coff) / BQ) * BQ : 0);
+    const int qend = WIN ? min(p.nq, min(k0 + BK, p.nk) - p.coff + p.wl) : p.nq;
+    for (int r0 = qstart; r0 < qend; r0 += BQ) {
         if (!ex_tile_live(p, r0, min(r0 + BQ, p.nq), k0, min(k0 + BK, p.nk))) continue;
         __syncthreads();
         ex_load_tile<T, DP, LD, NTH>(Qs, q + qbase, r0, BQ, p.nq, p.d, vec);
@@ -242,7 +248,7 @@ __global__ __launch_bounds__(NW * 64) void ex_dkdv_kernel(const T* __restrict__ 
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int key = k0 + w * 16 + lq * 4 + i;
-                const float pr = ex_visible(p, bh, row, key) ? expf(st[i] * p.scale - lq_) : 0.f;
+                const float pr = ex_visible<WIN>(p, bh, row, key) ? expf(st[i] * p.scale - lq_) : 0.f;
                 const float ks_ = (p.p_drop > 0.f) ? (ex_keep(p, bh, row, key) ? p.keep_scale : 0.f) : 1.f;
                 Pw[(lq * 4 + i) * PLD + qb * 16 + lr] = pr * ks_;                       // P_drop^T (feeds dV)
                 Sw[(lq * 4 + i) * PLD + qb * 16 + lr] = pr * (dpt[i] * ks_ - dl_);      // dS^T
@@ -278,7 +284,7 @@ __global__ __launch_bounds__(NW * 64) void ex_dkdv_kernel(const T* __restrict__ 
 }
 
 // ---- backward dQ: one workgroup = 16 NW query rows; loops over 32-key tiles (S and dP recomputed: deterministic)
-template <typename T, int DP, int NW>
+template <typename T, int DP, int NW, bool WIN>
 __global__ __launch_bounds__(NW * 64) void ex_dq_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                         const T* __restrict__ v, const T* __restrict__ dout,
                                                         const float* __restrict__ lse, const float* __restrict__ delta,
@@ -311,8 +317,9 @@ __global__ __launch_bounds__(NW * 64) void ex_dq_kernel(const T* __restrict__ q,
 #pragma unroll
     for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     float* Sw = Ss + w * 16 * PLD;
-    const int kend = p.causal ? max(0, min(p.nk, q0 + BM + p.coff)) : p.nk;
-    for (int k0 = 0; k0 < kend; k0 += BN) {
+    const int kend = WIN ? max(0, min(p.nk, q0 + BM + p.coff + p.wr)) : (p.causal ? max(0, min(p.nk, q0 + BM + p.coff)) : p.nk);
+    const int kstart = WIN ? (max(0, q0 + p.coff - p.wl) / BN) * BN : 0;   // (the forward kernel's tile range)
+    for (int k0 = kstart; k0 < kend; k0 += BN) {
         if (!ex_tile_live(p, q0, min(q0 + BM, p.nq), k0, min(k0 + BN, p.nk))) continue;
         __syncthreads();
         ex_load_tile<T, DP, LD, NTH>(Ks, k + kbase, k0, BN, p.nk, p.d, vec);
@@ -337,7 +344,7 @@ __global__ __launch_bounds__(NW * 64) void ex_dq_kernel(const T* __restrict__ q,
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int row = q0 + w * 16 + lq * 4 + i;
-                const float pr = ex_visible(p, bh, row, key) ? expf(s[i] * p.scale - lrow[i]) : 0.f;
+                const float pr = ex_visible<WIN>(p, bh, row, key) ? expf(s[i] * p.scale - lrow[i]) : 0.f;
                 const float ks_ = (p.p_drop > 0.f) ? (ex_keep(p, bh, row, key) ? p.keep_scale : 0.f) : 1.f;
                 Sw[(lq * 4 + i) * PLD + nb * 16 + lr] = pr * (dp[i] * ks_ - drow[i]);
             }
@@ -365,11 +372,11 @@ __global__ __launch_bounds__(NW * 64) void ex_dq_kernel(const T* __restrict__ q,
 }
 
 // ---- host launchers
-template <typename T, int DP, int NW>
+template <typename T, int DP, int NW, bool WIN>
 static hipError_t ex_fwd_t(const ExArgs& a, hipStream_t st) {
     constexpr int LD = DP + 4;
     const size_t smem = sizeof(float) * ((16 * NW + 64) * LD + NW * 16 * 36);
-    auto kern = ex_fwd_kernel<T, DP, NW>;
+    auto kern = ex_fwd_kernel<T, DP, NW, WIN>;
     hipError_t e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
     if (e != hipSuccess) return e;
     dim3 grid((unsigned)(((a.nq + 16 * NW - 1) / (16 * NW)) * a.bh));
@@ -379,7 +386,7 @@ static hipError_t ex_fwd_t(const ExArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-template <typename T, int DP, int NW>
+template <typename T, int DP, int NW, bool WIN>
 static hipError_t ex_bwd_t(const ExArgs& a, hipStream_t st) {
     constexpr int LD = DP + 4;
     float* delta = reinterpret_cast<float*>(a.workspace);
@@ -392,7 +399,7 @@ static hipError_t ex_bwd_t(const ExArgs& a, hipStream_t st) {
     if (e != hipSuccess) return e;
     {
         const size_t smem = sizeof(float) * ((2 * 16 * NW + 64) * LD + 2 * NW * 16 * 36 + 64);
-        auto kern = ex_dkdv_kernel<T, DP, NW>;
+        auto kern = ex_dkdv_kernel<T, DP, NW, WIN>;
         e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
         if (e != hipSuccess) return e;
         dim3 grid((unsigned)(((a.nk + 16 * NW - 1) / (16 * NW)) * a.bh));
@@ -403,7 +410,7 @@ static hipError_t ex_bwd_t(const ExArgs& a, hipStream_t st) {
     }
     {
         const size_t smem = sizeof(float) * ((2 * 16 * NW + 64) * LD + NW * 16 * 36);
-        auto kern = ex_dq_kernel<T, DP, NW>;
+        auto kern = ex_dq_kernel<T, DP, NW, WIN>;
         e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
         if (e != hipSuccess) return e;
         dim3 grid((unsigned)(((a.nq + 16 * NW - 1) / (16 * NW)) * a.bh));
@@ -414,11 +421,15 @@ static hipError_t ex_bwd_t(const ExArgs& a, hipStream_t st) {
     return e;
 }
 
+template <typename T, bool WIN>
+static hipError_t ex_by_d(const ExArgs& a, bool backward, hipStream_t st) {
+    if (a.d <= 64) return backward ? ex_bwd_t<T, 64, 4, WIN>(a, st) : ex_fwd_t<T, 64, 4, WIN>(a, st);
+    if (a.d <= 128) return backward ? ex_bwd_t<T, 128, 4, WIN>(a, st) : ex_fwd_t<T, 128, 4, WIN>(a, st);
+    return backward ? ex_bwd_t<T, 256, 2, WIN>(a, st) : ex_fwd_t<T, 256, 4, WIN>(a, st);
+}
 template <typename T>
 static hipError_t ex_by_d(const ExArgs& a, bool backward, hipStream_t st) {
-    if (a.d <= 64) return backward ? ex_bwd_t<T, 64, 4>(a, st) : ex_fwd_t<T, 64, 4>(a, st);
-    if (a.d <= 128) return backward ? ex_bwd_t<T, 128, 4>(a, st) : ex_fwd_t<T, 128, 4>(a, st);
-    return backward ? ex_bwd_t<T, 256, 2>(a, st) : ex_fwd_t<T, 256, 4>(a, st);
+    return ex_windowed(a) ? ex_by_d<T, true>(a, backward, st) : ex_by_d<T, false>(a, backward, st);
 }
 
 // Grouped-query attention (a.kv_group > 1) reaches every family below except the plain path's exact-f32 kernels (fa_generic.hip):
@@ -428,7 +439,9 @@ static hipError_t launch_ex_one(const ExArgs& a, bool backward, hipStream_t st) 
     const int path = option(OPT_EX_PATH);   // 0: MFMA kernels where they apply, 1: always these, 2: MFMA or fail, 3: MFMA, never the plain kernels
     // no extras at all on a square problem: this IS the plain path — hand it to the tuned kernels (same results contract;
     // the workspace of fa_ex_backward_workspace_bytes covers their row constants)
-    const bool plain = (path == 0 || path == 2) && !a.mask && !a.block_mask && a.dropout_p <= 0.0 && a.scale > 0.f;
+    // (a window that bounds something never leaves this file's families: the plain, nq != nk and fa_generic kernels know no band)
+    const bool win = ex_windowed(a);
+    const bool plain = (path == 0 || path == 2) && !win && !a.mask && !a.block_mask && a.dropout_p <= 0.0 && a.scale > 0.f;
     if (plain && a.nq == a.nk && (backward ? bwd_mfma_supported(a.dtype, a.d) : fwd_mfma_supported(a.dtype, a.d))) {
         if (!backward) {
             FwdArgs f{a.q, a.k, a.v, a.o, a.lse, a.bh, a.nq, a.d, a.dtype, a.causal, a.scale};
@@ -443,7 +456,7 @@ static hipError_t launch_ex_one(const ExArgs& a, bool backward, hipStream_t st) 
     }
     // the same for what the 16-bit kernels do not take (fp32 tensors, head dims that are not a multiple of 8): the plain path's
     // exact-f32 kernels (fa_generic.hip: register fragments, 16-byte operand reads — 2.5 x the rate of the kernels below)
-    if ((path == 0) && a.kv_group == 1 && !a.mask && !a.block_mask && a.dropout_p <= 0.0 && a.nq == a.nk && a.d <= 256 &&
+    if ((path == 0) && a.kv_group == 1 && !win && !a.mask && !a.block_mask && a.dropout_p <= 0.0 && a.nq == a.nk && a.d <= 256 &&
         !(backward ? bwd_mfma_supported(a.dtype, a.d) : fwd_mfma_supported(a.dtype, a.d))) {
         if (!backward) return launch_fwd_generic(FwdArgs{a.q, a.k, a.v, a.o, a.lse, a.bh, a.nq, a.d, a.dtype, a.causal, a.scale}, st);
         return launch_bwd_generic(BwdArgs{a.q, a.k, a.v, a.o, a.dout, a.lse, a.dq, a.dk, a.dv, a.bh, a.nq, a.d, a.dtype, a.causal, a.scale,

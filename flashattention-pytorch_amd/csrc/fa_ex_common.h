@@ -7,6 +7,10 @@
 namespace fa {
 
 struct ExParams {
+    // the band of row i: keys [i + coff - wl, i + coff + wr].  wr = 0 under the causal mask, kWinNone (wider than any
+    // problem: nq, nk <= 2^24) on an unbounded side, so the bounds enter the arithmetic without a branch.  (First: the
+    // fields after them keep their relative offsets and alignment, so kernels without a window load them as before.)
+    int wl, wr;
     int nq, nk, d;
     int causal;            // 0 | 1 (bottom-right aligned)
     int coff;              // nk - nq
@@ -21,6 +25,7 @@ struct ExParams {
     float scale;
     unsigned kvg;          // kv_magic(query heads per K/V head g): K / V rows of unit bh / g (dK / dV: of bh, the per-head partials)
 };
+constexpr int kWinNone = 1 << 30;
 
 // Dropout generator: ONE splitmix64 value per 2 x 2 quad of (query row, key) elements, 16 uniform bits per element — the
 // 64-bit mixing (two 64 x 64 multiplies) is the expensive part on a GPU, and in every kernel a lane owns either two
@@ -40,9 +45,12 @@ __device__ __forceinline__ bool ex_keep(const ExParams& p, int bh, int row, int 
     const unsigned u = (unsigned)(z >> (16 * (2 * (row & 1) + (key & 1)))) & 0xffffu;
     return u >= p.drop_thr;
 }
+// WIN: the call has a window (a separate instantiation: calls without one run the code they ran before it existed)
+template <bool WIN>
 __device__ __forceinline__ bool ex_visible(const ExParams& p, int bh, int row, int key) {
     if (row >= p.nq || key >= p.nk) return false;
     if (p.causal && key > row + p.coff) return false;
+    if (WIN && (key > row + p.coff + p.wr || key < row + p.coff - p.wl)) return false;   // (wr = 0 under the causal flag)
     if (p.mask && p.mask[(size_t)bh * p.mask_bh + (size_t)row * p.nk + key] == 0) return false;
     if (p.bmask && p.bmask[(row / p.br) * p.nbc + key / p.bc] == 0) return false;
     return true;
@@ -72,6 +80,8 @@ inline ExParams make_ex_params(const ExArgs& a) {
     p.seedmix = a.seed * 0x9E3779B97F4A7C15ull + 0x9E3779B97F4A7C15ull;
     p.scale = a.scale;
     p.kvg = kv_magic(a.kv_group);
+    p.wl = a.window_left >= 0 ? (int)a.window_left : kWinNone;
+    p.wr = a.causal ? 0 : (a.window_right >= 0 ? (int)a.window_right : kWinNone);
     return p;
 }
 

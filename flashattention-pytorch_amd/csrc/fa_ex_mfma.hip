@@ -6,7 +6,11 @@
 //   dQ        (fa_bwd_dq_mfma.hip)   : 8 waves x 32 query rows, K/V tiles of 64 keys, the query on the lane;
 // with Nq != Nk (separate row counts, causal diagonal shifted by Nk - Nq), and per element
 //   FEAT bit 0  dense mask and / or block-sparse mask (either pointer may be null at run time),
-//   FEAT bit 1  dropout (counter-based, fa_ex_common.h: a lane makes one splitmix64 value per two of its elements).
+//   FEAT bit 1  dropout (counter-based, fa_ex_common.h: a lane makes one splitmix64 value per two of its elements),
+//   FEAT bit 2  sliding window: row i sees keys [i + coff - wl, i + coff + wr].  The workgroup walks only the tiles of its
+//               band; a wave computes the tiles of its own 32 rows (keys) and only helps to load the others, before
+//               and after its own (feed-only); edge tiles mask per element against a lower and an upper threshold.
+//               Without the bit the instantiations are the ones of the causal / unmasked kernels, unchanged.
 // Dense mask bytes are fetched with range-checked buffer loads (rows / bytes past the mask read as 0 = masked); when Nk, the
 // mask pointer and the (b,h) stride are multiples of 4 a lane of the query-on-the-lane kernels takes the 4 keys of a
 // register group with one dword load.  The block-sparse mask needs br, bc multiples of 32 here (a wave's 32 x 32 block
@@ -20,7 +24,7 @@ namespace fa {
 
 namespace {
 
-constexpr int kFeatMask = 1, kFeatDrop = 2;
+constexpr int kFeatMask = 1, kFeatDrop = 2, kFeatWindow = 4;
 
 // rc(i): row (or key) offset inside a 32-wide block of accumulator register i, before the 4 * (lane >> 5) term
 __device__ __forceinline__ constexpr int rc_of(int i) { return (i & 3) + 8 * (i >> 2); }
@@ -262,18 +266,36 @@ __global__ __launch_bounds__(512, 2) void exm_fwd_kernel(const uint16_t* __restr
     float m_run = -INFINITY, l_run = 0.f;
 
     // keys past the last row's diagonal are masked for every row of the tile (of the wave)
-    const int kend = p.causal ? max(0, min(nk, q0 + BM + p.coff)) : nk;
-    const int kend_w = p.causal ? max(0, min(nk, q0 + 32 * w + 32 + p.coff)) : nk;
+    constexpr bool WIN = (FEAT & kFeatWindow) != 0;
+    // window: the band's right edge takes the diagonal's place (wr = 0 under the causal mask), and keys left of the first
+    // row's left edge are masked for every row as well: tiles [t_lo, ntiles) for the workgroup, [t_lo_w, ntiles_w) per wave,
+    // both bounded by the last row < nq (a wave without one computes nothing)
+    const int kend = WIN ? max(0, min(nk, min(q0 + BM, nq) + p.coff + p.wr)) : (p.causal ? max(0, min(nk, q0 + BM + p.coff)) : nk);
+    const int kend_w = WIN ? (q0 + 32 * w < nq ? max(0, min(nk, min(q0 + 32 * w + 32, nq) + p.coff + p.wr)) : 0)
+                           : (p.causal ? max(0, min(nk, q0 + 32 * w + 32 + p.coff)) : nk);
     const int ntiles = (kend + BN - 1) / BN, ntiles_w = (kend_w + BN - 1) / BN;
-    LiveScan<true, BN> scan;
+    const int t_lo = WIN ? max(0, q0 + p.coff - p.wl) / BN : 0;
+    const int t_lo_w = WIN ? max(0, q0 + 32 * w + p.coff - p.wl) / BN : 0;
+    LiveScan<true, BN> scan;   // (tiles keep their absolute index: the scan's first probe is at t_lo)
     if (use_bm) scan.init(p, q0, min(q0 + BM, nq), 0, nk, ntiles, lane);
     auto next_live = [&](int t) { return use_bm ? scan.next(t) : t; };
     const int li = lane & 15, g16 = (lane >> 4) & 1, tq = li >> 2, tp = li & 3;
 
-    int t = next_live(0), cur = 0;
+    int t = next_live(t_lo), cur = 0;
     if (t < ntiles) stage(0, t * BN);
     dma_wait_all();
     __syncthreads();
+    if constexpr (WIN) {
+        // leading feed-only tiles: left of this wave's band, inside the workgroup's
+        while (t < min(t_lo_w, ntiles)) {
+            const int tn = next_live(t + 1);
+            if (tn < ntiles) stage(cur ^ 1, tn * BN);
+            dma_wait_all();
+            __syncthreads();
+            cur ^= 1;
+            t = tn;
+        }
+    }
     // two loops instead of an `if` inside one (a conditional accumulate makes hipcc carry the accumulators through
     // copies): tiles this wave computes, then the ones it only helps to load
     // Dense mask: its loads are ordinary VMEM loads, and VMEM returns in order — were the next tile's LDS-DMA issued
@@ -325,15 +347,25 @@ __global__ __launch_bounds__(512, 2) void exm_fwd_kernel(const uint16_t* __restr
                 }
             }
             // ---- causal diagonal / ragged last tile: key index of register i is k0 + 32 kb + 4 h + rc(i)
-            const bool need_mask = (p.causal && (k0 + BN - 1 > q0 + 32 * w + p.coff)) || (k0 + BN > nk);
+            const bool need_mask = WIN ? ((k0 + BN - 1 > q0 + 32 * w + p.coff + p.wr) || (k0 + BN > nk) ||
+                                          (k0 < q0 + 32 * w + 31 + p.coff - p.wl))   // + the band's left edge
+                                       : ((p.causal && (k0 + BN - 1 > q0 + 32 * w + p.coff)) || (k0 + BN > nk));
             if (need_mask) {
-                const int lim = p.causal ? min(qrow + p.coff, nk - 1) : nk - 1;   // last visible key of this lane's row
+                // last visible key of this lane's row
+                const int lim = WIN ? min(qrow + p.coff + p.wr, nk - 1) : (p.causal ? min(qrow + p.coff, nk - 1) : nk - 1);
 #pragma unroll
                 for (int kb = 0; kb < KB; ++kb) {
                     const int thr = lim - (k0 + 32 * kb + 4 * h);
+                    if constexpr (WIN) {
+                        const int thl = qrow + p.coff - p.wl - (k0 + 32 * kb + 4 * h);   // the row's first visible key
 #pragma unroll
-                    for (int i = 0; i < 16; ++i)
-                        if (rc_of(i) > thr) sacc[kb][i] = -INFINITY;
+                        for (int i = 0; i < 16; ++i)
+                            if (rc_of(i) > thr || rc_of(i) < thl) sacc[kb][i] = -INFINITY;
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < 16; ++i)
+                            if (rc_of(i) > thr) sacc[kb][i] = -INFINITY;
+                    }
                 }
             }
             if constexpr (FEAT & kFeatMask) {
@@ -512,11 +544,18 @@ __global__ __launch_bounds__(512, 2) void exm_dkdv_kernel(const uint16_t* __rest
         for (int i = 0; i < 16; ++i) { dka[t][i] = 0.f; dva[t][i] = 0.f; }
 
     // key j is visible from row j - coff on: earlier query tiles see none of this workgroup's (this wave's) keys
-    const int qs_first = p.causal ? (max(0, key0 - p.coff) / BQ) * BQ : 0;
-    const int ntile = qs_first < nq ? (nq - qs_first + BQ - 1) / BQ : 0;
-    const int it_first = p.causal ? max(0, kw0 - p.coff) / BQ - qs_first / BQ : 0;
+    constexpr bool WIN = (FEAT & kFeatWindow) != 0;
+    // window: key j is visible from row j - coff - wr to row j - coff + wl; rows past the last key's band see none of
+    // the workgroup's (query tiles [0, ntile)) or of this wave's keys (iterations [it_first, it_last) compute)
+    const int qs_first = WIN ? (max(0, key0 - p.coff - p.wr) / BQ) * BQ : (p.causal ? (max(0, key0 - p.coff) / BQ) * BQ : 0);
+    const int qend = WIN ? min(nq, min(key0 + BK, nk) - p.coff + p.wl) : nq;
+    const int ntile = qs_first < qend ? (qend - qs_first + BQ - 1) / BQ : 0;
+    const int it_first = WIN ? max(0, kw0 - p.coff - p.wr) / BQ - qs_first / BQ
+                             : (p.causal ? max(0, kw0 - p.coff) / BQ - qs_first / BQ : 0);
+    const int it_last = WIN ? (kw0 < nk ? min(ntile, (max(0, min(nq, min(kw0 + 32, nk) - p.coff + p.wl)) + BQ - 1) / BQ - qs_first / BQ) : 0)
+                            : ntile;
     LiveScan<false, BQ> scan;
-    if (use_bm) scan.init(p, key0, min(key0 + BK, nk), qs_first, nq, ntile, lane);
+    if (use_bm) scan.init(p, key0, min(key0 + BK, nk), qs_first, nq, ntile, lane);   // (window: over the band's tiles)
     auto next_live = [&](int it) { return use_bm ? scan.next(it) : it; };
     const int li = lane & 15, g16 = (lane >> 4) & 1, tq = li >> 2, tp = li & 3;
 
@@ -533,7 +572,7 @@ __global__ __launch_bounds__(512, 2) void exm_dkdv_kernel(const uint16_t* __rest
         cur ^= 1;
         it = itn;
     }
-    while (it < ntile) {
+    while (it < it_last) {
         const int itn = next_live(it + 1);
         if (itn < ntile) stage(cur ^ 1, qs_first + itn * BQ);
         const int qs = qs_first + it * BQ;
@@ -554,9 +593,13 @@ __global__ __launch_bounds__(512, 2) void exm_dkdv_kernel(const uint16_t* __rest
             }
             // a block of which this wave sees nothing is not computed (wave-uniform; see the forward kernel)
             if ((FEAT & kFeatMask) && !__any(vis != 0)) continue;
-            // masked: the row precedes the key's first visible row (causal), or the key lies past nk: rc(i) < thr
-            const bool need_mask = (p.causal && (kw0 + 31 - p.coff > rb0)) || (kw0 + 32 > nk);
-            const int thr = !need_mask ? -1 : (key >= nk ? 64 : (p.causal ? key - p.coff - rb0 - 4 * h : -1));
+            // masked: the row precedes the key's first visible row (causal), or the key lies past nk: rc(i) < thr;
+            // window: also the row follows the key's last visible row, rc(i) > thh
+            const bool need_mask = WIN ? ((kw0 + 31 - p.coff - p.wr > rb0) || (kw0 + 32 > nk) || (rb0 + 31 > kw0 - p.coff + p.wl))
+                                       : ((p.causal && (kw0 + 31 - p.coff > rb0)) || (kw0 + 32 > nk));
+            const int thr = WIN ? (!need_mask ? -1 : (key >= nk ? 64 : key - p.coff - p.wr - rb0 - 4 * h))
+                                : (!need_mask ? -1 : (key >= nk ? 64 : (p.causal ? key - p.coff - rb0 - 4 * h : -1)));
+            [[maybe_unused]] const int thh = WIN && need_mask ? key - p.coff + p.wl - rb0 - 4 * h : 64;
             int kofs = 32 * w * 2 * D;
             asm volatile("" : "+v"(kofs));
             u32x4 pp[2], sp[2];
@@ -585,6 +628,7 @@ __global__ __launch_bounds__(512, 2) void exm_dkdv_kernel(const uint16_t* __rest
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
                         bool dead = rc_of(i) < thr;
+                        if constexpr (WIN) dead = dead || rc_of(i) > thh;
                         if constexpr (FEAT & kFeatMask) dead = dead || !((vis >> i) & 1u);
                         sacc[i] = dead ? 0.f : __builtin_amdgcn_exp2f(sacc[i] * c_log2);
                     }
@@ -651,6 +695,17 @@ __global__ __launch_bounds__(512, 2) void exm_dkdv_kernel(const uint16_t* __rest
         __syncthreads();
         cur ^= 1;
         it = itn;
+    }
+    if constexpr (WIN) {
+        // trailing feed-only iterations: rows past this wave's keys' band, inside the workgroup's
+        while (it < ntile) {
+            const int itn = next_live(it + 1);
+            if (itn < ntile) stage(cur ^ 1, qs_first + itn * BQ);
+            dma_wait_all();
+            __syncthreads();
+            cur ^= 1;
+            it = itn;
+        }
     }
 
     if (key < nk) {
@@ -723,18 +778,32 @@ __global__ __launch_bounds__(512, 2) void exm_dq_kernel(const uint16_t* __restri
 #pragma unroll
         for (int i = 0; i < 16; ++i) dqa[t][i] = 0.f;
 
-    const int kend = p.causal ? max(0, min(nk, q0 + BM + p.coff)) : nk;
-    const int kend_w = p.causal ? max(0, min(nk, q0 + 32 * w + 32 + p.coff)) : nk;
+    constexpr bool WIN = (FEAT & kFeatWindow) != 0;   // (the tile ranges of the forward kernel)
+    const int kend = WIN ? max(0, min(nk, min(q0 + BM, nq) + p.coff + p.wr)) : (p.causal ? max(0, min(nk, q0 + BM + p.coff)) : nk);
+    const int kend_w = WIN ? (q0 + 32 * w < nq ? max(0, min(nk, min(q0 + 32 * w + 32, nq) + p.coff + p.wr)) : 0)
+                           : (p.causal ? max(0, min(nk, q0 + 32 * w + 32 + p.coff)) : nk);
     const int ntiles = (kend + BN - 1) / BN, ntiles_w = (kend_w + BN - 1) / BN;
+    const int t_lo = WIN ? max(0, q0 + p.coff - p.wl) / BN : 0;
+    const int t_lo_w = WIN ? max(0, q0 + 32 * w + p.coff - p.wl) / BN : 0;
     LiveScan<true, BN> scan;
     if (use_bm) scan.init(p, q0, min(q0 + BM, nq), 0, nk, ntiles, lane);
     auto next_live = [&](int t) { return use_bm ? scan.next(t) : t; };
     const int li = lane & 15, g16 = (lane >> 4) & 1, tq = li >> 2, tp = li & 3;
 
-    int t = next_live(0), cur = 0;
+    int t = next_live(t_lo), cur = 0;
     if (t < ntiles) stage(0, t * BN);
     dma_wait_all();
     __syncthreads();
+    if constexpr (WIN) {
+        while (t < min(t_lo_w, ntiles)) {   // leading feed-only tiles
+            const int tn = next_live(t + 1);
+            if (tn < ntiles) stage(cur ^ 1, tn * BN);
+            dma_wait_all();
+            __syncthreads();
+            cur ^= 1;
+            t = tn;
+        }
+    }
     const bool late_stage = (FEAT & kFeatMask) && msk.on;   // see the forward kernel
     while (t < ntiles_w) {
         const int tn = next_live(t + 1);
@@ -774,9 +843,12 @@ __global__ __launch_bounds__(512, 2) void exm_dq_kernel(const uint16_t* __restri
                 const s16x8 va = *reinterpret_cast<const s16x8*>(Vt + off);
                 pacc = mfma32<Tag>(va, of[ks], pacc);
             }
-            const bool need_mask = (p.causal && (k0 + 32 * kb + 31 > q0 + 32 * w + p.coff)) || (k0 + 32 * kb + 32 > nk);
-            const int lim = p.causal ? min(qrow + p.coff, nk - 1) : nk - 1;
+            const bool need_mask = WIN ? ((k0 + 32 * kb + 31 > q0 + 32 * w + p.coff + p.wr) || (k0 + 32 * kb + 32 > nk) ||
+                                          (k0 + 32 * kb < q0 + 32 * w + 31 + p.coff - p.wl))
+                                       : ((p.causal && (k0 + 32 * kb + 31 > q0 + 32 * w + p.coff)) || (k0 + 32 * kb + 32 > nk));
+            const int lim = WIN ? min(qrow + p.coff + p.wr, nk - 1) : (p.causal ? min(qrow + p.coff, nk - 1) : nk - 1);
             const int thr = need_mask ? lim - (k0 + 32 * kb + 4 * h) : 64;
+            [[maybe_unused]] const int thl = WIN && need_mask ? qrow + p.coff - p.wl - (k0 + 32 * kb + 4 * h) : -64;
             // wave-uniform (not in the dropout build: two copies of its selects cost registers it does not have)
             const bool plain = !(FEAT & kFeatDrop) && !need_mask && (!(FEAT & kFeatMask) || !__any(vis != 0xffffu));
             if (plain) {
@@ -790,6 +862,7 @@ __global__ __launch_bounds__(512, 2) void exm_dq_kernel(const uint16_t* __restri
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     bool dead = rc_of(i) > thr;
+                    if constexpr (WIN) dead = dead || rc_of(i) < thl;
                     if constexpr (FEAT & kFeatMask) dead = dead || !((vis >> i) & 1u);
                     float dpv = pacc[i];
                     if constexpr (FEAT & kFeatDrop) dpv = (((kp >> i) & 1u) ? dpv * p.keep_scale : 0.f) + nd;
@@ -909,6 +982,11 @@ static hipError_t exm_bwd_t(const ExArgs& a, hipStream_t st) {
 template <typename Tag, int D>
 static hipError_t exm_by_feat(const ExArgs& a, bool backward, hipStream_t st) {
     const bool masks = a.mask || a.block_mask, drop = a.dropout_p > 0.0;
+    if (ex_windowed(a)) {
+        if (drop) return backward ? exm_bwd_t<Tag, D, 7>(a, st) : exm_fwd_t<Tag, D, 7>(a, st);
+        if (masks) return backward ? exm_bwd_t<Tag, D, 5>(a, st) : exm_fwd_t<Tag, D, 5>(a, st);
+        return backward ? exm_bwd_t<Tag, D, 4>(a, st) : exm_fwd_t<Tag, D, 4>(a, st);
+    }
     if (drop) return backward ? exm_bwd_t<Tag, D, 3>(a, st) : exm_fwd_t<Tag, D, 3>(a, st);
     if (masks) return backward ? exm_bwd_t<Tag, D, 1>(a, st) : exm_fwd_t<Tag, D, 1>(a, st);
     return backward ? exm_bwd_t<Tag, D, 0>(a, st) : exm_fwd_t<Tag, D, 0>(a, st);

@@ -136,7 +136,13 @@ struct ExArgs {
     void* workspace;              // backward: ex_backward_workspace_bytes
     size_t workspace_bytes = 0;   // what the caller really gave (more than the minimum lets plain calls hand dS over)
     int64_t kv_group = 1;         // query heads per K/V head: k, v, dk, dv hold bh / kv_group units (grouped-query attention)
+    // sliding window, canonicalised by the C layer (fa_capi.hip: window_canon): key j is visible to row i only if
+    // j >= i + (nk - nq) - window_left and j <= i + (nk - nq) + window_right; -1 = unbounded on that side.  After
+    // canonicalisation a bound that is not -1 bounds something, and causal != 0 comes with window_right = -1.
+    int64_t window_left = -1, window_right = -1;
 };
+// does the call carry a window that bounds something (canonicalised: any bound that is not -1)?
+inline bool ex_windowed(const ExArgs& a) { return a.window_left >= 0 || a.window_right >= 0; }
 hipError_t launch_ex(const ExArgs& a, bool backward, hipStream_t st);
 bool ex_mfma_supported(const ExArgs& a);
 hipError_t launch_ex_mfma(const ExArgs& a, bool backward, hipStream_t st);

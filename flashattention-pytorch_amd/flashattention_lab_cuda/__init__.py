@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import operator
 
 import torch
 
@@ -36,7 +37,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_set_kernel_mode", "fa_set_option", "fa_debug_trace_buffer", "fa_device_is_gfx950", "fa_profile_enable", "fa_profile_report",
     "fa_ex_forward", "fa_ex_backward", "fa_ex_backward_workspace_bytes", "fa_ex_backward_workspace_bytes_fast",
     "fa_ex_forward_grouped", "fa_ex_backward_grouped", "fa_ex_backward_workspace_bytes_grouped",
-    "fa_ex_backward_workspace_bytes_fast_grouped",
+    "fa_ex_backward_workspace_bytes_fast_grouped", "fa_ex_forward_window", "fa_ex_backward_window",
 )
 
 
@@ -102,6 +103,13 @@ def _load_library() -> ctypes.CDLL:
     lib.fa_ex_backward_workspace_bytes_grouped.restype = sz
     lib.fa_ex_backward_workspace_bytes_fast_grouped.argtypes = [i64, i64, i64, i64, i64, ci, ci, ci]
     lib.fa_ex_backward_workspace_bytes_fast_grouped.restype = sz
+    # sliding window: the grouped arguments with window_left, window_right right after causal
+    lib.fa_ex_forward_window.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, ci, i64, i64, dbl, vp, i64, vp, i64, i64, dbl,
+                                         u64, vp]
+    lib.fa_ex_forward_window.restype = ci
+    lib.fa_ex_backward_window.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, ci, i64, i64, dbl, vp, i64, vp,
+                                          i64, i64, dbl, u64, vp, sz, vp]
+    lib.fa_ex_backward_window.restype = ci
     return lib
 
 
@@ -320,10 +328,42 @@ def _ex_common(who, q, k, v, mask, block_mask, br, bc):
     return bh, nq, nk, d, _DTYPE_CODE[q.dtype], mask, mptr, mstride, block_mask, bptr, kv_group
 
 
-def ex_forward(q, k, v, causal, softmax_scale, mask=None, block_mask=None, br=128, bc=128, dropout_p=0.0, seed=0):
+def window_arg(who, window):
+    """`window` as (left, right) ints, -1 = unbounded on that side (FlashAttention-2's window_size); the C layer's error text
+    for anything else."""
+    try:
+        left, right = window
+    except (TypeError, ValueError):
+        raise RuntimeError(f"{who}: window must be a pair (left, right) of ints, got {window!r}") from None
+    try:
+        if isinstance(left, bool) or isinstance(right, bool):
+            raise TypeError
+        left, right = operator.index(left), operator.index(right)
+    except TypeError:
+        raise RuntimeError(f"{who}: window must be a pair (left, right) of ints, got {window!r}") from None
+    if left < -1 or right < -1:
+        raise RuntimeError(f"{who}: window ({left}, {right}): each bound must be >= 0, or -1 for unbounded")
+    return left, right
+
+
+def window_effective(nq, nk, causal, window) -> bool:
+    """Does `window` bound anything once the C layer has canonicalised it (fa_capi.hip: window_canon)?"""
+    left, right = window
+    if left >= nk - 1:
+        left = -1
+    if right >= nq - 1 or (causal and right >= 0):
+        right = -1
+    if not causal and right == 0:
+        right = -1   # (the causal mask)
+    return left >= 0 or right >= 0
+
+
+def ex_forward(q, k, v, causal, softmax_scale, mask=None, block_mask=None, br=128, bc=128, dropout_p=0.0, seed=0, window=(-1, -1)):
     """(o, lse) of attention with Nq != Nk (causal aligned bottom-right), dense mask (0 = masked), block-sparse mask
     (0 = tile skipped) and dropout; see include/fa_mi355x.h.  k and v with BH / g units (g query heads per K/V head) make
-    it grouped-query attention."""
+    it grouped-query attention.  window = (left, right): key j is visible to row i only within
+    [i + Nk - Nq - left, i + Nk - Nq + right], -1 = unbounded (fa_ex_forward_window)."""
+    wl, wr = window_arg("ex_forward", window)
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     bh, nq, nk, d, code, mask, mptr, mstride, block_mask, bptr, g = _ex_common("ex_forward", q, k, v, mask, block_mask, br, bc)
     with torch.cuda.device(q.device):
@@ -332,22 +372,27 @@ def ex_forward(q, k, v, causal, softmax_scale, mask=None, block_mask=None, br=12
         ptrs = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr())
         rest = (nq, nk, d, code, int(bool(causal)), float(softmax_scale), mptr, mstride, bptr, int(br), int(bc), float(dropout_p),
                 int(seed) & (2 ** 64 - 1), _stream_ptr(q.device))
-        if g > 1:
+        if (wl, wr) != (-1, -1):
+            _check(_lib.fa_ex_forward_window(*ptrs, bh, g, *rest[:5], wl, wr, *rest[5:]))
+        elif g > 1:
             _check(_lib.fa_ex_forward_grouped(*ptrs, bh, g, *rest))
         else:
             _check(_lib.fa_ex_forward(*ptrs, bh, *rest))
     return o, lse
 
 
-def ex_backward(q, k, v, o, do_, lse, causal, softmax_scale, mask=None, block_mask=None, br=128, bc=128, dropout_p=0.0, seed=0):
+def ex_backward(q, k, v, o, do_, lse, causal, softmax_scale, mask=None, block_mask=None, br=128, bc=128, dropout_p=0.0, seed=0,
+                window=(-1, -1)):
+    wl, wr = window_arg("ex_backward", window)
     q, k, v, o, do_, lse = (t.contiguous() for t in (q, k, v, o, do_, lse))
     bh, nq, nk, d, code, mask, mptr, mstride, block_mask, bptr, g = _ex_common("ex_backward", q, k, v, mask, block_mask, br, bc)
     if o.shape != q.shape or do_.shape != q.shape or lse.shape != (bh, nq) or lse.dtype != torch.float32:
         raise RuntimeError("ex_backward: o, do must be (BH, Nq, d) and lse (BH, Nq) float32")
     with torch.cuda.device(q.device):
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        extras = int(mask is not None or block_mask is not None or dropout_p > 0.0)
-        if g > 1:   # (+ the per-query-head dK / dV partials the library sums over each group)
+        extras = int(mask is not None or block_mask is not None or dropout_p > 0.0 or
+                     window_effective(nq, nk, bool(causal), (wl, wr)))   # (the dS hand-over does not serve a window)
+        if g > 1 or (wl, wr) != (-1, -1):   # (+ the per-query-head dK / dV partials the library sums over each group)
             small = int(_lib.fa_ex_backward_workspace_bytes_grouped(bh, g, nq, nk, d, code))
             fast = int(_lib.fa_ex_backward_workspace_bytes_fast_grouped(bh, g, nq, nk, d, code, int(bool(causal)), extras))
         else:
@@ -362,7 +407,9 @@ def ex_backward(q, k, v, o, do_, lse, causal, softmax_scale, mask=None, block_ma
                 dv.data_ptr())
         rest = (nq, nk, d, code, int(bool(causal)), float(softmax_scale), mptr, mstride, bptr, int(br), int(bc), float(dropout_p),
                 int(seed) & (2 ** 64 - 1), ws.data_ptr(), nbytes, _stream_ptr(q.device))
-        if g > 1:
+        if (wl, wr) != (-1, -1):
+            _check(_lib.fa_ex_backward_window(*ptrs, bh, g, *rest[:5], wl, wr, *rest[5:]))
+        elif g > 1:
             _check(_lib.fa_ex_backward_grouped(*ptrs, bh, g, *rest))
         else:
             _check(_lib.fa_ex_backward(*ptrs, bh, *rest))

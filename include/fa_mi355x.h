@@ -171,6 +171,37 @@ size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int6
 size_t fa_ex_backward_workspace_bytes_fast_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype,
                                                    int causal, int extras);
 
+/* --- Sliding-window (local) attention: the fa_ex_*_grouped calls with window_left, window_right right after causal
+ * (FlashAttention-2's window_size).  In the causal flag's coordinates (bottom-right aligned, coff = Nk - Nq) key j is visible to
+ * query row i iff
+ *     (window_left  < 0  or  j >= i + coff - window_left)   and   (window_right < 0  or  j <= i + coff + window_right)
+ *     and (causal == 0 or j <= i + coff), the dense mask, the block-sparse mask and the row / key ranges, as fa_ex_*.
+ * -1 = unbounded on that side; any other negative bound is FA_ERR_INVALID_ARGUMENT (checked before any HIP call).  Dropout
+ * counters, lse and the GQA indexing are those of the call without a window.  A row without a visible key gives o = 0,
+ * lse = -inf, dq = 0, a key that no row sees dk = dv = 0.  The bounds are canonicalised first: a left bound >= Nk - 1 or a right
+ * bound >= Nq - 1 bounds nothing and is dropped, so is a right bound >= 0 under the causal mask, and window_right = 0 without it
+ * is the causal mask.  What is left of a window that bounds nothing is exactly the fa_ex_*_grouped call (kv_group = 1: the
+ * fa_ex_* call): the same kernels, the same bits.  A window that bounds something runs on the extended kernels only — 16-bit
+ * MFMA where fa_ex_* would take them, exact f32 otherwise — which visit the key (query) tiles of each row's (key's) band and
+ * no others: O(N w) work instead of O(N^2).  The backward's workspace is fa_ex_backward_workspace_bytes_grouped: a window adds
+ * no storage, and the dS hand-over does not serve it — pass extras = 1 to fa_ex_backward_workspace_bytes_fast_grouped when the
+ * window bounds something. */
+int fa_ex_forward_window(const void* q, const void* k, const void* v, void* o, float* lse,
+                         int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype,
+                         int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                         const uint8_t* mask, int64_t mask_bh_stride,
+                         const uint8_t* block_mask, int64_t br, int64_t bc,
+                         double dropout_p, uint64_t dropout_seed, void* stream);
+
+int fa_ex_backward_window(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse,
+                          void* dq, void* dk, void* dv,
+                          int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype,
+                          int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                          const uint8_t* mask, int64_t mask_bh_stride,
+                          const uint8_t* block_mask, int64_t br, int64_t bc,
+                          double dropout_p, uint64_t dropout_seed,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* --- support entry points (no reference counterpart: the reference allocates inside the callee) --- */
 /* bytes for the CURRENT kernel mode: two float row constants per query row (+ an fp32 dQ scratch of bh*n*d floats in
  * FA_MODE_BWD_ATOMIC only); ask again after changing the mode */

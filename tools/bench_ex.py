@@ -10,6 +10,13 @@ route (K and V expanded by torch, autograd sums their gradients); forward and ba
 autograd step (flash_attention_ex forward + backward) for all three, and the group-sum kernel's share of the backward.
 
     python tools/bench_ex.py --kv-heads 8,1 [--batch 8] [--q-heads 32] [--nq 4096] [--head-dim 128]
+
+Sliding window (--window L,R; -1 = unbounded, bottom-right aligned as the causal flag; --causal for a causal window): three calls
+on the same kernel family (--paths, one of them; default mfma), timed alternately in one process — the native window
+(fa_ex_*_window), the same window as one shared dense mask, and the full causal call — forward and backward, with visible-pair
+TFLOP/s (4 / 10 x visible pairs x d, the pairs counted from the shapes).
+
+    python tools/bench_ex.py --window 1024,0 --causal [--bh 32] [--nq 16384] [--nk 16384] [--head-dim 128] [--rounds 3]
 """
 import argparse
 import json
@@ -45,9 +52,14 @@ def main():
     ap.add_argument("--kv-heads", default="", help="comma-separated K/V head counts: time grouped-query attention instead")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--q-heads", type=int, default=32)
+    ap.add_argument("--window", default="", help="L,R: time a sliding window against its dense mask and the causal call")
+    ap.add_argument("--causal", action="store_true", help="(--window) the causal flag with the window")
+    ap.add_argument("--rounds", type=int, default=3, help="(--window) alternations of the three calls")
     args = ap.parse_args()
     if args.kv_heads:
         return bench_gqa(args)
+    if args.window:
+        return bench_window(args)
     dt = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[args.dtype]
     bh, nq, nk, d = args.bh, args.nq, args.nk, args.head_dim
     g = torch.Generator(device="cuda").manual_seed(0)
@@ -140,6 +152,76 @@ def bench_gqa(args):
             rows.append(row)
             del leaves, full
     print(json.dumps(dict(shape=dict(batch=b, q_heads=hq, n=n, d=d, dtype=args.dtype), rows=rows), indent=1))
+
+
+def window_pairs(nq, nk, causal, wl, wr):
+    """Visible (query, key) pairs of one (b,h) under the window, counted row by row from the shapes."""
+    c, total = nk - nq, 0
+    for i in range(nq):
+        lo = 0 if wl < 0 else max(0, i + c - wl)
+        hi = nk - 1 if wr < 0 else min(nk - 1, i + c + wr)
+        if causal:
+            hi = min(hi, i + c)
+        total += max(0, hi - lo + 1)
+    return total
+
+
+def bench_window(args):
+    dt = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[args.dtype]
+    bh, nq, nk, d = args.bh, args.nq, args.nk, args.head_dim
+    wl, wr = (int(x) for x in args.window.split(","))
+    path = args.paths.split(",")[0]
+    scale = d ** -0.5
+    g = torch.Generator(device="cuda").manual_seed(0)
+    q = torch.randn((bh, nq, d), device="cuda", dtype=dt, generator=g)
+    k, v = (torch.randn((bh, nk, d), device="cuda", dtype=dt, generator=g) for _ in range(2))
+    do = torch.randn((bh, nq, d), device="cuda", dtype=dt, generator=g)
+    qi, kj = torch.arange(nq, device="cuda").unsqueeze(1), torch.arange(nk, device="cuda").unsqueeze(0)
+    vis = torch.ones((nq, nk), dtype=torch.bool, device="cuda")
+    if wl >= 0:
+        vis &= kj >= qi + (nk - nq) - wl
+    if wr >= 0:
+        vis &= kj <= qi + (nk - nq) + wr
+    if args.causal:
+        vis &= kj <= qi + (nk - nq)
+    calls = {
+        "window": (args.causal, dict(window=(wl, wr))),
+        "dense_mask": (False, dict(mask=vis.to(torch.uint8))),
+        "causal": (True, dict()),
+    }
+    pairs = {"window": window_pairs(nq, nk, args.causal, wl, wr), "causal": window_pairs(nq, nk, True, -1, -1)}
+    pairs["dense_mask"] = pairs["window"]
+    assert pairs["window"] == int(vis.sum().item())
+    ext.set_option("ex_path", {"mfma": 3, "exact": 1}.get(path, 0))
+    times = {name: ([], []) for name in calls}
+    try:
+        outs = {}
+        for name, (causal, kw) in calls.items():
+            outs[name] = ext.ex_forward(q, k, v, causal, scale, **kw)
+        for _ in range(args.rounds):
+            for name, (causal, kw) in calls.items():
+                o, lse = outs[name]
+                times[name][0].append(timed(lambda: ext.ex_forward(q, k, v, causal, scale, **kw), args.iters))
+                times[name][1].append(timed(lambda: ext.ex_backward(q, k, v, o, do, lse, causal, scale, **kw), args.iters))
+    finally:
+        ext.set_option("ex_path", 0)
+    rows = []
+    for name in calls:
+        tf, tb = sorted(times[name][0])[len(times[name][0]) // 2], sorted(times[name][1])[len(times[name][1]) // 2]
+        p = bh * pairs[name]
+        rows.append(dict(call=name, visible_pairs_per_bh=pairs[name], fwd_ms=round(tf, 3), bwd_ms=round(tb, 3),
+                         fwd_bwd_ms=round(tf + tb, 3), fwd_tflops=round(4 * p * d / tf / 1e9, 1),
+                         bwd_tflops=round(10 * p * d / tb / 1e9, 1), fwd_ms_all=[round(x, 3) for x in times[name][0]],
+                         bwd_ms_all=[round(x, 3) for x in times[name][1]]))
+    by = {r["call"]: r for r in rows}
+    summary = dict(
+        window_over_causal_time=round(by["window"]["fwd_bwd_ms"] / by["causal"]["fwd_bwd_ms"], 3),
+        dense_mask_over_window_time=round(by["dense_mask"]["fwd_bwd_ms"] / by["window"]["fwd_bwd_ms"], 2),
+        window_over_causal_pairs=round(pairs["window"] / pairs["causal"], 4),
+        window_over_causal_pair_rate=round((pairs["window"] / (by["window"]["fwd_bwd_ms"])) /
+                                           (pairs["causal"] / by["causal"]["fwd_bwd_ms"]), 3))
+    print(json.dumps(dict(shape=dict(bh=bh, nq=nq, nk=nk, d=d, dtype=args.dtype, window=[wl, wr], causal=args.causal,
+                                     kernels=path, iters=args.iters, rounds=args.rounds), rows=rows, summary=summary), indent=1))
 
 
 if __name__ == "__main__":
