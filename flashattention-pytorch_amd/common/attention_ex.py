@@ -119,3 +119,40 @@ def flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, bloc
         br, bc = min(br, nq), min(bc, nk)         # Br = min(block_size, q_len), Bc = min(block_size, kv_len)  (:100-101)
     o = _FlashAttnExFn.apply(q3, k3, v3, bool(causal), scale, m, block_sparse_mask, br, bc, float(dropout_p), int(seed), window)
     return o.reshape(q.shape) if four_d else o
+
+
+class _FlashAttnVarlenFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, cu_q, cu_k, max_q, max_k, dropout_p, scale, causal, window, seed):
+        import flashattention_lab_cuda as ext
+
+        o, lse = ext.ex_varlen_forward(q, k, v, cu_q, cu_k, max_q, max_k, causal, scale, dropout_p, seed, window=window)
+        ctx.save_for_backward(q, k, v, o, lse, cu_q, cu_k)
+        ctx.args = (max_q, max_k, dropout_p, scale, causal, window, seed)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        import flashattention_lab_cuda as ext
+
+        q, k, v, o, lse, cu_q, cu_k = ctx.saved_tensors
+        max_q, max_k, dropout_p, scale, causal, window, seed = ctx.args
+        dq, dk, dv = ext.ex_varlen_backward(q, k, v, o, do.contiguous(), lse, cu_q, cu_k, max_q, max_k, causal, scale, dropout_p, seed,
+                                            window=window)
+        return (dq, dk, dv) + (None,) * 9
+
+
+def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p=0.0, softmax_scale=None,
+                           causal=False, window_size=(-1, -1), seed=0):
+    """FlashAttention-2's flash_attn_varlen_func over packed sequences, differentiable: q (total_q, H_q, d), k and v
+    (total_k, H_kv, d) with H_q % H_kv == 0 (GQA), token-strided views (qkv.unbind(1) of a (total, 3, H, d) projection) taken
+    without a copy; cu_seqlens_* int32 (batch + 1,) device offsets.  Attention stays inside each sequence; `causal` is
+    bottom-right aligned per sequence and `window_size` has flash_attention_ex's meaning in each sequence's coordinates.
+    Returns o (total_q, H_q, d); the gradients of k and v come back in their shapes.  The dropout mask is that of the padded
+    (batch * H_q, max_seqlen_q, max_seqlen_k) call (include/fa_mi355x.h), so it depends on the max_seqlen_q passed."""
+    window = _window_size(window_size)
+    if not q.is_cuda:
+        raise RuntimeError("Inputs must be CUDA tensors")
+    scale = (1.0 / math.sqrt(q.shape[-1])) if softmax_scale is None else float(softmax_scale)
+    return _FlashAttnVarlenFn.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), float(dropout_p), scale,
+                                    bool(causal), window, int(seed))

@@ -504,6 +504,135 @@ int fa_ex_backward_window(const void* q, const void* k, const void* v, const voi
                             workspace, workspace_bytes, stream);
 }
 
+// ---- variable-length (packed) sequences: see include/fa_mi355x.h
+// Everything that can be checked without reading cu_seqlens (which would take a synchronise), before any HIP call.
+static int varlen_check(const char* who, const int32_t* cu_q, const int32_t* cu_k, int64_t batch, int64_t hq, int64_t hkv, int64_t total_q,
+                        int64_t total_k, int64_t max_q, int64_t max_k, int64_t d, int dtype, int64_t sq, int64_t sk, int64_t sv,
+                        int64_t wl, int64_t wr, double scale, double p) {
+    if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_F16 && dtype != FA_DTYPE_BF16)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: unknown dtype code %d", who, dtype);
+    if (batch < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch must be >= 1 (got %lld)", who, (long long)batch);
+    if (hq < 1 || hkv < 1 || hq % hkv != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads_q=%lld must be a positive multiple of heads_kv=%lld", who, (long long)hq, (long long)hkv);
+    if (d <= 0 || total_q < 0 || total_k < 0 || max_q < 0 || max_k < 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: bad shape (d=%lld, total_q=%lld, total_k=%lld, max_seqlen_q=%lld, max_seqlen_k=%lld)", who,
+                    (long long)d, (long long)total_q, (long long)total_k, (long long)max_q, (long long)max_k);
+    if (sq < hq * d || sk < hkv * d || sv < hkv * d)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: token strides (%lld, %lld, %lld) must be >= heads * d (%lld, %lld)", who, (long long)sq,
+                    (long long)sk, (long long)sv, (long long)(hq * d), (long long)(hkv * d));
+    if ((total_q > 0 && !cu_q) || (total_k > 0 && !cu_k)) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null cu_seqlens", who);
+    if (wl < -1 || wr < -1)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: window (%lld, %lld): each bound must be >= 0, or -1 for unbounded", who,
+                    (long long)wl, (long long)wr);
+    if (!(scale == scale)) return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale is NaN", who);
+    if (!(p >= 0.0 && p < 1.0)) return fail(FA_ERR_INVALID_ARGUMENT, "%s: dropout_p must lie in [0, 1)", who);
+    if (batch > ((int64_t)1 << 31) || hq > ((int64_t)1 << 31) || batch * hq * ((max_q + 1) / 2) >= ((int64_t)1 << 32))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch * heads_q * ceil(max_seqlen_q / 2) must stay below 2^32 (dropout counters)", who);
+    if (d > 256) return fail(FA_ERR_UNSUPPORTED, "%s: head_dim %lld > 256 is not supported", who, (long long)d);
+    const int64_t lim = (int64_t)1 << 31;
+    if (max_q > (int64_t)1 << 24 || max_k > (int64_t)1 << 24 || total_q >= lim || total_k >= lim || sq >= lim || sk >= lim || sv >= lim ||
+        hq * d >= lim || batch * hq * ((max_q + 15) / 16) >= lim || batch * hq * ((max_k + 15) / 16) >= lim ||
+        (total_q + 15) / 16 * hq >= ((int64_t)1 << 32))
+        return fail(FA_ERR_UNSUPPORTED, "%s: problem too large for one launch", who);
+    return FA_OK;
+}
+
+static fa::ExArgs varlen_args(const int32_t* cu_q, const int32_t* cu_k, int64_t batch, int64_t hq, int64_t hkv, int64_t total_q, int64_t total_k,
+                              int64_t max_q, int64_t max_k, int64_t d, int dtype, int64_t sq, int64_t sk, int64_t sv, int causal, int64_t wl,
+                              int64_t wr, double scale, double p, uint64_t seed) {
+    fa::ExArgs a{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, batch * hq, max_q, max_k, d, dtype,
+                 causal ? 1 : 0, (float)scale, nullptr, 0, nullptr, 0, 0, p, seed, nullptr};
+    a.kv_group = hq / hkv;
+    a.window_left = wl;
+    a.window_right = wr;
+    a.cu_q = cu_q;
+    a.cu_k = cu_k;
+    a.heads_q = hq;
+    a.total_q = total_q;
+    a.total_k = total_k;
+    a.stride_q = sq;
+    a.stride_k = sk;
+    a.stride_v = sv;
+    return a;
+}
+
+int fa_ex_forward_varlen(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
+                         const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k,
+                         int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride,
+                         int64_t v_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale, double dropout_p,
+                         uint64_t dropout_seed, void* stream) {
+    const char* who = "fa_ex_forward_varlen";
+    int rc = varlen_check(who, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype,
+                          q_stride, k_stride, v_stride, window_left, window_right, softmax_scale, dropout_p);
+    if (rc != FA_OK) return rc;
+    if ((rc = window_canon(who, max_seqlen_q, max_seqlen_k, causal, window_left, window_right)) != FA_OK) return rc;
+    if (total_q == 0 || max_seqlen_q == 0) return FA_OK;   // no query row in any sequence
+    if (!q || !o || !lse || (total_k > 0 && (!k || !v))) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (total_k == 0 || max_seqlen_k == 0) {   // no key in any sequence: o = 0, lse = -inf
+        hipError_t e = hipMemsetAsync(o, 0, (size_t)total_q * heads_q * d * (dtype == FA_DTYPE_F32 ? 4 : 2), st);
+        if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lse), (int)0xFF800000u, (size_t)heads_q * total_q, st);
+        if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
+        return FA_OK;
+    }
+    fa::ExArgs a = varlen_args(cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype,
+                               q_stride, k_stride, v_stride, causal, window_left, window_right, softmax_scale, dropout_p, dropout_seed);
+    a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse;
+    hipError_t e = fa::launch_ex(a, false, st);
+    if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
+    return FA_OK;
+}
+
+size_t fa_ex_backward_workspace_bytes_varlen(int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t d, int dtype) {
+    size_t need = fa_ex_backward_workspace_bytes(heads_q, total_q, total_k, d, dtype);   // the row constants, (heads_q, total_q)
+    if (heads_kv > 0 && heads_q > heads_kv && total_q > 0 && total_k > 0 && d > 0)
+        need += 2 * fa::kv_partial_bytes(total_k * heads_q, 1, d, dtype);              // + the per-query-head dK / dV partials
+    return need;
+}
+
+int fa_ex_backward_varlen(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
+                          void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q,
+                          int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d,
+                          int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride, int causal, int64_t window_left,
+                          int64_t window_right, double softmax_scale, double dropout_p, uint64_t dropout_seed, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    const char* who = "fa_ex_backward_varlen";
+    int rc = varlen_check(who, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype,
+                          q_stride, k_stride, v_stride, window_left, window_right, softmax_scale, dropout_p);
+    if (rc != FA_OK) return rc;
+    if ((rc = window_canon(who, max_seqlen_q, max_seqlen_k, causal, window_left, window_right)) != FA_OK) return rc;
+    const bool no_q = total_q == 0 || max_seqlen_q == 0, no_k = total_k == 0 || max_seqlen_k == 0;
+    if (no_q && no_k) return FA_OK;
+    if (no_q || no_k) {   // one side empty in every sequence: the gradients of the other side are sums over nothing
+        const size_t es = dtype == FA_DTYPE_F32 ? 4 : 2;
+        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+        hipError_t e = hipSuccess;
+        if (no_q) {
+            if (!dk || !dv) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+            e = hipMemsetAsync(dk, 0, (size_t)total_k * heads_kv * d * es, st);
+            if (e == hipSuccess) e = hipMemsetAsync(dv, 0, (size_t)total_k * heads_kv * d * es, st);
+        } else {
+            if (!dq) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+            e = hipMemsetAsync(dq, 0, (size_t)total_q * heads_q * d * es, st);
+        }
+        if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
+        return FA_OK;
+    }
+    if (!q || !k || !v || !o || !do_ || !lse || !dq || !dk || !dv) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    const size_t need = fa_ex_backward_workspace_bytes_varlen(heads_q, heads_kv, total_q, total_k, d, dtype);
+    if (!workspace || workspace_bytes < need)
+        return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
+    fa::ExArgs a = varlen_args(cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype,
+                               q_stride, k_stride, v_stride, causal, window_left, window_right, softmax_scale, dropout_p, dropout_seed);
+    a.q = q; a.k = k; a.v = v; a.o = const_cast<void*>(o); a.lse = const_cast<float*>(lse); a.dout = do_;
+    a.dq = dq; a.dk = dk; a.dv = dv;
+    a.workspace = workspace;
+    a.workspace_bytes = workspace_bytes;
+    hipError_t e = fa::launch_ex(a, true, reinterpret_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
+    return FA_OK;
+}
+
 size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {
     return ex_bwd_ws_grouped(bh, kv_group, nq, nk, d, dtype);
 }

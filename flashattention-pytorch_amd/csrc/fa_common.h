@@ -245,16 +245,20 @@ __device__ __forceinline__ s16x8 buf_load_frag(buf_rsrc_t rsrc, int off) {
 // absent); tiles and MFMA shapes stay D wide and the missing chunks are requested at kOobOff, an offset the buffer
 // range check rejects, so they arrive as zeros like the rows past the tensor's end.  dr == D folds to the plain form.
 constexpr int kOobOff = (int)0x80000000u;
-__device__ __forceinline__ int frag_off(int row, int col, int dr, bool pad) {
-    return (pad && col >= dr) ? kOobOff : (row * dr + col) * 2;
+// STRIDED (these helpers and dma_stage_tile, store_rows_via_lds): the rows are `stride` elements apart instead of dr — the token
+// stride of a packed (varlen) tensor, one head's row r at r * stride; dr stays the column bound.  A template flag, so that the
+// callers without it compile to what they did before the argument existed.
+template <bool STRIDED = false>
+__device__ __forceinline__ int frag_off(int row, int col, int dr, bool pad, int stride = 0) {
+    return (pad && col >= dr) ? kOobOff : (row * (STRIDED ? stride : dr) + col) * 2;
 }
-template <int D>
-__device__ __forceinline__ int dma_lane_voff(int lane, int w, int dr = D) {
+template <int D, bool STRIDED = false>
+__device__ __forceinline__ int dma_lane_voff(int lane, int w, int dr = D, int stride = 0) {
     constexpr int RPP = 512 / D, CPR = D / 8;
     const int rl = lane / CPR, slot = lane - rl * CPR;
     const int row = (RPP * w + rl) & 15;
     const int ch = (TileSwz<D>::off(row, slot) - 2 * D * row) >> 4;
-    return (8 * ch < dr) ? rl * 2 * dr + 16 * ch : kOobOff;
+    return (8 * ch < dr) ? rl * 2 * (STRIDED ? stride : dr) + 16 * ch : kOobOff;
 }
 // The DMA itself is issued from inline asm, so hipcc does not see it: with the builtin form hipcc treats every later
 // ds_read_b64_tr_b16 as possibly aliasing the pending LDS write and parks the wave on s_waitcnt vmcnt(0) in the
@@ -293,9 +297,9 @@ __device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0
 // stage rows [row0, row0 + ROWS) of the tensor behind `rsrc` (row stride 2*dr bytes) into the LDS tile at `tile`
 // (D = 256 with 4 waves: a wave's pieces alternate between two row classes mod 16, RPP * NW = 8; `voff_b` =
 // dma_lane_voff<D>(lane, w + NW, dr) serves the odd ones.)
-template <int D, int ROWS, int NW>
+template <int D, int ROWS, int NW, bool STRIDED = false>
 __device__ __forceinline__ void dma_stage_tile(rsrc_s_t rsrc, char* tile, int row0, int voff, int w, int dr = D,
-                                               int voff_b = 0) {
+                                               int voff_b = 0, int stride = 0) {
     constexpr int RPP = 512 / D, PIECES = ROWS / RPP, PER_WAVE = PIECES / NW;
     static_assert(PIECES % NW == 0 && ((RPP * NW) % 16 == 0 || RPP * NW == 8), "tile does not split evenly over the waves");
     const unsigned t0 = lds_addr_of(tile);
@@ -303,7 +307,7 @@ __device__ __forceinline__ void dma_stage_tile(rsrc_s_t rsrc, char* tile, int ro
     for (int j = 0; j < PER_WAVE; ++j) {
         const int pc = w + NW * j;
         const int vo = ((RPP * NW) % 16 != 0 && (j & 1)) ? voff_b : voff;
-        dma16_issue(rsrc, t0 + pc * 1024, vo, __builtin_amdgcn_readfirstlane((row0 + RPP * pc) * 2 * dr));
+        dma16_issue(rsrc, t0 + pc * 1024, vo, __builtin_amdgcn_readfirstlane((row0 + RPP * pc) * 2 * (STRIDED ? stride : dr)));
     }
 }
 
@@ -311,10 +315,10 @@ __device__ __forceinline__ void dma_stage_tile(rsrc_s_t rsrc, char* tile, int ro
 // 32 b + 8 g + 4 h of row r), goes through a wave-private LDS region and leaves as whole rows: 1 KiB contiguous per
 // store instruction instead of 64 scattered 16-byte pieces (the per-workgroup tail is store-issue bound).
 // `lrow`: the row of the 32-row tile this lane's values belong to (default: lane & 31; the dQ product kernel's lanes hold their
-// rows in the order of the kernel that wrote its operand tiles).
-template <int D>
+// rows in the order of the kernel that wrote its operand tiles).  STRIDED: destination rows `stride` elements apart.
+template <int D, bool STRIDED = false>
 __device__ __forceinline__ void store_rows_via_lds(char* wl, const u32x2 (&vals)[(D / 32) * 4], uint16_t* gdst, int row0,
-                                                   int n, int lane, int dr = D, int lrow = -1) {
+                                                   int n, int lane, int dr = D, int lrow = -1, int stride = 0) {
     constexpr int CPR = D / 8, RPI = 512 / D, ROWB = 2 * D;   // chunks per row, rows per 1-KiB store, row bytes
     const int r = lrow < 0 ? (lane & 31) : lrow, h = lane >> 5;
 #pragma unroll
@@ -327,7 +331,7 @@ __device__ __forceinline__ void store_rows_via_lds(char* wl, const u32x2 (&vals)
     for (int i = 0; i < 32 / RPI; ++i) {
         const int row = RPI * i + rl;
         const u32x4 v = *reinterpret_cast<const u32x4*>(wl + row * ROWB + 16 * (cc ^ (row & (CPR - 1) & 15)));
-        if (row0 + row < n && 8 * cc < dr) *reinterpret_cast<u32x4*>(gdst + (size_t)(row0 + row) * dr + 8 * cc) = v;
+        if (row0 + row < n && 8 * cc < dr) *reinterpret_cast<u32x4*>(gdst + (size_t)(row0 + row) * (STRIDED ? stride : dr) + 8 * cc) = v;
     }
 }
 

@@ -11,6 +11,8 @@
 //   * a sliding window (no reference counterpart; FlashAttention-2's window_size): key j is visible to query i only if
 //     i + (Nk - Nq) - wl <= j <= i + (Nk - Nq) + wr (ExParams: wr = 0 under the causal mask, kWinNone when unbounded); the
 //     key (query) tile ranges of every kernel are cut to the band at both ends.
+//   * packed (varlen) sequences (FlashAttention-2's flash_attn_varlen_func): each workgroup of the padded call's grid works inside
+//     its own sequence, in entries of their own (ex_*_varlen_kernel) around the bodies the other kernels share.
 // Exact-f32 math on the f32-input MFMA (any dtype in, head_dim <= 256), the structure of fa_generic.hip: forward by
 // query tile with online softmax over the visible keys; backward = delta pre-pass + dK/dV kernel + dQ kernel, no
 // atomics.  Rows without any visible key get o = 0, lse = -inf (the reference's softmax of an all -inf row is NaN).
@@ -27,19 +29,20 @@ namespace fa {
 
 // rows r0 .. r0 + rows - 1 of a (n, d) matrix into an f32 LDS tile, zero-filled past n and d; `vec` (wave-uniform: d % 4 == 0 and
 // the tensor aligned for it): four elements per load (16 bytes of f32, 8 bytes of 16-bit elements) and one 16-byte LDS store
-template <typename T, int DP, int LD, int NTHREADS>
+// (STRIDED: the rows of src are `ld` elements apart, the token stride of a packed tensor, instead of d)
+template <typename T, int DP, int LD, int NTHREADS, bool STRIDED = false>
 __device__ __forceinline__ void ex_load_tile(float* __restrict__ dst, const T* __restrict__ src, int r0, int rows, int n,
-                                             int d, bool vec) {
+                                             int d, bool vec, int ld = 0) {
     if (vec) {
         for (int idx = threadIdx.x; idx < rows * (DP / 4); idx += NTHREADS) {
             const int r = idx / (DP / 4), c = 4 * (idx - r * (DP / 4));
             f32x4 x = {0.f, 0.f, 0.f, 0.f};
             if (r0 + r < n && c < d) {
                 if constexpr (sizeof(T) == 4) {
-                    x = *reinterpret_cast<const f32x4*>(src + (size_t)(r0 + r) * d + c);
+                    x = *reinterpret_cast<const f32x4*>(src + (size_t)(r0 + r) * (STRIDED ? ld : d) + c);
                 } else {
                     T t[4];
-                    *reinterpret_cast<u32x2*>(t) = *reinterpret_cast<const u32x2*>(src + (size_t)(r0 + r) * d + c);
+                    *reinterpret_cast<u32x2*>(t) = *reinterpret_cast<const u32x2*>(src + (size_t)(r0 + r) * (STRIDED ? ld : d) + c);
                     x = f32x4{to_f32<T>(t[0]), to_f32<T>(t[1]), to_f32<T>(t[2]), to_f32<T>(t[3])};
                 }
             }
@@ -50,7 +53,7 @@ __device__ __forceinline__ void ex_load_tile(float* __restrict__ dst, const T* _
     for (int idx = threadIdx.x; idx < rows * DP; idx += NTHREADS) {
         const int r = idx / DP, c = idx - r * DP;
         float x = 0.f;
-        if (r0 + r < n && c < d) x = to_f32<T>(src[(size_t)(r0 + r) * d + c]);
+        if (r0 + r < n && c < d) x = to_f32<T>(src[(size_t)(r0 + r) * (STRIDED ? ld : d) + c]);
         dst[r * LD + c] = x;
     }
 }
@@ -63,10 +66,12 @@ template <typename T> __device__ __forceinline__ bool ex_quad_ok(int d, const vo
 // sum stays an f32 fma chain).  The P / dS staging areas are wave-private: no workgroup barrier between writing and reading them.
 
 // ---- forward: one workgroup = NW waves = 16 NW query rows of one (b,h); key tiles of 32
-template <typename T, int DP, int NW, bool WIN>
-__global__ __launch_bounds__(NW * 64) void ex_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
-                                                         const T* __restrict__ v, T* __restrict__ o,
-                                                         float* __restrict__ lse, ExParams p) {
+// VAR: packed sequences (ExParams' varlen fields; the ex_*_varlen_kernel entries): the tile of unit bh = b * hq + h of the padded
+// grid, inside sequence b.  q rows at token stride sq (k, v: sk, sv), o / dq / dk / dv rows at hq * d, lse at (h, token), delta at
+// (token, h).
+template <typename T, int DP, int NW, bool WIN, bool VAR>
+__device__ __forceinline__ void ex_fwd_body(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, T* __restrict__ o,
+                                            float* __restrict__ lse, ExParams& p) {
     constexpr int LD = DP + 4, BM = 16 * NW, BN = 32, NT = DP / 16, PLD = BN + 4, NTH = NW * 64;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Qs = smem;
@@ -76,12 +81,28 @@ __global__ __launch_bounds__(NW * 64) void ex_fwd_kernel(const T* __restrict__ q
     const int ntile = (p.nq + BM - 1) / BM;
     const int bh = blockIdx.x / ntile;
     const int q0 = (blockIdx.x - bh * ntile) * BM;
-    const size_t qbase = (size_t)bh * p.nq * p.d, kbase = (size_t)kv_unit(bh, p.kvg) * p.nk * p.d;
+    [[maybe_unused]] int sq0 = 0, sk0 = 0, hh = 0, hk = 0;
+    if constexpr (VAR) {   // packed sequences: narrow the padded call to sequence b (fa_ex_mfma.hip: EXM_VARLEN_UNIT)
+        const int b = bh / p.hq;
+        hh = bh - b * p.hq;
+        hk = kv_unit(hh, p.kvg);
+        int lq, lk;
+        seq_span(p.cu_q, b, p.total_q, p.nq, sq0, lq);
+        seq_span(p.cu_k, b, p.total_k, p.nk, sk0, lk);
+        p.nq = lq; p.nk = lk; p.coff = lk - lq;
+        if (q0 >= p.nq) return;
+    }
+    const size_t qbase = VAR ? (size_t)sq0 * p.sq + (size_t)hh * p.d : (size_t)bh * p.nq * p.d;
+    const size_t kbase = VAR ? (size_t)sk0 * p.sk + (size_t)hk * p.d : (size_t)kv_unit(bh, p.kvg) * p.nk * p.d;
+    const size_t vbase = VAR ? (size_t)sk0 * p.sv + (size_t)hk * p.d : kbase;
+    const size_t obase = VAR ? ((size_t)sq0 * p.hq + hh) * p.d : qbase;
+    const size_t ostr = VAR ? (size_t)p.hq * p.d : (size_t)p.d;
+    const size_t lbase = VAR ? (size_t)hh * p.total_q + sq0 : (size_t)bh * p.nq;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int lr = lane & 15, lq = lane >> 4;
 
-    const bool vec = ex_quad_ok<T>(p.d, q, k, v, q);
-    ex_load_tile<T, DP, LD, NTH>(Qs, q + qbase, q0, BM, p.nq, p.d, vec);
+    const bool vec = ex_quad_ok<T>(p.d, q, k, v, q) && (!VAR || (p.sq | p.sk | p.sv) % 4 == 0);
+    ex_load_tile<T, DP, LD, NTH, VAR>(Qs, q + qbase, q0, BM, p.nq, p.d, vec, VAR ? p.sq : 0);
     f32x4 acc[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -94,10 +115,10 @@ __global__ __launch_bounds__(NW * 64) void ex_fwd_kernel(const T* __restrict__ q
     float* Pw = Ps + w * 16 * PLD;
 
     for (int k0 = kstart; k0 < kend; k0 += BN) {
-        if (!ex_tile_live(p, q0, min(q0 + BM, p.nq), k0, min(k0 + BN, p.nk))) continue;   // block-sparse skip (uniform)
+        if (!VAR && !ex_tile_live(p, q0, min(q0 + BM, p.nq), k0, min(k0 + BN, p.nk))) continue;   // block-sparse skip (uniform)
         __syncthreads();
-        ex_load_tile<T, DP, LD, NTH>(Ks, k + kbase, k0, BN, p.nk, p.d, vec);
-        ex_load_tile<T, DP, LD, NTH>(Vs, v + kbase, k0, BN, p.nk, p.d, vec);
+        ex_load_tile<T, DP, LD, NTH, VAR>(Ks, k + kbase, k0, BN, p.nk, p.d, vec, VAR ? p.sk : 0);
+        ex_load_tile<T, DP, LD, NTH, VAR>(Vs, v + vbase, k0, BN, p.nk, p.d, vec, VAR ? p.sv : 0);
         __syncthreads();
         f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -115,8 +136,8 @@ __global__ __launch_bounds__(NW * 64) void ex_fwd_kernel(const T* __restrict__ q
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int row = q0 + w * 16 + lq * 4 + i;
-            float x0 = ex_visible<WIN>(p, bh, row, key0) ? s0[i] * p.scale : -INFINITY;
-            float x1 = ex_visible<WIN>(p, bh, row, key1) ? s1[i] * p.scale : -INFINITY;
+            float x0 = ex_visible<WIN, VAR>(p, bh, row, key0) ? s0[i] * p.scale : -INFINITY;
+            float x1 = ex_visible<WIN, VAR>(p, bh, row, key1) ? s1[i] * p.scale : -INFINITY;
             float mx = fmaxf(x0, x1);
             mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
             mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
@@ -159,11 +180,23 @@ __global__ __launch_bounds__(NW * 64) void ex_fwd_kernel(const T* __restrict__ q
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 const int c = 16 * t + lr;
-                if (c < p.d) o[qbase + (size_t)row * p.d + c] = from_f32<T>(acc[t][i] * inv);
+                if (c < p.d) o[obase + (size_t)row * ostr + c] = from_f32<T>(acc[t][i] * inv);
             }
-            if (lr == 0) lse[(size_t)bh * p.nq + row] = l[i] > 0.f ? m[i] + logf(l[i]) : -INFINITY;
+            if (lr == 0) lse[lbase + row] = l[i] > 0.f ? m[i] + logf(l[i]) : -INFINITY;
         }
     }
+}
+template <typename T, int DP, int NW, bool WIN>
+__global__ __launch_bounds__(NW * 64) void ex_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                         const T* __restrict__ v, T* __restrict__ o,
+                                                         float* __restrict__ lse, ExParams p) {
+    ex_fwd_body<T, DP, NW, WIN, false>(q, k, v, o, lse, p);
+}
+template <typename T, int DP, int NW, bool WIN>
+__global__ __launch_bounds__(NW * 64) void ex_fwd_varlen_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                                const T* __restrict__ v, T* __restrict__ o,
+                                                                float* __restrict__ lse, ExParams p) {
+    ex_fwd_body<T, DP, NW, WIN, true>(q, k, v, o, lse, p);
 }
 
 template <typename T>
@@ -183,11 +216,10 @@ __global__ __launch_bounds__(256) void ex_delta_kernel(const T* __restrict__ o, 
 
 // ---- backward dK/dV: one workgroup = 16 NW keys resident in LDS; loops over 32-row query tiles
 //      dV = P_drop^T dO,  dP = keep/(1-p) * (dO V^T),  dS = P (dP - delta),  dK = scale dS^T Q
-template <typename T, int DP, int NW, bool WIN>
-__global__ __launch_bounds__(NW * 64) void ex_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k,
-                                                          const T* __restrict__ v, const T* __restrict__ dout,
-                                                          const float* __restrict__ lse, const float* __restrict__ delta,
-                                                          T* __restrict__ dk, T* __restrict__ dv, ExParams p) {
+template <typename T, int DP, int NW, bool WIN, bool VAR>
+__device__ __forceinline__ void ex_dkdv_body(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
+                                             const T* __restrict__ dout, const float* __restrict__ lse,
+                                             const float* __restrict__ delta, T* __restrict__ dk, T* __restrict__ dv, ExParams& p) {
     constexpr int LD = DP + 4, BK = 16 * NW, BQ = 32, NT = DP / 16, PLD = BQ + 4, NTH = NW * 64;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Ks = smem;
@@ -200,14 +232,32 @@ __global__ __launch_bounds__(NW * 64) void ex_dkdv_kernel(const T* __restrict__ 
     const int ntile = (p.nk + BK - 1) / BK;
     const int bh = blockIdx.x / ntile;
     const int k0 = (blockIdx.x - bh * ntile) * BK;
-    const size_t qbase = (size_t)bh * p.nq * p.d, kbase = (size_t)kv_unit(bh, p.kvg) * p.nk * p.d;
-    const size_t dkbase = (size_t)bh * p.nk * p.d;   // dK / dV rows: per query head (grouped: the partials kv_group_sum adds up)
+    [[maybe_unused]] int sq0 = 0, sk0 = 0, hh = 0, hk = 0;
+    if constexpr (VAR) {   // packed sequences: narrow the padded call to sequence b (fa_ex_mfma.hip: EXM_VARLEN_UNIT)
+        const int b = bh / p.hq;
+        hh = bh - b * p.hq;
+        hk = kv_unit(hh, p.kvg);
+        int lq, lk;
+        seq_span(p.cu_q, b, p.total_q, p.nq, sq0, lq);
+        seq_span(p.cu_k, b, p.total_k, p.nk, sk0, lk);
+        p.nq = lq; p.nk = lk; p.coff = lk - lq;
+        if (k0 >= p.nk) return;
+    }
+    const size_t qbase = VAR ? (size_t)sq0 * p.sq + (size_t)hh * p.d : (size_t)bh * p.nq * p.d;
+    const size_t kbase = VAR ? (size_t)sk0 * p.sk + (size_t)hk * p.d : (size_t)kv_unit(bh, p.kvg) * p.nk * p.d;
+    const size_t vbase = VAR ? (size_t)sk0 * p.sv + (size_t)hk * p.d : kbase;
+    const size_t obase = VAR ? ((size_t)sq0 * p.hq + hh) * p.d : qbase;   // dO
+    const size_t ostr = VAR ? (size_t)p.hq * p.d : (size_t)p.d;           // rows of dO, dK, dV
+    const size_t lbase = VAR ? (size_t)hh * p.total_q + sq0 : (size_t)bh * p.nq;
+    const size_t dbase = VAR ? (size_t)sq0 * p.hq + hh : (size_t)bh * p.nq, dstep = VAR ? p.hq : 1;   // delta
+    // dK / dV rows: per query head (grouped: the partials kv_group_sum adds up)
+    const size_t dkbase = VAR ? ((size_t)sk0 * p.hq + hh) * p.d : (size_t)bh * p.nk * p.d;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int lr = lane & 15, lq = lane >> 4;
 
-    const bool vec = ex_quad_ok<T>(p.d, q, k, v, dout);
-    ex_load_tile<T, DP, LD, NTH>(Ks, k + kbase, k0, BK, p.nk, p.d, vec);
-    ex_load_tile<T, DP, LD, NTH>(Vs, v + kbase, k0, BK, p.nk, p.d, vec);
+    const bool vec = ex_quad_ok<T>(p.d, q, k, v, dout) && (!VAR || (p.sq | p.sk | p.sv) % 4 == 0);
+    ex_load_tile<T, DP, LD, NTH, VAR>(Ks, k + kbase, k0, BK, p.nk, p.d, vec, VAR ? p.sk : 0);
+    ex_load_tile<T, DP, LD, NTH, VAR>(Vs, v + vbase, k0, BK, p.nk, p.d, vec, VAR ? p.sv : 0);
     f32x4 dka[NT], dva[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) { dka[t] = f32x4{0.f, 0.f, 0.f, 0.f}; dva[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
@@ -218,14 +268,14 @@ __global__ __launch_bounds__(NW * 64) void ex_dkdv_kernel(const T* __restrict__ 
     const int qstart = WIN ? (max(0, k0 - p.coff - p.wr) / BQ) * BQ : (p.causal ? (max(0, k0 - p.coff) / BQ) * BQ : 0);
     const int qend = WIN ? min(p.nq, min(k0 + BK, p.nk) - p.coff + p.wl) : p.nq;
     for (int r0 = qstart; r0 < qend; r0 += BQ) {
-        if (!ex_tile_live(p, r0, min(r0 + BQ, p.nq), k0, min(k0 + BK, p.nk))) continue;
+        if (!VAR && !ex_tile_live(p, r0, min(r0 + BQ, p.nq), k0, min(k0 + BK, p.nk))) continue;
         __syncthreads();
-        ex_load_tile<T, DP, LD, NTH>(Qs, q + qbase, r0, BQ, p.nq, p.d, vec);
-        ex_load_tile<T, DP, LD, NTH>(Os, dout + qbase, r0, BQ, p.nq, p.d, vec);
+        ex_load_tile<T, DP, LD, NTH, VAR>(Qs, q + qbase, r0, BQ, p.nq, p.d, vec, VAR ? p.sq : 0);
+        ex_load_tile<T, DP, LD, NTH, VAR>(Os, dout + obase, r0, BQ, p.nq, p.d, vec, VAR ? (int)ostr : 0);
         if (threadIdx.x < BQ) {
             const int r = r0 + threadIdx.x;
-            Ls[threadIdx.x] = r < p.nq ? lse[(size_t)bh * p.nq + r] : 0.f;
-            Ls[BQ + threadIdx.x] = r < p.nq ? delta[(size_t)bh * p.nq + r] : 0.f;
+            Ls[threadIdx.x] = r < p.nq ? lse[lbase + r] : 0.f;
+            Ls[BQ + threadIdx.x] = r < p.nq ? delta[dbase + r * dstep] : 0.f;
         }
         __syncthreads();
 #pragma unroll
@@ -248,7 +298,7 @@ __global__ __launch_bounds__(NW * 64) void ex_dkdv_kernel(const T* __restrict__ 
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int key = k0 + w * 16 + lq * 4 + i;
-                const float pr = ex_visible<WIN>(p, bh, row, key) ? expf(st[i] * p.scale - lq_) : 0.f;
+                const float pr = ex_visible<WIN, VAR>(p, bh, row, key) ? expf(st[i] * p.scale - lq_) : 0.f;
                 const float ks_ = (p.p_drop > 0.f) ? (ex_keep(p, bh, row, key) ? p.keep_scale : 0.f) : 1.f;
                 Pw[(lq * 4 + i) * PLD + qb * 16 + lr] = pr * ks_;                       // P_drop^T (feeds dV)
                 Sw[(lq * 4 + i) * PLD + qb * 16 + lr] = pr * (dpt[i] * ks_ - dl_);      // dS^T
@@ -275,20 +325,33 @@ __global__ __launch_bounds__(NW * 64) void ex_dkdv_kernel(const T* __restrict__ 
             for (int t = 0; t < NT; ++t) {
                 const int c = 16 * t + lr;
                 if (c < p.d) {
-                    dk[dkbase + (size_t)key * p.d + c] = from_f32<T>(dka[t][i] * p.scale);
-                    dv[dkbase + (size_t)key * p.d + c] = from_f32<T>(dva[t][i]);
+                    dk[dkbase + (size_t)key * ostr + c] = from_f32<T>(dka[t][i] * p.scale);
+                    dv[dkbase + (size_t)key * ostr + c] = from_f32<T>(dva[t][i]);
                 }
             }
         }
     }
 }
+template <typename T, int DP, int NW, bool WIN>
+__global__ __launch_bounds__(NW * 64) void ex_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                          const T* __restrict__ v, const T* __restrict__ dout,
+                                                          const float* __restrict__ lse, const float* __restrict__ delta,
+                                                          T* __restrict__ dk, T* __restrict__ dv, ExParams p) {
+    ex_dkdv_body<T, DP, NW, WIN, false>(q, k, v, dout, lse, delta, dk, dv, p);
+}
+template <typename T, int DP, int NW, bool WIN>
+__global__ __launch_bounds__(NW * 64) void ex_dkdv_varlen_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                                 const T* __restrict__ v, const T* __restrict__ dout,
+                                                                 const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                 T* __restrict__ dk, T* __restrict__ dv, ExParams p) {
+    ex_dkdv_body<T, DP, NW, WIN, true>(q, k, v, dout, lse, delta, dk, dv, p);
+}
 
 // ---- backward dQ: one workgroup = 16 NW query rows; loops over 32-key tiles (S and dP recomputed: deterministic)
-template <typename T, int DP, int NW, bool WIN>
-__global__ __launch_bounds__(NW * 64) void ex_dq_kernel(const T* __restrict__ q, const T* __restrict__ k,
-                                                        const T* __restrict__ v, const T* __restrict__ dout,
-                                                        const float* __restrict__ lse, const float* __restrict__ delta,
-                                                        T* __restrict__ dq, ExParams p) {
+template <typename T, int DP, int NW, bool WIN, bool VAR>
+__device__ __forceinline__ void ex_dq_body(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
+                                           const T* __restrict__ dout, const float* __restrict__ lse,
+                                           const float* __restrict__ delta, T* __restrict__ dq, ExParams& p) {
     constexpr int LD = DP + 4, BM = 16 * NW, BN = 32, NT = DP / 16, PLD = BN + 4, NTH = NW * 64;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Qs = smem;
@@ -299,19 +362,36 @@ __global__ __launch_bounds__(NW * 64) void ex_dq_kernel(const T* __restrict__ q,
     const int ntile = (p.nq + BM - 1) / BM;
     const int bh = blockIdx.x / ntile;
     const int q0 = (blockIdx.x - bh * ntile) * BM;
-    const size_t qbase = (size_t)bh * p.nq * p.d, kbase = (size_t)kv_unit(bh, p.kvg) * p.nk * p.d;
+    [[maybe_unused]] int sq0 = 0, sk0 = 0, hh = 0, hk = 0;
+    if constexpr (VAR) {   // packed sequences: narrow the padded call to sequence b (fa_ex_mfma.hip: EXM_VARLEN_UNIT)
+        const int b = bh / p.hq;
+        hh = bh - b * p.hq;
+        hk = kv_unit(hh, p.kvg);
+        int lq, lk;
+        seq_span(p.cu_q, b, p.total_q, p.nq, sq0, lq);
+        seq_span(p.cu_k, b, p.total_k, p.nk, sk0, lk);
+        p.nq = lq; p.nk = lk; p.coff = lk - lq;
+        if (q0 >= p.nq) return;
+    }
+    const size_t qbase = VAR ? (size_t)sq0 * p.sq + (size_t)hh * p.d : (size_t)bh * p.nq * p.d;
+    const size_t kbase = VAR ? (size_t)sk0 * p.sk + (size_t)hk * p.d : (size_t)kv_unit(bh, p.kvg) * p.nk * p.d;
+    const size_t vbase = VAR ? (size_t)sk0 * p.sv + (size_t)hk * p.d : kbase;
+    const size_t obase = VAR ? ((size_t)sq0 * p.hq + hh) * p.d : qbase;   // dO, dQ
+    const size_t ostr = VAR ? (size_t)p.hq * p.d : (size_t)p.d;
+    const size_t lbase = VAR ? (size_t)hh * p.total_q + sq0 : (size_t)bh * p.nq;
+    const size_t dbase = VAR ? (size_t)sq0 * p.hq + hh : (size_t)bh * p.nq, dstep = VAR ? p.hq : 1;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int lr = lane & 15, lq = lane >> 4;
 
-    const bool vec = ex_quad_ok<T>(p.d, q, k, v, dout);
-    ex_load_tile<T, DP, LD, NTH>(Qs, q + qbase, q0, BM, p.nq, p.d, vec);
-    ex_load_tile<T, DP, LD, NTH>(Os, dout + qbase, q0, BM, p.nq, p.d, vec);
+    const bool vec = ex_quad_ok<T>(p.d, q, k, v, dout) && (!VAR || (p.sq | p.sk | p.sv) % 4 == 0);
+    ex_load_tile<T, DP, LD, NTH, VAR>(Qs, q + qbase, q0, BM, p.nq, p.d, vec, VAR ? p.sq : 0);
+    ex_load_tile<T, DP, LD, NTH, VAR>(Os, dout + obase, q0, BM, p.nq, p.d, vec, VAR ? (int)ostr : 0);
     float lrow[4], drow[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int row = q0 + w * 16 + lq * 4 + i;
-        lrow[i] = row < p.nq ? lse[(size_t)bh * p.nq + row] : 0.f;
-        drow[i] = row < p.nq ? delta[(size_t)bh * p.nq + row] : 0.f;
+        lrow[i] = row < p.nq ? lse[lbase + row] : 0.f;
+        drow[i] = row < p.nq ? delta[dbase + row * dstep] : 0.f;
     }
     f32x4 acc[NT];
 #pragma unroll
@@ -320,10 +400,10 @@ __global__ __launch_bounds__(NW * 64) void ex_dq_kernel(const T* __restrict__ q,
     const int kend = WIN ? max(0, min(p.nk, q0 + BM + p.coff + p.wr)) : (p.causal ? max(0, min(p.nk, q0 + BM + p.coff)) : p.nk);
     const int kstart = WIN ? (max(0, q0 + p.coff - p.wl) / BN) * BN : 0;   // (the forward kernel's tile range)
     for (int k0 = kstart; k0 < kend; k0 += BN) {
-        if (!ex_tile_live(p, q0, min(q0 + BM, p.nq), k0, min(k0 + BN, p.nk))) continue;
+        if (!VAR && !ex_tile_live(p, q0, min(q0 + BM, p.nq), k0, min(k0 + BN, p.nk))) continue;
         __syncthreads();
-        ex_load_tile<T, DP, LD, NTH>(Ks, k + kbase, k0, BN, p.nk, p.d, vec);
-        ex_load_tile<T, DP, LD, NTH>(Vs, v + kbase, k0, BN, p.nk, p.d, vec);
+        ex_load_tile<T, DP, LD, NTH, VAR>(Ks, k + kbase, k0, BN, p.nk, p.d, vec, VAR ? p.sk : 0);
+        ex_load_tile<T, DP, LD, NTH, VAR>(Vs, v + vbase, k0, BN, p.nk, p.d, vec, VAR ? p.sv : 0);
         __syncthreads();
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
@@ -344,7 +424,7 @@ __global__ __launch_bounds__(NW * 64) void ex_dq_kernel(const T* __restrict__ q,
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int row = q0 + w * 16 + lq * 4 + i;
-                const float pr = ex_visible<WIN>(p, bh, row, key) ? expf(s[i] * p.scale - lrow[i]) : 0.f;
+                const float pr = ex_visible<WIN, VAR>(p, bh, row, key) ? expf(s[i] * p.scale - lrow[i]) : 0.f;
                 const float ks_ = (p.p_drop > 0.f) ? (ex_keep(p, bh, row, key) ? p.keep_scale : 0.f) : 1.f;
                 Sw[(lq * 4 + i) * PLD + nb * 16 + lr] = pr * (dp[i] * ks_ - drow[i]);
             }
@@ -365,18 +445,32 @@ __global__ __launch_bounds__(NW * 64) void ex_dq_kernel(const T* __restrict__ q,
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 const int c = 16 * t + lr;
-                if (c < p.d) dq[qbase + (size_t)row * p.d + c] = from_f32<T>(acc[t][i] * p.scale);
+                if (c < p.d) dq[obase + (size_t)row * ostr + c] = from_f32<T>(acc[t][i] * p.scale);
             }
         }
     }
 }
+template <typename T, int DP, int NW, bool WIN>
+__global__ __launch_bounds__(NW * 64) void ex_dq_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                        const T* __restrict__ v, const T* __restrict__ dout,
+                                                        const float* __restrict__ lse, const float* __restrict__ delta,
+                                                        T* __restrict__ dq, ExParams p) {
+    ex_dq_body<T, DP, NW, WIN, false>(q, k, v, dout, lse, delta, dq, p);
+}
+template <typename T, int DP, int NW, bool WIN>
+__global__ __launch_bounds__(NW * 64) void ex_dq_varlen_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                               const T* __restrict__ v, const T* __restrict__ dout,
+                                                               const float* __restrict__ lse, const float* __restrict__ delta,
+                                                               T* __restrict__ dq, ExParams p) {
+    ex_dq_body<T, DP, NW, WIN, true>(q, k, v, dout, lse, delta, dq, p);
+}
 
 // ---- host launchers
-template <typename T, int DP, int NW, bool WIN>
+template <typename T, int DP, int NW, bool WIN, bool VAR = false>
 static hipError_t ex_fwd_t(const ExArgs& a, hipStream_t st) {
     constexpr int LD = DP + 4;
     const size_t smem = sizeof(float) * ((16 * NW + 64) * LD + NW * 16 * 36);
-    auto kern = ex_fwd_kernel<T, DP, NW, WIN>;
+    auto kern = VAR ? ex_fwd_varlen_kernel<T, DP, NW, WIN> : ex_fwd_kernel<T, DP, NW, WIN>;
     hipError_t e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
     if (e != hipSuccess) return e;
     dim3 grid((unsigned)(((a.nq + 16 * NW - 1) / (16 * NW)) * a.bh));
@@ -386,11 +480,11 @@ static hipError_t ex_fwd_t(const ExArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-template <typename T, int DP, int NW, bool WIN>
+template <typename T, int DP, int NW, bool WIN, bool VAR = false>
 static hipError_t ex_bwd_t(const ExArgs& a, hipStream_t st) {
     constexpr int LD = DP + 4;
     float* delta = reinterpret_cast<float*>(a.workspace);
-    const long long rows = (long long)a.bh * a.nq;
+    const long long rows = VAR ? (long long)a.total_q * a.heads_q : (long long)a.bh * a.nq;   // (varlen: (token, head) order)
     const ExParams p = make_ex_params(a);
     ProfScope ps(K_EX_BWD, st);
     hipLaunchKernelGGL(ex_delta_kernel<T>, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, (const T*)a.o,
@@ -399,7 +493,7 @@ static hipError_t ex_bwd_t(const ExArgs& a, hipStream_t st) {
     if (e != hipSuccess) return e;
     {
         const size_t smem = sizeof(float) * ((2 * 16 * NW + 64) * LD + 2 * NW * 16 * 36 + 64);
-        auto kern = ex_dkdv_kernel<T, DP, NW, WIN>;
+        auto kern = VAR ? ex_dkdv_varlen_kernel<T, DP, NW, WIN> : ex_dkdv_kernel<T, DP, NW, WIN>;
         e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
         if (e != hipSuccess) return e;
         dim3 grid((unsigned)(((a.nk + 16 * NW - 1) / (16 * NW)) * a.bh));
@@ -410,7 +504,7 @@ static hipError_t ex_bwd_t(const ExArgs& a, hipStream_t st) {
     }
     {
         const size_t smem = sizeof(float) * ((2 * 16 * NW + 64) * LD + NW * 16 * 36);
-        auto kern = ex_dq_kernel<T, DP, NW, WIN>;
+        auto kern = VAR ? ex_dq_varlen_kernel<T, DP, NW, WIN> : ex_dq_kernel<T, DP, NW, WIN>;
         e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
         if (e != hipSuccess) return e;
         dim3 grid((unsigned)(((a.nq + 16 * NW - 1) / (16 * NW)) * a.bh));
@@ -421,14 +515,15 @@ static hipError_t ex_bwd_t(const ExArgs& a, hipStream_t st) {
     return e;
 }
 
-template <typename T, bool WIN>
+template <typename T, bool WIN, bool VAR = false>
 static hipError_t ex_by_d(const ExArgs& a, bool backward, hipStream_t st) {
-    if (a.d <= 64) return backward ? ex_bwd_t<T, 64, 4, WIN>(a, st) : ex_fwd_t<T, 64, 4, WIN>(a, st);
-    if (a.d <= 128) return backward ? ex_bwd_t<T, 128, 4, WIN>(a, st) : ex_fwd_t<T, 128, 4, WIN>(a, st);
-    return backward ? ex_bwd_t<T, 256, 2, WIN>(a, st) : ex_fwd_t<T, 256, 4, WIN>(a, st);
+    if (a.d <= 64) return backward ? ex_bwd_t<T, 64, 4, WIN, VAR>(a, st) : ex_fwd_t<T, 64, 4, WIN, VAR>(a, st);
+    if (a.d <= 128) return backward ? ex_bwd_t<T, 128, 4, WIN, VAR>(a, st) : ex_fwd_t<T, 128, 4, WIN, VAR>(a, st);
+    return backward ? ex_bwd_t<T, 256, 2, WIN, VAR>(a, st) : ex_fwd_t<T, 256, 4, WIN, VAR>(a, st);
 }
 template <typename T>
 static hipError_t ex_by_d(const ExArgs& a, bool backward, hipStream_t st) {
+    if (a.cu_q) return ex_windowed(a) ? ex_by_d<T, true, true>(a, backward, st) : ex_by_d<T, false, true>(a, backward, st);
     return ex_windowed(a) ? ex_by_d<T, true>(a, backward, st) : ex_by_d<T, false>(a, backward, st);
 }
 
@@ -496,7 +591,35 @@ static hipError_t launch_ex_one(const ExArgs& a, bool backward, hipStream_t st) 
     }
 }
 
+// Packed sequences (a.cu_q != null; the C layer has handled the calls with an empty side): the extended kernels only — 16-bit MFMA
+// where they take the call, exact f32 otherwise (option ex_path as for the other calls: 1 = exact f32, 2 / 3 = MFMA or fail).
+static hipError_t launch_ex_varlen_one(const ExArgs& a, bool backward, hipStream_t st) {
+    const int path = option(OPT_EX_PATH);
+    if (path != 1 && ex_mfma_varlen_supported(a)) return launch_ex_mfma_varlen(a, backward, st);
+    if (path >= 2) return hipErrorInvalidConfiguration;
+    switch (a.dtype) {
+        case 0: return ex_by_d<float>(a, backward, st);
+        case 1: return ex_by_d<__half>(a, backward, st);
+        default: return ex_by_d<__hip_bfloat16>(a, backward, st);
+    }
+}
+
 hipError_t launch_ex(const ExArgs& a, bool backward, hipStream_t st) {
+    if (a.cu_q) {
+        if (!backward || a.kv_group <= 1) return launch_ex_varlen_one(a, backward, st);
+        // grouped: per-query-head partials (total_k, heads_q, d) in front of the row constants, then the group sum over units of
+        // d elements — unit t * heads_kv + j adds partial rows t * heads_q + j * g + m, m = 0 .. g-1, in that order
+        const size_t slab = kv_partial_bytes(a.total_k * a.heads_q, 1, a.d, a.dtype);
+        if (a.workspace_bytes < 2 * slab) return hipErrorInvalidValue;
+        ExArgs g = a;
+        g.dk = a.workspace;
+        g.dv = reinterpret_cast<char*>(a.workspace) + slab;
+        g.workspace = reinterpret_cast<char*>(a.workspace) + 2 * slab;
+        g.workspace_bytes = a.workspace_bytes - 2 * slab;
+        hipError_t e = launch_ex_varlen_one(g, true, st);
+        if (e != hipSuccess) return e;
+        return launch_kv_group_sum(g.dk, g.dv, a.dk, a.dv, a.total_k * (a.heads_q / a.kv_group), a.kv_group, 1, a.d, a.dtype, st);
+    }
     if (!backward || a.kv_group <= 1) return launch_ex_one(a, backward, st);
     // Grouped backward.  Workspace: [dK partials][dV partials][what the ungrouped call of bh query units takes]; the kernels write
     // one dK / dV unit per query head into the partials (their indexing and launch geometry as ungrouped), then the group sum.

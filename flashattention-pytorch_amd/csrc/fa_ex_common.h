@@ -14,10 +14,17 @@ struct ExParams {
     int nq, nk, d;
     int causal;            // 0 | 1 (bottom-right aligned)
     int coff;              // nk - nq
-    const uint8_t* mask;   // [nq][nk] bytes or null
-    long long mask_bh;     // elements between the masks of consecutive (b,h): 0 = shared
-    const uint8_t* bmask;  // [nbr][nbc] bytes or null
-    int br, bc, nbc;
+    // Variable-length (packed) sequences (the varlen instantiations; fa_ex_mfma.hip FEAT bit 3): their fields take the padding
+    // before `mask` and the places of the masks, which a varlen call does not have, so no other field moves and the kernels
+    // without them are the ones they were.  nq, nk are then max_seqlen_q / _k (grid, dropout counters) and each workgroup
+    // narrows them and coff to its sequence (seq_span).  Unit u = b * hq + h; token t of sequence b, head h of q is at
+    // q + (cu_q[b] + t) * sq + h * d (k, v: sk, sv and head h / kv_group); of o, do, dq, and of dk, dv per query head, at
+    // ((cu_q[b] + t) * hq + h) * d; lse (hq, total_q).
+    int hq;                // query heads
+    union { const uint8_t* mask;  const int* cu_q; };   // [nq][nk] bytes or null | varlen: [B + 1] untrusted token offsets
+    union { long long mask_bh;    struct { int total_q, total_k; }; };   // elements between the masks of consecutive (b,h): 0 = shared
+    union { const uint8_t* bmask; const int* cu_k; };   // [nbr][nbc] bytes or null
+    union { struct { int br, bc, nbc; }; struct { int sq, sk, sv; }; };   // varlen: token strides of q, k, v (elements)
     float p_drop, keep_scale;   // keep_scale = 1 / (1 - p)
     unsigned drop_thr;          // keep iff the element's 16 uniform bits are >= drop_thr = floor(65536 p) + 1
     unsigned nqh;               // ceil(nq / 2): row pairs per (b,h)
@@ -25,7 +32,21 @@ struct ExParams {
     float scale;
     unsigned kvg;          // kv_magic(query heads per K/V head g): K / V rows of unit bh / g (dK / dV: of bh, the per-head partials)
 };
+// (the varlen fields moved nothing: the offsets every kernel without them loads from)
+static_assert(offsetof(ExParams, mask) == 32 && offsetof(ExParams, mask_bh) == 40 && offsetof(ExParams, bmask) == 48 &&
+              offsetof(ExParams, br) == 56 && offsetof(ExParams, p_drop) == 68 && sizeof(ExParams) == 104, "ExParams layout");
 constexpr int kWinNone = 1 << 30;
+
+// first token and length of sequence b: start = clamp(cu[b], 0, total), end = clamp(cu[b + 1], start, total),
+// len = min(end - start, max_len).  b is uniform over the workgroup: scalar loads.
+__device__ __forceinline__ void seq_span(const int* cu, int b, int total, int max_len, int& start, int& len) {
+    const int a = min(max(cu[b], 0), total);
+    const int e = min(max(cu[b + 1], a), total);
+    start = a;
+    len = min(e - a, max_len);
+}
+// bytes of a buffer range that covers rows [0, n) of d 16-bit elements, `stride` elements apart (0 rows: nothing)
+__device__ __forceinline__ unsigned span_bytes(int n, int d, int stride) { return n > 0 ? (unsigned)((n - 1) * stride + d) * 2u : 0u; }
 
 // Dropout generator: ONE splitmix64 value per 2 x 2 quad of (query row, key) elements, 16 uniform bits per element — the
 // 64-bit mixing (two 64 x 64 multiplies) is the expensive part on a GPU, and in every kernel a lane owns either two
@@ -46,13 +67,14 @@ __device__ __forceinline__ bool ex_keep(const ExParams& p, int bh, int row, int 
     return u >= p.drop_thr;
 }
 // WIN: the call has a window (a separate instantiation: calls without one run the code they ran before it existed)
-template <bool WIN>
+// VAR: a varlen call (no masks: their fields hold the sequence offsets)
+template <bool WIN, bool VAR = false>
 __device__ __forceinline__ bool ex_visible(const ExParams& p, int bh, int row, int key) {
     if (row >= p.nq || key >= p.nk) return false;
     if (p.causal && key > row + p.coff) return false;
     if (WIN && (key > row + p.coff + p.wr || key < row + p.coff - p.wl)) return false;   // (wr = 0 under the causal flag)
-    if (p.mask && p.mask[(size_t)bh * p.mask_bh + (size_t)row * p.nk + key] == 0) return false;
-    if (p.bmask && p.bmask[(row / p.br) * p.nbc + key / p.bc] == 0) return false;
+    if (!VAR && p.mask && p.mask[(size_t)bh * p.mask_bh + (size_t)row * p.nk + key] == 0) return false;
+    if (!VAR && p.bmask && p.bmask[(row / p.br) * p.nbc + key / p.bc] == 0) return false;
     return true;
 }
 // does the block-sparse mask leave anything of rows [r0, r1) x keys [k0, k1)?  (uniform over the workgroup)
@@ -82,6 +104,13 @@ inline ExParams make_ex_params(const ExArgs& a) {
     p.kvg = kv_magic(a.kv_group);
     p.wl = a.window_left >= 0 ? (int)a.window_left : kWinNone;
     p.wr = a.causal ? 0 : (a.window_right >= 0 ? (int)a.window_right : kWinNone);
+    p.hq = 0;
+    if (a.cu_q) {   // varlen (no masks): the mask fields hold the sequences
+        p.hq = (int)a.heads_q;
+        p.cu_q = a.cu_q; p.cu_k = a.cu_k;
+        p.total_q = (int)a.total_q; p.total_k = (int)a.total_k;
+        p.sq = (int)a.stride_q; p.sk = (int)a.stride_k; p.sv = (int)a.stride_v;
+    }
     return p;
 }
 

@@ -11,6 +11,8 @@
 //               band; a wave computes the tiles of its own 32 rows (keys) and only helps to load the others, before
 //               and after its own (feed-only); edge tiles mask per element against a lower and an upper threshold.
 //               Without the bit the instantiations are the ones of the causal / unmasked kernels, unchanged.
+//   FEAT bit 3  packed (varlen) sequences: the padded call's grid, each workgroup narrowed to its sequence (EXM_VARLEN_UNIT; the
+//               fields in ExParams, fa_ex_common.h), token strides for q, k, v; combinable with bits 1 and 2, never with bit 0.
 // Dense mask bytes are fetched with range-checked buffer loads (rows / bytes past the mask read as 0 = masked); when Nk, the
 // mask pointer and the (b,h) stride are multiples of 4 a lane of the query-on-the-lane kernels takes the 4 keys of a
 // register group with one dword load.  The block-sparse mask needs br, bc multiples of 32 here (a wave's 32 x 32 block
@@ -24,7 +26,7 @@ namespace fa {
 
 namespace {
 
-constexpr int kFeatMask = 1, kFeatDrop = 2, kFeatWindow = 4;
+constexpr int kFeatMask = 1, kFeatDrop = 2, kFeatWindow = 4, kFeatVarlen = 8;
 
 // rc(i): row (or key) offset inside a 32-wide block of accumulator register i, before the 4 * (lane >> 5) term
 __device__ __forceinline__ constexpr int rc_of(int i) { return (i & 3) + 8 * (i >> 2); }
@@ -223,34 +225,58 @@ __device__ __forceinline__ unsigned keep_bits_k(const ExParams& p, unsigned hi_b
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ forward
+// Varlen (FEAT bit 3): the workgroup's unit bh = b * hq + h and its tile T0 come from the padded grid (nq, nk = the maxima); it
+// narrows nq, nk, coff to sequence b (seq_span) and leaves before its first barrier when its tile starts past the sequence.
+// Bases, buffer ranges and row strides become the sequence's; DR stays the column bound.
+#define EXM_VARLEN_UNIT(T0, N0)                                                                                         \
+    [[maybe_unused]] int sq0 = 0, sk0 = 0, hh = 0, hk = 0;                                                              \
+    if constexpr (VAR) {                                                                                                \
+        const int b = bh / p.hq;                                                                                        \
+        hh = bh - b * p.hq;                                                                                             \
+        hk = kv_unit(hh, p.kvg);                                                                                        \
+        int lq, lk;                                                                                                     \
+        seq_span(p.cu_q, b, p.total_q, nq, sq0, lq);                                                                    \
+        seq_span(p.cu_k, b, p.total_k, nk, sk0, lk);                                                                    \
+        nq = lq; nk = lk; p.coff = lk - lq;                                                                             \
+        if ((T0) >= (N0)) return;                                                                                       \
+    }
+
 template <typename Tag, int D, int FEAT>
 __global__ __launch_bounds__(512, 2) void exm_fwd_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                          const uint16_t* __restrict__ v, uint16_t* __restrict__ o,
                                                          float* __restrict__ lse, ExParams p, float c_log2) {
     constexpr int NW = 8, BM = 32 * NW, KB = 4, BN = 32 * KB, NKS = D / 16, NDV = D / 32, TILE_BYTES = BN * D * 2;
+    constexpr bool VAR = (FEAT & kFeatVarlen) != 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];   // [2 buffers][K tile | V tile]
-    const int DR = p.d, nq = p.nq, nk = p.nk;
+    const int DR = p.d;
+    int nq = p.nq, nk = p.nk;
     const int nqt = (nq + BM - 1) / BM;
     const int L = xcd_remap(blockIdx.x, gridDim.x);
     const int bh = L / nqt;
     const int q0 = (L - bh * nqt) * BM;
+    EXM_VARLEN_UNIT(q0, nq)
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
-    const size_t qbase = (size_t)bh * nq * DR, kbase = (size_t)kv_unit(bh, p.kvg) * nk * DR;
+    const size_t qbase = VAR ? (size_t)sq0 * p.sq + hh * DR : (size_t)bh * nq * DR;
+    const size_t kbase = VAR ? (size_t)sk0 * p.sk + hk * DR : (size_t)kv_unit(bh, p.kvg) * nk * DR;
+    const size_t vbase = VAR ? (size_t)sk0 * p.sv + hk * DR : kbase;
+    const size_t obase = VAR ? ((size_t)sq0 * p.hq + hh) * DR : qbase;
+    const size_t lbase = VAR ? (size_t)hh * p.total_q + sq0 : (size_t)bh * nq;
     const int qrow = q0 + 32 * w + r;
 
-    const buf_rsrc_t q_rs = make_rsrc(q + qbase, (unsigned)nq * DR * 2);
+    const buf_rsrc_t q_rs = make_rsrc(q + qbase, VAR ? span_bytes(nq, DR, p.sq) : (unsigned)nq * DR * 2);
     s16x8 qf[NKS];
 #pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) qf[ks] = buf_load_frag(q_rs, frag_off(qrow, 16 * ks + 8 * h, DR, true));
+    for (int ks = 0; ks < NKS; ++ks) qf[ks] = buf_load_frag(q_rs, frag_off<VAR>(qrow, 16 * ks + 8 * h, DR, true, VAR ? p.sq : DR));
 
-    const rsrc_s_t k_rs = make_rsrc_s(k + kbase, (unsigned)nk * DR * 2);
-    const rsrc_s_t v_rs = make_rsrc_s(v + kbase, (unsigned)nk * DR * 2);
-    const int dma_voff = dma_lane_voff<D>(lane, w, DR);
+    const rsrc_s_t k_rs = make_rsrc_s(k + kbase, VAR ? span_bytes(nk, DR, p.sk) : (unsigned)nk * DR * 2);
+    const rsrc_s_t v_rs = make_rsrc_s(v + vbase, VAR ? span_bytes(nk, DR, p.sv) : (unsigned)nk * DR * 2);
+    const int dma_voff = dma_lane_voff<D, VAR>(lane, w, DR, VAR ? p.sk : DR);
+    const int dma_voff_v = VAR ? dma_lane_voff<D, VAR>(lane, w, DR, p.sv) : dma_voff;
     auto stage = [&](int buf, int k0) {
         char* kb_ = smem + buf * 2 * TILE_BYTES;
-        dma_stage_tile<D, BN, NW>(k_rs, kb_, k0, dma_voff, w, DR);
-        dma_stage_tile<D, BN, NW>(v_rs, kb_ + TILE_BYTES, k0, dma_voff, w, DR);
+        dma_stage_tile<D, BN, NW, VAR>(k_rs, kb_, k0, dma_voff, w, DR, 0, VAR ? p.sk : DR);
+        dma_stage_tile<D, BN, NW, VAR>(v_rs, kb_ + TILE_BYTES, k0, dma_voff_v, w, DR, 0, VAR ? p.sv : DR);
     };
     const MaskSrc msk = make_mask_src(p, bh);
     const bool use_bm = (FEAT & kFeatMask) && p.bmask != nullptr;
@@ -456,8 +482,8 @@ __global__ __launch_bounds__(512, 2) void exm_fwd_kernel(const uint16_t* __restr
             vals[4 * dvb + g][0] = pack2_rn<Tag>(oacc[dvb][4 * g + 0] * inv, oacc[dvb][4 * g + 1] * inv);
             vals[4 * dvb + g][1] = pack2_rn<Tag>(oacc[dvb][4 * g + 2] * inv, oacc[dvb][4 * g + 3] * inv);
         }
-    store_rows_via_lds<D>(smem + w * 32 * D * 2, vals, o + qbase, q0 + 32 * w, nq, lane, DR);
-    if (qrow < nq && h == 0) lse[(size_t)bh * nq + qrow] = l_tot > 0.f ? m_run * p.scale + logf(l_tot) : -INFINITY;
+    store_rows_via_lds<D, VAR>(smem + w * 32 * D * 2, vals, o + obase, q0 + 32 * w, nq, lane, DR, -1, p.hq * DR);
+    if (qrow < nq && h == 0) lse[lbase + qrow] = l_tot > 0.f ? m_run * p.scale + logf(l_tot) : -INFINITY;
 }
 
 // ------------------------------------------------------------------------------------------------ row constants
@@ -487,6 +513,36 @@ __global__ __launch_bounds__(256) void exm_prep_kernel(const uint16_t* __restric
     }
 }
 
+// the same for packed sequences: o, dout (total_q, hq, d); lse and the two outputs (hq, total_q).  Workgroup x: head x / tph,
+// tokens 16 (x % tph) ..  Tokens no sequence covers get constants of their unspecified lse (no kernel reads them).
+template <typename Tag>
+__global__ __launch_bounds__(256) void exm_prep_varlen_kernel(const uint16_t* __restrict__ o, const uint16_t* __restrict__ dout,
+                                                              const float* __restrict__ lse, float* __restrict__ nlse,
+                                                              float* __restrict__ ndelta, int total_q, int tph, int hq, int d,
+                                                              float inv_scale) {
+    const int hd = blockIdx.x / tph;
+    const int tok = (blockIdx.x - hd * tph) * 16 + (threadIdx.x >> 4);
+    const int sub = threadIdx.x & 15;
+    const size_t row = ((size_t)tok * hq + hd) * d;
+    float s = 0.f;
+    if (tok < total_q && 8 * sub < d) {
+        const u32x4 a = *reinterpret_cast<const u32x4*>(o + row + 8 * sub);
+        const u32x4 b = *reinterpret_cast<const u32x4*>(dout + row + 8 * sub);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s += unpack_lo<Tag>(a[j]) * unpack_lo<Tag>(b[j]) + unpack_hi<Tag>(a[j]) * unpack_hi<Tag>(b[j]);
+    }
+    s += __shfl_xor(s, 1, 64);
+    s += __shfl_xor(s, 2, 64);
+    s += __shfl_xor(s, 4, 64);
+    s += __shfl_xor(s, 8, 64);
+    if (tok < total_q && sub == 0) {
+        const size_t i = (size_t)hd * total_q + tok;
+        const float l = lse[i];
+        nlse[i] = (l == -INFINITY) ? 0.f : -l * inv_scale;
+        ndelta[i] = -s;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ dK / dV
 // M16: the dense mask (if any) is 16-byte aligned in every respect — its bytes come through the wave's LDS image
 // (dense_bits_k_lds); a separate instantiation, not a run-time choice: with both loaders in one kernel the masked form spills
@@ -497,32 +553,40 @@ __global__ __launch_bounds__(512, 2) void exm_dkdv_kernel(const uint16_t* __rest
                                                           uint16_t* __restrict__ dk, uint16_t* __restrict__ dv, ExParams p,
                                                           float c_log2) {
     constexpr int NW = 8, BK = 32 * NW, BQ = 64, NKS = D / 16, NDB = D / 32;
+    constexpr bool VAR = (FEAT & kFeatVarlen) != 0;
     constexpr int K_BYTES = BK * D * 2, Q_BYTES = BQ * D * 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Ks = smem;                      // [256][D]
     char* Qs = Ks + K_BYTES;              // [2][64][D]
     char* Os = Qs + 2 * Q_BYTES;          // [2][64][D]   (dO)
     float* Ls = reinterpret_cast<float*>(Os + 2 * Q_BYTES);  // [2][ 64 x -lse/scale | 64 x -delta ]
-    const int DR = p.d, nq = p.nq, nk = p.nk;
+    const int DR = p.d;
+    int nq = p.nq, nk = p.nk;
     const int nkt = (nk + BK - 1) / BK;
     const int L = xcd_remap(blockIdx.x, gridDim.x);
     const int bh = L / nkt;
     const int key0 = (L - bh * nkt) * BK;
+    EXM_VARLEN_UNIT(key0, nk)
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
-    const size_t qbase = (size_t)bh * nq * DR, kbase = (size_t)kv_unit(bh, p.kvg) * nk * DR, rbase = (size_t)bh * nq;
+    const size_t qbase = VAR ? (size_t)sq0 * p.sq + hh * DR : (size_t)bh * nq * DR;
+    const size_t kbase = VAR ? (size_t)sk0 * p.sk + hk * DR : (size_t)kv_unit(bh, p.kvg) * nk * DR;
+    const size_t vbase = VAR ? (size_t)sk0 * p.sv + hk * DR : kbase;
+    const size_t obase = VAR ? ((size_t)sq0 * p.hq + hh) * DR : qbase;
+    const size_t rbase = VAR ? (size_t)hh * p.total_q + sq0 : (size_t)bh * nq;
     const int kw0 = key0 + 32 * w, key = kw0 + r;
 
-    const rsrc_s_t k_rs = make_rsrc_s(k + kbase, (unsigned)nk * DR * 2);
-    const rsrc_s_t q_rs = make_rsrc_s(q + qbase, (unsigned)nq * DR * 2);
-    const rsrc_s_t o_rs = make_rsrc_s(dout + qbase, (unsigned)nq * DR * 2);
+    const rsrc_s_t k_rs = make_rsrc_s(k + kbase, VAR ? span_bytes(nk, DR, p.sk) : (unsigned)nk * DR * 2);
+    const rsrc_s_t q_rs = make_rsrc_s(q + qbase, VAR ? span_bytes(nq, DR, p.sq) : (unsigned)nq * DR * 2);
+    const rsrc_s_t o_rs = make_rsrc_s(dout + obase, VAR ? span_bytes(nq, DR, p.hq * DR) : (unsigned)nq * DR * 2);
     const rsrc_s_t l_rs = make_rsrc_s(nlse + rbase, (unsigned)nq * 4);
     const rsrc_s_t d_rs = make_rsrc_s(ndelta + rbase, (unsigned)nq * 4);
-    const buf_rsrc_t v_rs = make_rsrc(v + kbase, (unsigned)nk * DR * 2);
-    const int dma_voff = dma_lane_voff<D>(lane, w, DR);
+    const buf_rsrc_t v_rs = make_rsrc(v + vbase, VAR ? span_bytes(nk, DR, p.sv) : (unsigned)nk * DR * 2);
+    const int dma_voff = dma_lane_voff<D, VAR>(lane, w, DR, VAR ? p.sq : DR);
+    const int dma_voff_o = VAR ? dma_lane_voff<D, VAR>(lane, w, DR, p.hq * DR) : dma_voff;
     auto stage = [&](int buf, int qs) {
-        dma_stage_tile<D, BQ, NW>(q_rs, Qs + buf * Q_BYTES, qs, dma_voff, w, DR);
-        dma_stage_tile<D, BQ, NW>(o_rs, Os + buf * Q_BYTES, qs, dma_voff, w, DR);
+        dma_stage_tile<D, BQ, NW, VAR>(q_rs, Qs + buf * Q_BYTES, qs, dma_voff, w, DR, 0, VAR ? p.sq : DR);
+        dma_stage_tile<D, BQ, NW, VAR>(o_rs, Os + buf * Q_BYTES, qs, dma_voff_o, w, DR, 0, VAR ? p.hq * DR : DR);
         // row constants: 64 floats each, one 4-byte LDS-DMA per lane (rows >= nq read as 0: harmless, their dO is 0)
         if (w == 0) dma4_issue(l_rs, lds_addr_of(Ls + buf * 128), lane * 4, __builtin_amdgcn_readfirstlane(qs * 4));
         if (w == 1) dma4_issue(d_rs, lds_addr_of(Ls + buf * 128 + 64), lane * 4, __builtin_amdgcn_readfirstlane(qs * 4));
@@ -532,10 +596,11 @@ __global__ __launch_bounds__(512, 2) void exm_dkdv_kernel(const uint16_t* __rest
     const bool drop = (FEAT & kFeatDrop) && p.p_drop > 0.f;
     const int cbw = min(kw0, nk - 1) / p.bc;   // block column of this wave's 32 keys (bc is a multiple of 32)
 
-    dma_stage_tile<D, BK, NW>(k_rs, Ks, key0, dma_voff, w, DR);
+    if constexpr (VAR) dma_stage_tile<D, BK, NW, VAR>(k_rs, Ks, key0, dma_lane_voff<D, VAR>(lane, w, DR, p.sk), w, DR, 0, p.sk);
+    else dma_stage_tile<D, BK, NW>(k_rs, Ks, key0, dma_voff, w, DR);
     s16x8 vf[NKS];
 #pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) vf[ks] = buf_load_frag(v_rs, frag_off(key, 16 * ks + 8 * h, DR, true));
+    for (int ks = 0; ks < NKS; ++ks) vf[ks] = buf_load_frag(v_rs, frag_off<VAR>(key, 16 * ks + 8 * h, DR, true, VAR ? p.sv : DR));
 
     f32x16 dka[NDB], dva[NDB];
 #pragma unroll
@@ -710,8 +775,10 @@ __global__ __launch_bounds__(512, 2) void exm_dkdv_kernel(const uint16_t* __rest
 
     if (key < nk) {
         // dK / dV rows: per query head (grouped: the partials kv_group_sum adds up)
-        uint16_t* dkrow = dk + ((size_t)bh * nk + key) * DR;
-        uint16_t* dvrow = dv + ((size_t)bh * nk + key) * DR;
+        // (varlen: rows of (total_k, hq, d) — the partials, or dk / dv themselves when hq = hkv)
+        const size_t krow = VAR ? ((size_t)(sk0 + key) * p.hq + hh) * DR : ((size_t)bh * nk + key) * DR;
+        uint16_t* dkrow = dk + krow;
+        uint16_t* dvrow = dv + krow;
 #pragma unroll
         for (int db = 0; db < NDB; ++db)
 #pragma unroll
@@ -727,7 +794,6 @@ __global__ __launch_bounds__(512, 2) void exm_dkdv_kernel(const uint16_t* __rest
             }
     }
 }
-
 // ------------------------------------------------------------------------------------------------ dQ
 template <typename Tag, int D, int FEAT>
 __global__ __launch_bounds__(512, 2) void exm_dq_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
@@ -735,36 +801,45 @@ __global__ __launch_bounds__(512, 2) void exm_dq_kernel(const uint16_t* __restri
                                                         const float* __restrict__ nlse, const float* __restrict__ ndelta,
                                                         uint16_t* __restrict__ dq, ExParams p, float c_log2) {
     constexpr int NW = 8, BM = 32 * NW, BN = 64, NKS = D / 16, NDB = D / 32, TILE_BYTES = BN * D * 2;
+    constexpr bool VAR = (FEAT & kFeatVarlen) != 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 buffers][K tile | V tile]
-    const int DR = p.d, nq = p.nq, nk = p.nk;
+    const int DR = p.d;
+    int nq = p.nq, nk = p.nk;
     const int nqt = (nq + BM - 1) / BM;
     const int L = xcd_remap(blockIdx.x, gridDim.x);
     const int bh = L / nqt;
     const int q0 = (L - bh * nqt) * BM;
+    EXM_VARLEN_UNIT(q0, nq)
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
-    const size_t qbase = (size_t)bh * nq * DR, kbase = (size_t)kv_unit(bh, p.kvg) * nk * DR;
+    const size_t qbase = VAR ? (size_t)sq0 * p.sq + hh * DR : (size_t)bh * nq * DR;
+    const size_t kbase = VAR ? (size_t)sk0 * p.sk + hk * DR : (size_t)kv_unit(bh, p.kvg) * nk * DR;
+    const size_t vbase = VAR ? (size_t)sk0 * p.sv + hk * DR : kbase;
+    const size_t obase = VAR ? ((size_t)sq0 * p.hq + hh) * DR : qbase;
+    const size_t rbase = VAR ? (size_t)hh * p.total_q + sq0 : (size_t)bh * nq;
+    const int ostr = VAR ? p.hq * DR : DR;   // rows of dout and dq
     const int qrow = q0 + 32 * w + r;
     const bool live_row = qrow < nq;
 
-    const buf_rsrc_t q_rs = make_rsrc(q + qbase, (unsigned)nq * DR * 2);
-    const buf_rsrc_t o_rs = make_rsrc(dout + qbase, (unsigned)nq * DR * 2);
+    const buf_rsrc_t q_rs = make_rsrc(q + qbase, VAR ? span_bytes(nq, DR, p.sq) : (unsigned)nq * DR * 2);
+    const buf_rsrc_t o_rs = make_rsrc(dout + obase, VAR ? span_bytes(nq, DR, ostr) : (unsigned)nq * DR * 2);
     s16x8 qf[NKS], of[NKS];
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) {
-        qf[ks] = buf_load_frag(q_rs, frag_off(qrow, 16 * ks + 8 * h, DR, true));
-        of[ks] = buf_load_frag(o_rs, frag_off(qrow, 16 * ks + 8 * h, DR, true));
+        qf[ks] = buf_load_frag(q_rs, frag_off<VAR>(qrow, 16 * ks + 8 * h, DR, true, VAR ? p.sq : DR));
+        of[ks] = buf_load_frag(o_rs, frag_off<VAR>(qrow, 16 * ks + 8 * h, DR, true, ostr));
     }
-    const float nl = live_row ? nlse[(size_t)bh * nq + qrow] : 0.f;
-    const float nd = live_row ? ndelta[(size_t)bh * nq + qrow] : 0.f;
+    const float nl = live_row ? nlse[rbase + qrow] : 0.f;
+    const float nd = live_row ? ndelta[rbase + qrow] : 0.f;
 
-    const rsrc_s_t k_rs = make_rsrc_s(k + kbase, (unsigned)nk * DR * 2);
-    const rsrc_s_t v_rs = make_rsrc_s(v + kbase, (unsigned)nk * DR * 2);
-    const int dma_voff = dma_lane_voff<D>(lane, w, DR);
+    const rsrc_s_t k_rs = make_rsrc_s(k + kbase, VAR ? span_bytes(nk, DR, p.sk) : (unsigned)nk * DR * 2);
+    const rsrc_s_t v_rs = make_rsrc_s(v + vbase, VAR ? span_bytes(nk, DR, p.sv) : (unsigned)nk * DR * 2);
+    const int dma_voff = dma_lane_voff<D, VAR>(lane, w, DR, VAR ? p.sk : DR);
+    const int dma_voff_v = VAR ? dma_lane_voff<D, VAR>(lane, w, DR, p.sv) : dma_voff;
     auto stage = [&](int buf, int k0) {
         char* kb_ = smem + buf * 2 * TILE_BYTES;
-        dma_stage_tile<D, BN, NW>(k_rs, kb_, k0, dma_voff, w, DR);
-        dma_stage_tile<D, BN, NW>(v_rs, kb_ + TILE_BYTES, k0, dma_voff, w, DR);
+        dma_stage_tile<D, BN, NW, VAR>(k_rs, kb_, k0, dma_voff, w, DR, 0, VAR ? p.sk : DR);
+        dma_stage_tile<D, BN, NW, VAR>(v_rs, kb_ + TILE_BYTES, k0, dma_voff_v, w, DR, 0, VAR ? p.sv : DR);
     };
     const MaskSrc msk = make_mask_src(p, bh);
     const bool use_bm = (FEAT & kFeatMask) && p.bmask != nullptr;
@@ -904,7 +979,7 @@ __global__ __launch_bounds__(512, 2) void exm_dq_kernel(const uint16_t* __restri
         t = tn;
     }
     if (live_row) {
-        uint16_t* drow = dq + qbase + (size_t)qrow * DR;
+        uint16_t* drow = dq + obase + (size_t)qrow * ostr;
 #pragma unroll
         for (int db = 0; db < NDB; ++db)
 #pragma unroll
@@ -917,7 +992,6 @@ __global__ __launch_bounds__(512, 2) void exm_dq_kernel(const uint16_t* __restri
             }
     }
 }
-
 // ------------------------------------------------------------------------------------------------ host side
 bool ex_mfma_supported(const ExArgs& a) {
     if (a.dtype != 1 && a.dtype != 2) return false;
@@ -990,6 +1064,81 @@ static hipError_t exm_by_feat(const ExArgs& a, bool backward, hipStream_t st) {
     if (drop) return backward ? exm_bwd_t<Tag, D, 3>(a, st) : exm_fwd_t<Tag, D, 3>(a, st);
     if (masks) return backward ? exm_bwd_t<Tag, D, 1>(a, st) : exm_fwd_t<Tag, D, 1>(a, st);
     return backward ? exm_bwd_t<Tag, D, 0>(a, st) : exm_fwd_t<Tag, D, 0>(a, st);
+}
+
+// ---- packed sequences: the varlen kernels on the padded grid (a.bh = batch * heads_q units, a.nq / a.nk = the maxima)
+bool ex_mfma_varlen_supported(const ExArgs& a) {
+    if (!ex_mfma_supported(a)) return false;
+    if (a.stride_q % 8 != 0 || a.stride_k % 8 != 0 || a.stride_v % 8 != 0) return false;   // 16-byte rows
+    const void* ptrs[] = {a.q, a.k, a.v, a.o, a.dout, a.dq, a.dk, a.dv};
+    for (const void* ptr : ptrs)
+        if ((reinterpret_cast<uintptr_t>(ptr) & 15) != 0) return false;
+    int64_t smax = a.heads_q * a.d;   // o, dout, dq rows
+    if (a.stride_q > smax) smax = a.stride_q;
+    if (a.stride_k > smax) smax = a.stride_k;
+    if (a.stride_v > smax) smax = a.stride_v;
+    const int64_t nmax = a.nq > a.nk ? a.nq : a.nk;
+    return nmax * smax * 2 < ((int64_t)1 << 31);   // the 32-bit buffer offsets inside one sequence
+}
+
+template <typename Tag, int D, int FEAT>
+static hipError_t exm_varlen_t(const ExArgs& a, bool backward, hipStream_t st) {
+    const ExParams p = make_ex_params(a);
+    const float c = a.scale * 1.4426950408889634f;
+    hipError_t e;
+    if (!backward) {
+        const size_t smem = 2 * 2 * 128 * D * 2;
+        auto kern = exm_fwd_kernel<Tag, D, FEAT | kFeatVarlen>;
+        e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
+        if (e != hipSuccess) return e;
+        ProfScope ps(K_EX_FWD, st);
+        hipLaunchKernelGGL(kern, dim3((unsigned)(((a.nq + 255) / 256) * a.bh)), dim3(512), smem, st, (const uint16_t*)a.q,
+                           (const uint16_t*)a.k, (const uint16_t*)a.v, (uint16_t*)a.o, a.lse, p, c);
+        return hipGetLastError();
+    }
+    // workspace: [-lse/scale | -delta], (heads_q, total_q) each
+    const long long rows = (long long)a.heads_q * a.total_q;
+    float* nlse = reinterpret_cast<float*>(a.workspace);
+    float* ndelta = nlse + ((rows + 63) & ~63ll);
+    const int tph = (int)((a.total_q + 15) / 16);
+    ProfScope ps(K_EX_BWD, st);
+    hipLaunchKernelGGL(exm_prep_varlen_kernel<Tag>, dim3((unsigned)(tph * a.heads_q)), dim3(256), 0, st, (const uint16_t*)a.o,
+                       (const uint16_t*)a.dout, (const float*)a.lse, nlse, ndelta, (int)a.total_q, tph, (int)a.heads_q, (int)a.d,
+                       1.f / a.scale);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    {
+        const size_t smem = (size_t)256 * D * 2 + 4 * 64 * D * 2 + 2 * 128 * sizeof(float);
+        auto kern = exm_dkdv_kernel<Tag, D, FEAT | kFeatVarlen>;
+        e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(((a.nk + 255) / 256) * a.bh)), dim3(512), smem, st, (const uint16_t*)a.q,
+                           (const uint16_t*)a.k, (const uint16_t*)a.v, (const uint16_t*)a.dout, (const float*)nlse, (const float*)ndelta,
+                           (uint16_t*)a.dk, (uint16_t*)a.dv, p, c);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    const size_t smem = 2 * 2 * 64 * D * 2;
+    auto kern = exm_dq_kernel<Tag, D, FEAT | kFeatVarlen>;
+    e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(((a.nq + 255) / 256) * a.bh)), dim3(512), smem, st, (const uint16_t*)a.q,
+                       (const uint16_t*)a.k, (const uint16_t*)a.v, (const uint16_t*)a.dout, (const float*)nlse, (const float*)ndelta,
+                       (uint16_t*)a.dq, p, c);
+    return hipGetLastError();
+}
+
+template <typename Tag, int D>
+static hipError_t exm_varlen_by_feat(const ExArgs& a, bool backward, hipStream_t st) {
+    const bool drop = a.dropout_p > 0.0;
+    if (ex_windowed(a)) return drop ? exm_varlen_t<Tag, D, kFeatWindow | kFeatDrop>(a, backward, st) : exm_varlen_t<Tag, D, kFeatWindow>(a, backward, st);
+    return drop ? exm_varlen_t<Tag, D, kFeatDrop>(a, backward, st) : exm_varlen_t<Tag, D, 0>(a, backward, st);
+}
+
+// (the caller has checked ex_mfma_varlen_supported, and that max_seqlen_q, max_seqlen_k, total_q, total_k are > 0)
+hipError_t launch_ex_mfma_varlen(const ExArgs& a, bool backward, hipStream_t st) {
+    if (a.dtype == 2) return a.d > 64 ? exm_varlen_by_feat<bf16_tag, 128>(a, backward, st) : exm_varlen_by_feat<bf16_tag, 64>(a, backward, st);
+    return a.d > 64 ? exm_varlen_by_feat<f16_tag, 128>(a, backward, st) : exm_varlen_by_feat<f16_tag, 64>(a, backward, st);
 }
 
 hipError_t launch_ex_mfma(const ExArgs& a, bool backward, hipStream_t st) {

@@ -140,12 +140,21 @@ struct ExArgs {
     // j >= i + (nk - nq) - window_left and j <= i + (nk - nq) + window_right; -1 = unbounded on that side.  After
     // canonicalisation a bound that is not -1 bounds something, and causal != 0 comes with window_right = -1.
     int64_t window_left = -1, window_right = -1;
+    // variable-length (packed) sequences (fa_ex_*_varlen; cu_q != null): bh = batch * heads_q units, nq / nk = max_seqlen_q / _k
+    // (the padded call's grid and dropout counters), the window canonicalised against them.  q: (total_q, heads_q, d) at token
+    // stride stride_q, k / v: (total_k, heads_q / kv_group, d) at stride_k / stride_v; o, dout, dq dense (total_q, heads_q, d),
+    // lse (heads_q, total_q); dk, dv dense (total_k, heads_q / kv_group, d).  cu_q / cu_k: batch + 1 untrusted device offsets.
+    const int* cu_q = nullptr;
+    const int* cu_k = nullptr;
+    int64_t heads_q = 0, total_q = 0, total_k = 0, stride_q = 0, stride_k = 0, stride_v = 0;
 };
 // does the call carry a window that bounds something (canonicalised: any bound that is not -1)?
 inline bool ex_windowed(const ExArgs& a) { return a.window_left >= 0 || a.window_right >= 0; }
 hipError_t launch_ex(const ExArgs& a, bool backward, hipStream_t st);
 bool ex_mfma_supported(const ExArgs& a);
 hipError_t launch_ex_mfma(const ExArgs& a, bool backward, hipStream_t st);
+bool ex_mfma_varlen_supported(const ExArgs& a);
+hipError_t launch_ex_mfma_varlen(const ExArgs& a, bool backward, hipStream_t st);
 size_t ex_backward_workspace_bytes(int64_t bh, int64_t nq);
 // the two per-query-head dK / dV partial slabs of a grouped backward (kv_group > 1), each rounded to 256 bytes
 inline size_t kv_partial_bytes(int64_t bh, int64_t nk, int64_t d, int dtype) {

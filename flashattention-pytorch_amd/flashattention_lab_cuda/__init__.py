@@ -38,6 +38,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_ex_forward", "fa_ex_backward", "fa_ex_backward_workspace_bytes", "fa_ex_backward_workspace_bytes_fast",
     "fa_ex_forward_grouped", "fa_ex_backward_grouped", "fa_ex_backward_workspace_bytes_grouped",
     "fa_ex_backward_workspace_bytes_fast_grouped", "fa_ex_forward_window", "fa_ex_backward_window",
+    "fa_ex_forward_varlen", "fa_ex_backward_varlen", "fa_ex_backward_workspace_bytes_varlen",
 )
 
 
@@ -110,6 +111,15 @@ def _load_library() -> ctypes.CDLL:
     lib.fa_ex_backward_window.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, ci, i64, i64, dbl, vp, i64, vp,
                                           i64, i64, dbl, u64, vp, sz, vp]
     lib.fa_ex_backward_window.restype = ci
+    # packed sequences: cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype,
+    # the three token strides, causal, window_left, window_right, softmax_scale, dropout_p, seed
+    varlen = [vp, vp, i64, i64, i64, i64, i64, i64, i64, i64, ci, i64, i64, i64, ci, i64, i64, dbl, dbl, u64]
+    lib.fa_ex_forward_varlen.argtypes = [vp, vp, vp, vp, vp] + varlen + [vp]
+    lib.fa_ex_forward_varlen.restype = ci
+    lib.fa_ex_backward_varlen.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp] + varlen + [vp, sz, vp]
+    lib.fa_ex_backward_varlen.restype = ci
+    lib.fa_ex_backward_workspace_bytes_varlen.argtypes = [i64, i64, i64, i64, i64, ci]
+    lib.fa_ex_backward_workspace_bytes_varlen.restype = sz
     return lib
 
 
@@ -413,4 +423,91 @@ def ex_backward(q, k, v, o, do_, lse, causal, softmax_scale, mask=None, block_ma
             _check(_lib.fa_ex_backward_grouped(*ptrs, bh, g, *rest))
         else:
             _check(_lib.fa_ex_backward(*ptrs, bh, *rest))
+    return dq, dk, dv
+
+
+# ---- variable-length (packed) sequences (include/fa_mi355x.h: fa_ex_forward_varlen / fa_ex_backward_varlen) ----
+
+def _token_stride(who, name, t, heads, d):
+    """Token stride (elements) of a (total, heads, d) tensor whose heads are adjacent at stride d, last dim contiguous."""
+    if t.stride(2) != 1:
+        raise RuntimeError(f"{who}: {name} must have a contiguous last dim")
+    if t.shape[0] > 0 and heads > 1 and t.stride(1) != d:
+        raise RuntimeError(f"{who}: the heads of {name} must be adjacent (head stride d = {d}, got {t.stride(1)})")
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), heads * d)
+
+
+def _varlen_common(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k):
+    for t in (q, k, v, cu_seqlens_q, cu_seqlens_k):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{who}: tensors must be on the GPU (HIP device); there is no CPU path")
+    if q.dim() != 3 or k.dim() != 3 or v.shape != k.shape or q.shape[2] != k.shape[2]:
+        raise RuntimeError(f"{who}: q must be (total_q, H_q, d), k and v (total_k, H_kv, d); got {tuple(q.shape)}, {tuple(k.shape)}, "
+                           f"{tuple(v.shape)}")
+    if q.dtype not in _DTYPE_CODE or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise RuntimeError(f"{who}: q, k, v must share a supported dtype")
+    if len({q.device, k.device, v.device, cu_seqlens_q.device, cu_seqlens_k.device}) != 1:
+        raise RuntimeError(f"{who}: all tensors must be on one device")
+    for name, c in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if c.dtype != torch.int32 or c.dim() != 1 or c.shape[0] < 2:
+            raise RuntimeError(f"{who}: {name} must be a 1-D int32 tensor of batch + 1 >= 2 offsets")
+    if cu_seqlens_q.shape != cu_seqlens_k.shape:
+        raise RuntimeError(f"{who}: cu_seqlens_q and cu_seqlens_k must have the same length (batch + 1)")
+    total_q, hq, d = q.shape
+    total_k, hkv = k.shape[0], k.shape[1]
+    if hkv == 0 or hq % hkv != 0:
+        raise RuntimeError(f"{who}: the query heads ({hq}) must be a multiple of the K/V heads ({hkv})")
+    mq, mk = operator.index(max_seqlen_q), operator.index(max_seqlen_k)
+    if mq < 0 or mk < 0:
+        raise RuntimeError(f"{who}: max_seqlen_q, max_seqlen_k must be >= 0")
+    sq = _token_stride(who, "q", q, hq, d)
+    sk = _token_stride(who, "k", k, hkv, d)
+    sv = _token_stride(who, "v", v, hkv, d)
+    cu_q, cu_k = cu_seqlens_q.contiguous(), cu_seqlens_k.contiguous()
+    return (cu_q, cu_k, cu_q.shape[0] - 1, hq, hkv, total_q, total_k, mq, mk, d, _DTYPE_CODE[q.dtype], sq, sk, sv)
+
+
+def ex_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, dropout_p=0.0, seed=0,
+                      window=(-1, -1)):
+    """(o, lse) of attention over packed sequences (FlashAttention-2's varlen layout): q (total_q, H_q, d), k and v
+    (total_k, H_kv, d) — strided views along the token dim allowed — cu_seqlens_* int32 (batch + 1,) device offsets.  o is
+    (total_q, H_q, d), lse (H_q, total_q) float32.  Never synchronises: cu_seqlens are clamped in the kernels."""
+    who = "ex_varlen_forward"
+    wl, wr = window_arg(who, window)
+    cu_q, cu_k, *dims = _varlen_common(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
+    _b, hq, _hkv, total_q, *_ = dims
+    d = q.shape[2]
+    with torch.cuda.device(q.device):
+        o = torch.empty((total_q, hq, d), dtype=q.dtype, device=q.device)
+        lse = torch.empty((hq, total_q), dtype=torch.float32, device=q.device)
+        _check(_lib.fa_ex_forward_varlen(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), cu_q.data_ptr(),
+                                         cu_k.data_ptr(), *dims, int(bool(causal)), wl, wr, float(softmax_scale), float(dropout_p),
+                                         int(seed) & (2 ** 64 - 1), _stream_ptr(q.device)))
+    return o, lse
+
+
+def ex_varlen_backward(q, k, v, o, do_, lse, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale,
+                       dropout_p=0.0, seed=0, window=(-1, -1)):
+    """(dq, dk, dv) of ex_varlen_forward: dq in q's (total_q, H_q, d) shape, dk and dv in k's and v's (dense)."""
+    who = "ex_varlen_backward"
+    wl, wr = window_arg(who, window)
+    cu_q, cu_k, *dims = _varlen_common(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
+    _b, hq, hkv, total_q, total_k, _mq, _mk, d, code = dims[:9]
+    for name, t in (("o", o), ("do", do_)):
+        if not t.is_cuda or t.shape != (total_q, hq, d) or t.dtype != q.dtype:
+            raise RuntimeError(f"{who}: {name} must be a (total_q, H_q, d) device tensor of q's dtype")
+    if not lse.is_cuda or lse.shape != (hq, total_q) or lse.dtype != torch.float32:
+        raise RuntimeError(f"{who}: lse must be a (H_q, total_q) float32 device tensor")
+    o, do_, lse = o.contiguous(), do_.contiguous(), lse.contiguous()
+    with torch.cuda.device(q.device):
+        dq = torch.empty((total_q, hq, d), dtype=q.dtype, device=q.device)
+        dk = torch.empty((total_k, hkv, d), dtype=q.dtype, device=q.device)
+        dv = torch.empty((total_k, hkv, d), dtype=q.dtype, device=q.device)
+        nbytes = int(_lib.fa_ex_backward_workspace_bytes_varlen(hq, hkv, total_q, total_k, d, code))
+        ws = _workspace(q.device, nbytes)
+        nbytes = max(nbytes, 0 if torch.cuda.is_current_stream_capturing() else _workspaces.capacity(q.device, _stream_ptr(q.device)))
+        _check(_lib.fa_ex_backward_varlen(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do_.data_ptr(), lse.data_ptr(),
+                                          dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr(), *dims,
+                                          int(bool(causal)), wl, wr, float(softmax_scale), float(dropout_p), int(seed) & (2 ** 64 - 1),
+                                          ws.data_ptr(), nbytes, _stream_ptr(q.device)))
     return dq, dk, dv

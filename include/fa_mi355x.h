@@ -202,6 +202,49 @@ int fa_ex_backward_window(const void* q, const void* k, const void* v, const voi
                           double dropout_p, uint64_t dropout_seed,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* --- Variable-length (packed) sequences: FlashAttention-2's varlen layout.  Sequence b (0 <= b < batch) is tokens
+ * [cu_seqlens_q[b], cu_seqlens_q[b+1]) of q, o, do, dq and [cu_seqlens_k[b], cu_seqlens_k[b+1]) of k, v, dk, dv; cu_seqlens_* are
+ * int32 device arrays of batch + 1 entries.
+ *     q (total_q, heads_q, d), token stride q_stride elements (>= heads_q * d; the heads of a token adjacent at stride d);
+ *     k, v (total_k, heads_kv, d), token strides k_stride, v_stride (>= heads_kv * d): views such as qkv.unbind(1) of a
+ *     (total, 3, H, d) projection go in without a copy;  o, do, dq (total_q, heads_q, d) and dk, dv (total_k, heads_kv, d)
+ *     dense;  lse (heads_q, total_q) float32.
+ * Attention never crosses a sequence.  In each sequence, with len_q, len_k its lengths and coff = len_k - len_q, the fa_ex_*_window
+ * rules hold in the sequence's own coordinates: causal is bottom-right aligned per sequence, the window (window_left,
+ * window_right) bounds keys to [i + coff - window_left, i + coff + window_right], query head h reads K/V head
+ * h / (heads_q / heads_kv).  A row without a visible key gives o = 0, lse = -inf, dq = 0; a key no row sees dk = dv = 0 (every
+ * key of a sequence with len_q = 0).  Empty sequences are allowed.
+ * Dropout: unit u = b * heads_q + h, row and key inside the sequence, ceil(max_seqlen_q / 2) row pairs per unit — the counters of
+ * the padded (batch * heads_q, max_seqlen_q, max_seqlen_k) fa_ex call, so its keep mask restricted to [u, :len_q, :len_k] is this
+ * call's.  The mask therefore depends on the max_seqlen_q passed.
+ * cu_seqlens are not read on the host (that would take a synchronise) and are not trusted: the kernels use
+ * start = clamp(cu[b], 0, total), end = clamp(cu[b+1], start, total), len = min(end - start, max_seqlen), so that malformed
+ * offsets never make them read or write outside the packed tensors.  Outputs at tokens that no sequence covers are unspecified.
+ * Checked before any HIP call (FA_ERR_INVALID_ARGUMENT): dtype, batch >= 1, heads_q a positive multiple of heads_kv, d > 0,
+ * totals and max_seqlen >= 0, strides >= heads * d, non-null cu_seqlens where the total is > 0, window bounds >= -1, the NaN
+ * scale, dropout_p in [0, 1), batch * heads_q * ceil(max_seqlen_q / 2) < 2^32.  The window is canonicalised against max_seqlen_q
+ * and max_seqlen_k (a bound that cuts nothing there cuts nothing in any sequence).  No dense or block-sparse mask.
+ * Kernels: the extended ones only — 16-bit MFMA for f16 / bf16, d % 8 == 0, d <= 128, strides multiples of 8 elements, 16-byte
+ * aligned tensors and max_seqlen * stride * 2 < 2^31; exact f32 otherwise (d <= 256).  The grid is that of the padded call:
+ * ceil(max_seqlen / tile) * batch * heads_q workgroups, those past their sequence's end leave at once.
+ * Backward workspace: fa_ex_backward_workspace_bytes_varlen (row constants; with heads_kv < heads_q also the per-query-head dK / dV
+ * partials, (total_k, heads_q, d) each, which are added in fp32 over each group in a fixed order). */
+int fa_ex_forward_varlen(const void* q, const void* k, const void* v, void* o, float* lse,
+                         const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                         int64_t total_q, int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype,
+                         int64_t q_stride, int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
+                         double softmax_scale, double dropout_p, uint64_t dropout_seed, void* stream);
+
+int fa_ex_backward_varlen(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse,
+                          void* dq, void* dk, void* dv,
+                          const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                          int64_t total_q, int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype,
+                          int64_t q_stride, int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
+                          double softmax_scale, double dropout_p, uint64_t dropout_seed,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
+size_t fa_ex_backward_workspace_bytes_varlen(int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t d, int dtype);
+
 /* --- support entry points (no reference counterpart: the reference allocates inside the callee) --- */
 /* bytes for the CURRENT kernel mode: two float row constants per query row (+ an fp32 dQ scratch of bh*n*d floats in
  * FA_MODE_BWD_ATOMIC only); ask again after changing the mode */

@@ -17,6 +17,15 @@ on the same kernel family (--paths, one of them; default mfma), timed alternatel
 TFLOP/s (4 / 10 x visible pairs x d, the pairs counted from the shapes).
 
     python tools/bench_ex.py --window 1024,0 --causal [--bh 32] [--nq 16384] [--nk 16384] [--head-dim 128] [--rounds 3]
+
+Packed sequences (--varlen LENS: NxB = B sequences of N tokens, or mix:COUNT:LO:HI = a seeded (--seed) mix of COUNT lengths in
+[LO, HI]): the varlen call (fa_ex_*_varlen, --q-heads, --kv-heads one count, default = --q-heads; --causal) timed alternately in
+one process against, with equal lengths, the same tensors in (B*H, N, d) layout through the extended MFMA kernels (ex_path 3);
+with a mix, (a) padding to the longest with a key-padding mask through flash_attention_ex's entry points and (b) one call per
+sequence.  Forward and backward, visible-pair TFLOP/s (4 / 10 x visible pairs x d).
+
+    python tools/bench_ex.py --varlen 4096x8 [--causal] [--q-heads 32] [--head-dim 128] [--rounds 3]
+    python tools/bench_ex.py --varlen mix:16:256:8192 --causal --q-heads 32 --kv-heads 8 [--seed 0]
 """
 import argparse
 import json
@@ -55,7 +64,11 @@ def main():
     ap.add_argument("--window", default="", help="L,R: time a sliding window against its dense mask and the causal call")
     ap.add_argument("--causal", action="store_true", help="(--window) the causal flag with the window")
     ap.add_argument("--rounds", type=int, default=3, help="(--window) alternations of the three calls")
+    ap.add_argument("--varlen", default="", help="NxB or mix:COUNT:LO:HI: time packed sequences")
+    ap.add_argument("--seed", type=int, default=0, help="(--varlen mix) the lengths' seed")
     args = ap.parse_args()
+    if args.varlen:
+        return bench_varlen(args)
     if args.kv_heads:
         return bench_gqa(args)
     if args.window:
@@ -222,6 +235,85 @@ def bench_window(args):
                                            (pairs["causal"] / by["causal"]["fwd_bwd_ms"]), 3))
     print(json.dumps(dict(shape=dict(bh=bh, nq=nq, nk=nk, d=d, dtype=args.dtype, window=[wl, wr], causal=args.causal,
                                      kernels=path, iters=args.iters, rounds=args.rounds), rows=rows, summary=summary), indent=1))
+
+
+def varlen_lengths(spec, seed):
+    if spec.startswith("mix:"):
+        _, count, lo, hi = spec.split(":")
+        g = torch.Generator().manual_seed(seed)
+        return torch.randint(int(lo), int(hi) + 1, (int(count),), generator=g).tolist()
+    n, b = spec.lower().split("x")
+    return [int(n)] * int(b)
+
+
+def bench_varlen(args):
+    dt = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[args.dtype]
+    lens = varlen_lengths(args.varlen, args.seed)
+    hq = args.q_heads
+    hkv = int(args.kv_heads) if args.kv_heads else hq
+    d, causal, scale, B = args.head_dim, args.causal, args.head_dim ** -0.5, len(lens)
+    total, mx = sum(lens), max(lens)
+    g = torch.Generator(device="cuda").manual_seed(0)
+    q = torch.randn((total, hq, d), device="cuda", dtype=dt, generator=g)
+    k, v = (torch.randn((total, hkv, d), device="cuda", dtype=dt, generator=g) for _ in range(2))
+    do = torch.randn((total, hq, d), device="cuda", dtype=dt, generator=g)
+    cu = torch.tensor([0] + torch.tensor(lens).cumsum(0).tolist(), dtype=torch.int32, device="cuda")
+    pairs = sum(hq * (n * (n + 1) // 2 if causal else n * n) for n in lens)
+    calls = {}
+    o, lse = ext.ex_varlen_forward(q, k, v, cu, cu, mx, mx, causal, scale)
+    calls["varlen"] = (lambda: ext.ex_varlen_forward(q, k, v, cu, cu, mx, mx, causal, scale),
+                       lambda: ext.ex_varlen_backward(q, k, v, o, do, lse, cu, cu, mx, mx, causal, scale), pairs)
+
+    def heads_first(t, n):   # (B*n, H, d) -> (B*H, n, d)
+        return t.view(-1, n, t.shape[1], d).transpose(1, 2).reshape(-1, n, d).contiguous()
+
+    if len(set(lens)) == 1:   # the same tensors in (B*H, N, d) layout
+        n = lens[0]
+        q3, k3, v3, do3 = (heads_first(t, n) for t in (q, k, v, do))
+        o3, lse3 = ext.ex_forward(q3, k3, v3, causal, scale)
+        calls["bhnd"] = (lambda: ext.ex_forward(q3, k3, v3, causal, scale),
+                         lambda: ext.ex_backward(q3, k3, v3, o3, do3, lse3, causal, scale), pairs)
+    else:
+        # (a) padded to the longest, keys past each sequence masked: (B*H, max, max) mask bytes
+        qp, kp, vp, dop = (torch.zeros((B * t.shape[1], mx, d), device="cuda", dtype=dt) for t in (q, k, v, do))
+        kpm = torch.zeros((B, mx), dtype=torch.uint8, device="cuda")
+        s0 = 0
+        for b, n in enumerate(lens):
+            for src, dst in ((q, qp), (k, kp), (v, vp), (do, dop)):
+                h = src.shape[1]
+                dst[b * h:(b + 1) * h, :n] = src[s0:s0 + n].transpose(0, 1)
+            kpm[b, :n] = 1
+            s0 += n
+        mask = kpm[:, None, None, :].expand(B, hq, mx, mx).reshape(B * hq, mx, mx).contiguous()
+        op, lsep = ext.ex_forward(qp, kp, vp, causal, scale, mask=mask)
+        calls["padded_mask"] = (lambda: ext.ex_forward(qp, kp, vp, causal, scale, mask=mask),
+                                lambda: ext.ex_backward(qp, kp, vp, op, dop, lsep, causal, scale, mask=mask), pairs)
+        # (b) one call per sequence
+        seqs, s0 = [], 0
+        for n in lens:
+            qs, ks, vs, dos = (t[s0:s0 + n].transpose(0, 1).contiguous() for t in (q, k, v, do))
+            os_, ls_ = ext.ex_forward(qs, ks, vs, causal, scale)
+            seqs.append((qs, ks, vs, dos, os_, ls_))
+            s0 += n
+        calls["per_sequence"] = (lambda: [ext.ex_forward(a[0], a[1], a[2], causal, scale) for a in seqs],
+                                 lambda: [ext.ex_backward(a[0], a[1], a[2], a[4], a[3], a[5], causal, scale) for a in seqs], pairs)
+    times = {name: ([], []) for name in calls}
+    ext.set_option("ex_path", 3 if len(set(lens)) == 1 else 0)   # equal lengths: the extended MFMA kernels on both sides
+    try:
+        for _ in range(args.rounds):
+            for name, (f, b, _p) in calls.items():
+                times[name][0].append(timed(f, args.iters))
+                times[name][1].append(timed(b, args.iters))
+    finally:
+        ext.set_option("ex_path", 0)
+    rows = []
+    for name, (_f, _b, p) in calls.items():
+        tf, tb = sorted(times[name][0])[len(times[name][0]) // 2], sorted(times[name][1])[len(times[name][1]) // 2]
+        rows.append(dict(call=name, fwd_ms=round(tf, 3), bwd_ms=round(tb, 3), fwd_bwd_ms=round(tf + tb, 3),
+                         fwd_tflops=round(4 * p * d / tf / 1e9, 1), bwd_tflops=round(10 * p * d / tb / 1e9, 1),
+                         fwd_ms_all=[round(x, 3) for x in times[name][0]], bwd_ms_all=[round(x, 3) for x in times[name][1]]))
+    print(json.dumps(dict(shape=dict(lens=lens, total=total, q_heads=hq, kv_heads=hkv, d=d, dtype=args.dtype, causal=causal,
+                                     visible_pairs=pairs, iters=args.iters, rounds=args.rounds), rows=rows), indent=1))
 
 
 if __name__ == "__main__":
