@@ -4,7 +4,8 @@
 extended entry points (`fa_ex_forward` / `fa_ex_backward`, include/fa_mi355x.h):
 
     flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, block_size=128,
-                       causal=False, dropout_p=0.0, seed=0, softmax_scale=None, window_size=(-1, -1)) -> o
+                       causal=False, dropout_p=0.0, seed=0, softmax_scale=None, window_size=(-1, -1),
+                       softcap=0.0, alibi_slopes=None) -> o
 
 q: (B, H, Nq, d) or (BH, Nq, d); k, v: (B, H_kv, Nk, d) or (B*H_kv, Nk, d).  H_kv < H is grouped-query attention (GQA; H_kv = 1:
 multi-query attention) with H % H_kv == 0: query head h reads K/V head h // (H / H_kv), with no copy of K and V, and the
@@ -15,7 +16,10 @@ broadcastable to (B, H, Nq, Nk), True / 1 = allowed (`look_ahead_mask_` builds t
 argument) in the causal flag's coordinates: key j is visible to query i only if i + Nk - Nq - left <= j <= i + Nk - Nq + right,
 -1 = unbounded on that side; `causal=True, window_size=(left, -1)` is the usual causal local attention.  It composes with every
 other argument (GQA K/V included), and the kernels visit only the tiles of each row's band (fa_ex_forward_window); a window
-that bounds nothing is the call without one, bit for bit.  Differentiable (autograd Function; the backward recomputes P and
+that bounds nothing is the call without one, bit for bit.  `softcap` > 0 (Gemma-2 style) replaces each score s = scale q.k by
+softcap * tanh(s / softcap), and `alibi_slopes` (float32 (H,) or (B, H) for 4-D q, (BH,) for 3-D q; BLOOM / MPT style) then
+subtracts slope * |i + Nk - Nq - j|, FlashAttention-2's arguments of the same names; the slopes get no gradient
+(fa_ex_forward_scoremod).  softcap = 0 without slopes is the call without them, bit for bit.  Differentiable (autograd Function; the backward recomputes P and
 regenerates the dropout mask from the seed).  No CPU path: the tensors must live on the GPU.
 """
 from __future__ import annotations
@@ -60,12 +64,13 @@ def normalize_mask(mask, lead, nq, nk):
 
 class _FlashAttnExFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale, mask, block_mask, br, bc, dropout_p, seed, window):
+    def forward(ctx, q, k, v, causal, scale, mask, block_mask, br, bc, dropout_p, seed, window, softcap=0.0, alibi_slopes=None):
         import flashattention_lab_cuda as ext
 
-        o, lse = ext.ex_forward(q, k, v, causal, scale, mask, block_mask, br, bc, dropout_p, seed, window=window)
+        o, lse = ext.ex_forward(q, k, v, causal, scale, mask, block_mask, br, bc, dropout_p, seed, window=window, softcap=softcap,
+                                alibi_slopes=alibi_slopes)
         ctx.save_for_backward(q, k, v, o, lse)
-        ctx.args = (causal, scale, mask, block_mask, br, bc, dropout_p, seed, window)
+        ctx.args = (causal, scale, mask, block_mask, br, bc, dropout_p, seed, window, softcap, alibi_slopes)
         return o
 
     @staticmethod
@@ -73,10 +78,10 @@ class _FlashAttnExFn(torch.autograd.Function):
         import flashattention_lab_cuda as ext
 
         q, k, v, o, lse = ctx.saved_tensors
-        causal, scale, mask, block_mask, br, bc, dropout_p, seed, window = ctx.args
+        causal, scale, mask, block_mask, br, bc, dropout_p, seed, window, softcap, alibi_slopes = ctx.args
         dq, dk, dv = ext.ex_backward(q, k, v, o, do.contiguous(), lse, causal, scale, mask, block_mask, br, bc, dropout_p, seed,
-                                     window=window)
-        return (dq, dk, dv) + (None,) * 9
+                                     window=window, softcap=softcap, alibi_slopes=alibi_slopes)
+        return (dq, dk, dv) + (None,) * 11   # (no gradient for the slopes, as in FlashAttention-2)
 
 
 def _window_size(window_size):
@@ -93,8 +98,20 @@ def _window_size(window_size):
     return left, right
 
 
+def _alibi_units(slopes, lead):
+    """4-D q (lead = (B, H)): FlashAttention-2's (H,) slopes as a (B, H) view with row stride 0 (no copy); the library checks
+    the rest (dtype, device, shape, layout: flashattention_lab_cuda.alibi_arg)."""
+    if slopes is None or len(lead) != 2 or not isinstance(slopes, torch.Tensor):
+        return slopes
+    if slopes.dim() == 1 and slopes.shape[0] == lead[1] and slopes.is_contiguous():
+        return slopes.detach().unsqueeze(0).expand(lead[0], lead[1])
+    if slopes.dim() == 2 and tuple(slopes.shape) == tuple(lead):
+        return slopes.detach()
+    raise RuntimeError(f"flash_attention_ex: alibi_slopes must be ({lead[1]},) or {tuple(lead)}, got {tuple(slopes.shape)}")
+
+
 def flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, block_size=128, causal=False, dropout_p=0.0,
-                       seed=0, softmax_scale=None, window_size=(-1, -1)):
+                       seed=0, softmax_scale=None, window_size=(-1, -1), softcap=0.0, alibi_slopes=None):
     window = _window_size(window_size)
     if not q.is_cuda:
         raise RuntimeError("Inputs must be CUDA tensors")   # as the reference's wrappers (src/fa2/cuda/impl.py:44)
@@ -117,18 +134,24 @@ def flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, bloc
     br = bc = int(block_size)
     if block_sparse_mask is not None:
         br, bc = min(br, nq), min(bc, nk)         # Br = min(block_size, q_len), Bc = min(block_size, kv_len)  (:100-101)
-    o = _FlashAttnExFn.apply(q3, k3, v3, bool(causal), scale, m, block_sparse_mask, br, bc, float(dropout_p), int(seed), window)
+    slopes = _alibi_units(alibi_slopes, tuple(q.shape[:-2]))
+    if softcap == 0.0 and slopes is None:   # (the call without modifiers, as before they existed)
+        o = _FlashAttnExFn.apply(q3, k3, v3, bool(causal), scale, m, block_sparse_mask, br, bc, float(dropout_p), int(seed), window)
+    else:
+        o = _FlashAttnExFn.apply(q3, k3, v3, bool(causal), scale, m, block_sparse_mask, br, bc, float(dropout_p), int(seed), window,
+                                 softcap, slopes)
     return o.reshape(q.shape) if four_d else o
 
 
 class _FlashAttnVarlenFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, cu_q, cu_k, max_q, max_k, dropout_p, scale, causal, window, seed):
+    def forward(ctx, q, k, v, cu_q, cu_k, max_q, max_k, dropout_p, scale, causal, window, seed, softcap=0.0, alibi_slopes=None):
         import flashattention_lab_cuda as ext
 
-        o, lse = ext.ex_varlen_forward(q, k, v, cu_q, cu_k, max_q, max_k, causal, scale, dropout_p, seed, window=window)
+        o, lse = ext.ex_varlen_forward(q, k, v, cu_q, cu_k, max_q, max_k, causal, scale, dropout_p, seed, window=window, softcap=softcap,
+                                       alibi_slopes=alibi_slopes)
         ctx.save_for_backward(q, k, v, o, lse, cu_q, cu_k)
-        ctx.args = (max_q, max_k, dropout_p, scale, causal, window, seed)
+        ctx.args = (max_q, max_k, dropout_p, scale, causal, window, seed, softcap, alibi_slopes)
         return o
 
     @staticmethod
@@ -136,23 +159,29 @@ class _FlashAttnVarlenFn(torch.autograd.Function):
         import flashattention_lab_cuda as ext
 
         q, k, v, o, lse, cu_q, cu_k = ctx.saved_tensors
-        max_q, max_k, dropout_p, scale, causal, window, seed = ctx.args
+        max_q, max_k, dropout_p, scale, causal, window, seed, softcap, alibi_slopes = ctx.args
         dq, dk, dv = ext.ex_varlen_backward(q, k, v, o, do.contiguous(), lse, cu_q, cu_k, max_q, max_k, causal, scale, dropout_p, seed,
-                                            window=window)
-        return (dq, dk, dv) + (None,) * 9
+                                            window=window, softcap=softcap, alibi_slopes=alibi_slopes)
+        return (dq, dk, dv) + (None,) * 11
 
 
 def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p=0.0, softmax_scale=None,
-                           causal=False, window_size=(-1, -1), seed=0):
+                           causal=False, window_size=(-1, -1), seed=0, softcap=0.0, alibi_slopes=None):
     """FlashAttention-2's flash_attn_varlen_func over packed sequences, differentiable: q (total_q, H_q, d), k and v
     (total_k, H_kv, d) with H_q % H_kv == 0 (GQA), token-strided views (qkv.unbind(1) of a (total, 3, H, d) projection) taken
     without a copy; cu_seqlens_* int32 (batch + 1,) device offsets.  Attention stays inside each sequence; `causal` is
     bottom-right aligned per sequence and `window_size` has flash_attention_ex's meaning in each sequence's coordinates.
     Returns o (total_q, H_q, d); the gradients of k and v come back in their shapes.  The dropout mask is that of the padded
-    (batch * H_q, max_seqlen_q, max_seqlen_k) call (include/fa_mi355x.h), so it depends on the max_seqlen_q passed."""
+    (batch * H_q, max_seqlen_q, max_seqlen_k) call (include/fa_mi355x.h), so it depends on the max_seqlen_q passed.  softcap and
+    alibi_slopes (float32 (H_q,) or (batch, H_q)) as in flash_attention_ex, in each sequence's coordinates."""
     window = _window_size(window_size)
     if not q.is_cuda:
         raise RuntimeError("Inputs must be CUDA tensors")
     scale = (1.0 / math.sqrt(q.shape[-1])) if softmax_scale is None else float(softmax_scale)
-    return _FlashAttnVarlenFn.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), float(dropout_p), scale,
-                                    bool(causal), window, int(seed))
+    args = (q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), float(dropout_p), scale, bool(causal), window,
+            int(seed))
+    if softcap == 0.0 and alibi_slopes is None:
+        return _FlashAttnVarlenFn.apply(*args)
+    if isinstance(alibi_slopes, torch.Tensor):
+        alibi_slopes = alibi_slopes.detach()
+    return _FlashAttnVarlenFn.apply(*args, softcap, alibi_slopes)

@@ -371,13 +371,40 @@ static int window_canon(const char* who, int64_t nq, int64_t nk, int& causal, in
     return FA_OK;
 }
 
+// score modifiers (fa_ex_*_scoremod): softcap and ALiBi slopes; the default is none
+struct ScoreMod {
+    double softcap = 0.0;
+    const float* alibi = nullptr;
+    int64_t heads = 1, bstride = 0;
+};
+static int score_check(const char* who, const ScoreMod& m, int64_t bh) {
+    if (!(m.softcap >= 0.0) || m.softcap > 1.7976931348623157e308)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: softcap must be a finite number >= 0 (got %g)", who, m.softcap);
+    if (m.bstride < 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: alibi_batch_stride must be >= 0 (got %lld)", who, (long long)m.bstride);
+    if (m.alibi && m.heads < 1)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: alibi_heads must be >= 1 (got %lld)", who, (long long)m.heads);
+    if (m.alibi && bh % m.heads != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: alibi_heads=%lld does not divide BH=%lld", who, (long long)m.heads, (long long)bh);
+    if (m.alibi && (m.heads >= ((int64_t)1 << 31) || m.bstride >= ((int64_t)1 << 31) || (bh / m.heads) * m.bstride >= ((int64_t)1 << 31)))
+        return fail(FA_ERR_UNSUPPORTED, "%s: alibi slope indices too large", who);
+    return FA_OK;
+}
+static void score_args(fa::ExArgs& a, const ScoreMod& m) {
+    a.softcap = m.softcap;
+    a.alibi = m.alibi;
+    a.alibi_heads = m.heads;
+    a.alibi_bstride = m.bstride;
+}
+
 static int ex_forward_impl(const char* who, const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t kv_group,
                            int64_t nq, int64_t nk, int64_t d, int dtype, int causal, int64_t wl, int64_t wr, double softmax_scale,
                            const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc,
-                           double dropout_p, uint64_t dropout_seed, void* stream) {
+                           double dropout_p, uint64_t dropout_seed, void* stream, const ScoreMod& sm = ScoreMod()) {
     int rc = ex_check(who, bh, nq, nk, d, dtype, softmax_scale, block_mask, br, bc, dropout_p);
     if (rc != FA_OK) return rc;
     if ((rc = group_check(who, bh, kv_group)) != FA_OK) return rc;
+    if ((rc = score_check(who, sm, bh)) != FA_OK) return rc;
     if ((rc = window_canon(who, nq, nk, causal, wl, wr)) != FA_OK) return rc;
     if (bh == 0 || nq == 0) return FA_OK;
     if (!q || !o || !lse || (nk > 0 && (!k || !v))) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
@@ -393,6 +420,7 @@ static int ex_forward_impl(const char* who, const void* q, const void* k, const 
     a.kv_group = kv_group;
     a.window_left = wl;
     a.window_right = wr;
+    score_args(a, sm);
     hipError_t e = fa::launch_ex(a, false, reinterpret_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
     return FA_OK;
@@ -404,10 +432,11 @@ static int ex_backward_impl(const char* who, const void* q, const void* k, const
                             void* dq, void* dk, void* dv, int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype,
                             int causal, int64_t wl, int64_t wr, double softmax_scale, const uint8_t* mask, int64_t mask_bh_stride,
                             const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* workspace,
-                            size_t workspace_bytes, void* stream) {
+                            size_t workspace_bytes, void* stream, const ScoreMod& sm = ScoreMod()) {
     int rc = ex_check(who, bh, nq, nk, d, dtype, softmax_scale, block_mask, br, bc, dropout_p);
     if (rc != FA_OK) return rc;
     if ((rc = group_check(who, bh, kv_group)) != FA_OK) return rc;
+    if ((rc = score_check(who, sm, bh)) != FA_OK) return rc;
     if ((rc = window_canon(who, nq, nk, causal, wl, wr)) != FA_OK) return rc;
     if (bh == 0 || (nq == 0 && nk == 0)) return FA_OK;
     if (nq == 0 || nk == 0) {   // one side empty: the gradients of the other side are sums over nothing
@@ -434,6 +463,7 @@ static int ex_backward_impl(const char* who, const void* q, const void* k, const
     a.kv_group = kv_group;
     a.window_left = wl;
     a.window_right = wr;
+    score_args(a, sm);
     hipError_t e = fa::launch_ex(a, true, reinterpret_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
     return FA_OK;
@@ -504,6 +534,30 @@ int fa_ex_backward_window(const void* q, const void* k, const void* v, const voi
                             workspace, workspace_bytes, stream);
 }
 
+int fa_ex_forward_scoremod(const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t kv_group, int64_t nq,
+                           int64_t nk, int64_t d, int dtype, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                           double softcap, const float* alibi_slopes, int64_t alibi_heads, int64_t alibi_batch_stride, const uint8_t* mask,
+                           int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p,
+                           uint64_t dropout_seed, void* stream) {
+    ScoreMod sm;
+    sm.softcap = softcap; sm.alibi = alibi_slopes; sm.heads = alibi_heads; sm.bstride = alibi_batch_stride;
+    return ex_forward_impl("fa_ex_forward_scoremod", q, k, v, o, lse, bh, kv_group, nq, nk, d, dtype, causal, window_left, window_right,
+                           softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, stream, sm);
+}
+
+int fa_ex_backward_scoremod(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq,
+                            void* dk, void* dv, int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype, int causal,
+                            int64_t window_left, int64_t window_right, double softmax_scale, double softcap, const float* alibi_slopes,
+                            int64_t alibi_heads, int64_t alibi_batch_stride, const uint8_t* mask, int64_t mask_bh_stride,
+                            const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    ScoreMod sm;
+    sm.softcap = softcap; sm.alibi = alibi_slopes; sm.heads = alibi_heads; sm.bstride = alibi_batch_stride;
+    return ex_backward_impl("fa_ex_backward_scoremod", q, k, v, o, do_, lse, dq, dk, dv, bh, kv_group, nq, nk, d, dtype, causal,
+                            window_left, window_right, softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed,
+                            workspace, workspace_bytes, stream, sm);
+}
+
 // ---- variable-length (packed) sequences: see include/fa_mi355x.h
 // Everything that can be checked without reading cu_seqlens (which would take a synchronise), before any HIP call.
 static int varlen_check(const char* who, const int32_t* cu_q, const int32_t* cu_k, int64_t batch, int64_t hq, int64_t hkv, int64_t total_q,
@@ -556,15 +610,15 @@ static fa::ExArgs varlen_args(const int32_t* cu_q, const int32_t* cu_k, int64_t 
     return a;
 }
 
-int fa_ex_forward_varlen(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
-                         const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k,
-                         int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride,
-                         int64_t v_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale, double dropout_p,
-                         uint64_t dropout_seed, void* stream) {
-    const char* who = "fa_ex_forward_varlen";
+static int varlen_forward_impl(const char* who, const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
+                               const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
+                               int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
+                               int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
+                               double softmax_scale, double dropout_p, uint64_t dropout_seed, void* stream, const ScoreMod& sm) {
     int rc = varlen_check(who, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype,
                           q_stride, k_stride, v_stride, window_left, window_right, softmax_scale, dropout_p);
     if (rc != FA_OK) return rc;
+    if (heads_q >= 1 && (rc = score_check(who, sm, batch * heads_q)) != FA_OK) return rc;
     if ((rc = window_canon(who, max_seqlen_q, max_seqlen_k, causal, window_left, window_right)) != FA_OK) return rc;
     if (total_q == 0 || max_seqlen_q == 0) return FA_OK;   // no query row in any sequence
     if (!q || !o || !lse || (total_k > 0 && (!k || !v))) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
@@ -578,9 +632,33 @@ int fa_ex_forward_varlen(const void* q, const void* k, const void* v, void* o, f
     fa::ExArgs a = varlen_args(cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype,
                                q_stride, k_stride, v_stride, causal, window_left, window_right, softmax_scale, dropout_p, dropout_seed);
     a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse;
+    score_args(a, sm);
     hipError_t e = fa::launch_ex(a, false, st);
     if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
     return FA_OK;
+}
+
+int fa_ex_forward_varlen(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
+                         const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k,
+                         int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride,
+                         int64_t v_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale, double dropout_p,
+                         uint64_t dropout_seed, void* stream) {
+    return varlen_forward_impl("fa_ex_forward_varlen", q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q,
+                               total_k, max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride, causal, window_left,
+                               window_right, softmax_scale, dropout_p, dropout_seed, stream, ScoreMod());
+}
+
+int fa_ex_forward_varlen_scoremod(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
+                                  const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
+                                  int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
+                                  int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
+                                  double softmax_scale, double softcap, const float* alibi_slopes, int64_t alibi_batch_stride,
+                                  double dropout_p, uint64_t dropout_seed, void* stream) {
+    ScoreMod sm;
+    sm.softcap = softcap; sm.alibi = alibi_slopes; sm.heads = heads_q; sm.bstride = alibi_batch_stride;
+    return varlen_forward_impl("fa_ex_forward_varlen_scoremod", q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv,
+                               total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride, causal, window_left,
+                               window_right, softmax_scale, dropout_p, dropout_seed, stream, sm);
 }
 
 size_t fa_ex_backward_workspace_bytes_varlen(int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t d, int dtype) {
@@ -590,16 +668,16 @@ size_t fa_ex_backward_workspace_bytes_varlen(int64_t heads_q, int64_t heads_kv, 
     return need;
 }
 
-int fa_ex_backward_varlen(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
-                          void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q,
-                          int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d,
-                          int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride, int causal, int64_t window_left,
-                          int64_t window_right, double softmax_scale, double dropout_p, uint64_t dropout_seed, void* workspace,
-                          size_t workspace_bytes, void* stream) {
-    const char* who = "fa_ex_backward_varlen";
+static int varlen_backward_impl(const char* who, const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse,
+                                void* dq, void* dk, void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch,
+                                int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q,
+                                int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride, int causal,
+                                int64_t window_left, int64_t window_right, double softmax_scale, double dropout_p, uint64_t dropout_seed,
+                                void* workspace, size_t workspace_bytes, void* stream, const ScoreMod& sm) {
     int rc = varlen_check(who, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype,
                           q_stride, k_stride, v_stride, window_left, window_right, softmax_scale, dropout_p);
     if (rc != FA_OK) return rc;
+    if (heads_q >= 1 && (rc = score_check(who, sm, batch * heads_q)) != FA_OK) return rc;
     if ((rc = window_canon(who, max_seqlen_q, max_seqlen_k, causal, window_left, window_right)) != FA_OK) return rc;
     const bool no_q = total_q == 0 || max_seqlen_q == 0, no_k = total_k == 0 || max_seqlen_k == 0;
     if (no_q && no_k) return FA_OK;
@@ -628,9 +706,37 @@ int fa_ex_backward_varlen(const void* q, const void* k, const void* v, const voi
     a.dq = dq; a.dk = dk; a.dv = dv;
     a.workspace = workspace;
     a.workspace_bytes = workspace_bytes;
+    score_args(a, sm);
     hipError_t e = fa::launch_ex(a, true, reinterpret_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
     return FA_OK;
+}
+
+int fa_ex_backward_varlen(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
+                          void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q,
+                          int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d,
+                          int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride, int causal, int64_t window_left,
+                          int64_t window_right, double softmax_scale, double dropout_p, uint64_t dropout_seed, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    return varlen_backward_impl("fa_ex_backward_varlen", q, k, v, o, do_, lse, dq, dk, dv, cu_seqlens_q, cu_seqlens_k, batch, heads_q,
+                                heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride, causal,
+                                window_left, window_right, softmax_scale, dropout_p, dropout_seed, workspace, workspace_bytes, stream,
+                                ScoreMod());
+}
+
+int fa_ex_backward_varlen_scoremod(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq,
+                                   void* dk, void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch,
+                                   int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q,
+                                   int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                                   int causal, int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
+                                   const float* alibi_slopes, int64_t alibi_batch_stride, double dropout_p, uint64_t dropout_seed,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    ScoreMod sm;
+    sm.softcap = softcap; sm.alibi = alibi_slopes; sm.heads = heads_q; sm.bstride = alibi_batch_stride;
+    return varlen_backward_impl("fa_ex_backward_varlen_scoremod", q, k, v, o, do_, lse, dq, dk, dv, cu_seqlens_q, cu_seqlens_k, batch,
+                                heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride,
+                                causal, window_left, window_right, softmax_scale, dropout_p, dropout_seed, workspace, workspace_bytes,
+                                stream, sm);
 }
 
 size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {

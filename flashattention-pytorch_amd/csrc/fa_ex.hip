@@ -13,6 +13,9 @@
 //     key (query) tile ranges of every kernel are cut to the band at both ends.
 //   * packed (varlen) sequences (FlashAttention-2's flash_attn_varlen_func): each workgroup of the padded call's grid works inside
 //     its own sequence, in entries of their own (ex_*_varlen_kernel) around the bodies the other kernels share.
+//   * score modifiers (FlashAttention-2's softcap and alibi_slopes): x = scale q.k becomes softcap tanh(x / softcap), then
+//     x - slope |i + coff - j|, before the visibility rule; the backward multiplies dS by 1 - tanh^2.  Entries of their own
+//     (ex_*_score_kernel: the bodies with ExParamsS), so the kernels without a modifier keep their code.
 // Exact-f32 math on the f32-input MFMA (any dtype in, head_dim <= 256), the structure of fa_generic.hip: forward by
 // query tile with online softmax over the visible keys; backward = delta pre-pass + dK/dV kernel + dQ kernel, no
 // atomics.  Rows without any visible key get o = 0, lse = -inf (the reference's softmax of an all -inf row is NaN).
@@ -57,6 +60,20 @@ __device__ __forceinline__ void ex_load_tile(float* __restrict__ dst, const T* _
         dst[r * LD + c] = x;
     }
 }
+// score modifiers of one element in the exact kernels' domain (ExScore; x = scale q.k, dist = i + coff - j); dt = 1 - t^2, the
+// softcap's derivative (1 without one).  The forward and both backward bodies evaluate it with these same operations.
+__device__ __forceinline__ float ex_score_mod(const ExScore& sc, float slope, float x, int dist, float& dt) {
+    dt = 1.f;
+    if (sc.softcap > 0.f) {
+        const float t = tanhf(x / sc.softcap);
+        dt = fmaf(-t, t, 1.f);
+        x = sc.softcap * t;
+    }
+    if (sc.alibi) x = fmaf(-slope, fabsf((float)dist), x);
+    return x;
+}
+template <typename P> constexpr bool ex_has_score() { return std::is_same<P, ExParamsS>::value; }
+
 template <typename T> __device__ __forceinline__ bool ex_quad_ok(int d, const void* a, const void* b, const void* c, const void* e) {
     return d % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
                            reinterpret_cast<uintptr_t>(e)) % (4 * sizeof(T))) == 0;
@@ -69,9 +86,11 @@ template <typename T> __device__ __forceinline__ bool ex_quad_ok(int d, const vo
 // VAR: packed sequences (ExParams' varlen fields; the ex_*_varlen_kernel entries): the tile of unit bh = b * hq + h of the padded
 // grid, inside sequence b.  q rows at token stride sq (k, v: sk, sv), o / dq / dk / dv rows at hq * d, lse at (h, token), delta at
 // (token, h).
-template <typename T, int DP, int NW, bool WIN, bool VAR>
+// P: ExParams, or ExParamsS for the score-modifier entries (the same for the backward bodies)
+template <typename T, int DP, int NW, bool WIN, bool VAR, typename P>
 __device__ __forceinline__ void ex_fwd_body(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, T* __restrict__ o,
-                                            float* __restrict__ lse, ExParams& p) {
+                                            float* __restrict__ lse, P& p) {
+    constexpr bool SC = ex_has_score<P>();
     constexpr int LD = DP + 4, BM = 16 * NW, BN = 32, NT = DP / 16, PLD = BN + 4, NTH = NW * 64;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Qs = smem;
@@ -113,6 +132,8 @@ __device__ __forceinline__ void ex_fwd_body(const T* __restrict__ q, const T* __
     const int kend = WIN ? max(0, min(p.nk, q0 + BM + p.coff + p.wr)) : (p.causal ? max(0, min(p.nk, q0 + BM + p.coff)) : p.nk);
     const int kstart = WIN ? (max(0, q0 + p.coff - p.wl) / BN) * BN : 0;   // (wr = 0 under the causal mask)
     float* Pw = Ps + w * 16 * PLD;
+    [[maybe_unused]] float slope = 0.f;
+    if constexpr (SC) slope = ex_slope(p.sc, bh);
 
     for (int k0 = kstart; k0 < kend; k0 += BN) {
         if (!VAR && !ex_tile_live(p, q0, min(q0 + BM, p.nq), k0, min(k0 + BN, p.nk))) continue;   // block-sparse skip (uniform)
@@ -136,8 +157,15 @@ __device__ __forceinline__ void ex_fwd_body(const T* __restrict__ q, const T* __
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int row = q0 + w * 16 + lq * 4 + i;
-            float x0 = ex_visible<WIN, VAR>(p, bh, row, key0) ? s0[i] * p.scale : -INFINITY;
-            float x1 = ex_visible<WIN, VAR>(p, bh, row, key1) ? s1[i] * p.scale : -INFINITY;
+            float x0, x1;
+            if constexpr (SC) {
+                float dt;
+                x0 = ex_visible<WIN, VAR>(p, bh, row, key0) ? ex_score_mod(p.sc, slope, s0[i] * p.scale, row + p.coff - key0, dt) : -INFINITY;
+                x1 = ex_visible<WIN, VAR>(p, bh, row, key1) ? ex_score_mod(p.sc, slope, s1[i] * p.scale, row + p.coff - key1, dt) : -INFINITY;
+            } else {
+                x0 = ex_visible<WIN, VAR>(p, bh, row, key0) ? s0[i] * p.scale : -INFINITY;
+                x1 = ex_visible<WIN, VAR>(p, bh, row, key1) ? s1[i] * p.scale : -INFINITY;
+            }
             float mx = fmaxf(x0, x1);
             mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
             mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
@@ -198,6 +226,18 @@ __global__ __launch_bounds__(NW * 64) void ex_fwd_varlen_kernel(const T* __restr
                                                                 float* __restrict__ lse, ExParams p) {
     ex_fwd_body<T, DP, NW, WIN, true>(q, k, v, o, lse, p);
 }
+template <typename T, int DP, int NW, bool WIN>
+__global__ __launch_bounds__(NW * 64) void ex_fwd_score_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                               const T* __restrict__ v, T* __restrict__ o,
+                                                               float* __restrict__ lse, ExParamsS p) {
+    ex_fwd_body<T, DP, NW, WIN, false>(q, k, v, o, lse, p);
+}
+template <typename T, int DP, int NW, bool WIN>
+__global__ __launch_bounds__(NW * 64) void ex_fwd_varlen_score_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                                      const T* __restrict__ v, T* __restrict__ o,
+                                                                      float* __restrict__ lse, ExParamsS p) {
+    ex_fwd_body<T, DP, NW, WIN, true>(q, k, v, o, lse, p);
+}
 
 template <typename T>
 __global__ __launch_bounds__(256) void ex_delta_kernel(const T* __restrict__ o, const T* __restrict__ dout,
@@ -216,10 +256,11 @@ __global__ __launch_bounds__(256) void ex_delta_kernel(const T* __restrict__ o, 
 
 // ---- backward dK/dV: one workgroup = 16 NW keys resident in LDS; loops over 32-row query tiles
 //      dV = P_drop^T dO,  dP = keep/(1-p) * (dO V^T),  dS = P (dP - delta),  dK = scale dS^T Q
-template <typename T, int DP, int NW, bool WIN, bool VAR>
+template <typename T, int DP, int NW, bool WIN, bool VAR, typename P>
 __device__ __forceinline__ void ex_dkdv_body(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
                                              const T* __restrict__ dout, const float* __restrict__ lse,
-                                             const float* __restrict__ delta, T* __restrict__ dk, T* __restrict__ dv, ExParams& p) {
+                                             const float* __restrict__ delta, T* __restrict__ dk, T* __restrict__ dv, P& p) {
+    constexpr bool SC = ex_has_score<P>();
     constexpr int LD = DP + 4, BK = 16 * NW, BQ = 32, NT = DP / 16, PLD = BQ + 4, NTH = NW * 64;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Ks = smem;
@@ -263,6 +304,8 @@ __device__ __forceinline__ void ex_dkdv_body(const T* __restrict__ q, const T* _
     for (int t = 0; t < NT; ++t) { dka[t] = f32x4{0.f, 0.f, 0.f, 0.f}; dva[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     float* Pw = Pt + w * 16 * PLD;
     float* Sw = St + w * 16 * PLD;
+    [[maybe_unused]] float slope = 0.f;
+    if constexpr (SC) slope = ex_slope(p.sc, bh);
     // rows before the tile's first key's diagonal see none of it: key k0 is visible from row k0 - coff - wr on (wr = 0
     // under the causal mask); with a left bound the tile's last key is visible up to row kl - coff + wl
     const int qstart = WIN ? (max(0, k0 - p.coff - p.wr) / BQ) * BQ : (p.causal ? (max(0, k0 - p.coff) / BQ) * BQ : 0);
@@ -298,10 +341,19 @@ __device__ __forceinline__ void ex_dkdv_body(const T* __restrict__ q, const T* _
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int key = k0 + w * 16 + lq * 4 + i;
-                const float pr = ex_visible<WIN, VAR>(p, bh, row, key) ? expf(st[i] * p.scale - lq_) : 0.f;
-                const float ks_ = (p.p_drop > 0.f) ? (ex_keep(p, bh, row, key) ? p.keep_scale : 0.f) : 1.f;
-                Pw[(lq * 4 + i) * PLD + qb * 16 + lr] = pr * ks_;                       // P_drop^T (feeds dV)
-                Sw[(lq * 4 + i) * PLD + qb * 16 + lr] = pr * (dpt[i] * ks_ - dl_);      // dS^T
+                if constexpr (SC) {   // dS = P (dP - delta) (1 - t^2)
+                    float dt;
+                    const float x = ex_score_mod(p.sc, slope, st[i] * p.scale, row + p.coff - key, dt);
+                    const float pr = ex_visible<WIN, VAR>(p, bh, row, key) ? expf(x - lq_) : 0.f;
+                    const float ks_ = (p.p_drop > 0.f) ? (ex_keep(p, bh, row, key) ? p.keep_scale : 0.f) : 1.f;
+                    Pw[(lq * 4 + i) * PLD + qb * 16 + lr] = pr * ks_;
+                    Sw[(lq * 4 + i) * PLD + qb * 16 + lr] = pr * (dpt[i] * ks_ - dl_) * dt;
+                } else {
+                    const float pr = ex_visible<WIN, VAR>(p, bh, row, key) ? expf(st[i] * p.scale - lq_) : 0.f;
+                    const float ks_ = (p.p_drop > 0.f) ? (ex_keep(p, bh, row, key) ? p.keep_scale : 0.f) : 1.f;
+                    Pw[(lq * 4 + i) * PLD + qb * 16 + lr] = pr * ks_;                       // P_drop^T (feeds dV)
+                    Sw[(lq * 4 + i) * PLD + qb * 16 + lr] = pr * (dpt[i] * ks_ - dl_);      // dS^T
+                }
             }
         }
 #pragma unroll
@@ -346,12 +398,27 @@ __global__ __launch_bounds__(NW * 64) void ex_dkdv_varlen_kernel(const T* __rest
                                                                  T* __restrict__ dk, T* __restrict__ dv, ExParams p) {
     ex_dkdv_body<T, DP, NW, WIN, true>(q, k, v, dout, lse, delta, dk, dv, p);
 }
+template <typename T, int DP, int NW, bool WIN>
+__global__ __launch_bounds__(NW * 64) void ex_dkdv_score_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                                const T* __restrict__ v, const T* __restrict__ dout,
+                                                                const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                T* __restrict__ dk, T* __restrict__ dv, ExParamsS p) {
+    ex_dkdv_body<T, DP, NW, WIN, false>(q, k, v, dout, lse, delta, dk, dv, p);
+}
+template <typename T, int DP, int NW, bool WIN>
+__global__ __launch_bounds__(NW * 64) void ex_dkdv_varlen_score_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                                       const T* __restrict__ v, const T* __restrict__ dout,
+                                                                       const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                       T* __restrict__ dk, T* __restrict__ dv, ExParamsS p) {
+    ex_dkdv_body<T, DP, NW, WIN, true>(q, k, v, dout, lse, delta, dk, dv, p);
+}
 
 // ---- backward dQ: one workgroup = 16 NW query rows; loops over 32-key tiles (S and dP recomputed: deterministic)
-template <typename T, int DP, int NW, bool WIN, bool VAR>
+template <typename T, int DP, int NW, bool WIN, bool VAR, typename P>
 __device__ __forceinline__ void ex_dq_body(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
                                            const T* __restrict__ dout, const float* __restrict__ lse,
-                                           const float* __restrict__ delta, T* __restrict__ dq, ExParams& p) {
+                                           const float* __restrict__ delta, T* __restrict__ dq, P& p) {
+    constexpr bool SC = ex_has_score<P>();
     constexpr int LD = DP + 4, BM = 16 * NW, BN = 32, NT = DP / 16, PLD = BN + 4, NTH = NW * 64;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Qs = smem;
@@ -397,6 +464,8 @@ __device__ __forceinline__ void ex_dq_body(const T* __restrict__ q, const T* __r
 #pragma unroll
     for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     float* Sw = Ss + w * 16 * PLD;
+    [[maybe_unused]] float slope = 0.f;
+    if constexpr (SC) slope = ex_slope(p.sc, bh);
     const int kend = WIN ? max(0, min(p.nk, q0 + BM + p.coff + p.wr)) : (p.causal ? max(0, min(p.nk, q0 + BM + p.coff)) : p.nk);
     const int kstart = WIN ? (max(0, q0 + p.coff - p.wl) / BN) * BN : 0;   // (the forward kernel's tile range)
     for (int k0 = kstart; k0 < kend; k0 += BN) {
@@ -424,9 +493,17 @@ __device__ __forceinline__ void ex_dq_body(const T* __restrict__ q, const T* __r
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int row = q0 + w * 16 + lq * 4 + i;
-                const float pr = ex_visible<WIN, VAR>(p, bh, row, key) ? expf(s[i] * p.scale - lrow[i]) : 0.f;
-                const float ks_ = (p.p_drop > 0.f) ? (ex_keep(p, bh, row, key) ? p.keep_scale : 0.f) : 1.f;
-                Sw[(lq * 4 + i) * PLD + nb * 16 + lr] = pr * (dp[i] * ks_ - drow[i]);
+                if constexpr (SC) {
+                    float dt;
+                    const float x = ex_score_mod(p.sc, slope, s[i] * p.scale, row + p.coff - key, dt);
+                    const float pr = ex_visible<WIN, VAR>(p, bh, row, key) ? expf(x - lrow[i]) : 0.f;
+                    const float ks_ = (p.p_drop > 0.f) ? (ex_keep(p, bh, row, key) ? p.keep_scale : 0.f) : 1.f;
+                    Sw[(lq * 4 + i) * PLD + nb * 16 + lr] = pr * (dp[i] * ks_ - drow[i]) * dt;
+                } else {
+                    const float pr = ex_visible<WIN, VAR>(p, bh, row, key) ? expf(s[i] * p.scale - lrow[i]) : 0.f;
+                    const float ks_ = (p.p_drop > 0.f) ? (ex_keep(p, bh, row, key) ? p.keep_scale : 0.f) : 1.f;
+                    Sw[(lq * 4 + i) * PLD + nb * 16 + lr] = pr * (dp[i] * ks_ - drow[i]);
+                }
             }
         }
 #pragma unroll
@@ -464,28 +541,60 @@ __global__ __launch_bounds__(NW * 64) void ex_dq_varlen_kernel(const T* __restri
                                                                T* __restrict__ dq, ExParams p) {
     ex_dq_body<T, DP, NW, WIN, true>(q, k, v, dout, lse, delta, dq, p);
 }
+template <typename T, int DP, int NW, bool WIN>
+__global__ __launch_bounds__(NW * 64) void ex_dq_score_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                              const T* __restrict__ v, const T* __restrict__ dout,
+                                                              const float* __restrict__ lse, const float* __restrict__ delta,
+                                                              T* __restrict__ dq, ExParamsS p) {
+    ex_dq_body<T, DP, NW, WIN, false>(q, k, v, dout, lse, delta, dq, p);
+}
+template <typename T, int DP, int NW, bool WIN>
+__global__ __launch_bounds__(NW * 64) void ex_dq_varlen_score_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                                     const T* __restrict__ v, const T* __restrict__ dout,
+                                                                     const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                     T* __restrict__ dq, ExParamsS p) {
+    ex_dq_body<T, DP, NW, WIN, true>(q, k, v, dout, lse, delta, dq, p);
+}
 
 // ---- host launchers
-template <typename T, int DP, int NW, bool WIN, bool VAR = false>
+// SC: a call with a score modifier (the *_score_kernel entries, ExParamsS)
+template <typename T, int DP, int NW, bool WIN, bool VAR, bool SC> static auto ex_fwd_entry() {
+    if constexpr (SC) return VAR ? ex_fwd_varlen_score_kernel<T, DP, NW, WIN> : ex_fwd_score_kernel<T, DP, NW, WIN>;
+    else return VAR ? ex_fwd_varlen_kernel<T, DP, NW, WIN> : ex_fwd_kernel<T, DP, NW, WIN>;
+}
+template <typename T, int DP, int NW, bool WIN, bool VAR, bool SC> static auto ex_dkdv_entry() {
+    if constexpr (SC) return VAR ? ex_dkdv_varlen_score_kernel<T, DP, NW, WIN> : ex_dkdv_score_kernel<T, DP, NW, WIN>;
+    else return VAR ? ex_dkdv_varlen_kernel<T, DP, NW, WIN> : ex_dkdv_kernel<T, DP, NW, WIN>;
+}
+template <typename T, int DP, int NW, bool WIN, bool VAR, bool SC> static auto ex_dq_entry() {
+    if constexpr (SC) return VAR ? ex_dq_varlen_score_kernel<T, DP, NW, WIN> : ex_dq_score_kernel<T, DP, NW, WIN>;
+    else return VAR ? ex_dq_varlen_kernel<T, DP, NW, WIN> : ex_dq_kernel<T, DP, NW, WIN>;
+}
+template <bool SC> static auto ex_params(const ExArgs& a) {
+    if constexpr (SC) return make_ex_params_s(a);
+    else return make_ex_params(a);
+}
+
+template <typename T, int DP, int NW, bool WIN, bool VAR = false, bool SC = false>
 static hipError_t ex_fwd_t(const ExArgs& a, hipStream_t st) {
     constexpr int LD = DP + 4;
     const size_t smem = sizeof(float) * ((16 * NW + 64) * LD + NW * 16 * 36);
-    auto kern = VAR ? ex_fwd_varlen_kernel<T, DP, NW, WIN> : ex_fwd_kernel<T, DP, NW, WIN>;
+    auto kern = ex_fwd_entry<T, DP, NW, WIN, VAR, SC>();
     hipError_t e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
     if (e != hipSuccess) return e;
     dim3 grid((unsigned)(((a.nq + 16 * NW - 1) / (16 * NW)) * a.bh));
     ProfScope ps(K_EX_FWD, st);
     hipLaunchKernelGGL(kern, grid, dim3(NW * 64), smem, st, (const T*)a.q, (const T*)a.k, (const T*)a.v, (T*)a.o, a.lse,
-                       make_ex_params(a));
+                       ex_params<SC>(a));
     return hipGetLastError();
 }
 
-template <typename T, int DP, int NW, bool WIN, bool VAR = false>
+template <typename T, int DP, int NW, bool WIN, bool VAR = false, bool SC = false>
 static hipError_t ex_bwd_t(const ExArgs& a, hipStream_t st) {
     constexpr int LD = DP + 4;
     float* delta = reinterpret_cast<float*>(a.workspace);
     const long long rows = VAR ? (long long)a.total_q * a.heads_q : (long long)a.bh * a.nq;   // (varlen: (token, head) order)
-    const ExParams p = make_ex_params(a);
+    const auto p = ex_params<SC>(a);
     ProfScope ps(K_EX_BWD, st);
     hipLaunchKernelGGL(ex_delta_kernel<T>, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, (const T*)a.o,
                        (const T*)a.dout, delta, rows, (int)a.d);
@@ -493,7 +602,7 @@ static hipError_t ex_bwd_t(const ExArgs& a, hipStream_t st) {
     if (e != hipSuccess) return e;
     {
         const size_t smem = sizeof(float) * ((2 * 16 * NW + 64) * LD + 2 * NW * 16 * 36 + 64);
-        auto kern = VAR ? ex_dkdv_varlen_kernel<T, DP, NW, WIN> : ex_dkdv_kernel<T, DP, NW, WIN>;
+        auto kern = ex_dkdv_entry<T, DP, NW, WIN, VAR, SC>();
         e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
         if (e != hipSuccess) return e;
         dim3 grid((unsigned)(((a.nk + 16 * NW - 1) / (16 * NW)) * a.bh));
@@ -504,7 +613,7 @@ static hipError_t ex_bwd_t(const ExArgs& a, hipStream_t st) {
     }
     {
         const size_t smem = sizeof(float) * ((2 * 16 * NW + 64) * LD + NW * 16 * 36);
-        auto kern = VAR ? ex_dq_varlen_kernel<T, DP, NW, WIN> : ex_dq_kernel<T, DP, NW, WIN>;
+        auto kern = ex_dq_entry<T, DP, NW, WIN, VAR, SC>();
         e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
         if (e != hipSuccess) return e;
         dim3 grid((unsigned)(((a.nq + 16 * NW - 1) / (16 * NW)) * a.bh));
@@ -515,16 +624,20 @@ static hipError_t ex_bwd_t(const ExArgs& a, hipStream_t st) {
     return e;
 }
 
-template <typename T, bool WIN, bool VAR = false>
+template <typename T, bool WIN, bool VAR = false, bool SC = false>
 static hipError_t ex_by_d(const ExArgs& a, bool backward, hipStream_t st) {
-    if (a.d <= 64) return backward ? ex_bwd_t<T, 64, 4, WIN, VAR>(a, st) : ex_fwd_t<T, 64, 4, WIN, VAR>(a, st);
-    if (a.d <= 128) return backward ? ex_bwd_t<T, 128, 4, WIN, VAR>(a, st) : ex_fwd_t<T, 128, 4, WIN, VAR>(a, st);
-    return backward ? ex_bwd_t<T, 256, 2, WIN, VAR>(a, st) : ex_fwd_t<T, 256, 4, WIN, VAR>(a, st);
+    if (a.d <= 64) return backward ? ex_bwd_t<T, 64, 4, WIN, VAR, SC>(a, st) : ex_fwd_t<T, 64, 4, WIN, VAR, SC>(a, st);
+    if (a.d <= 128) return backward ? ex_bwd_t<T, 128, 4, WIN, VAR, SC>(a, st) : ex_fwd_t<T, 128, 4, WIN, VAR, SC>(a, st);
+    return backward ? ex_bwd_t<T, 256, 2, WIN, VAR, SC>(a, st) : ex_fwd_t<T, 256, 4, WIN, VAR, SC>(a, st);
+}
+template <typename T, bool SC>
+static hipError_t ex_by_d_s(const ExArgs& a, bool backward, hipStream_t st) {
+    if (a.cu_q) return ex_windowed(a) ? ex_by_d<T, true, true, SC>(a, backward, st) : ex_by_d<T, false, true, SC>(a, backward, st);
+    return ex_windowed(a) ? ex_by_d<T, true, false, SC>(a, backward, st) : ex_by_d<T, false, false, SC>(a, backward, st);
 }
 template <typename T>
 static hipError_t ex_by_d(const ExArgs& a, bool backward, hipStream_t st) {
-    if (a.cu_q) return ex_windowed(a) ? ex_by_d<T, true, true>(a, backward, st) : ex_by_d<T, false, true>(a, backward, st);
-    return ex_windowed(a) ? ex_by_d<T, true>(a, backward, st) : ex_by_d<T, false>(a, backward, st);
+    return ex_scoremod(a) ? ex_by_d_s<T, true>(a, backward, st) : ex_by_d_s<T, false>(a, backward, st);
 }
 
 // Grouped-query attention (a.kv_group > 1) reaches every family below except the plain path's exact-f32 kernels (fa_generic.hip):
@@ -535,8 +648,9 @@ static hipError_t launch_ex_one(const ExArgs& a, bool backward, hipStream_t st) 
     // no extras at all on a square problem: this IS the plain path — hand it to the tuned kernels (same results contract;
     // the workspace of fa_ex_backward_workspace_bytes covers their row constants)
     // (a window that bounds something never leaves this file's families: the plain, nq != nk and fa_generic kernels know no band)
-    const bool win = ex_windowed(a);
-    const bool plain = (path == 0 || path == 2) && !win && !a.mask && !a.block_mask && a.dropout_p <= 0.0 && a.scale > 0.f;
+    // (nor does a score modifier: the plain, Nq != Nk and fa_generic kernels and the dS hand-over know none)
+    const bool win = ex_windowed(a), mod = ex_scoremod(a);
+    const bool plain = (path == 0 || path == 2) && !win && !mod && !a.mask && !a.block_mask && a.dropout_p <= 0.0 && a.scale > 0.f;
     if (plain && a.nq == a.nk && (backward ? bwd_mfma_supported(a.dtype, a.d) : fwd_mfma_supported(a.dtype, a.d))) {
         if (!backward) {
             FwdArgs f{a.q, a.k, a.v, a.o, a.lse, a.bh, a.nq, a.d, a.dtype, a.causal, a.scale};
@@ -551,7 +665,7 @@ static hipError_t launch_ex_one(const ExArgs& a, bool backward, hipStream_t st) 
     }
     // the same for what the 16-bit kernels do not take (fp32 tensors, head dims that are not a multiple of 8): the plain path's
     // exact-f32 kernels (fa_generic.hip: register fragments, 16-byte operand reads — 2.5 x the rate of the kernels below)
-    if ((path == 0) && a.kv_group == 1 && !win && !a.mask && !a.block_mask && a.dropout_p <= 0.0 && a.nq == a.nk && a.d <= 256 &&
+    if ((path == 0) && a.kv_group == 1 && !win && !mod && !a.mask && !a.block_mask && a.dropout_p <= 0.0 && a.nq == a.nk && a.d <= 256 &&
         !(backward ? bwd_mfma_supported(a.dtype, a.d) : fwd_mfma_supported(a.dtype, a.d))) {
         if (!backward) return launch_fwd_generic(FwdArgs{a.q, a.k, a.v, a.o, a.lse, a.bh, a.nq, a.d, a.dtype, a.causal, a.scale}, st);
         return launch_bwd_generic(BwdArgs{a.q, a.k, a.v, a.o, a.dout, a.lse, a.dq, a.dk, a.dv, a.bh, a.nq, a.d, a.dtype, a.causal, a.scale,

@@ -37,6 +37,29 @@ static_assert(offsetof(ExParams, mask) == 32 && offsetof(ExParams, mask_bh) == 4
               offsetof(ExParams, br) == 56 && offsetof(ExParams, p_drop) == 68 && sizeof(ExParams) == 104, "ExParams layout");
 constexpr int kWinNone = 1 << 30;
 
+// Score modifiers (softcap, ALiBi: ExArgs; the kFeatScore instantiations of fa_ex_mfma.hip and the *_score_kernel entries of
+// fa_ex.hip).  A kernel parameter block of their own, ExParamsS = ExParams + ExScore: the kernels without a modifier keep
+// ExParams, and with it their kernel-argument layout and their code.
+struct ExScore {
+    const float* alibi;    // null: no ALiBi; unit u: alibi[(u / al_heads) * al_bstride + u % al_heads]
+    int al_heads, al_bstride;
+    float softcap;         // > 0: on (the exact-f32 kernels: softcap tanh(x / softcap) of x = scale q.k)
+    // the 16-bit kernels work on raw scores S = q.k with scale log2(e) folded into exp2, so the modifier is applied in that
+    // domain: S~ = cap_a tanh(S / (scale softcap)) ... = cap_a (1 - 2 / (2^(cap_k S) + 1)) - al_k slope |i + coff - j|
+    float cap_k;           // 2 log2(e) scale / softcap
+    float cap_a;           // softcap / scale
+    float al_k;            // 1 / scale
+};
+struct ExParamsS : ExParams {
+    ExScore sc;
+};
+static_assert(sizeof(ExScore) == 32 && sizeof(ExParamsS) == sizeof(ExParams) + sizeof(ExScore), "ExParamsS layout: ExScore after every ExParams field");
+
+// this unit's slope (0 without ALiBi): uniform over the workgroup
+__device__ __forceinline__ float ex_slope(const ExScore& sc, int bh) {
+    return sc.alibi ? sc.alibi[(bh / sc.al_heads) * sc.al_bstride + bh % sc.al_heads] : 0.f;
+}
+
 // first token and length of sequence b: start = clamp(cu[b], 0, total), end = clamp(cu[b + 1], start, total),
 // len = min(end - start, max_len).  b is uniform over the workgroup: scalar loads.
 __device__ __forceinline__ void seq_span(const int* cu, int b, int total, int max_len, int& start, int& len) {
@@ -111,6 +134,19 @@ inline ExParams make_ex_params(const ExArgs& a) {
         p.total_q = (int)a.total_q; p.total_k = (int)a.total_k;
         p.sq = (int)a.stride_q; p.sk = (int)a.stride_k; p.sv = (int)a.stride_v;
     }
+    return p;
+}
+inline ExParamsS make_ex_params_s(const ExArgs& a) {
+    ExParamsS p;
+    static_cast<ExParams&>(p) = make_ex_params(a);
+    p.sc.alibi = a.alibi;
+    p.sc.al_heads = (int)(a.alibi_heads > 0 ? a.alibi_heads : 1);
+    p.sc.al_bstride = (int)a.alibi_bstride;
+    const double cap = a.softcap > 0.0 ? a.softcap : 0.0, sc = a.scale;
+    p.sc.softcap = (float)cap;
+    p.sc.cap_k = cap > 0.0 ? (float)(2.0 * 1.4426950408889634 * sc / cap) : 0.f;
+    p.sc.cap_a = cap > 0.0 ? (float)(cap / sc) : 0.f;
+    p.sc.al_k = (float)(1.0 / sc);
     return p;
 }
 

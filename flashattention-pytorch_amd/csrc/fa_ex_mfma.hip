@@ -13,6 +13,10 @@
 //               Without the bit the instantiations are the ones of the causal / unmasked kernels, unchanged.
 //   FEAT bit 3  packed (varlen) sequences: the padded call's grid, each workgroup narrowed to its sequence (EXM_VARLEN_UNIT; the
 //               fields in ExParams, fa_ex_common.h), token strides for q, k, v; combinable with bits 1 and 2, never with bit 0.
+//   FEAT bit 4  score modifiers (softcap, ALiBi slopes): the parameter block grows by ExScore (ExParamsS), and the raw scores are
+//               modified right after the S MFMAs, before any mask (mod_softcap / mod_alibi; on / off are wave-uniform run-time
+//               switches).  The backward kernels then start S at 0 and add -lse / scale after the modifier, and dS takes the
+//               softcap's 1 - t^2 in fp32 before its 16-bit pack.  Combinable with every other bit.
 // Dense mask bytes are fetched with range-checked buffer loads (rows / bytes past the mask read as 0 = masked); when Nk, the
 // mask pointer and the (b,h) stride are multiples of 4 a lane of the query-on-the-lane kernels takes the 4 keys of a
 // register group with one dword load.  The block-sparse mask needs br, bc multiples of 32 here (a wave's 32 x 32 block
@@ -26,7 +30,13 @@ namespace fa {
 
 namespace {
 
-constexpr int kFeatMask = 1, kFeatDrop = 2, kFeatWindow = 4, kFeatVarlen = 8;
+constexpr int kFeatMask = 1, kFeatDrop = 2, kFeatWindow = 4, kFeatVarlen = 8, kFeatScore = 16;
+// the parameter block of an instantiation: ExParamsS (+ the score modifiers) with kFeatScore, else ExParams as before
+template <int FEAT> using ExP = typename std::conditional<(FEAT & kFeatScore) != 0, ExParamsS, ExParams>::type;
+template <int FEAT> inline ExP<FEAT> make_exm_params(const ExArgs& a) {
+    if constexpr ((FEAT & kFeatScore) != 0) return make_ex_params_s(a);
+    else return make_ex_params(a);
+}
 
 // rc(i): row (or key) offset inside a 32-wide block of accumulator register i, before the 4 * (lane >> 5) term
 __device__ __forceinline__ constexpr int rc_of(int i) { return (i & 3) + 8 * (i >> 2); }
@@ -208,6 +218,24 @@ __device__ __forceinline__ unsigned keep_bits_q(const ExParams& p, unsigned hi, 
     return bits;
 }
 // Key on the lane: key fixed, rows rrow + rc(i) — registers 4g+0, 4g+1 are one row pair
+// Score modifiers (FEAT bit 4) on a raw score S of the 16-bit kernels (ExScore): the softcap as
+//   S~ = cap_a t,  t = tanh(S / (scale softcap)) = 1 - 2 r,  r = 1 / (2^(cap_k S) + 1)
+// (two transcendentals; safe at both ends: 2^x = inf gives r = 0, t = 1; 2^x = 0 gives r = 1, t = -1), and its derivative
+// dt = 1 - t^2 = 4 r (1 - r) for the backward.  The forward and both backward kernels evaluate S~ with these same fp32 operations,
+// so P in the backward is the P of the forward's lse.
+__device__ __forceinline__ float mod_softcap(float s, const ExScore& sc, float& dt) {
+    const float r = __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(s * sc.cap_k) + 1.f);
+    dt = r * fmaf(r, -4.f, 4.f);
+    return fmaf(r, -2.f * sc.cap_a, sc.cap_a);
+}
+// ALiBi: S~ - al |dist|, al = slope / scale, dist = i + coff - j an exact small integer held as a float
+__device__ __forceinline__ float mod_alibi(float s, float al, float dist) { return fmaf(-al, fabsf(dist), s); }
+// the modifiers of a kFeatScore instantiation's ExParamsS (a call dependent on FEAT: the bodies the plain entries include name it
+// only in discarded `if constexpr (SC)` branches)
+template <int FEAT, typename P> __device__ __forceinline__ const ExScore& sc_of(const P& p) { return p.sc; }
+// this unit's al (0 without ALiBi), the same product in every kernel
+__device__ __forceinline__ float alibi_k(const ExScore& sc, int bh) { return ex_slope(sc, bh) * sc.al_k; }
+
 __device__ __forceinline__ unsigned keep_bits_k(const ExParams& p, unsigned hi_bh, int rrow, int key) {
     unsigned bits = 0;
     const int sh = 16 * (key & 1);
@@ -245,245 +273,14 @@ template <typename Tag, int D, int FEAT>
 __global__ __launch_bounds__(512, 2) void exm_fwd_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                          const uint16_t* __restrict__ v, uint16_t* __restrict__ o,
                                                          float* __restrict__ lse, ExParams p, float c_log2) {
-    constexpr int NW = 8, BM = 32 * NW, KB = 4, BN = 32 * KB, NKS = D / 16, NDV = D / 32, TILE_BYTES = BN * D * 2;
-    constexpr bool VAR = (FEAT & kFeatVarlen) != 0;
-    extern __shared__ __attribute__((aligned(16))) char smem[];   // [2 buffers][K tile | V tile]
-    const int DR = p.d;
-    int nq = p.nq, nk = p.nk;
-    const int nqt = (nq + BM - 1) / BM;
-    const int L = xcd_remap(blockIdx.x, gridDim.x);
-    const int bh = L / nqt;
-    const int q0 = (L - bh * nqt) * BM;
-    EXM_VARLEN_UNIT(q0, nq)
-    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, h = lane >> 5;
-    const size_t qbase = VAR ? (size_t)sq0 * p.sq + hh * DR : (size_t)bh * nq * DR;
-    const size_t kbase = VAR ? (size_t)sk0 * p.sk + hk * DR : (size_t)kv_unit(bh, p.kvg) * nk * DR;
-    const size_t vbase = VAR ? (size_t)sk0 * p.sv + hk * DR : kbase;
-    const size_t obase = VAR ? ((size_t)sq0 * p.hq + hh) * DR : qbase;
-    const size_t lbase = VAR ? (size_t)hh * p.total_q + sq0 : (size_t)bh * nq;
-    const int qrow = q0 + 32 * w + r;
-
-    const buf_rsrc_t q_rs = make_rsrc(q + qbase, VAR ? span_bytes(nq, DR, p.sq) : (unsigned)nq * DR * 2);
-    s16x8 qf[NKS];
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) qf[ks] = buf_load_frag(q_rs, frag_off<VAR>(qrow, 16 * ks + 8 * h, DR, true, VAR ? p.sq : DR));
-
-    const rsrc_s_t k_rs = make_rsrc_s(k + kbase, VAR ? span_bytes(nk, DR, p.sk) : (unsigned)nk * DR * 2);
-    const rsrc_s_t v_rs = make_rsrc_s(v + vbase, VAR ? span_bytes(nk, DR, p.sv) : (unsigned)nk * DR * 2);
-    const int dma_voff = dma_lane_voff<D, VAR>(lane, w, DR, VAR ? p.sk : DR);
-    const int dma_voff_v = VAR ? dma_lane_voff<D, VAR>(lane, w, DR, p.sv) : dma_voff;
-    auto stage = [&](int buf, int k0) {
-        char* kb_ = smem + buf * 2 * TILE_BYTES;
-        dma_stage_tile<D, BN, NW, VAR>(k_rs, kb_, k0, dma_voff, w, DR, 0, VAR ? p.sk : DR);
-        dma_stage_tile<D, BN, NW, VAR>(v_rs, kb_ + TILE_BYTES, k0, dma_voff_v, w, DR, 0, VAR ? p.sv : DR);
-    };
-    const MaskSrc msk = make_mask_src(p, bh);
-    const bool use_bm = (FEAT & kFeatMask) && p.bmask != nullptr;
-    const bool drop = (FEAT & kFeatDrop) && p.p_drop > 0.f;
-    const unsigned hi = (unsigned)bh * p.nqh + ((unsigned)qrow >> 1);
-    const int rbw = min(q0 + 32 * w, nq - 1) / p.br;   // block row of this wave's 32 rows (br is a multiple of 32)
-
-    f32x16 oacc[NDV];
-#pragma unroll
-    for (int t = 0; t < NDV; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) oacc[t][i] = 0.f;
-    float m_run = -INFINITY, l_run = 0.f;
-
-    // keys past the last row's diagonal are masked for every row of the tile (of the wave)
-    constexpr bool WIN = (FEAT & kFeatWindow) != 0;
-    // window: the band's right edge takes the diagonal's place (wr = 0 under the causal mask), and keys left of the first
-    // row's left edge are masked for every row as well: tiles [t_lo, ntiles) for the workgroup, [t_lo_w, ntiles_w) per wave,
-    // both bounded by the last row < nq (a wave without one computes nothing)
-    const int kend = WIN ? max(0, min(nk, min(q0 + BM, nq) + p.coff + p.wr)) : (p.causal ? max(0, min(nk, q0 + BM + p.coff)) : nk);
-    const int kend_w = WIN ? (q0 + 32 * w < nq ? max(0, min(nk, min(q0 + 32 * w + 32, nq) + p.coff + p.wr)) : 0)
-                           : (p.causal ? max(0, min(nk, q0 + 32 * w + 32 + p.coff)) : nk);
-    const int ntiles = (kend + BN - 1) / BN, ntiles_w = (kend_w + BN - 1) / BN;
-    const int t_lo = WIN ? max(0, q0 + p.coff - p.wl) / BN : 0;
-    const int t_lo_w = WIN ? max(0, q0 + 32 * w + p.coff - p.wl) / BN : 0;
-    LiveScan<true, BN> scan;   // (tiles keep their absolute index: the scan's first probe is at t_lo)
-    if (use_bm) scan.init(p, q0, min(q0 + BM, nq), 0, nk, ntiles, lane);
-    auto next_live = [&](int t) { return use_bm ? scan.next(t) : t; };
-    const int li = lane & 15, g16 = (lane >> 4) & 1, tq = li >> 2, tp = li & 3;
-
-    int t = next_live(t_lo), cur = 0;
-    if (t < ntiles) stage(0, t * BN);
-    dma_wait_all();
-    __syncthreads();
-    if constexpr (WIN) {
-        // leading feed-only tiles: left of this wave's band, inside the workgroup's
-        while (t < min(t_lo_w, ntiles)) {
-            const int tn = next_live(t + 1);
-            if (tn < ntiles) stage(cur ^ 1, tn * BN);
-            dma_wait_all();
-            __syncthreads();
-            cur ^= 1;
-            t = tn;
-        }
-    }
-    // two loops instead of an `if` inside one (a conditional accumulate makes hipcc carry the accumulators through
-    // copies): tiles this wave computes, then the ones it only helps to load
-    // Dense mask: its loads are ordinary VMEM loads, and VMEM returns in order — were the next tile's LDS-DMA issued
-    // first, the wait for the mask words would also be a wait for that whole tile.  So the DMA goes out when the mask has
-    // been read (it still has the tile's products to land).  Fetching the words a tile ahead instead (16 more live
-    // registers) was measured slower: 1.15 vs 1.08 ms forward at BH 64, N 4096, half the pairs masked.
-    const bool late_stage = (FEAT & kFeatMask) && msk.on;
-    while (t < ntiles_w) {
-        const int tn = next_live(t + 1);
-        if (!late_stage && tn < ntiles) stage(cur ^ 1, tn * BN);
-        const int k0 = t * BN;
-        const char* Kt = smem + cur * 2 * TILE_BYTES;
-        const char* Vt = Kt + TILE_BYTES;
-        {
-            // visibility / keep bits of this lane's 4 x 16 elements, requested ahead of the S MFMAs
-            unsigned vis[KB], kp[KB];
-#pragma unroll
-            for (int kb = 0; kb < KB; ++kb) {
-                vis[kb] = 0xffffu;
-                kp[kb] = 0xffffu;
-                if constexpr (FEAT & kFeatMask) {
-                    if (msk.on) vis[kb] = dense_bits_q(msk, qrow, nk, k0 + 32 * kb + 4 * h, h);
-                    if (use_bm && p.bmask[rbw * p.nbc + min(k0 + 32 * kb, nk - 1) / p.bc] == 0) vis[kb] = 0;
-                }
-                if constexpr (FEAT & kFeatDrop) {
-                    if (drop) kp[kb] = keep_bits_q(p, hi, qrow, k0 + 32 * kb + 4 * h);
-                }
-            }
-            // a tile of which this wave sees nothing (the upper triangle of a causal mask handed over as a dense one, the
-            // dead blocks of a block-sparse tile) is not computed: wave-uniform
-            bool any_vis = true;
-            if constexpr (FEAT & kFeatMask) {
-                unsigned all = 0;
-#pragma unroll
-                for (int kb = 0; kb < KB; ++kb) all |= vis[kb];
-                any_vis = __any(all != 0) != 0;
-                if (late_stage && tn < ntiles) stage(cur ^ 1, tn * BN);   // the mask words have arrived
-            }
-            if (any_vis) {
-            f32x16 sacc[KB];
-#pragma unroll
-            for (int kb = 0; kb < KB; ++kb) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) sacc[kb][i] = 0.f;
-#pragma unroll
-                for (int ks = 0; ks < NKS; ++ks) {
-                    const s16x8 a = *reinterpret_cast<const s16x8*>(Kt + TileSwz<D>::off(32 * kb + r, 2 * ks + h));
-                    sacc[kb] = mfma32<Tag>(a, qf[ks], sacc[kb]);
-                }
-            }
-            // ---- causal diagonal / ragged last tile: key index of register i is k0 + 32 kb + 4 h + rc(i)
-            const bool need_mask = WIN ? ((k0 + BN - 1 > q0 + 32 * w + p.coff + p.wr) || (k0 + BN > nk) ||
-                                          (k0 < q0 + 32 * w + 31 + p.coff - p.wl))   // + the band's left edge
-                                       : ((p.causal && (k0 + BN - 1 > q0 + 32 * w + p.coff)) || (k0 + BN > nk));
-            if (need_mask) {
-                // last visible key of this lane's row
-                const int lim = WIN ? min(qrow + p.coff + p.wr, nk - 1) : (p.causal ? min(qrow + p.coff, nk - 1) : nk - 1);
-#pragma unroll
-                for (int kb = 0; kb < KB; ++kb) {
-                    const int thr = lim - (k0 + 32 * kb + 4 * h);
-                    if constexpr (WIN) {
-                        const int thl = qrow + p.coff - p.wl - (k0 + 32 * kb + 4 * h);   // the row's first visible key
-#pragma unroll
-                        for (int i = 0; i < 16; ++i)
-                            if (rc_of(i) > thr || rc_of(i) < thl) sacc[kb][i] = -INFINITY;
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < 16; ++i)
-                            if (rc_of(i) > thr) sacc[kb][i] = -INFINITY;
-                    }
-                }
-            }
-            if constexpr (FEAT & kFeatMask) {
-#pragma unroll
-                for (int kb = 0; kb < KB; ++kb)
-                    if (__any(vis[kb] != 0xffffu)) {   // wave-uniform
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) sacc[kb][i] = keep_or_minus_inf(sacc[kb][i], vis[kb], i);
-                    }
-            }
-            // ---- online softmax (fa_fwd_mfma.hip), with rows that have not met a visible key yet (m = -inf)
-            float mx = sacc[0][0];
-#pragma unroll
-            for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) mx = fmaxf(mx, sacc[kb][i]);
-            mx = fmaxf(mx, wave_half_swap(mx));
-            const float m_new = fmaxf(m_run, mx);
-            float mc;
-            // lazy rescale: keep the stale max while no row has grown past it by more than 2^8; -inf - -inf = NaN counts
-            // as "rescale", so a wave with a dead row takes the exact path
-            const bool rescale = __any(!((m_new - m_run) * c_log2 <= 8.0f)) != 0;
-            if (rescale) {
-                const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-                const float alpha = __builtin_amdgcn_exp2f((m_run - m_use) * c_log2);
-                mc = m_use * c_log2;
-                m_run = m_new;
-#pragma unroll
-                for (int t2 = 0; t2 < NDV; ++t2)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) oacc[t2][i] *= alpha;
-                l_run *= alpha;
-            } else {
-                mc = m_run * c_log2;
-            }
-            float rs = 0.f;
-#pragma unroll
-            for (int kb = 0; kb < KB; ++kb) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    float pe = __builtin_amdgcn_exp2f(fmaf(sacc[kb][i], c_log2, -mc));
-                    rs += pe;   // the denominator counts every visible key, dropped or not
-                    if constexpr (FEAT & kFeatDrop) pe = ((kp[kb] >> i) & 1u) ? pe * p.keep_scale : 0.f;
-                    sacc[kb][i] = pe;
-                }
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    u32x4 pk;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) pk[j] = pack2<Tag>(sacc[kb][8 * s + 2 * j], sacc[kb][8 * s + 2 * j + 1]);
-                    const s16x8 pb = *reinterpret_cast<s16x8*>(&pk);
-                    const int key_a = 32 * kb + 16 * s + 4 * h + tq;
-#pragma unroll
-                    for (int dvb = 0; dvb < NDV; ++dvb) {
-                        const int ch = 4 * dvb + 2 * g16 + (tp >> 1);
-                        const s16x4 lo = lds_tr16(Vt + TileSwz<D>::off(key_a, ch) + 8 * (tp & 1));
-                        const s16x4 hi4 = lds_tr16(Vt + TileSwz<D>::off(key_a + 8, ch) + 8 * (tp & 1));
-                        oacc[dvb] = mfma32<Tag>(cat8(lo, hi4), pb, oacc[dvb]);
-                    }
-                }
-            }
-            l_run += rs;
-            }   // any_vis
-        }
-        dma_wait_all();
-        __syncthreads();
-        cur ^= 1;
-        t = tn;
-    }
-    while (t < ntiles) {
-        const int tn = next_live(t + 1);
-        if (tn < ntiles) stage(cur ^ 1, tn * BN);
-        dma_wait_all();
-        __syncthreads();
-        cur ^= 1;
-        t = tn;
-    }
-
-    // ---- epilogue: normalise, store O and lse.  Every wave is past the last barrier and nothing is in flight: each wave
-    // stages its rows in 32 x D x 2 bytes of buffer 0
-    const float l_tot = l_run + wave_half_swap(l_run);
-    const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
-    u32x2 vals[NDV * 4];
-#pragma unroll
-    for (int dvb = 0; dvb < NDV; ++dvb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            vals[4 * dvb + g][0] = pack2_rn<Tag>(oacc[dvb][4 * g + 0] * inv, oacc[dvb][4 * g + 1] * inv);
-            vals[4 * dvb + g][1] = pack2_rn<Tag>(oacc[dvb][4 * g + 2] * inv, oacc[dvb][4 * g + 3] * inv);
-        }
-    store_rows_via_lds<D, VAR>(smem + w * 32 * D * 2, vals, o + obase, q0 + 32 * w, nq, lane, DR, -1, p.hq * DR);
-    if (qrow < nq && h == 0) lse[lbase + qrow] = l_tot > 0.f ? m_run * p.scale + logf(l_tot) : -INFINITY;
+#include "fa_ex_mfma_fwd.inc"
+}
+// FEAT with kFeatScore: the parameter block grows by the modifiers (ExParamsS)
+template <typename Tag, int D, int FEAT>
+__global__ __launch_bounds__(512, 2) void exm_fwd_score_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
+                                                               const uint16_t* __restrict__ v, uint16_t* __restrict__ o,
+                                                               float* __restrict__ lse, ExParamsS p, float c_log2) {
+#include "fa_ex_mfma_fwd.inc"
 }
 
 // ------------------------------------------------------------------------------------------------ row constants
@@ -552,247 +349,15 @@ __global__ __launch_bounds__(512, 2) void exm_dkdv_kernel(const uint16_t* __rest
                                                           const float* __restrict__ nlse, const float* __restrict__ ndelta,
                                                           uint16_t* __restrict__ dk, uint16_t* __restrict__ dv, ExParams p,
                                                           float c_log2) {
-    constexpr int NW = 8, BK = 32 * NW, BQ = 64, NKS = D / 16, NDB = D / 32;
-    constexpr bool VAR = (FEAT & kFeatVarlen) != 0;
-    constexpr int K_BYTES = BK * D * 2, Q_BYTES = BQ * D * 2;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* Ks = smem;                      // [256][D]
-    char* Qs = Ks + K_BYTES;              // [2][64][D]
-    char* Os = Qs + 2 * Q_BYTES;          // [2][64][D]   (dO)
-    float* Ls = reinterpret_cast<float*>(Os + 2 * Q_BYTES);  // [2][ 64 x -lse/scale | 64 x -delta ]
-    const int DR = p.d;
-    int nq = p.nq, nk = p.nk;
-    const int nkt = (nk + BK - 1) / BK;
-    const int L = xcd_remap(blockIdx.x, gridDim.x);
-    const int bh = L / nkt;
-    const int key0 = (L - bh * nkt) * BK;
-    EXM_VARLEN_UNIT(key0, nk)
-    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, h = lane >> 5;
-    const size_t qbase = VAR ? (size_t)sq0 * p.sq + hh * DR : (size_t)bh * nq * DR;
-    const size_t kbase = VAR ? (size_t)sk0 * p.sk + hk * DR : (size_t)kv_unit(bh, p.kvg) * nk * DR;
-    const size_t vbase = VAR ? (size_t)sk0 * p.sv + hk * DR : kbase;
-    const size_t obase = VAR ? ((size_t)sq0 * p.hq + hh) * DR : qbase;
-    const size_t rbase = VAR ? (size_t)hh * p.total_q + sq0 : (size_t)bh * nq;
-    const int kw0 = key0 + 32 * w, key = kw0 + r;
-
-    const rsrc_s_t k_rs = make_rsrc_s(k + kbase, VAR ? span_bytes(nk, DR, p.sk) : (unsigned)nk * DR * 2);
-    const rsrc_s_t q_rs = make_rsrc_s(q + qbase, VAR ? span_bytes(nq, DR, p.sq) : (unsigned)nq * DR * 2);
-    const rsrc_s_t o_rs = make_rsrc_s(dout + obase, VAR ? span_bytes(nq, DR, p.hq * DR) : (unsigned)nq * DR * 2);
-    const rsrc_s_t l_rs = make_rsrc_s(nlse + rbase, (unsigned)nq * 4);
-    const rsrc_s_t d_rs = make_rsrc_s(ndelta + rbase, (unsigned)nq * 4);
-    const buf_rsrc_t v_rs = make_rsrc(v + vbase, VAR ? span_bytes(nk, DR, p.sv) : (unsigned)nk * DR * 2);
-    const int dma_voff = dma_lane_voff<D, VAR>(lane, w, DR, VAR ? p.sq : DR);
-    const int dma_voff_o = VAR ? dma_lane_voff<D, VAR>(lane, w, DR, p.hq * DR) : dma_voff;
-    auto stage = [&](int buf, int qs) {
-        dma_stage_tile<D, BQ, NW, VAR>(q_rs, Qs + buf * Q_BYTES, qs, dma_voff, w, DR, 0, VAR ? p.sq : DR);
-        dma_stage_tile<D, BQ, NW, VAR>(o_rs, Os + buf * Q_BYTES, qs, dma_voff_o, w, DR, 0, VAR ? p.hq * DR : DR);
-        // row constants: 64 floats each, one 4-byte LDS-DMA per lane (rows >= nq read as 0: harmless, their dO is 0)
-        if (w == 0) dma4_issue(l_rs, lds_addr_of(Ls + buf * 128), lane * 4, __builtin_amdgcn_readfirstlane(qs * 4));
-        if (w == 1) dma4_issue(d_rs, lds_addr_of(Ls + buf * 128 + 64), lane * 4, __builtin_amdgcn_readfirstlane(qs * 4));
-    };
-    const MaskSrc msk = make_mask_src(p, bh);
-    const bool use_bm = (FEAT & kFeatMask) && p.bmask != nullptr;
-    const bool drop = (FEAT & kFeatDrop) && p.p_drop > 0.f;
-    const int cbw = min(kw0, nk - 1) / p.bc;   // block column of this wave's 32 keys (bc is a multiple of 32)
-
-    if constexpr (VAR) dma_stage_tile<D, BK, NW, VAR>(k_rs, Ks, key0, dma_lane_voff<D, VAR>(lane, w, DR, p.sk), w, DR, 0, p.sk);
-    else dma_stage_tile<D, BK, NW>(k_rs, Ks, key0, dma_voff, w, DR);
-    s16x8 vf[NKS];
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) vf[ks] = buf_load_frag(v_rs, frag_off<VAR>(key, 16 * ks + 8 * h, DR, true, VAR ? p.sv : DR));
-
-    f32x16 dka[NDB], dva[NDB];
-#pragma unroll
-    for (int t = 0; t < NDB; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { dka[t][i] = 0.f; dva[t][i] = 0.f; }
-
-    // key j is visible from row j - coff on: earlier query tiles see none of this workgroup's (this wave's) keys
-    constexpr bool WIN = (FEAT & kFeatWindow) != 0;
-    // window: key j is visible from row j - coff - wr to row j - coff + wl; rows past the last key's band see none of
-    // the workgroup's (query tiles [0, ntile)) or of this wave's keys (iterations [it_first, it_last) compute)
-    const int qs_first = WIN ? (max(0, key0 - p.coff - p.wr) / BQ) * BQ : (p.causal ? (max(0, key0 - p.coff) / BQ) * BQ : 0);
-    const int qend = WIN ? min(nq, min(key0 + BK, nk) - p.coff + p.wl) : nq;
-    const int ntile = qs_first < qend ? (qend - qs_first + BQ - 1) / BQ : 0;
-    const int it_first = WIN ? max(0, kw0 - p.coff - p.wr) / BQ - qs_first / BQ
-                             : (p.causal ? max(0, kw0 - p.coff) / BQ - qs_first / BQ : 0);
-    const int it_last = WIN ? (kw0 < nk ? min(ntile, (max(0, min(nq, min(kw0 + 32, nk) - p.coff + p.wl)) + BQ - 1) / BQ - qs_first / BQ) : 0)
-                            : ntile;
-    LiveScan<false, BQ> scan;
-    if (use_bm) scan.init(p, key0, min(key0 + BK, nk), qs_first, nq, ntile, lane);   // (window: over the band's tiles)
-    auto next_live = [&](int it) { return use_bm ? scan.next(it) : it; };
-    const int li = lane & 15, g16 = (lane >> 4) & 1, tq = li >> 2, tp = li & 3;
-
-    int it = next_live(0), cur = 0;
-    if (it < ntile) stage(0, qs_first + it * BQ);
-    dma_wait_all();
-    __syncthreads();
-    // feed-only iterations first (tiles before this wave's first visible row), then the computing ones
-    while (it < min(it_first, ntile)) {
-        const int itn = next_live(it + 1);
-        if (itn < ntile) stage(cur ^ 1, qs_first + itn * BQ);
-        dma_wait_all();
-        __syncthreads();
-        cur ^= 1;
-        it = itn;
-    }
-    while (it < it_last) {
-        const int itn = next_live(it + 1);
-        if (itn < ntile) stage(cur ^ 1, qs_first + itn * BQ);
-        const int qs = qs_first + it * BQ;
-        const char* Qt = Qs + cur * Q_BYTES;
-        const char* Ot = Os + cur * Q_BYTES;
-        const float* Lt = Ls + cur * 128;
-#pragma unroll
-        for (int qb = 0; qb < BQ / 32; ++qb) {
-            const int rb0 = qs + 32 * qb;              // first row of the block; register i holds row rb0 + 4 h + rc(i)
-            unsigned vis = 0xffffu, kp = 0xffffu;
-            if constexpr (FEAT & kFeatMask) {
-                if constexpr (M16) { if (msk.on) vis = dense_bits_k_lds(msk, rb0, nk, kw0, lane, reinterpret_cast<char*>(Ls + 2 * 128) + 1024 * w); }
-                else if (msk.on) vis = dense_bits_k(msk, rb0 + 4 * h, nk, key);
-                if (use_bm && p.bmask[(min(rb0, nq - 1) / p.br) * p.nbc + cbw] == 0) vis = 0;
-            }
-            if constexpr (FEAT & kFeatDrop) {
-                if (drop) kp = keep_bits_k(p, (unsigned)bh * p.nqh, rb0 + 4 * h, key);
-            }
-            // a block of which this wave sees nothing is not computed (wave-uniform; see the forward kernel)
-            if ((FEAT & kFeatMask) && !__any(vis != 0)) continue;
-            // masked: the row precedes the key's first visible row (causal), or the key lies past nk: rc(i) < thr;
-            // window: also the row follows the key's last visible row, rc(i) > thh
-            const bool need_mask = WIN ? ((kw0 + 31 - p.coff - p.wr > rb0) || (kw0 + 32 > nk) || (rb0 + 31 > kw0 - p.coff + p.wl))
-                                       : ((p.causal && (kw0 + 31 - p.coff > rb0)) || (kw0 + 32 > nk));
-            const int thr = WIN ? (!need_mask ? -1 : (key >= nk ? 64 : key - p.coff - p.wr - rb0 - 4 * h))
-                                : (!need_mask ? -1 : (key >= nk ? 64 : (p.causal ? key - p.coff - rb0 - 4 * h : -1)));
-            [[maybe_unused]] const int thh = WIN && need_mask ? key - p.coff + p.wl - rb0 - 4 * h : 64;
-            int kofs = 32 * w * 2 * D;
-            asm volatile("" : "+v"(kofs));
-            u32x4 pp[2], sp[2];
-            [[maybe_unused]] u32x4 pu[2];   // dropout: the un-dropped 16-bit P (dS = P (dP_drop - delta))
-            {
-                f32x16 sacc;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x4 a = *reinterpret_cast<const f32x4*>(Lt + 32 * qb + 8 * g + 4 * h);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) sacc[4 * g + j] = a[j];
-                }
-#pragma unroll
-                for (int ks = 0; ks < NKS; ++ks) {
-                    const int ro = TileSwz<D>::off(r, 2 * ks + h);
-                    const s16x8 qa = *reinterpret_cast<const s16x8*>(Qt + 32 * qb * 2 * D + ro);
-                    const s16x8 kf = *reinterpret_cast<const s16x8*>(Ks + ro + kofs);
-                    sacc = mfma32<Tag>(qa, kf, sacc);
-                }
-                // wave-uniform: blocks that every lane sees whole (most of a structured mask) skip the selects
-                const bool plain = !need_mask && (!(FEAT & kFeatMask) || !__any(vis != 0xffffu));
-                if (plain) {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) sacc[i] = __builtin_amdgcn_exp2f(sacc[i] * c_log2);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        bool dead = rc_of(i) < thr;
-                        if constexpr (WIN) dead = dead || rc_of(i) > thh;
-                        if constexpr (FEAT & kFeatMask) dead = dead || !((vis >> i) & 1u);
-                        sacc[i] = dead ? 0.f : __builtin_amdgcn_exp2f(sacc[i] * c_log2);
-                    }
-                }
-                if constexpr (FEAT & kFeatDrop) {
-#pragma unroll
-                    for (int s = 0; s < 2; ++s)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) pu[s][j] = pack2<Tag>(sacc[8 * s + 2 * j], sacc[8 * s + 2 * j + 1]);
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) sacc[i] = ((kp >> i) & 1u) ? sacc[i] * p.keep_scale : 0.f;
-                }
-#pragma unroll
-                for (int s = 0; s < 2; ++s)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) pp[s][j] = pack2<Tag>(sacc[8 * s + 2 * j], sacc[8 * s + 2 * j + 1]);
-            }
-            {
-                f32x16 pacc;
-                f32x4 ndv[4];
-#pragma unroll
-                for (int g = 0; g < 4; ++g) ndv[g] = *reinterpret_cast<const f32x4*>(Lt + 64 + 32 * qb + 8 * g + 4 * h);
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) pacc[4 * g + j] = (FEAT & kFeatDrop) ? 0.f : ndv[g][j];
-#pragma unroll
-                for (int ks = 0; ks < NKS; ++ks) {
-                    const s16x8 oa = *reinterpret_cast<const s16x8*>(Ot + 32 * qb * 2 * D + TileSwz<D>::off(r, 2 * ks + h));
-                    pacc = mfma32<Tag>(oa, vf[ks], pacc);
-                }
-                if constexpr (FEAT & kFeatDrop) {   // dP' = keep / (1 - p) * (dO V^T) - delta
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) pacc[i] = (((kp >> i) & 1u) ? pacc[i] * p.keep_scale : 0.f) + ndv[i >> 2][i & 3];
-                }
-                if constexpr (std::is_same<Tag, f16_tag>::value) mfma_result_fence(pacc);   // mul_pack<f16> reads pacc from asm
-#pragma unroll
-                for (int s = 0; s < 2; ++s)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        sp[s][j] = mul_pack<Tag>((FEAT & kFeatDrop) ? pu[s][j] : pp[s][j], pacc[8 * s + 2 * j], pacc[8 * s + 2 * j + 1]);
-                if constexpr (std::is_same<Tag, f16_tag>::value) asm volatile("s_nop 1" : "+v"(sp[0]), "+v"(sp[1]));
-            }
-            if (D > 64) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const s16x8 pb = *reinterpret_cast<s16x8*>(&pp[s]);
-                const s16x8 sb = *reinterpret_cast<s16x8*>(&sp[s]);
-                const int qa_ = 32 * qb + 16 * s + 4 * h + tq;
-#pragma unroll
-                for (int db = 0; db < NDB; ++db) {
-                    const int ch = 4 * db + 2 * g16 + (tp >> 1);
-                    const int o1 = TileSwz<D>::off(qa_, ch) + 8 * (tp & 1);
-                    const int o2 = TileSwz<D>::off(qa_ + 8, ch) + 8 * (tp & 1);
-                    const s16x8 doT = cat8(lds_tr16(Ot + o1), lds_tr16(Ot + o2));
-                    dva[db] = mfma32<Tag>(doT, pb, dva[db]);
-                    const s16x8 qT = cat8(lds_tr16(Qt + o1), lds_tr16(Qt + o2));
-                    dka[db] = mfma32<Tag>(qT, sb, dka[db]);
-                }
-                if (D > 64) __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        dma_wait_all();
-        __syncthreads();
-        cur ^= 1;
-        it = itn;
-    }
-    if constexpr (WIN) {
-        // trailing feed-only iterations: rows past this wave's keys' band, inside the workgroup's
-        while (it < ntile) {
-            const int itn = next_live(it + 1);
-            if (itn < ntile) stage(cur ^ 1, qs_first + itn * BQ);
-            dma_wait_all();
-            __syncthreads();
-            cur ^= 1;
-            it = itn;
-        }
-    }
-
-    if (key < nk) {
-        // dK / dV rows: per query head (grouped: the partials kv_group_sum adds up)
-        // (varlen: rows of (total_k, hq, d) — the partials, or dk / dv themselves when hq = hkv)
-        const size_t krow = VAR ? ((size_t)(sk0 + key) * p.hq + hh) * DR : ((size_t)bh * nk + key) * DR;
-        uint16_t* dkrow = dk + krow;
-        uint16_t* dvrow = dv + krow;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                u32x2 a, b;
-                a[0] = pack2_rn<Tag>(dka[db][4 * g + 0] * p.scale, dka[db][4 * g + 1] * p.scale);
-                a[1] = pack2_rn<Tag>(dka[db][4 * g + 2] * p.scale, dka[db][4 * g + 3] * p.scale);
-                b[0] = pack2_rn<Tag>(dva[db][4 * g + 0], dva[db][4 * g + 1]);
-                b[1] = pack2_rn<Tag>(dva[db][4 * g + 2], dva[db][4 * g + 3]);
-                if (32 * db + 8 * g + 4 * h >= DR) continue;   // padded columns (DR is a multiple of 8)
-                *reinterpret_cast<u32x2*>(dkrow + 32 * db + 8 * g + 4 * h) = a;
-                *reinterpret_cast<u32x2*>(dvrow + 32 * db + 8 * g + 4 * h) = b;
-            }
-    }
+#include "fa_ex_mfma_dkdv.inc"
+}
+template <typename Tag, int D, int FEAT, bool M16 = false>
+__global__ __launch_bounds__(512, 2) void exm_dkdv_score_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
+                                                                const uint16_t* __restrict__ v, const uint16_t* __restrict__ dout,
+                                                                const float* __restrict__ nlse, const float* __restrict__ ndelta,
+                                                                uint16_t* __restrict__ dk, uint16_t* __restrict__ dv, ExParamsS p,
+                                                                float c_log2) {
+#include "fa_ex_mfma_dkdv.inc"
 }
 // ------------------------------------------------------------------------------------------------ dQ
 template <typename Tag, int D, int FEAT>
@@ -800,197 +365,14 @@ __global__ __launch_bounds__(512, 2) void exm_dq_kernel(const uint16_t* __restri
                                                         const uint16_t* __restrict__ v, const uint16_t* __restrict__ dout,
                                                         const float* __restrict__ nlse, const float* __restrict__ ndelta,
                                                         uint16_t* __restrict__ dq, ExParams p, float c_log2) {
-    constexpr int NW = 8, BM = 32 * NW, BN = 64, NKS = D / 16, NDB = D / 32, TILE_BYTES = BN * D * 2;
-    constexpr bool VAR = (FEAT & kFeatVarlen) != 0;
-    extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 buffers][K tile | V tile]
-    const int DR = p.d;
-    int nq = p.nq, nk = p.nk;
-    const int nqt = (nq + BM - 1) / BM;
-    const int L = xcd_remap(blockIdx.x, gridDim.x);
-    const int bh = L / nqt;
-    const int q0 = (L - bh * nqt) * BM;
-    EXM_VARLEN_UNIT(q0, nq)
-    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, h = lane >> 5;
-    const size_t qbase = VAR ? (size_t)sq0 * p.sq + hh * DR : (size_t)bh * nq * DR;
-    const size_t kbase = VAR ? (size_t)sk0 * p.sk + hk * DR : (size_t)kv_unit(bh, p.kvg) * nk * DR;
-    const size_t vbase = VAR ? (size_t)sk0 * p.sv + hk * DR : kbase;
-    const size_t obase = VAR ? ((size_t)sq0 * p.hq + hh) * DR : qbase;
-    const size_t rbase = VAR ? (size_t)hh * p.total_q + sq0 : (size_t)bh * nq;
-    const int ostr = VAR ? p.hq * DR : DR;   // rows of dout and dq
-    const int qrow = q0 + 32 * w + r;
-    const bool live_row = qrow < nq;
-
-    const buf_rsrc_t q_rs = make_rsrc(q + qbase, VAR ? span_bytes(nq, DR, p.sq) : (unsigned)nq * DR * 2);
-    const buf_rsrc_t o_rs = make_rsrc(dout + obase, VAR ? span_bytes(nq, DR, ostr) : (unsigned)nq * DR * 2);
-    s16x8 qf[NKS], of[NKS];
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-        qf[ks] = buf_load_frag(q_rs, frag_off<VAR>(qrow, 16 * ks + 8 * h, DR, true, VAR ? p.sq : DR));
-        of[ks] = buf_load_frag(o_rs, frag_off<VAR>(qrow, 16 * ks + 8 * h, DR, true, ostr));
-    }
-    const float nl = live_row ? nlse[rbase + qrow] : 0.f;
-    const float nd = live_row ? ndelta[rbase + qrow] : 0.f;
-
-    const rsrc_s_t k_rs = make_rsrc_s(k + kbase, VAR ? span_bytes(nk, DR, p.sk) : (unsigned)nk * DR * 2);
-    const rsrc_s_t v_rs = make_rsrc_s(v + vbase, VAR ? span_bytes(nk, DR, p.sv) : (unsigned)nk * DR * 2);
-    const int dma_voff = dma_lane_voff<D, VAR>(lane, w, DR, VAR ? p.sk : DR);
-    const int dma_voff_v = VAR ? dma_lane_voff<D, VAR>(lane, w, DR, p.sv) : dma_voff;
-    auto stage = [&](int buf, int k0) {
-        char* kb_ = smem + buf * 2 * TILE_BYTES;
-        dma_stage_tile<D, BN, NW, VAR>(k_rs, kb_, k0, dma_voff, w, DR, 0, VAR ? p.sk : DR);
-        dma_stage_tile<D, BN, NW, VAR>(v_rs, kb_ + TILE_BYTES, k0, dma_voff_v, w, DR, 0, VAR ? p.sv : DR);
-    };
-    const MaskSrc msk = make_mask_src(p, bh);
-    const bool use_bm = (FEAT & kFeatMask) && p.bmask != nullptr;
-    const bool drop = (FEAT & kFeatDrop) && p.p_drop > 0.f;
-    const unsigned hi = (unsigned)bh * p.nqh + ((unsigned)qrow >> 1);
-    const int rbw = min(q0 + 32 * w, nq - 1) / p.br;
-
-    f32x16 dqa[NDB];
-#pragma unroll
-    for (int t = 0; t < NDB; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) dqa[t][i] = 0.f;
-
-    constexpr bool WIN = (FEAT & kFeatWindow) != 0;   // (the tile ranges of the forward kernel)
-    const int kend = WIN ? max(0, min(nk, min(q0 + BM, nq) + p.coff + p.wr)) : (p.causal ? max(0, min(nk, q0 + BM + p.coff)) : nk);
-    const int kend_w = WIN ? (q0 + 32 * w < nq ? max(0, min(nk, min(q0 + 32 * w + 32, nq) + p.coff + p.wr)) : 0)
-                           : (p.causal ? max(0, min(nk, q0 + 32 * w + 32 + p.coff)) : nk);
-    const int ntiles = (kend + BN - 1) / BN, ntiles_w = (kend_w + BN - 1) / BN;
-    const int t_lo = WIN ? max(0, q0 + p.coff - p.wl) / BN : 0;
-    const int t_lo_w = WIN ? max(0, q0 + 32 * w + p.coff - p.wl) / BN : 0;
-    LiveScan<true, BN> scan;
-    if (use_bm) scan.init(p, q0, min(q0 + BM, nq), 0, nk, ntiles, lane);
-    auto next_live = [&](int t) { return use_bm ? scan.next(t) : t; };
-    const int li = lane & 15, g16 = (lane >> 4) & 1, tq = li >> 2, tp = li & 3;
-
-    int t = next_live(t_lo), cur = 0;
-    if (t < ntiles) stage(0, t * BN);
-    dma_wait_all();
-    __syncthreads();
-    if constexpr (WIN) {
-        while (t < min(t_lo_w, ntiles)) {   // leading feed-only tiles
-            const int tn = next_live(t + 1);
-            if (tn < ntiles) stage(cur ^ 1, tn * BN);
-            dma_wait_all();
-            __syncthreads();
-            cur ^= 1;
-            t = tn;
-        }
-    }
-    const bool late_stage = (FEAT & kFeatMask) && msk.on;   // see the forward kernel
-    while (t < ntiles_w) {
-        const int tn = next_live(t + 1);
-        if (!late_stage && tn < ntiles) stage(cur ^ 1, tn * BN);
-        const int k0 = t * BN;
-        const char* Kt = smem + cur * 2 * TILE_BYTES;
-        const char* Vt = Kt + TILE_BYTES;
-        u32x4 dsb[2][2];
-        unsigned visw[2] = {0xffffu, 0xffffu};
-        if constexpr (FEAT & kFeatMask) {
-            if (msk.on) {
-                visw[0] = dense_bits_q(msk, qrow, nk, k0 + 4 * h, h);
-                visw[1] = dense_bits_q(msk, qrow, nk, k0 + 32 + 4 * h, h);
-                if (tn < ntiles) stage(cur ^ 1, tn * BN);
-            }
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-                if (use_bm && p.bmask[rbw * p.nbc + min(k0 + 32 * kb, nk - 1) / p.bc] == 0) visw[kb] = 0;
-        }
-        // a tile of which this wave sees nothing is not computed (wave-uniform; see the forward kernel)
-        const bool any_vis = !(FEAT & kFeatMask) || __any((visw[0] | visw[1]) != 0) != 0;
-        if (any_vis) {
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            unsigned vis = visw[kb], kp = 0xffffu;
-            if constexpr (FEAT & kFeatDrop) {
-                if (drop) kp = keep_bits_q(p, hi, qrow, k0 + 32 * kb + 4 * h);
-            }
-            f32x16 sacc, pacc;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { sacc[i] = nl; pacc[i] = (FEAT & kFeatDrop) ? 0.f : nd; }
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) {
-                const int off = TileSwz<D>::off(32 * kb + r, 2 * ks + h);
-                const s16x8 ka = *reinterpret_cast<const s16x8*>(Kt + off);
-                sacc = mfma32<Tag>(ka, qf[ks], sacc);
-                const s16x8 va = *reinterpret_cast<const s16x8*>(Vt + off);
-                pacc = mfma32<Tag>(va, of[ks], pacc);
-            }
-            const bool need_mask = WIN ? ((k0 + 32 * kb + 31 > q0 + 32 * w + p.coff + p.wr) || (k0 + 32 * kb + 32 > nk) ||
-                                          (k0 + 32 * kb < q0 + 32 * w + 31 + p.coff - p.wl))
-                                       : ((p.causal && (k0 + 32 * kb + 31 > q0 + 32 * w + p.coff)) || (k0 + 32 * kb + 32 > nk));
-            const int lim = WIN ? min(qrow + p.coff + p.wr, nk - 1) : (p.causal ? min(qrow + p.coff, nk - 1) : nk - 1);
-            const int thr = need_mask ? lim - (k0 + 32 * kb + 4 * h) : 64;
-            [[maybe_unused]] const int thl = WIN && need_mask ? qrow + p.coff - p.wl - (k0 + 32 * kb + 4 * h) : -64;
-            // wave-uniform (not in the dropout build: two copies of its selects cost registers it does not have)
-            const bool plain = !(FEAT & kFeatDrop) && !need_mask && (!(FEAT & kFeatMask) || !__any(vis != 0xffffu));
-            if (plain) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    float dpv = pacc[i];
-                    if constexpr (FEAT & kFeatDrop) dpv = (((kp >> i) & 1u) ? dpv * p.keep_scale : 0.f) + nd;
-                    pacc[i] = __builtin_amdgcn_exp2f(sacc[i] * c_log2) * dpv;
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    bool dead = rc_of(i) > thr;
-                    if constexpr (WIN) dead = dead || rc_of(i) < thl;
-                    if constexpr (FEAT & kFeatMask) dead = dead || !((vis >> i) & 1u);
-                    float dpv = pacc[i];
-                    if constexpr (FEAT & kFeatDrop) dpv = (((kp >> i) & 1u) ? dpv * p.keep_scale : 0.f) + nd;
-                    pacc[i] = dead ? 0.f : __builtin_amdgcn_exp2f(sacc[i] * c_log2) * dpv;
-                }
-            }
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) dsb[kb][s][j] = pack2<Tag>(pacc[8 * s + 2 * j], pacc[8 * s + 2 * j + 1]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const s16x8 sb = *reinterpret_cast<s16x8*>(&dsb[kb][s]);
-                const int key_a = 32 * kb + 16 * s + 4 * h + tq;
-#pragma unroll
-                for (int db = 0; db < NDB; ++db) {
-                    const int ch = 4 * db + 2 * g16 + (tp >> 1);
-                    const s16x8 a = cat8(lds_tr16(Kt + TileSwz<D>::off(key_a, ch) + 8 * (tp & 1)),
-                                         lds_tr16(Kt + TileSwz<D>::off(key_a + 8, ch) + 8 * (tp & 1)));
-                    dqa[db] = mfma32<Tag>(a, sb, dqa[db]);
-                }
-            }
-        }   // any_vis
-        dma_wait_all();
-        __syncthreads();
-        cur ^= 1;
-        t = tn;
-    }
-    while (t < ntiles) {
-        const int tn = next_live(t + 1);
-        if (tn < ntiles) stage(cur ^ 1, tn * BN);
-        dma_wait_all();
-        __syncthreads();
-        cur ^= 1;
-        t = tn;
-    }
-    if (live_row) {
-        uint16_t* drow = dq + obase + (size_t)qrow * ostr;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                if (32 * db + 8 * g + 4 * h >= DR) continue;
-                u32x2 val;
-                val[0] = pack2_rn<Tag>(dqa[db][4 * g + 0] * p.scale, dqa[db][4 * g + 1] * p.scale);
-                val[1] = pack2_rn<Tag>(dqa[db][4 * g + 2] * p.scale, dqa[db][4 * g + 3] * p.scale);
-                *reinterpret_cast<u32x2*>(drow + 32 * db + 8 * g + 4 * h) = val;
-            }
-    }
+#include "fa_ex_mfma_dq.inc"
+}
+template <typename Tag, int D, int FEAT>
+__global__ __launch_bounds__(512, 2) void exm_dq_score_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
+                                                              const uint16_t* __restrict__ v, const uint16_t* __restrict__ dout,
+                                                              const float* __restrict__ nlse, const float* __restrict__ ndelta,
+                                                              uint16_t* __restrict__ dq, ExParamsS p, float c_log2) {
+#include "fa_ex_mfma_dq.inc"
 }
 // ------------------------------------------------------------------------------------------------ host side
 bool ex_mfma_supported(const ExArgs& a) {
@@ -1003,16 +385,30 @@ bool ex_mfma_supported(const ExArgs& a) {
     return true;
 }
 
+// the kernel entry of an instantiation: exm_*_score_kernel with kFeatScore
+template <typename Tag, int D, int FEAT> static auto exm_fwd_entry() {
+    if constexpr ((FEAT & kFeatScore) != 0) return exm_fwd_score_kernel<Tag, D, FEAT>;
+    else return exm_fwd_kernel<Tag, D, FEAT>;
+}
+template <typename Tag, int D, int FEAT, bool M16> static auto exm_dkdv_entry() {
+    if constexpr ((FEAT & kFeatScore) != 0) return exm_dkdv_score_kernel<Tag, D, FEAT, M16>;
+    else return exm_dkdv_kernel<Tag, D, FEAT, M16>;
+}
+template <typename Tag, int D, int FEAT> static auto exm_dq_entry() {
+    if constexpr ((FEAT & kFeatScore) != 0) return exm_dq_score_kernel<Tag, D, FEAT>;
+    else return exm_dq_kernel<Tag, D, FEAT>;
+}
+
 template <typename Tag, int D, int FEAT>
 static hipError_t exm_fwd_t(const ExArgs& a, hipStream_t st) {
     const size_t smem = 2 * 2 * 128 * D * 2;
-    auto kern = exm_fwd_kernel<Tag, D, FEAT>;
+    auto kern = exm_fwd_entry<Tag, D, FEAT>();
     hipError_t e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
     if (e != hipSuccess) return e;
     dim3 grid((unsigned)(((a.nq + 255) / 256) * a.bh));
     ProfScope ps(K_EX_FWD, st);
     hipLaunchKernelGGL(kern, grid, dim3(512), smem, st, (const uint16_t*)a.q, (const uint16_t*)a.k, (const uint16_t*)a.v,
-                       (uint16_t*)a.o, a.lse, make_ex_params(a), a.scale * 1.4426950408889634f);
+                       (uint16_t*)a.o, a.lse, make_exm_params<FEAT>(a), a.scale * 1.4426950408889634f);
     return hipGetLastError();
 }
 
@@ -1021,7 +417,7 @@ static hipError_t exm_bwd_t(const ExArgs& a, hipStream_t st) {
     const long long rows = (long long)a.bh * a.nq;
     float* nlse = reinterpret_cast<float*>(a.workspace);
     float* ndelta = nlse + ((rows + 63) & ~63ll);
-    const ExParams p = make_ex_params(a);
+    const ExP<FEAT> p = make_exm_params<FEAT>(a);
     const float c = a.scale * 1.4426950408889634f;
     ProfScope ps(K_EX_BWD, st);
     hipLaunchKernelGGL(exm_prep_kernel<Tag>, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, (const uint16_t*)a.o,
@@ -1031,7 +427,7 @@ static hipError_t exm_bwd_t(const ExArgs& a, hipStream_t st) {
     if (a.nk > 0) {
         const bool m16 = (FEAT & kFeatMask) && p.mask != nullptr && (p.nk & 15) == 0 && (p.mask_bh & 15) == 0 && (((uintptr_t)p.mask) & 15) == 0;
         const size_t smem = (size_t)256 * D * 2 + 4 * 64 * D * 2 + 2 * 128 * sizeof(float) + (m16 ? 8 * 1024 : 0);   // + the waves' mask images
-        auto kern = m16 ? exm_dkdv_kernel<Tag, D, FEAT, (FEAT & kFeatMask) != 0> : exm_dkdv_kernel<Tag, D, FEAT, false>;
+        auto kern = m16 ? exm_dkdv_entry<Tag, D, FEAT, (FEAT & kFeatMask) != 0>() : exm_dkdv_entry<Tag, D, FEAT, false>();
         e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
         if (e != hipSuccess) return e;
         dim3 grid((unsigned)(((a.nk + 255) / 256) * a.bh));
@@ -1042,7 +438,7 @@ static hipError_t exm_bwd_t(const ExArgs& a, hipStream_t st) {
     }
     if (a.nq > 0) {
         const size_t smem = 2 * 2 * 64 * D * 2;
-        auto kern = exm_dq_kernel<Tag, D, FEAT>;
+        auto kern = exm_dq_entry<Tag, D, FEAT>();
         e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
         if (e != hipSuccess) return e;
         dim3 grid((unsigned)(((a.nq + 255) / 256) * a.bh));
@@ -1053,17 +449,22 @@ static hipError_t exm_bwd_t(const ExArgs& a, hipStream_t st) {
     return e;
 }
 
-template <typename Tag, int D>
-static hipError_t exm_by_feat(const ExArgs& a, bool backward, hipStream_t st) {
+// S: 0, or kFeatScore for a call with a score modifier (every other feature combination once more with it)
+template <typename Tag, int D, int S>
+static hipError_t exm_by_feat_s(const ExArgs& a, bool backward, hipStream_t st) {
     const bool masks = a.mask || a.block_mask, drop = a.dropout_p > 0.0;
     if (ex_windowed(a)) {
-        if (drop) return backward ? exm_bwd_t<Tag, D, 7>(a, st) : exm_fwd_t<Tag, D, 7>(a, st);
-        if (masks) return backward ? exm_bwd_t<Tag, D, 5>(a, st) : exm_fwd_t<Tag, D, 5>(a, st);
-        return backward ? exm_bwd_t<Tag, D, 4>(a, st) : exm_fwd_t<Tag, D, 4>(a, st);
+        if (drop) return backward ? exm_bwd_t<Tag, D, S | 7>(a, st) : exm_fwd_t<Tag, D, S | 7>(a, st);
+        if (masks) return backward ? exm_bwd_t<Tag, D, S | 5>(a, st) : exm_fwd_t<Tag, D, S | 5>(a, st);
+        return backward ? exm_bwd_t<Tag, D, S | 4>(a, st) : exm_fwd_t<Tag, D, S | 4>(a, st);
     }
-    if (drop) return backward ? exm_bwd_t<Tag, D, 3>(a, st) : exm_fwd_t<Tag, D, 3>(a, st);
-    if (masks) return backward ? exm_bwd_t<Tag, D, 1>(a, st) : exm_fwd_t<Tag, D, 1>(a, st);
-    return backward ? exm_bwd_t<Tag, D, 0>(a, st) : exm_fwd_t<Tag, D, 0>(a, st);
+    if (drop) return backward ? exm_bwd_t<Tag, D, S | 3>(a, st) : exm_fwd_t<Tag, D, S | 3>(a, st);
+    if (masks) return backward ? exm_bwd_t<Tag, D, S | 1>(a, st) : exm_fwd_t<Tag, D, S | 1>(a, st);
+    return backward ? exm_bwd_t<Tag, D, S>(a, st) : exm_fwd_t<Tag, D, S>(a, st);
+}
+template <typename Tag, int D>
+static hipError_t exm_by_feat(const ExArgs& a, bool backward, hipStream_t st) {
+    return ex_scoremod(a) ? exm_by_feat_s<Tag, D, kFeatScore>(a, backward, st) : exm_by_feat_s<Tag, D, 0>(a, backward, st);
 }
 
 // ---- packed sequences: the varlen kernels on the padded grid (a.bh = batch * heads_q units, a.nq / a.nk = the maxima)
@@ -1083,12 +484,12 @@ bool ex_mfma_varlen_supported(const ExArgs& a) {
 
 template <typename Tag, int D, int FEAT>
 static hipError_t exm_varlen_t(const ExArgs& a, bool backward, hipStream_t st) {
-    const ExParams p = make_ex_params(a);
+    const ExP<FEAT> p = make_exm_params<FEAT>(a);
     const float c = a.scale * 1.4426950408889634f;
     hipError_t e;
     if (!backward) {
         const size_t smem = 2 * 2 * 128 * D * 2;
-        auto kern = exm_fwd_kernel<Tag, D, FEAT | kFeatVarlen>;
+        auto kern = exm_fwd_entry<Tag, D, FEAT | kFeatVarlen>();
         e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
         if (e != hipSuccess) return e;
         ProfScope ps(K_EX_FWD, st);
@@ -1109,7 +510,7 @@ static hipError_t exm_varlen_t(const ExArgs& a, bool backward, hipStream_t st) {
     if (e != hipSuccess) return e;
     {
         const size_t smem = (size_t)256 * D * 2 + 4 * 64 * D * 2 + 2 * 128 * sizeof(float);
-        auto kern = exm_dkdv_kernel<Tag, D, FEAT | kFeatVarlen>;
+        auto kern = exm_dkdv_entry<Tag, D, FEAT | kFeatVarlen, false>();
         e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kern, dim3((unsigned)(((a.nk + 255) / 256) * a.bh)), dim3(512), smem, st, (const uint16_t*)a.q,
@@ -1119,7 +520,7 @@ static hipError_t exm_varlen_t(const ExArgs& a, bool backward, hipStream_t st) {
         if (e != hipSuccess) return e;
     }
     const size_t smem = 2 * 2 * 64 * D * 2;
-    auto kern = exm_dq_kernel<Tag, D, FEAT | kFeatVarlen>;
+    auto kern = exm_dq_entry<Tag, D, FEAT | kFeatVarlen>();
     e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3((unsigned)(((a.nq + 255) / 256) * a.bh)), dim3(512), smem, st, (const uint16_t*)a.q,
@@ -1128,11 +529,15 @@ static hipError_t exm_varlen_t(const ExArgs& a, bool backward, hipStream_t st) {
     return hipGetLastError();
 }
 
+template <typename Tag, int D, int S>
+static hipError_t exm_varlen_by_feat_s(const ExArgs& a, bool backward, hipStream_t st) {
+    const bool drop = a.dropout_p > 0.0;
+    if (ex_windowed(a)) return drop ? exm_varlen_t<Tag, D, S | kFeatWindow | kFeatDrop>(a, backward, st) : exm_varlen_t<Tag, D, S | kFeatWindow>(a, backward, st);
+    return drop ? exm_varlen_t<Tag, D, S | kFeatDrop>(a, backward, st) : exm_varlen_t<Tag, D, S>(a, backward, st);
+}
 template <typename Tag, int D>
 static hipError_t exm_varlen_by_feat(const ExArgs& a, bool backward, hipStream_t st) {
-    const bool drop = a.dropout_p > 0.0;
-    if (ex_windowed(a)) return drop ? exm_varlen_t<Tag, D, kFeatWindow | kFeatDrop>(a, backward, st) : exm_varlen_t<Tag, D, kFeatWindow>(a, backward, st);
-    return drop ? exm_varlen_t<Tag, D, kFeatDrop>(a, backward, st) : exm_varlen_t<Tag, D, 0>(a, backward, st);
+    return ex_scoremod(a) ? exm_varlen_by_feat_s<Tag, D, kFeatScore>(a, backward, st) : exm_varlen_by_feat_s<Tag, D, 0>(a, backward, st);
 }
 
 // (the caller has checked ex_mfma_varlen_supported, and that max_seqlen_q, max_seqlen_k, total_q, total_k are > 0)

@@ -147,7 +147,15 @@ struct ExArgs {
     const int* cu_q = nullptr;
     const int* cu_k = nullptr;
     int64_t heads_q = 0, total_q = 0, total_k = 0, stride_q = 0, stride_k = 0, stride_v = 0;
+    // score modifiers (fa_ex_*_scoremod), between Q K^T and the softmax: s' = softcap tanh(s / softcap) if softcap > 0, then
+    // s'' = s' - slope(u) |i + coff - j| if alibi != null, s = scale q.k.  Query unit u takes slope
+    // alibi[(u / alibi_heads) * alibi_bstride + u % alibi_heads] (device memory, read by the kernels only).
+    double softcap = 0.0;
+    const float* alibi = nullptr;
+    int64_t alibi_heads = 1, alibi_bstride = 0;
 };
+// does the call carry a score modifier (softcap or ALiBi)?  Such a call runs on the extended kernels only.
+inline bool ex_scoremod(const ExArgs& a) { return a.softcap > 0.0 || a.alibi != nullptr; }
 // does the call carry a window that bounds something (canonicalised: any bound that is not -1)?
 inline bool ex_windowed(const ExArgs& a) { return a.window_left >= 0 || a.window_right >= 0; }
 hipError_t launch_ex(const ExArgs& a, bool backward, hipStream_t st);

@@ -19,6 +19,8 @@ There is NO CPU fallback: a missing library or a non-device tensor is an error.
 from __future__ import annotations
 
 import ctypes
+import math
+import numbers
 import os
 import operator
 
@@ -39,6 +41,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_ex_forward_grouped", "fa_ex_backward_grouped", "fa_ex_backward_workspace_bytes_grouped",
     "fa_ex_backward_workspace_bytes_fast_grouped", "fa_ex_forward_window", "fa_ex_backward_window",
     "fa_ex_forward_varlen", "fa_ex_backward_varlen", "fa_ex_backward_workspace_bytes_varlen",
+    "fa_ex_forward_scoremod", "fa_ex_backward_scoremod", "fa_ex_forward_varlen_scoremod", "fa_ex_backward_varlen_scoremod",
 )
 
 
@@ -120,6 +123,19 @@ def _load_library() -> ctypes.CDLL:
     lib.fa_ex_backward_varlen.restype = ci
     lib.fa_ex_backward_workspace_bytes_varlen.argtypes = [i64, i64, i64, i64, i64, ci]
     lib.fa_ex_backward_workspace_bytes_varlen.restype = sz
+    # score modifiers: the window (varlen) arguments with softcap, alibi_slopes, alibi_heads (not varlen), alibi_batch_stride right
+    # after softmax_scale
+    lib.fa_ex_forward_scoremod.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, ci, i64, i64, dbl, dbl, vp, i64, i64, vp, i64,
+                                           vp, i64, i64, dbl, u64, vp]
+    lib.fa_ex_forward_scoremod.restype = ci
+    lib.fa_ex_backward_scoremod.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, ci, i64, i64, dbl, dbl, vp,
+                                            i64, i64, vp, i64, vp, i64, i64, dbl, u64, vp, sz, vp]
+    lib.fa_ex_backward_scoremod.restype = ci
+    varlen_sm = varlen[:18] + [dbl, vp, i64] + varlen[18:]
+    lib.fa_ex_forward_varlen_scoremod.argtypes = [vp, vp, vp, vp, vp] + varlen_sm + [vp]
+    lib.fa_ex_forward_varlen_scoremod.restype = ci
+    lib.fa_ex_backward_varlen_scoremod.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp] + varlen_sm + [vp, sz, vp]
+    lib.fa_ex_backward_varlen_scoremod.restype = ci
     return lib
 
 
@@ -368,21 +384,68 @@ def window_effective(nq, nk, causal, window) -> bool:
     return left >= 0 or right >= 0
 
 
-def ex_forward(q, k, v, causal, softmax_scale, mask=None, block_mask=None, br=128, bc=128, dropout_p=0.0, seed=0, window=(-1, -1)):
+def softcap_arg(who, softcap) -> float:
+    """softcap as a float, finite and >= 0 (0 = off); the C layer's error text for anything else."""
+    if isinstance(softcap, bool) or not isinstance(softcap, numbers.Real):
+        raise RuntimeError(f"{who}: softcap must be a finite number >= 0 (got {softcap!r})")
+    c = float(softcap)
+    if not (math.isfinite(c) and c >= 0.0):
+        raise RuntimeError(f"{who}: softcap must be a finite number >= 0 (got {c!r})")
+    return c
+
+
+def alibi_arg(who, slopes, device, units, heads=None):
+    """(pointer, alibi_heads, alibi_batch_stride, tensor) of ALiBi slopes (FlashAttention-2's alibi_slopes): float32 on `device`,
+    (heads,) or (units / heads, heads) with a unit last-dim stride — contiguous, or a (B, H) view of an (H,) vector (row stride 0).
+    heads=None (the 3-D calls, (BH, N, d)): one slope per unit, (BH,), or (B, H) with B * H = BH.  (0, 1, 0, None) without slopes."""
+    if slopes is None:
+        return 0, 1, 0, None
+    if not isinstance(slopes, torch.Tensor):
+        raise RuntimeError(f"{who}: alibi_slopes must be a float32 tensor")
+    if slopes.dtype != torch.float32:
+        raise RuntimeError(f"{who}: alibi_slopes must be float32, got {slopes.dtype}")
+    if slopes.device != device:
+        raise RuntimeError(f"{who}: alibi_slopes must be on q's device ({device}), got {slopes.device}")
+    if heads is None:
+        forms = f"({units},) or (B, H) with B * H = {units}"
+        ok = (slopes.dim() == 1 and slopes.shape[0] == units) or (slopes.dim() == 2 and slopes.shape[0] * slopes.shape[1] == units)
+    else:
+        forms = f"({heads},) or ({units // max(heads, 1)}, {heads})"
+        ok = (slopes.dim() == 1 and slopes.shape[0] == heads) or (slopes.dim() == 2 and tuple(slopes.shape) == (units // heads, heads))
+    if not ok:
+        raise RuntimeError(f"{who}: alibi_slopes must be {forms}, got {tuple(slopes.shape)}")
+    if slopes.dim() == 1:
+        if not slopes.is_contiguous():
+            raise RuntimeError(f"{who}: alibi_slopes must be contiguous")
+        return slopes.data_ptr(), slopes.shape[0], 0, slopes
+    if slopes.shape[1] > 1 and slopes.stride(1) != 1 or (slopes.shape[0] > 1 and slopes.stride(0) not in (0, slopes.shape[1])):
+        raise RuntimeError(f"{who}: alibi_slopes must be contiguous (or a (B, H) view of an (H,) vector)")
+    bstride = slopes.stride(0) if slopes.shape[0] > 1 else 0
+    return slopes.data_ptr(), slopes.shape[1], bstride, slopes
+
+
+def ex_forward(q, k, v, causal, softmax_scale, mask=None, block_mask=None, br=128, bc=128, dropout_p=0.0, seed=0, window=(-1, -1),
+               softcap=0.0, alibi_slopes=None):
     """(o, lse) of attention with Nq != Nk (causal aligned bottom-right), dense mask (0 = masked), block-sparse mask
     (0 = tile skipped) and dropout; see include/fa_mi355x.h.  k and v with BH / g units (g query heads per K/V head) make
     it grouped-query attention.  window = (left, right): key j is visible to row i only within
-    [i + Nk - Nq - left, i + Nk - Nq + right], -1 = unbounded (fa_ex_forward_window)."""
+    [i + Nk - Nq - left, i + Nk - Nq + right], -1 = unbounded (fa_ex_forward_window).  softcap > 0 caps the scores at
+    softcap * tanh(s / softcap); alibi_slopes (float32 (BH,), or (B, H) with B * H = BH) subtract slope * |i + Nk - Nq - j|
+    (fa_ex_forward_scoremod)."""
     wl, wr = window_arg("ex_forward", window)
+    cap = softcap_arg("ex_forward", softcap)
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     bh, nq, nk, d, code, mask, mptr, mstride, block_mask, bptr, g = _ex_common("ex_forward", q, k, v, mask, block_mask, br, bc)
+    aptr, aheads, astride, alibi_slopes = alibi_arg("ex_forward", alibi_slopes, q.device, bh)
     with torch.cuda.device(q.device):
         o = torch.empty_like(q)
         lse = torch.empty((bh, nq), dtype=torch.float32, device=q.device)
         ptrs = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr())
         rest = (nq, nk, d, code, int(bool(causal)), float(softmax_scale), mptr, mstride, bptr, int(br), int(bc), float(dropout_p),
                 int(seed) & (2 ** 64 - 1), _stream_ptr(q.device))
-        if (wl, wr) != (-1, -1):
+        if cap > 0.0 or aptr:
+            _check(_lib.fa_ex_forward_scoremod(*ptrs, bh, g, *rest[:5], wl, wr, rest[5], cap, aptr, aheads, astride, *rest[6:]))
+        elif (wl, wr) != (-1, -1):
             _check(_lib.fa_ex_forward_window(*ptrs, bh, g, *rest[:5], wl, wr, *rest[5:]))
         elif g > 1:
             _check(_lib.fa_ex_forward_grouped(*ptrs, bh, g, *rest))
@@ -392,17 +455,20 @@ def ex_forward(q, k, v, causal, softmax_scale, mask=None, block_mask=None, br=12
 
 
 def ex_backward(q, k, v, o, do_, lse, causal, softmax_scale, mask=None, block_mask=None, br=128, bc=128, dropout_p=0.0, seed=0,
-                window=(-1, -1)):
+                window=(-1, -1), softcap=0.0, alibi_slopes=None):
     wl, wr = window_arg("ex_backward", window)
+    cap = softcap_arg("ex_backward", softcap)
     q, k, v, o, do_, lse = (t.contiguous() for t in (q, k, v, o, do_, lse))
     bh, nq, nk, d, code, mask, mptr, mstride, block_mask, bptr, g = _ex_common("ex_backward", q, k, v, mask, block_mask, br, bc)
+    aptr, aheads, astride, alibi_slopes = alibi_arg("ex_backward", alibi_slopes, q.device, bh)
+    mod = cap > 0.0 or aptr != 0
     if o.shape != q.shape or do_.shape != q.shape or lse.shape != (bh, nq) or lse.dtype != torch.float32:
         raise RuntimeError("ex_backward: o, do must be (BH, Nq, d) and lse (BH, Nq) float32")
     with torch.cuda.device(q.device):
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        extras = int(mask is not None or block_mask is not None or dropout_p > 0.0 or
-                     window_effective(nq, nk, bool(causal), (wl, wr)))   # (the dS hand-over does not serve a window)
-        if g > 1 or (wl, wr) != (-1, -1):   # (+ the per-query-head dK / dV partials the library sums over each group)
+        extras = int(mask is not None or block_mask is not None or dropout_p > 0.0 or mod or
+                     window_effective(nq, nk, bool(causal), (wl, wr)))   # (the dS hand-over serves neither a window nor a modifier)
+        if g > 1 or (wl, wr) != (-1, -1) or mod:   # (+ the per-query-head dK / dV partials the library sums over each group)
             small = int(_lib.fa_ex_backward_workspace_bytes_grouped(bh, g, nq, nk, d, code))
             fast = int(_lib.fa_ex_backward_workspace_bytes_fast_grouped(bh, g, nq, nk, d, code, int(bool(causal)), extras))
         else:
@@ -417,7 +483,9 @@ def ex_backward(q, k, v, o, do_, lse, causal, softmax_scale, mask=None, block_ma
                 dv.data_ptr())
         rest = (nq, nk, d, code, int(bool(causal)), float(softmax_scale), mptr, mstride, bptr, int(br), int(bc), float(dropout_p),
                 int(seed) & (2 ** 64 - 1), ws.data_ptr(), nbytes, _stream_ptr(q.device))
-        if (wl, wr) != (-1, -1):
+        if mod:
+            _check(_lib.fa_ex_backward_scoremod(*ptrs, bh, g, *rest[:5], wl, wr, rest[5], cap, aptr, aheads, astride, *rest[6:]))
+        elif (wl, wr) != (-1, -1):
             _check(_lib.fa_ex_backward_window(*ptrs, bh, g, *rest[:5], wl, wr, *rest[5:]))
         elif g > 1:
             _check(_lib.fa_ex_backward_grouped(*ptrs, bh, g, *rest))
@@ -468,31 +536,40 @@ def _varlen_common(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_s
 
 
 def ex_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, dropout_p=0.0, seed=0,
-                      window=(-1, -1)):
+                      window=(-1, -1), softcap=0.0, alibi_slopes=None):
     """(o, lse) of attention over packed sequences (FlashAttention-2's varlen layout): q (total_q, H_q, d), k and v
     (total_k, H_kv, d) — strided views along the token dim allowed — cu_seqlens_* int32 (batch + 1,) device offsets.  o is
-    (total_q, H_q, d), lse (H_q, total_q) float32.  Never synchronises: cu_seqlens are clamped in the kernels."""
+    (total_q, H_q, d), lse (H_q, total_q) float32.  Never synchronises: cu_seqlens are clamped in the kernels.  softcap and
+    alibi_slopes (float32 (H_q,) or (batch, H_q)) as in ex_forward, per sequence (fa_ex_forward_varlen_scoremod)."""
     who = "ex_varlen_forward"
     wl, wr = window_arg(who, window)
+    cap = softcap_arg(who, softcap)
     cu_q, cu_k, *dims = _varlen_common(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
-    _b, hq, _hkv, total_q, *_ = dims
+    b, hq, _hkv, total_q, *_ = dims
     d = q.shape[2]
+    aptr, _h, astride, alibi_slopes = alibi_arg(who, alibi_slopes, q.device, b * hq, heads=hq)
     with torch.cuda.device(q.device):
         o = torch.empty((total_q, hq, d), dtype=q.dtype, device=q.device)
         lse = torch.empty((hq, total_q), dtype=torch.float32, device=q.device)
-        _check(_lib.fa_ex_forward_varlen(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), cu_q.data_ptr(),
-                                         cu_k.data_ptr(), *dims, int(bool(causal)), wl, wr, float(softmax_scale), float(dropout_p),
-                                         int(seed) & (2 ** 64 - 1), _stream_ptr(q.device)))
+        ptrs = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr())
+        tail = (float(dropout_p), int(seed) & (2 ** 64 - 1), _stream_ptr(q.device))
+        if cap > 0.0 or aptr:
+            _check(_lib.fa_ex_forward_varlen_scoremod(*ptrs, *dims, int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, astride,
+                                                      *tail))
+        else:
+            _check(_lib.fa_ex_forward_varlen(*ptrs, *dims, int(bool(causal)), wl, wr, float(softmax_scale), *tail))
     return o, lse
 
 
 def ex_varlen_backward(q, k, v, o, do_, lse, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale,
-                       dropout_p=0.0, seed=0, window=(-1, -1)):
+                       dropout_p=0.0, seed=0, window=(-1, -1), softcap=0.0, alibi_slopes=None):
     """(dq, dk, dv) of ex_varlen_forward: dq in q's (total_q, H_q, d) shape, dk and dv in k's and v's (dense)."""
     who = "ex_varlen_backward"
     wl, wr = window_arg(who, window)
+    cap = softcap_arg(who, softcap)
     cu_q, cu_k, *dims = _varlen_common(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
-    _b, hq, hkv, total_q, total_k, _mq, _mk, d, code = dims[:9]
+    b, hq, hkv, total_q, total_k, _mq, _mk, d, code = dims[:9]
+    aptr, _h, astride, alibi_slopes = alibi_arg(who, alibi_slopes, q.device, b * hq, heads=hq)
     for name, t in (("o", o), ("do", do_)):
         if not t.is_cuda or t.shape != (total_q, hq, d) or t.dtype != q.dtype:
             raise RuntimeError(f"{who}: {name} must be a (total_q, H_q, d) device tensor of q's dtype")
@@ -506,8 +583,12 @@ def ex_varlen_backward(q, k, v, o, do_, lse, cu_seqlens_q, cu_seqlens_k, max_seq
         nbytes = int(_lib.fa_ex_backward_workspace_bytes_varlen(hq, hkv, total_q, total_k, d, code))
         ws = _workspace(q.device, nbytes)
         nbytes = max(nbytes, 0 if torch.cuda.is_current_stream_capturing() else _workspaces.capacity(q.device, _stream_ptr(q.device)))
-        _check(_lib.fa_ex_backward_varlen(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do_.data_ptr(), lse.data_ptr(),
-                                          dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr(), *dims,
-                                          int(bool(causal)), wl, wr, float(softmax_scale), float(dropout_p), int(seed) & (2 ** 64 - 1),
-                                          ws.data_ptr(), nbytes, _stream_ptr(q.device)))
+        ptrs = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do_.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+                dv.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr())
+        tail = (float(dropout_p), int(seed) & (2 ** 64 - 1), ws.data_ptr(), nbytes, _stream_ptr(q.device))
+        if cap > 0.0 or aptr:
+            _check(_lib.fa_ex_backward_varlen_scoremod(*ptrs, *dims, int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, astride,
+                                                       *tail))
+        else:
+            _check(_lib.fa_ex_backward_varlen(*ptrs, *dims, int(bool(causal)), wl, wr, float(softmax_scale), *tail))
     return dq, dk, dv

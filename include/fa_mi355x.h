@@ -245,6 +245,57 @@ int fa_ex_backward_varlen(const void* q, const void* k, const void* v, const voi
 
 size_t fa_ex_backward_workspace_bytes_varlen(int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t d, int dtype);
 
+/* --- Score modifiers: FlashAttention-2's softcap and alibi_slopes.  With s = softmax_scale * q_i . k_j and coff = Nk - Nq (per
+ * sequence in the varlen calls), the score that enters the softmax is
+ *     s'  = softcap * tanh(s / softcap)               if softcap > 0, else s
+ *     s'' = s' - slope(u) * |i + coff - j|            if alibi_slopes != NULL
+ * and lse is the logsumexp of s'' over the visible keys (causal, window, masks and row / key ranges as in fa_ex_*_window and
+ * fa_ex_*_varlen).  Query unit u takes slope alibi_slopes[(u / alibi_heads) * alibi_batch_stride + u % alibi_heads]: stride 0 is
+ * FlashAttention-2's (H,) form, stride alibi_heads its (B, H) form; alibi_heads = bh with stride 0 gives one slope per unit.  The
+ * varlen calls use alibi_heads = heads_q (u = b * heads_q + h, slope alibi_slopes[b * alibi_batch_stride + h]).  The slopes are
+ * float32 device memory, read by the kernels only (no synchronise), and receive no gradient; the softcap is differentiated
+ * (ds'/ds = 1 - tanh^2(s / softcap)).  Dropout, the dead-row and dead-key conventions and the GQA indexing are unchanged.
+ * Checked before any HIP call (FA_ERR_INVALID_ARGUMENT): softcap finite and >= 0, alibi_batch_stride >= 0, and with slopes
+ * alibi_heads >= 1 dividing bh.  softcap = 0 without slopes is exactly the fa_ex_*_window / fa_ex_*_varlen call.  A call with a
+ * modifier runs on the extended kernels only (16-bit MFMA where fa_ex_* would take them, exact f32 otherwise).  Workspaces are
+ * those of the calls without modifiers; the dS hand-over does not serve them — pass extras = 1 to
+ * fa_ex_backward_workspace_bytes_fast_grouped. */
+int fa_ex_forward_scoremod(const void* q, const void* k, const void* v, void* o, float* lse,
+                           int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype,
+                           int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                           double softcap, const float* alibi_slopes, int64_t alibi_heads, int64_t alibi_batch_stride,
+                           const uint8_t* mask, int64_t mask_bh_stride,
+                           const uint8_t* block_mask, int64_t br, int64_t bc,
+                           double dropout_p, uint64_t dropout_seed, void* stream);
+
+int fa_ex_backward_scoremod(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse,
+                            void* dq, void* dk, void* dv,
+                            int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype,
+                            int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                            double softcap, const float* alibi_slopes, int64_t alibi_heads, int64_t alibi_batch_stride,
+                            const uint8_t* mask, int64_t mask_bh_stride,
+                            const uint8_t* block_mask, int64_t br, int64_t bc,
+                            double dropout_p, uint64_t dropout_seed,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
+int fa_ex_forward_varlen_scoremod(const void* q, const void* k, const void* v, void* o, float* lse,
+                                  const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q,
+                                  int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k,
+                                  int64_t d, int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride, int causal,
+                                  int64_t window_left, int64_t window_right, double softmax_scale,
+                                  double softcap, const float* alibi_slopes, int64_t alibi_batch_stride,
+                                  double dropout_p, uint64_t dropout_seed, void* stream);
+
+int fa_ex_backward_varlen_scoremod(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse,
+                                   void* dq, void* dk, void* dv,
+                                   const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q,
+                                   int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k,
+                                   int64_t d, int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride, int causal,
+                                   int64_t window_left, int64_t window_right, double softmax_scale,
+                                   double softcap, const float* alibi_slopes, int64_t alibi_batch_stride,
+                                   double dropout_p, uint64_t dropout_seed,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* --- support entry points (no reference counterpart: the reference allocates inside the callee) --- */
 /* bytes for the CURRENT kernel mode: two float row constants per query row (+ an fp32 dQ scratch of bh*n*d floats in
  * FA_MODE_BWD_ATOMIC only); ask again after changing the mode */

@@ -26,6 +26,13 @@ sequence.  Forward and backward, visible-pair TFLOP/s (4 / 10 x visible pairs x 
 
     python tools/bench_ex.py --varlen 4096x8 [--causal] [--q-heads 32] [--head-dim 128] [--rounds 3]
     python tools/bench_ex.py --varlen mix:16:256:8192 --causal --q-heads 32 --kv-heads 8 [--seed 0]
+
+Score modifiers (--softcap C and / or --alibi: the standard slopes 2^(-8 (h + 1) / H), shape (H,)): B x H query heads, N = --nq
+(square), timed alternately in one process — the modified call (fa_ex_*_scoremod), the same call without modifiers on the same
+kernel family (ex_path 3: the extended MFMA kernels), and without modifiers as the library routes it (ex_path 0: the plain
+kernels for a square call) — forward and backward.
+
+    python tools/bench_ex.py --softcap 30 --alibi [--causal] [--batch 8] [--q-heads 32] [--nq 4096] [--head-dim 128] [--rounds 3]
 """
 import argparse
 import json
@@ -66,7 +73,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=3, help="(--window) alternations of the three calls")
     ap.add_argument("--varlen", default="", help="NxB or mix:COUNT:LO:HI: time packed sequences")
     ap.add_argument("--seed", type=int, default=0, help="(--varlen mix) the lengths' seed")
+    ap.add_argument("--softcap", type=float, default=0.0, help="time the softcap (and --alibi) against the call without")
+    ap.add_argument("--alibi", action="store_true", help="time ALiBi slopes (and --softcap) against the call without")
     args = ap.parse_args()
+    if args.softcap > 0.0 or args.alibi:
+        return bench_scoremod(args)
     if args.varlen:
         return bench_varlen(args)
     if args.kv_heads:
@@ -314,6 +325,48 @@ def bench_varlen(args):
                          fwd_ms_all=[round(x, 3) for x in times[name][0]], bwd_ms_all=[round(x, 3) for x in times[name][1]]))
     print(json.dumps(dict(shape=dict(lens=lens, total=total, q_heads=hq, kv_heads=hkv, d=d, dtype=args.dtype, causal=causal,
                                      visible_pairs=pairs, iters=args.iters, rounds=args.rounds), rows=rows), indent=1))
+
+
+def bench_scoremod(args):
+    dt = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[args.dtype]
+    b, h, n, d, causal = args.batch, args.q_heads, args.nq, args.head_dim, args.causal
+    bh, scale = b * h, args.head_dim ** -0.5
+    g = torch.Generator(device="cuda").manual_seed(0)
+    q, k, v, do = (torch.randn((bh, n, d), device="cuda", dtype=dt, generator=g) for _ in range(4))
+    slopes = None
+    if args.alibi:   # (H,) as a (B, H) view: one slope per head, shared by the batch
+        slopes = torch.tensor([2.0 ** (-8.0 * (i + 1) / h) for i in range(h)], dtype=torch.float32, device="cuda")
+        slopes = slopes.unsqueeze(0).expand(b, h)
+    mod = dict(softcap=args.softcap, alibi_slopes=slopes)
+    pairs = bh * (n * (n + 1) // 2 if causal else n * n)
+    o, lse = ext.ex_forward(q, k, v, causal, scale, **mod)
+    o0, lse0 = ext.ex_forward(q, k, v, causal, scale)
+    calls = {   # name: (ex_path, forward, backward)
+        "scoremod": (0, lambda: ext.ex_forward(q, k, v, causal, scale, **mod),
+                     lambda: ext.ex_backward(q, k, v, o, do, lse, causal, scale, **mod)),
+        "none_ex_mfma": (3, lambda: ext.ex_forward(q, k, v, causal, scale),
+                         lambda: ext.ex_backward(q, k, v, o0, do, lse0, causal, scale)),
+        "none_auto": (0, lambda: ext.ex_forward(q, k, v, causal, scale),
+                      lambda: ext.ex_backward(q, k, v, o0, do, lse0, causal, scale)),
+    }
+    times = {name: ([], []) for name in calls}
+    try:
+        for _ in range(args.rounds):
+            for name, (path, f, bw) in calls.items():
+                ext.set_option("ex_path", path)
+                times[name][0].append(timed(f, args.iters))
+                times[name][1].append(timed(bw, args.iters))
+    finally:
+        ext.set_option("ex_path", 0)
+    med = {name: (sorted(t[0])[len(t[0]) // 2], sorted(t[1])[len(t[1]) // 2]) for name, t in times.items()}
+    rows = []
+    for name, (tf, tb) in med.items():
+        rows.append(dict(call=name, fwd_ms=round(tf, 3), bwd_ms=round(tb, 3), fwd_bwd_ms=round(tf + tb, 3),
+                         fwd_tflops=round(4 * pairs * d / tf / 1e9, 1), bwd_tflops=round(10 * pairs * d / tb / 1e9, 1),
+                         fwd_vs_ex=round(tf / med["none_ex_mfma"][0], 3), bwd_vs_ex=round(tb / med["none_ex_mfma"][1], 3),
+                         fwd_ms_all=[round(x, 3) for x in times[name][0]], bwd_ms_all=[round(x, 3) for x in times[name][1]]))
+    print(json.dumps(dict(shape=dict(batch=b, q_heads=h, n=n, d=d, dtype=args.dtype, causal=causal, softcap=args.softcap,
+                                     alibi=args.alibi, iters=args.iters, rounds=args.rounds), rows=rows)))
 
 
 if __name__ == "__main__":
