@@ -185,3 +185,30 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
     if isinstance(alibi_slopes, torch.Tensor):
         alibi_slopes = alibi_slopes.detach()
     return _FlashAttnVarlenFn.apply(*args, softcap, alibi_slopes)
+
+
+def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_sin=None, cache_seqlens=None,
+                            cache_batch_idx=None, cache_leftpad=None, block_table=None, softmax_scale=None, causal=False,
+                            window_size=(-1, -1), softcap=0.0, rotary_interleaved=True, alibi_slopes=None, num_splits=0,
+                            return_softmax_lse=False):
+    """FlashAttention-2's flash_attn_with_kvcache (forward; its argument order): q (B, Nq, H_q, d); k_cache, v_cache
+    (B, cache_len, H_kv, d) with H_q % H_kv == 0, updated in place — k, v (B, N_new, H_kv, d) are written at
+    cache_seqlens[b] .. + N_new before attention, and a cache view the library cannot take without a copy raises ValueError.
+    cache_seqlens: int32 (B,) device lengths, or an int; None means every sequence fills the cache (no k, v then).  Queries
+    attend over keys [0, cache_seqlens[b] + N_new) with causal bottom-right aligned, window_size, softcap and alibi_slopes
+    (float32 (H_q,) or (B, H_q)) as in flash_attention_ex.  num_splits = 0 lets the library split the keys over workgroups.
+    Returns o (B, Nq, H_q, d), and with return_softmax_lse also lse (B, H_q, Nq) float32.  No gradient.  Not supported:
+    rotary embedding, cache_batch_idx, cache_leftpad, block_table (a paged cache)."""
+    for name, val in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin), ("cache_batch_idx", cache_batch_idx),
+                      ("cache_leftpad", cache_leftpad), ("block_table", block_table)):
+        if val is not None:
+            raise NotImplementedError(f"flash_attn_with_kvcache: {name} is not supported")
+    import flashattention_lab_cuda as ext
+
+    if isinstance(alibi_slopes, torch.Tensor):
+        alibi_slopes = alibi_slopes.detach()
+    with torch.no_grad():
+        o, lse = ext.ex_kvcache_forward(q.detach(), k_cache, v_cache, None if k is None else k.detach(),
+                                        None if v is None else v.detach(), cache_seqlens, bool(causal), softmax_scale,
+                                        _window_size(window_size), softcap, alibi_slopes, num_splits)
+    return (o, lse) if return_softmax_lse else o

@@ -739,6 +739,110 @@ int fa_ex_backward_varlen_scoremod(const void* q, const void* k, const void* v, 
                                 stream, sm);
 }
 
+// ---- KV-cache decoding with split-KV: see include/fa_mi355x.h
+static int64_t kv_splits(int64_t batch, int64_t hq, int64_t hkv, int64_t nq, int64_t cache_len, int64_t num_splits) {
+    if (num_splits > 0) return num_splits;
+    return fa::kv_num_splits(batch, hkv, ((hq / hkv) * nq + 15) / 16, cache_len);
+}
+
+size_t fa_ex_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t d,
+                                     int64_t num_splits) {
+    if (batch <= 0 || heads_q <= 0 || heads_kv <= 0 || heads_q % heads_kv != 0 || seqlen_q <= 0 || d <= 0 || cache_len < 0 ||
+        num_splits < 0 || num_splits > 256)
+        return 0;
+    return fa::kv_workspace_bytes(batch, heads_q, seqlen_q, d, (int)kv_splits(batch, heads_q, heads_kv, seqlen_q, cache_len, num_splits));
+}
+
+int fa_ex_forward_kvcache(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new, const int32_t* cache_seqlens,
+                          void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_new,
+                          int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride, int64_t q_token_stride,
+                          int64_t k_cache_batch_stride, int64_t k_cache_token_stride, int64_t v_cache_batch_stride,
+                          int64_t v_cache_token_stride, int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t v_new_batch_stride,
+                          int64_t v_new_token_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                          double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    const char* who = "fa_ex_forward_kvcache";
+    if (dtype != FA_DTYPE_F16 && dtype != FA_DTYPE_BF16)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: dtype must be f16 or bf16 (got code %d)", who, dtype);
+    if (d < 8 || d > 256 || d % 8 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: head_dim must be a multiple of 8 in [8, 256] (got %lld)", who, (long long)d);
+    if (batch < 1 || batch > 65535) return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch must lie in [1, 65535] (got %lld)", who, (long long)batch);
+    if (heads_kv < 1 || heads_q < 1 || heads_q % heads_kv != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads_q=%lld must be a positive multiple of heads_kv=%lld", who, (long long)heads_q,
+                    (long long)heads_kv);
+    if (seqlen_q < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_q must be >= 1 (got %lld)", who, (long long)seqlen_q);
+    if (cache_len < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_len must be >= 1 (got %lld)", who, (long long)cache_len);
+    if (seqlen_new < 0 || seqlen_new > cache_len)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_new=%lld must lie in [0, cache_len=%lld]", who, (long long)seqlen_new,
+                    (long long)cache_len);
+    // strides: the heads of a token adjacent at stride d, tokens at >= heads * d, batch elements past the last token's heads
+    struct { const char* name; int64_t bs, ts, n, heads; } st[5] = {
+        {"q", q_batch_stride, q_token_stride, seqlen_q, heads_q},
+        {"k_cache", k_cache_batch_stride, k_cache_token_stride, cache_len, heads_kv},
+        {"v_cache", v_cache_batch_stride, v_cache_token_stride, cache_len, heads_kv},
+        {"k_new", k_new_batch_stride, k_new_token_stride, seqlen_new, heads_kv},
+        {"v_new", v_new_batch_stride, v_new_token_stride, seqlen_new, heads_kv}};
+    for (int i = 0; i < (seqlen_new > 0 ? 5 : 3); ++i) {
+        const int64_t span = (st[i].n - 1) * st[i].ts + st[i].heads * d;   // elements of one batch element
+        if (st[i].ts < st[i].heads * d || (batch > 1 && st[i].bs < span) || st[i].bs < 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of %s too small (batch %lld, token %lld; need token >= %lld, batch >= %lld)",
+                        who, st[i].name, (long long)st[i].bs, (long long)st[i].ts, (long long)(st[i].heads * d), (long long)span);
+        if (st[i].ts % 8 != 0 || st[i].bs % 8 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of %s must be multiples of 8 elements", who, st[i].name);
+        if (span * 2 >= ((int64_t)1 << 31))
+            return fail(FA_ERR_UNSUPPORTED, "%s: one batch element of %s spans %lld bytes, beyond 32-bit offsets", who, st[i].name,
+                        (long long)(span * 2));
+    }
+    if (seqlen_new > 0 && (!cache_seqlens || !k_new || !v_new))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_new > 0 needs cache_seqlens, k_new and v_new", who);
+    if (window_left < -1 || window_right < -1)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: window (%lld, %lld): each bound must be >= 0, or -1 for unbounded", who,
+                    (long long)window_left, (long long)window_right);
+    if (!(softmax_scale == softmax_scale) || softmax_scale - softmax_scale != 0.0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale must be finite (got %g)", who, softmax_scale);
+    if (!scale_ok(softmax_scale))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale must be > 0 (got %g)", who, softmax_scale);
+    if (!(softcap >= 0.0) || softcap > 1.7976931348623157e308)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: softcap must be a finite number >= 0 (got %g)", who, softcap);
+    if (alibi_batch_stride < 0 || alibi_batch_stride >= ((int64_t)1 << 31) / batch)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: alibi_batch_stride must be >= 0 and batch * stride < 2^31 (got %lld)", who,
+                    (long long)alibi_batch_stride);
+    if (num_splits < 0 || num_splits > 256)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_splits must lie in [0, 256] (got %lld)", who, (long long)num_splits);
+    if (cache_len > ((int64_t)1 << 28) || seqlen_q > ((int64_t)1 << 24) || heads_q > 65535 ||
+        ((heads_q / heads_kv) * seqlen_q + 15) / 16 * heads_kv > 65535)
+        return fail(FA_ERR_UNSUPPORTED, "%s: problem too large for one launch", who);
+    const int64_t S = kv_splits(batch, heads_q, heads_kv, seqlen_q, cache_len, num_splits);
+    if (S > 1 && batch * heads_q * seqlen_q >= ((int64_t)1 << 26))   // the combine: one wave per row, 2^32 lanes per launch
+        return fail(FA_ERR_UNSUPPORTED, "%s: batch * heads_q * seqlen_q = %lld rows are too many to combine %lld splits in one launch",
+                    who, (long long)(batch * heads_q * seqlen_q), (long long)S);
+    // Canonical window: a bound that cuts no key in any row is -1 (len_k <= cache_len: key 0 is in every row's band once
+    // window_left >= cache_len - 1, key len_k - 1 once window_right >= seqlen_q - 1), so the bounds the kernels take in int
+    // stay below 2^28 and the band arithmetic cannot overflow.
+    if (window_left >= cache_len - 1) window_left = -1;
+    if (window_right >= seqlen_q - 1) window_right = -1;
+    const size_t need = fa::kv_workspace_bytes(batch, heads_q, seqlen_q, d, (int)S);
+    if (workspace_bytes < need || (need > 0 && !workspace))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
+    if (!q || !k_cache || !v_cache || !o || !lse) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    if (!aligned16({q, k_cache, v_cache, o, workspace}) || (seqlen_new > 0 && !aligned16({k_new, v_new})))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: tensors must be 16-byte aligned", who);
+    fa::KvArgs a{};
+    a.q = q; a.k_cache = k_cache; a.v_cache = v_cache; a.k_new = k_new; a.v_new = v_new; a.o = o; a.lse = lse;
+    a.cache_seqlens = cache_seqlens;
+    a.batch = batch; a.heads_q = heads_q; a.heads_kv = heads_kv; a.seqlen_q = seqlen_q; a.seqlen_new = seqlen_new;
+    a.cache_len = cache_len; a.d = d; a.dtype = dtype; a.causal = causal ? 1 : 0;
+    a.q_bs = q_batch_stride; a.q_ts = q_token_stride; a.kc_bs = k_cache_batch_stride; a.kc_ts = k_cache_token_stride;
+    a.vc_bs = v_cache_batch_stride; a.vc_ts = v_cache_token_stride; a.kn_bs = k_new_batch_stride; a.kn_ts = k_new_token_stride;
+    a.vn_bs = v_new_batch_stride; a.vn_ts = v_new_token_stride;
+    a.window_left = window_left; a.window_right = window_right;
+    a.scale = (float)softmax_scale; a.softcap = softcap; a.alibi = alibi_slopes; a.alibi_bstride = alibi_batch_stride;
+    a.num_splits = S; a.workspace = workspace;
+    hipError_t e = fa::launch_kvcache(a, reinterpret_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
+    return FA_OK;
+}
+
 size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {
     return ex_bwd_ws_grouped(bh, kv_group, nq, nk, d, dtype);
 }

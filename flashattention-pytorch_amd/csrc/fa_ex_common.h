@@ -60,6 +60,18 @@ __device__ __forceinline__ float ex_slope(const ExScore& sc, int bh) {
     return sc.alibi ? sc.alibi[(bh / sc.al_heads) * sc.al_bstride + bh % sc.al_heads] : 0.f;
 }
 
+// Score modifiers on a raw score S of the 16-bit kernels (fa_ex_mfma.hip FEAT bit 4, fa_decode.hip) (ExScore): the softcap as
+//   S~ = cap_a t,  t = tanh(S / (scale softcap)) = 1 - 2 r,  r = 1 / (2^(cap_k S) + 1)
+// (two transcendentals; safe at both ends: 2^x = inf gives r = 0, t = 1; 2^x = 0 gives r = 1, t = -1), and its derivative
+// dt = 1 - t^2 = 4 r (1 - r) for the backward.  The forward and both backward kernels evaluate S~ with these same fp32 operations,
+// so P in the backward is the P of the forward's lse.
+__device__ __forceinline__ float mod_softcap(float s, const ExScore& sc, float& dt) {
+    const float r = __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(s * sc.cap_k) + 1.f);
+    dt = r * fmaf(r, -4.f, 4.f);
+    return fmaf(r, -2.f * sc.cap_a, sc.cap_a);
+}
+// ALiBi: S~ - al |dist|, al = slope / scale, dist = i + coff - j an exact small integer held as a float
+__device__ __forceinline__ float mod_alibi(float s, float al, float dist) { return fmaf(-al, fabsf(dist), s); }
 // first token and length of sequence b: start = clamp(cu[b], 0, total), end = clamp(cu[b + 1], start, total),
 // len = min(end - start, max_len).  b is uniform over the workgroup: scalar loads.
 __device__ __forceinline__ void seq_span(const int* cu, int b, int total, int max_len, int& start, int& len) {

@@ -218,18 +218,7 @@ __device__ __forceinline__ unsigned keep_bits_q(const ExParams& p, unsigned hi, 
     return bits;
 }
 // Key on the lane: key fixed, rows rrow + rc(i) — registers 4g+0, 4g+1 are one row pair
-// Score modifiers (FEAT bit 4) on a raw score S of the 16-bit kernels (ExScore): the softcap as
-//   S~ = cap_a t,  t = tanh(S / (scale softcap)) = 1 - 2 r,  r = 1 / (2^(cap_k S) + 1)
-// (two transcendentals; safe at both ends: 2^x = inf gives r = 0, t = 1; 2^x = 0 gives r = 1, t = -1), and its derivative
-// dt = 1 - t^2 = 4 r (1 - r) for the backward.  The forward and both backward kernels evaluate S~ with these same fp32 operations,
-// so P in the backward is the P of the forward's lse.
-__device__ __forceinline__ float mod_softcap(float s, const ExScore& sc, float& dt) {
-    const float r = __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(s * sc.cap_k) + 1.f);
-    dt = r * fmaf(r, -4.f, 4.f);
-    return fmaf(r, -2.f * sc.cap_a, sc.cap_a);
-}
-// ALiBi: S~ - al |dist|, al = slope / scale, dist = i + coff - j an exact small integer held as a float
-__device__ __forceinline__ float mod_alibi(float s, float al, float dist) { return fmaf(-al, fabsf(dist), s); }
+// Score modifiers (FEAT bit 4): mod_softcap / mod_alibi (fa_ex_common.h, shared with the decode kernels of fa_decode.hip)
 // the modifiers of a kFeatScore instantiation's ExParamsS (a call dependent on FEAT: the bodies the plain entries include name it
 // only in discarded `if constexpr (SC)` branches)
 template <int FEAT, typename P> __device__ __forceinline__ const ExScore& sc_of(const P& p) { return p.sc; }

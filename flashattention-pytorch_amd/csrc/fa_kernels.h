@@ -169,6 +169,30 @@ inline size_t kv_partial_bytes(int64_t bh, int64_t nk, int64_t d, int dtype) {
     return (((size_t)bh * nk * d * (dtype == 0 ? 4 : 2) + 255) & ~(size_t)255);
 }
 
+// KV-cache decoding with split-KV (fa_decode.hip; fa_ex_forward_kvcache).  16-bit tensors, d % 8 == 0 up to 256, strides
+// multiples of 8 elements, 16-byte aligned tensors, a batch element's cache span below 2^31 bytes (fa_capi.hip checks all of it).
+struct KvArgs {
+    const void* q;                 // (batch, seqlen_q, heads_q, d): batch stride q_bs, token stride q_ts, heads at stride d
+    void *k_cache, *v_cache;       // (batch, cache_len, heads_kv, d): kc_bs / kc_ts, vc_bs / vc_ts
+    const void *k_new, *v_new;     // (batch, seqlen_new, heads_kv, d): kn_bs / kn_ts, vn_bs / vn_ts; appended at L_b
+    void* o;                       // (batch, seqlen_q, heads_q, d) dense
+    float* lse;                    // (batch, heads_q, seqlen_q)
+    const int* cache_seqlens;      // (batch,) untrusted device lengths, null: L_b = cache_len
+    int64_t batch, heads_q, heads_kv, seqlen_q, seqlen_new, cache_len, d;
+    int dtype, causal;
+    int64_t q_bs, q_ts, kc_bs, kc_ts, vc_bs, vc_ts, kn_bs, kn_ts, vn_bs, vn_ts;
+    int64_t window_left, window_right;   // -1 = unbounded
+    float scale;
+    double softcap;
+    const float* alibi;            // slope of (b, h): alibi[b * alibi_bstride + h]; null = none
+    int64_t alibi_bstride;
+    int64_t num_splits;            // >= 1 (the C layer resolves 0 through kv_num_splits)
+    void* workspace;               // kv_workspace_bytes
+};
+int kv_num_splits(int64_t batch, int64_t heads_kv, int64_t row_tiles, int64_t cache_len);
+size_t kv_workspace_bytes(int64_t batch, int64_t heads_q, int64_t seqlen_q, int64_t d, int splits);
+hipError_t launch_kvcache(const KvArgs& a, hipStream_t st);
+
 // Grouped-query attention (fa_kv_group.hip): dk[u] = sum over m = 0 .. g-1 of pk[u g + m] (and dv from pv), accumulated in fp32 in
 // that order and rounded once to the tensor dtype; units of nk * d elements, bh / g of them in dk and dv.
 hipError_t launch_kv_group_sum(const void* pk, const void* pv, void* dk, void* dv, int64_t bh_kv, int64_t g, int64_t nk, int64_t d,

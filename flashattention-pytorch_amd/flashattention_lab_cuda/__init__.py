@@ -42,6 +42,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_ex_backward_workspace_bytes_fast_grouped", "fa_ex_forward_window", "fa_ex_backward_window",
     "fa_ex_forward_varlen", "fa_ex_backward_varlen", "fa_ex_backward_workspace_bytes_varlen",
     "fa_ex_forward_scoremod", "fa_ex_backward_scoremod", "fa_ex_forward_varlen_scoremod", "fa_ex_backward_varlen_scoremod",
+    "fa_ex_forward_kvcache", "fa_ex_kvcache_workspace_bytes",
 )
 
 
@@ -136,6 +137,13 @@ def _load_library() -> ctypes.CDLL:
     lib.fa_ex_forward_varlen_scoremod.restype = ci
     lib.fa_ex_backward_varlen_scoremod.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp] + varlen_sm + [vp, sz, vp]
     lib.fa_ex_backward_varlen_scoremod.restype = ci
+    # KV-cache decoding: q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse; batch, heads_q, heads_kv, seqlen_q, seqlen_new,
+    # cache_len, d, dtype; (batch, token) strides of q, k_cache, v_cache, k_new, v_new; causal, window, scale, softcap, alibi,
+    # alibi_batch_stride, num_splits, workspace, workspace_bytes, stream
+    lib.fa_ex_forward_kvcache.argtypes = [vp] * 8 + [i64] * 7 + [ci] + [i64] * 10 + [ci, i64, i64, dbl, dbl, vp, i64, i64, vp, sz, vp]
+    lib.fa_ex_forward_kvcache.restype = ci
+    lib.fa_ex_kvcache_workspace_bytes.argtypes = [i64] * 7
+    lib.fa_ex_kvcache_workspace_bytes.restype = sz
     return lib
 
 
@@ -592,3 +600,85 @@ def ex_varlen_backward(q, k, v, o, do_, lse, cu_seqlens_q, cu_seqlens_k, max_seq
         else:
             _check(_lib.fa_ex_backward_varlen(*ptrs, *dims, int(bool(causal)), wl, wr, float(softmax_scale), *tail))
     return dq, dk, dv
+
+
+# ---- KV-cache decoding with split-KV (include/fa_mi355x.h: fa_ex_forward_kvcache) ----
+
+def _kv_strides(who, name, t, heads, d, cache):
+    """(batch stride, token stride) of a (B, N, heads, d) tensor whose heads are adjacent at stride d, last dim contiguous."""
+    if t.stride(3) != 1 or (heads > 1 and t.stride(2) != d):
+        if cache:   # a copy would silently lose the in-place append
+            raise ValueError(f"{who}: {name} must have a contiguous last dim and its heads at stride d = {d} "
+                             f"(got strides {tuple(t.stride())}); the cache is never copied")
+        raise RuntimeError(f"{who}: {name} has an unsupported layout")
+    b, n = t.shape[0], t.shape[1]
+    ts = t.stride(1) if n > 1 else max(t.stride(1), heads * d)
+    bs = t.stride(0) if b > 1 else max(t.stride(0), (n - 1) * ts + heads * d)
+    return bs, ts
+
+
+def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlens=None, causal=False, softmax_scale=None,
+                       window=(-1, -1), softcap=0.0, alibi_slopes=None, num_splits=0):
+    """(o, lse) of a decode step over a KV cache (FlashAttention-2's flash_attn_with_kvcache, forward): q (B, Nq, H_q, d);
+    k_cache, v_cache (B, cache_len, H_kv, d), used in place (strided views such as kv.unbind(2) allowed, never copied);
+    k_new, v_new (B, N_new, H_kv, d) are written into the caches at cache_seqlens[b] first; cache_seqlens int32 (B,) on the
+    device, or an int.  o (B, Nq, H_q, d) in q's dtype, lse (B, H_q, Nq) float32.  See fa_ex_forward_kvcache."""
+    who = "ex_kvcache_forward"
+    wl, wr = window_arg(who, window)
+    cap = softcap_arg(who, softcap)
+    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{who}: {name} must be a GPU (HIP device) tensor; there is no CPU path")
+        if t.device != q.device:
+            raise RuntimeError(f"{who}: {name} must be on q's device ({q.device}), got {t.device}")
+        if t.dim() != 4:
+            raise RuntimeError(f"{who}: {name} must be 4-D (B, N, H, d), got {tuple(t.shape)}")
+    if q.dtype not in (torch.float16, torch.bfloat16) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+        raise RuntimeError(f"{who}: q, k_cache, v_cache must share a 16-bit dtype (float16 or bfloat16), got {q.dtype}, "
+                           f"{k_cache.dtype}, {v_cache.dtype}")
+    b, nq, hq, d = q.shape
+    cap_len, hkv = k_cache.shape[1], k_cache.shape[2]
+    if k_cache.shape != (b, cap_len, hkv, d) or v_cache.shape != k_cache.shape:
+        raise RuntimeError(f"{who}: k_cache and v_cache must be (B, cache_len, H_kv, d) = ({b}, ., ., {d}); got "
+                           f"{tuple(k_cache.shape)}, {tuple(v_cache.shape)}")
+    if d % 8 != 0 or not 8 <= d <= 256:
+        raise RuntimeError(f"{who}: head dim must be a multiple of 8 in [8, 256], got {d}")
+    if hkv == 0 or hq % hkv != 0:
+        raise RuntimeError(f"{who}: the query heads ({hq}) must be a multiple of the K/V heads ({hkv})")
+    if (k_new is None) != (v_new is None):
+        raise RuntimeError(f"{who}: k and v must be given together")
+    kvb, kvt = _kv_strides(who, "k_cache", k_cache, hkv, d, True)
+    vvb, vvt = _kv_strides(who, "v_cache", v_cache, hkv, d, True)
+    nnew = 0
+    knb = knt = vnb = vnt = 0
+    if k_new is not None:
+        for name, t in (("k", k_new), ("v", v_new)):
+            if not isinstance(t, torch.Tensor) or t.device != q.device or t.dtype != q.dtype or t.dim() != 4 or \
+                    t.shape[0] != b or t.shape[2:] != (hkv, d) or t.shape != k_new.shape:
+                raise RuntimeError(f"{who}: {name} must be a (B, N_new, H_kv, d) tensor of q's dtype and device")
+        nnew = k_new.shape[1]
+        k_new, v_new = k_new.contiguous(), v_new.contiguous()
+        knb, knt = _kv_strides(who, "k", k_new, hkv, d, False)
+        vnb, vnt = _kv_strides(who, "v", v_new, hkv, d, False)
+    q = q.contiguous()
+    qb, qt = _kv_strides(who, "q", q, hq, d, False)
+    scale = d ** -0.5 if softmax_scale is None else float(softmax_scale)
+    aptr, _h, astride, alibi_slopes = alibi_arg(who, alibi_slopes, q.device, b * hq, heads=hq)
+    with torch.cuda.device(q.device):
+        if cache_seqlens is not None and not isinstance(cache_seqlens, torch.Tensor):
+            cache_seqlens = torch.full((b,), operator.index(cache_seqlens), dtype=torch.int32, device=q.device)
+        if cache_seqlens is not None:
+            if cache_seqlens.device != q.device or cache_seqlens.dtype != torch.int32 or cache_seqlens.shape != (b,):
+                raise RuntimeError(f"{who}: cache_seqlens must be an int32 ({b},) tensor on q's device, or an int")
+            cache_seqlens = cache_seqlens.contiguous()
+        o = torch.empty((b, nq, hq, d), dtype=q.dtype, device=q.device)
+        lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)
+        nbytes = int(_lib.fa_ex_kvcache_workspace_bytes(b, hq, hkv, nq, cap_len, d, int(num_splits)))
+        ws = _workspace(q.device, nbytes) if nbytes > 0 else None
+        _check(_lib.fa_ex_forward_kvcache(
+            q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_new.data_ptr() if k_new is not None else 0,
+            v_new.data_ptr() if v_new is not None else 0, cache_seqlens.data_ptr() if cache_seqlens is not None else 0,
+            o.data_ptr(), lse.data_ptr(), b, hq, hkv, nq, nnew, cap_len, d, _DTYPE_CODE[q.dtype], qb, qt, kvb, kvt, vvb, vvt,
+            knb, knt, vnb, vnt, int(bool(causal)), wl, wr, scale, cap, aptr, astride, int(num_splits),
+            ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device)))
+    return o, lse

@@ -296,6 +296,47 @@ int fa_ex_backward_varlen_scoremod(const void* q, const void* k, const void* v, 
                                    double dropout_p, uint64_t dropout_seed,
                                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* --- KV-cache decoding with split-KV: FlashAttention-2's flash_attn_with_kvcache, forward only, no paged cache, no rotary.
+ * Layouts are batch first, tokens second; within a token the heads are adjacent at stride d; each tensor has its own batch and
+ * token stride (elements), so views such as kv.unbind(2) of a (B, cache_len, 2, H_kv, d) buffer go in without a copy:
+ *     q (batch, seqlen_q, heads_q, d);  k_cache, v_cache (batch, cache_len, heads_kv, d);  k_new, v_new (batch, seqlen_new, heads_kv, d);
+ *     o (batch, seqlen_q, heads_q, d) dense, q's dtype;  lse (batch, heads_q, seqlen_q) float32 dense.
+ * For batch element b, L_b = clamp(cache_seqlens[b], 0, cache_len - seqlen_new) (cache_seqlens: int32 (batch,) device memory, not read
+ * on the host and not trusted; NULL: L_b = cache_len, and seqlen_new must be 0).  k_new / v_new are first written in place into
+ * k_cache[b, L_b : L_b + seqlen_new] and v_cache[...]; nothing else in the caches changes.  Then queries attend over keys
+ * [0, len_k), len_k = L_b + seqlen_new, under the fa_ex_*_window / fa_ex_*_scoremod rules with coff = len_k - seqlen_q: causal is
+ * bottom-right aligned, the window bounds key j to [i + coff - window_left, i + coff + window_right] (-1 = unbounded), softcap and
+ * ALiBi (slope of (b, h): alibi_slopes[b * alibi_batch_stride + h], float32; stride 0 = the (H_q,) form) with distance
+ * |i + coff - j|, query head h reads K/V head h / (heads_q / heads_kv).  A row without a visible key gives o = 0, lse = -inf.
+ * Kernels (csrc/fa_decode.hip): an append launch when seqlen_new > 0; one wave per (split, 16-row tile of the heads_q / heads_kv *
+ * seqlen_q query rows that share a K/V head, K/V head, b) reads its share of the cache once; with num_splits S > 1 a combine launch
+ * merges the fp32 partials in split order (deterministic).  Split s takes 32-key tiles [floor(s nt / S), floor((s + 1) nt / S)) of
+ * the tile's visible band, cut from its first key; the band and nt follow len_k on the device.  num_splits = 0 takes the library's
+ * rule, which reads shapes only (batch, heads_kv, row tiles, cache_len and the MI355X's 256 CUs), so the call never synchronises or
+ * allocates and can be captured in a graph.  The workspace (fa_ex_kvcache_workspace_bytes with the same num_splits; 0 bytes for
+ * S = 1) holds batch * heads_q * seqlen_q * S rows of d floats, then as many floats of lse, each part rounded up to 256 bytes.
+ * Checked before any HIP call (FA_ERR_INVALID_ARGUMENT): dtype f16 or bf16; d a multiple of 8 in [8, 256]; batch in [1, 65535];
+ * heads_q a positive multiple of heads_kv; seqlen_q >= 1; cache_len >= 1; seqlen_new in [0, cache_len]; token strides >= heads * d,
+ * batch strides (batch > 1) >= (tokens - 1) * token stride + heads * d, all strides multiples of 8 (k_new / v_new only when
+ * seqlen_new > 0); seqlen_new > 0 with cache_seqlens, k_new and v_new; window bounds >= -1; a finite softmax_scale > 0; softcap
+ * finite and >= 0; alibi_batch_stride >= 0; num_splits in [0, 256]; the workspace; non-null q, caches, o, lse; 16-byte aligned
+ * tensors.  FA_ERR_UNSUPPORTED: a batch element of any tensor spanning 2^31 bytes or more (batch offsets are 64-bit, so the
+ * caches as a whole may be larger), cache_len > 2^28, seqlen_q > 2^24, and with S > 1 batch * heads_q * seqlen_q >= 2^26 (the
+ * combine launch).  The window is canonicalised first: window_left >= cache_len - 1 and window_right >= seqlen_q - 1 cut no key
+ * in any row and are taken as -1, so any bound up to INT64_MAX means unbounded. */
+int fa_ex_forward_kvcache(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new, const int32_t* cache_seqlens,
+                          void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_new,
+                          int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride, int64_t q_token_stride,
+                          int64_t k_cache_batch_stride, int64_t k_cache_token_stride, int64_t v_cache_batch_stride,
+                          int64_t v_cache_token_stride, int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t v_new_batch_stride,
+                          int64_t v_new_token_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                          double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
+/* bytes of workspace a fa_ex_forward_kvcache call with these shapes and num_splits needs (0 for S = 1 and for invalid shapes) */
+size_t fa_ex_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t d,
+                                     int64_t num_splits);
+
 /* --- support entry points (no reference counterpart: the reference allocates inside the callee) --- */
 /* bytes for the CURRENT kernel mode: two float row constants per query row (+ an fp32 dQ scratch of bh*n*d floats in
  * FA_MODE_BWD_ATOMIC only); ask again after changing the mode */

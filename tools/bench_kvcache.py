@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""Time a KV-cache decode step (flashattention_lab_cuda.ex_kvcache_forward) against the same decode through ex_forward.
+
+    python tools/bench_kvcache.py [--d 128] [--dtype bf16] [--nq 1] [--json out.json]
+
+Rows: B in {1, 8, 32}, H_q = 32, H_kv in {8, 32}, cache length in {1k, 8k, 32k, 128k}, plus one mixed-length batch.  The
+largest row (B = 32, 128k keys, H_kv = 32) holds 68 GB of cache and as much again in ex_forward's layout; --max-tokens drops
+rows with B * len above it on smaller devices.  Each row reports the median time per call of
+  kv      : the new path without append (cache_seqlens = len),
+  kv_app  : the new path appending one token (cache_seqlens = len - 1),
+  ex      : ex_forward with GQA on (B * H_q, 1, d) q and (B * H_kv, len, d) K/V (the layout it needs, copied once outside the timing),
+and the effective bandwidth of kv: bytes of K and V read (sum over b of len_b * H_kv * d * 2 * 2) / time, against 6.3 TB/s.
+Timing: HIP events around `--iters` back-to-back calls after `--warmup` calls; the median of `--reps` such groups."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "flashattention-pytorch_amd"))
+import flashattention_lab_cuda as ext  # noqa: E402
+
+COPY_RATE = 6.3e12
+
+
+def timed(fn, warmup, iters, reps):
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b) / iters * 1e3)   # us
+    return statistics.median(out)
+
+
+def row(b, hq, hkv, lens, d, dtype, args):
+    cap = max(lens)
+    dev = "cuda"
+    q = torch.randn((b, args.nq, hq, d), device=dev, dtype=dtype)
+    kc = torch.randn((b, cap, hkv, d), device=dev, dtype=dtype)   # (generated in the 16-bit dtype: B = 32 x 128k x 32 heads is 34 GB)
+    vc = torch.randn((b, cap, hkv, d), device=dev, dtype=dtype)
+    kn = torch.randn((b, 1, hkv, d), device=dev, dtype=dtype)
+    vn = torch.randn((b, 1, hkv, d), device=dev, dtype=dtype)
+    sl = torch.tensor(lens, dtype=torch.int32, device=dev)
+    sl1 = sl - 1
+    t_kv = timed(lambda: ext.ex_kvcache_forward(q, kc, vc, None, None, sl, True, None), args.warmup, args.iters, args.reps)
+    t_app = timed(lambda: ext.ex_kvcache_forward(q, kc, vc, kn, vn, sl1, True, None), args.warmup, args.iters, args.reps)
+    t_ex = None
+    if len(set(lens)) == 1:
+        q3 = q.permute(0, 2, 1, 3).reshape(b * hq, args.nq, d).contiguous()
+        k3 = kc.permute(0, 2, 1, 3).reshape(b * hkv, cap, d).contiguous()
+        v3 = vc.permute(0, 2, 1, 3).reshape(b * hkv, cap, d).contiguous()
+        t_ex = timed(lambda: ext.ex_forward(q3, k3, v3, True, d ** -0.5), args.warmup, args.iters, args.reps)
+        del q3, k3, v3
+    kv_bytes = sum(lens) * hkv * d * 2 * 2
+    r = dict(B=b, Hq=hq, Hkv=hkv, len=lens[0] if len(set(lens)) == 1 else "mixed", lens=None if len(set(lens)) == 1 else lens,
+             kv_us=round(t_kv, 2), kv_append_us=round(t_app, 2), ex_forward_us=None if t_ex is None else round(t_ex, 2),
+             speedup=None if t_ex is None else round(t_ex / t_kv, 2), kv_TBps=round(kv_bytes / t_kv / 1e6, 3),
+             frac_copy_rate=round(kv_bytes / t_kv / 1e6 / (COPY_RATE / 1e12), 3))
+    del q, kc, vc, kn, vn
+    torch.cuda.empty_cache()
+    return r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--d", type=int, default=128)
+    ap.add_argument("--dtype", default="bf16", choices=("bf16", "fp16"))
+    ap.add_argument("--nq", type=int, default=1)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--max-tokens", type=int, default=1 << 22, help="skip rows with B * len above this")
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16
+    # bring the clocks up before the first row (a second of large decode steps)
+    wq = torch.randn((8, 1, 32, args.d), device="cuda", dtype=dtype)
+    wk = torch.randn((8, 32768, 8, args.d), device="cuda", dtype=dtype)
+    wl = torch.full((8,), 32768, dtype=torch.int32, device="cuda")
+    for _ in range(2000):
+        ext.ex_kvcache_forward(wq, wk, wk, None, None, wl, True, None)
+    torch.cuda.synchronize()
+    del wq, wk
+    rows = []
+    for b in (1, 8, 32):
+        for hkv in (8, 32):
+            for L in (1024, 8192, 32768, 131072):
+                if b * L > args.max_tokens:
+                    continue
+                rows.append(row(b, 32, hkv, [L] * b, args.d, dtype, args))
+                print(json.dumps(rows[-1]), flush=True)
+    g = torch.Generator().manual_seed(0)
+    mixed = [int(x) for x in torch.randint(64, 32768, (8,), generator=g)]
+    rows.append(row(8, 32, 8, mixed, args.d, dtype, args))
+    print(json.dumps(rows[-1]), flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(dict(d=args.d, dtype=args.dtype, nq=args.nq, copy_rate_TBps=COPY_RATE / 1e12, rows=rows), f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
