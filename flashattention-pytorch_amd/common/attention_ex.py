@@ -197,10 +197,18 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     cache_seqlens: int32 (B,) device lengths, or an int; None means every sequence fills the cache (no k, v then).  Queries
     attend over keys [0, cache_seqlens[b] + N_new) with causal bottom-right aligned, window_size, softcap and alibi_slopes
     (float32 (H_q,) or (B, H_q)) as in flash_attention_ex.  num_splits = 0 lets the library split the keys over workgroups.
+    block_table: int32 (B, max_blocks_per_seq) on the device — k_cache, v_cache are then pools (num_blocks, page_block_size,
+    H_kv, d), page_block_size a multiple of 16, and token t of sequence b lives at pool[block_table[b, t // ps], t % ps]; a page
+    number outside the pool reads as zeros and drops the append.  cache_batch_idx: int32 (B,), sequence b uses cache row
+    idx[b] (the cache's batch dim may differ from B).  cache_leftpad: int32 (B,), the keys of sequence b start at cache position
+    leftpad[b] while cache_seqlens keeps counting from 0.  The last two combine; neither goes with block_table.
     Returns o (B, Nq, H_q, d), and with return_softmax_lse also lse (B, H_q, Nq) float32.  No gradient.  Not supported:
-    rotary embedding, cache_batch_idx, cache_leftpad, block_table (a paged cache)."""
-    for name, val in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin), ("cache_batch_idx", cache_batch_idx),
-                      ("cache_leftpad", cache_leftpad), ("block_table", block_table)):
+    rotary embedding."""
+    for name, val in (("block_table", block_table), ("cache_batch_idx", cache_batch_idx), ("cache_leftpad", cache_leftpad)):
+        if val is not None and not (isinstance(val, torch.Tensor) and val.dtype == torch.int32):
+            dt = val.dtype if isinstance(val, torch.Tensor) else type(val).__name__
+            raise NotImplementedError(f"flash_attn_with_kvcache: {name} of dtype {dt} is not supported (int32 tensor expected)")
+    for name, val in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
         if val is not None:
             raise NotImplementedError(f"flash_attn_with_kvcache: {name} is not supported")
     import flashattention_lab_cuda as ext
@@ -210,5 +218,6 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     with torch.no_grad():
         o, lse = ext.ex_kvcache_forward(q.detach(), k_cache, v_cache, None if k is None else k.detach(),
                                         None if v is None else v.detach(), cache_seqlens, bool(causal), softmax_scale,
-                                        _window_size(window_size), softcap, alibi_slopes, num_splits)
+                                        _window_size(window_size), softcap, alibi_slopes, num_splits, block_table, cache_batch_idx,
+                                        cache_leftpad)
     return (o, lse) if return_softmax_lse else o

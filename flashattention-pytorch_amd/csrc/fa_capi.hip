@@ -753,15 +753,17 @@ size_t fa_ex_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t hea
     return fa::kv_workspace_bytes(batch, heads_q, seqlen_q, d, (int)kv_splits(batch, heads_q, heads_kv, seqlen_q, cache_len, num_splits));
 }
 
-int fa_ex_forward_kvcache(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new, const int32_t* cache_seqlens,
-                          void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_new,
-                          int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride, int64_t q_token_stride,
-                          int64_t k_cache_batch_stride, int64_t k_cache_token_stride, int64_t v_cache_batch_stride,
-                          int64_t v_cache_token_stride, int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t v_new_batch_stride,
-                          int64_t v_new_token_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
-                          double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, void* workspace,
-                          size_t workspace_bytes, void* stream) {
-    const char* who = "fa_ex_forward_kvcache";
+// who: the entry point's name.  The last eight arguments are fa_ex_forward_kvcache_paged's; all null / 0 is fa_ex_forward_kvcache.
+static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                        const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                        int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
+                        int64_t q_token_stride, int64_t k_cache_batch_stride, int64_t k_cache_token_stride, int64_t v_cache_batch_stride,
+                        int64_t v_cache_token_stride, int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t v_new_batch_stride,
+                        int64_t v_new_token_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                        double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, void* workspace,
+                        size_t workspace_bytes, void* stream, const int32_t* block_table, int64_t block_table_row_stride,
+                        int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq, const int32_t* cache_batch_idx,
+                        int64_t cache_batch, const int32_t* cache_leftpad) {
     if (dtype != FA_DTYPE_F16 && dtype != FA_DTYPE_BF16)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: dtype must be f16 or bf16 (got code %d)", who, dtype);
     if (d < 8 || d > 256 || d % 8 != 0)
@@ -771,20 +773,56 @@ int fa_ex_forward_kvcache(const void* q, void* k_cache, void* v_cache, const voi
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads_q=%lld must be a positive multiple of heads_kv=%lld", who, (long long)heads_q,
                     (long long)heads_kv);
     if (seqlen_q < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_q must be >= 1 (got %lld)", who, (long long)seqlen_q);
+    // the paged cache and the two per-sequence cache selectors
+    if (block_table) {
+        if (cache_batch_idx || cache_leftpad)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: block_table cannot be combined with cache_batch_idx or cache_leftpad", who);
+        if (page_block_size < 16 || page_block_size % 16 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: page_block_size must be a positive multiple of 16 (got %lld)", who,
+                        (long long)page_block_size);
+        if (num_blocks < 1 || num_blocks > 0x7fffffff)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_blocks must lie in [1, 2^31) (got %lld)", who, (long long)num_blocks);
+        if (max_blocks_per_seq < 1)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: max_blocks_per_seq must be >= 1 (got %lld)", who, (long long)max_blocks_per_seq);
+        if (max_blocks_per_seq > ((int64_t)1 << 28) / page_block_size)
+            return fail(FA_ERR_UNSUPPORTED, "%s: capacity max_blocks_per_seq * page_block_size = %lld * %lld is beyond 2^28 tokens", who,
+                        (long long)max_blocks_per_seq, (long long)page_block_size);
+        if ((uintptr_t)block_table % 4 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: block_table must be 4-byte aligned", who);
+        if (block_table_row_stride < max_blocks_per_seq || block_table_row_stride > ((int64_t)1 << 40))
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: block_table_row_stride=%lld must be >= max_blocks_per_seq=%lld (and <= 2^40)", who,
+                        (long long)block_table_row_stride, (long long)max_blocks_per_seq);
+        cache_len = max_blocks_per_seq * page_block_size;   // the capacity: it stands for cache_len from here on
+    } else if (block_table_row_stride != 0 || num_blocks != 0 || page_block_size != 0 || max_blocks_per_seq != 0) {
+        return fail(FA_ERR_INVALID_ARGUMENT,
+                    "%s: block_table_row_stride, num_blocks, page_block_size and max_blocks_per_seq must be 0 without block_table", who);
+    }
+    if (cache_batch_idx) {
+        if (cache_batch < 1 || cache_batch > 0x7fffffff)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_batch must lie in [1, 2^31) with cache_batch_idx (got %lld)", who,
+                        (long long)cache_batch);
+    } else if (cache_batch != 0) {
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_batch must be 0 without cache_batch_idx (got %lld)", who, (long long)cache_batch);
+    }
+    if ((uintptr_t)cache_batch_idx % 4 != 0 || (uintptr_t)cache_leftpad % 4 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_batch_idx and cache_leftpad must be 4-byte aligned", who);
     if (cache_len < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_len must be >= 1 (got %lld)", who, (long long)cache_len);
     if (seqlen_new < 0 || seqlen_new > cache_len)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_new=%lld must lie in [0, cache_len=%lld]", who, (long long)seqlen_new,
                     (long long)cache_len);
     // strides: the heads of a token adjacent at stride d, tokens at >= heads * d, batch elements past the last token's heads
-    struct { const char* name; int64_t bs, ts, n, heads; } st[5] = {
-        {"q", q_batch_stride, q_token_stride, seqlen_q, heads_q},
-        {"k_cache", k_cache_batch_stride, k_cache_token_stride, cache_len, heads_kv},
-        {"v_cache", v_cache_batch_stride, v_cache_token_stride, cache_len, heads_kv},
-        {"k_new", k_new_batch_stride, k_new_token_stride, seqlen_new, heads_kv},
-        {"v_new", v_new_batch_stride, v_new_token_stride, seqlen_new, heads_kv}};
+    // (a cache's units: its num_blocks pages of page_block_size tokens, its cache_batch rows, or its batch rows)
+    const int64_t c_n = block_table ? page_block_size : cache_len;
+    const int64_t c_units = block_table ? num_blocks : cache_batch_idx ? cache_batch : batch;
+    struct { const char* name; int64_t bs, ts, n, heads, units; } st[5] = {
+        {"q", q_batch_stride, q_token_stride, seqlen_q, heads_q, batch},
+        {"k_cache", k_cache_batch_stride, k_cache_token_stride, c_n, heads_kv, c_units},
+        {"v_cache", v_cache_batch_stride, v_cache_token_stride, c_n, heads_kv, c_units},
+        {"k_new", k_new_batch_stride, k_new_token_stride, seqlen_new, heads_kv, batch},
+        {"v_new", v_new_batch_stride, v_new_token_stride, seqlen_new, heads_kv, batch}};
     for (int i = 0; i < (seqlen_new > 0 ? 5 : 3); ++i) {
-        const int64_t span = (st[i].n - 1) * st[i].ts + st[i].heads * d;   // elements of one batch element
-        if (st[i].ts < st[i].heads * d || (batch > 1 && st[i].bs < span) || st[i].bs < 0)
+        const int64_t span = (st[i].n - 1) * st[i].ts + st[i].heads * d;   // elements of one batch element (or page)
+        if (st[i].ts < st[i].heads * d || (st[i].units > 1 && st[i].bs < span) || st[i].bs < 0)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of %s too small (batch %lld, token %lld; need token >= %lld, batch >= %lld)",
                         who, st[i].name, (long long)st[i].bs, (long long)st[i].ts, (long long)(st[i].heads * d), (long long)span);
         if (st[i].ts % 8 != 0 || st[i].bs % 8 != 0)
@@ -830,6 +868,8 @@ int fa_ex_forward_kvcache(const void* q, void* k_cache, void* v_cache, const voi
     fa::KvArgs a{};
     a.q = q; a.k_cache = k_cache; a.v_cache = v_cache; a.k_new = k_new; a.v_new = v_new; a.o = o; a.lse = lse;
     a.cache_seqlens = cache_seqlens;
+    a.block_table = block_table; a.cache_batch_idx = cache_batch_idx; a.cache_leftpad = cache_leftpad;
+    a.table_row_stride = block_table_row_stride; a.num_blocks = num_blocks; a.page_size = page_block_size; a.cache_batch = cache_batch;
     a.batch = batch; a.heads_q = heads_q; a.heads_kv = heads_kv; a.seqlen_q = seqlen_q; a.seqlen_new = seqlen_new;
     a.cache_len = cache_len; a.d = d; a.dtype = dtype; a.causal = causal ? 1 : 0;
     a.q_bs = q_batch_stride; a.q_ts = q_token_stride; a.kc_bs = k_cache_batch_stride; a.kc_ts = k_cache_token_stride;
@@ -841,6 +881,40 @@ int fa_ex_forward_kvcache(const void* q, void* k_cache, void* v_cache, const voi
     hipError_t e = fa::launch_kvcache(a, reinterpret_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
     return FA_OK;
+}
+
+int fa_ex_forward_kvcache(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new, const int32_t* cache_seqlens,
+                          void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_new,
+                          int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride, int64_t q_token_stride,
+                          int64_t k_cache_batch_stride, int64_t k_cache_token_stride, int64_t v_cache_batch_stride,
+                          int64_t v_cache_token_stride, int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t v_new_batch_stride,
+                          int64_t v_new_token_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                          double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    return kvcache_impl("fa_ex_forward_kvcache", q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, batch, heads_q, heads_kv,
+                        seqlen_q, seqlen_new, cache_len, d, dtype, q_batch_stride, q_token_stride, k_cache_batch_stride,
+                        k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride, k_new_batch_stride, k_new_token_stride,
+                        v_new_batch_stride, v_new_token_stride, causal, window_left, window_right, softmax_scale, softcap, alibi_slopes,
+                        alibi_batch_stride, num_splits, workspace, workspace_bytes, stream, nullptr, 0, 0, 0, 0, nullptr, 0, nullptr);
+}
+
+int fa_ex_forward_kvcache_paged(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                                const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                                int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
+                                int64_t q_token_stride, int64_t k_cache_batch_stride, int64_t k_cache_token_stride,
+                                int64_t v_cache_batch_stride, int64_t v_cache_token_stride, int64_t k_new_batch_stride,
+                                int64_t k_new_token_stride, int64_t v_new_batch_stride, int64_t v_new_token_stride, int causal,
+                                int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
+                                const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, const int32_t* block_table,
+                                int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq,
+                                const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    return kvcache_impl("fa_ex_forward_kvcache_paged", q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, batch, heads_q, heads_kv,
+                        seqlen_q, seqlen_new, cache_len, d, dtype, q_batch_stride, q_token_stride, k_cache_batch_stride,
+                        k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride, k_new_batch_stride, k_new_token_stride,
+                        v_new_batch_stride, v_new_token_stride, causal, window_left, window_right, softmax_scale, softcap, alibi_slopes,
+                        alibi_batch_stride, num_splits, workspace, workspace_bytes, stream, block_table, block_table_row_stride,
+                        num_blocks, page_block_size, max_blocks_per_seq, cache_batch_idx, cache_batch, cache_leftpad);
 }
 
 size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {

@@ -11,7 +11,15 @@
 //   kv_combine_kernel: S > 1 only — one wave per (b, h_q, row) merges the S partials in split order.
 // Split ranges come from len_k on the device (kv_split_range), S from the shapes on the host (fa_capi.hip): the call never
 // synchronises and never allocates, so it can be captured in a graph.  Keys are addressed per 32-key tile from one base per
-// (batch element, K/V head): a page table would replace that base per tile.
+// (batch element, K/V head).  fa_ex_forward_kvcache_paged adds three ways to move that base, all in per-sequence key coordinates, so
+// the split rule, the masks and the combine do not change:
+//   cache_batch_idx : the base is cache row idx[b]; an index outside [0, B_cache) gives an empty buffer range (zeros, no append).
+//   cache_leftpad   : the base moves on by P_b = clamp(leftpad[b], 0, L_b) tokens and len_k = L_b + N_new - P_b.
+//   block_table     : kv_split_kernel<.., true>.  Per tile, lane l looks up the page of key k0 + (l & 31) (one 4-byte read, the next
+//                     tile's issued a tile ahead) and keeps the 64-bit element offsets page * page stride + slot * token stride of K
+//                     and of V; the lane that loads a key row takes its offset by a lane shuffle and reads with a global load at a
+//                     32-bit offset inside the page.  A key past the split's end or on a page outside [0, num_blocks) has offset -1
+//                     and reads as zeros without touching memory.  The contiguous instantiations hold none of this.
 #include "fa_common.h"
 #include "fa_ex_common.h"
 #include "fa_kernels.h"
@@ -40,6 +48,9 @@ struct KvParams {
     uint16_t *o;
     float *lse, *po, *plse;          // po / plse: the partials of S > 1 ((b, h_q, token)-major rows, then split)
     const int* seqlens;              // null: L_b = cache_len (and N_new = 0)
+    const int *table, *bidx, *leftpad;   // block_table (paged), cache_batch_idx, cache_leftpad: untrusted device memory, or null
+    long long tbl_rs;                // table row stride (entries)
+    int nblk, ps, bcache;            // pages in the pools, tokens a page, rows of a contiguous cache (bidx)
     const float* alibi;
     long long q_bs, kc_bs, vc_bs, kn_bs, vn_bs;   // batch strides (elements)
     int q_ts, kc_ts, vc_ts, kn_ts, vn_ts;         // token strides (elements)
@@ -50,10 +61,11 @@ struct KvParams {
     ExScore sc;                                   // cap_k / cap_a (softcap > 0) and al_k, as the extended kernels take them
 };
 
-// L_b (the cache_seqlens clamp) and len_k = L_b + N_new of batch element b
-__device__ __forceinline__ int kv_len_k(const KvParams& p, int b) {
-    const int L = p.seqlens ? min(max(p.seqlens[b], 0), p.cap - p.nnew) : p.cap;
-    return L + p.nnew;
+// L_b (the cache_seqlens clamp), P_b (the cache_leftpad clamp: the sequence's first cache position) and len_k = L_b + N_new - P_b
+__device__ __forceinline__ int kv_len_k(const KvParams& p, int b, int& L, int& P) {
+    L = p.seqlens ? min(max(p.seqlens[b], 0), p.cap - p.nnew) : p.cap;
+    P = p.leftpad ? min(max(p.leftpad[b], 0), L) : 0;
+    return L + p.nnew - P;
 }
 
 // Keys [kbeg, kend) of split s of S for the row tile whose query tokens are [qlo, qhi]: the union of the rows' bands,
@@ -70,27 +82,46 @@ __device__ __forceinline__ void kv_split_range(const KvParams& p, int lk, int ql
     kend = min(hi, lo + t1 * KT);
 }
 
+// Token L_b + n of batch element b goes to cache row (bidx ? bidx[b] : b) at position L_b + n, or through the table to
+// pool[table[b, (L_b + n) / ps], (L_b + n) % ps]; a row or page outside the cache / pool drops the token.
 __global__ __launch_bounds__(256) void kv_append_kernel(KvParams p) {
     const int cpr = p.d / 8;                                      // 16-byte chunks per head row
     const long long per_b = (long long)p.nnew * p.hkv * cpr;
     const int b = blockIdx.y;
-    const int L = kv_len_k(p, b) - p.nnew;
+    int L, P;
+    kv_len_k(p, b, L, P);
+    long long row = b;
+    if (p.bidx) {
+        const int ix = p.bidx[b];
+        if ((unsigned)ix >= (unsigned)p.bcache) return;
+        row = ix;
+    }
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < per_b; t += (long long)gridDim.x * blockDim.x) {
         const int c = (int)(t % cpr);
         const long long r = t / cpr;
         const int h = (int)(r % p.hkv), n = (int)(r / p.hkv);
         const size_t col = (size_t)h * p.d + 8 * c;
+        int pos = L + n;
+        long long unit = row;
+        if (p.table) {
+            const int j = pos / p.ps;
+            const int pg = p.table[b * p.tbl_rs + j];
+            if ((unsigned)pg >= (unsigned)p.nblk) continue;
+            pos -= j * p.ps;
+            unit = pg;
+        }
         const u32x4 kx = *reinterpret_cast<const u32x4*>(p.kn + b * p.kn_bs + (size_t)n * p.kn_ts + col);
         const u32x4 vx = *reinterpret_cast<const u32x4*>(p.vn + b * p.vn_bs + (size_t)n * p.vn_ts + col);
-        *reinterpret_cast<u32x4*>(p.kc + b * p.kc_bs + (size_t)(L + n) * p.kc_ts + col) = kx;
-        *reinterpret_cast<u32x4*>(p.vc + b * p.vc_bs + (size_t)(L + n) * p.vc_ts + col) = vx;
+        *reinterpret_cast<u32x4*>(p.kc + unit * p.kc_bs + (size_t)pos * p.kc_ts + col) = kx;
+        *reinterpret_cast<u32x4*>(p.vc + unit * p.vc_bs + (size_t)pos * p.vc_ts + col) = vx;
     }
 }
 
 // One wave: split blockIdx.x of gridDim.x, row tile blockIdx.y / hkv and K/V head blockIdx.y % hkv, batch element blockIdx.z.
 // Lane l: query row r = l & 15 of the tile (S^T's column, O^T's column), lane group g = l >> 4 (4 keys of each 16-key block
 // of S^T, 4 head-dim elements of each 16-wide block of O^T).  D: the padded tile width (64 | 128 | 256), p.d <= D.
-template <typename Tag, int D>
+// PAGED: keys are reached through p.table (see the head of this file); otherwise through one buffer range per wave.
+template <typename Tag, int D, bool PAGED>
 __global__ __launch_bounds__(64) void kv_split_kernel(KvParams p) {
     constexpr int KT = 32, NKS = D / 32, NDB = D / 16, CPR = D / 8, VLD = KT * CPR / 64;
     __shared__ __attribute__((aligned(16))) char vs[KT * D * 2];   // V tile, [key][D] in the TileSwz<D> image
@@ -98,7 +129,8 @@ __global__ __launch_bounds__(64) void kv_split_kernel(KvParams p) {
     const int s = blockIdx.x, S = gridDim.x;
     const int hk = blockIdx.y % p.hkv, rt = blockIdx.y / p.hkv, b = blockIdx.z;
     const int DR = p.d;
-    const int lk = kv_len_k(p, b), coff = lk - p.nq;
+    int L_b, P_b;
+    const int lk = kv_len_k(p, b, L_b, P_b), coff = lk - p.nq;
     const int pr0 = 16 * rt, pr = pr0 + r;
     const int qlo = pr0 / p.G, qhi = (min(pr0 + 16, p.rows) - 1) / p.G;
     int kbeg, kend;
@@ -119,8 +151,32 @@ __global__ __launch_bounds__(64) void kv_split_kernel(KvParams p) {
         const int col = 32 * ks + 8 * g;
         qf[ks] = buf_load_frag(q_rs, (valid && col < DR) ? (qi * p.q_ts + h * DR + col) * 2 : kOobOff);
     }
-    const buf_rsrc_t k_rs = make_rsrc(p.kc + b * p.kc_bs, (unsigned)(((p.cap - 1) * p.kc_ts + p.hkv * DR) * 2));
-    const buf_rsrc_t v_rs = make_rsrc(p.vc + b * p.vc_bs, (unsigned)(((p.cap - 1) * p.vc_ts + p.hkv * DR) * 2));
+    // contiguous: the sequence's keys start P_b tokens into cache row (bidx ? bidx[b] : b); a row outside the cache is an empty range
+    long long crow = b;
+    int ctok = PAGED ? 0 : p.cap - P_b;   // tokens the buffer range holds
+    if (!PAGED && p.bidx) {
+        const int ix = p.bidx[b];
+        crow = ix;
+        if ((unsigned)ix >= (unsigned)p.bcache) { crow = 0; ctok = 0; }
+    }
+    const buf_rsrc_t k_rs = make_rsrc(p.kc + crow * p.kc_bs + (long long)P_b * p.kc_ts,
+                                      ctok > 0 ? (unsigned)(((ctok - 1) * p.kc_ts + p.hkv * DR) * 2) : 0u);
+    const buf_rsrc_t v_rs = make_rsrc(p.vc + crow * p.vc_bs + (long long)P_b * p.vc_ts,
+                                      ctok > 0 ? (unsigned)(((ctok - 1) * p.vc_ts + p.hkv * DR) * 2) : 0u);
+    // paged: the table row, and the page j0 and slot s0 of the tile's first key (a 32-key tile spans at most three pages)
+    const int* tbl = PAGED ? p.table + b * p.tbl_rs : nullptr;
+    int j0 = 0, s0 = 0, pg = -1;
+    auto page_of = [&](int jt, int st, int kt) {   // the table entry of key kt + (lane & 31), or -1 past the split's end
+        int j = jt, sl = st + (lane & 31);
+        if (sl >= p.ps) { sl -= p.ps; ++j; }
+        if (sl >= p.ps) ++j;
+        return kt + (lane & 31) < kend ? tbl[j] : -1;
+    };
+    if (PAGED && kbeg < kend) {
+        j0 = kbeg / p.ps;
+        s0 = kbeg - j0 * p.ps;
+        pg = page_of(j0, s0, kbeg);
+    }
 
     f32x4_t oacc[NDB];
 #pragma unroll
@@ -132,21 +188,58 @@ __global__ __launch_bounds__(64) void kv_split_kernel(KvParams p) {
         // K fragments (A of S^T = K Q^T: key k0 + 16 kb + r, head dims 32 ks + 8 g ..) and this lane's share of the V tile;
         // keys past the split's end read as zeros (the cache behind them may hold anything)
         s16x8 kf[2][NKS];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            const int key = k0 + 16 * kb + r;
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) {
-                const int col = 32 * ks + 8 * g;
-                kf[kb][ks] = buf_load_frag(k_rs, (key < kend && col < DR) ? (key * p.kc_ts + hk * DR + col) * 2 : kOobOff);
-            }
-        }
         u32x4 vr[VLD];
+        if constexpr (PAGED) {
+            // this lane's key k0 + (lane & 31): element offsets of its token in the two pools, -1 = reads as zeros
+            long long ko = -1, vo = -1;
+            {
+                int sl = s0 + (lane & 31);
+                if (sl >= p.ps) sl -= p.ps;
+                if (sl >= p.ps) sl -= p.ps;
+                if ((unsigned)pg < (unsigned)p.nblk) {
+                    ko = pg * p.kc_bs + (long long)sl * p.kc_ts;
+                    vo = pg * p.vc_bs + (long long)sl * p.vc_ts;
+                }
+            }
+            s0 += KT;
+            if (s0 >= p.ps) { s0 -= p.ps; ++j0; }
+            if (s0 >= p.ps) { s0 -= p.ps; ++j0; }
+            if (k0 + KT < kend) pg = page_of(j0, s0, k0 + KT);   // the next tile's lookup, a tile ahead of its use
 #pragma unroll
-        for (int i = 0; i < VLD; ++i) {
-            const int idx = 64 * i + lane, row = idx / CPR, ch = idx - row * CPR, key = k0 + row;
-            vr[i] = __builtin_amdgcn_raw_buffer_load_b128(v_rs, (key < kend && 8 * ch < DR) ? (key * p.vc_ts + hk * DR + 8 * ch) * 2 : kOobOff,
-                                                          0, 0);
+            for (int kb = 0; kb < 2; ++kb) {
+                const long long ro = __shfl(ko, 16 * kb + r, 64);
+                const uint16_t* kp = p.kc + ro + hk * DR + 8 * g;
+#pragma unroll
+                for (int ks = 0; ks < NKS; ++ks) {
+                    const bool ok = ro >= 0 && 32 * ks + 8 * g < DR;
+                    const s16x8 x = *reinterpret_cast<const s16x8*>(ok ? kp + 32 * ks : p.q);
+                    kf[kb][ks] = ok ? x : s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < VLD; ++i) {
+                const int idx = 64 * i + lane, row = idx / CPR, ch = idx - row * CPR;
+                const long long ro = __shfl(vo, row, 64);
+                const bool ok = ro >= 0 && 8 * ch < DR;
+                const u32x4 x = *reinterpret_cast<const u32x4*>(ok ? p.vc + ro + hk * DR + 8 * ch : p.q);
+                vr[i] = ok ? x : u32x4{0u, 0u, 0u, 0u};
+            }
+        } else {
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) {
+                const int key = k0 + 16 * kb + r;
+#pragma unroll
+                for (int ks = 0; ks < NKS; ++ks) {
+                    const int col = 32 * ks + 8 * g;
+                    kf[kb][ks] = buf_load_frag(k_rs, (key < kend && col < DR) ? (key * p.kc_ts + hk * DR + col) * 2 : kOobOff);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < VLD; ++i) {
+                const int idx = 64 * i + lane, row = idx / CPR, ch = idx - row * CPR, key = k0 + row;
+                vr[i] = __builtin_amdgcn_raw_buffer_load_b128(v_rs, (key < kend && 8 * ch < DR) ? (key * p.vc_ts + hk * DR + 8 * ch) * 2 : kOobOff,
+                                                              0, 0);
+            }
         }
         f32x4_t sacc[2];
 #pragma unroll
@@ -290,7 +383,10 @@ __global__ __launch_bounds__(256) void kv_combine_kernel(KvParams p, int S, long
 
 template <typename Tag, int D>
 hipError_t launch_split(const KvParams& p, int S, int row_tiles, int batch, hipStream_t st) {
-    hipLaunchKernelGGL((kv_split_kernel<Tag, D>), dim3((unsigned)S, (unsigned)(row_tiles * p.hkv), (unsigned)batch), dim3(64), 0, st, p);
+    if (p.table)
+        hipLaunchKernelGGL((kv_split_kernel<Tag, D, true>), dim3((unsigned)S, (unsigned)(row_tiles * p.hkv), (unsigned)batch), dim3(64), 0, st, p);
+    else
+        hipLaunchKernelGGL((kv_split_kernel<Tag, D, false>), dim3((unsigned)S, (unsigned)(row_tiles * p.hkv), (unsigned)batch), dim3(64), 0, st, p);
     return hipGetLastError();
 }
 
@@ -329,6 +425,8 @@ hipError_t launch_kvcache(const KvArgs& a, hipStream_t st) {
     p.kn = (const uint16_t*)a.k_new; p.vn = (const uint16_t*)a.v_new;
     p.o = (uint16_t*)a.o; p.lse = a.lse;
     p.seqlens = a.cache_seqlens;
+    p.table = a.block_table; p.bidx = a.cache_batch_idx; p.leftpad = a.cache_leftpad;
+    p.tbl_rs = a.table_row_stride; p.nblk = (int)a.num_blocks; p.ps = (int)a.page_size; p.bcache = (int)a.cache_batch;
     p.alibi = a.alibi;
     p.q_bs = a.q_bs; p.kc_bs = a.kc_bs; p.vc_bs = a.vc_bs; p.kn_bs = a.kn_bs; p.vn_bs = a.vn_bs;
     p.q_ts = (int)a.q_ts; p.kc_ts = (int)a.kc_ts; p.vc_ts = (int)a.vc_ts; p.kn_ts = (int)a.kn_ts; p.vn_ts = (int)a.vn_ts;

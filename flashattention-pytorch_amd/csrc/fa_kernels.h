@@ -178,6 +178,12 @@ struct KvArgs {
     void* o;                       // (batch, seqlen_q, heads_q, d) dense
     float* lse;                    // (batch, heads_q, seqlen_q)
     const int* cache_seqlens;      // (batch,) untrusted device lengths, null: L_b = cache_len
+    // fa_ex_forward_kvcache_paged (all null / 0: the contiguous call).  With block_table k_cache / v_cache are pools
+    // (num_blocks, page_size, heads_kv, d), kc_bs / vc_bs their page strides and cache_len = max_blocks_per_seq * page_size.
+    const int* block_table;        // (batch, max_blocks_per_seq) untrusted device page numbers, rows at table_row_stride
+    const int* cache_batch_idx;    // (batch,) untrusted device cache rows in [0, cache_batch); contiguous cache only
+    const int* cache_leftpad;      // (batch,) untrusted device first cache positions; contiguous cache only
+    int64_t table_row_stride, num_blocks, page_size, cache_batch;
     int64_t batch, heads_q, heads_kv, seqlen_q, seqlen_new, cache_len, d;
     int dtype, causal;
     int64_t q_bs, q_ts, kc_bs, kc_ts, vc_bs, vc_ts, kn_bs, kn_ts, vn_bs, vn_ts;

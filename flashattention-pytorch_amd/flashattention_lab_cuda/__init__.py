@@ -42,7 +42,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_ex_backward_workspace_bytes_fast_grouped", "fa_ex_forward_window", "fa_ex_backward_window",
     "fa_ex_forward_varlen", "fa_ex_backward_varlen", "fa_ex_backward_workspace_bytes_varlen",
     "fa_ex_forward_scoremod", "fa_ex_backward_scoremod", "fa_ex_forward_varlen_scoremod", "fa_ex_backward_varlen_scoremod",
-    "fa_ex_forward_kvcache", "fa_ex_kvcache_workspace_bytes",
+    "fa_ex_forward_kvcache", "fa_ex_kvcache_workspace_bytes", "fa_ex_forward_kvcache_paged",
 )
 
 
@@ -142,6 +142,9 @@ def _load_library() -> ctypes.CDLL:
     # alibi_batch_stride, num_splits, workspace, workspace_bytes, stream
     lib.fa_ex_forward_kvcache.argtypes = [vp] * 8 + [i64] * 7 + [ci] + [i64] * 10 + [ci, i64, i64, dbl, dbl, vp, i64, i64, vp, sz, vp]
     lib.fa_ex_forward_kvcache.restype = ci
+    lib.fa_ex_forward_kvcache_paged.argtypes = [vp] * 8 + [i64] * 7 + [ci] + [i64] * 10 + [ci, i64, i64, dbl, dbl, vp, i64, i64] + \
+        [vp, i64, i64, i64, i64, vp, i64, vp] + [vp, sz, vp]
+    lib.fa_ex_forward_kvcache_paged.restype = ci
     lib.fa_ex_kvcache_workspace_bytes.argtypes = [i64] * 7
     lib.fa_ex_kvcache_workspace_bytes.restype = sz
     return lib
@@ -618,11 +621,17 @@ def _kv_strides(who, name, t, heads, d, cache):
 
 
 def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlens=None, causal=False, softmax_scale=None,
-                       window=(-1, -1), softcap=0.0, alibi_slopes=None, num_splits=0):
+                       window=(-1, -1), softcap=0.0, alibi_slopes=None, num_splits=0, block_table=None, cache_batch_idx=None,
+                       cache_leftpad=None):
     """(o, lse) of a decode step over a KV cache (FlashAttention-2's flash_attn_with_kvcache, forward): q (B, Nq, H_q, d);
     k_cache, v_cache (B, cache_len, H_kv, d), used in place (strided views such as kv.unbind(2) allowed, never copied);
     k_new, v_new (B, N_new, H_kv, d) are written into the caches at cache_seqlens[b] first; cache_seqlens int32 (B,) on the
-    device, or an int.  o (B, Nq, H_q, d) in q's dtype, lse (B, H_q, Nq) float32.  See fa_ex_forward_kvcache."""
+    device, or an int.  o (B, Nq, H_q, d) in q's dtype, lse (B, H_q, Nq) float32.  See fa_ex_forward_kvcache.
+    block_table int32 (B, max_blocks_per_seq): k_cache, v_cache are pools (num_blocks, page_block_size, H_kv, d) and token t of
+    sequence b lives at pool[block_table[b, t // ps], t % ps]; the capacity is max_blocks_per_seq * ps.  cache_batch_idx int32
+    (B,): sequence b uses cache row idx[b] of a (B_cache, cache_len, H_kv, d) cache.  cache_leftpad int32 (B,): the keys of
+    sequence b start at cache position leftpad[b].  The last two combine; neither goes with block_table.  All on q's device,
+    never read on the host.  See fa_ex_forward_kvcache_paged."""
     who = "ex_kvcache_forward"
     wl, wr = window_arg(who, window)
     cap = softcap_arg(who, softcap)
@@ -638,8 +647,26 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
                            f"{k_cache.dtype}, {v_cache.dtype}")
     b, nq, hq, d = q.shape
     cap_len, hkv = k_cache.shape[1], k_cache.shape[2]
-    if k_cache.shape != (b, cap_len, hkv, d) or v_cache.shape != k_cache.shape:
-        raise RuntimeError(f"{who}: k_cache and v_cache must be (B, cache_len, H_kv, d) = ({b}, ., ., {d}); got "
+    for name, t, shape in (("block_table", block_table, "(B, max_blocks_per_seq)"), ("cache_batch_idx", cache_batch_idx, "(B,)"),
+                           ("cache_leftpad", cache_leftpad, "(B,)")):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != q.device or \
+                t.dim() != (2 if name == "block_table" else 1) or t.shape[0] != b or t.numel() == 0:
+            raise RuntimeError(f"{who}: {name} must be an int32 {shape} tensor on q's device, B = {b}")
+    if block_table is not None and (cache_batch_idx is not None or cache_leftpad is not None):
+        raise RuntimeError(f"{who}: block_table cannot be combined with cache_batch_idx or cache_leftpad")
+    units = b   # leading dim of the caches: pages, cache rows, or batch elements
+    if block_table is not None:
+        units = k_cache.shape[0]
+        if cap_len < 16 or cap_len % 16 != 0:
+            raise RuntimeError(f"{who}: page_block_size (k_cache.shape[1]) must be a positive multiple of 16, got {cap_len}")
+    elif cache_batch_idx is not None:
+        units = k_cache.shape[0]
+    if units == 0 or k_cache.shape != (units, cap_len, hkv, d) or v_cache.shape != k_cache.shape:
+        what = "(num_blocks, page_block_size, H_kv, d)" if block_table is not None else \
+            "(B_cache, cache_len, H_kv, d)" if cache_batch_idx is not None else "(B, cache_len, H_kv, d)"
+        raise RuntimeError(f"{who}: k_cache and v_cache must be {what} = ({units}, ., ., {d}); got "
                            f"{tuple(k_cache.shape)}, {tuple(v_cache.shape)}")
     if d % 8 != 0 or not 8 <= d <= 256:
         raise RuntimeError(f"{who}: head dim must be a multiple of 8 in [8, 256], got {d}")
@@ -673,12 +700,31 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
             cache_seqlens = cache_seqlens.contiguous()
         o = torch.empty((b, nq, hq, d), dtype=q.dtype, device=q.device)
         lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)
-        nbytes = int(_lib.fa_ex_kvcache_workspace_bytes(b, hq, hkv, nq, cap_len, d, int(num_splits)))
-        ws = _workspace(q.device, nbytes) if nbytes > 0 else None
-        _check(_lib.fa_ex_forward_kvcache(
-            q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_new.data_ptr() if k_new is not None else 0,
-            v_new.data_ptr() if v_new is not None else 0, cache_seqlens.data_ptr() if cache_seqlens is not None else 0,
-            o.data_ptr(), lse.data_ptr(), b, hq, hkv, nq, nnew, cap_len, d, _DTYPE_CODE[q.dtype], qb, qt, kvb, kvt, vvb, vvt,
-            knb, knt, vnb, vnt, int(bool(causal)), wl, wr, scale, cap, aptr, astride, int(num_splits),
-            ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device)))
+        head = (q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_new.data_ptr() if k_new is not None else 0,
+                v_new.data_ptr() if v_new is not None else 0, cache_seqlens.data_ptr() if cache_seqlens is not None else 0,
+                o.data_ptr(), lse.data_ptr(), b, hq, hkv, nq, nnew, cap_len, d, _DTYPE_CODE[q.dtype], qb, qt, kvb, kvt, vvb, vvt,
+                knb, knt, vnb, vnt, int(bool(causal)), wl, wr, scale, cap, aptr, astride, int(num_splits))
+        if block_table is None and cache_batch_idx is None and cache_leftpad is None:
+            nbytes = int(_lib.fa_ex_kvcache_workspace_bytes(b, hq, hkv, nq, cap_len, d, int(num_splits)))
+            ws = _workspace(q.device, nbytes) if nbytes > 0 else None
+            _check(_lib.fa_ex_forward_kvcache(*head, ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device)))
+        else:
+            paged = (0, 0, 0, 0, 0)
+            capacity = cap_len
+            if block_table is not None:
+                if block_table.stride(1) != 1:
+                    block_table = block_table.contiguous()
+                paged = (block_table.data_ptr(), block_table.stride(0) if b > 1 else max(block_table.stride(0), block_table.shape[1]),
+                         units, cap_len, block_table.shape[1])
+                capacity = block_table.shape[1] * cap_len
+            if cache_batch_idx is not None:
+                cache_batch_idx = cache_batch_idx.contiguous()
+            if cache_leftpad is not None:
+                cache_leftpad = cache_leftpad.contiguous()
+            nbytes = int(_lib.fa_ex_kvcache_workspace_bytes(b, hq, hkv, nq, capacity, d, int(num_splits)))
+            ws = _workspace(q.device, nbytes) if nbytes > 0 else None
+            _check(_lib.fa_ex_forward_kvcache_paged(
+                *head, *paged, cache_batch_idx.data_ptr() if cache_batch_idx is not None else 0,
+                units if cache_batch_idx is not None else 0, cache_leftpad.data_ptr() if cache_leftpad is not None else 0,
+                ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device)))
     return o, lse

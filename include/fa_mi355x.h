@@ -296,7 +296,8 @@ int fa_ex_backward_varlen_scoremod(const void* q, const void* k, const void* v, 
                                    double dropout_p, uint64_t dropout_seed,
                                    void* workspace, size_t workspace_bytes, void* stream);
 
-/* --- KV-cache decoding with split-KV: FlashAttention-2's flash_attn_with_kvcache, forward only, no paged cache, no rotary.
+/* --- KV-cache decoding with split-KV: FlashAttention-2's flash_attn_with_kvcache, forward only, no rotary (the paged cache, cache_batch_idx
+ * and cache_leftpad: fa_ex_forward_kvcache_paged below).
  * Layouts are batch first, tokens second; within a token the heads are adjacent at stride d; each tensor has its own batch and
  * token stride (elements), so views such as kv.unbind(2) of a (B, cache_len, 2, H_kv, d) buffer go in without a copy:
  *     q (batch, seqlen_q, heads_q, d);  k_cache, v_cache (batch, cache_len, heads_kv, d);  k_new, v_new (batch, seqlen_new, heads_kv, d);
@@ -332,6 +333,50 @@ int fa_ex_forward_kvcache(const void* q, void* k_cache, void* v_cache, const voi
                           int64_t v_new_token_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
                           double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, void* workspace,
                           size_t workspace_bytes, void* stream);
+
+/* fa_ex_forward_kvcache with a paged cache (block_table), continuous batching (cache_batch_idx) and left-padded prompts
+ * (cache_leftpad), as in FlashAttention-2.  All three null with the five integers 0 is fa_ex_forward_kvcache, bit for bit.
+ * Everything not named here keeps its meaning; all three arrays are int32 device memory, never read on the host and not trusted.
+ *
+ * block_table (batch, max_blocks_per_seq), rows at block_table_row_stride entries.  k_cache / v_cache are pools
+ * (num_blocks, page_block_size, heads_kv, d): the two "batch" strides are the page strides, the token strides as before (each pool
+ * its own, so pool.unbind(1) of a (num_blocks, 2, ps, heads_kv, d) buffer goes in without a copy).  With ps = page_block_size, token
+ * t of sequence b lives at pool[block_table[b, t / ps], t % ps], element offset
+ *     block_table[b, t / ps] * page_stride + (t % ps) * token_stride + head * d + i.
+ * cache_len is ignored: the capacity max_blocks_per_seq * ps takes its place everywhere (the cache_seqlens clamp, seqlen_new's
+ * bound, the num_splits = 0 rule, the window canonicalisation; ask fa_ex_kvcache_workspace_bytes with the capacity as cache_len).
+ * k_new / v_new go through the table to tokens L_b .. L_b + seqlen_new - 1.  ps is any positive multiple of 16; page offsets are
+ * 64-bit (a pool may be larger than 4 GiB), offsets inside a page 32-bit.  Only entries j < ceil(len_k / ps) of row b are read.
+ * An entry outside [0, num_blocks) never leads to an access outside the pools: the tokens of that page read as zero K and zero V
+ * (they still take part in the softmax, with score 0), and an append to it is dropped.  Several sequences may name the same page
+ * (prefix sharing) for reading; appending to one page from two sequences in one call is undefined.
+ *
+ * cache_batch_idx (batch,), contiguous cache only: sequence b uses k_cache[idx[b]] / v_cache[idx[b]] of a cache with cache_batch
+ * rows (which may differ from batch); the append lands in that row and no other row changes.  An index outside [0, cache_batch)
+ * reads as zeros and drops the append.  Two sequences with the same index and seqlen_new > 0 are undefined.
+ *
+ * cache_leftpad (batch,), contiguous cache only: with L_b as before (cache_seqlens counts from cache position 0) and
+ * P_b = clamp(cache_leftpad[b], 0, L_b), the keys of sequence b are cache positions [P_b, L_b + seqlen_new): len_k = L_b +
+ * seqlen_new - P_b, and causal alignment, window, ALiBi distance and the split rule use these local coordinates (coff = len_k -
+ * seqlen_q).  k_new / v_new are still written at L_b.  cache_batch_idx and cache_leftpad may be combined.
+ *
+ * Checked before any HIP call, besides fa_ex_forward_kvcache's list (FA_ERR_INVALID_ARGUMENT): block_table together with
+ * cache_batch_idx or cache_leftpad; page_block_size a positive multiple of 16; num_blocks and max_blocks_per_seq >= 1; block_table
+ * 4-byte aligned with block_table_row_stride >= max_blocks_per_seq; the four table integers 0 without block_table; cache_batch >= 1
+ * with cache_batch_idx and 0 without; the cache strides, for a page of ps tokens (num_blocks > 1: page stride >= (ps - 1) * token
+ * stride + heads_kv * d) or for cache_batch rows.  FA_ERR_UNSUPPORTED: a capacity above 2^28 tokens; a page spanning 2^31 bytes
+ * or more. */
+int fa_ex_forward_kvcache_paged(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                                const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                                int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
+                                int64_t q_token_stride, int64_t k_cache_batch_stride, int64_t k_cache_token_stride,
+                                int64_t v_cache_batch_stride, int64_t v_cache_token_stride, int64_t k_new_batch_stride,
+                                int64_t k_new_token_stride, int64_t v_new_batch_stride, int64_t v_new_token_stride, int causal,
+                                int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
+                                const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, const int32_t* block_table,
+                                int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq,
+                                const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad, void* workspace,
+                                size_t workspace_bytes, void* stream);
 
 /* bytes of workspace a fa_ex_forward_kvcache call with these shapes and num_splits needs (0 for S = 1 and for invalid shapes) */
 size_t fa_ex_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t d,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time a KV-cache decode step (flashattention_lab_cuda.ex_kvcache_forward) against the same decode through ex_forward.
 
-    python tools/bench_kvcache.py [--d 128] [--dtype bf16] [--nq 1] [--json out.json]
+    python tools/bench_kvcache.py [--d 128] [--dtype bf16] [--nq 1] [--page-size 16 --page-size 256] [--json out.json]
 
 Rows: B in {1, 8, 32}, H_q = 32, H_kv in {8, 32}, cache length in {1k, 8k, 32k, 128k}, plus one mixed-length batch.  The
 largest row (B = 32, 128k keys, H_kv = 32) holds 68 GB of cache and as much again in ex_forward's layout; --max-tokens drops
@@ -9,6 +9,8 @@ rows with B * len above it on smaller devices.  Each row reports the median time
   kv      : the new path without append (cache_seqlens = len),
   kv_app  : the new path appending one token (cache_seqlens = len - 1),
   ex      : ex_forward with GQA on (B * H_q, 1, d) q and (B * H_kv, len, d) K/V (the layout it needs, copied once outside the timing),
+  paged_<ps> (one per --page-size): the paged call without append over a pool that holds the same tokens, its pages assigned to
+            the sequences in shuffled order (block_table; flashattention_lab_cuda.ex_kvcache_forward(..., block_table=...)),
 and the effective bandwidth of kv: bytes of K and V read (sum over b of len_b * H_kv * d * 2 * 2) / time, against 6.3 TB/s.
 Timing: HIP events around `--iters` back-to-back calls after `--warmup` calls; the median of `--reps` such groups."""
 import argparse
@@ -53,8 +55,26 @@ def row(b, hq, hkv, lens, d, dtype, args):
     sl1 = sl - 1
     t_kv = timed(lambda: ext.ex_kvcache_forward(q, kc, vc, None, None, sl, True, None), args.warmup, args.iters, args.reps)
     t_app = timed(lambda: ext.ex_kvcache_forward(q, kc, vc, kn, vn, sl1, True, None), args.warmup, args.iters, args.reps)
+    paged = {}
+    for ps in args.page_size:
+        mb = (cap + ps - 1) // ps
+        g = torch.Generator(device="cpu").manual_seed(ps)
+        table = torch.randperm(b * mb, generator=g).view(b, mb).to(torch.int32).to(dev)
+        kp = torch.empty((b * mb, ps, hkv, d), device=dev, dtype=dtype)
+        vp = torch.empty((b * mb, ps, hkv, d), device=dev, dtype=dtype)
+        pad = mb * ps - cap
+        for bb in range(b):   # the same tokens, page by page (the tail of a last partial page is never read)
+            rows = table[bb].long()
+            kp[rows] = torch.nn.functional.pad(kc[bb], (0, 0, 0, 0, 0, pad)).view(mb, ps, hkv, d)
+            vp[rows] = torch.nn.functional.pad(vc[bb], (0, 0, 0, 0, 0, pad)).view(mb, ps, hkv, d)
+        o_c = ext.ex_kvcache_forward(q, kc, vc, None, None, sl, True, None)[0]
+        o_p = ext.ex_kvcache_forward(q, kp, vp, None, None, sl, True, None, block_table=table)[0]
+        assert torch.equal(o_c, o_p), "paged and contiguous calls disagree"
+        paged[ps] = timed(lambda: ext.ex_kvcache_forward(q, kp, vp, None, None, sl, True, None, block_table=table),
+                          args.warmup, args.iters, args.reps)
+        del kp, vp, table
     t_ex = None
-    if len(set(lens)) == 1:
+    if len(set(lens)) == 1 and not args.no_ex:
         q3 = q.permute(0, 2, 1, 3).reshape(b * hq, args.nq, d).contiguous()
         k3 = kc.permute(0, 2, 1, 3).reshape(b * hkv, cap, d).contiguous()
         v3 = vc.permute(0, 2, 1, 3).reshape(b * hkv, cap, d).contiguous()
@@ -65,6 +85,10 @@ def row(b, hq, hkv, lens, d, dtype, args):
              kv_us=round(t_kv, 2), kv_append_us=round(t_app, 2), ex_forward_us=None if t_ex is None else round(t_ex, 2),
              speedup=None if t_ex is None else round(t_ex / t_kv, 2), kv_TBps=round(kv_bytes / t_kv / 1e6, 3),
              frac_copy_rate=round(kv_bytes / t_kv / 1e6 / (COPY_RATE / 1e12), 3))
+    for ps, t in paged.items():
+        r[f"paged_{ps}_us"] = round(t, 2)
+        r[f"paged_{ps}_TBps"] = round(kv_bytes / t / 1e6, 3)
+        r[f"paged_{ps}_vs_kv"] = round(t / t_kv, 3)
     del q, kc, vc, kn, vn
     torch.cuda.empty_cache()
     return r
@@ -79,6 +103,8 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--max-tokens", type=int, default=1 << 22, help="skip rows with B * len above this")
+    ap.add_argument("--page-size", type=int, action="append", default=[], help="also time the paged call with this page size (repeatable)")
+    ap.add_argument("--no-ex", action="store_true", help="skip the ex_forward column")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16
@@ -104,7 +130,7 @@ def main():
     print(json.dumps(rows[-1]), flush=True)
     if args.json:
         with open(args.json, "w") as f:
-            json.dump(dict(d=args.d, dtype=args.dtype, nq=args.nq, copy_rate_TBps=COPY_RATE / 1e12, rows=rows), f, indent=1)
+            json.dump(dict(d=args.d, dtype=args.dtype, nq=args.nq, page_sizes=args.page_size, copy_rate_TBps=COPY_RATE / 1e12, rows=rows), f, indent=1)
 
 
 if __name__ == "__main__":
