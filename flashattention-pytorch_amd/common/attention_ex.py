@@ -202,15 +202,20 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     number outside the pool reads as zeros and drops the append.  cache_batch_idx: int32 (B,), sequence b uses cache row
     idx[b] (the cache's batch dim may differ from B).  cache_leftpad: int32 (B,), the keys of sequence b start at cache position
     leftpad[b] while cache_seqlens keeps counting from 0.  The last two combine; neither goes with block_table.
-    Returns o (B, Nq, H_q, d), and with return_softmax_lse also lse (B, H_q, Nq) float32.  No gradient.  Not supported:
-    rotary embedding."""
+    rotary_cos, rotary_sin: (seqlen_ro, rotary_dim / 2) in q's dtype on the device, rotary_dim a multiple of 16 up to d; needs k, v
+    and cache_seqlens.  k is rotated at its position in the sequence (cache_seqlens[b] - leftpad[b] + n) before it is written to
+    the cache; q at the position of its token when causal or a window bound is given, else every q token at the position of
+    the first new token; q itself is not modified.  rotary_interleaved: pairs (2j, 2j + 1), else (j, j + rotary_dim / 2).
+    seqlen_ro must be at least the capacity (cache_len, or max_blocks_per_seq * page_block_size) + max(0, Nq - N_new).
+    Returns o (B, Nq, H_q, d), and with return_softmax_lse also lse (B, H_q, Nq) float32.  No gradient."""
     for name, val in (("block_table", block_table), ("cache_batch_idx", cache_batch_idx), ("cache_leftpad", cache_leftpad)):
         if val is not None and not (isinstance(val, torch.Tensor) and val.dtype == torch.int32):
             dt = val.dtype if isinstance(val, torch.Tensor) else type(val).__name__
             raise NotImplementedError(f"flash_attn_with_kvcache: {name} of dtype {dt} is not supported (int32 tensor expected)")
     for name, val in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
-        if val is not None:
-            raise NotImplementedError(f"flash_attn_with_kvcache: {name} is not supported")
+        if val is not None and not (isinstance(val, torch.Tensor) and val.dtype == q.dtype):
+            dt = val.dtype if isinstance(val, torch.Tensor) else type(val).__name__
+            raise NotImplementedError(f"flash_attn_with_kvcache: {name} of dtype {dt} is not supported (q's dtype expected)")
     import flashattention_lab_cuda as ext
 
     if isinstance(alibi_slopes, torch.Tensor):
@@ -219,5 +224,6 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
         o, lse = ext.ex_kvcache_forward(q.detach(), k_cache, v_cache, None if k is None else k.detach(),
                                         None if v is None else v.detach(), cache_seqlens, bool(causal), softmax_scale,
                                         _window_size(window_size), softcap, alibi_slopes, num_splits, block_table, cache_batch_idx,
-                                        cache_leftpad)
+                                        cache_leftpad, None if rotary_cos is None else rotary_cos.detach(),
+                                        None if rotary_sin is None else rotary_sin.detach(), bool(rotary_interleaved))
     return (o, lse) if return_softmax_lse else o

@@ -753,7 +753,8 @@ size_t fa_ex_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t hea
     return fa::kv_workspace_bytes(batch, heads_q, seqlen_q, d, (int)kv_splits(batch, heads_q, heads_kv, seqlen_q, cache_len, num_splits));
 }
 
-// who: the entry point's name.  The last eight arguments are fa_ex_forward_kvcache_paged's; all null / 0 is fa_ex_forward_kvcache.
+// who: the entry point's name.  After stream come the eight arguments fa_ex_forward_kvcache_paged adds (all null / 0 is
+// fa_ex_forward_kvcache), then the seven fa_ex_forward_kvcache_rotary adds (all null / 0 is fa_ex_forward_kvcache_paged).
 static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
                         const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
                         int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
@@ -763,7 +764,9 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
                         double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, void* workspace,
                         size_t workspace_bytes, void* stream, const int32_t* block_table, int64_t block_table_row_stride,
                         int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq, const int32_t* cache_batch_idx,
-                        int64_t cache_batch, const int32_t* cache_leftpad) {
+                        int64_t cache_batch, const int32_t* cache_leftpad, const void* rotary_cos, const void* rotary_sin,
+                        int64_t rotary_cos_row_stride, int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim,
+                        int rotary_interleaved) {
     if (dtype != FA_DTYPE_F16 && dtype != FA_DTYPE_BF16)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: dtype must be f16 or bf16 (got code %d)", who, dtype);
     if (d < 8 || d > 256 || d % 8 != 0)
@@ -836,6 +839,37 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
     if (window_left < -1 || window_right < -1)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: window (%lld, %lld): each bound must be >= 0, or -1 for unbounded", who,
                     (long long)window_left, (long long)window_right);
+    // rotary embedding: the tables are read on the device without a check, so every position a clamped length can give
+    // (new key n at L_b - P_b + n, q token i at L_b - P_b + i, L_b <= cache_len - seqlen_new) must be a table row
+    if ((rotary_cos != nullptr) != (rotary_sin != nullptr))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary_cos and rotary_sin must be given together", who);
+    if (rotary_cos) {
+        if (rotary_dim < 16 || rotary_dim > d || rotary_dim % 16 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary_dim must be a multiple of 16 in [16, head_dim=%lld] (got %lld)", who,
+                        (long long)d, (long long)rotary_dim);
+        if (seqlen_new < 1 || !cache_seqlens)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary needs seqlen_new > 0 (k_new, v_new) and cache_seqlens", who);
+        const int64_t ro_need = cache_len + (seqlen_q > seqlen_new ? seqlen_q - seqlen_new : 0);
+        if (seqlen_ro < ro_need)
+            return fail(FA_ERR_INVALID_ARGUMENT,
+                        "%s: seqlen_ro=%lld must be >= capacity + max(0, seqlen_q - seqlen_new) = %lld (the tables are not bounds-checked on "
+                        "the device)", who, (long long)seqlen_ro, (long long)ro_need);
+        if (rotary_cos_row_stride < rotary_dim / 2 || rotary_sin_row_stride < rotary_dim / 2 ||
+            rotary_cos_row_stride > ((int64_t)1 << 40) || rotary_sin_row_stride > ((int64_t)1 << 40))
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary row strides (%lld, %lld) must be >= rotary_dim / 2 = %lld (and <= 2^40)", who,
+                        (long long)rotary_cos_row_stride, (long long)rotary_sin_row_stride, (long long)(rotary_dim / 2));
+        if (rotary_cos_row_stride % 2 != 0 || rotary_sin_row_stride % 2 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary row strides (%lld, %lld) must be even", who,
+                        (long long)rotary_cos_row_stride, (long long)rotary_sin_row_stride);
+        if ((uintptr_t)rotary_cos % 4 != 0 || (uintptr_t)rotary_sin % 4 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary_cos and rotary_sin must be 4-byte aligned", who);
+    } else if (rotary_cos_row_stride != 0 || rotary_sin_row_stride != 0 || seqlen_ro != 0 || rotary_dim != 0 || rotary_interleaved != 0) {
+        return fail(FA_ERR_INVALID_ARGUMENT,
+                    "%s: the rotary row strides, seqlen_ro, rotary_dim and rotary_interleaved must be 0 without rotary_cos / rotary_sin", who);
+    }
+    // q token i is rotated at its own position when causal or a window bound was given: decided here, on the arguments as
+    // passed, before the window is canonicalised
+    const int rotary_q_per_token = (causal || window_left >= 0 || window_right >= 0) ? 1 : 0;
     if (!(softmax_scale == softmax_scale) || softmax_scale - softmax_scale != 0.0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale must be finite (got %g)", who, softmax_scale);
     if (!scale_ok(softmax_scale))
@@ -878,6 +912,8 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
     a.window_left = window_left; a.window_right = window_right;
     a.scale = (float)softmax_scale; a.softcap = softcap; a.alibi = alibi_slopes; a.alibi_bstride = alibi_batch_stride;
     a.num_splits = S; a.workspace = workspace;
+    a.rotary_cos = rotary_cos; a.rotary_sin = rotary_sin; a.rotary_cos_rs = rotary_cos_row_stride; a.rotary_sin_rs = rotary_sin_row_stride;
+    a.rotary_dim = rotary_dim; a.rotary_interleaved = rotary_interleaved ? 1 : 0; a.rotary_q_per_token = rotary_cos ? rotary_q_per_token : 0;
     hipError_t e = fa::launch_kvcache(a, reinterpret_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
     return FA_OK;
@@ -895,7 +931,8 @@ int fa_ex_forward_kvcache(const void* q, void* k_cache, void* v_cache, const voi
                         seqlen_q, seqlen_new, cache_len, d, dtype, q_batch_stride, q_token_stride, k_cache_batch_stride,
                         k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride, k_new_batch_stride, k_new_token_stride,
                         v_new_batch_stride, v_new_token_stride, causal, window_left, window_right, softmax_scale, softcap, alibi_slopes,
-                        alibi_batch_stride, num_splits, workspace, workspace_bytes, stream, nullptr, 0, 0, 0, 0, nullptr, 0, nullptr);
+                        alibi_batch_stride, num_splits, workspace, workspace_bytes, stream, nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, nullptr,
+                        nullptr, 0, 0, 0, 0, 0);
 }
 
 int fa_ex_forward_kvcache_paged(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
@@ -914,7 +951,30 @@ int fa_ex_forward_kvcache_paged(const void* q, void* k_cache, void* v_cache, con
                         k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride, k_new_batch_stride, k_new_token_stride,
                         v_new_batch_stride, v_new_token_stride, causal, window_left, window_right, softmax_scale, softcap, alibi_slopes,
                         alibi_batch_stride, num_splits, workspace, workspace_bytes, stream, block_table, block_table_row_stride,
-                        num_blocks, page_block_size, max_blocks_per_seq, cache_batch_idx, cache_batch, cache_leftpad);
+                        num_blocks, page_block_size, max_blocks_per_seq, cache_batch_idx, cache_batch, cache_leftpad, nullptr, nullptr, 0, 0,
+                        0, 0, 0);
+}
+
+int fa_ex_forward_kvcache_rotary(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                                 const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                                 int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
+                                 int64_t q_token_stride, int64_t k_cache_batch_stride, int64_t k_cache_token_stride,
+                                 int64_t v_cache_batch_stride, int64_t v_cache_token_stride, int64_t k_new_batch_stride,
+                                 int64_t k_new_token_stride, int64_t v_new_batch_stride, int64_t v_new_token_stride, int causal,
+                                 int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
+                                 const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, const int32_t* block_table,
+                                 int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq,
+                                 const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad,
+                                 const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride,
+                                 int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    return kvcache_impl("fa_ex_forward_kvcache_rotary", q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, batch, heads_q, heads_kv,
+                        seqlen_q, seqlen_new, cache_len, d, dtype, q_batch_stride, q_token_stride, k_cache_batch_stride,
+                        k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride, k_new_batch_stride, k_new_token_stride,
+                        v_new_batch_stride, v_new_token_stride, causal, window_left, window_right, softmax_scale, softcap, alibi_slopes,
+                        alibi_batch_stride, num_splits, workspace, workspace_bytes, stream, block_table, block_table_row_stride,
+                        num_blocks, page_block_size, max_blocks_per_seq, cache_batch_idx, cache_batch, cache_leftpad, rotary_cos,
+                        rotary_sin, rotary_cos_row_stride, rotary_sin_row_stride, seqlen_ro, rotary_dim, rotary_interleaved);
 }
 
 size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {

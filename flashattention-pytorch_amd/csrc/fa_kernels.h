@@ -194,6 +194,12 @@ struct KvArgs {
     int64_t alibi_bstride;
     int64_t num_splits;            // >= 1 (the C layer resolves 0 through kv_num_splits)
     void* workspace;               // kv_workspace_bytes
+    // fa_ex_forward_kvcache_rotary (null / 0: no rotation).  Tables (seqlen_ro, rotary_dim / 2) in q's dtype, rows at even
+    // strides; seqlen_ro >= cache_len + max(0, seqlen_q - seqlen_new), so the kernels read them unchecked; seqlen_new > 0.
+    const void *rotary_cos, *rotary_sin;
+    int64_t rotary_cos_rs, rotary_sin_rs, rotary_dim;
+    int rotary_interleaved;        // pairs (2j, 2j + 1), else (j, j + rotary_dim / 2)
+    int rotary_q_per_token;        // q token i at position L_b - P_b + i (causal or a window bound given), else all at L_b - P_b
 };
 int kv_num_splits(int64_t batch, int64_t heads_kv, int64_t row_tiles, int64_t cache_len);
 size_t kv_workspace_bytes(int64_t batch, int64_t heads_q, int64_t seqlen_q, int64_t d, int splits);

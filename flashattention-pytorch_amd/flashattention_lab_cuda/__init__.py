@@ -42,7 +42,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_ex_backward_workspace_bytes_fast_grouped", "fa_ex_forward_window", "fa_ex_backward_window",
     "fa_ex_forward_varlen", "fa_ex_backward_varlen", "fa_ex_backward_workspace_bytes_varlen",
     "fa_ex_forward_scoremod", "fa_ex_backward_scoremod", "fa_ex_forward_varlen_scoremod", "fa_ex_backward_varlen_scoremod",
-    "fa_ex_forward_kvcache", "fa_ex_kvcache_workspace_bytes", "fa_ex_forward_kvcache_paged",
+    "fa_ex_forward_kvcache", "fa_ex_kvcache_workspace_bytes", "fa_ex_forward_kvcache_paged", "fa_ex_forward_kvcache_rotary",
 )
 
 
@@ -145,6 +145,10 @@ def _load_library() -> ctypes.CDLL:
     lib.fa_ex_forward_kvcache_paged.argtypes = [vp] * 8 + [i64] * 7 + [ci] + [i64] * 10 + [ci, i64, i64, dbl, dbl, vp, i64, i64] + \
         [vp, i64, i64, i64, i64, vp, i64, vp] + [vp, sz, vp]
     lib.fa_ex_forward_kvcache_paged.restype = ci
+    # ... cache_leftpad; rotary_cos, rotary_sin, their row strides, seqlen_ro, rotary_dim, rotary_interleaved; workspace, ...
+    lib.fa_ex_forward_kvcache_rotary.argtypes = [vp] * 8 + [i64] * 7 + [ci] + [i64] * 10 + [ci, i64, i64, dbl, dbl, vp, i64, i64] + \
+        [vp, i64, i64, i64, i64, vp, i64, vp] + [vp, vp, i64, i64, i64, i64, ci] + [vp, sz, vp]
+    lib.fa_ex_forward_kvcache_rotary.restype = ci
     lib.fa_ex_kvcache_workspace_bytes.argtypes = [i64] * 7
     lib.fa_ex_kvcache_workspace_bytes.restype = sz
     return lib
@@ -622,7 +626,7 @@ def _kv_strides(who, name, t, heads, d, cache):
 
 def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlens=None, causal=False, softmax_scale=None,
                        window=(-1, -1), softcap=0.0, alibi_slopes=None, num_splits=0, block_table=None, cache_batch_idx=None,
-                       cache_leftpad=None):
+                       cache_leftpad=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True):
     """(o, lse) of a decode step over a KV cache (FlashAttention-2's flash_attn_with_kvcache, forward): q (B, Nq, H_q, d);
     k_cache, v_cache (B, cache_len, H_kv, d), used in place (strided views such as kv.unbind(2) allowed, never copied);
     k_new, v_new (B, N_new, H_kv, d) are written into the caches at cache_seqlens[b] first; cache_seqlens int32 (B,) on the
@@ -631,7 +635,12 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
     sequence b lives at pool[block_table[b, t // ps], t % ps]; the capacity is max_blocks_per_seq * ps.  cache_batch_idx int32
     (B,): sequence b uses cache row idx[b] of a (B_cache, cache_len, H_kv, d) cache.  cache_leftpad int32 (B,): the keys of
     sequence b start at cache position leftpad[b].  The last two combine; neither goes with block_table.  All on q's device,
-    never read on the host.  See fa_ex_forward_kvcache_paged."""
+    never read on the host.  See fa_ex_forward_kvcache_paged.
+    rotary_cos, rotary_sin (seqlen_ro, rotary_dim / 2) in q's dtype on q's device, rotary_dim a multiple of 16 in [16, d]: k_new
+    is rotated at its position in the sequence before it is written to the cache, and the kernel's copy of q at the position
+    of its token (causal or a window bound given) or of the first new token (neither); pairs (2j, 2j + 1) with
+    rotary_interleaved, else (j, j + rotary_dim / 2).  Needs k_new, v_new, cache_seqlens and seqlen_ro >= capacity +
+    max(0, Nq - N_new).  See fa_ex_forward_kvcache_rotary."""
     who = "ex_kvcache_forward"
     wl, wr = window_arg(who, window)
     cap = softcap_arg(who, softcap)
@@ -674,6 +683,20 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
         raise RuntimeError(f"{who}: the query heads ({hq}) must be a multiple of the K/V heads ({hkv})")
     if (k_new is None) != (v_new is None):
         raise RuntimeError(f"{who}: k and v must be given together")
+    if (rotary_cos is None) != (rotary_sin is None):
+        raise RuntimeError(f"{who}: rotary_cos and rotary_sin must be given together")
+    rdim = 0
+    if rotary_cos is not None:
+        for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+            if not isinstance(t, torch.Tensor) or t.dtype != q.dtype or t.device != q.device or t.dim() != 2 or \
+                    t.shape != rotary_cos.shape or t.numel() == 0:
+                raise RuntimeError(f"{who}: {name} must be a (seqlen_ro, rotary_dim / 2) tensor of q's dtype on q's device, "
+                                   f"rotary_cos and rotary_sin of one shape")
+        rdim = 2 * rotary_cos.shape[1]
+        if rdim % 16 != 0 or not 16 <= rdim <= d:
+            raise RuntimeError(f"{who}: rotary_dim = 2 * rotary_cos.shape[1] must be a multiple of 16 in [16, d = {d}], got {rdim}")
+        if k_new is None or cache_seqlens is None:
+            raise RuntimeError(f"{who}: rotary_cos / rotary_sin need k, v (the new tokens) and cache_seqlens")
     kvb, kvt = _kv_strides(who, "k_cache", k_cache, hkv, d, True)
     vvb, vvt = _kv_strides(who, "v_cache", v_cache, hkv, d, True)
     nnew = 0
@@ -687,6 +710,12 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
         k_new, v_new = k_new.contiguous(), v_new.contiguous()
         knb, knt = _kv_strides(who, "k", k_new, hkv, d, False)
         vnb, vnt = _kv_strides(who, "v", v_new, hkv, d, False)
+    if rotary_cos is not None:
+        capacity = cap_len * (block_table.shape[1] if block_table is not None else 1)
+        need = capacity + max(0, nq - nnew)   # the library's bound: every position a clamped length can give is a table row
+        if rotary_cos.shape[0] < need:
+            raise RuntimeError(f"{who}: rotary_cos / rotary_sin have {rotary_cos.shape[0]} rows; the capacity {capacity} + "
+                               f"max(0, Nq - N_new) = {need} are needed")
     q = q.contiguous()
     qb, qt = _kv_strides(who, "q", q, hq, d, False)
     scale = d ** -0.5 if softmax_scale is None else float(softmax_scale)
@@ -704,7 +733,7 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
                 v_new.data_ptr() if v_new is not None else 0, cache_seqlens.data_ptr() if cache_seqlens is not None else 0,
                 o.data_ptr(), lse.data_ptr(), b, hq, hkv, nq, nnew, cap_len, d, _DTYPE_CODE[q.dtype], qb, qt, kvb, kvt, vvb, vvt,
                 knb, knt, vnb, vnt, int(bool(causal)), wl, wr, scale, cap, aptr, astride, int(num_splits))
-        if block_table is None and cache_batch_idx is None and cache_leftpad is None:
+        if block_table is None and cache_batch_idx is None and cache_leftpad is None and rotary_cos is None:
             nbytes = int(_lib.fa_ex_kvcache_workspace_bytes(b, hq, hkv, nq, cap_len, d, int(num_splits)))
             ws = _workspace(q.device, nbytes) if nbytes > 0 else None
             _check(_lib.fa_ex_forward_kvcache(*head, ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device)))
@@ -721,10 +750,25 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
                 cache_batch_idx = cache_batch_idx.contiguous()
             if cache_leftpad is not None:
                 cache_leftpad = cache_leftpad.contiguous()
+            middle = (*paged, cache_batch_idx.data_ptr() if cache_batch_idx is not None else 0,
+                      units if cache_batch_idx is not None else 0, cache_leftpad.data_ptr() if cache_leftpad is not None else 0)
+            rotary = None
+            if rotary_cos is not None:
+                tabs = []
+                for t in (rotary_cos, rotary_sin):   # rows at an even stride, 4-byte aligned: otherwise a dense copy
+                    if t.stride(1) != 1 or (t.shape[0] > 1 and (t.stride(0) < t.shape[1] or t.stride(0) % 2)) or t.data_ptr() % 4:
+                        t = t.clone(memory_format=torch.contiguous_format)
+                    tabs.append(t)
+                rotary_cos, rotary_sin = tabs
+                rotary = (rotary_cos.data_ptr(), rotary_sin.data_ptr(),
+                          rotary_cos.stride(0) if rotary_cos.shape[0] > 1 else rotary_cos.shape[1],
+                          rotary_sin.stride(0) if rotary_sin.shape[0] > 1 else rotary_sin.shape[1],
+                          rotary_cos.shape[0], rdim, int(bool(rotary_interleaved)))
             nbytes = int(_lib.fa_ex_kvcache_workspace_bytes(b, hq, hkv, nq, capacity, d, int(num_splits)))
             ws = _workspace(q.device, nbytes) if nbytes > 0 else None
-            _check(_lib.fa_ex_forward_kvcache_paged(
-                *head, *paged, cache_batch_idx.data_ptr() if cache_batch_idx is not None else 0,
-                units if cache_batch_idx is not None else 0, cache_leftpad.data_ptr() if cache_leftpad is not None else 0,
-                ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device)))
+            tail = (ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device))
+            if rotary is None:
+                _check(_lib.fa_ex_forward_kvcache_paged(*head, *middle, *tail))
+            else:
+                _check(_lib.fa_ex_forward_kvcache_rotary(*head, *middle, *rotary, *tail))
     return o, lse

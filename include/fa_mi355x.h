@@ -296,8 +296,8 @@ int fa_ex_backward_varlen_scoremod(const void* q, const void* k, const void* v, 
                                    double dropout_p, uint64_t dropout_seed,
                                    void* workspace, size_t workspace_bytes, void* stream);
 
-/* --- KV-cache decoding with split-KV: FlashAttention-2's flash_attn_with_kvcache, forward only, no rotary (the paged cache, cache_batch_idx
- * and cache_leftpad: fa_ex_forward_kvcache_paged below).
+/* --- KV-cache decoding with split-KV: FlashAttention-2's flash_attn_with_kvcache, forward only (the paged cache, cache_batch_idx
+ * and cache_leftpad: fa_ex_forward_kvcache_paged below; rotary embedding: fa_ex_forward_kvcache_rotary below).
  * Layouts are batch first, tokens second; within a token the heads are adjacent at stride d; each tensor has its own batch and
  * token stride (elements), so views such as kv.unbind(2) of a (B, cache_len, 2, H_kv, d) buffer go in without a copy:
  *     q (batch, seqlen_q, heads_q, d);  k_cache, v_cache (batch, cache_len, heads_kv, d);  k_new, v_new (batch, seqlen_new, heads_kv, d);
@@ -377,6 +377,46 @@ int fa_ex_forward_kvcache_paged(const void* q, void* k_cache, void* v_cache, con
                                 int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq,
                                 const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad, void* workspace,
                                 size_t workspace_bytes, void* stream);
+
+/* fa_ex_forward_kvcache_paged with rotary position embedding fused into the call, as in FlashAttention-2 (rotary_cos, rotary_sin,
+ * rotary_interleaved).  Null tables with the five integers 0 is fa_ex_forward_kvcache_paged, bit for bit.  Everything not named here
+ * keeps its meaning.
+ *
+ * rotary_cos, rotary_sin (seqlen_ro, rotary_dim / 2): device memory in q's dtype, last dim contiguous, rows at
+ * rotary_cos_row_stride / rotary_sin_row_stride elements.  rotary_dim is a multiple of 16 in [16, d]; head-dim elements at and past
+ * it pass through unchanged.  rotary_interleaved != 0: the pairs are elements (2j, 2j + 1) (GPT-J); 0: (j, j + rotary_dim / 2)
+ * (GPT-NeoX).  A pair (x, y) with table entry j at table row `position` becomes
+ *     x' = x cos[position, j] - y sin[position, j],   y' = x sin[position, j] + y cos[position, j],
+ * evaluated in fp32 from the 16-bit inputs and rounded once to the 16-bit dtype.
+ * Positions are the sequence's own key coordinates, the ones causal, window and ALiBi use: with L_b and P_b as above (the clamps
+ * included; P_b = 0 without cache_leftpad), new key token n of sequence b has position L_b - P_b + n.  k_new[b, n] is rotated there
+ * and the rotated value is what the cache receives (contiguous, indexed, left-padded or paged); v_new is appended as it is.  q token
+ * i is rotated at position L_b - P_b + i when causal is set or a window bound is given, and otherwise every q token at L_b - P_b.
+ * "Given" is decided on window_left / window_right as the caller passed them (>= 0), before the canonicalisation described above: a
+ * bound so large that it cuts no key, and is therefore taken as -1 for masking, still selects the per-token positions.  q itself is
+ * not modified; only the kernel's operand is.
+ * The tables are read on the device without a bounds check.  Instead the call requires
+ *     seqlen_ro >= capacity + max(0, seqlen_q - seqlen_new),   capacity = cache_len, or max_blocks_per_seq * page_block_size,
+ * and since L_b <= capacity - seqlen_new after the clamp, every position used is below seqlen_ro whatever cache_seqlens and
+ * cache_leftpad hold.  (FlashAttention-2 does not check its tables against a paged cache's capacity; this call does, so a table
+ * that FlashAttention-2 accepts for a paged call can be refused here.)
+ * Checked before any HIP call, besides fa_ex_forward_kvcache_paged's list (FA_ERR_INVALID_ARGUMENT): one table without the other;
+ * rotary_dim not a multiple of 16 in [16, d]; rotary with seqlen_new = 0 or without cache_seqlens; seqlen_ro below the bound; a
+ * row stride below rotary_dim / 2, or odd; a table that is not 4-byte aligned; any of the five integers non-zero without tables.
+ * The workspace is fa_ex_forward_kvcache_paged's. */
+int fa_ex_forward_kvcache_rotary(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                                 const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                                 int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
+                                 int64_t q_token_stride, int64_t k_cache_batch_stride, int64_t k_cache_token_stride,
+                                 int64_t v_cache_batch_stride, int64_t v_cache_token_stride, int64_t k_new_batch_stride,
+                                 int64_t k_new_token_stride, int64_t v_new_batch_stride, int64_t v_new_token_stride, int causal,
+                                 int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
+                                 const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, const int32_t* block_table,
+                                 int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq,
+                                 const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad,
+                                 const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride,
+                                 int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
+                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* bytes of workspace a fa_ex_forward_kvcache call with these shapes and num_splits needs (0 for S = 1 and for invalid shapes) */
 size_t fa_ex_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t d,

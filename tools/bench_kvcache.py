@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time a KV-cache decode step (flashattention_lab_cuda.ex_kvcache_forward) against the same decode through ex_forward.
 
-    python tools/bench_kvcache.py [--d 128] [--dtype bf16] [--nq 1] [--page-size 16 --page-size 256] [--json out.json]
+    python tools/bench_kvcache.py [--d 128] [--dtype bf16] [--nq 1] [--page-size 16 --page-size 256] [--rotary] [--json out.json]
 
 Rows: B in {1, 8, 32}, H_q = 32, H_kv in {8, 32}, cache length in {1k, 8k, 32k, 128k}, plus one mixed-length batch.  The
 largest row (B = 32, 128k keys, H_kv = 32) holds 68 GB of cache and as much again in ex_forward's layout; --max-tokens drops
@@ -11,6 +11,9 @@ rows with B * len above it on smaller devices.  Each row reports the median time
   ex      : ex_forward with GQA on (B * H_q, 1, d) q and (B * H_kv, len, d) K/V (the layout it needs, copied once outside the timing),
   paged_<ps> (one per --page-size): the paged call without append over a pool that holds the same tokens, its pages assigned to
             the sequences in shuffled order (block_table; flashattention_lab_cuda.ex_kvcache_forward(..., block_table=...)),
+  kv_app_rot, unfused_rot (--rotary): kv_app with rotary_cos / rotary_sin (rotary_dim = d, not interleaved), the rotation of q and
+            of the new key fused into the call; and the same step with q and k_new rotated by torch elementwise ops on the device
+            in front of kv_app (checked against the fused call before it is timed),
 and the effective bandwidth of kv: bytes of K and V read (sum over b of len_b * H_kv * d * 2 * 2) / time, against 6.3 TB/s.
 Timing: HIP events around `--iters` back-to-back calls after `--warmup` calls; the median of `--reps` such groups."""
 import argparse
@@ -55,6 +58,30 @@ def row(b, hq, hkv, lens, d, dtype, args):
     sl1 = sl - 1
     t_kv = timed(lambda: ext.ex_kvcache_forward(q, kc, vc, None, None, sl, True, None), args.warmup, args.iters, args.reps)
     t_app = timed(lambda: ext.ex_kvcache_forward(q, kc, vc, kn, vn, sl1, True, None), args.warmup, args.iters, args.reps)
+    rot = {}
+    if args.rotary:
+        half = d // 2
+        inv = 10000.0 ** (-torch.arange(0, d, 2, dtype=torch.float64, device=dev) / d)
+        ang = torch.arange(cap + max(0, args.nq - 1), dtype=torch.float64, device=dev).view(-1, 1) * inv
+        cos, sin = torch.cos(ang).to(dtype), torch.sin(ang).to(dtype)
+        qi = torch.arange(args.nq, device=dev)
+
+        def rotate(x, pos):   # x (B, N, H, d), pos (B, N): GPT-NeoX pairs (j, j + d / 2), fp32, one rounding
+            c, s_ = cos[pos].float().unsqueeze(2), sin[pos].float().unsqueeze(2)
+            x1, x2 = x[..., :half].float(), x[..., half:].float()
+            return torch.cat((x1 * c - x2 * s_, x1 * s_ + x2 * c), -1).to(dtype)
+
+        def unfused():
+            pos = sl1.long().view(-1, 1)
+            return ext.ex_kvcache_forward(rotate(q, pos + qi), kc, vc, rotate(kn, pos), vn, sl1, True, None)
+
+        def fused():
+            return ext.ex_kvcache_forward(q, kc, vc, kn, vn, sl1, True, None, rotary_cos=cos, rotary_sin=sin, rotary_interleaved=False)
+
+        torch.testing.assert_close(fused()[0].float(), unfused()[0].float(), rtol=2e-2, atol=2e-2)
+        rot = dict(kv_app_rot_us=round(timed(fused, args.warmup, args.iters, args.reps), 2),
+                   unfused_rot_us=round(timed(unfused, args.warmup, args.iters, args.reps), 2))
+        del cos, sin, ang
     paged = {}
     for ps in args.page_size:
         mb = (cap + ps - 1) // ps
@@ -85,6 +112,7 @@ def row(b, hq, hkv, lens, d, dtype, args):
              kv_us=round(t_kv, 2), kv_append_us=round(t_app, 2), ex_forward_us=None if t_ex is None else round(t_ex, 2),
              speedup=None if t_ex is None else round(t_ex / t_kv, 2), kv_TBps=round(kv_bytes / t_kv / 1e6, 3),
              frac_copy_rate=round(kv_bytes / t_kv / 1e6 / (COPY_RATE / 1e12), 3))
+    r.update(rot)
     for ps, t in paged.items():
         r[f"paged_{ps}_us"] = round(t, 2)
         r[f"paged_{ps}_TBps"] = round(kv_bytes / t / 1e6, 3)
@@ -105,6 +133,7 @@ def main():
     ap.add_argument("--max-tokens", type=int, default=1 << 22, help="skip rows with B * len above this")
     ap.add_argument("--page-size", type=int, action="append", default=[], help="also time the paged call with this page size (repeatable)")
     ap.add_argument("--no-ex", action="store_true", help="skip the ex_forward column")
+    ap.add_argument("--rotary", action="store_true", help="also time the append with fused rotary embedding, and with torch rotating first")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16
@@ -130,7 +159,7 @@ def main():
     print(json.dumps(rows[-1]), flush=True)
     if args.json:
         with open(args.json, "w") as f:
-            json.dump(dict(d=args.d, dtype=args.dtype, nq=args.nq, page_sizes=args.page_size, copy_rate_TBps=COPY_RATE / 1e12, rows=rows), f, indent=1)
+            json.dump(dict(d=args.d, dtype=args.dtype, nq=args.nq, page_sizes=args.page_size, rotary=args.rotary, copy_rate_TBps=COPY_RATE / 1e12, rows=rows), f, indent=1)
 
 
 if __name__ == "__main__":
