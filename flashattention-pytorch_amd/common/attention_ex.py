@@ -190,7 +190,7 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_sin=None, cache_seqlens=None,
                             cache_batch_idx=None, cache_leftpad=None, block_table=None, softmax_scale=None, causal=False,
                             window_size=(-1, -1), softcap=0.0, rotary_interleaved=True, alibi_slopes=None, num_splits=0,
-                            return_softmax_lse=False):
+                            return_softmax_lse=False, k_descale=None, v_descale=None):
     """FlashAttention-2's flash_attn_with_kvcache (forward; its argument order): q (B, Nq, H_q, d); k_cache, v_cache
     (B, cache_len, H_kv, d) with H_q % H_kv == 0, updated in place — k, v (B, N_new, H_kv, d) are written at
     cache_seqlens[b] .. + N_new before attention, and a cache view the library cannot take without a copy raises ValueError.
@@ -207,6 +207,10 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     the cache; q at the position of its token when causal or a window bound is given, else every q token at the position of
     the first new token; q itself is not modified.  rotary_interleaved: pairs (2j, 2j + 1), else (j, j + rotary_dim / 2).
     seqlen_ro must be at least the capacity (cache_len, or max_blocks_per_seq * page_block_size) + max(0, Nq - N_new).
+    k_descale, v_descale (FlashAttention-3's): k_cache and v_cache may both be torch.float8_e4m3fn, half the bytes of a 16-bit
+    cache, with float32 dequantisation scales of shape (B, H_kv) or (H_kv,) on the device (None: 1.0; finite and > 0): a stored
+    value c of K head h of sequence b stands for c * k_descale[b, h].  q, k, v and the result stay 16-bit; k and v are quantised
+    as they are appended (after the rotation), with saturation at +-448.  Other 8-bit dtypes raise NotImplementedError.
     Returns o (B, Nq, H_q, d), and with return_softmax_lse also lse (B, H_q, Nq) float32.  No gradient."""
     for name, val in (("block_table", block_table), ("cache_batch_idx", cache_batch_idx), ("cache_leftpad", cache_leftpad)):
         if val is not None and not (isinstance(val, torch.Tensor) and val.dtype == torch.int32):
@@ -216,6 +220,10 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
         if val is not None and not (isinstance(val, torch.Tensor) and val.dtype == q.dtype):
             dt = val.dtype if isinstance(val, torch.Tensor) else type(val).__name__
             raise NotImplementedError(f"flash_attn_with_kvcache: {name} of dtype {dt} is not supported (q's dtype expected)")
+    for name, val in (("k_descale", k_descale), ("v_descale", v_descale)):
+        if val is not None and not (isinstance(val, torch.Tensor) and val.dtype == torch.float32):
+            dt = val.dtype if isinstance(val, torch.Tensor) else type(val).__name__
+            raise NotImplementedError(f"flash_attn_with_kvcache: {name} of dtype {dt} is not supported (float32 tensor expected)")
     import flashattention_lab_cuda as ext
 
     if isinstance(alibi_slopes, torch.Tensor):
@@ -225,5 +233,7 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
                                         None if v is None else v.detach(), cache_seqlens, bool(causal), softmax_scale,
                                         _window_size(window_size), softcap, alibi_slopes, num_splits, block_table, cache_batch_idx,
                                         cache_leftpad, None if rotary_cos is None else rotary_cos.detach(),
-                                        None if rotary_sin is None else rotary_sin.detach(), bool(rotary_interleaved))
+                                        None if rotary_sin is None else rotary_sin.detach(), bool(rotary_interleaved),
+                                        None if k_descale is None else k_descale.detach(),
+                                        None if v_descale is None else v_descale.detach())
     return (o, lse) if return_softmax_lse else o

@@ -754,7 +754,8 @@ size_t fa_ex_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t hea
 }
 
 // who: the entry point's name.  After stream come the eight arguments fa_ex_forward_kvcache_paged adds (all null / 0 is
-// fa_ex_forward_kvcache), then the seven fa_ex_forward_kvcache_rotary adds (all null / 0 is fa_ex_forward_kvcache_paged).
+// fa_ex_forward_kvcache), then the seven fa_ex_forward_kvcache_rotary adds (all null / 0 is fa_ex_forward_kvcache_paged), then the
+// four fa_ex_forward_kvcache_fp8 adds (cache_dtype = dtype, null, null, 0 is fa_ex_forward_kvcache_rotary).
 static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
                         const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
                         int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
@@ -766,9 +767,24 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
                         int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq, const int32_t* cache_batch_idx,
                         int64_t cache_batch, const int32_t* cache_leftpad, const void* rotary_cos, const void* rotary_sin,
                         int64_t rotary_cos_row_stride, int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim,
-                        int rotary_interleaved) {
+                        int rotary_interleaved, int cache_dtype, const float* k_descale, const float* v_descale,
+                        int64_t descale_batch_stride) {
     if (dtype != FA_DTYPE_F16 && dtype != FA_DTYPE_BF16)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: dtype must be f16 or bf16 (got code %d)", who, dtype);
+    // the cache's element type: q's, or e4m3 with a dequantisation scale per (sequence, K/V head)
+    if (cache_dtype != dtype && cache_dtype != FA_DTYPE_E4M3)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_dtype must be dtype (code %d) or FA_DTYPE_E4M3 (got code %d)", who, dtype,
+                    cache_dtype);
+    const bool e4m3 = cache_dtype == FA_DTYPE_E4M3;
+    if (!e4m3 && (k_descale || v_descale))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_descale / v_descale need an e4m3 cache (cache_dtype is code %d)", who, cache_dtype);
+    if (!e4m3 && descale_batch_stride != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: descale_batch_stride must be 0 with a 16-bit cache (got %lld)", who,
+                    (long long)descale_batch_stride);
+    if (descale_batch_stride < 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: descale_batch_stride must be >= 0 (got %lld)", who, (long long)descale_batch_stride);
+    if ((uintptr_t)k_descale % 4 != 0 || (uintptr_t)v_descale % 4 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_descale and v_descale must be 4-byte aligned", who);
     if (d < 8 || d > 256 || d % 8 != 0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: head_dim must be a multiple of 8 in [8, 256] (got %lld)", who, (long long)d);
     if (batch < 1 || batch > 65535) return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch must lie in [1, 65535] (got %lld)", who, (long long)batch);
@@ -776,6 +792,9 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads_q=%lld must be a positive multiple of heads_kv=%lld", who, (long long)heads_q,
                     (long long)heads_kv);
     if (seqlen_q < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_q must be >= 1 (got %lld)", who, (long long)seqlen_q);
+    if (descale_batch_stride != 0 && (descale_batch_stride < heads_kv || descale_batch_stride > ((int64_t)1 << 40)))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: descale_batch_stride=%lld must be 0 or >= heads_kv=%lld (and <= 2^40)", who,
+                    (long long)descale_batch_stride, (long long)heads_kv);
     // the paged cache and the two per-sequence cache selectors
     if (block_table) {
         if (cache_batch_idx || cache_leftpad)
@@ -817,12 +836,15 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
     // (a cache's units: its num_blocks pages of page_block_size tokens, its cache_batch rows, or its batch rows)
     const int64_t c_n = block_table ? page_block_size : cache_len;
     const int64_t c_units = block_table ? num_blocks : cache_batch_idx ? cache_batch : batch;
-    struct { const char* name; int64_t bs, ts, n, heads, units; } st[5] = {
-        {"q", q_batch_stride, q_token_stride, seqlen_q, heads_q, batch},
-        {"k_cache", k_cache_batch_stride, k_cache_token_stride, c_n, heads_kv, c_units},
-        {"v_cache", v_cache_batch_stride, v_cache_token_stride, c_n, heads_kv, c_units},
-        {"k_new", k_new_batch_stride, k_new_token_stride, seqlen_new, heads_kv, batch},
-        {"v_new", v_new_batch_stride, v_new_token_stride, seqlen_new, heads_kv, batch}};
+    // (esz: bytes an element.  The kernels keep 32-bit byte offsets inside one batch element or page, so the limit is on bytes:
+    // an e4m3 cache may hold twice the tokens of a 16-bit one)
+    const int64_t c_esz = e4m3 ? 1 : 2;
+    struct { const char* name; int64_t bs, ts, n, heads, units, esz; } st[5] = {
+        {"q", q_batch_stride, q_token_stride, seqlen_q, heads_q, batch, 2},
+        {"k_cache", k_cache_batch_stride, k_cache_token_stride, c_n, heads_kv, c_units, c_esz},
+        {"v_cache", v_cache_batch_stride, v_cache_token_stride, c_n, heads_kv, c_units, c_esz},
+        {"k_new", k_new_batch_stride, k_new_token_stride, seqlen_new, heads_kv, batch, 2},
+        {"v_new", v_new_batch_stride, v_new_token_stride, seqlen_new, heads_kv, batch, 2}};
     for (int i = 0; i < (seqlen_new > 0 ? 5 : 3); ++i) {
         const int64_t span = (st[i].n - 1) * st[i].ts + st[i].heads * d;   // elements of one batch element (or page)
         if (st[i].ts < st[i].heads * d || (st[i].units > 1 && st[i].bs < span) || st[i].bs < 0)
@@ -830,9 +852,9 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
                         who, st[i].name, (long long)st[i].bs, (long long)st[i].ts, (long long)(st[i].heads * d), (long long)span);
         if (st[i].ts % 8 != 0 || st[i].bs % 8 != 0)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of %s must be multiples of 8 elements", who, st[i].name);
-        if (span * 2 >= ((int64_t)1 << 31))
+        if (span * st[i].esz >= ((int64_t)1 << 31))
             return fail(FA_ERR_UNSUPPORTED, "%s: one batch element of %s spans %lld bytes, beyond 32-bit offsets", who, st[i].name,
-                        (long long)(span * 2));
+                        (long long)(span * st[i].esz));
     }
     if (seqlen_new > 0 && (!cache_seqlens || !k_new || !v_new))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_new > 0 needs cache_seqlens, k_new and v_new", who);
@@ -897,7 +919,12 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
     if (workspace_bytes < need || (need > 0 && !workspace))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
     if (!q || !k_cache || !v_cache || !o || !lse) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
-    if (!aligned16({q, k_cache, v_cache, o, workspace}) || (seqlen_new > 0 && !aligned16({k_new, v_new})))
+    if (e4m3) {   // an 8-element chunk of an e4m3 cache is 8 bytes: one load or store of 8 bytes, 8-byte aligned
+        if ((uintptr_t)k_cache % 8 != 0 || (uintptr_t)v_cache % 8 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: an e4m3 k_cache / v_cache must be 8-byte aligned", who);
+        if (!aligned16({q, o, workspace}) || (seqlen_new > 0 && !aligned16({k_new, v_new})))
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: tensors must be 16-byte aligned", who);
+    } else if (!aligned16({q, k_cache, v_cache, o, workspace}) || (seqlen_new > 0 && !aligned16({k_new, v_new})))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: tensors must be 16-byte aligned", who);
     fa::KvArgs a{};
     a.q = q; a.k_cache = k_cache; a.v_cache = v_cache; a.k_new = k_new; a.v_new = v_new; a.o = o; a.lse = lse;
@@ -914,6 +941,7 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
     a.num_splits = S; a.workspace = workspace;
     a.rotary_cos = rotary_cos; a.rotary_sin = rotary_sin; a.rotary_cos_rs = rotary_cos_row_stride; a.rotary_sin_rs = rotary_sin_row_stride;
     a.rotary_dim = rotary_dim; a.rotary_interleaved = rotary_interleaved ? 1 : 0; a.rotary_q_per_token = rotary_cos ? rotary_q_per_token : 0;
+    a.cache_e4m3 = e4m3 ? 1 : 0; a.k_descale = k_descale; a.v_descale = v_descale; a.descale_bstride = descale_batch_stride;
     hipError_t e = fa::launch_kvcache(a, reinterpret_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
     return FA_OK;
@@ -932,7 +960,7 @@ int fa_ex_forward_kvcache(const void* q, void* k_cache, void* v_cache, const voi
                         k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride, k_new_batch_stride, k_new_token_stride,
                         v_new_batch_stride, v_new_token_stride, causal, window_left, window_right, softmax_scale, softcap, alibi_slopes,
                         alibi_batch_stride, num_splits, workspace, workspace_bytes, stream, nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, nullptr,
-                        nullptr, 0, 0, 0, 0, 0);
+                        nullptr, 0, 0, 0, 0, 0, dtype, nullptr, nullptr, 0);
 }
 
 int fa_ex_forward_kvcache_paged(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
@@ -952,7 +980,7 @@ int fa_ex_forward_kvcache_paged(const void* q, void* k_cache, void* v_cache, con
                         v_new_batch_stride, v_new_token_stride, causal, window_left, window_right, softmax_scale, softcap, alibi_slopes,
                         alibi_batch_stride, num_splits, workspace, workspace_bytes, stream, block_table, block_table_row_stride,
                         num_blocks, page_block_size, max_blocks_per_seq, cache_batch_idx, cache_batch, cache_leftpad, nullptr, nullptr, 0, 0,
-                        0, 0, 0);
+                        0, 0, 0, dtype, nullptr, nullptr, 0);
 }
 
 int fa_ex_forward_kvcache_rotary(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
@@ -974,7 +1002,32 @@ int fa_ex_forward_kvcache_rotary(const void* q, void* k_cache, void* v_cache, co
                         v_new_batch_stride, v_new_token_stride, causal, window_left, window_right, softmax_scale, softcap, alibi_slopes,
                         alibi_batch_stride, num_splits, workspace, workspace_bytes, stream, block_table, block_table_row_stride,
                         num_blocks, page_block_size, max_blocks_per_seq, cache_batch_idx, cache_batch, cache_leftpad, rotary_cos,
-                        rotary_sin, rotary_cos_row_stride, rotary_sin_row_stride, seqlen_ro, rotary_dim, rotary_interleaved);
+                        rotary_sin, rotary_cos_row_stride, rotary_sin_row_stride, seqlen_ro, rotary_dim, rotary_interleaved, dtype, nullptr,
+                        nullptr, 0);
+}
+
+int fa_ex_forward_kvcache_fp8(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                              const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                              int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
+                              int64_t q_token_stride, int64_t k_cache_batch_stride, int64_t k_cache_token_stride,
+                              int64_t v_cache_batch_stride, int64_t v_cache_token_stride, int64_t k_new_batch_stride,
+                              int64_t k_new_token_stride, int64_t v_new_batch_stride, int64_t v_new_token_stride, int causal,
+                              int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
+                              const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, const int32_t* block_table,
+                              int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq,
+                              const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad,
+                              const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride,
+                              int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
+                              int cache_dtype, const float* k_descale, const float* v_descale, int64_t descale_batch_stride,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    return kvcache_impl("fa_ex_forward_kvcache_fp8", q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, batch, heads_q, heads_kv,
+                        seqlen_q, seqlen_new, cache_len, d, dtype, q_batch_stride, q_token_stride, k_cache_batch_stride,
+                        k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride, k_new_batch_stride, k_new_token_stride,
+                        v_new_batch_stride, v_new_token_stride, causal, window_left, window_right, softmax_scale, softcap, alibi_slopes,
+                        alibi_batch_stride, num_splits, workspace, workspace_bytes, stream, block_table, block_table_row_stride,
+                        num_blocks, page_block_size, max_blocks_per_seq, cache_batch_idx, cache_batch, cache_leftpad, rotary_cos,
+                        rotary_sin, rotary_cos_row_stride, rotary_sin_row_stride, seqlen_ro, rotary_dim, rotary_interleaved, cache_dtype,
+                        k_descale, v_descale, descale_batch_stride);
 }
 
 size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {

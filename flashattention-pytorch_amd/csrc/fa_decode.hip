@@ -141,14 +141,73 @@ __device__ __forceinline__ void kv_split_range(const KvParams& p, int lk, int ql
     kend = min(hi, lo + t1 * KT);
 }
 
+// e4m3 cache (fa_ex_forward_kvcache_fp8): the last argument of the *_q8 kernels.  The scale of (b, K/V head) is kd[b * bs + hk]
+// (vd likewise); null = 1.0.  The KvParams cache pointers then address bytes, and the cache strides are in bytes as well.
+struct KvQ8 {
+    const float *kd, *vd;
+    long long bs;
+};
+
+// 8 e4m3 bytes -> 8 values of q's 16-bit dtype, exact (every finite e4m3 value is a normal f16 and bf16 number): one
+// v_cvt_scalef32_pk_{f16,bf16}_fp8 at scale 1.0 per pair, element order kept
+template <typename Tag> __device__ __forceinline__ u32x4 kv_q8_widen(u32x2 c);
+template <> __device__ __forceinline__ u32x4 kv_q8_widen<f16_tag>(u32x2 c) {
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    u32x4 out;
+    out[0] = __builtin_bit_cast(uint32_t, (h2)__builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c[0], 1.0f, false));
+    out[1] = __builtin_bit_cast(uint32_t, (h2)__builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c[0], 1.0f, true));
+    out[2] = __builtin_bit_cast(uint32_t, (h2)__builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c[1], 1.0f, false));
+    out[3] = __builtin_bit_cast(uint32_t, (h2)__builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c[1], 1.0f, true));
+    return out;
+}
+template <> __device__ __forceinline__ u32x4 kv_q8_widen<bf16_tag>(u32x2 c) {
+    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
+    u32x4 out;
+    out[0] = __builtin_bit_cast(uint32_t, (b2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[0], 1.0f, false));
+    out[1] = __builtin_bit_cast(uint32_t, (b2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[0], 1.0f, true));
+    out[2] = __builtin_bit_cast(uint32_t, (b2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[1], 1.0f, false));
+    out[3] = __builtin_bit_cast(uint32_t, (b2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[1], 1.0f, true));
+    return out;
+}
+
+// 8 values of q's 16-bit dtype -> 8 e4m3 bytes: y = clamp(float(x) * inv, -448, 448) in fp32, then round to nearest even
+// (v_cvt_pk_fp8_f32; after the clamp its saturation mode cannot matter, and a finite x never gives the NaN code)
+template <typename Tag> __device__ __forceinline__ u32x2 kv_q8_quant(u32x4 x, float inv) {
+    float y[8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        y[2 * i] = fminf(fmaxf(unpack_lo<Tag>(x[i]) * inv, -448.f), 448.f);
+        y[2 * i + 1] = fminf(fmaxf(unpack_hi<Tag>(x[i]) * inv, -448.f), 448.f);
+    }
+    u32x2 out;
+#pragma unroll
+    for (int w = 0; w < 2; ++w) {
+        int v = __builtin_amdgcn_cvt_pk_fp8_f32(y[4 * w], y[4 * w + 1], 0, false);
+        v = __builtin_amdgcn_cvt_pk_fp8_f32(y[4 * w + 2], y[4 * w + 3], v, true);
+        out[w] = (uint32_t)v;
+    }
+    return out;
+}
+
 // kv_append_kernel and kv_split_kernel, then the same source with the rotation compiled in: kv_append_rot_kernel and
-// kv_split_rot_kernel, which take a KvRot beside the KvParams
+// kv_split_rot_kernel, which take a KvRot beside the KvParams; then both again for an e4m3 cache (KV_Q8): kv_append_q8_kernel,
+// kv_split_q8_kernel, kv_append_rot_q8_kernel and kv_split_rot_q8_kernel, which take a KvQ8 as well
+#define KV_Q8 0
 #define KV_ROT 0
 #include "fa_decode_kernels.inc"
 #undef KV_ROT
 #define KV_ROT 1
 #include "fa_decode_kernels.inc"
 #undef KV_ROT
+#undef KV_Q8
+#define KV_Q8 1
+#define KV_ROT 0
+#include "fa_decode_kernels.inc"
+#undef KV_ROT
+#define KV_ROT 1
+#include "fa_decode_kernels.inc"
+#undef KV_ROT
+#undef KV_Q8
 
 // One wave per (b, h_q, token) row, four rows per workgroup.  The lanes read the S lse partials side by side (lane c: splits
 // c, c + 64, ..), reduce max and weight sum over the wave in a fixed shuffle order, and park the weights in LDS; then lane c adds
@@ -200,9 +259,17 @@ __global__ __launch_bounds__(256) void kv_combine_kernel(KvParams p, int S, long
 }
 
 template <typename Tag, int D>
-hipError_t launch_split(const KvParams& p, const KvRot& ro, int S, int row_tiles, int batch, hipStream_t st) {
+hipError_t launch_split(const KvParams& p, const KvRot& ro, const KvQ8* q8, int S, int row_tiles, int batch, hipStream_t st) {
     const dim3 grid((unsigned)S, (unsigned)(row_tiles * p.hkv), (unsigned)batch);
-    if (ro.cos) {
+    if (q8) {
+        if (ro.cos) {
+            if (p.table) hipLaunchKernelGGL((kv_split_rot_q8_kernel<Tag, D, true>), grid, dim3(64), 0, st, p, ro, *q8);
+            else hipLaunchKernelGGL((kv_split_rot_q8_kernel<Tag, D, false>), grid, dim3(64), 0, st, p, ro, *q8);
+        } else if (p.table)
+            hipLaunchKernelGGL((kv_split_q8_kernel<Tag, D, true>), grid, dim3(64), 0, st, p, *q8);
+        else
+            hipLaunchKernelGGL((kv_split_q8_kernel<Tag, D, false>), grid, dim3(64), 0, st, p, *q8);
+    } else if (ro.cos) {
         if (p.table) hipLaunchKernelGGL((kv_split_rot_kernel<Tag, D, true>), grid, dim3(64), 0, st, p, ro);
         else hipLaunchKernelGGL((kv_split_rot_kernel<Tag, D, false>), grid, dim3(64), 0, st, p, ro);
     } else if (p.table)
@@ -213,19 +280,21 @@ hipError_t launch_split(const KvParams& p, const KvRot& ro, int S, int row_tiles
 }
 
 template <typename Tag>
-hipError_t launch_kv_t(const KvParams& p, const KvRot& ro, int S, int row_tiles, int batch, hipStream_t st) {
+hipError_t launch_kv_t(const KvParams& p, const KvRot& ro, const KvQ8* q8, int S, int row_tiles, int batch, hipStream_t st) {
     hipError_t e = hipSuccess;
     if (p.nnew > 0) {
         const long long per_b = (long long)p.nnew * p.hkv * (p.d / 8);
         const dim3 grid((unsigned)std::min<long long>((per_b + 255) / 256, 1024), (unsigned)batch);
-        if (ro.cos) hipLaunchKernelGGL(kv_append_rot_kernel<Tag>, grid, dim3(256), 0, st, p, ro);
+        if (q8 && ro.cos) hipLaunchKernelGGL(kv_append_rot_q8_kernel<Tag>, grid, dim3(256), 0, st, p, ro, *q8);
+        else if (q8) hipLaunchKernelGGL(kv_append_q8_kernel<Tag>, grid, dim3(256), 0, st, p, *q8);
+        else if (ro.cos) hipLaunchKernelGGL(kv_append_rot_kernel<Tag>, grid, dim3(256), 0, st, p, ro);
         else hipLaunchKernelGGL(kv_append_kernel, grid, dim3(256), 0, st, p);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    if (p.d <= 64) e = launch_split<Tag, 64>(p, ro, S, row_tiles, batch, st);
-    else if (p.d <= 128) e = launch_split<Tag, 128>(p, ro, S, row_tiles, batch, st);
-    else e = launch_split<Tag, 256>(p, ro, S, row_tiles, batch, st);
+    if (p.d <= 64) e = launch_split<Tag, 64>(p, ro, q8, S, row_tiles, batch, st);
+    else if (p.d <= 128) e = launch_split<Tag, 128>(p, ro, q8, S, row_tiles, batch, st);
+    else e = launch_split<Tag, 256>(p, ro, q8, S, row_tiles, batch, st);
     if (e != hipSuccess || S == 1) return e;
     const long long nrows = (long long)batch * p.hq * p.nq;
     hipLaunchKernelGGL((kv_combine_kernel<Tag>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st, p, S, nrows);
@@ -284,9 +353,12 @@ hipError_t launch_kvcache(const KvArgs& a, hipStream_t st) {
     ro.cos = (const uint16_t*)a.rotary_cos; ro.sin = (const uint16_t*)a.rotary_sin;
     ro.cos_rs = a.rotary_cos_rs; ro.sin_rs = a.rotary_sin_rs;
     ro.rdim = (int)a.rotary_dim; ro.inter = a.rotary_interleaved; ro.qseq = a.rotary_q_per_token;
+    const KvQ8 q8{a.k_descale, a.v_descale, (long long)a.descale_bstride};
+    const KvQ8* q8p = a.cache_e4m3 ? &q8 : nullptr;
     const int batch = (int)a.batch;
     const int row_tiles = (p.rows + 15) / 16;
-    return a.dtype == 1 ? launch_kv_t<f16_tag>(p, ro, S, row_tiles, batch, st) : launch_kv_t<bf16_tag>(p, ro, S, row_tiles, batch, st);
+    return a.dtype == 1 ? launch_kv_t<f16_tag>(p, ro, q8p, S, row_tiles, batch, st)
+                        : launch_kv_t<bf16_tag>(p, ro, q8p, S, row_tiles, batch, st);
 }
 
 }  // namespace fa

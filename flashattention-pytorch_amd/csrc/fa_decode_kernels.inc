@@ -1,11 +1,21 @@
 // The append and split kernels of fa_decode.hip, included twice: KV_ROT 0 gives kv_append_kernel and kv_split_kernel, KV_ROT 1
 // kv_append_rot_kernel and kv_split_rot_kernel (rotary embedding, KvRot).  One source, so the two cannot drift apart, and the
 // kernels without rotation are compiled from exactly the text they had before the rotation existed.
+// Two more inclusions with KV_Q8 1 give the same four kernels for an e4m3 cache (kv_*_q8_kernel, a KvQ8 as last argument):
+// the cache is addressed in bytes, a chunk of 8 head dims is 8 bytes, K and V chunks are widened to q's 16-bit dtype in
+// registers (kv_q8_widen) on their way into the unchanged 16-bit loop, and the append quantises (kv_q8_quant).  With KV_Q8 0
+// every line below preprocesses to what it was before KV_Q8 existed.
 
 // Token L_b + n of batch element b goes to cache row (bidx ? bidx[b] : b) at position L_b + n, or through the table to
 // pool[table[b, (L_b + n) / ps], (L_b + n) % ps]; a row or page outside the cache / pool drops the token.
 // KV_ROT: k_new[b, n] is rotated at position L_b - P_b + n on the way (Tag: its dtype).
-#if KV_ROT
+#if KV_Q8 && KV_ROT
+template <typename Tag>
+__global__ __launch_bounds__(256) void kv_append_rot_q8_kernel(KvParams p, KvRot ro, KvQ8 q8) {
+#elif KV_Q8
+template <typename Tag>
+__global__ __launch_bounds__(256) void kv_append_q8_kernel(KvParams p, KvQ8 q8) {
+#elif KV_ROT
 template <typename Tag>
 __global__ __launch_bounds__(256) void kv_append_rot_kernel(KvParams p, KvRot ro) {
 #else
@@ -48,8 +58,17 @@ __global__ __launch_bounds__(256) void kv_append_kernel(KvParams p) {
         const u32x4 kx = *reinterpret_cast<const u32x4*>(p.kn + b * p.kn_bs + (size_t)n * p.kn_ts + col);
 #endif
         const u32x4 vx = *reinterpret_cast<const u32x4*>(p.vn + b * p.vn_bs + (size_t)n * p.vn_ts + col);
+#if KV_Q8
+        // the (rotated, rounded) 16-bit values, quantised: one 8-byte store a chunk, the cache addressed in bytes
+        const float kinv = 1.0f / (q8.kd ? q8.kd[b * q8.bs + h] : 1.0f), vinv = 1.0f / (q8.vd ? q8.vd[b * q8.bs + h] : 1.0f);
+        uint8_t* kc8 = reinterpret_cast<uint8_t*>(p.kc);
+        uint8_t* vc8 = reinterpret_cast<uint8_t*>(p.vc);
+        *reinterpret_cast<u32x2*>(kc8 + unit * p.kc_bs + (size_t)pos * p.kc_ts + col) = kv_q8_quant<Tag>(kx, kinv);
+        *reinterpret_cast<u32x2*>(vc8 + unit * p.vc_bs + (size_t)pos * p.vc_ts + col) = kv_q8_quant<Tag>(vx, vinv);
+#else
         *reinterpret_cast<u32x4*>(p.kc + unit * p.kc_bs + (size_t)pos * p.kc_ts + col) = kx;
         *reinterpret_cast<u32x4*>(p.vc + unit * p.vc_bs + (size_t)pos * p.vc_ts + col) = vx;
+#endif
     }
 }
 
@@ -58,8 +77,13 @@ __global__ __launch_bounds__(256) void kv_append_kernel(KvParams p) {
 // of S^T, 4 head-dim elements of each 16-wide block of O^T).  D: the padded tile width (64 | 128 | 256), p.d <= D.
 // PAGED: keys are reached through p.table (see the head of this file); otherwise through one buffer range per wave.
 // KV_ROT: the q fragments are rotated (ro) before the key loop.
+// KV_Q8: the cache holds e4m3 (q8: the scales of (b, hk)); each lane loads 8 bytes where it loaded 16 and widens them.
 template <typename Tag, int D, bool PAGED>
-#if KV_ROT
+#if KV_Q8 && KV_ROT
+__global__ __launch_bounds__(64) void kv_split_rot_q8_kernel(KvParams p, KvRot ro, KvQ8 q8) {
+#elif KV_Q8
+__global__ __launch_bounds__(64) void kv_split_q8_kernel(KvParams p, KvQ8 q8) {
+#elif KV_ROT
 __global__ __launch_bounds__(64) void kv_split_rot_kernel(KvParams p, KvRot ro) {
 #else
 __global__ __launch_bounds__(64) void kv_split_kernel(KvParams p) {
@@ -114,10 +138,20 @@ __global__ __launch_bounds__(64) void kv_split_kernel(KvParams p) {
         crow = ix;
         if ((unsigned)ix >= (unsigned)p.bcache) { crow = 0; ctok = 0; }
     }
+#if KV_Q8
+    const uint8_t* kc8 = reinterpret_cast<const uint8_t*>(p.kc);
+    const uint8_t* vc8 = reinterpret_cast<const uint8_t*>(p.vc);
+    const float kdsc = q8.kd ? q8.kd[b * q8.bs + hk] : 1.0f, vdsc = q8.vd ? q8.vd[b * q8.bs + hk] : 1.0f;
+    const buf_rsrc_t k_rs = make_rsrc(kc8 + crow * p.kc_bs + (long long)P_b * p.kc_ts,
+                                      ctok > 0 ? (unsigned)((ctok - 1) * p.kc_ts + p.hkv * DR) : 0u);
+    const buf_rsrc_t v_rs = make_rsrc(vc8 + crow * p.vc_bs + (long long)P_b * p.vc_ts,
+                                      ctok > 0 ? (unsigned)((ctok - 1) * p.vc_ts + p.hkv * DR) : 0u);
+#else
     const buf_rsrc_t k_rs = make_rsrc(p.kc + crow * p.kc_bs + (long long)P_b * p.kc_ts,
                                       ctok > 0 ? (unsigned)(((ctok - 1) * p.kc_ts + p.hkv * DR) * 2) : 0u);
     const buf_rsrc_t v_rs = make_rsrc(p.vc + crow * p.vc_bs + (long long)P_b * p.vc_ts,
                                       ctok > 0 ? (unsigned)(((ctok - 1) * p.vc_ts + p.hkv * DR) * 2) : 0u);
+#endif
     // paged: the table row, and the page j0 and slot s0 of the tile's first key (a 32-key tile spans at most three pages)
     const int* tbl = PAGED ? p.table + b * p.tbl_rs : nullptr;
     int j0 = 0, s0 = 0, pg = -1;
@@ -163,6 +197,15 @@ __global__ __launch_bounds__(64) void kv_split_kernel(KvParams p) {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) {
                 const long long ro = __shfl(ko, 16 * kb + r, 64);
+#if KV_Q8
+                const uint8_t* kp = kc8 + ro + hk * DR + 8 * g;
+#pragma unroll
+                for (int ks = 0; ks < NKS; ++ks) {
+                    const bool ok = ro >= 0 && 32 * ks + 8 * g < DR;
+                    const u32x2 x = *reinterpret_cast<const u32x2*>(ok ? kp + 32 * ks : reinterpret_cast<const uint8_t*>(p.q));
+                    kf[kb][ks] = __builtin_bit_cast(s16x8, kv_q8_widen<Tag>(ok ? x : u32x2{0u, 0u}));
+                }
+#else
                 const uint16_t* kp = p.kc + ro + hk * DR + 8 * g;
 #pragma unroll
                 for (int ks = 0; ks < NKS; ++ks) {
@@ -170,14 +213,20 @@ __global__ __launch_bounds__(64) void kv_split_kernel(KvParams p) {
                     const s16x8 x = *reinterpret_cast<const s16x8*>(ok ? kp + 32 * ks : p.q);
                     kf[kb][ks] = ok ? x : s16x8{0, 0, 0, 0, 0, 0, 0, 0};
                 }
+#endif
             }
 #pragma unroll
             for (int i = 0; i < VLD; ++i) {
                 const int idx = 64 * i + lane, row = idx / CPR, ch = idx - row * CPR;
                 const long long ro = __shfl(vo, row, 64);
                 const bool ok = ro >= 0 && 8 * ch < DR;
+#if KV_Q8
+                const u32x2 x = *reinterpret_cast<const u32x2*>(ok ? vc8 + ro + hk * DR + 8 * ch : reinterpret_cast<const uint8_t*>(p.q));
+                vr[i] = kv_q8_widen<Tag>(ok ? x : u32x2{0u, 0u});
+#else
                 const u32x4 x = *reinterpret_cast<const u32x4*>(ok ? p.vc + ro + hk * DR + 8 * ch : p.q);
                 vr[i] = ok ? x : u32x4{0u, 0u, 0u, 0u};
+#endif
             }
         } else {
 #pragma unroll
@@ -186,14 +235,24 @@ __global__ __launch_bounds__(64) void kv_split_kernel(KvParams p) {
 #pragma unroll
                 for (int ks = 0; ks < NKS; ++ks) {
                     const int col = 32 * ks + 8 * g;
+#if KV_Q8
+                    kf[kb][ks] = __builtin_bit_cast(s16x8, kv_q8_widen<Tag>(__builtin_amdgcn_raw_buffer_load_b64(
+                        k_rs, (key < kend && col < DR) ? key * p.kc_ts + hk * DR + col : kOobOff, 0, 0)));
+#else
                     kf[kb][ks] = buf_load_frag(k_rs, (key < kend && col < DR) ? (key * p.kc_ts + hk * DR + col) * 2 : kOobOff);
+#endif
                 }
             }
 #pragma unroll
             for (int i = 0; i < VLD; ++i) {
                 const int idx = 64 * i + lane, row = idx / CPR, ch = idx - row * CPR, key = k0 + row;
+#if KV_Q8
+                vr[i] = kv_q8_widen<Tag>(__builtin_amdgcn_raw_buffer_load_b64(
+                    v_rs, (key < kend && 8 * ch < DR) ? key * p.vc_ts + hk * DR + 8 * ch : kOobOff, 0, 0));
+#else
                 vr[i] = __builtin_amdgcn_raw_buffer_load_b128(v_rs, (key < kend && 8 * ch < DR) ? (key * p.vc_ts + hk * DR + 8 * ch) * 2 : kOobOff,
                                                               0, 0);
+#endif
             }
         }
         f32x4_t sacc[2];
@@ -203,6 +262,11 @@ __global__ __launch_bounds__(64) void kv_split_kernel(KvParams p) {
 #pragma unroll
             for (int ks = 0; ks < NKS; ++ks) sacc[kb] = mfma16<Tag>(kf[kb][ks], qf[ks], sacc[kb]);
         }
+#if KV_Q8
+        // both score tiles live in VGPRs at one point: without this hipcc ends the second chain in the first one's registers
+        // (a[0:3] = .. + a[4:7]), a C operand that is not the destination, which tools/mfma_hazard_audit.py R1 does not pass
+        asm volatile("" : "+v"(sacc[0]), "+v"(sacc[1]));
+#endif
         // (the previous tile's transposed reads were issued before these writes: one wave, LDS in order)
 #pragma unroll
         for (int i = 0; i < VLD; ++i) {
@@ -217,7 +281,11 @@ __global__ __launch_bounds__(64) void kv_split_kernel(KvParams p) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int key = k0 + 16 * kb + 4 * g + i;
+#if KV_Q8
+                float x = sacc[kb][i] * kdsc;   // s = softmax_scale * k_descale * (q . k_stored): before softcap and ALiBi
+#else
                 float x = sacc[kb][i];
+#endif
                 if (p.sc.cap_a > 0.f) { float dt; x = mod_softcap(x, p.sc, dt); }
                 if (p.alibi) x = mod_alibi(x, al, (float)(qi + coff - key));
                 x = (key >= rlo && key <= rhi) ? x : -INFINITY;
@@ -270,8 +338,13 @@ __global__ __launch_bounds__(64) void kv_split_kernel(KvParams p) {
             const int col = 16 * t + 4 * g;
             if (col < DR) {
                 u32x2 v;
+#if KV_Q8
+                v[0] = pack2_rn<Tag>(oacc[t][0] * inv * vdsc, oacc[t][1] * inv * vdsc);
+                v[1] = pack2_rn<Tag>(oacc[t][2] * inv * vdsc, oacc[t][3] * inv * vdsc);
+#else
                 v[0] = pack2_rn<Tag>(oacc[t][0] * inv, oacc[t][1] * inv);
                 v[1] = pack2_rn<Tag>(oacc[t][2] * inv, oacc[t][3] * inv);
+#endif
                 *reinterpret_cast<u32x2*>(orow + col) = v;
             }
         }
@@ -281,7 +354,11 @@ __global__ __launch_bounds__(64) void kv_split_kernel(KvParams p) {
 #pragma unroll
         for (int t = 0; t < NDB; ++t) {
             const int col = 16 * t + 4 * g;
+#if KV_Q8
+            if (col < DR) *reinterpret_cast<f32x4_t*>(prow + col) = oacc[t] * inv * vdsc;
+#else
             if (col < DR) *reinterpret_cast<f32x4_t*>(prow + col) = oacc[t] * inv;
+#endif
         }
         if (g == 0) p.plse[row_id * S + s] = lse_v;
     }

@@ -200,6 +200,12 @@ struct KvArgs {
     int64_t rotary_cos_rs, rotary_sin_rs, rotary_dim;
     int rotary_interleaved;        // pairs (2j, 2j + 1), else (j, j + rotary_dim / 2)
     int rotary_q_per_token;        // q token i at position L_b - P_b + i (causal or a window bound given), else all at L_b - P_b
+    // fa_ex_forward_kvcache_fp8 (0 / null: a 16-bit cache).  cache_e4m3: k_cache / v_cache hold OCP e4m3 bytes, their strides
+    // (still in elements) are bytes, 8-byte aligned; a stored byte c of K head h of sequence b stands for
+    // e4m3(c) * k_descale[b * descale_bstride + h] (V likewise), a null scale for 1.0.
+    int cache_e4m3 = 0;
+    const float *k_descale = nullptr, *v_descale = nullptr;
+    int64_t descale_bstride = 0;
 };
 int kv_num_splits(int64_t batch, int64_t heads_kv, int64_t row_tiles, int64_t cache_len);
 size_t kv_workspace_bytes(int64_t batch, int64_t heads_q, int64_t seqlen_q, int64_t d, int splits);

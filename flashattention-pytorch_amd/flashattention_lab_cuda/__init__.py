@@ -43,6 +43,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_ex_forward_varlen", "fa_ex_backward_varlen", "fa_ex_backward_workspace_bytes_varlen",
     "fa_ex_forward_scoremod", "fa_ex_backward_scoremod", "fa_ex_forward_varlen_scoremod", "fa_ex_backward_varlen_scoremod",
     "fa_ex_forward_kvcache", "fa_ex_kvcache_workspace_bytes", "fa_ex_forward_kvcache_paged", "fa_ex_forward_kvcache_rotary",
+    "fa_ex_forward_kvcache_fp8",
 )
 
 
@@ -149,6 +150,10 @@ def _load_library() -> ctypes.CDLL:
     lib.fa_ex_forward_kvcache_rotary.argtypes = [vp] * 8 + [i64] * 7 + [ci] + [i64] * 10 + [ci, i64, i64, dbl, dbl, vp, i64, i64] + \
         [vp, i64, i64, i64, i64, vp, i64, vp] + [vp, vp, i64, i64, i64, i64, ci] + [vp, sz, vp]
     lib.fa_ex_forward_kvcache_rotary.restype = ci
+    # ... rotary_interleaved; cache_dtype, k_descale, v_descale, descale_batch_stride; workspace, ...
+    lib.fa_ex_forward_kvcache_fp8.argtypes = [vp] * 8 + [i64] * 7 + [ci] + [i64] * 10 + [ci, i64, i64, dbl, dbl, vp, i64, i64] + \
+        [vp, i64, i64, i64, i64, vp, i64, vp] + [vp, vp, i64, i64, i64, i64, ci] + [ci, vp, vp, i64] + [vp, sz, vp]
+    lib.fa_ex_forward_kvcache_fp8.restype = ci
     lib.fa_ex_kvcache_workspace_bytes.argtypes = [i64] * 7
     lib.fa_ex_kvcache_workspace_bytes.restype = sz
     return lib
@@ -611,6 +616,35 @@ def ex_varlen_backward(q, k, v, o, do_, lse, cu_seqlens_q, cu_seqlens_k, max_seq
 
 # ---- KV-cache decoding with split-KV (include/fa_mi355x.h: fa_ex_forward_kvcache) ----
 
+_E4M3_CODE = 3   # FA_DTYPE_E4M3
+_FLOAT8_DTYPES = tuple(getattr(torch, n) for n in ("float8_e4m3fn", "float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz")
+                       if hasattr(torch, n))
+
+
+def _kv_descale(who, name, t, q, b, hkv):
+    """(pointer, batch stride, the tensor to keep alive) of a float32 (B, H_kv) or (H_kv,) scale on q's device; None: (0, 0, None)"""
+    if t is None:
+        return 0, 0, None
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        dt = t.dtype if isinstance(t, torch.Tensor) else type(t).__name__
+        raise NotImplementedError(f"{who}: {name} of dtype {dt} is not supported (float32 tensor expected)")
+    if t.device != q.device:
+        raise RuntimeError(f"{who}: {name} must be on q's device ({q.device}), got {t.device}")
+    if t.shape == (hkv,):
+        if t.stride(0) != 1 and hkv > 1:
+            raise RuntimeError(f"{who}: {name} of shape (H_kv,) must be contiguous")
+        return t.data_ptr(), 0, t
+    if t.shape != (b, hkv):
+        raise RuntimeError(f"{who}: {name} must be float32 of shape (B, H_kv) = ({b}, {hkv}) or (H_kv,), got {tuple(t.shape)}")
+    if hkv > 1 and t.stride(1) != 1:
+        raise RuntimeError(f"{who}: {name} must have a contiguous last dim")
+    bs = t.stride(0) if b > 1 else max(t.stride(0), hkv)
+    if bs < hkv:   # an expanded row: the (H_kv,) form
+        if bs != 0:
+            raise RuntimeError(f"{who}: {name} has overlapping rows (stride {bs} < H_kv = {hkv})")
+    return t.data_ptr(), bs, t
+
+
 def _kv_strides(who, name, t, heads, d, cache):
     """(batch stride, token stride) of a (B, N, heads, d) tensor whose heads are adjacent at stride d, last dim contiguous."""
     if t.stride(3) != 1 or (heads > 1 and t.stride(2) != d):
@@ -626,7 +660,7 @@ def _kv_strides(who, name, t, heads, d, cache):
 
 def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlens=None, causal=False, softmax_scale=None,
                        window=(-1, -1), softcap=0.0, alibi_slopes=None, num_splits=0, block_table=None, cache_batch_idx=None,
-                       cache_leftpad=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True):
+                       cache_leftpad=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True, k_descale=None, v_descale=None):
     """(o, lse) of a decode step over a KV cache (FlashAttention-2's flash_attn_with_kvcache, forward): q (B, Nq, H_q, d);
     k_cache, v_cache (B, cache_len, H_kv, d), used in place (strided views such as kv.unbind(2) allowed, never copied);
     k_new, v_new (B, N_new, H_kv, d) are written into the caches at cache_seqlens[b] first; cache_seqlens int32 (B,) on the
@@ -640,7 +674,14 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
     is rotated at its position in the sequence before it is written to the cache, and the kernel's copy of q at the position
     of its token (causal or a window bound given) or of the first new token (neither); pairs (2j, 2j + 1) with
     rotary_interleaved, else (j, j + rotary_dim / 2).  Needs k_new, v_new, cache_seqlens and seqlen_ro >= capacity +
-    max(0, Nq - N_new).  See fa_ex_forward_kvcache_rotary."""
+    max(0, Nq - N_new).  See fa_ex_forward_kvcache_rotary.
+    k_cache and v_cache may both be torch.float8_e4m3fn (OCP e4m3) while q, k_new, v_new and o stay 16-bit: a stored byte c of
+    K head h of sequence b stands for e4m3(c) * k_descale[b, h] (V: v_descale).  k_descale, v_descale: float32 (B, H_kv) (last
+    dim contiguous, the row stride is passed through) or contiguous (H_kv,), on q's device, read by the kernels only; None means
+    1.0; they must be finite and > 0.  The scale follows the sequence b of the call, not the cache row or page.  k_new / v_new
+    are quantised on the append: clamp(float(x) * (1.0f / descale), -448, 448) in fp32, rounded to nearest even.  An e4m3 cache
+    view must have strides that are multiples of 8 and an 8-byte aligned address (ValueError otherwise; never copied).  See
+    fa_ex_forward_kvcache_fp8."""
     who = "ex_kvcache_forward"
     wl, wr = window_arg(who, window)
     cap = softcap_arg(who, softcap)
@@ -651,9 +692,15 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
             raise RuntimeError(f"{who}: {name} must be on q's device ({q.device}), got {t.device}")
         if t.dim() != 4:
             raise RuntimeError(f"{who}: {name} must be 4-D (B, N, H, d), got {tuple(t.shape)}")
-    if q.dtype not in (torch.float16, torch.bfloat16) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
-        raise RuntimeError(f"{who}: q, k_cache, v_cache must share a 16-bit dtype (float16 or bfloat16), got {q.dtype}, "
-                           f"{k_cache.dtype}, {v_cache.dtype}")
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.dtype in _FLOAT8_DTYPES and t.dtype != torch.float8_e4m3fn:
+            raise NotImplementedError(f"{who}: {name} of dtype {t.dtype} is not supported (an 8-bit cache is torch.float8_e4m3fn)")
+    e4m3 = k_cache.dtype == torch.float8_e4m3fn and v_cache.dtype == torch.float8_e4m3fn
+    if q.dtype not in (torch.float16, torch.bfloat16) or k_cache.dtype != v_cache.dtype or (not e4m3 and k_cache.dtype != q.dtype):
+        raise RuntimeError(f"{who}: q must have a 16-bit dtype (float16 or bfloat16) and k_cache, v_cache both q's dtype or both "
+                           f"torch.float8_e4m3fn, got {q.dtype}, {k_cache.dtype}, {v_cache.dtype}")
+    if not e4m3 and (k_descale is not None or v_descale is not None):
+        raise RuntimeError(f"{who}: k_descale / v_descale need a torch.float8_e4m3fn cache (the caches are {k_cache.dtype})")
     b, nq, hq, d = q.shape
     cap_len, hkv = k_cache.shape[1], k_cache.shape[2]
     for name, t, shape in (("block_table", block_table, "(B, max_blocks_per_seq)"), ("cache_batch_idx", cache_batch_idx, "(B,)"),
@@ -699,6 +746,26 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
             raise RuntimeError(f"{who}: rotary_cos / rotary_sin need k, v (the new tokens) and cache_seqlens")
     kvb, kvt = _kv_strides(who, "k_cache", k_cache, hkv, d, True)
     vvb, vvt = _kv_strides(who, "v_cache", v_cache, hkv, d, True)
+    kdp, kds, k_descale = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
+    vdp, vds, v_descale = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
+    if e4m3:
+        for name, t, bs_, ts_ in (("k_cache", k_cache, kvb, kvt), ("v_cache", v_cache, vvb, vvt)):
+            if bs_ % 8 != 0 or ts_ % 8 != 0 or t.data_ptr() % 8 != 0:
+                raise ValueError(f"{who}: an e4m3 {name} must be 8-byte aligned with batch and token strides that are multiples "
+                                 f"of 8 elements (got address % 8 = {t.data_ptr() % 8}, strides {tuple(t.stride())}); the cache "
+                                 f"is never copied")
+        if kdp and vdp and kds != vds:   # one batch stride serves both: give the (H_kv,) one B rows
+            if kds == 0:
+                k_descale = k_descale.expand(b, hkv).contiguous()
+                kdp, kds = k_descale.data_ptr(), hkv
+            elif vds == 0:
+                v_descale = v_descale.expand(b, hkv).contiguous()
+                vdp, vds = v_descale.data_ptr(), hkv
+            else:
+                v_descale = v_descale.contiguous()
+                k_descale = k_descale.contiguous()
+                kdp, kds, vdp, vds = k_descale.data_ptr(), hkv, v_descale.data_ptr(), hkv
+    dsc_bs = kds if kdp else vds
     nnew = 0
     knb = knt = vnb = vnt = 0
     if k_new is not None:
@@ -733,7 +800,7 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
                 v_new.data_ptr() if v_new is not None else 0, cache_seqlens.data_ptr() if cache_seqlens is not None else 0,
                 o.data_ptr(), lse.data_ptr(), b, hq, hkv, nq, nnew, cap_len, d, _DTYPE_CODE[q.dtype], qb, qt, kvb, kvt, vvb, vvt,
                 knb, knt, vnb, vnt, int(bool(causal)), wl, wr, scale, cap, aptr, astride, int(num_splits))
-        if block_table is None and cache_batch_idx is None and cache_leftpad is None and rotary_cos is None:
+        if not e4m3 and block_table is None and cache_batch_idx is None and cache_leftpad is None and rotary_cos is None:
             nbytes = int(_lib.fa_ex_kvcache_workspace_bytes(b, hq, hkv, nq, cap_len, d, int(num_splits)))
             ws = _workspace(q.device, nbytes) if nbytes > 0 else None
             _check(_lib.fa_ex_forward_kvcache(*head, ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device)))
@@ -752,7 +819,7 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
                 cache_leftpad = cache_leftpad.contiguous()
             middle = (*paged, cache_batch_idx.data_ptr() if cache_batch_idx is not None else 0,
                       units if cache_batch_idx is not None else 0, cache_leftpad.data_ptr() if cache_leftpad is not None else 0)
-            rotary = None
+            rotary = (0, 0, 0, 0, 0, 0, 0) if e4m3 else None
             if rotary_cos is not None:
                 tabs = []
                 for t in (rotary_cos, rotary_sin):   # rows at an even stride, 4-byte aligned: otherwise a dense copy
@@ -767,7 +834,9 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
             nbytes = int(_lib.fa_ex_kvcache_workspace_bytes(b, hq, hkv, nq, capacity, d, int(num_splits)))
             ws = _workspace(q.device, nbytes) if nbytes > 0 else None
             tail = (ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device))
-            if rotary is None:
+            if e4m3:
+                _check(_lib.fa_ex_forward_kvcache_fp8(*head, *middle, *rotary, _E4M3_CODE, kdp, vdp, dsc_bs, *tail))
+            elif rotary is None:
                 _check(_lib.fa_ex_forward_kvcache_paged(*head, *middle, *tail))
             else:
                 _check(_lib.fa_ex_forward_kvcache_rotary(*head, *middle, *rotary, *tail))

@@ -48,6 +48,7 @@ extern "C" {
 #define FA_DTYPE_F32 0
 #define FA_DTYPE_F16 1
 #define FA_DTYPE_BF16 2
+#define FA_DTYPE_E4M3 3 /* OCP e4m3 (float8_e4m3fn): only as cache_dtype of fa_ex_forward_kvcache_fp8 */
 
 /* Which implementation the dispatcher picks (fa_set_kernel_mode): AUTO = MFMA bf16/f16 kernels
  * when dtype is 16-bit and d is a multiple of 8 up to 256 (64 / 128 / 256 wide tiles, narrower rows zero-padded in the
@@ -417,6 +418,51 @@ int fa_ex_forward_kvcache_rotary(const void* q, void* k_cache, void* v_cache, co
                                  const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride,
                                  int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
                                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* fa_ex_forward_kvcache_rotary with a cache stored in 8 bits: k_cache and v_cache hold OCP e4m3 (float8_e4m3fn: 1 byte, finite
+ * max 448, no infinities) with a float32 dequantisation scale per (sequence, K/V head), as FlashAttention-3's k_descale / v_descale.
+ * cache_dtype = dtype with null scales and descale_batch_stride = 0 is fa_ex_forward_kvcache_rotary, bit for bit.  Everything not
+ * named here keeps its meaning; q, k_new, v_new, o and the rotary tables stay in dtype (f16 or bf16), lse and the workspace fp32.
+ *
+ * cache_dtype: dtype (a 16-bit cache, no scales) or FA_DTYPE_E4M3, for both caches.  The MI300X fnuz variant and e5m2 have no code.
+ * k_descale, v_descale: float32 device memory, read by the kernels only (no host read, no synchronisation: the call can still be
+ * captured in a graph).  The scale of K head h of sequence b is k_descale[b * descale_batch_stride + h]; stride 0 is the (heads_kv,)
+ * form, one row for every sequence.  b is the sequence of the call: cache_batch_idx and block_table do not move it.  A stored byte
+ * c stands for e4m3(c) * k_descale[b, h] (V: v_descale).  A null scale means 1.0.  Scales must be finite and > 0; not checked.
+ *
+ * Reading.  e4m3 -> f16 / bf16 is exact, so the split kernel widens K and V to dtype in registers and runs the 16-bit loop; q and
+ * the probabilities are not quantised.  The scales enter in fp32: the score is softmax_scale * k_descale[b, hk] * (q . k_stored),
+ * scaled before softcap and ALiBi, and v_descale[b, hk] multiplies the normalised output once, before its single rounding to dtype
+ * (one split) or before the fp32 partial is stored (more).  The result is that of fa_ex_forward_kvcache_rotary on the dequantised
+ * cache up to these two fp32 multiplies; lse is the logsumexp of the scaled, modified scores.
+ *
+ * Appending.  k_new is first rotated and rounded to dtype exactly as fa_ex_forward_kvcache_rotary does (when tables are given);
+ * v_new is taken as it is.  Each 16-bit value x then becomes a byte by
+ *     inv = 1.0f / descale (correctly rounded fp32);   y = clamp(float(x) * inv, -448, 448) in fp32;   byte = e4m3(y), nearest even.
+ * The clamp precedes the conversion, so values beyond the range store +-448 (0x7e / 0xfe) and a finite x never stores the NaN
+ * code; NaN input is unspecified.  The position clamp, the paged translation, dropped appends and cache_leftpad are unchanged.
+ *
+ * Strides of the e4m3 caches are in elements, which are bytes, and keep the multiple-of-8 rule; k_cache and v_cache must be 8-byte
+ * aligned (a chunk of 8 head dims is one 8-byte load or store), all other tensors 16-byte aligned as before.  The 2^31 limits are on
+ * bytes: a batch element or page of an e4m3 cache may span up to 2^31 - 1 elements, twice the tokens of a 16-bit one.
+ * Checked before any HIP call, besides fa_ex_forward_kvcache_rotary's list (FA_ERR_INVALID_ARGUMENT): cache_dtype neither dtype nor
+ * FA_DTYPE_E4M3; a scale or a non-zero descale_batch_stride with a 16-bit cache; descale_batch_stride negative, or non-zero and
+ * below heads_kv; a scale that is not 4-byte aligned; an e4m3 cache that is not 8-byte aligned.  The workspace is
+ * fa_ex_forward_kvcache's (fa_ex_kvcache_workspace_bytes does not depend on the cache's type). */
+int fa_ex_forward_kvcache_fp8(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                              const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                              int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
+                              int64_t q_token_stride, int64_t k_cache_batch_stride, int64_t k_cache_token_stride,
+                              int64_t v_cache_batch_stride, int64_t v_cache_token_stride, int64_t k_new_batch_stride,
+                              int64_t k_new_token_stride, int64_t v_new_batch_stride, int64_t v_new_token_stride, int causal,
+                              int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
+                              const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, const int32_t* block_table,
+                              int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq,
+                              const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad,
+                              const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride,
+                              int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
+                              int cache_dtype, const float* k_descale, const float* v_descale, int64_t descale_batch_stride,
+                              void* workspace, size_t workspace_bytes, void* stream);
 
 /* bytes of workspace a fa_ex_forward_kvcache call with these shapes and num_splits needs (0 for S = 1 and for invalid shapes) */
 size_t fa_ex_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t d,

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Time a KV-cache decode step (flashattention_lab_cuda.ex_kvcache_forward) against the same decode through ex_forward.
 
-    python tools/bench_kvcache.py [--d 128] [--dtype bf16] [--nq 1] [--page-size 16 --page-size 256] [--rotary] [--json out.json]
+    python tools/bench_kvcache.py [--d 128] [--dtype bf16] [--nq 1] [--page-size 16 --page-size 256] [--rotary] [--cache-dtype e4m3]
+                                  [--json out.json]
 
 Rows: B in {1, 8, 32}, H_q = 32, H_kv in {8, 32}, cache length in {1k, 8k, 32k, 128k}, plus one mixed-length batch.  The
 largest row (B = 32, 128k keys, H_kv = 32) holds 68 GB of cache and as much again in ex_forward's layout; --max-tokens drops
@@ -15,6 +16,9 @@ rows with B * len above it on smaller devices.  Each row reports the median time
             of the new key fused into the call; and the same step with q and k_new rotated by torch elementwise ops on the device
             in front of kv_app (checked against the fused call before it is timed),
 and the effective bandwidth of kv: bytes of K and V read (sum over b of len_b * H_kv * d * 2 * 2) / time, against 6.3 TB/s.
+--cache-dtype e4m3: the caches (and pools) are quantised once, outside the timed region, to torch.float8_e4m3fn with scales
+absmax / 448 per (b, head), and every kv / kv_app / paged / rotary call runs on them with k_descale / v_descale; the bytes of K
+and V are then 1 an element.  ex_forward and the unfused rotation keep the 16-bit tensors.
 Timing: HIP events around `--iters` back-to-back calls after `--warmup` calls; the median of `--reps` such groups."""
 import argparse
 import json
@@ -46,6 +50,19 @@ def timed(fn, warmup, iters, reps):
     return statistics.median(out)
 
 
+def quantise(x):
+    """(e4m3 tensor, float32 (B, H_kv) scales) of a (B, N, H_kv, d) 16-bit tensor: scale = absmax / 448 per (b, head); one batch
+    element at a time, so the fp32 copy stays small"""
+    out = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
+    scales = torch.empty((x.shape[0], x.shape[2]), dtype=torch.float32, device=x.device)
+    for bb in range(x.shape[0]):
+        xf = x[bb].float()
+        sc = (xf.abs().amax(dim=(0, 2)) / 448.0).clamp_min(2.0 ** -20)
+        out[bb] = (xf * (1.0 / sc).view(1, -1, 1)).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+        scales[bb] = sc
+    return out, scales
+
+
 def row(b, hq, hkv, lens, d, dtype, args):
     cap = max(lens)
     dev = "cuda"
@@ -56,8 +73,15 @@ def row(b, hq, hkv, lens, d, dtype, args):
     vn = torch.randn((b, 1, hkv, d), device=dev, dtype=dtype)
     sl = torch.tensor(lens, dtype=torch.int32, device=dev)
     sl1 = sl - 1
-    t_kv = timed(lambda: ext.ex_kvcache_forward(q, kc, vc, None, None, sl, True, None), args.warmup, args.iters, args.reps)
-    t_app = timed(lambda: ext.ex_kvcache_forward(q, kc, vc, kn, vn, sl1, True, None), args.warmup, args.iters, args.reps)
+    kc16, vc16, dsc = kc, vc, {}
+    if args.cache_dtype == "e4m3":
+        (kc, kd), (vc, vd) = quantise(kc16), quantise(vc16)
+        dsc = dict(k_descale=kd, v_descale=vd)
+        if len(set(lens)) != 1 or args.no_ex:
+            del kc16, vc16
+            kc16 = vc16 = None
+    t_kv = timed(lambda: ext.ex_kvcache_forward(q, kc, vc, None, None, sl, True, None, **dsc), args.warmup, args.iters, args.reps)
+    t_app = timed(lambda: ext.ex_kvcache_forward(q, kc, vc, kn, vn, sl1, True, None, **dsc), args.warmup, args.iters, args.reps)
     rot = {}
     if args.rotary:
         half = d // 2
@@ -73,10 +97,11 @@ def row(b, hq, hkv, lens, d, dtype, args):
 
         def unfused():
             pos = sl1.long().view(-1, 1)
-            return ext.ex_kvcache_forward(rotate(q, pos + qi), kc, vc, rotate(kn, pos), vn, sl1, True, None)
+            return ext.ex_kvcache_forward(rotate(q, pos + qi), kc, vc, rotate(kn, pos), vn, sl1, True, None, **dsc)
 
         def fused():
-            return ext.ex_kvcache_forward(q, kc, vc, kn, vn, sl1, True, None, rotary_cos=cos, rotary_sin=sin, rotary_interleaved=False)
+            return ext.ex_kvcache_forward(q, kc, vc, kn, vn, sl1, True, None, rotary_cos=cos, rotary_sin=sin, rotary_interleaved=False,
+                                          **dsc)
 
         torch.testing.assert_close(fused()[0].float(), unfused()[0].float(), rtol=2e-2, atol=2e-2)
         rot = dict(kv_app_rot_us=round(timed(fused, args.warmup, args.iters, args.reps), 2),
@@ -87,28 +112,30 @@ def row(b, hq, hkv, lens, d, dtype, args):
         mb = (cap + ps - 1) // ps
         g = torch.Generator(device="cpu").manual_seed(ps)
         table = torch.randperm(b * mb, generator=g).view(b, mb).to(torch.int32).to(dev)
-        kp = torch.empty((b * mb, ps, hkv, d), device=dev, dtype=dtype)
-        vp = torch.empty((b * mb, ps, hkv, d), device=dev, dtype=dtype)
+        kp = torch.empty((b * mb, ps, hkv, d), device=dev, dtype=kc.dtype)
+        vp = torch.empty((b * mb, ps, hkv, d), device=dev, dtype=vc.dtype)
         pad = mb * ps - cap
         for bb in range(b):   # the same tokens, page by page (the tail of a last partial page is never read)
             rows = table[bb].long()
-            kp[rows] = torch.nn.functional.pad(kc[bb], (0, 0, 0, 0, 0, pad)).view(mb, ps, hkv, d)
-            vp[rows] = torch.nn.functional.pad(vc[bb], (0, 0, 0, 0, 0, pad)).view(mb, ps, hkv, d)
-        o_c = ext.ex_kvcache_forward(q, kc, vc, None, None, sl, True, None)[0]
-        o_p = ext.ex_kvcache_forward(q, kp, vp, None, None, sl, True, None, block_table=table)[0]
+            kp.view(torch.uint8 if dsc else dtype)[rows] = torch.nn.functional.pad(
+                kc[bb].view(torch.uint8 if dsc else dtype), (0, 0, 0, 0, 0, pad)).view(mb, ps, hkv, d)
+            vp.view(torch.uint8 if dsc else dtype)[rows] = torch.nn.functional.pad(
+                vc[bb].view(torch.uint8 if dsc else dtype), (0, 0, 0, 0, 0, pad)).view(mb, ps, hkv, d)
+        o_c = ext.ex_kvcache_forward(q, kc, vc, None, None, sl, True, None, **dsc)[0]
+        o_p = ext.ex_kvcache_forward(q, kp, vp, None, None, sl, True, None, block_table=table, **dsc)[0]
         assert torch.equal(o_c, o_p), "paged and contiguous calls disagree"
-        paged[ps] = timed(lambda: ext.ex_kvcache_forward(q, kp, vp, None, None, sl, True, None, block_table=table),
+        paged[ps] = timed(lambda: ext.ex_kvcache_forward(q, kp, vp, None, None, sl, True, None, block_table=table, **dsc),
                           args.warmup, args.iters, args.reps)
         del kp, vp, table
     t_ex = None
     if len(set(lens)) == 1 and not args.no_ex:
         q3 = q.permute(0, 2, 1, 3).reshape(b * hq, args.nq, d).contiguous()
-        k3 = kc.permute(0, 2, 1, 3).reshape(b * hkv, cap, d).contiguous()
-        v3 = vc.permute(0, 2, 1, 3).reshape(b * hkv, cap, d).contiguous()
+        k3 = kc16.permute(0, 2, 1, 3).reshape(b * hkv, cap, d).contiguous()
+        v3 = vc16.permute(0, 2, 1, 3).reshape(b * hkv, cap, d).contiguous()
         t_ex = timed(lambda: ext.ex_forward(q3, k3, v3, True, d ** -0.5), args.warmup, args.iters, args.reps)
         del q3, k3, v3
-    kv_bytes = sum(lens) * hkv * d * 2 * 2
-    r = dict(B=b, Hq=hq, Hkv=hkv, len=lens[0] if len(set(lens)) == 1 else "mixed", lens=None if len(set(lens)) == 1 else lens,
+    kv_bytes = sum(lens) * hkv * d * 2 * (1 if dsc else 2)
+    r = dict(cache_dtype=args.cache_dtype, B=b, Hq=hq, Hkv=hkv, len=lens[0] if len(set(lens)) == 1 else "mixed", lens=None if len(set(lens)) == 1 else lens,
              kv_us=round(t_kv, 2), kv_append_us=round(t_app, 2), ex_forward_us=None if t_ex is None else round(t_ex, 2),
              speedup=None if t_ex is None else round(t_ex / t_kv, 2), kv_TBps=round(kv_bytes / t_kv / 1e6, 3),
              frac_copy_rate=round(kv_bytes / t_kv / 1e6 / (COPY_RATE / 1e12), 3))
@@ -117,7 +144,7 @@ def row(b, hq, hkv, lens, d, dtype, args):
         r[f"paged_{ps}_us"] = round(t, 2)
         r[f"paged_{ps}_TBps"] = round(kv_bytes / t / 1e6, 3)
         r[f"paged_{ps}_vs_kv"] = round(t / t_kv, 3)
-    del q, kc, vc, kn, vn
+    del q, kc, vc, kc16, vc16, kn, vn
     torch.cuda.empty_cache()
     return r
 
@@ -134,6 +161,8 @@ def main():
     ap.add_argument("--page-size", type=int, action="append", default=[], help="also time the paged call with this page size (repeatable)")
     ap.add_argument("--no-ex", action="store_true", help="skip the ex_forward column")
     ap.add_argument("--rotary", action="store_true", help="also time the append with fused rotary embedding, and with torch rotating first")
+    ap.add_argument("--cache-dtype", default="16", choices=("16", "e4m3"),
+                    help="16: the caches in --dtype; e4m3: quantised once to float8_e4m3fn with per-(b, head) scales")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16
@@ -159,7 +188,8 @@ def main():
     print(json.dumps(rows[-1]), flush=True)
     if args.json:
         with open(args.json, "w") as f:
-            json.dump(dict(d=args.d, dtype=args.dtype, nq=args.nq, page_sizes=args.page_size, rotary=args.rotary, copy_rate_TBps=COPY_RATE / 1e12, rows=rows), f, indent=1)
+            json.dump(dict(d=args.d, dtype=args.dtype, nq=args.nq, page_sizes=args.page_size, rotary=args.rotary, cache_dtype=args.cache_dtype,
+                           copy_rate_TBps=COPY_RATE / 1e12, rows=rows), f, indent=1)
 
 
 if __name__ == "__main__":
