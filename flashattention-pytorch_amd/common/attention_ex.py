@@ -5,7 +5,7 @@ extended entry points (`fa_ex_forward` / `fa_ex_backward`, include/fa_mi355x.h):
 
     flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, block_size=128,
                        causal=False, dropout_p=0.0, seed=0, softmax_scale=None, window_size=(-1, -1),
-                       softcap=0.0, alibi_slopes=None) -> o
+                       softcap=0.0, alibi_slopes=None, sinks=None) -> o
 
 q: (B, H, Nq, d) or (BH, Nq, d); k, v: (B, H_kv, Nk, d) or (B*H_kv, Nk, d).  H_kv < H is grouped-query attention (GQA; H_kv = 1:
 multi-query attention) with H % H_kv == 0: query head h reads K/V head h // (H / H_kv), with no copy of K and V, and the
@@ -19,7 +19,11 @@ other argument (GQA K/V included), and the kernels visit only the tiles of each 
 that bounds nothing is the call without one, bit for bit.  `softcap` > 0 (Gemma-2 style) replaces each score s = scale q.k by
 softcap * tanh(s / softcap), and `alibi_slopes` (float32 (H,) or (B, H) for 4-D q, (BH,) for 3-D q; BLOOM / MPT style) then
 subtracts slope * |i + Nk - Nq - j|, FlashAttention-2's arguments of the same names; the slopes get no gradient
-(fa_ex_forward_scoremod).  softcap = 0 without slopes is the call without them, bit for bit.  Differentiable (autograd Function; the backward recomputes P and
+(fa_ex_forward_scoremod).  softcap = 0 without slopes is the call without them, bit for bit.  `sinks` (float32 (H,) for 4-D q,
+(sink_heads,) with sink_heads dividing BH for 3-D q: unit u takes sinks[u % sink_heads]) are attention sinks (gpt-oss): one learnable
+logit per head that joins each row's softmax as an extra column with a zero value vector, in the units of the final logit, never
+capped, biased, masked or dropped; -inf switches a head's sink off.  `sinks` receives a float32 gradient (a bf16 parameter is passed
+as `p.float()` and gets its gradient through the cast).  Differentiable (autograd Function; the backward recomputes P and
 regenerates the dropout mask from the seed).  No CPU path: the tensors must live on the GPU.
 """
 from __future__ import annotations
@@ -64,21 +68,33 @@ def normalize_mask(mask, lead, nq, nk):
 
 class _FlashAttnExFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale, mask, block_mask, br, bc, dropout_p, seed, window, softcap=0.0, alibi_slopes=None):
+    def forward(ctx, q, k, v, causal, scale, mask, block_mask, br, bc, dropout_p, seed, window, softcap=0.0, alibi_slopes=None,
+                sinks=None):
         import flashattention_lab_cuda as ext
 
+        ctx.args = (causal, scale, mask, block_mask, br, bc, dropout_p, seed, window, softcap, alibi_slopes)
+        ctx.with_sinks = sinks is not None
+        if sinks is not None:
+            o, lse = ext.ex_forward(q, k, v, causal, scale, mask, block_mask, br, bc, dropout_p, seed, window=window, softcap=softcap,
+                                    alibi_slopes=alibi_slopes, sinks=sinks)
+            ctx.save_for_backward(q, k, v, o, lse, sinks)
+            return o
         o, lse = ext.ex_forward(q, k, v, causal, scale, mask, block_mask, br, bc, dropout_p, seed, window=window, softcap=softcap,
                                 alibi_slopes=alibi_slopes)
         ctx.save_for_backward(q, k, v, o, lse)
-        ctx.args = (causal, scale, mask, block_mask, br, bc, dropout_p, seed, window, softcap, alibi_slopes)
         return o
 
     @staticmethod
     def backward(ctx, do):
         import flashattention_lab_cuda as ext
 
-        q, k, v, o, lse = ctx.saved_tensors
         causal, scale, mask, block_mask, br, bc, dropout_p, seed, window, softcap, alibi_slopes = ctx.args
+        if ctx.with_sinks:
+            q, k, v, o, lse, sinks = ctx.saved_tensors
+            dq, dk, dv, dsinks = ext.ex_backward(q, k, v, o, do.contiguous(), lse, causal, scale, mask, block_mask, br, bc, dropout_p,
+                                                 seed, window=window, softcap=softcap, alibi_slopes=alibi_slopes, sinks=sinks)
+            return (dq, dk, dv) + (None,) * 11 + (dsinks,)
+        q, k, v, o, lse = ctx.saved_tensors
         dq, dk, dv = ext.ex_backward(q, k, v, o, do.contiguous(), lse, causal, scale, mask, block_mask, br, bc, dropout_p, seed,
                                      window=window, softcap=softcap, alibi_slopes=alibi_slopes)
         return (dq, dk, dv) + (None,) * 11   # (no gradient for the slopes, as in FlashAttention-2)
@@ -110,8 +126,17 @@ def _alibi_units(slopes, lead):
     raise RuntimeError(f"flash_attention_ex: alibi_slopes must be ({lead[1]},) or {tuple(lead)}, got {tuple(slopes.shape)}")
 
 
+def _sinks_units(who, sinks, heads):
+    """`sinks` for a call whose query heads are known (4-D q, varlen): float32 (heads,); the library checks the rest."""
+    if not isinstance(sinks, torch.Tensor) or sinks.dtype != torch.float32:
+        raise RuntimeError(f"{who}: sinks must be a float32 tensor (pass a 16-bit parameter as p.float())")
+    if tuple(sinks.shape) != (heads,):
+        raise RuntimeError(f"{who}: sinks must be ({heads},), got {tuple(sinks.shape)}")
+    return sinks.contiguous()
+
+
 def flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, block_size=128, causal=False, dropout_p=0.0,
-                       seed=0, softmax_scale=None, window_size=(-1, -1), softcap=0.0, alibi_slopes=None):
+                       seed=0, softmax_scale=None, window_size=(-1, -1), softcap=0.0, alibi_slopes=None, sinks=None):
     window = _window_size(window_size)
     if not q.is_cuda:
         raise RuntimeError("Inputs must be CUDA tensors")   # as the reference's wrappers (src/fa2/cuda/impl.py:44)
@@ -135,7 +160,14 @@ def flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, bloc
     if block_sparse_mask is not None:
         br, bc = min(br, nq), min(bc, nk)         # Br = min(block_size, q_len), Bc = min(block_size, kv_len)  (:100-101)
     slopes = _alibi_units(alibi_slopes, tuple(q.shape[:-2]))
-    if softcap == 0.0 and slopes is None:   # (the call without modifiers, as before they existed)
+    if sinks is not None:
+        if four_d:
+            sinks = _sinks_units("flash_attention_ex", sinks, h)
+        elif not isinstance(sinks, torch.Tensor) or sinks.dtype != torch.float32:
+            raise RuntimeError("flash_attention_ex: sinks must be a float32 tensor (pass a 16-bit parameter as p.float())")
+        o = _FlashAttnExFn.apply(q3, k3, v3, bool(causal), scale, m, block_sparse_mask, br, bc, float(dropout_p), int(seed), window,
+                                 softcap, slopes, sinks)
+    elif softcap == 0.0 and slopes is None:   # (the call without modifiers, as before they existed)
         o = _FlashAttnExFn.apply(q3, k3, v3, bool(causal), scale, m, block_sparse_mask, br, bc, float(dropout_p), int(seed), window)
     else:
         o = _FlashAttnExFn.apply(q3, k3, v3, bool(causal), scale, m, block_sparse_mask, br, bc, float(dropout_p), int(seed), window,
@@ -145,9 +177,17 @@ def flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, bloc
 
 class _FlashAttnVarlenFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, cu_q, cu_k, max_q, max_k, dropout_p, scale, causal, window, seed, softcap=0.0, alibi_slopes=None):
+    def forward(ctx, q, k, v, cu_q, cu_k, max_q, max_k, dropout_p, scale, causal, window, seed, softcap=0.0, alibi_slopes=None,
+                sinks=None):
         import flashattention_lab_cuda as ext
 
+        ctx.with_sinks = sinks is not None
+        if sinks is not None:
+            o, lse = ext.ex_varlen_forward(q, k, v, cu_q, cu_k, max_q, max_k, causal, scale, dropout_p, seed, window=window,
+                                           softcap=softcap, alibi_slopes=alibi_slopes, sinks=sinks)
+            ctx.save_for_backward(q, k, v, o, lse, cu_q, cu_k, sinks)
+            ctx.args = (max_q, max_k, dropout_p, scale, causal, window, seed, softcap, alibi_slopes)
+            return o
         o, lse = ext.ex_varlen_forward(q, k, v, cu_q, cu_k, max_q, max_k, causal, scale, dropout_p, seed, window=window, softcap=softcap,
                                        alibi_slopes=alibi_slopes)
         ctx.save_for_backward(q, k, v, o, lse, cu_q, cu_k)
@@ -158,39 +198,48 @@ class _FlashAttnVarlenFn(torch.autograd.Function):
     def backward(ctx, do):
         import flashattention_lab_cuda as ext
 
-        q, k, v, o, lse, cu_q, cu_k = ctx.saved_tensors
         max_q, max_k, dropout_p, scale, causal, window, seed, softcap, alibi_slopes = ctx.args
+        if ctx.with_sinks:
+            q, k, v, o, lse, cu_q, cu_k, sinks = ctx.saved_tensors
+            dq, dk, dv, dsinks = ext.ex_varlen_backward(q, k, v, o, do.contiguous(), lse, cu_q, cu_k, max_q, max_k, causal, scale,
+                                                        dropout_p, seed, window=window, softcap=softcap, alibi_slopes=alibi_slopes,
+                                                        sinks=sinks)
+            return (dq, dk, dv) + (None,) * 11 + (dsinks,)
+        q, k, v, o, lse, cu_q, cu_k = ctx.saved_tensors
         dq, dk, dv = ext.ex_varlen_backward(q, k, v, o, do.contiguous(), lse, cu_q, cu_k, max_q, max_k, causal, scale, dropout_p, seed,
                                             window=window, softcap=softcap, alibi_slopes=alibi_slopes)
         return (dq, dk, dv) + (None,) * 11
 
 
 def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p=0.0, softmax_scale=None,
-                           causal=False, window_size=(-1, -1), seed=0, softcap=0.0, alibi_slopes=None):
+                           causal=False, window_size=(-1, -1), seed=0, softcap=0.0, alibi_slopes=None, sinks=None):
     """FlashAttention-2's flash_attn_varlen_func over packed sequences, differentiable: q (total_q, H_q, d), k and v
     (total_k, H_kv, d) with H_q % H_kv == 0 (GQA), token-strided views (qkv.unbind(1) of a (total, 3, H, d) projection) taken
     without a copy; cu_seqlens_* int32 (batch + 1,) device offsets.  Attention stays inside each sequence; `causal` is
     bottom-right aligned per sequence and `window_size` has flash_attention_ex's meaning in each sequence's coordinates.
     Returns o (total_q, H_q, d); the gradients of k and v come back in their shapes.  The dropout mask is that of the padded
     (batch * H_q, max_seqlen_q, max_seqlen_k) call (include/fa_mi355x.h), so it depends on the max_seqlen_q passed.  softcap and
-    alibi_slopes (float32 (H_q,) or (batch, H_q)) as in flash_attention_ex, in each sequence's coordinates."""
+    alibi_slopes (float32 (H_q,) or (batch, H_q)) as in flash_attention_ex, in each sequence's coordinates.  sinks: float32 (H_q,)
+    attention sinks as in flash_attention_ex, differentiable."""
     window = _window_size(window_size)
     if not q.is_cuda:
         raise RuntimeError("Inputs must be CUDA tensors")
     scale = (1.0 / math.sqrt(q.shape[-1])) if softmax_scale is None else float(softmax_scale)
     args = (q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), float(dropout_p), scale, bool(causal), window,
             int(seed))
-    if softcap == 0.0 and alibi_slopes is None:
+    if softcap == 0.0 and alibi_slopes is None and sinks is None:
         return _FlashAttnVarlenFn.apply(*args)
     if isinstance(alibi_slopes, torch.Tensor):
         alibi_slopes = alibi_slopes.detach()
-    return _FlashAttnVarlenFn.apply(*args, softcap, alibi_slopes)
+    if sinks is None:
+        return _FlashAttnVarlenFn.apply(*args, softcap, alibi_slopes)
+    return _FlashAttnVarlenFn.apply(*args, softcap, alibi_slopes, _sinks_units("flash_attention_varlen", sinks, q.shape[1]))
 
 
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_sin=None, cache_seqlens=None,
                             cache_batch_idx=None, cache_leftpad=None, block_table=None, softmax_scale=None, causal=False,
                             window_size=(-1, -1), softcap=0.0, rotary_interleaved=True, alibi_slopes=None, num_splits=0,
-                            return_softmax_lse=False, k_descale=None, v_descale=None):
+                            return_softmax_lse=False, *, sinks=None, k_descale=None, v_descale=None):
     """FlashAttention-2's flash_attn_with_kvcache (forward; its argument order): q (B, Nq, H_q, d); k_cache, v_cache
     (B, cache_len, H_kv, d) with H_q % H_kv == 0, updated in place — k, v (B, N_new, H_kv, d) are written at
     cache_seqlens[b] .. + N_new before attention, and a cache view the library cannot take without a copy raises ValueError.
@@ -211,6 +260,8 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     cache, with float32 dequantisation scales of shape (B, H_kv) or (H_kv,) on the device (None: 1.0; finite and > 0): a stored
     value c of K head h of sequence b stands for c * k_descale[b, h].  q, k, v and the result stay 16-bit; k and v are quantised
     as they are appended (after the rotation), with saturation at +-448.  Other 8-bit dtypes raise NotImplementedError.
+    sinks (keyword-only, as k_descale and v_descale now are: FlashAttention-2's positional order ends before them): float32 (H_q,) attention sinks on q's device, one extra softmax column per query head with a zero value
+    (flash_attention_ex); the returned lse contains it, and a sequence without any key gives o = 0, lse = sink.
     Returns o (B, Nq, H_q, d), and with return_softmax_lse also lse (B, H_q, Nq) float32.  No gradient."""
     for name, val in (("block_table", block_table), ("cache_batch_idx", cache_batch_idx), ("cache_leftpad", cache_leftpad)):
         if val is not None and not (isinstance(val, torch.Tensor) and val.dtype == torch.int32):
@@ -228,12 +279,13 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
 
     if isinstance(alibi_slopes, torch.Tensor):
         alibi_slopes = alibi_slopes.detach()
+    extra = {} if sinks is None else {"sinks": sinks.detach() if isinstance(sinks, torch.Tensor) else sinks}
     with torch.no_grad():
         o, lse = ext.ex_kvcache_forward(q.detach(), k_cache, v_cache, None if k is None else k.detach(),
                                         None if v is None else v.detach(), cache_seqlens, bool(causal), softmax_scale,
                                         _window_size(window_size), softcap, alibi_slopes, num_splits, block_table, cache_batch_idx,
                                         cache_leftpad, None if rotary_cos is None else rotary_cos.detach(),
                                         None if rotary_sin is None else rotary_sin.detach(), bool(rotary_interleaved),
-                                        None if k_descale is None else k_descale.detach(),
-                                        None if v_descale is None else v_descale.detach())
+                                        k_descale=None if k_descale is None else k_descale.detach(),
+                                        v_descale=None if v_descale is None else v_descale.detach(), **extra)
     return (o, lse) if return_softmax_lse else o

@@ -397,21 +397,50 @@ static void score_args(fa::ExArgs& a, const ScoreMod& m) {
     a.alibi_bstride = m.bstride;
 }
 
+// attention sinks (fa_ex_*_sink): one learnable logit per head as an extra softmax column; the default is none.  sinks == null is
+// the call without them and nothing else of the struct is read.
+struct SinkArg {
+    const float* sinks = nullptr;
+    int64_t heads = 1;
+    float* dsinks = nullptr;   // backward: (heads,) float32
+};
+// units: the query units u (unit u takes sinks[u % heads]); backward: the call writes dsinks
+static int sink_check(const char* who, const SinkArg& sk, int64_t units, bool backward) {
+    if (!sk.sinks) return FA_OK;
+    if ((uintptr_t)sk.sinks % 4 != 0 || (uintptr_t)sk.dsinks % 4 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: sinks and dsinks must be 4-byte aligned", who);
+    if (sk.heads < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: sink_heads must be >= 1 (got %lld)", who, (long long)sk.heads);
+    if (units % sk.heads != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: sink_heads=%lld does not divide the %lld query units", who, (long long)sk.heads,
+                    (long long)units);
+    if (sk.heads >= ((int64_t)1 << 31)) return fail(FA_ERR_UNSUPPORTED, "%s: sink_heads too large", who);
+    if (backward && !sk.dsinks) return fail(FA_ERR_INVALID_ARGUMENT, "%s: sinks without dsinks", who);
+    return FA_OK;
+}
+static void sink_args(fa::ExArgs& a, const SinkArg& sk) {
+    a.sinks = sk.sinks;
+    a.sink_heads = sk.sinks ? sk.heads : 1;
+    a.dsinks = sk.dsinks;
+}
+
 static int ex_forward_impl(const char* who, const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t kv_group,
                            int64_t nq, int64_t nk, int64_t d, int dtype, int causal, int64_t wl, int64_t wr, double softmax_scale,
                            const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc,
-                           double dropout_p, uint64_t dropout_seed, void* stream, const ScoreMod& sm = ScoreMod()) {
+                           double dropout_p, uint64_t dropout_seed, void* stream, const ScoreMod& sm = ScoreMod(),
+                           const SinkArg& sk = SinkArg()) {
     int rc = ex_check(who, bh, nq, nk, d, dtype, softmax_scale, block_mask, br, bc, dropout_p);
     if (rc != FA_OK) return rc;
     if ((rc = group_check(who, bh, kv_group)) != FA_OK) return rc;
     if ((rc = score_check(who, sm, bh)) != FA_OK) return rc;
+    if ((rc = sink_check(who, sk, bh, false)) != FA_OK) return rc;
     if ((rc = window_canon(who, nq, nk, causal, wl, wr)) != FA_OK) return rc;
     if (bh == 0 || nq == 0) return FA_OK;
     if (!q || !o || !lse || (nk > 0 && (!k || !v))) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
-    if (nk == 0) {   // no key at all: every row is a row without a visible key, o = 0 and lse = -inf
+    if (nk == 0) {   // no key at all: every row is a row without a visible key, o = 0 and lse = -inf; the sink with sinks
         hipStream_t st = reinterpret_cast<hipStream_t>(stream);
         hipError_t e = hipMemsetAsync(o, 0, (size_t)bh * nq * d * (dtype == FA_DTYPE_F32 ? 4 : 2), st);
-        if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lse), (int)0xFF800000u, (size_t)bh * nq, st);
+        if (e == hipSuccess && sk.sinks) e = fa::launch_ex_sink_fill(lse, sk.sinks, sk.heads, bh, nq, st);
+        else if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lse), (int)0xFF800000u, (size_t)bh * nq, st);
         if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
         return FA_OK;
     }
@@ -421,6 +450,7 @@ static int ex_forward_impl(const char* who, const void* q, const void* k, const 
     a.window_left = wl;
     a.window_right = wr;
     score_args(a, sm);
+    sink_args(a, sk);
     hipError_t e = fa::launch_ex(a, false, reinterpret_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
     return FA_OK;
@@ -432,12 +462,17 @@ static int ex_backward_impl(const char* who, const void* q, const void* k, const
                             void* dq, void* dk, void* dv, int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype,
                             int causal, int64_t wl, int64_t wr, double softmax_scale, const uint8_t* mask, int64_t mask_bh_stride,
                             const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* workspace,
-                            size_t workspace_bytes, void* stream, const ScoreMod& sm = ScoreMod()) {
+                            size_t workspace_bytes, void* stream, const ScoreMod& sm = ScoreMod(), const SinkArg& sk = SinkArg()) {
     int rc = ex_check(who, bh, nq, nk, d, dtype, softmax_scale, block_mask, br, bc, dropout_p);
     if (rc != FA_OK) return rc;
     if ((rc = group_check(who, bh, kv_group)) != FA_OK) return rc;
     if ((rc = score_check(who, sm, bh)) != FA_OK) return rc;
+    if ((rc = sink_check(who, sk, bh, true)) != FA_OK) return rc;
     if ((rc = window_canon(who, nq, nk, causal, wl, wr)) != FA_OK) return rc;
+    if (sk.sinks && (bh == 0 || nq == 0 || nk == 0)) {   // no row, or rows with o = 0 (delta = 0): the sink's gradient is 0
+        hipError_t e = hipMemsetAsync(sk.dsinks, 0, (size_t)sk.heads * 4, reinterpret_cast<hipStream_t>(stream));
+        if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
+    }
     if (bh == 0 || (nq == 0 && nk == 0)) return FA_OK;
     if (nq == 0 || nk == 0) {   // one side empty: the gradients of the other side are sums over nothing
         const size_t es = dtype == FA_DTYPE_F32 ? 4 : 2;
@@ -464,6 +499,7 @@ static int ex_backward_impl(const char* who, const void* q, const void* k, const
     a.window_left = wl;
     a.window_right = wr;
     score_args(a, sm);
+    sink_args(a, sk);
     hipError_t e = fa::launch_ex(a, true, reinterpret_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
     return FA_OK;
@@ -558,6 +594,34 @@ int fa_ex_backward_scoremod(const void* q, const void* k, const void* v, const v
                             workspace, workspace_bytes, stream, sm);
 }
 
+int fa_ex_forward_sink(const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t kv_group, int64_t nq,
+                       int64_t nk, int64_t d, int dtype, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                       double softcap, const float* alibi_slopes, int64_t alibi_heads, int64_t alibi_batch_stride, const float* sinks,
+                       int64_t sink_heads, const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc,
+                       double dropout_p, uint64_t dropout_seed, void* stream) {
+    ScoreMod sm;
+    sm.softcap = softcap; sm.alibi = alibi_slopes; sm.heads = alibi_heads; sm.bstride = alibi_batch_stride;
+    SinkArg sk;
+    sk.sinks = sinks; sk.heads = sink_heads;
+    return ex_forward_impl("fa_ex_forward_sink", q, k, v, o, lse, bh, kv_group, nq, nk, d, dtype, causal, window_left, window_right,
+                           softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, stream, sm, sk);
+}
+
+int fa_ex_backward_sink(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
+                        void* dv, int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype, int causal,
+                        int64_t window_left, int64_t window_right, double softmax_scale, double softcap, const float* alibi_slopes,
+                        int64_t alibi_heads, int64_t alibi_batch_stride, const float* sinks, int64_t sink_heads, float* dsinks,
+                        const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p,
+                        uint64_t dropout_seed, void* workspace, size_t workspace_bytes, void* stream) {
+    ScoreMod sm;
+    sm.softcap = softcap; sm.alibi = alibi_slopes; sm.heads = alibi_heads; sm.bstride = alibi_batch_stride;
+    SinkArg sk;
+    sk.sinks = sinks; sk.heads = sink_heads; sk.dsinks = dsinks;
+    return ex_backward_impl("fa_ex_backward_sink", q, k, v, o, do_, lse, dq, dk, dv, bh, kv_group, nq, nk, d, dtype, causal, window_left,
+                            window_right, softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, workspace,
+                            workspace_bytes, stream, sm, sk);
+}
+
 // ---- variable-length (packed) sequences: see include/fa_mi355x.h
 // Everything that can be checked without reading cu_seqlens (which would take a synchronise), before any HIP call.
 static int varlen_check(const char* who, const int32_t* cu_q, const int32_t* cu_k, int64_t batch, int64_t hq, int64_t hkv, int64_t total_q,
@@ -614,18 +678,21 @@ static int varlen_forward_impl(const char* who, const void* q, const void* k, co
                                const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
                                int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
                                int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
-                               double softmax_scale, double dropout_p, uint64_t dropout_seed, void* stream, const ScoreMod& sm) {
+                               double softmax_scale, double dropout_p, uint64_t dropout_seed, void* stream, const ScoreMod& sm,
+                               const SinkArg& sk = SinkArg()) {
     int rc = varlen_check(who, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype,
                           q_stride, k_stride, v_stride, window_left, window_right, softmax_scale, dropout_p);
     if (rc != FA_OK) return rc;
     if (heads_q >= 1 && (rc = score_check(who, sm, batch * heads_q)) != FA_OK) return rc;
+    if ((rc = sink_check(who, sk, heads_q, false)) != FA_OK) return rc;   // (indexed by query head)
     if ((rc = window_canon(who, max_seqlen_q, max_seqlen_k, causal, window_left, window_right)) != FA_OK) return rc;
     if (total_q == 0 || max_seqlen_q == 0) return FA_OK;   // no query row in any sequence
     if (!q || !o || !lse || (total_k > 0 && (!k || !v))) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (total_k == 0 || max_seqlen_k == 0) {   // no key in any sequence: o = 0, lse = -inf
+    if (total_k == 0 || max_seqlen_k == 0) {   // no key in any sequence: o = 0, lse = -inf (with sinks: the head's sink)
         hipError_t e = hipMemsetAsync(o, 0, (size_t)total_q * heads_q * d * (dtype == FA_DTYPE_F32 ? 4 : 2), st);
-        if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lse), (int)0xFF800000u, (size_t)heads_q * total_q, st);
+        if (e == hipSuccess && sk.sinks) e = fa::launch_ex_sink_fill(lse, sk.sinks, sk.heads, heads_q, total_q, st);
+        else if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lse), (int)0xFF800000u, (size_t)heads_q * total_q, st);
         if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
         return FA_OK;
     }
@@ -633,6 +700,7 @@ static int varlen_forward_impl(const char* who, const void* q, const void* k, co
                                q_stride, k_stride, v_stride, causal, window_left, window_right, softmax_scale, dropout_p, dropout_seed);
     a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse;
     score_args(a, sm);
+    sink_args(a, sk);
     hipError_t e = fa::launch_ex(a, false, st);
     if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
     return FA_OK;
@@ -673,13 +741,19 @@ static int varlen_backward_impl(const char* who, const void* q, const void* k, c
                                 int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q,
                                 int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride, int causal,
                                 int64_t window_left, int64_t window_right, double softmax_scale, double dropout_p, uint64_t dropout_seed,
-                                void* workspace, size_t workspace_bytes, void* stream, const ScoreMod& sm) {
+                                void* workspace, size_t workspace_bytes, void* stream, const ScoreMod& sm,
+                                const SinkArg& sk = SinkArg()) {
     int rc = varlen_check(who, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype,
                           q_stride, k_stride, v_stride, window_left, window_right, softmax_scale, dropout_p);
     if (rc != FA_OK) return rc;
     if (heads_q >= 1 && (rc = score_check(who, sm, batch * heads_q)) != FA_OK) return rc;
+    if ((rc = sink_check(who, sk, heads_q, true)) != FA_OK) return rc;
     if ((rc = window_canon(who, max_seqlen_q, max_seqlen_k, causal, window_left, window_right)) != FA_OK) return rc;
     const bool no_q = total_q == 0 || max_seqlen_q == 0, no_k = total_k == 0 || max_seqlen_k == 0;
+    if (sk.sinks && (no_q || no_k)) {   // no row, or rows with o = 0 (delta = 0): the sink's gradient is 0
+        hipError_t e = hipMemsetAsync(sk.dsinks, 0, (size_t)sk.heads * 4, reinterpret_cast<hipStream_t>(stream));
+        if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
+    }
     if (no_q && no_k) return FA_OK;
     if (no_q || no_k) {   // one side empty in every sequence: the gradients of the other side are sums over nothing
         const size_t es = dtype == FA_DTYPE_F32 ? 4 : 2;
@@ -707,6 +781,7 @@ static int varlen_backward_impl(const char* who, const void* q, const void* k, c
     a.workspace = workspace;
     a.workspace_bytes = workspace_bytes;
     score_args(a, sm);
+    sink_args(a, sk);
     hipError_t e = fa::launch_ex(a, true, reinterpret_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
     return FA_OK;
@@ -739,6 +814,39 @@ int fa_ex_backward_varlen_scoremod(const void* q, const void* k, const void* v, 
                                 stream, sm);
 }
 
+int fa_ex_forward_varlen_sink(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
+                              const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
+                              int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
+                              int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
+                              double softmax_scale, double softcap, const float* alibi_slopes, int64_t alibi_batch_stride,
+                              const float* sinks, int64_t sink_heads, double dropout_p, uint64_t dropout_seed, void* stream) {
+    ScoreMod sm;
+    sm.softcap = softcap; sm.alibi = alibi_slopes; sm.heads = heads_q; sm.bstride = alibi_batch_stride;
+    SinkArg sk;
+    sk.sinks = sinks; sk.heads = sink_heads;
+    return varlen_forward_impl("fa_ex_forward_varlen_sink", q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q,
+                               total_k, max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride, causal, window_left,
+                               window_right, softmax_scale, dropout_p, dropout_seed, stream, sm, sk);
+}
+
+int fa_ex_backward_varlen_sink(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq,
+                               void* dk, void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch,
+                               int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q,
+                               int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                               int causal, int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
+                               const float* alibi_slopes, int64_t alibi_batch_stride, const float* sinks, int64_t sink_heads,
+                               float* dsinks, double dropout_p, uint64_t dropout_seed, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    ScoreMod sm;
+    sm.softcap = softcap; sm.alibi = alibi_slopes; sm.heads = heads_q; sm.bstride = alibi_batch_stride;
+    SinkArg sk;
+    sk.sinks = sinks; sk.heads = sink_heads; sk.dsinks = dsinks;
+    return varlen_backward_impl("fa_ex_backward_varlen_sink", q, k, v, o, do_, lse, dq, dk, dv, cu_seqlens_q, cu_seqlens_k, batch, heads_q,
+                                heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride, causal,
+                                window_left, window_right, softmax_scale, dropout_p, dropout_seed, workspace, workspace_bytes, stream, sm,
+                                sk);
+}
+
 // ---- KV-cache decoding with split-KV: see include/fa_mi355x.h
 static int64_t kv_splits(int64_t batch, int64_t hq, int64_t hkv, int64_t nq, int64_t cache_len, int64_t num_splits) {
     if (num_splits > 0) return num_splits;
@@ -753,9 +861,20 @@ size_t fa_ex_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t hea
     return fa::kv_workspace_bytes(batch, heads_q, seqlen_q, d, (int)kv_splits(batch, heads_q, heads_kv, seqlen_q, cache_len, num_splits));
 }
 
+// a sink call always runs the combine: at least two splits
+size_t fa_ex_kvcache_workspace_bytes_sink(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t d,
+                                          int64_t num_splits) {
+    if (batch <= 0 || heads_q <= 0 || heads_kv <= 0 || heads_q % heads_kv != 0 || seqlen_q <= 0 || d <= 0 || cache_len < 0 ||
+        num_splits < 0 || num_splits > 256)
+        return 0;
+    const int64_t S = kv_splits(batch, heads_q, heads_kv, seqlen_q, cache_len, num_splits);
+    return fa::kv_workspace_bytes(batch, heads_q, seqlen_q, d, (int)(S < 2 ? 2 : S));
+}
+
 // who: the entry point's name.  After stream come the eight arguments fa_ex_forward_kvcache_paged adds (all null / 0 is
 // fa_ex_forward_kvcache), then the seven fa_ex_forward_kvcache_rotary adds (all null / 0 is fa_ex_forward_kvcache_paged), then the
-// four fa_ex_forward_kvcache_fp8 adds (cache_dtype = dtype, null, null, 0 is fa_ex_forward_kvcache_rotary).
+// four fa_ex_forward_kvcache_fp8 adds (cache_dtype = dtype, null, null, 0 is fa_ex_forward_kvcache_rotary), then the two
+// fa_ex_forward_kvcache_sink adds (null sinks is fa_ex_forward_kvcache_fp8).
 static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
                         const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
                         int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
@@ -768,7 +887,7 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
                         int64_t cache_batch, const int32_t* cache_leftpad, const void* rotary_cos, const void* rotary_sin,
                         int64_t rotary_cos_row_stride, int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim,
                         int rotary_interleaved, int cache_dtype, const float* k_descale, const float* v_descale,
-                        int64_t descale_batch_stride) {
+                        int64_t descale_batch_stride, const float* sinks = nullptr, int64_t sink_heads = 1) {
     if (dtype != FA_DTYPE_F16 && dtype != FA_DTYPE_BF16)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: dtype must be f16 or bf16 (got code %d)", who, dtype);
     // the cache's element type: q's, or e4m3 with a dequantisation scale per (sequence, K/V head)
@@ -792,6 +911,12 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads_q=%lld must be a positive multiple of heads_kv=%lld", who, (long long)heads_q,
                     (long long)heads_kv);
     if (seqlen_q < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_q must be >= 1 (got %lld)", who, (long long)seqlen_q);
+    {   // attention sinks: head h of every sequence takes sinks[h % sink_heads]
+        SinkArg sk;
+        sk.sinks = sinks; sk.heads = sink_heads;
+        const int rc = sink_check(who, sk, heads_q, false);
+        if (rc != FA_OK) return rc;
+    }
     if (descale_batch_stride != 0 && (descale_batch_stride < heads_kv || descale_batch_stride > ((int64_t)1 << 40)))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: descale_batch_stride=%lld must be 0 or >= heads_kv=%lld (and <= 2^40)", who,
                     (long long)descale_batch_stride, (long long)heads_kv);
@@ -906,7 +1031,8 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
     if (cache_len > ((int64_t)1 << 28) || seqlen_q > ((int64_t)1 << 24) || heads_q > 65535 ||
         ((heads_q / heads_kv) * seqlen_q + 15) / 16 * heads_kv > 65535)
         return fail(FA_ERR_UNSUPPORTED, "%s: problem too large for one launch", who);
-    const int64_t S = kv_splits(batch, heads_q, heads_kv, seqlen_q, cache_len, num_splits);
+    int64_t S = kv_splits(batch, heads_q, heads_kv, seqlen_q, cache_len, num_splits);
+    if (sinks && S < 2) S = 2;   // the sink joins in the combine: where the rule or the caller gives one split, two are launched
     if (S > 1 && batch * heads_q * seqlen_q >= ((int64_t)1 << 26))   // the combine: one wave per row, 2^32 lanes per launch
         return fail(FA_ERR_UNSUPPORTED, "%s: batch * heads_q * seqlen_q = %lld rows are too many to combine %lld splits in one launch",
                     who, (long long)(batch * heads_q * seqlen_q), (long long)S);
@@ -942,6 +1068,7 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
     a.rotary_cos = rotary_cos; a.rotary_sin = rotary_sin; a.rotary_cos_rs = rotary_cos_row_stride; a.rotary_sin_rs = rotary_sin_row_stride;
     a.rotary_dim = rotary_dim; a.rotary_interleaved = rotary_interleaved ? 1 : 0; a.rotary_q_per_token = rotary_cos ? rotary_q_per_token : 0;
     a.cache_e4m3 = e4m3 ? 1 : 0; a.k_descale = k_descale; a.v_descale = v_descale; a.descale_bstride = descale_batch_stride;
+    a.sinks = sinks; a.sink_heads = sinks ? sink_heads : 1;
     hipError_t e = fa::launch_kvcache(a, reinterpret_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
     return FA_OK;
@@ -1028,6 +1155,30 @@ int fa_ex_forward_kvcache_fp8(const void* q, void* k_cache, void* v_cache, const
                         num_blocks, page_block_size, max_blocks_per_seq, cache_batch_idx, cache_batch, cache_leftpad, rotary_cos,
                         rotary_sin, rotary_cos_row_stride, rotary_sin_row_stride, seqlen_ro, rotary_dim, rotary_interleaved, cache_dtype,
                         k_descale, v_descale, descale_batch_stride);
+}
+
+int fa_ex_forward_kvcache_sink(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                               const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                               int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
+                               int64_t q_token_stride, int64_t k_cache_batch_stride, int64_t k_cache_token_stride,
+                               int64_t v_cache_batch_stride, int64_t v_cache_token_stride, int64_t k_new_batch_stride,
+                               int64_t k_new_token_stride, int64_t v_new_batch_stride, int64_t v_new_token_stride, int causal,
+                               int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
+                               const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, const int32_t* block_table,
+                               int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq,
+                               const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad,
+                               const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride,
+                               int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
+                               int cache_dtype, const float* k_descale, const float* v_descale, int64_t descale_batch_stride,
+                               const float* sinks, int64_t sink_heads, void* workspace, size_t workspace_bytes, void* stream) {
+    return kvcache_impl("fa_ex_forward_kvcache_sink", q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, batch, heads_q, heads_kv,
+                        seqlen_q, seqlen_new, cache_len, d, dtype, q_batch_stride, q_token_stride, k_cache_batch_stride,
+                        k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride, k_new_batch_stride, k_new_token_stride,
+                        v_new_batch_stride, v_new_token_stride, causal, window_left, window_right, softmax_scale, softcap, alibi_slopes,
+                        alibi_batch_stride, num_splits, workspace, workspace_bytes, stream, block_table, block_table_row_stride,
+                        num_blocks, page_block_size, max_blocks_per_seq, cache_batch_idx, cache_batch, cache_leftpad, rotary_cos,
+                        rotary_sin, rotary_cos_row_stride, rotary_sin_row_stride, seqlen_ro, rotary_dim, rotary_interleaved, cache_dtype,
+                        k_descale, v_descale, descale_batch_stride, sinks, sink_heads);
 }
 
 size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {

@@ -9,6 +9,9 @@
 //                      transposed with ds_read_b64_tr_b16 (the TileSwz image of the forward kernels).  Online softmax in fp32
 //                      on the lane of its query row.  One split writes o / lse directly; more write fp32 partials.
 //   kv_combine_kernel: S > 1 only — one wave per (b, h_q, row) merges the S partials in split order.
+// fa_ex_forward_kvcache_sink (attention sinks) changes the last launch only: kv_combine_sink_kernel merges the partials with one
+// more column, the head's sink logit with a zero value vector, so such a call always has S >= 2 (the C layer raises 1 to 2; the
+// second split of a short cache is empty, lse_s = -inf, and is selected away).  The append and split kernels are the ones above.
 // Split ranges come from len_k on the device (kv_split_range), S from the shapes on the host (fa_capi.hip): the call never
 // synchronises and never allocates, so it can be captured in a graph.  Keys are addressed per 32-key tile from one base per
 // (batch element, K/V head).  fa_ex_forward_kvcache_paged adds three ways to move that base, all in per-sequence key coordinates, so
@@ -258,6 +261,60 @@ __global__ __launch_bounds__(256) void kv_combine_kernel(KvParams p, int S, long
     if (c == 0) p.lse[row] = sum > 0.f ? m + logf(sum) : -INFINITY;
 }
 
+// kv_combine_kernel with the sink column (a kernel of its own: the one above keeps its instruction text).  Head h takes
+// snk = sinks[h % sink_heads] and
+//   m = max(max_s lse_s, snk),  denom = sum_s exp(lse_s - m) + exp(snk - m),  o = sum_s exp(lse_s - m) O_s / denom,
+//   lse = m + log(denom)
+// so a row without any visible key gives o = 0, lse = snk exactly (denom = 1).  snk = -inf adds nothing anywhere: the bits of
+// kv_combine_kernel.  The sink is added to the denominator after the wave's reduction, in a fixed place.
+template <typename Tag>
+__global__ __launch_bounds__(256) void kv_combine_sink_kernel(KvParams p, int S, long long nrows, const float* __restrict__ sinks,
+                                                              int sink_heads) {
+    __shared__ float wsh[4][256];
+    const int wv = threadIdx.x >> 6, c = threadIdx.x & 63, DR = p.d;
+    const long long row = (long long)blockIdx.x * 4 + wv;
+    if (row >= nrows) return;   // (wave-uniform; the LDS rows are wave-private, no barrier)
+    // row = (b * hq + h) * nq + qi  ->  o (b, qi, h)
+    const long long bh = row / p.nq;
+    const int qi = (int)(row - bh * p.nq), h = (int)(bh % p.hq);
+    const long long b = bh / p.hq;
+    const float snk = sinks[h % sink_heads];
+    const float* pl = p.plse + row * S;
+    float m = -INFINITY;
+    for (int s = c; s < S; s += 64) m = fmaxf(m, pl[s]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    m = fmaxf(m, snk);
+    float sum = 0.f;
+    for (int s = c; s < S; s += 64) {
+        const float ls = pl[s];
+        const float w = (ls == -INFINITY) ? 0.f : __expf(ls - m);
+        wsh[wv][s] = w;
+        sum += w;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    sum += (snk == -INFINITY) ? 0.f : __expf(snk - m);
+    f32x4_t acc = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    if (4 * c < DR) {
+        const float* po = p.po + row * S * DR + 4 * c;
+#pragma unroll 8
+        for (int s = 0; s < S; ++s) {
+            const float w = wsh[wv][s];
+            const f32x4_t x = *reinterpret_cast<const f32x4_t*>(po + (size_t)s * DR);
+            acc += (w != 0.f) ? w * x : f32x4_t{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+    const float inv = sum > 0.f ? 1.f / sum : 0.f;
+    if (4 * c < DR) {
+        u32x2 v;
+        v[0] = pack2_rn<Tag>(acc[0] * inv, acc[1] * inv);
+        v[1] = pack2_rn<Tag>(acc[2] * inv, acc[3] * inv);
+        *reinterpret_cast<u32x2*>(p.o + ((b * p.nq + qi) * p.hq + h) * DR + 4 * c) = v;
+    }
+    if (c == 0) p.lse[row] = sum > 0.f ? m + logf(sum) : -INFINITY;
+}
+
 template <typename Tag, int D>
 hipError_t launch_split(const KvParams& p, const KvRot& ro, const KvQ8* q8, int S, int row_tiles, int batch, hipStream_t st) {
     const dim3 grid((unsigned)S, (unsigned)(row_tiles * p.hkv), (unsigned)batch);
@@ -279,8 +336,10 @@ hipError_t launch_split(const KvParams& p, const KvRot& ro, const KvQ8* q8, int 
     return hipGetLastError();
 }
 
+// sinks != null (S >= 2 then): the combine with the sink column
 template <typename Tag>
-hipError_t launch_kv_t(const KvParams& p, const KvRot& ro, const KvQ8* q8, int S, int row_tiles, int batch, hipStream_t st) {
+hipError_t launch_kv_t(const KvParams& p, const KvRot& ro, const KvQ8* q8, int S, int row_tiles, int batch, hipStream_t st,
+                       const float* sinks, int sink_heads) {
     hipError_t e = hipSuccess;
     if (p.nnew > 0) {
         const long long per_b = (long long)p.nnew * p.hkv * (p.d / 8);
@@ -297,7 +356,10 @@ hipError_t launch_kv_t(const KvParams& p, const KvRot& ro, const KvQ8* q8, int S
     else e = launch_split<Tag, 256>(p, ro, q8, S, row_tiles, batch, st);
     if (e != hipSuccess || S == 1) return e;
     const long long nrows = (long long)batch * p.hq * p.nq;
-    hipLaunchKernelGGL((kv_combine_kernel<Tag>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st, p, S, nrows);
+    if (sinks)
+        hipLaunchKernelGGL((kv_combine_sink_kernel<Tag>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st, p, S, nrows, sinks, sink_heads);
+    else
+        hipLaunchKernelGGL((kv_combine_kernel<Tag>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st, p, S, nrows);
     return hipGetLastError();
 }
 
@@ -345,6 +407,7 @@ hipError_t launch_kvcache(const KvArgs& a, hipStream_t st) {
     p.sc.cap_a = cap > 0.0 ? (float)(cap / sc) : 0.f;
     p.sc.al_k = (float)(1.0 / sc);
     const int S = (int)a.num_splits;
+    if (a.sinks && S < 2) return hipErrorInvalidValue;   // (the C layer raises a sink call's S to 2: the sink joins in the combine)
     p.po = (float*)a.workspace;
     // workspace (S > 1): the O partials, then the lse partials, each rounded up to 256 bytes (kv_workspace_bytes)
     p.plse = S > 1 ? (float*)((char*)a.workspace + (((size_t)a.batch * a.heads_q * a.seqlen_q * S * a.d * 4 + 255) & ~(size_t)255))
@@ -357,8 +420,9 @@ hipError_t launch_kvcache(const KvArgs& a, hipStream_t st) {
     const KvQ8* q8p = a.cache_e4m3 ? &q8 : nullptr;
     const int batch = (int)a.batch;
     const int row_tiles = (p.rows + 15) / 16;
-    return a.dtype == 1 ? launch_kv_t<f16_tag>(p, ro, q8p, S, row_tiles, batch, st)
-                        : launch_kv_t<bf16_tag>(p, ro, q8p, S, row_tiles, batch, st);
+    const int sink_heads = (int)(a.sink_heads > 0 ? a.sink_heads : 1);
+    return a.dtype == 1 ? launch_kv_t<f16_tag>(p, ro, q8p, S, row_tiles, batch, st, a.sinks, sink_heads)
+                        : launch_kv_t<bf16_tag>(p, ro, q8p, S, row_tiles, batch, st, a.sinks, sink_heads);
 }
 
 }  // namespace fa

@@ -72,7 +72,8 @@ __device__ __forceinline__ float ex_score_mod(const ExScore& sc, float slope, fl
     if (sc.alibi) x = fmaf(-slope, fabsf((float)dist), x);
     return x;
 }
-template <typename P> constexpr bool ex_has_score() { return std::is_same<P, ExParamsS>::value; }
+template <typename P> constexpr bool ex_has_score() { return std::is_base_of<ExParamsS, P>::value; }
+template <typename P> constexpr bool ex_has_sink() { return std::is_same<P, ExParamsK>::value; }
 
 template <typename T> __device__ __forceinline__ bool ex_quad_ok(int d, const void* a, const void* b, const void* c, const void* e) {
     return d % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
@@ -86,11 +87,12 @@ template <typename T> __device__ __forceinline__ bool ex_quad_ok(int d, const vo
 // VAR: packed sequences (ExParams' varlen fields; the ex_*_varlen_kernel entries): the tile of unit bh = b * hq + h of the padded
 // grid, inside sequence b.  q rows at token stride sq (k, v: sk, sv), o / dq / dk / dv rows at hq * d, lse at (h, token), delta at
 // (token, h).
-// P: ExParams, or ExParamsS for the score-modifier entries (the same for the backward bodies)
+// P: ExParams, or ExParamsS for the score-modifier entries (the same for the backward bodies), or ExParamsK for the sink entries
+// (forward only: the sink joins the row's normaliser in the epilogue, the key loop does not know it)
 template <typename T, int DP, int NW, bool WIN, bool VAR, typename P>
 __device__ __forceinline__ void ex_fwd_body(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, T* __restrict__ o,
                                             float* __restrict__ lse, P& p) {
-    constexpr bool SC = ex_has_score<P>();
+    constexpr bool SC = ex_has_score<P>(), SNK = ex_has_sink<P>();
     constexpr int LD = DP + 4, BM = 16 * NW, BN = 32, NT = DP / 16, PLD = BN + 4, NTH = NW * 64;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Qs = smem;
@@ -134,6 +136,8 @@ __device__ __forceinline__ void ex_fwd_body(const T* __restrict__ q, const T* __
     float* Pw = Ps + w * 16 * PLD;
     [[maybe_unused]] float slope = 0.f;
     if constexpr (SC) slope = ex_slope(p.sc, bh);
+    [[maybe_unused]] float snk = -INFINITY;
+    if constexpr (SNK) snk = ex_sink(p.snk, bh);
 
     for (int k0 = kstart; k0 < kend; k0 += BN) {
         if (!VAR && !ex_tile_live(p, q0, min(q0 + BM, p.nq), k0, min(k0 + BN, p.nk))) continue;   // block-sparse skip (uniform)
@@ -204,13 +208,22 @@ __device__ __forceinline__ void ex_fwd_body(const T* __restrict__ q, const T* __
     for (int i = 0; i < 4; ++i) {
         const int row = q0 + w * 16 + lq * 4 + i;
         if (row < p.nq) {
-            const float inv = l[i] > 0.f ? 1.f / l[i] : 0.f;   // a row without a visible key: o = 0, lse = -inf
+            float inv = l[i] > 0.f ? 1.f / l[i] : 0.f;   // a row without a visible key: o = 0, lse = -inf
+            [[maybe_unused]] float lse_k = 0.f;
+            if constexpr (SNK) {   // (a head at -inf keeps the formulas of the call without sinks: the same bits)
+                lse_k = l[i] > 0.f ? m[i] + logf(l[i]) : -INFINITY;
+                if (snk != -INFINITY) ex_sink_norm(m[i], l[i], snk, inv, lse_k);
+            }
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 const int c = 16 * t + lr;
                 if (c < p.d) o[obase + (size_t)row * ostr + c] = from_f32<T>(acc[t][i] * inv);
             }
-            if (lr == 0) lse[lbase + row] = l[i] > 0.f ? m[i] + logf(l[i]) : -INFINITY;
+            if constexpr (SNK) {
+                if (lr == 0) lse[lbase + row] = lse_k;
+            } else {
+                if (lr == 0) lse[lbase + row] = l[i] > 0.f ? m[i] + logf(l[i]) : -INFINITY;
+            }
         }
     }
 }
@@ -236,6 +249,18 @@ template <typename T, int DP, int NW, bool WIN>
 __global__ __launch_bounds__(NW * 64) void ex_fwd_varlen_score_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                                       const T* __restrict__ v, T* __restrict__ o,
                                                                       float* __restrict__ lse, ExParamsS p) {
+    ex_fwd_body<T, DP, NW, WIN, true>(q, k, v, o, lse, p);
+}
+template <typename T, int DP, int NW, bool WIN>
+__global__ __launch_bounds__(NW * 64) void ex_fwd_sink_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                              const T* __restrict__ v, T* __restrict__ o,
+                                                              float* __restrict__ lse, ExParamsK p) {
+    ex_fwd_body<T, DP, NW, WIN, false>(q, k, v, o, lse, p);
+}
+template <typename T, int DP, int NW, bool WIN>
+__global__ __launch_bounds__(NW * 64) void ex_fwd_varlen_sink_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                                     const T* __restrict__ v, T* __restrict__ o,
+                                                                     float* __restrict__ lse, ExParamsK p) {
     ex_fwd_body<T, DP, NW, WIN, true>(q, k, v, o, lse, p);
 }
 
@@ -556,10 +581,84 @@ __global__ __launch_bounds__(NW * 64) void ex_dq_varlen_score_kernel(const T* __
     ex_dq_body<T, DP, NW, WIN, true>(q, k, v, dout, lse, delta, dq, p);
 }
 
+// ---- the sink's gradient: dsinks[h] = -sum over the rows of head h of exp(sink_h - lse) delta, delta = rowsum(dO * O) as the
+// backward's pre-pass left it in the workspace (dsign = -1 where that holds -delta).  One workgroup per head and a fixed order:
+// thread t adds its rows t, t + 1024, .. of segment after segment (a segment = the nq rows of one unit of the head, or the rows
+// of one packed sequence under one query head: only rows some sequence covers have an lse), then the wave adds by shuffles, then wave 0 adds the 16
+// wave sums from LDS.  No atomics: the same bits on every run.  exp(sink - lse) <= 1 because lse contains the sink.
+struct DsinkParams {
+    const int* cu_q;               // varlen: the sequences' token offsets (untrusted); null otherwise
+    long long l_hstride, d_hstride, d_tstride;   // varlen: lse[h * l_hstride + t], delta[h * d_hstride + t * d_tstride]
+    int nseg, nq, heads, total_q, hq;   // segments per head (units / heads, or the batch); rows per unit (varlen: max_seqlen_q)
+    float dsign;
+};
+__global__ __launch_bounds__(1024) void ex_dsink_kernel(const float* __restrict__ lse, const float* __restrict__ delta,
+                                                         const float* __restrict__ sinks, float* __restrict__ dsinks, DsinkParams p) {
+    __shared__ float part[16];
+    const int h = blockIdx.x;
+    const float snk = sinks[h];
+    if (snk == -INFINITY) {   // no sink for this head: gradient 0 (uniform over the workgroup)
+        if (threadIdx.x == 0) dsinks[h] = 0.f;
+        return;
+    }
+    float acc = 0.f;
+    if (p.cu_q) {   // packed sequences: the query heads h, h + heads, .. share the sink; sequence after sequence
+        for (int hh = h; hh < p.hq; hh += p.heads)
+            for (int b = 0; b < p.nseg; ++b) {
+                int start, len;
+                seq_span(p.cu_q, b, p.total_q, p.nq, start, len);
+                const long long lb = (long long)hh * p.l_hstride + start;
+                const long long db = (long long)hh * p.d_hstride + (long long)start * p.d_tstride;
+                for (int i = threadIdx.x; i < len; i += 1024) acc += expf(snk - lse[lb + i]) * delta[db + i * p.d_tstride];
+            }
+    } else {
+        for (int sgm = 0; sgm < p.nseg; ++sgm) {   // units h, h + heads, ..
+            const long long base = ((long long)sgm * p.heads + h) * p.nq;
+            for (int i = threadIdx.x; i < p.nq; i += 1024) acc += expf(snk - lse[base + i]) * delta[base + i];
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        float t = threadIdx.x < 16 ? part[threadIdx.x] : 0.f;
+#pragma unroll
+        for (int o = 8; o >= 1; o >>= 1) t += __shfl_xor(t, o, 64);
+        if (threadIdx.x == 0) dsinks[h] = -p.dsign * t;
+    }
+}
+hipError_t launch_ex_dsink(const ExArgs& a, const float* delta, long long d_hstride, long long d_tstride, float dsign, hipStream_t st) {
+    DsinkParams p;
+    p.cu_q = a.cu_q;
+    p.l_hstride = a.total_q; p.d_hstride = d_hstride; p.d_tstride = d_tstride;
+    p.heads = (int)a.sink_heads;
+    p.nseg = a.cu_q ? (int)(a.bh / a.heads_q) : (int)(a.bh / a.sink_heads);
+    p.nq = (int)a.nq; p.total_q = (int)a.total_q; p.hq = (int)a.heads_q;
+    p.dsign = dsign;
+    hipLaunchKernelGGL(ex_dsink_kernel, dim3((unsigned)a.sink_heads), dim3(1024), 0, st, (const float*)a.lse, delta, a.sinks, a.dsinks, p);
+    return hipGetLastError();
+}
+// the lse of a sink call's rows when no sequence has a key: the sink itself
+__global__ __launch_bounds__(256) void ex_sink_fill_kernel(float* __restrict__ lse, const float* __restrict__ sinks, int heads, long long nq,
+                                                           long long total) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < total) lse[i] = sinks[(i / nq) % heads];
+}
+hipError_t launch_ex_sink_fill(float* lse, const float* sinks, int64_t sink_heads, int64_t units, int64_t nq, hipStream_t st) {
+    const long long total = (long long)units * nq;
+    if (total <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ex_sink_fill_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, lse, sinks, (int)sink_heads,
+                       (long long)nq, total);
+    return hipGetLastError();
+}
+
 // ---- host launchers
-// SC: a call with a score modifier (the *_score_kernel entries, ExParamsS)
-template <typename T, int DP, int NW, bool WIN, bool VAR, bool SC> static auto ex_fwd_entry() {
-    if constexpr (SC) return VAR ? ex_fwd_varlen_score_kernel<T, DP, NW, WIN> : ex_fwd_score_kernel<T, DP, NW, WIN>;
+// SC: a call with a score modifier (the *_score_kernel entries, ExParamsS); SK: a forward with sinks (the *_sink_kernel entries,
+// ExParamsK; always with SC)
+template <typename T, int DP, int NW, bool WIN, bool VAR, bool SC, bool SK = false> static auto ex_fwd_entry() {
+    if constexpr (SK) return VAR ? ex_fwd_varlen_sink_kernel<T, DP, NW, WIN> : ex_fwd_sink_kernel<T, DP, NW, WIN>;
+    else if constexpr (SC) return VAR ? ex_fwd_varlen_score_kernel<T, DP, NW, WIN> : ex_fwd_score_kernel<T, DP, NW, WIN>;
     else return VAR ? ex_fwd_varlen_kernel<T, DP, NW, WIN> : ex_fwd_kernel<T, DP, NW, WIN>;
 }
 template <typename T, int DP, int NW, bool WIN, bool VAR, bool SC> static auto ex_dkdv_entry() {
@@ -570,22 +669,23 @@ template <typename T, int DP, int NW, bool WIN, bool VAR, bool SC> static auto e
     if constexpr (SC) return VAR ? ex_dq_varlen_score_kernel<T, DP, NW, WIN> : ex_dq_score_kernel<T, DP, NW, WIN>;
     else return VAR ? ex_dq_varlen_kernel<T, DP, NW, WIN> : ex_dq_kernel<T, DP, NW, WIN>;
 }
-template <bool SC> static auto ex_params(const ExArgs& a) {
-    if constexpr (SC) return make_ex_params_s(a);
+template <bool SC, bool SK = false> static auto ex_params(const ExArgs& a) {
+    if constexpr (SK) return make_ex_params_k(a);
+    else if constexpr (SC) return make_ex_params_s(a);
     else return make_ex_params(a);
 }
 
-template <typename T, int DP, int NW, bool WIN, bool VAR = false, bool SC = false>
+template <typename T, int DP, int NW, bool WIN, bool VAR = false, bool SC = false, bool SK = false>
 static hipError_t ex_fwd_t(const ExArgs& a, hipStream_t st) {
     constexpr int LD = DP + 4;
     const size_t smem = sizeof(float) * ((16 * NW + 64) * LD + NW * 16 * 36);
-    auto kern = ex_fwd_entry<T, DP, NW, WIN, VAR, SC>();
+    auto kern = ex_fwd_entry<T, DP, NW, WIN, VAR, SC, SK>();
     hipError_t e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
     if (e != hipSuccess) return e;
     dim3 grid((unsigned)(((a.nq + 16 * NW - 1) / (16 * NW)) * a.bh));
     ProfScope ps(K_EX_FWD, st);
     hipLaunchKernelGGL(kern, grid, dim3(NW * 64), smem, st, (const T*)a.q, (const T*)a.k, (const T*)a.v, (T*)a.o, a.lse,
-                       ex_params<SC>(a));
+                       ex_params<SC, SK>(a));
     return hipGetLastError();
 }
 
@@ -600,6 +700,10 @@ static hipError_t ex_bwd_t(const ExArgs& a, hipStream_t st) {
                        (const T*)a.dout, delta, rows, (int)a.d);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    if (a.sinks) {   // (delta rows: (unit, row), varlen (token, head))
+        e = launch_ex_dsink(a, delta, 1, a.heads_q, 1.f, st);
+        if (e != hipSuccess) return e;
+    }
     {
         const size_t smem = sizeof(float) * ((2 * 16 * NW + 64) * LD + 2 * NW * 16 * 36 + 64);
         auto kern = ex_dkdv_entry<T, DP, NW, WIN, VAR, SC>();
@@ -624,19 +728,22 @@ static hipError_t ex_bwd_t(const ExArgs& a, hipStream_t st) {
     return e;
 }
 
-template <typename T, bool WIN, bool VAR = false, bool SC = false>
+// (SK: the forward's sink entries; the backward of a sink call runs the kernels of the call without sinks, on the lse that contains
+// the sink, and ex_dsink_kernel beside them)
+template <typename T, bool WIN, bool VAR = false, bool SC = false, bool SK = false>
 static hipError_t ex_by_d(const ExArgs& a, bool backward, hipStream_t st) {
-    if (a.d <= 64) return backward ? ex_bwd_t<T, 64, 4, WIN, VAR, SC>(a, st) : ex_fwd_t<T, 64, 4, WIN, VAR, SC>(a, st);
-    if (a.d <= 128) return backward ? ex_bwd_t<T, 128, 4, WIN, VAR, SC>(a, st) : ex_fwd_t<T, 128, 4, WIN, VAR, SC>(a, st);
-    return backward ? ex_bwd_t<T, 256, 2, WIN, VAR, SC>(a, st) : ex_fwd_t<T, 256, 4, WIN, VAR, SC>(a, st);
+    if (a.d <= 64) return backward ? ex_bwd_t<T, 64, 4, WIN, VAR, SC>(a, st) : ex_fwd_t<T, 64, 4, WIN, VAR, SC, SK>(a, st);
+    if (a.d <= 128) return backward ? ex_bwd_t<T, 128, 4, WIN, VAR, SC>(a, st) : ex_fwd_t<T, 128, 4, WIN, VAR, SC, SK>(a, st);
+    return backward ? ex_bwd_t<T, 256, 2, WIN, VAR, SC>(a, st) : ex_fwd_t<T, 256, 4, WIN, VAR, SC, SK>(a, st);
 }
-template <typename T, bool SC>
+template <typename T, bool SC, bool SK = false>
 static hipError_t ex_by_d_s(const ExArgs& a, bool backward, hipStream_t st) {
-    if (a.cu_q) return ex_windowed(a) ? ex_by_d<T, true, true, SC>(a, backward, st) : ex_by_d<T, false, true, SC>(a, backward, st);
-    return ex_windowed(a) ? ex_by_d<T, true, false, SC>(a, backward, st) : ex_by_d<T, false, false, SC>(a, backward, st);
+    if (a.cu_q) return ex_windowed(a) ? ex_by_d<T, true, true, SC, SK>(a, backward, st) : ex_by_d<T, false, true, SC, SK>(a, backward, st);
+    return ex_windowed(a) ? ex_by_d<T, true, false, SC, SK>(a, backward, st) : ex_by_d<T, false, false, SC, SK>(a, backward, st);
 }
 template <typename T>
 static hipError_t ex_by_d(const ExArgs& a, bool backward, hipStream_t st) {
+    if (a.sinks && !backward) return ex_by_d_s<T, true, true>(a, false, st);
     return ex_scoremod(a) ? ex_by_d_s<T, true>(a, backward, st) : ex_by_d_s<T, false>(a, backward, st);
 }
 
@@ -649,7 +756,8 @@ static hipError_t launch_ex_one(const ExArgs& a, bool backward, hipStream_t st) 
     // the workspace of fa_ex_backward_workspace_bytes covers their row constants)
     // (a window that bounds something never leaves this file's families: the plain, nq != nk and fa_generic kernels know no band)
     // (nor does a score modifier: the plain, Nq != Nk and fa_generic kernels and the dS hand-over know none)
-    const bool win = ex_windowed(a), mod = ex_scoremod(a);
+    // (nor do sinks)
+    const bool win = ex_windowed(a), mod = ex_scoremod(a) || a.sinks != nullptr;
     const bool plain = (path == 0 || path == 2) && !win && !mod && !a.mask && !a.block_mask && a.dropout_p <= 0.0 && a.scale > 0.f;
     if (plain && a.nq == a.nk && (backward ? bwd_mfma_supported(a.dtype, a.d) : fwd_mfma_supported(a.dtype, a.d))) {
         if (!backward) {

@@ -55,6 +55,32 @@ struct ExParamsS : ExParams {
 };
 static_assert(sizeof(ExScore) == 32 && sizeof(ExParamsS) == sizeof(ExParams) + sizeof(ExScore), "ExParamsS layout: ExScore after every ExParams field");
 
+// Attention sinks (ExArgs; the *_sink_kernel forward entries of fa_ex.hip and fa_ex_mfma.hip, FEAT bit 5): a parameter block of
+// their own again, ExParamsK = ExParamsS + ExSink, so that every other kernel keeps its block and its code.  A sink call always
+// takes the score-modifier body (cap_a = 0 and alibi = null are run-time no-ops there).
+struct ExSink {
+    const float* sinks;    // unit u: sinks[u % heads] (natural-log units; -inf = none)
+    int heads, pad_;
+};
+struct ExParamsK : ExParamsS {
+    ExSink snk;
+};
+static_assert(sizeof(ExSink) == 16 && sizeof(ExParamsK) == sizeof(ExParamsS) + sizeof(ExSink), "ExParamsK layout: ExSink after every ExParamsS field");
+// this unit's sink logit: uniform over the workgroup (a scalar load)
+__device__ __forceinline__ float ex_sink(const ExSink& sk, int bh) { return sk.sinks[bh % sk.heads]; }
+// The row normaliser with the sink column.  In: m = the row's running max in natural-log units (-inf: no visible key), l = the sum
+// of exp(s - m) over the visible keys (0 then), snk = the sink logit (not -inf: the caller keeps the sink-free formulas for that,
+// bit for bit).  With m' = max(m, snk): l' = l exp(m - m') + exp(snk - m') >= 1, never exp(snk - m) itself, so a sink of +-1e4 is
+// safe.  Out: the factor for the unnormalised accumulator, exp(m - m') / l' (0 for a row without a visible key: o = 0), and
+// lse = m' + log(l') (= snk exactly for such a row: l' = 1).
+__device__ __forceinline__ void ex_sink_norm(float m, float l, float snk, float& inv, float& lse) {
+    const float mp = fmaxf(m, snk);
+    const float a = l > 0.f ? expf(m - mp) : 0.f;
+    const float lp = fmaf(l, a, expf(snk - mp));
+    inv = a / lp;
+    lse = mp + logf(lp);
+}
+
 // this unit's slope (0 without ALiBi): uniform over the workgroup
 __device__ __forceinline__ float ex_slope(const ExScore& sc, int bh) {
     return sc.alibi ? sc.alibi[(bh / sc.al_heads) * sc.al_bstride + bh % sc.al_heads] : 0.f;
@@ -159,6 +185,14 @@ inline ExParamsS make_ex_params_s(const ExArgs& a) {
     p.sc.cap_k = cap > 0.0 ? (float)(2.0 * 1.4426950408889634 * sc / cap) : 0.f;
     p.sc.cap_a = cap > 0.0 ? (float)(cap / sc) : 0.f;
     p.sc.al_k = (float)(1.0 / sc);
+    return p;
+}
+inline ExParamsK make_ex_params_k(const ExArgs& a) {
+    ExParamsK p;
+    static_cast<ExParamsS&>(p) = make_ex_params_s(a);
+    p.snk.sinks = a.sinks;
+    p.snk.heads = (int)(a.sink_heads > 0 ? a.sink_heads : 1);
+    p.snk.pad_ = 0;
     return p;
 }
 

@@ -17,6 +17,9 @@
 //               modified right after the S MFMAs, before any mask (mod_softcap / mod_alibi; on / off are wave-uniform run-time
 //               switches).  The backward kernels then start S at 0 and add -lse / scale after the modifier, and dS takes the
 //               softcap's 1 - t^2 in fp32 before its 16-bit pack.  Combinable with every other bit.
+//   FEAT bit 5  attention sinks (forward only, always with bit 4): the parameter block grows once more (ExParamsK) and the
+//               epilogue's normaliser takes the unit's sink logit as one more column (ex_sink_norm).  The key loop is bit 4's.
+//               The backward of a sink call runs the kernels of the call without sinks and ex_dsink_kernel (fa_ex.hip).
 // Dense mask bytes are fetched with range-checked buffer loads (rows / bytes past the mask read as 0 = masked); when Nk, the
 // mask pointer and the (b,h) stride are multiples of 4 a lane of the query-on-the-lane kernels takes the 4 keys of a
 // register group with one dword load.  The block-sparse mask needs br, bc multiples of 32 here (a wave's 32 x 32 block
@@ -30,11 +33,14 @@ namespace fa {
 
 namespace {
 
-constexpr int kFeatMask = 1, kFeatDrop = 2, kFeatWindow = 4, kFeatVarlen = 8, kFeatScore = 16;
-// the parameter block of an instantiation: ExParamsS (+ the score modifiers) with kFeatScore, else ExParams as before
-template <int FEAT> using ExP = typename std::conditional<(FEAT & kFeatScore) != 0, ExParamsS, ExParams>::type;
+constexpr int kFeatMask = 1, kFeatDrop = 2, kFeatWindow = 4, kFeatVarlen = 8, kFeatScore = 16, kFeatSink = 32;
+// the parameter block of an instantiation: ExParamsK (+ the sinks) with kFeatSink, ExParamsS (+ the score modifiers) with
+// kFeatScore, else ExParams as before
+template <int FEAT> using ExP = typename std::conditional<(FEAT & kFeatSink) != 0, ExParamsK,
+                                typename std::conditional<(FEAT & kFeatScore) != 0, ExParamsS, ExParams>::type>::type;
 template <int FEAT> inline ExP<FEAT> make_exm_params(const ExArgs& a) {
-    if constexpr ((FEAT & kFeatScore) != 0) return make_ex_params_s(a);
+    if constexpr ((FEAT & kFeatSink) != 0) return make_ex_params_k(a);
+    else if constexpr ((FEAT & kFeatScore) != 0) return make_ex_params_s(a);
     else return make_ex_params(a);
 }
 
@@ -222,6 +228,8 @@ __device__ __forceinline__ unsigned keep_bits_q(const ExParams& p, unsigned hi, 
 // the modifiers of a kFeatScore instantiation's ExParamsS (a call dependent on FEAT: the bodies the plain entries include name it
 // only in discarded `if constexpr (SC)` branches)
 template <int FEAT, typename P> __device__ __forceinline__ const ExScore& sc_of(const P& p) { return p.sc; }
+// the same for the sinks of a kFeatSink instantiation's ExParamsK
+template <int FEAT, typename P> __device__ __forceinline__ const ExSink& sink_of(const P& p) { return p.snk; }
 // this unit's al (0 without ALiBi), the same product in every kernel
 __device__ __forceinline__ float alibi_k(const ExScore& sc, int bh) { return ex_slope(sc, bh) * sc.al_k; }
 
@@ -269,6 +277,13 @@ template <typename Tag, int D, int FEAT>
 __global__ __launch_bounds__(512, 2) void exm_fwd_score_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                                const uint16_t* __restrict__ v, uint16_t* __restrict__ o,
                                                                float* __restrict__ lse, ExParamsS p, float c_log2) {
+#include "fa_ex_mfma_fwd.inc"
+}
+// FEAT with kFeatSink (and kFeatScore): the parameter block grows by the sinks (ExParamsK)
+template <typename Tag, int D, int FEAT>
+__global__ __launch_bounds__(512, 2) void exm_fwd_sink_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
+                                                              const uint16_t* __restrict__ v, uint16_t* __restrict__ o,
+                                                              float* __restrict__ lse, ExParamsK p, float c_log2) {
 #include "fa_ex_mfma_fwd.inc"
 }
 
@@ -376,7 +391,8 @@ bool ex_mfma_supported(const ExArgs& a) {
 
 // the kernel entry of an instantiation: exm_*_score_kernel with kFeatScore
 template <typename Tag, int D, int FEAT> static auto exm_fwd_entry() {
-    if constexpr ((FEAT & kFeatScore) != 0) return exm_fwd_score_kernel<Tag, D, FEAT>;
+    if constexpr ((FEAT & kFeatSink) != 0) return exm_fwd_sink_kernel<Tag, D, FEAT>;
+    else if constexpr ((FEAT & kFeatScore) != 0) return exm_fwd_score_kernel<Tag, D, FEAT>;
     else return exm_fwd_kernel<Tag, D, FEAT>;
 }
 template <typename Tag, int D, int FEAT, bool M16> static auto exm_dkdv_entry() {
@@ -401,6 +417,7 @@ static hipError_t exm_fwd_t(const ExArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
+// (FEAT never carries kFeatSink here: the backward of a sink call runs the kernels of the call without sinks)
 template <typename Tag, int D, int FEAT>
 static hipError_t exm_bwd_t(const ExArgs& a, hipStream_t st) {
     const long long rows = (long long)a.bh * a.nq;
@@ -413,6 +430,10 @@ static hipError_t exm_bwd_t(const ExArgs& a, hipStream_t st) {
                        (const uint16_t*)a.dout, (const float*)a.lse, nlse, ndelta, rows, (int)a.d, 1.f / a.scale);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    if (a.sinks) {   // the sink's gradient from the caller's lse and the -delta just written
+        e = launch_ex_dsink(a, ndelta, 0, 1, -1.f, st);
+        if (e != hipSuccess) return e;
+    }
     if (a.nk > 0) {
         const bool m16 = (FEAT & kFeatMask) && p.mask != nullptr && (p.nk & 15) == 0 && (p.mask_bh & 15) == 0 && (((uintptr_t)p.mask) & 15) == 0;
         const size_t smem = (size_t)256 * D * 2 + 4 * 64 * D * 2 + 2 * 128 * sizeof(float) + (m16 ? 8 * 1024 : 0);   // + the waves' mask images
@@ -451,8 +472,23 @@ static hipError_t exm_by_feat_s(const ExArgs& a, bool backward, hipStream_t st) 
     if (masks) return backward ? exm_bwd_t<Tag, D, S | 1>(a, st) : exm_fwd_t<Tag, D, S | 1>(a, st);
     return backward ? exm_bwd_t<Tag, D, S>(a, st) : exm_fwd_t<Tag, D, S>(a, st);
 }
+// the forward of a sink call: one sink entry per feature combination, on the score-modifier body
+template <typename Tag, int D>
+static hipError_t exm_fwd_sink(const ExArgs& a, hipStream_t st) {
+    constexpr int S = kFeatScore | kFeatSink;
+    const bool masks = a.mask || a.block_mask, drop = a.dropout_p > 0.0;
+    if (ex_windowed(a)) {
+        if (drop) return exm_fwd_t<Tag, D, S | 7>(a, st);
+        if (masks) return exm_fwd_t<Tag, D, S | 5>(a, st);
+        return exm_fwd_t<Tag, D, S | 4>(a, st);
+    }
+    if (drop) return exm_fwd_t<Tag, D, S | 3>(a, st);
+    if (masks) return exm_fwd_t<Tag, D, S | 1>(a, st);
+    return exm_fwd_t<Tag, D, S>(a, st);
+}
 template <typename Tag, int D>
 static hipError_t exm_by_feat(const ExArgs& a, bool backward, hipStream_t st) {
+    if (a.sinks && !backward) return exm_fwd_sink<Tag, D>(a, st);
     return ex_scoremod(a) ? exm_by_feat_s<Tag, D, kFeatScore>(a, backward, st) : exm_by_feat_s<Tag, D, 0>(a, backward, st);
 }
 
@@ -472,20 +508,25 @@ bool ex_mfma_varlen_supported(const ExArgs& a) {
 }
 
 template <typename Tag, int D, int FEAT>
+static hipError_t exm_varlen_fwd_t(const ExArgs& a, hipStream_t st) {
+    const ExP<FEAT> p = make_exm_params<FEAT>(a);
+    const float c = a.scale * 1.4426950408889634f;
+    const size_t smem = 2 * 2 * 128 * D * 2;
+    auto kern = exm_fwd_entry<Tag, D, FEAT | kFeatVarlen>();
+    hipError_t e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
+    if (e != hipSuccess) return e;
+    ProfScope ps(K_EX_FWD, st);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(((a.nq + 255) / 256) * a.bh)), dim3(512), smem, st, (const uint16_t*)a.q,
+                       (const uint16_t*)a.k, (const uint16_t*)a.v, (uint16_t*)a.o, a.lse, p, c);
+    return hipGetLastError();
+}
+
+template <typename Tag, int D, int FEAT>
 static hipError_t exm_varlen_t(const ExArgs& a, bool backward, hipStream_t st) {
+    if (!backward) return exm_varlen_fwd_t<Tag, D, FEAT>(a, st);
     const ExP<FEAT> p = make_exm_params<FEAT>(a);
     const float c = a.scale * 1.4426950408889634f;
     hipError_t e;
-    if (!backward) {
-        const size_t smem = 2 * 2 * 128 * D * 2;
-        auto kern = exm_fwd_entry<Tag, D, FEAT | kFeatVarlen>();
-        e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
-        if (e != hipSuccess) return e;
-        ProfScope ps(K_EX_FWD, st);
-        hipLaunchKernelGGL(kern, dim3((unsigned)(((a.nq + 255) / 256) * a.bh)), dim3(512), smem, st, (const uint16_t*)a.q,
-                           (const uint16_t*)a.k, (const uint16_t*)a.v, (uint16_t*)a.o, a.lse, p, c);
-        return hipGetLastError();
-    }
     // workspace: [-lse/scale | -delta], (heads_q, total_q) each
     const long long rows = (long long)a.heads_q * a.total_q;
     float* nlse = reinterpret_cast<float*>(a.workspace);
@@ -497,6 +538,10 @@ static hipError_t exm_varlen_t(const ExArgs& a, bool backward, hipStream_t st) {
                        1.f / a.scale);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
+    if (a.sinks) {   // (-delta at (head, token), as lse)
+        e = launch_ex_dsink(a, ndelta, a.total_q, 1, -1.f, st);
+        if (e != hipSuccess) return e;
+    }
     {
         const size_t smem = (size_t)256 * D * 2 + 4 * 64 * D * 2 + 2 * 128 * sizeof(float);
         auto kern = exm_dkdv_entry<Tag, D, FEAT | kFeatVarlen, false>();
@@ -526,6 +571,12 @@ static hipError_t exm_varlen_by_feat_s(const ExArgs& a, bool backward, hipStream
 }
 template <typename Tag, int D>
 static hipError_t exm_varlen_by_feat(const ExArgs& a, bool backward, hipStream_t st) {
+    if (a.sinks && !backward) {   // the forward of a sink call
+        constexpr int S = kFeatScore | kFeatSink;
+        const bool drop = a.dropout_p > 0.0;
+        if (ex_windowed(a)) return drop ? exm_varlen_fwd_t<Tag, D, S | kFeatWindow | kFeatDrop>(a, st) : exm_varlen_fwd_t<Tag, D, S | kFeatWindow>(a, st);
+        return drop ? exm_varlen_fwd_t<Tag, D, S | kFeatDrop>(a, st) : exm_varlen_fwd_t<Tag, D, S>(a, st);
+    }
     return ex_scoremod(a) ? exm_varlen_by_feat_s<Tag, D, kFeatScore>(a, backward, st) : exm_varlen_by_feat_s<Tag, D, 0>(a, backward, st);
 }
 

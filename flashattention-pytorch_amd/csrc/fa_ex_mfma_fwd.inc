@@ -1,10 +1,10 @@
 // Kernel body, included by the kernel entries of fa_ex_mfma.hip (the plain and the score-modifier entry of one kernel share
 // it textually, so that each entry is compiled as the one function it was before the score modifiers; a device function
 // called from both changes the code of the existing entries).  In scope: the kernel's parameters, p an ExParams or an
-// ExParamsS (kFeatScore), and the template parameters Tag, D, FEAT.
+// ExParamsS (kFeatScore) or an ExParamsK (kFeatSink), and the template parameters Tag, D, FEAT.
 
     constexpr int NW = 8, BM = 32 * NW, KB = 4, BN = 32 * KB, NKS = D / 16, NDV = D / 32, TILE_BYTES = BN * D * 2;
-    constexpr bool VAR = (FEAT & kFeatVarlen) != 0, SC = (FEAT & kFeatScore) != 0;
+    constexpr bool VAR = (FEAT & kFeatVarlen) != 0, SC = (FEAT & kFeatScore) != 0, SNK = (FEAT & kFeatSink) != 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];   // [2 buffers][K tile | V tile]
     const int DR = p.d;
     int nq = p.nq, nk = p.nk;
@@ -43,6 +43,8 @@
     const int rbw = min(q0 + 32 * w, nq - 1) / p.br;   // block row of this wave's 32 rows (br is a multiple of 32)
     [[maybe_unused]] float al = 0.f;
     if constexpr (SC) al = alibi_k(sc_of<FEAT>(p), bh);
+    [[maybe_unused]] float snk = -INFINITY;   // this unit's sink logit (kFeatSink): workgroup-uniform, one scalar load
+    if constexpr (SNK) snk = ex_sink(sink_of<FEAT>(p), bh);
 
     f32x16 oacc[NDV];
 #pragma unroll
@@ -249,7 +251,12 @@
     // ---- epilogue: normalise, store O and lse.  Every wave is past the last barrier and nothing is in flight: each wave
     // stages its rows in 32 x D x 2 bytes of buffer 0
     const float l_tot = l_run + wave_half_swap(l_run);
-    const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
+    float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
+    [[maybe_unused]] float lse_k = 0.f;
+    if constexpr (SNK) {   // the sink column (a head at -inf keeps the formulas of the call without sinks: the same bits)
+        lse_k = l_tot > 0.f ? m_run * p.scale + logf(l_tot) : -INFINITY;
+        if (snk != -INFINITY) ex_sink_norm(l_tot > 0.f ? m_run * p.scale : -INFINITY, l_tot, snk, inv, lse_k);
+    }
     u32x2 vals[NDV * 4];
 #pragma unroll
     for (int dvb = 0; dvb < NDV; ++dvb)
@@ -259,4 +266,8 @@
             vals[4 * dvb + g][1] = pack2_rn<Tag>(oacc[dvb][4 * g + 2] * inv, oacc[dvb][4 * g + 3] * inv);
         }
     store_rows_via_lds<D, VAR>(smem + w * 32 * D * 2, vals, o + obase, q0 + 32 * w, nq, lane, DR, -1, p.hq * DR);
-    if (qrow < nq && h == 0) lse[lbase + qrow] = l_tot > 0.f ? m_run * p.scale + logf(l_tot) : -INFINITY;
+    if constexpr (SNK) {
+        if (qrow < nq && h == 0) lse[lbase + qrow] = lse_k;
+    } else {
+        if (qrow < nq && h == 0) lse[lbase + qrow] = l_tot > 0.f ? m_run * p.scale + logf(l_tot) : -INFINITY;
+    }

@@ -153,12 +153,24 @@ struct ExArgs {
     double softcap = 0.0;
     const float* alibi = nullptr;
     int64_t alibi_heads = 1, alibi_bstride = 0;
+    // attention sinks (fa_ex_*_sink; sinks != null): one extra softmax column per row with logit sinks[u % sink_heads] of query
+    // unit u (natural-log units, after softcap and ALiBi; never masked or dropped) and a zero value vector.  Device memory, read
+    // by the kernels only; -inf = no sink for that head.  Backward: dsinks (sink_heads,) float32 receives the gradient.
+    const float* sinks = nullptr;
+    int64_t sink_heads = 1;
+    float* dsinks = nullptr;
 };
 // does the call carry a score modifier (softcap or ALiBi)?  Such a call runs on the extended kernels only.
 inline bool ex_scoremod(const ExArgs& a) { return a.softcap > 0.0 || a.alibi != nullptr; }
 // does the call carry a window that bounds something (canonicalised: any bound that is not -1)?
 inline bool ex_windowed(const ExArgs& a) { return a.window_left >= 0 || a.window_right >= 0; }
 hipError_t launch_ex(const ExArgs& a, bool backward, hipStream_t st);
+// dsinks[h] = -dsign * sum over the rows of head h of exp(sinks[h] - lse) * delta (fa_ex.hip: ex_dsink_kernel), launched by the
+// backward of a sink call after its delta pre-pass.  delta: the pre-pass's rowsum(dO * O) (dsign = 1) or its negation (-1); row i
+// of unit u at delta[u * nq + i], varlen token t of head h at delta[h * d_hstride + t * d_tstride].
+hipError_t launch_ex_dsink(const ExArgs& a, const float* delta, long long d_hstride, long long d_tstride, float dsign, hipStream_t st);
+// lse[u * nq + i] = sinks[u % sink_heads]: the rows of a sink call without any key
+hipError_t launch_ex_sink_fill(float* lse, const float* sinks, int64_t sink_heads, int64_t units, int64_t nq, hipStream_t st);
 bool ex_mfma_supported(const ExArgs& a);
 hipError_t launch_ex_mfma(const ExArgs& a, bool backward, hipStream_t st);
 bool ex_mfma_varlen_supported(const ExArgs& a);
@@ -206,6 +218,10 @@ struct KvArgs {
     int cache_e4m3 = 0;
     const float *k_descale = nullptr, *v_descale = nullptr;
     int64_t descale_bstride = 0;
+    // fa_ex_forward_kvcache_sink (null: no sinks): head h of every sequence takes the extra column sinks[h % sink_heads].  The call
+    // then always runs the combine (num_splits >= 2): the sink joins there (kv_combine_sink_kernel).
+    const float* sinks = nullptr;
+    int64_t sink_heads = 1;
 };
 int kv_num_splits(int64_t batch, int64_t heads_kv, int64_t row_tiles, int64_t cache_len);
 size_t kv_workspace_bytes(int64_t batch, int64_t heads_q, int64_t seqlen_q, int64_t d, int splits);

@@ -44,6 +44,8 @@ EXPORTED_C_SYMBOLS = (
     "fa_ex_forward_scoremod", "fa_ex_backward_scoremod", "fa_ex_forward_varlen_scoremod", "fa_ex_backward_varlen_scoremod",
     "fa_ex_forward_kvcache", "fa_ex_kvcache_workspace_bytes", "fa_ex_forward_kvcache_paged", "fa_ex_forward_kvcache_rotary",
     "fa_ex_forward_kvcache_fp8",
+    "fa_ex_forward_sink", "fa_ex_backward_sink", "fa_ex_forward_varlen_sink", "fa_ex_backward_varlen_sink",
+    "fa_ex_forward_kvcache_sink", "fa_ex_kvcache_workspace_bytes_sink",
 )
 
 
@@ -156,6 +158,24 @@ def _load_library() -> ctypes.CDLL:
     lib.fa_ex_forward_kvcache_fp8.restype = ci
     lib.fa_ex_kvcache_workspace_bytes.argtypes = [i64] * 7
     lib.fa_ex_kvcache_workspace_bytes.restype = sz
+    # attention sinks: the score-modifier arguments with sinks, sink_heads (backward: + dsinks) right after alibi_batch_stride; the
+    # KV-cache call: the e4m3 call's with sinks, sink_heads right after descale_batch_stride
+    lib.fa_ex_forward_sink.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, ci, i64, i64, dbl, dbl, vp, i64, i64, vp, i64, vp,
+                                       i64, vp, i64, i64, dbl, u64, vp]
+    lib.fa_ex_forward_sink.restype = ci
+    lib.fa_ex_backward_sink.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, ci, i64, i64, dbl, dbl, vp, i64,
+                                        i64, vp, i64, vp, vp, i64, vp, i64, i64, dbl, u64, vp, sz, vp]
+    lib.fa_ex_backward_sink.restype = ci
+    lib.fa_ex_forward_varlen_sink.argtypes = [vp, vp, vp, vp, vp] + varlen_sm[:21] + [vp, i64] + varlen_sm[21:] + [vp]
+    lib.fa_ex_forward_varlen_sink.restype = ci
+    lib.fa_ex_backward_varlen_sink.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp] + varlen_sm[:21] + [vp, i64, vp] + varlen_sm[21:] + \
+        [vp, sz, vp]
+    lib.fa_ex_backward_varlen_sink.restype = ci
+    lib.fa_ex_forward_kvcache_sink.argtypes = [vp] * 8 + [i64] * 7 + [ci] + [i64] * 10 + [ci, i64, i64, dbl, dbl, vp, i64, i64] + \
+        [vp, i64, i64, i64, i64, vp, i64, vp] + [vp, vp, i64, i64, i64, i64, ci] + [ci, vp, vp, i64] + [vp, i64] + [vp, sz, vp]
+    lib.fa_ex_forward_kvcache_sink.restype = ci
+    lib.fa_ex_kvcache_workspace_bytes_sink.argtypes = [i64] * 7
+    lib.fa_ex_kvcache_workspace_bytes_sink.restype = sz
     return lib
 
 
@@ -444,26 +464,56 @@ def alibi_arg(who, slopes, device, units, heads=None):
     return slopes.data_ptr(), slopes.shape[1], bstride, slopes
 
 
+def sinks_arg(who, sinks, device, units, heads=None):
+    """(pointer, sink_heads, tensor) of attention sinks: a contiguous float32 (sink_heads,) tensor on `device`, one logit per head
+    that joins each row's softmax as an extra column with a zero value (-inf = no sink for that head).  heads=None (the 3-D
+    calls, (BH, N, d)): sink_heads = len(sinks) must divide the BH units, unit u takes sinks[u % sink_heads]; otherwise
+    (the 4-D, varlen and KV-cache calls) sinks must be (heads,), one per query head.  (0, 1, None) without sinks."""
+    if sinks is None:
+        return 0, 1, None
+    if not isinstance(sinks, torch.Tensor):
+        raise RuntimeError(f"{who}: sinks must be a float32 tensor")
+    if sinks.dtype != torch.float32:
+        raise RuntimeError(f"{who}: sinks must be float32, got {sinks.dtype}")
+    if sinks.device != device:
+        raise RuntimeError(f"{who}: sinks must be on q's device ({device}), got {sinks.device}")
+    if heads is None:
+        ok = sinks.dim() == 1 and sinks.shape[0] >= 1 and units % sinks.shape[0] == 0
+        forms = f"(sink_heads,) with sink_heads dividing {units}"
+    else:
+        ok = sinks.dim() == 1 and sinks.shape[0] == heads
+        forms = f"({heads},)"
+    if not ok:
+        raise RuntimeError(f"{who}: sinks must be {forms}, got {tuple(sinks.shape)}")
+    if not sinks.is_contiguous():
+        raise RuntimeError(f"{who}: sinks must be contiguous")
+    return sinks.data_ptr(), sinks.shape[0], sinks
+
+
 def ex_forward(q, k, v, causal, softmax_scale, mask=None, block_mask=None, br=128, bc=128, dropout_p=0.0, seed=0, window=(-1, -1),
-               softcap=0.0, alibi_slopes=None):
+               softcap=0.0, alibi_slopes=None, sinks=None):
     """(o, lse) of attention with Nq != Nk (causal aligned bottom-right), dense mask (0 = masked), block-sparse mask
     (0 = tile skipped) and dropout; see include/fa_mi355x.h.  k and v with BH / g units (g query heads per K/V head) make
     it grouped-query attention.  window = (left, right): key j is visible to row i only within
     [i + Nk - Nq - left, i + Nk - Nq + right], -1 = unbounded (fa_ex_forward_window).  softcap > 0 caps the scores at
     softcap * tanh(s / softcap); alibi_slopes (float32 (BH,), or (B, H) with B * H = BH) subtract slope * |i + Nk - Nq - j|
-    (fa_ex_forward_scoremod)."""
+    (fa_ex_forward_scoremod).  sinks (float32 (sink_heads,), sink_heads dividing BH: unit u takes sinks[u % sink_heads]) adds one
+    column exp(sink) with a zero value to each row's softmax; lse contains it (fa_ex_forward_sink)."""
     wl, wr = window_arg("ex_forward", window)
     cap = softcap_arg("ex_forward", softcap)
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     bh, nq, nk, d, code, mask, mptr, mstride, block_mask, bptr, g = _ex_common("ex_forward", q, k, v, mask, block_mask, br, bc)
     aptr, aheads, astride, alibi_slopes = alibi_arg("ex_forward", alibi_slopes, q.device, bh)
+    sptr, sheads, sinks = sinks_arg("ex_forward", sinks, q.device, bh)
     with torch.cuda.device(q.device):
         o = torch.empty_like(q)
         lse = torch.empty((bh, nq), dtype=torch.float32, device=q.device)
         ptrs = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr())
         rest = (nq, nk, d, code, int(bool(causal)), float(softmax_scale), mptr, mstride, bptr, int(br), int(bc), float(dropout_p),
                 int(seed) & (2 ** 64 - 1), _stream_ptr(q.device))
-        if cap > 0.0 or aptr:
+        if sptr:
+            _check(_lib.fa_ex_forward_sink(*ptrs, bh, g, *rest[:5], wl, wr, rest[5], cap, aptr, aheads, astride, sptr, sheads, *rest[6:]))
+        elif cap > 0.0 or aptr:
             _check(_lib.fa_ex_forward_scoremod(*ptrs, bh, g, *rest[:5], wl, wr, rest[5], cap, aptr, aheads, astride, *rest[6:]))
         elif (wl, wr) != (-1, -1):
             _check(_lib.fa_ex_forward_window(*ptrs, bh, g, *rest[:5], wl, wr, *rest[5:]))
@@ -475,13 +525,16 @@ def ex_forward(q, k, v, causal, softmax_scale, mask=None, block_mask=None, br=12
 
 
 def ex_backward(q, k, v, o, do_, lse, causal, softmax_scale, mask=None, block_mask=None, br=128, bc=128, dropout_p=0.0, seed=0,
-                window=(-1, -1), softcap=0.0, alibi_slopes=None):
+                window=(-1, -1), softcap=0.0, alibi_slopes=None, sinks=None):
+    """(dq, dk, dv) of ex_forward; with sinks (and the lse ex_forward returned with them) also dsinks, float32 (sink_heads,), as a
+    fourth result (fa_ex_backward_sink)."""
     wl, wr = window_arg("ex_backward", window)
     cap = softcap_arg("ex_backward", softcap)
     q, k, v, o, do_, lse = (t.contiguous() for t in (q, k, v, o, do_, lse))
     bh, nq, nk, d, code, mask, mptr, mstride, block_mask, bptr, g = _ex_common("ex_backward", q, k, v, mask, block_mask, br, bc)
     aptr, aheads, astride, alibi_slopes = alibi_arg("ex_backward", alibi_slopes, q.device, bh)
-    mod = cap > 0.0 or aptr != 0
+    sptr, sheads, sinks = sinks_arg("ex_backward", sinks, q.device, bh)
+    mod = cap > 0.0 or aptr != 0 or sptr != 0
     if o.shape != q.shape or do_.shape != q.shape or lse.shape != (bh, nq) or lse.dtype != torch.float32:
         raise RuntimeError("ex_backward: o, do must be (BH, Nq, d) and lse (BH, Nq) float32")
     with torch.cuda.device(q.device):
@@ -503,6 +556,11 @@ def ex_backward(q, k, v, o, do_, lse, causal, softmax_scale, mask=None, block_ma
                 dv.data_ptr())
         rest = (nq, nk, d, code, int(bool(causal)), float(softmax_scale), mptr, mstride, bptr, int(br), int(bc), float(dropout_p),
                 int(seed) & (2 ** 64 - 1), ws.data_ptr(), nbytes, _stream_ptr(q.device))
+        if sptr:
+            dsinks = torch.empty((sheads,), dtype=torch.float32, device=q.device)
+            _check(_lib.fa_ex_backward_sink(*ptrs, bh, g, *rest[:5], wl, wr, rest[5], cap, aptr, aheads, astride, sptr, sheads,
+                                            dsinks.data_ptr(), *rest[6:]))
+            return dq, dk, dv, dsinks
         if mod:
             _check(_lib.fa_ex_backward_scoremod(*ptrs, bh, g, *rest[:5], wl, wr, rest[5], cap, aptr, aheads, astride, *rest[6:]))
         elif (wl, wr) != (-1, -1):
@@ -556,11 +614,12 @@ def _varlen_common(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_s
 
 
 def ex_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, dropout_p=0.0, seed=0,
-                      window=(-1, -1), softcap=0.0, alibi_slopes=None):
+                      window=(-1, -1), softcap=0.0, alibi_slopes=None, sinks=None):
     """(o, lse) of attention over packed sequences (FlashAttention-2's varlen layout): q (total_q, H_q, d), k and v
     (total_k, H_kv, d) — strided views along the token dim allowed — cu_seqlens_* int32 (batch + 1,) device offsets.  o is
     (total_q, H_q, d), lse (H_q, total_q) float32.  Never synchronises: cu_seqlens are clamped in the kernels.  softcap and
-    alibi_slopes (float32 (H_q,) or (batch, H_q)) as in ex_forward, per sequence (fa_ex_forward_varlen_scoremod)."""
+    alibi_slopes (float32 (H_q,) or (batch, H_q)) as in ex_forward, per sequence (fa_ex_forward_varlen_scoremod).  sinks: float32
+    (H_q,), one extra softmax column per query head (fa_ex_forward_varlen_sink)."""
     who = "ex_varlen_forward"
     wl, wr = window_arg(who, window)
     cap = softcap_arg(who, softcap)
@@ -568,12 +627,16 @@ def ex_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seq
     b, hq, _hkv, total_q, *_ = dims
     d = q.shape[2]
     aptr, _h, astride, alibi_slopes = alibi_arg(who, alibi_slopes, q.device, b * hq, heads=hq)
+    sptr, sheads, sinks = sinks_arg(who, sinks, q.device, b * hq, heads=hq)
     with torch.cuda.device(q.device):
         o = torch.empty((total_q, hq, d), dtype=q.dtype, device=q.device)
         lse = torch.empty((hq, total_q), dtype=torch.float32, device=q.device)
         ptrs = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr())
         tail = (float(dropout_p), int(seed) & (2 ** 64 - 1), _stream_ptr(q.device))
-        if cap > 0.0 or aptr:
+        if sptr:
+            _check(_lib.fa_ex_forward_varlen_sink(*ptrs, *dims, int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, astride,
+                                                  sptr, sheads, *tail))
+        elif cap > 0.0 or aptr:
             _check(_lib.fa_ex_forward_varlen_scoremod(*ptrs, *dims, int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, astride,
                                                       *tail))
         else:
@@ -582,14 +645,16 @@ def ex_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seq
 
 
 def ex_varlen_backward(q, k, v, o, do_, lse, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale,
-                       dropout_p=0.0, seed=0, window=(-1, -1), softcap=0.0, alibi_slopes=None):
-    """(dq, dk, dv) of ex_varlen_forward: dq in q's (total_q, H_q, d) shape, dk and dv in k's and v's (dense)."""
+                       dropout_p=0.0, seed=0, window=(-1, -1), softcap=0.0, alibi_slopes=None, sinks=None):
+    """(dq, dk, dv) of ex_varlen_forward: dq in q's (total_q, H_q, d) shape, dk and dv in k's and v's (dense); with sinks also
+    dsinks, float32 (H_q,), as a fourth result."""
     who = "ex_varlen_backward"
     wl, wr = window_arg(who, window)
     cap = softcap_arg(who, softcap)
     cu_q, cu_k, *dims = _varlen_common(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
     b, hq, hkv, total_q, total_k, _mq, _mk, d, code = dims[:9]
     aptr, _h, astride, alibi_slopes = alibi_arg(who, alibi_slopes, q.device, b * hq, heads=hq)
+    sptr, sheads, sinks = sinks_arg(who, sinks, q.device, b * hq, heads=hq)
     for name, t in (("o", o), ("do", do_)):
         if not t.is_cuda or t.shape != (total_q, hq, d) or t.dtype != q.dtype:
             raise RuntimeError(f"{who}: {name} must be a (total_q, H_q, d) device tensor of q's dtype")
@@ -606,6 +671,11 @@ def ex_varlen_backward(q, k, v, o, do_, lse, cu_seqlens_q, cu_seqlens_k, max_seq
         ptrs = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do_.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
                 dv.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr())
         tail = (float(dropout_p), int(seed) & (2 ** 64 - 1), ws.data_ptr(), nbytes, _stream_ptr(q.device))
+        if sptr:
+            dsinks = torch.empty((sheads,), dtype=torch.float32, device=q.device)
+            _check(_lib.fa_ex_backward_varlen_sink(*ptrs, *dims, int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, astride,
+                                                   sptr, sheads, dsinks.data_ptr(), *tail))
+            return dq, dk, dv, dsinks
         if cap > 0.0 or aptr:
             _check(_lib.fa_ex_backward_varlen_scoremod(*ptrs, *dims, int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, astride,
                                                        *tail))
@@ -660,7 +730,8 @@ def _kv_strides(who, name, t, heads, d, cache):
 
 def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlens=None, causal=False, softmax_scale=None,
                        window=(-1, -1), softcap=0.0, alibi_slopes=None, num_splits=0, block_table=None, cache_batch_idx=None,
-                       cache_leftpad=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True, k_descale=None, v_descale=None):
+                       cache_leftpad=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True, *, sinks=None, k_descale=None,
+                       v_descale=None):
     """(o, lse) of a decode step over a KV cache (FlashAttention-2's flash_attn_with_kvcache, forward): q (B, Nq, H_q, d);
     k_cache, v_cache (B, cache_len, H_kv, d), used in place (strided views such as kv.unbind(2) allowed, never copied);
     k_new, v_new (B, N_new, H_kv, d) are written into the caches at cache_seqlens[b] first; cache_seqlens int32 (B,) on the
@@ -681,7 +752,10 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
     1.0; they must be finite and > 0.  The scale follows the sequence b of the call, not the cache row or page.  k_new / v_new
     are quantised on the append: clamp(float(x) * (1.0f / descale), -448, 448) in fp32, rounded to nearest even.  An e4m3 cache
     view must have strides that are multiples of 8 and an 8-byte aligned address (ValueError otherwise; never copied).  See
-    fa_ex_forward_kvcache_fp8."""
+    fa_ex_forward_kvcache_fp8.
+    sinks: float32 (H_q,) on q's device, one extra softmax column per query head with a zero value; it joins where the splits are
+    combined, so such a call runs at least two splits.  lse contains it.  See fa_ex_forward_kvcache_sink.
+    sinks, k_descale and v_descale are keyword-only; the two scales stay the trailing keywords."""
     who = "ex_kvcache_forward"
     wl, wr = window_arg(who, window)
     cap = softcap_arg(who, softcap)
@@ -787,6 +861,7 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
     qb, qt = _kv_strides(who, "q", q, hq, d, False)
     scale = d ** -0.5 if softmax_scale is None else float(softmax_scale)
     aptr, _h, astride, alibi_slopes = alibi_arg(who, alibi_slopes, q.device, b * hq, heads=hq)
+    sptr, sheads, sinks = sinks_arg(who, sinks, q.device, b * hq, heads=hq)
     with torch.cuda.device(q.device):
         if cache_seqlens is not None and not isinstance(cache_seqlens, torch.Tensor):
             cache_seqlens = torch.full((b,), operator.index(cache_seqlens), dtype=torch.int32, device=q.device)
@@ -800,7 +875,7 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
                 v_new.data_ptr() if v_new is not None else 0, cache_seqlens.data_ptr() if cache_seqlens is not None else 0,
                 o.data_ptr(), lse.data_ptr(), b, hq, hkv, nq, nnew, cap_len, d, _DTYPE_CODE[q.dtype], qb, qt, kvb, kvt, vvb, vvt,
                 knb, knt, vnb, vnt, int(bool(causal)), wl, wr, scale, cap, aptr, astride, int(num_splits))
-        if not e4m3 and block_table is None and cache_batch_idx is None and cache_leftpad is None and rotary_cos is None:
+        if not sptr and not e4m3 and block_table is None and cache_batch_idx is None and cache_leftpad is None and rotary_cos is None:
             nbytes = int(_lib.fa_ex_kvcache_workspace_bytes(b, hq, hkv, nq, cap_len, d, int(num_splits)))
             ws = _workspace(q.device, nbytes) if nbytes > 0 else None
             _check(_lib.fa_ex_forward_kvcache(*head, ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device)))
@@ -819,7 +894,7 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
                 cache_leftpad = cache_leftpad.contiguous()
             middle = (*paged, cache_batch_idx.data_ptr() if cache_batch_idx is not None else 0,
                       units if cache_batch_idx is not None else 0, cache_leftpad.data_ptr() if cache_leftpad is not None else 0)
-            rotary = (0, 0, 0, 0, 0, 0, 0) if e4m3 else None
+            rotary = (0, 0, 0, 0, 0, 0, 0) if (e4m3 or sptr) else None
             if rotary_cos is not None:
                 tabs = []
                 for t in (rotary_cos, rotary_sin):   # rows at an even stride, 4-byte aligned: otherwise a dense copy
@@ -831,10 +906,14 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
                           rotary_cos.stride(0) if rotary_cos.shape[0] > 1 else rotary_cos.shape[1],
                           rotary_sin.stride(0) if rotary_sin.shape[0] > 1 else rotary_sin.shape[1],
                           rotary_cos.shape[0], rdim, int(bool(rotary_interleaved)))
-            nbytes = int(_lib.fa_ex_kvcache_workspace_bytes(b, hq, hkv, nq, capacity, d, int(num_splits)))
+            ws_bytes = _lib.fa_ex_kvcache_workspace_bytes_sink if sptr else _lib.fa_ex_kvcache_workspace_bytes
+            nbytes = int(ws_bytes(b, hq, hkv, nq, capacity, d, int(num_splits)))
             ws = _workspace(q.device, nbytes) if nbytes > 0 else None
             tail = (ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device))
-            if e4m3:
+            if sptr:
+                q8 = (_E4M3_CODE, kdp, vdp, dsc_bs) if e4m3 else (_DTYPE_CODE[q.dtype], 0, 0, 0)
+                _check(_lib.fa_ex_forward_kvcache_sink(*head, *middle, *rotary, *q8, sptr, sheads, *tail))
+            elif e4m3:
                 _check(_lib.fa_ex_forward_kvcache_fp8(*head, *middle, *rotary, _E4M3_CODE, kdp, vdp, dsc_bs, *tail))
             elif rotary is None:
                 _check(_lib.fa_ex_forward_kvcache_paged(*head, *middle, *tail))

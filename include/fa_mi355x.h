@@ -468,6 +468,71 @@ int fa_ex_forward_kvcache_fp8(const void* q, void* k_cache, void* v_cache, const
 size_t fa_ex_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t d,
                                      int64_t num_splits);
 
+/* --- Attention sinks (gpt-oss; `sinks` / `s_aux` of FlashAttention-3 and the serving stacks): every head carries one learnable
+ * logit that joins each row's softmax as an extra column with a zero value vector, so a row can give weight to nothing.  For query
+ * row i of head h with visible-key logits s_ij (after softcap and ALiBi, as the *_scoremod calls define them):
+ *     lse_i = log(exp(sink_h) + sum_j exp(s_ij))        o_i = sum_j exp(s_ij - lse_i) * keep_ij / (1 - p) * v_j
+ * The sink is in the units of the final logit (natural log); it is not softcapped, biased, masked, windowed or dropped.  The returned
+ * lse contains it (the backward needs that).  A row without a visible key gives o = 0 and lse = sink_h (-inf without sinks).  The
+ * normaliser is formed around max(row max, sink), so sinks of +-1e4 are safe.  sinks[h] = -inf means "no sink for this head": o and
+ * lse of that head are the bits of the call without sinks, and its gradient is 0.  NaN / +inf are undefined.
+ * sinks: float32 (sink_heads,) in device memory, read by the kernels only (no host read, no synchronisation).  Query unit u takes
+ * sinks[u % sink_heads] (the varlen and KV-cache calls: query head h takes sinks[h % sink_heads]).  The remaining arguments are those
+ * of fa_ex_*_scoremod / fa_ex_*_varlen_scoremod / fa_ex_forward_kvcache_fp8; sinks == NULL is exactly that call (sink_heads and dsinks
+ * are then not read).
+ * Backward: dq, dk, dv as before from the sink-including lse, and dsinks[h] = - sum over the rows i of the units of head h of
+ * exp(sink_h - lse_i) * rowsum(dO_i * O_i), float32 (sink_heads,), summed in a fixed order without atomics (the same bits on every
+ * run).  The workspace is that of the call without sinks.
+ * Checked before any HIP call (FA_ERR_INVALID_ARGUMENT): sinks (and dsinks) 4-byte aligned; sink_heads >= 1 dividing the number of
+ * query units (BH; heads_q for the varlen and KV-cache calls); a backward with sinks needs dsinks. */
+int fa_ex_forward_sink(const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t kv_group, int64_t nq,
+                       int64_t nk, int64_t d, int dtype, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                       double softcap, const float* alibi_slopes, int64_t alibi_heads, int64_t alibi_batch_stride, const float* sinks,
+                       int64_t sink_heads, const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc,
+                       double dropout_p, uint64_t dropout_seed, void* stream);
+int fa_ex_backward_sink(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
+                        void* dv, int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype, int causal,
+                        int64_t window_left, int64_t window_right, double softmax_scale, double softcap, const float* alibi_slopes,
+                        int64_t alibi_heads, int64_t alibi_batch_stride, const float* sinks, int64_t sink_heads, float* dsinks,
+                        const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p,
+                        uint64_t dropout_seed, void* workspace, size_t workspace_bytes, void* stream);
+int fa_ex_forward_varlen_sink(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
+                              const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
+                              int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
+                              int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
+                              double softmax_scale, double softcap, const float* alibi_slopes, int64_t alibi_batch_stride,
+                              const float* sinks, int64_t sink_heads, double dropout_p, uint64_t dropout_seed, void* stream);
+int fa_ex_backward_varlen_sink(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq,
+                               void* dk, void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch,
+                               int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q,
+                               int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                               int causal, int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
+                               const float* alibi_slopes, int64_t alibi_batch_stride, const float* sinks, int64_t sink_heads,
+                               float* dsinks, double dropout_p, uint64_t dropout_seed, void* workspace, size_t workspace_bytes,
+                               void* stream);
+/* Decoding: the sink joins when the per-split partials are combined,
+ *     m = max(max_s lse_s, sink)   denom = sum_s exp(lse_s - m) + exp(sink - m)   o = sum_s exp(lse_s - m) O_s / denom
+ *     lse = m + log(denom)
+ * so a sink call always runs the combine: where the split rule or num_splits gives one split, two are launched (the second is
+ * empty on a short cache).  The workspace is fa_ex_kvcache_workspace_bytes_sink (that of max(S, 2) splits).  o is rounded to 16 bits
+ * once, from fp32.  Like the other KV-cache calls it never synchronises or allocates and can be captured in a graph. */
+int fa_ex_forward_kvcache_sink(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                               const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                               int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
+                               int64_t q_token_stride, int64_t k_cache_batch_stride, int64_t k_cache_token_stride,
+                               int64_t v_cache_batch_stride, int64_t v_cache_token_stride, int64_t k_new_batch_stride,
+                               int64_t k_new_token_stride, int64_t v_new_batch_stride, int64_t v_new_token_stride, int causal,
+                               int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
+                               const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, const int32_t* block_table,
+                               int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq,
+                               const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad,
+                               const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride,
+                               int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
+                               int cache_dtype, const float* k_descale, const float* v_descale, int64_t descale_batch_stride,
+                               const float* sinks, int64_t sink_heads, void* workspace, size_t workspace_bytes, void* stream);
+size_t fa_ex_kvcache_workspace_bytes_sink(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
+                                          int64_t d, int64_t num_splits);
+
 /* --- support entry points (no reference counterpart: the reference allocates inside the callee) --- */
 /* bytes for the CURRENT kernel mode: two float row constants per query row (+ an fp32 dQ scratch of bh*n*d floats in
  * FA_MODE_BWD_ATOMIC only); ask again after changing the mode */

@@ -33,6 +33,9 @@ kernel family (ex_path 3: the extended MFMA kernels), and without modifiers as t
 kernels for a square call) — forward and backward.
 
     python tools/bench_ex.py --softcap 30 --alibi [--causal] [--batch 8] [--q-heads 32] [--nq 4096] [--head-dim 128] [--rounds 3]
+Attention sinks (--sinks: one logit per head, shape (H,)): the same shapes, optionally with --window L,R; the call with sinks
+against the call without on the extended MFMA kernels (ex_path 3) and on the default path, alternated --rounds times:
+    python tools/bench_ex.py --sinks --causal [--window 1024,-1] [--batch 8] [--q-heads 32] [--nq 4096] [--head-dim 128] [--rounds 3]
 """
 import argparse
 import json
@@ -75,7 +78,10 @@ def main():
     ap.add_argument("--seed", type=int, default=0, help="(--varlen mix) the lengths' seed")
     ap.add_argument("--softcap", type=float, default=0.0, help="time the softcap (and --alibi) against the call without")
     ap.add_argument("--alibi", action="store_true", help="time ALiBi slopes (and --softcap) against the call without")
+    ap.add_argument("--sinks", action="store_true", help="time attention sinks ((H,) logits) against the call without")
     args = ap.parse_args()
+    if args.sinks:
+        return bench_sinks(args)
     if args.softcap > 0.0 or args.alibi:
         return bench_scoremod(args)
     if args.varlen:
@@ -367,6 +373,45 @@ def bench_scoremod(args):
                          fwd_ms_all=[round(x, 3) for x in times[name][0]], bwd_ms_all=[round(x, 3) for x in times[name][1]]))
     print(json.dumps(dict(shape=dict(batch=b, q_heads=h, n=n, d=d, dtype=args.dtype, causal=causal, softcap=args.softcap,
                                      alibi=args.alibi, iters=args.iters, rounds=args.rounds), rows=rows)))
+
+
+def bench_sinks(args):
+    dt = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[args.dtype]
+    b, h, n, d, causal = args.batch, args.q_heads, args.nq, args.head_dim, args.causal
+    bh, scale = b * h, args.head_dim ** -0.5
+    g = torch.Generator(device="cuda").manual_seed(0)
+    q, k, v, do = (torch.randn((bh, n, d), device="cuda", dtype=dt, generator=g) for _ in range(4))
+    sinks = torch.randn((h,), device="cuda", generator=g)
+    kw = {}
+    if args.window:
+        kw["window"] = tuple(int(x) for x in args.window.split(","))
+    o, lse = ext.ex_forward(q, k, v, causal, scale, sinks=sinks, **kw)
+    o0, lse0 = ext.ex_forward(q, k, v, causal, scale, **kw)
+    calls = {   # name: (ex_path, forward, backward)
+        "sinks": (0, lambda: ext.ex_forward(q, k, v, causal, scale, sinks=sinks, **kw),
+                  lambda: ext.ex_backward(q, k, v, o, do, lse, causal, scale, sinks=sinks, **kw)),
+        "none_ex_mfma": (3, lambda: ext.ex_forward(q, k, v, causal, scale, **kw),
+                         lambda: ext.ex_backward(q, k, v, o0, do, lse0, causal, scale, **kw)),
+        "none_auto": (0, lambda: ext.ex_forward(q, k, v, causal, scale, **kw),
+                      lambda: ext.ex_backward(q, k, v, o0, do, lse0, causal, scale, **kw)),
+    }
+    times = {name: ([], []) for name in calls}
+    try:
+        for _ in range(args.rounds):
+            for name, (path, f, bw) in calls.items():
+                ext.set_option("ex_path", path)
+                times[name][0].append(timed(f, args.iters))
+                times[name][1].append(timed(bw, args.iters))
+    finally:
+        ext.set_option("ex_path", 0)
+    med = {name: (sorted(t[0])[len(t[0]) // 2], sorted(t[1])[len(t[1]) // 2]) for name, t in times.items()}
+    rows = []
+    for name, (tf, tb) in med.items():
+        rows.append(dict(call=name, fwd_ms=round(tf, 3), bwd_ms=round(tb, 3), fwd_bwd_ms=round(tf + tb, 3),
+                         fwd_vs_ex=round(tf / med["none_ex_mfma"][0], 3), bwd_vs_ex=round(tb / med["none_ex_mfma"][1], 3),
+                         fwd_ms_all=[round(x, 3) for x in times[name][0]], bwd_ms_all=[round(x, 3) for x in times[name][1]]))
+    print(json.dumps(dict(shape=dict(batch=b, q_heads=h, n=n, d=d, dtype=args.dtype, causal=causal, window=args.window, sinks=True,
+                                     iters=args.iters, rounds=args.rounds), rows=rows)))
 
 
 if __name__ == "__main__":

@@ -82,6 +82,15 @@ def row(b, hq, hkv, lens, d, dtype, args):
             kc16 = vc16 = None
     t_kv = timed(lambda: ext.ex_kvcache_forward(q, kc, vc, None, None, sl, True, None, **dsc), args.warmup, args.iters, args.reps)
     t_app = timed(lambda: ext.ex_kvcache_forward(q, kc, vc, kn, vn, sl1, True, None, **dsc), args.warmup, args.iters, args.reps)
+    snk = {}
+    if args.sinks:   # the call with sinks (always through the combine) against the call without, alternated twice
+        sinks = torch.randn((hq,), device=dev)
+        with_s = lambda: ext.ex_kvcache_forward(q, kc, vc, None, None, sl, True, None, sinks=sinks, **dsc)   # noqa: E731
+        without = lambda: ext.ex_kvcache_forward(q, kc, vc, None, None, sl, True, None, **dsc)              # noqa: E731
+        ts = [timed(with_s, args.warmup, args.iters, args.reps), timed(without, args.warmup, args.iters, args.reps),
+              timed(with_s, args.warmup, args.iters, args.reps), timed(without, args.warmup, args.iters, args.reps)]
+        snk = dict(kv_sinks_us=[round(ts[0], 2), round(ts[2], 2)], kv_again_us=[round(ts[1], 2), round(ts[3], 2)],
+                   sinks_vs_kv=round((ts[0] + ts[2]) / (ts[1] + ts[3]), 3), sinks_extra_us=round((ts[0] + ts[2] - ts[1] - ts[3]) / 2, 2))
     rot = {}
     if args.rotary:
         half = d // 2
@@ -140,6 +149,7 @@ def row(b, hq, hkv, lens, d, dtype, args):
              speedup=None if t_ex is None else round(t_ex / t_kv, 2), kv_TBps=round(kv_bytes / t_kv / 1e6, 3),
              frac_copy_rate=round(kv_bytes / t_kv / 1e6 / (COPY_RATE / 1e12), 3))
     r.update(rot)
+    r.update(snk)
     for ps, t in paged.items():
         r[f"paged_{ps}_us"] = round(t, 2)
         r[f"paged_{ps}_TBps"] = round(kv_bytes / t / 1e6, 3)
@@ -163,6 +173,8 @@ def main():
     ap.add_argument("--rotary", action="store_true", help="also time the append with fused rotary embedding, and with torch rotating first")
     ap.add_argument("--cache-dtype", default="16", choices=("16", "e4m3"),
                     help="16: the caches in --dtype; e4m3: quantised once to float8_e4m3fn with per-(b, head) scales")
+    ap.add_argument("--sinks", action="store_true", help="also time the call with attention sinks ((H_q,) logits) against the call without")
+    ap.add_argument("--lens", default="1024,8192,32768,131072", help="the grid's cache lengths")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16
@@ -177,7 +189,7 @@ def main():
     rows = []
     for b in (1, 8, 32):
         for hkv in (8, 32):
-            for L in (1024, 8192, 32768, 131072):
+            for L in (int(x) for x in args.lens.split(",")):
                 if b * L > args.max_tokens:
                     continue
                 rows.append(row(b, 32, hkv, [L] * b, args.d, dtype, args))
