@@ -239,7 +239,8 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_sin=None, cache_seqlens=None,
                             cache_batch_idx=None, cache_leftpad=None, block_table=None, softmax_scale=None, causal=False,
                             window_size=(-1, -1), softcap=0.0, rotary_interleaved=True, alibi_slopes=None, num_splits=0,
-                            return_softmax_lse=False, *, sinks=None, k_descale=None, v_descale=None):
+                            return_softmax_lse=False, *, cu_seqlens_q=None, cu_seqlens_k_new=None, max_seqlen_q=None, sinks=None,
+                            k_descale=None, v_descale=None):
     """FlashAttention-2's flash_attn_with_kvcache (forward; its argument order): q (B, Nq, H_q, d); k_cache, v_cache
     (B, cache_len, H_kv, d) with H_q % H_kv == 0, updated in place — k, v (B, N_new, H_kv, d) are written at
     cache_seqlens[b] .. + N_new before attention, and a cache view the library cannot take without a copy raises ValueError.
@@ -262,8 +263,19 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     as they are appended (after the rotation), with saturation at +-448.  Other 8-bit dtypes raise NotImplementedError.
     sinks (keyword-only, as k_descale and v_descale now are: FlashAttention-2's positional order ends before them): float32 (H_q,) attention sinks on q's device, one extra softmax column per query head with a zero value
     (flash_attention_ex); the returned lse contains it, and a sequence without any key gives o = 0, lse = sink.
+    cu_seqlens_q, cu_seqlens_k_new, max_seqlen_q (keyword-only; FlashAttention-3's): one call for sequences that bring different
+    numbers of tokens, a continuous-batching step.  With cu_seqlens_q (int32 (B + 1,) on the device) and max_seqlen_q (an int)
+    q is packed (total_q, H_q, d) — a token-strided view such as qkv[:, 0] is used without a copy — and sequence b owns tokens
+    [cu_seqlens_q[b], cu_seqlens_q[b + 1]), at most max_seqlen_q, none allowed.  With cu_seqlens_k_new (int32 (B + 1,); needs k,
+    v and cu_seqlens_q) k and v are packed (total_k_new, H_kv, d) and sequence b appends its own number of tokens; without it k,
+    v stay (B, N_new, H_kv, d) or None.  Each sequence gets exactly what the padded call returns for it alone, with its own
+    causal diagonal len_k_b - nq_b; one without q tokens still appends.  The arrays are never read on the host and may hold
+    anything: the kernels clamp them to the tensors.  Rotary then needs seqlen_ro >= capacity + max_seqlen_q.  A 4-D q with
+    cu_seqlens_q, a missing max_seqlen_q, or a packed q that would need a copy raises ValueError.  o is then (total_q, H_q, d) and
+    lse (H_q, total_q).
     Returns o (B, Nq, H_q, d), and with return_softmax_lse also lse (B, H_q, Nq) float32.  No gradient."""
-    for name, val in (("block_table", block_table), ("cache_batch_idx", cache_batch_idx), ("cache_leftpad", cache_leftpad)):
+    for name, val in (("block_table", block_table), ("cache_batch_idx", cache_batch_idx), ("cache_leftpad", cache_leftpad),
+                      ("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k_new", cu_seqlens_k_new)):
         if val is not None and not (isinstance(val, torch.Tensor) and val.dtype == torch.int32):
             dt = val.dtype if isinstance(val, torch.Tensor) else type(val).__name__
             raise NotImplementedError(f"flash_attn_with_kvcache: {name} of dtype {dt} is not supported (int32 tensor expected)")
@@ -280,6 +292,8 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     if isinstance(alibi_slopes, torch.Tensor):
         alibi_slopes = alibi_slopes.detach()
     extra = {} if sinks is None else {"sinks": sinks.detach() if isinstance(sinks, torch.Tensor) else sinks}
+    if cu_seqlens_q is not None or cu_seqlens_k_new is not None or max_seqlen_q is not None:
+        extra.update(cu_seqlens_q=cu_seqlens_q, cu_seqlens_k_new=cu_seqlens_k_new, max_seqlen_q=max_seqlen_q)
     with torch.no_grad():
         o, lse = ext.ex_kvcache_forward(q.detach(), k_cache, v_cache, None if k is None else k.detach(),
                                         None if v is None else v.detach(), cache_seqlens, bool(causal), softmax_scale,

@@ -871,10 +871,21 @@ size_t fa_ex_kvcache_workspace_bytes_sink(int64_t batch, int64_t heads_q, int64_
     return fa::kv_workspace_bytes(batch, heads_q, seqlen_q, d, (int)(S < 2 ? 2 : S));
 }
 
+// packed queries: S from max_seqlen_q's row tiles (shapes only), partials for total_q tokens; with_sinks: at least two splits
+size_t fa_ex_kvcache_workspace_bytes_varlen(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t max_seqlen_q,
+                                            int64_t cache_len, int64_t d, int64_t num_splits, int with_sinks) {
+    if (batch <= 0 || heads_q <= 0 || heads_kv <= 0 || heads_q % heads_kv != 0 || total_q <= 0 || max_seqlen_q <= 0 ||
+        max_seqlen_q > total_q || d <= 0 || cache_len < 0 || num_splits < 0 || num_splits > 256)
+        return 0;
+    const int64_t S = kv_splits(batch, heads_q, heads_kv, max_seqlen_q, cache_len, num_splits);
+    return fa::kv_workspace_bytes(1, heads_q, total_q, d, (int)(with_sinks && S < 2 ? 2 : S));
+}
+
 // who: the entry point's name.  After stream come the eight arguments fa_ex_forward_kvcache_paged adds (all null / 0 is
 // fa_ex_forward_kvcache), then the seven fa_ex_forward_kvcache_rotary adds (all null / 0 is fa_ex_forward_kvcache_paged), then the
 // four fa_ex_forward_kvcache_fp8 adds (cache_dtype = dtype, null, null, 0 is fa_ex_forward_kvcache_rotary), then the two
-// fa_ex_forward_kvcache_sink adds (null sinks is fa_ex_forward_kvcache_fp8).
+// fa_ex_forward_kvcache_sink adds (null sinks is fa_ex_forward_kvcache_fp8), then the five fa_ex_forward_kvcache_varlen adds
+// (null, null, 0, 0, 0 is fa_ex_forward_kvcache_sink).
 static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
                         const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
                         int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
@@ -887,7 +898,9 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
                         int64_t cache_batch, const int32_t* cache_leftpad, const void* rotary_cos, const void* rotary_sin,
                         int64_t rotary_cos_row_stride, int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim,
                         int rotary_interleaved, int cache_dtype, const float* k_descale, const float* v_descale,
-                        int64_t descale_batch_stride, const float* sinks = nullptr, int64_t sink_heads = 1) {
+                        int64_t descale_batch_stride, const float* sinks = nullptr, int64_t sink_heads = 1,
+                        const int32_t* cu_seqlens_q = nullptr, const int32_t* cu_seqlens_k_new = nullptr, int64_t total_q = 0,
+                        int64_t max_seqlen_q = 0, int64_t total_k_new = 0) {
     if (dtype != FA_DTYPE_F16 && dtype != FA_DTYPE_BF16)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: dtype must be f16 or bf16 (got code %d)", who, dtype);
     // the cache's element type: q's, or e4m3 with a dequantisation scale per (sequence, K/V head)
@@ -910,7 +923,31 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
     if (heads_kv < 1 || heads_q < 1 || heads_q % heads_kv != 0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads_q=%lld must be a positive multiple of heads_kv=%lld", who, (long long)heads_q,
                     (long long)heads_kv);
-    if (seqlen_q < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_q must be >= 1 (got %lld)", who, (long long)seqlen_q);
+    // packed queries / new keys: from here on seqlen_q stands for max_seqlen_q, the bound on every sequence's tokens (the grid,
+    // the split rule and the window take it), and q is one unit of tokens at q_token_stride
+    const bool vq = cu_seqlens_q != nullptr, vk = cu_seqlens_k_new != nullptr;
+    if (!vq && (total_q != 0 || max_seqlen_q != 0))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: total_q and max_seqlen_q must be 0 without cu_seqlens_q (got %lld, %lld)", who,
+                    (long long)total_q, (long long)max_seqlen_q);
+    if (!vk && total_k_new != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: total_k_new must be 0 without cu_seqlens_k_new (got %lld)", who, (long long)total_k_new);
+    if (vk && !vq) return fail(FA_ERR_INVALID_ARGUMENT, "%s: cu_seqlens_k_new needs cu_seqlens_q", who);
+    if (vk && (!k_new || !v_new)) return fail(FA_ERR_INVALID_ARGUMENT, "%s: cu_seqlens_k_new needs k_new and v_new", who);
+    if ((uintptr_t)cu_seqlens_q % 4 != 0 || (uintptr_t)cu_seqlens_k_new % 4 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: cu_seqlens_q and cu_seqlens_k_new must be 4-byte aligned", who);
+    if (vq) {
+        if (total_q < 0 || total_q > 0x7fffffff)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: total_q must lie in [0, 2^31) (got %lld)", who, (long long)total_q);
+        if (max_seqlen_q < 0 || max_seqlen_q > total_q)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: max_seqlen_q=%lld must lie in [0, total_q=%lld]", who, (long long)max_seqlen_q,
+                        (long long)total_q);
+        seqlen_q = max_seqlen_q;
+        q_batch_stride = 0;
+    } else if (seqlen_q < 1) {
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_q must be >= 1 (got %lld)", who, (long long)seqlen_q);
+    }
+    if (vk && (total_k_new < 0 || total_k_new > 0x7fffffff))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: total_k_new must lie in [0, 2^31) (got %lld)", who, (long long)total_k_new);
     {   // attention sinks: head h of every sequence takes sinks[h % sink_heads]
         SinkArg sk;
         sk.sinks = sinks; sk.heads = sink_heads;
@@ -954,6 +991,10 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
     if ((uintptr_t)cache_batch_idx % 4 != 0 || (uintptr_t)cache_leftpad % 4 != 0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_batch_idx and cache_leftpad must be 4-byte aligned", who);
     if (cache_len < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_len must be >= 1 (got %lld)", who, (long long)cache_len);
+    if (vk) {   // seqlen_new stands for the most tokens one sequence can append (the device clamps nnew_b to it)
+        seqlen_new = total_k_new < cache_len ? total_k_new : cache_len;
+        k_new_batch_stride = v_new_batch_stride = 0;
+    }
     if (seqlen_new < 0 || seqlen_new > cache_len)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_new=%lld must lie in [0, cache_len=%lld]", who, (long long)seqlen_new,
                     (long long)cache_len);
@@ -965,11 +1006,11 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
     // an e4m3 cache may hold twice the tokens of a 16-bit one)
     const int64_t c_esz = e4m3 ? 1 : 2;
     struct { const char* name; int64_t bs, ts, n, heads, units, esz; } st[5] = {
-        {"q", q_batch_stride, q_token_stride, seqlen_q, heads_q, batch, 2},
+        {"q", q_batch_stride, q_token_stride, seqlen_q, heads_q, vq ? 1 : batch, 2},
         {"k_cache", k_cache_batch_stride, k_cache_token_stride, c_n, heads_kv, c_units, c_esz},
         {"v_cache", v_cache_batch_stride, v_cache_token_stride, c_n, heads_kv, c_units, c_esz},
-        {"k_new", k_new_batch_stride, k_new_token_stride, seqlen_new, heads_kv, batch, 2},
-        {"v_new", v_new_batch_stride, v_new_token_stride, seqlen_new, heads_kv, batch, 2}};
+        {"k_new", k_new_batch_stride, k_new_token_stride, seqlen_new, heads_kv, vk ? 1 : batch, 2},
+        {"v_new", v_new_batch_stride, v_new_token_stride, seqlen_new, heads_kv, vk ? 1 : batch, 2}};
     for (int i = 0; i < (seqlen_new > 0 ? 5 : 3); ++i) {
         const int64_t span = (st[i].n - 1) * st[i].ts + st[i].heads * d;   // elements of one batch element (or page)
         if (st[i].ts < st[i].heads * d || (st[i].units > 1 && st[i].bs < span) || st[i].bs < 0)
@@ -996,11 +1037,12 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
                         (long long)d, (long long)rotary_dim);
         if (seqlen_new < 1 || !cache_seqlens)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary needs seqlen_new > 0 (k_new, v_new) and cache_seqlens", who);
-        const int64_t ro_need = cache_len + (seqlen_q > seqlen_new ? seqlen_q - seqlen_new : 0);
+        // (packed queries: nq_b - nnew_b is not known here; nq_b <= max_seqlen_q)
+        const int64_t ro_need = cache_len + (vq ? max_seqlen_q : seqlen_q > seqlen_new ? seqlen_q - seqlen_new : 0);
         if (seqlen_ro < ro_need)
             return fail(FA_ERR_INVALID_ARGUMENT,
-                        "%s: seqlen_ro=%lld must be >= capacity + max(0, seqlen_q - seqlen_new) = %lld (the tables are not bounds-checked on "
-                        "the device)", who, (long long)seqlen_ro, (long long)ro_need);
+                        "%s: seqlen_ro=%lld must be >= capacity + %s = %lld (the tables are not bounds-checked on the device)", who,
+                        (long long)seqlen_ro, vq ? "max_seqlen_q" : "max(0, seqlen_q - seqlen_new)", (long long)ro_need);
         if (rotary_cos_row_stride < rotary_dim / 2 || rotary_sin_row_stride < rotary_dim / 2 ||
             rotary_cos_row_stride > ((int64_t)1 << 40) || rotary_sin_row_stride > ((int64_t)1 << 40))
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary row strides (%lld, %lld) must be >= rotary_dim / 2 = %lld (and <= 2^40)", who,
@@ -1033,18 +1075,22 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
         return fail(FA_ERR_UNSUPPORTED, "%s: problem too large for one launch", who);
     int64_t S = kv_splits(batch, heads_q, heads_kv, seqlen_q, cache_len, num_splits);
     if (sinks && S < 2) S = 2;   // the sink joins in the combine: where the rule or the caller gives one split, two are launched
-    if (S > 1 && batch * heads_q * seqlen_q >= ((int64_t)1 << 26))   // the combine: one wave per row, 2^32 lanes per launch
-        return fail(FA_ERR_UNSUPPORTED, "%s: batch * heads_q * seqlen_q = %lld rows are too many to combine %lld splits in one launch",
-                    who, (long long)(batch * heads_q * seqlen_q), (long long)S);
+    const int64_t q_rows = vq ? heads_q * total_q : batch * heads_q * seqlen_q;
+    if (S > 1 && q_rows >= ((int64_t)1 << 26))   // the combine: one wave per row, 2^32 lanes per launch
+        return fail(FA_ERR_UNSUPPORTED, "%s: %s = %lld rows are too many to combine %lld splits in one launch", who,
+                    vq ? "heads_q * total_q" : "batch * heads_q * seqlen_q", (long long)q_rows, (long long)S);
     // Canonical window: a bound that cuts no key in any row is -1 (len_k <= cache_len: key 0 is in every row's band once
     // window_left >= cache_len - 1, key len_k - 1 once window_right >= seqlen_q - 1), so the bounds the kernels take in int
     // stay below 2^28 and the band arithmetic cannot overflow.
     if (window_left >= cache_len - 1) window_left = -1;
     if (window_right >= seqlen_q - 1) window_right = -1;
-    const size_t need = fa::kv_workspace_bytes(batch, heads_q, seqlen_q, d, (int)S);
+    const size_t need = vq ? (seqlen_q > 0 ? fa::kv_workspace_bytes(1, heads_q, total_q, d, (int)S) : 0)
+                           : fa::kv_workspace_bytes(batch, heads_q, seqlen_q, d, (int)S);
     if (workspace_bytes < need || (need > 0 && !workspace))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
-    if (!q || !k_cache || !v_cache || !o || !lse) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    // (packed queries without a token: q, o and lse are empty and may be null)
+    if (!k_cache || !v_cache || ((!q || !o || !lse) && !(vq && total_q == 0)))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
     if (e4m3) {   // an 8-element chunk of an e4m3 cache is 8 bytes: one load or store of 8 bytes, 8-byte aligned
         if ((uintptr_t)k_cache % 8 != 0 || (uintptr_t)v_cache % 8 != 0)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: an e4m3 k_cache / v_cache must be 8-byte aligned", who);
@@ -1069,6 +1115,9 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
     a.rotary_dim = rotary_dim; a.rotary_interleaved = rotary_interleaved ? 1 : 0; a.rotary_q_per_token = rotary_cos ? rotary_q_per_token : 0;
     a.cache_e4m3 = e4m3 ? 1 : 0; a.k_descale = k_descale; a.v_descale = v_descale; a.descale_bstride = descale_batch_stride;
     a.sinks = sinks; a.sink_heads = sinks ? sink_heads : 1;
+    a.cu_seqlens_q = cu_seqlens_q; a.cu_seqlens_k_new = cu_seqlens_k_new;
+    a.total_q = total_q; a.max_seqlen_q = max_seqlen_q; a.total_k_new = total_k_new;
+    if (vq && seqlen_q == 0 && seqlen_new == 0) return FA_OK;   // no query token and nothing to append: no launch
     hipError_t e = fa::launch_kvcache(a, reinterpret_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
     return FA_OK;
@@ -1179,6 +1228,33 @@ int fa_ex_forward_kvcache_sink(const void* q, void* k_cache, void* v_cache, cons
                         num_blocks, page_block_size, max_blocks_per_seq, cache_batch_idx, cache_batch, cache_leftpad, rotary_cos,
                         rotary_sin, rotary_cos_row_stride, rotary_sin_row_stride, seqlen_ro, rotary_dim, rotary_interleaved, cache_dtype,
                         k_descale, v_descale, descale_batch_stride, sinks, sink_heads);
+}
+
+int fa_ex_forward_kvcache_varlen(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                                 const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                                 int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
+                                 int64_t q_token_stride, int64_t k_cache_batch_stride, int64_t k_cache_token_stride,
+                                 int64_t v_cache_batch_stride, int64_t v_cache_token_stride, int64_t k_new_batch_stride,
+                                 int64_t k_new_token_stride, int64_t v_new_batch_stride, int64_t v_new_token_stride, int causal,
+                                 int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
+                                 const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, const int32_t* block_table,
+                                 int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq,
+                                 const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad,
+                                 const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride,
+                                 int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
+                                 int cache_dtype, const float* k_descale, const float* v_descale, int64_t descale_batch_stride,
+                                 const float* sinks, int64_t sink_heads, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k_new,
+                                 int64_t total_q, int64_t max_seqlen_q, int64_t total_k_new, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+    return kvcache_impl("fa_ex_forward_kvcache_varlen", q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, batch, heads_q, heads_kv,
+                        seqlen_q, seqlen_new, cache_len, d, dtype, q_batch_stride, q_token_stride, k_cache_batch_stride,
+                        k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride, k_new_batch_stride, k_new_token_stride,
+                        v_new_batch_stride, v_new_token_stride, causal, window_left, window_right, softmax_scale, softcap, alibi_slopes,
+                        alibi_batch_stride, num_splits, workspace, workspace_bytes, stream, block_table, block_table_row_stride,
+                        num_blocks, page_block_size, max_blocks_per_seq, cache_batch_idx, cache_batch, cache_leftpad, rotary_cos,
+                        rotary_sin, rotary_cos_row_stride, rotary_sin_row_stride, seqlen_ro, rotary_dim, rotary_interleaved, cache_dtype,
+                        k_descale, v_descale, descale_batch_stride, sinks, sink_heads, cu_seqlens_q, cu_seqlens_k_new, total_q,
+                        max_seqlen_q, total_k_new);
 }
 
 size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {

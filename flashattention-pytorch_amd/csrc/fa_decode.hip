@@ -36,6 +36,14 @@
 //   token i at L_b - P_b + i when causal or a window bound was given (qseq), else at L_b - P_b.  q is rotated in the prologue, after
 //   the fragments are loaded; nothing of it lives into the key loop.  The tables are read without a device check: the C layer
 //   requires seqlen_ro >= capacity + max(0, seqlen_q - seqlen_new), and L_b <= capacity - seqlen_new after the clamp.
+// fa_ex_forward_kvcache_varlen packs the queries and the new keys (KvParams::cu_q, cu_kn; null = the padded call): q and o
+// are (total_q, H_q, d), lse and the partials (H_q, total_q)-major, k_new / v_new (total_k_new, H_kv, d).  Sequence b owns the
+// tokens kv_cu_range gives it (untrusted offsets, clamped so that no content leaves the tensors): nq_b query tokens, nnew_b new
+// keys, len_k = L_b + nnew_b - P_b and coff = len_k - nq_b as if it were the padded call on b alone.  The split grid is sized for
+// max_seqlen_q; a wave whose row tile lies past G * nq_b leaves before its first load.  The append takes its loop bound and its
+// source rows from the device.  The combine runs per (packed token, h_q) without a sequence index; tokens that no sequence
+// owns are told by the fill the host puts into the lse partials (kv_combine_row) and stay unwritten.  All of it is wave-uniform
+// scalar work in the existing instantiations, a null test on cu_q / cu_kn as for bidx / leftpad.
 #include "fa_common.h"
 #include "fa_ex_common.h"
 #include "fa_kernels.h"
@@ -75,13 +83,45 @@ struct KvParams {
     int al_bs;
     float scale, c_log2;
     ExScore sc;                                   // cap_k / cap_a (softcap > 0) and al_k, as the extended kernels take them
+    // fa_ex_forward_kvcache_varlen (null: the padded call): untrusted device offsets of the packed q / k_new tokens
+    const int *cu_q, *cu_kn;
+    int total_q, max_q, total_kn;                 // tokens of q / o, the host's bound on nq_b, tokens of k_new / v_new
 };
 
-// L_b (the cache_seqlens clamp), P_b (the cache_leftpad clamp: the sequence's first cache position) and len_k = L_b + N_new - P_b
-__device__ __forceinline__ int kv_len_k(const KvParams& p, int b, int& L, int& P) {
-    L = p.seqlens ? min(max(p.seqlens[b], 0), p.cap - p.nnew) : p.cap;
+// One sequence's share of a packed tensor of total tokens, from untrusted offsets: its first token start = clamp(cu[b], 0, total)
+// and its n = clamp(cu[b + 1] - cu[b], 0, min(cap, total - start)) tokens, so start + n <= total whatever cu holds.
+// tests/kvcache_varlen_ref.py models this clamp.
+__device__ __forceinline__ int kv_cu_range(const int* cu, int b, int total, int cap, int& start) {
+    const long long c0 = cu[b], c1 = cu[b + 1];
+    start = (int)min(max(c0, 0LL), (long long)total);
+    return (int)min(max(c1 - c0, 0LL), (long long)min(cap, total - start));
+}
+
+// nq_b and the sequence's first packed q token (cu_seqlens_q), or the call's seqlen_q and token b * seqlen_q
+__device__ __forceinline__ int kv_seq_q(const KvParams& p, int b, long long& start) {
+    if (p.cu_q) {
+        int st;
+        const int n = kv_cu_range(p.cu_q, b, p.total_q, p.max_q, st);
+        start = st;
+        return n;
+    }
+    start = (long long)b * p.nq;
+    return p.nq;
+}
+
+// nnew_b and the sequence's first packed k_new token (cu_seqlens_k_new), or the call's seqlen_new
+__device__ __forceinline__ int kv_seq_new(const KvParams& p, int b, int& start) {
+    if (p.cu_kn) return kv_cu_range(p.cu_kn, b, p.total_kn, p.cap, start);
+    start = 0;
+    return p.nnew;
+}
+
+// L_b (the cache_seqlens clamp), P_b (the cache_leftpad clamp: the sequence's first cache position) and len_k = L_b + nnew_b - P_b
+// (nnew: the sequence's new tokens, kv_seq_new)
+__device__ __forceinline__ int kv_len_k(const KvParams& p, int b, int nnew, int& L, int& P) {
+    L = p.seqlens ? min(max(p.seqlens[b], 0), p.cap - nnew) : p.cap;
     P = p.leftpad ? min(max(p.leftpad[b], 0), L) : 0;
-    return L + p.nnew - P;
+    return L + nnew - P;
 }
 
 // Rotary embedding (fa_ex_forward_kvcache_rotary): the second argument of the *_rot kernels
@@ -131,12 +171,12 @@ __device__ __forceinline__ u32x4 kv_rotate_chunk(const KvRot& ro, long long pos,
 }
 
 // Keys [kbeg, kend) of split s of S for the row tile whose query tokens are [qlo, qhi]: the union of the rows' bands,
-// [max(0, qlo + coff - wl), min(len_k, qhi + coff + wr + 1)), cut into 32-key tiles from its start, tiles
+// [max(0, qlo + coff - wl), min(len_k, qhi + coff + wr + 1)) with coff = len_k - nq_b, cut into 32-key tiles from its start, tiles
 // [floor(s nt / S), floor((s + 1) nt / S)) to split s.  Empty (kbeg >= kend) when the band is, or nt < S for some s.
 // tests/test_kvcache_cpu.py models this rule.
-__device__ __forceinline__ void kv_split_range(const KvParams& p, int lk, int qlo, int qhi, int s, int S, int& kbeg, int& kend) {
+__device__ __forceinline__ void kv_split_range(const KvParams& p, int lk, int nq, int qlo, int qhi, int s, int S, int& kbeg, int& kend) {
     constexpr int KT = 32;
-    const int coff = lk - p.nq;
+    const int coff = lk - nq;
     const int lo = max(0, qlo + coff - p.wl), hi = min(lk, qhi + coff + p.wr + 1);
     const int nt = hi > lo ? (hi - lo + KT - 1) / KT : 0;
     const int t0 = (int)((long long)s * nt / S), t1 = (int)((long long)(s + 1) * nt / S);
@@ -212,7 +252,26 @@ template <typename Tag> __device__ __forceinline__ u32x2 kv_q8_quant(u32x4 x, fl
 #undef KV_ROT
 #undef KV_Q8
 
-// One wave per (b, h_q, token) row, four rows per workgroup.  The lanes read the S lse partials side by side (lane c: splits
+// The combine's row -> its query head h and the index of its (token, head) row of o.  Padded: row = (b * hq + h) * nq + qi.
+// Packed (cu_q): row = h * total_q + packed token, no sequence index; the host fills plse with kPlseFill bytes before the split
+// kernel runs, every wave of which writes the lse partial of each row it owns, so a row whose first partial still holds the
+// fill belongs to no sequence: false, and the wave leaves without writing.
+constexpr int kPlseFill = 0xff;
+__device__ __forceinline__ bool kv_combine_row(const KvParams& p, long long row, const float* pl, int& h, long long& orow) {
+    if (p.cu_q) {
+        h = (int)(row / p.total_q);
+        orow = (row - (long long)h * p.total_q) * p.hq + h;
+        return __float_as_uint(pl[0]) != 0xffffffffu;
+    }
+    const long long bh = row / p.nq;
+    const int qi = (int)(row - bh * p.nq);
+    h = (int)(bh % p.hq);
+    orow = ((bh / p.hq) * p.nq + qi) * p.hq + h;
+    return true;
+}
+
+// One wave per (b, h_q, token) row (packed queries: per (h_q, packed token)), four rows per workgroup.  The lanes read the S
+// lse partials side by side (lane c: splits
 // c, c + 64, ..), reduce max and weight sum over the wave in a fixed shuffle order, and park the weights in LDS; then lane c adds
 // head dims 4c .. 4c + 3 of the O partials in split order, eight loads in flight, branch-free: a split with lse_s = -inf (empty,
 // or no visible key) has weight 0 and its O partial, which it never wrote, is selected away.  A row without any visible key gives
@@ -224,6 +283,9 @@ __global__ __launch_bounds__(256) void kv_combine_kernel(KvParams p, int S, long
     const long long row = (long long)blockIdx.x * 4 + wv;
     if (row >= nrows) return;   // (wave-uniform; the LDS rows are wave-private, no barrier)
     const float* pl = p.plse + row * S;
+    int h;
+    long long orow;
+    if (!kv_combine_row(p, row, pl, h, orow)) return;
     float m = -INFINITY;
     for (int s = c; s < S; s += 64) m = fmaxf(m, pl[s]);
 #pragma unroll
@@ -248,15 +310,11 @@ __global__ __launch_bounds__(256) void kv_combine_kernel(KvParams p, int S, long
         }
     }
     const float inv = sum > 0.f ? 1.f / sum : 0.f;
-    // row = (b * hq + h) * nq + qi  ->  o (b, qi, h)
-    const long long bh = row / p.nq;
-    const int qi = (int)(row - bh * p.nq), h = (int)(bh % p.hq);
-    const long long b = bh / p.hq;
     if (4 * c < DR) {
         u32x2 v;
         v[0] = pack2_rn<Tag>(acc[0] * inv, acc[1] * inv);
         v[1] = pack2_rn<Tag>(acc[2] * inv, acc[3] * inv);
-        *reinterpret_cast<u32x2*>(p.o + ((b * p.nq + qi) * p.hq + h) * DR + 4 * c) = v;
+        *reinterpret_cast<u32x2*>(p.o + orow * DR + 4 * c) = v;
     }
     if (c == 0) p.lse[row] = sum > 0.f ? m + logf(sum) : -INFINITY;
 }
@@ -274,12 +332,11 @@ __global__ __launch_bounds__(256) void kv_combine_sink_kernel(KvParams p, int S,
     const int wv = threadIdx.x >> 6, c = threadIdx.x & 63, DR = p.d;
     const long long row = (long long)blockIdx.x * 4 + wv;
     if (row >= nrows) return;   // (wave-uniform; the LDS rows are wave-private, no barrier)
-    // row = (b * hq + h) * nq + qi  ->  o (b, qi, h)
-    const long long bh = row / p.nq;
-    const int qi = (int)(row - bh * p.nq), h = (int)(bh % p.hq);
-    const long long b = bh / p.hq;
-    const float snk = sinks[h % sink_heads];
     const float* pl = p.plse + row * S;
+    int h;
+    long long orow;
+    if (!kv_combine_row(p, row, pl, h, orow)) return;
+    const float snk = sinks[h % sink_heads];
     float m = -INFINITY;
     for (int s = c; s < S; s += 64) m = fmaxf(m, pl[s]);
 #pragma unroll
@@ -310,7 +367,7 @@ __global__ __launch_bounds__(256) void kv_combine_sink_kernel(KvParams p, int S,
         u32x2 v;
         v[0] = pack2_rn<Tag>(acc[0] * inv, acc[1] * inv);
         v[1] = pack2_rn<Tag>(acc[2] * inv, acc[3] * inv);
-        *reinterpret_cast<u32x2*>(p.o + ((b * p.nq + qi) * p.hq + h) * DR + 4 * c) = v;
+        *reinterpret_cast<u32x2*>(p.o + orow * DR + 4 * c) = v;
     }
     if (c == 0) p.lse[row] = sum > 0.f ? m + logf(sum) : -INFINITY;
 }
@@ -341,8 +398,9 @@ template <typename Tag>
 hipError_t launch_kv_t(const KvParams& p, const KvRot& ro, const KvQ8* q8, int S, int row_tiles, int batch, hipStream_t st,
                        const float* sinks, int sink_heads) {
     hipError_t e = hipSuccess;
-    if (p.nnew > 0) {
-        const long long per_b = (long long)p.nnew * p.hkv * (p.d / 8);
+    if (p.cu_kn ? p.total_kn > 0 : p.nnew > 0) {
+        // (packed k_new: a sequence has at most total_kn tokens; the kernel's loop takes its bound from the device)
+        const long long per_b = (long long)(p.cu_kn ? p.total_kn : p.nnew) * p.hkv * (p.d / 8);
         const dim3 grid((unsigned)std::min<long long>((per_b + 255) / 256, 1024), (unsigned)batch);
         if (q8 && ro.cos) hipLaunchKernelGGL(kv_append_rot_q8_kernel<Tag>, grid, dim3(256), 0, st, p, ro, *q8);
         else if (q8) hipLaunchKernelGGL(kv_append_q8_kernel<Tag>, grid, dim3(256), 0, st, p, *q8);
@@ -351,11 +409,16 @@ hipError_t launch_kv_t(const KvParams& p, const KvRot& ro, const KvQ8* q8, int S
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
+    if (row_tiles == 0) return e;   // packed queries without a token: the append was the call
+    if (p.cu_q && S > 1) {          // rows that no sequence owns keep this fill: kv_combine_row
+        e = hipMemsetAsync(p.plse, kPlseFill, (size_t)p.total_q * p.hq * S * 4, st);
+        if (e != hipSuccess) return e;
+    }
     if (p.d <= 64) e = launch_split<Tag, 64>(p, ro, q8, S, row_tiles, batch, st);
     else if (p.d <= 128) e = launch_split<Tag, 128>(p, ro, q8, S, row_tiles, batch, st);
     else e = launch_split<Tag, 256>(p, ro, q8, S, row_tiles, batch, st);
     if (e != hipSuccess || S == 1) return e;
-    const long long nrows = (long long)batch * p.hq * p.nq;
+    const long long nrows = p.cu_q ? (long long)p.total_q * p.hq : (long long)batch * p.hq * p.nq;
     if (sinks)
         hipLaunchKernelGGL((kv_combine_sink_kernel<Tag>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st, p, S, nrows, sinks, sink_heads);
     else
@@ -394,6 +457,8 @@ hipError_t launch_kvcache(const KvArgs& a, hipStream_t st) {
     p.hq = (int)a.heads_q; p.hkv = (int)a.heads_kv; p.G = (int)(a.heads_q / a.heads_kv);
     p.nq = (int)a.seqlen_q; p.nnew = (int)a.seqlen_new; p.cap = (int)a.cache_len; p.d = (int)a.d;
     p.rows = p.G * p.nq;
+    p.cu_q = a.cu_seqlens_q; p.cu_kn = a.cu_seqlens_k_new;
+    p.total_q = (int)a.total_q; p.max_q = (int)a.max_seqlen_q; p.total_kn = (int)a.total_k_new;
     p.wl = a.window_left >= 0 ? (int)a.window_left : kWinNone;
     p.wr = a.causal ? 0 : (a.window_right >= 0 ? (int)a.window_right : kWinNone);
     p.al_bs = (int)a.alibi_bstride;
@@ -410,8 +475,8 @@ hipError_t launch_kvcache(const KvArgs& a, hipStream_t st) {
     if (a.sinks && S < 2) return hipErrorInvalidValue;   // (the C layer raises a sink call's S to 2: the sink joins in the combine)
     p.po = (float*)a.workspace;
     // workspace (S > 1): the O partials, then the lse partials, each rounded up to 256 bytes (kv_workspace_bytes)
-    p.plse = S > 1 ? (float*)((char*)a.workspace + (((size_t)a.batch * a.heads_q * a.seqlen_q * S * a.d * 4 + 255) & ~(size_t)255))
-                   : nullptr;
+    const size_t q_rows = a.cu_seqlens_q ? (size_t)a.total_q * a.heads_q : (size_t)a.batch * a.heads_q * a.seqlen_q;
+    p.plse = S > 1 ? (float*)((char*)a.workspace + ((q_rows * S * a.d * 4 + 255) & ~(size_t)255)) : nullptr;
     KvRot ro{};
     ro.cos = (const uint16_t*)a.rotary_cos; ro.sin = (const uint16_t*)a.rotary_sin;
     ro.cos_rs = a.rotary_cos_rs; ro.sin_rs = a.rotary_sin_rs;
@@ -419,7 +484,7 @@ hipError_t launch_kvcache(const KvArgs& a, hipStream_t st) {
     const KvQ8 q8{a.k_descale, a.v_descale, (long long)a.descale_bstride};
     const KvQ8* q8p = a.cache_e4m3 ? &q8 : nullptr;
     const int batch = (int)a.batch;
-    const int row_tiles = (p.rows + 15) / 16;
+    const int row_tiles = ((a.cu_seqlens_q ? p.G * p.max_q : p.rows) + 15) / 16;
     const int sink_heads = (int)(a.sink_heads > 0 ? a.sink_heads : 1);
     return a.dtype == 1 ? launch_kv_t<f16_tag>(p, ro, q8p, S, row_tiles, batch, st, a.sinks, sink_heads)
                         : launch_kv_t<bf16_tag>(p, ro, q8p, S, row_tiles, batch, st, a.sinks, sink_heads);

@@ -4,9 +4,11 @@
 // Two more inclusions with KV_Q8 1 give the same four kernels for an e4m3 cache (kv_*_q8_kernel, a KvQ8 as last argument):
 // the cache is addressed in bytes, a chunk of 8 head dims is 8 bytes, K and V chunks are widened to q's 16-bit dtype in
 // registers (kv_q8_widen) on their way into the unchanged 16-bit loop, and the append quantises (kv_q8_quant).  With KV_Q8 0
-// every line below preprocesses to what it was before KV_Q8 existed.
+// every line below but one (the register constraint after the score MFMAs) preprocesses to what it was before KV_Q8 existed.
+// Packed queries and new keys (fa_ex_forward_kvcache_varlen) are run-time null tests on p.cu_q / p.cu_kn in every inclusion.
 
-// Token L_b + n of batch element b goes to cache row (bidx ? bidx[b] : b) at position L_b + n, or through the table to
+// Token L_b + n of batch element b (k_new[b, n], or row cu_k_new[b] + n of a packed k_new) goes to cache row
+// (bidx ? bidx[b] : b) at position L_b + n, or through the table to
 // pool[table[b, (L_b + n) / ps], (L_b + n) % ps]; a row or page outside the cache / pool drops the token.
 // KV_ROT: k_new[b, n] is rotated at position L_b - P_b + n on the way (Tag: its dtype).
 #if KV_Q8 && KV_ROT
@@ -22,10 +24,12 @@ __global__ __launch_bounds__(256) void kv_append_rot_kernel(KvParams p, KvRot ro
 __global__ __launch_bounds__(256) void kv_append_kernel(KvParams p) {
 #endif
     const int cpr = p.d / 8;                                      // 16-byte chunks per head row
-    const long long per_b = (long long)p.nnew * p.hkv * cpr;
     const int b = blockIdx.y;
-    int L, P;
-    kv_len_k(p, b, L, P);
+    int kn0, L, P;
+    const int nnew = kv_seq_new(p, b, kn0);                       // packed k_new: nnew_b tokens from row kn0 (else N_new, 0)
+    const long long per_b = (long long)nnew * p.hkv * cpr;
+    kv_len_k(p, b, nnew, L, P);
+    const long long kn_b = p.cu_kn ? (long long)kn0 * p.kn_ts : b * p.kn_bs, vn_b = p.cu_kn ? (long long)kn0 * p.vn_ts : b * p.vn_bs;
     long long row = b;
     if (p.bidx) {
         const int ix = p.bidx[b];
@@ -47,17 +51,17 @@ __global__ __launch_bounds__(256) void kv_append_kernel(KvParams p) {
             unit = pg;
         }
 #if KV_ROT
-        u32x4 kx = *reinterpret_cast<const u32x4*>(p.kn + b * p.kn_bs + (size_t)n * p.kn_ts + col);
+        u32x4 kx = *reinterpret_cast<const u32x4*>(p.kn + kn_b + (size_t)n * p.kn_ts + col);
         if (8 * c < ro.rdim) {
             u32x4 par = kx;
             if (!ro.inter)
-                par = *reinterpret_cast<const u32x4*>(p.kn + b * p.kn_bs + (size_t)n * p.kn_ts + (size_t)h * p.d + kv_rot_partner(ro, 8 * c));
+                par = *reinterpret_cast<const u32x4*>(p.kn + kn_b + (size_t)n * p.kn_ts + (size_t)h * p.d + kv_rot_partner(ro, 8 * c));
             kx = kv_rotate_chunk<Tag>(ro, L - P + n, 8 * c, kx, par);
         }
 #else
-        const u32x4 kx = *reinterpret_cast<const u32x4*>(p.kn + b * p.kn_bs + (size_t)n * p.kn_ts + col);
+        const u32x4 kx = *reinterpret_cast<const u32x4*>(p.kn + kn_b + (size_t)n * p.kn_ts + col);
 #endif
-        const u32x4 vx = *reinterpret_cast<const u32x4*>(p.vn + b * p.vn_bs + (size_t)n * p.vn_ts + col);
+        const u32x4 vx = *reinterpret_cast<const u32x4*>(p.vn + vn_b + (size_t)n * p.vn_ts + col);
 #if KV_Q8
         // the (rotated, rounded) 16-bit values, quantised: one 8-byte store a chunk, the cache addressed in bytes
         const float kinv = 1.0f / (q8.kd ? q8.kd[b * q8.bs + h] : 1.0f), vinv = 1.0f / (q8.vd ? q8.vd[b * q8.bs + h] : 1.0f);
@@ -94,22 +98,27 @@ __global__ __launch_bounds__(64) void kv_split_kernel(KvParams p) {
     const int s = blockIdx.x, S = gridDim.x;
     const int hk = blockIdx.y % p.hkv, rt = blockIdx.y / p.hkv, b = blockIdx.z;
     const int DR = p.d;
-    int L_b, P_b;
-    const int lk = kv_len_k(p, b, L_b, P_b), coff = lk - p.nq;
+    // packed queries (p.cu_q): the sequence's nq_b tokens start at packed token tok0 and the grid is sized for max_seqlen_q, so
+    // a wave whose row tile lies past the sequence's rows leaves before its first load.  Wave-uniform, scalar.
+    long long tok0;
+    const int nq = kv_seq_q(p, b, tok0), rows = p.G * nq;
     const int pr0 = 16 * rt, pr = pr0 + r;
-    const int qlo = pr0 / p.G, qhi = (min(pr0 + 16, p.rows) - 1) / p.G;
+    if (pr0 >= rows) return;
+    int kn0, L_b, P_b;
+    const int lk = kv_len_k(p, b, kv_seq_new(p, b, kn0), L_b, P_b), coff = lk - nq;
+    const int qlo = pr0 / p.G, qhi = (min(pr0 + 16, rows) - 1) / p.G;
     int kbeg, kend;
-    kv_split_range(p, lk, qlo, qhi, s, S, kbeg, kend);
+    kv_split_range(p, lk, nq, qlo, qhi, s, S, kbeg, kend);
 
     // this lane's query row: token qi, query head h; its visible keys [rlo, rhi] (padding rows of the tile: none)
-    const bool valid = pr < p.rows;
+    const bool valid = pr < rows;
     const int qi = valid ? pr / p.G : qlo, h = hk * p.G + (valid ? pr - qi * p.G : 0);
     const int rlo = max(qi + coff - p.wl, kbeg);
     const int rhi = valid ? min(min(qi + coff + p.wr, lk - 1), kend - 1) : -1;
     float al = 0.f;
     if (p.alibi && valid) al = p.alibi[(size_t)b * p.al_bs + h] * p.sc.al_k;
 
-    const buf_rsrc_t q_rs = make_rsrc(p.q + b * p.q_bs, (unsigned)(((p.nq - 1) * p.q_ts + p.hq * DR) * 2));
+    const buf_rsrc_t q_rs = make_rsrc(p.q + (p.cu_q ? tok0 * p.q_ts : b * p.q_bs), (unsigned)(((nq - 1) * p.q_ts + p.hq * DR) * 2));
     s16x8 qf[NKS];
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) {
@@ -262,11 +271,10 @@ __global__ __launch_bounds__(64) void kv_split_kernel(KvParams p) {
 #pragma unroll
             for (int ks = 0; ks < NKS; ++ks) sacc[kb] = mfma16<Tag>(kf[kb][ks], qf[ks], sacc[kb]);
         }
-#if KV_Q8
         // both score tiles live in VGPRs at one point: without this hipcc ends the second chain in the first one's registers
         // (a[0:3] = .. + a[4:7]), a C operand that is not the destination, which tools/mfma_hazard_audit.py R1 does not pass
+        // (the e4m3 kernels always did that; with the packed-query prologue the contiguous 16-bit D = 128 ones do as well)
         asm volatile("" : "+v"(sacc[0]), "+v"(sacc[1]));
-#endif
         // (the previous tile's transposed reads were issued before these writes: one wave, LDS in order)
 #pragma unroll
         for (int i = 0; i < VLD; ++i) {
@@ -330,9 +338,10 @@ __global__ __launch_bounds__(64) void kv_split_kernel(KvParams p) {
     const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
     const float lse_v = l_tot > 0.f ? m_run * p.scale + logf(l_tot) : -INFINITY;
     if (!valid) return;
-    const size_t row_id = ((size_t)b * p.hq + h) * p.nq + qi;
+    // o row (token, h) of the (packed or padded) token tok0 + qi; lse / partials row (b, h, qi), packed (h, token)
+    const size_t row_id = p.cu_q ? (size_t)h * p.total_q + tok0 + qi : ((size_t)b * p.hq + h) * p.nq + qi;
     if (S == 1) {
-        uint16_t* orow = p.o + (((size_t)b * p.nq + qi) * p.hq + h) * DR;
+        uint16_t* orow = p.o + ((size_t)(tok0 + qi) * p.hq + h) * DR;
 #pragma unroll
         for (int t = 0; t < NDB; ++t) {
             const int col = 16 * t + 4 * g;

@@ -222,6 +222,12 @@ struct KvArgs {
     // then always runs the combine (num_splits >= 2): the sink joins there (kv_combine_sink_kernel).
     const float* sinks = nullptr;
     int64_t sink_heads = 1;
+    // fa_ex_forward_kvcache_varlen (null / 0: the padded call).  cu_seqlens_q: q and o are packed (total_q, heads_q, d) at token
+    // stride q_ts (o dense), lse is (heads_q, total_q), sequence b owns at most max_seqlen_q of the tokens; seqlen_q and q_bs
+    // are not used.  cu_seqlens_k_new: k_new, v_new are packed (total_k_new, heads_kv, d); seqlen_new, kn_bs and vn_bs are
+    // not used.  Both untrusted device offsets (batch + 1,), clamped in the kernels (fa_decode.hip: kv_cu_range).
+    const int *cu_seqlens_q = nullptr, *cu_seqlens_k_new = nullptr;
+    int64_t total_q = 0, max_seqlen_q = 0, total_k_new = 0;
 };
 int kv_num_splits(int64_t batch, int64_t heads_kv, int64_t row_tiles, int64_t cache_len);
 size_t kv_workspace_bytes(int64_t batch, int64_t heads_q, int64_t seqlen_q, int64_t d, int splits);

@@ -46,6 +46,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_ex_forward_kvcache_fp8",
     "fa_ex_forward_sink", "fa_ex_backward_sink", "fa_ex_forward_varlen_sink", "fa_ex_backward_varlen_sink",
     "fa_ex_forward_kvcache_sink", "fa_ex_kvcache_workspace_bytes_sink",
+    "fa_ex_forward_kvcache_varlen", "fa_ex_kvcache_workspace_bytes_varlen",
 )
 
 
@@ -176,6 +177,14 @@ def _load_library() -> ctypes.CDLL:
     lib.fa_ex_forward_kvcache_sink.restype = ci
     lib.fa_ex_kvcache_workspace_bytes_sink.argtypes = [i64] * 7
     lib.fa_ex_kvcache_workspace_bytes_sink.restype = sz
+    # packed queries / new keys: the sink call's with cu_seqlens_q, cu_seqlens_k_new, total_q, max_seqlen_q, total_k_new right
+    # after sink_heads
+    lib.fa_ex_forward_kvcache_varlen.argtypes = [vp] * 8 + [i64] * 7 + [ci] + [i64] * 10 + [ci, i64, i64, dbl, dbl, vp, i64, i64] + \
+        [vp, i64, i64, i64, i64, vp, i64, vp] + [vp, vp, i64, i64, i64, i64, ci] + [ci, vp, vp, i64] + [vp, i64] + \
+        [vp, vp, i64, i64, i64] + [vp, sz, vp]
+    lib.fa_ex_forward_kvcache_varlen.restype = ci
+    lib.fa_ex_kvcache_workspace_bytes_varlen.argtypes = [i64] * 8 + [ci]
+    lib.fa_ex_kvcache_workspace_bytes_varlen.restype = sz
     return lib
 
 
@@ -728,10 +737,59 @@ def _kv_strides(who, name, t, heads, d, cache):
     return bs, ts
 
 
+def _rotary_tables(rotary_cos, rotary_sin, rdim, rotary_interleaved):
+    """the seven rotary arguments of the KV-cache entry points; rows at an even stride, 4-byte aligned: otherwise a dense copy"""
+    tabs = []
+    for t in (rotary_cos, rotary_sin):
+        if t.stride(1) != 1 or (t.shape[0] > 1 and (t.stride(0) < t.shape[1] or t.stride(0) % 2)) or t.data_ptr() % 4:
+            t = t.clone(memory_format=torch.contiguous_format)
+        tabs.append(t)
+    c, s_ = tabs
+    return tabs, (c.data_ptr(), s_.data_ptr(), c.stride(0) if c.shape[0] > 1 else c.shape[1],
+                  s_.stride(0) if s_.shape[0] > 1 else s_.shape[1], c.shape[0], rdim, int(bool(rotary_interleaved)))
+
+
+def _kvcache_varlen(who, q, k_cache, v_cache, k_new, v_new, cache_seqlens, cu_q, cu_kn, dims, block_table, cache_batch_idx, cache_leftpad,
+                    units, rotary_cos, rotary_sin, rdim, rotary_interleaved, q8, sptr, sheads, total_q, mq, total_kn):
+    """the packed call of ex_kvcache_forward (fa_ex_forward_kvcache_varlen), its arguments checked; the current device is q's"""
+    b, hq, hkv, d = dims[0], dims[1], dims[2], dims[6]
+    cap_len, num_splits = dims[5], dims[-1]
+    cu_q = cu_q.contiguous()
+    cu_kn = cu_kn.contiguous() if cu_kn is not None else None
+    paged = (0, 0, 0, 0, 0)
+    capacity = cap_len
+    if block_table is not None:
+        if block_table.stride(1) != 1:
+            block_table = block_table.contiguous()
+        paged = (block_table.data_ptr(), block_table.stride(0) if b > 1 else max(block_table.stride(0), block_table.shape[1]),
+                 units, cap_len, block_table.shape[1])
+        capacity = block_table.shape[1] * cap_len
+    if cache_batch_idx is not None:
+        cache_batch_idx = cache_batch_idx.contiguous()
+    if cache_leftpad is not None:
+        cache_leftpad = cache_leftpad.contiguous()
+    middle = (*paged, cache_batch_idx.data_ptr() if cache_batch_idx is not None else 0,
+              units if cache_batch_idx is not None else 0, cache_leftpad.data_ptr() if cache_leftpad is not None else 0)
+    rotary = (0, 0, 0, 0, 0, 0, 0)
+    if rotary_cos is not None:
+        _tabs, rotary = _rotary_tables(rotary_cos, rotary_sin, rdim, rotary_interleaved)
+    o = torch.empty((total_q, hq, d), dtype=q.dtype, device=q.device)
+    lse = torch.empty((hq, total_q), dtype=torch.float32, device=q.device)
+    nbytes = int(_lib.fa_ex_kvcache_workspace_bytes_varlen(b, hq, hkv, total_q, mq, capacity, d, num_splits, int(bool(sptr))))
+    ws = _workspace(q.device, nbytes) if nbytes > 0 else None
+    head = (q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_new.data_ptr() if k_new is not None else 0,
+            v_new.data_ptr() if v_new is not None else 0, cache_seqlens.data_ptr() if cache_seqlens is not None else 0,
+            o.data_ptr(), lse.data_ptr())
+    _check(_lib.fa_ex_forward_kvcache_varlen(*head, *dims, *middle, *rotary, *q8, sptr, sheads, cu_q.data_ptr(),
+                                             cu_kn.data_ptr() if cu_kn is not None else 0, total_q, mq, total_kn,
+                                             ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device)))
+    return o, lse
+
+
 def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlens=None, causal=False, softmax_scale=None,
                        window=(-1, -1), softcap=0.0, alibi_slopes=None, num_splits=0, block_table=None, cache_batch_idx=None,
-                       cache_leftpad=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True, *, sinks=None, k_descale=None,
-                       v_descale=None):
+                       cache_leftpad=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True, *, cu_seqlens_q=None,
+                       cu_seqlens_k_new=None, max_seqlen_q=None, sinks=None, k_descale=None, v_descale=None):
     """(o, lse) of a decode step over a KV cache (FlashAttention-2's flash_attn_with_kvcache, forward): q (B, Nq, H_q, d);
     k_cache, v_cache (B, cache_len, H_kv, d), used in place (strided views such as kv.unbind(2) allowed, never copied);
     k_new, v_new (B, N_new, H_kv, d) are written into the caches at cache_seqlens[b] first; cache_seqlens int32 (B,) on the
@@ -755,17 +813,51 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
     fa_ex_forward_kvcache_fp8.
     sinks: float32 (H_q,) on q's device, one extra softmax column per query head with a zero value; it joins where the splits are
     combined, so such a call runs at least two splits.  lse contains it.  See fa_ex_forward_kvcache_sink.
-    sinks, k_descale and v_descale are keyword-only; the two scales stay the trailing keywords."""
+    sinks, k_descale and v_descale are keyword-only; the two scales stay the trailing keywords.  So are the three below.
+    cu_seqlens_q int32 (B + 1,) on q's device with max_seqlen_q (an int, required): q is packed (total_q, H_q, d) — a view with
+    a token stride such as qkv[:, 0] is taken as it is — and sequence b owns tokens [cu_seqlens_q[b], cu_seqlens_q[b + 1]), at
+    most max_seqlen_q of them, none allowed.  o is then (total_q, H_q, d) and lse (H_q, total_q).  cu_seqlens_k_new int32
+    (B + 1,), only with k_new, v_new and cu_seqlens_q: k_new, v_new are packed (total_k_new, H_kv, d) and sequence b appends
+    its own count of tokens, independent of its count of q tokens; cu_seqlens_q also goes with padded (B, N_new, H_kv, d) new
+    keys, or with none.  Each sequence gets what the padded call returns for it alone (its causal diagonal is len_k_b - nq_b); a
+    sequence without q tokens still appends; rows of o and lse that no sequence owns are left as allocated.  Neither array is
+    read on the host: the kernels clamp them, as they clamp cache_seqlens, so no content reads or writes out of bounds.  Rotary
+    needs seqlen_ro >= capacity + max_seqlen_q.  A 4-D q with cu_seqlens_q, a missing max_seqlen_q and a packed q that would need
+    a copy raise ValueError.  See fa_ex_forward_kvcache_varlen."""
     who = "ex_kvcache_forward"
     wl, wr = window_arg(who, window)
     cap = softcap_arg(who, softcap)
+    packed = cu_seqlens_q is not None
+    if cu_seqlens_k_new is not None and not packed:
+        raise ValueError(f"{who}: cu_seqlens_k_new needs cu_seqlens_q")
+    if max_seqlen_q is not None and not packed:
+        raise ValueError(f"{who}: max_seqlen_q needs cu_seqlens_q")
     for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
             raise RuntimeError(f"{who}: {name} must be a GPU (HIP device) tensor; there is no CPU path")
         if t.device != q.device:
             raise RuntimeError(f"{who}: {name} must be on q's device ({q.device}), got {t.device}")
-        if t.dim() != 4:
+        if packed and name == "q":
+            if t.dim() != 3:
+                raise ValueError(f"{who}: with cu_seqlens_q q must be packed (total_q, H_q, d), got {tuple(t.shape)}")
+        elif t.dim() != 4:
             raise RuntimeError(f"{who}: {name} must be 4-D (B, N, H, d), got {tuple(t.shape)}")
+    total_q = total_kn = mq = 0
+    if packed:
+        if max_seqlen_q is None:
+            raise ValueError(f"{who}: cu_seqlens_q needs max_seqlen_q")
+        for name, t in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k_new", cu_seqlens_k_new)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+                dt = t.dtype if isinstance(t, torch.Tensor) else type(t).__name__
+                raise NotImplementedError(f"{who}: {name} of dtype {dt} is not supported (int32 tensor expected)")
+            if t.device != q.device or t.dim() != 1 or t.shape[0] < 2 or t.shape != cu_seqlens_q.shape:
+                raise RuntimeError(f"{who}: {name} must be an int32 (B + 1,) tensor on q's device, B >= 1, both of one length")
+        total_q, mq = q.shape[0], operator.index(max_seqlen_q)
+        if mq < 0 or mq > total_q:
+            raise ValueError(f"{who}: max_seqlen_q = {mq} must lie in [0, total_q = {total_q}]")
+        q = q.unsqueeze(0)   # (1, total_q, H_q, d) for the shape checks below; never copied
     for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
         if t.dtype in _FLOAT8_DTYPES and t.dtype != torch.float8_e4m3fn:
             raise NotImplementedError(f"{who}: {name} of dtype {t.dtype} is not supported (an 8-bit cache is torch.float8_e4m3fn)")
@@ -776,6 +868,8 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
     if not e4m3 and (k_descale is not None or v_descale is not None):
         raise RuntimeError(f"{who}: k_descale / v_descale need a torch.float8_e4m3fn cache (the caches are {k_cache.dtype})")
     b, nq, hq, d = q.shape
+    if packed:
+        b, nq = cu_seqlens_q.shape[0] - 1, mq
     cap_len, hkv = k_cache.shape[1], k_cache.shape[2]
     for name, t, shape in (("block_table", block_table, "(B, max_blocks_per_seq)"), ("cache_batch_idx", cache_batch_idx, "(B,)"),
                            ("cache_leftpad", cache_leftpad, "(B,)")):
@@ -842,7 +936,20 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
     dsc_bs = kds if kdp else vds
     nnew = 0
     knb = knt = vnb = vnt = 0
-    if k_new is not None:
+    if cu_seqlens_k_new is not None:
+        if k_new is None:
+            raise ValueError(f"{who}: cu_seqlens_k_new needs k and v")
+        for name, t in (("k", k_new), ("v", v_new)):
+            if not isinstance(t, torch.Tensor) or t.device != q.device or t.dtype != q.dtype or t.dim() != 3 or \
+                    t.shape[1:] != (hkv, d) or t.shape != k_new.shape:
+                raise RuntimeError(f"{who}: with cu_seqlens_k_new {name} must be a packed (total_k_new, H_kv, d) tensor of q's "
+                                   f"dtype and device")
+        total_kn = k_new.shape[0]
+        nnew = min(total_kn, 1)   # (for the checks below: new tokens or none)
+        k_new, v_new = k_new.contiguous().unsqueeze(0), v_new.contiguous().unsqueeze(0)
+        _kb, knt = _kv_strides(who, "k", k_new, hkv, d, False)
+        _vb, vnt = _kv_strides(who, "v", v_new, hkv, d, False)
+    elif k_new is not None:
         for name, t in (("k", k_new), ("v", v_new)):
             if not isinstance(t, torch.Tensor) or t.device != q.device or t.dtype != q.dtype or t.dim() != 4 or \
                     t.shape[0] != b or t.shape[2:] != (hkv, d) or t.shape != k_new.shape:
@@ -853,11 +960,19 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
         vnb, vnt = _kv_strides(who, "v", v_new, hkv, d, False)
     if rotary_cos is not None:
         capacity = cap_len * (block_table.shape[1] if block_table is not None else 1)
-        need = capacity + max(0, nq - nnew)   # the library's bound: every position a clamped length can give is a table row
+        # the library's bound: every position a clamped length can give is a table row
+        need = capacity + (mq if packed else max(0, nq - nnew))
         if rotary_cos.shape[0] < need:
             raise RuntimeError(f"{who}: rotary_cos / rotary_sin have {rotary_cos.shape[0]} rows; the capacity {capacity} + "
-                               f"max(0, Nq - N_new) = {need} are needed")
-    q = q.contiguous()
+                               f"{'max_seqlen_q' if packed else 'max(0, Nq - N_new)'} = {need} are needed")
+    if packed:   # a token-strided view is taken as it is; anything else would need a copy
+        if q.stride(3) != 1 or (hq > 1 and q.stride(2) != d) or (total_q > 1 and (q.stride(1) < hq * d or q.stride(1) % 8)) or \
+                q.data_ptr() % 16:
+            raise ValueError(f"{who}: a packed q must have a contiguous last dim, its heads at stride d = {d}, a token stride that "
+                             f"is a multiple of 8 and >= H_q d, and a 16-byte aligned address (got strides {tuple(q.stride()[1:])}); "
+                             f"it is never copied")
+    else:
+        q = q.contiguous()
     qb, qt = _kv_strides(who, "q", q, hq, d, False)
     scale = d ** -0.5 if softmax_scale is None else float(softmax_scale)
     aptr, _h, astride, alibi_slopes = alibi_arg(who, alibi_slopes, q.device, b * hq, heads=hq)
@@ -869,6 +984,14 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
             if cache_seqlens.device != q.device or cache_seqlens.dtype != torch.int32 or cache_seqlens.shape != (b,):
                 raise RuntimeError(f"{who}: cache_seqlens must be an int32 ({b},) tensor on q's device, or an int")
             cache_seqlens = cache_seqlens.contiguous()
+        if packed:
+            return _kvcache_varlen(who, q, k_cache, v_cache, k_new, v_new, cache_seqlens, cu_seqlens_q, cu_seqlens_k_new,
+                                   (b, hq, hkv, 0, 0 if cu_seqlens_k_new is not None else nnew, cap_len, d, _DTYPE_CODE[q.dtype], 0, qt,
+                                    kvb, kvt, vvb, vvt, knb, knt, vnb, vnt, int(bool(causal)), wl, wr, scale, cap, aptr, astride,
+                                    int(num_splits)),
+                                   block_table, cache_batch_idx, cache_leftpad, units, rotary_cos, rotary_sin, rdim, rotary_interleaved,
+                                   (_E4M3_CODE, kdp, vdp, dsc_bs) if e4m3 else (_DTYPE_CODE[q.dtype], 0, 0, 0), sptr, sheads,
+                                   total_q, mq, total_kn)
         o = torch.empty((b, nq, hq, d), dtype=q.dtype, device=q.device)
         lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)
         head = (q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_new.data_ptr() if k_new is not None else 0,

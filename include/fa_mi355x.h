@@ -533,6 +533,48 @@ int fa_ex_forward_kvcache_sink(const void* q, void* k_cache, void* v_cache, cons
 size_t fa_ex_kvcache_workspace_bytes_sink(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
                                           int64_t d, int64_t num_splits);
 
+/* --- variable-length queries and new keys in KV-cache decoding (FlashAttention-3's cu_seqlens_q / cu_seqlens_k_new) ---
+ * fa_ex_forward_kvcache_sink plus five arguments between sink_heads and workspace.  All null / 0: exactly that call.
+ * cu_seqlens_q (int32 (batch + 1,), device): q is packed (total_q, heads_q, d) at q_token_stride, sequence b owns tokens
+ * [cu_seqlens_q[b], cu_seqlens_q[b + 1]) (none allowed), at most max_seqlen_q of them; o is (total_q, heads_q, d) dense and lse
+ * (heads_q, total_q), the packed convention of the varlen calls.  seqlen_q and q_batch_stride are not used.
+ * cu_seqlens_k_new (int32 (batch + 1,), device; only with k_new, v_new and cu_seqlens_q): k_new, v_new are packed
+ * (total_k_new, heads_kv, d) and sequence b appends its nnew_b tokens (none allowed); seqlen_new and the k_new / v_new batch
+ * strides are not used.  cu_seqlens_q may also go with padded (batch, seqlen_new, ..) k_new, v_new, or with none.
+ * Every sequence gets what the padded call returns for it alone (batch = 1, its own q tokens, new keys, cache row, table row,
+ * leftpad, descale row, ALiBi row): L_b = clamp(cache_seqlens[b], 0, capacity - nnew_b), len_k = L_b + nnew_b - P_b, causal
+ * diagonal len_k - nq_b, rotary positions L_b - P_b + n (new key n) and L_b - P_b + i or L_b - P_b (q token i).  A sequence
+ * without q tokens writes nothing to o / lse and still appends; rows of o / lse that no sequence owns are not written.
+ * Both arrays are untrusted, as cache_seqlens is: start_b = clamp(cu[b], 0, total) and n_b = clamp(cu[b + 1] - cu[b], 0,
+ * min(bound, total - start_b)) with bound = max_seqlen_q (q) or the capacity (k_new), so no content reads outside q / k_new /
+ * v_new or writes outside o, lse, the workspace or the cache; overlapping ranges give unspecified values in the rows they share.
+ * num_splits = 0 takes ceil(max_seqlen_q * (heads_q / heads_kv) / 16) for the row tiles of the split rule; rotary needs
+ * seqlen_ro >= capacity + max_seqlen_q; a window bound is canonicalised against max_seqlen_q.  The workspace is
+ * fa_ex_kvcache_workspace_bytes_varlen: S * total_q * heads_q * (d + 1) floats for S > 1 splits (with_sinks: at least two), each
+ * of the two parts rounded up to 256 bytes.  Refused before any HIP call: total_q, max_seqlen_q or total_k_new non-zero without
+ * their array; cu_seqlens_k_new without k_new / v_new or without cu_seqlens_q; max_seqlen_q < 0 or > total_q; total_q or
+ * total_k_new at or past 2^31; max_seqlen_q tokens of q spanning 2^31 bytes or more (FA_ERR_UNSUPPORTED: the kernels keep 32-bit
+ * offsets inside one sequence and 64-bit ones between sequences).  Never synchronises or allocates; can be captured in a graph and
+ * replayed after the contents of the arrays changed (total_q, max_seqlen_q and total_k_new are fixed by the capture). */
+int fa_ex_forward_kvcache_varlen(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                                 const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                                 int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
+                                 int64_t q_token_stride, int64_t k_cache_batch_stride, int64_t k_cache_token_stride,
+                                 int64_t v_cache_batch_stride, int64_t v_cache_token_stride, int64_t k_new_batch_stride,
+                                 int64_t k_new_token_stride, int64_t v_new_batch_stride, int64_t v_new_token_stride, int causal,
+                                 int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
+                                 const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, const int32_t* block_table,
+                                 int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq,
+                                 const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad,
+                                 const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride,
+                                 int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
+                                 int cache_dtype, const float* k_descale, const float* v_descale, int64_t descale_batch_stride,
+                                 const float* sinks, int64_t sink_heads, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k_new,
+                                 int64_t total_q, int64_t max_seqlen_q, int64_t total_k_new, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+size_t fa_ex_kvcache_workspace_bytes_varlen(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t max_seqlen_q,
+                                            int64_t cache_len, int64_t d, int64_t num_splits, int with_sinks);
+
 /* --- support entry points (no reference counterpart: the reference allocates inside the callee) --- */
 /* bytes for the CURRENT kernel mode: two float row constants per query row (+ an fp32 dQ scratch of bh*n*d floats in
  * FA_MODE_BWD_ATOMIC only); ask again after changing the mode */

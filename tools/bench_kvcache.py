@@ -19,6 +19,13 @@ and the effective bandwidth of kv: bytes of K and V read (sum over b of len_b * 
 --cache-dtype e4m3: the caches (and pools) are quantised once, outside the timed region, to torch.float8_e4m3fn with scales
 absmax / 448 per (b, head), and every kv / kv_app / paged / rotary call runs on them with k_descale / v_descale; the bytes of K
 and V are then 1 an element.  ex_forward and the unfused rotation keep the 16-bit tensors.
+--varlen: instead of the grid, the packed call (cu_seqlens_q) on an 8k-key paged cache (page 16), H_q = 32, H_kv = 8:
+  uniform : B = 32 sequences of --nq tokens through cu_seqlens_q against the padded call on the same tensors (the same kernels:
+            the ratio should be 1), parent-comparable;
+  mixed   : 63 sequences of 1 token and one chunk of n tokens (--chunks, default 16 .. 512) in one packed call, against the two
+            padded calls that serve the same step (63 x 1 token, 1 x n tokens), with the share of the packed grid's waves that
+            leave empty, 1 - sum_b ceil(nq_b G / 16) / (B ceil(max_seqlen_q G / 16)); and the chunk alone through
+            ex_varlen_forward on its gathered keys (the gather timed apart), the call that overtakes this path on long chunks.
 Timing: HIP events around `--iters` back-to-back calls after `--warmup` calls; the median of `--reps` such groups."""
 import argparse
 import json
@@ -159,6 +166,69 @@ def row(b, hq, hkv, lens, d, dtype, args):
     return r
 
 
+def varlen_rows(args, dtype):
+    dev, hq, hkv, d, ps, cap = "cuda", 32, 8, args.d, 16, 8192
+    g = hq // hkv
+    rows = []
+
+    def pool(b):
+        mb = cap // ps
+        table = torch.randperm(b * mb, generator=torch.Generator().manual_seed(b)).view(b, mb).to(torch.int32).to(dev)
+        return torch.randn((b * mb, ps, hkv, d), device=dev, dtype=dtype), torch.randn((b * mb, ps, hkv, d), device=dev, dtype=dtype), table
+
+    def cu(lens):
+        return torch.tensor([0] + list(torch.tensor(lens).cumsum(0)), dtype=torch.int32, device=dev)
+
+    t = lambda fn: timed(fn, args.warmup, args.iters, args.reps)   # noqa: E731
+    # uniform lengths: the packed call against the padded call on the same tensors, alternated twice
+    b = 32
+    kp, vp, table = pool(b)
+    sl = torch.full((b,), cap, dtype=torch.int32, device=dev)
+    q = torch.randn((b, args.nq, hq, d), device=dev, dtype=dtype)
+    cu_q = cu([args.nq] * b)
+    padded = lambda: ext.ex_kvcache_forward(q, kp, vp, None, None, sl, True, None, block_table=table)   # noqa: E731
+    packed = lambda: ext.ex_kvcache_forward(q.view(b * args.nq, hq, d), kp, vp, None, None, sl, True, None, block_table=table,   # noqa: E731
+                                            cu_seqlens_q=cu_q, max_seqlen_q=args.nq)
+    assert torch.equal(padded()[0].view(b * args.nq, hq, d), packed()[0]), "packed and padded calls disagree"
+    ts = [t(packed), t(padded), t(packed), t(padded)]
+    rows.append(dict(kind="uniform", B=b, nq=args.nq, len=cap, packed_us=[round(ts[0], 2), round(ts[2], 2)],
+                     padded_us=[round(ts[1], 2), round(ts[3], 2)], packed_vs_padded=round((ts[0] + ts[2]) / (ts[1] + ts[3]), 3)))
+    print(json.dumps(rows[-1]), flush=True)
+    del kp, vp, table, q
+    # a mixed step: 63 decoding sequences and one prefill chunk
+    b = 64
+    kp, vp, table = pool(b)
+    for n in args.chunks:
+        lens = [1] * 63 + [n]
+        sl = torch.full((b,), cap, dtype=torch.int32, device=dev)   # (the chunk's own keys are the cache's last n: no append is timed)
+        q = torch.randn((63 + n, hq, d), device=dev, dtype=dtype)
+        cu_q = cu(lens)
+        q1, qn = q[:63].view(63, 1, hq, d), q[63:].view(1, n, hq, d)
+        packed = lambda: ext.ex_kvcache_forward(q, kp, vp, None, None, sl, True, None, block_table=table, cu_seqlens_q=cu_q,   # noqa: E731
+                                                max_seqlen_q=n)
+
+        def two():
+            ext.ex_kvcache_forward(q1, kp, vp, None, None, sl[:63], True, None, block_table=table[:63])
+            return ext.ex_kvcache_forward(qn, kp, vp, None, None, sl[63:], True, None, block_table=table[63:])
+
+        torch.testing.assert_close(packed()[0][63:].float(), two()[0][0].float(), rtol=2e-2, atol=2e-2)
+        # the chunk through the training path: its keys gathered from the pool, then one packed sequence
+        gather = lambda: (kp[table[63].long()].view(cap, hkv, d), vp[table[63].long()].view(cap, hkv, d))   # noqa: E731
+        kg, vg = gather()
+        cq, ck = cu([n]), cu([cap])
+        vl = lambda: ext.ex_varlen_forward(qn[0], kg, vg, cq, ck, n, cap, True, d ** -0.5)   # noqa: E731
+        torch.testing.assert_close(vl()[0].float(), two()[0][0].float(), rtol=2e-2, atol=2e-2)
+        tiles = (n * g + 15) // 16
+        live = sum((x * g + 15) // 16 for x in lens)
+        r = dict(kind="mixed", B=b, chunk=n, len=cap, packed_us=round(t(packed), 2), two_padded_us=round(t(two), 2),
+                 chunk_varlen_us=round(t(vl), 2), gather_us=round(t(gather), 2), empty_wave_share=round(1 - live / (b * tiles), 4))
+        r["packed_vs_two"] = round(r["packed_us"] / r["two_padded_us"], 3)
+        rows.append(r)
+        print(json.dumps(r), flush=True)
+        del q, kg, vg
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--d", type=int, default=128)
@@ -175,8 +245,11 @@ def main():
                     help="16: the caches in --dtype; e4m3: quantised once to float8_e4m3fn with per-(b, head) scales")
     ap.add_argument("--sinks", action="store_true", help="also time the call with attention sinks ((H_q,) logits) against the call without")
     ap.add_argument("--lens", default="1024,8192,32768,131072", help="the grid's cache lengths")
+    ap.add_argument("--varlen", action="store_true", help="time the packed call (cu_seqlens_q) instead of the grid: see the module docstring")
+    ap.add_argument("--chunks", default="16,32,64,128,256,512", help="--varlen: the chunk lengths of the mixed step")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
+    args.chunks = [int(x) for x in args.chunks.split(",")]
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16
     # bring the clocks up before the first row (a second of large decode steps)
     wq = torch.randn((8, 1, 32, args.d), device="cuda", dtype=dtype)
@@ -186,6 +259,12 @@ def main():
         ext.ex_kvcache_forward(wq, wk, wk, None, None, wl, True, None)
     torch.cuda.synchronize()
     del wq, wk
+    if args.varlen:
+        rows = varlen_rows(args, dtype)
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(dict(d=args.d, dtype=args.dtype, nq=args.nq, varlen=True, rows=rows), f, indent=1)
+        return
     rows = []
     for b in (1, 8, 32):
         for hkv in (8, 32):
