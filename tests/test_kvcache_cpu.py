@@ -187,6 +187,54 @@ def test_split_rule_partitions_the_visible_band():
             assert not nonempty or max(nonempty) - min(nonempty) <= KT
 
 
+# ---- model of the split kernel's row packing (csrc/fa_decode_kernels.inc: pr0, qlo, qhi, qi, h) for any G = H_q / H_kv: row
+# pr = token * G + head in the group, 16 rows a tile.  G need not divide 16 (a tile then starts in the middle of a token) and may
+# exceed it (one token's heads then span several tiles).
+ROWS = 16
+
+
+def tile_tokens(rt, g, nq):
+    """(qlo, qhi): the first and last query token with a row in row tile rt; None when the tile lies past the G * nq rows"""
+    rows, pr0 = g * nq, ROWS * rt
+    if pr0 >= rows:
+        return None
+    return pr0 // g, (min(pr0 + ROWS, rows) - 1) // g
+
+
+def tile_rows(rt, g, nq):
+    """[(token, head in the group)] of the valid lanes of row tile rt, in lane order"""
+    return [(pr // g, pr % g) for pr in range(ROWS * rt, min(ROWS * rt + ROWS, g * nq))]
+
+
+def row_band(lk, nq, i, causal, wl, wr):
+    return {j for j in range(lk) if visible(lk, nq, i, j, causal, wl, wr)}
+
+
+def check_group_arithmetic(g, nq, lk, causal, wl, wr, S):
+    """every (token, head) row is in exactly one tile, and over that tile's splits the keys [kbeg, kend) cut to the row's band
+    (the kernel's rlo / rhi) are the row's band, each key once"""
+    seen = []
+    for rt in range((g * nq + ROWS - 1) // ROWS):
+        qlo, qhi = tile_tokens(rt, g, nq)
+        rows = tile_rows(rt, g, nq)
+        assert {t for t, _ in rows} == set(range(qlo, qhi + 1)), "qlo / qhi are not the tile's tokens"
+        seen.extend(rows)
+        spans = [split_range(lk, nq, qlo, qhi, causal, wl, wr, s, S) for s in range(S)]
+        for i in sorted({t for t, _ in rows}):
+            band = row_band(lk, nq, i, causal, wl, wr)
+            got = [j for a, b in spans if a < b for j in range(a, b) if j in band]
+            assert len(got) == len(set(got)), "a key of the row's band is in two splits"
+            assert set(got) == band, (g, nq, lk, causal, wl, wr, S, rt, i)
+    assert tile_tokens((g * nq + ROWS - 1) // ROWS, g, nq) is None
+    assert sorted(seen) == [(t, h) for t in range(nq) for h in range(g)] and len(seen) == len(set(seen))
+
+
+def test_group_arithmetic_for_any_group_size():
+    for g, nq in itertools.product((1, 3, 5, 6, 8, 12, 16, 17, 20, 32), (1, 2, 3, 7, 18)):
+        for lk, S, causal, (wl, wr) in itertools.product((0, 1, 33, 100), (1, 2, 5), (False, True), ((-1, -1), (5, 0), (40, 2), (33, -1))):
+            check_group_arithmetic(g, nq, lk, causal, wl, wr, S)
+
+
 def combine(parts):
     """the kv_combine_kernel merge: parts = [(o_s (rows, d), lse_s (rows,))] in split order"""
     los = np.stack([l for _, l in parts])
