@@ -212,7 +212,8 @@ class _FlashAttnVarlenFn(torch.autograd.Function):
 
 
 def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p=0.0, softmax_scale=None,
-                           causal=False, window_size=(-1, -1), seed=0, softcap=0.0, alibi_slopes=None, sinks=None):
+                           causal=False, window_size=(-1, -1), seed=0, softcap=0.0, alibi_slopes=None, *,
+                           block_table=None, sinks=None):
     """FlashAttention-2's flash_attn_varlen_func over packed sequences, differentiable: q (total_q, H_q, d), k and v
     (total_k, H_kv, d) with H_q % H_kv == 0 (GQA), token-strided views (qkv.unbind(1) of a (total, 3, H, d) projection) taken
     without a copy; cu_seqlens_* int32 (batch + 1,) device offsets.  Attention stays inside each sequence; `causal` is
@@ -220,8 +221,27 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
     Returns o (total_q, H_q, d); the gradients of k and v come back in their shapes.  The dropout mask is that of the padded
     (batch * H_q, max_seqlen_q, max_seqlen_k) call (include/fa_mi355x.h), so it depends on the max_seqlen_q passed.  softcap and
     alibi_slopes (float32 (H_q,) or (batch, H_q)) as in flash_attention_ex, in each sequence's coordinates.  sinks: float32 (H_q,)
-    attention sinks as in flash_attention_ex, differentiable."""
+    attention sinks as in flash_attention_ex, differentiable.
+    block_table (keyword-only, and `sinks` with it: sinks stays the last parameter, so both are passed by name;
+    FlashAttention-2's argument of flash_attn_varlen_func): int32 (batch, max_blocks_per_seq) on the
+    device — k and v are then the pools of a paged KV cache, (num_blocks, page_block_size, H_kv, d) in q's dtype, page_block_size
+    a positive multiple of 16, and key t of sequence b lives at pool[block_table[b, t // ps], t % ps]: chunked prefill, or prefill
+    behind a shared prefix, straight from the cache flash_attn_with_kvcache appends to.  The lengths still come from
+    cu_seqlens_k — len_k[b] = cu_seqlens_k[b + 1] - cu_seqlens_k[b], its absolute offsets mean nothing for a pool — clamped on
+    the device to [0, min(max_seqlen_k, max_blocks_per_seq * ps)]; nothing is read on the host, so the call never synchronises
+    and can be captured and replayed with a changed table and changed offsets.  The table is untrusted: a page number outside
+    [0, num_blocks) reads as zero K and zero V, entries past ceil(len_k[b] / ps) are never read, page offsets are 64-bit (pools
+    above 4 GiB), sequences may share pages, and the pools are only read.  A pool may be a view with its own page and token
+    strides (the two halves of a K|V-interleaved allocation, a slice of the heads); the elements of a head must be contiguous,
+    and a view the library cannot take without a copy raises ValueError.  causal, window_size, GQA, softcap, alibi_slopes,
+    sinks, a token-strided q and empty sequences work as without the table, and each sequence gets the bits of this function on
+    the same tokens gathered into packed k, v.  Forward only: dropout_p > 0 raises ValueError, and q, k or v requiring grad
+    under grad mode raises RuntimeError (no paged backward, as in FlashAttention-2).  A block_table that is not an int32
+    tensor raises NotImplementedError."""
     window = _window_size(window_size)
+    if block_table is not None:
+        return _flash_attention_varlen_paged(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale,
+                                             causal, window, softcap, alibi_slopes, sinks, block_table)
     if not q.is_cuda:
         raise RuntimeError("Inputs must be CUDA tensors")
     scale = (1.0 / math.sqrt(q.shape[-1])) if softmax_scale is None else float(softmax_scale)
@@ -234,6 +254,34 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
     if sinks is None:
         return _FlashAttnVarlenFn.apply(*args, softcap, alibi_slopes)
     return _FlashAttnVarlenFn.apply(*args, softcap, alibi_slopes, _sinks_units("flash_attention_varlen", sinks, q.shape[1]))
+
+
+def _flash_attention_varlen_paged(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale, causal,
+                                  window, softcap, alibi_slopes, sinks, block_table):
+    """flash_attention_varlen with a block_table: forward only, nothing differentiable"""
+    who = "flash_attention_varlen"
+    if not (isinstance(block_table, torch.Tensor) and block_table.dtype == torch.int32):
+        dt = block_table.dtype if isinstance(block_table, torch.Tensor) else type(block_table).__name__
+        raise NotImplementedError(f"{who}: block_table of dtype {dt} is not supported (int32 tensor expected)")
+    if float(dropout_p) > 0.0:
+        raise ValueError(f"{who}: dropout_p > 0 is not supported with block_table (an inference path)")
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (q, k, v)):
+        raise RuntimeError(f"{who}: block_table is forward only — q, k or v requires grad and there is no backward through a paged "
+                           f"cache (call it under torch.no_grad(), or detach the tensors)")
+    if not q.is_cuda:
+        raise RuntimeError("Inputs must be CUDA tensors")
+    import flashattention_lab_cuda as ext
+
+    scale = (1.0 / math.sqrt(q.shape[-1])) if softmax_scale is None else float(softmax_scale)
+    if isinstance(alibi_slopes, torch.Tensor):
+        alibi_slopes = alibi_slopes.detach()
+    if sinks is not None:
+        sinks = _sinks_units(who, sinks, q.shape[1]).detach()
+    with torch.no_grad():
+        o, _lse = ext.ex_varlen_forward(q.detach(), k.detach(), v.detach(), cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q),
+                                        int(max_seqlen_k), bool(causal), scale, 0.0, 0, window=window, softcap=softcap,
+                                        alibi_slopes=alibi_slopes, sinks=sinks, block_table=block_table)
+    return o
 
 
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_sin=None, cache_seqlens=None,

@@ -847,6 +847,76 @@ int fa_ex_backward_varlen_sink(const void* q, const void* k, const void* v, cons
                                 sk);
 }
 
+// ---- the varlen forward over a paged K/V cache: see include/fa_mi355x.h
+int fa_ex_forward_varlen_paged(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
+                               const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
+                               int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
+                               int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
+                               double softmax_scale, double softcap, const float* alibi_slopes, int64_t alibi_batch_stride,
+                               const float* sinks, int64_t sink_heads, const int32_t* block_table, int64_t max_blocks_per_seq,
+                               int64_t num_blocks, int64_t page_block_size, int64_t k_page_stride, int64_t v_page_stride,
+                               void* stream) {
+    const char* who = "fa_ex_forward_varlen_paged";
+    (void)total_k;   // a pool has no token count: the keys of a sequence are found through the table
+    ScoreMod sm;
+    sm.softcap = softcap; sm.alibi = alibi_slopes; sm.heads = heads_q; sm.bstride = alibi_batch_stride;
+    SinkArg sk;
+    sk.sinks = sinks; sk.heads = sink_heads;
+    if (!block_table) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null block_table", who);
+    if ((uintptr_t)block_table % 4 != 0 || (uintptr_t)cu_seqlens_k % 4 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: block_table and cu_seqlens_k must be 4-byte aligned", who);
+    if (page_block_size < 16 || page_block_size % 16 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: page_block_size must be a positive multiple of 16 (got %lld)", who, (long long)page_block_size);
+    if (num_blocks < 0 || max_blocks_per_seq < 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_blocks=%lld and max_blocks_per_seq=%lld must be >= 0", who, (long long)num_blocks,
+                    (long long)max_blocks_per_seq);
+    // (the token strides against heads_kv * d, cu_seqlens_k against null with a key to read: total_k stands in as 1)
+    int rc = varlen_check(who, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, 1, max_seqlen_q, max_seqlen_k, d, dtype,
+                          q_stride, k_stride, v_stride, window_left, window_right, softmax_scale, 0.0);
+    if (rc != FA_OK) return rc;
+    const int64_t page_span = (page_block_size - 1) * (k_stride > v_stride ? k_stride : v_stride) + heads_kv * d;
+    if (num_blocks > 1 && (k_page_stride < (page_block_size - 1) * k_stride + heads_kv * d ||
+                           v_page_stride < (page_block_size - 1) * v_stride + heads_kv * d))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: page strides (%lld, %lld) must span a page of %lld tokens at token strides (%lld, %lld)",
+                    who, (long long)k_page_stride, (long long)v_page_stride, (long long)page_block_size, (long long)k_stride,
+                    (long long)v_stride);
+    if (k_page_stride < 0 || v_page_stride < 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: page strides must be >= 0", who);
+    if ((rc = score_check(who, sm, batch * heads_q)) != FA_OK) return rc;
+    if ((rc = sink_check(who, sk, heads_q, false)) != FA_OK) return rc;
+    if (page_block_size > 65536 || page_span * (dtype == FA_DTYPE_F32 ? 4 : 2) >= ((int64_t)1 << 31) || num_blocks >= ((int64_t)1 << 31) ||
+        max_blocks_per_seq >= ((int64_t)1 << 31) || batch * max_blocks_per_seq >= ((int64_t)1 << 40))
+        return fail(FA_ERR_UNSUPPORTED, "%s: a page above 65536 tokens or 2^31 bytes, or a table too large", who);
+    // the window against the same (max_seqlen_q, max_seqlen_k) as the packed call on the gathered tokens
+    if ((rc = window_canon(who, max_seqlen_q, max_seqlen_k, causal, window_left, window_right)) != FA_OK) return rc;
+    if (total_q == 0 || max_seqlen_q == 0) return FA_OK;
+    const int64_t capacity = max_blocks_per_seq * page_block_size;
+    const int64_t cap = max_seqlen_k < capacity ? max_seqlen_k : capacity;   // a sequence's keys: [0, cap]
+    if (!q || !o || !lse || (cap > 0 && num_blocks > 0 && (!k || !v))) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (cap == 0) {   // no key in any sequence: o = 0, lse = -inf (with sinks: the head's sink), as the packed call
+        hipError_t e = hipMemsetAsync(o, 0, (size_t)total_q * heads_q * d * (dtype == FA_DTYPE_F32 ? 4 : 2), st);
+        if (e == hipSuccess && sk.sinks) e = fa::launch_ex_sink_fill(lse, sk.sinks, sk.heads, heads_q, total_q, st);
+        else if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lse), (int)0xFF800000u, (size_t)heads_q * total_q, st);
+        if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
+        return FA_OK;
+    }
+    fa::ExArgs a = varlen_args(cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, 0, max_seqlen_q, cap, d, dtype, q_stride,
+                               k_stride, v_stride, causal, window_left, window_right, softmax_scale, 0.0, 0);
+    a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse;
+    score_args(a, sm);
+    sink_args(a, sk);
+    a.block_table = block_table;
+    a.max_blocks = max_blocks_per_seq;
+    a.num_blocks = num_blocks;
+    a.page_size = page_block_size;
+    a.page_stride_k = k_page_stride;
+    a.page_stride_v = v_page_stride;
+    hipError_t e = fa::launch_ex(a, false, st);
+    if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
+    return FA_OK;
+}
+
 // ---- KV-cache decoding with split-KV: see include/fa_mi355x.h
 static int64_t kv_splits(int64_t batch, int64_t hq, int64_t hkv, int64_t nq, int64_t cache_len, int64_t num_splits) {
     if (num_splits > 0) return num_splits;

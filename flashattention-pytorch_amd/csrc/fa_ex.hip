@@ -13,6 +13,9 @@
 //     key (query) tile ranges of every kernel are cut to the band at both ends.
 //   * packed (varlen) sequences (FlashAttention-2's flash_attn_varlen_func): each workgroup of the padded call's grid works inside
 //     its own sequence, in entries of their own (ex_*_varlen_kernel) around the bodies the other kernels share.
+//   * a paged K/V cache under the packed forward (FlashAttention-2's block_table of flash_attn_varlen_func): k and v are pools of
+//     pages and a sequence's keys are found through a table (ExPage), one lookup per row of a K/V tile (ex_load_tile_paged); entries
+//     of their own again (ex_fwd_varlen_paged_kernel: the forward body with ExParamsPg).
 //   * score modifiers (FlashAttention-2's softcap and alibi_slopes): x = scale q.k becomes softcap tanh(x / softcap), then
 //     x - slope |i + coff - j|, before the visibility rule; the backward multiplies dS by 1 - tanh^2.  Entries of their own
 //     (ex_*_score_kernel: the bodies with ExParamsS), so the kernels without a modifier keep their code.
@@ -60,6 +63,45 @@ __device__ __forceinline__ void ex_load_tile(float* __restrict__ dst, const T* _
         dst[r * LD + c] = x;
     }
 }
+// The same tile through a block table (ExPage; the paged varlen forward): row r0 + r of the sequence is row t % ps of page
+// trow[t / ps] of the pool behind src (page stride `pstride`, token stride `ld`, 64-bit offsets).  A page outside the pool gives
+// zeros like a row past n; only the entries of rows < n are read.
+template <typename T, int DP, int LD, int NTHREADS>
+__device__ __forceinline__ void ex_load_tile_paged(float* __restrict__ dst, const T* __restrict__ src, const ExPage& pg,
+                                                   const int* __restrict__ trow, long long pstride, int r0, int rows, int n, int d,
+                                                   bool vec, int ld) {
+    if (vec) {
+        for (int idx = threadIdx.x; idx < rows * (DP / 4); idx += NTHREADS) {
+            const int r = idx / (DP / 4), c = 4 * (idx - r * (DP / 4));
+            f32x4 x = {0.f, 0.f, 0.f, 0.f};
+            if (r0 + r < n && c < d) {
+                const int slot = pg_slot(pg, r0 + r), page = trow[slot];
+                if ((unsigned)page < (unsigned)pg.num_blocks) {
+                    const T* at = src + (size_t)page * (size_t)pstride + (size_t)(r0 + r - slot * pg.ps) * ld + c;
+                    if constexpr (sizeof(T) == 4) {
+                        x = *reinterpret_cast<const f32x4*>(at);
+                    } else {
+                        T t[4];
+                        *reinterpret_cast<u32x2*>(t) = *reinterpret_cast<const u32x2*>(at);
+                        x = f32x4{to_f32<T>(t[0]), to_f32<T>(t[1]), to_f32<T>(t[2]), to_f32<T>(t[3])};
+                    }
+                }
+            }
+            *reinterpret_cast<f32x4*>(dst + r * LD + c) = x;
+        }
+        return;
+    }
+    for (int idx = threadIdx.x; idx < rows * DP; idx += NTHREADS) {
+        const int r = idx / DP, c = idx - r * DP;
+        float x = 0.f;
+        if (r0 + r < n && c < d) {
+            const int slot = pg_slot(pg, r0 + r), page = trow[slot];
+            if ((unsigned)page < (unsigned)pg.num_blocks)
+                x = to_f32<T>(src[(size_t)page * (size_t)pstride + (size_t)(r0 + r - slot * pg.ps) * ld + c]);
+        }
+        dst[r * LD + c] = x;
+    }
+}
 // score modifiers of one element in the exact kernels' domain (ExScore; x = scale q.k, dist = i + coff - j); dt = 1 - t^2, the
 // softcap's derivative (1 without one).  The forward and both backward bodies evaluate it with these same operations.
 __device__ __forceinline__ float ex_score_mod(const ExScore& sc, float slope, float x, int dist, float& dt) {
@@ -73,7 +115,9 @@ __device__ __forceinline__ float ex_score_mod(const ExScore& sc, float slope, fl
     return x;
 }
 template <typename P> constexpr bool ex_has_score() { return std::is_base_of<ExParamsS, P>::value; }
-template <typename P> constexpr bool ex_has_sink() { return std::is_same<P, ExParamsK>::value; }
+template <typename P> constexpr bool ex_has_sink() { return std::is_base_of<ExParamsK, P>::value; }
+template <typename P> struct ex_is_paged : std::false_type {};
+template <typename B> struct ex_is_paged<ExParamsPg<B>> : std::true_type {};
 
 template <typename T> __device__ __forceinline__ bool ex_quad_ok(int d, const void* a, const void* b, const void* c, const void* e) {
     return d % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
@@ -88,11 +132,13 @@ template <typename T> __device__ __forceinline__ bool ex_quad_ok(int d, const vo
 // grid, inside sequence b.  q rows at token stride sq (k, v: sk, sv), o / dq / dk / dv rows at hq * d, lse at (h, token), delta at
 // (token, h).
 // P: ExParams, or ExParamsS for the score-modifier entries (the same for the backward bodies), or ExParamsK for the sink entries
-// (forward only: the sink joins the row's normaliser in the epilogue, the key loop does not know it)
+// (forward only: the sink joins the row's normaliser in the epilogue, the key loop does not know it), or ExParamsPg of one of them
+// for the paged entries (forward only, VAR: the K/V tiles come through the block table, nothing else differs)
 template <typename T, int DP, int NW, bool WIN, bool VAR, typename P>
 __device__ __forceinline__ void ex_fwd_body(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, T* __restrict__ o,
                                             float* __restrict__ lse, P& p) {
-    constexpr bool SC = ex_has_score<P>(), SNK = ex_has_sink<P>();
+    constexpr bool SC = ex_has_score<P>(), SNK = ex_has_sink<P>(), PG = ex_is_paged<P>::value;
+    static_assert(!PG || VAR, "the paged entries are varlen entries");
     constexpr int LD = DP + 4, BM = 16 * NW, BN = 32, NT = DP / 16, PLD = BN + 4, NTH = NW * 64;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Qs = smem;
@@ -103,13 +149,19 @@ __device__ __forceinline__ void ex_fwd_body(const T* __restrict__ q, const T* __
     const int bh = blockIdx.x / ntile;
     const int q0 = (blockIdx.x - bh * ntile) * BM;
     [[maybe_unused]] int sq0 = 0, sk0 = 0, hh = 0, hk = 0;
+    [[maybe_unused]] const int* pg_row = nullptr;   // paged: this sequence's table row
     if constexpr (VAR) {   // packed sequences: narrow the padded call to sequence b (fa_ex_mfma.hip: EXM_VARLEN_UNIT)
         const int b = bh / p.hq;
         hh = bh - b * p.hq;
         hk = kv_unit(hh, p.kvg);
         int lq, lk;
         seq_span(p.cu_q, b, p.total_q, p.nq, sq0, lq);
-        seq_span(p.cu_k, b, p.total_k, p.nk, sk0, lk);
+        if constexpr (PG) {   // (the keys are no span of a packed tensor: sk0 stays 0)
+            lk = paged_len(p.cu_k, b, p.nk);
+            pg_row = p.pg.table + (size_t)b * p.pg.max_blocks;
+        } else {
+            seq_span(p.cu_k, b, p.total_k, p.nk, sk0, lk);
+        }
         p.nq = lq; p.nk = lk; p.coff = lk - lq;
         if (q0 >= p.nq) return;
     }
@@ -122,7 +174,8 @@ __device__ __forceinline__ void ex_fwd_body(const T* __restrict__ q, const T* __
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int lr = lane & 15, lq = lane >> 4;
 
-    const bool vec = ex_quad_ok<T>(p.d, q, k, v, q) && (!VAR || (p.sq | p.sk | p.sv) % 4 == 0);
+    bool vec = ex_quad_ok<T>(p.d, q, k, v, q) && (!VAR || (p.sq | p.sk | p.sv) % 4 == 0);
+    if constexpr (PG) vec = vec && (p.pg.kps | p.pg.vps) % 4 == 0;
     ex_load_tile<T, DP, LD, NTH, VAR>(Qs, q + qbase, q0, BM, p.nq, p.d, vec, VAR ? p.sq : 0);
     f32x4 acc[NT];
 #pragma unroll
@@ -142,8 +195,13 @@ __device__ __forceinline__ void ex_fwd_body(const T* __restrict__ q, const T* __
     for (int k0 = kstart; k0 < kend; k0 += BN) {
         if (!VAR && !ex_tile_live(p, q0, min(q0 + BM, p.nq), k0, min(k0 + BN, p.nk))) continue;   // block-sparse skip (uniform)
         __syncthreads();
-        ex_load_tile<T, DP, LD, NTH, VAR>(Ks, k + kbase, k0, BN, p.nk, p.d, vec, VAR ? p.sk : 0);
-        ex_load_tile<T, DP, LD, NTH, VAR>(Vs, v + vbase, k0, BN, p.nk, p.d, vec, VAR ? p.sv : 0);
+        if constexpr (PG) {
+            ex_load_tile_paged<T, DP, LD, NTH>(Ks, k + kbase, p.pg, pg_row, p.pg.kps, k0, BN, p.nk, p.d, vec, p.sk);
+            ex_load_tile_paged<T, DP, LD, NTH>(Vs, v + vbase, p.pg, pg_row, p.pg.vps, k0, BN, p.nk, p.d, vec, p.sv);
+        } else {
+            ex_load_tile<T, DP, LD, NTH, VAR>(Ks, k + kbase, k0, BN, p.nk, p.d, vec, VAR ? p.sk : 0);
+            ex_load_tile<T, DP, LD, NTH, VAR>(Vs, v + vbase, k0, BN, p.nk, p.d, vec, VAR ? p.sv : 0);
+        }
         __syncthreads();
         f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -261,6 +319,13 @@ template <typename T, int DP, int NW, bool WIN>
 __global__ __launch_bounds__(NW * 64) void ex_fwd_varlen_sink_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                                      const T* __restrict__ v, T* __restrict__ o,
                                                                      float* __restrict__ lse, ExParamsK p) {
+    ex_fwd_body<T, DP, NW, WIN, true>(q, k, v, o, lse, p);
+}
+// paged K/V: P = ExParamsPg<ExParams | ExParamsS | ExParamsK>
+template <typename T, int DP, int NW, bool WIN, typename P>
+__global__ __launch_bounds__(NW * 64) void ex_fwd_varlen_paged_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                                      const T* __restrict__ v, T* __restrict__ o,
+                                                                      float* __restrict__ lse, P p) {
     ex_fwd_body<T, DP, NW, WIN, true>(q, k, v, o, lse, p);
 }
 
@@ -813,6 +878,46 @@ static hipError_t launch_ex_one(const ExArgs& a, bool backward, hipStream_t st) 
     }
 }
 
+// The paged varlen forward (a.block_table != null) on the exact kernels
+template <typename T, int DP, bool WIN, bool SC, bool SK>
+static hipError_t ex_paged_fwd_t(const ExArgs& a, hipStream_t st) {
+    constexpr int NW = 4, LD = DP + 4;
+    ExParamsPg<decltype(ex_params<SC, SK>(a))> p;
+    static_cast<decltype(ex_params<SC, SK>(a))&>(p) = ex_params<SC, SK>(a);
+    p.pg = make_ex_page(a);
+    const size_t smem = sizeof(float) * ((16 * NW + 64) * LD + NW * 16 * 36);
+    auto kern = ex_fwd_varlen_paged_kernel<T, DP, NW, WIN, decltype(p)>;
+    hipError_t e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
+    if (e != hipSuccess) return e;
+    dim3 grid((unsigned)(((a.nq + 16 * NW - 1) / (16 * NW)) * a.bh));
+    ProfScope ps(K_EX_FWD, st);
+    hipLaunchKernelGGL(kern, grid, dim3(NW * 64), smem, st, (const T*)a.q, (const T*)a.k, (const T*)a.v, (T*)a.o, a.lse, p);
+    return hipGetLastError();
+}
+template <typename T, bool WIN, bool SC, bool SK>
+static hipError_t ex_paged_by_d(const ExArgs& a, hipStream_t st) {
+    if (a.d <= 64) return ex_paged_fwd_t<T, 64, WIN, SC, SK>(a, st);
+    if (a.d <= 128) return ex_paged_fwd_t<T, 128, WIN, SC, SK>(a, st);
+    return ex_paged_fwd_t<T, 256, WIN, SC, SK>(a, st);
+}
+template <typename T>
+static hipError_t ex_paged(const ExArgs& a, hipStream_t st) {
+    const bool win = ex_windowed(a);
+    if (a.sinks) return win ? ex_paged_by_d<T, true, true, true>(a, st) : ex_paged_by_d<T, false, true, true>(a, st);
+    if (ex_scoremod(a)) return win ? ex_paged_by_d<T, true, true, false>(a, st) : ex_paged_by_d<T, false, true, false>(a, st);
+    return win ? ex_paged_by_d<T, true, false, false>(a, st) : ex_paged_by_d<T, false, false, false>(a, st);
+}
+static hipError_t launch_ex_varlen_paged(const ExArgs& a, hipStream_t st) {
+    const int path = option(OPT_EX_PATH);
+    if (path != 1 && ex_mfma_paged_supported(a)) return launch_ex_mfma_varlen_paged(a, st);
+    if (path >= 2) return hipErrorInvalidConfiguration;
+    switch (a.dtype) {
+        case 0: return ex_paged<float>(a, st);
+        case 1: return ex_paged<__half>(a, st);
+        default: return ex_paged<__hip_bfloat16>(a, st);
+    }
+}
+
 // Packed sequences (a.cu_q != null; the C layer has handled the calls with an empty side): the extended kernels only — 16-bit MFMA
 // where they take the call, exact f32 otherwise (option ex_path as for the other calls: 1 = exact f32, 2 / 3 = MFMA or fail).
 static hipError_t launch_ex_varlen_one(const ExArgs& a, bool backward, hipStream_t st) {
@@ -828,6 +933,7 @@ static hipError_t launch_ex_varlen_one(const ExArgs& a, bool backward, hipStream
 
 hipError_t launch_ex(const ExArgs& a, bool backward, hipStream_t st) {
     if (a.cu_q) {
+        if (a.block_table) return backward ? hipErrorInvalidValue : launch_ex_varlen_paged(a, st);   // (forward only)
         if (!backward || a.kv_group <= 1) return launch_ex_varlen_one(a, backward, st);
         // grouped: per-query-head partials (total_k, heads_q, d) in front of the row constants, then the group sum over units of
         // d elements — unit t * heads_kv + j adds partial rows t * heads_q + j * g + m, m = 0 .. g-1, in that order

@@ -81,6 +81,32 @@ __device__ __forceinline__ void ex_sink_norm(float m, float l, float snk, float&
     lse = mp + logf(lp);
 }
 
+// Paged K/V for the varlen forward (fa_ex_forward_varlen_paged; the kFeatPaged instantiations of fa_ex_mfma.hip and the
+// ex_fwd_varlen_paged_kernel entries of fa_ex.hip): k and v are pools (num_blocks, ps, heads_kv, d) and key t of sequence b is row
+// t % ps of page table[b * max_blocks + t / ps].  Once more a parameter block of its own, ExParamsPg<B> = B + ExPage for B any of
+// the three blocks above, so every other kernel keeps its block and its code.  nk is then the host's cap on a sequence's keys,
+// min(max_seqlen_k, max_blocks * ps); sk, sv stay the token strides inside a page; total_k is not used.
+struct ExPage {
+    const int* table;      // (batch, max_blocks) untrusted page numbers: one outside [0, num_blocks) reads as zero K and V
+    long long kps, vps;    // page strides of the K and the V pool (elements): page offsets are 64-bit
+    int max_blocks, num_blocks;
+    int ps;                // tokens per page, a multiple of 16 up to 2^16
+    unsigned ps16m;        // ceil(2^32 / (ps / 16)), 0 for ps = 16: t / ps = umulhi(t / 16, ps16m), exact for t < 2^24
+};
+template <typename B> struct ExParamsPg : B {
+    ExPage pg;
+};
+static_assert(sizeof(ExPage) == 40 && sizeof(ExParamsPg<ExParamsK>) == sizeof(ExParamsK) + sizeof(ExPage), "ExParamsPg layout: ExPage after every other field");
+// page slot t / ps of key t (uniform where t is)
+__device__ __forceinline__ int pg_slot(const ExPage& pg, int t) {
+    return pg.ps16m ? (int)__umulhi((unsigned)t >> 4, pg.ps16m) : (t >> 4);
+}
+// keys of sequence b of a paged call: only the difference of its two offsets means anything; clamped to [0, cap]
+__device__ __forceinline__ int paged_len(const int* cu, int b, int cap) {
+    const long long n = (long long)cu[b + 1] - (long long)cu[b];
+    return (int)min(max(n, 0ll), (long long)cap);
+}
+
 // this unit's slope (0 without ALiBi): uniform over the workgroup
 __device__ __forceinline__ float ex_slope(const ExScore& sc, int bh) {
     return sc.alibi ? sc.alibi[(bh / sc.al_heads) * sc.al_bstride + bh % sc.al_heads] : 0.f;
@@ -147,6 +173,40 @@ __device__ __forceinline__ bool ex_tile_live(const ExParams& p, int r0, int r1, 
     return false;
 }
 
+// Paged staging of one K tile and one V tile (the varlen forward of fa_ex_mfma.hip with kFeatPaged), in place of two
+// dma_stage_tile calls.  The LDS image, the pieces (1 KiB = RPP = 512 / D rows, wave w issues pieces w, w + NW, ..) and the lane
+// offsets inside a piece (dma_lane_voff with the pool's token stride) are dma_stage_tile's.  A piece starts at key row0 + RPP * pc,
+// row0 a multiple of ROWS = 128 and RPP * pc a multiple of RPP <= 8, and a page holds a multiple of 16 keys: no piece straddles a
+// page, so one wave-uniform table entry (a scalar load) serves a piece, K and V alike.  Instead of a 32-bit soffset from the
+// tensor's start each piece gets a descriptor of its own: the 64-bit address of its first row, and as num_records the bytes of
+// its rows below nk — 0 for a piece past the sequence or on a page outside the pool, whose lanes all fail the range check and
+// land as zeros, as the rows past a packed tensor's end do.  Never a branch around the DMA: the image is always fully written.
+// The descriptor words are SGPRs written right before dma16_issue, whose s_mov m0 + s_nop 3 are the five wait states a buffer
+// instruction needs after a v_readfirstlane wrote one of its SGPR operands.
+// trow: the sequence's table row; last = pg_slot(nk - 1) bounds the slot, so no entry past ceil(nk / ps) is read.
+template <int D, int ROWS, int NW>
+__device__ __forceinline__ void dma_stage_kv_paged(const ExPage& pg, const int* __restrict__ trow, int last, const uint16_t* kh,
+                                                   const uint16_t* vh, char* ktile, char* vtile, int row0, int nk, int voff_k,
+                                                   int voff_v, int w, int dr, int sk, int sv) {
+    constexpr int RPP = 512 / D, PIECES = ROWS / RPP, PER_WAVE = PIECES / NW;
+    static_assert(PIECES % NW == 0 && (RPP * NW) % 16 == 0 && 16 % RPP == 0, "pieces: whole per wave, one swizzle class, inside a page");
+    const unsigned tk = lds_addr_of(ktile), tv = lds_addr_of(vtile);
+#pragma unroll
+    for (int j = 0; j < PER_WAVE; ++j) {
+        const int pc = w + NW * j;
+        const int key = __builtin_amdgcn_readfirstlane(row0 + RPP * pc);
+        const int rows = min(RPP, nk - key);                 // <= 0: the piece lies past the sequence
+        const int slot = min(pg_slot(pg, key), last);
+        const int page = trow[slot];
+        const bool ok = rows > 0 && (unsigned)page < (unsigned)pg.num_blocks;
+        const long long inpage = key - slot * pg.ps;
+        const long long ko = ok ? (long long)page * pg.kps + inpage * sk : 0ll;
+        const long long vo = ok ? (long long)page * pg.vps + inpage * sv : 0ll;
+        dma16_issue(make_rsrc_s(kh + ko, ok ? span_bytes(rows, dr, sk) : 0u), tk + pc * 1024, voff_k, 0);
+        dma16_issue(make_rsrc_s(vh + vo, ok ? span_bytes(rows, dr, sv) : 0u), tv + pc * 1024, voff_v, 0);
+    }
+}
+
 inline ExParams make_ex_params(const ExArgs& a) {
     ExParams p;
     p.nq = (int)a.nq; p.nk = (int)a.nk; p.d = (int)a.d;
@@ -194,6 +254,16 @@ inline ExParamsK make_ex_params_k(const ExArgs& a) {
     p.snk.heads = (int)(a.sink_heads > 0 ? a.sink_heads : 1);
     p.snk.pad_ = 0;
     return p;
+}
+
+inline ExPage make_ex_page(const ExArgs& a) {
+    ExPage g;
+    g.table = a.block_table;
+    g.kps = a.page_stride_k; g.vps = a.page_stride_v;
+    g.max_blocks = (int)a.max_blocks; g.num_blocks = (int)a.num_blocks;
+    g.ps = (int)a.page_size;
+    g.ps16m = kv_magic(a.page_size / 16);
+    return g;
 }
 
 }  // namespace fa

@@ -20,6 +20,11 @@
 //   FEAT bit 5  attention sinks (forward only, always with bit 4): the parameter block grows once more (ExParamsK) and the
 //               epilogue's normaliser takes the unit's sink logit as one more column (ex_sink_norm).  The key loop is bit 4's.
 //               The backward of a sink call runs the kernels of the call without sinks and ex_dsink_kernel (fa_ex.hip).
+//   FEAT bit 6  paged K/V (forward only, always with bit 3, never with bits 0 and 1): k and v are pools of pages and a sequence's
+//               keys are found through a block table (ExPage: the parameter block grows by it, ExParamsPg).  Only the staging of
+//               a K/V tile differs (dma_stage_kv_paged): each 1-KiB piece takes its page from one scalar table load and gets a
+//               buffer descriptor of its own; everything after the staging is the text of the packed kernel, so a sequence gets
+//               the bits of the packed call on the same tokens.  Kernels of their own (exm_fwd_paged_kernel).
 // Dense mask bytes are fetched with range-checked buffer loads (rows / bytes past the mask read as 0 = masked); when Nk, the
 // mask pointer and the (b,h) stride are multiples of 4 a lane of the query-on-the-lane kernels takes the 4 keys of a
 // register group with one dword load.  The block-sparse mask needs br, bc multiples of 32 here (a wave's 32 x 32 block
@@ -33,7 +38,7 @@ namespace fa {
 
 namespace {
 
-constexpr int kFeatMask = 1, kFeatDrop = 2, kFeatWindow = 4, kFeatVarlen = 8, kFeatScore = 16, kFeatSink = 32;
+constexpr int kFeatMask = 1, kFeatDrop = 2, kFeatWindow = 4, kFeatVarlen = 8, kFeatScore = 16, kFeatSink = 32, kFeatPaged = 64;
 // the parameter block of an instantiation: ExParamsK (+ the sinks) with kFeatSink, ExParamsS (+ the score modifiers) with
 // kFeatScore, else ExParams as before
 template <int FEAT> using ExP = typename std::conditional<(FEAT & kFeatSink) != 0, ExParamsK,
@@ -230,6 +235,8 @@ __device__ __forceinline__ unsigned keep_bits_q(const ExParams& p, unsigned hi, 
 template <int FEAT, typename P> __device__ __forceinline__ const ExScore& sc_of(const P& p) { return p.sc; }
 // the same for the sinks of a kFeatSink instantiation's ExParamsK
 template <int FEAT, typename P> __device__ __forceinline__ const ExSink& sink_of(const P& p) { return p.snk; }
+// the same for the pages of a kFeatPaged instantiation's ExParamsPg
+template <int FEAT, typename P> __device__ __forceinline__ const ExPage& pg_of(const P& p) { return p.pg; }
 // this unit's al (0 without ALiBi), the same product in every kernel
 __device__ __forceinline__ float alibi_k(const ExScore& sc, int bh) { return ex_slope(sc, bh) * sc.al_k; }
 
@@ -253,15 +260,17 @@ __device__ __forceinline__ unsigned keep_bits_k(const ExParams& p, unsigned hi_b
 // Varlen (FEAT bit 3): the workgroup's unit bh = b * hq + h and its tile T0 come from the padded grid (nq, nk = the maxima); it
 // narrows nq, nk, coff to sequence b (seq_span) and leaves before its first barrier when its tile starts past the sequence.
 // Bases, buffer ranges and row strides become the sequence's; DR stays the column bound.
+// (kFeatPaged: the keys are no span of a packed tensor — sk0 stays 0, the length is paged_len, ub names the table row)
 #define EXM_VARLEN_UNIT(T0, N0)                                                                                         \
-    [[maybe_unused]] int sq0 = 0, sk0 = 0, hh = 0, hk = 0;                                                              \
+    [[maybe_unused]] int sq0 = 0, sk0 = 0, hh = 0, hk = 0, ub = 0;                                                      \
     if constexpr (VAR) {                                                                                                \
         const int b = bh / p.hq;                                                                                        \
         hh = bh - b * p.hq;                                                                                             \
         hk = kv_unit(hh, p.kvg);                                                                                        \
         int lq, lk;                                                                                                     \
         seq_span(p.cu_q, b, p.total_q, nq, sq0, lq);                                                                    \
-        seq_span(p.cu_k, b, p.total_k, nk, sk0, lk);                                                                    \
+        if constexpr ((FEAT & kFeatPaged) != 0) { ub = b; lk = paged_len(p.cu_k, b, nk); }                              \
+        else seq_span(p.cu_k, b, p.total_k, nk, sk0, lk);                                                               \
         nq = lq; nk = lk; p.coff = lk - lq;                                                                             \
         if ((T0) >= (N0)) return;                                                                                       \
     }
@@ -284,6 +293,14 @@ template <typename Tag, int D, int FEAT>
 __global__ __launch_bounds__(512, 2) void exm_fwd_sink_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                               const uint16_t* __restrict__ v, uint16_t* __restrict__ o,
                                                               float* __restrict__ lse, ExParamsK p, float c_log2) {
+#include "fa_ex_mfma_fwd.inc"
+}
+
+// FEAT with kFeatPaged (and kFeatVarlen): the parameter block of the instantiation without the bit grows by the pages (ExParamsPg)
+template <typename Tag, int D, int FEAT>
+__global__ __launch_bounds__(512, 2) void exm_fwd_paged_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
+                                                               const uint16_t* __restrict__ v, uint16_t* __restrict__ o,
+                                                               float* __restrict__ lse, ExParamsPg<ExP<FEAT>> p, float c_log2) {
 #include "fa_ex_mfma_fwd.inc"
 }
 
@@ -578,6 +595,46 @@ static hipError_t exm_varlen_by_feat(const ExArgs& a, bool backward, hipStream_t
         return drop ? exm_varlen_fwd_t<Tag, D, S | kFeatDrop>(a, st) : exm_varlen_fwd_t<Tag, D, S>(a, st);
     }
     return ex_scoremod(a) ? exm_varlen_by_feat_s<Tag, D, kFeatScore>(a, backward, st) : exm_varlen_by_feat_s<Tag, D, 0>(a, backward, st);
+}
+
+// ---- paged K/V (a.block_table != null): the varlen forward with kFeatPaged, {window} x {plain, score, score + sink}
+bool ex_mfma_paged_supported(const ExArgs& a) {
+    if (!ex_mfma_supported(a) || a.dropout_p > 0.0) return false;
+    if (a.stride_q % 8 != 0 || a.stride_k % 8 != 0 || a.stride_v % 8 != 0 || a.page_stride_k % 8 != 0 || a.page_stride_v % 8 != 0) return false;
+    const void* ptrs[] = {a.q, a.k, a.v, a.o};
+    for (const void* ptr : ptrs)
+        if ((reinterpret_cast<uintptr_t>(ptr) & 15) != 0) return false;
+    const int64_t sq = a.stride_q > a.heads_q * a.d ? a.stride_q : a.heads_q * a.d;
+    const int64_t skv = a.stride_k > a.stride_v ? a.stride_k : a.stride_v;
+    // the 32-bit buffer offsets: inside one sequence of q and o, inside one piece (at most 8 rows) of a page
+    return a.nq * sq * 2 < ((int64_t)1 << 31) && 8 * skv * 2 < ((int64_t)1 << 31);
+}
+
+template <typename Tag, int D, int FEAT>
+static hipError_t exm_paged_fwd_t(const ExArgs& a, hipStream_t st) {
+    ExParamsPg<ExP<FEAT>> p;
+    static_cast<ExP<FEAT>&>(p) = make_exm_params<FEAT>(a);
+    p.pg = make_ex_page(a);
+    const size_t smem = 2 * 2 * 128 * D * 2;
+    auto kern = exm_fwd_paged_kernel<Tag, D, FEAT | kFeatVarlen | kFeatPaged>;
+    hipError_t e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
+    if (e != hipSuccess) return e;
+    ProfScope ps(K_EX_FWD, st);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(((a.nq + 255) / 256) * a.bh)), dim3(512), smem, st, (const uint16_t*)a.q,
+                       (const uint16_t*)a.k, (const uint16_t*)a.v, (uint16_t*)a.o, a.lse, p, a.scale * 1.4426950408889634f);
+    return hipGetLastError();
+}
+template <typename Tag, int D>
+static hipError_t exm_paged_by_feat(const ExArgs& a, hipStream_t st) {
+    const bool win = ex_windowed(a);
+    if (a.sinks) return win ? exm_paged_fwd_t<Tag, D, kFeatScore | kFeatSink | kFeatWindow>(a, st) : exm_paged_fwd_t<Tag, D, kFeatScore | kFeatSink>(a, st);
+    if (ex_scoremod(a)) return win ? exm_paged_fwd_t<Tag, D, kFeatScore | kFeatWindow>(a, st) : exm_paged_fwd_t<Tag, D, kFeatScore>(a, st);
+    return win ? exm_paged_fwd_t<Tag, D, kFeatWindow>(a, st) : exm_paged_fwd_t<Tag, D, 0>(a, st);
+}
+// (the caller has checked ex_mfma_paged_supported, and that max_seqlen_q and the key cap are > 0)
+hipError_t launch_ex_mfma_varlen_paged(const ExArgs& a, hipStream_t st) {
+    if (a.dtype == 2) return a.d > 64 ? exm_paged_by_feat<bf16_tag, 128>(a, st) : exm_paged_by_feat<bf16_tag, 64>(a, st);
+    return a.d > 64 ? exm_paged_by_feat<f16_tag, 128>(a, st) : exm_paged_by_feat<f16_tag, 64>(a, st);
 }
 
 // (the caller has checked ex_mfma_varlen_supported, and that max_seqlen_q, max_seqlen_k, total_q, total_k are > 0)

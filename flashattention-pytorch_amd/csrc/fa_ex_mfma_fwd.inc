@@ -1,10 +1,12 @@
 // Kernel body, included by the kernel entries of fa_ex_mfma.hip (the plain and the score-modifier entry of one kernel share
 // it textually, so that each entry is compiled as the one function it was before the score modifiers; a device function
 // called from both changes the code of the existing entries).  In scope: the kernel's parameters, p an ExParams or an
-// ExParamsS (kFeatScore) or an ExParamsK (kFeatSink), and the template parameters Tag, D, FEAT.
+// ExParamsS (kFeatScore) or an ExParamsK (kFeatSink), or one of them grown by the pages (kFeatPaged: ExParamsPg), and the
+// template parameters Tag, D, FEAT.
 
     constexpr int NW = 8, BM = 32 * NW, KB = 4, BN = 32 * KB, NKS = D / 16, NDV = D / 32, TILE_BYTES = BN * D * 2;
     constexpr bool VAR = (FEAT & kFeatVarlen) != 0, SC = (FEAT & kFeatScore) != 0, SNK = (FEAT & kFeatSink) != 0;
+    constexpr bool PG = (FEAT & kFeatPaged) != 0;   // k, v are pools read through a block table: only `stage` differs
     extern __shared__ __attribute__((aligned(16))) char smem[];   // [2 buffers][K tile | V tile]
     const int DR = p.d;
     int nq = p.nq, nk = p.nk;
@@ -31,10 +33,21 @@
     const rsrc_s_t v_rs = make_rsrc_s(v + vbase, VAR ? span_bytes(nk, DR, p.sv) : (unsigned)nk * DR * 2);
     const int dma_voff = dma_lane_voff<D, VAR>(lane, w, DR, VAR ? p.sk : DR);
     const int dma_voff_v = VAR ? dma_lane_voff<D, VAR>(lane, w, DR, p.sv) : dma_voff;
+    [[maybe_unused]] const int* pg_row = nullptr;   // kFeatPaged: this sequence's table row and its last slot in use
+    [[maybe_unused]] int pg_last = 0;
+    if constexpr (PG) {
+        pg_row = pg_of<FEAT>(p).table + (size_t)ub * pg_of<FEAT>(p).max_blocks;
+        pg_last = pg_slot(pg_of<FEAT>(p), max(nk, 1) - 1);
+    }
     auto stage = [&](int buf, int k0) {
         char* kb_ = smem + buf * 2 * TILE_BYTES;
-        dma_stage_tile<D, BN, NW, VAR>(k_rs, kb_, k0, dma_voff, w, DR, 0, VAR ? p.sk : DR);
-        dma_stage_tile<D, BN, NW, VAR>(v_rs, kb_ + TILE_BYTES, k0, dma_voff_v, w, DR, 0, VAR ? p.sv : DR);
+        if constexpr (PG) {
+            dma_stage_kv_paged<D, BN, NW>(pg_of<FEAT>(p), pg_row, pg_last, k + kbase, v + vbase, kb_, kb_ + TILE_BYTES, k0, nk, dma_voff,
+                                          dma_voff_v, w, DR, p.sk, p.sv);
+        } else {
+            dma_stage_tile<D, BN, NW, VAR>(k_rs, kb_, k0, dma_voff, w, DR, 0, VAR ? p.sk : DR);
+            dma_stage_tile<D, BN, NW, VAR>(v_rs, kb_ + TILE_BYTES, k0, dma_voff_v, w, DR, 0, VAR ? p.sv : DR);
+        }
     };
     const MaskSrc msk = make_mask_src(p, bh);
     const bool use_bm = (FEAT & kFeatMask) && p.bmask != nullptr;

@@ -159,6 +159,12 @@ struct ExArgs {
     const float* sinks = nullptr;
     int64_t sink_heads = 1;
     float* dsinks = nullptr;
+    // paged K/V of the varlen forward (fa_ex_forward_varlen_paged; block_table != null, forward only, no dropout): k and v are pools
+    // (num_blocks, page_size, heads_q / kv_group, d) with token strides stride_k / stride_v and page strides page_stride_k / _v;
+    // key t of sequence b is row t % page_size of page block_table[b * max_blocks + t / page_size] (untrusted device numbers);
+    // len_k[b] = cu_k[b + 1] - cu_k[b] clamped to [0, nk], nk = min(max_seqlen_k, max_blocks * page_size); total_k is not used.
+    const int* block_table = nullptr;
+    int64_t max_blocks = 0, num_blocks = 0, page_size = 0, page_stride_k = 0, page_stride_v = 0;
 };
 // does the call carry a score modifier (softcap or ALiBi)?  Such a call runs on the extended kernels only.
 inline bool ex_scoremod(const ExArgs& a) { return a.softcap > 0.0 || a.alibi != nullptr; }
@@ -175,6 +181,8 @@ bool ex_mfma_supported(const ExArgs& a);
 hipError_t launch_ex_mfma(const ExArgs& a, bool backward, hipStream_t st);
 bool ex_mfma_varlen_supported(const ExArgs& a);
 hipError_t launch_ex_mfma_varlen(const ExArgs& a, bool backward, hipStream_t st);
+bool ex_mfma_paged_supported(const ExArgs& a);                        // the paged varlen forward (a.block_table != null)
+hipError_t launch_ex_mfma_varlen_paged(const ExArgs& a, hipStream_t st);
 size_t ex_backward_workspace_bytes(int64_t bh, int64_t nq);
 // the two per-query-head dK / dV partial slabs of a grouped backward (kv_group > 1), each rounded to 256 bytes
 inline size_t kv_partial_bytes(int64_t bh, int64_t nk, int64_t d, int dtype) {

@@ -47,6 +47,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_ex_forward_sink", "fa_ex_backward_sink", "fa_ex_forward_varlen_sink", "fa_ex_backward_varlen_sink",
     "fa_ex_forward_kvcache_sink", "fa_ex_kvcache_workspace_bytes_sink",
     "fa_ex_forward_kvcache_varlen", "fa_ex_kvcache_workspace_bytes_varlen",
+    "fa_ex_forward_varlen_paged",
 )
 
 
@@ -172,6 +173,10 @@ def _load_library() -> ctypes.CDLL:
     lib.fa_ex_backward_varlen_sink.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp] + varlen_sm[:21] + [vp, i64, vp] + varlen_sm[21:] + \
         [vp, sz, vp]
     lib.fa_ex_backward_varlen_sink.restype = ci
+    # the varlen forward over a paged K/V cache: the varlen sink call's without dropout_p, seed, then block_table,
+    # max_blocks_per_seq, num_blocks, page_block_size, k_page_stride, v_page_stride
+    lib.fa_ex_forward_varlen_paged.argtypes = [vp, vp, vp, vp, vp] + varlen_sm[:21] + [vp, i64] + [vp, i64, i64, i64, i64, i64] + [vp]
+    lib.fa_ex_forward_varlen_paged.restype = ci
     lib.fa_ex_forward_kvcache_sink.argtypes = [vp] * 8 + [i64] * 7 + [ci] + [i64] * 10 + [ci, i64, i64, dbl, dbl, vp, i64, i64] + \
         [vp, i64, i64, i64, i64, vp, i64, vp] + [vp, vp, i64, i64, i64, i64, ci] + [ci, vp, vp, i64] + [vp, i64] + [vp, sz, vp]
     lib.fa_ex_forward_kvcache_sink.restype = ci
@@ -622,16 +627,77 @@ def _varlen_common(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_s
     return (cu_q, cu_k, cu_q.shape[0] - 1, hq, hkv, total_q, total_k, mq, mk, d, _DTYPE_CODE[q.dtype], sq, sk, sv)
 
 
+def _varlen_paged_forward(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, dropout_p, wl, wr,
+                          cap, alibi_slopes, sinks, block_table):
+    """ex_varlen_forward with a block_table (fa_ex_forward_varlen_paged), its arguments checked"""
+    if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32:
+        dt = block_table.dtype if isinstance(block_table, torch.Tensor) else type(block_table).__name__
+        raise NotImplementedError(f"{who}: block_table of dtype {dt} is not supported (int32 tensor expected)")
+    if float(dropout_p) > 0.0:
+        raise ValueError(f"{who}: dropout_p > 0 is not supported with block_table (an inference path)")
+    for t in (q, k, v, cu_seqlens_q, cu_seqlens_k, block_table):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{who}: tensors must be on the GPU (HIP device); there is no CPU path")
+    if len({q.device, k.device, v.device, cu_seqlens_q.device, cu_seqlens_k.device, block_table.device}) != 1:
+        raise RuntimeError(f"{who}: all tensors must be on one device")
+    if q.dim() != 3 or k.dim() != 4 or v.shape != k.shape or q.shape[2] != k.shape[3]:
+        raise RuntimeError(f"{who}: with block_table q must be (total_q, H_q, d), k and v pools (num_blocks, page_block_size, H_kv, d); "
+                           f"got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    if q.dtype not in _DTYPE_CODE or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise RuntimeError(f"{who}: q, k, v must share a supported dtype")
+    for name, c in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if c.dtype != torch.int32 or c.dim() != 1 or c.shape[0] < 2:
+            raise RuntimeError(f"{who}: {name} must be a 1-D int32 tensor of batch + 1 >= 2 offsets")
+    if cu_seqlens_q.shape != cu_seqlens_k.shape:
+        raise RuntimeError(f"{who}: cu_seqlens_q and cu_seqlens_k must have the same length (batch + 1)")
+    b = cu_seqlens_q.shape[0] - 1
+    total_q, hq, d = q.shape
+    nblk, ps, hkv = k.shape[0], k.shape[1], k.shape[2]
+    if hkv == 0 or hq % hkv != 0:
+        raise RuntimeError(f"{who}: the query heads ({hq}) must be a multiple of the K/V heads ({hkv})")
+    if ps < 16 or ps % 16 != 0:
+        raise RuntimeError(f"{who}: page_block_size must be a positive multiple of 16, got {ps}")
+    if block_table.dim() != 2 or block_table.shape[0] != b:
+        raise RuntimeError(f"{who}: block_table must be an int32 (batch, max_blocks_per_seq) tensor, batch = {b}; got "
+                           f"{tuple(block_table.shape)}")
+    mq, mk = operator.index(max_seqlen_q), operator.index(max_seqlen_k)
+    if mq < 0 or mk < 0:
+        raise RuntimeError(f"{who}: max_seqlen_q, max_seqlen_k must be >= 0")
+    sq = _token_stride(who, "q", q, hq, d)
+    kps, kts = _kv_strides(who, "k", k, hkv, d, True)   # (ValueError on a pool view that would need a copy)
+    vps, vts = _kv_strides(who, "v", v, hkv, d, True)
+    cu_q, cu_k, block_table = cu_seqlens_q.contiguous(), cu_seqlens_k.contiguous(), block_table.contiguous()
+    aptr, _h, astride, alibi_slopes = alibi_arg(who, alibi_slopes, q.device, b * hq, heads=hq)
+    sptr, sheads, sinks = sinks_arg(who, sinks, q.device, b * hq, heads=hq)
+    with torch.cuda.device(q.device):
+        o = torch.empty((total_q, hq, d), dtype=q.dtype, device=q.device)
+        lse = torch.empty((hq, total_q), dtype=torch.float32, device=q.device)
+        _check(_lib.fa_ex_forward_varlen_paged(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), cu_q.data_ptr(),
+                                               cu_k.data_ptr(), b, hq, hkv, total_q, 0, mq, mk, d, _DTYPE_CODE[q.dtype], sq, kts, vts,
+                                               int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, astride, sptr, sheads,
+                                               block_table.data_ptr(), block_table.shape[1], nblk, ps, kps, vps,
+                                               _stream_ptr(q.device)))
+    return o, lse
+
+
 def ex_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, dropout_p=0.0, seed=0,
-                      window=(-1, -1), softcap=0.0, alibi_slopes=None, sinks=None):
+                      window=(-1, -1), softcap=0.0, alibi_slopes=None, *, block_table=None, sinks=None):
     """(o, lse) of attention over packed sequences (FlashAttention-2's varlen layout): q (total_q, H_q, d), k and v
     (total_k, H_kv, d) — strided views along the token dim allowed — cu_seqlens_* int32 (batch + 1,) device offsets.  o is
     (total_q, H_q, d), lse (H_q, total_q) float32.  Never synchronises: cu_seqlens are clamped in the kernels.  softcap and
     alibi_slopes (float32 (H_q,) or (batch, H_q)) as in ex_forward, per sequence (fa_ex_forward_varlen_scoremod).  sinks: float32
-    (H_q,), one extra softmax column per query head (fa_ex_forward_varlen_sink)."""
+    (H_q,), one extra softmax column per query head (fa_ex_forward_varlen_sink).
+    block_table (keyword-only, as sinks now is: sinks stays the last parameter) int32 (batch, max_blocks_per_seq): k and v are pools (num_blocks, page_block_size, H_kv, d), page_block_size a
+    multiple of 16, and key t of sequence b lives at pool[block_table[b, t // ps], t % ps]; len_k[b] = cu_seqlens_k[b + 1] -
+    cu_seqlens_k[b], clamped to min(max_seqlen_k, max_blocks_per_seq * ps).  The pools may be strided views (their own page and
+    token strides; a view that would need a copy raises ValueError) and are only read; no dropout.  Each sequence gets the bits
+    of the call on the same tokens gathered into packed k, v.  See fa_ex_forward_varlen_paged."""
     who = "ex_varlen_forward"
     wl, wr = window_arg(who, window)
     cap = softcap_arg(who, softcap)
+    if block_table is not None:
+        return _varlen_paged_forward(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale,
+                                     dropout_p, wl, wr, cap, alibi_slopes, sinks, block_table)
     cu_q, cu_k, *dims = _varlen_common(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
     b, hq, _hkv, total_q, *_ = dims
     d = q.shape[2]

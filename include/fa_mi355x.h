@@ -510,6 +510,39 @@ int fa_ex_backward_varlen_sink(const void* q, const void* k, const void* v, cons
                                const float* alibi_slopes, int64_t alibi_batch_stride, const float* sinks, int64_t sink_heads,
                                float* dsinks, double dropout_p, uint64_t dropout_seed, void* workspace, size_t workspace_bytes,
                                void* stream);
+/* --- The varlen forward over a paged K/V cache: FlashAttention-2's flash_attn_varlen_func(..., block_table=).  Chunked prefill, or
+ * prefill behind a shared prefix, reads its keys straight from the pools of the KV-cache calls, without a gathered copy and on the
+ * kernel that reads a sequence's keys once per 256 query rows.  Forward only, no dropout.  The arguments are those of
+ * fa_ex_forward_varlen_sink without dropout_p / dropout_seed, plus the table; q, o, lse, cu_seqlens_q, the masks (causal per
+ * sequence, bottom-right aligned; window), GQA, softcap, alibi_slopes and sinks (all three may be 0 / NULL) keep their meaning.
+ *   k, v: pools (num_blocks, page_block_size, heads_kv, d) in q's dtype.  k_stride / v_stride are the token strides inside a page,
+ *     k_page_stride / v_page_stride the page strides (elements): a view of a larger allocation is fine, K and V may differ.
+ *   block_table: int32 (batch, max_blocks_per_seq), contiguous, device memory.  Key t of sequence b is at element offset
+ *     block_table[b, t / ps] * page_stride + (t % ps) * token_stride + head * d + i.
+ *   len_k[b] = cu_seqlens_k[b + 1] - cu_seqlens_k[b], clamped in the kernels to [0, min(max_seqlen_k, max_blocks_per_seq * ps)]:
+ *     only the differences of cu_seqlens_k mean anything for a pool, and total_k is not used (pass anything).  cu_seqlens_q is
+ *     clamped as in fa_ex_forward_varlen.  Nothing is read on the host: no synchronisation, and a captured call may be replayed
+ *     with a changed table and changed offsets.
+ *   The table is untrusted: an entry outside [0, num_blocks) never leads to an access outside the pools — the keys of that page
+ *     read as zero K and zero V (they still take part in the softmax, with score 0).  Only entries j < ceil(len_k[b] / ps) of row b
+ *     are read.  Page offsets are 64-bit (a pool may be larger than 4 GiB), offsets inside a page 32-bit.  Sequences may name the
+ *     same pages (prefix sharing).  The pools are only read.
+ * Each sequence gets the bits of fa_ex_forward_varlen* on the same tokens gathered into packed k and v (same max_seqlen_q,
+ * max_seqlen_k), o and lse alike: the kernels differ only in where a K/V tile's rows come from.
+ * Kernels: 16-bit MFMA for f16 / bf16, d % 8 == 0, d <= 128, every stride a multiple of 8 elements and q, k, v, o 16-byte
+ * aligned; exact f32 otherwise (d <= 256).
+ * Checked before any HIP call (FA_ERR_INVALID_ARGUMENT), besides fa_ex_forward_varlen_sink's list: block_table null or not 4-byte
+ * aligned; page_block_size not a positive multiple of 16; num_blocks or max_blocks_per_seq negative; token strides below
+ * heads_kv * d; with num_blocks > 1 a page stride below (ps - 1) * token stride + heads_kv * d.  FA_ERR_UNSUPPORTED: a page above
+ * 65536 tokens or spanning 2^31 bytes or more. */
+int fa_ex_forward_varlen_paged(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
+                               const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
+                               int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
+                               int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
+                               double softmax_scale, double softcap, const float* alibi_slopes, int64_t alibi_batch_stride,
+                               const float* sinks, int64_t sink_heads, const int32_t* block_table, int64_t max_blocks_per_seq,
+                               int64_t num_blocks, int64_t page_block_size, int64_t k_page_stride, int64_t v_page_stride,
+                               void* stream);
 /* Decoding: the sink joins when the per-split partials are combined,
  *     m = max(max_s lse_s, sink)   denom = sum_s exp(lse_s - m) + exp(sink - m)   o = sum_s exp(lse_s - m) O_s / denom
  *     lse = m + log(denom)

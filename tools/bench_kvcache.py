@@ -26,6 +26,15 @@ and V are then 1 an element.  ex_forward and the unfused rotation keep the 16-bi
             padded calls that serve the same step (63 x 1 token, 1 x n tokens), with the share of the packed grid's waves that
             leave empty, 1 - sum_b ceil(nq_b G / 16) / (B ceil(max_seqlen_q G / 16)); and the chunk alone through
             ex_varlen_forward on its gathered keys (the gather timed apart), the call that overtakes this path on long chunks.
+--prefill: one prefill chunk of n new tokens (--prefill-chunks, default 16, 64, 128, 512, 2048) against a paged cache (page 16) of
+  8k and 32k tokens (--prefill-lens), H_q = 32, H_kv = 8 (G = 4), causal, the chunk's own keys being the cache's last n, three ways:
+  (a) decode_us        : the packed decode call (ex_kvcache_forward with cu_seqlens_q), which re-reads the keys ceil(n G / 16) times,
+  (b) paged_varlen_us  : ex_varlen_forward(..., block_table=), the prefill kernel reading the pool through the table,
+  (c) gather_varlen_us : the pages gathered into packed k, v by torch indexing, then ex_varlen_forward (the gather alone: gather_us).
+  The three are timed in turn, --rounds times over, so that clock and cache state drift hits all alike; each figure is the median
+  of the rounds (each round itself the median of --reps groups).  (b) is checked to be bitwise (c) before anything is timed.
+  --parent-check: only the packed ex_varlen_forward without a table at B H = 64, 4096 tokens, d = 128 (B = 2 sequences of 4096,
+  32 heads, causal): the figure to compare between two checkouts, with the spread of its rounds.
 Timing: HIP events around `--iters` back-to-back calls after `--warmup` calls; the median of `--reps` such groups."""
 import argparse
 import json
@@ -229,6 +238,63 @@ def varlen_rows(args, dtype):
     return rows
 
 
+def prefill_rows(args, dtype):
+    dev, hq, hkv, d, ps = "cuda", 32, 8, args.d, 16
+    rows = []
+    t = lambda fn: timed(fn, args.warmup, args.iters, args.reps)   # noqa: E731
+    i32 = lambda x: torch.tensor(x, dtype=torch.int32, device=dev)   # noqa: E731
+    for cap in args.prefill_lens:
+        mb = cap // ps
+        nblk = mb + 64
+        table = torch.randperm(nblk, generator=torch.Generator().manual_seed(cap))[:mb].view(1, mb).to(torch.int32).to(dev)
+        kp = torch.randn((nblk, ps, hkv, d), device=dev, dtype=dtype)
+        vp = torch.randn((nblk, ps, hkv, d), device=dev, dtype=dtype)
+        sl = i32([cap])
+        for n in args.prefill_chunks:
+            q = torch.randn((n, hq, d), device=dev, dtype=dtype)
+            cq, ck = i32([0, n]), i32([0, cap])
+            decode = lambda: ext.ex_kvcache_forward(q, kp, vp, None, None, sl, True, None, block_table=table, cu_seqlens_q=cq,   # noqa: E731
+                                                    max_seqlen_q=n)
+            paged = lambda: ext.ex_varlen_forward(q, kp, vp, cq, ck, n, cap, True, d ** -0.5, block_table=table)   # noqa: E731
+            gather = lambda: (kp[table[0].long()].view(cap, hkv, d), vp[table[0].long()].view(cap, hkv, d))   # noqa: E731
+
+            def gathered():
+                kg, vg = gather()
+                return ext.ex_varlen_forward(q, kg, vg, cq, ck, n, cap, True, d ** -0.5)
+
+            ob, oc = paged(), gathered()
+            assert torch.equal(ob[0], oc[0]) and torch.equal(ob[1], oc[1]), "the paged call and the gathered call disagree"
+            torch.testing.assert_close(decode()[0].float(), ob[0].float(), rtol=2e-2, atol=2e-2)
+            ta, tb, tc, tg = [], [], [], []
+            for _ in range(args.rounds):
+                ta.append(t(decode))
+                tb.append(t(paged))
+                tc.append(t(gathered))
+                tg.append(t(gather))
+            med = statistics.median
+            r = dict(kind="prefill", len=cap, chunk=n, decode_us=round(med(ta), 2), paged_varlen_us=round(med(tb), 2),
+                     gather_varlen_us=round(med(tc), 2), gather_us=round(med(tg), 2), decode_reads=(n * (hq // hkv) + 15) // 16,
+                     varlen_reads=(n + 255) // 256, paged_vs_decode=round(med(tb) / med(ta), 3),
+                     paged_vs_gathered=round(med(tb) / med(tc), 3), rounds=dict(decode=[round(x, 2) for x in ta], paged=[round(x, 2) for x in tb],
+                                                                             gathered=[round(x, 2) for x in tc]))
+            rows.append(r)
+            print(json.dumps(r), flush=True)
+        del kp, vp
+    return rows
+
+
+def parent_check(args, dtype):
+    dev, b, h, n, d = "cuda", 2, 32, 4096, 128
+    q, k, v = (torch.randn((b * n, h, d), device=dev, dtype=dtype) for _ in range(3))
+    cu = torch.tensor([0, n, 2 * n], dtype=torch.int32, device=dev)
+    fn = lambda: ext.ex_varlen_forward(q, k, v, cu, cu, n, n, True, d ** -0.5)   # noqa: E731
+    ts = [timed(fn, args.warmup, args.iters, args.reps) for _ in range(max(args.rounds, 5))]
+    r = dict(kind="parent_check", BH=b * h, n=n, d=d, varlen_fwd_us=round(statistics.median(ts), 2), rounds=[round(x, 2) for x in ts],
+             spread=round((max(ts) - min(ts)) / statistics.median(ts), 4), version=ext.version())
+    print(json.dumps(r), flush=True)
+    return [r]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--d", type=int, default=128)
@@ -247,9 +313,16 @@ def main():
     ap.add_argument("--lens", default="1024,8192,32768,131072", help="the grid's cache lengths")
     ap.add_argument("--varlen", action="store_true", help="time the packed call (cu_seqlens_q) instead of the grid: see the module docstring")
     ap.add_argument("--chunks", default="16,32,64,128,256,512", help="--varlen: the chunk lengths of the mixed step")
+    ap.add_argument("--prefill", action="store_true", help="time one prefill chunk against a paged cache three ways: see the module docstring")
+    ap.add_argument("--prefill-chunks", default="16,64,128,512,2048")
+    ap.add_argument("--prefill-lens", default="8192,32768")
+    ap.add_argument("--rounds", type=int, default=3, help="--prefill / --parent-check: interleaved rounds per figure")
+    ap.add_argument("--parent-check", action="store_true", help="time only the packed varlen forward at B H = 64, 4096 tokens, d = 128")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     args.chunks = [int(x) for x in args.chunks.split(",")]
+    args.prefill_chunks = [int(x) for x in args.prefill_chunks.split(",")]
+    args.prefill_lens = [int(x) for x in args.prefill_lens.split(",")]
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16
     # bring the clocks up before the first row (a second of large decode steps)
     wq = torch.randn((8, 1, 32, args.d), device="cuda", dtype=dtype)
@@ -259,6 +332,12 @@ def main():
         ext.ex_kvcache_forward(wq, wk, wk, None, None, wl, True, None)
     torch.cuda.synchronize()
     del wq, wk
+    if args.prefill or args.parent_check:
+        rows = parent_check(args, dtype) if args.parent_check else prefill_rows(args, dtype)
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(dict(d=args.d, dtype=args.dtype, prefill=True, rows=rows), f, indent=1)
+        return
     if args.varlen:
         rows = varlen_rows(args, dtype)
         if args.json:
