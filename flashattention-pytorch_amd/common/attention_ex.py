@@ -213,7 +213,7 @@ class _FlashAttnVarlenFn(torch.autograd.Function):
 
 def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p=0.0, softmax_scale=None,
                            causal=False, window_size=(-1, -1), seed=0, softcap=0.0, alibi_slopes=None, *,
-                           block_table=None, sinks=None):
+                           block_table=None, k_descale=None, v_descale=None, sinks=None):
     """FlashAttention-2's flash_attn_varlen_func over packed sequences, differentiable: q (total_q, H_q, d), k and v
     (total_k, H_kv, d) with H_q % H_kv == 0 (GQA), token-strided views (qkv.unbind(1) of a (total, 3, H, d) projection) taken
     without a copy; cu_seqlens_* int32 (batch + 1,) device offsets.  Attention stays inside each sequence; `causal` is
@@ -237,11 +237,21 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
     sinks, a token-strided q and empty sequences work as without the table, and each sequence gets the bits of this function on
     the same tokens gathered into packed k, v.  Forward only: dropout_p > 0 raises ValueError, and q, k or v requiring grad
     under grad mode raises RuntimeError (no paged backward, as in FlashAttention-2).  A block_table that is not an int32
-    tensor raises NotImplementedError."""
+    tensor raises NotImplementedError.
+    k_descale, v_descale (keyword-only, with block_table): the pools may both be torch.float8_e4m3fn (OCP e4m3), the cache that
+    flash_attn_with_kvcache appends to and decodes from, while q and o stay float16 / bfloat16.  A stored byte c of K head h of
+    sequence b (of this call, not of the page) stands for e4m3(c) * k_descale[b, h], for V with v_descale: float32 (batch, H_kv) or
+    (H_kv,) on the device, read by the kernels only, None = 1.0 — the same sentences as the decode call's, so one cache serves
+    append, decode and prefill.  Widening e4m3 to q's dtype is exact and the 16-bit kernel is kept: the score is softmax_scale *
+    k_descale * (q . k_stored), scaled before softcap and ALiBi, v_descale multiplies the normalised output once in fp32, and
+    everything above about the table, the views, the lengths and graph replay (changed scale values included) holds unchanged.
+    Give both scales in the same form: with one (H_kv,) and one (batch, H_kv) the former is first copied into (batch, H_kv) rows,
+    one more small kernel per call.  Other float8 dtypes raise NotImplementedError; scales without e4m3 pools, and e4m3 pools without block_table, RuntimeError."""
     window = _window_size(window_size)
     if block_table is not None:
         return _flash_attention_varlen_paged(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale,
-                                             causal, window, softcap, alibi_slopes, sinks, block_table)
+                                             causal, window, softcap, alibi_slopes, sinks, block_table, k_descale, v_descale)
+    _no_fp8_without_table("flash_attention_varlen", k, v, k_descale, v_descale)
     if not q.is_cuda:
         raise RuntimeError("Inputs must be CUDA tensors")
     scale = (1.0 / math.sqrt(q.shape[-1])) if softmax_scale is None else float(softmax_scale)
@@ -257,7 +267,7 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
 
 
 def _flash_attention_varlen_paged(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale, causal,
-                                  window, softcap, alibi_slopes, sinks, block_table):
+                                  window, softcap, alibi_slopes, sinks, block_table, k_descale=None, v_descale=None):
     """flash_attention_varlen with a block_table: forward only, nothing differentiable"""
     who = "flash_attention_varlen"
     if not (isinstance(block_table, torch.Tensor) and block_table.dtype == torch.int32):
@@ -280,8 +290,21 @@ def _flash_attention_varlen_paged(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqle
     with torch.no_grad():
         o, _lse = ext.ex_varlen_forward(q.detach(), k.detach(), v.detach(), cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q),
                                         int(max_seqlen_k), bool(causal), scale, 0.0, 0, window=window, softcap=softcap,
-                                        alibi_slopes=alibi_slopes, sinks=sinks, block_table=block_table)
+                                        alibi_slopes=alibi_slopes, sinks=sinks, block_table=block_table, k_descale=k_descale,
+                                        v_descale=v_descale)
     return o
+
+
+def _no_fp8_without_table(who, k, v, k_descale, v_descale):
+    """the packed (non-paged) call has no 8-bit K/V: float8 tensors and scales are refused before anything runs"""
+    f8 = tuple(getattr(torch, n) for n in ("float8_e4m3fn", "float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz") if hasattr(torch, n))
+    for name, t in (("k", k), ("v", v)):
+        if isinstance(t, torch.Tensor) and t.dtype in f8:
+            if t.dtype != torch.float8_e4m3fn:
+                raise NotImplementedError(f"{who}: {name} of dtype {t.dtype} is not supported (an 8-bit cache is torch.float8_e4m3fn)")
+            raise RuntimeError(f"{who}: torch.float8_e4m3fn k, v are pools of a paged cache and need block_table")
+    if k_descale is not None or v_descale is not None:
+        raise RuntimeError(f"{who}: k_descale / v_descale need torch.float8_e4m3fn pools and block_table")
 
 
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_sin=None, cache_seqlens=None,

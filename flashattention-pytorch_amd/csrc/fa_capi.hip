@@ -848,16 +848,43 @@ int fa_ex_backward_varlen_sink(const void* q, const void* k, const void* v, cons
 }
 
 // ---- the varlen forward over a paged K/V cache: see include/fa_mi355x.h
-int fa_ex_forward_varlen_paged(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
-                               const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
-                               int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
-                               int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
-                               double softmax_scale, double softcap, const float* alibi_slopes, int64_t alibi_batch_stride,
-                               const float* sinks, int64_t sink_heads, const int32_t* block_table, int64_t max_blocks_per_seq,
-                               int64_t num_blocks, int64_t page_block_size, int64_t k_page_stride, int64_t v_page_stride,
-                               void* stream) {
-    const char* who = "fa_ex_forward_varlen_paged";
+// One body under both entry points: the last four parameters are the ones fa_ex_forward_varlen_paged_fp8 adds (cache_dtype = dtype,
+// null, null, 0 is fa_ex_forward_varlen_paged: none of the e4m3 checks below can fire and the launch is the one it was).
+static int varlen_paged_impl(const char* who, const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
+                             const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
+                             int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
+                             int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
+                             double softmax_scale, double softcap, const float* alibi_slopes, int64_t alibi_batch_stride,
+                             const float* sinks, int64_t sink_heads, const int32_t* block_table, int64_t max_blocks_per_seq,
+                             int64_t num_blocks, int64_t page_block_size, int64_t k_page_stride, int64_t v_page_stride,
+                             void* stream, int cache_dtype, const float* k_descale, const float* v_descale,
+                             int64_t descale_batch_stride) {
     (void)total_k;   // a pool has no token count: the keys of a sequence are found through the table
+    // the pool's element type: q's, or e4m3 with a dequantisation scale per (sequence, K/V head): the checks of fa_ex_forward_kvcache_fp8
+    const bool e4m3 = cache_dtype == FA_DTYPE_E4M3;
+    if (cache_dtype != dtype && !e4m3)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_dtype must be dtype (code %d) or FA_DTYPE_E4M3 (got code %d)", who, dtype,
+                    cache_dtype);
+    if (e4m3 && dtype != FA_DTYPE_F16 && dtype != FA_DTYPE_BF16)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: dtype must be f16 or bf16 with an e4m3 pool (got code %d)", who, dtype);
+    if (!e4m3 && (k_descale || v_descale))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_descale / v_descale need an e4m3 pool (cache_dtype is code %d)", who, cache_dtype);
+    if (!e4m3 && descale_batch_stride != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: descale_batch_stride must be 0 with a 16-bit pool (got %lld)", who,
+                    (long long)descale_batch_stride);
+    if (descale_batch_stride < 0 || (descale_batch_stride != 0 && (descale_batch_stride < heads_kv || descale_batch_stride > ((int64_t)1 << 40))))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: descale_batch_stride=%lld must be 0 or >= heads_kv=%lld (and <= 2^40)", who,
+                    (long long)descale_batch_stride, (long long)heads_kv);
+    if ((uintptr_t)k_descale % 4 != 0 || (uintptr_t)v_descale % 4 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_descale and v_descale must be 4-byte aligned", who);
+    if (e4m3) {   // an 8-element chunk of an e4m3 pool is 8 bytes: loads of 4 and 8 bytes
+        if (d < 8 || d % 8 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: head_dim must be a multiple of 8 with an e4m3 pool (got %lld)", who, (long long)d);
+        if ((uintptr_t)k % 8 != 0 || (uintptr_t)v % 8 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: an e4m3 k / v pool must be 8-byte aligned", who);
+        if (k_stride % 8 != 0 || v_stride % 8 != 0 || k_page_stride % 8 != 0 || v_page_stride % 8 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of an e4m3 pool must be multiples of 8 elements", who);
+    }
     ScoreMod sm;
     sm.softcap = softcap; sm.alibi = alibi_slopes; sm.heads = heads_q; sm.bstride = alibi_batch_stride;
     SinkArg sk;
@@ -884,7 +911,7 @@ int fa_ex_forward_varlen_paged(const void* q, const void* k, const void* v, void
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: page strides must be >= 0", who);
     if ((rc = score_check(who, sm, batch * heads_q)) != FA_OK) return rc;
     if ((rc = sink_check(who, sk, heads_q, false)) != FA_OK) return rc;
-    if (page_block_size > 65536 || page_span * (dtype == FA_DTYPE_F32 ? 4 : 2) >= ((int64_t)1 << 31) || num_blocks >= ((int64_t)1 << 31) ||
+    if (page_block_size > 65536 || page_span * (e4m3 ? 1 : dtype == FA_DTYPE_F32 ? 4 : 2) >= ((int64_t)1 << 31) || num_blocks >= ((int64_t)1 << 31) ||
         max_blocks_per_seq >= ((int64_t)1 << 31) || batch * max_blocks_per_seq >= ((int64_t)1 << 40))
         return fail(FA_ERR_UNSUPPORTED, "%s: a page above 65536 tokens or 2^31 bytes, or a table too large", who);
     // the window against the same (max_seqlen_q, max_seqlen_k) as the packed call on the gathered tokens
@@ -912,9 +939,40 @@ int fa_ex_forward_varlen_paged(const void* q, const void* k, const void* v, void
     a.page_size = page_block_size;
     a.page_stride_k = k_page_stride;
     a.page_stride_v = v_page_stride;
+    a.kv_e4m3 = e4m3 ? 1 : 0; a.k_descale = k_descale; a.v_descale = v_descale; a.descale_bstride = descale_batch_stride;
     hipError_t e = fa::launch_ex(a, false, st);
     if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
     return FA_OK;
+}
+
+int fa_ex_forward_varlen_paged(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
+                               const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
+                               int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
+                               int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
+                               double softmax_scale, double softcap, const float* alibi_slopes, int64_t alibi_batch_stride,
+                               const float* sinks, int64_t sink_heads, const int32_t* block_table, int64_t max_blocks_per_seq,
+                               int64_t num_blocks, int64_t page_block_size, int64_t k_page_stride, int64_t v_page_stride,
+                               void* stream) {
+    return varlen_paged_impl("fa_ex_forward_varlen_paged", q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q,
+                             total_k, max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride, causal, window_left, window_right,
+                             softmax_scale, softcap, alibi_slopes, alibi_batch_stride, sinks, sink_heads, block_table, max_blocks_per_seq,
+                             num_blocks, page_block_size, k_page_stride, v_page_stride, stream, dtype, nullptr, nullptr, 0);
+}
+
+int fa_ex_forward_varlen_paged_fp8(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
+                                   const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
+                                   int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
+                                   int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
+                                   double softmax_scale, double softcap, const float* alibi_slopes, int64_t alibi_batch_stride,
+                                   const float* sinks, int64_t sink_heads, const int32_t* block_table, int64_t max_blocks_per_seq,
+                                   int64_t num_blocks, int64_t page_block_size, int64_t k_page_stride, int64_t v_page_stride,
+                                   int cache_dtype, const float* k_descale, const float* v_descale, int64_t descale_batch_stride,
+                                   void* stream) {
+    return varlen_paged_impl("fa_ex_forward_varlen_paged_fp8", q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv,
+                             total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride, causal, window_left,
+                             window_right, softmax_scale, softcap, alibi_slopes, alibi_batch_stride, sinks, sink_heads, block_table,
+                             max_blocks_per_seq, num_blocks, page_block_size, k_page_stride, v_page_stride, stream, cache_dtype, k_descale,
+                             v_descale, descale_batch_stride);
 }
 
 // ---- KV-cache decoding with split-KV: see include/fa_mi355x.h

@@ -191,28 +191,7 @@ struct KvQ8 {
     long long bs;
 };
 
-// 8 e4m3 bytes -> 8 values of q's 16-bit dtype, exact (every finite e4m3 value is a normal f16 and bf16 number): one
-// v_cvt_scalef32_pk_{f16,bf16}_fp8 at scale 1.0 per pair, element order kept
-template <typename Tag> __device__ __forceinline__ u32x4 kv_q8_widen(u32x2 c);
-template <> __device__ __forceinline__ u32x4 kv_q8_widen<f16_tag>(u32x2 c) {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    u32x4 out;
-    out[0] = __builtin_bit_cast(uint32_t, (h2)__builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c[0], 1.0f, false));
-    out[1] = __builtin_bit_cast(uint32_t, (h2)__builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c[0], 1.0f, true));
-    out[2] = __builtin_bit_cast(uint32_t, (h2)__builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c[1], 1.0f, false));
-    out[3] = __builtin_bit_cast(uint32_t, (h2)__builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c[1], 1.0f, true));
-    return out;
-}
-template <> __device__ __forceinline__ u32x4 kv_q8_widen<bf16_tag>(u32x2 c) {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    u32x4 out;
-    out[0] = __builtin_bit_cast(uint32_t, (b2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[0], 1.0f, false));
-    out[1] = __builtin_bit_cast(uint32_t, (b2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[0], 1.0f, true));
-    out[2] = __builtin_bit_cast(uint32_t, (b2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[1], 1.0f, false));
-    out[3] = __builtin_bit_cast(uint32_t, (b2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[1], 1.0f, true));
-    return out;
-}
-
+// (kv_q8_widen, 8 e4m3 bytes -> 8 values of q's 16-bit dtype: fa_ex_common.h, shared with the paged varlen forward)
 // 8 values of q's 16-bit dtype -> 8 e4m3 bytes: y = clamp(float(x) * inv, -448, 448) in fp32, then round to nearest even
 // (v_cvt_pk_fp8_f32; after the clamp its saturation mode cannot matter, and a finite x never gives the NaN code)
 template <typename Tag> __device__ __forceinline__ u32x2 kv_q8_quant(u32x4 x, float inv) {

@@ -102,6 +102,39 @@ __device__ __forceinline__ void ex_load_tile_paged(float* __restrict__ dst, cons
         dst[r * LD + c] = x;
     }
 }
+// The same from an e4m3 pool (ExKv8; fa_ex_forward_varlen_paged_fp8): src addresses bytes, pstride and ld are bytes, and a byte
+// widens exactly to f32 (v_cvt_f32_fp8).  The scales are not applied here: they are two fp32 multiplies in the body.
+template <int DP, int LD, int NTHREADS>
+__device__ __forceinline__ void ex_load_tile_paged_q8(float* __restrict__ dst, const uint8_t* __restrict__ src, const ExPage& pg,
+                                                      const int* __restrict__ trow, long long pstride, int r0, int rows, int n, int d,
+                                                      bool vec, int ld) {
+    if (vec) {   // (d % 4 == 0, the pool and its strides multiples of 4 bytes: one dword = four elements)
+        for (int idx = threadIdx.x; idx < rows * (DP / 4); idx += NTHREADS) {
+            const int r = idx / (DP / 4), c = 4 * (idx - r * (DP / 4));
+            f32x4 x = {0.f, 0.f, 0.f, 0.f};
+            if (r0 + r < n && c < d) {
+                const int slot = pg_slot(pg, r0 + r), page = trow[slot];
+                if ((unsigned)page < (unsigned)pg.num_blocks) {
+                    const int u = *reinterpret_cast<const int*>(src + (size_t)page * (size_t)pstride + (size_t)(r0 + r - slot * pg.ps) * ld + c);
+                    x = f32x4{__builtin_amdgcn_cvt_f32_fp8(u, 0), __builtin_amdgcn_cvt_f32_fp8(u, 1), __builtin_amdgcn_cvt_f32_fp8(u, 2),
+                              __builtin_amdgcn_cvt_f32_fp8(u, 3)};
+                }
+            }
+            *reinterpret_cast<f32x4*>(dst + r * LD + c) = x;
+        }
+        return;
+    }
+    for (int idx = threadIdx.x; idx < rows * DP; idx += NTHREADS) {
+        const int r = idx / DP, c = idx - r * DP;
+        float x = 0.f;
+        if (r0 + r < n && c < d) {
+            const int slot = pg_slot(pg, r0 + r), page = trow[slot];
+            if ((unsigned)page < (unsigned)pg.num_blocks)
+                x = __builtin_amdgcn_cvt_f32_fp8((int)src[(size_t)page * (size_t)pstride + (size_t)(r0 + r - slot * pg.ps) * ld + c], 0);
+        }
+        dst[r * LD + c] = x;
+    }
+}
 // score modifiers of one element in the exact kernels' domain (ExScore; x = scale q.k, dist = i + coff - j); dt = 1 - t^2, the
 // softcap's derivative (1 without one).  The forward and both backward bodies evaluate it with these same operations.
 __device__ __forceinline__ float ex_score_mod(const ExScore& sc, float slope, float x, int dist, float& dt) {
@@ -118,6 +151,9 @@ template <typename P> constexpr bool ex_has_score() { return std::is_base_of<ExP
 template <typename P> constexpr bool ex_has_sink() { return std::is_base_of<ExParamsK, P>::value; }
 template <typename P> struct ex_is_paged : std::false_type {};
 template <typename B> struct ex_is_paged<ExParamsPg<B>> : std::true_type {};
+template <typename B> struct ex_is_paged<ExParamsPg8<B>> : std::true_type {};
+template <typename P> struct ex_is_kv8 : std::false_type {};   // (paged, from an e4m3 pool)
+template <typename B> struct ex_is_kv8<ExParamsPg8<B>> : std::true_type {};
 
 template <typename T> __device__ __forceinline__ bool ex_quad_ok(int d, const void* a, const void* b, const void* c, const void* e) {
     return d % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
@@ -137,7 +173,7 @@ template <typename T> __device__ __forceinline__ bool ex_quad_ok(int d, const vo
 template <typename T, int DP, int NW, bool WIN, bool VAR, typename P>
 __device__ __forceinline__ void ex_fwd_body(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, T* __restrict__ o,
                                             float* __restrict__ lse, P& p) {
-    constexpr bool SC = ex_has_score<P>(), SNK = ex_has_sink<P>(), PG = ex_is_paged<P>::value;
+    constexpr bool SC = ex_has_score<P>(), SNK = ex_has_sink<P>(), PG = ex_is_paged<P>::value, Q8 = ex_is_kv8<P>::value;
     static_assert(!PG || VAR, "the paged entries are varlen entries");
     constexpr int LD = DP + 4, BM = 16 * NW, BN = 32, NT = DP / 16, PLD = BN + 4, NTH = NW * 64;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -165,6 +201,11 @@ __device__ __forceinline__ void ex_fwd_body(const T* __restrict__ q, const T* __
         p.nq = lq; p.nk = lk; p.coff = lk - lq;
         if (q0 >= p.nq) return;
     }
+    [[maybe_unused]] float vdsc = 1.0f;
+    if constexpr (Q8) {   // the scales of (sequence, K/V head): the score is scale * k_descale * (q . k_stored), before softcap and ALiBi
+        p.scale *= kv8_scale(p.q8.kd, p.q8.bs, bh / p.hq, hk);
+        vdsc = kv8_scale(p.q8.vd, p.q8.bs, bh / p.hq, hk);
+    }
     const size_t qbase = VAR ? (size_t)sq0 * p.sq + (size_t)hh * p.d : (size_t)bh * p.nq * p.d;
     const size_t kbase = VAR ? (size_t)sk0 * p.sk + (size_t)hk * p.d : (size_t)kv_unit(bh, p.kvg) * p.nk * p.d;
     const size_t vbase = VAR ? (size_t)sk0 * p.sv + (size_t)hk * p.d : kbase;
@@ -176,6 +217,9 @@ __device__ __forceinline__ void ex_fwd_body(const T* __restrict__ q, const T* __
 
     bool vec = ex_quad_ok<T>(p.d, q, k, v, q) && (!VAR || (p.sq | p.sk | p.sv) % 4 == 0);
     if constexpr (PG) vec = vec && (p.pg.kps | p.pg.vps) % 4 == 0;
+    [[maybe_unused]] bool vec8 = false;   // e4m3 pools: dwords of four bytes
+    if constexpr (Q8) vec8 = p.d % 4 == 0 && ((reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v)) % 4) == 0 &&
+                             (p.sk | p.sv) % 4 == 0 && (p.pg.kps | p.pg.vps) % 4 == 0;
     ex_load_tile<T, DP, LD, NTH, VAR>(Qs, q + qbase, q0, BM, p.nq, p.d, vec, VAR ? p.sq : 0);
     f32x4 acc[NT];
 #pragma unroll
@@ -195,7 +239,10 @@ __device__ __forceinline__ void ex_fwd_body(const T* __restrict__ q, const T* __
     for (int k0 = kstart; k0 < kend; k0 += BN) {
         if (!VAR && !ex_tile_live(p, q0, min(q0 + BM, p.nq), k0, min(k0 + BN, p.nk))) continue;   // block-sparse skip (uniform)
         __syncthreads();
-        if constexpr (PG) {
+        if constexpr (Q8) {
+            ex_load_tile_paged_q8<DP, LD, NTH>(Ks, reinterpret_cast<const uint8_t*>(k) + kbase, p.pg, pg_row, p.pg.kps, k0, BN, p.nk, p.d, vec8, p.sk);
+            ex_load_tile_paged_q8<DP, LD, NTH>(Vs, reinterpret_cast<const uint8_t*>(v) + vbase, p.pg, pg_row, p.pg.vps, k0, BN, p.nk, p.d, vec8, p.sv);
+        } else if constexpr (PG) {
             ex_load_tile_paged<T, DP, LD, NTH>(Ks, k + kbase, p.pg, pg_row, p.pg.kps, k0, BN, p.nk, p.d, vec, p.sk);
             ex_load_tile_paged<T, DP, LD, NTH>(Vs, v + vbase, p.pg, pg_row, p.pg.vps, k0, BN, p.nk, p.d, vec, p.sv);
         } else {
@@ -272,10 +319,15 @@ __device__ __forceinline__ void ex_fwd_body(const T* __restrict__ q, const T* __
                 lse_k = l[i] > 0.f ? m[i] + logf(l[i]) : -INFINITY;
                 if (snk != -INFINITY) ex_sink_norm(m[i], l[i], snk, inv, lse_k);
             }
+            [[maybe_unused]] const float invv = inv * vdsc;
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 const int c = 16 * t + lr;
-                if (c < p.d) o[obase + (size_t)row * ostr + c] = from_f32<T>(acc[t][i] * inv);
+                if constexpr (Q8) {   // v_descale joins the normaliser (above): one fp32 product in front of the single rounding
+                    if (c < p.d) o[obase + (size_t)row * ostr + c] = from_f32<T>(acc[t][i] * invv);
+                } else {
+                    if (c < p.d) o[obase + (size_t)row * ostr + c] = from_f32<T>(acc[t][i] * inv);
+                }
             }
             if constexpr (SNK) {
                 if (lr == 0) lse[lbase + row] = lse_k;
@@ -878,13 +930,15 @@ static hipError_t launch_ex_one(const ExArgs& a, bool backward, hipStream_t st) 
     }
 }
 
-// The paged varlen forward (a.block_table != null) on the exact kernels
-template <typename T, int DP, bool WIN, bool SC, bool SK>
+// The paged varlen forward (a.block_table != null) on the exact kernels (Q8: from an e4m3 pool, a.kv_e4m3)
+template <typename T, int DP, bool WIN, bool SC, bool SK, bool Q8 = false>
 static hipError_t ex_paged_fwd_t(const ExArgs& a, hipStream_t st) {
     constexpr int NW = 4, LD = DP + 4;
-    ExParamsPg<decltype(ex_params<SC, SK>(a))> p;
-    static_cast<decltype(ex_params<SC, SK>(a))&>(p) = ex_params<SC, SK>(a);
+    using B = decltype(ex_params<SC, SK>(a));
+    typename std::conditional<Q8, ExParamsPg8<B>, ExParamsPg<B>>::type p;
+    static_cast<B&>(p) = ex_params<SC, SK>(a);
     p.pg = make_ex_page(a);
+    if constexpr (Q8) p.q8 = make_ex_kv8(a);
     const size_t smem = sizeof(float) * ((16 * NW + 64) * LD + NW * 16 * 36);
     auto kern = ex_fwd_varlen_paged_kernel<T, DP, NW, WIN, decltype(p)>;
     hipError_t e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
@@ -896,6 +950,15 @@ static hipError_t ex_paged_fwd_t(const ExArgs& a, hipStream_t st) {
 }
 template <typename T, bool WIN, bool SC, bool SK>
 static hipError_t ex_paged_by_d(const ExArgs& a, hipStream_t st) {
+    if (a.kv_e4m3) {
+        if constexpr (sizeof(T) == 2) {
+            if (a.d <= 64) return ex_paged_fwd_t<T, 64, WIN, SC, SK, true>(a, st);
+            if (a.d <= 128) return ex_paged_fwd_t<T, 128, WIN, SC, SK, true>(a, st);
+            return ex_paged_fwd_t<T, 256, WIN, SC, SK, true>(a, st);
+        } else {
+            return hipErrorInvalidValue;   // (the C layer takes an e4m3 pool with f16 / bf16 queries only)
+        }
+    }
     if (a.d <= 64) return ex_paged_fwd_t<T, 64, WIN, SC, SK>(a, st);
     if (a.d <= 128) return ex_paged_fwd_t<T, 128, WIN, SC, SK>(a, st);
     return ex_paged_fwd_t<T, 256, WIN, SC, SK>(a, st);
@@ -909,7 +972,11 @@ static hipError_t ex_paged(const ExArgs& a, hipStream_t st) {
 }
 static hipError_t launch_ex_varlen_paged(const ExArgs& a, hipStream_t st) {
     const int path = option(OPT_EX_PATH);
-    if (path != 1 && ex_mfma_paged_supported(a)) return launch_ex_mfma_varlen_paged(a, st);
+    if (a.kv_e4m3) {
+        if (path != 1 && ex_mfma_paged_kv8_supported(a)) return launch_ex_mfma_varlen_paged_kv8(a, st);
+    } else if (path != 1 && ex_mfma_paged_supported(a)) {
+        return launch_ex_mfma_varlen_paged(a, st);
+    }
     if (path >= 2) return hipErrorInvalidConfiguration;
     switch (a.dtype) {
         case 0: return ex_paged<float>(a, st);

@@ -97,6 +97,42 @@ template <typename B> struct ExParamsPg : B {
     ExPage pg;
 };
 static_assert(sizeof(ExPage) == 40 && sizeof(ExParamsPg<ExParamsK>) == sizeof(ExParamsK) + sizeof(ExPage), "ExParamsPg layout: ExPage after every other field");
+// An e4m3 pool under the paged varlen forward (fa_ex_forward_varlen_paged_fp8; the kernels of fa_ex_mfma_kv8.hip and the
+// ex_fwd_varlen_paged_kernel instantiations of fa_ex.hip with this block): k and v address bytes, sk / sv / kps / vps are in
+// bytes, and a stored byte c of K head hk of sequence b stands for e4m3(c) * kd[b * bs + hk] (V: vd), null = 1.0.  One more
+// block of its own, ExParamsPg8<B> = ExParamsPg<B> + ExKv8, so every other kernel keeps its block and its code.
+struct ExKv8 {
+    const float *kd, *vd;  // (batch, heads_kv) at batch stride bs (0: one row for every sequence), or null
+    long long bs;
+};
+template <typename B> struct ExParamsPg8 : ExParamsPg<B> {
+    ExKv8 q8;
+};
+static_assert(sizeof(ExKv8) == 24 && sizeof(ExParamsPg8<ExParamsK>) == sizeof(ExParamsPg<ExParamsK>) + sizeof(ExKv8), "ExParamsPg8 layout: ExKv8 after every other field");
+// the two scales of (sequence b, K/V head hk): uniform over the workgroup (scalar loads)
+__device__ __forceinline__ float kv8_scale(const float* sc, long long bs, int b, int hk) { return sc ? sc[(long long)b * bs + hk] : 1.0f; }
+// 8 e4m3 bytes -> 8 values of q's 16-bit dtype, exact (every finite e4m3 value is a normal f16 and bf16 number): one
+// v_cvt_scalef32_pk_{f16,bf16}_fp8 at scale 1.0 per pair, element order kept (fa_decode.hip widens its cache with it as well)
+template <typename Tag> __device__ __forceinline__ u32x4 kv_q8_widen(u32x2 c);
+template <> __device__ __forceinline__ u32x4 kv_q8_widen<f16_tag>(u32x2 c) {
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    u32x4 out;
+    out[0] = __builtin_bit_cast(uint32_t, (h2)__builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c[0], 1.0f, false));
+    out[1] = __builtin_bit_cast(uint32_t, (h2)__builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c[0], 1.0f, true));
+    out[2] = __builtin_bit_cast(uint32_t, (h2)__builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c[1], 1.0f, false));
+    out[3] = __builtin_bit_cast(uint32_t, (h2)__builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c[1], 1.0f, true));
+    return out;
+}
+template <> __device__ __forceinline__ u32x4 kv_q8_widen<bf16_tag>(u32x2 c) {
+    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
+    u32x4 out;
+    out[0] = __builtin_bit_cast(uint32_t, (b2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[0], 1.0f, false));
+    out[1] = __builtin_bit_cast(uint32_t, (b2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[0], 1.0f, true));
+    out[2] = __builtin_bit_cast(uint32_t, (b2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[1], 1.0f, false));
+    out[3] = __builtin_bit_cast(uint32_t, (b2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[1], 1.0f, true));
+    return out;
+}
+
 // page slot t / ps of key t (uniform where t is)
 __device__ __forceinline__ int pg_slot(const ExPage& pg, int t) {
     return pg.ps16m ? (int)__umulhi((unsigned)t >> 4, pg.ps16m) : (t >> 4);
@@ -207,6 +243,67 @@ __device__ __forceinline__ void dma_stage_kv_paged(const ExPage& pg, const int* 
     }
 }
 
+// The same for an e4m3 pool (kFeatKv8): the DMA moves the pool's bytes into a staging area and the waves widen them into the 16-bit
+// tile image afterwards (kv8_widen_block).  Wave w owns the 16 keys row0 + 16 w .. + 15 of the tile, K and V alike: 16 keys never
+// straddle a page (a page holds a multiple of 16), so ONE table entry and one descriptor per tensor serve the wave's block, whose
+// num_records are the bytes of its rows below nk (0: past the sequence or a page outside the pool, everything lands as zeros).  The
+// block moves as 16 D / 256 buffer_load_dword .. lds of 256 bytes each: dword granularity, because an e4m3 head row of d bytes
+// (d % 8 == 0, the pool 8-byte aligned) starts on an 8-byte boundary only and the range check cuts a row at d, which a 16-byte
+// piece does neither.  Lane l of instruction j fetches bytes 4 (l % (D / 4)) .. + 3 of row (256 / D) j + l / (D / 4), so the staged
+// block is row-major [16][D] bytes; the columns past dr are requested at kOobOff and land as zeros.
+template <int D>
+__device__ __forceinline__ int dma_lane_voff8(int lane, int dr, int stride) {
+    constexpr int LPR = D / 4;   // lanes per row
+    const int rl = lane / LPR, c = lane - rl * LPR;
+    return 4 * c < dr ? rl * stride + 4 * c : kOobOff;
+}
+// one tensor's share of a block: its descriptor, then the 16 D / 256 loads.  The LDS address and the row offset (soffset) walk
+// from values made opaque per call: left to hipcc they are hoisted out of the key loop as 2 * 16 D / 256 scalar registers per
+// tensor, which the scalar file does not have (they came back as SGPRs spilled to VGPR lanes)
+template <int D>
+__device__ __forceinline__ void dma_stage_block8(const char* base, long long off, unsigned bytes, unsigned lds, int voff, int stride) {
+    constexpr int RPI = 256 / D, NI = 16 / RPI;   // rows per instruction, instructions per block
+    const rsrc_s_t rs = make_rsrc_s(base + off, bytes);
+    int soff = 0;
+    asm volatile("" : "+s"(lds), "+s"(soff));
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+        dma4_issue(rs, lds, voff, soff);
+        lds += 256;
+        soff += RPI * stride;
+    }
+}
+// (K's loads are all issued before V's descriptor is made: one descriptor's four scalar registers live at a time)
+template <int D, int ROWS, int NW>
+__device__ __forceinline__ void dma_stage_kv_paged8(const ExPage& pg, const int* __restrict__ trow, int last, const char* kh, const char* vh,
+                                                    char* kstage, char* vstage, int row0, int nk, int voff_k, int voff_v, int w, int dr,
+                                                    int sk, int sv) {
+    static_assert(ROWS == 16 * NW, "one block of 16 keys per wave");
+    const int key = __builtin_amdgcn_readfirstlane(row0 + 16 * w);
+    const int rows = min(16, nk - key);                  // <= 0: the block lies past the sequence
+    const int slot = min(pg_slot(pg, key), last);
+    const int page = trow[slot];
+    const bool ok = rows > 0 && (unsigned)page < (unsigned)pg.num_blocks;
+    const long long inpage = key - slot * pg.ps;
+    dma_stage_block8<D>(kh, ok ? (long long)page * pg.kps + inpage * sk : 0ll, ok ? (unsigned)((rows - 1) * sk + dr) : 0u,
+                        lds_addr_of(kstage) + w * 16 * D, voff_k, sk);
+    dma_stage_block8<D>(vh, ok ? (long long)page * pg.vps + inpage * sv : 0ll, ok ? (unsigned)((rows - 1) * sv + dr) : 0u,
+                        lds_addr_of(vstage) + w * 16 * D, voff_v, sv);
+}
+// Wave w widens the block it staged (after the caller's vmcnt(0) and barrier; no other wave touches these bytes) into rows
+// 16 w .. 16 w + 15 of the TileSwz<D> image: 8 bytes in, one 16-byte chunk out, chunk i * 64 + lane of the block's 2 D.
+template <typename Tag, int D>
+__device__ __forceinline__ void kv8_widen_block(const char* stage, char* tile, int w, int lane) {
+    constexpr int CPR = D / 8, PER_LANE = 16 * CPR / 64;
+    const char* src = stage + w * 16 * D + 8 * lane;
+#pragma unroll
+    for (int i = 0; i < PER_LANE; ++i) {
+        const int idx = i * 64 + lane, row = idx / CPR, ch = idx - row * CPR;
+        const u32x2 c = *reinterpret_cast<const u32x2*>(src + i * 512);
+        *reinterpret_cast<u32x4*>(tile + TileSwz<D>::off(16 * w + row, ch)) = kv_q8_widen<Tag>(c);
+    }
+}
+
 inline ExParams make_ex_params(const ExArgs& a) {
     ExParams p;
     p.nq = (int)a.nq; p.nk = (int)a.nk; p.d = (int)a.d;
@@ -265,5 +362,6 @@ inline ExPage make_ex_page(const ExArgs& a) {
     g.ps16m = kv_magic(a.page_size / 16);
     return g;
 }
+inline ExKv8 make_ex_kv8(const ExArgs& a) { return ExKv8{a.k_descale, a.v_descale, (long long)a.descale_bstride}; }
 
 }  // namespace fa

@@ -25,6 +25,7 @@
 //               a K/V tile differs (dma_stage_kv_paged): each 1-KiB piece takes its page from one scalar table load and gets a
 //               buffer descriptor of its own; everything after the staging is the text of the packed kernel, so a sequence gets
 //               the bits of the packed call on the same tokens.  Kernels of their own (exm_fwd_paged_kernel).
+//   FEAT bit 7  an e4m3 pool (always with bits 3 and 6): fa_ex_mfma_kv8.hip, a translation unit of its own.
 // Dense mask bytes are fetched with range-checked buffer loads (rows / bytes past the mask read as 0 = masked); when Nk, the
 // mask pointer and the (b,h) stride are multiples of 4 a lane of the query-on-the-lane kernels takes the 4 keys of a
 // register group with one dword load.  The block-sparse mask needs br, bc multiples of 32 here (a wave's 32 x 32 block
@@ -32,25 +33,12 @@
 // they are loaded, live tiles mask their dead 32 x 32 blocks.  A row without a visible key: o = 0, lse = -inf, dQ = 0.
 #include "fa_common.h"
 #include "fa_ex_common.h"
+#include "fa_ex_mfma_feat.h"
 #include "fa_kernels.h"
 
 namespace fa {
 
 namespace {
-
-constexpr int kFeatMask = 1, kFeatDrop = 2, kFeatWindow = 4, kFeatVarlen = 8, kFeatScore = 16, kFeatSink = 32, kFeatPaged = 64;
-// the parameter block of an instantiation: ExParamsK (+ the sinks) with kFeatSink, ExParamsS (+ the score modifiers) with
-// kFeatScore, else ExParams as before
-template <int FEAT> using ExP = typename std::conditional<(FEAT & kFeatSink) != 0, ExParamsK,
-                                typename std::conditional<(FEAT & kFeatScore) != 0, ExParamsS, ExParams>::type>::type;
-template <int FEAT> inline ExP<FEAT> make_exm_params(const ExArgs& a) {
-    if constexpr ((FEAT & kFeatSink) != 0) return make_ex_params_k(a);
-    else if constexpr ((FEAT & kFeatScore) != 0) return make_ex_params_s(a);
-    else return make_ex_params(a);
-}
-
-// rc(i): row (or key) offset inside a 32-wide block of accumulator register i, before the 4 * (lane >> 5) term
-__device__ __forceinline__ constexpr int rc_of(int i) { return (i & 3) + 8 * (i >> 2); }
 
 // Which tiles does the block-sparse mask leave alive?  A workgroup walks tiles along ONE axis (key tiles of T keys in
 // the forward and dQ kernels, query tiles of T rows in the dK/dV kernel) against a fixed range of the other axis.  One

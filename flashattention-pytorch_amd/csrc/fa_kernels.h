@@ -165,6 +165,12 @@ struct ExArgs {
     // len_k[b] = cu_k[b + 1] - cu_k[b] clamped to [0, nk], nk = min(max_seqlen_k, max_blocks * page_size); total_k is not used.
     const int* block_table = nullptr;
     int64_t max_blocks = 0, num_blocks = 0, page_size = 0, page_stride_k = 0, page_stride_v = 0;
+    // an e4m3 pool under the paged varlen forward (fa_ex_forward_varlen_paged_fp8; 0 / null: a pool of q's dtype).  kv_e4m3: k and v
+    // hold OCP e4m3 bytes and stride_k / stride_v / page_stride_k / _v (still in elements) are bytes; a stored byte c of K head h of
+    // sequence b stands for e4m3(c) * k_descale[b * descale_bstride + h] (V likewise), a null scale for 1.0 (KvArgs has the same).
+    int kv_e4m3 = 0;
+    const float *k_descale = nullptr, *v_descale = nullptr;
+    int64_t descale_bstride = 0;
 };
 // does the call carry a score modifier (softcap or ALiBi)?  Such a call runs on the extended kernels only.
 inline bool ex_scoremod(const ExArgs& a) { return a.softcap > 0.0 || a.alibi != nullptr; }
@@ -183,6 +189,8 @@ bool ex_mfma_varlen_supported(const ExArgs& a);
 hipError_t launch_ex_mfma_varlen(const ExArgs& a, bool backward, hipStream_t st);
 bool ex_mfma_paged_supported(const ExArgs& a);                        // the paged varlen forward (a.block_table != null)
 hipError_t launch_ex_mfma_varlen_paged(const ExArgs& a, hipStream_t st);
+bool ex_mfma_paged_kv8_supported(const ExArgs& a);                    // the same from an e4m3 pool (a.kv_e4m3; fa_ex_mfma_kv8.hip)
+hipError_t launch_ex_mfma_varlen_paged_kv8(const ExArgs& a, hipStream_t st);
 size_t ex_backward_workspace_bytes(int64_t bh, int64_t nq);
 // the two per-query-head dK / dV partial slabs of a grouped backward (kv_group > 1), each rounded to 256 bytes
 inline size_t kv_partial_bytes(int64_t bh, int64_t nk, int64_t d, int dtype) {

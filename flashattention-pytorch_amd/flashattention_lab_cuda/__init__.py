@@ -47,7 +47,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_ex_forward_sink", "fa_ex_backward_sink", "fa_ex_forward_varlen_sink", "fa_ex_backward_varlen_sink",
     "fa_ex_forward_kvcache_sink", "fa_ex_kvcache_workspace_bytes_sink",
     "fa_ex_forward_kvcache_varlen", "fa_ex_kvcache_workspace_bytes_varlen",
-    "fa_ex_forward_varlen_paged",
+    "fa_ex_forward_varlen_paged", "fa_ex_forward_varlen_paged_fp8",
 )
 
 
@@ -177,6 +177,9 @@ def _load_library() -> ctypes.CDLL:
     # max_blocks_per_seq, num_blocks, page_block_size, k_page_stride, v_page_stride
     lib.fa_ex_forward_varlen_paged.argtypes = [vp, vp, vp, vp, vp] + varlen_sm[:21] + [vp, i64] + [vp, i64, i64, i64, i64, i64] + [vp]
     lib.fa_ex_forward_varlen_paged.restype = ci
+    # the same over an e4m3 pool: + cache_dtype, k_descale, v_descale, descale_batch_stride in front of stream
+    lib.fa_ex_forward_varlen_paged_fp8.argtypes = lib.fa_ex_forward_varlen_paged.argtypes[:-1] + [ci, vp, vp, i64] + [vp]
+    lib.fa_ex_forward_varlen_paged_fp8.restype = ci
     lib.fa_ex_forward_kvcache_sink.argtypes = [vp] * 8 + [i64] * 7 + [ci] + [i64] * 10 + [ci, i64, i64, dbl, dbl, vp, i64, i64] + \
         [vp, i64, i64, i64, i64, vp, i64, vp] + [vp, vp, i64, i64, i64, i64, ci] + [ci, vp, vp, i64] + [vp, i64] + [vp, sz, vp]
     lib.fa_ex_forward_kvcache_sink.restype = ci
@@ -627,9 +630,25 @@ def _varlen_common(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_s
     return (cu_q, cu_k, cu_q.shape[0] - 1, hq, hkv, total_q, total_k, mq, mk, d, _DTYPE_CODE[q.dtype], sq, sk, sv)
 
 
+def _varlen_pool_e4m3(who, q, k, v, k_descale, v_descale):
+    """Are k and v torch.float8_e4m3fn pools?  The float8 rules of flash_attn_with_kvcache, for ex_varlen_forward."""
+    for name, t in (("k", k), ("v", v)):
+        if isinstance(t, torch.Tensor) and t.dtype in _FLOAT8_DTYPES and t.dtype != torch.float8_e4m3fn:
+            raise NotImplementedError(f"{who}: {name} of dtype {t.dtype} is not supported (an 8-bit cache is torch.float8_e4m3fn)")
+    e4m3 = k.dtype == torch.float8_e4m3fn and v.dtype == torch.float8_e4m3fn
+    if (k.dtype == torch.float8_e4m3fn or v.dtype == torch.float8_e4m3fn) and \
+            (not e4m3 or q.dtype not in (torch.float16, torch.bfloat16)):
+        raise RuntimeError(f"{who}: q must have a 16-bit dtype (float16 or bfloat16) and k, v both q's dtype or both "
+                           f"torch.float8_e4m3fn, got {q.dtype}, {k.dtype}, {v.dtype}")
+    if not e4m3 and (k_descale is not None or v_descale is not None):
+        raise RuntimeError(f"{who}: k_descale / v_descale need torch.float8_e4m3fn pools (k, v are {k.dtype})")
+    return e4m3
+
+
 def _varlen_paged_forward(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, dropout_p, wl, wr,
-                          cap, alibi_slopes, sinks, block_table):
-    """ex_varlen_forward with a block_table (fa_ex_forward_varlen_paged), its arguments checked"""
+                          cap, alibi_slopes, sinks, block_table, k_descale=None, v_descale=None):
+    """ex_varlen_forward with a block_table (fa_ex_forward_varlen_paged, fa_ex_forward_varlen_paged_fp8 for e4m3 pools), its
+    arguments checked"""
     if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32:
         dt = block_table.dtype if isinstance(block_table, torch.Tensor) else type(block_table).__name__
         raise NotImplementedError(f"{who}: block_table of dtype {dt} is not supported (int32 tensor expected)")
@@ -643,7 +662,8 @@ def _varlen_paged_forward(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q
     if q.dim() != 3 or k.dim() != 4 or v.shape != k.shape or q.shape[2] != k.shape[3]:
         raise RuntimeError(f"{who}: with block_table q must be (total_q, H_q, d), k and v pools (num_blocks, page_block_size, H_kv, d); "
                            f"got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
-    if q.dtype not in _DTYPE_CODE or k.dtype != q.dtype or v.dtype != q.dtype:
+    e4m3 = _varlen_pool_e4m3(who, q, k, v, k_descale, v_descale)
+    if not e4m3 and (q.dtype not in _DTYPE_CODE or k.dtype != q.dtype or v.dtype != q.dtype):
         raise RuntimeError(f"{who}: q, k, v must share a supported dtype")
     for name, c in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
         if c.dtype != torch.int32 or c.dim() != 1 or c.shape[0] < 2:
@@ -669,9 +689,32 @@ def _varlen_paged_forward(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q
     cu_q, cu_k, block_table = cu_seqlens_q.contiguous(), cu_seqlens_k.contiguous(), block_table.contiguous()
     aptr, _h, astride, alibi_slopes = alibi_arg(who, alibi_slopes, q.device, b * hq, heads=hq)
     sptr, sheads, sinks = sinks_arg(who, sinks, q.device, b * hq, heads=hq)
+    kdp, kds, k_descale = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
+    vdp, vds, v_descale = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
+    # The C entry point has ONE batch stride for both scales (as fa_ex_forward_kvcache_fp8 has).  Scales of the same form, the
+    # usual case, are passed as they are; in mixed forms, one (H_kv,) and one (B, H_kv), the (H_kv,) one is copied into (B, H_kv)
+    # rows here — one small copy kernel in front of the attention kernel, on the call's stream, captured and replayed with it (a
+    # replay reads the caller's tensor again, so changed scale values are seen).
+    if kdp and vdp and kds != vds:
+        if kds == 0:
+            k_descale = k_descale.expand(b, hkv).contiguous()
+            kdp, kds = k_descale.data_ptr(), hkv
+        elif vds == 0:
+            v_descale = v_descale.expand(b, hkv).contiguous()
+            vdp, vds = v_descale.data_ptr(), hkv
+        else:
+            k_descale, v_descale = k_descale.contiguous(), v_descale.contiguous()
+            kdp, kds, vdp, vds = k_descale.data_ptr(), hkv, v_descale.data_ptr(), hkv
     with torch.cuda.device(q.device):
         o = torch.empty((total_q, hq, d), dtype=q.dtype, device=q.device)
         lse = torch.empty((hq, total_q), dtype=torch.float32, device=q.device)
+        if e4m3:
+            _check(_lib.fa_ex_forward_varlen_paged_fp8(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(),
+                                                       cu_q.data_ptr(), cu_k.data_ptr(), b, hq, hkv, total_q, 0, mq, mk, d,
+                                                       _DTYPE_CODE[q.dtype], sq, kts, vts, int(bool(causal)), wl, wr, float(softmax_scale),
+                                                       cap, aptr, astride, sptr, sheads, block_table.data_ptr(), block_table.shape[1], nblk,
+                                                       ps, kps, vps, _E4M3_CODE, kdp, vdp, kds if kdp else vds, _stream_ptr(q.device)))
+            return o, lse
         _check(_lib.fa_ex_forward_varlen_paged(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), cu_q.data_ptr(),
                                                cu_k.data_ptr(), b, hq, hkv, total_q, 0, mq, mk, d, _DTYPE_CODE[q.dtype], sq, kts, vts,
                                                int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, astride, sptr, sheads,
@@ -681,7 +724,7 @@ def _varlen_paged_forward(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q
 
 
 def ex_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, dropout_p=0.0, seed=0,
-                      window=(-1, -1), softcap=0.0, alibi_slopes=None, *, block_table=None, sinks=None):
+                      window=(-1, -1), softcap=0.0, alibi_slopes=None, *, block_table=None, k_descale=None, v_descale=None, sinks=None):
     """(o, lse) of attention over packed sequences (FlashAttention-2's varlen layout): q (total_q, H_q, d), k and v
     (total_k, H_kv, d) — strided views along the token dim allowed — cu_seqlens_* int32 (batch + 1,) device offsets.  o is
     (total_q, H_q, d), lse (H_q, total_q) float32.  Never synchronises: cu_seqlens are clamped in the kernels.  softcap and
@@ -691,13 +734,21 @@ def ex_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seq
     multiple of 16, and key t of sequence b lives at pool[block_table[b, t // ps], t % ps]; len_k[b] = cu_seqlens_k[b + 1] -
     cu_seqlens_k[b], clamped to min(max_seqlen_k, max_blocks_per_seq * ps).  The pools may be strided views (their own page and
     token strides; a view that would need a copy raises ValueError) and are only read; no dropout.  Each sequence gets the bits
-    of the call on the same tokens gathered into packed k, v.  See fa_ex_forward_varlen_paged."""
+    of the call on the same tokens gathered into packed k, v.  See fa_ex_forward_varlen_paged.
+    With block_table the pools may both be torch.float8_e4m3fn (OCP e4m3; q and o stay 16-bit), the cache of flash_attn_with_kvcache:
+    a stored byte c of K head h of sequence b stands for e4m3(c) * k_descale[b, h] (V: v_descale), float32 (batch, H_kv) or (H_kv,)
+    on q's device, None = 1.0.  The score is softmax_scale * k_descale * (q . k_stored), v_descale multiplies the normalised output
+    once.  Other float8 dtypes raise NotImplementedError, scales without e4m3 pools and e4m3 pools without block_table RuntimeError.
+    See fa_ex_forward_varlen_paged_fp8."""
     who = "ex_varlen_forward"
     wl, wr = window_arg(who, window)
     cap = softcap_arg(who, softcap)
     if block_table is not None:
         return _varlen_paged_forward(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale,
-                                     dropout_p, wl, wr, cap, alibi_slopes, sinks, block_table)
+                                     dropout_p, wl, wr, cap, alibi_slopes, sinks, block_table, k_descale, v_descale)
+    if isinstance(k, torch.Tensor) and isinstance(v, torch.Tensor) and isinstance(q, torch.Tensor) and \
+            _varlen_pool_e4m3(who, q, k, v, k_descale, v_descale):
+        raise RuntimeError(f"{who}: torch.float8_e4m3fn k, v are pools of a paged cache and need block_table")
     cu_q, cu_k, *dims = _varlen_common(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
     b, hq, _hkv, total_q, *_ = dims
     d = q.shape[2]

@@ -48,7 +48,7 @@ extern "C" {
 #define FA_DTYPE_F32 0
 #define FA_DTYPE_F16 1
 #define FA_DTYPE_BF16 2
-#define FA_DTYPE_E4M3 3 /* OCP e4m3 (float8_e4m3fn): only as cache_dtype of fa_ex_forward_kvcache_fp8 */
+#define FA_DTYPE_E4M3 3 /* OCP e4m3 (float8_e4m3fn): only as cache_dtype of fa_ex_forward_kvcache_fp8 / fa_ex_forward_varlen_paged_fp8 */
 
 /* Which implementation the dispatcher picks (fa_set_kernel_mode): AUTO = MFMA bf16/f16 kernels
  * when dtype is 16-bit and d is a multiple of 8 up to 256 (64 / 128 / 256 wide tiles, narrower rows zero-padded in the
@@ -543,6 +543,40 @@ int fa_ex_forward_varlen_paged(const void* q, const void* k, const void* v, void
                                const float* sinks, int64_t sink_heads, const int32_t* block_table, int64_t max_blocks_per_seq,
                                int64_t num_blocks, int64_t page_block_size, int64_t k_page_stride, int64_t v_page_stride,
                                void* stream);
+/* --- The same over an e4m3 pool: the cache that fa_ex_forward_kvcache_fp8 appends to and decodes from, read by the prefill kernel.
+ * The arguments are those of fa_ex_forward_varlen_paged plus cache_dtype, k_descale, v_descale, descale_batch_stride in front of
+ * stream; cache_dtype == dtype with null scales and stride 0 IS fa_ex_forward_varlen_paged, bit for bit.  With FA_DTYPE_E4M3:
+ *   k, v: pools (num_blocks, page_block_size, heads_kv, d) of OCP e4m3 (float8_e4m3fn) bytes; their token and page strides are in
+ *     elements, which are bytes.  q and o stay f16 / bf16 (dtype), lse fp32.
+ *   A stored byte c of K head h of sequence b (the sequence of the call, not the page) stands for
+ *     e4m3(c) * k_descale[b * descale_batch_stride + h], for V with v_descale: float32, device memory, read by the kernels only,
+ *     (batch, heads_kv) or, at stride 0, (heads_kv,); NULL = 1.0.  The sentences of fa_ex_forward_kvcache_fp8: both calls agree on
+ *     one cache.
+ *   Widening e4m3 to f16 / bf16 is exact, so K and V are widened and the 16-bit kernel is kept; Q and P are not quantised.  The
+ *     score is softmax_scale * k_descale[b,h] * (q . k_stored), scaled before softcap and ALiBi; v_descale[b,h] multiplies the
+ *     normalised output once in fp32 before its single rounding; lse is the logsumexp of the scaled, modified scores (the sink
+ *     included, untouched by the scales).
+ *   Everything else is fa_ex_forward_varlen_paged's: the untrusted table (a page outside the pool reads as zero K and V, byte 0x00),
+ *     no entry past ceil(len_k / ps) read, 64-bit page offsets, strided pool views, device-side clamped lengths, no host read, graph
+ *     capture and replay (with changed scale values in the same scale tensors too).
+ * With null scales o and lse have the bits of fa_ex_forward_varlen_paged on the pools widened to dtype; with power-of-two scales
+ * those of that call at softmax_scale * k_descale, o times v_descale.
+ * Kernels: 16-bit MFMA for d <= 128 (q, o 16-byte aligned, q_stride % 8 == 0; every pool this call accepts), exact f32 for
+ * d <= 256.
+ * Checked before any HIP call (FA_ERR_INVALID_ARGUMENT), besides fa_ex_forward_varlen_paged's list: cache_dtype neither dtype nor
+ * FA_DTYPE_E4M3; a scale or a non-zero descale_batch_stride with a 16-bit pool; descale_batch_stride negative, or non-zero and
+ * below heads_kv; a scale not 4-byte aligned; with FA_DTYPE_E4M3: dtype not f16 / bf16, d not a multiple of 8, a pool not 8-byte
+ * aligned, a pool stride not a multiple of 8.  FA_ERR_UNSUPPORTED: a page spanning 2^31 bytes or more (bytes: an e4m3 page may
+ * hold twice the tokens). */
+int fa_ex_forward_varlen_paged_fp8(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
+                                   const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
+                                   int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
+                                   int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
+                                   double softmax_scale, double softcap, const float* alibi_slopes, int64_t alibi_batch_stride,
+                                   const float* sinks, int64_t sink_heads, const int32_t* block_table, int64_t max_blocks_per_seq,
+                                   int64_t num_blocks, int64_t page_block_size, int64_t k_page_stride, int64_t v_page_stride,
+                                   int cache_dtype, const float* k_descale, const float* v_descale, int64_t descale_batch_stride,
+                                   void* stream);
 /* Decoding: the sink joins when the per-split partials are combined,
  *     m = max(max_s lse_s, sink)   denom = sum_s exp(lse_s - m) + exp(sink - m)   o = sum_s exp(lse_s - m) O_s / denom
  *     lse = m + log(denom)

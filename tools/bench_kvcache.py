@@ -31,7 +31,11 @@ and V are then 1 an element.  ex_forward and the unfused rotation keep the 16-bi
   (a) decode_us        : the packed decode call (ex_kvcache_forward with cu_seqlens_q), which re-reads the keys ceil(n G / 16) times,
   (b) paged_varlen_us  : ex_varlen_forward(..., block_table=), the prefill kernel reading the pool through the table,
   (c) gather_varlen_us : the pages gathered into packed k, v by torch indexing, then ex_varlen_forward (the gather alone: gather_us).
-  The three are timed in turn, --rounds times over, so that clock and cache state drift hits all alike; each figure is the median
+  and, on an e4m3 copy of the same tokens (one absmax scale per K/V head; k_descale, v_descale):
+  (a8) decode_e4m3_us       : the packed decode call on the e4m3 pools, the only route to an e4m3 cache before (b8) existed,
+  (b8) paged_varlen_e4m3_us : ex_varlen_forward(..., block_table=, k_descale=, v_descale=), the prefill kernel on the e4m3 pools
+  ((b) itself is the 16-bit context for (b8): the same tokens on the same kernel without the widening pass).
+  All are timed in turn, --rounds times over, so that clock and cache state drift hits all alike; each figure is the median
   of the rounds (each round itself the median of --reps groups).  (b) is checked to be bitwise (c) before anything is timed.
   --parent-check: only the packed ex_varlen_forward without a table at B H = 64, 4096 tokens, d = 128 (B = 2 sequences of 4096,
   32 heads, causal): the figure to compare between two checkouts, with the spread of its rounds.
@@ -250,6 +254,11 @@ def prefill_rows(args, dtype):
         kp = torch.randn((nblk, ps, hkv, d), device=dev, dtype=dtype)
         vp = torch.randn((nblk, ps, hkv, d), device=dev, dtype=dtype)
         sl = i32([cap])
+        # the same tokens as e4m3 pools: one scale per K/V head over the whole pool, the (H_kv,) form
+        kd = (kp.float().abs().amax(dim=(0, 1, 3)) / 448.0).clamp_min(2.0 ** -20)
+        vd = (vp.float().abs().amax(dim=(0, 1, 3)) / 448.0).clamp_min(2.0 ** -20)
+        kp8 = (kp.float() / kd.view(1, 1, -1, 1)).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+        vp8 = (vp.float() / vd.view(1, 1, -1, 1)).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
         for n in args.prefill_chunks:
             q = torch.randn((n, hq, d), device=dev, dtype=dtype)
             cq, ck = i32([0, n]), i32([0, cap])
@@ -265,21 +274,31 @@ def prefill_rows(args, dtype):
             ob, oc = paged(), gathered()
             assert torch.equal(ob[0], oc[0]) and torch.equal(ob[1], oc[1]), "the paged call and the gathered call disagree"
             torch.testing.assert_close(decode()[0].float(), ob[0].float(), rtol=2e-2, atol=2e-2)
-            ta, tb, tc, tg = [], [], [], []
+            decode8 = lambda: ext.ex_kvcache_forward(q, kp8, vp8, None, None, sl, True, None, block_table=table, cu_seqlens_q=cq,   # noqa: E731
+                                                     max_seqlen_q=n, k_descale=kd, v_descale=vd)
+            paged8 = lambda: ext.ex_varlen_forward(q, kp8, vp8, cq, ck, n, cap, True, d ** -0.5, block_table=table, k_descale=kd,   # noqa: E731
+                                                   v_descale=vd)
+            torch.testing.assert_close(paged8()[0].float(), decode8()[0].float(), rtol=2e-2, atol=2e-2)
+            ta, tb, tc, tg, ta8, tb8 = [], [], [], [], [], []
             for _ in range(args.rounds):
                 ta.append(t(decode))
                 tb.append(t(paged))
                 tc.append(t(gathered))
                 tg.append(t(gather))
+                ta8.append(t(decode8))
+                tb8.append(t(paged8))
             med = statistics.median
             r = dict(kind="prefill", len=cap, chunk=n, decode_us=round(med(ta), 2), paged_varlen_us=round(med(tb), 2),
                      gather_varlen_us=round(med(tc), 2), gather_us=round(med(tg), 2), decode_reads=(n * (hq // hkv) + 15) // 16,
                      varlen_reads=(n + 255) // 256, paged_vs_decode=round(med(tb) / med(ta), 3),
                      paged_vs_gathered=round(med(tb) / med(tc), 3), rounds=dict(decode=[round(x, 2) for x in ta], paged=[round(x, 2) for x in tb],
                                                                              gathered=[round(x, 2) for x in tc]))
+            r.update(decode_e4m3_us=round(med(ta8), 2), paged_varlen_e4m3_us=round(med(tb8), 2),
+                     paged_e4m3_vs_decode_e4m3=round(med(tb8) / med(ta8), 3), paged_e4m3_vs_paged=round(med(tb8) / med(tb), 3))
+            r["rounds"].update(decode_e4m3=[round(x, 2) for x in ta8], paged_e4m3=[round(x, 2) for x in tb8])
             rows.append(r)
             print(json.dumps(r), flush=True)
-        del kp, vp
+        del kp, vp, kp8, vp8
     return rows
 
 
