@@ -3,7 +3,6 @@
 // enqueued on the caller's stream.
 #include "../../include/fa_mi355x.h"
 #include "fa_kernels.h"
-#include <mutex>
 #include <unordered_map>
 
 #include <atomic>
@@ -66,6 +65,12 @@ int fail(int code, const char* fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
     return code;
+}
+
+// the end of a call that enqueued something: e is what HIP said
+int launched(const char* who, hipError_t e) {
+    if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
+    return FA_OK;
 }
 
 int check_common(const char* who, int64_t bh, int64_t n, int64_t d, int dtype, double scale) {
@@ -423,86 +428,82 @@ static void sink_args(fa::ExArgs& a, const SinkArg& sk) {
     a.dsinks = sk.dsinks;
 }
 
-static int ex_forward_impl(const char* who, const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t kv_group,
-                           int64_t nq, int64_t nk, int64_t d, int dtype, int causal, int64_t wl, int64_t wr, double softmax_scale,
-                           const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc,
-                           double dropout_p, uint64_t dropout_seed, void* stream, const ScoreMod& sm = ScoreMod(),
-                           const SinkArg& sk = SinkArg()) {
-    int rc = ex_check(who, bh, nq, nk, d, dtype, softmax_scale, block_mask, br, bc, dropout_p);
-    if (rc != FA_OK) return rc;
-    if ((rc = group_check(who, bh, kv_group)) != FA_OK) return rc;
-    if ((rc = score_check(who, sm, bh)) != FA_OK) return rc;
-    if ((rc = sink_check(who, sk, bh, false)) != FA_OK) return rc;
-    if ((rc = window_canon(who, nq, nk, causal, wl, wr)) != FA_OK) return rc;
-    if (bh == 0 || nq == 0) return FA_OK;
-    if (!q || !o || !lse || (nk > 0 && (!k || !v))) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
-    if (nk == 0) {   // no key at all: every row is a row without a visible key, o = 0 and lse = -inf; the sink with sinks
-        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-        hipError_t e = hipMemsetAsync(o, 0, (size_t)bh * nq * d * (dtype == FA_DTYPE_F32 ? 4 : 2), st);
-        if (e == hipSuccess && sk.sinks) e = fa::launch_ex_sink_fill(lse, sk.sinks, sk.heads, bh, nq, st);
-        else if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lse), (int)0xFF800000u, (size_t)bh * nq, st);
-        if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
-        return FA_OK;
-    }
-    fa::ExArgs a{q, k, v, o, lse, nullptr, nullptr, nullptr, nullptr, bh, nq, nk, d, dtype, causal ? 1 : 0, (float)softmax_scale,
-                 mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, nullptr};
-    a.kv_group = kv_group;
-    a.window_left = wl;
-    a.window_right = wr;
-    score_args(a, sm);
-    sink_args(a, sk);
-    hipError_t e = fa::launch_ex(a, false, reinterpret_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
-    return FA_OK;
+// A forward without a key: every row is a row without a visible key, o = 0 and lse = -inf, with sinks the head's sink.
+// o: units * rows * d elements, lse: units * rows.
+static int no_key_fill(const char* who, void* o, float* lse, int64_t units, int64_t rows, int64_t d, int dtype, const SinkArg& sk, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(o, 0, (size_t)units * rows * d * (dtype == FA_DTYPE_F32 ? 4 : 2), st);
+    if (e == hipSuccess && sk.sinks) e = fa::launch_ex_sink_fill(lse, sk.sinks, sk.heads, units, rows, st);
+    else if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lse), (int)0xFF800000u, (size_t)units * rows, st);
+    return launched(who, e);
 }
 
-static size_t ex_bwd_ws_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype);
+// A backward without a query row or without a key.  With sinks their gradient is 0 (no row, or rows with o = 0: delta = 0); nothing
+// else where both sides are empty; else the gradients of the side that has rows are sums over nothing: dk and dv where there is no
+// query row, dq where there is no key.
+static int empty_backward(const char* who, bool both, bool no_q, void* dq, size_t dq_bytes, void* dk, void* dv, size_t dkv_bytes,
+                          const SinkArg& sk, hipStream_t st) {
+    hipError_t e = sk.sinks ? hipMemsetAsync(sk.dsinks, 0, (size_t)sk.heads * 4, st) : hipSuccess;
+    if (e != hipSuccess || both) return launched(who, e);
+    if (no_q ? (!dk || !dv) : !dq) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    if (no_q) {
+        e = hipMemsetAsync(dk, 0, dkv_bytes, st);
+        if (e == hipSuccess) e = hipMemsetAsync(dv, 0, dkv_bytes, st);
+    } else {
+        e = hipMemsetAsync(dq, 0, dq_bytes, st);
+    }
+    return launched(who, e);
+}
 
-static int ex_backward_impl(const char* who, const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse,
-                            void* dq, void* dk, void* dv, int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype,
-                            int causal, int64_t wl, int64_t wr, double softmax_scale, const uint8_t* mask, int64_t mask_bh_stride,
-                            const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* workspace,
-                            size_t workspace_bytes, void* stream, const ScoreMod& sm = ScoreMod(), const SinkArg& sk = SinkArg()) {
-    int rc = ex_check(who, bh, nq, nk, d, dtype, softmax_scale, block_mask, br, bc, dropout_p);
+// One call of the fa_ex_forward* / fa_ex_backward* family.  The defaults are the narrower entry points' "argument absent": an entry
+// point assigns the arguments it has (ex_call / ex_bwd_call: the ones all of them have) and leaves the rest.
+struct ExCall {
+    const void *q = nullptr, *k = nullptr, *v = nullptr, *do_ = nullptr;
+    void* o = nullptr;      // (the backward only reads o and lse)
+    float* lse = nullptr;
+    void *dq = nullptr, *dk = nullptr, *dv = nullptr;
+    int64_t bh = 0, kv_group = 1, nq = 0, nk = 0, d = 0, window_left = -1, window_right = -1;
+    int dtype = 0, causal = 0;
+    double softmax_scale = 0.0, dropout_p = 0.0;
+    ScoreMod sm;
+    SinkArg sk;
+    const uint8_t *mask = nullptr, *block_mask = nullptr;
+    int64_t mask_bh_stride = 0, br = 0, bc = 0;
+    uint64_t dropout_seed = 0;
+    void *workspace = nullptr, *stream = nullptr;
+    size_t workspace_bytes = 0;
+};
+
+// the argument checks of a forward and a backward, in their order; the mask comes back canonical
+static int ex_checks(const char* who, const ExCall& c, bool backward, int& causal, int64_t& wl, int64_t& wr) {
+    int rc = ex_check(who, c.bh, c.nq, c.nk, c.d, c.dtype, c.softmax_scale, c.block_mask, c.br, c.bc, c.dropout_p);
     if (rc != FA_OK) return rc;
-    if ((rc = group_check(who, bh, kv_group)) != FA_OK) return rc;
-    if ((rc = score_check(who, sm, bh)) != FA_OK) return rc;
-    if ((rc = sink_check(who, sk, bh, true)) != FA_OK) return rc;
-    if ((rc = window_canon(who, nq, nk, causal, wl, wr)) != FA_OK) return rc;
-    if (sk.sinks && (bh == 0 || nq == 0 || nk == 0)) {   // no row, or rows with o = 0 (delta = 0): the sink's gradient is 0
-        hipError_t e = hipMemsetAsync(sk.dsinks, 0, (size_t)sk.heads * 4, reinterpret_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
-    }
-    if (bh == 0 || (nq == 0 && nk == 0)) return FA_OK;
-    if (nq == 0 || nk == 0) {   // one side empty: the gradients of the other side are sums over nothing
-        const size_t es = dtype == FA_DTYPE_F32 ? 4 : 2;
-        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-        hipError_t e = hipSuccess;
-        if (nq == 0) {   // (grouped: dk and dv hold bh / kv_group units)
-            if (!dk || !dv) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
-            e = hipMemsetAsync(dk, 0, (size_t)(bh / kv_group) * nk * d * es, st);
-            if (e == hipSuccess) e = hipMemsetAsync(dv, 0, (size_t)(bh / kv_group) * nk * d * es, st);
-        } else {
-            if (!dq) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
-            e = hipMemsetAsync(dq, 0, (size_t)bh * nq * d * es, st);
-        }
-        if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
-        return FA_OK;
-    }
-    if (!q || !k || !v || !o || !do_ || !lse || !dq || !dk || !dv) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
-    const size_t need = ex_bwd_ws_grouped(bh, kv_group, nq, nk, d, dtype);
-    if (!workspace || workspace_bytes < need)
-        return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
-    fa::ExArgs a{q, k, v, const_cast<void*>(o), const_cast<float*>(lse), do_, dq, dk, dv, bh, nq, nk, d, dtype, causal ? 1 : 0,
-                 (float)softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, workspace, workspace_bytes};
-    a.kv_group = kv_group;
+    if ((rc = group_check(who, c.bh, c.kv_group)) != FA_OK) return rc;
+    if ((rc = score_check(who, c.sm, c.bh)) != FA_OK) return rc;
+    if ((rc = sink_check(who, c.sk, c.bh, backward)) != FA_OK) return rc;
+    return window_canon(who, c.nq, c.nk, causal, wl, wr);
+}
+
+// what the launcher takes (the canonical mask: the caller's; a forward leaves the backward's pointers and the workspace absent)
+static fa::ExArgs ex_args(const ExCall& c, int causal, int64_t wl, int64_t wr) {
+    fa::ExArgs a{c.q, c.k, c.v, c.o, c.lse, c.do_, c.dq, c.dk, c.dv, c.bh, c.nq, c.nk, c.d, c.dtype, causal ? 1 : 0,
+                 (float)c.softmax_scale, c.mask, c.mask_bh_stride, c.block_mask, c.br, c.bc, c.dropout_p, c.dropout_seed, c.workspace,
+                 c.workspace_bytes};
+    a.kv_group = c.kv_group;
     a.window_left = wl;
     a.window_right = wr;
-    score_args(a, sm);
-    sink_args(a, sk);
-    hipError_t e = fa::launch_ex(a, true, reinterpret_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
-    return FA_OK;
+    score_args(a, c.sm);
+    sink_args(a, c.sk);
+    return a;
+}
+
+static int ex_forward_impl(const char* who, const ExCall& c) {
+    int causal = c.causal;
+    int64_t wl = c.window_left, wr = c.window_right;   // (window_canon rewrites the three)
+    if (const int rc = ex_checks(who, c, false, causal, wl, wr); rc != FA_OK) return rc;
+    if (c.bh == 0 || c.nq == 0) return FA_OK;
+    if (!c.q || !c.o || !c.lse || (c.nk > 0 && (!c.k || !c.v))) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    if (c.nk == 0) return no_key_fill(who, c.o, c.lse, c.bh, c.nq, c.d, c.dtype, c.sk, reinterpret_cast<hipStream_t>(c.stream));
+    return launched(who, fa::launch_ex(ex_args(c, causal, wl, wr), false, reinterpret_cast<hipStream_t>(c.stream)));
 }
 
 // the grouped minimum: the ungrouped one for bh query units, plus (kv_group > 1) the dK / dV partial slabs in front of it
@@ -510,6 +511,23 @@ static size_t ex_bwd_ws_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_
     size_t need = fa_ex_backward_workspace_bytes(bh, nq, nk, d, dtype);
     if (kv_group > 1 && bh > 0 && nq > 0 && nk > 0 && d > 0) need += 2 * fa::kv_partial_bytes(bh, nk, d, dtype);
     return need;
+}
+
+static int ex_backward_impl(const char* who, const ExCall& c) {
+    int causal = c.causal;
+    int64_t wl = c.window_left, wr = c.window_right;
+    if (const int rc = ex_checks(who, c, true, causal, wl, wr); rc != FA_OK) return rc;
+    const bool no_q = c.bh == 0 || c.nq == 0, no_k = c.bh == 0 || c.nk == 0;
+    const size_t es = c.dtype == FA_DTYPE_F32 ? 4 : 2;
+    if (no_q || no_k)   // (grouped: dk and dv hold bh / kv_group units)
+        return empty_backward(who, no_q && no_k, no_q, c.dq, (size_t)c.bh * c.nq * c.d * es, c.dk, c.dv,
+                              (size_t)(c.bh / c.kv_group) * c.nk * c.d * es, c.sk, reinterpret_cast<hipStream_t>(c.stream));
+    if (!c.q || !c.k || !c.v || !c.o || !c.do_ || !c.lse || !c.dq || !c.dk || !c.dv)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    const size_t need = ex_bwd_ws_grouped(c.bh, c.kv_group, c.nq, c.nk, c.d, c.dtype);
+    if (!c.workspace || c.workspace_bytes < need)
+        return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, need, c.workspace_bytes);
+    return launched(who, fa::launch_ex(ex_args(c, causal, wl, wr), true, reinterpret_cast<hipStream_t>(c.stream)));
 }
 
 // the dS room of the hand-over where it serves the call (the plain backward's rule; grouped: sized for chunks of whole groups)
@@ -521,43 +539,71 @@ static size_t ex_bwd_ds_room(int64_t bh, int64_t kv_group, int64_t nq, int64_t n
     return fa::bwd_ds_extra_bytes(bh, nq, d, dtype, causal != 0, false, nk, kv_group);
 }
 
+// the arguments every fa_ex_forward* has
+static ExCall ex_call(const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t nq, int64_t nk, int64_t d,
+                      int dtype, int causal, double softmax_scale, const uint8_t* mask, int64_t mask_bh_stride,
+                      const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* stream) {
+    ExCall c;
+    c.q = q; c.k = k; c.v = v; c.o = o; c.lse = lse;
+    c.bh = bh; c.nq = nq; c.nk = nk; c.d = d; c.dtype = dtype; c.causal = causal; c.softmax_scale = softmax_scale;
+    c.mask = mask; c.mask_bh_stride = mask_bh_stride; c.block_mask = block_mask; c.br = br; c.bc = bc;
+    c.dropout_p = dropout_p; c.dropout_seed = dropout_seed; c.stream = stream;
+    return c;
+}
+// ... and every fa_ex_backward*
+static ExCall ex_bwd_call(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
+                          void* dv, int64_t bh, int64_t nq, int64_t nk, int64_t d, int dtype, int causal, double softmax_scale,
+                          const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p,
+                          uint64_t dropout_seed, void* workspace, size_t workspace_bytes, void* stream) {
+    ExCall c = ex_call(q, k, v, const_cast<void*>(o), const_cast<float*>(lse), bh, nq, nk, d, dtype, causal, softmax_scale, mask,
+                       mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, stream);
+    c.do_ = do_; c.dq = dq; c.dk = dk; c.dv = dv; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    return c;
+}
+
 int fa_ex_forward(const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t nq, int64_t nk, int64_t d,
                   int dtype, int causal, double softmax_scale, const uint8_t* mask, int64_t mask_bh_stride,
                   const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* stream) {
-    return ex_forward_impl("fa_ex_forward", q, k, v, o, lse, bh, 1, nq, nk, d, dtype, causal, -1, -1, softmax_scale, mask, mask_bh_stride,
-                           block_mask, br, bc, dropout_p, dropout_seed, stream);
+    return ex_forward_impl("fa_ex_forward", ex_call(q, k, v, o, lse, bh, nq, nk, d, dtype, causal, softmax_scale, mask, mask_bh_stride,
+                                                    block_mask, br, bc, dropout_p, dropout_seed, stream));
 }
 
 int fa_ex_forward_grouped(const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t kv_group, int64_t nq,
                           int64_t nk, int64_t d, int dtype, int causal, double softmax_scale, const uint8_t* mask, int64_t mask_bh_stride,
                           const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* stream) {
-    return ex_forward_impl("fa_ex_forward_grouped", q, k, v, o, lse, bh, kv_group, nq, nk, d, dtype, causal, -1, -1, softmax_scale, mask,
-                           mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, stream);
+    ExCall c = ex_call(q, k, v, o, lse, bh, nq, nk, d, dtype, causal, softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p,
+                       dropout_seed, stream);
+    c.kv_group = kv_group;
+    return ex_forward_impl("fa_ex_forward_grouped", c);
 }
 
 int fa_ex_backward(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
                    void* dv, int64_t bh, int64_t nq, int64_t nk, int64_t d, int dtype, int causal, double softmax_scale,
                    const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p,
                    uint64_t dropout_seed, void* workspace, size_t workspace_bytes, void* stream) {
-    return ex_backward_impl("fa_ex_backward", q, k, v, o, do_, lse, dq, dk, dv, bh, 1, nq, nk, d, dtype, causal, -1, -1, softmax_scale, mask,
-                            mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, workspace, workspace_bytes, stream);
+    return ex_backward_impl("fa_ex_backward", ex_bwd_call(q, k, v, o, do_, lse, dq, dk, dv, bh, nq, nk, d, dtype, causal, softmax_scale, mask,
+                                                          mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, workspace,
+                                                          workspace_bytes, stream));
 }
 
 int fa_ex_backward_grouped(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq,
                            void* dk, void* dv, int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype, int causal,
                            double softmax_scale, const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br,
                            int64_t bc, double dropout_p, uint64_t dropout_seed, void* workspace, size_t workspace_bytes, void* stream) {
-    return ex_backward_impl("fa_ex_backward_grouped", q, k, v, o, do_, lse, dq, dk, dv, bh, kv_group, nq, nk, d, dtype, causal,
-                            -1, -1, softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, workspace, workspace_bytes,
-                            stream);
+    ExCall c = ex_bwd_call(q, k, v, o, do_, lse, dq, dk, dv, bh, nq, nk, d, dtype, causal, softmax_scale, mask, mask_bh_stride, block_mask,
+                           br, bc, dropout_p, dropout_seed, workspace, workspace_bytes, stream);
+    c.kv_group = kv_group;
+    return ex_backward_impl("fa_ex_backward_grouped", c);
 }
 
 int fa_ex_forward_window(const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t kv_group, int64_t nq,
                          int64_t nk, int64_t d, int dtype, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
                          const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p,
                          uint64_t dropout_seed, void* stream) {
-    return ex_forward_impl("fa_ex_forward_window", q, k, v, o, lse, bh, kv_group, nq, nk, d, dtype, causal, window_left, window_right,
-                           softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, stream);
+    ExCall c = ex_call(q, k, v, o, lse, bh, nq, nk, d, dtype, causal, softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p,
+                       dropout_seed, stream);
+    c.kv_group = kv_group; c.window_left = window_left; c.window_right = window_right;
+    return ex_forward_impl("fa_ex_forward_window", c);
 }
 
 int fa_ex_backward_window(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq,
@@ -565,9 +611,10 @@ int fa_ex_backward_window(const void* q, const void* k, const void* v, const voi
                           int64_t window_left, int64_t window_right, double softmax_scale, const uint8_t* mask, int64_t mask_bh_stride,
                           const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* workspace,
                           size_t workspace_bytes, void* stream) {
-    return ex_backward_impl("fa_ex_backward_window", q, k, v, o, do_, lse, dq, dk, dv, bh, kv_group, nq, nk, d, dtype, causal,
-                            window_left, window_right, softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed,
-                            workspace, workspace_bytes, stream);
+    ExCall c = ex_bwd_call(q, k, v, o, do_, lse, dq, dk, dv, bh, nq, nk, d, dtype, causal, softmax_scale, mask, mask_bh_stride, block_mask,
+                           br, bc, dropout_p, dropout_seed, workspace, workspace_bytes, stream);
+    c.kv_group = kv_group; c.window_left = window_left; c.window_right = window_right;
+    return ex_backward_impl("fa_ex_backward_window", c);
 }
 
 int fa_ex_forward_scoremod(const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t kv_group, int64_t nq,
@@ -575,10 +622,11 @@ int fa_ex_forward_scoremod(const void* q, const void* k, const void* v, void* o,
                            double softcap, const float* alibi_slopes, int64_t alibi_heads, int64_t alibi_batch_stride, const uint8_t* mask,
                            int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p,
                            uint64_t dropout_seed, void* stream) {
-    ScoreMod sm;
-    sm.softcap = softcap; sm.alibi = alibi_slopes; sm.heads = alibi_heads; sm.bstride = alibi_batch_stride;
-    return ex_forward_impl("fa_ex_forward_scoremod", q, k, v, o, lse, bh, kv_group, nq, nk, d, dtype, causal, window_left, window_right,
-                           softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, stream, sm);
+    ExCall c = ex_call(q, k, v, o, lse, bh, nq, nk, d, dtype, causal, softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p,
+                       dropout_seed, stream);
+    c.kv_group = kv_group; c.window_left = window_left; c.window_right = window_right;
+    c.sm = {softcap, alibi_slopes, alibi_heads, alibi_batch_stride};
+    return ex_forward_impl("fa_ex_forward_scoremod", c);
 }
 
 int fa_ex_backward_scoremod(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq,
@@ -587,11 +635,11 @@ int fa_ex_backward_scoremod(const void* q, const void* k, const void* v, const v
                             int64_t alibi_heads, int64_t alibi_batch_stride, const uint8_t* mask, int64_t mask_bh_stride,
                             const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* workspace,
                             size_t workspace_bytes, void* stream) {
-    ScoreMod sm;
-    sm.softcap = softcap; sm.alibi = alibi_slopes; sm.heads = alibi_heads; sm.bstride = alibi_batch_stride;
-    return ex_backward_impl("fa_ex_backward_scoremod", q, k, v, o, do_, lse, dq, dk, dv, bh, kv_group, nq, nk, d, dtype, causal,
-                            window_left, window_right, softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed,
-                            workspace, workspace_bytes, stream, sm);
+    ExCall c = ex_bwd_call(q, k, v, o, do_, lse, dq, dk, dv, bh, nq, nk, d, dtype, causal, softmax_scale, mask, mask_bh_stride, block_mask,
+                           br, bc, dropout_p, dropout_seed, workspace, workspace_bytes, stream);
+    c.kv_group = kv_group; c.window_left = window_left; c.window_right = window_right;
+    c.sm = {softcap, alibi_slopes, alibi_heads, alibi_batch_stride};
+    return ex_backward_impl("fa_ex_backward_scoremod", c);
 }
 
 int fa_ex_forward_sink(const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t kv_group, int64_t nq,
@@ -599,12 +647,12 @@ int fa_ex_forward_sink(const void* q, const void* k, const void* v, void* o, flo
                        double softcap, const float* alibi_slopes, int64_t alibi_heads, int64_t alibi_batch_stride, const float* sinks,
                        int64_t sink_heads, const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc,
                        double dropout_p, uint64_t dropout_seed, void* stream) {
-    ScoreMod sm;
-    sm.softcap = softcap; sm.alibi = alibi_slopes; sm.heads = alibi_heads; sm.bstride = alibi_batch_stride;
-    SinkArg sk;
-    sk.sinks = sinks; sk.heads = sink_heads;
-    return ex_forward_impl("fa_ex_forward_sink", q, k, v, o, lse, bh, kv_group, nq, nk, d, dtype, causal, window_left, window_right,
-                           softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, stream, sm, sk);
+    ExCall c = ex_call(q, k, v, o, lse, bh, nq, nk, d, dtype, causal, softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p,
+                       dropout_seed, stream);
+    c.kv_group = kv_group; c.window_left = window_left; c.window_right = window_right;
+    c.sm = {softcap, alibi_slopes, alibi_heads, alibi_batch_stride};
+    c.sk = {sinks, sink_heads, nullptr};
+    return ex_forward_impl("fa_ex_forward_sink", c);
 }
 
 int fa_ex_backward_sink(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
@@ -613,20 +661,46 @@ int fa_ex_backward_sink(const void* q, const void* k, const void* v, const void*
                         int64_t alibi_heads, int64_t alibi_batch_stride, const float* sinks, int64_t sink_heads, float* dsinks,
                         const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p,
                         uint64_t dropout_seed, void* workspace, size_t workspace_bytes, void* stream) {
-    ScoreMod sm;
-    sm.softcap = softcap; sm.alibi = alibi_slopes; sm.heads = alibi_heads; sm.bstride = alibi_batch_stride;
-    SinkArg sk;
-    sk.sinks = sinks; sk.heads = sink_heads; sk.dsinks = dsinks;
-    return ex_backward_impl("fa_ex_backward_sink", q, k, v, o, do_, lse, dq, dk, dv, bh, kv_group, nq, nk, d, dtype, causal, window_left,
-                            window_right, softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p, dropout_seed, workspace,
-                            workspace_bytes, stream, sm, sk);
+    ExCall c = ex_bwd_call(q, k, v, o, do_, lse, dq, dk, dv, bh, nq, nk, d, dtype, causal, softmax_scale, mask, mask_bh_stride, block_mask,
+                           br, bc, dropout_p, dropout_seed, workspace, workspace_bytes, stream);
+    c.kv_group = kv_group; c.window_left = window_left; c.window_right = window_right;
+    c.sm = {softcap, alibi_slopes, alibi_heads, alibi_batch_stride};
+    c.sk = {sinks, sink_heads, dsinks};
+    return ex_backward_impl("fa_ex_backward_sink", c);
 }
 
 // ---- variable-length (packed) sequences: see include/fa_mi355x.h
 // Everything that can be checked without reading cu_seqlens (which would take a synchronise), before any HIP call.
-static int varlen_check(const char* who, const int32_t* cu_q, const int32_t* cu_k, int64_t batch, int64_t hq, int64_t hkv, int64_t total_q,
-                        int64_t total_k, int64_t max_q, int64_t max_k, int64_t d, int dtype, int64_t sq, int64_t sk, int64_t sv,
-                        int64_t wl, int64_t wr, double scale, double p) {
+// One call of the fa_ex_*_varlen* family, fa_ex_forward_varlen_paged / _paged_fp8 included.  Defaults: "argument absent"; cache_dtype is the
+// exception, an entry point without one sets it to dtype.
+struct VarlenCall {
+    const void *q = nullptr, *k = nullptr, *v = nullptr, *do_ = nullptr;
+    void* o = nullptr;      // (the backward only reads o and lse)
+    float* lse = nullptr;
+    void *dq = nullptr, *dk = nullptr, *dv = nullptr;
+    const int32_t *cu_seqlens_q = nullptr, *cu_seqlens_k = nullptr;
+    int64_t batch = 0, heads_q = 0, heads_kv = 0, total_q = 0, total_k = 0, max_seqlen_q = 0, max_seqlen_k = 0, d = 0;
+    int64_t q_stride = 0, k_stride = 0, v_stride = 0, window_left = -1, window_right = -1;
+    int dtype = 0, causal = 0;
+    double softmax_scale = 0.0, dropout_p = 0.0;
+    uint64_t dropout_seed = 0;
+    ScoreMod sm;            // (heads: heads_q)
+    SinkArg sk;
+    const int32_t* block_table = nullptr;   // the paged forward, and (cache_dtype, the scales) its e4m3 pool
+    int64_t max_blocks_per_seq = 0, num_blocks = 0, page_block_size = 0, k_page_stride = 0, v_page_stride = 0, descale_batch_stride = 0;
+    int cache_dtype = 0;
+    const float *k_descale = nullptr, *v_descale = nullptr;
+    void *workspace = nullptr, *stream = nullptr;
+    size_t workspace_bytes = 0;
+};
+
+// (total_k: the paged call has no token count and passes 1)
+static int varlen_check(const char* who, const VarlenCall& c, int64_t total_k) {
+    const int32_t *cu_q = c.cu_seqlens_q, *cu_k = c.cu_seqlens_k;
+    const int64_t batch = c.batch, hq = c.heads_q, hkv = c.heads_kv, total_q = c.total_q, max_q = c.max_seqlen_q, max_k = c.max_seqlen_k, d = c.d;
+    const int64_t sq = c.q_stride, sk = c.k_stride, sv = c.v_stride, wl = c.window_left, wr = c.window_right;
+    const int dtype = c.dtype;
+    const double scale = c.softmax_scale, p = c.dropout_p;
     if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_F16 && dtype != FA_DTYPE_BF16)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: unknown dtype code %d", who, dtype);
     if (batch < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch must be >= 1 (got %lld)", who, (long long)batch);
@@ -655,78 +729,108 @@ static int varlen_check(const char* who, const int32_t* cu_q, const int32_t* cu_
     return FA_OK;
 }
 
-static fa::ExArgs varlen_args(const int32_t* cu_q, const int32_t* cu_k, int64_t batch, int64_t hq, int64_t hkv, int64_t total_q, int64_t total_k,
-                              int64_t max_q, int64_t max_k, int64_t d, int dtype, int64_t sq, int64_t sk, int64_t sv, int causal, int64_t wl,
-                              int64_t wr, double scale, double p, uint64_t seed) {
-    fa::ExArgs a{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, batch * hq, max_q, max_k, d, dtype,
-                 causal ? 1 : 0, (float)scale, nullptr, 0, nullptr, 0, 0, p, seed, nullptr};
-    a.kv_group = hq / hkv;
+// (total_k, max_k and the canonical mask: the caller's)
+static fa::ExArgs varlen_args(const VarlenCall& c, int64_t total_k, int64_t max_k, int causal, int64_t wl, int64_t wr) {
+    fa::ExArgs a{c.q, c.k, c.v, c.o, c.lse, c.do_, c.dq, c.dk, c.dv, c.batch * c.heads_q, c.max_seqlen_q, max_k, c.d, c.dtype,
+                 causal ? 1 : 0, (float)c.softmax_scale, nullptr, 0, nullptr, 0, 0, c.dropout_p, c.dropout_seed, c.workspace, c.workspace_bytes};
+    a.kv_group = c.heads_q / c.heads_kv;
     a.window_left = wl;
     a.window_right = wr;
-    a.cu_q = cu_q;
-    a.cu_k = cu_k;
-    a.heads_q = hq;
-    a.total_q = total_q;
+    a.cu_q = c.cu_seqlens_q;
+    a.cu_k = c.cu_seqlens_k;
+    a.heads_q = c.heads_q;
+    a.total_q = c.total_q;
     a.total_k = total_k;
-    a.stride_q = sq;
-    a.stride_k = sk;
-    a.stride_v = sv;
+    a.stride_q = c.q_stride;
+    a.stride_k = c.k_stride;
+    a.stride_v = c.v_stride;
+    score_args(a, c.sm);
+    sink_args(a, c.sk);
     return a;
 }
 
-static int varlen_forward_impl(const char* who, const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
-                               const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
-                               int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
-                               int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
-                               double softmax_scale, double dropout_p, uint64_t dropout_seed, void* stream, const ScoreMod& sm,
-                               const SinkArg& sk = SinkArg()) {
-    int rc = varlen_check(who, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype,
-                          q_stride, k_stride, v_stride, window_left, window_right, softmax_scale, dropout_p);
+static int varlen_forward_impl(const char* who, const VarlenCall& c) {
+    int causal = c.causal;
+    int64_t wl = c.window_left, wr = c.window_right;   // (window_canon rewrites the three)
+    int rc = varlen_check(who, c, c.total_k);
     if (rc != FA_OK) return rc;
-    if (heads_q >= 1 && (rc = score_check(who, sm, batch * heads_q)) != FA_OK) return rc;
-    if ((rc = sink_check(who, sk, heads_q, false)) != FA_OK) return rc;   // (indexed by query head)
-    if ((rc = window_canon(who, max_seqlen_q, max_seqlen_k, causal, window_left, window_right)) != FA_OK) return rc;
-    if (total_q == 0 || max_seqlen_q == 0) return FA_OK;   // no query row in any sequence
-    if (!q || !o || !lse || (total_k > 0 && (!k || !v))) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (total_k == 0 || max_seqlen_k == 0) {   // no key in any sequence: o = 0, lse = -inf (with sinks: the head's sink)
-        hipError_t e = hipMemsetAsync(o, 0, (size_t)total_q * heads_q * d * (dtype == FA_DTYPE_F32 ? 4 : 2), st);
-        if (e == hipSuccess && sk.sinks) e = fa::launch_ex_sink_fill(lse, sk.sinks, sk.heads, heads_q, total_q, st);
-        else if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lse), (int)0xFF800000u, (size_t)heads_q * total_q, st);
-        if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
-        return FA_OK;
-    }
-    fa::ExArgs a = varlen_args(cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype,
-                               q_stride, k_stride, v_stride, causal, window_left, window_right, softmax_scale, dropout_p, dropout_seed);
-    a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse;
-    score_args(a, sm);
-    sink_args(a, sk);
-    hipError_t e = fa::launch_ex(a, false, st);
-    if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
-    return FA_OK;
+    if (c.heads_q >= 1 && (rc = score_check(who, c.sm, c.batch * c.heads_q)) != FA_OK) return rc;
+    if ((rc = sink_check(who, c.sk, c.heads_q, false)) != FA_OK) return rc;   // (indexed by query head)
+    if ((rc = window_canon(who, c.max_seqlen_q, c.max_seqlen_k, causal, wl, wr)) != FA_OK) return rc;
+    if (c.total_q == 0 || c.max_seqlen_q == 0) return FA_OK;   // no query row in any sequence
+    if (!c.q || !c.o || !c.lse || (c.total_k > 0 && (!c.k || !c.v))) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+    if (c.total_k == 0 || c.max_seqlen_k == 0) return no_key_fill(who, c.o, c.lse, c.heads_q, c.total_q, c.d, c.dtype, c.sk, st);   // in any sequence
+    fa::ExArgs a = varlen_args(c, c.total_k, c.max_seqlen_k, causal, wl, wr);
+    return launched(who, fa::launch_ex(a, false, st));
+}
+
+// the leading arguments every forward of the family has
+static VarlenCall varlen_call(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
+                              const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k,
+                              int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                              int causal, int64_t window_left, int64_t window_right, double softmax_scale) {
+    VarlenCall c;
+    c.q = q; c.k = k; c.v = v; c.o = o; c.lse = lse; c.cu_seqlens_q = cu_seqlens_q; c.cu_seqlens_k = cu_seqlens_k;
+    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.total_q = total_q; c.total_k = total_k;
+    c.max_seqlen_q = max_seqlen_q; c.max_seqlen_k = max_seqlen_k; c.d = d; c.dtype = dtype; c.cache_dtype = dtype;
+    c.q_stride = q_stride; c.k_stride = k_stride; c.v_stride = v_stride;
+    c.causal = causal; c.window_left = window_left; c.window_right = window_right; c.softmax_scale = softmax_scale;
+    return c;
+}
+// ... and every backward, with its workspace
+static VarlenCall varlen_bwd_call(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
+                                  void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q,
+                                  int64_t heads_kv,
+                                  int64_t total_q, int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype,
+                                  int64_t q_stride,
+                                  int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
+                                  double softmax_scale, void* workspace,
+                                  size_t workspace_bytes) {
+    VarlenCall c = varlen_call(q, k, v, const_cast<void*>(o), const_cast<float*>(lse), cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv,
+                               total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride, causal, window_left,
+                               window_right, softmax_scale);
+    c.do_ = do_; c.dq = dq; c.dk = dk; c.dv = dv; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    return c;
 }
 
 int fa_ex_forward_varlen(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
                          const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k,
-                         int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride,
-                         int64_t v_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale, double dropout_p,
-                         uint64_t dropout_seed, void* stream) {
-    return varlen_forward_impl("fa_ex_forward_varlen", q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q,
-                               total_k, max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride, causal, window_left,
-                               window_right, softmax_scale, dropout_p, dropout_seed, stream, ScoreMod());
+                         int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                         int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                         double dropout_p, uint64_t dropout_seed, void* stream) {
+    VarlenCall c = varlen_call(q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k,
+                               d, dtype, q_stride, k_stride, v_stride, causal, window_left, window_right, softmax_scale);
+    c.dropout_p = dropout_p; c.dropout_seed = dropout_seed; c.stream = stream;
+    return varlen_forward_impl("fa_ex_forward_varlen", c);
 }
 
 int fa_ex_forward_varlen_scoremod(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
-                                  const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
-                                  int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
-                                  int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
-                                  double softmax_scale, double softcap, const float* alibi_slopes, int64_t alibi_batch_stride,
-                                  double dropout_p, uint64_t dropout_seed, void* stream) {
-    ScoreMod sm;
-    sm.softcap = softcap; sm.alibi = alibi_slopes; sm.heads = heads_q; sm.bstride = alibi_batch_stride;
-    return varlen_forward_impl("fa_ex_forward_varlen_scoremod", q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv,
-                               total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride, causal, window_left,
-                               window_right, softmax_scale, dropout_p, dropout_seed, stream, sm);
+                                  const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k,
+                                  int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride,
+                                  int64_t v_stride,
+                                  int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                                  double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, double dropout_p,
+                                  uint64_t dropout_seed, void* stream) {
+    VarlenCall c = varlen_call(q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k,
+                               d, dtype, q_stride, k_stride, v_stride, causal, window_left, window_right, softmax_scale);
+    c.dropout_p = dropout_p; c.dropout_seed = dropout_seed; c.stream = stream;
+    c.sm = {softcap, alibi_slopes, heads_q, alibi_batch_stride};
+    return varlen_forward_impl("fa_ex_forward_varlen_scoremod", c);
+}
+
+int fa_ex_forward_varlen_sink(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
+                              const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k,
+                              int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                              int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                              double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, const float* sinks,
+                              int64_t sink_heads, double dropout_p, uint64_t dropout_seed, void* stream) {
+    VarlenCall c = varlen_call(q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k,
+                               d, dtype, q_stride, k_stride, v_stride, causal, window_left, window_right, softmax_scale);
+    c.dropout_p = dropout_p; c.dropout_seed = dropout_seed; c.stream = stream;
+    c.sm = {softcap, alibi_slopes, heads_q, alibi_batch_stride};
+    c.sk = {sinks, sink_heads, nullptr};
+    return varlen_forward_impl("fa_ex_forward_varlen_sink", c);
 }
 
 size_t fa_ex_backward_workspace_bytes_varlen(int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t d, int dtype) {
@@ -736,243 +840,183 @@ size_t fa_ex_backward_workspace_bytes_varlen(int64_t heads_q, int64_t heads_kv, 
     return need;
 }
 
-static int varlen_backward_impl(const char* who, const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse,
-                                void* dq, void* dk, void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch,
-                                int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q,
-                                int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride, int causal,
-                                int64_t window_left, int64_t window_right, double softmax_scale, double dropout_p, uint64_t dropout_seed,
-                                void* workspace, size_t workspace_bytes, void* stream, const ScoreMod& sm,
-                                const SinkArg& sk = SinkArg()) {
-    int rc = varlen_check(who, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype,
-                          q_stride, k_stride, v_stride, window_left, window_right, softmax_scale, dropout_p);
+static int varlen_backward_impl(const char* who, const VarlenCall& c) {
+    int causal = c.causal;
+    int64_t wl = c.window_left, wr = c.window_right;   // (window_canon rewrites the three)
+    int rc = varlen_check(who, c, c.total_k);
     if (rc != FA_OK) return rc;
-    if (heads_q >= 1 && (rc = score_check(who, sm, batch * heads_q)) != FA_OK) return rc;
-    if ((rc = sink_check(who, sk, heads_q, true)) != FA_OK) return rc;
-    if ((rc = window_canon(who, max_seqlen_q, max_seqlen_k, causal, window_left, window_right)) != FA_OK) return rc;
-    const bool no_q = total_q == 0 || max_seqlen_q == 0, no_k = total_k == 0 || max_seqlen_k == 0;
-    if (sk.sinks && (no_q || no_k)) {   // no row, or rows with o = 0 (delta = 0): the sink's gradient is 0
-        hipError_t e = hipMemsetAsync(sk.dsinks, 0, (size_t)sk.heads * 4, reinterpret_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
-    }
-    if (no_q && no_k) return FA_OK;
-    if (no_q || no_k) {   // one side empty in every sequence: the gradients of the other side are sums over nothing
-        const size_t es = dtype == FA_DTYPE_F32 ? 4 : 2;
-        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-        hipError_t e = hipSuccess;
-        if (no_q) {
-            if (!dk || !dv) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
-            e = hipMemsetAsync(dk, 0, (size_t)total_k * heads_kv * d * es, st);
-            if (e == hipSuccess) e = hipMemsetAsync(dv, 0, (size_t)total_k * heads_kv * d * es, st);
-        } else {
-            if (!dq) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
-            e = hipMemsetAsync(dq, 0, (size_t)total_q * heads_q * d * es, st);
-        }
-        if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
-        return FA_OK;
-    }
-    if (!q || !k || !v || !o || !do_ || !lse || !dq || !dk || !dv) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
-    const size_t need = fa_ex_backward_workspace_bytes_varlen(heads_q, heads_kv, total_q, total_k, d, dtype);
-    if (!workspace || workspace_bytes < need)
-        return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
-    fa::ExArgs a = varlen_args(cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype,
-                               q_stride, k_stride, v_stride, causal, window_left, window_right, softmax_scale, dropout_p, dropout_seed);
-    a.q = q; a.k = k; a.v = v; a.o = const_cast<void*>(o); a.lse = const_cast<float*>(lse); a.dout = do_;
-    a.dq = dq; a.dk = dk; a.dv = dv;
-    a.workspace = workspace;
-    a.workspace_bytes = workspace_bytes;
-    score_args(a, sm);
-    sink_args(a, sk);
-    hipError_t e = fa::launch_ex(a, true, reinterpret_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
-    return FA_OK;
+    if (c.heads_q >= 1 && (rc = score_check(who, c.sm, c.batch * c.heads_q)) != FA_OK) return rc;
+    if ((rc = sink_check(who, c.sk, c.heads_q, true)) != FA_OK) return rc;
+    if ((rc = window_canon(who, c.max_seqlen_q, c.max_seqlen_k, causal, wl, wr)) != FA_OK) return rc;
+    const bool no_q = c.total_q == 0 || c.max_seqlen_q == 0, no_k = c.total_k == 0 || c.max_seqlen_k == 0;
+    const size_t es = c.dtype == FA_DTYPE_F32 ? 4 : 2;
+    if (no_q || no_k)   // ... in every sequence
+        return empty_backward(who, no_q && no_k, no_q, c.dq, (size_t)c.total_q * c.heads_q * c.d * es, c.dk, c.dv,
+                              (size_t)c.total_k * c.heads_kv * c.d * es, c.sk, reinterpret_cast<hipStream_t>(c.stream));
+    if (!c.q || !c.k || !c.v || !c.o || !c.do_ || !c.lse || !c.dq || !c.dk || !c.dv)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    const size_t need = fa_ex_backward_workspace_bytes_varlen(c.heads_q, c.heads_kv, c.total_q, c.total_k, c.d, c.dtype);
+    if (!c.workspace || c.workspace_bytes < need)
+        return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, need, c.workspace_bytes);
+    fa::ExArgs a = varlen_args(c, c.total_k, c.max_seqlen_k, causal, wl, wr);
+    return launched(who, fa::launch_ex(a, true, reinterpret_cast<hipStream_t>(c.stream)));
 }
 
 int fa_ex_backward_varlen(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
-                          void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q,
-                          int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d,
-                          int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride, int causal, int64_t window_left,
-                          int64_t window_right, double softmax_scale, double dropout_p, uint64_t dropout_seed, void* workspace,
-                          size_t workspace_bytes, void* stream) {
-    return varlen_backward_impl("fa_ex_backward_varlen", q, k, v, o, do_, lse, dq, dk, dv, cu_seqlens_q, cu_seqlens_k, batch, heads_q,
-                                heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride, causal,
-                                window_left, window_right, softmax_scale, dropout_p, dropout_seed, workspace, workspace_bytes, stream,
-                                ScoreMod());
+                          void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                          int64_t total_q, int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
+                          int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                          double dropout_p, uint64_t dropout_seed, void* workspace, size_t workspace_bytes, void* stream) {
+    VarlenCall c = varlen_bwd_call(q, k, v, o, do_, lse, dq, dk, dv, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k,
+                                   max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride, causal, window_left, window_right,
+                                   softmax_scale, workspace, workspace_bytes);
+    c.dropout_p = dropout_p; c.dropout_seed = dropout_seed; c.stream = stream;
+    return varlen_backward_impl("fa_ex_backward_varlen", c);
 }
 
-int fa_ex_backward_varlen_scoremod(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq,
-                                   void* dk, void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch,
-                                   int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q,
-                                   int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride,
-                                   int causal, int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
-                                   const float* alibi_slopes, int64_t alibi_batch_stride, double dropout_p, uint64_t dropout_seed,
-                                   void* workspace, size_t workspace_bytes, void* stream) {
-    ScoreMod sm;
-    sm.softcap = softcap; sm.alibi = alibi_slopes; sm.heads = heads_q; sm.bstride = alibi_batch_stride;
-    return varlen_backward_impl("fa_ex_backward_varlen_scoremod", q, k, v, o, do_, lse, dq, dk, dv, cu_seqlens_q, cu_seqlens_k, batch,
-                                heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride,
-                                causal, window_left, window_right, softmax_scale, dropout_p, dropout_seed, workspace, workspace_bytes,
-                                stream, sm);
+int fa_ex_backward_varlen_scoremod(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
+                                   void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q,
+                                   int64_t heads_kv,
+                                   int64_t total_q, int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype,
+                                   int64_t q_stride,
+                                   int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                                   double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, double dropout_p,
+                                   uint64_t dropout_seed, void* workspace, size_t workspace_bytes, void* stream) {
+    VarlenCall c = varlen_bwd_call(q, k, v, o, do_, lse, dq, dk, dv, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k,
+                                   max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride, causal, window_left, window_right,
+                                   softmax_scale, workspace, workspace_bytes);
+    c.dropout_p = dropout_p; c.dropout_seed = dropout_seed; c.stream = stream;
+    c.sm = {softcap, alibi_slopes, heads_q, alibi_batch_stride};
+    return varlen_backward_impl("fa_ex_backward_varlen_scoremod", c);
 }
 
-int fa_ex_forward_varlen_sink(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
-                              const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
-                              int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
-                              int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
-                              double softmax_scale, double softcap, const float* alibi_slopes, int64_t alibi_batch_stride,
-                              const float* sinks, int64_t sink_heads, double dropout_p, uint64_t dropout_seed, void* stream) {
-    ScoreMod sm;
-    sm.softcap = softcap; sm.alibi = alibi_slopes; sm.heads = heads_q; sm.bstride = alibi_batch_stride;
-    SinkArg sk;
-    sk.sinks = sinks; sk.heads = sink_heads;
-    return varlen_forward_impl("fa_ex_forward_varlen_sink", q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q,
-                               total_k, max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride, causal, window_left,
-                               window_right, softmax_scale, dropout_p, dropout_seed, stream, sm, sk);
-}
-
-int fa_ex_backward_varlen_sink(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq,
-                               void* dk, void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch,
-                               int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q,
-                               int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride,
-                               int causal, int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
-                               const float* alibi_slopes, int64_t alibi_batch_stride, const float* sinks, int64_t sink_heads,
-                               float* dsinks, double dropout_p, uint64_t dropout_seed, void* workspace, size_t workspace_bytes,
-                               void* stream) {
-    ScoreMod sm;
-    sm.softcap = softcap; sm.alibi = alibi_slopes; sm.heads = heads_q; sm.bstride = alibi_batch_stride;
-    SinkArg sk;
-    sk.sinks = sinks; sk.heads = sink_heads; sk.dsinks = dsinks;
-    return varlen_backward_impl("fa_ex_backward_varlen_sink", q, k, v, o, do_, lse, dq, dk, dv, cu_seqlens_q, cu_seqlens_k, batch, heads_q,
-                                heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride, causal,
-                                window_left, window_right, softmax_scale, dropout_p, dropout_seed, workspace, workspace_bytes, stream, sm,
-                                sk);
+int fa_ex_backward_varlen_sink(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
+                               void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                               int64_t total_q, int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
+                               int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                               double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, const float* sinks,
+                               int64_t sink_heads, float* dsinks, double dropout_p, uint64_t dropout_seed, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    VarlenCall c = varlen_bwd_call(q, k, v, o, do_, lse, dq, dk, dv, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k,
+                                   max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride, causal, window_left, window_right,
+                                   softmax_scale, workspace, workspace_bytes);
+    c.dropout_p = dropout_p; c.dropout_seed = dropout_seed; c.stream = stream;
+    c.sm = {softcap, alibi_slopes, heads_q, alibi_batch_stride};
+    c.sk = {sinks, sink_heads, dsinks};
+    return varlen_backward_impl("fa_ex_backward_varlen_sink", c);
 }
 
 // ---- the varlen forward over a paged K/V cache: see include/fa_mi355x.h
-// One body under both entry points: the last four parameters are the ones fa_ex_forward_varlen_paged_fp8 adds (cache_dtype = dtype,
-// null, null, 0 is fa_ex_forward_varlen_paged: none of the e4m3 checks below can fire and the launch is the one it was).
-static int varlen_paged_impl(const char* who, const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
-                             const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
-                             int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
-                             int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
-                             double softmax_scale, double softcap, const float* alibi_slopes, int64_t alibi_batch_stride,
-                             const float* sinks, int64_t sink_heads, const int32_t* block_table, int64_t max_blocks_per_seq,
-                             int64_t num_blocks, int64_t page_block_size, int64_t k_page_stride, int64_t v_page_stride,
-                             void* stream, int cache_dtype, const float* k_descale, const float* v_descale,
-                             int64_t descale_batch_stride) {
-    (void)total_k;   // a pool has no token count: the keys of a sequence are found through the table
+// One body under both entry points: fa_ex_forward_varlen_paged leaves cache_dtype = dtype and the scales absent, so none of the e4m3
+// checks below can fire and the launch is the one it was.
+static int varlen_paged_impl(const char* who, const VarlenCall& c) {
+    int causal = c.causal;
+    int64_t wl = c.window_left, wr = c.window_right;   // (window_canon rewrites the three)
+    // (a pool has no token count: total_k is not read, the keys of a sequence are found through the table)
     // the pool's element type: q's, or e4m3 with a dequantisation scale per (sequence, K/V head): the checks of fa_ex_forward_kvcache_fp8
-    const bool e4m3 = cache_dtype == FA_DTYPE_E4M3;
-    if (cache_dtype != dtype && !e4m3)
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_dtype must be dtype (code %d) or FA_DTYPE_E4M3 (got code %d)", who, dtype,
-                    cache_dtype);
-    if (e4m3 && dtype != FA_DTYPE_F16 && dtype != FA_DTYPE_BF16)
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: dtype must be f16 or bf16 with an e4m3 pool (got code %d)", who, dtype);
-    if (!e4m3 && (k_descale || v_descale))
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_descale / v_descale need an e4m3 pool (cache_dtype is code %d)", who, cache_dtype);
-    if (!e4m3 && descale_batch_stride != 0)
+    const bool e4m3 = c.cache_dtype == FA_DTYPE_E4M3;
+    if (c.cache_dtype != c.dtype && !e4m3)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_dtype must be dtype (code %d) or FA_DTYPE_E4M3 (got code %d)", who, c.dtype,
+                    c.cache_dtype);
+    if (e4m3 && c.dtype != FA_DTYPE_F16 && c.dtype != FA_DTYPE_BF16)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: dtype must be f16 or bf16 with an e4m3 pool (got code %d)", who, c.dtype);
+    if (!e4m3 && (c.k_descale || c.v_descale))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_descale / v_descale need an e4m3 pool (cache_dtype is code %d)", who, c.cache_dtype);
+    if (!e4m3 && c.descale_batch_stride != 0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: descale_batch_stride must be 0 with a 16-bit pool (got %lld)", who,
-                    (long long)descale_batch_stride);
-    if (descale_batch_stride < 0 || (descale_batch_stride != 0 && (descale_batch_stride < heads_kv || descale_batch_stride > ((int64_t)1 << 40))))
+                    (long long)c.descale_batch_stride);
+    if (c.descale_batch_stride < 0 || (c.descale_batch_stride != 0 && (c.descale_batch_stride < c.heads_kv ||
+        c.descale_batch_stride > ((int64_t)1 << 40))))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: descale_batch_stride=%lld must be 0 or >= heads_kv=%lld (and <= 2^40)", who,
-                    (long long)descale_batch_stride, (long long)heads_kv);
-    if ((uintptr_t)k_descale % 4 != 0 || (uintptr_t)v_descale % 4 != 0)
+                    (long long)c.descale_batch_stride, (long long)c.heads_kv);
+    if ((uintptr_t)c.k_descale % 4 != 0 || (uintptr_t)c.v_descale % 4 != 0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_descale and v_descale must be 4-byte aligned", who);
     if (e4m3) {   // an 8-element chunk of an e4m3 pool is 8 bytes: loads of 4 and 8 bytes
-        if (d < 8 || d % 8 != 0)
-            return fail(FA_ERR_INVALID_ARGUMENT, "%s: head_dim must be a multiple of 8 with an e4m3 pool (got %lld)", who, (long long)d);
-        if ((uintptr_t)k % 8 != 0 || (uintptr_t)v % 8 != 0)
+        if (c.d < 8 || c.d % 8 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: head_dim must be a multiple of 8 with an e4m3 pool (got %lld)", who, (long long)c.d);
+        if ((uintptr_t)c.k % 8 != 0 || (uintptr_t)c.v % 8 != 0)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: an e4m3 k / v pool must be 8-byte aligned", who);
-        if (k_stride % 8 != 0 || v_stride % 8 != 0 || k_page_stride % 8 != 0 || v_page_stride % 8 != 0)
+        if (c.k_stride % 8 != 0 || c.v_stride % 8 != 0 || c.k_page_stride % 8 != 0 || c.v_page_stride % 8 != 0)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of an e4m3 pool must be multiples of 8 elements", who);
     }
-    ScoreMod sm;
-    sm.softcap = softcap; sm.alibi = alibi_slopes; sm.heads = heads_q; sm.bstride = alibi_batch_stride;
-    SinkArg sk;
-    sk.sinks = sinks; sk.heads = sink_heads;
-    if (!block_table) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null block_table", who);
-    if ((uintptr_t)block_table % 4 != 0 || (uintptr_t)cu_seqlens_k % 4 != 0)
+    if (!c.block_table) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null block_table", who);
+    if ((uintptr_t)c.block_table % 4 != 0 || (uintptr_t)c.cu_seqlens_k % 4 != 0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: block_table and cu_seqlens_k must be 4-byte aligned", who);
-    if (page_block_size < 16 || page_block_size % 16 != 0)
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: page_block_size must be a positive multiple of 16 (got %lld)", who, (long long)page_block_size);
-    if (num_blocks < 0 || max_blocks_per_seq < 0)
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_blocks=%lld and max_blocks_per_seq=%lld must be >= 0", who, (long long)num_blocks,
-                    (long long)max_blocks_per_seq);
+    if (c.page_block_size < 16 || c.page_block_size % 16 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: page_block_size must be a positive multiple of 16 (got %lld)", who, (long long)c.page_block_size);
+    if (c.num_blocks < 0 || c.max_blocks_per_seq < 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_blocks=%lld and max_blocks_per_seq=%lld must be >= 0", who, (long long)c.num_blocks,
+                    (long long)c.max_blocks_per_seq);
     // (the token strides against heads_kv * d, cu_seqlens_k against null with a key to read: total_k stands in as 1)
-    int rc = varlen_check(who, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, 1, max_seqlen_q, max_seqlen_k, d, dtype,
-                          q_stride, k_stride, v_stride, window_left, window_right, softmax_scale, 0.0);
+    int rc = varlen_check(who, c, 1);
     if (rc != FA_OK) return rc;
-    const int64_t page_span = (page_block_size - 1) * (k_stride > v_stride ? k_stride : v_stride) + heads_kv * d;
-    if (num_blocks > 1 && (k_page_stride < (page_block_size - 1) * k_stride + heads_kv * d ||
-                           v_page_stride < (page_block_size - 1) * v_stride + heads_kv * d))
+    const int64_t page_span = (c.page_block_size - 1) * (c.k_stride > c.v_stride ? c.k_stride : c.v_stride) + c.heads_kv * c.d;
+    if (c.num_blocks > 1 && (c.k_page_stride < (c.page_block_size - 1) * c.k_stride + c.heads_kv * c.d ||
+                           c.v_page_stride < (c.page_block_size - 1) * c.v_stride + c.heads_kv * c.d))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: page strides (%lld, %lld) must span a page of %lld tokens at token strides (%lld, %lld)",
-                    who, (long long)k_page_stride, (long long)v_page_stride, (long long)page_block_size, (long long)k_stride,
-                    (long long)v_stride);
-    if (k_page_stride < 0 || v_page_stride < 0)
+                    who, (long long)c.k_page_stride, (long long)c.v_page_stride, (long long)c.page_block_size, (long long)c.k_stride,
+                    (long long)c.v_stride);
+    if (c.k_page_stride < 0 || c.v_page_stride < 0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: page strides must be >= 0", who);
-    if ((rc = score_check(who, sm, batch * heads_q)) != FA_OK) return rc;
-    if ((rc = sink_check(who, sk, heads_q, false)) != FA_OK) return rc;
-    if (page_block_size > 65536 || page_span * (e4m3 ? 1 : dtype == FA_DTYPE_F32 ? 4 : 2) >= ((int64_t)1 << 31) || num_blocks >= ((int64_t)1 << 31) ||
-        max_blocks_per_seq >= ((int64_t)1 << 31) || batch * max_blocks_per_seq >= ((int64_t)1 << 40))
+    if ((rc = score_check(who, c.sm, c.batch * c.heads_q)) != FA_OK) return rc;
+    if ((rc = sink_check(who, c.sk, c.heads_q, false)) != FA_OK) return rc;
+    if (c.page_block_size > 65536 || page_span * (e4m3 ? 1 : c.dtype == FA_DTYPE_F32 ? 4 : 2) >= ((int64_t)1 << 31) ||
+        c.num_blocks >= ((int64_t)1 << 31) ||
+        c.max_blocks_per_seq >= ((int64_t)1 << 31) || c.batch * c.max_blocks_per_seq >= ((int64_t)1 << 40))
         return fail(FA_ERR_UNSUPPORTED, "%s: a page above 65536 tokens or 2^31 bytes, or a table too large", who);
     // the window against the same (max_seqlen_q, max_seqlen_k) as the packed call on the gathered tokens
-    if ((rc = window_canon(who, max_seqlen_q, max_seqlen_k, causal, window_left, window_right)) != FA_OK) return rc;
-    if (total_q == 0 || max_seqlen_q == 0) return FA_OK;
-    const int64_t capacity = max_blocks_per_seq * page_block_size;
-    const int64_t cap = max_seqlen_k < capacity ? max_seqlen_k : capacity;   // a sequence's keys: [0, cap]
-    if (!q || !o || !lse || (cap > 0 && num_blocks > 0 && (!k || !v))) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (cap == 0) {   // no key in any sequence: o = 0, lse = -inf (with sinks: the head's sink), as the packed call
-        hipError_t e = hipMemsetAsync(o, 0, (size_t)total_q * heads_q * d * (dtype == FA_DTYPE_F32 ? 4 : 2), st);
-        if (e == hipSuccess && sk.sinks) e = fa::launch_ex_sink_fill(lse, sk.sinks, sk.heads, heads_q, total_q, st);
-        else if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lse), (int)0xFF800000u, (size_t)heads_q * total_q, st);
-        if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
-        return FA_OK;
-    }
-    fa::ExArgs a = varlen_args(cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, 0, max_seqlen_q, cap, d, dtype, q_stride,
-                               k_stride, v_stride, causal, window_left, window_right, softmax_scale, 0.0, 0);
-    a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse;
-    score_args(a, sm);
-    sink_args(a, sk);
-    a.block_table = block_table;
-    a.max_blocks = max_blocks_per_seq;
-    a.num_blocks = num_blocks;
-    a.page_size = page_block_size;
-    a.page_stride_k = k_page_stride;
-    a.page_stride_v = v_page_stride;
-    a.kv_e4m3 = e4m3 ? 1 : 0; a.k_descale = k_descale; a.v_descale = v_descale; a.descale_bstride = descale_batch_stride;
-    hipError_t e = fa::launch_ex(a, false, st);
-    if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
-    return FA_OK;
+    if ((rc = window_canon(who, c.max_seqlen_q, c.max_seqlen_k, causal, wl, wr)) != FA_OK) return rc;
+    if (c.total_q == 0 || c.max_seqlen_q == 0) return FA_OK;
+    const int64_t capacity = c.max_blocks_per_seq * c.page_block_size;
+    const int64_t cap = c.max_seqlen_k < capacity ? c.max_seqlen_k : capacity;   // a sequence's keys: [0, cap]
+    if (!c.q || !c.o || !c.lse || (cap > 0 && c.num_blocks > 0 && (!c.k || !c.v)))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+    if (cap == 0) return no_key_fill(who, c.o, c.lse, c.heads_q, c.total_q, c.d, c.dtype, c.sk, st);   // in any sequence, as the packed call
+    fa::ExArgs a = varlen_args(c, 0, cap, causal, wl, wr);
+    a.block_table = c.block_table;
+    a.max_blocks = c.max_blocks_per_seq;
+    a.num_blocks = c.num_blocks;
+    a.page_size = c.page_block_size;
+    a.page_stride_k = c.k_page_stride;
+    a.page_stride_v = c.v_page_stride;
+    a.kv_e4m3 = e4m3 ? 1 : 0; a.k_descale = c.k_descale; a.v_descale = c.v_descale; a.descale_bstride = c.descale_batch_stride;
+    return launched(who, fa::launch_ex(a, false, st));
 }
 
 int fa_ex_forward_varlen_paged(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
-                               const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
-                               int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
-                               int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
-                               double softmax_scale, double softcap, const float* alibi_slopes, int64_t alibi_batch_stride,
-                               const float* sinks, int64_t sink_heads, const int32_t* block_table, int64_t max_blocks_per_seq,
-                               int64_t num_blocks, int64_t page_block_size, int64_t k_page_stride, int64_t v_page_stride,
-                               void* stream) {
-    return varlen_paged_impl("fa_ex_forward_varlen_paged", q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q,
-                             total_k, max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride, causal, window_left, window_right,
-                             softmax_scale, softcap, alibi_slopes, alibi_batch_stride, sinks, sink_heads, block_table, max_blocks_per_seq,
-                             num_blocks, page_block_size, k_page_stride, v_page_stride, stream, dtype, nullptr, nullptr, 0);
+                               const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k,
+                               int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                               int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                               double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, const float* sinks, int64_t sink_heads,
+                               const int32_t* block_table, int64_t max_blocks_per_seq,
+                               int64_t num_blocks, int64_t page_block_size, int64_t k_page_stride, int64_t v_page_stride, void* stream) {
+    VarlenCall c = varlen_call(q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k,
+                               d, dtype, q_stride, k_stride, v_stride, causal, window_left, window_right, softmax_scale);
+    c.sm = {softcap, alibi_slopes, heads_q, alibi_batch_stride};
+    c.sk = {sinks, sink_heads, nullptr};
+    c.block_table = block_table; c.max_blocks_per_seq = max_blocks_per_seq; c.num_blocks = num_blocks; c.page_block_size = page_block_size;
+    c.k_page_stride = k_page_stride; c.v_page_stride = v_page_stride; c.stream = stream;
+    return varlen_paged_impl("fa_ex_forward_varlen_paged", c);
 }
 
 int fa_ex_forward_varlen_paged_fp8(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
-                                   const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
-                                   int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
-                                   int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
-                                   double softmax_scale, double softcap, const float* alibi_slopes, int64_t alibi_batch_stride,
-                                   const float* sinks, int64_t sink_heads, const int32_t* block_table, int64_t max_blocks_per_seq,
-                                   int64_t num_blocks, int64_t page_block_size, int64_t k_page_stride, int64_t v_page_stride,
-                                   int cache_dtype, const float* k_descale, const float* v_descale, int64_t descale_batch_stride,
-                                   void* stream) {
-    return varlen_paged_impl("fa_ex_forward_varlen_paged_fp8", q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv,
-                             total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride, causal, window_left,
-                             window_right, softmax_scale, softcap, alibi_slopes, alibi_batch_stride, sinks, sink_heads, block_table,
-                             max_blocks_per_seq, num_blocks, page_block_size, k_page_stride, v_page_stride, stream, cache_dtype, k_descale,
-                             v_descale, descale_batch_stride);
+                                   const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k,
+                                   int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride,
+                                   int64_t v_stride,
+                                   int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                                   double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, const float* sinks, int64_t sink_heads,
+                                   const int32_t* block_table, int64_t max_blocks_per_seq,
+                                   int64_t num_blocks, int64_t page_block_size, int64_t k_page_stride, int64_t v_page_stride, int cache_dtype,
+                                   const float* k_descale, const float* v_descale, int64_t descale_batch_stride, void* stream) {
+    VarlenCall c = varlen_call(q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k,
+                               d, dtype, q_stride, k_stride, v_stride, causal, window_left, window_right, softmax_scale);
+    c.sm = {softcap, alibi_slopes, heads_q, alibi_batch_stride};
+    c.sk = {sinks, sink_heads, nullptr};
+    c.block_table = block_table; c.max_blocks_per_seq = max_blocks_per_seq; c.num_blocks = num_blocks; c.page_block_size = page_block_size;
+    c.k_page_stride = k_page_stride; c.v_page_stride = v_page_stride; c.stream = stream;
+    c.cache_dtype = cache_dtype; c.k_descale = k_descale; c.v_descale = v_descale; c.descale_batch_stride = descale_batch_stride;
+    return varlen_paged_impl("fa_ex_forward_varlen_paged_fp8", c);
 }
 
 // ---- KV-cache decoding with split-KV: see include/fa_mi355x.h
@@ -981,20 +1025,22 @@ static int64_t kv_splits(int64_t batch, int64_t hq, int64_t hkv, int64_t nq, int
     return fa::kv_num_splits(batch, hkv, ((hq / hkv) * nq + 15) / 16, cache_len);
 }
 
+// the arguments of the three workspace queries (seqlen_q: max_seqlen_q of the packed one); a bad one makes the answer 0
+static bool kv_ws_args_ok(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t d, int64_t num_splits) {
+    return batch > 0 && heads_q > 0 && heads_kv > 0 && heads_q % heads_kv == 0 && seqlen_q > 0 && d > 0 && cache_len >= 0 && num_splits >= 0 &&
+           num_splits <= 256;
+}
+
 size_t fa_ex_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t d,
                                      int64_t num_splits) {
-    if (batch <= 0 || heads_q <= 0 || heads_kv <= 0 || heads_q % heads_kv != 0 || seqlen_q <= 0 || d <= 0 || cache_len < 0 ||
-        num_splits < 0 || num_splits > 256)
-        return 0;
+    if (!kv_ws_args_ok(batch, heads_q, heads_kv, seqlen_q, cache_len, d, num_splits)) return 0;
     return fa::kv_workspace_bytes(batch, heads_q, seqlen_q, d, (int)kv_splits(batch, heads_q, heads_kv, seqlen_q, cache_len, num_splits));
 }
 
 // a sink call always runs the combine: at least two splits
 size_t fa_ex_kvcache_workspace_bytes_sink(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t d,
                                           int64_t num_splits) {
-    if (batch <= 0 || heads_q <= 0 || heads_kv <= 0 || heads_q % heads_kv != 0 || seqlen_q <= 0 || d <= 0 || cache_len < 0 ||
-        num_splits < 0 || num_splits > 256)
-        return 0;
+    if (!kv_ws_args_ok(batch, heads_q, heads_kv, seqlen_q, cache_len, d, num_splits)) return 0;
     const int64_t S = kv_splits(batch, heads_q, heads_kv, seqlen_q, cache_len, num_splits);
     return fa::kv_workspace_bytes(batch, heads_q, seqlen_q, d, (int)(S < 2 ? 2 : S));
 }
@@ -1002,125 +1048,138 @@ size_t fa_ex_kvcache_workspace_bytes_sink(int64_t batch, int64_t heads_q, int64_
 // packed queries: S from max_seqlen_q's row tiles (shapes only), partials for total_q tokens; with_sinks: at least two splits
 size_t fa_ex_kvcache_workspace_bytes_varlen(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t max_seqlen_q,
                                             int64_t cache_len, int64_t d, int64_t num_splits, int with_sinks) {
-    if (batch <= 0 || heads_q <= 0 || heads_kv <= 0 || heads_q % heads_kv != 0 || total_q <= 0 || max_seqlen_q <= 0 ||
-        max_seqlen_q > total_q || d <= 0 || cache_len < 0 || num_splits < 0 || num_splits > 256)
-        return 0;
+    if (!kv_ws_args_ok(batch, heads_q, heads_kv, max_seqlen_q, cache_len, d, num_splits) || max_seqlen_q > total_q) return 0;
     const int64_t S = kv_splits(batch, heads_q, heads_kv, max_seqlen_q, cache_len, num_splits);
     return fa::kv_workspace_bytes(1, heads_q, total_q, d, (int)(with_sinks && S < 2 ? 2 : S));
 }
 
-// who: the entry point's name.  After stream come the eight arguments fa_ex_forward_kvcache_paged adds (all null / 0 is
-// fa_ex_forward_kvcache), then the seven fa_ex_forward_kvcache_rotary adds (all null / 0 is fa_ex_forward_kvcache_paged), then the
-// four fa_ex_forward_kvcache_fp8 adds (cache_dtype = dtype, null, null, 0 is fa_ex_forward_kvcache_rotary), then the two
-// fa_ex_forward_kvcache_sink adds (null sinks is fa_ex_forward_kvcache_fp8), then the five fa_ex_forward_kvcache_varlen adds
-// (null, null, 0, 0, 0 is fa_ex_forward_kvcache_sink).
-static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
-                        const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
-                        int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
-                        int64_t q_token_stride, int64_t k_cache_batch_stride, int64_t k_cache_token_stride, int64_t v_cache_batch_stride,
-                        int64_t v_cache_token_stride, int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t v_new_batch_stride,
-                        int64_t v_new_token_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
-                        double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, void* workspace,
-                        size_t workspace_bytes, void* stream, const int32_t* block_table, int64_t block_table_row_stride,
-                        int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq, const int32_t* cache_batch_idx,
-                        int64_t cache_batch, const int32_t* cache_leftpad, const void* rotary_cos, const void* rotary_sin,
-                        int64_t rotary_cos_row_stride, int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim,
-                        int rotary_interleaved, int cache_dtype, const float* k_descale, const float* v_descale,
-                        int64_t descale_batch_stride, const float* sinks = nullptr, int64_t sink_heads = 1,
-                        const int32_t* cu_seqlens_q = nullptr, const int32_t* cu_seqlens_k_new = nullptr, int64_t total_q = 0,
-                        int64_t max_seqlen_q = 0, int64_t total_k_new = 0) {
-    if (dtype != FA_DTYPE_F16 && dtype != FA_DTYPE_BF16)
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: dtype must be f16 or bf16 (got code %d)", who, dtype);
+// One call of the fa_ex_forward_kvcache* family, a field per argument of the widest entry point under its name in the header.
+// Defaults: "argument absent", which is 0 / null but for sink_heads (1) and cache_dtype (kv_call sets it to dtype).
+struct KvCall {
+    const void *q = nullptr, *k_new = nullptr, *v_new = nullptr;
+    void *k_cache = nullptr, *v_cache = nullptr, *o = nullptr;
+    const int32_t* cache_seqlens = nullptr;
+    float* lse = nullptr;
+    int64_t batch = 0, heads_q = 0, heads_kv = 0, seqlen_q = 0, seqlen_new = 0, cache_len = 0, d = 0;
+    int64_t q_batch_stride = 0, q_token_stride = 0, k_cache_batch_stride = 0, k_cache_token_stride = 0, v_cache_batch_stride = 0,
+            v_cache_token_stride = 0, k_new_batch_stride = 0, k_new_token_stride = 0, v_new_batch_stride = 0, v_new_token_stride = 0;
+    int dtype = 0, causal = 0;
+    int64_t window_left = -1, window_right = -1, alibi_batch_stride = 0, num_splits = 0;
+    double softmax_scale = 0.0, softcap = 0.0;
+    const float* alibi_slopes = nullptr;
+    void *workspace = nullptr, *stream = nullptr;
+    size_t workspace_bytes = 0;
+    // fa_ex_forward_kvcache_paged adds
+    const int32_t *block_table = nullptr, *cache_batch_idx = nullptr, *cache_leftpad = nullptr;
+    int64_t block_table_row_stride = 0, num_blocks = 0, page_block_size = 0, max_blocks_per_seq = 0, cache_batch = 0;
+    // _rotary
+    const void *rotary_cos = nullptr, *rotary_sin = nullptr;
+    int64_t rotary_cos_row_stride = 0, rotary_sin_row_stride = 0, seqlen_ro = 0, rotary_dim = 0;
+    int rotary_interleaved = 0;
+    // _fp8
+    int cache_dtype = 0;
+    const float *k_descale = nullptr, *v_descale = nullptr;
+    int64_t descale_batch_stride = 0;
+    // _sink
+    const float* sinks = nullptr;
+    int64_t sink_heads = 1;
+    // _varlen
+    const int32_t *cu_seqlens_q = nullptr, *cu_seqlens_k_new = nullptr;
+    int64_t total_q = 0, max_seqlen_q = 0, total_k_new = 0;
+};
+
+static int kvcache_impl(const char* who, const KvCall& c) {
+    // what the packed and the paged forms, and the canonical window, overwrite below
+    int64_t seqlen_q = c.seqlen_q, seqlen_new = c.seqlen_new, cache_len = c.cache_len, window_left = c.window_left, window_right = c.window_right;
+    int64_t q_batch_stride = c.q_batch_stride, k_new_batch_stride = c.k_new_batch_stride, v_new_batch_stride = c.v_new_batch_stride;
+    if (c.dtype != FA_DTYPE_F16 && c.dtype != FA_DTYPE_BF16)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: dtype must be f16 or bf16 (got code %d)", who, c.dtype);
     // the cache's element type: q's, or e4m3 with a dequantisation scale per (sequence, K/V head)
-    if (cache_dtype != dtype && cache_dtype != FA_DTYPE_E4M3)
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_dtype must be dtype (code %d) or FA_DTYPE_E4M3 (got code %d)", who, dtype,
-                    cache_dtype);
-    const bool e4m3 = cache_dtype == FA_DTYPE_E4M3;
-    if (!e4m3 && (k_descale || v_descale))
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_descale / v_descale need an e4m3 cache (cache_dtype is code %d)", who, cache_dtype);
-    if (!e4m3 && descale_batch_stride != 0)
+    if (c.cache_dtype != c.dtype && c.cache_dtype != FA_DTYPE_E4M3)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_dtype must be dtype (code %d) or FA_DTYPE_E4M3 (got code %d)", who, c.dtype,
+                    c.cache_dtype);
+    const bool e4m3 = c.cache_dtype == FA_DTYPE_E4M3;
+    if (!e4m3 && (c.k_descale || c.v_descale))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_descale / v_descale need an e4m3 cache (cache_dtype is code %d)", who, c.cache_dtype);
+    if (!e4m3 && c.descale_batch_stride != 0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: descale_batch_stride must be 0 with a 16-bit cache (got %lld)", who,
-                    (long long)descale_batch_stride);
-    if (descale_batch_stride < 0)
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: descale_batch_stride must be >= 0 (got %lld)", who, (long long)descale_batch_stride);
-    if ((uintptr_t)k_descale % 4 != 0 || (uintptr_t)v_descale % 4 != 0)
+                    (long long)c.descale_batch_stride);
+    if (c.descale_batch_stride < 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: descale_batch_stride must be >= 0 (got %lld)", who, (long long)c.descale_batch_stride);
+    if ((uintptr_t)c.k_descale % 4 != 0 || (uintptr_t)c.v_descale % 4 != 0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_descale and v_descale must be 4-byte aligned", who);
-    if (d < 8 || d > 256 || d % 8 != 0)
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: head_dim must be a multiple of 8 in [8, 256] (got %lld)", who, (long long)d);
-    if (batch < 1 || batch > 65535) return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch must lie in [1, 65535] (got %lld)", who, (long long)batch);
-    if (heads_kv < 1 || heads_q < 1 || heads_q % heads_kv != 0)
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads_q=%lld must be a positive multiple of heads_kv=%lld", who, (long long)heads_q,
-                    (long long)heads_kv);
+    if (c.d < 8 || c.d > 256 || c.d % 8 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: head_dim must be a multiple of 8 in [8, 256] (got %lld)", who, (long long)c.d);
+    if (c.batch < 1 || c.batch > 65535) return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch must lie in [1, 65535] (got %lld)", who, (long long)c.batch);
+    if (c.heads_kv < 1 || c.heads_q < 1 || c.heads_q % c.heads_kv != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads_q=%lld must be a positive multiple of heads_kv=%lld", who, (long long)c.heads_q,
+                    (long long)c.heads_kv);
     // packed queries / new keys: from here on seqlen_q stands for max_seqlen_q, the bound on every sequence's tokens (the grid,
     // the split rule and the window take it), and q is one unit of tokens at q_token_stride
-    const bool vq = cu_seqlens_q != nullptr, vk = cu_seqlens_k_new != nullptr;
-    if (!vq && (total_q != 0 || max_seqlen_q != 0))
+    const bool vq = c.cu_seqlens_q != nullptr, vk = c.cu_seqlens_k_new != nullptr;
+    if (!vq && (c.total_q != 0 || c.max_seqlen_q != 0))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: total_q and max_seqlen_q must be 0 without cu_seqlens_q (got %lld, %lld)", who,
-                    (long long)total_q, (long long)max_seqlen_q);
-    if (!vk && total_k_new != 0)
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: total_k_new must be 0 without cu_seqlens_k_new (got %lld)", who, (long long)total_k_new);
+                    (long long)c.total_q, (long long)c.max_seqlen_q);
+    if (!vk && c.total_k_new != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: total_k_new must be 0 without cu_seqlens_k_new (got %lld)", who, (long long)c.total_k_new);
     if (vk && !vq) return fail(FA_ERR_INVALID_ARGUMENT, "%s: cu_seqlens_k_new needs cu_seqlens_q", who);
-    if (vk && (!k_new || !v_new)) return fail(FA_ERR_INVALID_ARGUMENT, "%s: cu_seqlens_k_new needs k_new and v_new", who);
-    if ((uintptr_t)cu_seqlens_q % 4 != 0 || (uintptr_t)cu_seqlens_k_new % 4 != 0)
+    if (vk && (!c.k_new || !c.v_new)) return fail(FA_ERR_INVALID_ARGUMENT, "%s: cu_seqlens_k_new needs k_new and v_new", who);
+    if ((uintptr_t)c.cu_seqlens_q % 4 != 0 || (uintptr_t)c.cu_seqlens_k_new % 4 != 0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: cu_seqlens_q and cu_seqlens_k_new must be 4-byte aligned", who);
     if (vq) {
-        if (total_q < 0 || total_q > 0x7fffffff)
-            return fail(FA_ERR_INVALID_ARGUMENT, "%s: total_q must lie in [0, 2^31) (got %lld)", who, (long long)total_q);
-        if (max_seqlen_q < 0 || max_seqlen_q > total_q)
-            return fail(FA_ERR_INVALID_ARGUMENT, "%s: max_seqlen_q=%lld must lie in [0, total_q=%lld]", who, (long long)max_seqlen_q,
-                        (long long)total_q);
-        seqlen_q = max_seqlen_q;
+        if (c.total_q < 0 || c.total_q > 0x7fffffff)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: total_q must lie in [0, 2^31) (got %lld)", who, (long long)c.total_q);
+        if (c.max_seqlen_q < 0 || c.max_seqlen_q > c.total_q)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: max_seqlen_q=%lld must lie in [0, total_q=%lld]", who, (long long)c.max_seqlen_q,
+                        (long long)c.total_q);
+        seqlen_q = c.max_seqlen_q;
         q_batch_stride = 0;
     } else if (seqlen_q < 1) {
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_q must be >= 1 (got %lld)", who, (long long)seqlen_q);
     }
-    if (vk && (total_k_new < 0 || total_k_new > 0x7fffffff))
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: total_k_new must lie in [0, 2^31) (got %lld)", who, (long long)total_k_new);
-    {   // attention sinks: head h of every sequence takes sinks[h % sink_heads]
-        SinkArg sk;
-        sk.sinks = sinks; sk.heads = sink_heads;
-        const int rc = sink_check(who, sk, heads_q, false);
-        if (rc != FA_OK) return rc;
-    }
-    if (descale_batch_stride != 0 && (descale_batch_stride < heads_kv || descale_batch_stride > ((int64_t)1 << 40)))
+    if (vk && (c.total_k_new < 0 || c.total_k_new > 0x7fffffff))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: total_k_new must lie in [0, 2^31) (got %lld)", who, (long long)c.total_k_new);
+    // attention sinks: head h of every sequence takes sinks[h % sink_heads]
+    if (const int rc = sink_check(who, SinkArg{c.sinks, c.sink_heads, nullptr}, c.heads_q, false); rc != FA_OK) return rc;
+    if (c.descale_batch_stride != 0 && (c.descale_batch_stride < c.heads_kv || c.descale_batch_stride > ((int64_t)1 << 40)))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: descale_batch_stride=%lld must be 0 or >= heads_kv=%lld (and <= 2^40)", who,
-                    (long long)descale_batch_stride, (long long)heads_kv);
+                    (long long)c.descale_batch_stride, (long long)c.heads_kv);
     // the paged cache and the two per-sequence cache selectors
-    if (block_table) {
-        if (cache_batch_idx || cache_leftpad)
+    if (c.block_table) {
+        if (c.cache_batch_idx || c.cache_leftpad)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: block_table cannot be combined with cache_batch_idx or cache_leftpad", who);
-        if (page_block_size < 16 || page_block_size % 16 != 0)
+        if (c.page_block_size < 16 || c.page_block_size % 16 != 0)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: page_block_size must be a positive multiple of 16 (got %lld)", who,
-                        (long long)page_block_size);
-        if (num_blocks < 1 || num_blocks > 0x7fffffff)
-            return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_blocks must lie in [1, 2^31) (got %lld)", who, (long long)num_blocks);
-        if (max_blocks_per_seq < 1)
-            return fail(FA_ERR_INVALID_ARGUMENT, "%s: max_blocks_per_seq must be >= 1 (got %lld)", who, (long long)max_blocks_per_seq);
-        if (max_blocks_per_seq > ((int64_t)1 << 28) / page_block_size)
+                        (long long)c.page_block_size);
+        if (c.num_blocks < 1 || c.num_blocks > 0x7fffffff)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_blocks must lie in [1, 2^31) (got %lld)", who, (long long)c.num_blocks);
+        if (c.max_blocks_per_seq < 1)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: max_blocks_per_seq must be >= 1 (got %lld)", who, (long long)c.max_blocks_per_seq);
+        if (c.max_blocks_per_seq > ((int64_t)1 << 28) / c.page_block_size)
             return fail(FA_ERR_UNSUPPORTED, "%s: capacity max_blocks_per_seq * page_block_size = %lld * %lld is beyond 2^28 tokens", who,
-                        (long long)max_blocks_per_seq, (long long)page_block_size);
-        if ((uintptr_t)block_table % 4 != 0)
+                        (long long)c.max_blocks_per_seq, (long long)c.page_block_size);
+        if ((uintptr_t)c.block_table % 4 != 0)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: block_table must be 4-byte aligned", who);
-        if (block_table_row_stride < max_blocks_per_seq || block_table_row_stride > ((int64_t)1 << 40))
+        if (c.block_table_row_stride < c.max_blocks_per_seq || c.block_table_row_stride > ((int64_t)1 << 40))
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: block_table_row_stride=%lld must be >= max_blocks_per_seq=%lld (and <= 2^40)", who,
-                        (long long)block_table_row_stride, (long long)max_blocks_per_seq);
-        cache_len = max_blocks_per_seq * page_block_size;   // the capacity: it stands for cache_len from here on
-    } else if (block_table_row_stride != 0 || num_blocks != 0 || page_block_size != 0 || max_blocks_per_seq != 0) {
+                        (long long)c.block_table_row_stride, (long long)c.max_blocks_per_seq);
+        cache_len = c.max_blocks_per_seq * c.page_block_size;   // the capacity: it stands for cache_len from here on
+    } else if (c.block_table_row_stride != 0 || c.num_blocks != 0 || c.page_block_size != 0 || c.max_blocks_per_seq != 0) {
         return fail(FA_ERR_INVALID_ARGUMENT,
                     "%s: block_table_row_stride, num_blocks, page_block_size and max_blocks_per_seq must be 0 without block_table", who);
     }
-    if (cache_batch_idx) {
-        if (cache_batch < 1 || cache_batch > 0x7fffffff)
+    if (c.cache_batch_idx) {
+        if (c.cache_batch < 1 || c.cache_batch > 0x7fffffff)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_batch must lie in [1, 2^31) with cache_batch_idx (got %lld)", who,
-                        (long long)cache_batch);
-    } else if (cache_batch != 0) {
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_batch must be 0 without cache_batch_idx (got %lld)", who, (long long)cache_batch);
+                        (long long)c.cache_batch);
+    } else if (c.cache_batch != 0) {
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_batch must be 0 without cache_batch_idx (got %lld)", who, (long long)c.cache_batch);
     }
-    if ((uintptr_t)cache_batch_idx % 4 != 0 || (uintptr_t)cache_leftpad % 4 != 0)
+    if ((uintptr_t)c.cache_batch_idx % 4 != 0 || (uintptr_t)c.cache_leftpad % 4 != 0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_batch_idx and cache_leftpad must be 4-byte aligned", who);
     if (cache_len < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_len must be >= 1 (got %lld)", who, (long long)cache_len);
     if (vk) {   // seqlen_new stands for the most tokens one sequence can append (the device clamps nnew_b to it)
-        seqlen_new = total_k_new < cache_len ? total_k_new : cache_len;
+        seqlen_new = c.total_k_new < cache_len ? c.total_k_new : cache_len;
         k_new_batch_stride = v_new_batch_stride = 0;
     }
     if (seqlen_new < 0 || seqlen_new > cache_len)
@@ -1128,82 +1187,82 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
                     (long long)cache_len);
     // strides: the heads of a token adjacent at stride d, tokens at >= heads * d, batch elements past the last token's heads
     // (a cache's units: its num_blocks pages of page_block_size tokens, its cache_batch rows, or its batch rows)
-    const int64_t c_n = block_table ? page_block_size : cache_len;
-    const int64_t c_units = block_table ? num_blocks : cache_batch_idx ? cache_batch : batch;
+    const int64_t c_n = c.block_table ? c.page_block_size : cache_len;
+    const int64_t c_units = c.block_table ? c.num_blocks : c.cache_batch_idx ? c.cache_batch : c.batch;
     // (esz: bytes an element.  The kernels keep 32-bit byte offsets inside one batch element or page, so the limit is on bytes:
     // an e4m3 cache may hold twice the tokens of a 16-bit one)
     const int64_t c_esz = e4m3 ? 1 : 2;
     struct { const char* name; int64_t bs, ts, n, heads, units, esz; } st[5] = {
-        {"q", q_batch_stride, q_token_stride, seqlen_q, heads_q, vq ? 1 : batch, 2},
-        {"k_cache", k_cache_batch_stride, k_cache_token_stride, c_n, heads_kv, c_units, c_esz},
-        {"v_cache", v_cache_batch_stride, v_cache_token_stride, c_n, heads_kv, c_units, c_esz},
-        {"k_new", k_new_batch_stride, k_new_token_stride, seqlen_new, heads_kv, vk ? 1 : batch, 2},
-        {"v_new", v_new_batch_stride, v_new_token_stride, seqlen_new, heads_kv, vk ? 1 : batch, 2}};
+        {"q", q_batch_stride, c.q_token_stride, seqlen_q, c.heads_q, vq ? 1 : c.batch, 2},
+        {"k_cache", c.k_cache_batch_stride, c.k_cache_token_stride, c_n, c.heads_kv, c_units, c_esz},
+        {"v_cache", c.v_cache_batch_stride, c.v_cache_token_stride, c_n, c.heads_kv, c_units, c_esz},
+        {"k_new", k_new_batch_stride, c.k_new_token_stride, seqlen_new, c.heads_kv, vk ? 1 : c.batch, 2},
+        {"v_new", v_new_batch_stride, c.v_new_token_stride, seqlen_new, c.heads_kv, vk ? 1 : c.batch, 2}};
     for (int i = 0; i < (seqlen_new > 0 ? 5 : 3); ++i) {
-        const int64_t span = (st[i].n - 1) * st[i].ts + st[i].heads * d;   // elements of one batch element (or page)
-        if (st[i].ts < st[i].heads * d || (st[i].units > 1 && st[i].bs < span) || st[i].bs < 0)
+        const int64_t span = (st[i].n - 1) * st[i].ts + st[i].heads * c.d;   // elements of one batch element (or page)
+        if (st[i].ts < st[i].heads * c.d || (st[i].units > 1 && st[i].bs < span) || st[i].bs < 0)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of %s too small (batch %lld, token %lld; need token >= %lld, batch >= %lld)",
-                        who, st[i].name, (long long)st[i].bs, (long long)st[i].ts, (long long)(st[i].heads * d), (long long)span);
+                        who, st[i].name, (long long)st[i].bs, (long long)st[i].ts, (long long)(st[i].heads * c.d), (long long)span);
         if (st[i].ts % 8 != 0 || st[i].bs % 8 != 0)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of %s must be multiples of 8 elements", who, st[i].name);
         if (span * st[i].esz >= ((int64_t)1 << 31))
             return fail(FA_ERR_UNSUPPORTED, "%s: one batch element of %s spans %lld bytes, beyond 32-bit offsets", who, st[i].name,
                         (long long)(span * st[i].esz));
     }
-    if (seqlen_new > 0 && (!cache_seqlens || !k_new || !v_new))
+    if (seqlen_new > 0 && (!c.cache_seqlens || !c.k_new || !c.v_new))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_new > 0 needs cache_seqlens, k_new and v_new", who);
     if (window_left < -1 || window_right < -1)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: window (%lld, %lld): each bound must be >= 0, or -1 for unbounded", who,
                     (long long)window_left, (long long)window_right);
     // rotary embedding: the tables are read on the device without a check, so every position a clamped length can give
     // (new key n at L_b - P_b + n, q token i at L_b - P_b + i, L_b <= cache_len - seqlen_new) must be a table row
-    if ((rotary_cos != nullptr) != (rotary_sin != nullptr))
+    if ((c.rotary_cos != nullptr) != (c.rotary_sin != nullptr))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary_cos and rotary_sin must be given together", who);
-    if (rotary_cos) {
-        if (rotary_dim < 16 || rotary_dim > d || rotary_dim % 16 != 0)
+    if (c.rotary_cos) {
+        if (c.rotary_dim < 16 || c.rotary_dim > c.d || c.rotary_dim % 16 != 0)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary_dim must be a multiple of 16 in [16, head_dim=%lld] (got %lld)", who,
-                        (long long)d, (long long)rotary_dim);
-        if (seqlen_new < 1 || !cache_seqlens)
+                        (long long)c.d, (long long)c.rotary_dim);
+        if (seqlen_new < 1 || !c.cache_seqlens)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary needs seqlen_new > 0 (k_new, v_new) and cache_seqlens", who);
         // (packed queries: nq_b - nnew_b is not known here; nq_b <= max_seqlen_q)
-        const int64_t ro_need = cache_len + (vq ? max_seqlen_q : seqlen_q > seqlen_new ? seqlen_q - seqlen_new : 0);
-        if (seqlen_ro < ro_need)
+        const int64_t ro_need = cache_len + (vq ? c.max_seqlen_q : seqlen_q > seqlen_new ? seqlen_q - seqlen_new : 0);
+        if (c.seqlen_ro < ro_need)
             return fail(FA_ERR_INVALID_ARGUMENT,
                         "%s: seqlen_ro=%lld must be >= capacity + %s = %lld (the tables are not bounds-checked on the device)", who,
-                        (long long)seqlen_ro, vq ? "max_seqlen_q" : "max(0, seqlen_q - seqlen_new)", (long long)ro_need);
-        if (rotary_cos_row_stride < rotary_dim / 2 || rotary_sin_row_stride < rotary_dim / 2 ||
-            rotary_cos_row_stride > ((int64_t)1 << 40) || rotary_sin_row_stride > ((int64_t)1 << 40))
+                        (long long)c.seqlen_ro, vq ? "max_seqlen_q" : "max(0, seqlen_q - seqlen_new)", (long long)ro_need);
+        if (c.rotary_cos_row_stride < c.rotary_dim / 2 || c.rotary_sin_row_stride < c.rotary_dim / 2 ||
+            c.rotary_cos_row_stride > ((int64_t)1 << 40) || c.rotary_sin_row_stride > ((int64_t)1 << 40))
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary row strides (%lld, %lld) must be >= rotary_dim / 2 = %lld (and <= 2^40)", who,
-                        (long long)rotary_cos_row_stride, (long long)rotary_sin_row_stride, (long long)(rotary_dim / 2));
-        if (rotary_cos_row_stride % 2 != 0 || rotary_sin_row_stride % 2 != 0)
+                        (long long)c.rotary_cos_row_stride, (long long)c.rotary_sin_row_stride, (long long)(c.rotary_dim / 2));
+        if (c.rotary_cos_row_stride % 2 != 0 || c.rotary_sin_row_stride % 2 != 0)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary row strides (%lld, %lld) must be even", who,
-                        (long long)rotary_cos_row_stride, (long long)rotary_sin_row_stride);
-        if ((uintptr_t)rotary_cos % 4 != 0 || (uintptr_t)rotary_sin % 4 != 0)
+                        (long long)c.rotary_cos_row_stride, (long long)c.rotary_sin_row_stride);
+        if ((uintptr_t)c.rotary_cos % 4 != 0 || (uintptr_t)c.rotary_sin % 4 != 0)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary_cos and rotary_sin must be 4-byte aligned", who);
-    } else if (rotary_cos_row_stride != 0 || rotary_sin_row_stride != 0 || seqlen_ro != 0 || rotary_dim != 0 || rotary_interleaved != 0) {
+    } else if (c.rotary_cos_row_stride != 0 || c.rotary_sin_row_stride != 0 || c.seqlen_ro != 0 || c.rotary_dim != 0 || c.rotary_interleaved != 0) {
         return fail(FA_ERR_INVALID_ARGUMENT,
                     "%s: the rotary row strides, seqlen_ro, rotary_dim and rotary_interleaved must be 0 without rotary_cos / rotary_sin", who);
     }
     // q token i is rotated at its own position when causal or a window bound was given: decided here, on the arguments as
     // passed, before the window is canonicalised
-    const int rotary_q_per_token = (causal || window_left >= 0 || window_right >= 0) ? 1 : 0;
-    if (!(softmax_scale == softmax_scale) || softmax_scale - softmax_scale != 0.0)
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale must be finite (got %g)", who, softmax_scale);
-    if (!scale_ok(softmax_scale))
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale must be > 0 (got %g)", who, softmax_scale);
-    if (!(softcap >= 0.0) || softcap > 1.7976931348623157e308)
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: softcap must be a finite number >= 0 (got %g)", who, softcap);
-    if (alibi_batch_stride < 0 || alibi_batch_stride >= ((int64_t)1 << 31) / batch)
+    const int rotary_q_per_token = (c.causal || window_left >= 0 || window_right >= 0) ? 1 : 0;
+    if (!(c.softmax_scale == c.softmax_scale) || c.softmax_scale - c.softmax_scale != 0.0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale must be finite (got %g)", who, c.softmax_scale);
+    if (!scale_ok(c.softmax_scale))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale must be > 0 (got %g)", who, c.softmax_scale);
+    if (!(c.softcap >= 0.0) || c.softcap > 1.7976931348623157e308)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: softcap must be a finite number >= 0 (got %g)", who, c.softcap);
+    if (c.alibi_batch_stride < 0 || c.alibi_batch_stride >= ((int64_t)1 << 31) / c.batch)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: alibi_batch_stride must be >= 0 and batch * stride < 2^31 (got %lld)", who,
-                    (long long)alibi_batch_stride);
-    if (num_splits < 0 || num_splits > 256)
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_splits must lie in [0, 256] (got %lld)", who, (long long)num_splits);
-    if (cache_len > ((int64_t)1 << 28) || seqlen_q > ((int64_t)1 << 24) || heads_q > 65535 ||
-        ((heads_q / heads_kv) * seqlen_q + 15) / 16 * heads_kv > 65535)
+                    (long long)c.alibi_batch_stride);
+    if (c.num_splits < 0 || c.num_splits > 256)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_splits must lie in [0, 256] (got %lld)", who, (long long)c.num_splits);
+    if (cache_len > ((int64_t)1 << 28) || seqlen_q > ((int64_t)1 << 24) || c.heads_q > 65535 ||
+        ((c.heads_q / c.heads_kv) * seqlen_q + 15) / 16 * c.heads_kv > 65535)
         return fail(FA_ERR_UNSUPPORTED, "%s: problem too large for one launch", who);
-    int64_t S = kv_splits(batch, heads_q, heads_kv, seqlen_q, cache_len, num_splits);
-    if (sinks && S < 2) S = 2;   // the sink joins in the combine: where the rule or the caller gives one split, two are launched
-    const int64_t q_rows = vq ? heads_q * total_q : batch * heads_q * seqlen_q;
+    int64_t S = kv_splits(c.batch, c.heads_q, c.heads_kv, seqlen_q, cache_len, c.num_splits);
+    if (c.sinks && S < 2) S = 2;   // the sink joins in the combine: where the rule or the caller gives one split, two are launched
+    const int64_t q_rows = vq ? c.heads_q * c.total_q : c.batch * c.heads_q * seqlen_q;
     if (S > 1 && q_rows >= ((int64_t)1 << 26))   // the combine: one wave per row, 2^32 lanes per launch
         return fail(FA_ERR_UNSUPPORTED, "%s: %s = %lld rows are too many to combine %lld splits in one launch", who,
                     vq ? "heads_q * total_q" : "batch * heads_q * seqlen_q", (long long)q_rows, (long long)S);
@@ -1212,43 +1271,63 @@ static int kvcache_impl(const char* who, const void* q, void* k_cache, void* v_c
     // stay below 2^28 and the band arithmetic cannot overflow.
     if (window_left >= cache_len - 1) window_left = -1;
     if (window_right >= seqlen_q - 1) window_right = -1;
-    const size_t need = vq ? (seqlen_q > 0 ? fa::kv_workspace_bytes(1, heads_q, total_q, d, (int)S) : 0)
-                           : fa::kv_workspace_bytes(batch, heads_q, seqlen_q, d, (int)S);
-    if (workspace_bytes < need || (need > 0 && !workspace))
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
+    const size_t need = vq ? (seqlen_q > 0 ? fa::kv_workspace_bytes(1, c.heads_q, c.total_q, c.d, (int)S) : 0)
+                           : fa::kv_workspace_bytes(c.batch, c.heads_q, seqlen_q, c.d, (int)S);
+    if (c.workspace_bytes < need || (need > 0 && !c.workspace))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace of %zu bytes needed, %zu given", who, need, c.workspace_bytes);
     // (packed queries without a token: q, o and lse are empty and may be null)
-    if (!k_cache || !v_cache || ((!q || !o || !lse) && !(vq && total_q == 0)))
+    if (!c.k_cache || !c.v_cache || ((!c.q || !c.o || !c.lse) && !(vq && c.total_q == 0)))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
     if (e4m3) {   // an 8-element chunk of an e4m3 cache is 8 bytes: one load or store of 8 bytes, 8-byte aligned
-        if ((uintptr_t)k_cache % 8 != 0 || (uintptr_t)v_cache % 8 != 0)
+        if ((uintptr_t)c.k_cache % 8 != 0 || (uintptr_t)c.v_cache % 8 != 0)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: an e4m3 k_cache / v_cache must be 8-byte aligned", who);
-        if (!aligned16({q, o, workspace}) || (seqlen_new > 0 && !aligned16({k_new, v_new})))
+        if (!aligned16({c.q, c.o, c.workspace}) || (seqlen_new > 0 && !aligned16({c.k_new, c.v_new})))
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: tensors must be 16-byte aligned", who);
-    } else if (!aligned16({q, k_cache, v_cache, o, workspace}) || (seqlen_new > 0 && !aligned16({k_new, v_new})))
+    } else if (!aligned16({c.q, c.k_cache, c.v_cache, c.o, c.workspace}) || (seqlen_new > 0 && !aligned16({c.k_new, c.v_new})))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: tensors must be 16-byte aligned", who);
     fa::KvArgs a{};
-    a.q = q; a.k_cache = k_cache; a.v_cache = v_cache; a.k_new = k_new; a.v_new = v_new; a.o = o; a.lse = lse;
-    a.cache_seqlens = cache_seqlens;
-    a.block_table = block_table; a.cache_batch_idx = cache_batch_idx; a.cache_leftpad = cache_leftpad;
-    a.table_row_stride = block_table_row_stride; a.num_blocks = num_blocks; a.page_size = page_block_size; a.cache_batch = cache_batch;
-    a.batch = batch; a.heads_q = heads_q; a.heads_kv = heads_kv; a.seqlen_q = seqlen_q; a.seqlen_new = seqlen_new;
-    a.cache_len = cache_len; a.d = d; a.dtype = dtype; a.causal = causal ? 1 : 0;
-    a.q_bs = q_batch_stride; a.q_ts = q_token_stride; a.kc_bs = k_cache_batch_stride; a.kc_ts = k_cache_token_stride;
-    a.vc_bs = v_cache_batch_stride; a.vc_ts = v_cache_token_stride; a.kn_bs = k_new_batch_stride; a.kn_ts = k_new_token_stride;
-    a.vn_bs = v_new_batch_stride; a.vn_ts = v_new_token_stride;
+    a.q = c.q; a.k_cache = c.k_cache; a.v_cache = c.v_cache; a.k_new = c.k_new; a.v_new = c.v_new; a.o = c.o; a.lse = c.lse;
+    a.cache_seqlens = c.cache_seqlens;
+    a.block_table = c.block_table; a.cache_batch_idx = c.cache_batch_idx; a.cache_leftpad = c.cache_leftpad;
+    a.table_row_stride = c.block_table_row_stride; a.num_blocks = c.num_blocks; a.page_size = c.page_block_size; a.cache_batch = c.cache_batch;
+    a.batch = c.batch; a.heads_q = c.heads_q; a.heads_kv = c.heads_kv; a.seqlen_q = seqlen_q; a.seqlen_new = seqlen_new;
+    a.cache_len = cache_len; a.d = c.d; a.dtype = c.dtype; a.causal = c.causal ? 1 : 0;
+    a.q_bs = q_batch_stride; a.q_ts = c.q_token_stride; a.kc_bs = c.k_cache_batch_stride; a.kc_ts = c.k_cache_token_stride;
+    a.vc_bs = c.v_cache_batch_stride; a.vc_ts = c.v_cache_token_stride; a.kn_bs = k_new_batch_stride; a.kn_ts = c.k_new_token_stride;
+    a.vn_bs = v_new_batch_stride; a.vn_ts = c.v_new_token_stride;
     a.window_left = window_left; a.window_right = window_right;
-    a.scale = (float)softmax_scale; a.softcap = softcap; a.alibi = alibi_slopes; a.alibi_bstride = alibi_batch_stride;
-    a.num_splits = S; a.workspace = workspace;
-    a.rotary_cos = rotary_cos; a.rotary_sin = rotary_sin; a.rotary_cos_rs = rotary_cos_row_stride; a.rotary_sin_rs = rotary_sin_row_stride;
-    a.rotary_dim = rotary_dim; a.rotary_interleaved = rotary_interleaved ? 1 : 0; a.rotary_q_per_token = rotary_cos ? rotary_q_per_token : 0;
-    a.cache_e4m3 = e4m3 ? 1 : 0; a.k_descale = k_descale; a.v_descale = v_descale; a.descale_bstride = descale_batch_stride;
-    a.sinks = sinks; a.sink_heads = sinks ? sink_heads : 1;
-    a.cu_seqlens_q = cu_seqlens_q; a.cu_seqlens_k_new = cu_seqlens_k_new;
-    a.total_q = total_q; a.max_seqlen_q = max_seqlen_q; a.total_k_new = total_k_new;
+    a.scale = (float)c.softmax_scale; a.softcap = c.softcap; a.alibi = c.alibi_slopes; a.alibi_bstride = c.alibi_batch_stride;
+    a.num_splits = S; a.workspace = c.workspace;
+    a.rotary_cos = c.rotary_cos; a.rotary_sin = c.rotary_sin; a.rotary_cos_rs = c.rotary_cos_row_stride; a.rotary_sin_rs = c.rotary_sin_row_stride;
+    a.rotary_dim = c.rotary_dim; a.rotary_interleaved = c.rotary_interleaved ? 1 : 0; a.rotary_q_per_token = c.rotary_cos ? rotary_q_per_token : 0;
+    a.cache_e4m3 = e4m3 ? 1 : 0; a.k_descale = c.k_descale; a.v_descale = c.v_descale; a.descale_bstride = c.descale_batch_stride;
+    a.sinks = c.sinks; a.sink_heads = c.sinks ? c.sink_heads : 1;
+    a.cu_seqlens_q = c.cu_seqlens_q; a.cu_seqlens_k_new = c.cu_seqlens_k_new;
+    a.total_q = c.total_q; a.max_seqlen_q = c.max_seqlen_q; a.total_k_new = c.total_k_new;
     if (vq && seqlen_q == 0 && seqlen_new == 0) return FA_OK;   // no query token and nothing to append: no launch
-    hipError_t e = fa::launch_kvcache(a, reinterpret_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(FA_ERR_LAUNCH, "%s: HIP error %d (%s)", who, (int)e, hipGetErrorString(e));
-    return FA_OK;
+    return launched(who, fa::launch_kvcache(a, reinterpret_cast<hipStream_t>(c.stream)));
+}
+
+// the 37 arguments of fa_ex_forward_kvcache, which every entry point of the family has
+static KvCall kv_call(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new, const int32_t* cache_seqlens,
+                      void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_new,
+                      int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride, int64_t q_token_stride,
+                      int64_t k_cache_batch_stride, int64_t k_cache_token_stride, int64_t v_cache_batch_stride,
+                      int64_t v_cache_token_stride, int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t v_new_batch_stride,
+                      int64_t v_new_token_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                      double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    KvCall c;
+    c.q = q; c.k_cache = k_cache; c.v_cache = v_cache; c.k_new = k_new; c.v_new = v_new; c.cache_seqlens = cache_seqlens; c.o = o; c.lse = lse;
+    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.seqlen_q = seqlen_q; c.seqlen_new = seqlen_new; c.cache_len = cache_len;
+    c.d = d; c.dtype = dtype; c.cache_dtype = dtype; c.q_batch_stride = q_batch_stride; c.q_token_stride = q_token_stride;
+    c.k_cache_batch_stride = k_cache_batch_stride; c.k_cache_token_stride = k_cache_token_stride; c.k_new_batch_stride = k_new_batch_stride;
+    c.v_cache_batch_stride = v_cache_batch_stride; c.v_cache_token_stride = v_cache_token_stride; c.v_new_batch_stride = v_new_batch_stride;
+    c.k_new_token_stride = k_new_token_stride; c.v_new_token_stride = v_new_token_stride;
+    c.causal = causal; c.window_left = window_left; c.window_right = window_right; c.softmax_scale = softmax_scale; c.softcap = softcap;
+    c.alibi_slopes = alibi_slopes; c.alibi_batch_stride = alibi_batch_stride; c.num_splits = num_splits;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    return c;
 }
 
 int fa_ex_forward_kvcache(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new, const int32_t* cache_seqlens,
@@ -1257,132 +1336,143 @@ int fa_ex_forward_kvcache(const void* q, void* k_cache, void* v_cache, const voi
                           int64_t k_cache_batch_stride, int64_t k_cache_token_stride, int64_t v_cache_batch_stride,
                           int64_t v_cache_token_stride, int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t v_new_batch_stride,
                           int64_t v_new_token_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
-                          double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, void* workspace,
-                          size_t workspace_bytes, void* stream) {
-    return kvcache_impl("fa_ex_forward_kvcache", q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, batch, heads_q, heads_kv,
-                        seqlen_q, seqlen_new, cache_len, d, dtype, q_batch_stride, q_token_stride, k_cache_batch_stride,
-                        k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride, k_new_batch_stride, k_new_token_stride,
-                        v_new_batch_stride, v_new_token_stride, causal, window_left, window_right, softmax_scale, softcap, alibi_slopes,
-                        alibi_batch_stride, num_splits, workspace, workspace_bytes, stream, nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, nullptr,
-                        nullptr, 0, 0, 0, 0, 0, dtype, nullptr, nullptr, 0);
+                          double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    KvCall c = kv_call(q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, batch, heads_q, heads_kv, seqlen_q, seqlen_new, cache_len, d, dtype,
+                       q_batch_stride, q_token_stride, k_cache_batch_stride, k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride,
+                       k_new_batch_stride, k_new_token_stride, v_new_batch_stride, v_new_token_stride, causal, window_left, window_right,
+                       softmax_scale, softcap, alibi_slopes, alibi_batch_stride, num_splits, workspace, workspace_bytes, stream);
+    return kvcache_impl("fa_ex_forward_kvcache", c);
 }
 
-int fa_ex_forward_kvcache_paged(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
-                                const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
-                                int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
-                                int64_t q_token_stride, int64_t k_cache_batch_stride, int64_t k_cache_token_stride,
-                                int64_t v_cache_batch_stride, int64_t v_cache_token_stride, int64_t k_new_batch_stride,
-                                int64_t k_new_token_stride, int64_t v_new_batch_stride, int64_t v_new_token_stride, int causal,
-                                int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
-                                const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, const int32_t* block_table,
-                                int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq,
-                                const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad, void* workspace,
-                                size_t workspace_bytes, void* stream) {
-    return kvcache_impl("fa_ex_forward_kvcache_paged", q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, batch, heads_q, heads_kv,
-                        seqlen_q, seqlen_new, cache_len, d, dtype, q_batch_stride, q_token_stride, k_cache_batch_stride,
-                        k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride, k_new_batch_stride, k_new_token_stride,
-                        v_new_batch_stride, v_new_token_stride, causal, window_left, window_right, softmax_scale, softcap, alibi_slopes,
-                        alibi_batch_stride, num_splits, workspace, workspace_bytes, stream, block_table, block_table_row_stride,
-                        num_blocks, page_block_size, max_blocks_per_seq, cache_batch_idx, cache_batch, cache_leftpad, nullptr, nullptr, 0, 0,
-                        0, 0, 0, dtype, nullptr, nullptr, 0);
+int fa_ex_forward_kvcache_paged(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new, const int32_t* cache_seqlens,
+                                void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_new,
+                                int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride, int64_t q_token_stride,
+                                int64_t k_cache_batch_stride, int64_t k_cache_token_stride, int64_t v_cache_batch_stride,
+                                int64_t v_cache_token_stride, int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t v_new_batch_stride,
+                                int64_t v_new_token_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                                double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits,
+                                const int32_t* block_table, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
+                                int64_t max_blocks_per_seq, const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    KvCall c = kv_call(q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, batch, heads_q, heads_kv, seqlen_q, seqlen_new, cache_len, d, dtype,
+                       q_batch_stride, q_token_stride, k_cache_batch_stride, k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride,
+                       k_new_batch_stride, k_new_token_stride, v_new_batch_stride, v_new_token_stride, causal, window_left, window_right,
+                       softmax_scale, softcap, alibi_slopes, alibi_batch_stride, num_splits, workspace, workspace_bytes, stream);
+    c.block_table = block_table; c.block_table_row_stride = block_table_row_stride; c.num_blocks = num_blocks;
+    c.page_block_size = page_block_size; c.max_blocks_per_seq = max_blocks_per_seq;
+    c.cache_batch_idx = cache_batch_idx; c.cache_batch = cache_batch; c.cache_leftpad = cache_leftpad;
+    return kvcache_impl("fa_ex_forward_kvcache_paged", c);
 }
 
-int fa_ex_forward_kvcache_rotary(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
-                                 const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
-                                 int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
-                                 int64_t q_token_stride, int64_t k_cache_batch_stride, int64_t k_cache_token_stride,
-                                 int64_t v_cache_batch_stride, int64_t v_cache_token_stride, int64_t k_new_batch_stride,
-                                 int64_t k_new_token_stride, int64_t v_new_batch_stride, int64_t v_new_token_stride, int causal,
-                                 int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
-                                 const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, const int32_t* block_table,
-                                 int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq,
-                                 const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad,
-                                 const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride,
-                                 int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
+int fa_ex_forward_kvcache_rotary(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new, const int32_t* cache_seqlens,
+                                 void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_new,
+                                 int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride, int64_t q_token_stride,
+                                 int64_t k_cache_batch_stride, int64_t k_cache_token_stride, int64_t v_cache_batch_stride,
+                                 int64_t v_cache_token_stride, int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t v_new_batch_stride,
+                                 int64_t v_new_token_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                                 double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits,
+                                 const int32_t* block_table, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
+                                 int64_t max_blocks_per_seq, const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad,
+                                 const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride, int64_t rotary_sin_row_stride,
+                                 int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
                                  void* workspace, size_t workspace_bytes, void* stream) {
-    return kvcache_impl("fa_ex_forward_kvcache_rotary", q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, batch, heads_q, heads_kv,
-                        seqlen_q, seqlen_new, cache_len, d, dtype, q_batch_stride, q_token_stride, k_cache_batch_stride,
-                        k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride, k_new_batch_stride, k_new_token_stride,
-                        v_new_batch_stride, v_new_token_stride, causal, window_left, window_right, softmax_scale, softcap, alibi_slopes,
-                        alibi_batch_stride, num_splits, workspace, workspace_bytes, stream, block_table, block_table_row_stride,
-                        num_blocks, page_block_size, max_blocks_per_seq, cache_batch_idx, cache_batch, cache_leftpad, rotary_cos,
-                        rotary_sin, rotary_cos_row_stride, rotary_sin_row_stride, seqlen_ro, rotary_dim, rotary_interleaved, dtype, nullptr,
-                        nullptr, 0);
+    KvCall c = kv_call(q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, batch, heads_q, heads_kv, seqlen_q, seqlen_new, cache_len, d, dtype,
+                       q_batch_stride, q_token_stride, k_cache_batch_stride, k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride,
+                       k_new_batch_stride, k_new_token_stride, v_new_batch_stride, v_new_token_stride, causal, window_left, window_right,
+                       softmax_scale, softcap, alibi_slopes, alibi_batch_stride, num_splits, workspace, workspace_bytes, stream);
+    c.block_table = block_table; c.block_table_row_stride = block_table_row_stride; c.num_blocks = num_blocks;
+    c.page_block_size = page_block_size; c.max_blocks_per_seq = max_blocks_per_seq;
+    c.cache_batch_idx = cache_batch_idx; c.cache_batch = cache_batch; c.cache_leftpad = cache_leftpad;
+    c.rotary_cos = rotary_cos; c.rotary_sin = rotary_sin; c.rotary_cos_row_stride = rotary_cos_row_stride;
+    c.rotary_sin_row_stride = rotary_sin_row_stride; c.seqlen_ro = seqlen_ro; c.rotary_dim = rotary_dim; c.rotary_interleaved = rotary_interleaved;
+    return kvcache_impl("fa_ex_forward_kvcache_rotary", c);
 }
 
-int fa_ex_forward_kvcache_fp8(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
-                              const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
-                              int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
-                              int64_t q_token_stride, int64_t k_cache_batch_stride, int64_t k_cache_token_stride,
-                              int64_t v_cache_batch_stride, int64_t v_cache_token_stride, int64_t k_new_batch_stride,
-                              int64_t k_new_token_stride, int64_t v_new_batch_stride, int64_t v_new_token_stride, int causal,
-                              int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
-                              const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, const int32_t* block_table,
-                              int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq,
-                              const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad,
-                              const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride,
-                              int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
+int fa_ex_forward_kvcache_fp8(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new, const int32_t* cache_seqlens,
+                              void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_new,
+                              int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride, int64_t q_token_stride,
+                              int64_t k_cache_batch_stride, int64_t k_cache_token_stride, int64_t v_cache_batch_stride,
+                              int64_t v_cache_token_stride, int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t v_new_batch_stride,
+                              int64_t v_new_token_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                              double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits,
+                              const int32_t* block_table, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
+                              int64_t max_blocks_per_seq, const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad,
+                              const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride, int64_t rotary_sin_row_stride,
+                              int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
                               int cache_dtype, const float* k_descale, const float* v_descale, int64_t descale_batch_stride,
                               void* workspace, size_t workspace_bytes, void* stream) {
-    return kvcache_impl("fa_ex_forward_kvcache_fp8", q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, batch, heads_q, heads_kv,
-                        seqlen_q, seqlen_new, cache_len, d, dtype, q_batch_stride, q_token_stride, k_cache_batch_stride,
-                        k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride, k_new_batch_stride, k_new_token_stride,
-                        v_new_batch_stride, v_new_token_stride, causal, window_left, window_right, softmax_scale, softcap, alibi_slopes,
-                        alibi_batch_stride, num_splits, workspace, workspace_bytes, stream, block_table, block_table_row_stride,
-                        num_blocks, page_block_size, max_blocks_per_seq, cache_batch_idx, cache_batch, cache_leftpad, rotary_cos,
-                        rotary_sin, rotary_cos_row_stride, rotary_sin_row_stride, seqlen_ro, rotary_dim, rotary_interleaved, cache_dtype,
-                        k_descale, v_descale, descale_batch_stride);
+    KvCall c = kv_call(q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, batch, heads_q, heads_kv, seqlen_q, seqlen_new, cache_len, d, dtype,
+                       q_batch_stride, q_token_stride, k_cache_batch_stride, k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride,
+                       k_new_batch_stride, k_new_token_stride, v_new_batch_stride, v_new_token_stride, causal, window_left, window_right,
+                       softmax_scale, softcap, alibi_slopes, alibi_batch_stride, num_splits, workspace, workspace_bytes, stream);
+    c.block_table = block_table; c.block_table_row_stride = block_table_row_stride; c.num_blocks = num_blocks;
+    c.page_block_size = page_block_size; c.max_blocks_per_seq = max_blocks_per_seq;
+    c.cache_batch_idx = cache_batch_idx; c.cache_batch = cache_batch; c.cache_leftpad = cache_leftpad;
+    c.rotary_cos = rotary_cos; c.rotary_sin = rotary_sin; c.rotary_cos_row_stride = rotary_cos_row_stride;
+    c.rotary_sin_row_stride = rotary_sin_row_stride; c.seqlen_ro = seqlen_ro; c.rotary_dim = rotary_dim; c.rotary_interleaved = rotary_interleaved;
+    c.cache_dtype = cache_dtype; c.k_descale = k_descale; c.v_descale = v_descale; c.descale_batch_stride = descale_batch_stride;
+    return kvcache_impl("fa_ex_forward_kvcache_fp8", c);
 }
 
-int fa_ex_forward_kvcache_sink(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
-                               const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
-                               int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
-                               int64_t q_token_stride, int64_t k_cache_batch_stride, int64_t k_cache_token_stride,
-                               int64_t v_cache_batch_stride, int64_t v_cache_token_stride, int64_t k_new_batch_stride,
-                               int64_t k_new_token_stride, int64_t v_new_batch_stride, int64_t v_new_token_stride, int causal,
-                               int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
-                               const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, const int32_t* block_table,
-                               int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq,
-                               const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad,
-                               const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride,
-                               int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
+int fa_ex_forward_kvcache_sink(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new, const int32_t* cache_seqlens,
+                               void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_new,
+                               int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride, int64_t q_token_stride,
+                               int64_t k_cache_batch_stride, int64_t k_cache_token_stride, int64_t v_cache_batch_stride,
+                               int64_t v_cache_token_stride, int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t v_new_batch_stride,
+                               int64_t v_new_token_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                               double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits,
+                               const int32_t* block_table, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
+                               int64_t max_blocks_per_seq, const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad,
+                               const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride, int64_t rotary_sin_row_stride,
+                               int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
                                int cache_dtype, const float* k_descale, const float* v_descale, int64_t descale_batch_stride,
-                               const float* sinks, int64_t sink_heads, void* workspace, size_t workspace_bytes, void* stream) {
-    return kvcache_impl("fa_ex_forward_kvcache_sink", q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, batch, heads_q, heads_kv,
-                        seqlen_q, seqlen_new, cache_len, d, dtype, q_batch_stride, q_token_stride, k_cache_batch_stride,
-                        k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride, k_new_batch_stride, k_new_token_stride,
-                        v_new_batch_stride, v_new_token_stride, causal, window_left, window_right, softmax_scale, softcap, alibi_slopes,
-                        alibi_batch_stride, num_splits, workspace, workspace_bytes, stream, block_table, block_table_row_stride,
-                        num_blocks, page_block_size, max_blocks_per_seq, cache_batch_idx, cache_batch, cache_leftpad, rotary_cos,
-                        rotary_sin, rotary_cos_row_stride, rotary_sin_row_stride, seqlen_ro, rotary_dim, rotary_interleaved, cache_dtype,
-                        k_descale, v_descale, descale_batch_stride, sinks, sink_heads);
+                               const float* sinks, int64_t sink_heads,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    KvCall c = kv_call(q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, batch, heads_q, heads_kv, seqlen_q, seqlen_new, cache_len, d, dtype,
+                       q_batch_stride, q_token_stride, k_cache_batch_stride, k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride,
+                       k_new_batch_stride, k_new_token_stride, v_new_batch_stride, v_new_token_stride, causal, window_left, window_right,
+                       softmax_scale, softcap, alibi_slopes, alibi_batch_stride, num_splits, workspace, workspace_bytes, stream);
+    c.block_table = block_table; c.block_table_row_stride = block_table_row_stride; c.num_blocks = num_blocks;
+    c.page_block_size = page_block_size; c.max_blocks_per_seq = max_blocks_per_seq;
+    c.cache_batch_idx = cache_batch_idx; c.cache_batch = cache_batch; c.cache_leftpad = cache_leftpad;
+    c.rotary_cos = rotary_cos; c.rotary_sin = rotary_sin; c.rotary_cos_row_stride = rotary_cos_row_stride;
+    c.rotary_sin_row_stride = rotary_sin_row_stride; c.seqlen_ro = seqlen_ro; c.rotary_dim = rotary_dim; c.rotary_interleaved = rotary_interleaved;
+    c.cache_dtype = cache_dtype; c.k_descale = k_descale; c.v_descale = v_descale; c.descale_batch_stride = descale_batch_stride;
+    c.sinks = sinks; c.sink_heads = sink_heads;
+    return kvcache_impl("fa_ex_forward_kvcache_sink", c);
 }
 
-int fa_ex_forward_kvcache_varlen(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
-                                 const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
-                                 int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
-                                 int64_t q_token_stride, int64_t k_cache_batch_stride, int64_t k_cache_token_stride,
-                                 int64_t v_cache_batch_stride, int64_t v_cache_token_stride, int64_t k_new_batch_stride,
-                                 int64_t k_new_token_stride, int64_t v_new_batch_stride, int64_t v_new_token_stride, int causal,
-                                 int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
-                                 const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, const int32_t* block_table,
-                                 int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq,
-                                 const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad,
-                                 const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride,
-                                 int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
+int fa_ex_forward_kvcache_varlen(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new, const int32_t* cache_seqlens,
+                                 void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_new,
+                                 int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride, int64_t q_token_stride,
+                                 int64_t k_cache_batch_stride, int64_t k_cache_token_stride, int64_t v_cache_batch_stride,
+                                 int64_t v_cache_token_stride, int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t v_new_batch_stride,
+                                 int64_t v_new_token_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                                 double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits,
+                                 const int32_t* block_table, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
+                                 int64_t max_blocks_per_seq, const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad,
+                                 const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride, int64_t rotary_sin_row_stride,
+                                 int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
                                  int cache_dtype, const float* k_descale, const float* v_descale, int64_t descale_batch_stride,
-                                 const float* sinks, int64_t sink_heads, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k_new,
-                                 int64_t total_q, int64_t max_seqlen_q, int64_t total_k_new, void* workspace, size_t workspace_bytes,
-                                 void* stream) {
-    return kvcache_impl("fa_ex_forward_kvcache_varlen", q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, batch, heads_q, heads_kv,
-                        seqlen_q, seqlen_new, cache_len, d, dtype, q_batch_stride, q_token_stride, k_cache_batch_stride,
-                        k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride, k_new_batch_stride, k_new_token_stride,
-                        v_new_batch_stride, v_new_token_stride, causal, window_left, window_right, softmax_scale, softcap, alibi_slopes,
-                        alibi_batch_stride, num_splits, workspace, workspace_bytes, stream, block_table, block_table_row_stride,
-                        num_blocks, page_block_size, max_blocks_per_seq, cache_batch_idx, cache_batch, cache_leftpad, rotary_cos,
-                        rotary_sin, rotary_cos_row_stride, rotary_sin_row_stride, seqlen_ro, rotary_dim, rotary_interleaved, cache_dtype,
-                        k_descale, v_descale, descale_batch_stride, sinks, sink_heads, cu_seqlens_q, cu_seqlens_k_new, total_q,
-                        max_seqlen_q, total_k_new);
+                                 const float* sinks, int64_t sink_heads,
+                                 const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k_new, int64_t total_q,
+                                 int64_t max_seqlen_q, int64_t total_k_new,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    KvCall c = kv_call(q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, batch, heads_q, heads_kv, seqlen_q, seqlen_new, cache_len, d, dtype,
+                       q_batch_stride, q_token_stride, k_cache_batch_stride, k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride,
+                       k_new_batch_stride, k_new_token_stride, v_new_batch_stride, v_new_token_stride, causal, window_left, window_right,
+                       softmax_scale, softcap, alibi_slopes, alibi_batch_stride, num_splits, workspace, workspace_bytes, stream);
+    c.block_table = block_table; c.block_table_row_stride = block_table_row_stride; c.num_blocks = num_blocks;
+    c.page_block_size = page_block_size; c.max_blocks_per_seq = max_blocks_per_seq;
+    c.cache_batch_idx = cache_batch_idx; c.cache_batch = cache_batch; c.cache_leftpad = cache_leftpad;
+    c.rotary_cos = rotary_cos; c.rotary_sin = rotary_sin; c.rotary_cos_row_stride = rotary_cos_row_stride;
+    c.rotary_sin_row_stride = rotary_sin_row_stride; c.seqlen_ro = seqlen_ro; c.rotary_dim = rotary_dim; c.rotary_interleaved = rotary_interleaved;
+    c.cache_dtype = cache_dtype; c.k_descale = k_descale; c.v_descale = v_descale; c.descale_batch_stride = descale_batch_stride;
+    c.sinks = sinks; c.sink_heads = sink_heads;
+    c.cu_seqlens_q = cu_seqlens_q; c.cu_seqlens_k_new = cu_seqlens_k_new; c.total_q = total_q; c.max_seqlen_q = max_seqlen_q;
+    c.total_k_new = total_k_new;
+    return kvcache_impl("fa_ex_forward_kvcache_varlen", c);
 }
 
 size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {

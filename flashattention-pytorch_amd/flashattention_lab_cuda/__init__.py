@@ -51,6 +51,99 @@ EXPORTED_C_SYMBOLS = (
 )
 
 
+# ---- the C signatures (include/fa_mi355x.h): for each exported function its return type and its ordered (field, ctype) parameters,
+# composed from named groups.  An argument group a feature adds is one new group here, appended where the header has it.
+_TYPES = {"p": ctypes.c_void_p, "i": ctypes.c_int64, "c": ctypes.c_int, "d": ctypes.c_double, "u": ctypes.c_uint64, "z": ctypes.c_size_t,
+          "s": ctypes.c_char_p}
+
+
+def _fields(spec):
+    """'p:q,k i:bh' -> (("q", c_void_p), ("k", c_void_p), ("bh", c_int64))"""
+    return tuple((name, _TYPES[group[0]]) for group in spec.split() for name in group[2:].split(","))
+
+
+_FWD = _fields("p:q,k,v,o,lse")
+_BWD = _fields("p:q,k,v,o,do_,lse,dq,dk,dv")                 # the nine backward pointers
+_STREAM = _fields("p:stream")
+_WS = _fields("p:workspace z:workspace_bytes p:stream")
+_BHND = _fields("i:bh,n,d c:dtype")
+_PLAIN = _BHND + _fields("c:causal d:softmax_scale i:br,bc")   # fa1 / fa2 / fa3
+_FA3 = _fields("i:stages c:fp8")
+_GROUP = _fields("i:kv_group")
+_EXDIMS = _fields("i:nq,nk,d c:dtype")
+_WINDOW = _fields("i:window_left,window_right")
+_SCALE = _fields("d:softmax_scale")
+_MOD = _fields("d:softcap p:alibi_slopes i:alibi_heads,alibi_batch_stride")
+_MODH = _fields("d:softcap p:alibi_slopes i:alibi_batch_stride")   # varlen and KV-cache: one slope per query head
+_SINK = _fields("p:sinks i:sink_heads")
+_DSINK = _fields("p:dsinks")
+_MASKS = _fields("p:mask i:mask_bh_stride p:block_mask i:br,bc")
+_DROPOUT = _fields("d:dropout_p u:dropout_seed")
+_VARLEN = _fields("p:cu_seqlens_q,cu_seqlens_k i:batch,heads_q,heads_kv,total_q,total_k,max_seqlen_q,max_seqlen_k,d c:dtype "
+                  "i:q_stride,k_stride,v_stride c:causal") + _WINDOW + _SCALE
+_VPAGED = _fields("p:block_table i:max_blocks_per_seq,num_blocks,page_block_size,k_page_stride,v_page_stride")
+_FP8 = _fields("c:cache_dtype p:k_descale,v_descale i:descale_batch_stride")
+_KV = _fields("p:q,k_cache,v_cache,k_new,v_new,cache_seqlens,o,lse i:batch,heads_q,heads_kv,seqlen_q,seqlen_new,cache_len,d c:dtype "
+              "i:q_batch_stride,q_token_stride,k_cache_batch_stride,k_cache_token_stride,v_cache_batch_stride,v_cache_token_stride,"
+              "k_new_batch_stride,k_new_token_stride,v_new_batch_stride,v_new_token_stride c:causal") + _WINDOW + _SCALE + _MODH + \
+    _fields("i:num_splits")
+_PAGED = _fields("p:block_table i:block_table_row_stride,num_blocks,page_block_size,max_blocks_per_seq p:cache_batch_idx i:cache_batch "
+                 "p:cache_leftpad")
+_ROTARY = _fields("p:rotary_cos,rotary_sin i:rotary_cos_row_stride,rotary_sin_row_stride,seqlen_ro,rotary_dim c:rotary_interleaved")
+_KVVARLEN = _fields("p:cu_seqlens_q,cu_seqlens_k_new i:total_q,max_seqlen_q,total_k_new")
+_KVWS = _fields("i:batch,heads_q,heads_kv,seqlen_q,cache_len,d,num_splits")
+
+_SIGNATURES = {}
+
+
+def _sig(names, fields, restype=ctypes.c_int):
+    for name in names.split():
+        _SIGNATURES[name] = (restype, fields)
+
+
+def _ex_sig(ptrs, tail, group=(), window=(), mod=()):
+    return ptrs + _fields("i:bh") + group + _EXDIMS + _fields("c:causal") + window + _SCALE + mod + _MASKS + _DROPOUT + tail
+
+
+_SIZE = ctypes.c_size_t
+_sig("fa1_forward fa2_forward", _FWD + _PLAIN + _STREAM)
+_sig("fa1_backward fa2_backward", _BWD + _PLAIN + _WS)
+_sig("fa3_forward", _FWD + _PLAIN + _FA3 + _WS)
+_sig("fa3_backward", _BWD + _PLAIN + _FA3 + _WS)
+_sig("fa_backward_workspace_bytes", _BHND, _SIZE)
+_sig("fa_backward_workspace_bytes_fast", _BHND + _fields("c:causal"), _SIZE)
+_sig("fa3_forward_workspace_bytes fa3_backward_workspace_bytes", _BHND + _fields("c:fp8"), _SIZE)
+_sig("fa_last_error fa_version", (), ctypes.c_char_p)
+_sig("fa_set_kernel_mode", _fields("c:mode"))
+_sig("fa_set_option", _fields("s:name c:value"))
+_sig("fa_debug_trace_buffer", _fields("p:device_ptr"))
+_sig("fa_device_is_gfx950", _fields("c:device"))
+_sig("fa_profile_enable", _fields("c:on"))
+_sig("fa_profile_report", _fields("s:buf z:cap"))
+for _dir, _ptrs, _tail, _ds in (("forward", _FWD, _STREAM, ()), ("backward", _BWD, _WS, _DSINK)):
+    _sig(f"fa_ex_{_dir}", _ex_sig(_ptrs, _tail))
+    _sig(f"fa_ex_{_dir}_grouped", _ex_sig(_ptrs, _tail, _GROUP))
+    _sig(f"fa_ex_{_dir}_window", _ex_sig(_ptrs, _tail, _GROUP, _WINDOW))
+    _sig(f"fa_ex_{_dir}_scoremod", _ex_sig(_ptrs, _tail, _GROUP, _WINDOW, _MOD))
+    _sig(f"fa_ex_{_dir}_sink", _ex_sig(_ptrs, _tail, _GROUP, _WINDOW, _MOD + _SINK + _ds))
+    _sig(f"fa_ex_{_dir}_varlen", _ptrs + _VARLEN + _DROPOUT + _tail)
+    _sig(f"fa_ex_{_dir}_varlen_scoremod", _ptrs + _VARLEN + _MODH + _DROPOUT + _tail)
+    _sig(f"fa_ex_{_dir}_varlen_sink", _ptrs + _VARLEN + _MODH + _SINK + _ds + _DROPOUT + _tail)
+_sig("fa_ex_forward_varlen_paged", _FWD + _VARLEN + _MODH + _SINK + _VPAGED + _STREAM)
+_sig("fa_ex_forward_varlen_paged_fp8", _FWD + _VARLEN + _MODH + _SINK + _VPAGED + _FP8 + _STREAM)
+_sig("fa_ex_backward_workspace_bytes", _fields("i:bh") + _EXDIMS, _SIZE)
+_sig("fa_ex_backward_workspace_bytes_fast", _fields("i:bh") + _EXDIMS + _fields("c:causal,extras"), _SIZE)
+_sig("fa_ex_backward_workspace_bytes_grouped", _fields("i:bh") + _GROUP + _EXDIMS, _SIZE)
+_sig("fa_ex_backward_workspace_bytes_fast_grouped", _fields("i:bh") + _GROUP + _EXDIMS + _fields("c:causal,extras"), _SIZE)
+_sig("fa_ex_backward_workspace_bytes_varlen", _fields("i:heads_q,heads_kv,total_q,total_k,d c:dtype"), _SIZE)
+_kv = _KV   # each KV-cache entry point: the one before it and one more group, in front of the workspace
+for _suffix, _added in (("", ()), ("_paged", _PAGED), ("_rotary", _ROTARY), ("_fp8", _FP8), ("_sink", _SINK), ("_varlen", _KVVARLEN)):
+    _kv += _added
+    _sig("fa_ex_forward_kvcache" + _suffix, _kv + _WS)
+_sig("fa_ex_kvcache_workspace_bytes fa_ex_kvcache_workspace_bytes_sink", _KVWS, _SIZE)
+_sig("fa_ex_kvcache_workspace_bytes_varlen", _fields("i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,d,num_splits c:with_sinks"), _SIZE)
+
+
 def _load_library() -> ctypes.CDLL:
     if not os.path.exists(_LIB_PATH):
         raise ImportError(
@@ -58,146 +151,32 @@ def _load_library() -> ctypes.CDLL:
             "(or `python -c 'import __graft_entry__ as g; g.build()'`)"
         )
     lib = ctypes.CDLL(_LIB_PATH)
-    vp, i64, ci, dbl, sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_size_t
-    fwd = [vp, vp, vp, vp, vp, i64, i64, i64, ci, ci, dbl, i64, i64, vp]
-    bwd = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, ci, ci, dbl, i64, i64, vp, sz, vp]
-    for name in ("fa1_forward", "fa2_forward"):
-        getattr(lib, name).argtypes = fwd
-        getattr(lib, name).restype = ci
-    for name in ("fa1_backward", "fa2_backward"):
-        getattr(lib, name).argtypes = bwd
-        getattr(lib, name).restype = ci
-    lib.fa3_forward.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, ci, ci, dbl, i64, i64, i64, ci, vp, sz, vp]
-    lib.fa3_forward.restype = ci
-    lib.fa3_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, ci, ci, dbl, i64, i64, i64, ci, vp, sz, vp]
-    lib.fa3_backward.restype = ci
-    lib.fa_backward_workspace_bytes.argtypes = [i64, i64, i64, ci]
-    lib.fa_backward_workspace_bytes.restype = sz
-    lib.fa_backward_workspace_bytes_fast.argtypes = [i64, i64, i64, ci, ci]
-    lib.fa_backward_workspace_bytes_fast.restype = sz
-    lib.fa3_forward_workspace_bytes.argtypes = [i64, i64, i64, ci, ci]
-    lib.fa3_forward_workspace_bytes.restype = sz
-    lib.fa3_backward_workspace_bytes.argtypes = [i64, i64, i64, ci, ci]
-    lib.fa3_backward_workspace_bytes.restype = sz
-    lib.fa_last_error.restype = ctypes.c_char_p
-    lib.fa_version.restype = ctypes.c_char_p
-    lib.fa_set_kernel_mode.argtypes = [ci]
-    lib.fa_set_kernel_mode.restype = ci
-    lib.fa_debug_trace_buffer.argtypes = [vp]
-    lib.fa_debug_trace_buffer.restype = ci
-    lib.fa_set_option.argtypes = [ctypes.c_char_p, ci]
-    lib.fa_set_option.restype = ci
-    lib.fa_device_is_gfx950.argtypes = [ci]
-    lib.fa_device_is_gfx950.restype = ci
-    lib.fa_profile_enable.argtypes = [ci]
-    lib.fa_profile_enable.restype = ci
-    lib.fa_profile_report.argtypes = [ctypes.c_char_p, sz]
-    lib.fa_profile_report.restype = ci
-    u64 = ctypes.c_uint64
-    lib.fa_ex_forward.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, ci, ci, dbl, vp, i64, vp, i64, i64, dbl, u64, vp]
-    lib.fa_ex_forward.restype = ci
-    lib.fa_ex_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, ci, ci, dbl, vp, i64, vp, i64, i64, dbl, u64,
-                                   vp, sz, vp]
-    lib.fa_ex_backward.restype = ci
-    lib.fa_ex_backward_workspace_bytes.argtypes = [i64, i64, i64, i64, ci]
-    lib.fa_ex_backward_workspace_bytes.restype = sz
-    lib.fa_ex_backward_workspace_bytes_fast.argtypes = [i64, i64, i64, i64, ci, ci, ci]
-    lib.fa_ex_backward_workspace_bytes_fast.restype = sz
-    # grouped-query attention: the same arguments with kv_group right after bh
-    lib.fa_ex_forward_grouped.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, ci, dbl, vp, i64, vp, i64, i64, dbl, u64, vp]
-    lib.fa_ex_forward_grouped.restype = ci
-    lib.fa_ex_backward_grouped.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, ci, dbl, vp, i64, vp, i64, i64,
-                                           dbl, u64, vp, sz, vp]
-    lib.fa_ex_backward_grouped.restype = ci
-    lib.fa_ex_backward_workspace_bytes_grouped.argtypes = [i64, i64, i64, i64, i64, ci]
-    lib.fa_ex_backward_workspace_bytes_grouped.restype = sz
-    lib.fa_ex_backward_workspace_bytes_fast_grouped.argtypes = [i64, i64, i64, i64, i64, ci, ci, ci]
-    lib.fa_ex_backward_workspace_bytes_fast_grouped.restype = sz
-    # sliding window: the grouped arguments with window_left, window_right right after causal
-    lib.fa_ex_forward_window.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, ci, i64, i64, dbl, vp, i64, vp, i64, i64, dbl,
-                                         u64, vp]
-    lib.fa_ex_forward_window.restype = ci
-    lib.fa_ex_backward_window.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, ci, i64, i64, dbl, vp, i64, vp,
-                                          i64, i64, dbl, u64, vp, sz, vp]
-    lib.fa_ex_backward_window.restype = ci
-    # packed sequences: cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype,
-    # the three token strides, causal, window_left, window_right, softmax_scale, dropout_p, seed
-    varlen = [vp, vp, i64, i64, i64, i64, i64, i64, i64, i64, ci, i64, i64, i64, ci, i64, i64, dbl, dbl, u64]
-    lib.fa_ex_forward_varlen.argtypes = [vp, vp, vp, vp, vp] + varlen + [vp]
-    lib.fa_ex_forward_varlen.restype = ci
-    lib.fa_ex_backward_varlen.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp] + varlen + [vp, sz, vp]
-    lib.fa_ex_backward_varlen.restype = ci
-    lib.fa_ex_backward_workspace_bytes_varlen.argtypes = [i64, i64, i64, i64, i64, ci]
-    lib.fa_ex_backward_workspace_bytes_varlen.restype = sz
-    # score modifiers: the window (varlen) arguments with softcap, alibi_slopes, alibi_heads (not varlen), alibi_batch_stride right
-    # after softmax_scale
-    lib.fa_ex_forward_scoremod.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, ci, i64, i64, dbl, dbl, vp, i64, i64, vp, i64,
-                                           vp, i64, i64, dbl, u64, vp]
-    lib.fa_ex_forward_scoremod.restype = ci
-    lib.fa_ex_backward_scoremod.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, ci, i64, i64, dbl, dbl, vp,
-                                            i64, i64, vp, i64, vp, i64, i64, dbl, u64, vp, sz, vp]
-    lib.fa_ex_backward_scoremod.restype = ci
-    varlen_sm = varlen[:18] + [dbl, vp, i64] + varlen[18:]
-    lib.fa_ex_forward_varlen_scoremod.argtypes = [vp, vp, vp, vp, vp] + varlen_sm + [vp]
-    lib.fa_ex_forward_varlen_scoremod.restype = ci
-    lib.fa_ex_backward_varlen_scoremod.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp] + varlen_sm + [vp, sz, vp]
-    lib.fa_ex_backward_varlen_scoremod.restype = ci
-    # KV-cache decoding: q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse; batch, heads_q, heads_kv, seqlen_q, seqlen_new,
-    # cache_len, d, dtype; (batch, token) strides of q, k_cache, v_cache, k_new, v_new; causal, window, scale, softcap, alibi,
-    # alibi_batch_stride, num_splits, workspace, workspace_bytes, stream
-    lib.fa_ex_forward_kvcache.argtypes = [vp] * 8 + [i64] * 7 + [ci] + [i64] * 10 + [ci, i64, i64, dbl, dbl, vp, i64, i64, vp, sz, vp]
-    lib.fa_ex_forward_kvcache.restype = ci
-    lib.fa_ex_forward_kvcache_paged.argtypes = [vp] * 8 + [i64] * 7 + [ci] + [i64] * 10 + [ci, i64, i64, dbl, dbl, vp, i64, i64] + \
-        [vp, i64, i64, i64, i64, vp, i64, vp] + [vp, sz, vp]
-    lib.fa_ex_forward_kvcache_paged.restype = ci
-    # ... cache_leftpad; rotary_cos, rotary_sin, their row strides, seqlen_ro, rotary_dim, rotary_interleaved; workspace, ...
-    lib.fa_ex_forward_kvcache_rotary.argtypes = [vp] * 8 + [i64] * 7 + [ci] + [i64] * 10 + [ci, i64, i64, dbl, dbl, vp, i64, i64] + \
-        [vp, i64, i64, i64, i64, vp, i64, vp] + [vp, vp, i64, i64, i64, i64, ci] + [vp, sz, vp]
-    lib.fa_ex_forward_kvcache_rotary.restype = ci
-    # ... rotary_interleaved; cache_dtype, k_descale, v_descale, descale_batch_stride; workspace, ...
-    lib.fa_ex_forward_kvcache_fp8.argtypes = [vp] * 8 + [i64] * 7 + [ci] + [i64] * 10 + [ci, i64, i64, dbl, dbl, vp, i64, i64] + \
-        [vp, i64, i64, i64, i64, vp, i64, vp] + [vp, vp, i64, i64, i64, i64, ci] + [ci, vp, vp, i64] + [vp, sz, vp]
-    lib.fa_ex_forward_kvcache_fp8.restype = ci
-    lib.fa_ex_kvcache_workspace_bytes.argtypes = [i64] * 7
-    lib.fa_ex_kvcache_workspace_bytes.restype = sz
-    # attention sinks: the score-modifier arguments with sinks, sink_heads (backward: + dsinks) right after alibi_batch_stride; the
-    # KV-cache call: the e4m3 call's with sinks, sink_heads right after descale_batch_stride
-    lib.fa_ex_forward_sink.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, ci, i64, i64, dbl, dbl, vp, i64, i64, vp, i64, vp,
-                                       i64, vp, i64, i64, dbl, u64, vp]
-    lib.fa_ex_forward_sink.restype = ci
-    lib.fa_ex_backward_sink.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, ci, i64, i64, dbl, dbl, vp, i64,
-                                        i64, vp, i64, vp, vp, i64, vp, i64, i64, dbl, u64, vp, sz, vp]
-    lib.fa_ex_backward_sink.restype = ci
-    lib.fa_ex_forward_varlen_sink.argtypes = [vp, vp, vp, vp, vp] + varlen_sm[:21] + [vp, i64] + varlen_sm[21:] + [vp]
-    lib.fa_ex_forward_varlen_sink.restype = ci
-    lib.fa_ex_backward_varlen_sink.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp] + varlen_sm[:21] + [vp, i64, vp] + varlen_sm[21:] + \
-        [vp, sz, vp]
-    lib.fa_ex_backward_varlen_sink.restype = ci
-    # the varlen forward over a paged K/V cache: the varlen sink call's without dropout_p, seed, then block_table,
-    # max_blocks_per_seq, num_blocks, page_block_size, k_page_stride, v_page_stride
-    lib.fa_ex_forward_varlen_paged.argtypes = [vp, vp, vp, vp, vp] + varlen_sm[:21] + [vp, i64] + [vp, i64, i64, i64, i64, i64] + [vp]
-    lib.fa_ex_forward_varlen_paged.restype = ci
-    # the same over an e4m3 pool: + cache_dtype, k_descale, v_descale, descale_batch_stride in front of stream
-    lib.fa_ex_forward_varlen_paged_fp8.argtypes = lib.fa_ex_forward_varlen_paged.argtypes[:-1] + [ci, vp, vp, i64] + [vp]
-    lib.fa_ex_forward_varlen_paged_fp8.restype = ci
-    lib.fa_ex_forward_kvcache_sink.argtypes = [vp] * 8 + [i64] * 7 + [ci] + [i64] * 10 + [ci, i64, i64, dbl, dbl, vp, i64, i64] + \
-        [vp, i64, i64, i64, i64, vp, i64, vp] + [vp, vp, i64, i64, i64, i64, ci] + [ci, vp, vp, i64] + [vp, i64] + [vp, sz, vp]
-    lib.fa_ex_forward_kvcache_sink.restype = ci
-    lib.fa_ex_kvcache_workspace_bytes_sink.argtypes = [i64] * 7
-    lib.fa_ex_kvcache_workspace_bytes_sink.restype = sz
-    # packed queries / new keys: the sink call's with cu_seqlens_q, cu_seqlens_k_new, total_q, max_seqlen_q, total_k_new right
-    # after sink_heads
-    lib.fa_ex_forward_kvcache_varlen.argtypes = [vp] * 8 + [i64] * 7 + [ci] + [i64] * 10 + [ci, i64, i64, dbl, dbl, vp, i64, i64] + \
-        [vp, i64, i64, i64, i64, vp, i64, vp] + [vp, vp, i64, i64, i64, i64, ci] + [ci, vp, vp, i64] + [vp, i64] + \
-        [vp, vp, i64, i64, i64] + [vp, sz, vp]
-    lib.fa_ex_forward_kvcache_varlen.restype = ci
-    lib.fa_ex_kvcache_workspace_bytes_varlen.argtypes = [i64] * 8 + [ci]
-    lib.fa_ex_kvcache_workspace_bytes_varlen.restype = sz
+    for name in EXPORTED_C_SYMBOLS:
+        restype, fields = _SIGNATURES[name]
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = [ctype for _field, ctype in fields], restype
     return lib
 
 
 _lib = _load_library()
 LIBRARY_PATH = _LIB_PATH
+_CALLS = {}   # name -> (the C function, a getter of its arguments from the widest entry point's, their count): see _call
+
+
+def _family(widest, narrower):
+    """The entry points of a family take the widest one's arguments less the groups they were defined before; each gets a getter
+    of its own arguments from a tuple of the widest one's (a field the widest one lacks is a ValueError here, at import)."""
+    wide = [field for field, _ctype in _SIGNATURES[widest][1]]
+    for name in (widest, *narrower):
+        own = operator.itemgetter(*[wide.index(field) for field, _ctype in _SIGNATURES[name][1]])
+        _CALLS[name] = (getattr(_lib, name), own, len(wide))
+
+
+for _dir in ("forward", "backward"):
+    _family(f"fa_ex_{_dir}_sink", [f"fa_ex_{_dir}{_suffix}" for _suffix in ("", "_grouped", "_window", "_scoremod")])
+    _family(f"fa_ex_{_dir}_varlen_sink", [f"fa_ex_{_dir}_varlen", f"fa_ex_{_dir}_varlen_scoremod"])
+_family("fa_ex_forward_varlen_paged_fp8", ["fa_ex_forward_varlen_paged"])
+_family("fa_ex_forward_kvcache_varlen", ["fa_ex_forward_kvcache" + _suffix for _suffix in ("", "_paged", "_rotary", "_fp8", "_sink")])
 
 
 def version() -> str:
@@ -240,6 +219,24 @@ def profile_report() -> dict:
 def _check(rc: int) -> None:
     if rc != 0:
         raise RuntimeError(_lib.fa_last_error().decode())
+
+
+def _call(name, values) -> None:
+    """Call the C function `name`.  values: the arguments of the widest entry point of its family, in that one's order; a narrower
+    entry point is passed the ones it takes.  RuntimeError with the library's text on an error code."""
+    fn, own, count = _CALLS[name]
+    if len(values) != count:
+        raise TypeError(f"{name}: {len(values)} values for the {count} arguments of its family")
+    if fn(*own(values)) != 0:
+        raise RuntimeError(_lib.fa_last_error().decode())
+
+
+def _ptr(t) -> int:
+    return t.data_ptr() if t is not None else 0
+
+
+def _contiguous(t):
+    return t.contiguous() if t is not None else None
 
 
 def _check_inputs(who, *tensors):
@@ -507,6 +504,11 @@ def sinks_arg(who, sinks, device, units, heads=None):
     return sinks.data_ptr(), sinks.shape[0], sinks
 
 
+def _ex_variant(sinks, mod, window, grouped=False) -> str:
+    """the narrowest entry point of a family that takes what the call carries: each one adds a group of arguments to the one before"""
+    return "_sink" if sinks else "_scoremod" if mod else "_window" if window else "_grouped" if grouped else ""
+
+
 def ex_forward(q, k, v, causal, softmax_scale, mask=None, block_mask=None, br=128, bc=128, dropout_p=0.0, seed=0, window=(-1, -1),
                softcap=0.0, alibi_slopes=None, sinks=None):
     """(o, lse) of attention with Nq != Nk (causal aligned bottom-right), dense mask (0 = masked), block-sparse mask
@@ -525,19 +527,10 @@ def ex_forward(q, k, v, causal, softmax_scale, mask=None, block_mask=None, br=12
     with torch.cuda.device(q.device):
         o = torch.empty_like(q)
         lse = torch.empty((bh, nq), dtype=torch.float32, device=q.device)
-        ptrs = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr())
-        rest = (nq, nk, d, code, int(bool(causal)), float(softmax_scale), mptr, mstride, bptr, int(br), int(bc), float(dropout_p),
-                int(seed) & (2 ** 64 - 1), _stream_ptr(q.device))
-        if sptr:
-            _check(_lib.fa_ex_forward_sink(*ptrs, bh, g, *rest[:5], wl, wr, rest[5], cap, aptr, aheads, astride, sptr, sheads, *rest[6:]))
-        elif cap > 0.0 or aptr:
-            _check(_lib.fa_ex_forward_scoremod(*ptrs, bh, g, *rest[:5], wl, wr, rest[5], cap, aptr, aheads, astride, *rest[6:]))
-        elif (wl, wr) != (-1, -1):
-            _check(_lib.fa_ex_forward_window(*ptrs, bh, g, *rest[:5], wl, wr, *rest[5:]))
-        elif g > 1:
-            _check(_lib.fa_ex_forward_grouped(*ptrs, bh, g, *rest))
-        else:
-            _check(_lib.fa_ex_forward(*ptrs, bh, *rest))
+        _call("fa_ex_forward" + _ex_variant(sptr, cap > 0.0 or aptr, (wl, wr) != (-1, -1), g > 1), (
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), bh, g, nq, nk, d, code, int(bool(causal)), wl, wr,
+            float(softmax_scale), cap, aptr, aheads, astride, sptr, sheads, mptr, mstride, bptr, int(br), int(bc), float(dropout_p),
+            int(seed) & (2 ** 64 - 1), _stream_ptr(q.device)))
     return o, lse
 
 
@@ -569,24 +562,13 @@ def ex_backward(q, k, v, o, do_, lse, causal, softmax_scale, mask=None, block_ma
         nbytes = plan_backward_workspace(small, fast, have, None if (have >= fast or capturing) else _device_headroom(q.device))
         ws = _workspace(q.device, nbytes)
         nbytes = max(nbytes, 0 if capturing else _workspaces.capacity(q.device, _stream_ptr(q.device)))
-        ptrs = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do_.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
-                dv.data_ptr())
-        rest = (nq, nk, d, code, int(bool(causal)), float(softmax_scale), mptr, mstride, bptr, int(br), int(bc), float(dropout_p),
-                int(seed) & (2 ** 64 - 1), ws.data_ptr(), nbytes, _stream_ptr(q.device))
-        if sptr:
-            dsinks = torch.empty((sheads,), dtype=torch.float32, device=q.device)
-            _check(_lib.fa_ex_backward_sink(*ptrs, bh, g, *rest[:5], wl, wr, rest[5], cap, aptr, aheads, astride, sptr, sheads,
-                                            dsinks.data_ptr(), *rest[6:]))
-            return dq, dk, dv, dsinks
-        if mod:
-            _check(_lib.fa_ex_backward_scoremod(*ptrs, bh, g, *rest[:5], wl, wr, rest[5], cap, aptr, aheads, astride, *rest[6:]))
-        elif (wl, wr) != (-1, -1):
-            _check(_lib.fa_ex_backward_window(*ptrs, bh, g, *rest[:5], wl, wr, *rest[5:]))
-        elif g > 1:
-            _check(_lib.fa_ex_backward_grouped(*ptrs, bh, g, *rest))
-        else:
-            _check(_lib.fa_ex_backward(*ptrs, bh, *rest))
-    return dq, dk, dv
+        dsinks = torch.empty((sheads,), dtype=torch.float32, device=q.device) if sptr else None
+        _call("fa_ex_backward" + _ex_variant(sptr, mod, (wl, wr) != (-1, -1), g > 1), (
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do_.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+            dv.data_ptr(), bh, g, nq, nk, d, code, int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, aheads, astride, sptr,
+            sheads, _ptr(dsinks), mptr, mstride, bptr, int(br), int(bc), float(dropout_p), int(seed) & (2 ** 64 - 1), ws.data_ptr(),
+            nbytes, _stream_ptr(q.device)))
+    return (dq, dk, dv, dsinks) if sptr else (dq, dk, dv)
 
 
 # ---- variable-length (packed) sequences (include/fa_mi355x.h: fa_ex_forward_varlen / fa_ex_backward_varlen) ----
@@ -689,37 +671,15 @@ def _varlen_paged_forward(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q
     cu_q, cu_k, block_table = cu_seqlens_q.contiguous(), cu_seqlens_k.contiguous(), block_table.contiguous()
     aptr, _h, astride, alibi_slopes = alibi_arg(who, alibi_slopes, q.device, b * hq, heads=hq)
     sptr, sheads, sinks = sinks_arg(who, sinks, q.device, b * hq, heads=hq)
-    kdp, kds, k_descale = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
-    vdp, vds, v_descale = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
-    # The C entry point has ONE batch stride for both scales (as fa_ex_forward_kvcache_fp8 has).  Scales of the same form, the
-    # usual case, are passed as they are; in mixed forms, one (H_kv,) and one (B, H_kv), the (H_kv,) one is copied into (B, H_kv)
-    # rows here — one small copy kernel in front of the attention kernel, on the call's stream, captured and replayed with it (a
-    # replay reads the caller's tensor again, so changed scale values are seen).
-    if kdp and vdp and kds != vds:
-        if kds == 0:
-            k_descale = k_descale.expand(b, hkv).contiguous()
-            kdp, kds = k_descale.data_ptr(), hkv
-        elif vds == 0:
-            v_descale = v_descale.expand(b, hkv).contiguous()
-            vdp, vds = v_descale.data_ptr(), hkv
-        else:
-            k_descale, v_descale = k_descale.contiguous(), v_descale.contiguous()
-            kdp, kds, vdp, vds = k_descale.data_ptr(), hkv, v_descale.data_ptr(), hkv
+    kdp, vdp, dsc_bs, _scales = _kv_descales(who, k_descale, v_descale, q, b, hkv)
     with torch.cuda.device(q.device):
         o = torch.empty((total_q, hq, d), dtype=q.dtype, device=q.device)
         lse = torch.empty((hq, total_q), dtype=torch.float32, device=q.device)
-        if e4m3:
-            _check(_lib.fa_ex_forward_varlen_paged_fp8(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(),
-                                                       cu_q.data_ptr(), cu_k.data_ptr(), b, hq, hkv, total_q, 0, mq, mk, d,
-                                                       _DTYPE_CODE[q.dtype], sq, kts, vts, int(bool(causal)), wl, wr, float(softmax_scale),
-                                                       cap, aptr, astride, sptr, sheads, block_table.data_ptr(), block_table.shape[1], nblk,
-                                                       ps, kps, vps, _E4M3_CODE, kdp, vdp, kds if kdp else vds, _stream_ptr(q.device)))
-            return o, lse
-        _check(_lib.fa_ex_forward_varlen_paged(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), cu_q.data_ptr(),
-                                               cu_k.data_ptr(), b, hq, hkv, total_q, 0, mq, mk, d, _DTYPE_CODE[q.dtype], sq, kts, vts,
-                                               int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, astride, sptr, sheads,
-                                               block_table.data_ptr(), block_table.shape[1], nblk, ps, kps, vps,
-                                               _stream_ptr(q.device)))
+        _call("fa_ex_forward_varlen_paged_fp8" if e4m3 else "fa_ex_forward_varlen_paged", (
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr(), b, hq, hkv,
+            total_q, 0, mq, mk, d, _DTYPE_CODE[q.dtype], sq, kts, vts, int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr,
+            astride, sptr, sheads, block_table.data_ptr(), block_table.shape[1], nblk, ps, kps, vps, _E4M3_CODE, kdp, vdp, dsc_bs,
+            _stream_ptr(q.device)))
     return o, lse
 
 
@@ -757,16 +717,10 @@ def ex_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seq
     with torch.cuda.device(q.device):
         o = torch.empty((total_q, hq, d), dtype=q.dtype, device=q.device)
         lse = torch.empty((hq, total_q), dtype=torch.float32, device=q.device)
-        ptrs = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr())
-        tail = (float(dropout_p), int(seed) & (2 ** 64 - 1), _stream_ptr(q.device))
-        if sptr:
-            _check(_lib.fa_ex_forward_varlen_sink(*ptrs, *dims, int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, astride,
-                                                  sptr, sheads, *tail))
-        elif cap > 0.0 or aptr:
-            _check(_lib.fa_ex_forward_varlen_scoremod(*ptrs, *dims, int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, astride,
-                                                      *tail))
-        else:
-            _check(_lib.fa_ex_forward_varlen(*ptrs, *dims, int(bool(causal)), wl, wr, float(softmax_scale), *tail))
+        _call("fa_ex_forward_varlen" + _ex_variant(sptr, cap > 0.0 or aptr, False), (
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr(), *dims,
+            int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, astride, sptr, sheads, float(dropout_p),
+            int(seed) & (2 ** 64 - 1), _stream_ptr(q.device)))
     return o, lse
 
 
@@ -794,20 +748,12 @@ def ex_varlen_backward(q, k, v, o, do_, lse, cu_seqlens_q, cu_seqlens_k, max_seq
         nbytes = int(_lib.fa_ex_backward_workspace_bytes_varlen(hq, hkv, total_q, total_k, d, code))
         ws = _workspace(q.device, nbytes)
         nbytes = max(nbytes, 0 if torch.cuda.is_current_stream_capturing() else _workspaces.capacity(q.device, _stream_ptr(q.device)))
-        ptrs = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do_.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
-                dv.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr())
-        tail = (float(dropout_p), int(seed) & (2 ** 64 - 1), ws.data_ptr(), nbytes, _stream_ptr(q.device))
-        if sptr:
-            dsinks = torch.empty((sheads,), dtype=torch.float32, device=q.device)
-            _check(_lib.fa_ex_backward_varlen_sink(*ptrs, *dims, int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, astride,
-                                                   sptr, sheads, dsinks.data_ptr(), *tail))
-            return dq, dk, dv, dsinks
-        if cap > 0.0 or aptr:
-            _check(_lib.fa_ex_backward_varlen_scoremod(*ptrs, *dims, int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, astride,
-                                                       *tail))
-        else:
-            _check(_lib.fa_ex_backward_varlen(*ptrs, *dims, int(bool(causal)), wl, wr, float(softmax_scale), *tail))
-    return dq, dk, dv
+        dsinks = torch.empty((sheads,), dtype=torch.float32, device=q.device) if sptr else None
+        _call("fa_ex_backward_varlen" + _ex_variant(sptr, cap > 0.0 or aptr, False), (
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do_.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+            dv.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr(), *dims, int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, astride,
+            sptr, sheads, _ptr(dsinks), float(dropout_p), int(seed) & (2 ** 64 - 1), ws.data_ptr(), nbytes, _stream_ptr(q.device)))
+    return (dq, dk, dv, dsinks) if sptr else (dq, dk, dv)
 
 
 # ---- KV-cache decoding with split-KV (include/fa_mi355x.h: fa_ex_forward_kvcache) ----
@@ -841,6 +787,29 @@ def _kv_descale(who, name, t, q, b, hkv):
     return t.data_ptr(), bs, t
 
 
+def _kv_descales(who, k_descale, v_descale, q, b, hkv):
+    """(k_descale pointer, v_descale pointer, descale_batch_stride, the tensors to keep alive) of an e4m3 cache's two scales.
+    The C entry points have ONE batch stride for both.  Scales of the same form, the usual case, are passed as they are; in mixed
+    forms, one (H_kv,) and one (B, H_kv), the (H_kv,) one is copied into (B, H_kv) rows here: one small copy kernel in front of the
+    attention kernel, on the call's stream, captured and replayed with it (a replay reads the caller's tensor again, so changed
+    scale values are seen)."""
+    if k_descale is None and v_descale is None:
+        return 0, 0, 0, None
+    kdp, kds, k_descale = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
+    vdp, vds, v_descale = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
+    if kdp and vdp and kds != vds:
+        if kds == 0:
+            k_descale = k_descale.expand(b, hkv).contiguous()
+            kdp, kds = k_descale.data_ptr(), hkv
+        elif vds == 0:
+            v_descale = v_descale.expand(b, hkv).contiguous()
+            vdp, vds = v_descale.data_ptr(), hkv
+        else:
+            k_descale, v_descale = k_descale.contiguous(), v_descale.contiguous()
+            kdp, kds, vdp, vds = k_descale.data_ptr(), hkv, v_descale.data_ptr(), hkv
+    return kdp, vdp, kds if kdp else vds, (k_descale, v_descale)
+
+
 def _kv_strides(who, name, t, heads, d, cache):
     """(batch stride, token stride) of a (B, N, heads, d) tensor whose heads are adjacent at stride d, last dim contiguous."""
     if t.stride(3) != 1 or (heads > 1 and t.stride(2) != d):
@@ -855,7 +824,10 @@ def _kv_strides(who, name, t, heads, d, cache):
 
 
 def _rotary_tables(rotary_cos, rotary_sin, rdim, rotary_interleaved):
-    """the seven rotary arguments of the KV-cache entry points; rows at an even stride, 4-byte aligned: otherwise a dense copy"""
+    """(the tables to keep alive, the seven rotary arguments of the KV-cache entry points); rows at an even stride, 4-byte aligned:
+    otherwise a dense copy.  Without tables: all 0."""
+    if rotary_cos is None:
+        return None, (0,) * len(_ROTARY)
     tabs = []
     for t in (rotary_cos, rotary_sin):
         if t.stride(1) != 1 or (t.shape[0] > 1 and (t.stride(0) < t.shape[1] or t.stride(0) % 2)) or t.data_ptr() % 4:
@@ -866,41 +838,8 @@ def _rotary_tables(rotary_cos, rotary_sin, rdim, rotary_interleaved):
                   s_.stride(0) if s_.shape[0] > 1 else s_.shape[1], c.shape[0], rdim, int(bool(rotary_interleaved)))
 
 
-def _kvcache_varlen(who, q, k_cache, v_cache, k_new, v_new, cache_seqlens, cu_q, cu_kn, dims, block_table, cache_batch_idx, cache_leftpad,
-                    units, rotary_cos, rotary_sin, rdim, rotary_interleaved, q8, sptr, sheads, total_q, mq, total_kn):
-    """the packed call of ex_kvcache_forward (fa_ex_forward_kvcache_varlen), its arguments checked; the current device is q's"""
-    b, hq, hkv, d = dims[0], dims[1], dims[2], dims[6]
-    cap_len, num_splits = dims[5], dims[-1]
-    cu_q = cu_q.contiguous()
-    cu_kn = cu_kn.contiguous() if cu_kn is not None else None
-    paged = (0, 0, 0, 0, 0)
-    capacity = cap_len
-    if block_table is not None:
-        if block_table.stride(1) != 1:
-            block_table = block_table.contiguous()
-        paged = (block_table.data_ptr(), block_table.stride(0) if b > 1 else max(block_table.stride(0), block_table.shape[1]),
-                 units, cap_len, block_table.shape[1])
-        capacity = block_table.shape[1] * cap_len
-    if cache_batch_idx is not None:
-        cache_batch_idx = cache_batch_idx.contiguous()
-    if cache_leftpad is not None:
-        cache_leftpad = cache_leftpad.contiguous()
-    middle = (*paged, cache_batch_idx.data_ptr() if cache_batch_idx is not None else 0,
-              units if cache_batch_idx is not None else 0, cache_leftpad.data_ptr() if cache_leftpad is not None else 0)
-    rotary = (0, 0, 0, 0, 0, 0, 0)
-    if rotary_cos is not None:
-        _tabs, rotary = _rotary_tables(rotary_cos, rotary_sin, rdim, rotary_interleaved)
-    o = torch.empty((total_q, hq, d), dtype=q.dtype, device=q.device)
-    lse = torch.empty((hq, total_q), dtype=torch.float32, device=q.device)
-    nbytes = int(_lib.fa_ex_kvcache_workspace_bytes_varlen(b, hq, hkv, total_q, mq, capacity, d, num_splits, int(bool(sptr))))
-    ws = _workspace(q.device, nbytes) if nbytes > 0 else None
-    head = (q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_new.data_ptr() if k_new is not None else 0,
-            v_new.data_ptr() if v_new is not None else 0, cache_seqlens.data_ptr() if cache_seqlens is not None else 0,
-            o.data_ptr(), lse.data_ptr())
-    _check(_lib.fa_ex_forward_kvcache_varlen(*head, *dims, *middle, *rotary, *q8, sptr, sheads, cu_q.data_ptr(),
-                                             cu_kn.data_ptr() if cu_kn is not None else 0, total_q, mq, total_kn,
-                                             ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device)))
-    return o, lse
+# what the entry points after fa_ex_forward_kvcache add, for a call it serves: it takes none of them (see _call), any value does
+_KV_NOTHING_ADDED = (0,) * (len(_SIGNATURES["fa_ex_forward_kvcache_varlen"][1]) - len(_SIGNATURES["fa_ex_forward_kvcache"][1]))
 
 
 def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlens=None, causal=False, softmax_scale=None,
@@ -1031,26 +970,13 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
             raise RuntimeError(f"{who}: rotary_cos / rotary_sin need k, v (the new tokens) and cache_seqlens")
     kvb, kvt = _kv_strides(who, "k_cache", k_cache, hkv, d, True)
     vvb, vvt = _kv_strides(who, "v_cache", v_cache, hkv, d, True)
-    kdp, kds, k_descale = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
-    vdp, vds, v_descale = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
+    kdp, vdp, dsc_bs, _scales = _kv_descales(who, k_descale, v_descale, q, b, hkv)
     if e4m3:
         for name, t, bs_, ts_ in (("k_cache", k_cache, kvb, kvt), ("v_cache", v_cache, vvb, vvt)):
             if bs_ % 8 != 0 or ts_ % 8 != 0 or t.data_ptr() % 8 != 0:
                 raise ValueError(f"{who}: an e4m3 {name} must be 8-byte aligned with batch and token strides that are multiples "
                                  f"of 8 elements (got address % 8 = {t.data_ptr() % 8}, strides {tuple(t.stride())}); the cache "
                                  f"is never copied")
-        if kdp and vdp and kds != vds:   # one batch stride serves both: give the (H_kv,) one B rows
-            if kds == 0:
-                k_descale = k_descale.expand(b, hkv).contiguous()
-                kdp, kds = k_descale.data_ptr(), hkv
-            elif vds == 0:
-                v_descale = v_descale.expand(b, hkv).contiguous()
-                vdp, vds = v_descale.data_ptr(), hkv
-            else:
-                v_descale = v_descale.contiguous()
-                k_descale = k_descale.contiguous()
-                kdp, kds, vdp, vds = k_descale.data_ptr(), hkv, v_descale.data_ptr(), hkv
-    dsc_bs = kds if kdp else vds
     nnew = 0
     knb = knt = vnb = vnt = 0
     if cu_seqlens_k_new is not None:
@@ -1101,62 +1027,39 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
             if cache_seqlens.device != q.device or cache_seqlens.dtype != torch.int32 or cache_seqlens.shape != (b,):
                 raise RuntimeError(f"{who}: cache_seqlens must be an int32 ({b},) tensor on q's device, or an int")
             cache_seqlens = cache_seqlens.contiguous()
-        if packed:
-            return _kvcache_varlen(who, q, k_cache, v_cache, k_new, v_new, cache_seqlens, cu_seqlens_q, cu_seqlens_k_new,
-                                   (b, hq, hkv, 0, 0 if cu_seqlens_k_new is not None else nnew, cap_len, d, _DTYPE_CODE[q.dtype], 0, qt,
-                                    kvb, kvt, vvb, vvt, knb, knt, vnb, vnt, int(bool(causal)), wl, wr, scale, cap, aptr, astride,
-                                    int(num_splits)),
-                                   block_table, cache_batch_idx, cache_leftpad, units, rotary_cos, rotary_sin, rdim, rotary_interleaved,
-                                   (_E4M3_CODE, kdp, vdp, dsc_bs) if e4m3 else (_DTYPE_CODE[q.dtype], 0, 0, 0), sptr, sheads,
-                                   total_q, mq, total_kn)
-        o = torch.empty((b, nq, hq, d), dtype=q.dtype, device=q.device)
-        lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)
-        head = (q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_new.data_ptr() if k_new is not None else 0,
-                v_new.data_ptr() if v_new is not None else 0, cache_seqlens.data_ptr() if cache_seqlens is not None else 0,
-                o.data_ptr(), lse.data_ptr(), b, hq, hkv, nq, nnew, cap_len, d, _DTYPE_CODE[q.dtype], qb, qt, kvb, kvt, vvb, vvt,
-                knb, knt, vnb, vnt, int(bool(causal)), wl, wr, scale, cap, aptr, astride, int(num_splits))
-        if not sptr and not e4m3 and block_table is None and cache_batch_idx is None and cache_leftpad is None and rotary_cos is None:
-            nbytes = int(_lib.fa_ex_kvcache_workspace_bytes(b, hq, hkv, nq, cap_len, d, int(num_splits)))
-            ws = _workspace(q.device, nbytes) if nbytes > 0 else None
-            _check(_lib.fa_ex_forward_kvcache(*head, ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device)))
-        else:
-            paged = (0, 0, 0, 0, 0)
-            capacity = cap_len
+        # the narrowest entry point that takes what the call carries (each adds a group of arguments to the one before), its
+        # workspace query, and those groups: marshalled in one place, and not at all for a call that carries none of them
+        variant = "_varlen" if packed else "_sink" if sptr else "_fp8" if e4m3 else "_rotary" if rotary_cos is not None else \
+            "_paged" if (block_table is not None or cache_batch_idx is not None or cache_leftpad is not None) else ""
+        code, capacity, added = _DTYPE_CODE[q.dtype], cap_len, _KV_NOTHING_ADDED
+        if variant:
+            cu_q, cu_kn = _contiguous(cu_seqlens_q), _contiguous(cu_seqlens_k_new)
+            cache_batch_idx, cache_leftpad = _contiguous(cache_batch_idx), _contiguous(cache_leftpad)
+            paged = (0, 0, 0, 0, 0)   # block_table, its row stride, num_blocks, page_block_size, max_blocks_per_seq
             if block_table is not None:
                 if block_table.stride(1) != 1:
                     block_table = block_table.contiguous()
+                capacity = block_table.shape[1] * cap_len
                 paged = (block_table.data_ptr(), block_table.stride(0) if b > 1 else max(block_table.stride(0), block_table.shape[1]),
                          units, cap_len, block_table.shape[1])
-                capacity = block_table.shape[1] * cap_len
-            if cache_batch_idx is not None:
-                cache_batch_idx = cache_batch_idx.contiguous()
-            if cache_leftpad is not None:
-                cache_leftpad = cache_leftpad.contiguous()
-            middle = (*paged, cache_batch_idx.data_ptr() if cache_batch_idx is not None else 0,
-                      units if cache_batch_idx is not None else 0, cache_leftpad.data_ptr() if cache_leftpad is not None else 0)
-            rotary = (0, 0, 0, 0, 0, 0, 0) if (e4m3 or sptr) else None
-            if rotary_cos is not None:
-                tabs = []
-                for t in (rotary_cos, rotary_sin):   # rows at an even stride, 4-byte aligned: otherwise a dense copy
-                    if t.stride(1) != 1 or (t.shape[0] > 1 and (t.stride(0) < t.shape[1] or t.stride(0) % 2)) or t.data_ptr() % 4:
-                        t = t.clone(memory_format=torch.contiguous_format)
-                    tabs.append(t)
-                rotary_cos, rotary_sin = tabs
-                rotary = (rotary_cos.data_ptr(), rotary_sin.data_ptr(),
-                          rotary_cos.stride(0) if rotary_cos.shape[0] > 1 else rotary_cos.shape[1],
-                          rotary_sin.stride(0) if rotary_sin.shape[0] > 1 else rotary_sin.shape[1],
-                          rotary_cos.shape[0], rdim, int(bool(rotary_interleaved)))
+            _tabs, rotary = _rotary_tables(rotary_cos, rotary_sin, rdim, rotary_interleaved)
+            added = (*paged, _ptr(cache_batch_idx), 0 if cache_batch_idx is None else units, _ptr(cache_leftpad), *rotary,
+                     _E4M3_CODE if e4m3 else code, kdp, vdp, dsc_bs, sptr, sheads, _ptr(cu_q), _ptr(cu_kn), total_q, mq, total_kn)
+        if packed:
+            o = torch.empty((total_q, hq, d), dtype=q.dtype, device=q.device)
+            lse = torch.empty((hq, total_q), dtype=torch.float32, device=q.device)
+            nbytes = int(_lib.fa_ex_kvcache_workspace_bytes_varlen(b, hq, hkv, total_q, mq, capacity, d, int(num_splits), int(bool(sptr))))
+        else:
+            o = torch.empty((b, nq, hq, d), dtype=q.dtype, device=q.device)
+            lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)
             ws_bytes = _lib.fa_ex_kvcache_workspace_bytes_sink if sptr else _lib.fa_ex_kvcache_workspace_bytes
             nbytes = int(ws_bytes(b, hq, hkv, nq, capacity, d, int(num_splits)))
-            ws = _workspace(q.device, nbytes) if nbytes > 0 else None
-            tail = (ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device))
-            if sptr:
-                q8 = (_E4M3_CODE, kdp, vdp, dsc_bs) if e4m3 else (_DTYPE_CODE[q.dtype], 0, 0, 0)
-                _check(_lib.fa_ex_forward_kvcache_sink(*head, *middle, *rotary, *q8, sptr, sheads, *tail))
-            elif e4m3:
-                _check(_lib.fa_ex_forward_kvcache_fp8(*head, *middle, *rotary, _E4M3_CODE, kdp, vdp, dsc_bs, *tail))
-            elif rotary is None:
-                _check(_lib.fa_ex_forward_kvcache_paged(*head, *middle, *tail))
-            else:
-                _check(_lib.fa_ex_forward_kvcache_rotary(*head, *middle, *rotary, *tail))
+        ws = _workspace(q.device, nbytes) if nbytes > 0 else None
+        _call("fa_ex_forward_kvcache" + variant, (
+            q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_new.data_ptr() if k_new is not None else 0,
+            v_new.data_ptr() if v_new is not None else 0, cache_seqlens.data_ptr() if cache_seqlens is not None else 0, o.data_ptr(), lse.data_ptr(),
+            b, hq, hkv, 0 if packed else nq, 0 if cu_seqlens_k_new is not None else nnew, cap_len, d, code,
+            0 if packed else qb, qt, kvb, kvt, vvb, vvt, knb, knt, vnb, vnt,
+            int(bool(causal)), wl, wr, scale, cap, aptr, astride, int(num_splits), *added,
+            ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device)))
     return o, lse
