@@ -1475,6 +1475,113 @@ int fa_ex_forward_kvcache_varlen(const void* q, void* k_cache, void* v_cache, co
     return kvcache_impl("fa_ex_forward_kvcache_varlen", c);
 }
 
+// One call of the fa_rotary_apply family, a field per argument under its name in the header.  Defaults: "argument absent".
+struct RotaryCall {
+    const void* x = nullptr;
+    void* y = nullptr;
+    int64_t batch = 0, seqlen = 0, heads = 0, d = 0;
+    int dtype = 0;
+    int64_t x_batch_stride = 0, x_token_stride = 0, y_batch_stride = 0, y_token_stride = 0;
+    // _rotary
+    const void *rotary_cos = nullptr, *rotary_sin = nullptr;
+    int64_t rotary_cos_row_stride = 0, rotary_sin_row_stride = 0, seqlen_ro = 0, rotary_dim = 0;
+    int rotary_interleaved = 0;
+    int conjugate = 0;
+    int64_t seqlen_offset = 0;
+    const int32_t *seqlen_offsets = nullptr, *cu_seqlens = nullptr;
+    int64_t total = 0, max_seqlen = 0;
+    void* stream = nullptr;
+};
+
+static int rotary_impl(const char* who, const RotaryCall& c) {
+    const int64_t kStrideMax = (int64_t)1 << 31, kBatchStrideMax = (int64_t)1 << 44;   // no 64-bit offset can overflow
+    if (c.dtype != FA_DTYPE_F16 && c.dtype != FA_DTYPE_BF16)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: dtype must be f16 or bf16 (got code %d)", who, c.dtype);
+    if (c.d < 8 || c.d > 256 || c.d % 8 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: head_dim must be a multiple of 8 in [8, 256] (got %lld)", who, (long long)c.d);
+    if (c.batch < 1 || c.batch > 65535) return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch must lie in [1, 65535] (got %lld)", who, (long long)c.batch);
+    if (c.heads < 1 || c.heads > 0x7fffffff / c.d)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads must be >= 1 with heads * head_dim < 2^31 (got %lld)", who, (long long)c.heads);
+    if (c.seqlen < 0 || c.seqlen > 0x7fffffff)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen must lie in [0, 2^31) (got %lld)", who, (long long)c.seqlen);
+    if (!c.x || !c.y) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    if ((uintptr_t)c.x % 16 != 0 || (uintptr_t)c.y % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: x and y must be 16-byte aligned", who);
+    if ((uintptr_t)c.seqlen_offsets % 4 != 0 || (uintptr_t)c.cu_seqlens % 4 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_offsets and cu_seqlens must be 4-byte aligned", who);
+    const bool packed = c.cu_seqlens != nullptr;
+    if (packed) {
+        if (c.total < 0 || c.total > 0x7fffffff)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: total must lie in [0, 2^31) (got %lld)", who, (long long)c.total);
+        if (c.max_seqlen < 0 || c.max_seqlen > c.total)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: max_seqlen=%lld must lie in [0, total=%lld]", who, (long long)c.max_seqlen,
+                        (long long)c.total);
+        if (c.seqlen != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen must be 0 with cu_seqlens (got %lld)", who, (long long)c.seqlen);
+    } else if (c.total != 0 || c.max_seqlen != 0) {
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: total and max_seqlen must be 0 without cu_seqlens (got %lld, %lld)", who,
+                    (long long)c.total, (long long)c.max_seqlen);
+    }
+    const int64_t row = c.heads * c.d;
+    if (c.x_token_stride < row || c.y_token_stride < row || c.x_token_stride > kStrideMax || c.y_token_stride > kStrideMax)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: token strides (%lld, %lld) must be >= heads * head_dim = %lld (and <= 2^31)", who,
+                    (long long)c.x_token_stride, (long long)c.y_token_stride, (long long)row);
+    if (!packed && c.batch > 1) {
+        const int64_t xs = (c.seqlen > 0 ? (c.seqlen - 1) * c.x_token_stride : 0) + row;
+        const int64_t ys = (c.seqlen > 0 ? (c.seqlen - 1) * c.y_token_stride : 0) + row;
+        if (c.x_batch_stride < xs || c.y_batch_stride < ys || c.x_batch_stride > kBatchStrideMax || c.y_batch_stride > kBatchStrideMax)
+            return fail(FA_ERR_INVALID_ARGUMENT,
+                        "%s: batch strides (%lld, %lld) must be >= (seqlen - 1) * token stride + heads * head_dim = (%lld, %lld) (and <= 2^44)", who,
+                        (long long)c.x_batch_stride, (long long)c.y_batch_stride, (long long)xs, (long long)ys);
+    }
+    const bool batch_strides = !packed && c.batch > 1;   // the only form that addresses with them
+    if (c.x_token_stride % 8 != 0 || c.y_token_stride % 8 != 0 ||
+        (batch_strides && (c.x_batch_stride % 8 != 0 || c.y_batch_stride % 8 != 0)))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: every stride must be a multiple of 8 elements", who);
+    if (c.y == c.x && (c.x_token_stride != c.y_token_stride || (batch_strides && c.x_batch_stride != c.y_batch_stride)))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: y == x (in place) needs equal strides", who);
+    if (!c.rotary_cos || !c.rotary_sin) return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary_cos and rotary_sin must both be given", who);
+    if ((uintptr_t)c.rotary_cos % 4 != 0 || (uintptr_t)c.rotary_sin % 4 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary_cos and rotary_sin must be 4-byte aligned", who);
+    if (c.rotary_dim < 16 || c.rotary_dim > c.d || c.rotary_dim % 16 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary_dim must be a multiple of 16 in [16, head_dim=%lld] (got %lld)", who,
+                    (long long)c.d, (long long)c.rotary_dim);
+    if (c.rotary_cos_row_stride < c.rotary_dim / 2 || c.rotary_sin_row_stride < c.rotary_dim / 2 ||
+        c.rotary_cos_row_stride > kStrideMax || c.rotary_sin_row_stride > kStrideMax)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary row strides (%lld, %lld) must be >= rotary_dim / 2 = %lld (and <= 2^31)", who,
+                    (long long)c.rotary_cos_row_stride, (long long)c.rotary_sin_row_stride, (long long)(c.rotary_dim / 2));
+    if (c.rotary_cos_row_stride % 2 != 0 || c.rotary_sin_row_stride % 2 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary row strides (%lld, %lld) must be even", who,
+                    (long long)c.rotary_cos_row_stride, (long long)c.rotary_sin_row_stride);
+    if (c.seqlen_ro < 1 || c.seqlen_ro > 0x7fffffff)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_ro must lie in [1, 2^31) (got %lld)", who, (long long)c.seqlen_ro);
+    if (c.seqlen_offset <= -((int64_t)1 << 31) || c.seqlen_offset >= ((int64_t)1 << 31))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: |seqlen_offset| must be < 2^31 (got %lld)", who, (long long)c.seqlen_offset);
+    if ((packed ? c.max_seqlen : c.seqlen) == 0) return FA_OK;   // no token: no launch
+    fa::RotaryArgs a;
+    a.x = c.x; a.y = c.y; a.batch = c.batch; a.seqlen = c.seqlen; a.heads = c.heads; a.d = c.d; a.dtype = c.dtype;
+    a.x_bs = batch_strides ? c.x_batch_stride : 0; a.x_ts = c.x_token_stride;
+    a.y_bs = batch_strides ? c.y_batch_stride : 0; a.y_ts = c.y_token_stride;
+    a.rotary_cos = c.rotary_cos; a.rotary_sin = c.rotary_sin; a.rotary_cos_rs = c.rotary_cos_row_stride; a.rotary_sin_rs = c.rotary_sin_row_stride;
+    a.seqlen_ro = c.seqlen_ro; a.rotary_dim = c.rotary_dim; a.rotary_interleaved = c.rotary_interleaved ? 1 : 0;
+    a.conjugate = c.conjugate ? 1 : 0; a.seqlen_offset = c.seqlen_offset; a.seqlen_offsets = c.seqlen_offsets;
+    a.cu_seqlens = c.cu_seqlens; a.total = c.total; a.max_seqlen = c.max_seqlen;
+    return launched(who, fa::launch_rotary(a, reinterpret_cast<hipStream_t>(c.stream)));
+}
+
+int fa_rotary_apply(const void* x, void* y, int64_t batch, int64_t seqlen, int64_t heads, int64_t d, int dtype, int64_t x_batch_stride,
+                    int64_t x_token_stride, int64_t y_batch_stride, int64_t y_token_stride, const void* rotary_cos, const void* rotary_sin,
+                    int64_t rotary_cos_row_stride, int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim,
+                    int rotary_interleaved, int conjugate, int64_t seqlen_offset, const int32_t* seqlen_offsets,
+                    const int32_t* cu_seqlens, int64_t total, int64_t max_seqlen, void* stream) {
+    RotaryCall c;
+    c.x = x; c.y = y; c.batch = batch; c.seqlen = seqlen; c.heads = heads; c.d = d; c.dtype = dtype;
+    c.x_batch_stride = x_batch_stride; c.x_token_stride = x_token_stride; c.y_batch_stride = y_batch_stride; c.y_token_stride = y_token_stride;
+    c.rotary_cos = rotary_cos; c.rotary_sin = rotary_sin; c.rotary_cos_row_stride = rotary_cos_row_stride;
+    c.rotary_sin_row_stride = rotary_sin_row_stride; c.seqlen_ro = seqlen_ro; c.rotary_dim = rotary_dim; c.rotary_interleaved = rotary_interleaved;
+    c.conjugate = conjugate; c.seqlen_offset = seqlen_offset; c.seqlen_offsets = seqlen_offsets;
+    c.cu_seqlens = cu_seqlens; c.total = total; c.max_seqlen = max_seqlen; c.stream = stream;
+    return rotary_impl("fa_rotary_apply", c);
+}
+
 size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {
     return ex_bwd_ws_grouped(bh, kv_group, nq, nk, d, dtype);
 }

@@ -249,6 +249,24 @@ int kv_num_splits(int64_t batch, int64_t heads_kv, int64_t row_tiles, int64_t ca
 size_t kv_workspace_bytes(int64_t batch, int64_t heads_q, int64_t seqlen_q, int64_t d, int splits);
 hipError_t launch_kvcache(const KvArgs& a, hipStream_t st);
 
+// Rotary embedding for training and prefill (fa_rotary.hip; fa_rotary_apply).  16-bit x, y (batch, seqlen, heads, d), heads at
+// stride d, strides multiples of 8 elements, 16-byte aligned; y == x (with x's strides) is the in-place form.  Tables as KvArgs'.
+struct RotaryArgs {
+    const void* x;
+    void* y;
+    int64_t batch, seqlen, heads, d;
+    int dtype;
+    int64_t x_bs, x_ts, y_bs, y_ts;
+    const void *rotary_cos, *rotary_sin;
+    int64_t rotary_cos_rs, rotary_sin_rs, seqlen_ro, rotary_dim;
+    int rotary_interleaved, conjugate;   // conjugate: rotate by -sin (the backward)
+    int64_t seqlen_offset;               // token i of sequence b at seqlen_offset + seqlen_offsets[b] + i; rotated iff in [0, seqlen_ro)
+    const int* seqlen_offsets;           // (batch,) untrusted device memory, or null
+    const int* cu_seqlens;               // (batch + 1,) untrusted device offsets of packed (total, heads, d) tensors, or null
+    int64_t total, max_seqlen;
+};
+hipError_t launch_rotary(const RotaryArgs& a, hipStream_t st);
+
 // Grouped-query attention (fa_kv_group.hip): dk[u] = sum over m = 0 .. g-1 of pk[u g + m] (and dv from pv), accumulated in fp32 in
 // that order and rounded once to the tensor dtype; units of nk * d elements, bh / g of them in dk and dv.
 hipError_t launch_kv_group_sum(const void* pk, const void* pv, void* dk, void* dv, int64_t bh_kv, int64_t g, int64_t nk, int64_t d,

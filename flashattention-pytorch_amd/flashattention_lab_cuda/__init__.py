@@ -48,6 +48,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_ex_forward_kvcache_sink", "fa_ex_kvcache_workspace_bytes_sink",
     "fa_ex_forward_kvcache_varlen", "fa_ex_kvcache_workspace_bytes_varlen",
     "fa_ex_forward_varlen_paged", "fa_ex_forward_varlen_paged_fp8",
+    "fa_rotary_apply",
 )
 
 
@@ -92,6 +93,8 @@ _PAGED = _fields("p:block_table i:block_table_row_stride,num_blocks,page_block_s
 _ROTARY = _fields("p:rotary_cos,rotary_sin i:rotary_cos_row_stride,rotary_sin_row_stride,seqlen_ro,rotary_dim c:rotary_interleaved")
 _KVVARLEN = _fields("p:cu_seqlens_q,cu_seqlens_k_new i:total_q,max_seqlen_q,total_k_new")
 _KVWS = _fields("i:batch,heads_q,heads_kv,seqlen_q,cache_len,d,num_splits")
+_ROXY = _fields("p:x,y i:batch,seqlen,heads,d c:dtype i:x_batch_stride,x_token_stride,y_batch_stride,y_token_stride")
+_ROPOS = _fields("c:conjugate i:seqlen_offset p:seqlen_offsets,cu_seqlens i:total,max_seqlen")
 
 _SIGNATURES = {}
 
@@ -141,6 +144,7 @@ for _suffix, _added in (("", ()), ("_paged", _PAGED), ("_rotary", _ROTARY), ("_f
     _kv += _added
     _sig("fa_ex_forward_kvcache" + _suffix, _kv + _WS)
 _sig("fa_ex_kvcache_workspace_bytes fa_ex_kvcache_workspace_bytes_sink", _KVWS, _SIZE)
+_sig("fa_rotary_apply", _ROXY + _ROTARY + _ROPOS + _STREAM)
 _sig("fa_ex_kvcache_workspace_bytes_varlen", _fields("i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,d,num_splits c:with_sinks"), _SIZE)
 
 
@@ -176,6 +180,7 @@ for _dir in ("forward", "backward"):
     _family(f"fa_ex_{_dir}_sink", [f"fa_ex_{_dir}{_suffix}" for _suffix in ("", "_grouped", "_window", "_scoremod")])
     _family(f"fa_ex_{_dir}_varlen_sink", [f"fa_ex_{_dir}_varlen", f"fa_ex_{_dir}_varlen_scoremod"])
 _family("fa_ex_forward_varlen_paged_fp8", ["fa_ex_forward_varlen_paged"])
+_family("fa_rotary_apply", [])
 _family("fa_ex_forward_kvcache_varlen", ["fa_ex_forward_kvcache" + _suffix for _suffix in ("", "_paged", "_rotary", "_fp8", "_sink")])
 
 
@@ -1063,3 +1068,99 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
             int(bool(causal)), wl, wr, scale, cap, aptr, astride, int(num_splits), *added,
             ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device)))
     return o, lse
+
+
+# ---- rotary embedding for training and prefill (include/fa_mi355x.h: fa_rotary_apply) ----
+
+def _rotary_view(who, name, t, packed):
+    """(batch stride, token stride) of a (B, S, heads, d) or packed (total, heads, d) view as fa_rotary_apply addresses it: last
+    dim contiguous, heads adjacent at stride d, strides multiples of 8, 16-byte aligned.  Anything else raises: the tensor may be
+    the target of the call, and a copy would silently lose the write."""
+    heads, d = t.shape[-2], t.shape[-1]
+    tokens = t.shape[-3]
+    ts = t.stride(-3) if tokens > 1 else max(t.stride(-3), heads * d)
+    bs = 0
+    if not packed:
+        bs = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), (tokens - 1) * ts + heads * d)
+    if t.stride(-1) != 1 or (heads > 1 and t.stride(-2) != d) or ts < heads * d or ts % 8 or bs % 8 or t.data_ptr() % 16 or \
+            (not packed and t.shape[0] > 1 and bs < (tokens - 1) * ts + heads * d):
+        raise ValueError(f"{who}: {name} must have a contiguous last dim, its heads at stride d = {d}, token and batch strides that "
+                         f"are multiples of 8 and do not overlap, and a 16-byte aligned address (got strides {tuple(t.stride())}); "
+                         f"it is never copied")
+    return bs, ts
+
+
+def rotary_apply(x, cos, sin, out=None, interleaved=False, conjugate=False, seqlen_offsets=0, cu_seqlens=None, max_seqlen=None):
+    """Rotary position embedding of the first rotary_dim = 2 * cos.shape[1] head dims of every head of x, one launch
+    (fa_rotary_apply).  x: (B, S, heads, d) float16 / bfloat16 on the GPU, or packed (total, heads, d) with cu_seqlens (int32
+    (B + 1,) on x's device) and max_seqlen (an int, required); a strided view whose heads are adjacent (qkv[:, :, :2].reshape(B, S,
+    2 * H, d) of a (B, S, 3, H, d) projection) is addressed as it is.  cos, sin: (seqlen_ro, rotary_dim / 2) in x's dtype on x's
+    device, rotary_dim a multiple of 16 in [16, d].  out: None allocates a dense result; `out is x` (or a view of the same memory
+    and strides) rotates in place, and the head dims at and past rotary_dim are then not touched; any other tensor of x's shape,
+    dtype and device receives the result.  interleaved: pairs (2j, 2j + 1), else (j, j + rotary_dim / 2).  conjugate: rotate by
+    -sin, the backward of the forward map.  seqlen_offsets: an int, or an int32 (B,) tensor on x's device that is read by the
+    kernel only; token i of sequence b sits at seqlen_offsets[b] + i and is rotated iff that is a row of the tables, otherwise it
+    passes through.  Nothing is read on the host, so the call can be captured and replayed with changed offsets and cu_seqlens.
+    A layout the kernel cannot address raises ValueError; nothing is copied.  Returns out."""
+    who = "rotary_apply"
+    packed = cu_seqlens is not None
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError(f"{who}: x must be a GPU (HIP device) tensor; there is no CPU path")
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError(f"{who}: x must have a 16-bit dtype (float16 or bfloat16), got {x.dtype}")
+    if max_seqlen is not None and not packed:
+        raise ValueError(f"{who}: max_seqlen needs cu_seqlens")
+    if packed:
+        if x.dim() != 3:
+            raise ValueError(f"{who}: with cu_seqlens x must be packed (total, heads, d), got {tuple(x.shape)}")
+        if max_seqlen is None:
+            raise ValueError(f"{who}: cu_seqlens needs max_seqlen")
+        if not isinstance(cu_seqlens, torch.Tensor) or cu_seqlens.dtype != torch.int32:
+            dt = cu_seqlens.dtype if isinstance(cu_seqlens, torch.Tensor) else type(cu_seqlens).__name__
+            raise NotImplementedError(f"{who}: cu_seqlens of dtype {dt} is not supported (int32 tensor expected)")
+        if cu_seqlens.device != x.device or cu_seqlens.dim() != 1 or cu_seqlens.shape[0] < 2:
+            raise RuntimeError(f"{who}: cu_seqlens must be an int32 (B + 1,) tensor on x's device, B >= 1")
+        total, heads, d = x.shape
+        b, seqlen, mx = cu_seqlens.shape[0] - 1, 0, operator.index(max_seqlen)
+        if mx < 0 or mx > total:
+            raise ValueError(f"{who}: max_seqlen = {mx} must lie in [0, total = {total}]")
+    else:
+        if x.dim() != 4:
+            raise RuntimeError(f"{who}: x must be 4-D (B, S, heads, d), or packed (total, heads, d) with cu_seqlens; got {tuple(x.shape)}")
+        b, seqlen, heads, d = x.shape
+        total = mx = 0
+    if d % 8 != 0 or not 8 <= d <= 256:
+        raise RuntimeError(f"{who}: head dim must be a multiple of 8 in [8, 256], got {d}")
+    for name, t in (("cos", cos), ("sin", sin)):
+        if not isinstance(t, torch.Tensor) or t.dtype != x.dtype or t.device != x.device or t.dim() != 2 or \
+                t.shape != cos.shape or t.numel() == 0:
+            raise RuntimeError(f"{who}: {name} must be a (seqlen_ro, rotary_dim / 2) tensor of x's dtype on x's device, cos and sin "
+                               f"of one shape")
+    rdim = 2 * cos.shape[1]
+    if rdim % 16 != 0 or not 16 <= rdim <= d:
+        raise RuntimeError(f"{who}: rotary_dim = 2 * cos.shape[1] must be a multiple of 16 in [16, d = {d}], got {rdim}")
+    off0, offs = 0, None
+    if isinstance(seqlen_offsets, torch.Tensor):
+        if seqlen_offsets.dtype != torch.int32 or seqlen_offsets.device != x.device or seqlen_offsets.shape != (b,):
+            raise RuntimeError(f"{who}: seqlen_offsets must be an int, or an int32 ({b},) tensor on x's device")
+        offs = seqlen_offsets.contiguous()
+    else:
+        off0 = operator.index(seqlen_offsets)
+        if abs(off0) >= 2 ** 31:
+            raise ValueError(f"{who}: |seqlen_offsets| must be < 2^31, got {off0}")
+    if out is None:
+        out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    elif not isinstance(out, torch.Tensor) or out.shape != x.shape or out.dtype != x.dtype or out.device != x.device:
+        raise RuntimeError(f"{who}: out must be a tensor of x's shape, dtype and device")
+    if b == 0 or heads == 0 or (total if packed else seqlen) == 0 or (packed and mx == 0):
+        return out
+    xb, xt = _rotary_view(who, "x", x, packed)
+    yb, yt = _rotary_view(who, "out", out, packed)
+    if out.data_ptr() == x.data_ptr() and (xb, xt) != (yb, yt):
+        raise ValueError(f"{who}: out shares x's address with other strides; in place needs the same view")
+    with torch.cuda.device(x.device):
+        _tabs, rotary = _rotary_tables(cos, sin, rdim, interleaved)
+        cu = cu_seqlens.contiguous() if packed else None
+        _call("fa_rotary_apply", (x.data_ptr(), out.data_ptr(), b, seqlen, heads, d, _DTYPE_CODE[x.dtype], xb, xt, yb, yt, *rotary,
+                                  int(bool(conjugate)), off0, _ptr(offs), _ptr(cu), total, mx, _stream_ptr(x.device)))
+    return out

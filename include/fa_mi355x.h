@@ -642,6 +642,49 @@ int fa_ex_forward_kvcache_varlen(const void* q, void* k_cache, void* v_cache, co
 size_t fa_ex_kvcache_workspace_bytes_varlen(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t max_seqlen_q,
                                             int64_t cache_len, int64_t d, int64_t num_splits, int with_sinks);
 
+/* --- Rotary position embedding for training and prefill (FlashAttention's flash_attn.layers.rotary: apply_rotary_emb,
+ * apply_rotary_emb_qkv_), forward and backward.  One memory-bound launch on `stream` rotates the first rotary_dim head dims of
+ * every head of one 16-bit tensor: x -> y, both (batch, seqlen, heads, d) with the heads adjacent at stride d, the last dim
+ * contiguous, and a batch stride and a token stride each (elements).  So qkv[:, :, :2] of a (B, S, 3, H, d) projection is one call
+ * with heads = 2 H at token stride 3 H d, and the first H_q + H_kv heads of a GQA-packed (B, S, H_q + 2 H_kv, d) tensor likewise.
+ * y == x (the same pointer, with the same strides) is the in-place form; any other overlap of x and y is undefined.  Head dims at
+ * and past rotary_dim are copied out of place and neither read nor written in place.
+ * Tables and arithmetic are fa_ex_forward_kvcache_rotary's, to the bit: rotary_cos, rotary_sin (seqlen_ro, rotary_dim / 2) in x's
+ * dtype, last dim contiguous, rows at the even strides rotary_cos_row_stride / rotary_sin_row_stride, 4-byte aligned; rotary_dim
+ * a multiple of 16 in [16, d]; rotary_interleaved != 0 pairs elements (2j, 2j + 1) (GPT-J), 0 pairs (j, j + rotary_dim / 2)
+ * (GPT-NeoX); a pair (x, y) with table entry j at table row pos becomes
+ *     x' = x cos[pos, j] - y sin[pos, j],   y' = x sin[pos, j] + y cos[pos, j],
+ * in fp32 from the 16-bit inputs (the products are exact), rounded once to nearest even.  A key rotated here at position p has
+ * the bits the decode call stores for the same k_new at position p.
+ * conjugate != 0 rotates by -sin: x' = x cos + y sin, y' = -x sin + y cos.  That is the transpose of the forward map, so applied
+ * to the gradient of y it is the whole backward; the sign flip is exact.
+ * Positions: token i of sequence b is at pos = seqlen_offset + (seqlen_offsets ? seqlen_offsets[b] : 0) + i.  seqlen_offset is a
+ * host integer; seqlen_offsets is int32 (batch,) device memory, never read on the host and not trusted: pos is formed in 64 bits,
+ * and a token is rotated iff 0 <= pos < seqlen_ro.  Every other token passes through unrotated (copied out of place, untouched
+ * in place), FlashAttention's rule, where rows past the table read cos = 1, sin = 0; no table row outside the table is addressed
+ * whatever the offsets hold.  (fa_ex_forward_kvcache_rotary bounds seqlen_ro on the host instead.)
+ * Packed form: cu_seqlens int32 (batch + 1,) device memory; x and y are (total, heads, d) at their token strides, seqlen is 0
+ * and the batch strides are not used.  Sequence b owns the tokens of fa_ex_forward_varlen's clamp: start = clamp(cu[b], 0, total),
+ * end = clamp(cu[b + 1], start, total), len = min(end - start, max_seqlen); positions count from the sequence's own first token.
+ * Tokens that no sequence owns are not written out of place and unchanged in place; nothing outside x / y is touched whatever
+ * cu_seqlens holds.
+ * Nothing allocates, synchronises or reads device memory on the host: the call can be captured in a graph and replayed with
+ * changed offsets and changed cu_seqlens (batch, total, max_seqlen and seqlen_offset are fixed by the capture).  fp32 tensors
+ * and separate tables for K are not supported.
+ * Checked before any HIP call (FA_ERR_INVALID_ARGUMENT, the first broken rule named in fa_last_error()), in this order: dtype f16
+ * or bf16; d a multiple of 8 in [8, 256]; batch in [1, 65535]; heads >= 1 (heads * d < 2^31); seqlen in [0, 2^31); x, y non-null
+ * and 16-byte aligned; seqlen_offsets, cu_seqlens 4-byte aligned; with cu_seqlens 0 <= max_seqlen <= total < 2^31 and
+ * seqlen == 0, without it total == max_seqlen == 0; token strides >= heads * d (and <= 2^31); with batch > 1 in the padded form
+ * batch strides >= (seqlen - 1) * token stride + heads * d (and <= 2^44); every stride used a multiple of 8; y == x only with
+ * equal strides; both tables given and 4-byte aligned; rotary_dim a multiple of 16 in [16, d]; row strides >= rotary_dim / 2 (and
+ * <= 2^31) and even; seqlen_ro in [1, 2^31); |seqlen_offset| < 2^31.  A call with no tokens (seqlen == 0, or max_seqlen == 0)
+ * that passes them returns FA_OK without a launch. */
+int fa_rotary_apply(const void* x, void* y, int64_t batch, int64_t seqlen, int64_t heads, int64_t d, int dtype,
+                    int64_t x_batch_stride, int64_t x_token_stride, int64_t y_batch_stride, int64_t y_token_stride,
+                    const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride, int64_t rotary_sin_row_stride,
+                    int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved, int conjugate, int64_t seqlen_offset,
+                    const int32_t* seqlen_offsets, const int32_t* cu_seqlens, int64_t total, int64_t max_seqlen, void* stream);
+
 /* --- support entry points (no reference counterpart: the reference allocates inside the callee) --- */
 /* bytes for the CURRENT kernel mode: two float row constants per query row (+ an fp32 dQ scratch of bh*n*d floats in
  * FA_MODE_BWD_ATOMIC only); ask again after changing the mode */
