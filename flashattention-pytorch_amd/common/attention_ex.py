@@ -5,7 +5,7 @@ extended entry points (`fa_ex_forward` / `fa_ex_backward`, include/fa_mi355x.h):
 
     flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, block_size=128,
                        causal=False, dropout_p=0.0, seed=0, softmax_scale=None, window_size=(-1, -1),
-                       softcap=0.0, alibi_slopes=None, sinks=None) -> o
+                       softcap=0.0, alibi_slopes=None, *, return_lse=False, sinks=None) -> o  |  (o, lse)
 
 q: (B, H, Nq, d) or (BH, Nq, d); k, v: (B, H_kv, Nk, d) or (B*H_kv, Nk, d).  H_kv < H is grouped-query attention (GQA; H_kv = 1:
 multi-query attention) with H % H_kv == 0: query head h reads K/V head h // (H / H_kv), with no copy of K and V, and the
@@ -25,6 +25,21 @@ logit per head that joins each row's softmax as an extra column with a zero valu
 capped, biased, masked or dropped; -inf switches a head's sink off.  `sinks` receives a float32 gradient (a bf16 parameter is passed
 as `p.float()` and gets its gradient through the cast).  Differentiable (autograd Function; the backward recomputes P and
 regenerates the dropout mask from the seed).  No CPU path: the tensors must live on the GPU.
+
+`return_lse=True` (keyword-only, and `sinks` with it now: sinks stays the last parameter, so both are passed by name) returns (o, lse): lse is the natural-log normaliser of each row, float32 (B, H, Nq) for 4-D q and
+(BH, Nq) for 3-D q, -inf for a row without a visible key (and without a sink), and it is differentiable: a gradient of lse enters
+the backward as one more row constant (fa_ex_backward_dlse).  o has the bits of the call without the keyword, and while lse
+receives no gradient so have dq, dk, dv and dsinks.  (o, lse) pairs over disjoint key sets are combined by
+common.merge_states.merge_attention_states; chained through autograd that gives the gradients of the one call over all the keys.
+
+Chunking the keys of one call.  `causal` is aligned bottom-right (row i sees keys j <= i + Nk - Nq), so a chunk keys[j0:j1] of a
+causal call over Nk keys is NOT a causal call on the chunk.  It is `causal=False, window_size=(left, Nk - j1)` on the chunk, where
+`left` is the full call's left bound moved with the chunk (-1 if it had none: left' = left - (Nk - j1) where that is >= 0, and a
+chunk wholly left of the band is not called at all): the chunk's last key j1 - 1 then sits Nk - j1 to the right of where the
+full call's diagonal ends.  The last chunk (j1 = Nk) is plain `causal=True`.  Rows that see no key of a chunk come back with o = 0
+and lse = -inf, which the merge treats as weight 0.  With `sinks`, pass them to exactly one chunk (the sink is one more column of
+the union).  `mask` and `block_sparse_mask` are sliced with the keys.  ALiBi across chunks is not expressible (the bias of a chunk
+would need the chunk's offset, which the call does not take) and is out of scope; dropout draws a different mask per chunk.
 """
 from __future__ import annotations
 
@@ -100,6 +115,40 @@ class _FlashAttnExFn(torch.autograd.Function):
         return (dq, dk, dv) + (None,) * 11   # (no gradient for the slopes, as in FlashAttention-2)
 
 
+class _FlashAttnExLseFn(torch.autograd.Function):
+    """_FlashAttnExFn that also returns lse (flash_attention_ex(..., return_lse=True)).  A gradient of lse goes to the library as
+    dlse; without one the backward is _FlashAttnExFn's call, launch for launch."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, causal, scale, mask, block_mask, br, bc, dropout_p, seed, window, softcap, alibi_slopes, sinks):
+        import flashattention_lab_cuda as ext
+
+        ctx.set_materialize_grads(False)
+        ctx.args = (causal, scale, mask, block_mask, br, bc, dropout_p, seed, window, softcap, alibi_slopes)
+        ctx.with_sinks = sinks is not None
+        kw = {"sinks": sinks} if sinks is not None else {}
+        o, lse = ext.ex_forward(q, k, v, causal, scale, mask, block_mask, br, bc, dropout_p, seed, window=window, softcap=softcap,
+                                alibi_slopes=alibi_slopes, **kw)
+        ctx.save_for_backward(q, k, v, o, lse, *kw.values())
+        return o, lse
+
+    @staticmethod
+    def backward(ctx, do, dlse):
+        import flashattention_lab_cuda as ext
+
+        if do is None and dlse is None:
+            return (None,) * 15
+        causal, scale, mask, block_mask, br, bc, dropout_p, seed, window, softcap, alibi_slopes = ctx.args
+        q, k, v, o, lse = ctx.saved_tensors[:5]
+        do = torch.zeros_like(o) if do is None else do.contiguous()
+        kw = {"sinks": ctx.saved_tensors[5]} if ctx.with_sinks else {}
+        if dlse is not None:
+            kw["dlse"] = dlse.contiguous()
+        grads = ext.ex_backward(q, k, v, o, do, lse, causal, scale, mask, block_mask, br, bc, dropout_p, seed, window=window,
+                                softcap=softcap, alibi_slopes=alibi_slopes, **kw)
+        return tuple(grads[:3]) + (None,) * 11 + ((grads[3],) if ctx.with_sinks else (None,))
+
+
 def _window_size(window_size):
     """(left, right) ints >= -1, with the library's error text (flashattention_lab_cuda.window_arg, fa_capi.hip)."""
     try:
@@ -136,7 +185,8 @@ def _sinks_units(who, sinks, heads):
 
 
 def flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, block_size=128, causal=False, dropout_p=0.0,
-                       seed=0, softmax_scale=None, window_size=(-1, -1), softcap=0.0, alibi_slopes=None, sinks=None):
+                       seed=0, softmax_scale=None, window_size=(-1, -1), softcap=0.0, alibi_slopes=None, *, return_lse=False,
+                       sinks=None):
     window = _window_size(window_size)
     if not q.is_cuda:
         raise RuntimeError("Inputs must be CUDA tensors")   # as the reference's wrappers (src/fa2/cuda/impl.py:44)
@@ -160,6 +210,15 @@ def flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, bloc
     if block_sparse_mask is not None:
         br, bc = min(br, nq), min(bc, nk)         # Br = min(block_size, q_len), Bc = min(block_size, kv_len)  (:100-101)
     slopes = _alibi_units(alibi_slopes, tuple(q.shape[:-2]))
+    if return_lse:
+        if sinks is not None:
+            if four_d:
+                sinks = _sinks_units("flash_attention_ex", sinks, h)
+            elif not isinstance(sinks, torch.Tensor) or sinks.dtype != torch.float32:
+                raise RuntimeError("flash_attention_ex: sinks must be a float32 tensor (pass a 16-bit parameter as p.float())")
+        o, lse = _FlashAttnExLseFn.apply(q3, k3, v3, bool(causal), scale, m, block_sparse_mask, br, bc, float(dropout_p), int(seed),
+                                         window, softcap, slopes, sinks)
+        return (o.reshape(q.shape), lse.reshape(b, h, nq)) if four_d else (o, lse)
     if sinks is not None:
         if four_d:
             sinks = _sinks_units("flash_attention_ex", sinks, h)
@@ -211,9 +270,42 @@ class _FlashAttnVarlenFn(torch.autograd.Function):
         return (dq, dk, dv) + (None,) * 11
 
 
+class _FlashAttnVarlenLseFn(torch.autograd.Function):
+    """_FlashAttnVarlenFn that also returns lse (flash_attention_varlen(..., return_softmax_lse=True)), as _FlashAttnExLseFn"""
+
+    @staticmethod
+    def forward(ctx, q, k, v, cu_q, cu_k, max_q, max_k, dropout_p, scale, causal, window, seed, softcap, alibi_slopes, sinks):
+        import flashattention_lab_cuda as ext
+
+        ctx.set_materialize_grads(False)
+        ctx.with_sinks = sinks is not None
+        kw = {"sinks": sinks} if sinks is not None else {}
+        o, lse = ext.ex_varlen_forward(q, k, v, cu_q, cu_k, max_q, max_k, causal, scale, dropout_p, seed, window=window, softcap=softcap,
+                                       alibi_slopes=alibi_slopes, **kw)
+        ctx.save_for_backward(q, k, v, o, lse, cu_q, cu_k, *kw.values())
+        ctx.args = (max_q, max_k, dropout_p, scale, causal, window, seed, softcap, alibi_slopes)
+        return o, lse
+
+    @staticmethod
+    def backward(ctx, do, dlse):
+        import flashattention_lab_cuda as ext
+
+        if do is None and dlse is None:
+            return (None,) * 15
+        max_q, max_k, dropout_p, scale, causal, window, seed, softcap, alibi_slopes = ctx.args
+        q, k, v, o, lse, cu_q, cu_k = ctx.saved_tensors[:7]
+        do = torch.zeros_like(o) if do is None else do.contiguous()
+        kw = {"sinks": ctx.saved_tensors[7]} if ctx.with_sinks else {}
+        if dlse is not None:
+            kw["dlse"] = dlse.contiguous()
+        grads = ext.ex_varlen_backward(q, k, v, o, do, lse, cu_q, cu_k, max_q, max_k, causal, scale, dropout_p, seed, window=window,
+                                       softcap=softcap, alibi_slopes=alibi_slopes, **kw)
+        return tuple(grads[:3]) + (None,) * 11 + ((grads[3],) if ctx.with_sinks else (None,))
+
+
 def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p=0.0, softmax_scale=None,
                            causal=False, window_size=(-1, -1), seed=0, softcap=0.0, alibi_slopes=None, *,
-                           block_table=None, k_descale=None, v_descale=None, sinks=None):
+                           return_softmax_lse=False, block_table=None, k_descale=None, v_descale=None, sinks=None):
     """FlashAttention-2's flash_attn_varlen_func over packed sequences, differentiable: q (total_q, H_q, d), k and v
     (total_k, H_kv, d) with H_q % H_kv == 0 (GQA), token-strided views (qkv.unbind(1) of a (total, 3, H, d) projection) taken
     without a copy; cu_seqlens_* int32 (batch + 1,) device offsets.  Attention stays inside each sequence; `causal` is
@@ -246,17 +338,32 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
     k_descale * (q . k_stored), scaled before softcap and ALiBi, v_descale multiplies the normalised output once in fp32, and
     everything above about the table, the views, the lengths and graph replay (changed scale values included) holds unchanged.
     Give both scales in the same form: with one (H_kv,) and one (batch, H_kv) the former is first copied into (batch, H_kv) rows,
-    one more small kernel per call.  Other float8 dtypes raise NotImplementedError; scales without e4m3 pools, and e4m3 pools without block_table, RuntimeError."""
+    one more small kernel per call.  Other float8 dtypes raise NotImplementedError; scales without e4m3 pools, and e4m3 pools without block_table, RuntimeError.
+    return_softmax_lse (keyword-only; FlashAttention-2's name): return (o, lse), lse float32 (H_q, total_q), the natural-log
+    normaliser of each token and head, -inf for a row without a visible key; tokens no sequence owns hold unspecified values.  lse
+    is differentiable (fa_ex_backward_varlen_dlse); with block_table it is returned without a gradient, that path being forward only.
+    o has the bits of the call without the keyword, and so have the gradients while lse receives none.  (o, lse) pairs over
+    disjoint key sets merge with common.merge_states.merge_attention_states(..., layout="thd").  Chunking keys under `causal`:
+    per sequence the rule of flash_attention_ex's docstring — the chunk keys[j0:j1] of a sequence's Nk keys is causal=False,
+    window_size=(left', Nk - j1), the last chunk plain causal=True — which one call can express only where Nk - j1 is the same
+    for every sequence; sinks go to exactly one chunk; ALiBi across chunks is not expressible and out of scope."""
     window = _window_size(window_size)
     if block_table is not None:
         return _flash_attention_varlen_paged(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale,
-                                             causal, window, softcap, alibi_slopes, sinks, block_table, k_descale, v_descale)
+                                             causal, window, softcap, alibi_slopes, sinks, block_table, k_descale, v_descale,
+                                             return_softmax_lse)
     _no_fp8_without_table("flash_attention_varlen", k, v, k_descale, v_descale)
     if not q.is_cuda:
         raise RuntimeError("Inputs must be CUDA tensors")
     scale = (1.0 / math.sqrt(q.shape[-1])) if softmax_scale is None else float(softmax_scale)
     args = (q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), float(dropout_p), scale, bool(causal), window,
             int(seed))
+    if return_softmax_lse:
+        if isinstance(alibi_slopes, torch.Tensor):
+            alibi_slopes = alibi_slopes.detach()
+        if sinks is not None:
+            sinks = _sinks_units("flash_attention_varlen", sinks, q.shape[1])
+        return _FlashAttnVarlenLseFn.apply(*args, softcap, alibi_slopes, sinks)
     if softcap == 0.0 and alibi_slopes is None and sinks is None:
         return _FlashAttnVarlenFn.apply(*args)
     if isinstance(alibi_slopes, torch.Tensor):
@@ -267,7 +374,8 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
 
 
 def _flash_attention_varlen_paged(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale, causal,
-                                  window, softcap, alibi_slopes, sinks, block_table, k_descale=None, v_descale=None):
+                                  window, softcap, alibi_slopes, sinks, block_table, k_descale=None, v_descale=None,
+                                  return_softmax_lse=False):
     """flash_attention_varlen with a block_table: forward only, nothing differentiable"""
     who = "flash_attention_varlen"
     if not (isinstance(block_table, torch.Tensor) and block_table.dtype == torch.int32):
@@ -288,11 +396,11 @@ def _flash_attention_varlen_paged(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqle
     if sinks is not None:
         sinks = _sinks_units(who, sinks, q.shape[1]).detach()
     with torch.no_grad():
-        o, _lse = ext.ex_varlen_forward(q.detach(), k.detach(), v.detach(), cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q),
-                                        int(max_seqlen_k), bool(causal), scale, 0.0, 0, window=window, softcap=softcap,
-                                        alibi_slopes=alibi_slopes, sinks=sinks, block_table=block_table, k_descale=k_descale,
-                                        v_descale=v_descale)
-    return o
+        o, lse = ext.ex_varlen_forward(q.detach(), k.detach(), v.detach(), cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q),
+                                       int(max_seqlen_k), bool(causal), scale, 0.0, 0, window=window, softcap=softcap,
+                                       alibi_slopes=alibi_slopes, sinks=sinks, block_table=block_table, k_descale=k_descale,
+                                       v_descale=v_descale)
+    return (o, lse) if return_softmax_lse else o
 
 
 def _no_fp8_without_table(who, k, v, k_descale, v_descale):

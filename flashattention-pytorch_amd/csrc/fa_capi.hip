@@ -466,6 +466,7 @@ struct ExCall {
     double softmax_scale = 0.0, dropout_p = 0.0;
     ScoreMod sm;
     SinkArg sk;
+    const float* dlse = nullptr;   // fa_ex_backward_dlse: the gradient of lse, (bh, nq) float32
     const uint8_t *mask = nullptr, *block_mask = nullptr;
     int64_t mask_bh_stride = 0, br = 0, bc = 0;
     uint64_t dropout_seed = 0;
@@ -493,7 +494,20 @@ static fa::ExArgs ex_args(const ExCall& c, int causal, int64_t wl, int64_t wr) {
     a.window_right = wr;
     score_args(a, c.sm);
     sink_args(a, c.sk);
+    a.dlse = c.dlse;
     return a;
+}
+
+// the gradient of lse (fa_ex_backward_dlse / fa_ex_backward_varlen_dlse): null = none
+static int dlse_check(const char* who, const float* dlse) {
+    if ((uintptr_t)dlse % 4 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: dlse must be 4-byte aligned", who);
+    return FA_OK;
+}
+// A backward with query rows but without a key, with sinks and a gradient of lse: every row's lse is its head's sink, so
+// dsinks[h] = the sum of dlse over the rows of head h (empty_backward has zeroed it; the sum kernel overwrites it)
+static int no_key_dsinks(const char* who, const fa::ExArgs& a, hipStream_t st) {
+    if (!a.lse) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    return launched(who, fa::launch_ex_dsink(a, a.dlse, a.cu_q ? a.total_q : 0, 1, -1.f, st));
 }
 
 static int ex_forward_impl(const char* who, const ExCall& c) {
@@ -517,11 +531,15 @@ static int ex_backward_impl(const char* who, const ExCall& c) {
     int causal = c.causal;
     int64_t wl = c.window_left, wr = c.window_right;
     if (const int rc = ex_checks(who, c, true, causal, wl, wr); rc != FA_OK) return rc;
+    if (const int rc = dlse_check(who, c.dlse); rc != FA_OK) return rc;
     const bool no_q = c.bh == 0 || c.nq == 0, no_k = c.bh == 0 || c.nk == 0;
     const size_t es = c.dtype == FA_DTYPE_F32 ? 4 : 2;
-    if (no_q || no_k)   // (grouped: dk and dv hold bh / kv_group units)
-        return empty_backward(who, no_q && no_k, no_q, c.dq, (size_t)c.bh * c.nq * c.d * es, c.dk, c.dv,
-                              (size_t)(c.bh / c.kv_group) * c.nk * c.d * es, c.sk, reinterpret_cast<hipStream_t>(c.stream));
+    if (no_q || no_k) {   // (grouped: dk and dv hold bh / kv_group units)
+        const int rc = empty_backward(who, no_q && no_k, no_q, c.dq, (size_t)c.bh * c.nq * c.d * es, c.dk, c.dv,
+                                      (size_t)(c.bh / c.kv_group) * c.nk * c.d * es, c.sk, reinterpret_cast<hipStream_t>(c.stream));
+        if (rc != FA_OK || no_q || !c.sk.sinks || !c.dlse) return rc;
+        return no_key_dsinks(who, ex_args(c, causal, wl, wr), reinterpret_cast<hipStream_t>(c.stream));
+    }
     if (!c.q || !c.k || !c.v || !c.o || !c.do_ || !c.lse || !c.dq || !c.dk || !c.dv)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
     const size_t need = ex_bwd_ws_grouped(c.bh, c.kv_group, c.nq, c.nk, c.d, c.dtype);
@@ -669,6 +687,21 @@ int fa_ex_backward_sink(const void* q, const void* k, const void* v, const void*
     return ex_backward_impl("fa_ex_backward_sink", c);
 }
 
+int fa_ex_backward_dlse(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
+                        void* dv, int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype, int causal,
+                        int64_t window_left, int64_t window_right, double softmax_scale, double softcap, const float* alibi_slopes,
+                        int64_t alibi_heads, int64_t alibi_batch_stride, const float* sinks, int64_t sink_heads, float* dsinks,
+                        const float* dlse, const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br, int64_t bc,
+                        double dropout_p, uint64_t dropout_seed, void* workspace, size_t workspace_bytes, void* stream) {
+    ExCall c = ex_bwd_call(q, k, v, o, do_, lse, dq, dk, dv, bh, nq, nk, d, dtype, causal, softmax_scale, mask, mask_bh_stride, block_mask,
+                           br, bc, dropout_p, dropout_seed, workspace, workspace_bytes, stream);
+    c.kv_group = kv_group; c.window_left = window_left; c.window_right = window_right;
+    c.sm = {softcap, alibi_slopes, alibi_heads, alibi_batch_stride};
+    c.sk = {sinks, sink_heads, dsinks};
+    c.dlse = dlse;
+    return ex_backward_impl("fa_ex_backward_dlse", c);
+}
+
 // ---- variable-length (packed) sequences: see include/fa_mi355x.h
 // Everything that can be checked without reading cu_seqlens (which would take a synchronise), before any HIP call.
 // One call of the fa_ex_*_varlen* family, fa_ex_forward_varlen_paged / _paged_fp8 included.  Defaults: "argument absent"; cache_dtype is the
@@ -686,6 +719,7 @@ struct VarlenCall {
     uint64_t dropout_seed = 0;
     ScoreMod sm;            // (heads: heads_q)
     SinkArg sk;
+    const float* dlse = nullptr;   // fa_ex_backward_varlen_dlse: the gradient of lse, (heads_q, total_q) float32
     const int32_t* block_table = nullptr;   // the paged forward, and (cache_dtype, the scales) its e4m3 pool
     int64_t max_blocks_per_seq = 0, num_blocks = 0, page_block_size = 0, k_page_stride = 0, v_page_stride = 0, descale_batch_stride = 0;
     int cache_dtype = 0;
@@ -746,6 +780,7 @@ static fa::ExArgs varlen_args(const VarlenCall& c, int64_t total_k, int64_t max_
     a.stride_v = c.v_stride;
     score_args(a, c.sm);
     sink_args(a, c.sk);
+    a.dlse = c.dlse;
     return a;
 }
 
@@ -847,12 +882,16 @@ static int varlen_backward_impl(const char* who, const VarlenCall& c) {
     if (rc != FA_OK) return rc;
     if (c.heads_q >= 1 && (rc = score_check(who, c.sm, c.batch * c.heads_q)) != FA_OK) return rc;
     if ((rc = sink_check(who, c.sk, c.heads_q, true)) != FA_OK) return rc;
+    if ((rc = dlse_check(who, c.dlse)) != FA_OK) return rc;
     if ((rc = window_canon(who, c.max_seqlen_q, c.max_seqlen_k, causal, wl, wr)) != FA_OK) return rc;
     const bool no_q = c.total_q == 0 || c.max_seqlen_q == 0, no_k = c.total_k == 0 || c.max_seqlen_k == 0;
     const size_t es = c.dtype == FA_DTYPE_F32 ? 4 : 2;
-    if (no_q || no_k)   // ... in every sequence
-        return empty_backward(who, no_q && no_k, no_q, c.dq, (size_t)c.total_q * c.heads_q * c.d * es, c.dk, c.dv,
-                              (size_t)c.total_k * c.heads_kv * c.d * es, c.sk, reinterpret_cast<hipStream_t>(c.stream));
+    if (no_q || no_k) {   // ... in every sequence
+        rc = empty_backward(who, no_q && no_k, no_q, c.dq, (size_t)c.total_q * c.heads_q * c.d * es, c.dk, c.dv,
+                            (size_t)c.total_k * c.heads_kv * c.d * es, c.sk, reinterpret_cast<hipStream_t>(c.stream));
+        if (rc != FA_OK || no_q || !c.sk.sinks || !c.dlse) return rc;
+        return no_key_dsinks(who, varlen_args(c, c.total_k, c.max_seqlen_k, causal, wl, wr), reinterpret_cast<hipStream_t>(c.stream));
+    }
     if (!c.q || !c.k || !c.v || !c.o || !c.do_ || !c.lse || !c.dq || !c.dk || !c.dv)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
     const size_t need = fa_ex_backward_workspace_bytes_varlen(c.heads_q, c.heads_kv, c.total_q, c.total_k, c.d, c.dtype);
@@ -904,6 +943,23 @@ int fa_ex_backward_varlen_sink(const void* q, const void* k, const void* v, cons
     c.sm = {softcap, alibi_slopes, heads_q, alibi_batch_stride};
     c.sk = {sinks, sink_heads, dsinks};
     return varlen_backward_impl("fa_ex_backward_varlen_sink", c);
+}
+
+int fa_ex_backward_varlen_dlse(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
+                               void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                               int64_t total_q, int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
+                               int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                               double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, const float* sinks,
+                               int64_t sink_heads, float* dsinks, const float* dlse, double dropout_p, uint64_t dropout_seed, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    VarlenCall c = varlen_bwd_call(q, k, v, o, do_, lse, dq, dk, dv, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k,
+                                   max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride, causal, window_left, window_right,
+                                   softmax_scale, workspace, workspace_bytes);
+    c.dropout_p = dropout_p; c.dropout_seed = dropout_seed; c.stream = stream;
+    c.sm = {softcap, alibi_slopes, heads_q, alibi_batch_stride};
+    c.sk = {sinks, sink_heads, dsinks};
+    c.dlse = dlse;
+    return varlen_backward_impl("fa_ex_backward_varlen_dlse", c);
 }
 
 // ---- the varlen forward over a paged K/V cache: see include/fa_mi355x.h
@@ -1580,6 +1636,129 @@ int fa_rotary_apply(const void* x, void* y, int64_t batch, int64_t seqlen, int64
     c.conjugate = conjugate; c.seqlen_offset = seqlen_offset; c.seqlen_offsets = seqlen_offsets;
     c.cu_seqlens = cu_seqlens; c.total = total; c.max_seqlen = max_seqlen; c.stream = stream;
     return rotary_impl("fa_rotary_apply", c);
+}
+
+// ---- merge of two partial attention results: see include/fa_mi355x.h
+// One call of the fa_merge_states family (forward and backward): a tensor is a pointer and its (batch, head, row) strides.
+struct MergeCall {
+    fa::MergeTensor o_a, lse_a, o_b, lse_b, o, lse, do_, dlse, do_a, do_b, dlse_a, dlse_b;
+    int64_t batch = 0, heads = 0, rows = 0, d = 0;
+    int dtype = 0;
+    void* stream = nullptr;
+};
+
+static int merge_impl(const char* who, const MergeCall& c, bool backward) {
+    struct Named { const char* name; const fa::MergeTensor* t; bool wide, optional; };   // wide: d elements of the dtype per row
+    const Named fwd[] = {{"o_a", &c.o_a, true, false}, {"lse_a", &c.lse_a, false, false}, {"o_b", &c.o_b, true, false},
+                         {"lse_b", &c.lse_b, false, false}, {"o", &c.o, true, false}, {"lse", &c.lse, false, false}};
+    const Named bwd[] = {{"o_a", &c.o_a, true, false}, {"lse_a", &c.lse_a, false, false}, {"o_b", &c.o_b, true, false},
+                         {"lse_b", &c.lse_b, false, false}, {"do_", &c.do_, true, false}, {"dlse", &c.dlse, false, true},
+                         {"do_a", &c.do_a, true, false}, {"do_b", &c.do_b, true, false}, {"dlse_a", &c.dlse_a, false, false},
+                         {"dlse_b", &c.dlse_b, false, false}};
+    const Named* ts = backward ? bwd : fwd;
+    const int nt = backward ? 10 : 6;
+    if (c.dtype != FA_DTYPE_F32 && c.dtype != FA_DTYPE_F16 && c.dtype != FA_DTYPE_BF16)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: unknown dtype code %d", who, c.dtype);
+    const int64_t lim = (int64_t)1 << 31;
+    if (c.batch < 0 || c.heads < 0 || c.rows < 0 || c.d < 1 || c.batch >= lim || c.heads >= lim || c.rows >= lim)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: bad shape (batch=%lld, heads=%lld, rows=%lld, d=%lld)", who, (long long)c.batch,
+                    (long long)c.heads, (long long)c.rows, (long long)c.d);
+    if (c.d > 256) return fail(FA_ERR_UNSUPPORTED, "%s: head_dim %lld > 256 is not supported", who, (long long)c.d);
+    const bool f32 = c.dtype == FA_DTYPE_F32;
+    if (!f32 && c.d % 8 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: head_dim must be a multiple of 8 for 16-bit tensors (got %lld)", who, (long long)c.d);
+    if (c.batch == 0 || c.heads == 0 || c.rows == 0) return FA_OK;   // no row: no launch
+    if (c.batch * c.heads >= lim) return fail(FA_ERR_UNSUPPORTED, "%s: batch * heads too large for one launch", who);
+    for (int i = 0; i < nt; ++i)
+        if (!ts[i].t->p && !ts[i].optional) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer (%s)", who, ts[i].name);
+    bool vec = f32 && c.d % 4 == 0;   // fp32: 16-byte accesses where everything allows them, 4-byte ones otherwise
+    for (int i = 0; i < nt; ++i) {
+        const Named& n = ts[i];
+        if (!n.t->p) continue;
+        const uintptr_t ptr = (uintptr_t)n.t->p;
+        if (!n.wide || f32) {
+            if (ptr % 4 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: %s must be 4-byte aligned", who, n.name);
+            if (n.wide && (ptr % 16 != 0 || n.t->bs % 4 != 0 || n.t->hs % 4 != 0 || n.t->rs % 4 != 0)) vec = false;
+        } else {
+            if (ptr % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: %s must be 16-byte aligned", who, n.name);
+            if (n.t->bs % 8 != 0 || n.t->hs % 8 != 0 || n.t->rs % 8 != 0)
+                return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (%lld, %lld, %lld) must be multiples of 8 elements", who, n.name,
+                            (long long)n.t->bs, (long long)n.t->hs, (long long)n.t->rs);
+        }
+    }
+    // no 64-bit byte offset can overflow: every (extent - 1) * stride stays below 2^58 elements
+    const int64_t kSpan = (int64_t)1 << 58;
+    for (int i = 0; i < nt; ++i) {
+        const fa::MergeTensor& t = *ts[i].t;
+        if (!t.p) continue;
+        const int64_t ext[3] = {c.batch, c.heads, c.rows}, str[3] = {t.bs, t.hs, t.rs};
+        for (int j = 0; j < 3; ++j)
+            if (str[j] < 0 || (ext[j] > 1 && str[j] > kSpan / (ext[j] - 1)))
+                return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (%lld, %lld, %lld) must be >= 0 with (extent - 1) * stride <= 2^58",
+                            who, ts[i].name, (long long)t.bs, (long long)t.hs, (long long)t.rs);
+    }
+    if (!backward) {   // the in-place forms: the output pair on one of the input pairs, with that one's strides
+        const fa::MergeTensor* pairs[2][2] = {{&c.o_a, &c.lse_a}, {&c.o_b, &c.lse_b}};
+        for (auto& pr : pairs) {
+            const bool same_o = c.o.p == pr[0]->p, same_l = c.lse.p == pr[1]->p;
+            if ((same_o && (c.o.bs != pr[0]->bs || c.o.hs != pr[0]->hs || c.o.rs != pr[0]->rs)) ||
+                (same_l && (c.lse.bs != pr[1]->bs || c.lse.hs != pr[1]->hs || c.lse.rs != pr[1]->rs)))
+                return fail(FA_ERR_INVALID_ARGUMENT, "%s: an output that is an input (in place) needs that input's strides", who);
+        }
+    }
+    fa::MergeArgs a;
+    a.o_a = c.o_a; a.lse_a = c.lse_a; a.o_b = c.o_b; a.lse_b = c.lse_b; a.o = c.o; a.lse = c.lse;
+    a.dout = c.do_; a.dlse = c.dlse; a.do_a = c.do_a; a.do_b = c.do_b; a.dlse_a = c.dlse_a; a.dlse_b = c.dlse_b;
+    a.batch = c.batch; a.heads = c.heads; a.rows = c.rows; a.d = c.d; a.dtype = c.dtype; a.vec = vec;
+    return launched(who, fa::launch_merge(a, backward, reinterpret_cast<hipStream_t>(c.stream)));
+}
+
+static fa::MergeTensor merge_t(const void* p, int64_t bs, int64_t hs, int64_t rs) {
+    fa::MergeTensor t;
+    t.p = p; t.bs = bs; t.hs = hs; t.rs = rs;
+    return t;
+}
+
+int fa_merge_states(const void* o_a, const float* lse_a, const void* o_b, const float* lse_b, void* o, float* lse, int64_t batch,
+                    int64_t heads, int64_t rows, int64_t d, int dtype, int64_t o_a_batch_stride, int64_t o_a_head_stride,
+                    int64_t o_a_row_stride, int64_t lse_a_batch_stride, int64_t lse_a_head_stride, int64_t lse_a_row_stride,
+                    int64_t o_b_batch_stride, int64_t o_b_head_stride, int64_t o_b_row_stride, int64_t lse_b_batch_stride,
+                    int64_t lse_b_head_stride, int64_t lse_b_row_stride, int64_t o_batch_stride, int64_t o_head_stride,
+                    int64_t o_row_stride, int64_t lse_batch_stride, int64_t lse_head_stride, int64_t lse_row_stride, void* stream) {
+    MergeCall c;
+    c.o_a = merge_t(o_a, o_a_batch_stride, o_a_head_stride, o_a_row_stride);
+    c.lse_a = merge_t(lse_a, lse_a_batch_stride, lse_a_head_stride, lse_a_row_stride);
+    c.o_b = merge_t(o_b, o_b_batch_stride, o_b_head_stride, o_b_row_stride);
+    c.lse_b = merge_t(lse_b, lse_b_batch_stride, lse_b_head_stride, lse_b_row_stride);
+    c.o = merge_t(o, o_batch_stride, o_head_stride, o_row_stride);
+    c.lse = merge_t(lse, lse_batch_stride, lse_head_stride, lse_row_stride);
+    c.batch = batch; c.heads = heads; c.rows = rows; c.d = d; c.dtype = dtype; c.stream = stream;
+    return merge_impl("fa_merge_states", c, false);
+}
+
+int fa_merge_states_backward(const void* o_a, const float* lse_a, const void* o_b, const float* lse_b, const void* do_, const float* dlse,
+                             void* do_a, void* do_b, float* dlse_a, float* dlse_b, int64_t batch, int64_t heads, int64_t rows, int64_t d,
+                             int dtype, int64_t o_a_batch_stride, int64_t o_a_head_stride, int64_t o_a_row_stride,
+                             int64_t lse_a_batch_stride, int64_t lse_a_head_stride, int64_t lse_a_row_stride, int64_t o_b_batch_stride,
+                             int64_t o_b_head_stride, int64_t o_b_row_stride, int64_t lse_b_batch_stride, int64_t lse_b_head_stride,
+                             int64_t lse_b_row_stride, int64_t do_batch_stride, int64_t do_head_stride, int64_t do_row_stride,
+                             int64_t dlse_batch_stride, int64_t dlse_head_stride, int64_t dlse_row_stride, int64_t do_a_batch_stride,
+                             int64_t do_a_head_stride, int64_t do_a_row_stride, int64_t do_b_batch_stride, int64_t do_b_head_stride,
+                             int64_t do_b_row_stride, int64_t dlse_a_batch_stride, int64_t dlse_a_head_stride, int64_t dlse_a_row_stride,
+                             int64_t dlse_b_batch_stride, int64_t dlse_b_head_stride, int64_t dlse_b_row_stride, void* stream) {
+    MergeCall c;
+    c.o_a = merge_t(o_a, o_a_batch_stride, o_a_head_stride, o_a_row_stride);
+    c.lse_a = merge_t(lse_a, lse_a_batch_stride, lse_a_head_stride, lse_a_row_stride);
+    c.o_b = merge_t(o_b, o_b_batch_stride, o_b_head_stride, o_b_row_stride);
+    c.lse_b = merge_t(lse_b, lse_b_batch_stride, lse_b_head_stride, lse_b_row_stride);
+    c.do_ = merge_t(do_, do_batch_stride, do_head_stride, do_row_stride);
+    c.dlse = merge_t(dlse, dlse_batch_stride, dlse_head_stride, dlse_row_stride);
+    c.do_a = merge_t(do_a, do_a_batch_stride, do_a_head_stride, do_a_row_stride);
+    c.do_b = merge_t(do_b, do_b_batch_stride, do_b_head_stride, do_b_row_stride);
+    c.dlse_a = merge_t(dlse_a, dlse_a_batch_stride, dlse_a_head_stride, dlse_a_row_stride);
+    c.dlse_b = merge_t(dlse_b, dlse_b_batch_stride, dlse_b_head_stride, dlse_b_row_stride);
+    c.batch = batch; c.heads = heads; c.rows = rows; c.d = d; c.dtype = dtype; c.stream = stream;
+    return merge_impl("fa_merge_states_backward", c, true);
 }
 
 size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {

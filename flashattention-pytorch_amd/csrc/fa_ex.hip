@@ -381,9 +381,14 @@ __global__ __launch_bounds__(NW * 64) void ex_fwd_varlen_paged_kernel(const T* _
     ex_fwd_body<T, DP, NW, WIN, true>(q, k, v, o, lse, p);
 }
 
+// dlse != null (fa_ex_backward_dlse): the gradient of the row's lse leaves the row constant, delta - dlse, so that the kernels'
+// dS = P (dP - delta) becomes P (dP - delta + dlse); a row whose lse is -inf (no visible key) ignores its dlse.  lse and dlse are
+// indexed by the row, or (hq > 0: packed sequences, rows in (token, head) order) at [head * total_q + token].
 template <typename T>
 __global__ __launch_bounds__(256) void ex_delta_kernel(const T* __restrict__ o, const T* __restrict__ dout,
-                                                       float* __restrict__ delta, long long rows, int d) {
+                                                       float* __restrict__ delta, long long rows, int d,
+                                                       const float* __restrict__ lse, const float* __restrict__ dlse, long long hq,
+                                                       long long total_q) {
     const long long row = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
     const int sub = threadIdx.x & 15;
     float s = 0.f;
@@ -393,7 +398,13 @@ __global__ __launch_bounds__(256) void ex_delta_kernel(const T* __restrict__ o, 
     s += __shfl_xor(s, 2, 64);
     s += __shfl_xor(s, 4, 64);
     s += __shfl_xor(s, 8, 64);
-    if (row < rows && sub == 0) delta[row] = s;
+    if (row < rows && sub == 0) {
+        if (dlse) {
+            const long long li = hq > 0 ? (row % hq) * total_q + row / hq : row;
+            if (lse[li] != -INFINITY) s -= dlse[li];
+        }
+        delta[row] = s;
+    }
 }
 
 // ---- backward dK/dV: one workgroup = 16 NW keys resident in LDS; loops over 32-row query tiles
@@ -814,7 +825,8 @@ static hipError_t ex_bwd_t(const ExArgs& a, hipStream_t st) {
     const auto p = ex_params<SC>(a);
     ProfScope ps(K_EX_BWD, st);
     hipLaunchKernelGGL(ex_delta_kernel<T>, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, (const T*)a.o,
-                       (const T*)a.dout, delta, rows, (int)a.d);
+                       (const T*)a.dout, delta, rows, (int)a.d, (const float*)a.lse, a.dlse, VAR ? (long long)a.heads_q : 0LL,
+                       (long long)a.total_q);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (a.sinks) {   // (delta rows: (unit, row), varlen (token, head))
@@ -874,7 +886,9 @@ static hipError_t launch_ex_one(const ExArgs& a, bool backward, hipStream_t st) 
     // (a window that bounds something never leaves this file's families: the plain, nq != nk and fa_generic kernels know no band)
     // (nor does a score modifier: the plain, Nq != Nk and fa_generic kernels and the dS hand-over know none)
     // (nor do sinks)
-    const bool win = ex_windowed(a), mod = ex_scoremod(a) || a.sinks != nullptr;
+    // (nor does a gradient of lse: the plain kernels make their row constants inside the matrix kernels or hand dS over; a call with
+    // dlse takes the recomputing kernels, whose pre-pass is a launch of its own — DESIGN.md 9p)
+    const bool win = ex_windowed(a), mod = ex_scoremod(a) || a.sinks != nullptr || a.dlse != nullptr;
     const bool plain = (path == 0 || path == 2) && !win && !mod && !a.mask && !a.block_mask && a.dropout_p <= 0.0 && a.scale > 0.f;
     if (plain && a.nq == a.nk && (backward ? bwd_mfma_supported(a.dtype, a.d) : fwd_mfma_supported(a.dtype, a.d))) {
         if (!backward) {

@@ -295,10 +295,13 @@ __global__ __launch_bounds__(512, 2) void exm_fwd_paged_kernel(const uint16_t* _
 // ------------------------------------------------------------------------------------------------ row constants
 // nlse = -lse / scale (0 for a row without a visible key: every element of such a row is masked by a select, and an
 // infinite initial accumulator would only make NaNs on the way), ndelta = -rowsum(dO * O).  16 lanes per row.
+// dlse != null (fa_ex_backward_dlse): ndelta = dlse - rowsum(dO * O), the gradient of the row's lse, which is all a gradient of lse
+// does to the backward (dS = P (dP + ndelta)); a row whose lse is -inf ignores its dlse.
 template <typename Tag>
 __global__ __launch_bounds__(256) void exm_prep_kernel(const uint16_t* __restrict__ o, const uint16_t* __restrict__ dout,
                                                        const float* __restrict__ lse, float* __restrict__ nlse,
-                                                       float* __restrict__ ndelta, long long rows, int d, float inv_scale) {
+                                                       float* __restrict__ ndelta, long long rows, int d, float inv_scale,
+                                                       const float* __restrict__ dlse) {
     const long long row = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
     const int sub = threadIdx.x & 15;
     float s = 0.f;
@@ -315,7 +318,7 @@ __global__ __launch_bounds__(256) void exm_prep_kernel(const uint16_t* __restric
     if (row < rows && sub == 0) {
         const float l = lse[row];
         nlse[row] = (l == -INFINITY) ? 0.f : -l * inv_scale;
-        ndelta[row] = -s;
+        ndelta[row] = (dlse && l != -INFINITY) ? dlse[row] - s : -s;
     }
 }
 
@@ -325,7 +328,7 @@ template <typename Tag>
 __global__ __launch_bounds__(256) void exm_prep_varlen_kernel(const uint16_t* __restrict__ o, const uint16_t* __restrict__ dout,
                                                               const float* __restrict__ lse, float* __restrict__ nlse,
                                                               float* __restrict__ ndelta, int total_q, int tph, int hq, int d,
-                                                              float inv_scale) {
+                                                              float inv_scale, const float* __restrict__ dlse) {
     const int hd = blockIdx.x / tph;
     const int tok = (blockIdx.x - hd * tph) * 16 + (threadIdx.x >> 4);
     const int sub = threadIdx.x & 15;
@@ -345,7 +348,7 @@ __global__ __launch_bounds__(256) void exm_prep_varlen_kernel(const uint16_t* __
         const size_t i = (size_t)hd * total_q + tok;
         const float l = lse[i];
         nlse[i] = (l == -INFINITY) ? 0.f : -l * inv_scale;
-        ndelta[i] = -s;
+        ndelta[i] = (dlse && l != -INFINITY) ? dlse[i] - s : -s;
     }
 }
 
@@ -432,7 +435,7 @@ static hipError_t exm_bwd_t(const ExArgs& a, hipStream_t st) {
     const float c = a.scale * 1.4426950408889634f;
     ProfScope ps(K_EX_BWD, st);
     hipLaunchKernelGGL(exm_prep_kernel<Tag>, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, (const uint16_t*)a.o,
-                       (const uint16_t*)a.dout, (const float*)a.lse, nlse, ndelta, rows, (int)a.d, 1.f / a.scale);
+                       (const uint16_t*)a.dout, (const float*)a.lse, nlse, ndelta, rows, (int)a.d, 1.f / a.scale, a.dlse);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (a.sinks) {   // the sink's gradient from the caller's lse and the -delta just written
@@ -540,7 +543,7 @@ static hipError_t exm_varlen_t(const ExArgs& a, bool backward, hipStream_t st) {
     ProfScope ps(K_EX_BWD, st);
     hipLaunchKernelGGL(exm_prep_varlen_kernel<Tag>, dim3((unsigned)(tph * a.heads_q)), dim3(256), 0, st, (const uint16_t*)a.o,
                        (const uint16_t*)a.dout, (const float*)a.lse, nlse, ndelta, (int)a.total_q, tph, (int)a.heads_q, (int)a.d,
-                       1.f / a.scale);
+                       1.f / a.scale, a.dlse);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (a.sinks) {   // (-delta at (head, token), as lse)

@@ -159,6 +159,10 @@ struct ExArgs {
     const float* sinks = nullptr;
     int64_t sink_heads = 1;
     float* dsinks = nullptr;
+    // the gradient of lse (fa_ex_backward_dlse / fa_ex_backward_varlen_dlse; null: none): float32 in lse's layout, added to the row
+    // constant the backward kernels read, -delta + dlse; rows whose lse is -inf ignore it.  Such a call runs the recomputing extended
+    // kernels (fa_ex_mfma.hip, fa_ex.hip), whose pre-pass is a launch of its own.
+    const float* dlse = nullptr;
     // paged K/V of the varlen forward (fa_ex_forward_varlen_paged; block_table != null, forward only, no dropout): k and v are pools
     // (num_blocks, page_size, heads_q / kv_group, d) with token strides stride_k / stride_v and page strides page_stride_k / _v;
     // key t of sequence b is row t % page_size of page block_table[b * max_blocks + t / page_size] (untrusted device numbers);
@@ -266,6 +270,23 @@ struct RotaryArgs {
     int64_t total, max_seqlen;
 };
 hipError_t launch_rotary(const RotaryArgs& a, hipStream_t st);
+
+// Merge of two partial attention results over disjoint key sets (fa_merge.hip; fa_merge_states / fa_merge_states_backward).  Every
+// tensor is addressed by (batch, head, row) through a stride triple in elements; the d elements of an o-like row are contiguous.
+struct MergeTensor {
+    const void* p = nullptr;
+    int64_t bs = 0, hs = 0, rs = 0;
+};
+struct MergeArgs {
+    MergeTensor o_a, lse_a, o_b, lse_b;   // inputs of both directions
+    MergeTensor o, lse;                   // forward outputs (o == o_a and lse == lse_a with equal strides: in place)
+    MergeTensor dout, dlse;               // backward inputs (dlse.p null: zero)
+    MergeTensor do_a, do_b, dlse_a, dlse_b;   // backward outputs
+    int64_t batch = 0, heads = 0, rows = 0, d = 0;
+    int dtype = 0;
+    bool vec = true;                      // fp32 only: 16-byte accesses (d % 4 == 0 and everything aligned); else 4-byte ones
+};
+hipError_t launch_merge(const MergeArgs& a, bool backward, hipStream_t st);
 
 // Grouped-query attention (fa_kv_group.hip): dk[u] = sum over m = 0 .. g-1 of pk[u g + m] (and dv from pv), accumulated in fp32 in
 // that order and rounded once to the tensor dtype; units of nk * d elements, bh / g of them in dk and dv.

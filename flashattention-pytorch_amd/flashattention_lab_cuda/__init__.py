@@ -49,6 +49,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_ex_forward_kvcache_varlen", "fa_ex_kvcache_workspace_bytes_varlen",
     "fa_ex_forward_varlen_paged", "fa_ex_forward_varlen_paged_fp8",
     "fa_rotary_apply",
+    "fa_ex_backward_dlse", "fa_ex_backward_varlen_dlse", "fa_merge_states", "fa_merge_states_backward",
 )
 
 
@@ -78,6 +79,7 @@ _MOD = _fields("d:softcap p:alibi_slopes i:alibi_heads,alibi_batch_stride")
 _MODH = _fields("d:softcap p:alibi_slopes i:alibi_batch_stride")   # varlen and KV-cache: one slope per query head
 _SINK = _fields("p:sinks i:sink_heads")
 _DSINK = _fields("p:dsinks")
+_DLSE = _fields("p:dlse")                                     # the gradient of lse, after the sink group
 _MASKS = _fields("p:mask i:mask_bh_stride p:block_mask i:br,bc")
 _DROPOUT = _fields("d:dropout_p u:dropout_seed")
 _VARLEN = _fields("p:cu_seqlens_q,cu_seqlens_k i:batch,heads_q,heads_kv,total_q,total_k,max_seqlen_q,max_seqlen_k,d c:dtype "
@@ -95,6 +97,13 @@ _KVVARLEN = _fields("p:cu_seqlens_q,cu_seqlens_k_new i:total_q,max_seqlen_q,tota
 _KVWS = _fields("i:batch,heads_q,heads_kv,seqlen_q,cache_len,d,num_splits")
 _ROXY = _fields("p:x,y i:batch,seqlen,heads,d c:dtype i:x_batch_stride,x_token_stride,y_batch_stride,y_token_stride")
 _ROPOS = _fields("c:conjugate i:seqlen_offset p:seqlen_offsets,cu_seqlens i:total,max_seqlen")
+_MDIMS = _fields("i:batch,heads,rows,d c:dtype")
+
+
+def _strides(*tensors):
+    """the (batch, head, row) stride triple of each named tensor of the merge calls"""
+    return sum((_fields(f"i:{t}_batch_stride,{t}_head_stride,{t}_row_stride") for t in tensors), ())
+
 
 _SIGNATURES = {}
 
@@ -132,6 +141,8 @@ for _dir, _ptrs, _tail, _ds in (("forward", _FWD, _STREAM, ()), ("backward", _BW
     _sig(f"fa_ex_{_dir}_varlen", _ptrs + _VARLEN + _DROPOUT + _tail)
     _sig(f"fa_ex_{_dir}_varlen_scoremod", _ptrs + _VARLEN + _MODH + _DROPOUT + _tail)
     _sig(f"fa_ex_{_dir}_varlen_sink", _ptrs + _VARLEN + _MODH + _SINK + _ds + _DROPOUT + _tail)
+_sig("fa_ex_backward_dlse", _ex_sig(_BWD, _WS, _GROUP, _WINDOW, _MOD + _SINK + _DSINK + _DLSE))
+_sig("fa_ex_backward_varlen_dlse", _BWD + _VARLEN + _MODH + _SINK + _DSINK + _DLSE + _DROPOUT + _WS)
 _sig("fa_ex_forward_varlen_paged", _FWD + _VARLEN + _MODH + _SINK + _VPAGED + _STREAM)
 _sig("fa_ex_forward_varlen_paged_fp8", _FWD + _VARLEN + _MODH + _SINK + _VPAGED + _FP8 + _STREAM)
 _sig("fa_ex_backward_workspace_bytes", _fields("i:bh") + _EXDIMS, _SIZE)
@@ -145,6 +156,9 @@ for _suffix, _added in (("", ()), ("_paged", _PAGED), ("_rotary", _ROTARY), ("_f
     _sig("fa_ex_forward_kvcache" + _suffix, _kv + _WS)
 _sig("fa_ex_kvcache_workspace_bytes fa_ex_kvcache_workspace_bytes_sink", _KVWS, _SIZE)
 _sig("fa_rotary_apply", _ROXY + _ROTARY + _ROPOS + _STREAM)
+_sig("fa_merge_states", _fields("p:o_a,lse_a,o_b,lse_b,o,lse") + _MDIMS + _strides("o_a", "lse_a", "o_b", "lse_b", "o", "lse") + _STREAM)
+_sig("fa_merge_states_backward", _fields("p:o_a,lse_a,o_b,lse_b,do_,dlse,do_a,do_b,dlse_a,dlse_b") + _MDIMS +
+     _strides("o_a", "lse_a", "o_b", "lse_b", "do", "dlse", "do_a", "do_b", "dlse_a", "dlse_b") + _STREAM)
 _sig("fa_ex_kvcache_workspace_bytes_varlen", _fields("i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,d,num_splits c:with_sinks"), _SIZE)
 
 
@@ -176,11 +190,14 @@ def _family(widest, narrower):
         _CALLS[name] = (getattr(_lib, name), own, len(wide))
 
 
-for _dir in ("forward", "backward"):
-    _family(f"fa_ex_{_dir}_sink", [f"fa_ex_{_dir}{_suffix}" for _suffix in ("", "_grouped", "_window", "_scoremod")])
-    _family(f"fa_ex_{_dir}_varlen_sink", [f"fa_ex_{_dir}_varlen", f"fa_ex_{_dir}_varlen_scoremod"])
+_family("fa_ex_forward_sink", ["fa_ex_forward" + _suffix for _suffix in ("", "_grouped", "_window", "_scoremod")])
+_family("fa_ex_forward_varlen_sink", ["fa_ex_forward_varlen", "fa_ex_forward_varlen_scoremod"])
+_family("fa_ex_backward_dlse", ["fa_ex_backward" + _suffix for _suffix in ("", "_grouped", "_window", "_scoremod", "_sink")])
+_family("fa_ex_backward_varlen_dlse", ["fa_ex_backward_varlen" + _suffix for _suffix in ("", "_scoremod", "_sink")])
 _family("fa_ex_forward_varlen_paged_fp8", ["fa_ex_forward_varlen_paged"])
 _family("fa_rotary_apply", [])
+_family("fa_merge_states", [])
+_family("fa_merge_states_backward", [])
 _family("fa_ex_forward_kvcache_varlen", ["fa_ex_forward_kvcache" + _suffix for _suffix in ("", "_paged", "_rotary", "_fp8", "_sink")])
 
 
@@ -378,6 +395,16 @@ def fa3_backward(q, k, v, o, do_, lse, causal, softmax_scale, br, bc, stages, fp
 
 # ---- extended attention (include/fa_mi355x.h: fa_ex_forward / fa_ex_backward) ----
 
+def _dlse_arg(who, dlse, lse, form):
+    """dlse, the gradient of lse, contiguous: float32 with exactly lse's shape on lse's device; None passes through"""
+    if dlse is None:
+        return None
+    if not isinstance(dlse, torch.Tensor) or dlse.dtype != torch.float32 or dlse.shape != lse.shape or dlse.device != lse.device:
+        got = f"{tuple(dlse.shape)} {dlse.dtype} on {dlse.device}" if isinstance(dlse, torch.Tensor) else type(dlse).__name__
+        raise RuntimeError(f"{who}: dlse must be a {form} float32 tensor on lse's device, lse's shape {tuple(lse.shape)}; got {got}")
+    return dlse.contiguous()
+
+
 def _ex_common(who, q, k, v, mask, block_mask, br, bc):
     for t in (q, k, v):
         if not t.is_cuda:
@@ -509,9 +536,9 @@ def sinks_arg(who, sinks, device, units, heads=None):
     return sinks.data_ptr(), sinks.shape[0], sinks
 
 
-def _ex_variant(sinks, mod, window, grouped=False) -> str:
+def _ex_variant(sinks, mod, window, grouped=False, dlse=False) -> str:
     """the narrowest entry point of a family that takes what the call carries: each one adds a group of arguments to the one before"""
-    return "_sink" if sinks else "_scoremod" if mod else "_window" if window else "_grouped" if grouped else ""
+    return "_dlse" if dlse else "_sink" if sinks else "_scoremod" if mod else "_window" if window else "_grouped" if grouped else ""
 
 
 def ex_forward(q, k, v, causal, softmax_scale, mask=None, block_mask=None, br=128, bc=128, dropout_p=0.0, seed=0, window=(-1, -1),
@@ -540,9 +567,10 @@ def ex_forward(q, k, v, causal, softmax_scale, mask=None, block_mask=None, br=12
 
 
 def ex_backward(q, k, v, o, do_, lse, causal, softmax_scale, mask=None, block_mask=None, br=128, bc=128, dropout_p=0.0, seed=0,
-                window=(-1, -1), softcap=0.0, alibi_slopes=None, sinks=None):
+                window=(-1, -1), softcap=0.0, alibi_slopes=None, *, dlse=None, sinks=None):
     """(dq, dk, dv) of ex_forward; with sinks (and the lse ex_forward returned with them) also dsinks, float32 (sink_heads,), as a
-    fourth result (fa_ex_backward_sink)."""
+    fourth result (fa_ex_backward_sink).  dlse: the gradient of lse, float32 (BH, Nq) on q's device, or None
+    (fa_ex_backward_dlse); rows whose lse is -inf ignore it.  dlse is keyword-only, and sinks with it: sinks stays the last parameter."""
     wl, wr = window_arg("ex_backward", window)
     cap = softcap_arg("ex_backward", softcap)
     q, k, v, o, do_, lse = (t.contiguous() for t in (q, k, v, o, do_, lse))
@@ -552,10 +580,12 @@ def ex_backward(q, k, v, o, do_, lse, causal, softmax_scale, mask=None, block_ma
     mod = cap > 0.0 or aptr != 0 or sptr != 0
     if o.shape != q.shape or do_.shape != q.shape or lse.shape != (bh, nq) or lse.dtype != torch.float32:
         raise RuntimeError("ex_backward: o, do must be (BH, Nq, d) and lse (BH, Nq) float32")
+    dlse = _dlse_arg("ex_backward", dlse, lse, "(BH, Nq)")
     with torch.cuda.device(q.device):
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        extras = int(mask is not None or block_mask is not None or dropout_p > 0.0 or mod or
-                     window_effective(nq, nk, bool(causal), (wl, wr)))   # (the dS hand-over serves neither a window nor a modifier)
+        extras = int(mask is not None or block_mask is not None or dropout_p > 0.0 or mod or dlse is not None or
+                     window_effective(nq, nk, bool(causal), (wl, wr)))   # (the dS hand-over serves neither a window nor a modifier,
+        #                                                                    nor a gradient of lse)
         if g > 1 or (wl, wr) != (-1, -1) or mod:   # (+ the per-query-head dK / dV partials the library sums over each group)
             small = int(_lib.fa_ex_backward_workspace_bytes_grouped(bh, g, nq, nk, d, code))
             fast = int(_lib.fa_ex_backward_workspace_bytes_fast_grouped(bh, g, nq, nk, d, code, int(bool(causal)), extras))
@@ -568,10 +598,10 @@ def ex_backward(q, k, v, o, do_, lse, causal, softmax_scale, mask=None, block_ma
         ws = _workspace(q.device, nbytes)
         nbytes = max(nbytes, 0 if capturing else _workspaces.capacity(q.device, _stream_ptr(q.device)))
         dsinks = torch.empty((sheads,), dtype=torch.float32, device=q.device) if sptr else None
-        _call("fa_ex_backward" + _ex_variant(sptr, mod, (wl, wr) != (-1, -1), g > 1), (
+        _call("fa_ex_backward" + _ex_variant(sptr, mod, (wl, wr) != (-1, -1), g > 1, dlse is not None), (
             q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do_.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
             dv.data_ptr(), bh, g, nq, nk, d, code, int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, aheads, astride, sptr,
-            sheads, _ptr(dsinks), mptr, mstride, bptr, int(br), int(bc), float(dropout_p), int(seed) & (2 ** 64 - 1), ws.data_ptr(),
+            sheads, _ptr(dsinks), _ptr(dlse), mptr, mstride, bptr, int(br), int(bc), float(dropout_p), int(seed) & (2 ** 64 - 1), ws.data_ptr(),
             nbytes, _stream_ptr(q.device)))
     return (dq, dk, dv, dsinks) if sptr else (dq, dk, dv)
 
@@ -730,9 +760,10 @@ def ex_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seq
 
 
 def ex_varlen_backward(q, k, v, o, do_, lse, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale,
-                       dropout_p=0.0, seed=0, window=(-1, -1), softcap=0.0, alibi_slopes=None, sinks=None):
+                       dropout_p=0.0, seed=0, window=(-1, -1), softcap=0.0, alibi_slopes=None, *, dlse=None, sinks=None):
     """(dq, dk, dv) of ex_varlen_forward: dq in q's (total_q, H_q, d) shape, dk and dv in k's and v's (dense); with sinks also
-    dsinks, float32 (H_q,), as a fourth result."""
+    dsinks, float32 (H_q,), as a fourth result.  dlse: the gradient of lse, float32 (H_q, total_q), or None
+    (fa_ex_backward_varlen_dlse)."""
     who = "ex_varlen_backward"
     wl, wr = window_arg(who, window)
     cap = softcap_arg(who, softcap)
@@ -745,6 +776,7 @@ def ex_varlen_backward(q, k, v, o, do_, lse, cu_seqlens_q, cu_seqlens_k, max_seq
             raise RuntimeError(f"{who}: {name} must be a (total_q, H_q, d) device tensor of q's dtype")
     if not lse.is_cuda or lse.shape != (hq, total_q) or lse.dtype != torch.float32:
         raise RuntimeError(f"{who}: lse must be a (H_q, total_q) float32 device tensor")
+    dlse = _dlse_arg(who, dlse, lse, "(H_q, total_q)")
     o, do_, lse = o.contiguous(), do_.contiguous(), lse.contiguous()
     with torch.cuda.device(q.device):
         dq = torch.empty((total_q, hq, d), dtype=q.dtype, device=q.device)
@@ -754,10 +786,10 @@ def ex_varlen_backward(q, k, v, o, do_, lse, cu_seqlens_q, cu_seqlens_k, max_seq
         ws = _workspace(q.device, nbytes)
         nbytes = max(nbytes, 0 if torch.cuda.is_current_stream_capturing() else _workspaces.capacity(q.device, _stream_ptr(q.device)))
         dsinks = torch.empty((sheads,), dtype=torch.float32, device=q.device) if sptr else None
-        _call("fa_ex_backward_varlen" + _ex_variant(sptr, cap > 0.0 or aptr, False), (
+        _call("fa_ex_backward_varlen" + _ex_variant(sptr, cap > 0.0 or aptr, False, False, dlse is not None), (
             q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do_.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
             dv.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr(), *dims, int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, astride,
-            sptr, sheads, _ptr(dsinks), float(dropout_p), int(seed) & (2 ** 64 - 1), ws.data_ptr(), nbytes, _stream_ptr(q.device)))
+            sptr, sheads, _ptr(dsinks), _ptr(dlse), float(dropout_p), int(seed) & (2 ** 64 - 1), ws.data_ptr(), nbytes, _stream_ptr(q.device)))
     return (dq, dk, dv, dsinks) if sptr else (dq, dk, dv)
 
 
@@ -1164,3 +1196,122 @@ def rotary_apply(x, cos, sin, out=None, interleaved=False, conjugate=False, seql
         _call("fa_rotary_apply", (x.data_ptr(), out.data_ptr(), b, seqlen, heads, d, _DTYPE_CODE[x.dtype], xb, xt, yb, yt, *rotary,
                                   int(bool(conjugate)), off0, _ptr(offs), _ptr(cu), total, mx, _stream_ptr(x.device)))
     return out
+
+
+# ---- merge of two partial attention results (include/fa_mi355x.h: fa_merge_states / fa_merge_states_backward) ----
+
+MERGE_LAYOUTS = ("bhnd", "bnhd", "thd")
+
+
+def _merge_views(who, layout, o_likes, lse_likes):
+    """The (batch, heads, rows, d) of a merge call and each tensor's (batch, head, row) stride triple, from the views themselves.
+    o_likes / lse_likes: (name, tensor) pairs, the first of each the model for the others' shape, dtype and device.  layout:
+    "bhnd" o (B, H, N, d) or (BH, N, d) with lse (B, H, N) or (BH, N); "bnhd" o (B, N, H, d) with lse (B, H, N); "thd" o (T, H, d)
+    with lse (H, T).  RuntimeError on mismatched shapes, dtypes or devices, ValueError on a view the kernel cannot address."""
+    if layout not in MERGE_LAYOUTS:
+        raise ValueError(f"{who}: layout must be one of {MERGE_LAYOUTS}, got {layout!r}")
+    o0, l0 = o_likes[0][1], lse_likes[0][1]
+    for name, t in (*o_likes, *lse_likes):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{who}: {name} must be a tensor on the GPU (HIP device); there is no CPU path")
+        if t.device != o0.device:
+            raise RuntimeError(f"{who}: all tensors must be on one device ({name} is on {t.device}, {o_likes[0][0]} on {o0.device})")
+    if o0.dtype not in _DTYPE_CODE:
+        raise RuntimeError(f"{who}: unsupported dtype {o0.dtype}")
+    for name, t in o_likes:
+        if t.shape != o0.shape or t.dtype != o0.dtype:
+            raise RuntimeError(f"{who}: {name} must have the shape and dtype of {o_likes[0][0]} ({tuple(o0.shape)}, {o0.dtype}); got "
+                               f"{tuple(t.shape)}, {t.dtype}")
+    for name, t in lse_likes:
+        if t.shape != l0.shape or t.dtype != torch.float32:
+            raise RuntimeError(f"{who}: {name} must be float32 of shape {tuple(l0.shape)}; got {tuple(t.shape)}, {t.dtype}")
+    if layout == "bhnd" and o0.dim() == 3:
+        want, dims = (o0.shape[0], o0.shape[1]), (1, o0.shape[0], o0.shape[1])
+        o_tr = lambda t: (0, t.stride(0), t.stride(1))
+        l_tr = lambda t: (0, t.stride(0), t.stride(1))
+    elif layout == "bhnd" and o0.dim() == 4:
+        b, h, n, d = o0.shape
+        want, dims = (b, h, n), (b, h, n)
+        o_tr = lambda t: (t.stride(0), t.stride(1), t.stride(2))
+        l_tr = lambda t: (t.stride(0), t.stride(1), t.stride(2))
+    elif layout == "bnhd" and o0.dim() == 4:
+        b, n, h, d = o0.shape
+        want, dims = (b, h, n), (b, h, n)
+        o_tr = lambda t: (t.stride(0), t.stride(2), t.stride(1))
+        l_tr = lambda t: (t.stride(0), t.stride(1), t.stride(2))
+    elif layout == "thd" and o0.dim() == 3:
+        n, h, d = o0.shape
+        want, dims = (h, n), (1, h, n)
+        o_tr = lambda t: (0, t.stride(1), t.stride(0))
+        l_tr = lambda t: (0, t.stride(0), t.stride(1))
+    else:
+        raise RuntimeError(f"{who}: layout {layout!r} does not take {o_likes[0][0]} of shape {tuple(o0.shape)}")
+    if tuple(l0.shape) != tuple(want):
+        raise RuntimeError(f"{who}: with layout {layout!r} and {o_likes[0][0]} of shape {tuple(o0.shape)}, {lse_likes[0][0]} must be "
+                           f"{tuple(want)}; got {tuple(l0.shape)}")
+    d = o0.shape[-1]
+    if d < 1 or d > 256 or (o0.dtype != torch.float32 and d % 8 != 0):
+        raise RuntimeError(f"{who}: head_dim must lie in [1, 256], a multiple of 8 for 16-bit tensors (got {d})")
+    strides = []
+    for name, t in o_likes:
+        if d > 1 and t.stride(-1) != 1:
+            raise ValueError(f"{who}: {name} must have a contiguous last dim (a view that would need a copy)")
+        tr = o_tr(t)
+        if t.dtype != torch.float32 and t.numel() > 0 and (t.data_ptr() % 16 != 0 or any(x % 8 != 0 for x, n_ in zip(tr, dims) if n_ > 1)):
+            raise ValueError(f"{who}: {name} is a view the kernel cannot address: 16-bit tensors need a 16-byte aligned start and "
+                             f"strides that are multiples of 8 elements (strides {tr})")
+        strides.append(tr)
+    for name, t in lse_likes:
+        strides.append(l_tr(t))
+    for tr in strides:
+        if any(x < 0 for x in tr):
+            raise ValueError(f"{who}: negative strides cannot be addressed")
+    # (a stride of an extent-1 dim is not used: hand 0 on, so that the C layer's alignment rule sees only the strides that address)
+    strides = [tuple(x if n_ > 1 else 0 for x, n_ in zip(tr, dims)) for tr in strides]
+    return dims, d, _DTYPE_CODE[o0.dtype], strides
+
+
+def merge_states(o_a, lse_a, o_b, lse_b, layout="bhnd", out=None):
+    """(o, lse) of attention over the union of two disjoint key sets from the two partial results (fa_merge_states):
+    lse = logaddexp(lse_a, lse_b), o = exp(lse_a - lse) o_a + exp(lse_b - lse) o_b.  Strides come from the views; nothing is
+    copied.  out = (o, lse) to write into given tensors, which may be (o_a, lse_a) themselves (in place).  Nothing is recorded by
+    autograd."""
+    who = "merge_states"
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise RuntimeError(f"{who}: out must be a pair (o, lse) of tensors")
+        o, lse = out
+    _merge_views(who, layout, (("o_a", o_a), ("o_b", o_b)), (("lse_a", lse_a), ("lse_b", lse_b)))
+    with torch.cuda.device(o_a.device):
+        if out is None:
+            o = torch.empty(o_a.shape, dtype=o_a.dtype, device=o_a.device)
+            lse = torch.empty(lse_a.shape, dtype=torch.float32, device=o_a.device)
+        dims, d, code, st = _merge_views(who, layout, (("o_a", o_a), ("o_b", o_b), ("o", o)), (("lse_a", lse_a), ("lse_b", lse_b), ("lse", lse)))
+        s_oa, s_ob, s_o, s_la, s_lb, s_l = st
+        _call("fa_merge_states", (o_a.data_ptr(), lse_a.data_ptr(), o_b.data_ptr(), lse_b.data_ptr(), o.data_ptr(), lse.data_ptr(), *dims, d,
+                                  code, *s_oa, *s_la, *s_ob, *s_lb, *s_o, *s_l, _stream_ptr(o_a.device)))
+    return o, lse
+
+
+def merge_states_backward(o_a, lse_a, o_b, lse_b, do_, dlse=None, layout="bhnd"):
+    """(do_a, do_b, dlse_a, dlse_b) of merge_states from the gradients of its o and lse (dlse None: zero), one launch
+    (fa_merge_states_backward).  The results are new contiguous tensors of the inputs' shapes."""
+    who = "merge_states_backward"
+    o_likes = [("o_a", o_a), ("o_b", o_b), ("do", do_)]
+    lse_likes = [("lse_a", lse_a), ("lse_b", lse_b)] + ([("dlse", dlse)] if dlse is not None else [])
+    _merge_views(who, layout, o_likes, lse_likes)
+    with torch.cuda.device(o_a.device):
+        do_a, do_b = (torch.empty(o_a.shape, dtype=o_a.dtype, device=o_a.device) for _ in range(2))
+        dlse_a, dlse_b = (torch.empty(lse_a.shape, dtype=torch.float32, device=o_a.device) for _ in range(2))
+        dims, d, code, st = _merge_views(who, layout, o_likes + [("do_a", do_a), ("do_b", do_b)],
+                                         lse_likes + [("dlse_a", dlse_a), ("dlse_b", dlse_b)])
+        s_oa, s_ob, s_do, s_doa, s_dob = st[:5]
+        s_la, s_lb = st[5:7]
+        s_dl = st[7] if dlse is not None else (0, 0, 0)
+        s_dla, s_dlb = st[-2:]
+        _call("fa_merge_states_backward", (
+            o_a.data_ptr(), lse_a.data_ptr(), o_b.data_ptr(), lse_b.data_ptr(), do_.data_ptr(), _ptr(dlse), do_a.data_ptr(),
+            do_b.data_ptr(), dlse_a.data_ptr(), dlse_b.data_ptr(), *dims, d, code, *s_oa, *s_la, *s_ob, *s_lb, *s_do, *s_dl, *s_doa,
+            *s_dob, *s_dla, *s_dlb, _stream_ptr(o_a.device)))
+    return do_a, do_b, dlse_a, dlse_b
+

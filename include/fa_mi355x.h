@@ -510,6 +510,35 @@ int fa_ex_backward_varlen_sink(const void* q, const void* k, const void* v, cons
                                const float* alibi_slopes, int64_t alibi_batch_stride, const float* sinks, int64_t sink_heads,
                                float* dsinks, double dropout_p, uint64_t dropout_seed, void* workspace, size_t workspace_bytes,
                                void* stream);
+/* --- A gradient of lse in the extended backward: what a merge of partial results (fa_merge_states) sends back to the attention
+ * call of each key chunk, in ring / context-parallel training.  With P = exp(S - lse), dP = dO V^T and delta = rowsum(dO * O), a
+ * gradient dlse on a row's lse gives
+ *     dS = P * (dP - delta + dlse)
+ * and leaves dV as it is; with sinks, dsinks[h] = sum over the rows of head h of exp(sink_h - lse) * (-delta + dlse).  So dlse
+ * enters the whole backward through the one row constant its kernels read, -delta + dlse, and through nothing else.
+ * dlse: float32 in lse's own layout, (BH, Nq), for the varlen call (heads_q, total_q); device memory on the tensors' device, 4-byte
+ * aligned (checked, FA_ERR_INVALID_ARGUMENT, after the sink checks), read by the kernels only.  It sits after the sink group and
+ * before the masks / dropout group; the remaining arguments, their checks and the order of those are fa_ex_backward_sink's /
+ * fa_ex_backward_varlen_sink's, and so is the workspace.  dlse == NULL is exactly that call: the same launches, the same bits.
+ * Rows whose lse is -inf (no visible key and no sink) ignore their dlse, whatever it holds, and keep dq = 0.
+ * A call with dlse != NULL runs the recomputing extended kernels (the 16-bit MFMA ones where they take the call, the exact-f32
+ * ones otherwise), whose row-constant pre-pass is a launch of its own: the plain kernels and the dS hand-over form -delta inside
+ * their matrix kernels and are not used.  fa_ex_backward_workspace_bytes_fast answers for such a call with extras = 1.  A call with
+ * query rows, no key, sinks and dlse gives dsinks[h] = the sum of dlse over the head's rows (every lse there is the sink). */
+int fa_ex_backward_dlse(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
+                        void* dv, int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype, int causal,
+                        int64_t window_left, int64_t window_right, double softmax_scale, double softcap, const float* alibi_slopes,
+                        int64_t alibi_heads, int64_t alibi_batch_stride, const float* sinks, int64_t sink_heads, float* dsinks,
+                        const float* dlse, const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br,
+                        int64_t bc, double dropout_p, uint64_t dropout_seed, void* workspace, size_t workspace_bytes, void* stream);
+int fa_ex_backward_varlen_dlse(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq,
+                               void* dk, void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch,
+                               int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q,
+                               int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                               int causal, int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
+                               const float* alibi_slopes, int64_t alibi_batch_stride, const float* sinks, int64_t sink_heads,
+                               float* dsinks, const float* dlse, double dropout_p, uint64_t dropout_seed, void* workspace,
+                               size_t workspace_bytes, void* stream);
 /* --- The varlen forward over a paged K/V cache: FlashAttention-2's flash_attn_varlen_func(..., block_table=).  Chunked prefill, or
  * prefill behind a shared prefix, reads its keys straight from the pools of the KV-cache calls, without a gathered copy and on the
  * kernel that reads a sequence's keys once per 256 query rows.  Forward only, no dropout.  The arguments are those of
@@ -684,6 +713,54 @@ int fa_rotary_apply(const void* x, void* y, int64_t batch, int64_t seqlen, int64
                     const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride, int64_t rotary_sin_row_stride,
                     int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved, int conjugate, int64_t seqlen_offset,
                     const int32_t* seqlen_offsets, const int32_t* cu_seqlens, int64_t total, int64_t max_seqlen, void* stream);
+
+/* --- Merge of two partial attention results (merge_attn_states of the serving stacks; the update step of ring attention).
+ * (o_a, lse_a) and (o_b, lse_b) are attention of the same queries over two DISJOINT key sets, each with its natural-log lse as the
+ * calls above return it.  Then attention over the union is
+ *     lse = logaddexp(lse_a, lse_b),    w_x = exp(lse_x - lse),    o = w_a * o_a + w_b * o_b.
+ * The weights are formed around the larger lse, once per row, in fp64; each element's w_a o_a + w_b o_b is formed in fp64 (the
+ * products are exact there) and rounded to fp32 and then to the tensor dtype, to nearest even.  A side with w_x = 0 (lse_x = -inf, or
+ * lse_x so far below the other that exp underflows) is not used: its o_x may hold NaN or garbage, and the result is the other side's
+ * o with its own bits.  Both -inf (a row without a visible key on either side): o = 0 and lse = -inf, the convention of the calls
+ * above.  NaN or +inf in an lse is undefined.
+ * Every tensor is addressed by (batch, head, row) through its own stride triple in elements: element e of row (b, h, i) of o_a is
+ * o_a[b * o_a_batch_stride + h * o_a_head_stride + i * o_a_row_stride + e], the d elements of a row contiguous; lse_a[b *
+ * lse_a_batch_stride + h * lse_a_head_stride + i * lse_a_row_stride] is that row's lse.  So (B, H, N, d) with lse (B, H, N), the
+ * decode call's (B, N, H, d) with lse (B, H, N), and packed (T, H, d) with lse (H, T) (batch = 1, rows = T) are all one call
+ * without a copy, and so is a slice of a wider tensor.  o_a, o_b and o share dtype (f16, bf16 or f32); every lse is float32.
+ * d <= 256; for 16-bit tensors d is a multiple of 8, for fp32 any d >= 1 (fp32 rows are moved by 16-byte accesses when d % 4 == 0
+ * and every o-like pointer is 16-byte aligned with strides that are multiples of 4, by 4-byte accesses otherwise).
+ * In place: o == o_a with o_a's strides and lse == lse_a with lse_a's strides is allowed (likewise on the b pair): every element
+ * is read before the thread that owns it writes it.  Any other overlap of an output with anything is undefined.
+ * fa_merge_states_backward: from dO (do_) and dlse, the gradients of o and lse (dlse == NULL: zero), with t = <dO, o_a - o_b> per
+ * row (an fp32 sum in a fixed order: the same bits on every run)
+ *     dO_a = w_a dO,   dO_b = w_b dO,   dlse_a = w_a (dlse + w_b t),   dlse_b = w_b (dlse - w_a t),
+ * all four written by the one launch.  A side with w_x = 0 gets zeros (and t, which may hold its NaN, is not used); a row with
+ * both lse -inf gets zeros everywhere and its dlse is not read.  The stored o is not needed.  No in-place form.
+ * Both calls are one launch on `stream`; nothing allocates, synchronises or reads device memory on the host: they can be captured.
+ * Checked before any HIP call, the first broken rule named in fa_last_error(), in this order: dtype f32, f16 or bf16; 0 <= batch,
+ * heads, rows < 2^31 and d >= 1 (FA_ERR_INVALID_ARGUMENT); d <= 256 (FA_ERR_UNSUPPORTED); d % 8 == 0 for 16-bit tensors; then a call
+ * without a row (batch, heads or rows == 0) returns FA_OK without a launch and without looking at the pointers; batch * heads < 2^31
+ * (FA_ERR_UNSUPPORTED); every pointer non-null (dlse alone may be); 16-bit o-like tensors 16-byte aligned with strides that are
+ * multiples of 8 elements, every float32 tensor 4-byte aligned; every stride >= 0 with (extent - 1) * stride <= 2^58, so that no
+ * 64-bit offset can overflow; an output that is an input has that input's strides. */
+int fa_merge_states(const void* o_a, const float* lse_a, const void* o_b, const float* lse_b, void* o, float* lse, int64_t batch,
+                    int64_t heads, int64_t rows, int64_t d, int dtype, int64_t o_a_batch_stride, int64_t o_a_head_stride,
+                    int64_t o_a_row_stride, int64_t lse_a_batch_stride, int64_t lse_a_head_stride, int64_t lse_a_row_stride,
+                    int64_t o_b_batch_stride, int64_t o_b_head_stride, int64_t o_b_row_stride, int64_t lse_b_batch_stride,
+                    int64_t lse_b_head_stride, int64_t lse_b_row_stride, int64_t o_batch_stride, int64_t o_head_stride,
+                    int64_t o_row_stride, int64_t lse_batch_stride, int64_t lse_head_stride, int64_t lse_row_stride, void* stream);
+int fa_merge_states_backward(const void* o_a, const float* lse_a, const void* o_b, const float* lse_b, const void* do_,
+                             const float* dlse, void* do_a, void* do_b, float* dlse_a, float* dlse_b, int64_t batch, int64_t heads,
+                             int64_t rows, int64_t d, int dtype, int64_t o_a_batch_stride, int64_t o_a_head_stride,
+                             int64_t o_a_row_stride, int64_t lse_a_batch_stride, int64_t lse_a_head_stride, int64_t lse_a_row_stride,
+                             int64_t o_b_batch_stride, int64_t o_b_head_stride, int64_t o_b_row_stride, int64_t lse_b_batch_stride,
+                             int64_t lse_b_head_stride, int64_t lse_b_row_stride, int64_t do_batch_stride, int64_t do_head_stride,
+                             int64_t do_row_stride, int64_t dlse_batch_stride, int64_t dlse_head_stride, int64_t dlse_row_stride,
+                             int64_t do_a_batch_stride, int64_t do_a_head_stride, int64_t do_a_row_stride, int64_t do_b_batch_stride,
+                             int64_t do_b_head_stride, int64_t do_b_row_stride, int64_t dlse_a_batch_stride, int64_t dlse_a_head_stride,
+                             int64_t dlse_a_row_stride, int64_t dlse_b_batch_stride, int64_t dlse_b_head_stride,
+                             int64_t dlse_b_row_stride, void* stream);
 
 /* --- support entry points (no reference counterpart: the reference allocates inside the callee) --- */
 /* bytes for the CURRENT kernel mode: two float row constants per query row (+ an fp32 dQ scratch of bh*n*d floats in
