@@ -418,8 +418,8 @@ def _no_fp8_without_table(who, k, v, k_descale, v_descale):
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_sin=None, cache_seqlens=None,
                             cache_batch_idx=None, cache_leftpad=None, block_table=None, softmax_scale=None, causal=False,
                             window_size=(-1, -1), softcap=0.0, rotary_interleaved=True, alibi_slopes=None, num_splits=0,
-                            return_softmax_lse=False, *, cu_seqlens_q=None, cu_seqlens_k_new=None, max_seqlen_q=None, sinks=None,
-                            k_descale=None, v_descale=None):
+                            return_softmax_lse=False, *, cu_seqlens_q=None, cu_seqlens_k_new=None, max_seqlen_q=None, qv=None,
+                            sinks=None, k_descale=None, v_descale=None):
     """FlashAttention-2's flash_attn_with_kvcache (forward; its argument order): q (B, Nq, H_q, d); k_cache, v_cache
     (B, cache_len, H_kv, d) with H_q % H_kv == 0, updated in place — k, v (B, N_new, H_kv, d) are written at
     cache_seqlens[b] .. + N_new before attention, and a cache view the library cannot take without a copy raises ValueError.
@@ -452,6 +452,16 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     anything: the kernels clamp them to the tensors.  Rotary then needs seqlen_ro >= capacity + max_seqlen_q.  A 4-D q with
     cu_seqlens_q, a missing max_seqlen_q, or a packed q that would need a copy raises ValueError.  o is then (total_q, H_q, d) and
     lse (H_q, total_q).
+    qv (keyword-only; FlashAttention-3's): a second query operand (B, Nq, H_q, 512) in q's dtype, for K and V of different widths —
+    DeepSeek-style multi-head latent attention at decode time after weight absorption.  q and k_cache are then 64 wide (the
+    rotary part), v_cache (.., H_kv, 512) holds the latent rows and o is (B, Nq, H_q, 512):
+        s[i, j] = softmax_scale * (q[i, h] . k[j] + qv[i, h] . v[j]),   o[i, h] = sum_j softmax_j(s)[i, j] v[j]
+    with softmax_scale defaulting to (64 + 512) ** -0.5.  Each latent row is read from memory once and serves the score and the
+    value.  k_cache and v_cache may be views of one allocation (pool[..., 512:] and pool[..., :512] of a (.., 576) pool,
+    contiguous or paged); their own strides are used, never a copy.  Goes with cache_seqlens, cache_batch_idx, block_table,
+    causal, window_size, softmax_scale, num_splits and return_softmax_lse.  Other widths, k / v, cu_seqlens_k_new, rotary_cos /
+    rotary_sin, an e4m3 cache (k_descale / v_descale), softcap, alibi_slopes, sinks, cu_seqlens_q and cache_leftpad raise
+    NotImplementedError with the argument's name.
     Returns o (B, Nq, H_q, d), and with return_softmax_lse also lse (B, H_q, Nq) float32.  No gradient."""
     for name, val in (("block_table", block_table), ("cache_batch_idx", cache_batch_idx), ("cache_leftpad", cache_leftpad),
                       ("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k_new", cu_seqlens_k_new)):
@@ -473,6 +483,10 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     extra = {} if sinks is None else {"sinks": sinks.detach() if isinstance(sinks, torch.Tensor) else sinks}
     if cu_seqlens_q is not None or cu_seqlens_k_new is not None or max_seqlen_q is not None:
         extra.update(cu_seqlens_q=cu_seqlens_q, cu_seqlens_k_new=cu_seqlens_k_new, max_seqlen_q=max_seqlen_q)
+    if qv is not None:
+        if not isinstance(qv, torch.Tensor):
+            raise NotImplementedError(f"flash_attn_with_kvcache: qv of type {type(qv).__name__} is not supported (a tensor of q's dtype expected)")
+        extra.update(qv=qv.detach())
     with torch.no_grad():
         o, lse = ext.ex_kvcache_forward(q.detach(), k_cache, v_cache, None if k is None else k.detach(),
                                         None if v is None else v.detach(), cache_seqlens, bool(causal), softmax_scale,

@@ -1081,6 +1081,12 @@ static int64_t kv_splits(int64_t batch, int64_t hq, int64_t hkv, int64_t nq, int
     return fa::kv_num_splits(batch, hkv, ((hq / hkv) * nq + 15) / 16, cache_len);
 }
 
+// the same for a call with qv (fa_mla.hip: workgroups of up to four row tiles)
+static int64_t kv_splits_qv(int64_t batch, int64_t hq, int64_t hkv, int64_t nq, int64_t cache_len, int64_t num_splits) {
+    if (num_splits > 0) return num_splits;
+    return fa::mla_num_splits(batch, hkv, (hq / hkv) * nq, cache_len);
+}
+
 // the arguments of the three workspace queries (seqlen_q: max_seqlen_q of the packed one); a bad one makes the answer 0
 static bool kv_ws_args_ok(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t d, int64_t num_splits) {
     return batch > 0 && heads_q > 0 && heads_kv > 0 && heads_q % heads_kv == 0 && seqlen_q > 0 && d > 0 && cache_len >= 0 && num_splits >= 0 &&
@@ -1107,6 +1113,16 @@ size_t fa_ex_kvcache_workspace_bytes_varlen(int64_t batch, int64_t heads_q, int6
     if (!kv_ws_args_ok(batch, heads_q, heads_kv, max_seqlen_q, cache_len, d, num_splits) || max_seqlen_q > total_q) return 0;
     const int64_t S = kv_splits(batch, heads_q, heads_kv, max_seqlen_q, cache_len, num_splits);
     return fa::kv_workspace_bytes(1, heads_q, total_q, d, (int)(with_sinks && S < 2 ? 2 : S));
+}
+
+// d_v = 0: fa_ex_kvcache_workspace_bytes_varlen.  d_v > 0 (a call with qv): o and the partials are d_v wide and S follows the
+// launch rule of that kernel
+size_t fa_ex_kvcache_workspace_bytes_qv(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t max_seqlen_q,
+                                        int64_t cache_len, int64_t d, int64_t num_splits, int with_sinks, int64_t d_v) {
+    if (d_v == 0) return fa_ex_kvcache_workspace_bytes_varlen(batch, heads_q, heads_kv, total_q, max_seqlen_q, cache_len, d, num_splits, with_sinks);
+    if (!kv_ws_args_ok(batch, heads_q, heads_kv, max_seqlen_q, cache_len, d, num_splits) || max_seqlen_q > total_q || d_v < 0) return 0;
+    const int64_t S = kv_splits_qv(batch, heads_q, heads_kv, max_seqlen_q, cache_len, num_splits);
+    return fa::kv_workspace_bytes(1, heads_q, total_q, d_v, (int)(with_sinks && S < 2 ? 2 : S));
 }
 
 // One call of the fa_ex_forward_kvcache* family, a field per argument of the widest entry point under its name in the header.
@@ -1142,6 +1158,9 @@ struct KvCall {
     // _varlen
     const int32_t *cu_seqlens_q = nullptr, *cu_seqlens_k_new = nullptr;
     int64_t total_q = 0, max_seqlen_q = 0, total_k_new = 0;
+    // _qv
+    const void* qv = nullptr;
+    int64_t qv_batch_stride = 0, qv_token_stride = 0, d_v = 0;
 };
 
 static int kvcache_impl(const char* who, const KvCall& c) {
@@ -1248,17 +1267,19 @@ static int kvcache_impl(const char* who, const KvCall& c) {
     // (esz: bytes an element.  The kernels keep 32-bit byte offsets inside one batch element or page, so the limit is on bytes:
     // an e4m3 cache may hold twice the tokens of a 16-bit one)
     const int64_t c_esz = e4m3 ? 1 : 2;
-    struct { const char* name; int64_t bs, ts, n, heads, units, esz; } st[5] = {
-        {"q", q_batch_stride, c.q_token_stride, seqlen_q, c.heads_q, vq ? 1 : c.batch, 2},
-        {"k_cache", c.k_cache_batch_stride, c.k_cache_token_stride, c_n, c.heads_kv, c_units, c_esz},
-        {"v_cache", c.v_cache_batch_stride, c.v_cache_token_stride, c_n, c.heads_kv, c_units, c_esz},
-        {"k_new", k_new_batch_stride, c.k_new_token_stride, seqlen_new, c.heads_kv, vk ? 1 : c.batch, 2},
-        {"v_new", v_new_batch_stride, c.v_new_token_stride, seqlen_new, c.heads_kv, vk ? 1 : c.batch, 2}};
+    // (w: a head's width.  With qv, v_cache and o are d_v wide; the checks of qv's own group follow the existing ones below)
+    const int64_t d_o = (c.qv && c.d_v > 0) ? c.d_v : c.d;
+    struct { const char* name; int64_t bs, ts, n, heads, units, esz, w; } st[5] = {
+        {"q", q_batch_stride, c.q_token_stride, seqlen_q, c.heads_q, vq ? 1 : c.batch, 2, c.d},
+        {"k_cache", c.k_cache_batch_stride, c.k_cache_token_stride, c_n, c.heads_kv, c_units, c_esz, c.d},
+        {"v_cache", c.v_cache_batch_stride, c.v_cache_token_stride, c_n, c.heads_kv, c_units, c_esz, d_o},
+        {"k_new", k_new_batch_stride, c.k_new_token_stride, seqlen_new, c.heads_kv, vk ? 1 : c.batch, 2, c.d},
+        {"v_new", v_new_batch_stride, c.v_new_token_stride, seqlen_new, c.heads_kv, vk ? 1 : c.batch, 2, c.d}};
     for (int i = 0; i < (seqlen_new > 0 ? 5 : 3); ++i) {
-        const int64_t span = (st[i].n - 1) * st[i].ts + st[i].heads * c.d;   // elements of one batch element (or page)
-        if (st[i].ts < st[i].heads * c.d || (st[i].units > 1 && st[i].bs < span) || st[i].bs < 0)
+        const int64_t span = (st[i].n - 1) * st[i].ts + st[i].heads * st[i].w;   // elements of one batch element (or page)
+        if (st[i].ts < st[i].heads * st[i].w || (st[i].units > 1 && st[i].bs < span) || st[i].bs < 0)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of %s too small (batch %lld, token %lld; need token >= %lld, batch >= %lld)",
-                        who, st[i].name, (long long)st[i].bs, (long long)st[i].ts, (long long)(st[i].heads * c.d), (long long)span);
+                        who, st[i].name, (long long)st[i].bs, (long long)st[i].ts, (long long)(st[i].heads * st[i].w), (long long)span);
         if (st[i].ts % 8 != 0 || st[i].bs % 8 != 0)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of %s must be multiples of 8 elements", who, st[i].name);
         if (span * st[i].esz >= ((int64_t)1 << 31))
@@ -1316,7 +1337,8 @@ static int kvcache_impl(const char* who, const KvCall& c) {
     if (cache_len > ((int64_t)1 << 28) || seqlen_q > ((int64_t)1 << 24) || c.heads_q > 65535 ||
         ((c.heads_q / c.heads_kv) * seqlen_q + 15) / 16 * c.heads_kv > 65535)
         return fail(FA_ERR_UNSUPPORTED, "%s: problem too large for one launch", who);
-    int64_t S = kv_splits(c.batch, c.heads_q, c.heads_kv, seqlen_q, cache_len, c.num_splits);
+    int64_t S = c.qv ? kv_splits_qv(c.batch, c.heads_q, c.heads_kv, seqlen_q, cache_len, c.num_splits)
+                     : kv_splits(c.batch, c.heads_q, c.heads_kv, seqlen_q, cache_len, c.num_splits);
     if (c.sinks && S < 2) S = 2;   // the sink joins in the combine: where the rule or the caller gives one split, two are launched
     const int64_t q_rows = vq ? c.heads_q * c.total_q : c.batch * c.heads_q * seqlen_q;
     if (S > 1 && q_rows >= ((int64_t)1 << 26))   // the combine: one wave per row, 2^32 lanes per launch
@@ -1327,8 +1349,8 @@ static int kvcache_impl(const char* who, const KvCall& c) {
     // stay below 2^28 and the band arithmetic cannot overflow.
     if (window_left >= cache_len - 1) window_left = -1;
     if (window_right >= seqlen_q - 1) window_right = -1;
-    const size_t need = vq ? (seqlen_q > 0 ? fa::kv_workspace_bytes(1, c.heads_q, c.total_q, c.d, (int)S) : 0)
-                           : fa::kv_workspace_bytes(c.batch, c.heads_q, seqlen_q, c.d, (int)S);
+    const size_t need = vq ? (seqlen_q > 0 ? fa::kv_workspace_bytes(1, c.heads_q, c.total_q, d_o, (int)S) : 0)
+                           : fa::kv_workspace_bytes(c.batch, c.heads_q, seqlen_q, d_o, (int)S);
     if (c.workspace_bytes < need || (need > 0 && !c.workspace))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace of %zu bytes needed, %zu given", who, need, c.workspace_bytes);
     // (packed queries without a token: q, o and lse are empty and may be null)
@@ -1341,6 +1363,34 @@ static int kvcache_impl(const char* who, const KvCall& c) {
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: tensors must be 16-byte aligned", who);
     } else if (!aligned16({c.q, c.k_cache, c.v_cache, c.o, c.workspace}) || (seqlen_new > 0 && !aligned16({c.k_new, c.v_new})))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: tensors must be 16-byte aligned", who);
+    // qv (fa_ex_forward_kvcache_qv): a second query operand against v_cache, K and V of different widths
+    if (!c.qv && (c.qv_batch_stride != 0 || c.qv_token_stride != 0 || c.d_v != 0))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: qv_batch_stride, qv_token_stride and d_v must be 0 without qv (got %lld, %lld, %lld)", who,
+                    (long long)c.qv_batch_stride, (long long)c.qv_token_stride, (long long)c.d_v);
+    if (c.qv) {
+        if (c.d != 64 || c.d_v != 512)
+            return fail(FA_ERR_UNSUPPORTED, "%s: qv is supported for head_dim = 64 with d_v = 512 only (got head_dim = %lld, d_v = %lld)", who,
+                        (long long)c.d, (long long)c.d_v);
+        const char* with = seqlen_new > 0 || c.k_new || c.v_new ? "k_new / v_new (new tokens to append)"
+                           : vk ? "cu_seqlens_k_new"
+                           : c.rotary_cos ? "rotary_cos / rotary_sin"
+                           : e4m3 ? "an e4m3 cache (cache_dtype, k_descale, v_descale)"
+                           : c.softcap > 0.0 ? "softcap"
+                           : c.alibi_slopes ? "alibi_slopes"
+                           : c.sinks ? "sinks"
+                           : vq ? "cu_seqlens_q"
+                           : c.cache_leftpad ? "cache_leftpad" : nullptr;
+        if (with) return fail(FA_ERR_UNSUPPORTED, "%s: qv cannot be combined with %s", who, with);
+        const int64_t span = (seqlen_q - 1) * c.qv_token_stride + c.heads_q * c.d_v;
+        if (c.qv_token_stride < c.heads_q * c.d_v || (c.batch > 1 && c.qv_batch_stride < span) || c.qv_batch_stride < 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of qv too small (batch %lld, token %lld; need token >= %lld, batch >= %lld)",
+                        who, (long long)c.qv_batch_stride, (long long)c.qv_token_stride, (long long)(c.heads_q * c.d_v), (long long)span);
+        if (c.qv_token_stride % 8 != 0 || c.qv_batch_stride % 8 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of qv must be multiples of 8 elements", who);
+        if (span * 2 >= ((int64_t)1 << 31))
+            return fail(FA_ERR_UNSUPPORTED, "%s: one batch element of qv spans %lld bytes, beyond 32-bit offsets", who, (long long)(span * 2));
+        if (!aligned16({c.qv})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: tensors must be 16-byte aligned", who);
+    }
     fa::KvArgs a{};
     a.q = c.q; a.k_cache = c.k_cache; a.v_cache = c.v_cache; a.k_new = c.k_new; a.v_new = c.v_new; a.o = c.o; a.lse = c.lse;
     a.cache_seqlens = c.cache_seqlens;
@@ -1360,6 +1410,7 @@ static int kvcache_impl(const char* who, const KvCall& c) {
     a.sinks = c.sinks; a.sink_heads = c.sinks ? c.sink_heads : 1;
     a.cu_seqlens_q = c.cu_seqlens_q; a.cu_seqlens_k_new = c.cu_seqlens_k_new;
     a.total_q = c.total_q; a.max_seqlen_q = c.max_seqlen_q; a.total_k_new = c.total_k_new;
+    a.qv = c.qv; a.qv_bs = c.qv_batch_stride; a.qv_ts = c.qv_token_stride; a.d_v = c.d_v;
     if (vq && seqlen_q == 0 && seqlen_new == 0) return FA_OK;   // no query token and nothing to append: no launch
     return launched(who, fa::launch_kvcache(a, reinterpret_cast<hipStream_t>(c.stream)));
 }
@@ -1529,6 +1580,40 @@ int fa_ex_forward_kvcache_varlen(const void* q, void* k_cache, void* v_cache, co
     c.cu_seqlens_q = cu_seqlens_q; c.cu_seqlens_k_new = cu_seqlens_k_new; c.total_q = total_q; c.max_seqlen_q = max_seqlen_q;
     c.total_k_new = total_k_new;
     return kvcache_impl("fa_ex_forward_kvcache_varlen", c);
+}
+
+int fa_ex_forward_kvcache_qv(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new, const int32_t* cache_seqlens,
+                                 void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_new,
+                                 int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride, int64_t q_token_stride,
+                                 int64_t k_cache_batch_stride, int64_t k_cache_token_stride, int64_t v_cache_batch_stride,
+                                 int64_t v_cache_token_stride, int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t v_new_batch_stride,
+                                 int64_t v_new_token_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                                 double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits,
+                                 const int32_t* block_table, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
+                                 int64_t max_blocks_per_seq, const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad,
+                                 const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride, int64_t rotary_sin_row_stride,
+                                 int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
+                                 int cache_dtype, const float* k_descale, const float* v_descale, int64_t descale_batch_stride,
+                                 const float* sinks, int64_t sink_heads,
+                                 const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k_new, int64_t total_q,
+                                 int64_t max_seqlen_q, int64_t total_k_new,
+                                 const void* qv, int64_t qv_batch_stride, int64_t qv_token_stride, int64_t d_v,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    KvCall c = kv_call(q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, batch, heads_q, heads_kv, seqlen_q, seqlen_new, cache_len, d, dtype,
+                       q_batch_stride, q_token_stride, k_cache_batch_stride, k_cache_token_stride, v_cache_batch_stride, v_cache_token_stride,
+                       k_new_batch_stride, k_new_token_stride, v_new_batch_stride, v_new_token_stride, causal, window_left, window_right,
+                       softmax_scale, softcap, alibi_slopes, alibi_batch_stride, num_splits, workspace, workspace_bytes, stream);
+    c.block_table = block_table; c.block_table_row_stride = block_table_row_stride; c.num_blocks = num_blocks;
+    c.page_block_size = page_block_size; c.max_blocks_per_seq = max_blocks_per_seq;
+    c.cache_batch_idx = cache_batch_idx; c.cache_batch = cache_batch; c.cache_leftpad = cache_leftpad;
+    c.rotary_cos = rotary_cos; c.rotary_sin = rotary_sin; c.rotary_cos_row_stride = rotary_cos_row_stride;
+    c.rotary_sin_row_stride = rotary_sin_row_stride; c.seqlen_ro = seqlen_ro; c.rotary_dim = rotary_dim; c.rotary_interleaved = rotary_interleaved;
+    c.cache_dtype = cache_dtype; c.k_descale = k_descale; c.v_descale = v_descale; c.descale_batch_stride = descale_batch_stride;
+    c.sinks = sinks; c.sink_heads = sink_heads;
+    c.cu_seqlens_q = cu_seqlens_q; c.cu_seqlens_k_new = cu_seqlens_k_new; c.total_q = total_q; c.max_seqlen_q = max_seqlen_q;
+    c.total_k_new = total_k_new;
+    c.qv = qv; c.qv_batch_stride = qv_batch_stride; c.qv_token_stride = qv_token_stride; c.d_v = d_v;
+    return kvcache_impl("fa_ex_forward_kvcache_qv", c);
 }
 
 // One call of the fa_rotary_apply family, a field per argument under its name in the header.  Defaults: "argument absent".

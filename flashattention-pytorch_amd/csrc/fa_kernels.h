@@ -245,13 +245,22 @@ struct KvArgs {
     // fa_ex_forward_kvcache_varlen (null / 0: the padded call).  cu_seqlens_q: q and o are packed (total_q, heads_q, d) at token
     // stride q_ts (o dense), lse is (heads_q, total_q), sequence b owns at most max_seqlen_q of the tokens; seqlen_q and q_bs
     // are not used.  cu_seqlens_k_new: k_new, v_new are packed (total_k_new, heads_kv, d); seqlen_new, kn_bs and vn_bs are
-    // not used.  Both untrusted device offsets (batch + 1,), clamped in the kernels (fa_decode.hip: kv_cu_range).
+    // not used.  Both untrusted device offsets (batch + 1,), clamped in the kernels (fa_decode_common.h: kv_cu_range).
     const int *cu_seqlens_q = nullptr, *cu_seqlens_k_new = nullptr;
     int64_t total_q = 0, max_seqlen_q = 0, total_k_new = 0;
+    // fa_ex_forward_kvcache_qv (null / 0: K and V of one width).  qv: a second query operand (batch, seqlen_q, heads_q, d_v) at
+    // qv_bs / qv_ts, heads at stride d_v; v_cache and o are then d_v wide, the score is scale * (q . k + qv . v), and the call goes
+    // to launch_kvcache_mla (fa_mla.hip: d = 64, d_v = 512; no new tokens, rotary, e4m3, softcap, ALiBi, sinks, packing, leftpad).
+    const void* qv = nullptr;
+    int64_t qv_bs = 0, qv_ts = 0, d_v = 0;
 };
 int kv_num_splits(int64_t batch, int64_t heads_kv, int64_t row_tiles, int64_t cache_len);
+// the qv call's launch rule (fa_mla.hip): waves a workgroup for rows = (heads_q / heads_kv) * seqlen_q packed rows, and its splits
+int mla_waves(int64_t rows);
+int mla_num_splits(int64_t batch, int64_t heads_kv, int64_t rows, int64_t cache_len);
 size_t kv_workspace_bytes(int64_t batch, int64_t heads_q, int64_t seqlen_q, int64_t d, int splits);
 hipError_t launch_kvcache(const KvArgs& a, hipStream_t st);
+hipError_t launch_kvcache_mla(const KvArgs& a, hipStream_t st);
 
 // Rotary embedding for training and prefill (fa_rotary.hip; fa_rotary_apply).  16-bit x, y (batch, seqlen, heads, d), heads at
 // stride d, strides multiples of 8 elements, 16-byte aligned; y == x (with x's strides) is the in-place form.  Tables as KvArgs'.

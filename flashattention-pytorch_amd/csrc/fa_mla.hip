@@ -1,0 +1,396 @@
+// KV-cache decoding with a second query operand and K and V of different widths (fa_ex_forward_kvcache_qv; FlashAttention-3's
+// qv): multi-head latent attention at decode time.  Every cached token is a 64-wide rotary row k (k_cache) and a 512-wide latent
+// row v (v_cache); for query head h reading K/V head hk = h / G
+//   s[i, j] = scale * (q[i, h, :] . k[j, hk, :] + qv[i, h, :] . v[j, hk, :]),   o[i, h, :] = sum_j softmax_j(s)[i, j] v[j, hk, :]
+// so the latent row is the score operand and the value operand.  It is fetched from memory once per workgroup:
+//   mla_split_kernel  : NW waves (1 | 2 | 4), wave w the row tile NW * blockIdx.y' + w of 16 packed rows (row = token * G + head,
+//                       the mapping of kv_split_kernel).  Per 32-key tile the workgroup copies the 32 x 512 latent rows and the
+//                       32 x 64 rotary rows into LDS (36 KiB, 16 bytes a lane and step, through registers; with four waves the
+//                       loads of tile t + 1 are issued before tile t is computed on), the latent in the swizzled image MlaSwz.  S^T = K Q^T reads that image row-wise (ds_read_b128: 8 consecutive head dims a
+//                       lane, 2 + 16 k-steps of v_mfma_f32_16x16x32 per 16 keys against the q and qv fragments the wave keeps in
+//                       registers); O^T = V^T P^T reads the same bytes transposed (ds_read_b64_tr_b16), 32 MFMAs into a 16 x 512
+//                       fp32 accumulator.  Online softmax in fp32 on the lane of its query row, as in kv_split_kernel.
+//   mla_combine_kernel: S > 1 only — kv_combine_kernel with a loop over the two 256-column halves of a 512-wide row.
+// Lengths, pages, cache rows, split ranges and masks are kv_len_k, kv_split_range and the page rules of fa_decode.hip
+// (fa_decode_common.h): the split range of a workgroup is the union of its row tiles' bands, every row masks its own band.
+// Small launches: the wave count follows the packed rows (mla_waves: 16 rows -> one wave a workgroup), so no wave of a
+// workgroup is without rows unless the last row tile of a larger call is; the launch rule (mla_num_splits) then cuts the keys
+// into more splits, and the partial results meet in mla_combine_kernel in the fixed split order.  That is the merge a
+// workgroup-internal key split would need a second, LDS-resident copy of; here it is the one the split path already has.
+#include "fa_decode_common.h"
+#include <algorithm>
+
+namespace fa {
+
+namespace {
+
+constexpr int kMlaDk = 64, kMlaDv = 512, kMlaKT = 32;
+constexpr int kMlaLatBytes = kMlaKT * kMlaDv * 2, kMlaLdsBytes = kMlaLatBytes + kMlaKT * kMlaDk * 2;
+
+// the latent tile [32][512]: 1024-byte rows, the 16-chunk pattern of TileSwz<256> repeating (a chunk's bank is its index mod 16)
+struct MlaSwz {
+    static __device__ __forceinline__ int off(int row, int ch) { return 1024 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
+};
+
+struct MlaParams {
+    KvParams p;            // p.d = 64: q, k_cache; v_cache, o and the partials are 512 wide
+    const uint16_t* qv;    // (batch, nq, hq, 512): batch stride qv_bs, token stride qv_ts
+    long long qv_bs;
+    int qv_ts;
+};
+
+template <typename Tag, int NW, bool PAGED>
+__global__ __launch_bounds__(64 * NW) void mla_split_kernel(MlaParams mp) {
+    constexpr int KT = kMlaKT, DK = kMlaDk, DV = kMlaDv, NDB = DV / 16, T = 64 * NW;
+    constexpr int LCH = KT * (DV / 8) / T, RCH = KT * (DK / 8) / T;   // 16-byte chunks a thread moves per tile: latent, rotary
+    static_assert(LCH * T == KT * DV / 8 && RCH >= 1, "tile copy");
+    __shared__ __attribute__((aligned(16))) char lds[kMlaLdsBytes];
+    char* const lat = lds;
+    char* const rop = lds + kMlaLatBytes;
+    const KvParams& p = mp.p;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, g = lane >> 4;
+    const int s = blockIdx.x, S = gridDim.x;
+    const int hk = blockIdx.y % p.hkv, wt = blockIdx.y / p.hkv, b = blockIdx.z;
+    const int nq = p.nq, rows = p.rows;
+    const long long tok0 = (long long)b * nq;
+    int L_b, P_b;
+    const int lk = kv_len_k(p, b, 0, L_b, P_b), coff = lk - nq;
+    // the workgroup's rows [wr0, wr1) and the key range of their bands' union; wr0 < rows by the grid
+    const int wr0 = 16 * NW * wt, wr1 = min(wr0 + 16 * NW, rows);
+    int kbeg, kend;
+    kv_split_range(p, lk, nq, wr0 / p.G, (wr1 - 1) / p.G, s, S, kbeg, kend);
+
+    // this wave's row tile (none: the wave only copies), this lane's query row and its visible keys [rlo, rhi]
+    const int pr0 = wr0 + 16 * w, pr = pr0 + r;
+    const bool active = pr0 < rows, valid = pr < rows;
+    const int qlo = min(pr0, rows - 1) / p.G;
+    const int qi = valid ? pr / p.G : qlo, h = hk * p.G + (valid ? pr - qi * p.G : 0);
+    const int rlo = max(qi + coff - p.wl, kbeg);
+    const int rhi = valid ? min(min(qi + coff + p.wr, lk - 1), kend - 1) : -1;
+
+    s16x8 qf[DK / 32], qvf[DV / 32];
+    {
+        const buf_rsrc_t q_rs = make_rsrc(p.q + b * p.q_bs, (unsigned)(((nq - 1) * p.q_ts + p.hq * DK) * 2));
+        const buf_rsrc_t qv_rs = make_rsrc(mp.qv + b * mp.qv_bs, (unsigned)(((nq - 1) * mp.qv_ts + p.hq * DV) * 2));
+#pragma unroll
+        for (int ks = 0; ks < DK / 32; ++ks) qf[ks] = buf_load_frag(q_rs, valid ? (qi * p.q_ts + h * DK + 32 * ks + 8 * g) * 2 : kOobOff);
+#pragma unroll
+        for (int ks = 0; ks < DV / 32; ++ks) qvf[ks] = buf_load_frag(qv_rs, valid ? (qi * mp.qv_ts + h * DV + 32 * ks + 8 * g) * 2 : kOobOff);
+    }
+    // contiguous: cache row (bidx ? bidx[b] : b); a row outside the cache is an empty range (kv_split_kernel's rule)
+    long long crow = b;
+    int ctok = PAGED ? 0 : p.cap;
+    if (!PAGED && p.bidx) {
+        const int ix = p.bidx[b];
+        crow = ix;
+        if ((unsigned)ix >= (unsigned)p.bcache) { crow = 0; ctok = 0; }
+    }
+    const buf_rsrc_t k_rs = make_rsrc(p.kc + crow * p.kc_bs, ctok > 0 ? (unsigned)(((ctok - 1) * p.kc_ts + p.hkv * DK) * 2) : 0u);
+    const buf_rsrc_t v_rs = make_rsrc(p.vc + crow * p.vc_bs, ctok > 0 ? (unsigned)(((ctok - 1) * p.vc_ts + p.hkv * DV) * 2) : 0u);
+    // paged: kv_split_kernel's lookup, done by every wave for itself (lane l: key k0 + (l & 31), the next tile's a tile ahead)
+    const int* tbl = PAGED ? p.table + b * p.tbl_rs : nullptr;
+    int j0 = 0, s0 = 0, pg = -1;
+    auto page_of = [&](int jt, int st, int kt) {
+        int j = jt, sl = st + (lane & 31);
+        if (sl >= p.ps) { sl -= p.ps; ++j; }
+        if (sl >= p.ps) ++j;
+        return kt + (lane & 31) < kend ? tbl[j] : -1;
+    };
+    if (PAGED && kbeg < kend) {
+        j0 = kbeg / p.ps;
+        s0 = kbeg - j0 * p.ps;
+        pg = page_of(j0, s0, kbeg);
+    }
+
+    f32x4_t oacc[NDB];
+#pragma unroll
+    for (int t = 0; t < NDB; ++t) oacc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    float m_run = -INFINITY, l_run = 0.f;
+    const int q4 = r >> 2, p4 = r & 3;
+
+    // One tile's copy, loads and LDS writes apart: chunk idx = T i + tid of the latent rows (row idx / 64 = (T / 64) i + w, the
+    // same for the whole wave; chunk idx % 64 = lane), then of the rotary rows (idx / 8, idx % 8).  Keys past the split's end,
+    // on a page outside the pool or in a row outside the cache are zeros.  Paged: this lane's key kt + (lane & 31) has element
+    // offsets ko / vo in the two pools, -1 = reads as zeros.  Four waves (PRE): a thread holds a whole tile's share, 9 chunks,
+    // and the loads of tile k0 + 32 are in flight while tile k0 is computed on.  Fewer waves move 18 or 36 chunks a thread,
+    // eight at a time between the barriers; there the other workgroups of the CU cover the latency.
+    constexpr bool PRE = LCH <= 8;
+    constexpr int LB = PRE ? LCH : 8;
+    static_assert(LCH % LB == 0, "tile copy");
+    u32x4 xl[LB], xr[RCH];
+    long long ko = -1, vo = -1;
+    const int wu = __builtin_amdgcn_readfirstlane(w);
+    auto offsets = [&](int kt) {
+        if constexpr (PAGED) {
+            int sl = s0 + (lane & 31);
+            if (sl >= p.ps) sl -= p.ps;
+            if (sl >= p.ps) sl -= p.ps;
+            ko = vo = -1;
+            if ((unsigned)pg < (unsigned)p.nblk) {
+                ko = pg * p.kc_bs + (long long)sl * p.kc_ts;
+                vo = pg * p.vc_bs + (long long)sl * p.vc_ts;
+            }
+            s0 += KT;
+            if (s0 >= p.ps) { s0 -= p.ps; ++j0; }
+            if (s0 >= p.ps) { s0 -= p.ps; ++j0; }
+            if (kt + KT < kend) pg = page_of(j0, s0, kt + KT);   // the next tile's lookup, a tile ahead of its use
+        }
+    };
+    auto load_lat = [&](int kt, int i0) {
+#pragma unroll
+        for (int i = 0; i < LB; ++i) {
+            const int row = (T / 64) * (i0 + i) + wu;
+            if constexpr (PAGED) {
+                const long long ro = ((long long)__builtin_amdgcn_readlane((int)(vo >> 32), row) << 32) |
+                                     (unsigned)__builtin_amdgcn_readlane((int)vo, row);   // (wave-uniform: a scalar base)
+                const bool ok = ro >= 0;
+                const u32x4 y = *reinterpret_cast<const u32x4*>(ok ? p.vc + ro + hk * DV + 8 * lane : p.q);
+                xl[i] = ok ? y : u32x4{0u, 0u, 0u, 0u};
+            } else {
+                const int key = kt + row;
+                xl[i] = __builtin_amdgcn_raw_buffer_load_b128(v_rs, key < kend ? (key * p.vc_ts + hk * DV + 8 * lane) * 2 : kOobOff, 0, 0);
+            }
+        }
+    };
+    auto store_lat = [&](int i0) {
+#pragma unroll
+        for (int i = 0; i < LB; ++i) *reinterpret_cast<u32x4*>(lat + MlaSwz::off((T / 64) * (i0 + i) + wu, lane)) = xl[i];
+    };
+    auto load_rot = [&](int kt) {
+#pragma unroll
+        for (int i = 0; i < RCH; ++i) {
+            const int idx = T * i + tid, row = idx >> 3, ch = idx & 7;
+            if constexpr (PAGED) {
+                const long long ro = __shfl(ko, row, 64);
+                const bool ok = ro >= 0;
+                const u32x4 y = *reinterpret_cast<const u32x4*>(ok ? p.kc + ro + hk * DK + 8 * ch : p.q);
+                xr[i] = ok ? y : u32x4{0u, 0u, 0u, 0u};
+            } else {
+                const int key = kt + row;
+                xr[i] = __builtin_amdgcn_raw_buffer_load_b128(k_rs, key < kend ? (key * p.kc_ts + hk * DK + 8 * ch) * 2 : kOobOff, 0, 0);
+            }
+        }
+    };
+    auto store_rot = [&]() {
+#pragma unroll
+        for (int i = 0; i < RCH; ++i) {
+            const int idx = T * i + tid;
+            *reinterpret_cast<u32x4*>(rop + TileSwz<64>::off(idx >> 3, idx & 7)) = xr[i];
+        }
+    };
+    if (PRE && kbeg < kend) {
+        offsets(kbeg);
+        load_lat(kbeg, 0);
+        load_rot(kbeg);
+    }
+
+    for (int k0 = kbeg; k0 < kend; k0 += KT) {
+        if constexpr (!PRE) offsets(k0);
+        __syncthreads();   // every wave has read the previous tile
+        if constexpr (PRE) {
+            store_lat(0);
+        } else {
+#pragma unroll 1
+            for (int i0 = 0; i0 < LCH; i0 += LB) {
+                load_lat(k0, i0);
+                store_lat(i0);
+            }
+            load_rot(k0);
+        }
+        store_rot();
+        __syncthreads();
+        if (PRE && k0 + KT < kend) {
+            offsets(k0 + KT);
+            load_lat(k0 + KT, 0);
+            load_rot(k0 + KT);
+        }
+        if (!active) continue;   // (wave-uniform; the wave still takes part in the copies and the barriers)
+
+        // S^T = K Q^T: A = key 16 kb + r, head dims 32 ks + 8 g .. of the rotary row, then of the latent row
+        f32x4_t sacc[2];
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+            sacc[kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < DK / 32; ++ks)
+                sacc[kb] = mfma16<Tag>(*reinterpret_cast<const s16x8*>(rop + TileSwz<64>::off(16 * kb + r, 4 * ks + g)), qf[ks], sacc[kb]);
+#pragma unroll
+            for (int ks = 0; ks < DV / 32; ++ks) {
+                // (four operand reads in flight: hipcc would otherwise hoist all of a tile's reads and spill)
+                if (ks % 4 == 0) __builtin_amdgcn_sched_barrier(0);
+                sacc[kb] = mfma16<Tag>(*reinterpret_cast<const s16x8*>(lat + MlaSwz::off(16 * kb + r, 4 * ks + g)), qvf[ks], sacc[kb]);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // both score tiles live in VGPRs at one point (kv_split_kernel: the second chain must not end in the first one's registers)
+        asm volatile("" : "+v"(sacc[0]), "+v"(sacc[1]));
+        // the row's band: register i of block kb holds key k0 + 16 kb + 4 g + i
+        float mx = -INFINITY;
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int key = k0 + 16 * kb + 4 * g + i;
+                const float x = (key >= rlo && key <= rhi) ? sacc[kb][i] : -INFINITY;
+                sacc[kb][i] = x;
+                mx = fmaxf(mx, x);
+            }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float m_new = fmaxf(m_run, mx);
+        const float m_use = m_new == -INFINITY ? 0.f : m_new;
+        const float alpha = __builtin_amdgcn_exp2f((m_run - m_use) * p.c_log2);
+        const float mc = m_use * p.c_log2;
+        m_run = m_new;
+        l_run *= alpha;
+#pragma unroll
+        for (int t = 0; t < NDB; ++t) oacc[t] *= alpha;
+        // P^T as the B operand of O^T = V^T P^T: k-slot 8 g + j is key 4 g + j (j < 4) and 16 + 4 g + j - 4 (j >= 4)
+        u32x4 pk;
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const float e0 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][2 * j], p.c_log2, -mc));
+                const float e1 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][2 * j + 1], p.c_log2, -mc));
+                l_run += e0 + e1;
+                pk[2 * kb + j] = pack2<Tag>(e0, e1);
+            }
+        const s16x8 pb = *reinterpret_cast<s16x8*>(&pk);
+        // V^T operand from the same latent image: rows (keys) 4 g + q and 16 + 4 g + q, head dims 16 t + 4 p ..
+#pragma unroll
+        for (int t = 0; t < NDB; ++t) {
+            if (t % 4 == 0) __builtin_amdgcn_sched_barrier(0);
+            const int ch = 2 * t + (p4 >> 1), bo = 8 * (p4 & 1);
+            const s16x4 lo = lds_tr16(lat + MlaSwz::off(4 * g + q4, ch) + bo);
+            const s16x4 hi = lds_tr16(lat + MlaSwz::off(16 + 4 * g + q4, ch) + bo);
+            oacc[t] = mfma16<Tag>(cat8(lo, hi), pb, oacc[t]);
+        }
+    }
+
+    // ---- epilogue (kv_split_kernel's): O^T register i of block t is head dim 16 t + 4 g + i
+    float l_tot = l_run + __shfl_xor(l_run, 16, 64);
+    l_tot += __shfl_xor(l_tot, 32, 64);
+    const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
+    const float lse_v = l_tot > 0.f ? m_run * p.scale + logf(l_tot) : -INFINITY;
+    if (!valid) return;
+    const size_t row_id = ((size_t)b * p.hq + h) * nq + qi;
+    if (S == 1) {
+        uint16_t* orow = p.o + ((size_t)(tok0 + qi) * p.hq + h) * DV;
+#pragma unroll
+        for (int t = 0; t < NDB; ++t) {
+            u32x2 v;
+            v[0] = pack2_rn<Tag>(oacc[t][0] * inv, oacc[t][1] * inv);
+            v[1] = pack2_rn<Tag>(oacc[t][2] * inv, oacc[t][3] * inv);
+            *reinterpret_cast<u32x2*>(orow + 16 * t + 4 * g) = v;
+        }
+        if (g == 0) p.lse[row_id] = lse_v;
+    } else {
+        float* prow = p.po + (row_id * S + s) * DV;
+#pragma unroll
+        for (int t = 0; t < NDB; ++t) *reinterpret_cast<f32x4_t*>(prow + 16 * t + 4 * g) = oacc[t] * inv;
+        if (g == 0) p.plse[row_id * S + s] = lse_v;
+    }
+}
+
+// kv_combine_kernel for 512-wide rows: one wave per (b, h_q, token) row, four rows a workgroup; the weights as there, then lane c
+// adds head dims 256 j + 4 c .. + 3 (j = 0, 1) of the O partials in split order.  A split with lse_s = -inf has weight 0 and its
+// O partial, which it never wrote, is selected away; a row without any visible key gives o = 0, lse = -inf.  Same bits on every run.
+template <typename Tag>
+__global__ __launch_bounds__(256) void mla_combine_kernel(KvParams p, int S, long long nrows) {
+    constexpr int DV = kMlaDv;
+    __shared__ float wsh[4][256];
+    const int wv = threadIdx.x >> 6, c = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + wv;
+    if (row >= nrows) return;   // (wave-uniform; the LDS rows are wave-private, no barrier)
+    const float* pl = p.plse + row * S;
+    int h;
+    long long orow;
+    if (!kv_combine_row(p, row, pl, h, orow)) return;
+    float m = -INFINITY;
+    for (int s = c; s < S; s += 64) m = fmaxf(m, pl[s]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    float sum = 0.f;
+    for (int s = c; s < S; s += 64) {
+        const float ls = pl[s];
+        const float wgt = (ls == -INFINITY) ? 0.f : __expf(ls - m);
+        wsh[wv][s] = wgt;
+        sum += wgt;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    const float inv = sum > 0.f ? 1.f / sum : 0.f;
+#pragma unroll
+    for (int j = 0; j < DV / 256; ++j) {
+        const int col = 256 * j + 4 * c;
+        const float* po = p.po + row * S * DV + col;
+        f32x4_t acc = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 8
+        for (int s = 0; s < S; ++s) {
+            const float wgt = wsh[wv][s];
+            const f32x4_t x = *reinterpret_cast<const f32x4_t*>(po + (size_t)s * DV);
+            acc += (wgt != 0.f) ? wgt * x : f32x4_t{0.f, 0.f, 0.f, 0.f};
+        }
+        u32x2 v;
+        v[0] = pack2_rn<Tag>(acc[0] * inv, acc[1] * inv);
+        v[1] = pack2_rn<Tag>(acc[2] * inv, acc[3] * inv);
+        *reinterpret_cast<u32x2*>(p.o + orow * DV + col) = v;
+    }
+    if (c == 0) p.lse[row] = sum > 0.f ? m + logf(sum) : -INFINITY;
+}
+
+template <typename Tag, int NW>
+hipError_t launch_mla_split(const MlaParams& mp, int S, int batch, hipStream_t st) {
+    const int wg_tiles = (mp.p.rows + 16 * NW - 1) / (16 * NW);
+    const dim3 grid((unsigned)S, (unsigned)(wg_tiles * mp.p.hkv), (unsigned)batch);
+    if (mp.p.table) hipLaunchKernelGGL((mla_split_kernel<Tag, NW, true>), grid, dim3(64 * NW), 0, st, mp);
+    else hipLaunchKernelGGL((mla_split_kernel<Tag, NW, false>), grid, dim3(64 * NW), 0, st, mp);
+    return hipGetLastError();
+}
+
+template <typename Tag>
+hipError_t launch_mla_t(const MlaParams& mp, int S, int batch, hipStream_t st) {
+    const int nw = mla_waves(mp.p.rows);
+    hipError_t e = nw == 1 ? launch_mla_split<Tag, 1>(mp, S, batch, st)
+                 : nw == 2 ? launch_mla_split<Tag, 2>(mp, S, batch, st) : launch_mla_split<Tag, 4>(mp, S, batch, st);
+    if (e != hipSuccess || S == 1) return e;
+    const long long nrows = (long long)batch * mp.p.hq * mp.p.nq;
+    hipLaunchKernelGGL((mla_combine_kernel<Tag>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st, mp.p, S, nrows);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+// Waves a workgroup: one per 16-row tile of the rows = G * Nq packed rows of a (sequence, K/V head), at most four (one per SIMD)
+int mla_waves(int64_t rows) { return rows <= 16 ? 1 : rows <= 32 ? 2 : 4; }
+
+// kv_num_splits for mla_split_kernel.  A unit is a workgroup of mla_waves(rows) waves over 16 * waves rows, not a wave over 16.
+// The 16 x 512 fp32 accumulator beside the q and qv fragments takes a wave past 256 registers, so one wave runs per SIMD and a
+// CU holds 4 / waves workgroups (36 KiB of LDS each).  Enough splits to fill the 256 CUs once, none shorter than 128 keys, at
+// most 256 (the combine's weight row).
+int mla_num_splits(int64_t batch, int64_t heads_kv, int64_t rows, int64_t cache_len) {
+    constexpr int64_t kCUs = 256, kMinKeys = 128;
+    if (rows <= 0) return 1;
+    const int64_t nw = mla_waves(rows), per_cu = 4 / nw;
+    const int64_t units = batch * heads_kv * ((rows + 16 * nw - 1) / (16 * nw));
+    if (units <= 0 || cache_len <= 0) return 1;
+    int64_t s = (kCUs * per_cu + units - 1) / units;
+    s = std::min<int64_t>(s, (cache_len + kMinKeys - 1) / kMinKeys);
+    return (int)std::max<int64_t>(1, std::min<int64_t>(s, 256));
+}
+
+hipError_t launch_kvcache_mla(const KvArgs& a, hipStream_t st) {
+    if (a.d != kMlaDk || a.d_v != kMlaDv) return hipErrorInvalidValue;   // (the C layer's check)
+    MlaParams mp;
+    mp.p = kv_make_params(a);
+    mp.qv = (const uint16_t*)a.qv; mp.qv_bs = a.qv_bs; mp.qv_ts = (int)a.qv_ts;
+    const int S = (int)a.num_splits;
+    // workspace (S > 1): kv_workspace_bytes at d_v, the O partials and then the lse partials
+    const size_t q_rows = (size_t)a.batch * a.heads_q * a.seqlen_q;
+    mp.p.po = (float*)a.workspace;
+    mp.p.plse = S > 1 ? (float*)((char*)a.workspace + ((q_rows * S * kMlaDv * 4 + 255) & ~(size_t)255)) : nullptr;
+    return a.dtype == 1 ? launch_mla_t<f16_tag>(mp, S, (int)a.batch, st) : launch_mla_t<bf16_tag>(mp, S, (int)a.batch, st);
+}
+
+}  // namespace fa

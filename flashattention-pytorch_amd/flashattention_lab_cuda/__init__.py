@@ -47,6 +47,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_ex_forward_sink", "fa_ex_backward_sink", "fa_ex_forward_varlen_sink", "fa_ex_backward_varlen_sink",
     "fa_ex_forward_kvcache_sink", "fa_ex_kvcache_workspace_bytes_sink",
     "fa_ex_forward_kvcache_varlen", "fa_ex_kvcache_workspace_bytes_varlen",
+    "fa_ex_forward_kvcache_qv", "fa_ex_kvcache_workspace_bytes_qv",
     "fa_ex_forward_varlen_paged", "fa_ex_forward_varlen_paged_fp8",
     "fa_rotary_apply",
     "fa_ex_backward_dlse", "fa_ex_backward_varlen_dlse", "fa_merge_states", "fa_merge_states_backward",
@@ -94,6 +95,7 @@ _PAGED = _fields("p:block_table i:block_table_row_stride,num_blocks,page_block_s
                  "p:cache_leftpad")
 _ROTARY = _fields("p:rotary_cos,rotary_sin i:rotary_cos_row_stride,rotary_sin_row_stride,seqlen_ro,rotary_dim c:rotary_interleaved")
 _KVVARLEN = _fields("p:cu_seqlens_q,cu_seqlens_k_new i:total_q,max_seqlen_q,total_k_new")
+_KVQV = _fields("p:qv i:qv_batch_stride,qv_token_stride,d_v")
 _KVWS = _fields("i:batch,heads_q,heads_kv,seqlen_q,cache_len,d,num_splits")
 _ROXY = _fields("p:x,y i:batch,seqlen,heads,d c:dtype i:x_batch_stride,x_token_stride,y_batch_stride,y_token_stride")
 _ROPOS = _fields("c:conjugate i:seqlen_offset p:seqlen_offsets,cu_seqlens i:total,max_seqlen")
@@ -151,7 +153,8 @@ _sig("fa_ex_backward_workspace_bytes_grouped", _fields("i:bh") + _GROUP + _EXDIM
 _sig("fa_ex_backward_workspace_bytes_fast_grouped", _fields("i:bh") + _GROUP + _EXDIMS + _fields("c:causal,extras"), _SIZE)
 _sig("fa_ex_backward_workspace_bytes_varlen", _fields("i:heads_q,heads_kv,total_q,total_k,d c:dtype"), _SIZE)
 _kv = _KV   # each KV-cache entry point: the one before it and one more group, in front of the workspace
-for _suffix, _added in (("", ()), ("_paged", _PAGED), ("_rotary", _ROTARY), ("_fp8", _FP8), ("_sink", _SINK), ("_varlen", _KVVARLEN)):
+for _suffix, _added in (("", ()), ("_paged", _PAGED), ("_rotary", _ROTARY), ("_fp8", _FP8), ("_sink", _SINK), ("_varlen", _KVVARLEN),
+                        ("_qv", _KVQV)):
     _kv += _added
     _sig("fa_ex_forward_kvcache" + _suffix, _kv + _WS)
 _sig("fa_ex_kvcache_workspace_bytes fa_ex_kvcache_workspace_bytes_sink", _KVWS, _SIZE)
@@ -159,7 +162,9 @@ _sig("fa_rotary_apply", _ROXY + _ROTARY + _ROPOS + _STREAM)
 _sig("fa_merge_states", _fields("p:o_a,lse_a,o_b,lse_b,o,lse") + _MDIMS + _strides("o_a", "lse_a", "o_b", "lse_b", "o", "lse") + _STREAM)
 _sig("fa_merge_states_backward", _fields("p:o_a,lse_a,o_b,lse_b,do_,dlse,do_a,do_b,dlse_a,dlse_b") + _MDIMS +
      _strides("o_a", "lse_a", "o_b", "lse_b", "do", "dlse", "do_a", "do_b", "dlse_a", "dlse_b") + _STREAM)
-_sig("fa_ex_kvcache_workspace_bytes_varlen", _fields("i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,d,num_splits c:with_sinks"), _SIZE)
+_KVWSV = _fields("i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,d,num_splits c:with_sinks")
+_sig("fa_ex_kvcache_workspace_bytes_varlen", _KVWSV, _SIZE)
+_sig("fa_ex_kvcache_workspace_bytes_qv", _KVWSV + _fields("i:d_v"), _SIZE)
 
 
 def _load_library() -> ctypes.CDLL:
@@ -198,7 +203,7 @@ _family("fa_ex_forward_varlen_paged_fp8", ["fa_ex_forward_varlen_paged"])
 _family("fa_rotary_apply", [])
 _family("fa_merge_states", [])
 _family("fa_merge_states_backward", [])
-_family("fa_ex_forward_kvcache_varlen", ["fa_ex_forward_kvcache" + _suffix for _suffix in ("", "_paged", "_rotary", "_fp8", "_sink")])
+_family("fa_ex_forward_kvcache_qv", ["fa_ex_forward_kvcache" + _suffix for _suffix in ("", "_paged", "_rotary", "_fp8", "_sink", "_varlen")])
 
 
 def version() -> str:
@@ -876,13 +881,13 @@ def _rotary_tables(rotary_cos, rotary_sin, rdim, rotary_interleaved):
 
 
 # what the entry points after fa_ex_forward_kvcache add, for a call it serves: it takes none of them (see _call), any value does
-_KV_NOTHING_ADDED = (0,) * (len(_SIGNATURES["fa_ex_forward_kvcache_varlen"][1]) - len(_SIGNATURES["fa_ex_forward_kvcache"][1]))
+_KV_NOTHING_ADDED = (0,) * (len(_SIGNATURES["fa_ex_forward_kvcache_qv"][1]) - len(_SIGNATURES["fa_ex_forward_kvcache"][1]))
 
 
 def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlens=None, causal=False, softmax_scale=None,
                        window=(-1, -1), softcap=0.0, alibi_slopes=None, num_splits=0, block_table=None, cache_batch_idx=None,
                        cache_leftpad=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True, *, cu_seqlens_q=None,
-                       cu_seqlens_k_new=None, max_seqlen_q=None, sinks=None, k_descale=None, v_descale=None):
+                       cu_seqlens_k_new=None, max_seqlen_q=None, qv=None, sinks=None, k_descale=None, v_descale=None):
     """(o, lse) of a decode step over a KV cache (FlashAttention-2's flash_attn_with_kvcache, forward): q (B, Nq, H_q, d);
     k_cache, v_cache (B, cache_len, H_kv, d), used in place (strided views such as kv.unbind(2) allowed, never copied);
     k_new, v_new (B, N_new, H_kv, d) are written into the caches at cache_seqlens[b] first; cache_seqlens int32 (B,) on the
@@ -916,8 +921,24 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
     sequence without q tokens still appends; rows of o and lse that no sequence owns are left as allocated.  Neither array is
     read on the host: the kernels clamp them, as they clamp cache_seqlens, so no content reads or writes out of bounds.  Rotary
     needs seqlen_ro >= capacity + max_seqlen_q.  A 4-D q with cu_seqlens_q, a missing max_seqlen_q and a packed q that would need
-    a copy raise ValueError.  See fa_ex_forward_kvcache_varlen."""
+    a copy raise ValueError.  See fa_ex_forward_kvcache_varlen.
+    qv (keyword-only; FlashAttention-3's): a second query operand (B, Nq, H_q, 512) in q's dtype for K and V of different widths,
+    multi-head latent attention at decode time.  q and k_cache are then 64 wide, v_cache (.., H_kv, 512), o (B, Nq, H_q, 512), the
+    score is softmax_scale * (q . k + qv . v) and softmax_scale defaults to (64 + 512) ** -0.5.  k_cache and v_cache may be the two
+    slices of one (.., 576) pool: each view's own page and token strides are taken, never a copy (ValueError where that is not
+    possible); a token-strided qv is taken as it is.  Goes with cache_seqlens, cache_batch_idx, block_table, causal, window,
+    softmax_scale and num_splits; other widths, k_new / v_new, cu_seqlens_k_new, rotary_cos / rotary_sin, an e4m3 cache with
+    k_descale / v_descale, softcap, alibi_slopes, sinks, cu_seqlens_q and cache_leftpad raise NotImplementedError with the name.
+    See fa_ex_forward_kvcache_qv."""
     who = "ex_kvcache_forward"
+    if qv is not None:
+        for name, val in (("k / v (new tokens to append)", k_new if k_new is not None else v_new), ("cu_seqlens_k_new", cu_seqlens_k_new),
+                          ("rotary_cos / rotary_sin", rotary_cos if rotary_cos is not None else rotary_sin),
+                          ("k_descale / v_descale", k_descale if k_descale is not None else v_descale),
+                          ("softcap", softcap or None), ("alibi_slopes", alibi_slopes), ("sinks", sinks), ("cu_seqlens_q", cu_seqlens_q),
+                          ("cache_leftpad", cache_leftpad)):
+            if val is not None:
+                raise NotImplementedError(f"{who}: qv cannot be combined with {name}")
     wl, wr = window_arg(who, window)
     cap = softcap_arg(who, softcap)
     packed = cu_seqlens_q is not None
@@ -925,7 +946,7 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
         raise ValueError(f"{who}: cu_seqlens_k_new needs cu_seqlens_q")
     if max_seqlen_q is not None and not packed:
         raise ValueError(f"{who}: max_seqlen_q needs cu_seqlens_q")
-    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
+    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)) + ((("qv", qv),) if qv is not None else ()):
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
             raise RuntimeError(f"{who}: {name} must be a GPU (HIP device) tensor; there is no CPU path")
         if t.device != q.device:
@@ -964,6 +985,17 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
     if packed:
         b, nq = cu_seqlens_q.shape[0] - 1, mq
     cap_len, hkv = k_cache.shape[1], k_cache.shape[2]
+    dv = d   # the width of v_cache and o
+    if qv is not None:
+        if e4m3:
+            raise NotImplementedError(f"{who}: qv cannot be combined with an e4m3 cache (k_descale / v_descale)")
+        dv = v_cache.shape[3]
+        if (d, dv) != (64, 512):
+            raise NotImplementedError(f"{who}: qv is supported for q, k_cache of head dim 64 with v_cache of head dim 512 only "
+                                      f"(got {d}, {dv})")
+        if qv.dtype != q.dtype or qv.shape != (b, nq, hq, dv):
+            raise RuntimeError(f"{who}: qv must be a (B, Nq, H_q, {dv}) = ({b}, {nq}, {hq}, {dv}) tensor of q's dtype, got "
+                               f"{qv.dtype}, {tuple(qv.shape)}")
     for name, t, shape in (("block_table", block_table, "(B, max_blocks_per_seq)"), ("cache_batch_idx", cache_batch_idx, "(B,)"),
                            ("cache_leftpad", cache_leftpad, "(B,)")):
         if t is None:
@@ -980,7 +1012,7 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
             raise RuntimeError(f"{who}: page_block_size (k_cache.shape[1]) must be a positive multiple of 16, got {cap_len}")
     elif cache_batch_idx is not None:
         units = k_cache.shape[0]
-    if units == 0 or k_cache.shape != (units, cap_len, hkv, d) or v_cache.shape != k_cache.shape:
+    if units == 0 or k_cache.shape != (units, cap_len, hkv, d) or v_cache.shape != (units, cap_len, hkv, dv):
         what = "(num_blocks, page_block_size, H_kv, d)" if block_table is not None else \
             "(B_cache, cache_len, H_kv, d)" if cache_batch_idx is not None else "(B, cache_len, H_kv, d)"
         raise RuntimeError(f"{who}: k_cache and v_cache must be {what} = ({units}, ., ., {d}); got "
@@ -1006,7 +1038,7 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
         if k_new is None or cache_seqlens is None:
             raise RuntimeError(f"{who}: rotary_cos / rotary_sin need k, v (the new tokens) and cache_seqlens")
     kvb, kvt = _kv_strides(who, "k_cache", k_cache, hkv, d, True)
-    vvb, vvt = _kv_strides(who, "v_cache", v_cache, hkv, d, True)
+    vvb, vvt = _kv_strides(who, "v_cache", v_cache, hkv, dv, True)
     kdp, vdp, dsc_bs, _scales = _kv_descales(who, k_descale, v_descale, q, b, hkv)
     if e4m3:
         for name, t, bs_, ts_ in (("k_cache", k_cache, kvb, kvt), ("v_cache", v_cache, vvb, vvt)):
@@ -1054,7 +1086,13 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
     else:
         q = q.contiguous()
     qb, qt = _kv_strides(who, "q", q, hq, d, False)
-    scale = d ** -0.5 if softmax_scale is None else float(softmax_scale)
+    qvb = qvt = 0
+    if qv is not None:   # a view whose heads are adjacent is taken as it is (a token-strided one, say); anything else is copied
+        if qv.stride(3) != 1 or (hq > 1 and qv.stride(2) != dv) or qv.stride(1) % 8 or qv.stride(0) % 8 or qv.data_ptr() % 16 or \
+                (nq > 1 and qv.stride(1) < hq * dv) or (b > 1 and qv.stride(0) < (nq - 1) * qv.stride(1) + hq * dv):
+            qv = qv.contiguous()
+        qvb, qvt = _kv_strides(who, "qv", qv, hq, dv, False)
+    scale = (d + (dv if qv is not None else 0)) ** -0.5 if softmax_scale is None else float(softmax_scale)
     aptr, _h, astride, alibi_slopes = alibi_arg(who, alibi_slopes, q.device, b * hq, heads=hq)
     sptr, sheads, sinks = sinks_arg(who, sinks, q.device, b * hq, heads=hq)
     with torch.cuda.device(q.device):
@@ -1066,7 +1104,7 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
             cache_seqlens = cache_seqlens.contiguous()
         # the narrowest entry point that takes what the call carries (each adds a group of arguments to the one before), its
         # workspace query, and those groups: marshalled in one place, and not at all for a call that carries none of them
-        variant = "_varlen" if packed else "_sink" if sptr else "_fp8" if e4m3 else "_rotary" if rotary_cos is not None else \
+        variant = "_qv" if qv is not None else "_varlen" if packed else "_sink" if sptr else "_fp8" if e4m3 else "_rotary" if rotary_cos is not None else \
             "_paged" if (block_table is not None or cache_batch_idx is not None or cache_leftpad is not None) else ""
         code, capacity, added = _DTYPE_CODE[q.dtype], cap_len, _KV_NOTHING_ADDED
         if variant:
@@ -1081,11 +1119,16 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
                          units, cap_len, block_table.shape[1])
             _tabs, rotary = _rotary_tables(rotary_cos, rotary_sin, rdim, rotary_interleaved)
             added = (*paged, _ptr(cache_batch_idx), 0 if cache_batch_idx is None else units, _ptr(cache_leftpad), *rotary,
-                     _E4M3_CODE if e4m3 else code, kdp, vdp, dsc_bs, sptr, sheads, _ptr(cu_q), _ptr(cu_kn), total_q, mq, total_kn)
+                     _E4M3_CODE if e4m3 else code, kdp, vdp, dsc_bs, sptr, sheads, _ptr(cu_q), _ptr(cu_kn), total_q, mq, total_kn,
+                     _ptr(qv), qvb, qvt, dv if qv is not None else 0)
         if packed:
             o = torch.empty((total_q, hq, d), dtype=q.dtype, device=q.device)
             lse = torch.empty((hq, total_q), dtype=torch.float32, device=q.device)
             nbytes = int(_lib.fa_ex_kvcache_workspace_bytes_varlen(b, hq, hkv, total_q, mq, capacity, d, int(num_splits), int(bool(sptr))))
+        elif qv is not None:
+            o = torch.empty((b, nq, hq, dv), dtype=q.dtype, device=q.device)
+            lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)
+            nbytes = int(_lib.fa_ex_kvcache_workspace_bytes_qv(b, hq, hkv, b * nq, nq, capacity, d, int(num_splits), 0, dv))
         else:
             o = torch.empty((b, nq, hq, d), dtype=q.dtype, device=q.device)
             lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)

@@ -671,6 +671,45 @@ int fa_ex_forward_kvcache_varlen(const void* q, void* k_cache, void* v_cache, co
 size_t fa_ex_kvcache_workspace_bytes_varlen(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t max_seqlen_q,
                                             int64_t cache_len, int64_t d, int64_t num_splits, int with_sinks);
 
+/* --- a second query operand and K, V of different widths in KV-cache decoding (FlashAttention-3's qv): multi-head latent
+ * attention (MLA) at decode time.  fa_ex_forward_kvcache_varlen plus four arguments between total_k_new and workspace.  All null /
+ * 0: exactly that call.  With qv (device, q's dtype, (batch, seqlen_q, heads_q, d_v) at qv_batch_stride / qv_token_stride elements,
+ * heads adjacent at stride d_v, 16-byte aligned, strides multiples of 8) v_cache is (.., heads_kv, d_v) — a contiguous cache or a
+ * pool, addressed with its own batch / page and token strides, so k_cache and v_cache may be the two column ranges of one
+ * (.., d + d_v) allocation — o is (batch, seqlen_q, heads_q, d_v) dense, and for query head h reading K/V head h / G
+ *     s[i, j] = softmax_scale * (q[i, h, :] . k[j, :] + qv[i, h, :] . v[j, :]),   o[i, h, :] = sum_j softmax_j(s)[i, j] * v[j, :]
+ * (callers following FlashAttention-3 pass softmax_scale = (d + d_v)^-1/2).  Each row of v_cache is read from memory once and
+ * serves as the score operand and as the value operand.  cache_seqlens, block_table (untrusted; a page outside the pool reads as
+ * a zero key with a zero value), cache_batch_idx, causal, the window, num_splits, graph capture and the o = 0 / lse = -inf of a row
+ * without a visible key are as without qv.  Supported: d = 64 with d_v = 512; any other pair is FA_ERR_UNSUPPORTED, with both
+ * numbers in the text.  Not supported with qv, each FA_ERR_UNSUPPORTED with the argument's name before any HIP call: k_new / v_new
+ * (seqlen_new > 0), cu_seqlens_k_new, rotary_cos / rotary_sin, an e4m3 cache (cache_dtype, k_descale, v_descale), softcap,
+ * alibi_slopes, sinks, cu_seqlens_q, cache_leftpad.  (The checks every entry point of the family shares come first, in their
+ * order and with their texts: rotary tables without new tokens, for one, are refused there as FA_ERR_INVALID_ARGUMENT.)
+ * qv_batch_stride, qv_token_stride and d_v must be 0 without qv.
+ * The workspace is fa_ex_kvcache_workspace_bytes_qv: fa_ex_kvcache_workspace_bytes_varlen plus d_v (0: that query; pass total_q =
+ * batch * seqlen_q and max_seqlen_q = seqlen_q for the padded call): S * total_q * heads_q * (d_v + 1) floats for S > 1 splits, each
+ * part rounded up to 256 bytes, with S from this kernel's own launch rule when num_splits = 0. */
+int fa_ex_forward_kvcache_qv(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                             const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                             int64_t seqlen_q, int64_t seqlen_new, int64_t cache_len, int64_t d, int dtype, int64_t q_batch_stride,
+                             int64_t q_token_stride, int64_t k_cache_batch_stride, int64_t k_cache_token_stride,
+                             int64_t v_cache_batch_stride, int64_t v_cache_token_stride, int64_t k_new_batch_stride,
+                             int64_t k_new_token_stride, int64_t v_new_batch_stride, int64_t v_new_token_stride, int causal,
+                             int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
+                             const float* alibi_slopes, int64_t alibi_batch_stride, int64_t num_splits, const int32_t* block_table,
+                             int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq,
+                             const int32_t* cache_batch_idx, int64_t cache_batch, const int32_t* cache_leftpad,
+                             const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride,
+                             int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
+                             int cache_dtype, const float* k_descale, const float* v_descale, int64_t descale_batch_stride,
+                             const float* sinks, int64_t sink_heads, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k_new,
+                             int64_t total_q, int64_t max_seqlen_q, int64_t total_k_new, const void* qv, int64_t qv_batch_stride,
+                             int64_t qv_token_stride, int64_t d_v, void* workspace, size_t workspace_bytes,
+                             void* stream);
+size_t fa_ex_kvcache_workspace_bytes_qv(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t max_seqlen_q,
+                                        int64_t cache_len, int64_t d, int64_t num_splits, int with_sinks, int64_t d_v);
+
 /* --- Rotary position embedding for training and prefill (FlashAttention's flash_attn.layers.rotary: apply_rotary_emb,
  * apply_rotary_emb_qkv_), forward and backward.  One memory-bound launch on `stream` rotates the first rotary_dim head dims of
  * every head of one 16-bit tensor: x -> y, both (batch, seqlen, heads, d) with the heads adjacent at stride d, the last dim

@@ -39,6 +39,12 @@ and V are then 1 an element.  ex_forward and the unfused rotation keep the 16-bi
   of the rounds (each round itself the median of --reps groups).  (b) is checked to be bitwise (c) before anything is timed.
   --parent-check: only the packed ex_varlen_forward without a table at B H = 64, 4096 tokens, d = 128 (B = 2 sequences of 4096,
   32 heads, causal): the figure to compare between two checkouts, with the spread of its rounds.
+--mla: the call with a second query operand (qv=; q, k_cache 64 wide, qv, v_cache, o 512 wide) at (B, H_q, H_kv, Nq, len) =
+  (32, 128, 1, 1, 8192), (32, 16, 1, 1, 8192), (4, 128, 1, 2, 32768), bf16, the two caches as the slices of one (.., 576) pool,
+  contiguous and paged (page 64, shuffled; checked bitwise against the contiguous call first): the median time over --rounds
+  rounds with their spread, the split count the launch rule takes, and the cache bytes read per second with the cache counted
+  once per sequence, B * len * 576 * 2.  In the same run, the plain split kernel at d = 256, H_q / H_kv = 8 on a cache of the same
+  B and len (its bytes: B * len * H_kv * 256 * 2 * 2), from the unchanged code path.
 Timing: HIP events around `--iters` back-to-back calls after `--warmup` calls; the median of `--reps` such groups."""
 import argparse
 import json
@@ -302,6 +308,52 @@ def prefill_rows(args, dtype):
     return rows
 
 
+def mla_rows(args):
+    dev, dtype, d, dv, ps = "cuda", torch.bfloat16, 64, 512, 64
+    rows = []
+    t = lambda fn: [timed(fn, args.warmup, args.iters, args.reps) for _ in range(args.rounds)]   # noqa: E731
+    med = statistics.median
+
+    def figures(ts, nbytes):
+        return dict(us=round(med(ts), 2), rounds=[round(x, 2) for x in ts], spread=round((max(ts) - min(ts)) / med(ts), 4),
+                    TBps=round(nbytes / med(ts) / 1e6, 3))
+
+    for b, hq, hkv, nq, L in ((32, 128, 1, 1, 8192), (32, 16, 1, 1, 8192), (4, 128, 1, 2, 32768)):
+        q = torch.randn((b, nq, hq, d), device=dev, dtype=dtype)
+        qv = torch.randn((b, nq, hq, dv), device=dev, dtype=dtype)
+        pool = torch.randn((b, L, hkv, d + dv), device=dev, dtype=dtype)
+        sl = torch.full((b,), L, dtype=torch.int32, device=dev)
+        kc, vc = pool[..., dv:], pool[..., :dv]
+        mb = L // ps
+        table = torch.randperm(b * mb, generator=torch.Generator().manual_seed(b)).view(b, mb).to(torch.int32).to(dev)
+        ppool = torch.empty((b * mb, ps, hkv, d + dv), device=dev, dtype=dtype)
+        for bb in range(b):
+            ppool[table[bb].long()] = pool[bb].view(mb, ps, hkv, d + dv)
+        kp, vp = ppool[..., dv:], ppool[..., :dv]
+        cont = lambda: ext.ex_kvcache_forward(q, kc, vc, None, None, sl, True, None, qv=qv)                       # noqa: E731
+        paged = lambda: ext.ex_kvcache_forward(q, kp, vp, None, None, sl, True, None, block_table=table, qv=qv)   # noqa: E731
+        oc, op = cont(), paged()
+        assert torch.equal(oc[0], op[0]) and torch.equal(oc[1], op[1]), "paged and contiguous calls disagree"
+        nbytes = b * L * (d + dv) * 2
+        splits = next((s_ for s_ in range(2, 257) if ext._lib.fa_ex_kvcache_workspace_bytes_qv(b, hq, hkv, b * nq, nq, L, d, s_, 0, dv) ==
+                       ext._lib.fa_ex_kvcache_workspace_bytes_qv(b, hq, hkv, b * nq, nq, L, d, 0, 0, dv)), 1)
+        r = dict(kind="mla", B=b, Hq=hq, Hkv=hkv, nq=nq, len=L, splits=splits, cache_bytes=nbytes, contiguous=figures(t(cont), nbytes),
+                 paged_64=figures(t(paged), nbytes))
+        del pool, ppool, kc, vc, kp, vp
+        # the plain split kernel on a cache of the same B and len: d = 256, H_q / H_kv = 8
+        hq2, hkv2, d2 = 8, 1, 256
+        q2 = torch.randn((b, nq, hq2, d2), device=dev, dtype=dtype)
+        k2 = torch.randn((b, L, hkv2, d2), device=dev, dtype=dtype)
+        v2 = torch.randn((b, L, hkv2, d2), device=dev, dtype=dtype)
+        plain = lambda: ext.ex_kvcache_forward(q2, k2, v2, None, None, sl, True, None)   # noqa: E731
+        r["plain_d256_g8"] = figures(t(plain), b * L * hkv2 * d2 * 2 * 2)
+        rows.append(r)
+        print(json.dumps(r), flush=True)
+        del q2, k2, v2
+        torch.cuda.empty_cache()
+    return rows
+
+
 def parent_check(args, dtype):
     dev, b, h, n, d = "cuda", 2, 32, 4096, 128
     q, k, v = (torch.randn((b * n, h, d), device=dev, dtype=dtype) for _ in range(3))
@@ -337,6 +389,7 @@ def main():
     ap.add_argument("--prefill-lens", default="8192,32768")
     ap.add_argument("--rounds", type=int, default=3, help="--prefill / --parent-check: interleaved rounds per figure")
     ap.add_argument("--parent-check", action="store_true", help="time only the packed varlen forward at B H = 64, 4096 tokens, d = 128")
+    ap.add_argument("--mla", action="store_true", help="time the call with qv (64 + 512 head dims): see the module docstring")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     args.chunks = [int(x) for x in args.chunks.split(",")]
@@ -351,6 +404,12 @@ def main():
         ext.ex_kvcache_forward(wq, wk, wk, None, None, wl, True, None)
     torch.cuda.synchronize()
     del wq, wk
+    if args.mla:
+        rows = mla_rows(args)
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(dict(mla=True, version=ext.version(), rows=rows), f, indent=1)
+        return
     if args.prefill or args.parent_check:
         rows = parent_check(args, dtype) if args.parent_check else prefill_rows(args, dtype)
         if args.json:
