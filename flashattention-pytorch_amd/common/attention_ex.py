@@ -496,3 +496,33 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
                                         k_descale=None if k_descale is None else k_descale.detach(),
                                         v_descale=None if v_descale is None else v_descale.detach(), **extra)
     return (o, lse) if return_softmax_lse else o
+
+
+def flash_mla_sparse_attn(q, qv, k_cache, v_cache, indices, *, cache_seqlens=None, block_table=None, cache_batch_idx=None,
+                          softmax_scale=None, causal=False, num_splits=0, return_softmax_lse=False):
+    """Sparse multi-head latent attention at decode time (DeepSeek sparse attention): flash_attn_with_kvcache(..., qv=qv) over a
+    per-query list of cached tokens instead of every token of the sequence.  q (B, Nq, H_q, 64), qv (B, Nq, H_q, 512), k_cache
+    (.., H_kv, 64) and v_cache (.., H_kv, 512) exactly as that call takes them: contiguous (B, cache_len, H_kv, .) caches, rows
+    picked by cache_batch_idx, or pools under block_table; views of one (.., 576) allocation are used with their own strides,
+    never copied.  indices: int32 (B, Nq, topk), one list per query token for all K/V heads, or (B, Nq, H_kv, topk), on q's device,
+    last dim contiguous.  An entry is a token position of sequence b; for query token i and head h reading K/V head h // G
+        visible(j)  <=>  0 <= I[j] < len_b  and, if causal,  I[j] <= len_b - Nq + i           (len_b = cache_seqlens[b], clamped)
+        s[j] = softmax_scale * (q[b, i, h] . k[I[j]] + qv[b, i, h] . v[I[j]]),    o[b, i, h] = sum_j softmax_j(s)[j] v[I[j]]
+    over the visible j.  Every list position is a key (a token named twice counts twice); -1 padding and any entry outside the
+    sequence are skipped and never read; a row without a visible entry gives o = 0, lse = -inf.  A visible entry on a page outside
+    the pool reads as a zero key with a zero value (flash_attn_with_kvcache's rule).  cache_seqlens: int32 (B,) on the device, an int
+    or None (the capacity).  softmax_scale defaults to (64 + 512) ** -0.5.  Nothing is read on the host: the call can be captured
+    in a graph and replayed with changed indices, lengths and tables.  indices (block_table, cache_batch_idx) of another dtype
+    raise NotImplementedError with the name; wrong shapes and devices RuntimeError.  No window, softcap, ALiBi, sinks, rotary, new
+    tokens, e4m3 cache, packed queries or left padding.
+    Returns o (B, Nq, H_q, 512), and with return_softmax_lse also lse (B, H_q, Nq) float32.  No gradient."""
+    for name, val in (("indices", indices), ("block_table", block_table), ("cache_batch_idx", cache_batch_idx)):
+        if (val is not None or name == "indices") and not (isinstance(val, torch.Tensor) and val.dtype == torch.int32):
+            dt = val.dtype if isinstance(val, torch.Tensor) else type(val).__name__
+            raise NotImplementedError(f"flash_mla_sparse_attn: {name} of dtype {dt} is not supported (int32 tensor expected)")
+    import flashattention_lab_cuda as ext
+
+    with torch.no_grad():
+        o, lse = ext.ex_mla_sparse_forward(q.detach(), qv.detach(), k_cache, v_cache, indices, cache_seqlens, bool(causal), softmax_scale,
+                                           block_table, cache_batch_idx, num_splits)
+    return (o, lse) if return_softmax_lse else o

@@ -1616,6 +1616,184 @@ int fa_ex_forward_kvcache_qv(const void* q, void* k_cache, void* v_cache, const 
     return kvcache_impl("fa_ex_forward_kvcache_qv", c);
 }
 
+// ---- sparse MLA decoding: see include/fa_mi355x.h
+static int64_t mla_sparse_splits(int64_t batch, int64_t hq, int64_t hkv, int64_t nq, int64_t topk, int64_t num_splits) {
+    if (num_splits > 0) return num_splits;
+    return fa::mla_sparse_num_splits(batch * nq, hkv, hq / hkv, topk);
+}
+
+size_t fa_mla_sparse_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t topk, int64_t num_splits) {
+    if (batch <= 0 || heads_q <= 0 || heads_kv <= 0 || heads_q % heads_kv != 0 || seqlen_q <= 0 || topk < 0 || num_splits < 0 || num_splits > 256)
+        return 0;
+    return fa::kv_workspace_bytes(1, heads_q, batch * seqlen_q, 512, (int)mla_sparse_splits(batch, heads_q, heads_kv, seqlen_q, topk, num_splits));
+}
+
+// One call of the fa_mla_sparse_forward family, a field per argument under its name in the header.  Defaults: "argument absent".
+struct MlaSparseCall {
+    const void *q = nullptr, *qv = nullptr, *k_cache = nullptr, *v_cache = nullptr;
+    const int32_t *indices = nullptr, *cache_seqlens = nullptr;
+    void* o = nullptr;
+    float* lse = nullptr;
+    int64_t batch = 0, heads_q = 0, heads_kv = 0, seqlen_q = 0, cache_len = 0, topk = 0, d = 0, d_v = 0;
+    int dtype = 0;
+    int64_t q_batch_stride = 0, q_token_stride = 0, qv_batch_stride = 0, qv_token_stride = 0, k_cache_batch_stride = 0,
+            k_cache_token_stride = 0, v_cache_batch_stride = 0, v_cache_token_stride = 0, indices_batch_stride = 0,
+            indices_token_stride = 0, indices_head_stride = 0;
+    int causal = 0;
+    double softmax_scale = 0.0;
+    int64_t num_splits = 0;
+    const int32_t *block_table = nullptr, *cache_batch_idx = nullptr;
+    int64_t block_table_row_stride = 0, num_blocks = 0, page_block_size = 0, max_blocks_per_seq = 0, cache_batch = 0;
+    void *workspace = nullptr, *stream = nullptr;
+    size_t workspace_bytes = 0;
+};
+
+// The checks, in the order the header documents: (0) the shape's signs and the empty call; (1) null pointers; (2) widths; (3) dtype,
+// then the ranges of the shape; (4) strides and alignment of every tensor; (5) indices; (6) the page geometry; (7) the workspace.
+static int mla_sparse_impl(const char* who, const MlaSparseCall& c) {
+    if (c.batch < 0 || c.seqlen_q < 0 || c.heads_q < 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch, seqlen_q and heads_q must be >= 0 (got %lld, %lld, %lld)", who, (long long)c.batch,
+                    (long long)c.seqlen_q, (long long)c.heads_q);
+    if (c.batch == 0 || c.seqlen_q == 0 || c.heads_q == 0) return FA_OK;   // no row: no launch
+    // (1)
+    if (!c.q || !c.qv || !c.k_cache || !c.v_cache || !c.o || !c.lse || (!c.indices && c.topk != 0))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    // (2)
+    if (c.d != 64 || c.d_v != 512)
+        return fail(FA_ERR_UNSUPPORTED, "%s: supported for head_dim = 64 with d_v = 512 only (got head_dim = %lld, d_v = %lld)", who,
+                    (long long)c.d, (long long)c.d_v);
+    // (3)
+    if (c.dtype != FA_DTYPE_F16 && c.dtype != FA_DTYPE_BF16)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: dtype must be f16 or bf16 (got code %d)", who, c.dtype);
+    if (c.heads_kv < 1 || c.heads_q % c.heads_kv != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads_q=%lld must be a positive multiple of heads_kv=%lld", who, (long long)c.heads_q,
+                    (long long)c.heads_kv);
+    if (!(c.softmax_scale == c.softmax_scale) || c.softmax_scale - c.softmax_scale != 0.0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale must be finite (got %g)", who, c.softmax_scale);
+    if (!scale_ok(c.softmax_scale)) return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale must be > 0 (got %g)", who, c.softmax_scale);
+    if (c.num_splits < 0 || c.num_splits > 256)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_splits must lie in [0, 256] (got %lld)", who, (long long)c.num_splits);
+    const bool paged = c.block_table != nullptr;
+    if (!paged && c.cache_len < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_len must be >= 1 (got %lld)", who, (long long)c.cache_len);
+    if (c.cache_batch_idx) {
+        if (paged) return fail(FA_ERR_INVALID_ARGUMENT, "%s: block_table cannot be combined with cache_batch_idx", who);
+        if (c.cache_batch < 1 || c.cache_batch > 0x7fffffff)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_batch must lie in [1, 2^31) with cache_batch_idx (got %lld)", who,
+                        (long long)c.cache_batch);
+    } else if (c.cache_batch != 0) {
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_batch must be 0 without cache_batch_idx (got %lld)", who, (long long)c.cache_batch);
+    }
+    // (one list per grid column, the K/V heads' row tiles along z, the combine one wave per row)
+    if (c.batch > 0x7fffffff / c.seqlen_q || c.heads_q > 65535 || c.cache_len > ((int64_t)1 << 28) || c.seqlen_q > ((int64_t)1 << 24) ||
+        c.batch * c.seqlen_q * c.heads_q >= ((int64_t)1 << 31))
+        return fail(FA_ERR_UNSUPPORTED, "%s: problem too large for one launch", who);
+    // (4) the heads of a token adjacent at its width, tokens at >= heads * width, units past the last token's heads
+    const int64_t c_n = paged ? c.page_block_size : c.cache_len;
+    const int64_t c_units = paged ? c.num_blocks : c.cache_batch_idx ? c.cache_batch : c.batch;
+    struct { const char* name; int64_t bs, ts, n, heads, units, w; } st[4] = {
+        {"q", c.q_batch_stride, c.q_token_stride, c.seqlen_q, c.heads_q, c.batch, c.d},
+        {"qv", c.qv_batch_stride, c.qv_token_stride, c.seqlen_q, c.heads_q, c.batch, c.d_v},
+        {"k_cache", c.k_cache_batch_stride, c.k_cache_token_stride, c_n, c.heads_kv, c_units, c.d},
+        {"v_cache", c.v_cache_batch_stride, c.v_cache_token_stride, c_n, c.heads_kv, c_units, c.d_v}};
+    for (auto& t : st) {
+        const int64_t span = (t.n > 0 ? (t.n - 1) * t.ts : 0) + t.heads * t.w;   // elements of one batch element (or page)
+        if (t.ts < t.heads * t.w || (t.units > 1 && t.bs < span) || t.bs < 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of %s too small (batch %lld, token %lld; need token >= %lld, batch >= %lld)",
+                        who, t.name, (long long)t.bs, (long long)t.ts, (long long)(t.heads * t.w), (long long)span);
+        if (t.ts % 8 != 0 || t.bs % 8 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of %s must be multiples of 8 elements", who, t.name);
+        if (span * 2 >= ((int64_t)1 << 31) || t.bs > ((int64_t)1 << 44))
+            return fail(FA_ERR_UNSUPPORTED, "%s: one batch element of %s spans %lld bytes, beyond 32-bit offsets", who, t.name,
+                        (long long)(span * 2));
+    }
+    if (!aligned16({c.q, c.qv, c.k_cache, c.v_cache, c.o}))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: tensors must be 16-byte aligned", who);
+    if ((uintptr_t)c.lse % 4 != 0 || (uintptr_t)c.indices % 4 != 0 || (uintptr_t)c.cache_seqlens % 4 != 0 || (uintptr_t)c.block_table % 4 != 0 ||
+        (uintptr_t)c.cache_batch_idx % 4 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: lse, indices, cache_seqlens, block_table and cache_batch_idx must be 4-byte aligned", who);
+    // (5) a list is topk adjacent entries; head stride 0: one list for the K/V heads of a token
+    if (c.topk < 0 || c.topk > ((int64_t)1 << 30))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: topk must lie in [0, 2^30] (got %lld)", who, (long long)c.topk);
+    const int64_t kIxMax = (int64_t)1 << 40;
+    const int64_t ix_tok = c.indices_head_stride > 0 ? (c.heads_kv - 1) * c.indices_head_stride + c.topk : c.topk;
+    const int64_t ix_seq = (c.seqlen_q - 1) * c.indices_token_stride + ix_tok;
+    if ((c.indices_head_stride != 0 && c.indices_head_stride < c.topk) || c.indices_head_stride > kIxMax ||
+        (c.seqlen_q > 1 && c.indices_token_stride < ix_tok) || c.indices_token_stride < 0 || c.indices_token_stride > kIxMax ||
+        (c.batch > 1 && c.indices_batch_stride < ix_seq) || c.indices_batch_stride < 0 || c.indices_batch_stride > kIxMax)
+        return fail(FA_ERR_INVALID_ARGUMENT,
+                    "%s: strides of indices (batch %lld, token %lld, head %lld): head must be 0 or >= topk = %lld, token >= %lld, batch >= %lld "
+                    "(each <= 2^40)", who, (long long)c.indices_batch_stride, (long long)c.indices_token_stride,
+                    (long long)c.indices_head_stride, (long long)c.topk, (long long)ix_tok, (long long)ix_seq);
+    // (6)
+    int64_t capacity = c.cache_len;
+    if (paged) {
+        if (c.page_block_size < 16 || c.page_block_size % 16 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: page_block_size must be a positive multiple of 16 (got %lld)", who,
+                        (long long)c.page_block_size);
+        if (c.num_blocks < 1 || c.num_blocks > 0x7fffffff)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_blocks must lie in [1, 2^31) (got %lld)", who, (long long)c.num_blocks);
+        if (c.max_blocks_per_seq < 1)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: max_blocks_per_seq must be >= 1 (got %lld)", who, (long long)c.max_blocks_per_seq);
+        if (c.max_blocks_per_seq > ((int64_t)1 << 28) / c.page_block_size)
+            return fail(FA_ERR_UNSUPPORTED, "%s: capacity max_blocks_per_seq * page_block_size = %lld * %lld is beyond 2^28 tokens", who,
+                        (long long)c.max_blocks_per_seq, (long long)c.page_block_size);
+        if (c.block_table_row_stride < c.max_blocks_per_seq || c.block_table_row_stride > ((int64_t)1 << 40))
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: block_table_row_stride=%lld must be >= max_blocks_per_seq=%lld (and <= 2^40)", who,
+                        (long long)c.block_table_row_stride, (long long)c.max_blocks_per_seq);
+        capacity = c.max_blocks_per_seq * c.page_block_size;
+    } else if (c.block_table_row_stride != 0 || c.num_blocks != 0 || c.page_block_size != 0 || c.max_blocks_per_seq != 0) {
+        return fail(FA_ERR_INVALID_ARGUMENT,
+                    "%s: block_table_row_stride, num_blocks, page_block_size and max_blocks_per_seq must be 0 without block_table", who);
+    }
+    // (7)
+    const int64_t S = mla_sparse_splits(c.batch, c.heads_q, c.heads_kv, c.seqlen_q, c.topk, c.num_splits);
+    if (S > 1 && c.batch * c.seqlen_q * c.heads_q >= ((int64_t)1 << 26))   // the combine: one wave per row, 2^32 lanes per launch
+        return fail(FA_ERR_UNSUPPORTED, "%s: batch * seqlen_q * heads_q = %lld rows are too many to combine %lld splits in one launch", who,
+                    (long long)(c.batch * c.seqlen_q * c.heads_q), (long long)S);
+    const size_t need = fa::kv_workspace_bytes(1, c.heads_q, c.batch * c.seqlen_q, c.d_v, (int)S);
+    if (c.workspace_bytes < need || (need > 0 && !c.workspace))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace of %zu bytes needed, %zu given", who, need, c.workspace_bytes);
+    if (need > 0 && !aligned16({c.workspace})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
+    fa::MlaSparseArgs a{};
+    fa::KvArgs& kv = a.kv;
+    kv.q = c.q; kv.qv = c.qv; kv.k_cache = const_cast<void*>(c.k_cache); kv.v_cache = const_cast<void*>(c.v_cache); kv.o = c.o; kv.lse = c.lse;
+    kv.cache_seqlens = c.cache_seqlens; kv.block_table = c.block_table; kv.cache_batch_idx = c.cache_batch_idx;
+    kv.table_row_stride = c.block_table_row_stride; kv.num_blocks = c.num_blocks; kv.page_size = c.page_block_size; kv.cache_batch = c.cache_batch;
+    kv.batch = c.batch; kv.heads_q = c.heads_q; kv.heads_kv = c.heads_kv; kv.seqlen_q = c.seqlen_q; kv.cache_len = capacity;
+    kv.d = c.d; kv.d_v = c.d_v; kv.dtype = c.dtype; kv.causal = c.causal ? 1 : 0;
+    kv.q_bs = c.q_batch_stride; kv.q_ts = c.q_token_stride; kv.qv_bs = c.qv_batch_stride; kv.qv_ts = c.qv_token_stride;
+    kv.kc_bs = c.k_cache_batch_stride; kv.kc_ts = c.k_cache_token_stride; kv.vc_bs = c.v_cache_batch_stride; kv.vc_ts = c.v_cache_token_stride;
+    kv.window_left = kv.window_right = -1;
+    kv.scale = (float)c.softmax_scale; kv.num_splits = S; kv.workspace = c.workspace;
+    a.indices = c.indices; a.ix_bs = c.indices_batch_stride; a.ix_ts = c.indices_token_stride; a.ix_hs = c.indices_head_stride; a.topk = c.topk;
+    return launched(who, fa::launch_mla_sparse(a, reinterpret_cast<hipStream_t>(c.stream)));
+}
+
+int fa_mla_sparse_forward(const void* q, const void* qv, const void* k_cache, const void* v_cache, const int32_t* indices,
+                          const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q,
+                          int64_t cache_len, int64_t topk, int64_t d, int64_t d_v, int dtype, int64_t q_batch_stride, int64_t q_token_stride,
+                          int64_t qv_batch_stride, int64_t qv_token_stride, int64_t k_cache_batch_stride, int64_t k_cache_token_stride,
+                          int64_t v_cache_batch_stride, int64_t v_cache_token_stride, int64_t indices_batch_stride,
+                          int64_t indices_token_stride, int64_t indices_head_stride, int causal, double softmax_scale, int64_t num_splits,
+                          const int32_t* block_table, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
+                          int64_t max_blocks_per_seq, const int32_t* cache_batch_idx, int64_t cache_batch, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    MlaSparseCall c;
+    c.q = q; c.qv = qv; c.k_cache = k_cache; c.v_cache = v_cache; c.indices = indices; c.cache_seqlens = cache_seqlens; c.o = o; c.lse = lse;
+    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.seqlen_q = seqlen_q; c.cache_len = cache_len; c.topk = topk;
+    c.d = d; c.d_v = d_v; c.dtype = dtype;
+    c.q_batch_stride = q_batch_stride; c.q_token_stride = q_token_stride; c.qv_batch_stride = qv_batch_stride; c.qv_token_stride = qv_token_stride;
+    c.k_cache_batch_stride = k_cache_batch_stride; c.k_cache_token_stride = k_cache_token_stride;
+    c.v_cache_batch_stride = v_cache_batch_stride; c.v_cache_token_stride = v_cache_token_stride;
+    c.indices_batch_stride = indices_batch_stride; c.indices_token_stride = indices_token_stride; c.indices_head_stride = indices_head_stride;
+    c.causal = causal; c.softmax_scale = softmax_scale; c.num_splits = num_splits;
+    c.block_table = block_table; c.block_table_row_stride = block_table_row_stride; c.num_blocks = num_blocks;
+    c.page_block_size = page_block_size; c.max_blocks_per_seq = max_blocks_per_seq;
+    c.cache_batch_idx = cache_batch_idx; c.cache_batch = cache_batch;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    return mla_sparse_impl("fa_mla_sparse_forward", c);
+}
+
 // One call of the fa_rotary_apply family, a field per argument under its name in the header.  Defaults: "argument absent".
 struct RotaryCall {
     const void* x = nullptr;

@@ -262,6 +262,19 @@ size_t kv_workspace_bytes(int64_t batch, int64_t heads_q, int64_t seqlen_q, int6
 hipError_t launch_kvcache(const KvArgs& a, hipStream_t st);
 hipError_t launch_kvcache_mla(const KvArgs& a, hipStream_t st);
 
+// Sparse MLA decoding (fa_mla.hip; fa_mla_sparse_forward): the qv call over a list of cached tokens per (sequence, query token,
+// K/V head).  kv: that call's arguments (d = 64, d_v = 512, no window); indices: untrusted device int32 token positions, entry j
+// of (b, i, hk) at indices[b * ix_bs + i * ix_ts + hk * ix_hs + j], j < topk.  An entry outside [0, L_b) (causal: above
+// L_b - seqlen_q + i) is no key and is never turned into an address.
+struct MlaSparseArgs {
+    KvArgs kv;
+    const int* indices;
+    int64_t ix_bs, ix_ts, ix_hs, topk;
+};
+// its launch rule: units = batch * seqlen_q lists a K/V head, each a workgroup row of mla_waves(group) waves over the group's heads
+int mla_sparse_num_splits(int64_t units, int64_t heads_kv, int64_t group, int64_t topk);
+hipError_t launch_mla_sparse(const MlaSparseArgs& a, hipStream_t st);
+
 // Rotary embedding for training and prefill (fa_rotary.hip; fa_rotary_apply).  16-bit x, y (batch, seqlen, heads, d), heads at
 // stride d, strides multiples of 8 elements, 16-byte aligned; y == x (with x's strides) is the in-place form.  Tables as KvArgs'.
 struct RotaryArgs {

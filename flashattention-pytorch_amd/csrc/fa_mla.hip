@@ -17,6 +17,7 @@
 // workgroup is without rows unless the last row tile of a larger call is; the launch rule (mla_num_splits) then cuts the keys
 // into more splits, and the partial results meet in mla_combine_kernel in the fixed split order.  That is the merge a
 // workgroup-internal key split would need a second, LDS-resident copy of; here it is the one the split path already has.
+// Sparse form (fa_mla_sparse_forward): mla_sparse_kernel below, the same tile pipeline over a per-query list of token positions.
 #include "fa_decode_common.h"
 #include <algorithm>
 
@@ -360,6 +361,284 @@ hipError_t launch_mla_t(const MlaParams& mp, int S, int batch, hipStream_t st) {
     return hipGetLastError();
 }
 
+// ---- sparse MLA (fa_mla_sparse_forward): the keys of a (sequence b, query token i, K/V head hk) are the topk entries of a list
+// of token positions.  mla_sparse_kernel is mla_split_kernel with another producer of ko / vo: a workgroup serves one list
+// (blockIdx.x = b * nq + i; its rows are the G heads of hk, 16 a wave), a tile is 32 list positions, and from ko / vo on the copy
+// is the PAGED branch of load_lat / load_rot there (wave-uniform latent row through v_readlane, 16 bytes a lane, MlaSwz image).
+// Lane l holds entry j0 + (l & 31): one coalesced 128-byte read two tiles ahead of its use; a tile ahead the lane decides
+// visibility (0 <= entry < len_b, and <= len_b - nq + i if causal) and, paged, looks up its page.  An entry that is not visible
+// is never turned into an address: its row is zeros in LDS and its score is -inf by the tile's 32-bit ballot of the per-key flag.
+// A visible entry on a page outside the pool or in a cache row outside the cache is a zero row too, with score 0 (the page rule
+// of fa_decode.hip).  Splits cut the list positions [0, topk) into ranges of whole tiles; partials and mla_combine_kernel as above.
+struct MlaSparseParams {
+    MlaParams mp;          // mp.p.nq: the query tokens of a sequence (the window fields are not used)
+    const int* idx;        // entry j of (b, i, hk): idx[b * ix_bs + i * ix_ts + hk * ix_hs + j]; untrusted device memory
+    long long ix_bs, ix_ts, ix_hs;
+    int topk, causal;
+};
+
+template <typename Tag, int NW, bool PAGED>
+__global__ __launch_bounds__(64 * NW) void mla_sparse_kernel(MlaSparseParams sp) {
+    constexpr int KT = kMlaKT, DK = kMlaDk, DV = kMlaDv, NDB = DV / 16, T = 64 * NW;
+    constexpr int LCH = KT * (DV / 8) / T, RCH = KT * (DK / 8) / T;
+    static_assert(LCH * T == KT * DV / 8 && RCH >= 1, "tile copy");
+    __shared__ __attribute__((aligned(16))) char lds[kMlaLdsBytes];
+    char* const lat = lds;
+    char* const rop = lds + kMlaLatBytes;
+    const KvParams& p = sp.mp.p;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, g = lane >> 4;
+    const int s = blockIdx.y, S = gridDim.y;
+    const int hk = blockIdx.z % p.hkv, wt = blockIdx.z / p.hkv;
+    const int nq = p.nq, b = blockIdx.x / nq, qi = blockIdx.x - b * nq;
+    int L_b, P_b;
+    const int lk = kv_len_k(p, b, 0, L_b, P_b);
+    // visible token positions: [0, tlim)
+    const int thi = sp.causal ? lk - nq + qi : lk - 1;
+    const unsigned tlim = thi >= 0 ? (unsigned)thi + 1u : 0u;
+    // list positions [jbeg, jend) of split s: whole tiles
+    const int nt = (sp.topk + KT - 1) / KT;
+    const int jbeg = (int)((long long)s * nt / S) * KT, jend = min(sp.topk, (int)((long long)(s + 1) * nt / S) * KT);
+
+    // this wave's row tile of the G heads (none: the wave only copies) and this lane's head
+    const int pr0 = 16 * NW * wt + 16 * w, pr = pr0 + r;
+    const bool active = pr0 < p.G, valid = pr < p.G;
+    const int h = hk * p.G + (valid ? pr : 0);
+
+    s16x8 qf[DK / 32], qvf[DV / 32];
+    {
+        const buf_rsrc_t q_rs = make_rsrc(p.q + b * p.q_bs, (unsigned)(((nq - 1) * p.q_ts + p.hq * DK) * 2));
+        const buf_rsrc_t qv_rs = make_rsrc(sp.mp.qv + b * sp.mp.qv_bs, (unsigned)(((nq - 1) * sp.mp.qv_ts + p.hq * DV) * 2));
+#pragma unroll
+        for (int ks = 0; ks < DK / 32; ++ks) qf[ks] = buf_load_frag(q_rs, valid ? (qi * p.q_ts + h * DK + 32 * ks + 8 * g) * 2 : kOobOff);
+#pragma unroll
+        for (int ks = 0; ks < DV / 32; ++ks) qvf[ks] = buf_load_frag(qv_rs, valid ? (qi * sp.mp.qv_ts + h * DV + 32 * ks + 8 * g) * 2 : kOobOff);
+    }
+    // contiguous: cache row (bidx ? bidx[b] : b); a row outside the cache holds zero rows
+    long long crow = b;
+    if (!PAGED && p.bidx) {
+        const int ix = p.bidx[b];
+        crow = (unsigned)ix < (unsigned)p.bcache ? ix : -1;
+    }
+    const int* tbl = PAGED ? p.table + b * p.tbl_rs : nullptr;
+    const int* il = sp.idx + b * sp.ix_bs + qi * sp.ix_ts + hk * sp.ix_hs;
+
+    // The list pipeline of lane l (list position + (l & 31) of a tile): e2 the raw entry of the tile after next; s1 the next
+    // tile's visible entry as its token position (contiguous) or its slot in its page pg1 (paged), -1 = not visible.
+    int e2 = -1, s1 = -1, pg1 = -1;
+    auto entry = [&](int jt) {
+        const int pos = jt + (lane & 31);
+        return pos < jend ? il[pos] : -1;
+    };
+    auto advance = [&](int jt) {   // e2 -> s1 (pg1); e2 = the entries of the tile at jt
+        const bool vis = (unsigned)e2 < tlim;
+        if constexpr (PAGED) {
+            const unsigned j = (unsigned)e2 / (unsigned)p.ps;   // (< max_blocks_per_seq: e2 < len_b <= the capacity)
+            s1 = vis ? (int)((unsigned)e2 - j * (unsigned)p.ps) : -1;
+            pg1 = vis ? tbl[j] : -1;
+        } else {
+            s1 = vis ? e2 : -1;
+        }
+        e2 = entry(jt);
+    };
+    if (jbeg < jend) {
+        e2 = entry(jbeg);
+        advance(jbeg + KT);
+    }
+
+    f32x4_t oacc[NDB];
+#pragma unroll
+    for (int t = 0; t < NDB; ++t) oacc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    float m_run = -INFINITY, l_run = 0.f;
+    const int q4 = r >> 2, p4 = r & 3;
+
+    // One tile's copy, as in mla_split_kernel<.., PAGED = true>: this lane's key has element offsets ko / vo in the two caches,
+    // -1 = not fetched, zeros in LDS.  offsets() returns the tile's visibility flags, bit k = list position kt + k.
+    constexpr bool PRE = LCH <= 8;
+    constexpr int LB = PRE ? LCH : 8;
+    static_assert(LCH % LB == 0, "tile copy");
+    u32x4 xl[LB], xr[RCH];
+    long long ko = -1, vo = -1;
+    const int wu = __builtin_amdgcn_readfirstlane(w);
+    auto offsets = [&](int kt) {
+        ko = vo = -1;
+        if constexpr (PAGED) {
+            if (s1 >= 0 && (unsigned)pg1 < (unsigned)p.nblk) {
+                ko = pg1 * p.kc_bs + (long long)s1 * p.kc_ts;
+                vo = pg1 * p.vc_bs + (long long)s1 * p.vc_ts;
+            }
+        } else if (s1 >= 0 && crow >= 0) {
+            ko = crow * p.kc_bs + (long long)s1 * p.kc_ts;
+            vo = crow * p.vc_bs + (long long)s1 * p.vc_ts;
+        }
+        const unsigned vm = (unsigned)__ballot(s1 >= 0);
+        advance(kt + 2 * KT);
+        return vm;
+    };
+    auto load_lat = [&](int i0) {
+#pragma unroll
+        for (int i = 0; i < LB; ++i) {
+            const int row = (T / 64) * (i0 + i) + wu;
+            const long long ro = ((long long)__builtin_amdgcn_readlane((int)(vo >> 32), row) << 32) |
+                                 (unsigned)__builtin_amdgcn_readlane((int)vo, row);   // (wave-uniform: a scalar base)
+            const bool ok = ro >= 0;
+            const u32x4 y = *reinterpret_cast<const u32x4*>(ok ? p.vc + ro + hk * DV + 8 * lane : p.q);
+            xl[i] = ok ? y : u32x4{0u, 0u, 0u, 0u};
+        }
+    };
+    auto store_lat = [&](int i0) {
+#pragma unroll
+        for (int i = 0; i < LB; ++i) *reinterpret_cast<u32x4*>(lat + MlaSwz::off((T / 64) * (i0 + i) + wu, lane)) = xl[i];
+    };
+    auto load_rot = [&]() {
+#pragma unroll
+        for (int i = 0; i < RCH; ++i) {
+            const int idx = T * i + tid, row = idx >> 3, ch = idx & 7;
+            const long long ro = __shfl(ko, row, 64);
+            const bool ok = ro >= 0;
+            const u32x4 y = *reinterpret_cast<const u32x4*>(ok ? p.kc + ro + hk * DK + 8 * ch : p.q);
+            xr[i] = ok ? y : u32x4{0u, 0u, 0u, 0u};
+        }
+    };
+    auto store_rot = [&]() {
+#pragma unroll
+        for (int i = 0; i < RCH; ++i) {
+            const int idx = T * i + tid;
+            *reinterpret_cast<u32x4*>(rop + TileSwz<64>::off(idx >> 3, idx & 7)) = xr[i];
+        }
+    };
+    unsigned vm_next = 0u;
+    if (PRE && jbeg < jend) {
+        vm_next = offsets(jbeg);
+        load_lat(0);
+        load_rot();
+    }
+
+    for (int k0 = jbeg; k0 < jend; k0 += KT) {
+        unsigned vm = vm_next;
+        if constexpr (!PRE) vm = offsets(k0);
+        __syncthreads();   // every wave has read the previous tile
+        if constexpr (PRE) {
+            store_lat(0);
+        } else {
+#pragma unroll 1
+            for (int i0 = 0; i0 < LCH; i0 += LB) {
+                load_lat(i0);
+                store_lat(i0);
+            }
+            load_rot();
+        }
+        store_rot();
+        __syncthreads();
+        if (PRE && k0 + KT < jend) {
+            vm_next = offsets(k0 + KT);
+            load_lat(0);
+            load_rot();
+        }
+        if (!active) continue;   // (wave-uniform; the wave still takes part in the copies and the barriers)
+
+        // S^T = K Q^T, as in mla_split_kernel
+        f32x4_t sacc[2];
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+            sacc[kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < DK / 32; ++ks)
+                sacc[kb] = mfma16<Tag>(*reinterpret_cast<const s16x8*>(rop + TileSwz<64>::off(16 * kb + r, 4 * ks + g)), qf[ks], sacc[kb]);
+#pragma unroll
+            for (int ks = 0; ks < DV / 32; ++ks) {
+                if (ks % 4 == 0) __builtin_amdgcn_sched_barrier(0);
+                sacc[kb] = mfma16<Tag>(*reinterpret_cast<const s16x8*>(lat + MlaSwz::off(16 * kb + r, 4 * ks + g)), qvf[ks], sacc[kb]);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" : "+v"(sacc[0]), "+v"(sacc[1]));
+        // the list's flags: register i of block kb holds list position k0 + 16 kb + 4 g + i
+        const unsigned vg = valid ? vm >> (4 * g) : 0u;
+        float mx = -INFINITY;
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float x = ((vg >> (16 * kb + i)) & 1u) ? sacc[kb][i] : -INFINITY;
+                sacc[kb][i] = x;
+                mx = fmaxf(mx, x);
+            }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float m_new = fmaxf(m_run, mx);
+        const float m_use = m_new == -INFINITY ? 0.f : m_new;
+        const float alpha = __builtin_amdgcn_exp2f((m_run - m_use) * p.c_log2);
+        const float mc = m_use * p.c_log2;
+        m_run = m_new;
+        l_run *= alpha;
+#pragma unroll
+        for (int t = 0; t < NDB; ++t) oacc[t] *= alpha;
+        u32x4 pk;
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const float e0 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][2 * j], p.c_log2, -mc));
+                const float e1 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][2 * j + 1], p.c_log2, -mc));
+                l_run += e0 + e1;
+                pk[2 * kb + j] = pack2<Tag>(e0, e1);
+            }
+        const s16x8 pb = *reinterpret_cast<s16x8*>(&pk);
+#pragma unroll
+        for (int t = 0; t < NDB; ++t) {
+            if (t % 4 == 0) __builtin_amdgcn_sched_barrier(0);
+            const int ch = 2 * t + (p4 >> 1), bo = 8 * (p4 & 1);
+            const s16x4 lo = lds_tr16(lat + MlaSwz::off(4 * g + q4, ch) + bo);
+            const s16x4 hi = lds_tr16(lat + MlaSwz::off(16 + 4 * g + q4, ch) + bo);
+            oacc[t] = mfma16<Tag>(cat8(lo, hi), pb, oacc[t]);
+        }
+    }
+
+    // ---- epilogue (mla_split_kernel's)
+    float l_tot = l_run + __shfl_xor(l_run, 16, 64);
+    l_tot += __shfl_xor(l_tot, 32, 64);
+    const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
+    const float lse_v = l_tot > 0.f ? m_run * p.scale + logf(l_tot) : -INFINITY;
+    if (!valid) return;
+    const size_t row_id = ((size_t)b * p.hq + h) * nq + qi;
+    if (S == 1) {
+        uint16_t* orow = p.o + ((size_t)blockIdx.x * p.hq + h) * DV;
+#pragma unroll
+        for (int t = 0; t < NDB; ++t) {
+            u32x2 v;
+            v[0] = pack2_rn<Tag>(oacc[t][0] * inv, oacc[t][1] * inv);
+            v[1] = pack2_rn<Tag>(oacc[t][2] * inv, oacc[t][3] * inv);
+            *reinterpret_cast<u32x2*>(orow + 16 * t + 4 * g) = v;
+        }
+        if (g == 0) p.lse[row_id] = lse_v;
+    } else {
+        float* prow = p.po + (row_id * S + s) * DV;
+#pragma unroll
+        for (int t = 0; t < NDB; ++t) *reinterpret_cast<f32x4_t*>(prow + 16 * t + 4 * g) = oacc[t] * inv;
+        if (g == 0) p.plse[row_id * S + s] = lse_v;
+    }
+}
+
+template <typename Tag, int NW>
+hipError_t launch_mla_sparse_split(const MlaSparseParams& sp, int S, long long units, hipStream_t st) {
+    const int wg_tiles = (sp.mp.p.G + 16 * NW - 1) / (16 * NW);
+    const dim3 grid((unsigned)units, (unsigned)S, (unsigned)(wg_tiles * sp.mp.p.hkv));
+    if (sp.mp.p.table) hipLaunchKernelGGL((mla_sparse_kernel<Tag, NW, true>), grid, dim3(64 * NW), 0, st, sp);
+    else hipLaunchKernelGGL((mla_sparse_kernel<Tag, NW, false>), grid, dim3(64 * NW), 0, st, sp);
+    return hipGetLastError();
+}
+
+template <typename Tag>
+hipError_t launch_mla_sparse_t(const MlaSparseParams& sp, int S, long long units, hipStream_t st) {
+    const int nw = mla_waves(sp.mp.p.G);
+    hipError_t e = nw == 1 ? launch_mla_sparse_split<Tag, 1>(sp, S, units, st)
+                 : nw == 2 ? launch_mla_sparse_split<Tag, 2>(sp, S, units, st) : launch_mla_sparse_split<Tag, 4>(sp, S, units, st);
+    if (e != hipSuccess || S == 1) return e;
+    const long long nrows = units * sp.mp.p.hq;
+    hipLaunchKernelGGL((mla_combine_kernel<Tag>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st, sp.mp.p, S, nrows);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 // Waves a workgroup: one per 16-row tile of the rows = G * Nq packed rows of a (sequence, K/V head), at most four (one per SIMD)
@@ -378,6 +657,37 @@ int mla_num_splits(int64_t batch, int64_t heads_kv, int64_t rows, int64_t cache_
     int64_t s = (kCUs * per_cu + units - 1) / units;
     s = std::min<int64_t>(s, (cache_len + kMinKeys - 1) / kMinKeys);
     return (int)std::max<int64_t>(1, std::min<int64_t>(s, 256));
+}
+
+// mla_num_splits for mla_sparse_kernel, with its constants.  A unit is a workgroup of mla_waves(group) waves over 16 * waves of the
+// group heads of one list (units = batch * seqlen_q lists a K/V head); the splits cut the topk list positions, none shorter than
+// 128 entries.
+int mla_sparse_num_splits(int64_t units, int64_t heads_kv, int64_t group, int64_t topk) {
+    constexpr int64_t kCUs = 256, kMinKeys = 128;
+    if (group <= 0) return 1;
+    const int64_t nw = mla_waves(group), per_cu = 4 / nw;
+    const int64_t wgs = units * heads_kv * ((group + 16 * nw - 1) / (16 * nw));
+    if (wgs <= 0 || topk <= 0) return 1;
+    int64_t s = (kCUs * per_cu + wgs - 1) / wgs;
+    s = std::min<int64_t>(s, (topk + kMinKeys - 1) / kMinKeys);
+    return (int)std::max<int64_t>(1, std::min<int64_t>(s, 256));
+}
+
+hipError_t launch_mla_sparse(const MlaSparseArgs& a, hipStream_t st) {
+    const KvArgs& kv = a.kv;
+    if (kv.d != kMlaDk || kv.d_v != kMlaDv) return hipErrorInvalidValue;   // (the C layer's check)
+    MlaSparseParams sp;
+    sp.mp.p = kv_make_params(kv);
+    sp.mp.qv = (const uint16_t*)kv.qv; sp.mp.qv_bs = kv.qv_bs; sp.mp.qv_ts = (int)kv.qv_ts;
+    sp.idx = a.indices; sp.ix_bs = a.ix_bs; sp.ix_ts = a.ix_ts; sp.ix_hs = a.ix_hs;
+    sp.topk = (int)a.topk; sp.causal = kv.causal;
+    const int S = (int)kv.num_splits;
+    // workspace (S > 1): kv_workspace_bytes at d_v, the O partials and then the lse partials
+    const size_t q_rows = (size_t)kv.batch * kv.heads_q * kv.seqlen_q;
+    sp.mp.p.po = (float*)kv.workspace;
+    sp.mp.p.plse = S > 1 ? (float*)((char*)kv.workspace + ((q_rows * S * kMlaDv * 4 + 255) & ~(size_t)255)) : nullptr;
+    const long long units = (long long)kv.batch * kv.seqlen_q;
+    return kv.dtype == 1 ? launch_mla_sparse_t<f16_tag>(sp, S, units, st) : launch_mla_sparse_t<bf16_tag>(sp, S, units, st);
 }
 
 hipError_t launch_kvcache_mla(const KvArgs& a, hipStream_t st) {

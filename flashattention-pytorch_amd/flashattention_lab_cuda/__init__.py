@@ -51,6 +51,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_ex_forward_varlen_paged", "fa_ex_forward_varlen_paged_fp8",
     "fa_rotary_apply",
     "fa_ex_backward_dlse", "fa_ex_backward_varlen_dlse", "fa_merge_states", "fa_merge_states_backward",
+    "fa_mla_sparse_forward", "fa_mla_sparse_workspace_bytes",
 )
 
 
@@ -162,6 +163,12 @@ _sig("fa_rotary_apply", _ROXY + _ROTARY + _ROPOS + _STREAM)
 _sig("fa_merge_states", _fields("p:o_a,lse_a,o_b,lse_b,o,lse") + _MDIMS + _strides("o_a", "lse_a", "o_b", "lse_b", "o", "lse") + _STREAM)
 _sig("fa_merge_states_backward", _fields("p:o_a,lse_a,o_b,lse_b,do_,dlse,do_a,do_b,dlse_a,dlse_b") + _MDIMS +
      _strides("o_a", "lse_a", "o_b", "lse_b", "do", "dlse", "do_a", "do_b", "dlse_a", "dlse_b") + _STREAM)
+_sig("fa_mla_sparse_forward", _fields(
+    "p:q,qv,k_cache,v_cache,indices,cache_seqlens,o,lse i:batch,heads_q,heads_kv,seqlen_q,cache_len,topk,d,d_v c:dtype "
+    "i:q_batch_stride,q_token_stride,qv_batch_stride,qv_token_stride,k_cache_batch_stride,k_cache_token_stride,v_cache_batch_stride,"
+    "v_cache_token_stride,indices_batch_stride,indices_token_stride,indices_head_stride c:causal d:softmax_scale i:num_splits "
+    "p:block_table i:block_table_row_stride,num_blocks,page_block_size,max_blocks_per_seq p:cache_batch_idx i:cache_batch") + _WS)
+_sig("fa_mla_sparse_workspace_bytes", _fields("i:batch,heads_q,heads_kv,seqlen_q,topk,num_splits"), _SIZE)
 _KVWSV = _fields("i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,d,num_splits c:with_sinks")
 _sig("fa_ex_kvcache_workspace_bytes_varlen", _KVWSV, _SIZE)
 _sig("fa_ex_kvcache_workspace_bytes_qv", _KVWSV + _fields("i:d_v"), _SIZE)
@@ -203,6 +210,7 @@ _family("fa_ex_forward_varlen_paged_fp8", ["fa_ex_forward_varlen_paged"])
 _family("fa_rotary_apply", [])
 _family("fa_merge_states", [])
 _family("fa_merge_states_backward", [])
+_family("fa_mla_sparse_forward", [])
 _family("fa_ex_forward_kvcache_qv", ["fa_ex_forward_kvcache" + _suffix for _suffix in ("", "_paged", "_rotary", "_fp8", "_sink", "_varlen")])
 
 
@@ -1141,6 +1149,113 @@ def ex_kvcache_forward(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlen
             b, hq, hkv, 0 if packed else nq, 0 if cu_seqlens_k_new is not None else nnew, cap_len, d, code,
             0 if packed else qb, qt, kvb, kvt, vvb, vvt, knb, knt, vnb, vnt,
             int(bool(causal)), wl, wr, scale, cap, aptr, astride, int(num_splits), *added,
+            ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device)))
+    return o, lse
+
+
+def _index_strides(indices, b, nq, hkv, topk):
+    """(indices, batch stride, token stride, head stride) of the lists of a sparse call as the library addresses them: the topk
+    entries of a list adjacent, head stride 0 for a (B, Nq, topk) tensor or a view expanded over the K/V heads, lists that do not
+    overlap.  Any other view is copied (the lists are only read)."""
+    def strides(t):
+        ixh = t.stride(2) if t.dim() == 4 and hkv > 1 else 0
+        span = (hkv - 1) * ixh + topk if ixh else topk                 # entries of one token's lists
+        ixt = t.stride(1) if nq > 1 else span
+        ixb = t.stride(0) if b > 1 else (nq - 1) * ixt + span
+        ok = (ixh == 0 or ixh >= topk) and ixt >= span and ixb >= (nq - 1) * ixt + span
+        return ok, ixb, ixt, ixh
+    if indices.numel() == 0:
+        return indices, 0, 0, 0
+    ok, ixb, ixt, ixh = strides(indices)
+    if not ok or indices.stride(-1) != 1 or indices.data_ptr() % 4:
+        indices = indices.contiguous()
+        ok, ixb, ixt, ixh = strides(indices)
+    return indices, ixb, ixt, ixh
+
+
+def ex_mla_sparse_forward(q, qv, k_cache, v_cache, indices, cache_seqlens=None, causal=False, softmax_scale=None, block_table=None,
+                          cache_batch_idx=None, num_splits=0):
+    """(o, lse) of sparse MLA decoding: ex_kvcache_forward(q, k_cache, v_cache, qv=qv, ...) over a list of cached tokens per query
+    token.  q (B, Nq, H_q, 64), qv (B, Nq, H_q, 512), k_cache (.., H_kv, 64), v_cache (.., H_kv, 512) as that call takes them
+    (contiguous, cache_batch_idx rows, or pools under block_table; cache views are never copied); indices int32 (B, Nq, topk) or
+    (B, Nq, H_kv, topk) on q's device: entry j is a token position of sequence b, a key iff 0 <= entry < cache_seqlens[b] (and
+    <= cache_seqlens[b] - Nq + i if causal); anything else is skipped and never read.  Never read on the host.  o (B, Nq, H_q, 512)
+    in q's dtype, lse (B, H_q, Nq) float32; softmax_scale defaults to (64 + 512) ** -0.5.  See fa_mla_sparse_forward."""
+    who = "ex_mla_sparse_forward"
+    for name, t in (("q", q), ("qv", qv), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{who}: {name} must be a GPU (HIP device) tensor; there is no CPU path")
+        if t.device != q.device:
+            raise RuntimeError(f"{who}: {name} must be on q's device ({q.device}), got {t.device}")
+        if t.dim() != 4:
+            raise RuntimeError(f"{who}: {name} must be 4-D (B, N, H, d), got {tuple(t.shape)}")
+    if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int32:
+        dt = indices.dtype if isinstance(indices, torch.Tensor) else type(indices).__name__
+        raise NotImplementedError(f"{who}: indices of dtype {dt} is not supported (int32 tensor expected)")
+    if q.dtype not in (torch.float16, torch.bfloat16) or any(t.dtype != q.dtype for t in (qv, k_cache, v_cache)):
+        raise RuntimeError(f"{who}: q, qv, k_cache and v_cache must share a 16-bit dtype (float16 or bfloat16), got {q.dtype}, "
+                           f"{qv.dtype}, {k_cache.dtype}, {v_cache.dtype}")
+    b, nq, hq, d = q.shape
+    cap_len, hkv, dv = k_cache.shape[1], k_cache.shape[2], v_cache.shape[3]
+    if (d, dv) != (64, 512):
+        raise NotImplementedError(f"{who}: supported for q, k_cache of head dim 64 with v_cache of head dim 512 only (got {d}, {dv})")
+    if qv.shape != (b, nq, hq, dv):
+        raise RuntimeError(f"{who}: qv must be a (B, Nq, H_q, {dv}) = ({b}, {nq}, {hq}, {dv}) tensor, got {tuple(qv.shape)}")
+    if hkv == 0 or hq % hkv != 0:
+        raise RuntimeError(f"{who}: the query heads ({hq}) must be a multiple of the K/V heads ({hkv})")
+    for name, t, shape in (("block_table", block_table, "(B, max_blocks_per_seq)"), ("cache_batch_idx", cache_batch_idx, "(B,)")):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != q.device or \
+                t.dim() != (2 if name == "block_table" else 1) or t.shape[0] != b or t.numel() == 0:
+            raise RuntimeError(f"{who}: {name} must be an int32 {shape} tensor on q's device, B = {b}")
+    if block_table is not None and cache_batch_idx is not None:
+        raise RuntimeError(f"{who}: block_table cannot be combined with cache_batch_idx")
+    units = b if block_table is None and cache_batch_idx is None else k_cache.shape[0]
+    if block_table is not None and (cap_len < 16 or cap_len % 16 != 0):
+        raise RuntimeError(f"{who}: page_block_size (k_cache.shape[1]) must be a positive multiple of 16, got {cap_len}")
+    if units == 0 or cap_len == 0 or k_cache.shape != (units, cap_len, hkv, d) or v_cache.shape != (units, cap_len, hkv, dv):
+        what = "(num_blocks, page_block_size, H_kv, .)" if block_table is not None else \
+            "(B_cache, cache_len, H_kv, .)" if cache_batch_idx is not None else "(B, cache_len, H_kv, .)"
+        raise RuntimeError(f"{who}: k_cache and v_cache must be {what} = ({units}, ., ., {d} | {dv}); got "
+                           f"{tuple(k_cache.shape)}, {tuple(v_cache.shape)}")
+    if indices.device != q.device or indices.dim() not in (3, 4) or indices.shape[:2] != (b, nq) or \
+            (indices.dim() == 4 and indices.shape[2] != hkv):
+        raise RuntimeError(f"{who}: indices must be an int32 (B, Nq, topk) or (B, Nq, H_kv, topk) = ({b}, {nq}, [{hkv},] topk) tensor on "
+                           f"q's device, got {tuple(indices.shape)} on {indices.device}")
+    topk = indices.shape[-1]
+    indices, ixb, ixt, ixh = _index_strides(indices, b, nq, hkv, topk)
+    kvb, kvt = _kv_strides(who, "k_cache", k_cache, hkv, d, True)
+    vvb, vvt = _kv_strides(who, "v_cache", v_cache, hkv, dv, True)
+    q = q.contiguous()
+    qb, qt = _kv_strides(who, "q", q, hq, d, False)
+    if qv.stride(3) != 1 or (hq > 1 and qv.stride(2) != dv) or qv.stride(1) % 8 or qv.stride(0) % 8 or qv.data_ptr() % 16 or \
+            (nq > 1 and qv.stride(1) < hq * dv) or (b > 1 and qv.stride(0) < (nq - 1) * qv.stride(1) + hq * dv):
+        qv = qv.contiguous()   # a view whose heads are adjacent (a token-strided one, say) is taken as it is
+    qvb, qvt = _kv_strides(who, "qv", qv, hq, dv, False)
+    scale = (d + dv) ** -0.5 if softmax_scale is None else float(softmax_scale)
+    with torch.cuda.device(q.device):
+        if cache_seqlens is not None and not isinstance(cache_seqlens, torch.Tensor):
+            cache_seqlens = torch.full((b,), operator.index(cache_seqlens), dtype=torch.int32, device=q.device)
+        if cache_seqlens is not None:
+            if cache_seqlens.device != q.device or cache_seqlens.dtype != torch.int32 or cache_seqlens.shape != (b,):
+                raise RuntimeError(f"{who}: cache_seqlens must be an int32 ({b},) tensor on q's device, or an int")
+            cache_seqlens = cache_seqlens.contiguous()
+        cache_batch_idx = _contiguous(cache_batch_idx)
+        paged = (0, 0, 0, 0, 0)   # block_table, its row stride, num_blocks, page_block_size, max_blocks_per_seq
+        if block_table is not None:
+            if block_table.stride(1) != 1:
+                block_table = block_table.contiguous()
+            paged = (block_table.data_ptr(), block_table.stride(0) if b > 1 else max(block_table.stride(0), block_table.shape[1]),
+                     units, cap_len, block_table.shape[1])
+        o = torch.empty((b, nq, hq, dv), dtype=q.dtype, device=q.device)
+        lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)
+        nbytes = int(_lib.fa_mla_sparse_workspace_bytes(b, hq, hkv, nq, topk, int(num_splits))) if b and nq and hq else 0
+        ws = _workspace(q.device, nbytes) if nbytes > 0 else None
+        _call("fa_mla_sparse_forward", (
+            q.data_ptr(), qv.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), indices.data_ptr(), _ptr(cache_seqlens), o.data_ptr(),
+            lse.data_ptr(), b, hq, hkv, nq, cap_len, topk, d, dv, _DTYPE_CODE[q.dtype], qb, qt, qvb, qvt, kvb, kvt, vvb, vvt, ixb, ixt, ixh,
+            int(bool(causal)), scale, int(num_splits), *paged, _ptr(cache_batch_idx), 0 if cache_batch_idx is None else units,
             ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device)))
     return o, lse
 

@@ -710,6 +710,59 @@ int fa_ex_forward_kvcache_qv(const void* q, void* k_cache, void* v_cache, const 
 size_t fa_ex_kvcache_workspace_bytes_qv(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t max_seqlen_q,
                                         int64_t cache_len, int64_t d, int64_t num_splits, int with_sinks, int64_t d_v);
 
+/* --- Sparse MLA decoding: fa_ex_forward_kvcache_qv over a per-query list of cached tokens (DeepSeek sparse attention: an indexer
+ * picks, for every query token, the topk cached tokens it may attend to).  A call family of its own; the caches, cache_seqlens,
+ * block_table and cache_batch_idx are those of the dense qv call and mean the same.  q (batch, seqlen_q, heads_q, 64) and qv
+ * (batch, seqlen_q, heads_q, 512) at their batch / token strides, heads adjacent; k_cache (.., heads_kv, 64) and v_cache
+ * (.., heads_kv, 512) contiguous caches (batch or cache_batch rows of cache_len tokens) or pools (num_blocks pages of
+ * page_block_size tokens; cache_len is then not used, the capacity is max_blocks_per_seq * page_block_size), each with its own
+ * batch / page and token strides; o (batch, seqlen_q, heads_q, 512) dense, lse (batch, heads_q, seqlen_q) float32.
+ * indices: int32 device memory, entry j < topk of (sequence b, query token i, K/V head hk) at
+ *     indices[b * indices_batch_stride + i * indices_token_stride + hk * indices_head_stride + j]
+ * (indices_head_stride = 0: one list for all K/V heads of a token).  For query head h reading K/V head hk = h / G, list I and
+ * len_b = clamp(cache_seqlens[b], 0, capacity) (null: the capacity):
+ *     visible(j)  <=>  0 <= I[j] < len_b  and, if causal,  I[j] <= len_b - seqlen_q + i
+ *     s[j] = softmax_scale * (q[b, i, h, :] . k[I[j], hk, :] + qv[b, i, h, :] . v[I[j], hk, :])   over the visible j
+ *     o[b, i, h, :] = sum_j softmax_j(s)[j] * v[I[j], hk, :],     lse[b, h, i] = logsumexp_j s[j]
+ * An index is a logical token position of sequence b, resolved as the dense call resolves a position: token I of cache row
+ * (cache_batch_idx ? cache_batch_idx[b] : b), or slot I % page_block_size of page block_table[b, I / page_block_size].  Every list
+ * position is a key: a token named twice counts twice; the order of a list changes the result by rounding only.  An entry that is
+ * not visible (-1 padding, anything negative or >= len_b, above the causal bound) is no key and never becomes an address: the
+ * indices are untrusted and are not read on the host.  A visible entry whose page lies outside [0, num_blocks), or whose cache
+ * row lies outside [0, cache_batch), is a zero key with a zero value and score 0 that takes part in the softmax (the dense call's
+ * rule).  A row without a visible entry (topk = 0 included) gives o = 0, lse = -inf.  No window, softcap, ALiBi, sinks, rotary, new
+ * tokens, e4m3 cache, packed queries or left padding.
+ * Split-KV over the list positions: num_splits in [1, 256], or 0 for the launch rule; the partials are combined in a fixed order
+ * (the same bits on every run).  workspace: fa_mla_sparse_workspace_bytes (0 for one split; 0 too for arguments the call would
+ * reject): S * batch * seqlen_q * heads_q * (512 + 1) floats, each part rounded up to 256 bytes.  Nothing allocates, synchronises
+ * or reads device memory on the host: the call can be captured and replayed with changed indices, lengths and tables.
+ * Checked before any HIP call, the first broken rule named in fa_last_error(), in this order: batch, seqlen_q, heads_q >= 0, and a
+ * call with one of them 0 returns FA_OK without a launch and without looking at anything else; (1) q, qv, k_cache, v_cache, o, lse
+ * (and indices unless topk = 0) non-null; (2) d = 64 and d_v = 512, else FA_ERR_UNSUPPORTED with both numbers in the text; (3) dtype
+ * f16 or bf16, then heads_q a multiple of heads_kv >= 1, softmax_scale finite and > 0, num_splits in [0, 256], cache_len >= 1
+ * without block_table, cache_batch in [1, 2^31) with cache_batch_idx (which does not go with block_table) and 0 without, and
+ * (FA_ERR_UNSUPPORTED) heads_q <= 65535, cache_len <= 2^28, seqlen_q <= 2^24, batch * seqlen_q * heads_q < 2^31; (4) for q, qv,
+ * k_cache, v_cache token strides >= heads * width, with more than one batch element (page, cache row) batch strides >= (tokens - 1)
+ * * token stride + heads * width, strides multiples of 8, one batch element below 2^31 bytes (FA_ERR_UNSUPPORTED), q, qv, k_cache,
+ * v_cache, o 16-byte and lse, indices, cache_seqlens, block_table, cache_batch_idx 4-byte aligned; (5) topk in [0, 2^30],
+ * indices_head_stride 0 or >= topk, with seqlen_q > 1 indices_token_stride >= a token's lists, with batch > 1
+ * indices_batch_stride >= a sequence's lists, none negative; (6) with block_table page_block_size a positive multiple of 16,
+ * num_blocks in [1, 2^31), max_blocks_per_seq >= 1 with a capacity <= 2^28 tokens (FA_ERR_UNSUPPORTED),
+ * block_table_row_stride >= max_blocks_per_seq, and without it all four 0; (7) with S > 1 fewer than 2^26 rows
+ * (FA_ERR_UNSUPPORTED), workspace_bytes >= the need, workspace non-null and 16-byte aligned. */
+int fa_mla_sparse_forward(const void* q, const void* qv, const void* k_cache, const void* v_cache, const int32_t* indices,
+                          const int32_t* cache_seqlens, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                          int64_t seqlen_q, int64_t cache_len, int64_t topk, int64_t d, int64_t d_v, int dtype,
+                          int64_t q_batch_stride, int64_t q_token_stride, int64_t qv_batch_stride, int64_t qv_token_stride,
+                          int64_t k_cache_batch_stride, int64_t k_cache_token_stride, int64_t v_cache_batch_stride,
+                          int64_t v_cache_token_stride, int64_t indices_batch_stride, int64_t indices_token_stride,
+                          int64_t indices_head_stride, int causal, double softmax_scale, int64_t num_splits,
+                          const int32_t* block_table, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
+                          int64_t max_blocks_per_seq, const int32_t* cache_batch_idx, int64_t cache_batch, void* workspace,
+                          size_t workspace_bytes, void* stream);
+size_t fa_mla_sparse_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t topk,
+                                     int64_t num_splits);
+
 /* --- Rotary position embedding for training and prefill (FlashAttention's flash_attn.layers.rotary: apply_rotary_emb,
  * apply_rotary_emb_qkv_), forward and backward.  One memory-bound launch on `stream` rotates the first rotary_dim head dims of
  * every head of one 16-bit tensor: x -> y, both (batch, seqlen, heads, d) with the heads adjacent at stride d, the last dim

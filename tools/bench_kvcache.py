@@ -45,6 +45,14 @@ and V are then 1 an element.  ex_forward and the unfused rotation keep the 16-bi
   rounds with their spread, the split count the launch rule takes, and the cache bytes read per second with the cache counted
   once per sequence, B * len * 576 * 2.  In the same run, the plain split kernel at d = 256, H_q / H_kv = 8 on a cache of the same
   B and len (its bytes: B * len * H_kv * 256 * 2 * 2), from the unchanged code path.
+--mla-sparse: the sparse call (ex_mla_sparse_forward: topk = 2048 listed tokens per query token) at (B, H_q, Nq) = (32, 128, 1),
+  (32, 16, 1), (1, 128, 512) (a prefill chunk), H_kv = 1, bf16, over caches of len 8192 and 65536 (the two slices of one
+  (.., 576) pool), contiguous and paged (page 64, shuffled; checked bitwise against the contiguous call first), with uniformly
+  random lists and with the same lists sorted.  The yardstick, in the same run: the dense qv call on a cache of len = topk (the
+  same number of keys and the same matrix work, every row read in order), and that call through a page table (page 64, pages
+  in order), whose copy path the sparse kernel shares.  Per figure the median over --rounds rounds with their
+  spread, the ratio to the dense call, and the listed bytes gathered per second, B * Nq * topk * 576 * 2 (a list counted once: at
+  H_q = 128 two workgroups gather it).
 Timing: HIP events around `--iters` back-to-back calls after `--warmup` calls; the median of `--reps` such groups."""
 import argparse
 import json
@@ -354,6 +362,64 @@ def mla_rows(args):
     return rows
 
 
+def mla_sparse_rows(args):
+    dev, dtype, d, dv, ps, topk, hkv = "cuda", torch.bfloat16, 64, 512, 64, 2048, 1
+    rows = []
+    t = lambda fn: [timed(fn, args.warmup, args.iters, args.reps) for _ in range(args.rounds)]   # noqa: E731
+    med = statistics.median
+
+    def figures(ts, nbytes, base=None):
+        f = dict(us=round(med(ts), 2), rounds=[round(x, 2) for x in ts], spread=round((max(ts) - min(ts)) / med(ts), 4),
+                 TBps=round(nbytes / med(ts) / 1e6, 3))
+        if base is not None:
+            f["vs_dense"] = round(med(ts) / base, 3)
+        return f
+
+    def splits_of(query, *a):
+        return next((s_ for s_ in range(2, 257) if query(*a[:-1], s_, *a[-1]) == query(*a[:-1], 0, *a[-1])), 1)
+
+    for b, hq, nq in ((32, 128, 1), (32, 16, 1), (1, 128, 512)):
+        q = torch.randn((b, nq, hq, d), device=dev, dtype=dtype)
+        qv = torch.randn((b, nq, hq, dv), device=dev, dtype=dtype)
+        # the yardstick: the dense call over topk keys (no causal cut: every row sees them all)
+        dpool = torch.randn((b, topk, hkv, d + dv), device=dev, dtype=dtype)
+        dense = lambda: ext.ex_kvcache_forward(q, dpool[..., dv:], dpool[..., :dv], None, None, topk, False, None, qv=qv)   # noqa: E731
+        gathered = b * nq * hkv * topk * (d + dv) * 2
+        td = t(dense)
+        base = med(td)
+        # the same keys through the dense call's paged copy (page 64, in order): the copy path the sparse kernel derives from
+        dtable = torch.arange(b * topk // ps, dtype=torch.int32, device=dev).view(b, topk // ps)
+        dpp = dpool.view(b * topk // ps, ps, hkv, d + dv)
+        dense_paged = lambda: ext.ex_kvcache_forward(q, dpp[..., dv:], dpp[..., :dv], None, None, topk, False, None, block_table=dtable, qv=qv)   # noqa: E731
+        tdp = t(dense_paged)
+        dsplits = splits_of(ext._lib.fa_ex_kvcache_workspace_bytes_qv, b, hq, hkv, b * nq, nq, topk, d, (0, dv))
+        for L in (8192, 65536):
+            pool = torch.randn((b, L, hkv, d + dv), device=dev, dtype=dtype)
+            kc, vc = pool[..., dv:], pool[..., :dv]
+            mb = L // ps
+            table = torch.randperm(b * mb, generator=torch.Generator().manual_seed(b)).view(b, mb).to(torch.int32).to(dev)
+            ppool = torch.empty((b * mb, ps, hkv, d + dv), device=dev, dtype=dtype)
+            for bb in range(b):
+                ppool[table[bb].long()] = pool[bb].view(mb, ps, hkv, d + dv)
+            kp, vp = ppool[..., dv:], ppool[..., :dv]
+            rnd = torch.randint(0, L, (b, nq, topk), device=dev, dtype=torch.int32)
+            r = dict(kind="mla_sparse", B=b, Hq=hq, Hkv=hkv, nq=nq, len=L, topk=topk, cache_bytes=b * L * (d + dv) * 2, listed_bytes=gathered,
+                     splits=splits_of(ext._lib.fa_mla_sparse_workspace_bytes, b, hq, hkv, nq, topk, ()),
+                     dense_len_topk=dict(figures(td, b * topk * (d + dv) * 2), splits=dsplits),
+                     dense_paged_64_len_topk=figures(tdp, b * topk * (d + dv) * 2, base))
+            for order, ix in (("random", rnd), ("sorted", rnd.sort(dim=-1).values.contiguous())):
+                cont = lambda: ext.ex_mla_sparse_forward(q, qv, kc, vc, ix, L)                           # noqa: E731
+                paged = lambda: ext.ex_mla_sparse_forward(q, qv, kp, vp, ix, L, block_table=table)       # noqa: E731
+                oc, op = cont(), paged()
+                assert torch.equal(oc[0], op[0]) and torch.equal(oc[1], op[1]), "paged and contiguous calls disagree"
+                r[order] = dict(contiguous=figures(t(cont), gathered, base), paged_64=figures(t(paged), gathered, base))
+            rows.append(r)
+            print(json.dumps(r), flush=True)
+            del pool, ppool, kc, vc, kp, vp
+            torch.cuda.empty_cache()
+    return rows
+
+
 def parent_check(args, dtype):
     dev, b, h, n, d = "cuda", 2, 32, 4096, 128
     q, k, v = (torch.randn((b * n, h, d), device=dev, dtype=dtype) for _ in range(3))
@@ -390,6 +456,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3, help="--prefill / --parent-check: interleaved rounds per figure")
     ap.add_argument("--parent-check", action="store_true", help="time only the packed varlen forward at B H = 64, 4096 tokens, d = 128")
     ap.add_argument("--mla", action="store_true", help="time the call with qv (64 + 512 head dims): see the module docstring")
+    ap.add_argument("--mla-sparse", action="store_true", help="time the sparse MLA call against the dense qv call at equal keys: see the module docstring")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     args.chunks = [int(x) for x in args.chunks.split(",")]
@@ -404,11 +471,11 @@ def main():
         ext.ex_kvcache_forward(wq, wk, wk, None, None, wl, True, None)
     torch.cuda.synchronize()
     del wq, wk
-    if args.mla:
-        rows = mla_rows(args)
+    if args.mla or args.mla_sparse:
+        rows = mla_sparse_rows(args) if args.mla_sparse else mla_rows(args)
         if args.json:
             with open(args.json, "w") as f:
-                json.dump(dict(mla=True, version=ext.version(), rows=rows), f, indent=1)
+                json.dump(dict(mla=True, sparse=bool(args.mla_sparse), version=ext.version(), rows=rows), f, indent=1)
         return
     if args.prefill or args.parent_check:
         rows = parent_check(args, dtype) if args.parent_check else prefill_rows(args, dtype)
