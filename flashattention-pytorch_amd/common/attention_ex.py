@@ -7,7 +7,8 @@ extended entry points (`fa_ex_forward` / `fa_ex_backward`, include/fa_mi355x.h):
                        causal=False, dropout_p=0.0, seed=0, softmax_scale=None, window_size=(-1, -1),
                        softcap=0.0, alibi_slopes=None, *, return_lse=False, sinks=None) -> o  |  (o, lse)
 
-q: (B, H, Nq, d) or (BH, Nq, d); k, v: (B, H_kv, Nk, d) or (B*H_kv, Nk, d).  H_kv < H is grouped-query attention (GQA; H_kv = 1:
+q: (B, H, Nq, d) or (BH, Nq, d); k, v: (B, H_kv, Nk, d) or (B*H_kv, Nk, d); v may be narrower, (B, H_kv, Nk, d_v) or (B*H_kv, Nk, d_v)
+(see "A v of its own width" below).  H_kv < H is grouped-query attention (GQA; H_kv = 1:
 multi-query attention) with H % H_kv == 0: query head h reads K/V head h // (H / H_kv), with no copy of K and V, and the
 gradients of k and v come back in k's and v's shape, summed over each group by the library.  `mask` follows the model's convention — a boolean / 0-1 tensor
 broadcastable to (B, H, Nq, Nk), True / 1 = allowed (`look_ahead_mask_` builds the causal one for Nq != Nk, :176-190;
@@ -40,6 +41,19 @@ full call's diagonal ends.  The last chunk (j1 = Nk) is plain `causal=True`.  Ro
 and lse = -inf, which the merge treats as weight 0.  With `sinks`, pass them to exactly one chunk (the sink is one more column of
 the union).  `mask` and `block_sparse_mask` are sliced with the keys.  ALiBi across chunks is not expressible (the bias of a chunk
 would need the chunk's offset, which the call does not take) and is out of scope; dropout draws a different mask per chunk.
+
+A v of its own width (fa_ex_forward_vdim / fa_ex_backward_vdim; flash_attention_varlen takes v (total_k, H_kv, d_v) alike).  Before
+weight absorption, in training and prefill, DeepSeek-style multi-head latent attention is ordinary attention whose q and k are 192
+wide (128 nope + 64 rope) and whose v and o are 128 wide.  v (..., d_v) with 8 <= d_v < d <= 192, d_v <= 128, both multiples of 8,
+float16 / bfloat16: o (and dO) are d_v wide, dv comes back in v's shape, and the default scale stays d ** -0.5 with q's width d
+(FlashAttention's rule: 192 ** -0.5 for MLA).  It goes with causal (bottom-right aligned for Nq != Nk), softmax_scale / tau, GQA,
+return_lse with a differentiable lse, and packed sequences; mask, block_sparse_mask, dropout_p > 0, window_size, softcap,
+alibi_slopes, sinks (and block_table, k_descale / v_descale of flash_attention_varlen) raise NotImplementedError naming the
+argument, as do d_v > d, wider tensors and float32.  d_v == d is the call it always was.  Strides: flash_attention_ex copies a
+non-contiguous k or v (.contiguous()), so a v sliced out of a (.., 128 + 128) kv projection costs one copy of v; the packed call
+takes token-strided views without a copy but wants the heads of v adjacent at stride d_v, as it wants k's at d, and raises
+RuntimeError otherwise.  Chunked MLA prefill composes with merge_attention_states exactly as above: o, lse pairs of key chunks
+merge at any width.
 """
 from __future__ import annotations
 
@@ -188,20 +202,26 @@ def flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, bloc
                        seed=0, softmax_scale=None, window_size=(-1, -1), softcap=0.0, alibi_slopes=None, *, return_lse=False,
                        sinks=None):
     window = _window_size(window_size)
+    if all(isinstance(t, torch.Tensor) for t in (q, k, v)) and k.dim() == v.dim() and v.shape[:-1] == k.shape[:-1] and v.shape[-1] != k.shape[-1]:
+        # a v of its own width: what the two-width kernels do not take is refused by name, before anything runs
+        _vdim_refuse("flash_attention_ex", k.shape[-1], v.shape[-1], q.dtype, mask=mask is not None,
+                     block_sparse_mask=block_sparse_mask is not None, dropout_p=float(dropout_p) > 0.0, window_size=window != (-1, -1),
+                     softcap=softcap != 0.0, alibi_slopes=alibi_slopes is not None, sinks=sinks is not None)
     if not q.is_cuda:
         raise RuntimeError("Inputs must be CUDA tensors")   # as the reference's wrappers (src/fa2/cuda/impl.py:44)
     four_d = q.dim() == 4
     if four_d:
         b, h, nq, d = q.shape
-        if k.dim() != 4 or k.shape[0] != b or v.shape != k.shape:
-            raise RuntimeError(f"k and v must be (B, H_kv, Nk, d) with q's B; got {tuple(k.shape)}, {tuple(v.shape)}")
+        if k.dim() != 4 or k.shape[0] != b or v.dim() != 4 or v.shape[:3] != k.shape[:3]:
+            raise RuntimeError(f"k must be (B, H_kv, Nk, d) with q's B and v (B, H_kv, Nk, d_v); got {tuple(k.shape)}, {tuple(v.shape)}")
         hkv, nk = k.shape[1], k.shape[2]
         if hkv == 0 or h % hkv != 0:
             raise RuntimeError(f"the query heads ({h}) must be a multiple of the K/V heads ({hkv})")
-        q3, k3, v3 = q.reshape(b * h, nq, d), k.reshape(b * hkv, nk, d), v.reshape(b * hkv, nk, d)
+        q3, k3, v3 = q.reshape(b * h, nq, d), k.reshape(b * hkv, nk, d), v.reshape(b * hkv, nk, v.shape[3])
     else:
         q3, k3, v3 = q, k, v
         (_, nq, d), nk = q.shape, k.shape[1]
+    d_v = v.shape[-1]
     scale = (tau / math.sqrt(d)) if softmax_scale is None else float(softmax_scale) * tau   # :134
     m = None
     if mask is not None:
@@ -218,7 +238,7 @@ def flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, bloc
                 raise RuntimeError("flash_attention_ex: sinks must be a float32 tensor (pass a 16-bit parameter as p.float())")
         o, lse = _FlashAttnExLseFn.apply(q3, k3, v3, bool(causal), scale, m, block_sparse_mask, br, bc, float(dropout_p), int(seed),
                                          window, softcap, slopes, sinks)
-        return (o.reshape(q.shape), lse.reshape(b, h, nq)) if four_d else (o, lse)
+        return (o.reshape(b, h, nq, d_v), lse.reshape(b, h, nq)) if four_d else (o, lse)
     if sinks is not None:
         if four_d:
             sinks = _sinks_units("flash_attention_ex", sinks, h)
@@ -231,7 +251,14 @@ def flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, bloc
     else:
         o = _FlashAttnExFn.apply(q3, k3, v3, bool(causal), scale, m, block_sparse_mask, br, bc, float(dropout_p), int(seed), window,
                                  softcap, slopes)
-    return o.reshape(q.shape) if four_d else o
+    return o.reshape(b, h, nq, d_v) if four_d else o
+
+
+def _vdim_refuse(who, d, d_v, dtype, **carried):
+    """the rules of a v of its own width (flashattention_lab_cuda.vdim_arg), under this module's argument names"""
+    import flashattention_lab_cuda as ext
+
+    ext.vdim_arg(who, d, d_v, dtype, **carried)
 
 
 class _FlashAttnVarlenFn(torch.autograd.Function):
@@ -307,7 +334,8 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
                            causal=False, window_size=(-1, -1), seed=0, softcap=0.0, alibi_slopes=None, *,
                            return_softmax_lse=False, block_table=None, k_descale=None, v_descale=None, sinks=None):
     """FlashAttention-2's flash_attn_varlen_func over packed sequences, differentiable: q (total_q, H_q, d), k and v
-    (total_k, H_kv, d) with H_q % H_kv == 0 (GQA), token-strided views (qkv.unbind(1) of a (total, 3, H, d) projection) taken
+    (total_k, H_kv, d) — v may be narrower, (total_k, H_kv, d_v): "A v of its own width" in this module's docstring; o is then
+    (total_q, H_q, d_v) — with H_q % H_kv == 0 (GQA), token-strided views (qkv.unbind(1) of a (total, 3, H, d) projection) taken
     without a copy; cu_seqlens_* int32 (batch + 1,) device offsets.  Attention stays inside each sequence; `causal` is
     bottom-right aligned per sequence and `window_size` has flash_attention_ex's meaning in each sequence's coordinates.
     Returns o (total_q, H_q, d); the gradients of k and v come back in their shapes.  The dropout mask is that of the padded
@@ -348,6 +376,11 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
     window_size=(left', Nk - j1), the last chunk plain causal=True — which one call can express only where Nk - j1 is the same
     for every sequence; sinks go to exactly one chunk; ALiBi across chunks is not expressible and out of scope."""
     window = _window_size(window_size)
+    if all(isinstance(t, torch.Tensor) for t in (q, k, v)) and k.dim() == v.dim() and v.shape[:-1] == k.shape[:-1] and v.shape[-1] != k.shape[-1]:
+        _vdim_refuse("flash_attention_varlen", k.shape[-1], v.shape[-1], q.dtype, dropout_p=float(dropout_p) > 0.0,
+                     window_size=window != (-1, -1), softcap=softcap != 0.0, alibi_slopes=alibi_slopes is not None,
+                     sinks=sinks is not None, block_table=block_table is not None, k_descale=k_descale is not None,
+                     v_descale=v_descale is not None)
     if block_table is not None:
         return _flash_attention_varlen_paged(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale,
                                              causal, window, softcap, alibi_slopes, sinks, block_table, k_descale, v_descale,

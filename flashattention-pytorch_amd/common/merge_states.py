@@ -27,6 +27,11 @@ Nk keys is `causal=False, window_size=(left', Nk - j1)` on the chunk (left' = th
 the last chunk is plain `causal=True`; with sinks, pass `sinks` to exactly one chunk.  ALiBi across chunks is not expressible and is
 out of scope.  See flash_attention_ex's docstring.
 
+The merge works at o's width, whatever it is, so chunked MLA prefill composes with it: (o, lse) pairs of flash_attention_ex /
+flash_attention_varlen calls whose v is narrower than q and k (192 + 128) merge as any others, gradients included.  Those calls take
+no window_size; the chunking they can express is the usual one of prefill behind a prefix — the keys every row sees whole as one
+`causal=False` chunk, the trailing Nq keys as the `causal=True` chunk.
+
 Errors: mismatched shapes, dtypes or devices RuntimeError; an unknown layout, or a view the kernel cannot address (a last dim that
 is not contiguous, 16-bit tensors that are not 16-byte aligned with strides that are multiples of 8 elements) ValueError — nothing is
 copied silently.  No CPU path.

@@ -440,18 +440,52 @@ static int no_key_fill(const char* who, void* o, float* lse, int64_t units, int6
 // A backward without a query row or without a key.  With sinks their gradient is 0 (no row, or rows with o = 0: delta = 0); nothing
 // else where both sides are empty; else the gradients of the side that has rows are sums over nothing: dk and dv where there is no
 // query row, dq where there is no key.
+// (dv_bytes: dv's own size where v is narrower than k, fa_ex_*_vdim; default: dk's)
 static int empty_backward(const char* who, bool both, bool no_q, void* dq, size_t dq_bytes, void* dk, void* dv, size_t dkv_bytes,
-                          const SinkArg& sk, hipStream_t st) {
+                          const SinkArg& sk, hipStream_t st, size_t dv_bytes = ~(size_t)0) {
     hipError_t e = sk.sinks ? hipMemsetAsync(sk.dsinks, 0, (size_t)sk.heads * 4, st) : hipSuccess;
     if (e != hipSuccess || both) return launched(who, e);
     if (no_q ? (!dk || !dv) : !dq) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
     if (no_q) {
         e = hipMemsetAsync(dk, 0, dkv_bytes, st);
-        if (e == hipSuccess) e = hipMemsetAsync(dv, 0, dkv_bytes, st);
+        if (e == hipSuccess) e = hipMemsetAsync(dv, 0, dv_bytes == ~(size_t)0 ? dkv_bytes : dv_bytes, st);
     } else {
         e = hipMemsetAsync(dq, 0, dq_bytes, st);
     }
     return launched(who, e);
+}
+
+// V narrower than Q / K (fa_ex_*_vdim: d_v after the sink / dlse group).  d_v = 0 and d_v = d are the call without the argument and
+// never come here.  The first broken rule, in this order: the widths (d_v > d; multiples of 8; d <= 192; d_v <= 128), the dtype,
+// then each feature the two-width kernels do not have, by name, then the scale.  Before any other check and any HIP call.
+struct VdimExtras {
+    bool mask = false, block_mask = false, dropout = false, window = false, softcap = false, alibi = false, sinks = false;
+};
+static int vdim_check(const char* who, int64_t d, int64_t d_v, int dtype, double scale, const VdimExtras& x) {
+    if (d_v < 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: d_v must be >= 0 (got %lld)", who, (long long)d_v);
+    if (d_v > d)
+        return fail(FA_ERR_UNSUPPORTED, "%s: d_v=%lld > d=%lld: a v wider than q and k is not supported", who, (long long)d_v, (long long)d);
+    if (d % 8 != 0 || d_v % 8 != 0)
+        return fail(FA_ERR_UNSUPPORTED, "%s: d_v != d needs d and d_v to be multiples of 8 (got d=%lld, d_v=%lld)", who, (long long)d,
+                    (long long)d_v);
+    if (d > 192) return fail(FA_ERR_UNSUPPORTED, "%s: d_v != d needs d <= 192 (got d=%lld)", who, (long long)d);
+    if (d_v > 128) return fail(FA_ERR_UNSUPPORTED, "%s: d_v != d needs d_v <= 128 (got d_v=%lld)", who, (long long)d_v);
+    if (dtype != FA_DTYPE_F16 && dtype != FA_DTYPE_BF16)
+        return fail(FA_ERR_UNSUPPORTED, "%s: d_v != d needs f16 or bf16 tensors (dtype code %d): there are no exact-f32 kernels with two widths",
+                    who, dtype);
+    const char* name = x.mask ? "mask" : x.block_mask ? "block_sparse_mask" : x.dropout ? "dropout_p > 0" : x.window ? "window_size"
+                       : x.softcap ? "softcap" : x.alibi ? "alibi_slopes" : x.sinks ? "sinks" : nullptr;
+    if (name) return fail(FA_ERR_UNSUPPORTED, "%s: %s is not supported with d_v != d", who, name);
+    if (!(scale > 0.0)) return fail(FA_ERR_UNSUPPORTED, "%s: d_v != d needs softmax_scale > 0", who);
+    return FA_OK;
+}
+// ... and what only the pointers and strides tell, once they are known to be there: 16-byte aligned tensors, 16-byte rows
+static int vdim_layout_check(const char* who, std::initializer_list<const void*> ptrs, std::initializer_list<int64_t> strides) {
+    for (const void* ptr : ptrs)
+        if ((uintptr_t)ptr % 16 != 0) return fail(FA_ERR_UNSUPPORTED, "%s: d_v != d needs 16-byte aligned tensors", who);
+    for (const int64_t st : strides)
+        if (st % 8 != 0) return fail(FA_ERR_UNSUPPORTED, "%s: d_v != d needs token strides that are multiples of 8 elements", who);
+    return FA_OK;
 }
 
 // One call of the fa_ex_forward* / fa_ex_backward* family.  The defaults are the narrower entry points' "argument absent": an entry
@@ -467,12 +501,24 @@ struct ExCall {
     ScoreMod sm;
     SinkArg sk;
     const float* dlse = nullptr;   // fa_ex_backward_dlse: the gradient of lse, (bh, nq) float32
+    int64_t d_v = 0;               // fa_ex_*_vdim: the width of v, o, do_ and dv (0: d)
     const uint8_t *mask = nullptr, *block_mask = nullptr;
     int64_t mask_bh_stride = 0, br = 0, bc = 0;
     uint64_t dropout_seed = 0;
     void *workspace = nullptr, *stream = nullptr;
     size_t workspace_bytes = 0;
 };
+
+// does the call carry a v of its own width?  (d_v = 0 and d_v = d: the call without the argument)
+static bool ex_vdim(const ExCall& c) { return c.d_v != 0 && c.d_v != c.d; }
+static int ex_vdim_check(const char* who, const ExCall& c) {
+    if (!ex_vdim(c) || c.d <= 0) return FA_OK;
+    VdimExtras x;
+    x.mask = c.mask != nullptr; x.block_mask = c.block_mask != nullptr; x.dropout = c.dropout_p > 0.0;
+    x.window = c.window_left != -1 || c.window_right != -1; x.softcap = c.sm.softcap > 0.0; x.alibi = c.sm.alibi != nullptr;
+    x.sinks = c.sk.sinks != nullptr;
+    return vdim_check(who, c.d, c.d_v, c.dtype, c.softmax_scale, x);
+}
 
 // the argument checks of a forward and a backward, in their order; the mask comes back canonical
 static int ex_checks(const char* who, const ExCall& c, bool backward, int& causal, int64_t& wl, int64_t& wr) {
@@ -495,6 +541,7 @@ static fa::ExArgs ex_args(const ExCall& c, int causal, int64_t wl, int64_t wr) {
     score_args(a, c.sm);
     sink_args(a, c.sk);
     a.dlse = c.dlse;
+    a.d_v = ex_vdim(c) ? c.d_v : 0;
     return a;
 }
 
@@ -513,10 +560,13 @@ static int no_key_dsinks(const char* who, const fa::ExArgs& a, hipStream_t st) {
 static int ex_forward_impl(const char* who, const ExCall& c) {
     int causal = c.causal;
     int64_t wl = c.window_left, wr = c.window_right;   // (window_canon rewrites the three)
+    if (const int rc = ex_vdim_check(who, c); rc != FA_OK) return rc;
     if (const int rc = ex_checks(who, c, false, causal, wl, wr); rc != FA_OK) return rc;
     if (c.bh == 0 || c.nq == 0) return FA_OK;
     if (!c.q || !c.o || !c.lse || (c.nk > 0 && (!c.k || !c.v))) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
-    if (c.nk == 0) return no_key_fill(who, c.o, c.lse, c.bh, c.nq, c.d, c.dtype, c.sk, reinterpret_cast<hipStream_t>(c.stream));
+    if (ex_vdim(c))
+        if (const int rc = vdim_layout_check(who, {c.q, c.k, c.v, c.o}, {}); rc != FA_OK) return rc;
+    if (c.nk == 0) return no_key_fill(who, c.o, c.lse, c.bh, c.nq, ex_vdim(c) ? c.d_v : c.d, c.dtype, c.sk, reinterpret_cast<hipStream_t>(c.stream));
     return launched(who, fa::launch_ex(ex_args(c, causal, wl, wr), false, reinterpret_cast<hipStream_t>(c.stream)));
 }
 
@@ -530,19 +580,23 @@ static size_t ex_bwd_ws_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_
 static int ex_backward_impl(const char* who, const ExCall& c) {
     int causal = c.causal;
     int64_t wl = c.window_left, wr = c.window_right;
+    if (const int rc = ex_vdim_check(who, c); rc != FA_OK) return rc;
     if (const int rc = ex_checks(who, c, true, causal, wl, wr); rc != FA_OK) return rc;
     if (const int rc = dlse_check(who, c.dlse); rc != FA_OK) return rc;
     const bool no_q = c.bh == 0 || c.nq == 0, no_k = c.bh == 0 || c.nk == 0;
     const size_t es = c.dtype == FA_DTYPE_F32 ? 4 : 2;
     if (no_q || no_k) {   // (grouped: dk and dv hold bh / kv_group units)
         const int rc = empty_backward(who, no_q && no_k, no_q, c.dq, (size_t)c.bh * c.nq * c.d * es, c.dk, c.dv,
-                                      (size_t)(c.bh / c.kv_group) * c.nk * c.d * es, c.sk, reinterpret_cast<hipStream_t>(c.stream));
+                                      (size_t)(c.bh / c.kv_group) * c.nk * c.d * es, c.sk, reinterpret_cast<hipStream_t>(c.stream),
+                                      (size_t)(c.bh / c.kv_group) * c.nk * (ex_vdim(c) ? c.d_v : c.d) * es);
         if (rc != FA_OK || no_q || !c.sk.sinks || !c.dlse) return rc;
         return no_key_dsinks(who, ex_args(c, causal, wl, wr), reinterpret_cast<hipStream_t>(c.stream));
     }
     if (!c.q || !c.k || !c.v || !c.o || !c.do_ || !c.lse || !c.dq || !c.dk || !c.dv)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
-    const size_t need = ex_bwd_ws_grouped(c.bh, c.kv_group, c.nq, c.nk, c.d, c.dtype);
+    if (ex_vdim(c))
+        if (const int rc = vdim_layout_check(who, {c.q, c.k, c.v, c.o, c.do_, c.dq, c.dk, c.dv}, {}); rc != FA_OK) return rc;
+    const size_t need = ex_bwd_ws_grouped(c.bh, c.kv_group, c.nq, c.nk, c.d, c.dtype);   // (d_v < d: the same rows, slabs of d's size)
     if (!c.workspace || c.workspace_bytes < need)
         return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, need, c.workspace_bytes);
     return launched(who, fa::launch_ex(ex_args(c, causal, wl, wr), true, reinterpret_cast<hipStream_t>(c.stream)));
@@ -702,6 +756,36 @@ int fa_ex_backward_dlse(const void* q, const void* k, const void* v, const void*
     return ex_backward_impl("fa_ex_backward_dlse", c);
 }
 
+int fa_ex_forward_vdim(const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t kv_group, int64_t nq,
+                       int64_t nk, int64_t d, int dtype, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                       double softcap, const float* alibi_slopes, int64_t alibi_heads, int64_t alibi_batch_stride, const float* sinks,
+                       int64_t sink_heads, int64_t d_v, const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br,
+                       int64_t bc, double dropout_p, uint64_t dropout_seed, void* stream) {
+    ExCall c = ex_call(q, k, v, o, lse, bh, nq, nk, d, dtype, causal, softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p,
+                       dropout_seed, stream);
+    c.kv_group = kv_group; c.window_left = window_left; c.window_right = window_right;
+    c.sm = {softcap, alibi_slopes, alibi_heads, alibi_batch_stride};
+    c.sk = {sinks, sink_heads, nullptr};
+    c.d_v = d_v;
+    return ex_forward_impl("fa_ex_forward_vdim", c);
+}
+
+int fa_ex_backward_vdim(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
+                        void* dv, int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype, int causal,
+                        int64_t window_left, int64_t window_right, double softmax_scale, double softcap, const float* alibi_slopes,
+                        int64_t alibi_heads, int64_t alibi_batch_stride, const float* sinks, int64_t sink_heads, float* dsinks,
+                        const float* dlse, int64_t d_v, const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br,
+                        int64_t bc, double dropout_p, uint64_t dropout_seed, void* workspace, size_t workspace_bytes, void* stream) {
+    ExCall c = ex_bwd_call(q, k, v, o, do_, lse, dq, dk, dv, bh, nq, nk, d, dtype, causal, softmax_scale, mask, mask_bh_stride, block_mask,
+                           br, bc, dropout_p, dropout_seed, workspace, workspace_bytes, stream);
+    c.kv_group = kv_group; c.window_left = window_left; c.window_right = window_right;
+    c.sm = {softcap, alibi_slopes, alibi_heads, alibi_batch_stride};
+    c.sk = {sinks, sink_heads, dsinks};
+    c.dlse = dlse;
+    c.d_v = d_v;
+    return ex_backward_impl("fa_ex_backward_vdim", c);
+}
+
 // ---- variable-length (packed) sequences: see include/fa_mi355x.h
 // Everything that can be checked without reading cu_seqlens (which would take a synchronise), before any HIP call.
 // One call of the fa_ex_*_varlen* family, fa_ex_forward_varlen_paged / _paged_fp8 included.  Defaults: "argument absent"; cache_dtype is the
@@ -720,6 +804,7 @@ struct VarlenCall {
     ScoreMod sm;            // (heads: heads_q)
     SinkArg sk;
     const float* dlse = nullptr;   // fa_ex_backward_varlen_dlse: the gradient of lse, (heads_q, total_q) float32
+    int64_t d_v = 0;               // fa_ex_*_varlen_vdim: the width of v, o, do_ and dv (0: d)
     const int32_t* block_table = nullptr;   // the paged forward, and (cache_dtype, the scales) its e4m3 pool
     int64_t max_blocks_per_seq = 0, num_blocks = 0, page_block_size = 0, k_page_stride = 0, v_page_stride = 0, descale_batch_stride = 0;
     int cache_dtype = 0;
@@ -727,6 +812,15 @@ struct VarlenCall {
     void *workspace = nullptr, *stream = nullptr;
     size_t workspace_bytes = 0;
 };
+
+static bool varlen_vdim(const VarlenCall& c) { return c.d_v != 0 && c.d_v != c.d; }
+static int varlen_vdim_check(const char* who, const VarlenCall& c) {
+    if (!varlen_vdim(c) || c.d <= 0) return FA_OK;
+    VdimExtras x;
+    x.dropout = c.dropout_p > 0.0; x.window = c.window_left != -1 || c.window_right != -1; x.softcap = c.sm.softcap > 0.0;
+    x.alibi = c.sm.alibi != nullptr; x.sinks = c.sk.sinks != nullptr;
+    return vdim_check(who, c.d, c.d_v, c.dtype, c.softmax_scale, x);
+}
 
 // (total_k: the paged call has no token count and passes 1)
 static int varlen_check(const char* who, const VarlenCall& c, int64_t total_k) {
@@ -743,7 +837,7 @@ static int varlen_check(const char* who, const VarlenCall& c, int64_t total_k) {
     if (d <= 0 || total_q < 0 || total_k < 0 || max_q < 0 || max_k < 0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: bad shape (d=%lld, total_q=%lld, total_k=%lld, max_seqlen_q=%lld, max_seqlen_k=%lld)", who,
                     (long long)d, (long long)total_q, (long long)total_k, (long long)max_q, (long long)max_k);
-    if (sq < hq * d || sk < hkv * d || sv < hkv * d)
+    if (sq < hq * d || sk < hkv * d || sv < hkv * (varlen_vdim(c) ? c.d_v : d))   // (a v of its own width: rows of heads_kv * d_v)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: token strides (%lld, %lld, %lld) must be >= heads * d (%lld, %lld)", who, (long long)sq,
                     (long long)sk, (long long)sv, (long long)(hq * d), (long long)(hkv * d));
     if ((total_q > 0 && !cu_q) || (total_k > 0 && !cu_k)) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null cu_seqlens", who);
@@ -781,13 +875,16 @@ static fa::ExArgs varlen_args(const VarlenCall& c, int64_t total_k, int64_t max_
     score_args(a, c.sm);
     sink_args(a, c.sk);
     a.dlse = c.dlse;
+    a.d_v = varlen_vdim(c) ? c.d_v : 0;
     return a;
 }
 
 static int varlen_forward_impl(const char* who, const VarlenCall& c) {
     int causal = c.causal;
     int64_t wl = c.window_left, wr = c.window_right;   // (window_canon rewrites the three)
-    int rc = varlen_check(who, c, c.total_k);
+    int rc = varlen_vdim_check(who, c);
+    if (rc != FA_OK) return rc;
+    rc = varlen_check(who, c, c.total_k);
     if (rc != FA_OK) return rc;
     if (c.heads_q >= 1 && (rc = score_check(who, c.sm, c.batch * c.heads_q)) != FA_OK) return rc;
     if ((rc = sink_check(who, c.sk, c.heads_q, false)) != FA_OK) return rc;   // (indexed by query head)
@@ -795,7 +892,9 @@ static int varlen_forward_impl(const char* who, const VarlenCall& c) {
     if (c.total_q == 0 || c.max_seqlen_q == 0) return FA_OK;   // no query row in any sequence
     if (!c.q || !c.o || !c.lse || (c.total_k > 0 && (!c.k || !c.v))) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
     hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
-    if (c.total_k == 0 || c.max_seqlen_k == 0) return no_key_fill(who, c.o, c.lse, c.heads_q, c.total_q, c.d, c.dtype, c.sk, st);   // in any sequence
+    if (varlen_vdim(c) && (rc = vdim_layout_check(who, {c.q, c.k, c.v, c.o}, {c.q_stride, c.k_stride, c.v_stride})) != FA_OK) return rc;
+    if (c.total_k == 0 || c.max_seqlen_k == 0)   // in any sequence
+        return no_key_fill(who, c.o, c.lse, c.heads_q, c.total_q, varlen_vdim(c) ? c.d_v : c.d, c.dtype, c.sk, st);
     fa::ExArgs a = varlen_args(c, c.total_k, c.max_seqlen_k, causal, wl, wr);
     return launched(who, fa::launch_ex(a, false, st));
 }
@@ -878,7 +977,9 @@ size_t fa_ex_backward_workspace_bytes_varlen(int64_t heads_q, int64_t heads_kv, 
 static int varlen_backward_impl(const char* who, const VarlenCall& c) {
     int causal = c.causal;
     int64_t wl = c.window_left, wr = c.window_right;   // (window_canon rewrites the three)
-    int rc = varlen_check(who, c, c.total_k);
+    int rc = varlen_vdim_check(who, c);
+    if (rc != FA_OK) return rc;
+    rc = varlen_check(who, c, c.total_k);
     if (rc != FA_OK) return rc;
     if (c.heads_q >= 1 && (rc = score_check(who, c.sm, c.batch * c.heads_q)) != FA_OK) return rc;
     if ((rc = sink_check(who, c.sk, c.heads_q, true)) != FA_OK) return rc;
@@ -888,12 +989,15 @@ static int varlen_backward_impl(const char* who, const VarlenCall& c) {
     const size_t es = c.dtype == FA_DTYPE_F32 ? 4 : 2;
     if (no_q || no_k) {   // ... in every sequence
         rc = empty_backward(who, no_q && no_k, no_q, c.dq, (size_t)c.total_q * c.heads_q * c.d * es, c.dk, c.dv,
-                            (size_t)c.total_k * c.heads_kv * c.d * es, c.sk, reinterpret_cast<hipStream_t>(c.stream));
+                            (size_t)c.total_k * c.heads_kv * c.d * es, c.sk, reinterpret_cast<hipStream_t>(c.stream),
+                            (size_t)c.total_k * c.heads_kv * (varlen_vdim(c) ? c.d_v : c.d) * es);
         if (rc != FA_OK || no_q || !c.sk.sinks || !c.dlse) return rc;
         return no_key_dsinks(who, varlen_args(c, c.total_k, c.max_seqlen_k, causal, wl, wr), reinterpret_cast<hipStream_t>(c.stream));
     }
     if (!c.q || !c.k || !c.v || !c.o || !c.do_ || !c.lse || !c.dq || !c.dk || !c.dv)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    if (varlen_vdim(c) && (rc = vdim_layout_check(who, {c.q, c.k, c.v, c.o, c.do_, c.dq, c.dk, c.dv}, {c.q_stride, c.k_stride, c.v_stride})) != FA_OK)
+        return rc;
     const size_t need = fa_ex_backward_workspace_bytes_varlen(c.heads_q, c.heads_kv, c.total_q, c.total_k, c.d, c.dtype);
     if (!c.workspace || c.workspace_bytes < need)
         return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, need, c.workspace_bytes);
@@ -960,6 +1064,39 @@ int fa_ex_backward_varlen_dlse(const void* q, const void* k, const void* v, cons
     c.sk = {sinks, sink_heads, dsinks};
     c.dlse = dlse;
     return varlen_backward_impl("fa_ex_backward_varlen_dlse", c);
+}
+
+int fa_ex_forward_varlen_vdim(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
+                              const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k,
+                              int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                              int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                              double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, const float* sinks,
+                              int64_t sink_heads, int64_t d_v, double dropout_p, uint64_t dropout_seed, void* stream) {
+    VarlenCall c = varlen_call(q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k,
+                               d, dtype, q_stride, k_stride, v_stride, causal, window_left, window_right, softmax_scale);
+    c.dropout_p = dropout_p; c.dropout_seed = dropout_seed; c.stream = stream;
+    c.sm = {softcap, alibi_slopes, heads_q, alibi_batch_stride};
+    c.sk = {sinks, sink_heads, nullptr};
+    c.d_v = d_v;
+    return varlen_forward_impl("fa_ex_forward_varlen_vdim", c);
+}
+
+int fa_ex_backward_varlen_vdim(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
+                               void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                               int64_t total_q, int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
+                               int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                               double softcap, const float* alibi_slopes, int64_t alibi_batch_stride, const float* sinks,
+                               int64_t sink_heads, float* dsinks, const float* dlse, int64_t d_v, double dropout_p, uint64_t dropout_seed,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    VarlenCall c = varlen_bwd_call(q, k, v, o, do_, lse, dq, dk, dv, cu_seqlens_q, cu_seqlens_k, batch, heads_q, heads_kv, total_q, total_k,
+                                   max_seqlen_q, max_seqlen_k, d, dtype, q_stride, k_stride, v_stride, causal, window_left, window_right,
+                                   softmax_scale, workspace, workspace_bytes);
+    c.dropout_p = dropout_p; c.dropout_seed = dropout_seed; c.stream = stream;
+    c.sm = {softcap, alibi_slopes, heads_q, alibi_batch_stride};
+    c.sk = {sinks, sink_heads, dsinks};
+    c.dlse = dlse;
+    c.d_v = d_v;
+    return varlen_backward_impl("fa_ex_backward_varlen_vdim", c);
 }
 
 // ---- the varlen forward over a paged K/V cache: see include/fa_mi355x.h

@@ -1013,6 +1013,8 @@ static hipError_t launch_ex_varlen_one(const ExArgs& a, bool backward, hipStream
 }
 
 hipError_t launch_ex(const ExArgs& a, bool backward, hipStream_t st) {
+    // V narrower than Q / K: kernels of their own, or nothing (the C layer has refused by name what they do not take)
+    if (a.d_v != 0) return ex_vdim_supported(a) ? launch_ex_vdim(a, backward, st) : hipErrorInvalidConfiguration;
     if (a.cu_q) {
         if (a.block_table) return backward ? hipErrorInvalidValue : launch_ex_varlen_paged(a, st);   // (forward only)
         if (!backward || a.kv_group <= 1) return launch_ex_varlen_one(a, backward, st);

@@ -467,6 +467,24 @@ static hipError_t exm_bwd_t(const ExArgs& a, hipStream_t st) {
     return e;
 }
 
+// The row-constant pre-pass for the kernels of another translation unit (fa_ex_mfma_vdim.hip): exm_prep_kernel /
+// exm_prep_varlen_kernel as exm_bwd_t and exm_varlen_t launch them, with d_row the row width of o and dout.
+hipError_t launch_exm_prep(const ExArgs& a, int64_t d_row, float* nlse, float* ndelta, hipStream_t st) {
+    const bool bf = a.dtype == 2;
+    if (a.cu_q) {
+        const int tph = (int)((a.total_q + 15) / 16);
+        auto kern = bf ? exm_prep_varlen_kernel<bf16_tag> : exm_prep_varlen_kernel<f16_tag>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(tph * a.heads_q)), dim3(256), 0, st, (const uint16_t*)a.o, (const uint16_t*)a.dout,
+                           (const float*)a.lse, nlse, ndelta, (int)a.total_q, tph, (int)a.heads_q, (int)d_row, 1.f / a.scale, a.dlse);
+    } else {
+        const long long rows = (long long)a.bh * a.nq;
+        auto kern = bf ? exm_prep_kernel<bf16_tag> : exm_prep_kernel<f16_tag>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, (const uint16_t*)a.o, (const uint16_t*)a.dout,
+                           (const float*)a.lse, nlse, ndelta, rows, (int)d_row, 1.f / a.scale, a.dlse);
+    }
+    return hipGetLastError();
+}
+
 // S: 0, or kFeatScore for a call with a score modifier (every other feature combination once more with it)
 template <typename Tag, int D, int S>
 static hipError_t exm_by_feat_s(const ExArgs& a, bool backward, hipStream_t st) {

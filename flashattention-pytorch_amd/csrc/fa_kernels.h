@@ -175,6 +175,10 @@ struct ExArgs {
     int kv_e4m3 = 0;
     const float *k_descale = nullptr, *v_descale = nullptr;
     int64_t descale_bstride = 0;
+    // V narrower than Q / K (fa_ex_*_vdim; 0: v, o, dout, dv are d wide like q and k).  d_v != 0: v, o, dout and dv are d_v wide
+    // (varlen: o, dout rows of heads_q * d_v), the call goes to launch_ex_vdim (fa_ex_mfma_vdim.hip) and carries no other feature
+    // than causal, kv_group, packing and dlse.  The C layer passes d_v = d as 0.
+    int64_t d_v = 0;
 };
 // does the call carry a score modifier (softcap or ALiBi)?  Such a call runs on the extended kernels only.
 inline bool ex_scoremod(const ExArgs& a) { return a.softcap > 0.0 || a.alibi != nullptr; }
@@ -196,6 +200,11 @@ hipError_t launch_ex_mfma_varlen_paged(const ExArgs& a, hipStream_t st);
 bool ex_mfma_paged_kv8_supported(const ExArgs& a);                    // the same from an e4m3 pool (a.kv_e4m3; fa_ex_mfma_kv8.hip)
 hipError_t launch_ex_mfma_varlen_paged_kv8(const ExArgs& a, hipStream_t st);
 size_t ex_backward_workspace_bytes(int64_t bh, int64_t nq);
+// the row constants [-lse / scale | -delta (+ dlse)] of a backward whose o and dout rows are d_row wide (fa_ex_mfma.hip's pre-pass)
+hipError_t launch_exm_prep(const ExArgs& a, int64_t d_row, float* nlse, float* ndelta, hipStream_t st);
+// a.d_v != 0 (fa_ex_mfma_vdim.hip): 16-bit MFMA kernels with two widths, d <= 192 and d_v <= 128; padded and packed
+bool ex_vdim_supported(const ExArgs& a);
+hipError_t launch_ex_vdim(const ExArgs& a, bool backward, hipStream_t st);
 // the two per-query-head dK / dV partial slabs of a grouped backward (kv_group > 1), each rounded to 256 bytes
 inline size_t kv_partial_bytes(int64_t bh, int64_t nk, int64_t d, int dtype) {
     return (((size_t)bh * nk * d * (dtype == 0 ? 4 : 2) + 255) & ~(size_t)255);
@@ -314,5 +323,8 @@ hipError_t launch_merge(const MergeArgs& a, bool backward, hipStream_t st);
 // that order and rounded once to the tensor dtype; units of nk * d elements, bh / g of them in dk and dv.
 hipError_t launch_kv_group_sum(const void* pk, const void* pv, void* dk, void* dv, int64_t bh_kv, int64_t g, int64_t nk, int64_t d,
                                int dtype, hipStream_t st);
+
+// the same for one tensor (dK and dV of different widths)
+hipError_t launch_kv_group_sum_one(const void* src, void* dst, int64_t bh_kv, int64_t g, int64_t nk, int64_t d, int dtype, hipStream_t st);
 
 }  // namespace fa

@@ -70,6 +70,68 @@ static hipError_t kv_group_sum_t(const void* pk, const void* pv, void* dk, void*
     return hipGetLastError();
 }
 
+// One tensor alone (dK and dV of different widths: fa_ex_mfma_vdim.hip): the same sum, member 0 first, fp32, one rounding.
+template <typename T>
+__global__ __launch_bounds__(256) void kv_group_sum_one_kernel(const T* __restrict__ src, T* __restrict__ dst, long long per_unit,
+                                                               long long cpu, long long nchunk, int g, int vec_ok) {
+    constexpr int VEC = 16 / (int)sizeof(T);
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nchunk) return;
+    const long long u = i / cpu, off = (i - u * cpu) * VEC;
+    const T* s0 = src + (u * g) * per_unit + off;
+    T* d0 = dst + u * per_unit + off;
+    float acc[VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) acc[j] = 0.f;
+    if (vec_ok) {
+        for (int m = 0; m < g; ++m) {
+            const uint4 x = *reinterpret_cast<const uint4*>(s0 + (long long)m * per_unit);
+            const T* e = reinterpret_cast<const T*>(&x);
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) acc[j] += to_f32<T>(e[j]);
+        }
+        uint4 y;
+        T* e = reinterpret_cast<T*>(&y);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) e[j] = from_f32<T>(acc[j]);
+        *reinterpret_cast<uint4*>(d0) = y;
+        return;
+    }
+    const int cnt = per_unit - off < VEC ? (int)(per_unit - off) : VEC;
+    for (int m = 0; m < g; ++m)
+#pragma unroll
+        for (int j = 0; j < VEC; ++j)
+            if (j < cnt) acc[j] += to_f32<T>(s0[(long long)m * per_unit + j]);
+#pragma unroll
+    for (int j = 0; j < VEC; ++j)
+        if (j < cnt) d0[j] = from_f32<T>(acc[j]);
+}
+
+template <typename T>
+static hipError_t kv_group_sum_one_t(const void* src, void* dst, int64_t bh_kv, int64_t g, int64_t nk, int64_t d, hipStream_t st) {
+    constexpr int VEC = 16 / (int)sizeof(T);
+    const long long per_unit = (long long)nk * d;
+    const long long cpu = (per_unit + VEC - 1) / VEC;
+    const long long nchunk = cpu * bh_kv;
+    if (nchunk == 0) return hipSuccess;
+    const int vec_ok = per_unit % VEC == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+    const long long blocks = (nchunk + 255) / 256;
+    if (blocks * 256 >= ((long long)1 << 32)) return hipErrorInvalidConfiguration;
+    ProfScope ps(K_KV_GROUP_SUM, st);
+    hipLaunchKernelGGL(kv_group_sum_one_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, (const T*)src, (T*)dst, per_unit, cpu,
+                       nchunk, (int)g, vec_ok);
+    return hipGetLastError();
+}
+
+hipError_t launch_kv_group_sum_one(const void* src, void* dst, int64_t bh_kv, int64_t g, int64_t nk, int64_t d, int dtype,
+                                   hipStream_t st) {
+    switch (dtype) {
+        case 0: return kv_group_sum_one_t<float>(src, dst, bh_kv, g, nk, d, st);
+        case 1: return kv_group_sum_one_t<__half>(src, dst, bh_kv, g, nk, d, st);
+        default: return kv_group_sum_one_t<__hip_bfloat16>(src, dst, bh_kv, g, nk, d, st);
+    }
+}
+
 hipError_t launch_kv_group_sum(const void* pk, const void* pv, void* dk, void* dv, int64_t bh_kv, int64_t g, int64_t nk, int64_t d,
                                int dtype, hipStream_t st) {
     switch (dtype) {

@@ -52,6 +52,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_rotary_apply",
     "fa_ex_backward_dlse", "fa_ex_backward_varlen_dlse", "fa_merge_states", "fa_merge_states_backward",
     "fa_mla_sparse_forward", "fa_mla_sparse_workspace_bytes",
+    "fa_ex_forward_vdim", "fa_ex_backward_vdim", "fa_ex_forward_varlen_vdim", "fa_ex_backward_varlen_vdim",
 )
 
 
@@ -82,6 +83,7 @@ _MODH = _fields("d:softcap p:alibi_slopes i:alibi_batch_stride")   # varlen and 
 _SINK = _fields("p:sinks i:sink_heads")
 _DSINK = _fields("p:dsinks")
 _DLSE = _fields("p:dlse")                                     # the gradient of lse, after the sink group
+_VDIM = _fields("i:d_v")                                      # the width of v, o, do_, dv (0: d), after the sink / dlse group
 _MASKS = _fields("p:mask i:mask_bh_stride p:block_mask i:br,bc")
 _DROPOUT = _fields("d:dropout_p u:dropout_seed")
 _VARLEN = _fields("p:cu_seqlens_q,cu_seqlens_k i:batch,heads_q,heads_kv,total_q,total_k,max_seqlen_q,max_seqlen_k,d c:dtype "
@@ -146,6 +148,10 @@ for _dir, _ptrs, _tail, _ds in (("forward", _FWD, _STREAM, ()), ("backward", _BW
     _sig(f"fa_ex_{_dir}_varlen_sink", _ptrs + _VARLEN + _MODH + _SINK + _ds + _DROPOUT + _tail)
 _sig("fa_ex_backward_dlse", _ex_sig(_BWD, _WS, _GROUP, _WINDOW, _MOD + _SINK + _DSINK + _DLSE))
 _sig("fa_ex_backward_varlen_dlse", _BWD + _VARLEN + _MODH + _SINK + _DSINK + _DLSE + _DROPOUT + _WS)
+_sig("fa_ex_forward_vdim", _ex_sig(_FWD, _STREAM, _GROUP, _WINDOW, _MOD + _SINK + _VDIM))
+_sig("fa_ex_backward_vdim", _ex_sig(_BWD, _WS, _GROUP, _WINDOW, _MOD + _SINK + _DSINK + _DLSE + _VDIM))
+_sig("fa_ex_forward_varlen_vdim", _FWD + _VARLEN + _MODH + _SINK + _VDIM + _DROPOUT + _STREAM)
+_sig("fa_ex_backward_varlen_vdim", _BWD + _VARLEN + _MODH + _SINK + _DSINK + _DLSE + _VDIM + _DROPOUT + _WS)
 _sig("fa_ex_forward_varlen_paged", _FWD + _VARLEN + _MODH + _SINK + _VPAGED + _STREAM)
 _sig("fa_ex_forward_varlen_paged_fp8", _FWD + _VARLEN + _MODH + _SINK + _VPAGED + _FP8 + _STREAM)
 _sig("fa_ex_backward_workspace_bytes", _fields("i:bh") + _EXDIMS, _SIZE)
@@ -206,6 +212,10 @@ _family("fa_ex_forward_sink", ["fa_ex_forward" + _suffix for _suffix in ("", "_g
 _family("fa_ex_forward_varlen_sink", ["fa_ex_forward_varlen", "fa_ex_forward_varlen_scoremod"])
 _family("fa_ex_backward_dlse", ["fa_ex_backward" + _suffix for _suffix in ("", "_grouped", "_window", "_scoremod", "_sink")])
 _family("fa_ex_backward_varlen_dlse", ["fa_ex_backward_varlen" + _suffix for _suffix in ("", "_scoremod", "_sink")])
+# a v of its own width: each entry point takes the widest member above plus d_v and is called with exactly its own arguments, so
+# the four families above, and what their members are handed, stay what they were
+for _name in ("fa_ex_forward_vdim", "fa_ex_backward_vdim", "fa_ex_forward_varlen_vdim", "fa_ex_backward_varlen_vdim"):
+    _family(_name, [])
 _family("fa_ex_forward_varlen_paged_fp8", ["fa_ex_forward_varlen_paged"])
 _family("fa_rotary_apply", [])
 _family("fa_merge_states", [])
@@ -423,10 +433,10 @@ def _ex_common(who, q, k, v, mask, block_mask, br, bc):
         if not t.is_cuda:
             raise RuntimeError(f"{who}: tensors must be on the GPU (HIP device); there is no CPU path")
     # grouped-query attention: k and v may hold fewer units than q, BH / kv_group, query unit u reading K/V unit u // kv_group
-    if (q.dim() != 3 or k.dim() != 3 or v.shape != k.shape or q.shape[2] != k.shape[2] or
+    if (q.dim() != 3 or k.dim() != 3 or v.dim() != 3 or v.shape[:2] != k.shape[:2] or q.shape[2] != k.shape[2] or
             (k.shape[0] == 0 and q.shape[0] != 0) or (k.shape[0] > 0 and q.shape[0] % k.shape[0] != 0)):
-        raise RuntimeError(f"{who}: q must be (BH, Nq, d), k and v (BH / kv_group, Nk, d); got {tuple(q.shape)}, {tuple(k.shape)}, "
-                           f"{tuple(v.shape)}")
+        raise RuntimeError(f"{who}: q must be (BH, Nq, d), k (BH / kv_group, Nk, d) and v (BH / kv_group, Nk, d_v); got {tuple(q.shape)}, "
+                           f"{tuple(k.shape)}, {tuple(v.shape)}")
     if q.dtype not in _DTYPE_CODE or k.dtype != q.dtype or v.dtype != q.dtype:
         raise RuntimeError(f"{who}: q, k, v must share a supported dtype")
     bh, nq, d = q.shape
@@ -549,9 +559,31 @@ def sinks_arg(who, sinks, device, units, heads=None):
     return sinks.data_ptr(), sinks.shape[0], sinks
 
 
-def _ex_variant(sinks, mod, window, grouped=False, dlse=False) -> str:
+def vdim_arg(who, d, d_v, dtype, **carried):
+    """The width of v as the library takes it: 0 where v is as wide as q and k (the call without the argument), else d_v after the
+    rules of fa_ex_*_vdim in the library's order — NotImplementedError naming the first one broken: the widths, the dtype, then
+    each argument in `carried` (name=truthy) that the two-width kernels do not take."""
+    if d_v == d:
+        return 0
+    if d_v > d:
+        raise NotImplementedError(f"{who}: v wider than q and k (d_v={d_v} > d={d}) is not supported")
+    if d % 8 != 0 or d_v % 8 != 0 or d_v < 8:
+        raise NotImplementedError(f"{who}: d_v != d needs d and d_v to be positive multiples of 8 (got d={d}, d_v={d_v})")
+    if d > 192:
+        raise NotImplementedError(f"{who}: d_v != d needs d <= 192 (got d={d})")
+    if d_v > 128:
+        raise NotImplementedError(f"{who}: d_v != d needs d_v <= 128 (got d_v={d_v})")
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise NotImplementedError(f"{who}: d_v != d needs float16 or bfloat16 tensors, got dtype {dtype} (no exact-f32 kernels with two widths)")
+    for name, on in carried.items():
+        if on:
+            raise NotImplementedError(f"{who}: {name} is not supported with d_v != d (v of shape (..., {d_v}), q and k (..., {d}))")
+    return d_v
+
+
+def _ex_variant(sinks, mod, window, grouped=False, dlse=False, vdim=False) -> str:
     """the narrowest entry point of a family that takes what the call carries: each one adds a group of arguments to the one before"""
-    return "_dlse" if dlse else "_sink" if sinks else "_scoremod" if mod else "_window" if window else "_grouped" if grouped else ""
+    return "_vdim" if vdim else "_dlse" if dlse else "_sink" if sinks else "_scoremod" if mod else "_window" if window else "_grouped" if grouped else ""
 
 
 def ex_forward(q, k, v, causal, softmax_scale, mask=None, block_mask=None, br=128, bc=128, dropout_p=0.0, seed=0, window=(-1, -1),
@@ -562,19 +594,24 @@ def ex_forward(q, k, v, causal, softmax_scale, mask=None, block_mask=None, br=12
     [i + Nk - Nq - left, i + Nk - Nq + right], -1 = unbounded (fa_ex_forward_window).  softcap > 0 caps the scores at
     softcap * tanh(s / softcap); alibi_slopes (float32 (BH,), or (B, H) with B * H = BH) subtract slope * |i + Nk - Nq - j|
     (fa_ex_forward_scoremod).  sinks (float32 (sink_heads,), sink_heads dividing BH: unit u takes sinks[u % sink_heads]) adds one
-    column exp(sink) with a zero value to each row's softmax; lse contains it (fa_ex_forward_sink)."""
+    column exp(sink) with a zero value to each row's softmax; lse contains it (fa_ex_forward_sink).
+    v may be narrower than q and k, (BH / g, Nk, d_v) with 8 <= d_v < d <= 192, d_v <= 128, both multiples of 8, float16 / bfloat16
+    (fa_ex_forward_vdim; MLA prefill: 192 + 128): o is then (BH, Nq, d_v).  It goes with causal, GQA and softmax_scale only: mask,
+    block_sparse_mask, dropout_p, window_size, softcap, alibi_slopes and sinks raise NotImplementedError with the name (vdim_arg)."""
     wl, wr = window_arg("ex_forward", window)
     cap = softcap_arg("ex_forward", softcap)
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     bh, nq, nk, d, code, mask, mptr, mstride, block_mask, bptr, g = _ex_common("ex_forward", q, k, v, mask, block_mask, br, bc)
     aptr, aheads, astride, alibi_slopes = alibi_arg("ex_forward", alibi_slopes, q.device, bh)
     sptr, sheads, sinks = sinks_arg("ex_forward", sinks, q.device, bh)
+    d_v = vdim_arg("ex_forward", d, v.shape[2], q.dtype, mask=mask is not None, block_sparse_mask=block_mask is not None,
+                   dropout_p=dropout_p > 0.0, window_size=(wl, wr) != (-1, -1), softcap=cap > 0.0, alibi_slopes=aptr, sinks=sptr)
     with torch.cuda.device(q.device):
-        o = torch.empty_like(q)
+        o = torch.empty((bh, nq, v.shape[2]), dtype=q.dtype, device=q.device)
         lse = torch.empty((bh, nq), dtype=torch.float32, device=q.device)
-        _call("fa_ex_forward" + _ex_variant(sptr, cap > 0.0 or aptr, (wl, wr) != (-1, -1), g > 1), (
+        _call("fa_ex_forward" + _ex_variant(sptr, cap > 0.0 or aptr, (wl, wr) != (-1, -1), g > 1, vdim=d_v), (
             q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), bh, g, nq, nk, d, code, int(bool(causal)), wl, wr,
-            float(softmax_scale), cap, aptr, aheads, astride, sptr, sheads, mptr, mstride, bptr, int(br), int(bc), float(dropout_p),
+            float(softmax_scale), cap, aptr, aheads, astride, sptr, sheads, *((d_v,) if d_v else ()), mptr, mstride, bptr, int(br), int(bc), float(dropout_p),
             int(seed) & (2 ** 64 - 1), _stream_ptr(q.device)))
     return o, lse
 
@@ -583,7 +620,8 @@ def ex_backward(q, k, v, o, do_, lse, causal, softmax_scale, mask=None, block_ma
                 window=(-1, -1), softcap=0.0, alibi_slopes=None, *, dlse=None, sinks=None):
     """(dq, dk, dv) of ex_forward; with sinks (and the lse ex_forward returned with them) also dsinks, float32 (sink_heads,), as a
     fourth result (fa_ex_backward_sink).  dlse: the gradient of lse, float32 (BH, Nq) on q's device, or None
-    (fa_ex_backward_dlse); rows whose lse is -inf ignore it.  dlse is keyword-only, and sinks with it: sinks stays the last parameter."""
+    (fa_ex_backward_dlse); rows whose lse is -inf ignore it.  dlse is keyword-only, and sinks with it: sinks stays the last parameter.
+    With a v of its own width (ex_forward) o and do_ are (BH, Nq, d_v) and dv comes back in v's shape (fa_ex_backward_vdim)."""
     wl, wr = window_arg("ex_backward", window)
     cap = softcap_arg("ex_backward", softcap)
     q, k, v, o, do_, lse = (t.contiguous() for t in (q, k, v, o, do_, lse))
@@ -591,15 +629,17 @@ def ex_backward(q, k, v, o, do_, lse, causal, softmax_scale, mask=None, block_ma
     aptr, aheads, astride, alibi_slopes = alibi_arg("ex_backward", alibi_slopes, q.device, bh)
     sptr, sheads, sinks = sinks_arg("ex_backward", sinks, q.device, bh)
     mod = cap > 0.0 or aptr != 0 or sptr != 0
-    if o.shape != q.shape or do_.shape != q.shape or lse.shape != (bh, nq) or lse.dtype != torch.float32:
-        raise RuntimeError("ex_backward: o, do must be (BH, Nq, d) and lse (BH, Nq) float32")
+    d_v = vdim_arg("ex_backward", d, v.shape[2], q.dtype, mask=mask is not None, block_sparse_mask=block_mask is not None,
+                   dropout_p=dropout_p > 0.0, window_size=(wl, wr) != (-1, -1), softcap=cap > 0.0, alibi_slopes=aptr, sinks=sptr)
+    if o.shape != (bh, nq, v.shape[2]) or do_.shape != o.shape or lse.shape != (bh, nq) or lse.dtype != torch.float32:
+        raise RuntimeError("ex_backward: o, do must be (BH, Nq, d_v) (v's width) and lse (BH, Nq) float32")
     dlse = _dlse_arg("ex_backward", dlse, lse, "(BH, Nq)")
     with torch.cuda.device(q.device):
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        extras = int(mask is not None or block_mask is not None or dropout_p > 0.0 or mod or dlse is not None or
+        extras = int(mask is not None or block_mask is not None or dropout_p > 0.0 or mod or dlse is not None or d_v != 0 or
                      window_effective(nq, nk, bool(causal), (wl, wr)))   # (the dS hand-over serves neither a window nor a modifier,
         #                                                                    nor a gradient of lse)
-        if g > 1 or (wl, wr) != (-1, -1) or mod:   # (+ the per-query-head dK / dV partials the library sums over each group)
+        if g > 1 or (wl, wr) != (-1, -1) or mod or d_v:   # (+ the per-query-head dK / dV partials the library sums over each group)
             small = int(_lib.fa_ex_backward_workspace_bytes_grouped(bh, g, nq, nk, d, code))
             fast = int(_lib.fa_ex_backward_workspace_bytes_fast_grouped(bh, g, nq, nk, d, code, int(bool(causal)), extras))
         else:
@@ -611,10 +651,10 @@ def ex_backward(q, k, v, o, do_, lse, causal, softmax_scale, mask=None, block_ma
         ws = _workspace(q.device, nbytes)
         nbytes = max(nbytes, 0 if capturing else _workspaces.capacity(q.device, _stream_ptr(q.device)))
         dsinks = torch.empty((sheads,), dtype=torch.float32, device=q.device) if sptr else None
-        _call("fa_ex_backward" + _ex_variant(sptr, mod, (wl, wr) != (-1, -1), g > 1, dlse is not None), (
+        _call("fa_ex_backward" + _ex_variant(sptr, mod, (wl, wr) != (-1, -1), g > 1, dlse is not None, vdim=d_v), (
             q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do_.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
             dv.data_ptr(), bh, g, nq, nk, d, code, int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, aheads, astride, sptr,
-            sheads, _ptr(dsinks), _ptr(dlse), mptr, mstride, bptr, int(br), int(bc), float(dropout_p), int(seed) & (2 ** 64 - 1), ws.data_ptr(),
+            sheads, _ptr(dsinks), _ptr(dlse), *((d_v,) if d_v else ()), mptr, mstride, bptr, int(br), int(bc), float(dropout_p), int(seed) & (2 ** 64 - 1), ws.data_ptr(),
             nbytes, _stream_ptr(q.device)))
     return (dq, dk, dv, dsinks) if sptr else (dq, dk, dv)
 
@@ -634,9 +674,9 @@ def _varlen_common(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_s
     for t in (q, k, v, cu_seqlens_q, cu_seqlens_k):
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
             raise RuntimeError(f"{who}: tensors must be on the GPU (HIP device); there is no CPU path")
-    if q.dim() != 3 or k.dim() != 3 or v.shape != k.shape or q.shape[2] != k.shape[2]:
-        raise RuntimeError(f"{who}: q must be (total_q, H_q, d), k and v (total_k, H_kv, d); got {tuple(q.shape)}, {tuple(k.shape)}, "
-                           f"{tuple(v.shape)}")
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3 or v.shape[:2] != k.shape[:2] or q.shape[2] != k.shape[2]:
+        raise RuntimeError(f"{who}: q must be (total_q, H_q, d), k (total_k, H_kv, d) and v (total_k, H_kv, d_v); got {tuple(q.shape)}, "
+                           f"{tuple(k.shape)}, {tuple(v.shape)}")
     if q.dtype not in _DTYPE_CODE or k.dtype != q.dtype or v.dtype != q.dtype:
         raise RuntimeError(f"{who}: q, k, v must share a supported dtype")
     if len({q.device, k.device, v.device, cu_seqlens_q.device, cu_seqlens_k.device}) != 1:
@@ -655,7 +695,7 @@ def _varlen_common(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_s
         raise RuntimeError(f"{who}: max_seqlen_q, max_seqlen_k must be >= 0")
     sq = _token_stride(who, "q", q, hq, d)
     sk = _token_stride(who, "k", k, hkv, d)
-    sv = _token_stride(who, "v", v, hkv, d)
+    sv = _token_stride(who, "v", v, hkv, v.shape[2])   # (v's own width: its heads adjacent at stride d_v)
     cu_q, cu_k = cu_seqlens_q.contiguous(), cu_seqlens_k.contiguous()
     return (cu_q, cu_k, cu_q.shape[0] - 1, hq, hkv, total_q, total_k, mq, mk, d, _DTYPE_CODE[q.dtype], sq, sk, sv)
 
@@ -747,10 +787,19 @@ def ex_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seq
     a stored byte c of K head h of sequence b stands for e4m3(c) * k_descale[b, h] (V: v_descale), float32 (batch, H_kv) or (H_kv,)
     on q's device, None = 1.0.  The score is softmax_scale * k_descale * (q . k_stored), v_descale multiplies the normalised output
     once.  Other float8 dtypes raise NotImplementedError, scales without e4m3 pools and e4m3 pools without block_table RuntimeError.
-    See fa_ex_forward_varlen_paged_fp8."""
+    See fa_ex_forward_varlen_paged_fp8.
+    Without block_table v may be narrower than q and k, (total_k, H_kv, d_v) as in ex_forward (fa_ex_forward_varlen_vdim): o is
+    (total_q, H_q, d_v); dropout_p, window_size, softcap, alibi_slopes, sinks, block_table and k_descale / v_descale then raise
+    NotImplementedError with the name.  The heads of v must be adjacent at stride d_v (as k's at d): a slice of a wider projection
+    whose head stride is not d_v raises RuntimeError like any k the library cannot take without a copy."""
     who = "ex_varlen_forward"
     wl, wr = window_arg(who, window)
     cap = softcap_arg(who, softcap)
+    if isinstance(k, torch.Tensor) and isinstance(v, torch.Tensor) and isinstance(q, torch.Tensor) and k.dim() == v.dim() and \
+            k.dim() in (3, 4) and v.shape[:-1] == k.shape[:-1] and v.shape[-1] != k.shape[-1]:
+        # a v of its own width goes with neither a paged cache nor an e4m3 one: refused by name, before the checks of those paths
+        vdim_arg(who, k.shape[-1], v.shape[-1], q.dtype, block_table=block_table is not None, k_descale=k_descale is not None,
+                 v_descale=v_descale is not None)
     if block_table is not None:
         return _varlen_paged_forward(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale,
                                      dropout_p, wl, wr, cap, alibi_slopes, sinks, block_table, k_descale, v_descale)
@@ -762,12 +811,14 @@ def ex_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seq
     d = q.shape[2]
     aptr, _h, astride, alibi_slopes = alibi_arg(who, alibi_slopes, q.device, b * hq, heads=hq)
     sptr, sheads, sinks = sinks_arg(who, sinks, q.device, b * hq, heads=hq)
+    d_v = vdim_arg(who, d, v.shape[2], q.dtype, dropout_p=dropout_p > 0.0, window_size=(wl, wr) != (-1, -1), softcap=cap > 0.0,
+                   alibi_slopes=aptr, sinks=sptr, k_descale=k_descale is not None, v_descale=v_descale is not None)
     with torch.cuda.device(q.device):
-        o = torch.empty((total_q, hq, d), dtype=q.dtype, device=q.device)
+        o = torch.empty((total_q, hq, v.shape[2]), dtype=q.dtype, device=q.device)
         lse = torch.empty((hq, total_q), dtype=torch.float32, device=q.device)
-        _call("fa_ex_forward_varlen" + _ex_variant(sptr, cap > 0.0 or aptr, False), (
+        _call("fa_ex_forward_varlen" + _ex_variant(sptr, cap > 0.0 or aptr, False, vdim=d_v), (
             q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr(), *dims,
-            int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, astride, sptr, sheads, float(dropout_p),
+            int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, astride, sptr, sheads, *((d_v,) if d_v else ()), float(dropout_p),
             int(seed) & (2 ** 64 - 1), _stream_ptr(q.device)))
     return o, lse
 
@@ -776,7 +827,8 @@ def ex_varlen_backward(q, k, v, o, do_, lse, cu_seqlens_q, cu_seqlens_k, max_seq
                        dropout_p=0.0, seed=0, window=(-1, -1), softcap=0.0, alibi_slopes=None, *, dlse=None, sinks=None):
     """(dq, dk, dv) of ex_varlen_forward: dq in q's (total_q, H_q, d) shape, dk and dv in k's and v's (dense); with sinks also
     dsinks, float32 (H_q,), as a fourth result.  dlse: the gradient of lse, float32 (H_q, total_q), or None
-    (fa_ex_backward_varlen_dlse)."""
+    (fa_ex_backward_varlen_dlse).  With a v of its own width o and do_ are (total_q, H_q, d_v) and dv is (total_k, H_kv, d_v)
+    (fa_ex_backward_varlen_vdim)."""
     who = "ex_varlen_backward"
     wl, wr = window_arg(who, window)
     cap = softcap_arg(who, softcap)
@@ -784,9 +836,11 @@ def ex_varlen_backward(q, k, v, o, do_, lse, cu_seqlens_q, cu_seqlens_k, max_seq
     b, hq, hkv, total_q, total_k, _mq, _mk, d, code = dims[:9]
     aptr, _h, astride, alibi_slopes = alibi_arg(who, alibi_slopes, q.device, b * hq, heads=hq)
     sptr, sheads, sinks = sinks_arg(who, sinks, q.device, b * hq, heads=hq)
+    d_v = vdim_arg(who, d, v.shape[2], q.dtype, dropout_p=dropout_p > 0.0, window_size=(wl, wr) != (-1, -1), softcap=cap > 0.0,
+                   alibi_slopes=aptr, sinks=sptr)
     for name, t in (("o", o), ("do", do_)):
-        if not t.is_cuda or t.shape != (total_q, hq, d) or t.dtype != q.dtype:
-            raise RuntimeError(f"{who}: {name} must be a (total_q, H_q, d) device tensor of q's dtype")
+        if not t.is_cuda or t.shape != (total_q, hq, v.shape[2]) or t.dtype != q.dtype:
+            raise RuntimeError(f"{who}: {name} must be a (total_q, H_q, d_v) device tensor of q's dtype (d_v: v's width)")
     if not lse.is_cuda or lse.shape != (hq, total_q) or lse.dtype != torch.float32:
         raise RuntimeError(f"{who}: lse must be a (H_q, total_q) float32 device tensor")
     dlse = _dlse_arg(who, dlse, lse, "(H_q, total_q)")
@@ -794,15 +848,16 @@ def ex_varlen_backward(q, k, v, o, do_, lse, cu_seqlens_q, cu_seqlens_k, max_seq
     with torch.cuda.device(q.device):
         dq = torch.empty((total_q, hq, d), dtype=q.dtype, device=q.device)
         dk = torch.empty((total_k, hkv, d), dtype=q.dtype, device=q.device)
-        dv = torch.empty((total_k, hkv, d), dtype=q.dtype, device=q.device)
+        dv = torch.empty((total_k, hkv, v.shape[2]), dtype=q.dtype, device=q.device)
         nbytes = int(_lib.fa_ex_backward_workspace_bytes_varlen(hq, hkv, total_q, total_k, d, code))
         ws = _workspace(q.device, nbytes)
         nbytes = max(nbytes, 0 if torch.cuda.is_current_stream_capturing() else _workspaces.capacity(q.device, _stream_ptr(q.device)))
         dsinks = torch.empty((sheads,), dtype=torch.float32, device=q.device) if sptr else None
-        _call("fa_ex_backward_varlen" + _ex_variant(sptr, cap > 0.0 or aptr, False, False, dlse is not None), (
+        _call("fa_ex_backward_varlen" + _ex_variant(sptr, cap > 0.0 or aptr, False, False, dlse is not None, vdim=d_v), (
             q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do_.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
             dv.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr(), *dims, int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, astride,
-            sptr, sheads, _ptr(dsinks), _ptr(dlse), float(dropout_p), int(seed) & (2 ** 64 - 1), ws.data_ptr(), nbytes, _stream_ptr(q.device)))
+            sptr, sheads, _ptr(dsinks), _ptr(dlse), *((d_v,) if d_v else ()), float(dropout_p), int(seed) & (2 ** 64 - 1), ws.data_ptr(), nbytes,
+            _stream_ptr(q.device)))
     return (dq, dk, dv, dsinks) if sptr else (dq, dk, dv)
 
 

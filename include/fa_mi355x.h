@@ -539,6 +539,56 @@ int fa_ex_backward_varlen_dlse(const void* q, const void* k, const void* v, cons
                                const float* alibi_slopes, int64_t alibi_batch_stride, const float* sinks, int64_t sink_heads,
                                float* dsinks, const float* dlse, double dropout_p, uint64_t dropout_seed, void* workspace,
                                size_t workspace_bytes, void* stream);
+/* --- V narrower than Q and K: attention whose q, k (dq, dk) are d wide while v, o, do_ (dv) are d_v wide, as FlashAttention-2
+ * (>= 2.7, head dim 192 / 128) and FlashAttention-3 take it.  DeepSeek-style multi-head latent attention before weight absorption,
+ * in training and prefill: d = 192 (128 nope + 64 rope), d_v = 128.  One argument, d_v, after the sink group (forward) and after
+ * dlse (backward), in front of the masks / dropout group; the remaining arguments are those of fa_ex_forward_sink /
+ * fa_ex_backward_dlse / fa_ex_forward_varlen_sink / fa_ex_backward_varlen_dlse.  d_v = 0 and d_v = d are exactly that call: the same
+ * checks, the same launches, the same bits.
+ *   Layout with d_v != d: q, dq (BH, Nq, d); k, dk (BH / kv_group, Nk, d); v, dv (BH / kv_group, Nk, d_v); o, do_ (BH, Nq, d_v);
+ *   lse, dlse (BH, Nq).  Packed: q (total_q, heads_q, d) at q_stride, k (total_k, heads_kv, d) at k_stride, v (total_k, heads_kv, d_v)
+ *   at v_stride >= heads_kv * d_v; o, do_ dense (total_q, heads_q, d_v); dq dense (total_q, heads_q, d); dk dense (total_k, heads_kv, d),
+ *   dv dense (total_k, heads_kv, d_v); lse, dlse (heads_q, total_q).  The heads of a tensor stay adjacent at its own width.
+ *   softmax_scale is the caller's (FlashAttention's default is d^-1/2 with q's width: 192^-1/2 for MLA).
+ * Supported: f16 / bf16, d % 8 == 0, d_v % 8 == 0, 8 <= d_v < d <= 192, d_v <= 128, softmax_scale > 0, 16-byte aligned tensors, token
+ * strides that are multiples of 8; causal (bottom-right aligned), kv_group, cu_seqlens (clamped in the kernels as in
+ * fa_ex_forward_varlen: no host read, no synchronisation), lse and dlse.  Kernels of their own on the 16-bit MFMA
+ * (fa_ex_mfma_vdim.hip), one instantiation at 192 + 128 into which narrower widths are zero-padded; deterministic, no atomics.
+ * Refused before any other check and before any HIP call, the first broken rule in this order, each with a text of its own:
+ * d_v < 0 (FA_ERR_INVALID_ARGUMENT); then FA_ERR_UNSUPPORTED for d_v > d; d or d_v not a multiple of 8; d > 192; d_v > 128; f32
+ * tensors; then by name mask, block_sparse_mask, dropout_p > 0, window_size (window_left / window_right other than -1), softcap,
+ * alibi_slopes, sinks; then softmax_scale <= 0.  (The paged forward, fa_ex_forward_varlen_paged*, has no d_v.)
+ * Workspace of the backward: two float rows per query row as without d_v, plus for kv_group > 1 (heads_q > heads_kv) the per-query-head
+ * dK / dV partials, summed per group at each tensor's own width.  fa_ex_backward_workspace_bytes_grouped(bh, kv_group, nq, nk, d, dtype)
+ * and fa_ex_backward_workspace_bytes_varlen(heads_q, heads_kv, total_q, total_k, d, dtype) with q's width d answer for a d_v call as
+ * they stand (the dV slab is sized like dK's): there is no query of its own. */
+int fa_ex_forward_vdim(const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t kv_group, int64_t nq,
+                       int64_t nk, int64_t d, int dtype, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                       double softcap, const float* alibi_slopes, int64_t alibi_heads, int64_t alibi_batch_stride, const float* sinks,
+                       int64_t sink_heads, int64_t d_v, const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask, int64_t br,
+                       int64_t bc, double dropout_p, uint64_t dropout_seed, void* stream);
+int fa_ex_backward_vdim(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
+                        void* dv, int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype, int causal,
+                        int64_t window_left, int64_t window_right, double softmax_scale, double softcap, const float* alibi_slopes,
+                        int64_t alibi_heads, int64_t alibi_batch_stride, const float* sinks, int64_t sink_heads, float* dsinks,
+                        const float* dlse, int64_t d_v, const uint8_t* mask, int64_t mask_bh_stride, const uint8_t* block_mask,
+                        int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* workspace, size_t workspace_bytes,
+                        void* stream);
+int fa_ex_forward_varlen_vdim(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_seqlens_q,
+                              const int32_t* cu_seqlens_k, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
+                              int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride,
+                              int64_t k_stride, int64_t v_stride, int causal, int64_t window_left, int64_t window_right,
+                              double softmax_scale, double softcap, const float* alibi_slopes, int64_t alibi_batch_stride,
+                              const float* sinks, int64_t sink_heads, int64_t d_v, double dropout_p, uint64_t dropout_seed,
+                              void* stream);
+int fa_ex_backward_varlen_vdim(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq,
+                               void* dk, void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch,
+                               int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q,
+                               int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                               int causal, int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
+                               const float* alibi_slopes, int64_t alibi_batch_stride, const float* sinks, int64_t sink_heads,
+                               float* dsinks, const float* dlse, int64_t d_v, double dropout_p, uint64_t dropout_seed,
+                               void* workspace, size_t workspace_bytes, void* stream);
 /* --- The varlen forward over a paged K/V cache: FlashAttention-2's flash_attn_varlen_func(..., block_table=).  Chunked prefill, or
  * prefill behind a shared prefix, reads its keys straight from the pools of the KV-cache calls, without a gathered copy and on the
  * kernel that reads a sequence's keys once per 256 query rows.  Forward only, no dropout.  The arguments are those of
