@@ -559,3 +559,87 @@ def flash_mla_sparse_attn(q, qv, k_cache, v_cache, indices, *, cache_seqlens=Non
         o, lse = ext.ex_mla_sparse_forward(q.detach(), qv.detach(), k_cache, v_cache, indices, cache_seqlens, bool(causal), softmax_scale,
                                            block_table, cache_batch_idx, num_splits)
     return (o, lse) if return_softmax_lse else o
+
+
+def mla_fp8_pack_cache(latent_new, rope_new, kv_cache, cache_seqlens, block_table, *, scale_pow2=False):
+    """Quantise new MLA tokens and append them to a packed 8-bit latent cache, in place: the write side of
+    flash_mla_with_kvcache(..., is_fp8_kvcache=True).  latent_new (B, N_new, 512) and rope_new (B, N_new, 64) bfloat16 on the GPU
+    (the two column ranges of one (B, N_new, 576) tensor are used as they are; rotate the rope part first, with rotary_apply);
+    kv_cache (num_blocks, page_block_size, 1, 656) torch.uint8 or torch.float8_e4m3fn, FlashMLA's token:
+        byte 0 .. 511: 512 e4m3, quantised per 128-wide tile | 512 .. 527: 4 float32 scales | 528 .. 655: 64 bfloat16, as they are
+    Token i of sequence b goes to position cache_seqlens[b] + i (cache_seqlens: int32 (B,) lengths before the append, or an int;
+    not modified) through block_table (int32 (B, max_blocks_per_seq)).  Per tile, in fp32: scale = amax / 448 (1 for an all-zero
+    tile; scale_pow2: rounded up to a power of two, FlashMLA's ue8m0 option), byte = e4m3(clamp(x / scale, +-448)), round to
+    nearest even.  Neither array is read on the host: a negative length, a position past the table's capacity or a page outside
+    the pool drops that token, and the call can be captured in a graph.  Two tokens on one slot, or a NaN / infinity in a tile,
+    are undefined (nothing is written out of bounds).  Wrong dtypes raise NotImplementedError with the name, wrong shapes and
+    devices RuntimeError, a cache view that would need a copy ValueError.  Returns None.  No gradient."""
+    import flashattention_lab_cuda as ext
+
+    with torch.no_grad():
+        ext.ex_mla_fp8_pack(latent_new.detach() if isinstance(latent_new, torch.Tensor) else latent_new,
+                            rope_new.detach() if isinstance(rope_new, torch.Tensor) else rope_new, kv_cache, cache_seqlens, block_table,
+                            bool(scale_pow2))
+
+
+def flash_mla_with_kvcache(q, k_cache, block_table, cache_seqlens, head_dim_v=512, *, softmax_scale=None, causal=False,
+                           is_fp8_kvcache=False, indices=None, num_splits=0):
+    """FlashMLA's flash_mla_with_kvcache (its argument order): multi-head latent attention at decode time over a paged cache of
+    576-wide tokens [latent 512 | rotary 64].  q (B, Nq, H_q, 576) in the same layout: q[..., :512] meets the latent (which is
+    also the value), q[..., 512:] the rotary part; block_table int32 (B, max_blocks_per_seq), cache_seqlens int32 (B,) on the
+    device (or an int, or None: the capacity); indices None, or int32 (B, Nq, topk) token positions per query token (sparse
+    attention: flash_mla_sparse_attn's rules).  softmax_scale defaults to 576 ** -0.5.
+    is_fp8_kvcache=False: k_cache (num_blocks, page_block_size, 1, 576) in q's dtype (bfloat16 / float16); the call is
+    flash_attn_with_kvcache(q[..., 512:], k_cache[..., 512:], k_cache[..., :512], qv=q[..., :512], ...) — with indices
+    flash_mla_sparse_attn on the same views — and gives those calls' bits.
+    is_fp8_kvcache=True: k_cache (num_blocks, page_block_size, 1, 656) torch.uint8 or torch.float8_e4m3fn, read as bytes: 512 e4m3
+    | 4 float32 scales, one per 128-wide tile | 64 bfloat16 (mla_fp8_pack_cache writes it); q bfloat16, used without a copy.  A
+    latent element is bfloat16(float(e4m3) * scale), rounded once, and the result is, to the bit, the 16-bit call's on these
+    values.  0.57 of the 16-bit cache's bytes a token.
+    head_dim_v other than 512 and wrong dtypes raise NotImplementedError with the name, wrong shapes and devices RuntimeError.
+    Returns (o (B, Nq, H_q, 512), lse (B, H_q, Nq) float32).  No gradient."""
+    who = "flash_mla_with_kvcache"
+    if head_dim_v != 512:
+        raise NotImplementedError(f"{who}: head_dim_v = {head_dim_v} is not supported (512 expected)")
+    if not isinstance(q, torch.Tensor) or q.dtype not in (torch.bfloat16, torch.float16):
+        dt = q.dtype if isinstance(q, torch.Tensor) else type(q).__name__
+        raise NotImplementedError(f"{who}: q of dtype {dt} is not supported (bfloat16 or float16 expected)")
+    if is_fp8_kvcache and q.dtype != torch.bfloat16:
+        raise NotImplementedError(f"{who}: q of dtype {q.dtype} is not supported with is_fp8_kvcache (bfloat16 expected: the rotary part "
+                                  f"of a packed token is bfloat16)")
+    want = (torch.uint8, torch.float8_e4m3fn) if is_fp8_kvcache else (q.dtype,)
+    if not isinstance(k_cache, torch.Tensor) or k_cache.dtype not in want:
+        dt = k_cache.dtype if isinstance(k_cache, torch.Tensor) else type(k_cache).__name__
+        raise NotImplementedError(f"{who}: k_cache of dtype {dt} is not supported ({' or '.join(str(w) for w in want)} expected with "
+                                  f"is_fp8_kvcache={bool(is_fp8_kvcache)})")
+    for name, val in (("block_table", block_table), ("indices", indices)):
+        if (val is not None or name == "block_table") and not (isinstance(val, torch.Tensor) and val.dtype == torch.int32):
+            dt = val.dtype if isinstance(val, torch.Tensor) else type(val).__name__
+            raise NotImplementedError(f"{who}: {name} of dtype {dt} is not supported (int32 tensor expected)")
+    if isinstance(cache_seqlens, torch.Tensor) and cache_seqlens.dtype != torch.int32:
+        raise NotImplementedError(f"{who}: cache_seqlens of dtype {cache_seqlens.dtype} is not supported (int32 tensor expected)")
+    if not q.is_cuda or not k_cache.is_cuda:
+        raise RuntimeError(f"{who}: q and k_cache must be GPU (HIP device) tensors; there is no CPU path")
+    if q.dim() != 4 or q.shape[3] != 576:
+        raise RuntimeError(f"{who}: q must be (B, Nq, H_q, 576), got {tuple(q.shape)}")
+    width = 656 if is_fp8_kvcache else 576
+    if k_cache.dim() != 4 or k_cache.shape[2:] != (1, width):
+        raise RuntimeError(f"{who}: k_cache must be (num_blocks, page_block_size, 1, {width}) with is_fp8_kvcache={bool(is_fp8_kvcache)}, "
+                           f"got {tuple(k_cache.shape)}")
+    if indices is not None and (indices.dim() != 3 or indices.shape[:2] != q.shape[:2]):
+        raise RuntimeError(f"{who}: indices must be an int32 (B, Nq, topk) tensor, got {tuple(indices.shape)}")
+    import flashattention_lab_cuda as ext
+
+    scale = 576 ** -0.5 if softmax_scale is None else softmax_scale
+    q = q.detach()
+    with torch.no_grad():
+        if is_fp8_kvcache:
+            return ext.ex_mla_fp8_forward(q[..., 512:], q[..., :512], k_cache, block_table, cache_seqlens, indices, bool(causal), scale,
+                                          num_splits)
+        if indices is not None:
+            return flash_mla_sparse_attn(q[..., 512:], q[..., :512], k_cache[..., 512:], k_cache[..., :512], indices,
+                                         cache_seqlens=cache_seqlens, block_table=block_table, softmax_scale=scale, causal=causal,
+                                         num_splits=num_splits, return_softmax_lse=True)
+        return flash_attn_with_kvcache(q[..., 512:], k_cache[..., 512:], k_cache[..., :512], cache_seqlens=cache_seqlens,
+                                       block_table=block_table, softmax_scale=scale, causal=causal, num_splits=num_splits,
+                                       return_softmax_lse=True, qv=q[..., :512])

@@ -1931,6 +1931,189 @@ int fa_mla_sparse_forward(const void* q, const void* qv, const void* k_cache, co
     return mla_sparse_impl("fa_mla_sparse_forward", c);
 }
 
+// ---- MLA decoding from the packed 8-bit latent cache, and the append into it: see include/fa_mi355x.h
+static int64_t mla_fp8_splits(int64_t batch, int64_t hq, int64_t hkv, int64_t nq, int64_t capacity, int64_t topk, bool sparse, int64_t num_splits) {
+    return sparse ? mla_sparse_splits(batch, hq, hkv, nq, topk, num_splits) : kv_splits_qv(batch, hq, hkv, nq, capacity, num_splits);
+}
+
+size_t fa_mla_fp8_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t topk,
+                                  int with_indices, int64_t num_splits) {
+    if (batch <= 0 || heads_q <= 0 || heads_kv != 1 || seqlen_q <= 0 || cache_len < 0 || topk < 0 || (!with_indices && topk != 0) ||
+        num_splits < 0 || num_splits > 256)
+        return 0;
+    return fa::kv_workspace_bytes(1, heads_q, batch * seqlen_q, 512,
+                                  (int)mla_fp8_splits(batch, heads_q, heads_kv, seqlen_q, cache_len, topk, with_indices != 0, num_splits));
+}
+
+static const int64_t kF8TokenBytes = 656;
+
+// the rules of a packed pool's geometry that fa_mla_fp8_forward and fa_mla_fp8_pack share: the two byte strides, then the pages
+static int mla_fp8_pool_ok(const char* who, const void* pool, int64_t page_stride_bytes, int64_t token_stride_bytes, int64_t page_block_size) {
+    if (token_stride_bytes < kF8TokenBytes || token_stride_bytes % 16 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: token_stride_bytes must be >= 656 and a multiple of 16 (got %lld)", who,
+                    (long long)token_stride_bytes);
+    if (token_stride_bytes >= ((int64_t)1 << 31))
+        return fail(FA_ERR_UNSUPPORTED, "%s: token_stride_bytes = %lld is beyond 32-bit offsets", who, (long long)token_stride_bytes);
+    const int64_t span = (page_block_size > 0 ? page_block_size - 1 : 0) * token_stride_bytes + kF8TokenBytes;
+    if (page_stride_bytes < span || page_stride_bytes % 16 != 0 || page_stride_bytes > ((int64_t)1 << 44))
+        return fail(FA_ERR_INVALID_ARGUMENT,
+                    "%s: page_stride_bytes must be >= (page_block_size - 1) * token_stride_bytes + 656 = %lld and a multiple of 16 (got %lld)", who,
+                    (long long)span, (long long)page_stride_bytes);
+    if (!aligned16({pool})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: kv_cache must be 16-byte aligned", who);
+    return FA_OK;
+}
+
+static int mla_fp8_pages_ok(const char* who, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq) {
+    if (page_block_size < 16 || page_block_size % 16 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: page_block_size must be a positive multiple of 16 (got %lld)", who, (long long)page_block_size);
+    if (num_blocks < 1 || num_blocks > 0x7fffffff)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_blocks must lie in [1, 2^31) (got %lld)", who, (long long)num_blocks);
+    if (max_blocks_per_seq < 1)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: max_blocks_per_seq must be >= 1 (got %lld)", who, (long long)max_blocks_per_seq);
+    if (max_blocks_per_seq > ((int64_t)1 << 28) / page_block_size)
+        return fail(FA_ERR_UNSUPPORTED, "%s: capacity max_blocks_per_seq * page_block_size = %lld * %lld is beyond 2^28 tokens", who,
+                    (long long)max_blocks_per_seq, (long long)page_block_size);
+    if (block_table_row_stride < max_blocks_per_seq || block_table_row_stride > ((int64_t)1 << 40))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: block_table_row_stride=%lld must be >= max_blocks_per_seq=%lld (and <= 2^40)", who,
+                    (long long)block_table_row_stride, (long long)max_blocks_per_seq);
+    return FA_OK;
+}
+
+// The checks, in the order the header documents: (0) the shape's signs and the empty call; (1) null pointers; (2) widths; (3) dtype,
+// heads_kv, block_table, then the ranges of the shape; (4) strides and alignment of q and qv, then the pool's; (5) indices; (6) the
+// page geometry; (7) the workspace.
+int fa_mla_fp8_forward(const void* q, const void* qv, const void* kv_cache, const int32_t* indices, const int32_t* cache_seqlens,
+                       const int32_t* block_table, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q,
+                       int64_t topk, int64_t d, int64_t d_v, int dtype, int64_t q_batch_stride, int64_t q_token_stride, int64_t q_head_stride,
+                       int64_t qv_batch_stride, int64_t qv_token_stride, int64_t qv_head_stride, int64_t page_stride_bytes, int64_t token_stride_bytes,
+                       int64_t indices_batch_stride, int64_t indices_token_stride, int64_t block_table_row_stride, int64_t num_blocks,
+                       int64_t page_block_size, int64_t max_blocks_per_seq, int causal, double softmax_scale, int64_t num_splits,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "fa_mla_fp8_forward";
+    if (batch < 0 || seqlen_q < 0 || heads_q < 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch, seqlen_q and heads_q must be >= 0 (got %lld, %lld, %lld)", who, (long long)batch,
+                    (long long)seqlen_q, (long long)heads_q);
+    if (batch == 0 || seqlen_q == 0 || heads_q == 0) return FA_OK;   // no row: no launch
+    // (1)
+    if (!q || !qv || !kv_cache || !o || !lse) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    // (2)
+    if (d != 64 || d_v != 512)
+        return fail(FA_ERR_UNSUPPORTED, "%s: supported for head_dim = 64 with d_v = 512 only (got head_dim = %lld, d_v = %lld)", who,
+                    (long long)d, (long long)d_v);
+    // (3)
+    if (dtype == FA_DTYPE_F16)
+        return fail(FA_ERR_UNSUPPORTED, "%s: f16 is not supported: the rotary part of a packed token is bf16, and so are q, qv and o", who);
+    if (dtype != FA_DTYPE_BF16) return fail(FA_ERR_INVALID_ARGUMENT, "%s: dtype must be bf16 (got code %d)", who, dtype);
+    if (heads_kv != 1)
+        return fail(FA_ERR_UNSUPPORTED, "%s: heads_kv must be 1: a packed token holds one latent row (got %lld)", who, (long long)heads_kv);
+    if (!block_table) return fail(FA_ERR_INVALID_ARGUMENT, "%s: block_table is required: the packed cache is a paged pool", who);
+    if (!(softmax_scale == softmax_scale) || softmax_scale - softmax_scale != 0.0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale must be finite (got %g)", who, softmax_scale);
+    if (!scale_ok(softmax_scale)) return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale must be > 0 (got %g)", who, softmax_scale);
+    if (num_splits < 0 || num_splits > 256)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_splits must lie in [0, 256] (got %lld)", who, (long long)num_splits);
+    // (dense: the row tiles along grid y, the sequences along z; lists: one per grid column)
+    if (batch > 0x7fffffff / seqlen_q || heads_q > 65535 || seqlen_q > ((int64_t)1 << 24) || batch * seqlen_q * heads_q >= ((int64_t)1 << 31) ||
+        (!indices && (batch > 65535 || (heads_q * seqlen_q + 15) / 16 > 65535)))
+        return fail(FA_ERR_UNSUPPORTED, "%s: problem too large for one launch", who);
+    // (4)
+    struct { const char* name; int64_t bs, ts, hs, w; } st[2] = {{"q", q_batch_stride, q_token_stride, q_head_stride, d},
+                                                                {"qv", qv_batch_stride, qv_token_stride, qv_head_stride, d_v}};
+    for (auto& t : st) {
+        if (t.hs < t.w || t.hs > ((int64_t)1 << 20))
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: head stride of %s must lie in [%lld, 2^20] (got %lld)", who, t.name, (long long)t.w,
+                        (long long)t.hs);
+        const int64_t tok = (heads_q - 1) * t.hs + t.w, span = (seqlen_q - 1) * t.ts + tok;
+        if (t.ts < tok || (batch > 1 && t.bs < span) || t.bs < 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of %s too small (batch %lld, token %lld; need token >= %lld, batch >= %lld)",
+                        who, t.name, (long long)t.bs, (long long)t.ts, (long long)tok, (long long)span);
+        if (t.ts % 8 != 0 || t.bs % 8 != 0 || t.hs % 8 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of %s must be multiples of 8 elements", who, t.name);
+        if (span * 2 >= ((int64_t)1 << 31) || t.bs > ((int64_t)1 << 44))
+            return fail(FA_ERR_UNSUPPORTED, "%s: one batch element of %s spans %lld bytes, beyond 32-bit offsets", who, t.name,
+                        (long long)(span * 2));
+    }
+    if (int rc = mla_fp8_pool_ok(who, kv_cache, page_stride_bytes, token_stride_bytes, page_block_size)) return rc;
+    if (!aligned16({q, qv, o})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: tensors must be 16-byte aligned", who);
+    if ((uintptr_t)lse % 4 != 0 || (uintptr_t)indices % 4 != 0 || (uintptr_t)cache_seqlens % 4 != 0 || (uintptr_t)block_table % 4 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: lse, indices, cache_seqlens and block_table must be 4-byte aligned", who);
+    // (5) a list is topk adjacent entries, one list a query token
+    if (indices) {
+        if (topk < 0 || topk > ((int64_t)1 << 30))
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: topk must lie in [0, 2^30] (got %lld)", who, (long long)topk);
+        const int64_t kIxMax = (int64_t)1 << 40;
+        const int64_t ix_seq = (seqlen_q - 1) * indices_token_stride + topk;
+        if ((seqlen_q > 1 && indices_token_stride < topk) || indices_token_stride < 0 || indices_token_stride > kIxMax ||
+            (batch > 1 && indices_batch_stride < ix_seq) || indices_batch_stride < 0 || indices_batch_stride > kIxMax)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of indices (batch %lld, token %lld): token >= topk = %lld, batch >= %lld (each <= 2^40)",
+                        who, (long long)indices_batch_stride, (long long)indices_token_stride, (long long)topk, (long long)ix_seq);
+    } else if (topk != 0 || indices_batch_stride != 0 || indices_token_stride != 0) {
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: topk, indices_batch_stride and indices_token_stride must be 0 without indices", who);
+    }
+    // (6)
+    if (int rc = mla_fp8_pages_ok(who, block_table_row_stride, num_blocks, page_block_size, max_blocks_per_seq)) return rc;
+    const int64_t capacity = max_blocks_per_seq * page_block_size;
+    // (7)
+    const int64_t S = mla_fp8_splits(batch, heads_q, heads_kv, seqlen_q, capacity, topk, indices != nullptr, num_splits);
+    if (S > 1 && batch * seqlen_q * heads_q >= ((int64_t)1 << 26))   // the combine: one wave per row, 2^32 lanes per launch
+        return fail(FA_ERR_UNSUPPORTED, "%s: batch * seqlen_q * heads_q = %lld rows are too many to combine %lld splits in one launch", who,
+                    (long long)(batch * seqlen_q * heads_q), (long long)S);
+    const size_t need = fa::kv_workspace_bytes(1, heads_q, batch * seqlen_q, d_v, (int)S);
+    if (workspace_bytes < need || (need > 0 && !workspace))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
+    if (need > 0 && !aligned16({workspace})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
+    fa::MlaF8Args a{};
+    fa::KvArgs& kv = a.sa.kv;
+    kv.q = q; kv.qv = qv; kv.o = o; kv.lse = lse;
+    kv.cache_seqlens = cache_seqlens; kv.block_table = block_table;
+    kv.table_row_stride = block_table_row_stride; kv.num_blocks = num_blocks; kv.page_size = page_block_size;
+    kv.batch = batch; kv.heads_q = heads_q; kv.heads_kv = heads_kv; kv.seqlen_q = seqlen_q; kv.cache_len = capacity;
+    kv.d = d; kv.d_v = d_v; kv.dtype = dtype; kv.causal = causal ? 1 : 0;
+    kv.q_bs = q_batch_stride; kv.q_ts = q_token_stride; kv.qv_bs = qv_batch_stride; kv.qv_ts = qv_token_stride;
+    kv.window_left = kv.window_right = -1;
+    kv.scale = (float)softmax_scale; kv.num_splits = S; kv.workspace = workspace;
+    a.sa.indices = indices; a.sa.ix_bs = indices_batch_stride; a.sa.ix_ts = indices_token_stride; a.sa.ix_hs = 0; a.sa.topk = topk;
+    a.pool = kv_cache; a.page_sb = page_stride_bytes; a.tok_sb = token_stride_bytes;
+    a.q_hs = q_head_stride; a.qv_hs = qv_head_stride;
+    return launched(who, fa::launch_mla_f8(a, reinterpret_cast<hipStream_t>(stream)));
+}
+
+int fa_mla_fp8_pack(const void* latent_new, const void* rope_new, void* kv_cache, const int32_t* cache_seqlens, const int32_t* block_table,
+                    int64_t batch, int64_t seqlen_new, int64_t latent_batch_stride, int64_t latent_token_stride, int64_t rope_batch_stride,
+                    int64_t rope_token_stride, int64_t page_stride_bytes, int64_t token_stride_bytes, int64_t block_table_row_stride,
+                    int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq, int scale_pow2, void* stream) {
+    const char* who = "fa_mla_fp8_pack";
+    if (batch < 0 || seqlen_new < 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch and seqlen_new must be >= 0 (got %lld, %lld)", who, (long long)batch, (long long)seqlen_new);
+    if (batch == 0 || seqlen_new == 0) return FA_OK;   // no token: no launch
+    if (!latent_new || !rope_new || !kv_cache || !cache_seqlens || !block_table) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    if (batch > 0x7fffffff / seqlen_new) return fail(FA_ERR_UNSUPPORTED, "%s: problem too large for one launch", who);
+    struct { const char* name; int64_t bs, ts, w; } st[2] = {{"latent_new", latent_batch_stride, latent_token_stride, 512},
+                                                            {"rope_new", rope_batch_stride, rope_token_stride, 64}};
+    for (auto& t : st) {
+        const int64_t span = (seqlen_new - 1) * t.ts + t.w;
+        if (t.ts < t.w || (batch > 1 && t.bs < span) || t.bs < 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of %s too small (batch %lld, token %lld; need token >= %lld, batch >= %lld)",
+                        who, t.name, (long long)t.bs, (long long)t.ts, (long long)t.w, (long long)span);
+        if (t.ts % 8 != 0 || t.bs % 8 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of %s must be multiples of 8 elements", who, t.name);
+        if (t.ts > ((int64_t)1 << 31) || t.bs > ((int64_t)1 << 44))
+            return fail(FA_ERR_UNSUPPORTED, "%s: strides of %s beyond 2^31 (token) or 2^44 (batch) elements", who, t.name);
+    }
+    if (int rc = mla_fp8_pool_ok(who, kv_cache, page_stride_bytes, token_stride_bytes, page_block_size)) return rc;
+    if (!aligned16({latent_new, rope_new})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: tensors must be 16-byte aligned", who);
+    if ((uintptr_t)cache_seqlens % 4 != 0 || (uintptr_t)block_table % 4 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_seqlens and block_table must be 4-byte aligned", who);
+    if (int rc = mla_fp8_pages_ok(who, block_table_row_stride, num_blocks, page_block_size, max_blocks_per_seq)) return rc;
+    fa::MlaF8PackArgs a{};
+    a.latent = latent_new; a.rope = rope_new; a.pool = kv_cache; a.cache_seqlens = cache_seqlens; a.block_table = block_table;
+    a.batch = batch; a.seqlen_new = seqlen_new; a.lat_bs = latent_batch_stride; a.lat_ts = latent_token_stride;
+    a.rope_bs = rope_batch_stride; a.rope_ts = rope_token_stride; a.page_sb = page_stride_bytes; a.tok_sb = token_stride_bytes;
+    a.table_row_stride = block_table_row_stride; a.num_blocks = num_blocks; a.page_size = page_block_size; a.max_blocks = max_blocks_per_seq;
+    a.scale_pow2 = scale_pow2;
+    return launched(who, fa::launch_mla_f8_pack(a, reinterpret_cast<hipStream_t>(stream)));
+}
+
 // One call of the fa_rotary_apply family, a field per argument under its name in the header.  Defaults: "argument absent".
 struct RotaryCall {
     const void* x = nullptr;

@@ -284,6 +284,28 @@ struct MlaSparseArgs {
 int mla_sparse_num_splits(int64_t units, int64_t heads_kv, int64_t group, int64_t topk);
 hipError_t launch_mla_sparse(const MlaSparseArgs& a, hipStream_t st);
 
+// MLA decoding from the packed 8-bit latent cache (fa_mla.hip; fa_mla_fp8_forward): 656-byte tokens [512 e4m3 | 4 float32 scales,
+// one per 128-wide tile | 64 bf16] in a paged pool, token slot of page pg at pool + pg * page_sb + slot * tok_sb bytes.  sa: the
+// sparse call's arguments with k_cache / v_cache null, bf16, heads_kv = 1 and a block_table; sa.indices null: the dense call
+// (sa.kv as launch_kvcache_mla takes it), else the list call with ix_hs = 0.  Waves, splits and workspace are those calls'.
+struct MlaF8Args {
+    MlaSparseArgs sa;
+    const void* pool;
+    int64_t page_sb, tok_sb;
+    int64_t q_hs, qv_hs;   // head strides of q and qv in elements (>= 64, >= 512)
+};
+hipError_t launch_mla_f8(const MlaF8Args& a, hipStream_t st);
+// the append into that pool (fa_mla_fp8_pack): new token i of sequence b, latent (512) and rope (64) bf16 rows at their batch /
+// token strides in elements, quantised and written at position cache_seqlens[b] + i; both device arrays untrusted
+struct MlaF8PackArgs {
+    const void *latent, *rope;
+    void* pool;
+    const int *cache_seqlens, *block_table;
+    int64_t batch, seqlen_new, lat_bs, lat_ts, rope_bs, rope_ts, page_sb, tok_sb, table_row_stride, num_blocks, page_size, max_blocks;
+    int scale_pow2;
+};
+hipError_t launch_mla_f8_pack(const MlaF8PackArgs& a, hipStream_t st);
+
 // Rotary embedding for training and prefill (fa_rotary.hip; fa_rotary_apply).  16-bit x, y (batch, seqlen, heads, d), heads at
 // stride d, strides multiples of 8 elements, 16-byte aligned; y == x (with x's strides) is the in-place form.  Tables as KvArgs'.
 struct RotaryArgs {

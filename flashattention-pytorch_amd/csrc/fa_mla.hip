@@ -703,4 +703,461 @@ hipError_t launch_kvcache_mla(const KvArgs& a, hipStream_t st) {
     return a.dtype == 1 ? launch_mla_t<f16_tag>(mp, S, (int)a.batch, st) : launch_mla_t<bf16_tag>(mp, S, (int)a.batch, st);
 }
 
+// ---- the packed 8-bit latent cache (fa_mla_fp8_forward, fa_mla_fp8_pack): FlashMLA's 656-byte token
+//   byte 0 .. 511: 512 e4m3 (the latent, quantised per 128-wide tile) | 512 .. 527: 4 float32 scales | 528 .. 655: 64 bf16 (rotary)
+// in a paged pool, token t of sequence b at pool + page * page_sb + (t % ps) * tok_sb bytes (64-bit), one K/V head, bf16 only.
+// mla_f8_kernel<NW, SPARSE> is mla_split_kernel<bf16_tag, NW, true> (SPARSE: mla_sparse_kernel<bf16_tag, NW, true>) with another
+// copy into the same 36 KiB LDS image; from the barrier after the copy on the two are the same text, so a call on a pool gives
+// the bits of the 16-bit call on the pool's dequantised rows.  The copy: row tid / TPR of the tile belongs to TPR = T / 32
+// threads; a thread loads the row's four scales (one 16-byte load) and its 16-byte chunks c = tid % TPR + TPR i of e4m3 (16 head
+// dims of the 128-wide tile c / 8), and writes for each the two MlaSwz chunks 2c, 2c + 1 of
+//   bf16_rne(fp32(e4m3) * scale)    (one exact widening, one fp32 multiply, one rounding to nearest even).
+// The rotary 128 bytes are 8 chunks, copied as there.  A row that is not fetched (its loads are redirected to the first bytes of
+// q and their results selected away, as in the 16-bit kernels: no address is formed from the key) has zero bytes and zero
+// scales: zeros.  Four waves: a thread holds 4 + 1 + 1 chunks of tile t + 1 while tile t is computed on.
+// The text shared with mla_split_kernel / mla_sparse_kernel carries their comments; a change to the loop there belongs here too
+// (tests/test_mla_fp8_gpu.py holds the two to the same bits).
+namespace {
+
+constexpr int kF8Scales = 512, kF8Rope = 528;   // byte offsets in a token (656 bytes)
+
+struct MlaF8Params {
+    MlaSparseParams sp;    // sp.mp.p.kc / vc are not used; sp.idx, topk: SPARSE only
+    const unsigned char* pool;
+    long long page_sb;     // bytes from page to page
+    int tok_sb;            // bytes from token to token of a page
+    int q_hs, qv_hs;       // head strides of q and qv (elements): the two column ranges of one (.., 576) tensor are 576 apart
+};
+
+// 16 e4m3 bytes times one scale -> the two 16-byte chunks of bf16 they fill
+__device__ __forceinline__ void mla_f8_widen(u32x4 x, float sc, u32x4& lo, u32x4& hi) {
+    uint32_t out[8];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)x[d], false);
+        const auto b = __builtin_amdgcn_cvt_pk_f32_fp8((int)x[d], true);
+        out[2 * d] = pack2<bf16_tag>(a[0] * sc, a[1] * sc);
+        out[2 * d + 1] = pack2<bf16_tag>(b[0] * sc, b[1] * sc);
+    }
+    lo = u32x4{out[0], out[1], out[2], out[3]};
+    hi = u32x4{out[4], out[5], out[6], out[7]};
+}
+
+template <int NW, bool SPARSE>
+__global__ __launch_bounds__(64 * NW) void mla_f8_kernel(MlaF8Params fp) {
+    using Tag = bf16_tag;
+    constexpr int KT = kMlaKT, DK = kMlaDk, DV = kMlaDv, NDB = DV / 16, T = 64 * NW;
+    constexpr int TPR = T / KT, FCH = (DV / 16) / TPR, RCH = KT * (DK / 8) / T;   // threads a latent row; 16-byte chunks a thread: e4m3, rotary
+    static_assert(TPR * FCH * 16 == DV && 8 % TPR == 0 && RCH >= 1, "tile copy");
+    __shared__ __attribute__((aligned(16))) char lds[kMlaLdsBytes];
+    char* const lat = lds;
+    char* const rop = lds + kMlaLatBytes;
+    const MlaSparseParams& sp = fp.sp;
+    const KvParams& p = sp.mp.p;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, g = lane >> 4;
+    const int s = SPARSE ? blockIdx.y : blockIdx.x, S = SPARSE ? gridDim.y : gridDim.x;
+    const int wt = SPARSE ? blockIdx.z : blockIdx.y;
+    const int nq = p.nq, b = SPARSE ? blockIdx.x / nq : blockIdx.z;
+    int L_b, P_b;
+    const int lk = kv_len_k(p, b, 0, L_b, P_b);   // (one K/V head: hk = 0 throughout)
+
+    // the positions [kbeg, kend) of this split (keys, SPARSE: list positions), this wave's row tile (none: the wave only
+    // copies), this lane's query row: mla_split_kernel's, SPARSE mla_sparse_kernel's
+    int kbeg, kend, qi, h, rlo = 0, rhi = -1;
+    bool active, valid;
+    unsigned tlim = 0u;
+    if constexpr (SPARSE) {
+        qi = blockIdx.x - b * nq;
+        // visible token positions: [0, tlim)
+        const int thi = sp.causal ? lk - nq + qi : lk - 1;
+        tlim = thi >= 0 ? (unsigned)thi + 1u : 0u;
+        // list positions [kbeg, kend) of split s: whole tiles
+        const int nt = (sp.topk + KT - 1) / KT;
+        kbeg = (int)((long long)s * nt / S) * KT;
+        kend = min(sp.topk, (int)((long long)(s + 1) * nt / S) * KT);
+        // this wave's row tile of the G heads (none: the wave only copies) and this lane's head
+        const int pr0 = 16 * NW * wt + 16 * w, pr = pr0 + r;
+        active = pr0 < p.G;
+        valid = pr < p.G;
+        h = valid ? pr : 0;
+    } else {
+        const int rows = p.rows, coff = lk - nq;
+        // the workgroup's rows [wr0, wr1) and the key range of their bands' union; wr0 < rows by the grid
+        const int wr0 = 16 * NW * wt, wr1 = min(wr0 + 16 * NW, rows);
+        kv_split_range(p, lk, nq, wr0 / p.G, (wr1 - 1) / p.G, s, S, kbeg, kend);
+        // this wave's row tile (none: the wave only copies), this lane's query row and its visible keys [rlo, rhi]
+        const int pr0 = wr0 + 16 * w, pr = pr0 + r;
+        active = pr0 < rows;
+        valid = pr < rows;
+        const int qlo = min(pr0, rows - 1) / p.G;
+        qi = valid ? pr / p.G : qlo;
+        h = valid ? pr - qi * p.G : 0;
+        rlo = max(qi + coff - p.wl, kbeg);
+        rhi = valid ? min(min(qi + coff + p.wr, lk - 1), kend - 1) : -1;
+    }
+
+    s16x8 qf[DK / 32], qvf[DV / 32];
+    {
+        const buf_rsrc_t q_rs = make_rsrc(p.q + b * p.q_bs, (unsigned)(((nq - 1) * p.q_ts + (p.hq - 1) * fp.q_hs + DK) * 2));
+        const buf_rsrc_t qv_rs = make_rsrc(sp.mp.qv + b * sp.mp.qv_bs, (unsigned)(((nq - 1) * sp.mp.qv_ts + (p.hq - 1) * fp.qv_hs + DV) * 2));
+#pragma unroll
+        for (int ks = 0; ks < DK / 32; ++ks) qf[ks] = buf_load_frag(q_rs, valid ? (qi * p.q_ts + h * fp.q_hs + 32 * ks + 8 * g) * 2 : kOobOff);
+#pragma unroll
+        for (int ks = 0; ks < DV / 32; ++ks) qvf[ks] = buf_load_frag(qv_rs, valid ? (qi * sp.mp.qv_ts + h * fp.qv_hs + 32 * ks + 8 * g) * 2 : kOobOff);
+    }
+    const int* tbl = p.table + b * p.tbl_rs;
+
+    // The producer of this lane's key (position + (lane & 31) of a tile).  Dense: kv_split_kernel's page lookup, done by every
+    // wave for itself, the next tile's a tile ahead.  SPARSE: the list pipeline of mla_sparse_kernel: e2 the raw entry of the
+    // tile after next (one coalesced 128-byte read), s1 the next tile's visible entry as its slot in its page pg1, -1 = not
+    // visible: an entry that is not visible is never turned into an address.
+    int j0 = 0, s0 = 0, pg = -1;
+    int e2 = -1, s1 = -1, pg1 = -1;
+    const int* il = nullptr;
+    auto page_of = [&](int jt, int st, int kt) {
+        int j = jt, sl = st + (lane & 31);
+        if (sl >= p.ps) { sl -= p.ps; ++j; }
+        if (sl >= p.ps) ++j;
+        return kt + (lane & 31) < kend ? tbl[j] : -1;
+    };
+    auto entry = [&](int jt) {
+        const int pos = jt + (lane & 31);
+        return pos < kend ? il[pos] : -1;
+    };
+    auto advance = [&](int jt) {   // e2 -> s1, pg1; e2 = the entries of the tile at jt
+        const bool vis = (unsigned)e2 < tlim;
+        const unsigned j = (unsigned)e2 / (unsigned)p.ps;   // (< max_blocks_per_seq: e2 < len_b <= the capacity)
+        s1 = vis ? (int)((unsigned)e2 - j * (unsigned)p.ps) : -1;
+        pg1 = vis ? tbl[j] : -1;
+        e2 = entry(jt);
+    };
+    if constexpr (SPARSE) {
+        il = sp.idx + b * sp.ix_bs + qi * sp.ix_ts;
+        if (kbeg < kend) {
+            e2 = entry(kbeg);
+            advance(kbeg + KT);
+        }
+    } else if (kbeg < kend) {
+        j0 = kbeg / p.ps;
+        s0 = kbeg - j0 * p.ps;
+        pg = page_of(j0, s0, kbeg);
+    }
+
+    f32x4_t oacc[NDB];
+#pragma unroll
+    for (int t = 0; t < NDB; ++t) oacc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    float m_run = -INFINITY, l_run = 0.f;
+    const int q4 = r >> 2, p4 = r & 3;
+
+    // One tile's copy, loads and LDS writes apart.  to: the byte offset of this lane's token in the pool, -1 = reads as zeros
+    // (past the split's end, not visible, or on a page outside the pool); offsets() returns the SPARSE tile's visibility flags.
+    constexpr bool PRE = NW == 4;
+    constexpr int FB = FCH < 8 ? FCH : 8;
+    static_assert(FCH % FB == 0, "tile copy");
+    u32x4 xl[FB], xs, xr[RCH];
+    long long to = -1, lro = -1;
+    const int lrow = tid / TPR, lc0 = tid % TPR;
+    auto offsets = [&](int kt) {
+        to = -1;
+        unsigned vm = 0u;
+        if constexpr (SPARSE) {
+            if (s1 >= 0 && (unsigned)pg1 < (unsigned)p.nblk) to = pg1 * fp.page_sb + (long long)s1 * fp.tok_sb;
+            vm = (unsigned)__ballot(s1 >= 0);
+            advance(kt + 2 * KT);
+        } else {
+            int sl = s0 + (lane & 31);
+            if (sl >= p.ps) sl -= p.ps;
+            if (sl >= p.ps) sl -= p.ps;
+            if ((unsigned)pg < (unsigned)p.nblk) to = pg * fp.page_sb + (long long)sl * fp.tok_sb;
+            s0 += KT;
+            if (s0 >= p.ps) { s0 -= p.ps; ++j0; }
+            if (s0 >= p.ps) { s0 -= p.ps; ++j0; }
+            if (kt + KT < kend) pg = page_of(j0, s0, kt + KT);   // the next tile's lookup, a tile ahead of its use
+        }
+        return vm;
+    };
+    auto load_lat = [&](int i0) {
+        if (i0 == 0) {
+            lro = __shfl(to, lrow, 64);
+            const u32x4 y = *reinterpret_cast<const u32x4*>(lro >= 0 ? fp.pool + lro + kF8Scales : (const unsigned char*)p.q);
+            xs = lro >= 0 ? y : u32x4{0u, 0u, 0u, 0u};
+        }
+        const bool ok = lro >= 0;
+#pragma unroll
+        for (int i = 0; i < FB; ++i) {
+            const u32x4 y = *reinterpret_cast<const u32x4*>(ok ? fp.pool + lro + 16 * (lc0 + TPR * (i0 + i)) : (const unsigned char*)p.q);
+            xl[i] = ok ? y : u32x4{0u, 0u, 0u, 0u};
+        }
+    };
+    auto store_lat = [&](int i0) {
+#pragma unroll
+        for (int i = 0; i < FB; ++i) {
+            const int c = lc0 + TPR * (i0 + i), tile = (TPR * (i0 + i)) >> 3;
+            const uint32_t sb = tile == 0 ? xs[0] : tile == 1 ? xs[1] : tile == 2 ? xs[2] : xs[3];
+            u32x4 lo, hi;
+            mla_f8_widen(xl[i], __uint_as_float(sb), lo, hi);
+            *reinterpret_cast<u32x4*>(lat + MlaSwz::off(lrow, 2 * c)) = lo;
+            *reinterpret_cast<u32x4*>(lat + MlaSwz::off(lrow, 2 * c + 1)) = hi;
+        }
+    };
+    auto load_rot = [&]() {
+#pragma unroll
+        for (int i = 0; i < RCH; ++i) {
+            const int idx = T * i + tid, row = idx >> 3, ch = idx & 7;
+            const long long ro = __shfl(to, row, 64);
+            const bool ok = ro >= 0;
+            const u32x4 y = *reinterpret_cast<const u32x4*>(ok ? fp.pool + ro + kF8Rope + 16 * ch : (const unsigned char*)p.q);
+            xr[i] = ok ? y : u32x4{0u, 0u, 0u, 0u};
+        }
+    };
+    auto store_rot = [&]() {
+#pragma unroll
+        for (int i = 0; i < RCH; ++i) {
+            const int idx = T * i + tid;
+            *reinterpret_cast<u32x4*>(rop + TileSwz<64>::off(idx >> 3, idx & 7)) = xr[i];
+        }
+    };
+    unsigned vm_next = 0u;
+    if (PRE && kbeg < kend) {
+        vm_next = offsets(kbeg);
+        load_lat(0);
+        load_rot();
+    }
+
+    for (int k0 = kbeg; k0 < kend; k0 += KT) {
+        unsigned vm = vm_next;
+        if constexpr (!PRE) vm = offsets(k0);
+        __syncthreads();   // every wave has read the previous tile
+        if constexpr (PRE) {
+            store_lat(0);
+        } else {
+#pragma unroll 1
+            for (int i0 = 0; i0 < FCH; i0 += FB) {
+                load_lat(i0);
+                store_lat(i0);
+            }
+            load_rot();
+        }
+        store_rot();
+        __syncthreads();
+        if (PRE && k0 + KT < kend) {
+            vm_next = offsets(k0 + KT);
+            load_lat(0);
+            load_rot();
+        }
+        if (!active) continue;   // (wave-uniform; the wave still takes part in the copies and the barriers)
+
+        // ---- from here to the end: mla_split_kernel's text (SPARSE: mla_sparse_kernel's mask)
+        // S^T = K Q^T: A = key 16 kb + r, head dims 32 ks + 8 g .. of the rotary row, then of the latent row
+        f32x4_t sacc[2];
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+            sacc[kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < DK / 32; ++ks)
+                sacc[kb] = mfma16<Tag>(*reinterpret_cast<const s16x8*>(rop + TileSwz<64>::off(16 * kb + r, 4 * ks + g)), qf[ks], sacc[kb]);
+#pragma unroll
+            for (int ks = 0; ks < DV / 32; ++ks) {
+                // (four operand reads in flight: hipcc would otherwise hoist all of a tile's reads and spill)
+                if (ks % 4 == 0) __builtin_amdgcn_sched_barrier(0);
+                sacc[kb] = mfma16<Tag>(*reinterpret_cast<const s16x8*>(lat + MlaSwz::off(16 * kb + r, 4 * ks + g)), qvf[ks], sacc[kb]);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // both score tiles live in VGPRs at one point (kv_split_kernel: the second chain must not end in the first one's registers)
+        asm volatile("" : "+v"(sacc[0]), "+v"(sacc[1]));
+        // register i of block kb holds position k0 + 16 kb + 4 g + i: the row's band [rlo, rhi], SPARSE the list's flags
+        const unsigned vg = valid ? vm >> (4 * g) : 0u;
+        float mx = -INFINITY;
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                bool vis;
+                if constexpr (SPARSE) {
+                    vis = (vg >> (16 * kb + i)) & 1u;
+                } else {
+                    const int key = k0 + 16 * kb + 4 * g + i;
+                    vis = key >= rlo && key <= rhi;
+                }
+                const float x = vis ? sacc[kb][i] : -INFINITY;
+                sacc[kb][i] = x;
+                mx = fmaxf(mx, x);
+            }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float m_new = fmaxf(m_run, mx);
+        const float m_use = m_new == -INFINITY ? 0.f : m_new;
+        const float alpha = __builtin_amdgcn_exp2f((m_run - m_use) * p.c_log2);
+        const float mc = m_use * p.c_log2;
+        m_run = m_new;
+        l_run *= alpha;
+#pragma unroll
+        for (int t = 0; t < NDB; ++t) oacc[t] *= alpha;
+        // P^T as the B operand of O^T = V^T P^T: k-slot 8 g + j is key 4 g + j (j < 4) and 16 + 4 g + j - 4 (j >= 4)
+        u32x4 pk;
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const float e0 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][2 * j], p.c_log2, -mc));
+                const float e1 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][2 * j + 1], p.c_log2, -mc));
+                l_run += e0 + e1;
+                pk[2 * kb + j] = pack2<Tag>(e0, e1);
+            }
+        const s16x8 pb = *reinterpret_cast<s16x8*>(&pk);
+        // V^T operand from the same latent image: rows (keys) 4 g + q and 16 + 4 g + q, head dims 16 t + 4 p ..
+#pragma unroll
+        for (int t = 0; t < NDB; ++t) {
+            if (t % 4 == 0) __builtin_amdgcn_sched_barrier(0);
+            const int ch = 2 * t + (p4 >> 1), bo = 8 * (p4 & 1);
+            const s16x4 lo = lds_tr16(lat + MlaSwz::off(4 * g + q4, ch) + bo);
+            const s16x4 hi = lds_tr16(lat + MlaSwz::off(16 + 4 * g + q4, ch) + bo);
+            oacc[t] = mfma16<Tag>(cat8(lo, hi), pb, oacc[t]);
+        }
+    }
+
+    // ---- epilogue (kv_split_kernel's): O^T register i of block t is head dim 16 t + 4 g + i
+    float l_tot = l_run + __shfl_xor(l_run, 16, 64);
+    l_tot += __shfl_xor(l_tot, 32, 64);
+    const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
+    const float lse_v = l_tot > 0.f ? m_run * p.scale + logf(l_tot) : -INFINITY;
+    if (!valid) return;
+    const size_t row_id = ((size_t)b * p.hq + h) * nq + qi;
+    if (S == 1) {
+        uint16_t* orow = p.o + (((size_t)b * nq + qi) * p.hq + h) * DV;
+#pragma unroll
+        for (int t = 0; t < NDB; ++t) {
+            u32x2 v;
+            v[0] = pack2_rn<Tag>(oacc[t][0] * inv, oacc[t][1] * inv);
+            v[1] = pack2_rn<Tag>(oacc[t][2] * inv, oacc[t][3] * inv);
+            *reinterpret_cast<u32x2*>(orow + 16 * t + 4 * g) = v;
+        }
+        if (g == 0) p.lse[row_id] = lse_v;
+    } else {
+        float* prow = p.po + (row_id * S + s) * DV;
+#pragma unroll
+        for (int t = 0; t < NDB; ++t) *reinterpret_cast<f32x4_t*>(prow + 16 * t + 4 * g) = oacc[t] * inv;
+        if (g == 0) p.plse[row_id * S + s] = lse_v;
+    }
+}
+
+template <int NW>
+hipError_t launch_mla_f8_split(const MlaF8Params& fp, bool sparse, int S, int batch, hipStream_t st) {
+    const KvParams& p = fp.sp.mp.p;
+    if (sparse) {
+        const dim3 grid((unsigned)(batch * p.nq), (unsigned)S, (unsigned)((p.G + 16 * NW - 1) / (16 * NW)));
+        hipLaunchKernelGGL((mla_f8_kernel<NW, true>), grid, dim3(64 * NW), 0, st, fp);
+    } else {
+        const dim3 grid((unsigned)S, (unsigned)((p.rows + 16 * NW - 1) / (16 * NW)), (unsigned)batch);
+        hipLaunchKernelGGL((mla_f8_kernel<NW, false>), grid, dim3(64 * NW), 0, st, fp);
+    }
+    return hipGetLastError();
+}
+
+// fa_mla_fp8_pack: one wave a new token.  Lane l holds 8 latent elements of tile l / 16: amax over the tile's 16 lanes,
+// scale = amax > 0 ? amax / 448 : 1 (pow2: rounded up to a power of two), byte = e4m3_rne(clamp(x / scale, +-448)) with both
+// divisions IEEE-rounded; 8 bytes a lane, the four scales one 16-byte store of lane 0, the rotary 128 bytes by lanes 0 .. 7.
+// The token goes to position cache_seqlens[b] + i through the table; a negative length, a position at or past the table's
+// capacity or a page outside the pool drops it: nothing is written.  The power of two is taken in the bit pattern (a mantissa
+// that is not zero: the next exponent), exact for every normal scale below 2^127; a subnormal scale would go to 2^-126 and one
+// in the top binade to +inf, where tests/mla_fp8_ref.py (frexp / ldexp) differs: amax below 448 * 2^-126 or above 448 * 2^127,
+// outside the contract as NaN and infinity are (values in [2^-6, 8] give scales in [2^-15, 2^-5]).
+struct MlaF8PackParams {
+    const uint16_t *lat, *rope;
+    unsigned char* pool;
+    const int *seqlens, *table;
+    long long lat_bs, lat_ts, rope_bs, rope_ts, page_sb, tok_sb, tbl_rs, tokens;
+    int nnew, nblk, ps, mb, pow2;
+};
+
+__global__ __launch_bounds__(256) void mla_f8_pack_kernel(MlaF8PackParams a) {
+    const int lane = threadIdx.x & 63;
+    const long long t = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= a.tokens) return;   // (wave-uniform, as everything up to the loads)
+    const long long b = t / a.nnew;
+    const int i = (int)(t - b * a.nnew);
+    const int len = a.seqlens[b];
+    const long long pos = (long long)len + i;
+    if (len < 0 || pos >= (long long)a.mb * a.ps) return;
+    const int j = (int)(pos / a.ps), slot = (int)(pos - (long long)j * a.ps);
+    const int pg = a.table[b * a.tbl_rs + j];
+    if ((unsigned)pg >= (unsigned)a.nblk) return;
+    unsigned char* dst = a.pool + pg * a.page_sb + slot * a.tok_sb;
+
+    const u32x4 x = *reinterpret_cast<const u32x4*>(a.lat + b * a.lat_bs + i * a.lat_ts + 8 * lane);
+    float v[8];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        v[2 * k] = unpack_lo<bf16_tag>(x[k]);
+        v[2 * k + 1] = unpack_hi<bf16_tag>(x[k]);
+    }
+    float amax = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) amax = fmaxf(amax, fabsf(v[k]));
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    float scale = amax > 0.f ? __fdiv_rn(amax, 448.f) : 1.f;
+    if (a.pow2) {
+        uint32_t bits = __float_as_uint(scale);
+        if (bits & 0x007fffffu) bits = (bits & 0x7f800000u) + 0x00800000u;
+        scale = __uint_as_float(bits);
+    }
+    float y[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) y[k] = fminf(fmaxf(__fdiv_rn(v[k], scale), -448.f), 448.f);
+    u32x2 q8;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        int c = __builtin_amdgcn_cvt_pk_fp8_f32(y[4 * k], y[4 * k + 1], 0, false);
+        c = __builtin_amdgcn_cvt_pk_fp8_f32(y[4 * k + 2], y[4 * k + 3], c, true);
+        q8[k] = (uint32_t)c;
+    }
+    *reinterpret_cast<u32x2*>(dst + 8 * lane) = q8;
+    u32x4 sc;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) sc[k] = __float_as_uint(__shfl(scale, 16 * k, 64));
+    if (lane == 0) *reinterpret_cast<u32x4*>(dst + kF8Scales) = sc;
+    if (lane < 8)
+        *reinterpret_cast<u32x4*>(dst + kF8Rope + 16 * lane) = *reinterpret_cast<const u32x4*>(a.rope + b * a.rope_bs + i * a.rope_ts + 8 * lane);
+}
+
+}  // namespace
+
+hipError_t launch_mla_f8(const MlaF8Args& a, hipStream_t st) {
+    const KvArgs& kv = a.sa.kv;
+    if (kv.d != kMlaDk || kv.d_v != kMlaDv || kv.dtype != 2 || kv.heads_kv != 1 || !kv.block_table) return hipErrorInvalidValue;   // (the C layer's checks)
+    const bool sparse = a.sa.indices != nullptr;
+    MlaF8Params fp;
+    fp.sp.mp.p = kv_make_params(kv);
+    fp.sp.mp.qv = (const uint16_t*)kv.qv; fp.sp.mp.qv_bs = kv.qv_bs; fp.sp.mp.qv_ts = (int)kv.qv_ts;
+    fp.sp.idx = a.sa.indices; fp.sp.ix_bs = a.sa.ix_bs; fp.sp.ix_ts = a.sa.ix_ts; fp.sp.ix_hs = 0;
+    fp.sp.topk = (int)a.sa.topk; fp.sp.causal = kv.causal;
+    fp.pool = (const unsigned char*)a.pool; fp.page_sb = a.page_sb; fp.tok_sb = (int)a.tok_sb;
+    fp.q_hs = (int)a.q_hs; fp.qv_hs = (int)a.qv_hs;
+    const int S = (int)kv.num_splits;
+    KvParams& p = fp.sp.mp.p;
+    const size_t q_rows = (size_t)kv.batch * kv.heads_q * kv.seqlen_q;
+    p.po = (float*)kv.workspace;
+    p.plse = S > 1 ? (float*)((char*)kv.workspace + ((q_rows * S * kMlaDv * 4 + 255) & ~(size_t)255)) : nullptr;
+    const int nw = mla_waves(sparse ? p.G : p.rows);
+    hipError_t e = nw == 1 ? launch_mla_f8_split<1>(fp, sparse, S, (int)kv.batch, st)
+                 : nw == 2 ? launch_mla_f8_split<2>(fp, sparse, S, (int)kv.batch, st) : launch_mla_f8_split<4>(fp, sparse, S, (int)kv.batch, st);
+    if (e != hipSuccess || S == 1) return e;
+    const long long nrows = (long long)q_rows;
+    hipLaunchKernelGGL((mla_combine_kernel<bf16_tag>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st, p, S, nrows);
+    return hipGetLastError();
+}
+
+hipError_t launch_mla_f8_pack(const MlaF8PackArgs& a, hipStream_t st) {
+    MlaF8PackParams k;
+    k.lat = (const uint16_t*)a.latent; k.rope = (const uint16_t*)a.rope; k.pool = (unsigned char*)a.pool;
+    k.seqlens = a.cache_seqlens; k.table = a.block_table;
+    k.lat_bs = a.lat_bs; k.lat_ts = a.lat_ts; k.rope_bs = a.rope_bs; k.rope_ts = a.rope_ts;
+    k.page_sb = a.page_sb; k.tok_sb = a.tok_sb; k.tbl_rs = a.table_row_stride; k.tokens = a.batch * a.seqlen_new;
+    k.nnew = (int)a.seqlen_new; k.nblk = (int)a.num_blocks; k.ps = (int)a.page_size; k.mb = (int)a.max_blocks; k.pow2 = a.scale_pow2 ? 1 : 0;
+    hipLaunchKernelGGL(mla_f8_pack_kernel, dim3((unsigned)((k.tokens + 3) / 4)), dim3(256), 0, st, k);
+    return hipGetLastError();
+}
+
 }  // namespace fa

@@ -52,6 +52,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_rotary_apply",
     "fa_ex_backward_dlse", "fa_ex_backward_varlen_dlse", "fa_merge_states", "fa_merge_states_backward",
     "fa_mla_sparse_forward", "fa_mla_sparse_workspace_bytes",
+    "fa_mla_fp8_forward", "fa_mla_fp8_workspace_bytes", "fa_mla_fp8_pack",
     "fa_ex_forward_vdim", "fa_ex_backward_vdim", "fa_ex_forward_varlen_vdim", "fa_ex_backward_varlen_vdim",
 )
 
@@ -175,6 +176,16 @@ _sig("fa_mla_sparse_forward", _fields(
     "v_cache_token_stride,indices_batch_stride,indices_token_stride,indices_head_stride c:causal d:softmax_scale i:num_splits "
     "p:block_table i:block_table_row_stride,num_blocks,page_block_size,max_blocks_per_seq p:cache_batch_idx i:cache_batch") + _WS)
 _sig("fa_mla_sparse_workspace_bytes", _fields("i:batch,heads_q,heads_kv,seqlen_q,topk,num_splits"), _SIZE)
+_F8POOL = _fields("i:page_stride_bytes,token_stride_bytes")
+_F8PAGES = _fields("i:block_table_row_stride,num_blocks,page_block_size,max_blocks_per_seq")
+_sig("fa_mla_fp8_forward", _fields(
+    "p:q,qv,kv_cache,indices,cache_seqlens,block_table,o,lse i:batch,heads_q,heads_kv,seqlen_q,topk,d,d_v c:dtype "
+    "i:q_batch_stride,q_token_stride,q_head_stride,qv_batch_stride,qv_token_stride,qv_head_stride") + _F8POOL + _fields("i:indices_batch_stride,indices_token_stride") +
+     _F8PAGES + _fields("c:causal d:softmax_scale i:num_splits") + _WS)
+_sig("fa_mla_fp8_workspace_bytes", _fields("i:batch,heads_q,heads_kv,seqlen_q,cache_len,topk c:with_indices i:num_splits"), _SIZE)
+_sig("fa_mla_fp8_pack", _fields(
+    "p:latent_new,rope_new,kv_cache,cache_seqlens,block_table i:batch,seqlen_new,latent_batch_stride,latent_token_stride,"
+    "rope_batch_stride,rope_token_stride") + _F8POOL + _F8PAGES + _fields("c:scale_pow2") + _STREAM)
 _KVWSV = _fields("i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,d,num_splits c:with_sinks")
 _sig("fa_ex_kvcache_workspace_bytes_varlen", _KVWSV, _SIZE)
 _sig("fa_ex_kvcache_workspace_bytes_qv", _KVWSV + _fields("i:d_v"), _SIZE)
@@ -221,6 +232,8 @@ _family("fa_rotary_apply", [])
 _family("fa_merge_states", [])
 _family("fa_merge_states_backward", [])
 _family("fa_mla_sparse_forward", [])
+_family("fa_mla_fp8_forward", [])
+_family("fa_mla_fp8_pack", [])
 _family("fa_ex_forward_kvcache_qv", ["fa_ex_forward_kvcache" + _suffix for _suffix in ("", "_paged", "_rotary", "_fp8", "_sink", "_varlen")])
 
 
@@ -1313,6 +1326,161 @@ def ex_mla_sparse_forward(q, qv, k_cache, v_cache, indices, cache_seqlens=None, 
             int(bool(causal)), scale, int(num_splits), *paged, _ptr(cache_batch_idx), 0 if cache_batch_idx is None else units,
             ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device)))
     return o, lse
+
+
+# ---- the packed 8-bit latent cache (include/fa_mi355x.h: fa_mla_fp8_forward, fa_mla_fp8_pack) ----
+MLA_FP8_TOKEN_BYTES = 656   # 512 e4m3 | 4 float32 scales | 64 bf16
+
+
+def _f8_pool(who, kv_cache, device):
+    """(the pool as bytes, page stride, token stride, num_blocks, page_block_size) of a packed (num_blocks, page_block_size, 1, 656)
+    uint8 / float8_e4m3fn cache; a view of a wider allocation keeps its strides, nothing is copied"""
+    if not isinstance(kv_cache, torch.Tensor) or kv_cache.dtype not in (torch.uint8, torch.float8_e4m3fn):
+        dt = kv_cache.dtype if isinstance(kv_cache, torch.Tensor) else type(kv_cache).__name__
+        raise NotImplementedError(f"{who}: kv_cache of dtype {dt} is not supported (torch.uint8 or torch.float8_e4m3fn bytes expected)")
+    if not kv_cache.is_cuda or kv_cache.device != device:
+        raise RuntimeError(f"{who}: kv_cache must be a GPU (HIP device) tensor on q's device; there is no CPU path")
+    if kv_cache.dim() != 4 or kv_cache.shape[2:] != (1, MLA_FP8_TOKEN_BYTES) or kv_cache.shape[0] == 0:
+        raise RuntimeError(f"{who}: kv_cache must be (num_blocks, page_block_size, 1, {MLA_FP8_TOKEN_BYTES}), got {tuple(kv_cache.shape)}")
+    nblk, ps = kv_cache.shape[:2]
+    if ps < 16 or ps % 16 != 0:
+        raise RuntimeError(f"{who}: page_block_size (kv_cache.shape[1]) must be a positive multiple of 16, got {ps}")
+    tsb = kv_cache.stride(1)
+    psb = kv_cache.stride(0) if nblk > 1 else max(kv_cache.stride(0), (ps - 1) * tsb + MLA_FP8_TOKEN_BYTES)
+    if kv_cache.stride(3) != 1 or tsb < MLA_FP8_TOKEN_BYTES or tsb % 16 or psb % 16 or psb < (ps - 1) * tsb + MLA_FP8_TOKEN_BYTES or \
+            kv_cache.data_ptr() % 16:
+        raise ValueError(f"{who}: kv_cache must have contiguous 656-byte tokens at a stride that is a multiple of 16, pages that do not "
+                         f"overlap at a stride that is a multiple of 16, and a 16-byte aligned address (got strides "
+                         f"{tuple(kv_cache.stride())}); it is never copied")
+    return kv_cache, psb, tsb, nblk, ps
+
+
+def _f8_table(who, block_table, cache_seqlens, b, device, need_lens):
+    if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32:
+        dt = block_table.dtype if isinstance(block_table, torch.Tensor) else type(block_table).__name__
+        raise NotImplementedError(f"{who}: block_table of dtype {dt} is not supported (int32 tensor expected)")
+    if block_table.device != device or block_table.dim() != 2 or block_table.shape[0] != b or block_table.numel() == 0:
+        raise RuntimeError(f"{who}: block_table must be an int32 (B, max_blocks_per_seq) tensor on q's device, B = {b}")
+    if cache_seqlens is None and need_lens:
+        raise RuntimeError(f"{who}: cache_seqlens must be an int32 ({b},) tensor on the device, or an int")
+    if cache_seqlens is not None and not isinstance(cache_seqlens, (torch.Tensor, numbers.Integral)):
+        raise NotImplementedError(f"{who}: cache_seqlens of type {type(cache_seqlens).__name__} is not supported (int32 tensor or int expected)")
+    if isinstance(cache_seqlens, torch.Tensor):
+        if cache_seqlens.dtype != torch.int32:
+            raise NotImplementedError(f"{who}: cache_seqlens of dtype {cache_seqlens.dtype} is not supported (int32 tensor expected)")
+        if cache_seqlens.device != device or cache_seqlens.shape != (b,):
+            raise RuntimeError(f"{who}: cache_seqlens must be an int32 ({b},) tensor on q's device, or an int")
+
+
+def _f8_table_args(block_table, cache_seqlens, b, device):
+    """(cache_seqlens, block_table, its row stride, max_blocks_per_seq) as handed to the library; inside torch.cuda.device"""
+    if cache_seqlens is not None and not isinstance(cache_seqlens, torch.Tensor):
+        cache_seqlens = torch.full((b,), operator.index(cache_seqlens), dtype=torch.int32, device=device)
+    cache_seqlens = _contiguous(cache_seqlens)
+    if block_table.stride(1) != 1:
+        block_table = block_table.contiguous()
+    trs = block_table.stride(0) if b > 1 else max(block_table.stride(0), block_table.shape[1])
+    return cache_seqlens, block_table, trs, block_table.shape[1]
+
+
+def _f8_rows(who, name, t, heads, width):
+    """(batch, token, head) strides of a (B, N, heads, width) bf16 view as the packed calls address it; anything they cannot
+    address is copied (the tensor is only read)"""
+    def ok(t):
+        b, n = t.shape[:2]
+        hs = t.stride(2) if heads > 1 else width
+        tok = (heads - 1) * hs + width
+        ts = t.stride(1) if n > 1 else tok
+        bs = t.stride(0) if b > 1 else (n - 1) * ts + tok
+        good = t.stride(3) == 1 and hs >= width and ts >= tok and bs >= (n - 1) * ts + tok and not (hs % 8 or ts % 8 or bs % 8 or t.data_ptr() % 16)
+        return good, bs, ts, hs
+    good, bs, ts, hs = ok(t)
+    if not good:
+        t = t.contiguous()
+        good, bs, ts, hs = ok(t)
+    return t, bs, ts, hs
+
+
+def ex_mla_fp8_forward(q, qv, kv_cache, block_table, cache_seqlens=None, indices=None, causal=False, softmax_scale=None, num_splits=0):
+    """(o, lse) of MLA decoding from a packed 8-bit latent cache (FlashMLA's 656-byte token: 512 e4m3 | 4 float32 tile scales | 64
+    bf16): q (B, Nq, H_q, 64) and qv (B, Nq, H_q, 512) bfloat16 — views such as the two column ranges of one (B, Nq, H_q, 576)
+    tensor are used with their own strides; kv_cache (num_blocks, page_block_size, 1, 656) torch.uint8 or torch.float8_e4m3fn,
+    read as bytes, a view of a wider allocation with its own strides, never copied; block_table int32 (B, max_blocks_per_seq);
+    cache_seqlens int32 (B,), an int or None (the capacity); indices None (every cached token: ex_kvcache_forward(..., qv=qv) on
+    the dequantised pool, to the bit) or int32 (B, Nq, topk) (ex_mla_sparse_forward on it, to the bit).  o (B, Nq, H_q, 512)
+    bfloat16, lse (B, H_q, Nq) float32; softmax_scale defaults to (64 + 512) ** -0.5.  See fa_mla_fp8_forward."""
+    who = "ex_mla_fp8_forward"
+    for name, t in (("q", q), ("qv", qv)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{who}: {name} must be a GPU (HIP device) tensor; there is no CPU path")
+        if t.device != q.device:
+            raise RuntimeError(f"{who}: {name} must be on q's device ({q.device}), got {t.device}")
+        if t.dim() != 4:
+            raise RuntimeError(f"{who}: {name} must be 4-D (B, Nq, H_q, d), got {tuple(t.shape)}")
+    if q.dtype != torch.bfloat16 or qv.dtype != torch.bfloat16:
+        raise NotImplementedError(f"{who}: q and qv of dtype {q.dtype}, {qv.dtype} are not supported (torch.bfloat16 expected: the rotary "
+                                  f"part of a packed token is bfloat16)")
+    if indices is not None and not (isinstance(indices, torch.Tensor) and indices.dtype == torch.int32):
+        dt = indices.dtype if isinstance(indices, torch.Tensor) else type(indices).__name__
+        raise NotImplementedError(f"{who}: indices of dtype {dt} is not supported (int32 tensor expected)")
+    b, nq, hq, d = q.shape
+    dv = qv.shape[3]
+    if (d, dv) != (64, 512):
+        raise NotImplementedError(f"{who}: supported for q of head dim 64 with qv of head dim 512 only (got {d}, {dv})")
+    if qv.shape != (b, nq, hq, dv):
+        raise RuntimeError(f"{who}: qv must be a (B, Nq, H_q, {dv}) = ({b}, {nq}, {hq}, {dv}) tensor, got {tuple(qv.shape)}")
+    kv_cache, psb, tsb, nblk, ps = _f8_pool(who, kv_cache, q.device)
+    _f8_table(who, block_table, cache_seqlens, b, q.device, False)
+    topk = ixb = ixt = 0
+    if indices is not None:
+        if indices.device != q.device or indices.dim() != 3 or indices.shape[:2] != (b, nq):
+            raise RuntimeError(f"{who}: indices must be an int32 (B, Nq, topk) = ({b}, {nq}, topk) tensor on q's device, got "
+                               f"{tuple(indices.shape)} on {indices.device}")
+        topk = indices.shape[-1]
+        indices, ixb, ixt, _ixh = _index_strides(indices, b, nq, 1, topk)
+        if indices.numel() == 0:   # (a non-null address selects the list call; nothing is read through it)
+            indices = torch.zeros((1,), dtype=torch.int32, device=q.device) if b and nq else indices
+    q, qb, qt, qh = _f8_rows(who, "q", q, hq, d)
+    qv, qvb, qvt, qvh = _f8_rows(who, "qv", qv, hq, dv)
+    scale = (d + dv) ** -0.5 if softmax_scale is None else float(softmax_scale)
+    with torch.cuda.device(q.device):
+        cache_seqlens, block_table, trs, mb = _f8_table_args(block_table, cache_seqlens, b, q.device)
+        o = torch.empty((b, nq, hq, dv), dtype=q.dtype, device=q.device)
+        lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)
+        nbytes = int(_lib.fa_mla_fp8_workspace_bytes(b, hq, 1, nq, mb * ps, topk, int(indices is not None), int(num_splits))) if b and nq and hq else 0
+        ws = _workspace(q.device, nbytes) if nbytes > 0 else None
+        _call("fa_mla_fp8_forward", (
+            q.data_ptr(), qv.data_ptr(), kv_cache.data_ptr(), _ptr(indices), _ptr(cache_seqlens), block_table.data_ptr(), o.data_ptr(),
+            lse.data_ptr(), b, hq, 1, nq, topk, d, dv, _DTYPE_CODE[q.dtype], qb, qt, qh, qvb, qvt, qvh, psb, tsb, ixb, ixt, trs, nblk, ps, mb,
+            int(bool(causal)), scale, int(num_splits), ws.data_ptr() if ws is not None else 0, nbytes, _stream_ptr(q.device)))
+    return o, lse
+
+
+def ex_mla_fp8_pack(latent_new, rope_new, kv_cache, cache_seqlens, block_table, scale_pow2=False):
+    """Quantise and append new tokens to a packed 8-bit latent cache, in place (fa_mla_fp8_pack): latent_new (B, N_new, 512) and
+    rope_new (B, N_new, 64) bfloat16 on the GPU — the two column ranges of one (B, N_new, 576) tensor are used as they are —
+    go to positions cache_seqlens[b] .. + N_new of sequence b (cache_seqlens: int32 (B,) lengths before the append, or an int)
+    through block_table; a token whose position or page falls outside the table or the pool is dropped.  Returns None."""
+    who = "ex_mla_fp8_pack"
+    for name, t, w in (("latent_new", latent_new, 512), ("rope_new", rope_new, 64)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{who}: {name} must be a GPU (HIP device) tensor; there is no CPU path")
+        if t.dtype != torch.bfloat16:
+            raise NotImplementedError(f"{who}: {name} of dtype {t.dtype} is not supported (torch.bfloat16 expected)")
+        if t.device != latent_new.device or t.dim() != 3 or t.shape[2] != w or t.shape[:2] != latent_new.shape[:2]:
+            raise RuntimeError(f"{who}: latent_new and rope_new must be (B, N_new, 512) and (B, N_new, 64) on one device, got "
+                               f"{tuple(latent_new.shape)}, {tuple(rope_new.shape)}")
+    b, nnew = latent_new.shape[:2]
+    dev = latent_new.device
+    kv_cache, psb, tsb, nblk, ps = _f8_pool(who, kv_cache, dev)
+    _f8_table(who, block_table, cache_seqlens, b, dev, True)
+    latent_new, lb, lt, _h = _f8_rows(who, "latent_new", latent_new.unsqueeze(2), 1, 512)
+    rope_new, rb, rt, _h = _f8_rows(who, "rope_new", rope_new.unsqueeze(2), 1, 64)
+    with torch.cuda.device(dev):
+        cache_seqlens, block_table, trs, mb = _f8_table_args(block_table, cache_seqlens, b, dev)
+        _call("fa_mla_fp8_pack", (
+            latent_new.data_ptr(), rope_new.data_ptr(), kv_cache.data_ptr(), cache_seqlens.data_ptr(), block_table.data_ptr(), b, nnew,
+            lb, lt, rb, rt, psb, tsb, trs, nblk, ps, mb, int(bool(scale_pow2)), _stream_ptr(dev)))
 
 
 # ---- rotary embedding for training and prefill (include/fa_mi355x.h: fa_rotary_apply) ----

@@ -813,6 +813,73 @@ int fa_mla_sparse_forward(const void* q, const void* qv, const void* k_cache, co
 size_t fa_mla_sparse_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t topk,
                                      int64_t num_splits);
 
+/* --- MLA decoding from a packed 8-bit latent cache (FlashMLA's fp8 KV cache), and the append into it.  A call family of its own:
+ * fa_ex_forward_kvcache_qv and fa_mla_sparse_forward keep refusing an e4m3 cache and new tokens.  A cached token is 656 bytes:
+ *     byte   0 .. 511   512 e4m3 (OCP, torch.float8_e4m3fn)   the latent, quantised per 128-wide tile
+ *     byte 512 .. 527   4 float32                             one scale per tile
+ *     byte 528 .. 655   64 bf16                               the rotary part, not quantised
+ * kv_cache is a paged pool of such tokens, one K/V head: slot s of page p starts at kv_cache + p * page_stride_bytes + s *
+ * token_stride_bytes (64-bit arithmetic); token t of sequence b is slot t % page_block_size of page block_table[b, t /
+ * page_block_size].  A contiguous (B, cap, 656) cache with cap a multiple of 16 is a pool of B pages of cap tokens.
+ * Read contract: latent element i of a token is  bf16_rne(float(e4m3[i]) * scale[i / 128])  — one exact widening, one fp32
+ * multiply, one rounding to nearest even — and the 64 rotary values are taken as they are.  fa_mla_fp8_forward on a pool is, to
+ * the bit, the 16-bit call on these values with the same table, lengths and num_splits: fa_ex_forward_kvcache_qv (q against the
+ * rotary part as k_cache, qv against the latent as v_cache, paged) when indices is null, fa_mla_sparse_forward with one list a
+ * query token (indices_head_stride 0) when it is not; indices, topk, visibility, causal, cache_seqlens (untrusted, clamped to the
+ * capacity max_blocks_per_seq * page_block_size; null: the capacity), a page outside [0, num_blocks) (a zero key with a zero
+ * value), the o = 0 / lse = -inf of a row without a key, num_splits, the launch rule and the combine are those calls'.  q
+ * (batch, seqlen_q, heads_q, 64) and qv (batch, seqlen_q, heads_q, 512) bf16 at their batch / token / head strides (elements) —
+ * the two column ranges of one (.., 576) tensor, say, heads 576 apart; o (batch, seqlen_q, heads_q, 512) bf16 dense, lse (batch, heads_q,
+ * seqlen_q) float32.  bf16 only, heads_kv = 1, paged only; no window.  Scales that are not finite are outside the contract
+ * (nothing is read or written out of bounds).  workspace: fa_mla_fp8_workspace_bytes (cache_len: the capacity; with_indices != 0
+ * for a call with indices, else topk must be 0), which equals fa_ex_kvcache_workspace_bytes_qv / fa_mla_sparse_workspace_bytes of
+ * the same shape.  Nothing allocates, synchronises or reads device memory on the host: the calls can be captured in a graph.
+ * fa_mla_fp8_forward checks before any HIP call, the first broken rule named in fa_last_error(), in this order: batch, seqlen_q,
+ * heads_q >= 0, and a call with one of them 0 returns FA_OK without a launch and without looking at anything else; (1) q, qv,
+ * kv_cache, o, lse non-null; (2) d = 64 and d_v = 512, else FA_ERR_UNSUPPORTED with both numbers in the text; (3) dtype bf16
+ * (f16: FA_ERR_UNSUPPORTED by name; any other code FA_ERR_INVALID_ARGUMENT), heads_kv = 1 (FA_ERR_UNSUPPORTED), block_table
+ * non-null, softmax_scale finite and > 0, num_splits in [0, 256], and (FA_ERR_UNSUPPORTED) heads_q <= 65535, seqlen_q <= 2^24,
+ * batch * seqlen_q * heads_q < 2^31, without indices batch <= 65535 and at most 65535 tiles of 16 rows; (4) for q and qv head
+ * strides in [width, 2^20], token strides >= (heads_q - 1) * head stride + width, with batch > 1 batch strides >= (seqlen_q - 1)
+ * * token stride + a token's heads, strides multiples of 8, one batch element below 2^31 bytes (FA_ERR_UNSUPPORTED);
+ * token_stride_bytes >= 656 and a multiple of 16 (below 2^31: FA_ERR_UNSUPPORTED); page_stride_bytes >= (page_block_size - 1) *
+ * token_stride_bytes + 656 and a multiple of 16; kv_cache 16-byte aligned; q, qv, o 16-byte and lse, indices, cache_seqlens,
+ * block_table 4-byte aligned; (5) with indices topk in [0, 2^30], with seqlen_q > 1 indices_token_stride >= topk, with batch > 1
+ * indices_batch_stride >= a sequence's lists, none negative; without indices all three 0; (6) page_block_size a positive multiple
+ * of 16, num_blocks in [1, 2^31), max_blocks_per_seq >= 1 with a capacity <= 2^28 tokens (FA_ERR_UNSUPPORTED),
+ * block_table_row_stride >= max_blocks_per_seq; (7) with S > 1 fewer than 2^26 rows (FA_ERR_UNSUPPORTED), workspace_bytes >= the
+ * need, workspace non-null and 16-byte aligned.
+ * fa_mla_fp8_pack quantises and appends: latent_new (batch, seqlen_new, 512) and rope_new (batch, seqlen_new, 64) bf16 at their
+ * batch / token strides (elements; the two column ranges of one (.., 576) tensor, say; rotate the rope part first, with
+ * fa_rotary_apply); token i of sequence b goes to position cache_seqlens[b] + i (cache_seqlens: the lengths before the append,
+ * required, not modified) through block_table.  Per 128-wide tile, in fp32 from the exact bf16 values:
+ *     amax = max |x|;   scale = amax > 0 ? amax / 448 : 1   (scale_pow2 != 0: rounded up to the next power of two);
+ *     byte = e4m3_rne(clamp(x / scale, -448, 448))
+ * with both divisions IEEE-rounded; the rotary 128 bytes are copied.  (The power of two is exact for every normal scale; a
+ * subnormal scale, or one in the top binade — amax below 448 * 2^-126 or above 448 * 2^127 — is outside the contract.)  Both device arrays are untrusted: a negative length, a
+ * position at or beyond max_blocks_per_seq * page_block_size, or a page outside [0, num_blocks) drops that token, and nothing of
+ * it is written; bytes of a token's stride past its 656 are never written.  Two tokens mapped to one slot: undefined.  A tile
+ * with a NaN or an infinity is outside the contract (nothing is written out of bounds).  Checked before any HIP call, in this
+ * order: batch, seqlen_new >= 0 (one of them 0: FA_OK, no launch); the five pointers non-null; batch * seqlen_new < 2^31; token
+ * strides >= 512 / 64, with batch > 1 batch strides >= (seqlen_new - 1) * token stride + width, multiples of 8; the rules of
+ * token_stride_bytes, page_stride_bytes and kv_cache above; latent_new, rope_new 16-byte, cache_seqlens, block_table 4-byte
+ * aligned; the page geometry (6). */
+int fa_mla_fp8_forward(const void* q, const void* qv, const void* kv_cache, const int32_t* indices, const int32_t* cache_seqlens,
+                       const int32_t* block_table, void* o, float* lse, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                       int64_t seqlen_q, int64_t topk, int64_t d, int64_t d_v, int dtype, int64_t q_batch_stride,
+                       int64_t q_token_stride, int64_t q_head_stride, int64_t qv_batch_stride, int64_t qv_token_stride,
+                       int64_t qv_head_stride, int64_t page_stride_bytes, int64_t token_stride_bytes,
+                       int64_t indices_batch_stride, int64_t indices_token_stride,
+                       int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq,
+                       int causal, double softmax_scale, int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream);
+size_t fa_mla_fp8_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
+                                  int64_t topk, int with_indices, int64_t num_splits);
+int fa_mla_fp8_pack(const void* latent_new, const void* rope_new, void* kv_cache, const int32_t* cache_seqlens,
+                    const int32_t* block_table, int64_t batch, int64_t seqlen_new, int64_t latent_batch_stride,
+                    int64_t latent_token_stride, int64_t rope_batch_stride, int64_t rope_token_stride, int64_t page_stride_bytes,
+                    int64_t token_stride_bytes, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
+                    int64_t max_blocks_per_seq, int scale_pow2, void* stream);
+
 /* --- Rotary position embedding for training and prefill (FlashAttention's flash_attn.layers.rotary: apply_rotary_emb,
  * apply_rotary_emb_qkv_), forward and backward.  One memory-bound launch on `stream` rotates the first rotary_dim head dims of
  * every head of one 16-bit tensor: x -> y, both (batch, seqlen, heads, d) with the heads adjacent at stride d, the last dim

@@ -53,6 +53,12 @@ and V are then 1 an element.  ex_forward and the unfused rotation keep the 16-bi
   in order), whose copy path the sparse kernel shares.  Per figure the median over --rounds rounds with their
   spread, the ratio to the dense call, and the listed bytes gathered per second, B * Nq * topk * 576 * 2 (a list counted once: at
   H_q = 128 two workgroups gather it).
+--mla-fp8: the packed 8-bit latent cache (ex_mla_fp8_forward: 656-byte tokens, 512 e4m3 + 4 scales + 64 bf16) against the 16-bit
+  paged call on the same tokens through the same table (page 64, shuffled), in the same run: --mla's three rows, and --mla-sparse's
+  (32, 128, 1) row at len 8192 with random lists; per figure the median over --rounds rounds with their spread, the bytes of the
+  tokens read per second in each format, and the ratio packed / 16-bit.  Then the append (ex_mla_fp8_pack) of 1, 512 and 8192 new
+  tokens to each of 32 sequences, with and without power-of-two scales, against the bytes it moves (1152 read + 656 written a
+  token): eager calls, and the same calls replayed from one captured graph (without the wrapper and the launch path).
 Timing: HIP events around `--iters` back-to-back calls after `--warmup` calls; the median of `--reps` such groups."""
 import argparse
 import json
@@ -420,6 +426,90 @@ def mla_sparse_rows(args):
     return rows
 
 
+def mla_fp8_rows(args):
+    """--mla-fp8: the packed 8-bit latent cache (656-byte tokens) against the 16-bit paged call on the same tokens and table"""
+    dev, dtype, d, dv, ps, hkv, tok8 = "cuda", torch.bfloat16, 64, 512, 64, 1, 656
+    rows = []
+    t = lambda fn: [timed(fn, args.warmup, args.iters, args.reps) for _ in range(args.rounds)]   # noqa: E731
+    med = statistics.median
+
+    def figures(ts, nbytes, base=None):
+        f = dict(us=round(med(ts), 2), rounds=[round(x, 2) for x in ts], spread=round((max(ts) - min(ts)) / med(ts), 4),
+                 TBps=round(nbytes / med(ts) / 1e6, 3))
+        if base is not None:
+            f["vs_16bit"] = round(med(ts) / base, 3)
+        return f
+
+    def pools(b, L):
+        """a bf16 (b, L, 1, 576) cache, the same tokens paged (page 64, shuffled), and packed through the same table"""
+        pool = torch.randn((b, L, hkv, dv + d), device=dev, dtype=dtype)
+        mb = L // ps
+        table = torch.randperm(b * mb, generator=torch.Generator().manual_seed(b)).view(b, mb).to(torch.int32).to(dev)
+        p16 = torch.empty((b * mb, ps, hkv, dv + d), device=dev, dtype=dtype)
+        for bb in range(b):
+            p16[table[bb].long()] = pool[bb].view(mb, ps, hkv, dv + d)
+        p8 = torch.zeros((b * mb, ps, hkv, tok8), device=dev, dtype=torch.uint8)
+        ext.ex_mla_fp8_pack(pool[:, :, 0, :dv], pool[:, :, 0, dv:], p8, 0, table)
+        return pool, p16, p8, table
+
+    for b, hq, nq, L, topk in ((32, 128, 1, 8192, 0), (32, 16, 1, 8192, 0), (4, 128, 2, 32768, 0), (32, 128, 1, 8192, 2048)):
+        q = torch.randn((b, nq, hq, dv + d), device=dev, dtype=dtype)
+        qr, ql = q[..., dv:], q[..., :dv]               # the packed call takes the views; the 16-bit calls get their own copies
+        qr16, ql16 = qr.contiguous(), ql.contiguous()
+        pool, p16, p8, table = pools(b, L)
+        del pool
+        sl = torch.full((b,), L, dtype=torch.int32, device=dev)
+        if topk:
+            ix = torch.randint(0, L, (b, nq, topk), device=dev, dtype=torch.int32)
+            ref16 = lambda: ext.ex_mla_sparse_forward(qr16, ql16, p16[..., dv:], p16[..., :dv], ix, sl, False, None, table)   # noqa: E731
+            packed = lambda: ext.ex_mla_fp8_forward(qr, ql, p8, table, sl, ix)                                            # noqa: E731
+            tokens = b * nq * topk
+        else:
+            ref16 = lambda: ext.ex_kvcache_forward(qr16, p16[..., dv:], p16[..., :dv], None, None, sl, True, None, block_table=table, qv=ql16)   # noqa: E731
+            packed = lambda: ext.ex_mla_fp8_forward(qr, ql, p8, table, sl, None, True)                                    # noqa: E731
+            tokens = b * L
+        o16, o8 = ref16()[0].float(), packed()[0].float()
+        assert torch.isfinite(o8).all() and (o8 - o16).abs().max() < 0.25, "the packed call is far from the 16-bit one"
+        t16 = t(ref16)
+        r = dict(kind="mla_fp8", B=b, Hq=hq, nq=nq, len=L, topk=topk, bytes_16bit=tokens * (d + dv) * 2, bytes_packed=tokens * tok8,
+                 paged_64_16bit=figures(t16, tokens * (d + dv) * 2), paged_64_packed=figures(t(packed), tokens * tok8, med(t16)))
+        rows.append(r)
+        print(json.dumps(r), flush=True)
+        del p16, p8
+        torch.cuda.empty_cache()
+    # the append: 32 sequences, 1, 512 and 8192 new tokens each, against the bytes it moves (576 * 2 read, 656 written a token).
+    # Eager calls carry the wrapper and the launch (about 19 us); the same calls replayed from one captured graph do not
+    b, L = 32, 8192
+    mb = L // ps
+    table = torch.randperm(b * mb, generator=torch.Generator().manual_seed(b)).view(b, mb).to(torch.int32).to(dev)
+    p8 = torch.zeros((b * mb, ps, hkv, tok8), device=dev, dtype=torch.uint8)
+
+    def graphed(fn):
+        """us a call of args.iters calls captured once and replayed: median of args.reps replays, of args.rounds rounds"""
+        fn()
+        torch.cuda.synchronize()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(side), torch.cuda.graph(graph, stream=side):
+            for _ in range(args.iters):
+                fn()
+        torch.cuda.current_stream().wait_stream(side)
+        return [timed(graph.replay, args.warmup, 1, args.reps) / args.iters for _ in range(args.rounds)]
+
+    for nnew in (1, 512, 8192):
+        new = torch.randn((b, nnew, dv + d), device=dev, dtype=dtype)
+        sl = torch.full((b,), min(4096, L - nnew), dtype=torch.int32, device=dev)
+        for pow2 in (False, True):
+            fn = lambda: ext.ex_mla_fp8_pack(new[..., :dv], new[..., dv:], p8, sl, table, pow2)   # noqa: E731
+            moved = b * nnew * ((d + dv) * 2 + tok8)
+            r = dict(kind="mla_fp8_pack", B=b, n_new=nnew, scale_pow2=pow2, bytes_moved=moved, pack=figures(t(fn), moved),
+                     pack_graph=figures(graphed(fn), moved))
+            rows.append(r)
+            print(json.dumps(r), flush=True)
+    return rows
+
+
 def parent_check(args, dtype):
     dev, b, h, n, d = "cuda", 2, 32, 4096, 128
     q, k, v = (torch.randn((b * n, h, d), device=dev, dtype=dtype) for _ in range(3))
@@ -457,6 +547,7 @@ def main():
     ap.add_argument("--parent-check", action="store_true", help="time only the packed varlen forward at B H = 64, 4096 tokens, d = 128")
     ap.add_argument("--mla", action="store_true", help="time the call with qv (64 + 512 head dims): see the module docstring")
     ap.add_argument("--mla-sparse", action="store_true", help="time the sparse MLA call against the dense qv call at equal keys: see the module docstring")
+    ap.add_argument("--mla-fp8", action="store_true", help="time the packed 8-bit latent cache against the 16-bit paged call, and the append: see the module docstring")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     args.chunks = [int(x) for x in args.chunks.split(",")]
@@ -471,6 +562,12 @@ def main():
         ext.ex_kvcache_forward(wq, wk, wk, None, None, wl, True, None)
     torch.cuda.synchronize()
     del wq, wk
+    if args.mla_fp8:
+        rows = mla_fp8_rows(args)
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(dict(mla_fp8=True, version=ext.version(), rows=rows), f, indent=1)
+        return
     if args.mla or args.mla_sparse:
         rows = mla_sparse_rows(args) if args.mla_sparse else mla_rows(args)
         if args.json:
