@@ -118,15 +118,7 @@ template <int OFF> __device__ __forceinline__ void lds_acc_init_asm(unsigned add
 //   option value + 512: one key tile per workgroup under the mask too;  bit 11: no mask branch in the loop
 // LDS-DMA pieces of the stream: the LDS address and the soffset come from scalar arithmetic on kernel arguments and the
 // block counter (no v_readfirstlane feeds them), so the one wait state M0 needs is all the padding there is
-// (fa_common.h's dma16_issue carries the five states a VALU-written SGPR operand would need).
-__device__ __forceinline__ void dma16_issue_s(rsrc_s_t rsrc, unsigned lds_dst, int voff, int soff) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, %3 offen lds"
-                 :: "v"(voff), "s"(lds_dst), "s"(rsrc), "s"(soff) : "memory");
-}
-__device__ __forceinline__ void dma4_issue_s(rsrc_s_t rsrc, unsigned lds_dst, int voff, int soff) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dword %0, %2, %3 offen lds"
-                 :: "v"(voff), "s"(lds_dst), "s"(rsrc), "s"(soff) : "memory");
-}
+// (fa_common.h's dma16_issue carries the five states a VALU-written SGPR operand would need): dma16_issue_s / dma4_issue_s there.
 
 // Placement of the block's vector work in its 64 MFMA gaps (slice S = the gap behind MFMA S), made by
 // tools/gen_dkdv_schedule.py from the gap budgets: an MFMA leaves the wave about 24 cycles of issue, the operand

@@ -292,6 +292,16 @@ __device__ __forceinline__ void dma4_issue(rsrc_s_t rsrc, unsigned lds_dst, int 
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 3\n\tbuffer_load_dword %0, %2, %3 offen lds"
                  :: "v"(voff), "s"(lds_dst), "s"(rsrc), "s"(soff) : "memory");
 }
+// The same with the LDS address and the soffset from scalar arithmetic on kernel arguments and a tile counter (no
+// v_readfirstlane or lane move feeds them): the one wait state M0 needs is all the padding there is.
+__device__ __forceinline__ void dma16_issue_s(rsrc_s_t rsrc, unsigned lds_dst, int voff, int soff) {
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, %3 offen lds"
+                 :: "v"(voff), "s"(lds_dst), "s"(rsrc), "s"(soff) : "memory");
+}
+__device__ __forceinline__ void dma4_issue_s(rsrc_s_t rsrc, unsigned lds_dst, int voff, int soff) {
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dword %0, %2, %3 offen lds"
+                 :: "v"(voff), "s"(lds_dst), "s"(rsrc), "s"(soff) : "memory");
+}
 __device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // stage rows [row0, row0 + ROWS) of the tensor behind `rsrc` (row stride 2*dr bytes) into the LDS tile at `tile`

@@ -343,7 +343,11 @@ bool fwd_mfma_supported(int dtype, int64_t d) { return (dtype == 1 || dtype == 2
 // Debug trace (tools/trace_stag.py): when a buffer is registered, waves 0 and 4 of workgroup 0 of the staggered kernel
 // store the shader clock after every phase body and after every barrier.  [wave half][event] int64; event 0 = count.
 __device__ long long* g_trace = nullptr;
-hipError_t set_trace_buffer(void* p) { return hipMemcpyToSymbol(HIP_SYMBOL(g_trace), &p, sizeof(p)); }
+static bool g_trace_on = false;   // host side: a buffer is registered, so the launcher picks the DBG instantiation
+hipError_t set_trace_buffer(void* p) {
+    g_trace_on = p != nullptr;
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_trace), &p, sizeof(p));
+}
 
 // Staggered ("ping-pong") forward: the DEFAULT at d = 128 with 128-key tiles (1.95 ms against 2.14 for the lock-step kernel
 // above at B8 H32 N4096, bitwise the same results; profiles/r01_tile_sweep.md); also built with 64-key tiles (fwd_stag = 1).  The two waves that share a SIMD run the same program; with
@@ -387,14 +391,21 @@ constexpr int piece_at(bool pv, int j) {   // DMA piece issued at the head of st
     return -1;
 }
 }  // namespace fwdsched
-template <typename Tag, int D, bool CAUSAL, int KB, bool PAD = false, int RD = 4, bool W2 = false, bool KA = false>
+// DBG: the debug instantiation reads the ablation flags (option fwd_abl) and the trace pointer at run time.  The production
+// one (DBG = false, built for the default schedule KA / RD = 4 only; the launcher picks it when no flag is set and no trace
+// buffer is registered) has neither: no flag tests, no stamps, the masked-tile block behind a scalar branch, and the in-stream
+// DMA state of a wave (ONE descriptor, picked before the loop; LDS destination and soffset advanced by scalar adds) in SGPRs
+// across the loop — profiles/fwd_production.md has the instruction census of both.  Same operations in the same order: bitwise
+// the same results.  The other schedules (64-key tiles, fwd_stag = 4, fwd_rd, fwd_w2) are A/B variants and exist as DBG only.
+template <typename Tag, int D, bool CAUSAL, int KB, bool PAD = false, int RD = 4, bool W2 = false, bool KA = false, bool DBG = true>
 __global__ __launch_bounds__(512, 2) void fwd_mfma_stag_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                                const uint16_t* __restrict__ v, uint16_t* __restrict__ o,
                                                                float* __restrict__ lse, int n, int nqt, float c_log2,
                                                                float scale, int dr_dbg /* row length | debug ablation flags (option fwd_abl) << 16 */,
                                                                int nk /* keys; n = query rows; causal needs nk >= n: the diagonal sits at key = row + nk - n */,
                                                                unsigned kvg /* kv_magic(query heads per K/V head) */) {
-    const int dbg = dr_dbg >> 16;
+    static_assert(DBG || KA, "the production instantiation exists for the default schedule only");
+    const int dbg = DBG ? dr_dbg >> 16 : 0;
     const int DR = PAD ? (dr_dbg & 0xffff) : D;   // elements per tensor row (PAD: head dims below the tile width, fa_common.h)
     constexpr int BM = 256, BN = 32 * KB, NKS = D / 16, NDV = D / 32;
     constexpr int TILE_BYTES = BN * D * 2;
@@ -420,7 +431,7 @@ __global__ __launch_bounds__(512, 2) void fwd_mfma_stag_kernel(const uint16_t* _
     const int coff = nk - n;
     // waves 4..7 (the second wave of every SIMD) run one half-step behind (debug flag 64: waves 0..3 lag instead — does the longer
     // matrix phase of the lagging half follow the wave's age or its role?)
-    const int stag = ((dr_dbg >> 16) & 64) ? 1 - (w >> 2) : (w >> 2);
+    const int stag = (dbg & 64) ? 1 - (w >> 2) : (w >> 2);
 
     const buf_rsrc_t q_rs = make_rsrc(q + base, (unsigned)n * DR * 2);
     s16x8 qf[NKS];
@@ -464,7 +475,52 @@ __global__ __launch_bounds__(512, 2) void fwd_mfma_stag_kernel(const uint16_t* _
         dma_soff = __builtin_amdgcn_readfirstlane(live ? (tile * BN + 4 * (w & 3)) * 2 * DR : 0);
         dma_vo = live ? dma_voff : kOobOff;
     };
-    auto dma_piece = [&](int p) { dma16_issue(dma_rs, dma_dst + 4096 * p, dma_vo, dma_soff + p * 32 * DR); };
+    auto dma_piece = [&](int p) {
+        if constexpr (DBG) dma16_issue(dma_rs, dma_dst + 4096 * p, dma_vo, dma_soff + p * 32 * DR);
+        else {
+            // the pieces of a tile come in order, p = 0 .. 7: both scalar operands advance by one piece behind each (no
+            // VALU-written SGPR).  They are made opaque here: otherwise hipcc gathers the eight pieces' sums into two 8-dword
+            // SGPR vectors ahead of the phase, which spill
+            asm volatile("" : "+s"(dma_dst), "+s"(dma_soff));
+            dma16_issue_s(dma_rs, dma_dst, dma_vo, dma_soff);
+            dma_dst += 4096;
+            dma_soff += 32 * DR;
+        }
+    };
+    // Production form of dma_set.  The calls come in tile order (u = 0, 1, 2, ...), so the state advances by one tile a call:
+    // the descriptor is this half's own for good, the LDS destination walks its ring of buffers (lo .. hi) and the soffset
+    // grows by one tile of rows; only `live` is a comparison on u.  All of it scalar arithmetic on kernel arguments.
+    unsigned dma_lo = 0, dma_hi = 0, dma_tile = 0;
+    int dma_run = 0;
+    auto dma_live = [&](int u) {   // the tile's first piece
+        const bool live = u + 2 * stag < T;
+        dma_dst = dma_tile;
+        dma_soff = live ? dma_run : 0;
+        dma_vo = live ? dma_voff : kOobOff;
+    };
+    auto dma_begin = [&]() {
+        if constexpr (DBG) {
+            dma_set(0, T);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dma_rs[i] = stag ? k_rs[i] : v_rs[i];
+            dma_lo = lds_addr_of(stag ? Kbuf : Vbuf) + (w & 3) * 1024;
+            dma_hi = dma_lo + (stag ? 3 : 2) * TILE_BYTES;
+            dma_tile = dma_lo + (stag ? 2 * TILE_BYTES : 0);                 // K(2) in buffer 2, V(0) in buffer 0
+            dma_run = (2 * stag * BN + 4 * (w & 3)) * 2 * DR;
+            dma_live(0);
+        }
+    };
+    auto dma_next = [&](int u) {
+        if constexpr (DBG) {
+            dma_set(u, T);
+        } else {
+            dma_tile += TILE_BYTES;
+            if (dma_tile == dma_hi) dma_tile = dma_lo;
+            dma_run += BN * 2 * DR;
+            dma_live(u);
+        }
+    };
 
     f32x16 oacc[NDV];
 #pragma unroll
@@ -505,7 +561,12 @@ __global__ __launch_bounds__(512, 2) void fwd_mfma_stag_kernel(const uint16_t* _
         const int k0 = t * BN;
         const bool need_mask = (CAUSAL && (k0 + BN - 1 > q0 + 32 * w + coff)) || (k0 + BN > nk);
         if (need_mask) {
-            const int lim = CAUSAL ? min(qrow + coff, nk - 1) : nk - 1;
+            // need_mask is wave-uniform and false on all but the diagonal / ragged tiles, but hipcc turns this block into selects
+            // (64 compares into SGPR pairs, 60 s_and_b64, 64 v_cndmask on EVERY tile — and the SGPR pairs are what spills into
+            // VGPR lanes).  An asm statement cannot be speculated and nothing moves across it that it reads or writes, so with
+            // the limit passed through one at the head and the scores through one at the end the block stays behind a scalar branch.
+            int lim = CAUSAL ? min(qrow + coff, nk - 1) : nk - 1;
+            if constexpr (!DBG) asm volatile("; masked tile" : "+v"(lim));
 #pragma unroll
             for (int kb = 0; kb < KB; ++kb) {
                 const int thr = lim - (k0 + 32 * kb + 4 * h);
@@ -513,6 +574,7 @@ __global__ __launch_bounds__(512, 2) void fwd_mfma_stag_kernel(const uint16_t* _
                 for (int i = 0; i < 16; ++i)
                     if ((i & 3) + 8 * (i >> 2) > thr) sacc[kb][i] = -INFINITY;
             }
+            if constexpr (!DBG) asm volatile("; end of masked tile" : "+v"(sacc[0]), "+v"(sacc[1]), "+v"(sacc[2]), "+v"(sacc[3]));
         }
         float mx = sacc[0][0];
 #pragma unroll
@@ -663,7 +725,7 @@ __global__ __launch_bounds__(512, 2) void fwd_mfma_stag_kernel(const uint16_t* _
     // K(0), K(1), V(0), then global half-steps g = 0 .. 2T+1, one barrier after each; a wave's local step is g - stag.
     // What half-step 2u+2 reads was issued at 2u-2 or earlier: at the barrier that ends the ODD half-step 2u+1 each
     // wave waits until only its newest issue (that of 2u) is still in flight.
-    long long* const trace = g_trace;
+    long long* const trace = DBG ? g_trace : nullptr;   // (nullptr: the stamps below fold away)
     const bool tron = trace != nullptr && blockIdx.x == 0 && (w == 0 || w == 4);
     int tri = 1;
     auto stamp = [&]() {
@@ -698,14 +760,14 @@ __global__ __launch_bounds__(512, 2) void fwd_mfma_stag_kernel(const uint16_t* _
         __syncthreads();
         int g = 0;
         if (stag) { end_half_ka(false); g = 1; }              // second half idles through half-step 0
-        dma_set(0, T);
+        dma_begin();
         do_M(std::false_type{}, std::true_type{}, std::integral_constant<int, 0>{}, 0);
         do_M(std::false_type{}, std::true_type{}, std::integral_constant<int, 1>{}, 0);         // M_0 = S(0), issues tile 0 / 2
         end_half_ka(false); ++g;
         for (int t = 0; t < Tw; ++t) {
             do_softmax(t);                                    // V_t
             do_M(std::true_type{}, std::true_type{}, std::integral_constant<int, 0>{}, t);      // S operands of M_{t+1}: K(t+1) landed a half-step ago
-            dma_set(t + 1, T);
+            dma_next(t + 1);
             end_half_ka(true); ++g;
             do_M(std::true_type{}, std::true_type{}, std::integral_constant<int, 1>{}, t);      // M_{t+1} = P.V(t) ; S(t+1)
             end_half_ka(false); ++g;
@@ -713,7 +775,7 @@ __global__ __launch_bounds__(512, 2) void fwd_mfma_stag_kernel(const uint16_t* _
         for (; g < 2 * T + 2; ++g) {                          // feed-only half-steps (causal tail)
             const int l = g - stag;
             if (!(l & 1)) {
-                dma_set(l >> 1, T);
+                dma_next(l >> 1);
 #pragma unroll
                 for (int p = 0; p < 8; ++p) dma_piece(p);
             }
@@ -841,7 +903,10 @@ static hipError_t launch_fwd_t(const FwdArgs& a, hipStream_t st, bool want_stag 
                         if (rd == 6) return a.causal ? launch_s(fwd_mfma_stag_kernel<Tag, D, true, KB, PAD, 6, false, true>) : launch_s(fwd_mfma_stag_kernel<Tag, D, false, KB, PAD, 6, false, true>);
                         if (rd == 8) return a.causal ? launch_s(fwd_mfma_stag_kernel<Tag, D, true, KB, PAD, 8, false, true>) : launch_s(fwd_mfma_stag_kernel<Tag, D, false, KB, PAD, 8, false, true>);
                     }
-                    return a.causal ? launch_s(fwd_mfma_stag_kernel<Tag, D, true, KB, PAD, 4, false, true>) : launch_s(fwd_mfma_stag_kernel<Tag, D, false, KB, PAD, 4, false, true>);
+                    // the default schedule: the production instantiation unless a debug flag is set or a trace buffer registered
+                    if ((last_arg >> 16) != 0 || g_trace_on)
+                        return a.causal ? launch_s(fwd_mfma_stag_kernel<Tag, D, true, KB, PAD, 4, false, true, true>) : launch_s(fwd_mfma_stag_kernel<Tag, D, false, KB, PAD, 4, false, true, true>);
+                    return a.causal ? launch_s(fwd_mfma_stag_kernel<Tag, D, true, KB, PAD, 4, false, true, false>) : launch_s(fwd_mfma_stag_kernel<Tag, D, false, KB, PAD, 4, false, true, false>);
                 }
             }
             return a.causal ? launch_s(fwd_mfma_stag_kernel<Tag, D, true, KB, PAD>) : launch_s(fwd_mfma_stag_kernel<Tag, D, false, KB, PAD>);
