@@ -24,6 +24,8 @@ the kernels and named where it is applied below:
   * with GQA the per-query-head dK / dV partials rounded before the group sum (fa_ex.hip, launch_ex: the kernels write them into the
     workspace in the tensor dtype, kv_partial_bytes / launch_kv_group_sum);
   * every result rounded once.
+Those are the extended kernels' points and the defaults of `Model`; the plain path's kernels differ in some of them, and
+tests/hot_cases.py passes baseline a Model per route (below: key tile, lazy rescale, exp2 domain, row sum, dS of dK, fa_generic.hip).
 For float32 tensors it is the whole computation in fp32.  With fp64 and no rounding it is the reference again
 (tests/test_ex_sweep_cpu.py holds the two to each other at 1e-10; the references of single features at 1e-12)."""
 from collections import namedtuple
@@ -56,7 +58,12 @@ def _visible(units, nq, nk, causal, window, mask, block_mask, br, bc, mutant):
     if wr >= 0:
         vis &= j <= i + c + wr
     if causal:
-        vis &= j <= i + (0 if mutant == "causal_top_left" else c)
+        edge = j <= i + (0 if mutant == "causal_top_left" else c)
+        if mutant == "diagonal_mask_shifted":      # (hot_mutant) one key more, inside the row's 64 x 64 diagonal block
+            edge = edge | ((j == i + c + 1) & (j // 64 == (i + c) // 64))
+        vis &= edge
+        if mutant == "causal_tail_keys_dropped" and nk % 128 and nk > 128:      # (hot_mutant) the ragged last 128-key tile, under the mask only
+            vis[:, nk - nk % 128:] = False
     vis = vis.unsqueeze(0)
     if mask is not None or block_mask is not None:
         vis = vis & orc.extended_visible(units, nq, nk, False, mask, block_mask, br, bc)
@@ -105,13 +112,74 @@ def _problems(call, mutant=None):
 LOG2E = 1.4426950408889634
 KEY_TILE = 64      # keys per step of the forward's online softmax
 
+# The rounding points that differ between kernel families, as one record (the argument `model` of baseline).  The defaults are the
+# extended kernels' (the module docstring); tests/hot_cases.py names a model per route of the plain path.  Each non-default value
+# models the file and function written beside it:
+#   key_tile           keys per step of the online softmax: 128 on the plain forward (fa_fwd_mfma.hip, launch_fwd_kb: launch_fwd_t<Tag, D,
+#                      4>, KB = 4 blocks of 32 keys), 64 at d = 64 without the mask and at 256-wide (launch_fwd_kb / launch_fwd_mfma:
+#                      launch_fwd_t<Tag, D, 2>), 32 / 64 under fwd_kb = 1 / 2
+#   lazy_rescale       the running max moves, and o and l are rescaled, only on a tile where some row of the wave's 32 grew by more than
+#                      2^8 (fa_fwd_mfma.hip, fwd_mfma_kernel: `if (LAZY) rescale = __any((m_new - m_run) * c_log2 > 8.0f)`; every row of
+#                      the 32 then moves to its own new max); False: every tile (fwd_eager, and the extended kernels)
+#   exp2               P = exp2(fma(q.k, scale * log2 e, -m * scale * log2 e)) on the unscaled scores with the max of the unscaled scores,
+#                      lse = m * scale + log(l) (fa_fwd_mfma.hip, fwd_mfma_kernel: `exp2f(fmaf(sacc, c_log2, -mc))`, `m_run * scale +
+#                      logf(l_tot)`)
+#   rowsum_rounded_p   the row sum l from the P that was rounded for P V, on the matrix pipe (fa_fwd_mfma.hip, fwd_mfma_kernel, RS_MFMA:
+#                      `lacc = mfma32(ones, pb, lacc)`; option fwd_rs)
+#   dk_ds_from_rounded_p  the dS of dK = dS^T Q is round(round(P) * (dP - delta)): the 8-wave dK/dV kernel multiplies the 16-bit P it made
+#                      for P^T dO (fa_bwd_dkdv_mfma.hip, bwd_dkdv_mfma_kernel: "dS = P dP' with the 16-bit P that also feeds dV", mul_pack;
+#                      DESIGN.md section 6, "stream: dS"); False: from the f32 P, one rounding (fa_bwd_dkdv_w4.hip, bwd_dkdv_w4_kernel;
+#                      fa_bwd_mfma.hip, bwd_mfma_kernel: `pacc[i] = p * pacc[i]`).  The dS of dQ is from the f32 P in every kernel
+#                      (fa_bwd_dq_mfma.hip, bwd_dq_mfma_kernel: `pacc[i] = exp2f(..) * pacc[i]`)
+#   f32_inside         16-bit tensors through the exact kernels: P and dS stay float32, every product is the float32 matrix instruction's
+#                      (fa_generic.hip, header: "any dtype in, f32 math", v_mfma_f32_16x16x4_f32; fwd_f32_kernel walks key tiles of 32);
+#                      only the results are rounded
+#   fma_chain          every product an fma chain, one term at a time on the accumulator (_mm, chunk = 1), the forward's P V chain starting
+#                      from the rescaled running o (fa_generic.hip, fwd_f32_kernel: `acc[t] = MFMA_F32(a[j], Vs[..], acc[t])`).  Four
+#                      roundings at the accumulator's magnitude where a product summed a run at a time has one: twice the noise
+Model = namedtuple("Model", "key_tile lazy_rescale exp2 rowsum_rounded_p dk_ds_from_rounded_p f32_inside fma_chain",
+                   defaults=(KEY_TILE, False, False, False, False, False, False))
+DEFAULT_MODEL = Model()
 
-def _mm(a, b, chunk=0):
+
+def _fma(a, b, c, ct):
+    """a * b + c rounded once, as v_fma_f32 rounds it (float32: through float64, where the product is exact)"""
+    if ct != torch.float32:
+        return a * b + c
+    return (a.double() * b + c.double()).float()
+
+
+def _mm(a, b, chunk=0, init=None):
     """a @ b with the contraction cut into runs of `chunk` terms that are added to the accumulator one after another, as a matrix
     instruction adds its short dot product to an fp32 accumulator register (0: one product, the library's own order).  chunk = 4
     is the exact-f32 kernels' order (fa_ex.hip, the MFMA_F32 loops of ex_fwd_body / ex_dkdv_body / ex_dq_body): per block of 16
-    columns, instruction j = 0 .. 3 takes the columns j, 4 + j, 8 + j, 12 + j, one from each of the four lane groups."""
+    columns, instruction j = 0 .. 3 takes the columns j, 4 + j, 8 + j, 12 + j, one from each of the four lane groups.  chunk = 1 is
+    that order with every term added to the accumulator on its own, rounded once — the plain path's exact kernels (fa_generic.hip,
+    header: v_mfma_f32_16x16x4_f32, "whose result is bit-for-bit an f32 fma chain"); `init` is then the accumulator the chain
+    starts from (the rescaled running o of the forward)."""
     k = a.shape[-1]
+    if chunk == 1:
+        pad = (-k) % 16
+        if pad:
+            a = torch.nn.functional.pad(a, (0, pad))
+            b = torch.nn.functional.pad(b, (0, 0, 0, pad))
+        order = torch.arange(k + pad).reshape(-1, 4, 4).transpose(1, 2).reshape(-1)
+        a, b = a[..., order], b[..., order, :]
+        # float32: term by term in float64, where the product is exact, rounded to float32 after every addition (in place: the
+        # (Nq, Nk) products take d steps each)
+        acc = (torch.zeros(a.shape[:-1] + (b.shape[-1],), dtype=a.dtype) if init is None else init).double()
+        a64, b64 = a.double(), b.double()
+        if a.dtype != torch.float32:
+            for k0 in range(k + pad):
+                acc.addcmul_(a64[..., k0:k0 + 1], b64[..., k0:k0 + 1, :])
+            return acc.to(a.dtype)
+        out = torch.empty(acc.shape, dtype=torch.float32)
+        for k0 in range(k + pad):
+            acc.addcmul_(a64[..., k0:k0 + 1], b64[..., k0:k0 + 1, :])
+            out.copy_(acc)
+            acc.copy_(out)
+        return out
+    assert init is None
     if chunk <= 0 or k <= chunk:
         return a @ b
     if chunk == 4:
@@ -229,7 +297,7 @@ def lse_loss(lse, dlse):
 
 def full_reference(call, mutant=None):
     """Result of the call in fp64 (lse too); tokens no sequence owns hold zeros (lse: NaN)"""
-    assert mutant is None or mutant in MUTANTS
+    assert mutant is None or mutant in MUTANTS or mutant in ("causal_tail_keys_dropped", "diagonal_mask_shifted")
     qd, kd, vd = (call[n].detach().double().clone().requires_grad_(True) for n in ("q", "k", "v"))
     sd = None if call["sinks"] is None else call["sinks"].detach().double().clone().requires_grad_(True)
     packed = call["layout"] != "padded"
@@ -263,15 +331,19 @@ def round_to(dtype):
     return lambda x: x.to(dtype).to(x.dtype)
 
 
-def baseline(call, compute=torch.float32, tensor_dtype="call"):
+def baseline(call, compute=torch.float32, tensor_dtype="call", model=DEFAULT_MODEL):
     """The call through the closed-form forward and backward in dtype `compute`, rounded at the points of the module docstring to
-    `tensor_dtype` (default: the call's; None: nowhere).  Results in `compute`; the sets are not filled in."""
+    `tensor_dtype` (default: the call's; None: nowhere), with the rounding points of `model` (a Model; the default is the extended
+    kernels').  Results in `compute`; the sets are not filled in."""
     ct = compute
+    md = model
+    assert not md.exp2 or (call["softcap"] == 0.0 and call["alibi_slopes"] is None and call["sinks"] is None), "exp2: plain calls only"
     dt = call["dtype"] if tensor_dtype == "call" else tensor_dtype
     rnd = round_to(None if dt is None or dt == ct else dt)
     # the products' accumulation: 16 terms an instruction on the 16-bit kernels (v_mfma_f32_32x32x16_{bf16,f16}: DESIGN.md §4), 4 on
     # the exact-f32 kernels (fa_ex.hip, MFMA_F32 over f32x4 operands, four per 16 columns)
-    chunk = 4 if call["dtype"] == torch.float32 else 16
+    chunk = 1 if md.fma_chain else 4 if call["dtype"] == torch.float32 or md.f32_inside else 16
+    rin = round_to(None) if md.f32_inside else rnd      # the roundings between the loads and the stores
     hq, hkv = call["heads"]
     g = hq // hkv
     q, k, v, do = (call[n].to(ct) for n in ("q", "k", "v", "do"))
@@ -296,30 +368,45 @@ def baseline(call, compute=torch.float32, tensor_dtype="call"):
         m = torch.full((u, nq), NEG_INF, dtype=ct)
         l_ = torch.zeros((u, nq), dtype=ct)
         acc = torch.zeros((u, nq, vr.shape[2]), dtype=ct)
-        for t0 in list(range(0, nk, KEY_TILE)) + ([None] if su is not None else []):
+        c2 = scale * LOG2E                                                   # (exp2: the kernels' c_log2, a float)
+        if md.exp2:
+            c2 = float(torch.tensor(scale, dtype=torch.float32) * torch.tensor(LOG2E, dtype=torch.float32)) if ct == torch.float32 else c2
+            s_fwd = torch.where(pr["vis"], _mm(qp, kr.transpose(1, 2), chunk), torch.tensor(NEG_INF, dtype=ct))    # unscaled scores
+        else:
+            s_fwd = s
+        for t0 in list(range(0, nk, md.key_tile)) + ([None] if su is not None else []):
             if t0 is None:
                 m_new = torch.maximum(m, su.expand(u, nq))
             else:
-                st = s[..., t0:t0 + KEY_TILE]
+                st = s_fwd[..., t0:t0 + md.key_tile]
                 m_new = torch.maximum(m, st.max(-1).values)
+            if md.lazy_rescale:
+                # a wave's 32 query rows decide together; a row that stays keeps its stale max (and alpha = 1)
+                grow = (m_new - m) * (c2 if md.exp2 else LOG2E) > 8.0            # (first visible key: inf > 8; none yet: nan > 8 is False)
+                pad = (-nq) % 32
+                gw = torch.nn.functional.pad(grow, (0, pad)).reshape(u, -1, 32).any(-1, keepdim=True).expand(u, -1, 32).reshape(u, -1)[:, :nq]
+                m_new = torch.where(gw, m_new, m)
             msafe = torch.where(m_new > NEG_INF, m_new, zero)
-            alpha = torch.exp(m - msafe)
+            alpha = torch.exp2((m - msafe) * c2) if md.exp2 else torch.exp(m - msafe)
             if t0 is None:
                 l_ = l_ * alpha + torch.exp(su - msafe)
                 acc = acc * alpha.unsqueeze(-1)
             else:
-                pt = torch.exp(st - msafe.unsqueeze(-1))
-                l_ = l_ * alpha + pt.sum(-1)
-                ptd = rnd(pt if dmul is None else pt * dmul[..., t0:t0 + KEY_TILE])
-                acc = acc * alpha.unsqueeze(-1) + _mm(ptd, vr[:, t0:t0 + KEY_TILE], chunk)
+                pt = torch.exp2(_fma(st, c2, -(msafe * c2).unsqueeze(-1), ct)) if md.exp2 else torch.exp(st - msafe.unsqueeze(-1))
+                ptd = rin(pt if dmul is None else pt * dmul[..., t0:t0 + md.key_tile])
+                l_ = l_ * alpha + (rin(pt) if md.rowsum_rounded_p else pt).sum(-1)
+                if md.fma_chain:
+                    acc = _mm(ptd, vr[:, t0:t0 + md.key_tile], chunk, init=acc * alpha.unsqueeze(-1))
+                else:
+                    acc = acc * alpha.unsqueeze(-1) + _mm(ptd, vr[:, t0:t0 + md.key_tile], chunk)
             m = m_new
         live = m > NEG_INF
         l_ = torch.where(live, l_, torch.ones((), dtype=ct))
-        lp = torch.where(live, m + torch.log(l_), torch.tensor(NEG_INF, dtype=ct))
+        lp = torch.where(live, (m * scale if md.exp2 else m) + torch.log(l_), torch.tensor(NEG_INF, dtype=ct))
         op = rnd(acc * (1.0 / l_).unsqueeze(-1))                  # (fa_ex.hip, ex_fwd_body: inv = 1.f / l, o = acc * inv)
         # backward, from the stored o and lse: P = exp(s - lse) again (ex_dq_body / ex_dkdv_body and the MFMA kernels read lse back)
         prob = torch.where(live.unsqueeze(-1), torch.exp(s - torch.where(live, lp, zero).unsqueeze(-1)), zero)
-        pd = rnd(prob if dmul is None else prob * dmul)
+        pd = rin(prob if dmul is None else prob * dmul)
         dp = _mm(dop, vr.transpose(1, 2), chunk)
         if dmul is not None:
             dp = dp * dmul
@@ -330,9 +417,13 @@ def baseline(call, compute=torch.float32, tensor_dtype="call"):
         dsc = prob * (dp + c.unsqueeze(-1))
         if dt is not None:
             dsc = dsc * dt
-        dsc = rnd(torch.where(pr["vis"], dsc, zero))
+        dsc = rin(torch.where(pr["vis"], dsc, zero))
+        dsk = dsc
+        if md.dk_ds_from_rounded_p:
+            assert dt is None, "dk_ds_from_rounded_p: plain calls only"
+            dsk = rin(torch.where(pr["vis"], rin(prob) * (dp + c.unsqueeze(-1)), zero))
         dqp = rnd(scale * _mm(dsc, kr, chunk))
-        dk_u, dv_u = scale * _mm(dsc.transpose(1, 2), qp, chunk), _mm(pd.transpose(1, 2), dop, chunk)
+        dk_u, dv_u = scale * _mm(dsk.transpose(1, 2), qp, chunk), _mm(pd.transpose(1, 2), dop, chunk)
         if g > 1:
             dk_u, dv_u = rnd(dk_u), rnd(dv_u)
         dkp = rnd(torch.zeros_like(kp).index_add_(0, kvi, dk_u))
@@ -429,3 +520,84 @@ def sharp_bar(got, ref, base, dtype):
         if not err <= bound:
             bad.append(f"{name}: max |got - fp64| = {err:.3e} > 2 * {eb[name][0]:.3e} (baseline) + {eps:.1e} * {big:.3e} = {bound:.3e}")
     return bad, ratio
+
+
+def _cut(res, names, a, b):
+    """a Result with the tensors `names` cut to [a, b) of dimension 1 and nothing else (padded calls)"""
+    return Result(*[(getattr(res, n)[:, a:b] if n in names and getattr(res, n) is not None else None) for n in TENSORS], None, None, None, None, None)
+
+
+def band_edges(nq, nk):
+    """The bands of a padded call under the causal mask: query rows [0, 64), [64, 256), [256, Nq) for o, lse and dq — the first rows,
+    where |o| ~ |v|, would otherwise set the maximum for the long rows — and keys [0, Nk - 256), [Nk - 256, Nk - 64), [Nk - 64, Nk)
+    for dk and dv, whose last keys few rows see.  Empty bands are left out."""
+    rows = [(a, min(b, nq)) for a, b in ((0, 64), (64, 256), (256, nq)) if a < min(b, nq)]
+    e1, e2 = max(nk - 256, 0), max(nk - 64, 0)
+    keys = [(a, b) for a, b in ((0, e1), (e1, e2), (e2, nk)) if a < b]
+    return rows, keys
+
+
+def banded_sharp_bar(got, ref, base, dtype):
+    """sharp_bar — the same function, the same factor — on each band of band_edges alone: (failures, {tensor[a:b]: ratio})"""
+    rows, keys = band_edges(ref.o.shape[1], ref.dk.shape[1])
+    bad, ratio = [], {}
+    for names, bands in ((("o", "lse", "dq"), rows), (("dk", "dv"), keys)):
+        for a, b in bands:
+            fails, r = sharp_bar(_cut(got, names, a, b), _cut(ref, names, a, b), _cut(base, names, a, b), dtype)
+            bad += [f"[{a}:{b}] {f}" for f in fails]
+            ratio.update({f"{n}[{a}:{b}]": v for n, v in r.items()})
+    return bad, ratio
+
+
+# ---- bugs of the kind a schedule rewrite of the plain kernels makes (tests/test_hot_sweep_cpu.py; plain padded calls only)
+
+HOT_MUTANTS = ("delta_over_half_d", "o_times_1.02", "dq_times_1.1", "lse_plus_2e-4", "causal_tail_keys_dropped", "pv_block_rescaled_twice",
+               "dq_stale_k_block", "diagonal_mask_shifted", "dk_last_query_tile_missing")
+
+
+def hot_mutant(call, ref, name):
+    """the fp64 Result of a plain padded call with one bug built in:
+      delta_over_half_d           delta = rowsum(dO * O) over the first d / 2 columns (a row constant made from half a row)
+      o_times_1.02, dq_times_1.1  a scale slip; lse_plus_2e-4: lse off by 200 times its rounding error
+      causal_tail_keys_dropped    under the mask, the last Nk % 128 keys are never visited (the ragged last key tile)
+      diagonal_mask_shifted       under the mask, row i also sees key i + 1 inside its 64 x 64 diagonal block
+      pv_block_rescaled_twice     unit 0, the last 32-row block of queries: the P V sum over keys [0, 64) multiplied once more by the
+                                  factor exp(m(keys < 64) - m(keys < 128)) of the second tile
+      dq_stale_k_block            unit 0: dS[:, 64:96] meets K[0:32], the rows the operand slot held one 64-key tile earlier
+      dk_last_query_tile_missing  dK without the contribution of the last 64-row query tile"""
+    assert name in HOT_MUTANTS and call["layout"] == "padded" and call["heads"] == (1, 1)
+    if name in ("causal_tail_keys_dropped", "diagonal_mask_shifted"):
+        return full_reference(call, mutant=name)
+    if name == "o_times_1.02":
+        return ref._replace(o=ref.o * 1.02)
+    if name == "dq_times_1.1":
+        return ref._replace(dq=ref.dq * 1.1)
+    if name == "lse_plus_2e-4":
+        return ref._replace(lse=ref.lse + 2e-4)
+    q, k, v, do = (call[n].double() for n in ("q", "k", "v", "do"))
+    (pr,) = _problems(call)
+    nq, nk, scale = pr["nq"], pr["nk"], call["scale"]
+    s, _dt = _scores(q, k, pr, call, torch.float64)
+    p = torch.exp(s - ref.lse.unsqueeze(-1))                      # (no dead rows in a plain call: Nk >= Nq under the mask)
+    if name == "pv_block_rescaled_twice":
+        if nk <= 64:
+            return ref
+        r0 = 32 * ((nq - 1) // 32)
+        alpha = torch.exp(s[0, r0:, :64].max(-1).values - s[0, r0:, :128].max(-1).values)
+        o = ref.o.clone()
+        o[0, r0:] += (alpha - 1.0).unsqueeze(-1) * (p[0, r0:, :64] @ v[0, :64])
+        return ref._replace(o=o)
+    d = q.shape[2]
+    half = name == "delta_over_half_d"
+    delta = (do * ref.o)[..., :d // 2 if half else d].sum(-1, keepdim=True)
+    ds = p * (do @ v.transpose(1, 2) - delta)
+    if half:
+        return ref._replace(dq=scale * ds @ k, dk=scale * ds.transpose(1, 2) @ q)
+    if name == "dq_stale_k_block":
+        if nk < 96:
+            return ref
+        dq = ref.dq.clone()
+        dq[0] += scale * ds[0, :, 64:96] @ (k[0, 0:32] - k[0, 64:96])
+        return ref._replace(dq=dq)
+    r0 = 64 * ((nq - 1) // 64)                                       # dk_last_query_tile_missing
+    return ref._replace(dk=ref.dk - scale * ds[:, r0:].transpose(1, 2) @ q[:, r0:])
