@@ -1,25 +1,42 @@
-// KV-cache decoding with a second query operand and K and V of different widths (fa_ex_forward_kvcache_qv; FlashAttention-3's
-// qv): multi-head latent attention at decode time.  Every cached token is a 64-wide rotary row k (k_cache) and a 512-wide latent
-// row v (v_cache); for query head h reading K/V head hk = h / G
+// Multi-head latent attention at decode time: KV-cache decoding with a second query operand and K and V of different widths
+// (fa_ex_forward_kvcache_qv; FlashAttention-3's qv), over a per-query list of cached tokens (fa_mla_sparse_forward), and over
+// FlashMLA's packed 8-bit latent cache (fa_mla_fp8_forward, fa_mla_fp8_pack).  Every cached token is a 64-wide rotary row k and a
+// 512-wide latent row v; for query head h reading K/V head hk = h / G
 //   s[i, j] = scale * (q[i, h, :] . k[j, hk, :] + qv[i, h, :] . v[j, hk, :]),   o[i, h, :] = sum_j softmax_j(s)[i, j] v[j, hk, :]
-// so the latent row is the score operand and the value operand.  It is fetched from memory once per workgroup:
-//   mla_split_kernel  : NW waves (1 | 2 | 4), wave w the row tile NW * blockIdx.y' + w of 16 packed rows (row = token * G + head,
-//                       the mapping of kv_split_kernel).  Per 32-key tile the workgroup copies the 32 x 512 latent rows and the
-//                       32 x 64 rotary rows into LDS (36 KiB, 16 bytes a lane and step, through registers; with four waves the
-//                       loads of tile t + 1 are issued before tile t is computed on), the latent in the swizzled image MlaSwz.  S^T = K Q^T reads that image row-wise (ds_read_b128: 8 consecutive head dims a
-//                       lane, 2 + 16 k-steps of v_mfma_f32_16x16x32 per 16 keys against the q and qv fragments the wave keeps in
-//                       registers); O^T = V^T P^T reads the same bytes transposed (ds_read_b64_tr_b16), 32 MFMAs into a 16 x 512
-//                       fp32 accumulator.  Online softmax in fp32 on the lane of its query row, as in kv_split_kernel.
-//   mla_combine_kernel: S > 1 only — kv_combine_kernel with a loop over the two 256-column halves of a 512-wide row.
-// Lengths, pages, cache rows, split ranges and masks are kv_len_k, kv_split_range and the page rules of fa_decode.hip
-// (fa_decode_common.h): the split range of a workgroup is the union of its row tiles' bands, every row masks its own band.
+// so the latent row is the score operand and the value operand.  It is fetched from memory once per workgroup.
+//
+// One kernel text, mla_decode, in three shells.  A workgroup has NW waves (1 | 2 | 4), each with a tile of 16 query rows.  Per
+// tile of 32 keys the workgroup copies the 32 x 512 latent rows and the 32 x 64 rotary rows into LDS (36 KiB, 16 bytes a lane and
+// step, through registers; with four waves the loads of tile t + 1 are issued before tile t is computed on), the latent in the
+// swizzled image MlaSwz.  mla_tile_step: S^T = K Q^T reads that image row-wise (ds_read_b128: 8 consecutive head dims a lane,
+// 2 + 16 k-steps of v_mfma_f32_16x16x32 per 16 keys against the q and qv fragments the wave keeps in registers); O^T = V^T P^T
+// reads the same bytes transposed (ds_read_b64_tr_b16), 32 MFMAs into a 16 x 512 fp32 accumulator.  Online softmax in fp32 on the
+// lane of its query row, as in kv_split_kernel.  mla_epilogue: o and lse (S == 1) or the fp32 partials of a split, which meet in
+// mla_combine_kernel (kv_combine_kernel with a loop over the two 256-column halves of a 512-wide row) in the fixed split order.
+//
+// What differs between the forms is who names a tile's keys and how a key's bytes reach LDS; each piece is written once:
+//   keys    MlaDenseKeys  the keys [kbeg, kend) of a split (kv_split_range: the union of the workgroup's rows' bands; every row
+//                         masks its own band), contiguous or through the page table.  Row = token * G + head, the mapping of
+//                         kv_split_kernel; lengths, pages and cache rows follow fa_decode.hip (fa_decode_common.h).
+//           MlaListKeys   the topk entries of the list of a (sequence, query token, K/V head); a workgroup serves one list and
+//                         its rows are the G heads.  The mask is the tile's ballot of the per-entry visibility flag.
+//           Both hand out, per lane, the key's page (or cache row) and its slot there, or "not fetched".
+//   copy    MlaCopy16Contig  16-bit caches, contiguous: buffer loads with the bound in the descriptor
+//           MlaCopy16At      16-bit caches by per-key offset (paged dense, every list): v_readlane for the latent row's base
+//           MlaCopyF8        the packed token: scales and e4m3 chunks, widened to the same bf16 image (mla_f8_widen)
+//   shell   mla_split_kernel<Tag, NW, PAGED>   MlaDenseKeys + (PAGED ? MlaCopy16At : MlaCopy16Contig)
+//           mla_sparse_kernel<Tag, NW, PAGED>  MlaListKeys  + MlaCopy16At
+//           mla_f8_kernel<NW, SPARSE>          (SPARSE ? MlaListKeys : MlaDenseKeys), paged, + MlaCopyF8; bf16 only
+// From the barrier after the copy on every form runs the same instructions on the same LDS image, so a call on a packed pool gives
+// the bits of the 16-bit call on the pool's dequantised rows, and a paged call those of the contiguous call on the gathered tokens.
+//
 // Small launches: the wave count follows the packed rows (mla_waves: 16 rows -> one wave a workgroup), so no wave of a
 // workgroup is without rows unless the last row tile of a larger call is; the launch rule (mla_num_splits) then cuts the keys
-// into more splits, and the partial results meet in mla_combine_kernel in the fixed split order.  That is the merge a
-// workgroup-internal key split would need a second, LDS-resident copy of; here it is the one the split path already has.
-// Sparse form (fa_mla_sparse_forward): mla_sparse_kernel below, the same tile pipeline over a per-query list of token positions.
+// into more splits.  That is the merge a workgroup-internal key split would need a second, LDS-resident copy of; here it is the
+// one the split path already has.
 #include "fa_decode_common.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace fa {
 
@@ -40,244 +57,475 @@ struct MlaParams {
     int qv_ts;
 };
 
-template <typename Tag, int NW, bool PAGED>
-__global__ __launch_bounds__(64 * NW) void mla_split_kernel(MlaParams mp) {
-    constexpr int KT = kMlaKT, DK = kMlaDk, DV = kMlaDv, NDB = DV / 16, T = 64 * NW;
-    constexpr int LCH = KT * (DV / 8) / T, RCH = KT * (DK / 8) / T;   // 16-byte chunks a thread moves per tile: latent, rotary
-    static_assert(LCH * T == KT * DV / 8 && RCH >= 1, "tile copy");
-    __shared__ __attribute__((aligned(16))) char lds[kMlaLdsBytes];
-    char* const lat = lds;
-    char* const rop = lds + kMlaLatBytes;
-    const KvParams& p = mp.p;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, g = lane >> 4;
-    const int s = blockIdx.x, S = gridDim.x;
-    const int hk = blockIdx.y % p.hkv, wt = blockIdx.y / p.hkv, b = blockIdx.z;
-    const int nq = p.nq, rows = p.rows;
-    const long long tok0 = (long long)b * nq;
-    int L_b, P_b;
-    const int lk = kv_len_k(p, b, 0, L_b, P_b), coff = lk - nq;
-    // the workgroup's rows [wr0, wr1) and the key range of their bands' union; wr0 < rows by the grid
-    const int wr0 = 16 * NW * wt, wr1 = min(wr0 + 16 * NW, rows);
-    int kbeg, kend;
-    kv_split_range(p, lk, nq, wr0 / p.G, (wr1 - 1) / p.G, s, S, kbeg, kend);
+// Sparse form: the keys of a (sequence b, query token i, K/V head hk) are the topk entries of a list of token positions.  An
+// entry is visible if 0 <= entry < len_b (and <= len_b - nq + i if causal).  An entry that is not visible is never turned into
+// an address: its row is zeros in LDS and its score is -inf.  A visible entry on a page outside the pool or in a cache row outside
+// the cache is a zero row too, with score 0 (the page rule of fa_decode.hip).  Splits cut the list positions [0, topk) into
+// ranges of whole tiles.
+struct MlaSparseParams {
+    MlaParams mp;          // mp.p.nq: the query tokens of a sequence (the window fields are not used)
+    const int* idx;        // entry j of (b, i, hk): idx[b * ix_bs + i * ix_ts + hk * ix_hs + j]; untrusted device memory
+    long long ix_bs, ix_ts, ix_hs;
+    int topk, causal;
+};
 
-    // this wave's row tile (none: the wave only copies), this lane's query row and its visible keys [rlo, rhi]
-    const int pr0 = wr0 + 16 * w, pr = pr0 + r;
-    const bool active = pr0 < rows, valid = pr < rows;
-    const int qlo = min(pr0, rows - 1) / p.G;
-    const int qi = valid ? pr / p.G : qlo, h = hk * p.G + (valid ? pr - qi * p.G : 0);
-    const int rlo = max(qi + coff - p.wl, kbeg);
-    const int rhi = valid ? min(min(qi + coff + p.wr, lk - 1), kend - 1) : -1;
+// The packed 8-bit latent cache: FlashMLA's 656-byte token
+//   byte 0 .. 511: 512 e4m3 (the latent, quantised per 128-wide tile) | 512 .. 527: 4 float32 scales | 528 .. 655: 64 bf16 (rotary)
+// in a paged pool, token t of sequence b at pool + page * page_sb + (t % ps) * tok_sb bytes (64-bit), one K/V head, bf16 only.
+constexpr int kF8Scales = 512, kF8Rope = 528;   // byte offsets in a token (656 bytes)
 
-    s16x8 qf[DK / 32], qvf[DV / 32];
-    {
-        const buf_rsrc_t q_rs = make_rsrc(p.q + b * p.q_bs, (unsigned)(((nq - 1) * p.q_ts + p.hq * DK) * 2));
-        const buf_rsrc_t qv_rs = make_rsrc(mp.qv + b * mp.qv_bs, (unsigned)(((nq - 1) * mp.qv_ts + p.hq * DV) * 2));
-#pragma unroll
-        for (int ks = 0; ks < DK / 32; ++ks) qf[ks] = buf_load_frag(q_rs, valid ? (qi * p.q_ts + h * DK + 32 * ks + 8 * g) * 2 : kOobOff);
-#pragma unroll
-        for (int ks = 0; ks < DV / 32; ++ks) qvf[ks] = buf_load_frag(qv_rs, valid ? (qi * mp.qv_ts + h * DV + 32 * ks + 8 * g) * 2 : kOobOff);
+struct MlaF8Params {
+    MlaSparseParams sp;    // sp.mp.p.kc / vc are not used; sp.idx, topk: SPARSE only
+    const unsigned char* pool;
+    long long page_sb;     // bytes from page to page
+    int tok_sb;            // bytes from token to token of a page
+    int q_hs, qv_hs;       // head strides of q and qv (elements): the two column ranges of one (.., 576) tensor are 576 apart
+};
+
+// ---- keys.  What mla_decode reads of either producer: the workgroup's sequence b, split s of S and positions [kbeg, kend) (keys,
+// or list positions); this wave's row tile (active; none: the wave only copies) and this lane's query row (valid), its query token
+// qi and head h.  start() does the first lookups, next(kt, unit, slot) gives this lane's key kt + (lane & 31) of the tile at kt as
+// the page (or cache row) it is in and its slot there, unit = -1: not fetched, and moves on; it returns the tile's flags for mask().
+struct MlaRows {
+    int b, s, S, kbeg, kend, qi, h;
+    bool active, valid;
+};
+
+// register i of score block kb holds position k0 + 16 kb + 4 g + i: inside the row's band
+struct MlaBandMask {
+    int k0, g, rlo, rhi;
+    __device__ __forceinline__ bool operator()(int kb, int i) const {
+        const int key = k0 + 16 * kb + 4 * g + i;
+        return key >= rlo && key <= rhi;
     }
-    // contiguous: cache row (bidx ? bidx[b] : b); a row outside the cache is an empty range (kv_split_kernel's rule)
-    long long crow = b;
-    int ctok = PAGED ? 0 : p.cap;
-    if (!PAGED && p.bidx) {
-        const int ix = p.bidx[b];
-        crow = ix;
-        if ((unsigned)ix >= (unsigned)p.bcache) { crow = 0; ctok = 0; }
+};
+
+// ... or flagged visible in the list: bit k of the tile's flags is list position k0 + k
+struct MlaFlagMask {
+    unsigned vg;
+    __device__ __forceinline__ bool operator()(int kb, int i) const { return (vg >> (16 * kb + i)) & 1u; }
+};
+
+// Dense: grid (split, row tiles of 16 NW rows x K/V heads, sequence).  PAGED: kv_split_kernel's lookup, done by every wave for
+// itself, the next tile's a tile ahead of its use.  Contiguous: the copy takes the key from kt itself, there is nothing to hand out.
+template <int NW, bool PAGED>
+struct MlaDenseKeys : MlaRows {
+    const KvParams& p;
+    const int* tbl;
+    int lane, rlo, rhi, j0 = 0, s0 = 0, pg = -1;
+
+    __device__ __forceinline__ MlaDenseKeys(const KvParams& p_, int hk, int wt) : p(p_) {
+        lane = threadIdx.x & 63;
+        const int w = threadIdx.x >> 6, r = lane & 15;
+        s = blockIdx.x, S = gridDim.x, b = blockIdx.z;
+        const int nq = p.nq, rows = p.rows;
+        int L_b, P_b;
+        const int lk = kv_len_k(p, b, 0, L_b, P_b), coff = lk - nq;
+        // the workgroup's rows [wr0, wr1) and the key range of their bands' union; wr0 < rows by the grid
+        const int wr0 = 16 * NW * wt, wr1 = min(wr0 + 16 * NW, rows);
+        kv_split_range(p, lk, nq, wr0 / p.G, (wr1 - 1) / p.G, s, S, kbeg, kend);
+        // this wave's row tile, this lane's query row and its visible keys [rlo, rhi]
+        const int pr0 = wr0 + 16 * w, pr = pr0 + r;
+        active = pr0 < rows, valid = pr < rows;
+        const int qlo = min(pr0, rows - 1) / p.G;
+        qi = valid ? pr / p.G : qlo;
+        h = hk * p.G + (valid ? pr - qi * p.G : 0);
+        rlo = max(qi + coff - p.wl, kbeg);
+        rhi = valid ? min(min(qi + coff + p.wr, lk - 1), kend - 1) : -1;
+        tbl = PAGED ? p.table + b * p.tbl_rs : nullptr;
     }
-    const buf_rsrc_t k_rs = make_rsrc(p.kc + crow * p.kc_bs, ctok > 0 ? (unsigned)(((ctok - 1) * p.kc_ts + p.hkv * DK) * 2) : 0u);
-    const buf_rsrc_t v_rs = make_rsrc(p.vc + crow * p.vc_bs, ctok > 0 ? (unsigned)(((ctok - 1) * p.vc_ts + p.hkv * DV) * 2) : 0u);
-    // paged: kv_split_kernel's lookup, done by every wave for itself (lane l: key k0 + (l & 31), the next tile's a tile ahead)
-    const int* tbl = PAGED ? p.table + b * p.tbl_rs : nullptr;
-    int j0 = 0, s0 = 0, pg = -1;
-    auto page_of = [&](int jt, int st, int kt) {
+    __device__ __forceinline__ int page_of(int jt, int st, int kt) const {
         int j = jt, sl = st + (lane & 31);
         if (sl >= p.ps) { sl -= p.ps; ++j; }
         if (sl >= p.ps) ++j;
         return kt + (lane & 31) < kend ? tbl[j] : -1;
-    };
-    if (PAGED && kbeg < kend) {
-        j0 = kbeg / p.ps;
-        s0 = kbeg - j0 * p.ps;
-        pg = page_of(j0, s0, kbeg);
     }
-
-    f32x4_t oacc[NDB];
-#pragma unroll
-    for (int t = 0; t < NDB; ++t) oacc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    float m_run = -INFINITY, l_run = 0.f;
-    const int q4 = r >> 2, p4 = r & 3;
-
-    // One tile's copy, loads and LDS writes apart: chunk idx = T i + tid of the latent rows (row idx / 64 = (T / 64) i + w, the
-    // same for the whole wave; chunk idx % 64 = lane), then of the rotary rows (idx / 8, idx % 8).  Keys past the split's end,
-    // on a page outside the pool or in a row outside the cache are zeros.  Paged: this lane's key kt + (lane & 31) has element
-    // offsets ko / vo in the two pools, -1 = reads as zeros.  Four waves (PRE): a thread holds a whole tile's share, 9 chunks,
-    // and the loads of tile k0 + 32 are in flight while tile k0 is computed on.  Fewer waves move 18 or 36 chunks a thread,
-    // eight at a time between the barriers; there the other workgroups of the CU cover the latency.
-    constexpr bool PRE = LCH <= 8;
-    constexpr int LB = PRE ? LCH : 8;
-    static_assert(LCH % LB == 0, "tile copy");
-    u32x4 xl[LB], xr[RCH];
-    long long ko = -1, vo = -1;
-    const int wu = __builtin_amdgcn_readfirstlane(w);
-    auto offsets = [&](int kt) {
+    __device__ __forceinline__ void start() {
+        if (PAGED && kbeg < kend) {
+            j0 = kbeg / p.ps;
+            s0 = kbeg - j0 * p.ps;
+            pg = page_of(j0, s0, kbeg);
+        }
+    }
+    // a key past the split's end or on a page outside the pool is not fetched
+    __device__ __forceinline__ unsigned next(int kt, int& unit, int& slot) {
+        unit = -1, slot = 0;
         if constexpr (PAGED) {
             int sl = s0 + (lane & 31);
             if (sl >= p.ps) sl -= p.ps;
             if (sl >= p.ps) sl -= p.ps;
-            ko = vo = -1;
-            if ((unsigned)pg < (unsigned)p.nblk) {
-                ko = pg * p.kc_bs + (long long)sl * p.kc_ts;
-                vo = pg * p.vc_bs + (long long)sl * p.vc_ts;
-            }
-            s0 += KT;
+            slot = sl;
+            if ((unsigned)pg < (unsigned)p.nblk) unit = pg;
+            s0 += kMlaKT;
             if (s0 >= p.ps) { s0 -= p.ps; ++j0; }
             if (s0 >= p.ps) { s0 -= p.ps; ++j0; }
-            if (kt + KT < kend) pg = page_of(j0, s0, kt + KT);   // the next tile's lookup, a tile ahead of its use
+            if (kt + kMlaKT < kend) pg = page_of(j0, s0, kt + kMlaKT);   // the next tile's lookup, a tile ahead of its use
         }
-    };
-    auto load_lat = [&](int kt, int i0) {
-#pragma unroll
-        for (int i = 0; i < LB; ++i) {
-            const int row = (T / 64) * (i0 + i) + wu;
-            if constexpr (PAGED) {
-                const long long ro = ((long long)__builtin_amdgcn_readlane((int)(vo >> 32), row) << 32) |
-                                     (unsigned)__builtin_amdgcn_readlane((int)vo, row);   // (wave-uniform: a scalar base)
-                const bool ok = ro >= 0;
-                const u32x4 y = *reinterpret_cast<const u32x4*>(ok ? p.vc + ro + hk * DV + 8 * lane : p.q);
-                xl[i] = ok ? y : u32x4{0u, 0u, 0u, 0u};
-            } else {
-                const int key = kt + row;
-                xl[i] = __builtin_amdgcn_raw_buffer_load_b128(v_rs, key < kend ? (key * p.vc_ts + hk * DV + 8 * lane) * 2 : kOobOff, 0, 0);
-            }
+        return 0u;
+    }
+    __device__ __forceinline__ MlaBandMask mask(int k0, unsigned, int g) const { return MlaBandMask{k0, g, rlo, rhi}; }
+};
+
+// Lists: grid (list = b * nq + i, split, row tiles of 16 NW heads x K/V heads).  The pipeline of lane l (list position + (l & 31)
+// of a tile): e2 the raw entry of the tile after next, one coalesced 128-byte read two tiles ahead of its use; s1 the next tile's
+// visible entry as its token position (contiguous) or its slot in its page pg1 (paged), -1 = not visible, decided a tile ahead.
+template <int NW, bool PAGED>
+struct MlaListKeys : MlaRows {
+    const KvParams& p;
+    const int *tbl, *il;
+    unsigned tlim;
+    int lane, crow, e2 = -1, s1 = -1, pg1 = -1;
+
+    __device__ __forceinline__ MlaListKeys(const MlaSparseParams& sp, int hk, int wt) : p(sp.mp.p) {
+        constexpr int KT = kMlaKT;
+        lane = threadIdx.x & 63;
+        const int w = threadIdx.x >> 6, r = lane & 15;
+        s = blockIdx.y, S = gridDim.y;
+        const int nq = p.nq;
+        b = blockIdx.x / nq, qi = blockIdx.x - b * nq;
+        int L_b, P_b;
+        const int lk = kv_len_k(p, b, 0, L_b, P_b);
+        // visible token positions: [0, tlim)
+        const int thi = sp.causal ? lk - nq + qi : lk - 1;
+        tlim = thi >= 0 ? (unsigned)thi + 1u : 0u;
+        // list positions [kbeg, kend) of split s: whole tiles
+        const int nt = (sp.topk + KT - 1) / KT;
+        kbeg = (int)((long long)s * nt / S) * KT, kend = min(sp.topk, (int)((long long)(s + 1) * nt / S) * KT);
+        // this wave's row tile of the G heads and this lane's head
+        const int pr0 = 16 * NW * wt + 16 * w, pr = pr0 + r;
+        active = pr0 < p.G, valid = pr < p.G;
+        h = hk * p.G + (valid ? pr : 0);
+        // contiguous: cache row (bidx ? bidx[b] : b); a row outside the cache holds zero rows
+        crow = b;
+        if (!PAGED && p.bidx) {
+            const int ix = p.bidx[b];
+            crow = (unsigned)ix < (unsigned)p.bcache ? ix : -1;
         }
-    };
-    auto store_lat = [&](int i0) {
+        tbl = PAGED ? p.table + b * p.tbl_rs : nullptr;
+        il = sp.idx + b * sp.ix_bs + qi * sp.ix_ts + hk * sp.ix_hs;
+    }
+    __device__ __forceinline__ int entry(int jt) const {
+        const int pos = jt + (lane & 31);
+        return pos < kend ? il[pos] : -1;
+    }
+    __device__ __forceinline__ void advance(int jt) {   // e2 -> s1 (pg1); e2 = the entries of the tile at jt
+        const bool vis = (unsigned)e2 < tlim;
+        if constexpr (PAGED) {
+            const unsigned j = (unsigned)e2 / (unsigned)p.ps;   // (< max_blocks_per_seq: e2 < len_b <= the capacity)
+            s1 = vis ? (int)((unsigned)e2 - j * (unsigned)p.ps) : -1;
+            pg1 = vis ? tbl[j] : -1;
+        } else {
+            s1 = vis ? e2 : -1;
+        }
+        e2 = entry(jt);
+    }
+    __device__ __forceinline__ void start() {
+        if (kbeg < kend) {
+            e2 = entry(kbeg);
+            advance(kbeg + kMlaKT);
+        }
+    }
+    __device__ __forceinline__ unsigned next(int kt, int& unit, int& slot) {
+        unit = -1, slot = s1;
+        if constexpr (PAGED) {
+            if (s1 >= 0 && (unsigned)pg1 < (unsigned)p.nblk) unit = pg1;
+        } else if (s1 >= 0 && crow >= 0) {
+            unit = crow;
+        }
+        const unsigned vm = (unsigned)__ballot(s1 >= 0);
+        advance(kt + 2 * kMlaKT);
+        return vm;
+    }
+    __device__ __forceinline__ MlaFlagMask mask(int, unsigned vm, int g) const { return MlaFlagMask{valid ? vm >> (4 * g) : 0u}; }
+};
+
+// ---- copies.  One tile's copy, loads and LDS writes apart: place(unit, slot) takes this lane's key from the producer,
+// load_lat / load_rot fetch a thread's share into registers, store_lat / mla_store_rot write it to LDS.  A key that is not fetched
+// is zeros in LDS: its loads are redirected to the first bytes of q and their results selected away, no address is formed from
+// the key.  Four waves: a thread holds a whole tile's share (CH == B latent chunks) and the loads of tile k0 + 32 are in flight
+// while tile k0 is computed on.  Fewer waves move their CH chunks B at a time between the barriers; there the other workgroups of
+// the CU cover the latency.
+
+// 16-bit caches: chunk idx = T i + tid of the latent rows (row idx / 64 = (T / 64) i + w, the same for the whole wave; chunk
+// idx % 64 = lane), 9, 18 or 36 chunks a thread with the rotary ones
+template <int NW>
+struct MlaCopy16 {
+    static constexpr int T = 64 * NW, CH = kMlaKT * (kMlaDv / 8) / T, B = CH <= 8 ? CH : 8, RCH = kMlaKT * (kMlaDk / 8) / T;
+    static_assert(CH * T == kMlaKT * kMlaDv / 8 && CH % B == 0 && RCH >= 1, "tile copy");
+    const KvParams& p;
+    const int hk, tid, lane, wu;
+    u32x4 xl[B], xr[RCH];
+
+    __device__ __forceinline__ MlaCopy16(const KvParams& p_, int hk_)
+        : p(p_), hk(hk_), tid(threadIdx.x), lane(threadIdx.x & 63), wu(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) {}
+    __device__ __forceinline__ void store_lat(char* lat, int i0) const {
 #pragma unroll
-        for (int i = 0; i < LB; ++i) *reinterpret_cast<u32x4*>(lat + MlaSwz::off((T / 64) * (i0 + i) + wu, lane)) = xl[i];
-    };
-    auto load_rot = [&](int kt) {
+        for (int i = 0; i < B; ++i) *reinterpret_cast<u32x4*>(lat + MlaSwz::off((T / 64) * (i0 + i) + wu, lane)) = xl[i];
+    }
+};
+
+// contiguous: cache row (bidx ? bidx[b] : b); a row outside the cache is an empty range (kv_split_kernel's rule), keys past the
+// split's end are requested at kOobOff
+template <int NW>
+struct MlaCopy16Contig : MlaCopy16<NW> {
+    using Base = MlaCopy16<NW>;
+    using Base::p, Base::hk, Base::tid, Base::lane, Base::wu, Base::xl, Base::xr;
+    buf_rsrc_t k_rs, v_rs;
+
+    __device__ __forceinline__ MlaCopy16Contig(const KvParams& p_, int hk_, int b) : Base(p_, hk_) {
+        long long crow = b;
+        int ctok = p.cap;
+        if (p.bidx) {
+            const int ix = p.bidx[b];
+            crow = ix;
+            if ((unsigned)ix >= (unsigned)p.bcache) { crow = 0; ctok = 0; }
+        }
+        k_rs = make_rsrc(p.kc + crow * p.kc_bs, ctok > 0 ? (unsigned)(((ctok - 1) * p.kc_ts + p.hkv * kMlaDk) * 2) : 0u);
+        v_rs = make_rsrc(p.vc + crow * p.vc_bs, ctok > 0 ? (unsigned)(((ctok - 1) * p.vc_ts + p.hkv * kMlaDv) * 2) : 0u);
+    }
+    __device__ __forceinline__ void place(int, int) {}
+    __device__ __forceinline__ void load_lat(int kt, int kend, int i0) {
+#pragma unroll
+        for (int i = 0; i < Base::B; ++i) {
+            const int key = kt + (Base::T / 64) * (i0 + i) + wu;
+            xl[i] = __builtin_amdgcn_raw_buffer_load_b128(v_rs, key < kend ? (key * p.vc_ts + hk * kMlaDv + 8 * lane) * 2 : kOobOff, 0, 0);
+        }
+    }
+    __device__ __forceinline__ void load_rot(int kt, int kend) {
+#pragma unroll
+        for (int i = 0; i < Base::RCH; ++i) {
+            const int idx = Base::T * i + tid, key = kt + (idx >> 3), ch = idx & 7;
+            xr[i] = __builtin_amdgcn_raw_buffer_load_b128(k_rs, key < kend ? (key * p.kc_ts + hk * kMlaDk + 8 * ch) * 2 : kOobOff, 0, 0);
+        }
+    }
+};
+
+// by offset: this lane's key has element offsets ko / vo in the two caches (pools), -1 = not fetched
+template <int NW>
+struct MlaCopy16At : MlaCopy16<NW> {
+    using Base = MlaCopy16<NW>;
+    using Base::p, Base::hk, Base::tid, Base::lane, Base::wu, Base::xl, Base::xr;
+    static constexpr bool kPre = Base::B == Base::CH;   // the prefetch: a thread holds a whole tile's share
+    long long ko = -1, vo = -1;
+
+    __device__ __forceinline__ MlaCopy16At(const KvParams& p_, int hk_, int) : Base(p_, hk_) {}
+    __device__ __forceinline__ void place(int unit, int slot) {
+        ko = vo = -1;
+        if (unit >= 0) {
+            ko = unit * p.kc_bs + (long long)slot * p.kc_ts;
+            vo = unit * p.vc_bs + (long long)slot * p.vc_ts;
+        }
+    }
+    __device__ __forceinline__ void load_lat(int, int, int i0) {
+        bool ok[Base::B];
+#pragma unroll
+        for (int i = 0; i < Base::B; ++i) {
+            const int row = (Base::T / 64) * (i0 + i) + wu;
+            const long long ro = ((long long)__builtin_amdgcn_readlane((int)(vo >> 32), row) << 32) |
+                                 (unsigned)__builtin_amdgcn_readlane((int)vo, row);   // (wave-uniform: a scalar base)
+            ok[i] = ro >= 0;
+            xl[i] = *reinterpret_cast<const u32x4*>(ok[i] ? p.vc + ro + hk * kMlaDv + 8 * lane : p.q);
+        }
+        // (without the prefetch the LDS writes follow at once: every load of the batch is issued before the first select waits
+        // for one; hipcc otherwise holds the last load back behind the first wait, and in load_rot waits after each)
+        if constexpr (!kPre) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < Base::B; ++i) xl[i] = ok[i] ? xl[i] : u32x4{0u, 0u, 0u, 0u};
+    }
+    __device__ __forceinline__ void load_rot(int, int) {
+        bool ok[Base::RCH];
+#pragma unroll
+        for (int i = 0; i < Base::RCH; ++i) {
+            const int idx = Base::T * i + tid, row = idx >> 3, ch = idx & 7;
+            const long long ro = __shfl(ko, row, 64);
+            ok[i] = ro >= 0;
+            xr[i] = *reinterpret_cast<const u32x4*>(ok[i] ? p.kc + ro + hk * kMlaDk + 8 * ch : p.q);
+        }
+        if constexpr (!kPre) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < Base::RCH; ++i) xr[i] = ok[i] ? xr[i] : u32x4{0u, 0u, 0u, 0u};
+    }
+};
+
+// 16 e4m3 bytes times one scale -> the two 16-byte chunks of bf16 they fill
+__device__ __forceinline__ void mla_f8_widen(u32x4 x, float sc, u32x4& lo, u32x4& hi) {
+    uint32_t out[8];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)x[d], false);
+        const auto b = __builtin_amdgcn_cvt_pk_f32_fp8((int)x[d], true);
+        out[2 * d] = pack2<bf16_tag>(a[0] * sc, a[1] * sc);
+        out[2 * d + 1] = pack2<bf16_tag>(b[0] * sc, b[1] * sc);
+    }
+    lo = u32x4{out[0], out[1], out[2], out[3]};
+    hi = u32x4{out[4], out[5], out[6], out[7]};
+}
+
+// the packed token: row tid / TPR of the tile belongs to TPR = T / 32 threads; a thread loads the row's four scales (one 16-byte
+// load) and its 16-byte chunks c = tid % TPR + TPR i of e4m3 (16 head dims of the 128-wide tile c / 8), and writes for each the
+// two MlaSwz chunks 2c, 2c + 1 of
+//   bf16_rne(fp32(e4m3) * scale)    (one exact widening, one fp32 multiply, one rounding to nearest even).
+// The rotary 128 bytes are 8 chunks, copied as in the 16-bit forms.  to: the byte offset of this lane's token in the pool, -1 =
+// not fetched: zero bytes and zero scales, zeros.  Four waves: a thread holds 4 + 1 + 1 chunks of tile t + 1 while tile t is
+// computed on.
+template <int NW>
+struct MlaCopyF8 {
+    static constexpr int T = 64 * NW, TPR = T / kMlaKT, CH = (kMlaDv / 16) / TPR, B = CH < 8 ? CH : 8, RCH = kMlaKT * (kMlaDk / 8) / T;
+    static_assert(TPR * CH * 16 == kMlaDv && 8 % TPR == 0 && CH % B == 0 && RCH >= 1, "tile copy");
+    const MlaF8Params& fp;
+    const unsigned char* const none;   // where the loads of a token that is not fetched go
+    const int tid, lrow, lc0;
+    u32x4 xl[B], xs, xr[RCH];
+    long long to = -1, lro = -1;
+
+    __device__ __forceinline__ MlaCopyF8(const MlaF8Params& fp_)
+        : fp(fp_), none((const unsigned char*)fp_.sp.mp.p.q), tid(threadIdx.x), lrow(threadIdx.x / TPR), lc0(threadIdx.x % TPR) {}
+    __device__ __forceinline__ void place(int unit, int slot) { to = unit >= 0 ? unit * fp.page_sb + (long long)slot * fp.tok_sb : -1; }
+    __device__ __forceinline__ void load_lat(int, int, int i0) {
+        if (i0 == 0) {
+            lro = __shfl(to, lrow, 64);
+            const u32x4 y = *reinterpret_cast<const u32x4*>(lro >= 0 ? fp.pool + lro + kF8Scales : none);
+            xs = lro >= 0 ? y : u32x4{0u, 0u, 0u, 0u};
+        }
+        const bool ok = lro >= 0;
+#pragma unroll
+        for (int i = 0; i < B; ++i) {
+            const u32x4 y = *reinterpret_cast<const u32x4*>(ok ? fp.pool + lro + 16 * (lc0 + TPR * (i0 + i)) : none);
+            xl[i] = ok ? y : u32x4{0u, 0u, 0u, 0u};
+        }
+    }
+    __device__ __forceinline__ void store_lat(char* lat, int i0) const {
+#pragma unroll
+        for (int i = 0; i < B; ++i) {
+            const int c = lc0 + TPR * (i0 + i), tile = (TPR * (i0 + i)) >> 3;
+            const uint32_t sb = tile == 0 ? xs[0] : tile == 1 ? xs[1] : tile == 2 ? xs[2] : xs[3];
+            u32x4 lo, hi;
+            mla_f8_widen(xl[i], __uint_as_float(sb), lo, hi);
+            *reinterpret_cast<u32x4*>(lat + MlaSwz::off(lrow, 2 * c)) = lo;
+            *reinterpret_cast<u32x4*>(lat + MlaSwz::off(lrow, 2 * c + 1)) = hi;
+        }
+    }
+    __device__ __forceinline__ void load_rot(int, int) {
 #pragma unroll
         for (int i = 0; i < RCH; ++i) {
             const int idx = T * i + tid, row = idx >> 3, ch = idx & 7;
-            if constexpr (PAGED) {
-                const long long ro = __shfl(ko, row, 64);
-                const bool ok = ro >= 0;
-                const u32x4 y = *reinterpret_cast<const u32x4*>(ok ? p.kc + ro + hk * DK + 8 * ch : p.q);
-                xr[i] = ok ? y : u32x4{0u, 0u, 0u, 0u};
-            } else {
-                const int key = kt + row;
-                xr[i] = __builtin_amdgcn_raw_buffer_load_b128(k_rs, key < kend ? (key * p.kc_ts + hk * DK + 8 * ch) * 2 : kOobOff, 0, 0);
-            }
-        }
-    };
-    auto store_rot = [&]() {
-#pragma unroll
-        for (int i = 0; i < RCH; ++i) {
-            const int idx = T * i + tid;
-            *reinterpret_cast<u32x4*>(rop + TileSwz<64>::off(idx >> 3, idx & 7)) = xr[i];
-        }
-    };
-    if (PRE && kbeg < kend) {
-        offsets(kbeg);
-        load_lat(kbeg, 0);
-        load_rot(kbeg);
-    }
-
-    for (int k0 = kbeg; k0 < kend; k0 += KT) {
-        if constexpr (!PRE) offsets(k0);
-        __syncthreads();   // every wave has read the previous tile
-        if constexpr (PRE) {
-            store_lat(0);
-        } else {
-#pragma unroll 1
-            for (int i0 = 0; i0 < LCH; i0 += LB) {
-                load_lat(k0, i0);
-                store_lat(i0);
-            }
-            load_rot(k0);
-        }
-        store_rot();
-        __syncthreads();
-        if (PRE && k0 + KT < kend) {
-            offsets(k0 + KT);
-            load_lat(k0 + KT, 0);
-            load_rot(k0 + KT);
-        }
-        if (!active) continue;   // (wave-uniform; the wave still takes part in the copies and the barriers)
-
-        // S^T = K Q^T: A = key 16 kb + r, head dims 32 ks + 8 g .. of the rotary row, then of the latent row
-        f32x4_t sacc[2];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            sacc[kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < DK / 32; ++ks)
-                sacc[kb] = mfma16<Tag>(*reinterpret_cast<const s16x8*>(rop + TileSwz<64>::off(16 * kb + r, 4 * ks + g)), qf[ks], sacc[kb]);
-#pragma unroll
-            for (int ks = 0; ks < DV / 32; ++ks) {
-                // (four operand reads in flight: hipcc would otherwise hoist all of a tile's reads and spill)
-                if (ks % 4 == 0) __builtin_amdgcn_sched_barrier(0);
-                sacc[kb] = mfma16<Tag>(*reinterpret_cast<const s16x8*>(lat + MlaSwz::off(16 * kb + r, 4 * ks + g)), qvf[ks], sacc[kb]);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        // both score tiles live in VGPRs at one point (kv_split_kernel: the second chain must not end in the first one's registers)
-        asm volatile("" : "+v"(sacc[0]), "+v"(sacc[1]));
-        // the row's band: register i of block kb holds key k0 + 16 kb + 4 g + i
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int key = k0 + 16 * kb + 4 * g + i;
-                const float x = (key >= rlo && key <= rhi) ? sacc[kb][i] : -INFINITY;
-                sacc[kb][i] = x;
-                mx = fmaxf(mx, x);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);
-        const float m_use = m_new == -INFINITY ? 0.f : m_new;
-        const float alpha = __builtin_amdgcn_exp2f((m_run - m_use) * p.c_log2);
-        const float mc = m_use * p.c_log2;
-        m_run = m_new;
-        l_run *= alpha;
-#pragma unroll
-        for (int t = 0; t < NDB; ++t) oacc[t] *= alpha;
-        // P^T as the B operand of O^T = V^T P^T: k-slot 8 g + j is key 4 g + j (j < 4) and 16 + 4 g + j - 4 (j >= 4)
-        u32x4 pk;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const float e0 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][2 * j], p.c_log2, -mc));
-                const float e1 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][2 * j + 1], p.c_log2, -mc));
-                l_run += e0 + e1;
-                pk[2 * kb + j] = pack2<Tag>(e0, e1);
-            }
-        const s16x8 pb = *reinterpret_cast<s16x8*>(&pk);
-        // V^T operand from the same latent image: rows (keys) 4 g + q and 16 + 4 g + q, head dims 16 t + 4 p ..
-#pragma unroll
-        for (int t = 0; t < NDB; ++t) {
-            if (t % 4 == 0) __builtin_amdgcn_sched_barrier(0);
-            const int ch = 2 * t + (p4 >> 1), bo = 8 * (p4 & 1);
-            const s16x4 lo = lds_tr16(lat + MlaSwz::off(4 * g + q4, ch) + bo);
-            const s16x4 hi = lds_tr16(lat + MlaSwz::off(16 + 4 * g + q4, ch) + bo);
-            oacc[t] = mfma16<Tag>(cat8(lo, hi), pb, oacc[t]);
+            const long long ro = __shfl(to, row, 64);
+            const bool ok = ro >= 0;
+            const u32x4 y = *reinterpret_cast<const u32x4*>(ok ? fp.pool + ro + kF8Rope + 16 * ch : none);
+            xr[i] = ok ? y : u32x4{0u, 0u, 0u, 0u};
         }
     }
+};
 
-    // ---- epilogue (kv_split_kernel's): O^T register i of block t is head dim 16 t + 4 g + i
+// the rotary rows of a tile, chunk idx = T i + tid (row idx / 8, chunk idx % 8), from a thread's registers to LDS
+template <int T, int RCH>
+__device__ __forceinline__ void mla_store_rot(char* rop, const u32x4 (&xr)[RCH]) {
+#pragma unroll
+    for (int i = 0; i < RCH; ++i) {
+        const int idx = T * i + (int)threadIdx.x;
+        *reinterpret_cast<u32x4*>(rop + TileSwz<64>::off(idx >> 3, idx & 7)) = xr[i];
+    }
+}
+
+// ---- the wave's share of the work
+
+// q and qv as the B operand of S^T = K Q^T: head dims 32 ks + 8 g .. of row (qi, h), heads q_hs / qv_hs elements apart
+__device__ __forceinline__ void mla_load_q(const MlaParams& mp, int q_hs, int qv_hs, const MlaRows& row, int g,
+                                           s16x8 (&qf)[kMlaDk / 32], s16x8 (&qvf)[kMlaDv / 32]) {
+    constexpr int DK = kMlaDk, DV = kMlaDv;
+    const KvParams& p = mp.p;
+    const buf_rsrc_t q_rs = make_rsrc(p.q + row.b * p.q_bs, (unsigned)(((p.nq - 1) * p.q_ts + (p.hq - 1) * q_hs + DK) * 2));
+    const buf_rsrc_t qv_rs = make_rsrc(mp.qv + row.b * mp.qv_bs, (unsigned)(((p.nq - 1) * mp.qv_ts + (p.hq - 1) * qv_hs + DV) * 2));
+#pragma unroll
+    for (int ks = 0; ks < DK / 32; ++ks)
+        qf[ks] = buf_load_frag(q_rs, row.valid ? (row.qi * p.q_ts + row.h * q_hs + 32 * ks + 8 * g) * 2 : kOobOff);
+#pragma unroll
+    for (int ks = 0; ks < DV / 32; ++ks)
+        qvf[ks] = buf_load_frag(qv_rs, row.valid ? (row.qi * mp.qv_ts + row.h * qv_hs + 32 * ks + 8 * g) * 2 : kOobOff);
+}
+
+// One tile of 32 keys in LDS against the wave's 16 rows: scores, mask (vis(kb, i): register i of score block kb is visible),
+// online softmax, P^T and the update of the accumulator
+template <typename Tag, typename Mask>
+__device__ __forceinline__ void mla_tile_step(const char* lat, const char* rop, const s16x8 (&qf)[kMlaDk / 32], const s16x8 (&qvf)[kMlaDv / 32],
+                                              f32x4_t (&oacc)[kMlaDv / 16], float& m_run, float& l_run, float c_log2, int r, int g, Mask vis) {
+    constexpr int DK = kMlaDk, DV = kMlaDv, NDB = DV / 16;
+    const int q4 = r >> 2, p4 = r & 3;
+    // S^T = K Q^T: A = key 16 kb + r, head dims 32 ks + 8 g .. of the rotary row, then of the latent row
+    f32x4_t sacc[2];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+        sacc[kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < DK / 32; ++ks)
+            sacc[kb] = mfma16<Tag>(*reinterpret_cast<const s16x8*>(rop + TileSwz<64>::off(16 * kb + r, 4 * ks + g)), qf[ks], sacc[kb]);
+#pragma unroll
+        for (int ks = 0; ks < DV / 32; ++ks) {
+            // (four operand reads in flight: hipcc would otherwise hoist all of a tile's reads and spill)
+            if (ks % 4 == 0) __builtin_amdgcn_sched_barrier(0);
+            sacc[kb] = mfma16<Tag>(*reinterpret_cast<const s16x8*>(lat + MlaSwz::off(16 * kb + r, 4 * ks + g)), qvf[ks], sacc[kb]);
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // both score tiles live in VGPRs at one point (kv_split_kernel: the second chain must not end in the first one's registers)
+    asm volatile("" : "+v"(sacc[0]), "+v"(sacc[1]));
+    float mx = -INFINITY;
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float x = vis(kb, i) ? sacc[kb][i] : -INFINITY;
+            sacc[kb][i] = x;
+            mx = fmaxf(mx, x);
+        }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float m_new = fmaxf(m_run, mx);
+    const float m_use = m_new == -INFINITY ? 0.f : m_new;
+    const float alpha = __builtin_amdgcn_exp2f((m_run - m_use) * c_log2);
+    const float mc = m_use * c_log2;
+    m_run = m_new;
+#pragma unroll
+    for (int t = 0; t < NDB; ++t) oacc[t] *= alpha;
+    // P^T as the B operand of O^T = V^T P^T: k-slot 8 g + j is key 4 g + j (j < 4) and 16 + 4 g + j - 4 (j >= 4).
+    // l_run = l_run * alpha + the tile's four pair sums in order; the product and the first sum are one fma.  That is what hipcc's
+    // contraction made of `l_run *= alpha; l_run += e0 + e1` in every instantiation while each form had its own text; it is
+    // written out because the contraction depends on how the adds around it get vectorised.
+    u32x4 pk;
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const float e0 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][2 * j], c_log2, -mc));
+            const float e1 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][2 * j + 1], c_log2, -mc));
+            l_run = kb + j == 0 ? fmaf(l_run, alpha, e0 + e1) : l_run + (e0 + e1);
+            pk[2 * kb + j] = pack2<Tag>(e0, e1);
+        }
+    const s16x8 pb = *reinterpret_cast<s16x8*>(&pk);
+    // V^T operand from the same latent image: rows (keys) 4 g + q and 16 + 4 g + q, head dims 16 t + 4 p ..
+#pragma unroll
+    for (int t = 0; t < NDB; ++t) {
+        if (t % 4 == 0) __builtin_amdgcn_sched_barrier(0);
+        const int ch = 2 * t + (p4 >> 1), bo = 8 * (p4 & 1);
+        const s16x4 lo = lds_tr16(lat + MlaSwz::off(4 * g + q4, ch) + bo);
+        const s16x4 hi = lds_tr16(lat + MlaSwz::off(16 + 4 * g + q4, ch) + bo);
+        oacc[t] = mfma16<Tag>(cat8(lo, hi), pb, oacc[t]);
+    }
+}
+
+// kv_split_kernel's epilogue: O^T register i of block t is head dim 16 t + 4 g + i of row (b, qi, h); o and lse, or with S > 1
+// the partials of split s
+template <typename Tag>
+__device__ __forceinline__ void mla_epilogue(const KvParams& p, const MlaRows& row, int g, const f32x4_t (&oacc)[kMlaDv / 16], float m_run, float l_run) {
+    constexpr int DV = kMlaDv, NDB = DV / 16;
     float l_tot = l_run + __shfl_xor(l_run, 16, 64);
     l_tot += __shfl_xor(l_tot, 32, 64);
     const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
     const float lse_v = l_tot > 0.f ? m_run * p.scale + logf(l_tot) : -INFINITY;
-    if (!valid) return;
-    const size_t row_id = ((size_t)b * p.hq + h) * nq + qi;
-    if (S == 1) {
-        uint16_t* orow = p.o + ((size_t)(tok0 + qi) * p.hq + h) * DV;
+    if (!row.valid) return;
+    const size_t row_id = ((size_t)row.b * p.hq + row.h) * p.nq + row.qi;
+    if (row.S == 1) {
+        uint16_t* orow = p.o + (((size_t)row.b * p.nq + row.qi) * p.hq + row.h) * DV;
 #pragma unroll
         for (int t = 0; t < NDB; ++t) {
             u32x2 v;
@@ -287,10 +535,102 @@ __global__ __launch_bounds__(64 * NW) void mla_split_kernel(MlaParams mp) {
         }
         if (g == 0) p.lse[row_id] = lse_v;
     } else {
-        float* prow = p.po + (row_id * S + s) * DV;
+        float* prow = p.po + (row_id * row.S + row.s) * DV;
 #pragma unroll
         for (int t = 0; t < NDB; ++t) *reinterpret_cast<f32x4_t*>(prow + 16 * t + 4 * g) = oacc[t] * inv;
-        if (g == 0) p.plse[row_id * S + s] = lse_v;
+        if (g == 0) p.plse[row_id * row.S + row.s] = lse_v;
+    }
+}
+
+// The kernel: the tile pipeline over the keys that `keys` names, brought to LDS by `copy`
+template <typename Tag, int NW, typename Keys, typename Copy>
+__device__ __forceinline__ void mla_decode(char* lds, const MlaParams& mp, int q_hs, int qv_hs, Keys& keys, Copy& copy) {
+    constexpr int KT = kMlaKT, NDB = kMlaDv / 16;
+    constexpr bool PRE = NW == 4;
+    char* const lat = lds;
+    char* const rop = lds + kMlaLatBytes;
+    const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
+    const int kbeg = keys.kbeg, kend = keys.kend;
+
+    s16x8 qf[kMlaDk / 32], qvf[kMlaDv / 32];
+    mla_load_q(mp, q_hs, qv_hs, keys, g, qf, qvf);
+    keys.start();
+
+    f32x4_t oacc[NDB];
+#pragma unroll
+    for (int t = 0; t < NDB; ++t) oacc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    float m_run = -INFINITY, l_run = 0.f;
+
+    // this lane's key of the tile at kt, from the producer to the copy; the tile's flags
+    auto produce = [&](int kt) {
+        int unit, slot;
+        const unsigned vm = keys.next(kt, unit, slot);
+        copy.place(unit, slot);
+        return vm;
+    };
+    unsigned vm_next = 0u;
+    if (PRE && kbeg < kend) {
+        vm_next = produce(kbeg);
+        copy.load_lat(kbeg, kend, 0);
+        copy.load_rot(kbeg, kend);
+    }
+
+    for (int k0 = kbeg; k0 < kend; k0 += KT) {
+        unsigned vm = vm_next;
+        if constexpr (!PRE) vm = produce(k0);
+        __syncthreads();   // every wave has read the previous tile
+        if constexpr (PRE) {
+            copy.store_lat(lat, 0);
+        } else {
+#pragma unroll 1
+            for (int i0 = 0; i0 < Copy::CH; i0 += Copy::B) {
+                copy.load_lat(k0, kend, i0);
+                copy.store_lat(lat, i0);
+            }
+            copy.load_rot(k0, kend);
+        }
+        mla_store_rot<64 * NW>(rop, copy.xr);
+        __syncthreads();
+        if (PRE && k0 + KT < kend) {
+            vm_next = produce(k0 + KT);
+            copy.load_lat(k0 + KT, kend, 0);
+            copy.load_rot(k0 + KT, kend);
+        }
+        if (!keys.active) continue;   // (wave-uniform; the wave still takes part in the copies and the barriers)
+        mla_tile_step<Tag>(lat, rop, qf, qvf, oacc, m_run, l_run, mp.p.c_log2, r, g, keys.mask(k0, vm, g));
+    }
+    mla_epilogue<Tag>(mp.p, keys, g, oacc, m_run, l_run);
+}
+
+template <typename Tag, int NW, bool PAGED>
+__global__ __launch_bounds__(64 * NW) void mla_split_kernel(MlaParams mp) {
+    __shared__ __attribute__((aligned(16))) char lds[kMlaLdsBytes];
+    const int hk = blockIdx.y % mp.p.hkv, wt = blockIdx.y / mp.p.hkv;
+    MlaDenseKeys<NW, PAGED> keys(mp.p, hk, wt);
+    std::conditional_t<PAGED, MlaCopy16At<NW>, MlaCopy16Contig<NW>> copy(mp.p, hk, keys.b);
+    mla_decode<Tag, NW>(lds, mp, kMlaDk, kMlaDv, keys, copy);
+}
+
+template <typename Tag, int NW, bool PAGED>
+__global__ __launch_bounds__(64 * NW) void mla_sparse_kernel(MlaSparseParams sp) {
+    __shared__ __attribute__((aligned(16))) char lds[kMlaLdsBytes];
+    const int hk = blockIdx.z % sp.mp.p.hkv, wt = blockIdx.z / sp.mp.p.hkv;
+    MlaListKeys<NW, PAGED> keys(sp, hk, wt);
+    MlaCopy16At<NW> copy(sp.mp.p, hk, keys.b);
+    mla_decode<Tag, NW>(lds, sp.mp, kMlaDk, kMlaDv, keys, copy);
+}
+
+// (one K/V head: hk = 0 throughout)
+template <int NW, bool SPARSE>
+__global__ __launch_bounds__(64 * NW) void mla_f8_kernel(MlaF8Params fp) {
+    __shared__ __attribute__((aligned(16))) char lds[kMlaLdsBytes];
+    MlaCopyF8<NW> copy(fp);
+    if constexpr (SPARSE) {
+        MlaListKeys<NW, true> keys(fp.sp, 0, blockIdx.z);
+        mla_decode<bf16_tag, NW>(lds, fp.sp.mp, fp.q_hs, fp.qv_hs, keys, copy);
+    } else {
+        MlaDenseKeys<NW, true> keys(fp.sp.mp.p, 0, blockIdx.y);
+        mla_decode<bf16_tag, NW>(lds, fp.sp.mp, fp.q_hs, fp.qv_hs, keys, copy);
     }
 }
 
@@ -339,720 +679,6 @@ __global__ __launch_bounds__(256) void mla_combine_kernel(KvParams p, int S, lon
         *reinterpret_cast<u32x2*>(p.o + orow * DV + col) = v;
     }
     if (c == 0) p.lse[row] = sum > 0.f ? m + logf(sum) : -INFINITY;
-}
-
-template <typename Tag, int NW>
-hipError_t launch_mla_split(const MlaParams& mp, int S, int batch, hipStream_t st) {
-    const int wg_tiles = (mp.p.rows + 16 * NW - 1) / (16 * NW);
-    const dim3 grid((unsigned)S, (unsigned)(wg_tiles * mp.p.hkv), (unsigned)batch);
-    if (mp.p.table) hipLaunchKernelGGL((mla_split_kernel<Tag, NW, true>), grid, dim3(64 * NW), 0, st, mp);
-    else hipLaunchKernelGGL((mla_split_kernel<Tag, NW, false>), grid, dim3(64 * NW), 0, st, mp);
-    return hipGetLastError();
-}
-
-template <typename Tag>
-hipError_t launch_mla_t(const MlaParams& mp, int S, int batch, hipStream_t st) {
-    const int nw = mla_waves(mp.p.rows);
-    hipError_t e = nw == 1 ? launch_mla_split<Tag, 1>(mp, S, batch, st)
-                 : nw == 2 ? launch_mla_split<Tag, 2>(mp, S, batch, st) : launch_mla_split<Tag, 4>(mp, S, batch, st);
-    if (e != hipSuccess || S == 1) return e;
-    const long long nrows = (long long)batch * mp.p.hq * mp.p.nq;
-    hipLaunchKernelGGL((mla_combine_kernel<Tag>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st, mp.p, S, nrows);
-    return hipGetLastError();
-}
-
-// ---- sparse MLA (fa_mla_sparse_forward): the keys of a (sequence b, query token i, K/V head hk) are the topk entries of a list
-// of token positions.  mla_sparse_kernel is mla_split_kernel with another producer of ko / vo: a workgroup serves one list
-// (blockIdx.x = b * nq + i; its rows are the G heads of hk, 16 a wave), a tile is 32 list positions, and from ko / vo on the copy
-// is the PAGED branch of load_lat / load_rot there (wave-uniform latent row through v_readlane, 16 bytes a lane, MlaSwz image).
-// Lane l holds entry j0 + (l & 31): one coalesced 128-byte read two tiles ahead of its use; a tile ahead the lane decides
-// visibility (0 <= entry < len_b, and <= len_b - nq + i if causal) and, paged, looks up its page.  An entry that is not visible
-// is never turned into an address: its row is zeros in LDS and its score is -inf by the tile's 32-bit ballot of the per-key flag.
-// A visible entry on a page outside the pool or in a cache row outside the cache is a zero row too, with score 0 (the page rule
-// of fa_decode.hip).  Splits cut the list positions [0, topk) into ranges of whole tiles; partials and mla_combine_kernel as above.
-struct MlaSparseParams {
-    MlaParams mp;          // mp.p.nq: the query tokens of a sequence (the window fields are not used)
-    const int* idx;        // entry j of (b, i, hk): idx[b * ix_bs + i * ix_ts + hk * ix_hs + j]; untrusted device memory
-    long long ix_bs, ix_ts, ix_hs;
-    int topk, causal;
-};
-
-template <typename Tag, int NW, bool PAGED>
-__global__ __launch_bounds__(64 * NW) void mla_sparse_kernel(MlaSparseParams sp) {
-    constexpr int KT = kMlaKT, DK = kMlaDk, DV = kMlaDv, NDB = DV / 16, T = 64 * NW;
-    constexpr int LCH = KT * (DV / 8) / T, RCH = KT * (DK / 8) / T;
-    static_assert(LCH * T == KT * DV / 8 && RCH >= 1, "tile copy");
-    __shared__ __attribute__((aligned(16))) char lds[kMlaLdsBytes];
-    char* const lat = lds;
-    char* const rop = lds + kMlaLatBytes;
-    const KvParams& p = sp.mp.p;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, g = lane >> 4;
-    const int s = blockIdx.y, S = gridDim.y;
-    const int hk = blockIdx.z % p.hkv, wt = blockIdx.z / p.hkv;
-    const int nq = p.nq, b = blockIdx.x / nq, qi = blockIdx.x - b * nq;
-    int L_b, P_b;
-    const int lk = kv_len_k(p, b, 0, L_b, P_b);
-    // visible token positions: [0, tlim)
-    const int thi = sp.causal ? lk - nq + qi : lk - 1;
-    const unsigned tlim = thi >= 0 ? (unsigned)thi + 1u : 0u;
-    // list positions [jbeg, jend) of split s: whole tiles
-    const int nt = (sp.topk + KT - 1) / KT;
-    const int jbeg = (int)((long long)s * nt / S) * KT, jend = min(sp.topk, (int)((long long)(s + 1) * nt / S) * KT);
-
-    // this wave's row tile of the G heads (none: the wave only copies) and this lane's head
-    const int pr0 = 16 * NW * wt + 16 * w, pr = pr0 + r;
-    const bool active = pr0 < p.G, valid = pr < p.G;
-    const int h = hk * p.G + (valid ? pr : 0);
-
-    s16x8 qf[DK / 32], qvf[DV / 32];
-    {
-        const buf_rsrc_t q_rs = make_rsrc(p.q + b * p.q_bs, (unsigned)(((nq - 1) * p.q_ts + p.hq * DK) * 2));
-        const buf_rsrc_t qv_rs = make_rsrc(sp.mp.qv + b * sp.mp.qv_bs, (unsigned)(((nq - 1) * sp.mp.qv_ts + p.hq * DV) * 2));
-#pragma unroll
-        for (int ks = 0; ks < DK / 32; ++ks) qf[ks] = buf_load_frag(q_rs, valid ? (qi * p.q_ts + h * DK + 32 * ks + 8 * g) * 2 : kOobOff);
-#pragma unroll
-        for (int ks = 0; ks < DV / 32; ++ks) qvf[ks] = buf_load_frag(qv_rs, valid ? (qi * sp.mp.qv_ts + h * DV + 32 * ks + 8 * g) * 2 : kOobOff);
-    }
-    // contiguous: cache row (bidx ? bidx[b] : b); a row outside the cache holds zero rows
-    long long crow = b;
-    if (!PAGED && p.bidx) {
-        const int ix = p.bidx[b];
-        crow = (unsigned)ix < (unsigned)p.bcache ? ix : -1;
-    }
-    const int* tbl = PAGED ? p.table + b * p.tbl_rs : nullptr;
-    const int* il = sp.idx + b * sp.ix_bs + qi * sp.ix_ts + hk * sp.ix_hs;
-
-    // The list pipeline of lane l (list position + (l & 31) of a tile): e2 the raw entry of the tile after next; s1 the next
-    // tile's visible entry as its token position (contiguous) or its slot in its page pg1 (paged), -1 = not visible.
-    int e2 = -1, s1 = -1, pg1 = -1;
-    auto entry = [&](int jt) {
-        const int pos = jt + (lane & 31);
-        return pos < jend ? il[pos] : -1;
-    };
-    auto advance = [&](int jt) {   // e2 -> s1 (pg1); e2 = the entries of the tile at jt
-        const bool vis = (unsigned)e2 < tlim;
-        if constexpr (PAGED) {
-            const unsigned j = (unsigned)e2 / (unsigned)p.ps;   // (< max_blocks_per_seq: e2 < len_b <= the capacity)
-            s1 = vis ? (int)((unsigned)e2 - j * (unsigned)p.ps) : -1;
-            pg1 = vis ? tbl[j] : -1;
-        } else {
-            s1 = vis ? e2 : -1;
-        }
-        e2 = entry(jt);
-    };
-    if (jbeg < jend) {
-        e2 = entry(jbeg);
-        advance(jbeg + KT);
-    }
-
-    f32x4_t oacc[NDB];
-#pragma unroll
-    for (int t = 0; t < NDB; ++t) oacc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    float m_run = -INFINITY, l_run = 0.f;
-    const int q4 = r >> 2, p4 = r & 3;
-
-    // One tile's copy, as in mla_split_kernel<.., PAGED = true>: this lane's key has element offsets ko / vo in the two caches,
-    // -1 = not fetched, zeros in LDS.  offsets() returns the tile's visibility flags, bit k = list position kt + k.
-    constexpr bool PRE = LCH <= 8;
-    constexpr int LB = PRE ? LCH : 8;
-    static_assert(LCH % LB == 0, "tile copy");
-    u32x4 xl[LB], xr[RCH];
-    long long ko = -1, vo = -1;
-    const int wu = __builtin_amdgcn_readfirstlane(w);
-    auto offsets = [&](int kt) {
-        ko = vo = -1;
-        if constexpr (PAGED) {
-            if (s1 >= 0 && (unsigned)pg1 < (unsigned)p.nblk) {
-                ko = pg1 * p.kc_bs + (long long)s1 * p.kc_ts;
-                vo = pg1 * p.vc_bs + (long long)s1 * p.vc_ts;
-            }
-        } else if (s1 >= 0 && crow >= 0) {
-            ko = crow * p.kc_bs + (long long)s1 * p.kc_ts;
-            vo = crow * p.vc_bs + (long long)s1 * p.vc_ts;
-        }
-        const unsigned vm = (unsigned)__ballot(s1 >= 0);
-        advance(kt + 2 * KT);
-        return vm;
-    };
-    auto load_lat = [&](int i0) {
-#pragma unroll
-        for (int i = 0; i < LB; ++i) {
-            const int row = (T / 64) * (i0 + i) + wu;
-            const long long ro = ((long long)__builtin_amdgcn_readlane((int)(vo >> 32), row) << 32) |
-                                 (unsigned)__builtin_amdgcn_readlane((int)vo, row);   // (wave-uniform: a scalar base)
-            const bool ok = ro >= 0;
-            const u32x4 y = *reinterpret_cast<const u32x4*>(ok ? p.vc + ro + hk * DV + 8 * lane : p.q);
-            xl[i] = ok ? y : u32x4{0u, 0u, 0u, 0u};
-        }
-    };
-    auto store_lat = [&](int i0) {
-#pragma unroll
-        for (int i = 0; i < LB; ++i) *reinterpret_cast<u32x4*>(lat + MlaSwz::off((T / 64) * (i0 + i) + wu, lane)) = xl[i];
-    };
-    auto load_rot = [&]() {
-#pragma unroll
-        for (int i = 0; i < RCH; ++i) {
-            const int idx = T * i + tid, row = idx >> 3, ch = idx & 7;
-            const long long ro = __shfl(ko, row, 64);
-            const bool ok = ro >= 0;
-            const u32x4 y = *reinterpret_cast<const u32x4*>(ok ? p.kc + ro + hk * DK + 8 * ch : p.q);
-            xr[i] = ok ? y : u32x4{0u, 0u, 0u, 0u};
-        }
-    };
-    auto store_rot = [&]() {
-#pragma unroll
-        for (int i = 0; i < RCH; ++i) {
-            const int idx = T * i + tid;
-            *reinterpret_cast<u32x4*>(rop + TileSwz<64>::off(idx >> 3, idx & 7)) = xr[i];
-        }
-    };
-    unsigned vm_next = 0u;
-    if (PRE && jbeg < jend) {
-        vm_next = offsets(jbeg);
-        load_lat(0);
-        load_rot();
-    }
-
-    for (int k0 = jbeg; k0 < jend; k0 += KT) {
-        unsigned vm = vm_next;
-        if constexpr (!PRE) vm = offsets(k0);
-        __syncthreads();   // every wave has read the previous tile
-        if constexpr (PRE) {
-            store_lat(0);
-        } else {
-#pragma unroll 1
-            for (int i0 = 0; i0 < LCH; i0 += LB) {
-                load_lat(i0);
-                store_lat(i0);
-            }
-            load_rot();
-        }
-        store_rot();
-        __syncthreads();
-        if (PRE && k0 + KT < jend) {
-            vm_next = offsets(k0 + KT);
-            load_lat(0);
-            load_rot();
-        }
-        if (!active) continue;   // (wave-uniform; the wave still takes part in the copies and the barriers)
-
-        // S^T = K Q^T, as in mla_split_kernel
-        f32x4_t sacc[2];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            sacc[kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < DK / 32; ++ks)
-                sacc[kb] = mfma16<Tag>(*reinterpret_cast<const s16x8*>(rop + TileSwz<64>::off(16 * kb + r, 4 * ks + g)), qf[ks], sacc[kb]);
-#pragma unroll
-            for (int ks = 0; ks < DV / 32; ++ks) {
-                if (ks % 4 == 0) __builtin_amdgcn_sched_barrier(0);
-                sacc[kb] = mfma16<Tag>(*reinterpret_cast<const s16x8*>(lat + MlaSwz::off(16 * kb + r, 4 * ks + g)), qvf[ks], sacc[kb]);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("" : "+v"(sacc[0]), "+v"(sacc[1]));
-        // the list's flags: register i of block kb holds list position k0 + 16 kb + 4 g + i
-        const unsigned vg = valid ? vm >> (4 * g) : 0u;
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float x = ((vg >> (16 * kb + i)) & 1u) ? sacc[kb][i] : -INFINITY;
-                sacc[kb][i] = x;
-                mx = fmaxf(mx, x);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);
-        const float m_use = m_new == -INFINITY ? 0.f : m_new;
-        const float alpha = __builtin_amdgcn_exp2f((m_run - m_use) * p.c_log2);
-        const float mc = m_use * p.c_log2;
-        m_run = m_new;
-        l_run *= alpha;
-#pragma unroll
-        for (int t = 0; t < NDB; ++t) oacc[t] *= alpha;
-        u32x4 pk;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const float e0 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][2 * j], p.c_log2, -mc));
-                const float e1 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][2 * j + 1], p.c_log2, -mc));
-                l_run += e0 + e1;
-                pk[2 * kb + j] = pack2<Tag>(e0, e1);
-            }
-        const s16x8 pb = *reinterpret_cast<s16x8*>(&pk);
-#pragma unroll
-        for (int t = 0; t < NDB; ++t) {
-            if (t % 4 == 0) __builtin_amdgcn_sched_barrier(0);
-            const int ch = 2 * t + (p4 >> 1), bo = 8 * (p4 & 1);
-            const s16x4 lo = lds_tr16(lat + MlaSwz::off(4 * g + q4, ch) + bo);
-            const s16x4 hi = lds_tr16(lat + MlaSwz::off(16 + 4 * g + q4, ch) + bo);
-            oacc[t] = mfma16<Tag>(cat8(lo, hi), pb, oacc[t]);
-        }
-    }
-
-    // ---- epilogue (mla_split_kernel's)
-    float l_tot = l_run + __shfl_xor(l_run, 16, 64);
-    l_tot += __shfl_xor(l_tot, 32, 64);
-    const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
-    const float lse_v = l_tot > 0.f ? m_run * p.scale + logf(l_tot) : -INFINITY;
-    if (!valid) return;
-    const size_t row_id = ((size_t)b * p.hq + h) * nq + qi;
-    if (S == 1) {
-        uint16_t* orow = p.o + ((size_t)blockIdx.x * p.hq + h) * DV;
-#pragma unroll
-        for (int t = 0; t < NDB; ++t) {
-            u32x2 v;
-            v[0] = pack2_rn<Tag>(oacc[t][0] * inv, oacc[t][1] * inv);
-            v[1] = pack2_rn<Tag>(oacc[t][2] * inv, oacc[t][3] * inv);
-            *reinterpret_cast<u32x2*>(orow + 16 * t + 4 * g) = v;
-        }
-        if (g == 0) p.lse[row_id] = lse_v;
-    } else {
-        float* prow = p.po + (row_id * S + s) * DV;
-#pragma unroll
-        for (int t = 0; t < NDB; ++t) *reinterpret_cast<f32x4_t*>(prow + 16 * t + 4 * g) = oacc[t] * inv;
-        if (g == 0) p.plse[row_id * S + s] = lse_v;
-    }
-}
-
-template <typename Tag, int NW>
-hipError_t launch_mla_sparse_split(const MlaSparseParams& sp, int S, long long units, hipStream_t st) {
-    const int wg_tiles = (sp.mp.p.G + 16 * NW - 1) / (16 * NW);
-    const dim3 grid((unsigned)units, (unsigned)S, (unsigned)(wg_tiles * sp.mp.p.hkv));
-    if (sp.mp.p.table) hipLaunchKernelGGL((mla_sparse_kernel<Tag, NW, true>), grid, dim3(64 * NW), 0, st, sp);
-    else hipLaunchKernelGGL((mla_sparse_kernel<Tag, NW, false>), grid, dim3(64 * NW), 0, st, sp);
-    return hipGetLastError();
-}
-
-template <typename Tag>
-hipError_t launch_mla_sparse_t(const MlaSparseParams& sp, int S, long long units, hipStream_t st) {
-    const int nw = mla_waves(sp.mp.p.G);
-    hipError_t e = nw == 1 ? launch_mla_sparse_split<Tag, 1>(sp, S, units, st)
-                 : nw == 2 ? launch_mla_sparse_split<Tag, 2>(sp, S, units, st) : launch_mla_sparse_split<Tag, 4>(sp, S, units, st);
-    if (e != hipSuccess || S == 1) return e;
-    const long long nrows = units * sp.mp.p.hq;
-    hipLaunchKernelGGL((mla_combine_kernel<Tag>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st, sp.mp.p, S, nrows);
-    return hipGetLastError();
-}
-
-}  // namespace
-
-// Waves a workgroup: one per 16-row tile of the rows = G * Nq packed rows of a (sequence, K/V head), at most four (one per SIMD)
-int mla_waves(int64_t rows) { return rows <= 16 ? 1 : rows <= 32 ? 2 : 4; }
-
-// kv_num_splits for mla_split_kernel.  A unit is a workgroup of mla_waves(rows) waves over 16 * waves rows, not a wave over 16.
-// The 16 x 512 fp32 accumulator beside the q and qv fragments takes a wave past 256 registers, so one wave runs per SIMD and a
-// CU holds 4 / waves workgroups (36 KiB of LDS each).  Enough splits to fill the 256 CUs once, none shorter than 128 keys, at
-// most 256 (the combine's weight row).
-int mla_num_splits(int64_t batch, int64_t heads_kv, int64_t rows, int64_t cache_len) {
-    constexpr int64_t kCUs = 256, kMinKeys = 128;
-    if (rows <= 0) return 1;
-    const int64_t nw = mla_waves(rows), per_cu = 4 / nw;
-    const int64_t units = batch * heads_kv * ((rows + 16 * nw - 1) / (16 * nw));
-    if (units <= 0 || cache_len <= 0) return 1;
-    int64_t s = (kCUs * per_cu + units - 1) / units;
-    s = std::min<int64_t>(s, (cache_len + kMinKeys - 1) / kMinKeys);
-    return (int)std::max<int64_t>(1, std::min<int64_t>(s, 256));
-}
-
-// mla_num_splits for mla_sparse_kernel, with its constants.  A unit is a workgroup of mla_waves(group) waves over 16 * waves of the
-// group heads of one list (units = batch * seqlen_q lists a K/V head); the splits cut the topk list positions, none shorter than
-// 128 entries.
-int mla_sparse_num_splits(int64_t units, int64_t heads_kv, int64_t group, int64_t topk) {
-    constexpr int64_t kCUs = 256, kMinKeys = 128;
-    if (group <= 0) return 1;
-    const int64_t nw = mla_waves(group), per_cu = 4 / nw;
-    const int64_t wgs = units * heads_kv * ((group + 16 * nw - 1) / (16 * nw));
-    if (wgs <= 0 || topk <= 0) return 1;
-    int64_t s = (kCUs * per_cu + wgs - 1) / wgs;
-    s = std::min<int64_t>(s, (topk + kMinKeys - 1) / kMinKeys);
-    return (int)std::max<int64_t>(1, std::min<int64_t>(s, 256));
-}
-
-hipError_t launch_mla_sparse(const MlaSparseArgs& a, hipStream_t st) {
-    const KvArgs& kv = a.kv;
-    if (kv.d != kMlaDk || kv.d_v != kMlaDv) return hipErrorInvalidValue;   // (the C layer's check)
-    MlaSparseParams sp;
-    sp.mp.p = kv_make_params(kv);
-    sp.mp.qv = (const uint16_t*)kv.qv; sp.mp.qv_bs = kv.qv_bs; sp.mp.qv_ts = (int)kv.qv_ts;
-    sp.idx = a.indices; sp.ix_bs = a.ix_bs; sp.ix_ts = a.ix_ts; sp.ix_hs = a.ix_hs;
-    sp.topk = (int)a.topk; sp.causal = kv.causal;
-    const int S = (int)kv.num_splits;
-    // workspace (S > 1): kv_workspace_bytes at d_v, the O partials and then the lse partials
-    const size_t q_rows = (size_t)kv.batch * kv.heads_q * kv.seqlen_q;
-    sp.mp.p.po = (float*)kv.workspace;
-    sp.mp.p.plse = S > 1 ? (float*)((char*)kv.workspace + ((q_rows * S * kMlaDv * 4 + 255) & ~(size_t)255)) : nullptr;
-    const long long units = (long long)kv.batch * kv.seqlen_q;
-    return kv.dtype == 1 ? launch_mla_sparse_t<f16_tag>(sp, S, units, st) : launch_mla_sparse_t<bf16_tag>(sp, S, units, st);
-}
-
-hipError_t launch_kvcache_mla(const KvArgs& a, hipStream_t st) {
-    if (a.d != kMlaDk || a.d_v != kMlaDv) return hipErrorInvalidValue;   // (the C layer's check)
-    MlaParams mp;
-    mp.p = kv_make_params(a);
-    mp.qv = (const uint16_t*)a.qv; mp.qv_bs = a.qv_bs; mp.qv_ts = (int)a.qv_ts;
-    const int S = (int)a.num_splits;
-    // workspace (S > 1): kv_workspace_bytes at d_v, the O partials and then the lse partials
-    const size_t q_rows = (size_t)a.batch * a.heads_q * a.seqlen_q;
-    mp.p.po = (float*)a.workspace;
-    mp.p.plse = S > 1 ? (float*)((char*)a.workspace + ((q_rows * S * kMlaDv * 4 + 255) & ~(size_t)255)) : nullptr;
-    return a.dtype == 1 ? launch_mla_t<f16_tag>(mp, S, (int)a.batch, st) : launch_mla_t<bf16_tag>(mp, S, (int)a.batch, st);
-}
-
-// ---- the packed 8-bit latent cache (fa_mla_fp8_forward, fa_mla_fp8_pack): FlashMLA's 656-byte token
-//   byte 0 .. 511: 512 e4m3 (the latent, quantised per 128-wide tile) | 512 .. 527: 4 float32 scales | 528 .. 655: 64 bf16 (rotary)
-// in a paged pool, token t of sequence b at pool + page * page_sb + (t % ps) * tok_sb bytes (64-bit), one K/V head, bf16 only.
-// mla_f8_kernel<NW, SPARSE> is mla_split_kernel<bf16_tag, NW, true> (SPARSE: mla_sparse_kernel<bf16_tag, NW, true>) with another
-// copy into the same 36 KiB LDS image; from the barrier after the copy on the two are the same text, so a call on a pool gives
-// the bits of the 16-bit call on the pool's dequantised rows.  The copy: row tid / TPR of the tile belongs to TPR = T / 32
-// threads; a thread loads the row's four scales (one 16-byte load) and its 16-byte chunks c = tid % TPR + TPR i of e4m3 (16 head
-// dims of the 128-wide tile c / 8), and writes for each the two MlaSwz chunks 2c, 2c + 1 of
-//   bf16_rne(fp32(e4m3) * scale)    (one exact widening, one fp32 multiply, one rounding to nearest even).
-// The rotary 128 bytes are 8 chunks, copied as there.  A row that is not fetched (its loads are redirected to the first bytes of
-// q and their results selected away, as in the 16-bit kernels: no address is formed from the key) has zero bytes and zero
-// scales: zeros.  Four waves: a thread holds 4 + 1 + 1 chunks of tile t + 1 while tile t is computed on.
-// The text shared with mla_split_kernel / mla_sparse_kernel carries their comments; a change to the loop there belongs here too
-// (tests/test_mla_fp8_gpu.py holds the two to the same bits).
-namespace {
-
-constexpr int kF8Scales = 512, kF8Rope = 528;   // byte offsets in a token (656 bytes)
-
-struct MlaF8Params {
-    MlaSparseParams sp;    // sp.mp.p.kc / vc are not used; sp.idx, topk: SPARSE only
-    const unsigned char* pool;
-    long long page_sb;     // bytes from page to page
-    int tok_sb;            // bytes from token to token of a page
-    int q_hs, qv_hs;       // head strides of q and qv (elements): the two column ranges of one (.., 576) tensor are 576 apart
-};
-
-// 16 e4m3 bytes times one scale -> the two 16-byte chunks of bf16 they fill
-__device__ __forceinline__ void mla_f8_widen(u32x4 x, float sc, u32x4& lo, u32x4& hi) {
-    uint32_t out[8];
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)x[d], false);
-        const auto b = __builtin_amdgcn_cvt_pk_f32_fp8((int)x[d], true);
-        out[2 * d] = pack2<bf16_tag>(a[0] * sc, a[1] * sc);
-        out[2 * d + 1] = pack2<bf16_tag>(b[0] * sc, b[1] * sc);
-    }
-    lo = u32x4{out[0], out[1], out[2], out[3]};
-    hi = u32x4{out[4], out[5], out[6], out[7]};
-}
-
-template <int NW, bool SPARSE>
-__global__ __launch_bounds__(64 * NW) void mla_f8_kernel(MlaF8Params fp) {
-    using Tag = bf16_tag;
-    constexpr int KT = kMlaKT, DK = kMlaDk, DV = kMlaDv, NDB = DV / 16, T = 64 * NW;
-    constexpr int TPR = T / KT, FCH = (DV / 16) / TPR, RCH = KT * (DK / 8) / T;   // threads a latent row; 16-byte chunks a thread: e4m3, rotary
-    static_assert(TPR * FCH * 16 == DV && 8 % TPR == 0 && RCH >= 1, "tile copy");
-    __shared__ __attribute__((aligned(16))) char lds[kMlaLdsBytes];
-    char* const lat = lds;
-    char* const rop = lds + kMlaLatBytes;
-    const MlaSparseParams& sp = fp.sp;
-    const KvParams& p = sp.mp.p;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, g = lane >> 4;
-    const int s = SPARSE ? blockIdx.y : blockIdx.x, S = SPARSE ? gridDim.y : gridDim.x;
-    const int wt = SPARSE ? blockIdx.z : blockIdx.y;
-    const int nq = p.nq, b = SPARSE ? blockIdx.x / nq : blockIdx.z;
-    int L_b, P_b;
-    const int lk = kv_len_k(p, b, 0, L_b, P_b);   // (one K/V head: hk = 0 throughout)
-
-    // the positions [kbeg, kend) of this split (keys, SPARSE: list positions), this wave's row tile (none: the wave only
-    // copies), this lane's query row: mla_split_kernel's, SPARSE mla_sparse_kernel's
-    int kbeg, kend, qi, h, rlo = 0, rhi = -1;
-    bool active, valid;
-    unsigned tlim = 0u;
-    if constexpr (SPARSE) {
-        qi = blockIdx.x - b * nq;
-        // visible token positions: [0, tlim)
-        const int thi = sp.causal ? lk - nq + qi : lk - 1;
-        tlim = thi >= 0 ? (unsigned)thi + 1u : 0u;
-        // list positions [kbeg, kend) of split s: whole tiles
-        const int nt = (sp.topk + KT - 1) / KT;
-        kbeg = (int)((long long)s * nt / S) * KT;
-        kend = min(sp.topk, (int)((long long)(s + 1) * nt / S) * KT);
-        // this wave's row tile of the G heads (none: the wave only copies) and this lane's head
-        const int pr0 = 16 * NW * wt + 16 * w, pr = pr0 + r;
-        active = pr0 < p.G;
-        valid = pr < p.G;
-        h = valid ? pr : 0;
-    } else {
-        const int rows = p.rows, coff = lk - nq;
-        // the workgroup's rows [wr0, wr1) and the key range of their bands' union; wr0 < rows by the grid
-        const int wr0 = 16 * NW * wt, wr1 = min(wr0 + 16 * NW, rows);
-        kv_split_range(p, lk, nq, wr0 / p.G, (wr1 - 1) / p.G, s, S, kbeg, kend);
-        // this wave's row tile (none: the wave only copies), this lane's query row and its visible keys [rlo, rhi]
-        const int pr0 = wr0 + 16 * w, pr = pr0 + r;
-        active = pr0 < rows;
-        valid = pr < rows;
-        const int qlo = min(pr0, rows - 1) / p.G;
-        qi = valid ? pr / p.G : qlo;
-        h = valid ? pr - qi * p.G : 0;
-        rlo = max(qi + coff - p.wl, kbeg);
-        rhi = valid ? min(min(qi + coff + p.wr, lk - 1), kend - 1) : -1;
-    }
-
-    s16x8 qf[DK / 32], qvf[DV / 32];
-    {
-        const buf_rsrc_t q_rs = make_rsrc(p.q + b * p.q_bs, (unsigned)(((nq - 1) * p.q_ts + (p.hq - 1) * fp.q_hs + DK) * 2));
-        const buf_rsrc_t qv_rs = make_rsrc(sp.mp.qv + b * sp.mp.qv_bs, (unsigned)(((nq - 1) * sp.mp.qv_ts + (p.hq - 1) * fp.qv_hs + DV) * 2));
-#pragma unroll
-        for (int ks = 0; ks < DK / 32; ++ks) qf[ks] = buf_load_frag(q_rs, valid ? (qi * p.q_ts + h * fp.q_hs + 32 * ks + 8 * g) * 2 : kOobOff);
-#pragma unroll
-        for (int ks = 0; ks < DV / 32; ++ks) qvf[ks] = buf_load_frag(qv_rs, valid ? (qi * sp.mp.qv_ts + h * fp.qv_hs + 32 * ks + 8 * g) * 2 : kOobOff);
-    }
-    const int* tbl = p.table + b * p.tbl_rs;
-
-    // The producer of this lane's key (position + (lane & 31) of a tile).  Dense: kv_split_kernel's page lookup, done by every
-    // wave for itself, the next tile's a tile ahead.  SPARSE: the list pipeline of mla_sparse_kernel: e2 the raw entry of the
-    // tile after next (one coalesced 128-byte read), s1 the next tile's visible entry as its slot in its page pg1, -1 = not
-    // visible: an entry that is not visible is never turned into an address.
-    int j0 = 0, s0 = 0, pg = -1;
-    int e2 = -1, s1 = -1, pg1 = -1;
-    const int* il = nullptr;
-    auto page_of = [&](int jt, int st, int kt) {
-        int j = jt, sl = st + (lane & 31);
-        if (sl >= p.ps) { sl -= p.ps; ++j; }
-        if (sl >= p.ps) ++j;
-        return kt + (lane & 31) < kend ? tbl[j] : -1;
-    };
-    auto entry = [&](int jt) {
-        const int pos = jt + (lane & 31);
-        return pos < kend ? il[pos] : -1;
-    };
-    auto advance = [&](int jt) {   // e2 -> s1, pg1; e2 = the entries of the tile at jt
-        const bool vis = (unsigned)e2 < tlim;
-        const unsigned j = (unsigned)e2 / (unsigned)p.ps;   // (< max_blocks_per_seq: e2 < len_b <= the capacity)
-        s1 = vis ? (int)((unsigned)e2 - j * (unsigned)p.ps) : -1;
-        pg1 = vis ? tbl[j] : -1;
-        e2 = entry(jt);
-    };
-    if constexpr (SPARSE) {
-        il = sp.idx + b * sp.ix_bs + qi * sp.ix_ts;
-        if (kbeg < kend) {
-            e2 = entry(kbeg);
-            advance(kbeg + KT);
-        }
-    } else if (kbeg < kend) {
-        j0 = kbeg / p.ps;
-        s0 = kbeg - j0 * p.ps;
-        pg = page_of(j0, s0, kbeg);
-    }
-
-    f32x4_t oacc[NDB];
-#pragma unroll
-    for (int t = 0; t < NDB; ++t) oacc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    float m_run = -INFINITY, l_run = 0.f;
-    const int q4 = r >> 2, p4 = r & 3;
-
-    // One tile's copy, loads and LDS writes apart.  to: the byte offset of this lane's token in the pool, -1 = reads as zeros
-    // (past the split's end, not visible, or on a page outside the pool); offsets() returns the SPARSE tile's visibility flags.
-    constexpr bool PRE = NW == 4;
-    constexpr int FB = FCH < 8 ? FCH : 8;
-    static_assert(FCH % FB == 0, "tile copy");
-    u32x4 xl[FB], xs, xr[RCH];
-    long long to = -1, lro = -1;
-    const int lrow = tid / TPR, lc0 = tid % TPR;
-    auto offsets = [&](int kt) {
-        to = -1;
-        unsigned vm = 0u;
-        if constexpr (SPARSE) {
-            if (s1 >= 0 && (unsigned)pg1 < (unsigned)p.nblk) to = pg1 * fp.page_sb + (long long)s1 * fp.tok_sb;
-            vm = (unsigned)__ballot(s1 >= 0);
-            advance(kt + 2 * KT);
-        } else {
-            int sl = s0 + (lane & 31);
-            if (sl >= p.ps) sl -= p.ps;
-            if (sl >= p.ps) sl -= p.ps;
-            if ((unsigned)pg < (unsigned)p.nblk) to = pg * fp.page_sb + (long long)sl * fp.tok_sb;
-            s0 += KT;
-            if (s0 >= p.ps) { s0 -= p.ps; ++j0; }
-            if (s0 >= p.ps) { s0 -= p.ps; ++j0; }
-            if (kt + KT < kend) pg = page_of(j0, s0, kt + KT);   // the next tile's lookup, a tile ahead of its use
-        }
-        return vm;
-    };
-    auto load_lat = [&](int i0) {
-        if (i0 == 0) {
-            lro = __shfl(to, lrow, 64);
-            const u32x4 y = *reinterpret_cast<const u32x4*>(lro >= 0 ? fp.pool + lro + kF8Scales : (const unsigned char*)p.q);
-            xs = lro >= 0 ? y : u32x4{0u, 0u, 0u, 0u};
-        }
-        const bool ok = lro >= 0;
-#pragma unroll
-        for (int i = 0; i < FB; ++i) {
-            const u32x4 y = *reinterpret_cast<const u32x4*>(ok ? fp.pool + lro + 16 * (lc0 + TPR * (i0 + i)) : (const unsigned char*)p.q);
-            xl[i] = ok ? y : u32x4{0u, 0u, 0u, 0u};
-        }
-    };
-    auto store_lat = [&](int i0) {
-#pragma unroll
-        for (int i = 0; i < FB; ++i) {
-            const int c = lc0 + TPR * (i0 + i), tile = (TPR * (i0 + i)) >> 3;
-            const uint32_t sb = tile == 0 ? xs[0] : tile == 1 ? xs[1] : tile == 2 ? xs[2] : xs[3];
-            u32x4 lo, hi;
-            mla_f8_widen(xl[i], __uint_as_float(sb), lo, hi);
-            *reinterpret_cast<u32x4*>(lat + MlaSwz::off(lrow, 2 * c)) = lo;
-            *reinterpret_cast<u32x4*>(lat + MlaSwz::off(lrow, 2 * c + 1)) = hi;
-        }
-    };
-    auto load_rot = [&]() {
-#pragma unroll
-        for (int i = 0; i < RCH; ++i) {
-            const int idx = T * i + tid, row = idx >> 3, ch = idx & 7;
-            const long long ro = __shfl(to, row, 64);
-            const bool ok = ro >= 0;
-            const u32x4 y = *reinterpret_cast<const u32x4*>(ok ? fp.pool + ro + kF8Rope + 16 * ch : (const unsigned char*)p.q);
-            xr[i] = ok ? y : u32x4{0u, 0u, 0u, 0u};
-        }
-    };
-    auto store_rot = [&]() {
-#pragma unroll
-        for (int i = 0; i < RCH; ++i) {
-            const int idx = T * i + tid;
-            *reinterpret_cast<u32x4*>(rop + TileSwz<64>::off(idx >> 3, idx & 7)) = xr[i];
-        }
-    };
-    unsigned vm_next = 0u;
-    if (PRE && kbeg < kend) {
-        vm_next = offsets(kbeg);
-        load_lat(0);
-        load_rot();
-    }
-
-    for (int k0 = kbeg; k0 < kend; k0 += KT) {
-        unsigned vm = vm_next;
-        if constexpr (!PRE) vm = offsets(k0);
-        __syncthreads();   // every wave has read the previous tile
-        if constexpr (PRE) {
-            store_lat(0);
-        } else {
-#pragma unroll 1
-            for (int i0 = 0; i0 < FCH; i0 += FB) {
-                load_lat(i0);
-                store_lat(i0);
-            }
-            load_rot();
-        }
-        store_rot();
-        __syncthreads();
-        if (PRE && k0 + KT < kend) {
-            vm_next = offsets(k0 + KT);
-            load_lat(0);
-            load_rot();
-        }
-        if (!active) continue;   // (wave-uniform; the wave still takes part in the copies and the barriers)
-
-        // ---- from here to the end: mla_split_kernel's text (SPARSE: mla_sparse_kernel's mask)
-        // S^T = K Q^T: A = key 16 kb + r, head dims 32 ks + 8 g .. of the rotary row, then of the latent row
-        f32x4_t sacc[2];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            sacc[kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < DK / 32; ++ks)
-                sacc[kb] = mfma16<Tag>(*reinterpret_cast<const s16x8*>(rop + TileSwz<64>::off(16 * kb + r, 4 * ks + g)), qf[ks], sacc[kb]);
-#pragma unroll
-            for (int ks = 0; ks < DV / 32; ++ks) {
-                // (four operand reads in flight: hipcc would otherwise hoist all of a tile's reads and spill)
-                if (ks % 4 == 0) __builtin_amdgcn_sched_barrier(0);
-                sacc[kb] = mfma16<Tag>(*reinterpret_cast<const s16x8*>(lat + MlaSwz::off(16 * kb + r, 4 * ks + g)), qvf[ks], sacc[kb]);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        // both score tiles live in VGPRs at one point (kv_split_kernel: the second chain must not end in the first one's registers)
-        asm volatile("" : "+v"(sacc[0]), "+v"(sacc[1]));
-        // register i of block kb holds position k0 + 16 kb + 4 g + i: the row's band [rlo, rhi], SPARSE the list's flags
-        const unsigned vg = valid ? vm >> (4 * g) : 0u;
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                bool vis;
-                if constexpr (SPARSE) {
-                    vis = (vg >> (16 * kb + i)) & 1u;
-                } else {
-                    const int key = k0 + 16 * kb + 4 * g + i;
-                    vis = key >= rlo && key <= rhi;
-                }
-                const float x = vis ? sacc[kb][i] : -INFINITY;
-                sacc[kb][i] = x;
-                mx = fmaxf(mx, x);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);
-        const float m_use = m_new == -INFINITY ? 0.f : m_new;
-        const float alpha = __builtin_amdgcn_exp2f((m_run - m_use) * p.c_log2);
-        const float mc = m_use * p.c_log2;
-        m_run = m_new;
-        l_run *= alpha;
-#pragma unroll
-        for (int t = 0; t < NDB; ++t) oacc[t] *= alpha;
-        // P^T as the B operand of O^T = V^T P^T: k-slot 8 g + j is key 4 g + j (j < 4) and 16 + 4 g + j - 4 (j >= 4)
-        u32x4 pk;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const float e0 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][2 * j], p.c_log2, -mc));
-                const float e1 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][2 * j + 1], p.c_log2, -mc));
-                l_run += e0 + e1;
-                pk[2 * kb + j] = pack2<Tag>(e0, e1);
-            }
-        const s16x8 pb = *reinterpret_cast<s16x8*>(&pk);
-        // V^T operand from the same latent image: rows (keys) 4 g + q and 16 + 4 g + q, head dims 16 t + 4 p ..
-#pragma unroll
-        for (int t = 0; t < NDB; ++t) {
-            if (t % 4 == 0) __builtin_amdgcn_sched_barrier(0);
-            const int ch = 2 * t + (p4 >> 1), bo = 8 * (p4 & 1);
-            const s16x4 lo = lds_tr16(lat + MlaSwz::off(4 * g + q4, ch) + bo);
-            const s16x4 hi = lds_tr16(lat + MlaSwz::off(16 + 4 * g + q4, ch) + bo);
-            oacc[t] = mfma16<Tag>(cat8(lo, hi), pb, oacc[t]);
-        }
-    }
-
-    // ---- epilogue (kv_split_kernel's): O^T register i of block t is head dim 16 t + 4 g + i
-    float l_tot = l_run + __shfl_xor(l_run, 16, 64);
-    l_tot += __shfl_xor(l_tot, 32, 64);
-    const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
-    const float lse_v = l_tot > 0.f ? m_run * p.scale + logf(l_tot) : -INFINITY;
-    if (!valid) return;
-    const size_t row_id = ((size_t)b * p.hq + h) * nq + qi;
-    if (S == 1) {
-        uint16_t* orow = p.o + (((size_t)b * nq + qi) * p.hq + h) * DV;
-#pragma unroll
-        for (int t = 0; t < NDB; ++t) {
-            u32x2 v;
-            v[0] = pack2_rn<Tag>(oacc[t][0] * inv, oacc[t][1] * inv);
-            v[1] = pack2_rn<Tag>(oacc[t][2] * inv, oacc[t][3] * inv);
-            *reinterpret_cast<u32x2*>(orow + 16 * t + 4 * g) = v;
-        }
-        if (g == 0) p.lse[row_id] = lse_v;
-    } else {
-        float* prow = p.po + (row_id * S + s) * DV;
-#pragma unroll
-        for (int t = 0; t < NDB; ++t) *reinterpret_cast<f32x4_t*>(prow + 16 * t + 4 * g) = oacc[t] * inv;
-        if (g == 0) p.plse[row_id * S + s] = lse_v;
-    }
-}
-
-template <int NW>
-hipError_t launch_mla_f8_split(const MlaF8Params& fp, bool sparse, int S, int batch, hipStream_t st) {
-    const KvParams& p = fp.sp.mp.p;
-    if (sparse) {
-        const dim3 grid((unsigned)(batch * p.nq), (unsigned)S, (unsigned)((p.G + 16 * NW - 1) / (16 * NW)));
-        hipLaunchKernelGGL((mla_f8_kernel<NW, true>), grid, dim3(64 * NW), 0, st, fp);
-    } else {
-        const dim3 grid((unsigned)S, (unsigned)((p.rows + 16 * NW - 1) / (16 * NW)), (unsigned)batch);
-        hipLaunchKernelGGL((mla_f8_kernel<NW, false>), grid, dim3(64 * NW), 0, st, fp);
-    }
-    return hipGetLastError();
 }
 
 // fa_mla_fp8_pack: one wave a new token.  Lane l holds 8 latent elements of tile l / 16: amax over the tile's 16 lanes,
@@ -1122,31 +748,108 @@ __global__ __launch_bounds__(256) void mla_f8_pack_kernel(MlaF8PackParams a) {
         *reinterpret_cast<u32x4*>(dst + kF8Rope + 16 * lane) = *reinterpret_cast<const u32x4*>(a.rope + b * a.rope_bs + i * a.rope_ts + 8 * lane);
 }
 
+// ---- host
+
+// The split rule of every form.  A unit is a workgroup of mla_waves(rows) waves over 16 * waves of the rows that share a key
+// stream; there are lists * heads_kv such streams.  The 16 x 512 fp32 accumulator beside the q and qv fragments takes a wave past
+// 256 registers, so one wave runs per SIMD and a CU holds 4 / waves workgroups (36 KiB of LDS each).  Enough splits to fill the
+// 256 CUs once, none shorter than 128 keys, at most 256 (the combine's weight row).
+int mla_split_rule(int64_t lists, int64_t heads_kv, int64_t rows, int64_t keys) {
+    constexpr int64_t kCUs = 256, kMinKeys = 128;
+    if (rows <= 0) return 1;
+    const int64_t nw = mla_waves(rows), per_cu = 4 / nw;
+    const int64_t units = lists * heads_kv * ((rows + 16 * nw - 1) / (16 * nw));
+    if (units <= 0 || keys <= 0) return 1;
+    int64_t s = (kCUs * per_cu + units - 1) / units;
+    s = std::min<int64_t>(s, (keys + kMinKeys - 1) / kMinKeys);
+    return (int)std::max<int64_t>(1, std::min<int64_t>(s, 256));
+}
+
+// What the three launchers share: the kernel parameters of the call in mp, with the workspace (S > 1: kv_workspace_bytes at d_v,
+// the O partials and then the lse partials); the split kernel with the wave count of the rows of a workgroup's key stream (lists:
+// the G heads, else the G * Nq packed rows) through split(tag, waves), which returns the launch's error; then the combine.
+template <typename Tag, typename Split>
+hipError_t mla_launch(MlaParams& mp, const KvArgs& kv, bool lists, hipStream_t st, Split&& split) {
+    mp.p = kv_make_params(kv);
+    mp.qv = (const uint16_t*)kv.qv; mp.qv_bs = kv.qv_bs; mp.qv_ts = (int)kv.qv_ts;
+    const int S = (int)kv.num_splits;
+    const size_t q_rows = (size_t)kv.batch * kv.heads_q * kv.seqlen_q;
+    mp.p.po = (float*)kv.workspace;
+    mp.p.plse = S > 1 ? (float*)((char*)kv.workspace + ((q_rows * S * kMlaDv * 4 + 255) & ~(size_t)255)) : nullptr;
+    const int nw = mla_waves(lists ? mp.p.G : mp.p.rows);
+    const hipError_t e = nw == 1 ? split(Tag{}, std::integral_constant<int, 1>{})
+                       : nw == 2 ? split(Tag{}, std::integral_constant<int, 2>{}) : split(Tag{}, std::integral_constant<int, 4>{});
+    if (e != hipSuccess || S == 1) return e;
+    const long long nrows = (long long)q_rows;
+    hipLaunchKernelGGL((mla_combine_kernel<Tag>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st, mp.p, S, nrows);
+    return hipGetLastError();
+}
+
+// the grids: dense (split, row tiles x K/V heads, sequence); lists (list, split, row tiles x K/V heads)
+inline dim3 mla_grid(const KvParams& p, const KvArgs& kv, bool lists, int nw) {
+    const unsigned S = (unsigned)kv.num_splits, tiles = (unsigned)(((lists ? p.G : p.rows) + 16 * nw - 1) / (16 * nw) * p.hkv);
+    return lists ? dim3((unsigned)(kv.batch * kv.seqlen_q), S, tiles) : dim3(S, tiles, (unsigned)kv.batch);
+}
+
 }  // namespace
+
+// Waves a workgroup: one per 16-row tile of the rows = G * Nq packed rows of a (sequence, K/V head), at most four (one per SIMD)
+int mla_waves(int64_t rows) { return rows <= 16 ? 1 : rows <= 32 ? 2 : 4; }
+
+// kv_num_splits for the dense forms: rows = G * Nq packed rows of each of the batch sequences, over cache_len keys
+int mla_num_splits(int64_t batch, int64_t heads_kv, int64_t rows, int64_t cache_len) { return mla_split_rule(batch, heads_kv, rows, cache_len); }
+
+// ... and for the lists: units = batch * seqlen_q lists a K/V head, the group heads of each over topk list positions
+int mla_sparse_num_splits(int64_t units, int64_t heads_kv, int64_t group, int64_t topk) { return mla_split_rule(units, heads_kv, group, topk); }
+
+hipError_t launch_kvcache_mla(const KvArgs& a, hipStream_t st) {
+    if (a.d != kMlaDk || a.d_v != kMlaDv) return hipErrorInvalidValue;   // (the C layer's check)
+    MlaParams mp;
+    auto split = [&](auto tag, auto nw) {
+        using Tag = decltype(tag);
+        constexpr int NW = decltype(nw)::value;
+        const dim3 grid = mla_grid(mp.p, a, false, NW);
+        if (mp.p.table) hipLaunchKernelGGL((mla_split_kernel<Tag, NW, true>), grid, dim3(64 * NW), 0, st, mp);
+        else hipLaunchKernelGGL((mla_split_kernel<Tag, NW, false>), grid, dim3(64 * NW), 0, st, mp);
+        return hipGetLastError();
+    };
+    return a.dtype == 1 ? mla_launch<f16_tag>(mp, a, false, st, split) : mla_launch<bf16_tag>(mp, a, false, st, split);
+}
+
+hipError_t launch_mla_sparse(const MlaSparseArgs& a, hipStream_t st) {
+    const KvArgs& kv = a.kv;
+    if (kv.d != kMlaDk || kv.d_v != kMlaDv) return hipErrorInvalidValue;   // (the C layer's check)
+    MlaSparseParams sp;
+    sp.idx = a.indices; sp.ix_bs = a.ix_bs; sp.ix_ts = a.ix_ts; sp.ix_hs = a.ix_hs;
+    sp.topk = (int)a.topk; sp.causal = kv.causal;
+    auto split = [&](auto tag, auto nw) {
+        using Tag = decltype(tag);
+        constexpr int NW = decltype(nw)::value;
+        const dim3 grid = mla_grid(sp.mp.p, kv, true, NW);
+        if (sp.mp.p.table) hipLaunchKernelGGL((mla_sparse_kernel<Tag, NW, true>), grid, dim3(64 * NW), 0, st, sp);
+        else hipLaunchKernelGGL((mla_sparse_kernel<Tag, NW, false>), grid, dim3(64 * NW), 0, st, sp);
+        return hipGetLastError();
+    };
+    return kv.dtype == 1 ? mla_launch<f16_tag>(sp.mp, kv, true, st, split) : mla_launch<bf16_tag>(sp.mp, kv, true, st, split);
+}
 
 hipError_t launch_mla_f8(const MlaF8Args& a, hipStream_t st) {
     const KvArgs& kv = a.sa.kv;
     if (kv.d != kMlaDk || kv.d_v != kMlaDv || kv.dtype != 2 || kv.heads_kv != 1 || !kv.block_table) return hipErrorInvalidValue;   // (the C layer's checks)
     const bool sparse = a.sa.indices != nullptr;
     MlaF8Params fp;
-    fp.sp.mp.p = kv_make_params(kv);
-    fp.sp.mp.qv = (const uint16_t*)kv.qv; fp.sp.mp.qv_bs = kv.qv_bs; fp.sp.mp.qv_ts = (int)kv.qv_ts;
     fp.sp.idx = a.sa.indices; fp.sp.ix_bs = a.sa.ix_bs; fp.sp.ix_ts = a.sa.ix_ts; fp.sp.ix_hs = 0;
     fp.sp.topk = (int)a.sa.topk; fp.sp.causal = kv.causal;
     fp.pool = (const unsigned char*)a.pool; fp.page_sb = a.page_sb; fp.tok_sb = (int)a.tok_sb;
     fp.q_hs = (int)a.q_hs; fp.qv_hs = (int)a.qv_hs;
-    const int S = (int)kv.num_splits;
-    KvParams& p = fp.sp.mp.p;
-    const size_t q_rows = (size_t)kv.batch * kv.heads_q * kv.seqlen_q;
-    p.po = (float*)kv.workspace;
-    p.plse = S > 1 ? (float*)((char*)kv.workspace + ((q_rows * S * kMlaDv * 4 + 255) & ~(size_t)255)) : nullptr;
-    const int nw = mla_waves(sparse ? p.G : p.rows);
-    hipError_t e = nw == 1 ? launch_mla_f8_split<1>(fp, sparse, S, (int)kv.batch, st)
-                 : nw == 2 ? launch_mla_f8_split<2>(fp, sparse, S, (int)kv.batch, st) : launch_mla_f8_split<4>(fp, sparse, S, (int)kv.batch, st);
-    if (e != hipSuccess || S == 1) return e;
-    const long long nrows = (long long)q_rows;
-    hipLaunchKernelGGL((mla_combine_kernel<bf16_tag>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st, p, S, nrows);
-    return hipGetLastError();
+    auto split = [&](auto, auto nw) {
+        constexpr int NW = decltype(nw)::value;
+        const dim3 grid = mla_grid(fp.sp.mp.p, kv, sparse, NW);
+        if (sparse) hipLaunchKernelGGL((mla_f8_kernel<NW, true>), grid, dim3(64 * NW), 0, st, fp);
+        else hipLaunchKernelGGL((mla_f8_kernel<NW, false>), grid, dim3(64 * NW), 0, st, fp);
+        return hipGetLastError();
+    };
+    return mla_launch<bf16_tag>(fp.sp.mp, kv, sparse, st, split);
 }
 
 hipError_t launch_mla_f8_pack(const MlaF8PackArgs& a, hipStream_t st) {
