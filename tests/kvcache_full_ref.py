@@ -4,6 +4,11 @@ cache row or page, the append (rotated, rounded to the 16-bit dtype, quantised),
 them (dequantised), the rotated queries, the scores (GQA, scale, softcap, ALiBi, the causal / window band aligned bottom-right)
 and the softmax with the sink column.  ALiBi goes with sinks.  It never imports the extension.
 
+Everything up to the rotated queries is addressing, not arithmetic, and lives in front_half, which tests/decode_baseline.py (the
+rounding model of the decode kernels) shares: per sequence it hands out the rotated q, the keys and values as they lie in the
+cache, the scales, slopes and mask parameters.  Both take caches_after: the caches some call left behind, to attend over instead
+of the ones appended here.  full_reference is dense_attention on front_half's sequences.
+
 The parts are the ones the feature tests use: kvcache_varlen_ref.cu_range, kvcache_rotary_ref.rotate64 / round_once / slot_of,
 kvcache_fp8_ref.quantize / dequantize, kvcache_paged_ref.paged_tokens.  tests/test_kvcache_sweep_cpu.py holds this module to
 each of the single-feature references on every case they can express."""
@@ -63,20 +68,23 @@ def dense_attention(qd, kd, vd, causal, window, scale, softcap=0.0, slopes=None,
     return (p @ vv).permute(1, 0, 2), lse, ~vis.any(-1)
 
 
-def full_reference(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlens=None, causal=False, softmax_scale=None,
-                   window=(-1, -1), softcap=0.0, alibi_slopes=None, num_splits=0, block_table=None, cache_batch_idx=None,
-                   cache_leftpad=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True, *, cu_seqlens_q=None,
-                   cu_seqlens_k_new=None, max_seqlen_q=None, sinks=None, k_descale=None, v_descale=None):
-    """The arguments of ex_kvcache_forward (num_splits changes nothing that is defined).  Returns a namespace of
-      o, lse        fp64, in the call's shapes; rows that no sequence owns: o = 0, lse = nan
-      own           bool (total_q,) (packed) or (B, Nq): the tokens some sequence owns
-      novis         bool, own's shape: the owned tokens whose rows see no key (o = 0 exactly, lse = the sink or -inf)
-      k_cache, v_cache   the caches after the call, in the caches' dtype
-      k_mask, v_mask     bool, the caches' shape: the elements the call may write
-      slots         [(b, n, unit, pos)]: new key n of sequence b landed at cache[unit, pos]
-      k_exact       per sequence the fp64 (nnew_b, H_kv, d) value of its new keys before any rounding (rotated when rotary is on)
-      k_new16, v_new16   per sequence the 16-bit values that are stored or quantised (K: rotated and rounded once)
-      L, P, nq, nnew     per sequence: the clamped length and left pad, its query tokens, its new keys"""
+def front_half(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlens=None, causal=False, softmax_scale=None,
+               window=(-1, -1), softcap=0.0, alibi_slopes=None, num_splits=0, block_table=None, cache_batch_idx=None,
+               cache_leftpad=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True, *, cu_seqlens_q=None,
+               cu_seqlens_k_new=None, max_seqlen_q=None, sinks=None, k_descale=None, v_descale=None, caches_after=None):
+    """Everything of a call that is addressing and not arithmetic, shared by full_reference and tests/decode_baseline.py: the
+    packed-tensor clamp, the length clamps, the cache row or pages, the append and, per sequence with query tokens, what its
+    attention reads.  caches_after = (k_cache, v_cache) as some call left them (the caches' shape and dtype): the sequences'
+    keys and values are then read from those instead of from the caches this function appended to itself.
+    Returns (call, seqs).  call: a namespace of the per-call fields full_reference returns (all but o, lse, novis) and of packed,
+    bsz, hq, hkv, d, ps (tokens a page or cache row), paged, e4m3, dtype, scale, causal, window, softcap, sinks, o_shape,
+    lse_shape.  seqs: one namespace per sequence with query tokens:
+      b, start, n   the sequence, its first query token (packed) and its query tokens
+      q             (n, H_q, d) in the tensor dtype, rotated and rounded once when rotary is on
+      q_exact       the fp64 rotation before its rounding (None without rotary)
+      k, v          (lk, H_kv, d) as they lie in the cache: the 16-bit dtype, or e4m3 codes as torch.float8_e4m3fn
+      k_scale, v_scale   (H_kv,) float32 (ones for a 16-bit cache)
+      slopes        (H_q,) or None"""
     packed = cu_seqlens_q is not None
     dtype = q.dtype
     hq, d = q.shape[-2], q.shape[-1]
@@ -90,14 +98,12 @@ def full_reference(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlens=No
     if packed:
         bsz, total_q = len(cu_seqlens_q) - 1, q.shape[0]
         q_rng = [cu_range(cu_seqlens_q, b, total_q, max_seqlen_q) for b in range(bsz)]
-        o = torch.zeros((total_q, hq, d), dtype=torch.float64)
-        lse = torch.full((hq, total_q), math.nan, dtype=torch.float64)
+        o_shape, lse_shape = (total_q, hq, d), (hq, total_q)
         own = torch.zeros((total_q,), dtype=torch.bool)
     else:
         bsz, nq_all = q.shape[0], q.shape[1]
         q_rng = [(0, nq_all)] * bsz
-        o = torch.zeros((bsz, nq_all, hq, d), dtype=torch.float64)
-        lse = torch.full((bsz, hq, nq_all), math.nan, dtype=torch.float64)
+        o_shape, lse_shape = (bsz, nq_all, hq, d), (bsz, hq, nq_all)
         own = torch.ones((bsz, nq_all), dtype=torch.bool)
     if cu_seqlens_k_new is not None:
         kn_rng = [cu_range(cu_seqlens_k_new, b, k_new.shape[0], cap) for b in range(bsz)]
@@ -149,38 +155,74 @@ def full_reference(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlens=No
                 ek[unit, pos], ev[unit, pos] = ks[n], vs[n]
                 k_mask[unit, pos] = v_mask[unit, pos] = True
                 slots.append((b, n, unit, pos))
-    # ---- attention per sequence over the keys as they now lie in the caches
-    novis = torch.zeros(own.shape, dtype=torch.bool)
+    out_bits = (lambda t: t.view(E4M3)) if e4m3 else (lambda t: t)   # noqa: E731
+    # ---- per sequence: the keys as they now lie in the caches (or in the caches some call left behind)
+    rk, rv = (ek, ev) if caches_after is None else (as_bits(caches_after[0]), as_bits(caches_after[1]))
+    assert rk.shape == ek.shape and rv.shape == ev.shape and rk.dtype == ek.dtype
+    seqs = []
     for b in range(bsz):
         start, n = q_rng[b]
         if n == 0:
             continue
         lk = L[b] + nnew[b]
         if block_table is not None:
-            kt, vt = paged_tokens(ek, block_table[b], lk, ps), paged_tokens(ev, block_table[b], lk, ps)
+            kt, vt = paged_tokens(rk, block_table[b], lk, ps), paged_tokens(rv, block_table[b], lk, ps)
         else:
             row = int(cache_batch_idx[b]) if cache_batch_idx is not None else b
-            if 0 <= row < ek.shape[0]:
-                kt, vt = ek[row, P[b]:lk], ev[row, P[b]:lk]
+            if 0 <= row < rk.shape[0]:
+                kt, vt = rk[row, P[b]:lk], rv[row, P[b]:lk]
             else:   # a row outside the cache reads as zeros
-                kt, vt = torch.zeros((lk - P[b], hkv, d), dtype=ek.dtype), torch.zeros((lk - P[b], hkv, d), dtype=ev.dtype)
-        if e4m3:
-            kd = kt.view(E4M3).double() * scale_row(k_descale, b).double().view(1, hkv, 1)
-            vd = vt.view(E4M3).double() * scale_row(v_descale, b).double().view(1, hkv, 1)
-        else:
-            kd, vd = kt.double(), vt.double()
+                kt, vt = torch.zeros((lk - P[b], hkv, d), dtype=rk.dtype), torch.zeros((lk - P[b], hkv, d), dtype=rv.dtype)
         qb = q[start:start + n] if packed else q[b]
+        q_exact = None
         if rotary:
             first = L[b] - P[b]
-            qb = round_once(rotate64(qb, rotary_cos, rotary_sin, [first + (i if per_token else 0) for i in range(n)], rotary_interleaved), dtype)
+            q_exact = rotate64(qb, rotary_cos, rotary_sin, [first + (i if per_token else 0) for i in range(n)], rotary_interleaved)
+            qb = round_once(q_exact, dtype)
         sl = None if alibi_slopes is None else (alibi_slopes[b] if alibi_slopes.dim() == 2 else alibi_slopes)
-        ob, lb, nv = dense_attention(qb.double(), kd, vd, bool(causal), window, scale, softcap, sl, sinks)
+        own_b = slice(start, start + n) if packed else b
         if packed:
-            o[start:start + n], lse[:, start:start + n] = ob, lb
             own[start:start + n] = True
-            novis[start:start + n] = nv
-        else:
-            o[b], lse[b], novis[b] = ob, lb, nv
-    out_bits = (lambda t: t.view(E4M3)) if e4m3 else (lambda t: t)   # noqa: E731
-    return SimpleNamespace(o=o, lse=lse, own=own, novis=novis, k_cache=out_bits(ek), v_cache=out_bits(ev), k_mask=k_mask, v_mask=v_mask, slots=slots,
-                           k_exact=k_exact, k_new16=k_new16, v_new16=v_new16, L=L, P=P, nq=nq, nnew=nnew)
+        seqs.append(SimpleNamespace(b=b, start=start, n=n, rows=own_b, q=qb, q_exact=q_exact, k=out_bits(kt), v=out_bits(vt),
+                                    k_scale=scale_row(k_descale, b) if e4m3 else torch.ones((hkv,), dtype=torch.float32),
+                                    v_scale=scale_row(v_descale, b) if e4m3 else torch.ones((hkv,), dtype=torch.float32), slopes=sl))
+    call = SimpleNamespace(own=own, k_cache=out_bits(ek), v_cache=out_bits(ev), k_mask=k_mask, v_mask=v_mask, slots=slots, k_exact=k_exact,
+                           k_new16=k_new16, v_new16=v_new16, L=L, P=P, nq=nq, nnew=nnew, q_first=[a for a, _ in q_rng], packed=packed, bsz=bsz, hq=hq, hkv=hkv, d=d, ps=ps,
+                           paged=block_table is not None, e4m3=e4m3, dtype=dtype, scale=scale, causal=bool(causal), window=tuple(window),
+                           softcap=float(softcap), sinks=sinks, o_shape=o_shape, lse_shape=lse_shape)
+    return call, seqs
+
+
+def place(call, sq, o, lse, ob, lb):
+    """sequence sq's (n, H_q, d) rows ob and (H_q, n) rows lb into the call's o and lse"""
+    if call.packed:
+        o[sq.start:sq.start + sq.n], lse[:, sq.start:sq.start + sq.n] = ob, lb
+    else:
+        o[sq.b], lse[sq.b] = ob, lb
+
+
+def full_reference(*args, **kwargs):
+    """The arguments of ex_kvcache_forward (num_splits changes nothing that is defined) and caches_after (front_half).  Returns a
+    namespace of
+      o, lse        fp64, in the call's shapes; rows that no sequence owns: o = 0, lse = nan
+      own           bool (total_q,) (packed) or (B, Nq): the tokens some sequence owns
+      novis         bool, own's shape: the owned tokens whose rows see no key (o = 0 exactly, lse = the sink or -inf)
+      k_cache, v_cache   the caches after the call, in the caches' dtype
+      k_mask, v_mask     bool, the caches' shape: the elements the call may write
+      slots         [(b, n, unit, pos)]: new key n of sequence b landed at cache[unit, pos]
+      k_exact       per sequence the fp64 (nnew_b, H_kv, d) value of its new keys before any rounding (rotated when rotary is on)
+      k_new16, v_new16   per sequence the 16-bit values that are stored or quantised (K: rotated and rounded once)
+      L, P, nq, nnew     per sequence: the clamped length and left pad, its query tokens, its new keys
+    and of front_half's other per-call fields."""
+    call, seqs = front_half(*args, **kwargs)
+    o = torch.zeros(call.o_shape, dtype=torch.float64)
+    lse = torch.full(call.lse_shape, math.nan, dtype=torch.float64)
+    novis = torch.zeros(call.own.shape, dtype=torch.bool)
+    for sq in seqs:
+        kd = sq.k.double() * sq.k_scale.double().view(1, call.hkv, 1) if call.e4m3 else sq.k.double()
+        vd = sq.v.double() * sq.v_scale.double().view(1, call.hkv, 1) if call.e4m3 else sq.v.double()
+        ob, lb, nv = dense_attention(sq.q.double(), kd, vd, call.causal, call.window, call.scale, call.softcap, sq.slopes, call.sinks)
+        place(call, sq, o, lse, ob, lb)
+        novis[sq.rows] = nv
+    call.o, call.lse, call.novis = o, lse, novis
+    return call

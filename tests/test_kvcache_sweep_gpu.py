@@ -5,12 +5,20 @@ itself.  The bars are the ones every decode test uses: tests.helpers.dtype_toler
 the -inf pattern and o == 0 on rows without a visible key exact; every cache element outside the reference's write mask keeps
 its bits; appended elements are k_new / v_new's own bits, or judged by the rotary (kvcache_rotary_ref.check_caches) and e4m3
 (test_kvcache_fp8_gpu.check_appended) tests' rules.  The cases with a head dim or group size no other test runs also run at
-fixed split counts: 1 and 5 against the reference, and a packed call bitwise against the padded call on each sequence alone."""
+fixed split counts: 1 and 5 against the reference, and a packed call bitwise against the padded call on each sequence alone.
+
+Every case, and every fixed-split extra, is also held to the sharp bar (sharp_out): tests/ex_full_ref.sharp_bar's inequality against
+tests/decode_baseline.kv_baseline, the rounding model of the decode kernels, per call and per sequence.  Reference and baseline of
+that bar attend over the cache contents the call left behind, read back from the device: the append is judged by
+check_caches_after, whose rules let a rotated or quantised element differ from the reference's by one step, and that step is
+neither charged to the attention kernel nor used to excuse it.  tests/test_decode_sharp_cpu.py proves on the CPU that this bar
+rejects the decode bugs the bars above let through; profiles/decode_sweep.md records the measured ratios."""
 import functools
 
 import pytest
 import torch
 
+from tests import decode_baseline as db
 from tests import kvcache_sweep_cases as sc
 from tests.helpers import dtype_tolerances
 from tests.kvcache_full_ref import full_reference
@@ -53,6 +61,42 @@ def check_out(o, lse, r, dtype, what=""):
     torch.testing.assert_close(lse[fin], rlse[fin], rtol=1e-3, atol=1e-3, msg=lambda m: f"lse {what}: {m}")
     novis = r.novis[r.own].unsqueeze(0).expand(rlse.shape) if r.lse.dim() == 2 else r.novis.unsqueeze(1).expand(rlse.shape)
     assert (o[novis] == 0).all(), f"o != 0 on rows without a visible key {what}"
+
+
+AFTER = {}
+
+
+def after_the_call(key, kw, k_big, v_big, splits):
+    """(reference, baseline at `splits` splits; None: the call's own) of the call kw over the caches it left behind, computed once
+    per problem (key) and split count: the append does not depend on the split count, and a repeated call leaves the same bits"""
+    caches = (k_big[1:-1], v_big[1:-1])
+    hit = AFTER.get(key)
+    if hit is None or not (torch.equal(bits(hit["caches"][0]), bits(caches[0])) and torch.equal(bits(hit["caches"][1]), bits(caches[1]))):
+        AFTER[key] = hit = dict(caches=caches, r=full_reference(**sc.call_keywords(kw), caches_after=caches), base={})
+    if splits not in hit["base"]:
+        hit["base"][splits] = db.kv_baseline(sc.call_keywords(kw), splits, caches_after=caches)
+    return hit["r"], hit["base"][splits]
+
+
+def family(kw, splits):
+    """the split kernel instantiation a call launches and how its results are finished (csrc/fa_decode.hip: launch_split, launch_kv_t)"""
+    d = kw["q"].shape[-1]
+    name = "kv_split" + ("_rot" if kw["rotary_cos"] is not None else "") + ("_q8" if kw["k_cache"].dtype == E4M3 else "") + "_kernel"
+    end = "kv_combine_sink_kernel" if kw["sinks"] is not None else "kv_combine_kernel" if splits > 1 else "direct"
+    return f"{name}<D={64 if d <= 64 else 128 if d <= 128 else 256},{'paged' if kw['block_table'] is not None else 'contig'}>+{end}"
+
+
+def sharp_out(o, lse, kw, r, base, what=""):
+    """tests/ex_full_ref.sharp_bar on o and lse — max |kernel - fp64| <= 2 * max |baseline - fp64| + eps * max |fp64|, eps of the
+    tensor dtype for o and of float32 for lse — over the call's owned rows and over each sequence's rows alone (a case holds
+    lengths 0, 1, 33, 100 and full side by side, and the short rows, where |o| ~ |v|, would otherwise set the maximum for the
+    192-key rows).  A sequence without a visible key stays under check_out's exact rules only; no other (case, sequence) is left
+    out.  r and base: after_the_call's."""
+    bad, ratios, used = db.sharp_rows(o, lse, r.o, r.lse, base.o, base.lse, kw["q"].dtype, db.kv_groups(r))
+    top = lambda t: max([g[t] for n, g in ratios.items() if n != "call" and t in g], default=0.0)   # noqa: E731
+    print(f"decode_sweep_ratio {what} o={ratios['call'].get('o', 0.0):.3f} lse={ratios['call'].get('lse', 0.0):.3f} per sequence o={top('o'):.3f} "
+          f"lse={top('lse'):.3f} used={used:.3f} family={family(kw, base.splits)}")
+    assert not bad, f"sharp bar {what}: " + "; ".join(bad)
 
 
 def padded_new(per_seq, hkv, d, dtype):
@@ -116,6 +160,7 @@ def test_case(i):
     assert o.shape == r.o.shape and lse.shape == r.lse.shape and lse.dtype == torch.float32 and o.dtype == kw["q"].dtype
     check_out(o, lse, r, kw["q"].dtype, IDS[i])
     check_caches_after(kw, r, k_big, v_big, IDS[i])
+    sharp_out(o, lse, kw, *after_the_call(i, kw, k_big, v_big, None), IDS[i])
 
 
 EXTRA = sc.fixed_split_cases()
@@ -128,6 +173,7 @@ def test_fixed_splits_match_the_reference(i):
         o, lse, k_big, v_big = run(kw, num_splits=splits)
         check_out(o, lse, r, kw["q"].dtype, f"{IDS[i]} S={splits}")
         check_caches_after(kw, r, k_big, v_big, f"{IDS[i]} S={splits}")
+        sharp_out(o, lse, kw, *after_the_call(i, kw, k_big, v_big, splits), f"{IDS[i]} S={splits}")
 
 
 @pytest.mark.parametrize("i", EXTRA, ids=[IDS[i] for i in EXTRA])

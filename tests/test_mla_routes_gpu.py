@@ -17,12 +17,17 @@ One pool serves every case: a packed pool, the bf16 pool its read contract gives
 rounded to float16, and per sequence the same tokens gathered into a contiguous cache.  Per case: within
 tests/test_kvcache_gpu.py::check of the fp64 reference (tests/mla_ref.py, tests/mla_sparse_ref.py) on those values; the paged call
 has the bits of the contiguous call; the packed call has the bits of the 16-bit paged call; a repeated call has the same bits;
-the dead sequence gives o = 0, lse = -inf.  A reference is computed once per (form, dtype, H_q) and shared."""
+the dead sequence gives o = 0, lse = -inf.  A reference is computed once per (form, dtype, H_q) and shared.
+
+Every case is also held to the sharp bar (sharp_out): tests/ex_full_ref.sharp_bar's inequality against the rounding model of
+mla_decode (tests/decode_baseline.mla_dense_baseline / mla_list_baseline at the case's split count), per call and per sequence.
+tests/test_decode_sharp_cpu.py proves that this bar rejects the bugs `check` lets through; profiles/decode_sweep.md has the ratios."""
 import functools
 
 import pytest
 import torch
 
+from tests import decode_baseline as db
 from tests import mla_fp8_ref as ref
 from tests.kvcache_paged_ref import paged_tokens
 from tests.mla_ref import mla_reference
@@ -107,6 +112,31 @@ def expected(form, dtype, hq):
     return mla_sparse_reference(q[..., 512:], q[..., :512], pool[..., 512:], pool[..., :512], lists(), sl, False, SCALE, table)
 
 
+@functools.lru_cache(maxsize=None)
+def baseline(form, dtype, hq, splits):
+    """the rounding model of the case's kernel on the values expected() reads, at the case's split count"""
+    pool, _cont = caches(dtype)
+    q, table, sl = queries(dtype, hq), pools()[2], torch.tensor(LENS, dtype=torch.int32)
+    if form == "dense":
+        return db.mla_dense_baseline(q[..., 512:], q[..., :512], pool[..., 512:], pool[..., :512], sl, False, (-1, -1), SCALE, table, splits=splits)
+    return db.mla_list_baseline(q[..., 512:], q[..., :512], pool[..., 512:], pool[..., :512], lists(), sl, False, SCALE, table, splits=splits)
+
+
+def sharp_out(o, lse, form, dtype, hq, splits, what):
+    """tests/ex_full_ref.sharp_bar on o and lse — max |kernel - fp64| <= 2 * max |baseline - fp64| + eps * max |fp64|, eps of the
+    tensor dtype for o and of float32 for lse — over the call and over the sequence with keys alone; the dead sequence stays under
+    hold's exact rules"""
+    ro, rlse = expected(form, dtype, hq)
+    bo, bl = baseline(form, dtype, hq, splits)
+    bad, ratios, used = db.sharp_rows(o.cpu(), lse.cpu(), ro, rlse, bo, bl, dtype, db.mla_groups(LENS))
+    top = lambda t: max([g[t] for n, g in ratios.items() if n != "call" and t in g], default=0.0)   # noqa: E731
+    kernel = what.split(": ")[1].split("<")[0]
+    print(f"decode_sweep_ratio {ident(form, dtype, hq, splits)} o={ratios['call'].get('o', 0.0):.3f} lse={ratios['call'].get('lse', 0.0):.3f} "
+          f"per sequence o={top('o'):.3f} lse={top('lse'):.3f} used={used:.3f} "
+          f"family={kernel}<{'lists' if form == 'lists' else 'dense'}>+{'mla_combine_kernel' if splits > 1 else 'direct'}")
+    assert not bad, f"sharp bar {what}: " + "; ".join(bad)
+
+
 def run_16bit(form, dtype, hq, splits):
     """(contiguous, paged, paged again), each (o, lse) on the device"""
     pool, cont = caches(dtype)
@@ -129,7 +159,7 @@ def run_packed(form, hq, splits):
     return [packed[0], wide, packed[1]]
 
 
-def hold(outs, form, dtype, hq, what):
+def hold(outs, form, dtype, hq, what, splits):
     """outs = (a call, the call it must equal bit for bit, the first call repeated)"""
     ro, rlse = expected(form, dtype, hq)
     (o, lse), (o2, lse2), (o3, lse3) = outs
@@ -138,6 +168,7 @@ def hold(outs, form, dtype, hq, what):
     check(o2, lse2, ro, rlse, dtype)
     assert torch.equal(o, o2) and torch.equal(lse, lse2), what
     assert torch.equal(o, o3) and torch.equal(lse, lse3), "a repeated call"
+    sharp_out(o, lse, form, dtype, hq, splits, what)
     dead = LENS.index(0)
     assert (o[dead] == 0).all() and (lse[dead] == -float("inf")).all() and torch.isfinite(lse[1 - dead]).all()
 
@@ -149,9 +180,9 @@ def ident(form, dtype, hq, splits):
 @pytest.mark.parametrize("form,dtype,hq,splits", CASES, ids=[ident(*c) for c in CASES])
 def test_16_bit_routes(form, dtype, hq, splits):
     cont, paged, again = run_16bit(form, dtype, hq, splits)
-    hold((paged, cont, again), form, dtype, hq, "paged against contiguous: " + ", ".join(routes(form, dtype, hq)))
+    hold((paged, cont, again), form, dtype, hq, "paged against contiguous: " + ", ".join(routes(form, dtype, hq)), splits)
 
 
 @pytest.mark.parametrize("form,hq,splits", PACKED, ids=[ident(f, BF16, h, s) for f, h, s in PACKED])
 def test_packed_routes(form, hq, splits):
-    hold(run_packed(form, hq, splits), form, BF16, hq, "packed against 16-bit paged: " + routes(form, BF16, hq, True)[0])
+    hold(run_packed(form, hq, splits), form, BF16, hq, "packed against 16-bit paged: " + routes(form, BF16, hq, True)[0], splits)
