@@ -186,7 +186,7 @@ __device__ __forceinline__ void ex_fwd_body(const T* __restrict__ q, const T* __
     const int q0 = (blockIdx.x - bh * ntile) * BM;
     [[maybe_unused]] int sq0 = 0, sk0 = 0, hh = 0, hk = 0;
     [[maybe_unused]] const int* pg_row = nullptr;   // paged: this sequence's table row
-    if constexpr (VAR) {   // packed sequences: narrow the padded call to sequence b (fa_ex_mfma.hip: EXM_VARLEN_UNIT)
+    if constexpr (VAR) {   // packed sequences: narrow the padded call to sequence b (fa_ex_mfma_kernels.h: exm_varlen_unit)
         const int b = bh / p.hq;
         hh = bh - b * p.hq;
         hk = kv_unit(hh, p.kvg);
@@ -427,7 +427,7 @@ __device__ __forceinline__ void ex_dkdv_body(const T* __restrict__ q, const T* _
     const int bh = blockIdx.x / ntile;
     const int k0 = (blockIdx.x - bh * ntile) * BK;
     [[maybe_unused]] int sq0 = 0, sk0 = 0, hh = 0, hk = 0;
-    if constexpr (VAR) {   // packed sequences: narrow the padded call to sequence b (fa_ex_mfma.hip: EXM_VARLEN_UNIT)
+    if constexpr (VAR) {   // packed sequences: narrow the padded call to sequence b (fa_ex_mfma_kernels.h: exm_varlen_unit)
         const int b = bh / p.hq;
         hh = bh - b * p.hq;
         hk = kv_unit(hh, p.kvg);
@@ -583,7 +583,7 @@ __device__ __forceinline__ void ex_dq_body(const T* __restrict__ q, const T* __r
     const int bh = blockIdx.x / ntile;
     const int q0 = (blockIdx.x - bh * ntile) * BM;
     [[maybe_unused]] int sq0 = 0, sk0 = 0, hh = 0, hk = 0;
-    if constexpr (VAR) {   // packed sequences: narrow the padded call to sequence b (fa_ex_mfma.hip: EXM_VARLEN_UNIT)
+    if constexpr (VAR) {   // packed sequences: narrow the padded call to sequence b (fa_ex_mfma_kernels.h: exm_varlen_unit)
         const int b = bh / p.hq;
         hh = bh - b * p.hq;
         hk = kv_unit(hh, p.kvg);

@@ -1,6 +1,6 @@
 """CPU: the variable-length (packed) sequence entry points (include/fa_mi355x.h, fa_ex_forward_varlen / fa_ex_backward_varlen) —
 declared, exported, every host-side validation before any HIP call, the Python wrappers' checks — and a model of the kernels'
-per-sequence tile ranges with the cu_seqlens clamps (csrc/fa_ex_common.h: seq_span; fa_ex_mfma.hip: FEAT bit 3), checked
+per-sequence tile ranges with the cu_seqlens clamps (csrc/fa_ex_common.h: seq_span; fa_ex_mfma_kernels.h: FEAT bit 3), checked
 exhaustively on small length sets: every visible (sequence, row, key) is computed, no computed tile leaves its sequence, and
 malformed offsets stay inside [0, total)."""
 import ctypes

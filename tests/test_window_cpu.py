@@ -1,6 +1,6 @@
 """CPU: the sliding-window entry points (include/fa_mi355x.h, fa_ex_forward_window / fa_ex_backward_window) — declared, exported,
 argument validation before any HIP call, the Python wrappers' checks — and a model of the 16-bit kernels' window tile ranges
-(csrc/fa_ex_mfma.hip, FEAT bit 2), checked exhaustively on small shapes: every visible element is computed, every computed tile
+(csrc/fa_ex_mfma_kernels.h, FEAT bit 2), checked exhaustively on small shapes: every visible element is computed, every computed tile
 holds a visible element, and the per-element thresholds keep exactly the visible elements."""
 import ctypes
 import os
