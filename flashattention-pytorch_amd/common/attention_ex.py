@@ -163,6 +163,55 @@ class _FlashAttnExLseFn(torch.autograd.Function):
         return tuple(grads[:3]) + (None,) * 11 + ((grads[3],) if ctx.with_sinks else (None,))
 
 
+class _FlashAttnExBiasFn(torch.autograd.Function):
+    """flash_attention_ex(..., attn_bias=) (fa_ex_forward_bias / fa_ex_backward_bias): a Function of its own, so the calls without a
+    bias stay launch for launch what they were.  With_lse: (o, lse) and a gradient of lse; dbias only where the bias requires grad."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, bias, causal, scale, with_lse):
+        import flashattention_lab_cuda as ext
+
+        ctx.set_materialize_grads(False)
+        ctx.args = (causal, scale)
+        o, lse = ext.ex_forward(q, k, v, causal, scale, attn_bias=bias)
+        ctx.save_for_backward(q, k, v, o, lse, bias)
+        if with_lse:
+            return o, lse
+        ctx.mark_non_differentiable(lse)
+        return o, lse
+
+    @staticmethod
+    def backward(ctx, do, dlse):
+        import flashattention_lab_cuda as ext
+
+        if do is None and dlse is None:
+            return (None,) * 7
+        causal, scale = ctx.args
+        q, k, v, o, lse, bias = ctx.saved_tensors
+        do = torch.zeros_like(o) if do is None else do.contiguous()
+        kw = {"dlse": dlse.contiguous()} if dlse is not None else {}
+        need = bool(ctx.needs_input_grad[3])
+        grads = ext.ex_backward(q, k, v, o, do, lse, causal, scale, attn_bias=bias, need_dbias=need, **kw)
+        return tuple(grads[:3]) + (grads[3] if need else None,) + (None,) * 3
+
+
+def _bias_units(who, bias, lead, nq, nk):
+    """attn_bias for a 4-D q ((B, H) = lead): (Bb, Hb, Rb, Nk) with Bb in {1, B}, Hb in {1, H}, Rb in {1, Nq}; for a 3-D q
+    (BH or 1, Rb, Nk).  The library checks the rest (dtype, device, layout: flashattention_lab_cuda.bias_arg)."""
+    if not isinstance(bias, torch.Tensor):
+        raise RuntimeError(f"{who}: attn_bias must be a tensor of q's dtype")
+    shape = tuple(bias.shape)
+    if len(lead) == 2:
+        want = f"(1 or {lead[0]}, 1 or {lead[1]}, 1 or {nq}, {nk})"
+        ok = bias.dim() == 4 and shape[0] in (1, lead[0]) and shape[1] in (1, lead[1]) and shape[2] in (1, nq) and shape[3] == nk
+    else:
+        want = f"(1 or {lead[0]}, 1 or {nq}, {nk})"
+        ok = bias.dim() == 3 and shape[0] in (1, lead[0]) and shape[1] in (1, nq) and shape[2] == nk
+    if not ok:
+        raise RuntimeError(f"{who}: attn_bias must be {want}, got {shape}")
+    return bias
+
+
 def _window_size(window_size):
     """(left, right) ints >= -1, with the library's error text (flashattention_lab_cuda.window_arg, fa_capi.hip)."""
     try:
@@ -200,8 +249,16 @@ def _sinks_units(who, sinks, heads):
 
 def flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, block_size=128, causal=False, dropout_p=0.0,
                        seed=0, softmax_scale=None, window_size=(-1, -1), softcap=0.0, alibi_slopes=None, *, return_lse=False,
-                       sinks=None):
+                       attn_bias=None, sinks=None):
     window = _window_size(window_size)
+    if attn_bias is not None:
+        # an additive bias: what the bias kernels do not take is refused by name, before anything runs
+        import flashattention_lab_cuda as ext
+
+        ext.bias_refuse("flash_attention_ex", mask=mask is not None, block_sparse_mask=block_sparse_mask is not None,
+                        dropout_p=float(dropout_p) > 0.0, window_size=window != (-1, -1), softcap=softcap != 0.0,
+                        alibi_slopes=alibi_slopes is not None, sinks=sinks is not None,
+                        **{"d_v != d": isinstance(v, torch.Tensor) and isinstance(k, torch.Tensor) and v.shape[-1] != k.shape[-1]})
     if all(isinstance(t, torch.Tensor) for t in (q, k, v)) and k.dim() == v.dim() and v.shape[:-1] == k.shape[:-1] and v.shape[-1] != k.shape[-1]:
         # a v of its own width: what the two-width kernels do not take is refused by name, before anything runs
         _vdim_refuse("flash_attention_ex", k.shape[-1], v.shape[-1], q.dtype, mask=mask is not None,
@@ -223,6 +280,12 @@ def flash_attention_ex(q, k, v, tau=1.0, mask=None, block_sparse_mask=None, bloc
         (_, nq, d), nk = q.shape, k.shape[1]
     d_v = v.shape[-1]
     scale = (tau / math.sqrt(d)) if softmax_scale is None else float(softmax_scale) * tau   # :134
+    if attn_bias is not None:
+        bias = _bias_units("flash_attention_ex", attn_bias, tuple(q.shape[:-2]), nq, nk)
+        o, lse = _FlashAttnExBiasFn.apply(q3, k3, v3, bias, bool(causal), scale, bool(return_lse))
+        if four_d:
+            o, lse = o.reshape(b, h, nq, d_v), lse.reshape(b, h, nq)
+        return (o, lse) if return_lse else o
     m = None
     if mask is not None:
         m = normalize_mask(mask, tuple(q.shape[:-2]), nq, nk)

@@ -488,6 +488,55 @@ static int vdim_layout_check(const char* who, std::initializer_list<const void*>
     return FA_OK;
 }
 
+// An additive attention bias (fa_ex_*_bias: the group after d_v).  bias == null with everything else of the group 0 / null is the
+// call without the argument and goes no further than the first rule.  The first broken rule, in this order, before any other check
+// and any HIP call: (1) a null bias with a stride or a dbias; (2) bias or dbias not 16-byte aligned; (3) a stride that is negative
+// or no multiple of 8; (4) bias_heads < 1 or not dividing BH; (5) a dbias for a row-broadcast bias; then each feature the bias kernels
+// do not have, by name: (6) mask, block_sparse_mask, dropout_p > 0, window_size, softcap, alibi_slopes, sinks, d_v != d;
+// (7) f32 tensors; (8) d > 128 or d % 8 != 0; (9) softmax_scale <= 0; (10) a unit's rows beyond the 32-bit offsets.
+struct BiasArg {
+    const void* bias = nullptr;
+    int64_t heads = 0, bs = 0, hs = 0, rs = 0;
+    void* dbias = nullptr;         // backward: null = no gradient asked for
+    int64_t dbs = 0, dhs = 0, drs = 0;
+};
+struct BiasExtras {
+    bool mask = false, block_mask = false, dropout = false, window = false, softcap = false, alibi = false, sinks = false, vdim = false;
+};
+static int bias_check(const char* who, const BiasArg& b, int64_t bh, int64_t nq, int64_t nk, int64_t d, int dtype, double scale,
+                      const BiasExtras& x) {
+    if (!b.bias) {
+        if (b.bs != 0 || b.hs != 0 || b.rs != 0 || b.dbias || b.dbs != 0 || b.dhs != 0 || b.drs != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: bias is null, but a bias stride or dbias is given", who);
+        return FA_OK;
+    }
+    if ((uintptr_t)b.bias % 16 != 0 || (uintptr_t)b.dbias % 16 != 0)
+        return fail(FA_ERR_UNSUPPORTED, "%s: bias and dbias must be 16-byte aligned", who);
+    for (const int64_t s : {b.bs, b.hs, b.rs, b.dbs, b.dhs, b.drs})
+        if (s < 0 || s % 8 != 0)
+            return fail(FA_ERR_UNSUPPORTED,
+                        "%s: every bias and dbias stride must be 0 (broadcast) or a positive multiple of 8 elements (got %lld): allocate the "
+                        "last dim padded to a multiple of 8 and pass the slice", who, (long long)s);
+    if (b.heads < 1 || bh % b.heads != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: bias_heads=%lld does not divide BH=%lld", who, (long long)b.heads, (long long)bh);
+    if (b.dbias && nq > 1 && (b.rs == 0 || b.drs == 0))
+        return fail(FA_ERR_UNSUPPORTED, "%s: dbias for a row-broadcast bias (bias_row_stride = 0) is not supported", who);
+    if (x.mask) return fail(FA_ERR_UNSUPPORTED, "%s: mask is not supported with a bias: fold it into the bias as -inf", who);
+    const char* name = x.block_mask ? "block_sparse_mask" : x.dropout ? "dropout_p > 0" : x.window ? "window_size" : x.softcap ? "softcap"
+                       : x.alibi ? "alibi_slopes" : x.sinks ? "sinks" : x.vdim ? "d_v != d" : nullptr;
+    if (name) return fail(FA_ERR_UNSUPPORTED, "%s: %s is not supported with a bias", who, name);
+    if (dtype != FA_DTYPE_F16 && dtype != FA_DTYPE_BF16)
+        return fail(FA_ERR_UNSUPPORTED, "%s: a bias needs f16 or bf16 tensors (dtype code %d): there are no exact-f32 kernels with a bias", who, dtype);
+    if (d > 128 || d % 8 != 0)
+        return fail(FA_ERR_UNSUPPORTED, "%s: a bias needs d <= 128 and d %% 8 == 0 (got d=%lld): there are no exact-f32 kernels with a bias", who,
+                    (long long)d);
+    if (!(scale > 0.0)) return fail(FA_ERR_UNSUPPORTED, "%s: a bias needs softmax_scale > 0", who);
+    const int64_t rmax = b.rs > b.drs ? b.rs : b.drs;
+    if (nq > 0 && nk > 0 && (nq + 256) > (((int64_t)1 << 30) - nk - 512) / (rmax > 0 ? rmax : 1))
+        return fail(FA_ERR_UNSUPPORTED, "%s: a unit's bias rows span more than 2^31 bytes", who);
+    return FA_OK;
+}
+
 // One call of the fa_ex_forward* / fa_ex_backward* family.  The defaults are the narrower entry points' "argument absent": an entry
 // point assigns the arguments it has (ex_call / ex_bwd_call: the ones all of them have) and leaves the rest.
 struct ExCall {
@@ -502,6 +551,7 @@ struct ExCall {
     SinkArg sk;
     const float* dlse = nullptr;   // fa_ex_backward_dlse: the gradient of lse, (bh, nq) float32
     int64_t d_v = 0;               // fa_ex_*_vdim: the width of v, o, do_ and dv (0: d)
+    BiasArg bi;                    // fa_ex_*_bias
     const uint8_t *mask = nullptr, *block_mask = nullptr;
     int64_t mask_bh_stride = 0, br = 0, bc = 0;
     uint64_t dropout_seed = 0;
@@ -518,6 +568,18 @@ static int ex_vdim_check(const char* who, const ExCall& c) {
     x.window = c.window_left != -1 || c.window_right != -1; x.softcap = c.sm.softcap > 0.0; x.alibi = c.sm.alibi != nullptr;
     x.sinks = c.sk.sinks != nullptr;
     return vdim_check(who, c.d, c.d_v, c.dtype, c.softmax_scale, x);
+}
+
+static int ex_bias_check(const char* who, const ExCall& c) {
+    BiasExtras x;
+    x.mask = c.mask != nullptr; x.block_mask = c.block_mask != nullptr; x.dropout = c.dropout_p > 0.0;
+    x.window = c.window_left != -1 || c.window_right != -1; x.softcap = c.sm.softcap > 0.0; x.alibi = c.sm.alibi != nullptr;
+    x.sinks = c.sk.sinks != nullptr; x.vdim = ex_vdim(c);
+    return bias_check(who, c.bi, c.bh, c.nq, c.nk, c.d, c.dtype, c.softmax_scale, x);
+}
+// is dbias the sum over a broadcast batch or head dimension (through the workspace)?
+static bool ex_dbias_reduced(const ExCall& c) {
+    return c.bi.bias && c.bi.dbias && fa::ex_bias_reduced(c.bh, c.bi.heads, c.bi.dbs, c.bi.dhs);
 }
 
 // the argument checks of a forward and a backward, in their order; the mask comes back canonical
@@ -542,6 +604,12 @@ static fa::ExArgs ex_args(const ExCall& c, int causal, int64_t wl, int64_t wr) {
     sink_args(a, c.sk);
     a.dlse = c.dlse;
     a.d_v = ex_vdim(c) ? c.d_v : 0;
+    if (c.bi.bias) {
+        a.bias = c.bi.bias; a.bias_heads = c.bi.heads;
+        a.bias_bstride = c.bi.bs; a.bias_hstride = c.bi.hs; a.bias_rstride = c.bi.rs;
+        a.dbias = c.bi.dbias;
+        a.dbias_bstride = c.bi.dbs; a.dbias_hstride = c.bi.dhs; a.dbias_rstride = c.bi.drs;
+    }
     return a;
 }
 
@@ -560,6 +628,7 @@ static int no_key_dsinks(const char* who, const fa::ExArgs& a, hipStream_t st) {
 static int ex_forward_impl(const char* who, const ExCall& c) {
     int causal = c.causal;
     int64_t wl = c.window_left, wr = c.window_right;   // (window_canon rewrites the three)
+    if (const int rc = ex_bias_check(who, c); rc != FA_OK) return rc;
     if (const int rc = ex_vdim_check(who, c); rc != FA_OK) return rc;
     if (const int rc = ex_checks(who, c, false, causal, wl, wr); rc != FA_OK) return rc;
     if (c.bh == 0 || c.nq == 0) return FA_OK;
@@ -580,6 +649,7 @@ static size_t ex_bwd_ws_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_
 static int ex_backward_impl(const char* who, const ExCall& c) {
     int causal = c.causal;
     int64_t wl = c.window_left, wr = c.window_right;
+    if (const int rc = ex_bias_check(who, c); rc != FA_OK) return rc;
     if (const int rc = ex_vdim_check(who, c); rc != FA_OK) return rc;
     if (const int rc = ex_checks(who, c, true, causal, wl, wr); rc != FA_OK) return rc;
     if (const int rc = dlse_check(who, c.dlse); rc != FA_OK) return rc;
@@ -596,7 +666,8 @@ static int ex_backward_impl(const char* who, const ExCall& c) {
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
     if (ex_vdim(c))
         if (const int rc = vdim_layout_check(who, {c.q, c.k, c.v, c.o, c.do_, c.dq, c.dk, c.dv}, {}); rc != FA_OK) return rc;
-    const size_t need = ex_bwd_ws_grouped(c.bh, c.kv_group, c.nq, c.nk, c.d, c.dtype);   // (d_v < d: the same rows, slabs of d's size)
+    size_t need = ex_bwd_ws_grouped(c.bh, c.kv_group, c.nq, c.nk, c.d, c.dtype);   // (d_v < d: the same rows, slabs of d's size)
+    if (ex_dbias_reduced(c)) need += fa::ex_bias_ds_bytes(c.bh, c.nq, c.nk);          // (the per-unit dS of a broadcast dbias)
     if (!c.workspace || c.workspace_bytes < need)
         return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, need, c.workspace_bytes);
     return launched(who, fa::launch_ex(ex_args(c, causal, wl, wr), true, reinterpret_cast<hipStream_t>(c.stream)));
@@ -784,6 +855,49 @@ int fa_ex_backward_vdim(const void* q, const void* k, const void* v, const void*
     c.dlse = dlse;
     c.d_v = d_v;
     return ex_backward_impl("fa_ex_backward_vdim", c);
+}
+
+int fa_ex_forward_bias(const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t kv_group, int64_t nq,
+                       int64_t nk, int64_t d, int dtype, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                       double softcap, const float* alibi_slopes, int64_t alibi_heads, int64_t alibi_batch_stride, const float* sinks,
+                       int64_t sink_heads, int64_t d_v, const void* bias, int64_t bias_heads, int64_t bias_batch_stride,
+                       int64_t bias_head_stride, int64_t bias_row_stride, const uint8_t* mask, int64_t mask_bh_stride,
+                       const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* stream) {
+    ExCall c = ex_call(q, k, v, o, lse, bh, nq, nk, d, dtype, causal, softmax_scale, mask, mask_bh_stride, block_mask, br, bc, dropout_p,
+                       dropout_seed, stream);
+    c.kv_group = kv_group; c.window_left = window_left; c.window_right = window_right;
+    c.sm = {softcap, alibi_slopes, alibi_heads, alibi_batch_stride};
+    c.sk = {sinks, sink_heads, nullptr};
+    c.d_v = d_v;
+    c.bi = {bias, bias_heads, bias_batch_stride, bias_head_stride, bias_row_stride, nullptr, 0, 0, 0};
+    return ex_forward_impl("fa_ex_forward_bias", c);
+}
+
+int fa_ex_backward_bias(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
+                        void* dv, int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype, int causal,
+                        int64_t window_left, int64_t window_right, double softmax_scale, double softcap, const float* alibi_slopes,
+                        int64_t alibi_heads, int64_t alibi_batch_stride, const float* sinks, int64_t sink_heads, float* dsinks,
+                        const float* dlse, int64_t d_v, const void* bias, int64_t bias_heads, int64_t bias_batch_stride,
+                        int64_t bias_head_stride, int64_t bias_row_stride, void* dbias, int64_t dbias_batch_stride,
+                        int64_t dbias_head_stride, int64_t dbias_row_stride, const uint8_t* mask, int64_t mask_bh_stride,
+                        const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    ExCall c = ex_bwd_call(q, k, v, o, do_, lse, dq, dk, dv, bh, nq, nk, d, dtype, causal, softmax_scale, mask, mask_bh_stride, block_mask,
+                           br, bc, dropout_p, dropout_seed, workspace, workspace_bytes, stream);
+    c.kv_group = kv_group; c.window_left = window_left; c.window_right = window_right;
+    c.sm = {softcap, alibi_slopes, alibi_heads, alibi_batch_stride};
+    c.sk = {sinks, sink_heads, dsinks};
+    c.dlse = dlse;
+    c.d_v = d_v;
+    c.bi = {bias, bias_heads, bias_batch_stride, bias_head_stride, bias_row_stride, dbias, dbias_batch_stride, dbias_head_stride,
+            dbias_row_stride};
+    return ex_backward_impl("fa_ex_backward_bias", c);
+}
+
+size_t fa_ex_backward_workspace_bytes_bias(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype, int dbias_reduced) {
+    size_t need = fa_ex_backward_workspace_bytes_grouped(bh, kv_group, nq, nk, d, dtype);
+    if (dbias_reduced && bh > 0 && nq > 0 && nk > 0) need += fa::ex_bias_ds_bytes(bh, nq, nk);
+    return need;
 }
 
 // ---- variable-length (packed) sequences: see include/fa_mi355x.h

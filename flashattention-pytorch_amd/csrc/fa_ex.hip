@@ -881,6 +881,9 @@ static hipError_t ex_by_d(const ExArgs& a, bool backward, hipStream_t st) {
 // dK / dV partials that launch_ex adds up.
 static hipError_t launch_ex_one(const ExArgs& a, bool backward, hipStream_t st) {
     const int path = option(OPT_EX_PATH);   // 0: MFMA kernels where they apply, 1: always these, 2: MFMA or fail, 3: MFMA, never the plain kernels
+    // an additive bias: kernels of their own, or nothing (the C layer has refused by name what they do not take) — never the plain
+    // kernels, the dS hand-over or the exact-f32 kernels, which know no bias
+    if (a.bias) return ex_mfma_bias_supported(a) ? launch_ex_mfma_bias(a, backward, st) : hipErrorInvalidConfiguration;
     // no extras at all on a square problem: this IS the plain path — hand it to the tuned kernels (same results contract;
     // the workspace of fa_ex_backward_workspace_bytes covers their row constants)
     // (a window that bounds something never leaves this file's families: the plain, nq != nk and fa_generic kernels know no band)

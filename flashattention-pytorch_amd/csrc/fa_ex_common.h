@@ -81,6 +81,23 @@ __device__ __forceinline__ void ex_sink_norm(float m, float l, float snk, float&
     lse = mp + logf(lp);
 }
 
+// An additive bias on the scores (fa_ex_*_bias; the kFeatBias instantiations of fa_ex_mfma_bias.hip): one more parameter block of
+// its own, ExParamsB = ExParamsS + ExBias (the bias joins on the score-modifier body, where ALiBi joins), so every other kernel
+// keeps its block and its code.  Unit u = b * heads + h reads bias + b * b_bs + h * b_hs + i * b_rs + j (elements, 0 = broadcast)
+// and the dQ kernel stores its 16-bit dS at ds + b * s_bs + h * s_hs + i * s_rs + j where ds is not null.
+struct ExBias {
+    const uint16_t* bias;
+    uint16_t* ds;
+    long long b_bs, b_hs, s_bs, s_hs;
+    int b_rs, s_rs;
+    int heads;
+    float inv_scale;       // 1 / scale: the kernels work on raw scores q.k, so the bias enters as fma(bias, 1 / scale, q.k)
+};
+struct ExParamsB : ExParamsS {
+    ExBias bs;
+};
+static_assert(sizeof(ExBias) == 64 && sizeof(ExParamsB) == sizeof(ExParamsS) + sizeof(ExBias), "ExParamsB layout: ExBias after every ExParamsS field");
+
 // Paged K/V for the varlen forward (fa_ex_forward_varlen_paged; the kFeatPaged instantiations of fa_ex_mfma.hip and the
 // ex_fwd_varlen_paged_kernel entries of fa_ex.hip): k and v are pools (num_blocks, ps, heads_kv, d) and key t of sequence b is row
 // t % ps of page table[b * max_blocks + t / ps].  Once more a parameter block of its own, ExParamsPg<B> = B + ExPage for B any of
@@ -351,6 +368,17 @@ inline ExParamsK make_ex_params_k(const ExArgs& a) {
     p.snk.heads = (int)(a.sink_heads > 0 ? a.sink_heads : 1);
     p.snk.pad_ = 0;
     return p;
+}
+
+inline ExBias make_ex_bias(const ExArgs& a) {
+    ExBias b;
+    b.bias = reinterpret_cast<const uint16_t*>(a.bias);
+    b.ds = reinterpret_cast<uint16_t*>(a.dbias);
+    b.b_bs = a.bias_bstride; b.b_hs = a.bias_hstride; b.s_bs = a.dbias_bstride; b.s_hs = a.dbias_hstride;
+    b.b_rs = (int)a.bias_rstride; b.s_rs = (int)a.dbias_rstride;
+    b.heads = (int)(a.bias_heads > 0 ? a.bias_heads : 1);
+    b.inv_scale = (float)(1.0 / (double)a.scale);
+    return b;
 }
 
 inline ExPage make_ex_page(const ExArgs& a) {

@@ -26,6 +26,8 @@
 //               buffer descriptor of its own; everything after the staging is the text of the packed kernel, so a sequence gets
 //               the bits of the packed call on the same tokens.
 //   FEAT bit 7  an e4m3 pool (always with bits 3 and 6): instantiated by fa_ex_mfma_kv8.hip, a translation unit of its own.
+//   FEAT bit 8  an additive bias (always with bit 4 and with no other): instantiated by fa_ex_mfma_bias.hip, a translation unit of
+//               its own, whose header has the loaders and where dS is stored.
 // One kernel template per pass (fa_ex_mfma_kernels.h: the bodies and their device helpers; the parameter block is a function of
 // FEAT), one forward and one backward launcher, one function from a call to its FEAT and one list of the FEAT values a call family
 // may instantiate (fa_ex_mfma_feat.h).  This file holds the row-constant pre-pass, the support checks and the launches.
@@ -129,49 +131,6 @@ hipError_t launch_exm_prep(const ExArgs& a, int64_t d_row, float* nlse, float* n
                            (const float*)a.lse, nlse, ndelta, rows, (int)d_row, 1.f / a.scale, a.dlse);
     }
     return hipGetLastError();
-}
-
-// The backward of an instantiation, dense or packed (kFeatVarlen: a.cu_q is set).  FEAT never carries kFeatSink here: the backward
-// of a sink call runs the kernels of the call without sinks, and ex_dsink_kernel for the sinks' gradient.
-// workspace: [-lse/scale | -delta], one float per row each: (bh, nq), packed (heads_q, total_q)
-template <typename Tag, int D, int FEAT>
-static hipError_t exm_bwd_t(const ExArgs& a, hipStream_t st) {
-    constexpr bool VAR = (FEAT & kFeatVarlen) != 0;
-    const long long rows = VAR ? (long long)a.heads_q * a.total_q : (long long)a.bh * a.nq;
-    float* nlse = reinterpret_cast<float*>(a.workspace);
-    float* ndelta = nlse + ((rows + 63) & ~63ll);
-    const ExB<FEAT> p = make_exm_block<FEAT>(a);
-    const float c = a.scale * 1.4426950408889634f;
-    ProfScope ps(K_EX_BWD, st);
-    hipError_t e = launch_exm_prep(a, a.d, nlse, ndelta, st);
-    if (e != hipSuccess) return e;
-    if (a.sinks) {   // the sink's gradient from the caller's lse and the -delta just written (packed: at (head, token), as lse)
-        e = launch_ex_dsink(a, ndelta, VAR ? a.total_q : 0, 1, -1.f, st);
-        if (e != hipSuccess) return e;
-    }
-    if (a.nk > 0) {
-        const bool m16 = (FEAT & kFeatMask) && p.mask != nullptr && (p.nk & 15) == 0 && (p.mask_bh & 15) == 0 && (((uintptr_t)p.mask) & 15) == 0;
-        const size_t smem = (size_t)256 * D * 2 + 4 * 64 * D * 2 + 2 * 128 * sizeof(float) + (m16 ? 8 * 1024 : 0);   // + the waves' mask images
-        auto kern = m16 ? exm_dkdv_kernel<Tag, D, FEAT, (FEAT & kFeatMask) != 0> : exm_dkdv_kernel<Tag, D, FEAT, false>;
-        e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
-        if (e != hipSuccess) return e;
-        dim3 grid((unsigned)(((a.nk + 255) / 256) * a.bh));
-        hipLaunchKernelGGL(kern, grid, dim3(512), smem, st, (const uint16_t*)a.q, (const uint16_t*)a.k, (const uint16_t*)a.v,
-                           (const uint16_t*)a.dout, (const float*)nlse, (const float*)ndelta, (uint16_t*)a.dk, (uint16_t*)a.dv, p, c);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    if (a.nq > 0) {
-        const size_t smem = 2 * 2 * 64 * D * 2;
-        auto kern = exm_dq_kernel<Tag, D, FEAT>;
-        e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
-        if (e != hipSuccess) return e;
-        dim3 grid((unsigned)(((a.nq + 255) / 256) * a.bh));
-        hipLaunchKernelGGL(kern, grid, dim3(512), smem, st, (const uint16_t*)a.q, (const uint16_t*)a.k, (const uint16_t*)a.v,
-                           (const uint16_t*)a.dout, (const float*)nlse, (const float*)ndelta, (uint16_t*)a.dq, p, c);
-        e = hipGetLastError();
-    }
-    return e;
 }
 
 // one call of a family: its FEAT (exm_feat, fa_ex_mfma_feat.h), then the instantiation of the family's list that has it

@@ -1,5 +1,5 @@
-// Shared by the translation units of the 16-bit MFMA extended kernels (fa_ex_mfma.hip; fa_ex_mfma_kv8.hip: the e4m3 pool; and
-// fa_ex_mfma_vdim.hip, which takes the bits, ExP and the register map): the FEAT bits of an instantiation (fa_ex_mfma.hip's header
+// Shared by the translation units of the 16-bit MFMA extended kernels (fa_ex_mfma.hip; fa_ex_mfma_kv8.hip: the e4m3 pool;
+// fa_ex_mfma_bias.hip: the additive bias; and fa_ex_mfma_vdim.hip, which takes the bits, ExP and the register map): the FEAT bits of an instantiation (fa_ex_mfma.hip's header
 // has what each stands for), the parameter block that goes with them, the one function from a call to its FEAT with the table
 // that pins it, the FEAT values each call family may instantiate, and the accumulator register map.  Internal linkage, as when
 // each file had its own.
@@ -16,6 +16,7 @@ namespace fa {
 namespace {
 
 constexpr int kFeatMask = 1, kFeatDrop = 2, kFeatWindow = 4, kFeatVarlen = 8, kFeatScore = 16, kFeatSink = 32, kFeatPaged = 64, kFeatKv8 = 128;
+constexpr int kFeatBias = 256;   // an additive bias (fa_ex_mfma_bias.hip): always with kFeatScore, never with another bit
 // the parameter block of an instantiation: ExParamsK (+ the sinks) with kFeatSink, ExParamsS (+ the score modifiers) with
 // kFeatScore, else ExParams as before
 template <int FEAT> using ExP = typename std::conditional<(FEAT & kFeatSink) != 0, ExParamsK,
@@ -27,14 +28,17 @@ template <int FEAT> inline ExP<FEAT> make_exm_params(const ExArgs& a) {
 }
 // ... grown by the pages with kFeatPaged (ExParamsPg), and by the scales of an e4m3 pool with kFeatKv8 (ExParamsPg8): what a
 // kernel takes.  K and V are addressed as 16-bit words, or as bytes with kFeatKv8.
-template <int FEAT> using ExB = typename std::conditional<(FEAT & kFeatKv8) != 0, ExParamsPg8<ExP<FEAT>>,
-                                typename std::conditional<(FEAT & kFeatPaged) != 0, ExParamsPg<ExP<FEAT>>, ExP<FEAT>>::type>::type;
+// ... or by the bias group with kFeatBias (ExParamsB)
+template <int FEAT> using ExB = typename std::conditional<(FEAT & kFeatBias) != 0, ExParamsB,
+                                typename std::conditional<(FEAT & kFeatKv8) != 0, ExParamsPg8<ExP<FEAT>>,
+                                typename std::conditional<(FEAT & kFeatPaged) != 0, ExParamsPg<ExP<FEAT>>, ExP<FEAT>>::type>::type>::type;
 template <int FEAT> using ExKV = typename std::conditional<(FEAT & kFeatKv8) != 0, uint8_t, uint16_t>::type;
 template <int FEAT> inline ExB<FEAT> make_exm_block(const ExArgs& a) {
     ExB<FEAT> p;
     static_cast<ExP<FEAT>&>(p) = make_exm_params<FEAT>(a);
     if constexpr ((FEAT & kFeatPaged) != 0) p.pg = make_ex_page(a);
     if constexpr ((FEAT & kFeatKv8) != 0) p.q8 = make_ex_kv8(a);
+    if constexpr ((FEAT & kFeatBias) != 0) p.bs = make_ex_bias(a);
     return p;
 }
 
@@ -42,13 +46,15 @@ template <int FEAT> inline ExB<FEAT> make_exm_block(const ExArgs& a) {
 __device__ __forceinline__ constexpr int rc_of(int i) { return (i & 3) + 8 * (i >> 2); }
 
 // ---- from a call to its FEAT.  The four call families (the five launch_ex_mfma* entry points):
-enum ExmFamily { kExmDense, kExmVarlen, kExmPaged, kExmPagedKv8 };
+enum ExmFamily { kExmDense, kExmVarlen, kExmPaged, kExmPagedKv8, kExmBias };
 // masks: a dense or a block-sparse mask; sink_fwd: the forward of a call with sinks (its backward is the call's without them).
 //   dense          dropout takes the mask bit with it (the dropout kernels are the masked ones); a mask alone is bit 0
 //   varlen         never bit 0 (the C layer hands a packed call no mask); dropout is bit 1 alone
 //   paged, e4m3    forward only, neither mask nor dropout (ex_mfma_paged_supported turns dropout away)
 //   a sink forward always carries kFeatScore: it runs on the score-modifier body, with or without a modifier
+//   bias           kFeatBias | kFeatScore and nothing else: the C layer has refused every other feature by name
 constexpr int exm_feat(ExmFamily fam, bool masks, bool drop, bool window, bool score, bool sink_fwd) {
+    if (fam == kExmBias) return kFeatBias | kFeatScore;
     int f = fam == kExmDense ? 0 : fam == kExmVarlen ? kFeatVarlen : fam == kExmPaged ? kFeatVarlen | kFeatPaged : kFeatVarlen | kFeatPaged | kFeatKv8;
     if (fam == kExmDense) f |= drop ? kFeatMask | kFeatDrop : masks ? kFeatMask : 0;
     if (fam == kExmVarlen && drop) f |= kFeatDrop;
@@ -103,6 +109,9 @@ static_assert(exm_feat(kExmPaged, x0, false, true, false, false) == (P | 4) && e
 static_assert(exm_feat(kExmPagedKv8, x0, false, true, x0, true) == (Q | K | 4) && exm_feat(kExmPagedKv8, x0, false, false, x1, true) == (Q | K));  // kv8 297
 static_assert(exm_feat(kExmPagedKv8, x0, false, true, true, false) == (Q | S | 4) && exm_feat(kExmPagedKv8, x0, false, false, true, false) == (Q | S));   // kv8 298
 static_assert(exm_feat(kExmPagedKv8, x0, false, true, false, false) == (Q | 4) && exm_feat(kExmPagedKv8, x1, false, false, false, false) == Q);    // kv8 299
+// the bias family (fa_ex_mfma_bias.hip): one FEAT, whatever the other inputs say
+static_assert(exm_feat(kExmBias, x0, x0, x0, x0, x0) == (256 | S) && exm_feat(kExmBias, x1, x1, x1, x1, x1) == (256 | S));
+static_assert(exm_feat(kExmBias, x0, x0, x0, x1, x0) == (kFeatBias | kFeatScore));
 }  // namespace exm_feat_table
 
 // ---- the FEAT values a family may instantiate: {feature bits} x {plain, score, score + sink}.  An instantiation with kFeatSink
@@ -113,6 +122,7 @@ using ExmDenseFeats = ExmFeatsX3<0, 0, 1, 3, 4, 5, 7>;
 using ExmVarlenFeats = ExmFeatsX3<kFeatVarlen, 0, 2, 4, 6>;
 using ExmPagedFeats = ExmFeatsX3<kFeatVarlen | kFeatPaged, 0, 4>;
 using ExmPagedKv8Feats = ExmFeatsX3<kFeatVarlen | kFeatPaged | kFeatKv8, 0, 4>;
+using ExmBiasFeats = ExmFeats<kFeatBias | kFeatScore>;   // a forward, a dK/dV and a dQ kernel (fa_ex_mfma_bias.hip)
 
 // run(tag, D, FEAT as integral constants) for the call's dtype and head_dim and for `feat`, if the list holds it; a FEAT outside
 // the list is hipErrorInvalidValue, never another kernel

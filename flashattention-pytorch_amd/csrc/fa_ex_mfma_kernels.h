@@ -1,5 +1,6 @@
-// The three kernels of the extended 16-bit MFMA family and the device helpers they use, for the two translation units that
-// instantiate them (fa_ex_mfma.hip: every 16-bit call; fa_ex_mfma_kv8.hip: the kFeatKv8 instantiations of the forward):
+// The three kernels of the extended 16-bit MFMA family and the device helpers they use, for the three translation units that
+// instantiate them (fa_ex_mfma.hip: every 16-bit call; fa_ex_mfma_kv8.hip: the kFeatKv8 instantiations of the forward;
+// fa_ex_mfma_bias.hip: the kFeatBias instantiations of all three, whose header says what the bit changes):
 //   exm_fwd_kernel<Tag, D, FEAT>, exm_dkdv_kernel<Tag, D, FEAT, M16>, exm_dq_kernel<Tag, D, FEAT>.
 // fa_ex_mfma.hip's header says what each FEAT bit stands for.  The parameter block (ExB<FEAT>) and the type K and V are addressed
 // by (ExKV<FEAT>) are functions of FEAT alone, so every instantiation is one function of its own, as when each parameter block
@@ -205,6 +206,83 @@ template <int FEAT, typename P> __device__ __forceinline__ const ExPage& pg_of(c
 // this unit's al (0 without ALiBi), the same product in every kernel
 __device__ __forceinline__ float alibi_k(const ExScore& sc, int bh) { return ex_slope(sc, bh) * sc.al_k; }
 
+// ---- Additive bias (FEAT bit 8, always on the kFeatScore body): s = scale q.k + bias[b, h, i, j], in the raw-score domain of these
+// kernels fma(bias, 1 / scale, q.k), the bias widened exactly.  The bias group of a kFeatBias instantiation's ExParamsB:
+template <int FEAT, typename P> __device__ __forceinline__ const ExBias& bias_of(const P& p) { return p.bs; }
+// This unit's bias as a range-checked buffer (rows i * b_rs, b_rs = 0: one row for every query), sized to the unit's span with the
+// last row's keys rounded up to 8: the C layer asks for that much storage, and a load is then wholly inside or wholly outside the
+// range.  Reads past it (rows >= nq) return 0.  A key >= nk of an earlier row reads padding, whatever it holds: the kernels make such
+// a key invisible with a select after the sum, so it reaches no result.  ds: the unit's dS rows (null: none asked for).
+struct BiasSrc {
+    buf_rsrc_t rs;
+    uint16_t* ds;
+    int b_rs, s_rs;
+    float binv;
+};
+__device__ __forceinline__ BiasSrc make_bias_src(const ExBias& bs, int bh, int nq, int nk) {
+    BiasSrc s;
+    const int b = bh / bs.heads, hh = bh - b * bs.heads;
+    s.rs = make_rsrc(bs.bias + b * bs.b_bs + hh * bs.b_hs, ((unsigned)(nq - 1) * (unsigned)bs.b_rs + (unsigned)((nk + 7) & ~7)) * 2u);
+    s.ds = bs.ds ? bs.ds + b * bs.s_bs + hh * bs.s_hs : nullptr;
+    s.b_rs = bs.b_rs; s.s_rs = bs.s_rs;
+    s.binv = bs.inv_scale;
+    return s;
+}
+// Query on the lane: the lane's row is `row`, registers 4 g .. 4 g + 3 hold keys kcol + 8 g .. + 3 — four 8-byte loads per block
+__device__ __forceinline__ void bias_load_q(const BiasSrc& s, int row, int kcol, u32x2 (&bw)[4]) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) bw[g] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(s.rs, (row * s.b_rs + kcol + 8 * g) * 2, 0, 0));
+}
+template <typename Tag>
+__device__ __forceinline__ void bias_add_q(f32x16& sacc, const u32x2 (&bw)[4], float binv) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        sacc[4 * g + 0] = fmaf(unpack_lo<Tag>(bw[g][0]), binv, sacc[4 * g + 0]);
+        sacc[4 * g + 1] = fmaf(unpack_hi<Tag>(bw[g][0]), binv, sacc[4 * g + 1]);
+        sacc[4 * g + 2] = fmaf(unpack_lo<Tag>(bw[g][1]), binv, sacc[4 * g + 2]);
+        sacc[4 * g + 3] = fmaf(unpack_hi<Tag>(bw[g][1]), binv, sacc[4 * g + 3]);
+    }
+}
+// Key on the lane: a lane needs 16 rows of one key column.  The block's 32 x 32 values are 2 KiB, two 16-byte loads per lane (lane
+// l: row l >> 1, bytes 32 (l & 1) ..), written to a 2 KiB image [row][64 bytes] of the wave's own, from which the lane reads its
+// key's column (dense_bits_k_lds does the same with the mask's bytes; a wave's LDS instructions execute in order, so the reads see
+// the wave's own writes without a barrier, and the next block's writes come after this block's reads).
+__device__ __forceinline__ void bias_load_k(const BiasSrc& s, int rb0, int kw0, int lane, u32x4& w0, u32x4& w1) {
+    asm volatile("" : "+v"(lane));   // (the lane-constant part of the address is made per call, as in dense_bits_k_lds)
+    const int off = ((rb0 + (lane >> 1)) * s.b_rs + kw0 + 16 * (lane & 1)) * 2;
+    w0 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(s.rs, off, 0, 0));
+    w1 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(s.rs, off + 16, 0, 0));
+}
+template <typename Tag>
+__device__ __forceinline__ void bias_add_k(f32x16& sacc, const u32x4& w0, const u32x4& w1, int lane, char* img /* this wave's 2 KiB */, float binv) {
+    asm volatile("" : "+v"(lane));
+    *reinterpret_cast<volatile u32x4*>(img + 32 * lane) = w0;
+    *reinterpret_cast<volatile u32x4*>(img + 32 * lane + 16) = w1;
+    const char* col = img + 256 * (lane >> 5) + 2 * (lane & 31);   // row 4 h + rc(i): immediate offsets from one address
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        unsigned v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = *reinterpret_cast<const volatile uint16_t*>(col + 64 * (j + 8 * g));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sacc[4 * g + j] = fmaf(unpack_lo<Tag>(v[j]), binv, sacc[4 * g + j]);   // four reads in flight at a time
+    }
+}
+// dS out (the dQ kernel): the 16-bit words a lane packs for its MFMA are 4 consecutive keys of its row per register group, 8
+// bytes; the row's last group stores its keys below nk one by one, so nothing past column nk is written
+__device__ __forceinline__ void bias_ds_store(uint16_t* row, int col, int nk, unsigned lo, unsigned hi) {
+    if (col + 4 <= nk) {
+        u32x2 v;
+        v[0] = lo; v[1] = hi;
+        *reinterpret_cast<u32x2*>(row + col) = v;
+    } else {
+        if (col + 0 < nk) row[col + 0] = (uint16_t)(lo & 0xffffu);
+        if (col + 1 < nk) row[col + 1] = (uint16_t)(lo >> 16);
+        if (col + 2 < nk) row[col + 2] = (uint16_t)(hi & 0xffffu);
+        if (col + 3 < nk) row[col + 3] = (uint16_t)(hi >> 16);
+    }
+}
+
 __device__ __forceinline__ unsigned keep_bits_k(const ExParams& p, unsigned hi_bh, int rrow, int key) {
     unsigned bits = 0;
     const int sh = 16 * (key & 1);
@@ -259,6 +337,8 @@ __global__ __launch_bounds__(512, 2) void exm_fwd_kernel(const uint16_t* __restr
     constexpr bool VAR = (FEAT & kFeatVarlen) != 0, SC = (FEAT & kFeatScore) != 0, SNK = (FEAT & kFeatSink) != 0;
     constexpr bool PG = (FEAT & kFeatPaged) != 0;   // k, v are pools read through a block table: only `stage` differs
     constexpr bool KV8 = (FEAT & kFeatKv8) != 0;    // ... of e4m3 bytes: `stage` and `land` differ
+    constexpr bool BIAS = (FEAT & kFeatBias) != 0;  // an additive bias joins the scores where ALiBi does
+    static_assert(!BIAS || (FEAT & ~kFeatBias) == kFeatScore, "a bias instantiation is the score-modifier body and nothing else");
     extern __shared__ __attribute__((aligned(16))) char smem[];   // [2 buffers][K tile | V tile]; kFeatKv8: then [K | V] e4m3 bytes of one tile
     const int DR = p.d;
     int nq = p.nq, nk = p.nk;
@@ -347,6 +427,8 @@ __global__ __launch_bounds__(512, 2) void exm_fwd_kernel(const uint16_t* __restr
     if constexpr (SC) al = alibi_k(sc_of<FEAT>(p), bh);
     [[maybe_unused]] float snk = -INFINITY;   // this unit's sink logit (kFeatSink): workgroup-uniform, one scalar load
     if constexpr (SNK) snk = ex_sink(sink_of<FEAT>(p), bh);
+    [[maybe_unused]] BiasSrc bsrc;
+    if constexpr (BIAS) bsrc = make_bias_src(bias_of<FEAT>(p), bh, nq, nk);
 
     f32x16 oacc[NDV];
 #pragma unroll
@@ -392,7 +474,8 @@ __global__ __launch_bounds__(512, 2) void exm_fwd_kernel(const uint16_t* __restr
     // first, the wait for the mask words would also be a wait for that whole tile.  So the DMA goes out when the mask has
     // been read (it still has the tile's products to land).  Fetching the words a tile ahead instead (16 more live
     // registers) was measured slower: 1.15 vs 1.08 ms forward at BH 64, N 4096, half the pairs masked.
-    const bool late_stage = (FEAT & kFeatMask) && msk.on;
+    // (the bias words are VMEM loads as well: a kFeatBias instantiation always stages late)
+    const bool late_stage = BIAS || ((FEAT & kFeatMask) && msk.on);
     while (t < ntiles_w) {
         const int tn = next_live(t + 1);
         if (!late_stage && tn < ntiles) stage(cur ^ 1, tn * BN);
@@ -424,6 +507,12 @@ __global__ __launch_bounds__(512, 2) void exm_fwd_kernel(const uint16_t* __restr
                 any_vis = __any(all != 0) != 0;
                 if (late_stage && tn < ntiles) stage(cur ^ 1, tn * BN);   // the mask words have arrived
             }
+            [[maybe_unused]] u32x2 bw[KB][4];   // kFeatBias: this lane's 4 x 16 bias values, requested ahead of the S MFMAs
+            if constexpr (BIAS) {
+#pragma unroll
+                for (int kb = 0; kb < KB; ++kb) bias_load_q(bsrc, qrow, k0 + 32 * kb + 4 * h, bw[kb]);
+                if (tn < ntiles) stage(cur ^ 1, tn * BN);   // behind the bias loads: VMEM returns in order
+            }
             if (any_vis) {
             f32x16 sacc[KB];
 #pragma unroll
@@ -450,6 +539,10 @@ __global__ __launch_bounds__(512, 2) void exm_fwd_kernel(const uint16_t* __restr
 #pragma unroll
                         for (int i = 0; i < 16; ++i) sacc[kb][i] = mod_alibi(sacc[kb][i], al, fb - (float)rc_of(i));
                     }
+                }
+                if constexpr (BIAS) {   // a key >= nk may have added padding, NaN included: the select below takes it out
+#pragma unroll
+                    for (int kb = 0; kb < KB; ++kb) bias_add_q<Tag>(sacc[kb], bw[kb], bsrc.binv);
                 }
             }
             // ---- causal diagonal / ragged last tile: key index of register i is k0 + 32 kb + 4 h + rc(i)
@@ -589,6 +682,8 @@ __global__ __launch_bounds__(512, 2) void exm_dkdv_kernel(const uint16_t* __rest
     static_assert((FEAT & (kFeatSink | kFeatPaged | kFeatKv8)) == 0, "forward-only bits");
     constexpr int NW = 8, BK = 32 * NW, BQ = 64, NKS = D / 16, NDB = D / 32;
     constexpr bool VAR = (FEAT & kFeatVarlen) != 0, SC = (FEAT & kFeatScore) != 0;
+    constexpr bool BIAS = (FEAT & kFeatBias) != 0;   // + 8 x 2 KiB behind the row constants: the waves' bias images
+    static_assert(!BIAS || ((FEAT & ~kFeatBias) == kFeatScore && !M16), "a bias instantiation is the score-modifier body and nothing else");
     constexpr int K_BYTES = BK * D * 2, Q_BYTES = BQ * D * 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Ks = smem;                      // [256][D]
@@ -637,6 +732,8 @@ __global__ __launch_bounds__(512, 2) void exm_dkdv_kernel(const uint16_t* __rest
     const int cbw = min(kw0, nk - 1) / p.bc;   // block column of this wave's 32 keys (bc is a multiple of 32)
     [[maybe_unused]] float al = 0.f;
     if constexpr (SC) al = alibi_k(sc_of<FEAT>(p), bh);
+    [[maybe_unused]] BiasSrc bsrc;
+    if constexpr (BIAS) bsrc = make_bias_src(bias_of<FEAT>(p), bh, nq, nk);
 
     if constexpr (VAR) dma_stage_tile<D, BK, NW, VAR>(k_rs, Ks, key0, dma_lane_voff<D, VAR>(lane, w, DR, p.sk), w, DR, 0, p.sk);
     else dma_stage_tile<D, BK, NW>(k_rs, Ks, key0, dma_voff, w, DR);
@@ -712,6 +809,8 @@ __global__ __launch_bounds__(512, 2) void exm_dkdv_kernel(const uint16_t* __rest
             u32x4 pp[2], sp[2];
             [[maybe_unused]] u32x4 pu[2];   // dropout: the un-dropped 16-bit P (dS = P (dP_drop - delta)); score modifiers: P (1 - t^2)
             [[maybe_unused]] float dt[16];  // score modifiers: the softcap's derivative 1 - t^2
+            [[maybe_unused]] u32x4 bq0, bq1;   // kFeatBias: this lane's 32 bytes of the block's bias, requested ahead of the S MFMAs
+            if constexpr (BIAS) bias_load_k(bsrc, rb0, kw0, lane, bq0, bq1);
             {
                 f32x16 sacc;
                 // seeded with -lse / scale; with a score modifier S starts at 0, is modified, and then -lse / scale is added
@@ -741,6 +840,7 @@ __global__ __launch_bounds__(512, 2) void exm_dkdv_kernel(const uint16_t* __rest
 #pragma unroll
                         for (int i = 0; i < 16; ++i) sacc[i] = mod_alibi(sacc[i], al, fb + (float)rc_of(i));
                     }
+                    if constexpr (BIAS) bias_add_k<Tag>(sacc, bq0, bq1, lane, reinterpret_cast<char*>(Ls + 2 * 128) + 2048 * w, bsrc.binv);
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         const f32x4 a = *reinterpret_cast<const f32x4*>(Lt + 32 * qb + 8 * g + 4 * h);
@@ -890,6 +990,8 @@ __global__ __launch_bounds__(512, 2) void exm_dq_kernel(const uint16_t* __restri
     static_assert((FEAT & (kFeatSink | kFeatPaged | kFeatKv8)) == 0, "forward-only bits");
     constexpr int NW = 8, BM = 32 * NW, BN = 64, NKS = D / 16, NDB = D / 32, TILE_BYTES = BN * D * 2;
     constexpr bool VAR = (FEAT & kFeatVarlen) != 0, SC = (FEAT & kFeatScore) != 0;
+    constexpr bool BIAS = (FEAT & kFeatBias) != 0;   // the bias joins the scores; this kernel also stores dS where it is asked for
+    static_assert(!BIAS || (FEAT & ~kFeatBias) == kFeatScore, "a bias instantiation is the score-modifier body and nothing else");
     extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 buffers][K tile | V tile]
     const int DR = p.d;
     int nq = p.nq, nk = p.nk;
@@ -941,6 +1043,12 @@ __global__ __launch_bounds__(512, 2) void exm_dq_kernel(const uint16_t* __restri
     const int rbw = min(q0 + 32 * w, nq - 1) / p.br;
     [[maybe_unused]] float al = 0.f;
     if constexpr (SC) al = alibi_k(sc_of<FEAT>(p), bh);
+    [[maybe_unused]] BiasSrc bsrc;
+    [[maybe_unused]] uint16_t* dsrow = nullptr;   // this lane's row of dS (null: none to store)
+    if constexpr (BIAS) {
+        bsrc = make_bias_src(bias_of<FEAT>(p), bh, nq, nk);
+        if (bsrc.ds && live_row) dsrow = bsrc.ds + (size_t)qrow * bsrc.s_rs;
+    }
 
     f32x16 dqa[NDB];
 #pragma unroll
@@ -974,7 +1082,7 @@ __global__ __launch_bounds__(512, 2) void exm_dq_kernel(const uint16_t* __restri
             t = tn;
         }
     }
-    const bool late_stage = (FEAT & kFeatMask) && msk.on;   // see the forward kernel
+    const bool late_stage = BIAS || ((FEAT & kFeatMask) && msk.on);   // see the forward kernel
     while (t < ntiles_w) {
         const int tn = next_live(t + 1);
         if (!late_stage && tn < ntiles) stage(cur ^ 1, tn * BN);
@@ -992,6 +1100,12 @@ __global__ __launch_bounds__(512, 2) void exm_dq_kernel(const uint16_t* __restri
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
                 if (use_bm && p.bmask[rbw * p.nbc + min(k0 + 32 * kb, nk - 1) / p.bc] == 0) visw[kb] = 0;
+        }
+        [[maybe_unused]] u32x2 bw[2][4];   // kFeatBias: this lane's 2 x 16 bias values
+        if constexpr (BIAS) {
+            bias_load_q(bsrc, qrow, k0 + 4 * h, bw[0]);
+            bias_load_q(bsrc, qrow, k0 + 32 + 4 * h, bw[1]);
+            if (tn < ntiles) stage(cur ^ 1, tn * BN);
         }
         // a tile of which this wave sees nothing is not computed (wave-uniform; see the forward kernel)
         const bool any_vis = !(FEAT & kFeatMask) || __any((visw[0] | visw[1]) != 0) != 0;
@@ -1034,6 +1148,7 @@ __global__ __launch_bounds__(512, 2) void exm_dq_kernel(const uint16_t* __restri
 #pragma unroll
                     for (int i = 0; i < 16; ++i) sacc[i] = mod_alibi(sacc[i], al, fb - (float)rc_of(i));
                 }
+                if constexpr (BIAS) bias_add_q<Tag>(sacc, bw[kb], bsrc.binv);
 #pragma unroll
                 for (int i = 0; i < 16; ++i) sacc[i] += nl;
             }
@@ -1075,6 +1190,15 @@ __global__ __launch_bounds__(512, 2) void exm_dq_kernel(const uint16_t* __restri
                 for (int j = 0; j < 4; ++j) dsb[kb][s][j] = pack2<Tag>(pacc[8 * s + 2 * j], pacc[8 * s + 2 * j + 1]);
             __builtin_amdgcn_sched_barrier(0);
         }
+        if constexpr (BIAS) {   // dS out: the words of the MFMA below, group g = registers 4 g .. 4 g + 3 = words 2 (g & 1), + 1 of half g >> 1
+            if (dsrow) {
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+                        bias_ds_store(dsrow, k0 + 32 * kb + 4 * h + 8 * g, nk, dsb[kb][g >> 1][2 * (g & 1)], dsb[kb][g >> 1][2 * (g & 1) + 1]);
+            }
+        }
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -1102,6 +1226,16 @@ __global__ __launch_bounds__(512, 2) void exm_dq_kernel(const uint16_t* __restri
         __syncthreads();
         cur ^= 1;
         t = tn;
+    }
+    if constexpr (BIAS) {
+        // dS of the keys right of the tiles this wave computed (under the causal diagonal; a dead row computes none): zeros, so that
+        // every element [:nq, :nk] is written by the call.  Row by row, the lanes across the row's keys.
+        if (bsrc.ds) {
+            for (int rr = 0; rr < 32 && q0 + 32 * w + rr < nq; ++rr) {
+                uint16_t* zrow = bsrc.ds + (size_t)(q0 + 32 * w + rr) * bsrc.s_rs;
+                for (int c = ntiles_w * BN + 4 * lane; c < nk; c += 256) bias_ds_store(zrow, c, nk, 0u, 0u);
+            }
+        }
     }
     if (live_row) {
         uint16_t* drow = dq + obase + (size_t)qrow * ostr;
@@ -1131,6 +1265,50 @@ static hipError_t exm_fwd_t(const ExArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(kern, grid, dim3(512), smem, st, (const uint16_t*)a.q, (const ExKV<FEAT>*)a.k, (const ExKV<FEAT>*)a.v,
                        (uint16_t*)a.o, a.lse, make_exm_block<FEAT>(a), a.scale * 1.4426950408889634f);
     return hipGetLastError();
+}
+
+// The backward launches of an instantiation, dense or packed (kFeatVarlen: a.cu_q is set): the pre-pass (fa_ex_mfma.hip), dK/dV, dQ.  FEAT never carries kFeatSink here: the backward
+// of a sink call runs the kernels of the call without sinks, and ex_dsink_kernel for the sinks' gradient.
+// workspace: [-lse/scale | -delta], one float per row each: (bh, nq), packed (heads_q, total_q)
+template <typename Tag, int D, int FEAT>
+static hipError_t exm_bwd_t(const ExArgs& a, hipStream_t st) {
+    constexpr bool VAR = (FEAT & kFeatVarlen) != 0;
+    const long long rows = VAR ? (long long)a.heads_q * a.total_q : (long long)a.bh * a.nq;
+    float* nlse = reinterpret_cast<float*>(a.workspace);
+    float* ndelta = nlse + ((rows + 63) & ~63ll);
+    const ExB<FEAT> p = make_exm_block<FEAT>(a);
+    const float c = a.scale * 1.4426950408889634f;
+    ProfScope ps(K_EX_BWD, st);
+    hipError_t e = launch_exm_prep(a, a.d, nlse, ndelta, st);
+    if (e != hipSuccess) return e;
+    if (a.sinks) {   // the sink's gradient from the caller's lse and the -delta just written (packed: at (head, token), as lse)
+        e = launch_ex_dsink(a, ndelta, VAR ? a.total_q : 0, 1, -1.f, st);
+        if (e != hipSuccess) return e;
+    }
+    if (a.nk > 0) {
+        const bool m16 = (FEAT & kFeatMask) && p.mask != nullptr && (p.nk & 15) == 0 && (p.mask_bh & 15) == 0 && (((uintptr_t)p.mask) & 15) == 0;
+        const size_t smem = (size_t)256 * D * 2 + 4 * 64 * D * 2 + 2 * 128 * sizeof(float) + (m16 ? 8 * 1024 : 0)   // + the waves' mask images
+                            + ((FEAT & kFeatBias) != 0 ? 8 * 2048 : 0);                                              // or their bias images
+        auto kern = m16 ? exm_dkdv_kernel<Tag, D, FEAT, (FEAT & kFeatMask) != 0> : exm_dkdv_kernel<Tag, D, FEAT, false>;
+        e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
+        if (e != hipSuccess) return e;
+        dim3 grid((unsigned)(((a.nk + 255) / 256) * a.bh));
+        hipLaunchKernelGGL(kern, grid, dim3(512), smem, st, (const uint16_t*)a.q, (const uint16_t*)a.k, (const uint16_t*)a.v,
+                           (const uint16_t*)a.dout, (const float*)nlse, (const float*)ndelta, (uint16_t*)a.dk, (uint16_t*)a.dv, p, c);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (a.nq > 0) {
+        const size_t smem = 2 * 2 * 64 * D * 2;
+        auto kern = exm_dq_kernel<Tag, D, FEAT>;
+        e = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
+        if (e != hipSuccess) return e;
+        dim3 grid((unsigned)(((a.nq + 255) / 256) * a.bh));
+        hipLaunchKernelGGL(kern, grid, dim3(512), smem, st, (const uint16_t*)a.q, (const uint16_t*)a.k, (const uint16_t*)a.v,
+                           (const uint16_t*)a.dout, (const float*)nlse, (const float*)ndelta, (uint16_t*)a.dq, p, c);
+        e = hipGetLastError();
+    }
+    return e;
 }
 
 }  // namespace fa

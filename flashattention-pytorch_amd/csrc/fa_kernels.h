@@ -179,6 +179,16 @@ struct ExArgs {
     // (varlen: o, dout rows of heads_q * d_v), the call goes to launch_ex_vdim (fa_ex_mfma_vdim.hip) and carries no other feature
     // than causal, kv_group, packing and dlse.  The C layer passes d_v = d as 0.
     int64_t d_v = 0;
+    // additive attention bias (fa_ex_*_bias; bias != null): s = scale q.k + bias[b, h, i, j] for query unit u = b * bias_heads + h,
+    // in q's dtype (f16 / bf16), read at bias + b * bias_bstride + h * bias_hstride + i * bias_rstride + j (elements; a stride of 0
+    // broadcasts); -inf = the key is not visible.  The call goes to launch_ex_mfma_bias (fa_ex_mfma_bias.hip) and carries no other
+    // feature than causal, kv_group and dlse.  Backward: dbias != null receives dS = P (dP - delta + dlse) at its own strides, every
+    // element [.., :nq, :nk] written; a dbias stride of 0 over a dimension of more than one unit is the fp32 sum over it, in unit
+    // order, rounded once (through a workspace of ex_bias_ds_bytes behind the row constants).
+    const void* bias = nullptr;
+    int64_t bias_heads = 1, bias_bstride = 0, bias_hstride = 0, bias_rstride = 0;
+    void* dbias = nullptr;
+    int64_t dbias_bstride = 0, dbias_hstride = 0, dbias_rstride = 0;
 };
 // does the call carry a score modifier (softcap or ALiBi)?  Such a call runs on the extended kernels only.
 inline bool ex_scoremod(const ExArgs& a) { return a.softcap > 0.0 || a.alibi != nullptr; }
@@ -200,6 +210,15 @@ hipError_t launch_ex_mfma_varlen_paged(const ExArgs& a, hipStream_t st);
 bool ex_mfma_paged_kv8_supported(const ExArgs& a);                    // the same from an e4m3 pool (a.kv_e4m3; fa_ex_mfma_kv8.hip)
 hipError_t launch_ex_mfma_varlen_paged_kv8(const ExArgs& a, hipStream_t st);
 size_t ex_backward_workspace_bytes(int64_t bh, int64_t nq);
+// a call with an additive bias (a.bias != null; fa_ex_mfma_bias.hip): the kFeatBias instantiations of the 16-bit MFMA kernels
+bool ex_mfma_bias_supported(const ExArgs& a);
+hipError_t launch_ex_mfma_bias(const ExArgs& a, bool backward, hipStream_t st);
+// is a.dbias the sum of the per-unit dS over a broadcast batch or head dimension?  Then the kernels write (bh, nq, nk padded to 8)
+// 16-bit dS into the workspace behind the row constants, ex_bias_ds_bytes of it, and one more launch sums them.
+inline bool ex_bias_reduced(int64_t bh, int64_t bias_heads, int64_t dbias_bstride, int64_t dbias_hstride) {
+    return bias_heads > 0 && ((dbias_bstride == 0 && bh / bias_heads > 1) || (dbias_hstride == 0 && bias_heads > 1));
+}
+inline size_t ex_bias_ds_bytes(int64_t bh, int64_t nq, int64_t nk) { return (size_t)bh * nq * ((nk + 7) & ~(int64_t)7) * 2; }
 // the row constants [-lse / scale | -delta (+ dlse)] of a backward whose o and dout rows are d_row wide (fa_ex_mfma.hip's pre-pass)
 hipError_t launch_exm_prep(const ExArgs& a, int64_t d_row, float* nlse, float* ndelta, hipStream_t st);
 // a.d_v != 0 (fa_ex_mfma_vdim.hip): 16-bit MFMA kernels with two widths, d <= 192 and d_v <= 128; padded and packed

@@ -54,6 +54,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_mla_sparse_forward", "fa_mla_sparse_workspace_bytes",
     "fa_mla_fp8_forward", "fa_mla_fp8_workspace_bytes", "fa_mla_fp8_pack",
     "fa_ex_forward_vdim", "fa_ex_backward_vdim", "fa_ex_forward_varlen_vdim", "fa_ex_backward_varlen_vdim",
+    "fa_ex_forward_bias", "fa_ex_backward_bias", "fa_ex_backward_workspace_bytes_bias",
 )
 
 
@@ -85,6 +86,8 @@ _SINK = _fields("p:sinks i:sink_heads")
 _DSINK = _fields("p:dsinks")
 _DLSE = _fields("p:dlse")                                     # the gradient of lse, after the sink group
 _VDIM = _fields("i:d_v")                                      # the width of v, o, do_, dv (0: d), after the sink / dlse group
+_BIAS = _fields("p:bias i:bias_heads,bias_batch_stride,bias_head_stride,bias_row_stride")   # an additive bias, after d_v
+_DBIAS = _fields("p:dbias i:dbias_batch_stride,dbias_head_stride,dbias_row_stride")          # its gradient (backward)
 _MASKS = _fields("p:mask i:mask_bh_stride p:block_mask i:br,bc")
 _DROPOUT = _fields("d:dropout_p u:dropout_seed")
 _VARLEN = _fields("p:cu_seqlens_q,cu_seqlens_k i:batch,heads_q,heads_kv,total_q,total_k,max_seqlen_q,max_seqlen_k,d c:dtype "
@@ -153,6 +156,9 @@ _sig("fa_ex_forward_vdim", _ex_sig(_FWD, _STREAM, _GROUP, _WINDOW, _MOD + _SINK 
 _sig("fa_ex_backward_vdim", _ex_sig(_BWD, _WS, _GROUP, _WINDOW, _MOD + _SINK + _DSINK + _DLSE + _VDIM))
 _sig("fa_ex_forward_varlen_vdim", _FWD + _VARLEN + _MODH + _SINK + _VDIM + _DROPOUT + _STREAM)
 _sig("fa_ex_backward_varlen_vdim", _BWD + _VARLEN + _MODH + _SINK + _DSINK + _DLSE + _VDIM + _DROPOUT + _WS)
+_sig("fa_ex_forward_bias", _ex_sig(_FWD, _STREAM, _GROUP, _WINDOW, _MOD + _SINK + _VDIM + _BIAS))
+_sig("fa_ex_backward_bias", _ex_sig(_BWD, _WS, _GROUP, _WINDOW, _MOD + _SINK + _DSINK + _DLSE + _VDIM + _BIAS + _DBIAS))
+_sig("fa_ex_backward_workspace_bytes_bias", _fields("i:bh") + _GROUP + _EXDIMS + _fields("c:dbias_reduced"), _SIZE)
 _sig("fa_ex_forward_varlen_paged", _FWD + _VARLEN + _MODH + _SINK + _VPAGED + _STREAM)
 _sig("fa_ex_forward_varlen_paged_fp8", _FWD + _VARLEN + _MODH + _SINK + _VPAGED + _FP8 + _STREAM)
 _sig("fa_ex_backward_workspace_bytes", _fields("i:bh") + _EXDIMS, _SIZE)
@@ -226,6 +232,9 @@ _family("fa_ex_backward_varlen_dlse", ["fa_ex_backward_varlen" + _suffix for _su
 # a v of its own width: each entry point takes the widest member above plus d_v and is called with exactly its own arguments, so
 # the four families above, and what their members are handed, stay what they were
 for _name in ("fa_ex_forward_vdim", "fa_ex_backward_vdim", "fa_ex_forward_varlen_vdim", "fa_ex_backward_varlen_vdim"):
+    _family(_name, [])
+# an additive bias: likewise a family of one each, called with exactly its own arguments
+for _name in ("fa_ex_forward_bias", "fa_ex_backward_bias"):
     _family(_name, [])
 _family("fa_ex_forward_varlen_paged_fp8", ["fa_ex_forward_varlen_paged"])
 _family("fa_rotary_apply", [])
@@ -572,6 +581,81 @@ def sinks_arg(who, sinks, device, units, heads=None):
     return sinks.data_ptr(), sinks.shape[0], sinks
 
 
+def bias_refuse(who, **carried):
+    """NotImplementedError naming the first argument in `carried` (name=truthy) that a call with attn_bias does not take"""
+    for name, on in carried.items():
+        if on:
+            hint = ": fold it into attn_bias as -inf" if name == "mask" else ""
+            raise NotImplementedError(f"{who}: {name} is not supported with attn_bias{hint}")
+
+
+def bias_arg(who, bias, q, nq, nk, units, heads=None, need_dbias=False, **carried):
+    """(pointer, bias_heads, batch stride, head stride, row stride, tensor) of an additive attention bias: q's dtype on q's device,
+    (Bb, Hb, Rb, Nk) with Bb in {1, B}, Hb in {1, H}, Rb in {1, Nq} and B * H = `units`, or (Ub, Rb, Nk) with Ub in {1, units}
+    (one bias per unit).  heads=None (the 3-D calls): H is the bias's own Hb (H = 1 with Hb = 1 and Bb = 1, units / Bb with Hb = 1).
+    It is passed by strides, never copied: the last dim contiguous, the data 16-byte aligned, every stride of a dimension that is
+    not broadcast a multiple of 8, the storage of a row reaching to Nk rounded up to 8 — ValueError otherwise, which says how to
+    allocate it.  Then NotImplementedError naming the first argument in `carried` (name=truthy) the bias kernels do not take, and
+    a gradient for a row-broadcast bias.  (0, 1, 0, 0, 0, None) without a bias."""
+    if bias is None:
+        return 0, 1, 0, 0, 0, None
+    if not isinstance(bias, torch.Tensor):
+        raise RuntimeError(f"{who}: attn_bias must be a tensor of q's dtype")
+    if bias.dtype != q.dtype:
+        raise RuntimeError(f"{who}: attn_bias must have q's dtype ({q.dtype}), got {bias.dtype}")
+    if bias.device != q.device:
+        raise RuntimeError(f"{who}: attn_bias must be on q's device ({q.device}), got {bias.device}")
+    shape = tuple(bias.shape)
+    if bias.dim() == 3:
+        forms = f"({units} or 1, {nq} or 1, {nk})"
+        ok = shape[0] in (1, units) and shape[1] in (1, nq) and shape[2] == nk
+        h = 1
+        sizes, strides = (shape[0], 1, shape[1]), (bias.stride(0), 0, bias.stride(1))
+    else:
+        if heads is None and bias.dim() == 4:
+            heads = shape[1] if shape[1] > 1 else (1 if shape[0] == 1 else max(units // max(shape[0], 1), 1))
+        h = heads if heads else 1
+        forms = f"(B or 1, H or 1, {nq} or 1, {nk}) with B * H = {units}" + (f", H = {h}" if heads else "")
+        ok = (bias.dim() == 4 and units % h == 0 and shape[0] in (1, units // h) and shape[1] in (1, h) and shape[2] in (1, nq) and
+              shape[3] == nk)
+        sizes, strides = shape[:3], bias.stride()[:3]
+    if not ok:
+        raise RuntimeError(f"{who}: attn_bias must be {forms}, got {shape}")
+    bias_refuse(who, **carried)
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise NotImplementedError(f"{who}: attn_bias needs float16 or bfloat16 tensors, got dtype {q.dtype} (no exact-f32 kernels with a bias)")
+    d = q.shape[-1]
+    if d > 128 or d % 8 != 0:
+        raise NotImplementedError(f"{who}: attn_bias needs d <= 128 and d % 8 == 0, got d={d} (no exact-f32 kernels with a bias)")
+    if need_dbias and sizes[2] == 1 and nq > 1:
+        raise NotImplementedError(f"{who}: a gradient for a row-broadcast attn_bias (shape {shape}, Nq={nq}) is not supported")
+    pad = "allocate the last dim padded to a multiple of 8 and pass the slice, bias_padded[..., :Nk]; the library never copies a bias"
+    if nk > 1 and bias.stride(-1) != 1:
+        raise ValueError(f"{who}: attn_bias must have a contiguous last dim (stride {bias.stride(-1)}); {pad}")
+    bs, hs, rs = (st if n > 1 else 0 for n, st in zip(sizes, strides))
+    if bs % 8 or hs % 8 or rs % 8 or bs < 0 or hs < 0 or rs < 0:
+        raise ValueError(f"{who}: attn_bias of shape {shape} has strides {tuple(bias.stride())}: every stride of a dimension that is not "
+                         f"broadcast must be a multiple of 8 elements; {pad}")
+    nkp = (nk + 7) // 8 * 8
+    last = bias.storage_offset() + (sizes[0] - 1) * bs + (sizes[1] - 1) * hs + (sizes[2] - 1) * rs
+    if nk > 0 and (last + nkp) * bias.element_size() > bias.untyped_storage().nbytes():
+        raise ValueError(f"{who}: the storage of attn_bias (shape {shape}) ends before Nk = {nk} rounded up to {nkp} in its last row; {pad}")
+    if bias.data_ptr() % 16 != 0:
+        raise ValueError(f"{who}: attn_bias must be 16-byte aligned; {pad}")
+    return bias.data_ptr(), h, bs, hs, rs, bias
+
+
+def _dbias_alloc(bias, nk):
+    """dbias for `bias`: the bias's own shape, a slice of a buffer whose last dim is padded to 8, and its three strides (0 = a
+    dimension of one: broadcast).  The call writes every element of the slice and nothing of the padding."""
+    lead = tuple(bias.shape[:-1])
+    dbias = torch.empty(lead + ((nk + 7) // 8 * 8,), dtype=bias.dtype, device=bias.device)[..., :nk]
+    st = dbias.stride()
+    if bias.dim() == 3:
+        return dbias, (st[0] if lead[0] > 1 else 0, 0, st[1] if lead[1] > 1 else 0)
+    return dbias, tuple(s if n > 1 else 0 for n, s in zip(lead, st[:3]))
+
+
 def vdim_arg(who, d, d_v, dtype, **carried):
     """The width of v as the library takes it: 0 where v is as wide as q and k (the call without the argument), else d_v after the
     rules of fa_ex_*_vdim in the library's order — NotImplementedError naming the first one broken: the widths, the dtype, then
@@ -600,7 +684,7 @@ def _ex_variant(sinks, mod, window, grouped=False, dlse=False, vdim=False) -> st
 
 
 def ex_forward(q, k, v, causal, softmax_scale, mask=None, block_mask=None, br=128, bc=128, dropout_p=0.0, seed=0, window=(-1, -1),
-               softcap=0.0, alibi_slopes=None, sinks=None):
+               softcap=0.0, alibi_slopes=None, *, attn_bias=None, sinks=None):
     """(o, lse) of attention with Nq != Nk (causal aligned bottom-right), dense mask (0 = masked), block-sparse mask
     (0 = tile skipped) and dropout; see include/fa_mi355x.h.  k and v with BH / g units (g query heads per K/V head) make
     it grouped-query attention.  window = (left, right): key j is visible to row i only within
@@ -610,18 +694,29 @@ def ex_forward(q, k, v, causal, softmax_scale, mask=None, block_mask=None, br=12
     column exp(sink) with a zero value to each row's softmax; lse contains it (fa_ex_forward_sink).
     v may be narrower than q and k, (BH / g, Nk, d_v) with 8 <= d_v < d <= 192, d_v <= 128, both multiples of 8, float16 / bfloat16
     (fa_ex_forward_vdim; MLA prefill: 192 + 128): o is then (BH, Nq, d_v).  It goes with causal, GQA and softmax_scale only: mask,
-    block_sparse_mask, dropout_p, window_size, softcap, alibi_slopes and sinks raise NotImplementedError with the name (vdim_arg)."""
+    block_sparse_mask, dropout_p, window_size, softcap, alibi_slopes and sinks raise NotImplementedError with the name (vdim_arg).
+    attn_bias (keyword-only; q's dtype, (Bb, Hb, Rb, Nk) or (BH or 1, Rb, Nk), broadcast by size 1, passed by strides: bias_arg) is
+    added to the scaled scores, -inf = masked (fa_ex_forward_bias).  It goes with causal, GQA and softmax_scale only as well."""
     wl, wr = window_arg("ex_forward", window)
     cap = softcap_arg("ex_forward", softcap)
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     bh, nq, nk, d, code, mask, mptr, mstride, block_mask, bptr, g = _ex_common("ex_forward", q, k, v, mask, block_mask, br, bc)
     aptr, aheads, astride, alibi_slopes = alibi_arg("ex_forward", alibi_slopes, q.device, bh)
     sptr, sheads, sinks = sinks_arg("ex_forward", sinks, q.device, bh)
+    bias = bias_arg("ex_forward", attn_bias, q, nq, nk, bh, mask=mask is not None, block_sparse_mask=block_mask is not None,
+                    dropout_p=dropout_p > 0.0, window_size=(wl, wr) != (-1, -1), softcap=cap > 0.0, alibi_slopes=aptr, sinks=sptr,
+                    **{"d_v != d": v.shape[2] != d})
     d_v = vdim_arg("ex_forward", d, v.shape[2], q.dtype, mask=mask is not None, block_sparse_mask=block_mask is not None,
                    dropout_p=dropout_p > 0.0, window_size=(wl, wr) != (-1, -1), softcap=cap > 0.0, alibi_slopes=aptr, sinks=sptr)
     with torch.cuda.device(q.device):
         o = torch.empty((bh, nq, v.shape[2]), dtype=q.dtype, device=q.device)
         lse = torch.empty((bh, nq), dtype=torch.float32, device=q.device)
+        if bias[0]:
+            _call("fa_ex_forward_bias", (
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), bh, g, nq, nk, d, code, int(bool(causal)), wl, wr,
+                float(softmax_scale), cap, aptr, aheads, astride, sptr, sheads, 0, *bias[:5], mptr, mstride, bptr, int(br), int(bc),
+                float(dropout_p), int(seed) & (2 ** 64 - 1), _stream_ptr(q.device)))
+            return o, lse
         _call("fa_ex_forward" + _ex_variant(sptr, cap > 0.0 or aptr, (wl, wr) != (-1, -1), g > 1, vdim=d_v), (
             q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), bh, g, nq, nk, d, code, int(bool(causal)), wl, wr,
             float(softmax_scale), cap, aptr, aheads, astride, sptr, sheads, *((d_v,) if d_v else ()), mptr, mstride, bptr, int(br), int(bc), float(dropout_p),
@@ -630,11 +725,14 @@ def ex_forward(q, k, v, causal, softmax_scale, mask=None, block_mask=None, br=12
 
 
 def ex_backward(q, k, v, o, do_, lse, causal, softmax_scale, mask=None, block_mask=None, br=128, bc=128, dropout_p=0.0, seed=0,
-                window=(-1, -1), softcap=0.0, alibi_slopes=None, *, dlse=None, sinks=None):
+                window=(-1, -1), softcap=0.0, alibi_slopes=None, *, dlse=None, attn_bias=None, need_dbias=False, sinks=None):
     """(dq, dk, dv) of ex_forward; with sinks (and the lse ex_forward returned with them) also dsinks, float32 (sink_heads,), as a
     fourth result (fa_ex_backward_sink).  dlse: the gradient of lse, float32 (BH, Nq) on q's device, or None
     (fa_ex_backward_dlse); rows whose lse is -inf ignore it.  dlse is keyword-only, and sinks with it: sinks stays the last parameter.
-    With a v of its own width (ex_forward) o and do_ are (BH, Nq, d_v) and dv comes back in v's shape (fa_ex_backward_vdim)."""
+    With a v of its own width (ex_forward) o and do_ are (BH, Nq, d_v) and dv comes back in v's shape (fa_ex_backward_vdim).
+    attn_bias: the bias of the forward (fa_ex_backward_bias); with need_dbias its gradient dS = P (dP - delta + dlse) comes back as an
+    extra last result, in the bias's own shape and dtype (the fp32 sum in unit order, rounded once, over a batch or head dimension
+    of size 1); a row-broadcast bias has no gradient here (NotImplementedError)."""
     wl, wr = window_arg("ex_backward", window)
     cap = softcap_arg("ex_backward", softcap)
     q, k, v, o, do_, lse = (t.contiguous() for t in (q, k, v, o, do_, lse))
@@ -642,6 +740,11 @@ def ex_backward(q, k, v, o, do_, lse, causal, softmax_scale, mask=None, block_ma
     aptr, aheads, astride, alibi_slopes = alibi_arg("ex_backward", alibi_slopes, q.device, bh)
     sptr, sheads, sinks = sinks_arg("ex_backward", sinks, q.device, bh)
     mod = cap > 0.0 or aptr != 0 or sptr != 0
+    bias = bias_arg("ex_backward", attn_bias, q, nq, nk, bh, need_dbias=bool(need_dbias), mask=mask is not None,
+                    block_sparse_mask=block_mask is not None, dropout_p=dropout_p > 0.0, window_size=(wl, wr) != (-1, -1),
+                    softcap=cap > 0.0, alibi_slopes=aptr, sinks=sptr, **{"d_v != d": v.shape[2] != d})
+    if need_dbias and not bias[0]:
+        raise RuntimeError("ex_backward: need_dbias without attn_bias")
     d_v = vdim_arg("ex_backward", d, v.shape[2], q.dtype, mask=mask is not None, block_sparse_mask=block_mask is not None,
                    dropout_p=dropout_p > 0.0, window_size=(wl, wr) != (-1, -1), softcap=cap > 0.0, alibi_slopes=aptr, sinks=sptr)
     if o.shape != (bh, nq, v.shape[2]) or do_.shape != o.shape or lse.shape != (bh, nq) or lse.dtype != torch.float32:
@@ -649,6 +752,17 @@ def ex_backward(q, k, v, o, do_, lse, causal, softmax_scale, mask=None, block_ma
     dlse = _dlse_arg("ex_backward", dlse, lse, "(BH, Nq)")
     with torch.cuda.device(q.device):
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        if bias[0]:
+            dbias, dstr = _dbias_alloc(bias[5], nk) if need_dbias else (None, (0, 0, 0))
+            reduced = int(need_dbias and ((dstr[0] == 0 and bh // bias[1] > 1) or (dstr[1] == 0 and bias[1] > 1)))
+            nbytes = int(_lib.fa_ex_backward_workspace_bytes_bias(bh, g, nq, nk, d, code, reduced))
+            ws = _workspace(q.device, nbytes)
+            _call("fa_ex_backward_bias", (
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do_.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+                dv.data_ptr(), bh, g, nq, nk, d, code, int(bool(causal)), wl, wr, float(softmax_scale), cap, aptr, aheads, astride, sptr,
+                sheads, 0, _ptr(dlse), 0, *bias[:5], _ptr(dbias), *dstr, mptr, mstride, bptr, int(br), int(bc), float(dropout_p),
+                int(seed) & (2 ** 64 - 1), ws.data_ptr(), nbytes, _stream_ptr(q.device)))
+            return (dq, dk, dv, dbias) if need_dbias else (dq, dk, dv)
         extras = int(mask is not None or block_mask is not None or dropout_p > 0.0 or mod or dlse is not None or d_v != 0 or
                      window_effective(nq, nk, bool(causal), (wl, wr)))   # (the dS hand-over serves neither a window nor a modifier,
         #                                                                    nor a gradient of lse)

@@ -589,6 +589,53 @@ int fa_ex_backward_varlen_vdim(const void* q, const void* k, const void* v, cons
                                const float* alibi_slopes, int64_t alibi_batch_stride, const float* sinks, int64_t sink_heads,
                                float* dsinks, const float* dlse, int64_t d_v, double dropout_p, uint64_t dropout_seed,
                                void* workspace, size_t workspace_bytes, void* stream);
+/* --- An additive attention bias with its gradient: the float attn_mask of scaled_dot_product_attention, CK FlashAttention's bias,
+ * xFormers' attn_bias, a relative-position table, a pair bias.  For query unit u = b * bias_heads + h, row i, key j
+ *     s[i, j] = softmax_scale * (q_i . k_j) + bias[b, h, i, j]
+ * and the softmax, o and lse are those of s; the causal flag (bottom-right aligned, Nq != Nk) applies as without a bias.  The bias
+ * has q's dtype (f16 / bf16), is read as stored, widened exactly and added in fp32; it is not multiplied by the scale.  An element
+ * may be -inf: that key is not visible, and a row whose visible keys are all -inf gives o = 0, lse = -inf, dq = 0.  +inf and NaN are
+ * the caller's error and are not checked.  fa_ex_forward_bias / fa_ex_backward_bias take the arguments of fa_ex_forward_vdim /
+ * fa_ex_backward_vdim and after d_v the group (bias, bias_heads, bias_batch_stride, bias_head_stride, bias_row_stride), the backward
+ * then (dbias, dbias_batch_stride, dbias_head_stride, dbias_row_stride).  bias == NULL with the rest of the group 0 / NULL is
+ * exactly the _vdim call: the same checks, the same launches, the same bits.
+ *   Layout: element [b, h, i, j] at bias + b * bias_batch_stride + h * bias_head_stride + i * bias_row_stride + j (elements); a
+ *   stride of 0 broadcasts that dimension and nothing is expanded in memory.  With kv_group > 1 the bias is per query head.  The
+ *   last dim is contiguous, the pointer 16-byte aligned, every non-zero stride a multiple of 8, and the storage of a row extends
+ *   to Nk rounded up to 8 elements (allocate the last dim padded and pass the slice); the padding may hold anything, NaN included,
+ *   and reaches no result.  The library never copies a bias.
+ *   dbias (NULL: none) receives dS[i, j] = P (dP - delta + dlse_i), the value the kernels round to 16 bits for their dQ / dK products
+ *   (without the scale), in the bias dtype at its own strides: exactly 0 wherever the key is not visible (causal flag, dead row,
+ *   -inf bias); every element [.., :Nq, :Nk] is written by the call and nothing past column Nk of a row is.  A dbias stride of 0
+ *   over the batch (BH / bias_heads > 1) or the heads (bias_heads > 1) makes dbias the sum of the per-unit dS over that dimension,
+ *   in fp32 in unit order, rounded once: deterministic, no atomics, through the workspace.  A dbias for a row-broadcast bias
+ *   (bias_row_stride = 0 with Nq > 1) is refused.
+ * Combines with causal, Nq != Nk, kv_group, softmax_scale, lse and dlse.  Kernels: the kFeatBias instantiations of the 16-bit MFMA
+ * extended kernels (fa_ex_mfma_bias.hip); never the plain kernels, the dS hand-over or the exact-f32 kernels.
+ * Refused before any other check and before any HIP call, the first broken rule in this order, each with a text of its own:
+ * (1) bias NULL with a stride or a dbias (FA_ERR_INVALID_ARGUMENT); (2) bias or dbias not 16-byte aligned (FA_ERR_UNSUPPORTED);
+ * (3) a stride that is negative or no multiple of 8 (FA_ERR_UNSUPPORTED); (4) bias_heads < 1 or not dividing BH
+ * (FA_ERR_INVALID_ARGUMENT); (5) dbias for a row-broadcast bias; then FA_ERR_UNSUPPORTED by name for (6) mask (fold it into the bias
+ * as -inf), block_sparse_mask, dropout_p > 0, window_size (window_left / window_right other than -1), softcap, alibi_slopes, sinks,
+ * d_v != d; (7) f32 tensors; (8) d > 128 or d % 8 != 0; (9) softmax_scale <= 0; (10) a unit's rows beyond 2^31 bytes.
+ * Workspace of the backward: fa_ex_backward_workspace_bytes_bias = fa_ex_backward_workspace_bytes_grouped, plus with dbias_reduced != 0
+ * (a dbias that is a sum over the batch or the heads) BH * Nq * (Nk rounded up to 8) * 2 bytes of per-unit dS. */
+int fa_ex_forward_bias(const void* q, const void* k, const void* v, void* o, float* lse, int64_t bh, int64_t kv_group, int64_t nq,
+                       int64_t nk, int64_t d, int dtype, int causal, int64_t window_left, int64_t window_right, double softmax_scale,
+                       double softcap, const float* alibi_slopes, int64_t alibi_heads, int64_t alibi_batch_stride, const float* sinks,
+                       int64_t sink_heads, int64_t d_v, const void* bias, int64_t bias_heads, int64_t bias_batch_stride,
+                       int64_t bias_head_stride, int64_t bias_row_stride, const uint8_t* mask, int64_t mask_bh_stride,
+                       const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* stream);
+int fa_ex_backward_bias(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq, void* dk,
+                        void* dv, int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype, int causal,
+                        int64_t window_left, int64_t window_right, double softmax_scale, double softcap, const float* alibi_slopes,
+                        int64_t alibi_heads, int64_t alibi_batch_stride, const float* sinks, int64_t sink_heads, float* dsinks,
+                        const float* dlse, int64_t d_v, const void* bias, int64_t bias_heads, int64_t bias_batch_stride,
+                        int64_t bias_head_stride, int64_t bias_row_stride, void* dbias, int64_t dbias_batch_stride,
+                        int64_t dbias_head_stride, int64_t dbias_row_stride, const uint8_t* mask, int64_t mask_bh_stride,
+                        const uint8_t* block_mask, int64_t br, int64_t bc, double dropout_p, uint64_t dropout_seed, void* workspace,
+                        size_t workspace_bytes, void* stream);
+size_t fa_ex_backward_workspace_bytes_bias(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype, int dbias_reduced);
 /* --- The varlen forward over a paged K/V cache: FlashAttention-2's flash_attn_varlen_func(..., block_table=).  Chunked prefill, or
  * prefill behind a shared prefix, reads its keys straight from the pools of the KV-cache calls, without a gathered copy and on the
  * kernel that reads a sequence's keys once per 256 query rows.  Forward only, no dropout.  The arguments are those of

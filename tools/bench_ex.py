@@ -36,6 +36,11 @@ kernels for a square call) — forward and backward.
 Attention sinks (--sinks: one logit per head, shape (H,)): the same shapes, optionally with --window L,R; the call with sinks
 against the call without on the extended MFMA kernels (ex_path 3) and on the default path, alternated --rounds times:
     python tools/bench_ex.py --sinks --causal [--window 1024,-1] [--batch 8] [--q-heads 32] [--nq 4096] [--head-dim 128] [--rounds 3]
+An additive bias (--bias: attn_bias, randn * 2 in the tensor dtype): BH = --bh units as B = BH / --q-heads batches of --q-heads heads,
+Nq = --nq, Nk = --nk.  Alternated --rounds times in one process: the call with a full (B, H, Nq, Nk) bias and with a (1, H, Nq, Nk)
+bias, forward and backward with and without dbias; the same call without a bias on the extended MFMA kernels (ex_path 3) and as the
+library routes it; and the call with a random dense mask (half the pairs).  Beside the times the bytes the bias adds per pass:
+    python tools/bench_ex.py --bias [--causal] [--bh 32] [--q-heads 8] [--nq 2048] [--nk 4096] [--head-dim 128] [--rounds 3]
 """
 import argparse
 import json
@@ -79,7 +84,10 @@ def main():
     ap.add_argument("--softcap", type=float, default=0.0, help="time the softcap (and --alibi) against the call without")
     ap.add_argument("--alibi", action="store_true", help="time ALiBi slopes (and --softcap) against the call without")
     ap.add_argument("--sinks", action="store_true", help="time attention sinks ((H,) logits) against the call without")
+    ap.add_argument("--bias", action="store_true", help="time an additive attn_bias (and its dbias) against the call without")
     args = ap.parse_args()
+    if args.bias:
+        return bench_bias(args)
     if args.sinks:
         return bench_sinks(args)
     if args.softcap > 0.0 or args.alibi:
@@ -412,6 +420,54 @@ def bench_sinks(args):
                          fwd_ms_all=[round(x, 3) for x in times[name][0]], bwd_ms_all=[round(x, 3) for x in times[name][1]]))
     print(json.dumps(dict(shape=dict(batch=b, q_heads=h, n=n, d=d, dtype=args.dtype, causal=causal, window=args.window, sinks=True,
                                      iters=args.iters, rounds=args.rounds), rows=rows)))
+
+
+def bench_bias(args):
+    dt = {"bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
+    bh, nq, nk, d, causal = args.bh, args.nq, args.nk, args.head_dim, args.causal
+    h = args.q_heads if bh % args.q_heads == 0 else 1
+    b, scale = bh // h, d ** -0.5
+    g = torch.Generator(device="cuda").manual_seed(0)
+    q, do = (torch.randn((bh, nq, d), device="cuda", dtype=dt, generator=g) for _ in range(2))
+    k, v = (torch.randn((bh, nk, d), device="cuda", dtype=dt, generator=g) for _ in range(2))
+    nkp = (nk + 7) // 8 * 8
+    full = (torch.randn((b, h, nq, nkp), device="cuda", generator=g) * 2).to(dt)[..., :nk]
+    one_h = (torch.randn((1, h, nq, nkp), device="cuda", generator=g) * 2).to(dt)[..., :nk]
+    mask = (torch.rand((nq, nk), device="cuda", generator=g) < 0.5).to(torch.uint8)
+    mask[:, 0] = 1
+    o0, l0 = ext.ex_forward(q, k, v, causal, scale)
+    of, lf = ext.ex_forward(q, k, v, causal, scale, attn_bias=full)
+    oh, lh = ext.ex_forward(q, k, v, causal, scale, attn_bias=one_h)
+    om, lm = ext.ex_forward(q, k, v, causal, scale, mask=mask)
+
+    def bwd(o, lse, **kw):
+        return lambda: ext.ex_backward(q, k, v, o, do, lse, causal, scale, **kw)
+    calls = {   # name: (ex_path, forward, backward, backward with dbias)
+        "bias_full": (0, lambda: ext.ex_forward(q, k, v, causal, scale, attn_bias=full), bwd(of, lf, attn_bias=full),
+                      bwd(of, lf, attn_bias=full, need_dbias=True)),
+        "bias_1h": (0, lambda: ext.ex_forward(q, k, v, causal, scale, attn_bias=one_h), bwd(oh, lh, attn_bias=one_h),
+                    bwd(oh, lh, attn_bias=one_h, need_dbias=True)),
+        "none_ex_mfma": (3, lambda: ext.ex_forward(q, k, v, causal, scale), bwd(o0, l0), None),
+        "none_auto": (0, lambda: ext.ex_forward(q, k, v, causal, scale), bwd(o0, l0), None),
+        "dense_mask": (0, lambda: ext.ex_forward(q, k, v, causal, scale, mask=mask), bwd(om, lm, mask=mask), None),
+    }
+    times = {name: ([], [], []) for name in calls}
+    try:
+        for _ in range(args.rounds):
+            for name, (path, f, bw, bwd_db) in calls.items():
+                ext.set_option("ex_path", path)
+                times[name][0].append(timed(f, args.iters))
+                times[name][1].append(timed(bw, args.iters))
+                if bwd_db is not None:
+                    times[name][2].append(timed(bwd_db, args.iters))
+    finally:
+        ext.set_option("ex_path", 0)
+    med = lambda t: round(sorted(t)[len(t) // 2], 3) if t else None   # noqa: E731
+    rows = [dict(call=name, fwd_ms=med(t[0]), bwd_ms=med(t[1]), bwd_dbias_ms=med(t[2]), fwd_ms_all=[round(x, 3) for x in t[0]],
+                 bwd_ms_all=[round(x, 3) for x in t[1]], bwd_dbias_ms_all=[round(x, 3) for x in t[2]]) for name, t in times.items()]
+    print(json.dumps(dict(shape=dict(bh=bh, batch=b, q_heads=h, nq=nq, nk=nk, d=d, dtype=args.dtype, causal=causal, bias=True, iters=args.iters,
+                                     rounds=args.rounds),
+                          bias_bytes_per_pass=bh * nq * nk * 2, dbias_bytes=bh * nq * nk * 2, rows=rows)))
 
 
 if __name__ == "__main__":
