@@ -706,3 +706,56 @@ def flash_mla_with_kvcache(q, k_cache, block_table, cache_seqlens, head_dim_v=51
         return flash_attn_with_kvcache(q[..., 512:], k_cache[..., 512:], k_cache[..., :512], cache_seqlens=cache_seqlens,
                                        block_table=block_table, softmax_scale=scale, causal=causal, num_splits=num_splits,
                                        return_softmax_lse=True, qv=q[..., :512])
+
+
+_FP8_REFUSED = ("window_size", "softcap", "alibi_slopes", "sinks", "attn_bias", "mask", "block_sparse_mask", "dropout_p", "cu_seqlens_q",
+                "cu_seqlens_k", "block_table", "rotary_cos", "rotary_sin")
+
+
+def flash_attention_fp8(q, k, v, *, q_descale=None, k_descale=None, v_descale=None, softmax_scale=None, causal=False,
+                        out_dtype=torch.bfloat16, layout="bhnd", return_lse=False, **unsupported):
+    """FlashAttention-3's fp8 call: attention over q, k, v that are ALREADY torch.float8_e4m3fn, with one float32 descale per
+    (batch, K/V head) for each of them (flash_attn_func(..., q_descale=, k_descale=, v_descale=)).  Forward only.
+        o = softmax(softmax_scale * q_descale * k_descale * q8 k8^T [causal]) (v8 * v_descale)
+    q (B, H_q, Nq, 128), k and v (B, H_kv, Nk, 128) with layout="bhnd"; (B, N, H, 128), FlashAttention-3's own layout, with
+    layout="bnhd".  Views are used at their own strides and never copied (a contiguous last dim, a 16-byte aligned start and strides
+    that are multiples of 16 bytes): the [:, :Nk] prefix of a (B, capacity, H_kv, 128) e4m3 cache of flash_attn_with_kvcache is such a
+    view, and nothing of the cache past Nk reaches the result.  H_q is a multiple of H_kv; query head h reads K/V head
+    h // (H_q // H_kv).  Descales: float32 (B, H_kv) or (H_kv,) on q's device, q_descale included; None = 1.  They are read on the
+    device only (positive, finite), so a captured call replays with changed values.  softmax_scale defaults to 128 ** -0.5; the
+    causal diagonal is bottom-right aligned (row i sees j <= i + Nk - Nq), and a row without a visible key gives o = 0, lse = -inf.
+    Both products run on the e4m3 matrix instruction; P is rounded to e4m3 on every row, as in FlashAttention-3 (2^-4 relative
+    per probability: it averages out over a row's keys and stands in full on a row that sees a couple).
+    Refused by name before anything runs (NotImplementedError): window_size, softcap, alibi_slopes, sinks, attn_bias, masks,
+    dropout, packed or paged forms, head dims other than 128, 16-bit q / k / v (fa3_attention(fp8=True) and flash_attention_ex take
+    those), out_dtype other than bfloat16 / float16.  Wrong shapes and devices raise RuntimeError, a view that would need a copy
+    ValueError.  Returns o in `layout` and out_dtype, and with return_lse also lse (B, H_q, Nq) float32.  No gradient."""
+    who = "flash_attention_fp8"
+    for name, val in unsupported.items():
+        if name in _FP8_REFUSED:
+            if val is None or val is False or (name == "window_size" and tuple(val) == (-1, -1)) or \
+                    (name in ("softcap", "dropout_p") and val == 0.0):
+                continue
+            raise NotImplementedError(f"{who}: {name} is not supported by the fp8 call")
+        raise TypeError(f"{who}() got an unexpected keyword argument {name!r}")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
+        if t.dtype in (torch.float16, torch.bfloat16, torch.float32):
+            raise NotImplementedError(f"{who}: 16-bit inputs are not supported: {name} is {t.dtype}, torch.float8_e4m3fn expected "
+                                      f"(quantise first, or use fa3_attention(fp8=True) / flash_attention_ex)")
+        if t.dtype != torch.float8_e4m3fn:
+            raise NotImplementedError(f"{who}: {name} of dtype {t.dtype} is not supported (torch.float8_e4m3fn expected)")
+        if t.dim() == 4 and t.shape[3] != 128:
+            raise NotImplementedError(f"{who}: head_dim {t.shape[3]} is not supported (128 only)")
+    if out_dtype not in (torch.bfloat16, torch.float16):
+        raise NotImplementedError(f"{who}: out_dtype {out_dtype} is not supported (torch.bfloat16 or torch.float16)")
+    import flashattention_lab_cuda as ext
+
+    with torch.no_grad():
+        o, lse = ext.fp8_forward(q.detach(), k.detach(), v.detach(), bool(causal), softmax_scale,
+                                 None if q_descale is None else q_descale.detach() if isinstance(q_descale, torch.Tensor) else q_descale,
+                                 None if k_descale is None else k_descale.detach() if isinstance(k_descale, torch.Tensor) else k_descale,
+                                 None if v_descale is None else v_descale.detach() if isinstance(v_descale, torch.Tensor) else v_descale,
+                                 out_dtype, layout)
+    return (o, lse) if return_lse else o

@@ -29,7 +29,8 @@ std::vector<ProfRec> g_prof_recs;
 std::vector<hipEvent_t> g_prof_free;
 hipEvent_t g_prof_open[fa::K_COUNT];
 const char* const kKernelNames[fa::K_COUNT] = {"fwd_f32", "bwd_delta", "bwd_dkdv_f32", "bwd_dq_f32", "fwd_mfma",
-                                               "bwd_mfma", "bwd_dq_cvt", "bwd_dq_mfma", "fp8_quant", "fwd_fp8", "ex_fwd", "ex_bwd", "kv_group_sum"};
+                                               "bwd_mfma", "bwd_dq_cvt", "bwd_dq_mfma", "fp8_quant", "fwd_fp8", "ex_fwd", "ex_bwd", "kv_group_sum",
+                                               "fp8in_vt", "fp8in_fwd"};
 
 hipEvent_t prof_get_event() {
     if (!g_prof_free.empty()) { hipEvent_t e = g_prof_free.back(); g_prof_free.pop_back(); return e; }
@@ -2456,6 +2457,119 @@ int fa_merge_states_backward(const void* o_a, const float* lse_a, const void* o_
     c.dlse_b = merge_t(dlse_b, dlse_b_batch_stride, dlse_b_head_stride, dlse_b_row_stride);
     c.batch = batch; c.heads = heads; c.rows = rows; c.d = d; c.dtype = dtype; c.stream = stream;
     return merge_impl("fa_merge_states_backward", c, true);
+}
+
+// ---- e4m3 q, k, v with per-head descales (FlashAttention-3's fp8 call): see include/fa_mi355x.h
+// One call of fa_fp8_forward: a tensor is a pointer and its (batch, head, token) strides.
+struct Fp8Tensor {
+    const void* p = nullptr;
+    int64_t bs = 0, hs = 0, ts = 0;
+};
+struct Fp8Call {
+    Fp8Tensor q, k, v, o;
+    float* lse = nullptr;
+    const float *q_descale = nullptr, *k_descale = nullptr, *v_descale = nullptr;
+    int64_t qds_bs = 0, kds_bs = 0, vds_bs = 0;
+    int64_t batch = 0, heads_q = 0, heads_kv = 0, nq = 0, nk = 0, d = 0;
+    int dtype = 0, causal = 0;
+    double scale = 0.0;
+    void* workspace = nullptr;
+    size_t workspace_bytes = 0;
+    void* stream = nullptr;
+};
+
+static int fp8_forward_impl(const char* who, const Fp8Call& c) {
+    // (1) null pointers
+    if (!c.q.p || !c.k.p || !c.v.p || !c.o.p || !c.lse) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    // (2) dims
+    if (c.batch <= 0 || c.heads_q <= 0 || c.heads_kv <= 0 || c.nq <= 0 || c.nk <= 0 || c.d <= 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch, heads_q, heads_kv, seqlen_q, seqlen_k and d must be > 0 (got %lld, %lld, %lld, %lld, %lld, %lld)",
+                    who, (long long)c.batch, (long long)c.heads_q, (long long)c.heads_kv, (long long)c.nq, (long long)c.nk, (long long)c.d);
+    // (3) the head dim
+    if (c.d != 128) return fail(FA_ERR_UNSUPPORTED, "%s: head_dim %lld is not supported (128 only)", who, (long long)c.d);
+    // (4) the heads ratio
+    if (c.heads_q % c.heads_kv != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads_q=%lld must be a multiple of heads_kv=%lld", who, (long long)c.heads_q, (long long)c.heads_kv);
+    // (5) the output dtype, the scale, the descale strides
+    if (c.dtype != FA_DTYPE_F16 && c.dtype != FA_DTYPE_BF16)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: dtype (of o) must be f16 or bf16 (got code %d)", who, c.dtype);
+    if (!(c.scale == c.scale) || !scale_ok(c.scale))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale must be finite and > 0", who);
+    const struct { const char* name; const float* p; int64_t bs; } ds[3] = {
+        {"q_descale", c.q_descale, c.qds_bs}, {"k_descale", c.k_descale, c.kds_bs}, {"v_descale", c.v_descale, c.vds_bs}};
+    for (const auto& s : ds) {
+        if (!s.p && s.bs != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: %s_batch_stride must be 0 without %s", who, s.name, s.name);
+        if (s.bs < 0 || (s.bs != 0 && s.bs < c.heads_kv) || s.bs >= ((int64_t)1 << 31) / c.batch)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: %s_batch_stride=%lld must be 0 or >= heads_kv=%lld", who, s.name, (long long)s.bs,
+                        (long long)c.heads_kv);
+        if ((uintptr_t)s.p % 4 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: %s must be 4-byte aligned", who, s.name);
+    }
+    // (6) alignment and strides: 16-byte units (q, k, v in bytes, o in 16-bit elements), rows that do not overlap
+    if (!aligned16({c.q.p, c.k.p, c.v.p, c.o.p})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: q, k, v and o must be 16-byte aligned", who);
+    if ((uintptr_t)c.lse % 4 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: lse must be 4-byte aligned", who);
+    const struct { const char* name; const Fp8Tensor* t; int64_t unit, heads, rows; } ts[4] = {
+        {"q", &c.q, 16, c.heads_q, c.nq}, {"k", &c.k, 16, c.heads_kv, c.nk}, {"v", &c.v, 16, c.heads_kv, c.nk}, {"o", &c.o, 8, c.heads_q, c.nq}};
+    const int64_t kMaxStride = (int64_t)1 << 44;
+    for (const auto& t : ts) {
+        const int64_t bs = c.batch > 1 ? t.t->bs : 0, hs = t.heads > 1 ? t.t->hs : 0, tk = t.rows > 1 ? t.t->ts : 128;
+        if (bs % t.unit != 0 || hs % t.unit != 0 || tk % t.unit != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (%lld, %lld, %lld) must be multiples of %lld elements (16 bytes)", who,
+                        t.name, (long long)t.t->bs, (long long)t.t->hs, (long long)t.t->ts, (long long)t.unit);
+        if (bs < 0 || hs < 0 || tk < 128 || bs > kMaxStride || hs > kMaxStride || tk > kMaxStride)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (%lld, %lld, %lld) must be >= 0, the token stride >= 128", who, t.name,
+                        (long long)t.t->bs, (long long)t.t->hs, (long long)t.t->ts);
+    }
+    // (7) the span limit: q and k are read through 32-bit buffer descriptors and offsets per (batch, head) unit
+    const int64_t kSpan = ((int64_t)1 << 31) - 1;
+    const int64_t q_span = (c.nq + 255) / 256 * 256 * (c.nq > 1 ? c.q.ts : 128), k_span = (c.nk + 255) / 256 * 256 * (c.nk > 1 ? c.k.ts : 128);
+    if (q_span > kSpan || k_span > kSpan)
+        return fail(FA_ERR_UNSUPPORTED, "%s: span limit: round_up(rows, 256) * token stride of %s is %lld bytes, at or above 2^31", who,
+                    q_span > kSpan ? "q" : "k", (long long)(q_span > kSpan ? q_span : k_span));
+    if (c.batch * c.heads_q >= ((int64_t)1 << 31) / ((c.nq + 255) / 256) || c.batch * c.heads_kv >= ((int64_t)1 << 31) / ((c.nk + 63) / 64))
+        return fail(FA_ERR_UNSUPPORTED, "%s: span limit: batch * heads * tiles too large for one launch", who);
+    // (8) the workspace
+    const size_t need = fa::fp8in_workspace_bytes(c.batch * c.heads_kv, c.nk);
+    if (!c.workspace || c.workspace_bytes < need)
+        return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes is too small (need %zu: fa_fp8_forward_workspace_bytes)", who,
+                    c.workspace ? c.workspace_bytes : (size_t)0, need);
+    if ((uintptr_t)c.workspace % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
+
+    fa::Fp8InArgs a;
+    a.q = c.q.p; a.k = c.k.p; a.v = c.v.p; a.o = const_cast<void*>(c.o.p); a.lse = c.lse;
+    a.q_descale = c.q_descale; a.k_descale = c.k_descale; a.v_descale = c.v_descale;
+    a.qds_bs = c.qds_bs; a.kds_bs = c.kds_bs; a.vds_bs = c.vds_bs;
+    a.batch = c.batch; a.heads_q = c.heads_q; a.heads_kv = c.heads_kv; a.nq = c.nq; a.nk = c.nk; a.dtype = c.dtype;
+    a.q_bs = c.batch > 1 ? c.q.bs : 0; a.q_hs = c.heads_q > 1 ? c.q.hs : 0; a.q_ts = c.nq > 1 ? c.q.ts : 128;
+    a.k_bs = c.batch > 1 ? c.k.bs : 0; a.k_hs = c.heads_kv > 1 ? c.k.hs : 0; a.k_ts = c.nk > 1 ? c.k.ts : 128;
+    a.v_bs = c.batch > 1 ? c.v.bs : 0; a.v_hs = c.heads_kv > 1 ? c.v.hs : 0; a.v_ts = c.nk > 1 ? c.v.ts : 128;
+    a.o_bs = c.batch > 1 ? c.o.bs : 0; a.o_hs = c.heads_q > 1 ? c.o.hs : 0; a.o_ts = c.nq > 1 ? c.o.ts : 128;
+    a.causal = c.causal != 0; a.scale = (float)c.scale; a.workspace = c.workspace;
+    return launched(who, fa::launch_fp8_inputs(a, reinterpret_cast<hipStream_t>(c.stream)));
+}
+
+size_t fa_fp8_forward_workspace_bytes(int64_t batch, int64_t heads_kv, int64_t seqlen_k, int64_t d) {
+    if (batch <= 0 || heads_kv <= 0 || seqlen_k <= 0 || d != 128) return 0;
+    return fa::fp8in_workspace_bytes(batch * heads_kv, seqlen_k);
+}
+
+int fa_fp8_forward(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
+                   const float* v_descale, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_k, int64_t d,
+                   int dtype, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_token_stride, int64_t k_batch_stride,
+                   int64_t k_head_stride, int64_t k_token_stride, int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride,
+                   int64_t o_batch_stride, int64_t o_head_stride, int64_t o_token_stride, int64_t q_descale_batch_stride,
+                   int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace,
+                   size_t workspace_bytes, void* stream) {
+    Fp8Call c;
+    c.q.p = q; c.q.bs = q_batch_stride; c.q.hs = q_head_stride; c.q.ts = q_token_stride;
+    c.k.p = k; c.k.bs = k_batch_stride; c.k.hs = k_head_stride; c.k.ts = k_token_stride;
+    c.v.p = v; c.v.bs = v_batch_stride; c.v.hs = v_head_stride; c.v.ts = v_token_stride;
+    c.o.p = o; c.o.bs = o_batch_stride; c.o.hs = o_head_stride; c.o.ts = o_token_stride;
+    c.lse = lse; c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
+    c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
+    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.nq = seqlen_q; c.nk = seqlen_k; c.d = d;
+    c.dtype = dtype; c.causal = causal; c.scale = softmax_scale;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    return fp8_forward_impl("fa_fp8_forward", c);
 }
 
 size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {

@@ -1,0 +1,293 @@
+// FlashAttention-3's fp8 call for gfx950: q, k, v arrive ALREADY in OCP e4m3 (float8_e4m3fn) with one float32 descale per (batch,
+// K/V head) for each of them, and both products run on v_mfma_scale_f32_32x32x64_f8f6f4 with unit hardware scales.  Forward only,
+// head_dim 128, o in f16 / bf16, lse float32.  (include/fa_mi355x.h: fa_fp8_forward)
+//
+//     o = softmax(softmax_scale * q_descale * k_descale * q8 k8^T [causal, bottom-right aligned]) (v8 * v_descale)
+//
+// Two launches:
+//   fp8in_vt_kernel     V -> V^T in the image fwd_fp8v_kernel (fa_fwd_fp8.hip) reads: [K/V unit][128-key tile][d row][128 key bytes],
+//                       every 64-key group in fp8_quant_v_kernel's key permutation (byte 32 hi + 16 h + jj of a group is key
+//                       32 hi + 4 h + (jj & 3) + 8 (jj >> 2)), zeros for keys >= Nk including the second half of an odd last tile.  A
+//                       byte permutation through LDS: no arithmetic, no scales.  It reads v at the caller's strides and writes the
+//                       caller's workspace.
+//   fwd_fp8in_kernel    fwd_fp8v_kernel's structure (512 threads, 256 query rows a workgroup, 128-key tiles, double-buffered LDS-DMA
+//                       of K8 and V8^T) with: separate nq / nk and the causal diagonal shifted by nk - nq in the tile bound, the
+//                       per-wave bound and the mask; the K/V unit from the GQA rule (query head h reads K/V head h / (H_q / H_kv));
+//                       ONE score factor per workgroup, f = softmax_scale * log2(e) * q_descale * k_descale, instead of per-block
+//                       scale loads; v_descale applied once in the epilogue together with 1 / l; a guard for rows without a visible
+//                       key (o = 0, lse = -inf, where 1 / l would give NaN); q, k and o at the caller's strides.
+//
+// Arithmetic, in the order tests/fp8_inputs_ref.py (baseline) transcribes it:
+//   * raw scores: two 64-term instructions over the 128 head-dim bytes, f32 accumulation;
+//   * row maxima on the raw products, times f once (f > 0); p = exp2(fma(s, f, -m)) with the lazy rescale (the running max moves
+//     only on a tile where some row of the wave's 32 grew by more than 8 in log2 units);
+//   * P rounded to e4m3 (RNE) on EVERY row; l and lse from the unrounded p;
+//   * o = RNE(acc * (v_descale * (1 / l))), lse = (m + log2 l) * ln 2.
+// There is NO 16-bit-P route for short rows.  fa3_forward(fp8 = 1) keeps one (fa_fwd_fp8.hip, launch_fp8_t) because its backward takes
+// delta from o; this call has no backward, and FlashAttention-3 rounds P everywhere.  The cost: 2^-4 relative per probability, which
+// averages out over a row's keys but stands in full on a row that sees a couple of keys (up to 6 % of |v| on a row that sees two).
+//
+// Bytes outside [0, Nk) of a view never reach a result: K rows >= Nk are cut off by the buffer descriptor's range check (they
+// arrive as zeros), their scores are masked to -inf, and the transposer writes zeros for them; likewise q rows >= Nq.  So the
+// [:, :Nk] prefix of a cache with a larger capacity can be passed as it is, whatever the rest holds (e4m3 NaN bytes included).
+// NaN codes inside the view propagate.
+//
+// Span limit: q and k are addressed through 32-bit buffer descriptors and 32-bit offsets per (batch, head) unit, so
+// round_up(rows, 256) * token_stride_bytes must stay below 2^31 for both (fa_capi.hip checks it; batch and head offsets are 64-bit).
+#include "fa_common.h"
+#include "fa_kernels.h"
+
+namespace fa {
+
+// one workgroup = one 64-key block of one K/V unit (blockIdx.x = unit * nb + block: gridDim.y stops at 65535)
+__global__ __launch_bounds__(256) void fp8in_vt_kernel(const uint8_t* __restrict__ v, uint8_t* __restrict__ v8t, int nk, int nb,
+                                                       int ntile, int hkv, long long v_bs, long long v_hs, long long v_ts) {
+    constexpr int D = 128, CPR = D / 16, PER = (64 * CPR) / 256;   // 16-byte chunks per row / per thread
+    __shared__ __attribute__((aligned(16))) uint8_t tr[D * 64];   // [d row][permuted key position]
+    const int unit = blockIdx.x / nb, blk = blockIdx.x - unit * nb, row0 = blk * 64;
+    const int b = unit / hkv, hk = unit - b * hkv;
+    const uint8_t* src = v + (size_t)b * v_bs + (size_t)hk * v_hs;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const int c = threadIdx.x + 256 * i, key = c / CPR, ch = c % CPR;   // key within the 64-key block
+        u32x4 x = u32x4{0u, 0u, 0u, 0u};
+        if (row0 + key < nk) x = *reinterpret_cast<const u32x4*>(src + (size_t)(row0 + key) * v_ts + 16 * ch);
+        const int wlo = key & 31, pos = 32 * (key >> 5) + 16 * ((wlo >> 2) & 1) + (wlo & 3) + 4 * (wlo >> 3);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) tr[(16 * ch + j) * 64 + pos] = (uint8_t)((x[j >> 2] >> (8 * (j & 3))) & 0xff);
+    }
+    __syncthreads();
+    // d row r of the block: 64 bytes at [tile blk / 2][r][64 (blk & 1) ...]; a thread stores half a row
+    const int r = threadIdx.x >> 1, half = threadIdx.x & 1;
+    uint8_t* dst = v8t + (((size_t)unit * ntile + (blk >> 1)) * D + r) * 128 + 64 * (blk & 1) + 32 * half;
+    const u32x4* s4 = reinterpret_cast<const u32x4*>(tr + r * 64 + 32 * half);
+    reinterpret_cast<u32x4*>(dst)[0] = s4[0];
+    reinterpret_cast<u32x4*>(dst)[1] = s4[1];
+    // an odd block count leaves the second half of the last tile unwritten by any block: zero it (those keys lie past Nk)
+    if ((nb & 1) && blk == nb - 1) {
+        reinterpret_cast<u32x4*>(dst + 64)[0] = u32x4{0u, 0u, 0u, 0u};
+        reinterpret_cast<u32x4*>(dst + 64)[1] = u32x4{0u, 0u, 0u, 0u};
+    }
+}
+
+struct Fp8InKernelArgs {
+    const uint8_t *q, *k, *v8t;
+    uint16_t* o;
+    float* lse;
+    const float *qds, *kds, *vds;          // (B, H_kv) descales at their batch strides; null: 1
+    int qds_bs, kds_bs, vds_bs;
+    int nq, nk, hq, hkv, group, nqt, ntile;
+    int q_ts, k_ts, o_ts;                  // token strides: q and k in bytes, o in elements
+    long long q_bs, q_hs, k_bs, k_hs, o_bs, o_hs;
+    float c_log2;                          // float(softmax_scale) * log2(e)
+};
+
+template <typename Tag, bool CAUSAL>
+__global__ __launch_bounds__(512, 2) void fwd_fp8in_kernel(const Fp8InKernelArgs a) {
+    constexpr int D = 128, BM = 256, BN = 128, KB = 4, NM = D / 32, NDV = D / 32;
+    constexpr int TILE = BN * D;                         // bytes of a K tile and of a V^T tile alike
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // [2 buffers][K8 tile | V8^T tile]
+    typedef int i32x8_t __attribute__((ext_vector_type(8)));
+
+    const int nq = a.nq, nk = a.nk;
+    const int L = xcd_remap(blockIdx.x, gridDim.x);
+    const int bh = L / a.nqt;                            // query unit b * H_q + head
+    int qt = L - bh * a.nqt;
+    if (CAUSAL) qt = a.nqt - 1 - qt;
+    const int b = bh / a.hq, hd = bh - b * a.hq, hk = hd / a.group;
+    const int ukv = b * a.hkv + hk;                      // the GQA rule: query head hd reads K/V head hd / (H_q / H_kv)
+    const int q0 = qt * BM;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const int qrow = q0 + 32 * w + r;
+    const int shift = nk - nq;                           // row i sees key j <= i + shift
+
+    // q rows >= nq and k rows >= nk lie outside the descriptors: they read as zeros, whatever the memory behind them holds
+    const buf_rsrc_t q_rs = make_rsrc(a.q + (size_t)b * a.q_bs + (size_t)hd * a.q_hs, (unsigned)(nq - 1) * (unsigned)a.q_ts + D);
+    u32x4 qf[NM];
+#pragma unroll
+    for (int m = 0; m < NM; ++m) qf[m] = __builtin_amdgcn_raw_buffer_load_b128(q_rs, qrow * a.q_ts + 32 * m + 16 * h, 0, 0);
+    const float qd = a.qds ? a.qds[(size_t)b * a.qds_bs + hk] : 1.f;
+    const float kd = a.kds ? a.kds[(size_t)b * a.kds_bs + hk] : 1.f;
+    const float vd = a.vds ? a.vds[(size_t)b * a.vds_bs + hk] : 1.f;
+    const float f = (a.c_log2 * qd) * kd;                // the one score factor of this workgroup, > 0
+
+    const int kend = CAUSAL ? max(0, min(nk, q0 + BM + shift)) : nk;
+    const int ntiles = (kend + BN - 1) / BN;             // 0: no row of this tile sees a key
+    const rsrc_s_t k_rs = make_rsrc_s(a.k + (size_t)b * a.k_bs + (size_t)hk * a.k_hs, (unsigned)(nk - 1) * (unsigned)a.k_ts + D);
+    const rsrc_s_t v_rs = make_rsrc_s(a.v8t + (size_t)ukv * a.ntile * TILE, (unsigned)a.ntile * TILE);
+    const int kstride = a.k_ts >> 1;                     // the STRIDED helpers count 2-byte elements
+    const int voff_k = dma_lane_voff<64, true>(lane, w, 64, kstride);   // 128-byte rows: the geometry of a 16-bit d = 64 tile
+    const int voff_v = dma_lane_voff<64>(lane, w);
+    auto stage = [&](int buf, int t) {
+        char* b_ = smem + buf * 2 * TILE;
+        dma_stage_tile<64, BN, 8, true>(k_rs, b_, t * BN, voff_k, w, 64, 0, kstride);
+        dma_stage_tile<64, BN, 8>(v_rs, b_ + TILE, t * BN, voff_v, w);   // V^T tile t = rows 128 t .. of the [tile][d row] matrix
+    };
+
+    f32x16 oacc[NDV];
+#pragma unroll
+    for (int t = 0; t < NDV; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) oacc[t][i] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;                // running max in log2 units of the scaled score
+
+    if (ntiles > 0) {
+        stage(0, 0);
+        dma_wait_all();
+        __syncthreads();
+    }
+    const int last_w = q0 + 32 * w + 31 + shift;         // the last key the wave's last row sees under the mask
+    const int ntiles_w = CAUSAL ? (last_w < 0 ? 0 : min(ntiles, last_w / BN + 1)) : ntiles;
+
+    for (int t = 0; t < ntiles_w; ++t) {
+        const int k0 = t * BN, cur = t & 1;
+        if (t + 1 < ntiles) stage(cur ^ 1, t + 1);
+        const char* Kt = smem + cur * 2 * TILE;
+        const char* Vt = Kt + TILE;
+        f32x16 sacc[KB];
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) sacc[kb][i] = 0.f;
+#pragma unroll
+            for (int M = 0; M < NM / 2; ++M) {
+                const u32x4 a0 = *reinterpret_cast<const u32x4*>(Kt + TileSwz<64>::off(32 * kb + r, 4 * M + h));
+                const u32x4 a1 = *reinterpret_cast<const u32x4*>(Kt + TileSwz<64>::off(32 * kb + r, 4 * M + 2 + h));
+                const i32x8_t ka = {(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], (int)a1[0], (int)a1[1], (int)a1[2], (int)a1[3]};
+                const u32x4 b0_ = qf[2 * M], b1_ = qf[2 * M + 1];
+                const i32x8_t qb = {(int)b0_[0], (int)b0_[1], (int)b0_[2], (int)b0_[3], (int)b1_[0], (int)b1_[1], (int)b1_[2], (int)b1_[3]};
+                sacc[kb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ka, qb, sacc[kb], 0, 0, 0, 127, 0, 127);
+            }
+        }
+        // mask and row maximum on the RAW products; f > 0 is applied to the maximum once and to every element inside the exp2
+        // argument's fma
+        const bool need_mask = (CAUSAL && (k0 + BN - 1 > q0 + 32 * w + shift)) || (k0 + BN > nk);
+        const int lim = CAUSAL ? min(qrow + shift, nk - 1) : nk - 1;   // (negative: the row sees no key)
+        float mx = -INFINITY;
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) {
+            if (need_mask) {
+                const int thr = lim - (k0 + 32 * kb + 4 * h);
+#pragma unroll
+                for (int i = 0; i < 16; ++i)
+                    if ((i & 3) + 8 * (i >> 2) > thr) sacc[kb][i] = -INFINITY;
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) mx = fmaxf(mx, sacc[kb][i]);
+        }
+        mx = mx * f;
+        mx = fmaxf(mx, wave_half_swap(mx));
+        const float m_new = fmaxf(m_run, mx);
+        float m_use;
+        if (__any(m_new - m_run > 8.0f) != 0) {   // lazy rescale (fa_fwd_mfma.hip); a row's first visible key: inf > 8
+            m_use = m_new;
+            const float alpha = __builtin_amdgcn_exp2f(m_run - ((m_new == -INFINITY) ? 0.f : m_new));
+            m_run = m_new;
+            l_run *= alpha;
+#pragma unroll
+            for (int t2 = 0; t2 < NDV; ++t2)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) oacc[t2][i] *= alpha;
+        } else {
+            m_use = m_run;
+        }
+        if (m_use == -INFINITY) m_use = 0.f;      // a row without a visible key so far: p = exp2(-inf) = 0, not exp2(-inf + inf)
+        float rs = 0.f;
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            i32x8_t pb;
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {
+                const int kb = 2 * g + kk;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float p = __builtin_amdgcn_exp2f(fmaf(sacc[kb][i], f, -m_use));   // (-inf stays -inf: f > 0)
+                    sacc[kb][i] = p;
+                    rs += p;
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    int wd = 0;
+                    wd = __builtin_amdgcn_cvt_pk_fp8_f32(sacc[kb][4 * j + 0], sacc[kb][4 * j + 1], wd, false);
+                    wd = __builtin_amdgcn_cvt_pk_fp8_f32(sacc[kb][4 * j + 2], sacc[kb][4 * j + 3], wd, true);
+                    pb[4 * kk + j] = wd;
+                }
+            }
+#pragma unroll
+            for (int dvb = 0; dvb < NDV; ++dvb) {
+                const u32x4 a0 = *reinterpret_cast<const u32x4*>(Vt + TileSwz<64>::off(32 * dvb + r, 4 * g + h));
+                const u32x4 a1 = *reinterpret_cast<const u32x4*>(Vt + TileSwz<64>::off(32 * dvb + r, 4 * g + 2 + h));
+                const i32x8_t va = {(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], (int)a1[0], (int)a1[1], (int)a1[2], (int)a1[3]};
+                oacc[dvb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(va, pb, oacc[dvb], 0, 0, 0, 127, 0, 127);
+            }
+        }
+        l_run += rs;
+        dma_wait_all();
+        __syncthreads();
+    }
+    for (int t = ntiles_w; t < ntiles; ++t) {
+        if (t + 1 < ntiles) stage((t & 1) ^ 1, t + 1);
+        dma_wait_all();
+        __syncthreads();
+    }
+
+    // every wave is past the last barrier (the tile loops end with one): the K / V buffers are dead and each wave turns its
+    // row-on-the-lane tile into whole-row stores through 8 KiB of them (fa_fwd_mfma.hip's epilogue)
+    const float l_tot = l_run + wave_half_swap(l_run);
+    const bool dead = l_tot == 0.f;                      // no visible key: o = 0, lse = -inf (a NaN l is not dead: it propagates)
+    const float inv = vd * (1.f / l_tot);                // v_descale once, with 1 / l
+    u32x2 vals[NDV * 4];
+#pragma unroll
+    for (int dvb = 0; dvb < NDV; ++dvb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            float y[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) y[j] = dead ? 0.f : oacc[dvb][4 * g + j] * inv;
+            vals[4 * dvb + g][0] = pack2_rn<Tag>(y[0], y[1]);
+            vals[4 * dvb + g][1] = pack2_rn<Tag>(y[2], y[3]);
+        }
+    store_rows_via_lds<D, true>(smem + w * 32 * D * 2, vals, a.o + (size_t)b * a.o_bs + (size_t)hd * a.o_hs, q0 + 32 * w, nq, lane, D, -1,
+                                a.o_ts);
+    if (qrow < nq && h == 0) a.lse[(size_t)bh * nq + qrow] = dead ? -INFINITY : (m_run + log2f(l_tot)) * 0.6931471805599453f;
+}
+
+size_t fp8in_workspace_bytes(int64_t units_kv, int64_t nk) {
+    return (size_t)units_kv * (size_t)((nk + 127) / 128) * 128 * 128 + 256;   // V^T tiles and a pad
+}
+
+hipError_t launch_fp8_inputs(const Fp8InArgs& c, hipStream_t st) {
+    const int nb = (int)((c.nk + 63) / 64), ntile = (int)((c.nk + 127) / 128), nqt = (int)((c.nq + 255) / 256);
+    const int64_t units_kv = c.batch * c.heads_kv;
+    {
+        ProfScope ps(K_FP8IN_VT, st);
+        hipLaunchKernelGGL(fp8in_vt_kernel, dim3((unsigned)(units_kv * nb)), dim3(256), 0, st, (const uint8_t*)c.v, (uint8_t*)c.workspace,
+                           (int)c.nk, nb, ntile, (int)c.heads_kv, (long long)c.v_bs, (long long)c.v_hs, (long long)c.v_ts);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    Fp8InKernelArgs a;
+    a.q = (const uint8_t*)c.q; a.k = (const uint8_t*)c.k; a.v8t = (const uint8_t*)c.workspace;
+    a.o = (uint16_t*)c.o; a.lse = c.lse;
+    a.qds = c.q_descale; a.kds = c.k_descale; a.vds = c.v_descale;
+    a.qds_bs = (int)c.qds_bs; a.kds_bs = (int)c.kds_bs; a.vds_bs = (int)c.vds_bs;
+    a.nq = (int)c.nq; a.nk = (int)c.nk; a.hq = (int)c.heads_q; a.hkv = (int)c.heads_kv; a.group = (int)(c.heads_q / c.heads_kv);
+    a.nqt = nqt; a.ntile = ntile;
+    a.q_ts = (int)c.q_ts; a.k_ts = (int)c.k_ts; a.o_ts = (int)c.o_ts;
+    a.q_bs = c.q_bs; a.q_hs = c.q_hs; a.k_bs = c.k_bs; a.k_hs = c.k_hs; a.o_bs = c.o_bs; a.o_hs = c.o_hs;
+    a.c_log2 = c.scale * 1.4426950408889634f;
+    const size_t smem = 2 * 2 * 128 * 128;
+    const unsigned grid = (unsigned)(c.batch * c.heads_q * nqt);
+    ProfScope ps(K_FP8IN_FWD, st);
+    auto launch = [&](auto kern) -> hipError_t {
+        hipError_t e2 = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
+        if (e2 != hipSuccess) return e2;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, st, a);
+        return hipGetLastError();
+    };
+    if (c.dtype == 2) return c.causal ? launch(fwd_fp8in_kernel<bf16_tag, true>) : launch(fwd_fp8in_kernel<bf16_tag, false>);
+    return c.causal ? launch(fwd_fp8in_kernel<f16_tag, true>) : launch(fwd_fp8in_kernel<f16_tag, false>);
+}
+
+}  // namespace fa

@@ -42,7 +42,7 @@ struct BwdArgs {
 // Optional per-kernel timing with HIP events recorded on the launch stream (used by bench.py for the
 // roofline figure; off by default, costs nothing when off).
 enum KernelId { K_FWD_F32 = 0, K_BWD_DELTA, K_BWD_DKDV_F32, K_BWD_DQ_F32, K_FWD_MFMA, K_BWD_MFMA, K_BWD_DQ_CVT, K_BWD_DQ_MFMA,
-                K_FP8_QUANT, K_FWD_FP8, K_EX_FWD, K_EX_BWD, K_KV_GROUP_SUM, K_COUNT };
+                K_FP8_QUANT, K_FWD_FP8, K_EX_FWD, K_EX_BWD, K_KV_GROUP_SUM, K_FP8IN_VT, K_FP8IN_FWD, K_COUNT };
 void prof_begin(int id, hipStream_t st);
 void prof_end(int id, hipStream_t st);
 struct ProfScope {
@@ -367,5 +367,23 @@ hipError_t launch_kv_group_sum(const void* pk, const void* pv, void* dk, void* d
 
 // the same for one tensor (dK and dV of different widths)
 hipError_t launch_kv_group_sum_one(const void* src, void* dst, int64_t bh_kv, int64_t g, int64_t nk, int64_t d, int dtype, hipStream_t st);
+
+// e4m3 q, k, v with per-(batch, K/V head) descales (fa_fp8_inputs.hip; fa_fp8_forward): a V^T byte permutation into the workspace,
+// then the attention kernel.  q, k, v strides in bytes (= e4m3 elements), o strides in elements of its 16-bit dtype; head_dim 128.
+struct Fp8InArgs {
+    const void *q = nullptr, *k = nullptr, *v = nullptr;
+    void* o = nullptr;
+    float* lse = nullptr;                                   // (batch, heads_q, nq) contiguous
+    const float *q_descale = nullptr, *k_descale = nullptr, *v_descale = nullptr;   // (batch, heads_kv) device floats; null: 1
+    int64_t qds_bs = 0, kds_bs = 0, vds_bs = 0;             // their batch strides (0: one row for every batch)
+    int64_t batch = 0, heads_q = 0, heads_kv = 0, nq = 0, nk = 0;
+    int dtype = 0;                                          // of o: FA_DTYPE_F16 / FA_DTYPE_BF16
+    int64_t q_bs = 0, q_hs = 0, q_ts = 0, k_bs = 0, k_hs = 0, k_ts = 0, v_bs = 0, v_hs = 0, v_ts = 0, o_bs = 0, o_hs = 0, o_ts = 0;
+    int causal = 0;
+    float scale = 0.f;
+    void* workspace = nullptr;                              // fp8in_workspace_bytes(batch * heads_kv, nk)
+};
+size_t fp8in_workspace_bytes(int64_t units_kv, int64_t nk);
+hipError_t launch_fp8_inputs(const Fp8InArgs& a, hipStream_t st);
 
 }  // namespace fa

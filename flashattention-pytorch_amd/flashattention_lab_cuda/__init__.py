@@ -55,6 +55,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_mla_fp8_forward", "fa_mla_fp8_workspace_bytes", "fa_mla_fp8_pack",
     "fa_ex_forward_vdim", "fa_ex_backward_vdim", "fa_ex_forward_varlen_vdim", "fa_ex_backward_varlen_vdim",
     "fa_ex_forward_bias", "fa_ex_backward_bias", "fa_ex_backward_workspace_bytes_bias",
+    "fa_fp8_forward", "fa_fp8_forward_workspace_bytes",
 )
 
 
@@ -192,6 +193,11 @@ _sig("fa_mla_fp8_workspace_bytes", _fields("i:batch,heads_q,heads_kv,seqlen_q,ca
 _sig("fa_mla_fp8_pack", _fields(
     "p:latent_new,rope_new,kv_cache,cache_seqlens,block_table i:batch,seqlen_new,latent_batch_stride,latent_token_stride,"
     "rope_batch_stride,rope_token_stride") + _F8POOL + _F8PAGES + _fields("c:scale_pow2") + _STREAM)
+_sig("fa_fp8_forward", _fields("p:q,k,v,o,lse,q_descale,k_descale,v_descale i:batch,heads_q,heads_kv,seqlen_q,seqlen_k,d c:dtype "
+                               "i:q_batch_stride,q_head_stride,q_token_stride,k_batch_stride,k_head_stride,k_token_stride,v_batch_stride,"
+                               "v_head_stride,v_token_stride,o_batch_stride,o_head_stride,o_token_stride,q_descale_batch_stride,"
+                               "k_descale_batch_stride,v_descale_batch_stride c:causal d:softmax_scale") + _WS)
+_sig("fa_fp8_forward_workspace_bytes", _fields("i:batch,heads_kv,seqlen_k,d"), _SIZE)
 _KVWSV = _fields("i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,d,num_splits c:with_sinks")
 _sig("fa_ex_kvcache_workspace_bytes_varlen", _KVWSV, _SIZE)
 _sig("fa_ex_kvcache_workspace_bytes_qv", _KVWSV + _fields("i:d_v"), _SIZE)
@@ -243,6 +249,7 @@ _family("fa_merge_states_backward", [])
 _family("fa_mla_sparse_forward", [])
 _family("fa_mla_fp8_forward", [])
 _family("fa_mla_fp8_pack", [])
+_family("fa_fp8_forward", [])
 _family("fa_ex_forward_kvcache_qv", ["fa_ex_forward_kvcache" + _suffix for _suffix in ("", "_paged", "_rotary", "_fp8", "_sink", "_varlen")])
 
 
@@ -1810,3 +1817,75 @@ def merge_states_backward(o_a, lse_a, o_b, lse_b, do_, dlse=None, layout="bhnd")
             *s_dob, *s_dla, *s_dlb, _stream_ptr(o_a.device)))
     return do_a, do_b, dlse_a, dlse_b
 
+
+
+# ---- e4m3 q, k, v with per-head descales (include/fa_mi355x.h: fa_fp8_forward) ----
+
+FP8_LAYOUTS = ("bhnd", "bnhd")
+
+
+def _fp8_view(who, name, t, layout):
+    """(batch, heads, rows, (batch, head, token) strides in elements) of a 4-D (.., 128) tensor under `layout`; a stride of an extent-1
+    dim is handed on as 0 (token: 128), so that the C layer's rules see only the strides that address"""
+    if t.dim() != 4 or t.shape[3] != 128:
+        if t.dim() == 4:
+            raise NotImplementedError(f"{who}: head_dim {t.shape[3]} is not supported (128 only); got {name} of shape {tuple(t.shape)}")
+        raise RuntimeError(f"{who}: {name} must be 4-D ({'B, H, N, 128' if layout == 'bhnd' else 'B, N, H, 128'}), got {tuple(t.shape)}")
+    if t.stride(3) != 1:
+        raise ValueError(f"{who}: {name} must have a contiguous last dim (a view that would need a copy)")
+    b, h, n = (t.shape[0], t.shape[1], t.shape[2]) if layout == "bhnd" else (t.shape[0], t.shape[2], t.shape[1])
+    hs, ts = (t.stride(1), t.stride(2)) if layout == "bhnd" else (t.stride(2), t.stride(1))
+    st = (t.stride(0) if b > 1 else 0, hs if h > 1 else 0, ts if n > 1 else 128)
+    unit = 16 // t.element_size()
+    if t.numel() and (t.data_ptr() % 16 != 0 or any(x % unit != 0 or x < 0 for x in st)):
+        raise ValueError(f"{who}: {name} is a view the kernel cannot address: a 16-byte aligned start and non-negative strides that are "
+                         f"multiples of 16 bytes are needed (strides {st})")
+    return b, h, n, st
+
+
+def fp8_forward(q, k, v, causal, softmax_scale, q_descale=None, k_descale=None, v_descale=None, out_dtype=torch.bfloat16, layout="bhnd"):
+    """(o, lse) of FlashAttention-3's fp8 call (fa_fp8_forward): q (B, H_q, Nq, 128), k and v (B, H_kv, Nk, 128) in torch.float8_e4m3fn
+    (layout "bnhd": (B, N, H, 128)), used at their own strides, never copied; q_descale, k_descale, v_descale float32 (B, H_kv) or
+    (H_kv,) on q's device, None = 1.  o comes back contiguous in `layout` and out_dtype (bfloat16 / float16), lse float32
+    (B, H_q, Nq).  The V^T workspace is the shim's persistent one.  Nothing is recorded by autograd."""
+    who = "fp8_forward"
+    if layout not in FP8_LAYOUTS:
+        raise ValueError(f"{who}: layout must be one of {FP8_LAYOUTS}, got {layout!r}")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float8_e4m3fn:
+            dt = t.dtype if isinstance(t, torch.Tensor) else type(t).__name__
+            raise NotImplementedError(f"{who}: {name} of dtype {dt} is not supported (torch.float8_e4m3fn expected; 16-bit tensors go to "
+                                      f"fa3_forward(fp8=1) or flash_attention_ex)")
+    if out_dtype not in (torch.bfloat16, torch.float16):
+        raise NotImplementedError(f"{who}: out_dtype {out_dtype} is not supported (torch.bfloat16 or torch.float16)")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: tensors must be on the GPU (HIP device); there is no CPU path")
+        if t.device != q.device:
+            raise RuntimeError(f"{who}: q, k, v must be on one device ({name} is on {t.device}, q on {q.device})")
+    b, hq, nq, sq = _fp8_view(who, "q", q, layout)
+    bk, hkv, nk, sk = _fp8_view(who, "k", k, layout)
+    bv, hv, nv, sv = _fp8_view(who, "v", v, layout)
+    if (bk, bv) != (b, b) or (hv, nv) != (hkv, nk):
+        raise RuntimeError(f"{who}: k and v must share (B, H_kv, Nk) and q's batch; got q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}")
+    if min(b, hq, hkv, nq, nk) < 1:
+        raise RuntimeError(f"{who}: empty tensors are not supported (q {tuple(q.shape)}, k {tuple(k.shape)})")
+    if hq % hkv != 0:
+        raise RuntimeError(f"{who}: H_q = {hq} must be a multiple of H_kv = {hkv}")
+    scale = 128 ** -0.5 if softmax_scale is None else float(softmax_scale)
+    if not (math.isfinite(scale) and scale > 0.0):
+        raise RuntimeError(f"{who}: softmax_scale must be finite and > 0 (got {scale})")
+    qdp, qds, keep_q = _kv_descale(who, "q_descale", q_descale, q, b, hkv)
+    kdp, kds, keep_k = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
+    vdp, vds, keep_v = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
+    with torch.cuda.device(q.device):
+        o = torch.empty((b, hq, nq, 128) if layout == "bhnd" else (b, nq, hq, 128), dtype=out_dtype, device=q.device)
+        lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)
+        _b, _h, _n, so = _fp8_view(who, "o", o, layout)
+        need = int(_lib.fa_fp8_forward_workspace_bytes(b, hkv, nk, 128))
+        ws = _workspace(q.device, need)
+        _call("fa_fp8_forward", (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp, b, hq, hkv, nq, nk,
+                                 128, _DTYPE_CODE[out_dtype], *sq, *sk, *sv, *so, qds, kds, vds, int(bool(causal)), scale, ws.data_ptr(),
+                                 ws.numel(), _stream_ptr(q.device)))
+    del keep_q, keep_k, keep_v
+    return o, lse

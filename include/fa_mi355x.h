@@ -48,7 +48,7 @@ extern "C" {
 #define FA_DTYPE_F32 0
 #define FA_DTYPE_F16 1
 #define FA_DTYPE_BF16 2
-#define FA_DTYPE_E4M3 3 /* OCP e4m3 (float8_e4m3fn): only as cache_dtype of fa_ex_forward_kvcache_fp8 / fa_ex_forward_varlen_paged_fp8 */
+#define FA_DTYPE_E4M3 3 /* OCP e4m3 (float8_e4m3fn): as cache_dtype of fa_ex_forward_kvcache_fp8 / fa_ex_forward_varlen_paged_fp8; q, k, v of fa_fp8_forward are e4m3 by definition (its dtype argument names o's) */
 
 /* Which implementation the dispatcher picks (fa_set_kernel_mode): AUTO = MFMA bf16/f16 kernels
  * when dtype is 16-bit and d is a multiple of 8 up to 256 (64 / 128 / 256 wide tiles, narrower rows zero-padded in the
@@ -1017,6 +1017,44 @@ int fa_merge_states_backward(const void* o_a, const float* lse_a, const void* o_
                              int64_t do_b_head_stride, int64_t do_b_row_stride, int64_t dlse_a_batch_stride, int64_t dlse_a_head_stride,
                              int64_t dlse_a_row_stride, int64_t dlse_b_batch_stride, int64_t dlse_b_head_stride,
                              int64_t dlse_b_row_stride, void* stream);
+
+/* --- FlashAttention-3's fp8 call: q, k, v ALREADY in OCP e4m3 (float8_e4m3fn), one float32 descale per (batch, K/V head) each.
+ * Forward only.  q is (batch, heads_q, seqlen_q, 128), k and v are (batch, heads_kv, seqlen_k, 128) as raw e4m3 bytes; heads_q is a
+ * multiple of heads_kv and query head h reads K/V head h / (heads_q / heads_kv).  q_descale, k_descale, v_descale: float32
+ * (batch, heads_kv) device memory at their batch strides (0: one (heads_kv,) row for every batch), q's included (FlashAttention-3's
+ * shape); NULL means 1.0 (and needs a stride of 0).  They are read on the device only and must be positive and finite.
+ *     o = softmax(softmax_scale * q_descale * k_descale * q8 k8^T [causal]) (v8 * v_descale)
+ * The causal diagonal is bottom-right aligned: row i sees key j <= i + seqlen_k - seqlen_q (fa_ex_forward's rule).  o is f16 or bf16
+ * (`dtype`), lse float32 (batch, heads_q, seqlen_q) contiguous, natural log.  A row without a visible key gives o = 0, lse = -inf.
+ * Arithmetic: both products run on the e4m3 matrix instruction with unit hardware scales and fp32 accumulation;
+ * f = softmax_scale * log2(e) * q_descale * k_descale is one float per workgroup; p = exp2(fma(s, f, -m)); P is rounded to e4m3 on
+ * EVERY row (l and lse come from the unrounded p); v_descale is applied once, with 1 / l.  There is no 16-bit-P route for short rows
+ * (fa3_forward(fp8 = 1) has one for its backward's sake; FlashAttention-3 rounds P everywhere): 2^-4 relative per probability stands in
+ * full on a row that sees a couple of keys.  NaN codes in the inputs propagate.
+ * Layouts: each of q, k, v, o has batch, head and token strides in ELEMENTS of its own type (bytes for q, k, v; 16-bit elements for
+ * o), the 128 elements of a row contiguous; bases and strides are multiples of 16 bytes.  So (B, N, H, 128) tensors need no copy,
+ * nor does the [:, :seqlen_k] prefix of a contiguous (B, capacity, heads_kv, 128) e4m3 cache: bytes outside rows [0, seqlen_k) of a
+ * view never reach a result, whatever they hold.  A stride of a dimension of extent 1 is not used.
+ * Span limit: q and k are addressed through 32-bit buffer descriptors per (batch, head) unit, so round_up(rows, 256) * token stride
+ * (bytes) must stay below 2^31 for both; above it the call is refused (FA_ERR_UNSUPPORTED, "span limit").
+ * Workspace: the caller's, fa_fp8_forward_workspace_bytes(batch, heads_kv, seqlen_k, d) bytes (V^T: batch * heads_kv *
+ * ceil(seqlen_k / 128) * 16384, plus 256 of padding; 0 for arguments the call would refuse), 16-byte aligned.  Two launches on
+ * `stream` (a byte permutation of V into the workspace, the attention kernel); nothing allocates, synchronises or reads device
+ * memory on the host: the call can be captured in a graph and replayed with changed descale values.
+ * Checked before any HIP call, the first broken rule named in fa_last_error(), in this order: (1) q, k, v, o, lse non-null; (2) batch,
+ * heads_q, heads_kv, seqlen_q, seqlen_k, d > 0; (3) d == 128, else FA_ERR_UNSUPPORTED; (4) heads_q % heads_kv == 0; (5) dtype f16 or
+ * bf16, softmax_scale finite and > 0, a descale stride 0 or >= heads_kv (0 with a NULL descale), descales 4-byte aligned; (6) q, k,
+ * v, o 16-byte aligned, lse 4-byte aligned, every stride used >= 0 and a multiple of 16 bytes, token strides >= 128; (7) the span
+ * limit, and batch * heads * tiles below 2^31 (FA_ERR_UNSUPPORTED); (8) workspace non-null with workspace_bytes >= the need
+ * (FA_ERR_WORKSPACE), 16-byte aligned.  Everything else is FA_ERR_INVALID_ARGUMENT. */
+int fa_fp8_forward(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
+                   const float* v_descale, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_k,
+                   int64_t d, int dtype, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_token_stride,
+                   int64_t k_batch_stride, int64_t k_head_stride, int64_t k_token_stride, int64_t v_batch_stride, int64_t v_head_stride,
+                   int64_t v_token_stride, int64_t o_batch_stride, int64_t o_head_stride, int64_t o_token_stride,
+                   int64_t q_descale_batch_stride, int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal,
+                   double softmax_scale, void* workspace, size_t workspace_bytes, void* stream);
+size_t fa_fp8_forward_workspace_bytes(int64_t batch, int64_t heads_kv, int64_t seqlen_k, int64_t d);
 
 /* --- support entry points (no reference counterpart: the reference allocates inside the callee) --- */
 /* bytes for the CURRENT kernel mode: two float row constants per query row (+ an fp32 dQ scratch of bh*n*d floats in
