@@ -267,7 +267,7 @@ struct KvArgs {
     const float *k_descale = nullptr, *v_descale = nullptr;
     int64_t descale_bstride = 0;
     // fa_ex_forward_kvcache_sink (null: no sinks): head h of every sequence takes the extra column sinks[h % sink_heads].  The call
-    // then always runs the combine (num_splits >= 2): the sink joins there (kv_combine_sink_kernel).
+    // then always runs the combine (num_splits >= 2): the sink joins there (kv_combine_kernel<Tag, SINK = true>).
     const float* sinks = nullptr;
     int64_t sink_heads = 1;
     // fa_ex_forward_kvcache_varlen (null / 0: the padded call).  cu_seqlens_q: q and o are packed (total_q, heads_q, d) at token

@@ -1,4 +1,4 @@
-"""A rounding model of the decode kernels (csrc/fa_decode.hip, fa_decode_kernels.inc, fa_mla.hip), for the sharp bar on the decode
+"""A rounding model of the decode kernels (csrc/fa_decode.hip, fa_decode_kernels.h, fa_mla.hip), for the sharp bar on the decode
 sweeps (tests/test_kvcache_sweep_gpu.py, tests/test_mla_routes_gpu.py; proved on the CPU by tests/test_decode_sharp_cpu.py):
 
     kv_baseline(call, S)                the whole ex_kvcache_forward call at S splits, as a careful kernel of the tensors' dtype
@@ -12,8 +12,8 @@ It holds no kernel code: it is the closed form with the kernels' rounding points
 addressing and the append are kvcache_full_ref.front_half's, shared with the reference.  The points, each with where it was read:
 
   * inputs as stored; an e4m3 element widens exactly (fa_ex_common.h, kv_q8_widen).  With rotary, q is rotated in fp32 from the
-    16-bit values — the products are exact, the sum is rounded to fp32 — and rounded once to 16 bits (fa_decode.hip,
-    kv_rotate_chunk; fa_decode_kernels.inc, kv_split_*_kernel's prologue)
+    16-bit values — the products are exact, the sum is rounded to fp32 — and rounded once to 16 bits (fa_decode_kernels.h,
+    kv_rotate_chunk and the kKvRot branch of kv_split_kernel's prologue)
   * scores: unscaled products, 32 terms an instruction into an fp32 accumulator (fa_decode_common.h, mfma16:
     v_mfma_f32_16x16x32; kv_split_kernel `sacc[kb] = mfma16(kf[kb][ks], qf[ks], sacc[kb])`).  MLA: the 64 rotary dims, then the
     512 latent dims (fa_mla.hip, mla_tile_step)
@@ -35,7 +35,7 @@ addressing and the append are kvcache_full_ref.front_half's, shared with the ref
   * S > 1: fp32 partials acc * (1 / l) [* v_descale] and lse_s; the combine (fa_decode.hip, kv_combine_kernel; fa_mla.hip,
     mla_combine_kernel): m = max_s lse_s, w_s = exp(lse_s - m), their sum by a butterfly over the 64 lanes (xor 32, 16, .. 1),
     acc += w_s O_s in split order, o = round(acc * (1 / sum)), lse = m + log(sum)
-  * the sink column joins in the combine only (kv_combine_sink_kernel): m = max(m, sink), sum += exp(sink - m) after the
+  * the sink column joins in the combine only (kv_combine_kernel<Tag, SINK = true>): m = max(m, sink), sum += exp(sink - m) after the
     butterfly.  The C layer raises a sink call's S from 1 to 2 (fa_capi.hip)
   * the number of splits of num_splits = 0: kv_num_splits (fa_decode.hip), mla_split_rule (fa_mla.hip), transcribed below and held
     to the library's workspace-size entry points by tests/test_decode_sharp_cpu.py

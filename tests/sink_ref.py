@@ -98,8 +98,8 @@ def dsink_sum(term, sink_heads):
 
 
 def combine_model(po, plse, sink):
-    """The decode combine (kv_combine_sink_kernel) as a torch model in fp64: po (S, d) per-split normalised partial outputs,
-    plse (S,) their lse (-inf: an empty split, whose po is never written — any value), sink a float (-inf: none).
+    """The decode combine (kv_combine_kernel<Tag, SINK = true>) as a torch model in fp64: po (S, d) per-split normalised partial
+    outputs, plse (S,) their lse (-inf: an empty split, whose po is never written — any value), sink a float (-inf: none).
         m = max(max_s lse_s, sink), denom = sum_s exp(lse_s - m) + exp(sink - m), o = sum_s exp(lse_s - m) O_s / denom,
         lse = m + log(denom);  nothing visible at all (and no sink): o = 0, lse = -inf."""
     plse = plse.double()

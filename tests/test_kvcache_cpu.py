@@ -187,7 +187,7 @@ def test_split_rule_partitions_the_visible_band():
             assert not nonempty or max(nonempty) - min(nonempty) <= KT
 
 
-# ---- model of the split kernel's row packing (csrc/fa_decode_kernels.inc: pr0, qlo, qhi, qi, h) for any G = H_q / H_kv: row
+# ---- model of the split kernel's row packing (csrc/fa_decode_kernels.h: pr0, qlo, qhi, qi, h) for any G = H_q / H_kv: row
 # pr = token * G + head in the group, 16 rows a tile.  G need not divide 16 (a tile then starts in the middle of a token) and may
 # exceed it (one token's heads then span several tiles).
 ROWS = 16

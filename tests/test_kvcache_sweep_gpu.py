@@ -79,11 +79,11 @@ def after_the_call(key, kw, k_big, v_big, splits):
 
 
 def family(kw, splits):
-    """the split kernel instantiation a call launches and how its results are finished (csrc/fa_decode.hip: launch_split, launch_kv_t)"""
+    """the split kernel instantiation a call launches and how its results are finished (csrc/fa_decode.hip: kv_dispatch, kv_launch)"""
     d = kw["q"].shape[-1]
-    name = "kv_split" + ("_rot" if kw["rotary_cos"] is not None else "") + ("_q8" if kw["k_cache"].dtype == E4M3 else "") + "_kernel"
-    end = "kv_combine_sink_kernel" if kw["sinks"] is not None else "kv_combine_kernel" if splits > 1 else "direct"
-    return f"{name}<D={64 if d <= 64 else 128 if d <= 128 else 256},{'paged' if kw['block_table'] is not None else 'contig'}>+{end}"
+    feat = (1 if kw["rotary_cos"] is not None else 0) | (2 if kw["k_cache"].dtype == E4M3 else 0)   # kKvRot | kKvQ8
+    end = "kv_combine_kernel<SINK>" if kw["sinks"] is not None else "kv_combine_kernel" if splits > 1 else "direct"
+    return f"kv_split_kernel<D={64 if d <= 64 else 128 if d <= 128 else 256},{'paged' if kw['block_table'] is not None else 'contig'},FEAT={feat}>+{end}"
 
 
 def sharp_out(o, lse, kw, r, base, what=""):
