@@ -759,3 +759,63 @@ def flash_attention_fp8(q, k, v, *, q_descale=None, k_descale=None, v_descale=No
                                  None if v_descale is None else v_descale.detach() if isinstance(v_descale, torch.Tensor) else v_descale,
                                  out_dtype, layout)
     return (o, lse) if return_lse else o
+
+
+_FP8_VARLEN_REFUSED = ("window_size", "softcap", "alibi_slopes", "sinks", "attn_bias", "mask", "block_sparse_mask", "dropout_p",
+                       "seqused_q", "seqused_k", "cache_leftpad", "cache_batch_idx", "rotary_cos", "rotary_sin")
+
+
+def flash_attention_fp8_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, *, block_table=None, q_descale=None,
+                               k_descale=None, v_descale=None, softmax_scale=None, causal=False, out_dtype=torch.bfloat16,
+                               return_softmax_lse=False, **unsupported):
+    """The packed and the paged form of flash_attention_fp8 (FlashAttention-3's flash_attn_varlen_func with q_descale / k_descale /
+    v_descale): q (total_q, H_q, 128) in torch.float8_e4m3fn packed by cu_seqlens_q, a token- or head-strided view (a slice of a
+    fused projection) taken without a copy.  Without block_table k and v are (total_k, H_kv, 128) e4m3 packed by cu_seqlens_k.  With
+    block_table, int32 (B, max_blocks_per_seq) on the device, k and v are the e4m3 pools (num_blocks, ps, H_kv, 128) of the paged
+    cache flash_attn_with_kvcache appends to, ps a multiple of 16, each pool at its own page and token strides; key t of sequence
+    b is pool[block_table[b, t // ps], t % ps] and len_k[b] = cu_seqlens_k[b + 1] - cu_seqlens_k[b], clamped on the device to
+    [0, min(max_seqlen_k, max_blocks_per_seq * ps)].  Descales: float32 (B, H_kv), B the number of sequences, or (H_kv,); None = 1;
+    read on the device only.  H_q % H_kv == 0 and query head h reads K/V head h // (H_q // H_kv).  softmax_scale defaults to
+    128 ** -0.5; the causal diagonal is bottom-right aligned per sequence (j <= i + len_k[b] - len_q[b]).  Every sequence has the
+    bits of flash_attention_fp8 on that sequence alone.  A row without a visible key (an empty key sequence, a causal row above the
+    diagonal) gives o = 0 and lse = -inf; rows of o that belong to no sequence are not written.
+    Nothing is read on the host: the call never synchronises and a captured call replays after the offsets, the table and the
+    descale values changed in place.  Offsets and table are untrusted: offsets and lengths are clamped, a page outside
+    [0, num_blocks) reads as zero bytes for K and V, no entry past ceil(len_k / ps) is read, page offsets are 64-bit and pages may be
+    shared.  Forward only: q, k or v requiring grad under grad mode raises RuntimeError.
+    Refused by name before anything runs (NotImplementedError): window_size, softcap, alibi_slopes, sinks, attn_bias, masks,
+    dropout, seqused_q / seqused_k, cache_leftpad, cache_batch_idx, head dims other than 128, 16-bit q / k / v
+    (flash_attention_varlen takes those), out_dtype other than bfloat16 / float16.
+    Returns o (total_q, H_q, 128) in out_dtype, and with return_softmax_lse also lse float32 (H_q, total_q), the layout of
+    flash_attention_varlen(return_softmax_lse=True)."""
+    who = "flash_attention_fp8_varlen"
+    for name, val in unsupported.items():
+        if name in _FP8_VARLEN_REFUSED:
+            if val is None or val is False or (name == "window_size" and tuple(val) == (-1, -1)) or \
+                    (name in ("softcap", "dropout_p") and val == 0.0):
+                continue
+            raise NotImplementedError(f"{who}: {name} is not supported by the fp8 call")
+        raise TypeError(f"{who}() got an unexpected keyword argument {name!r}")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
+        if t.dtype in (torch.float16, torch.bfloat16, torch.float32):
+            raise NotImplementedError(f"{who}: 16-bit inputs are not supported: {name} is {t.dtype}, torch.float8_e4m3fn expected "
+                                      f"(quantise first, or use flash_attention_varlen)")
+        if t.dtype != torch.float8_e4m3fn:
+            raise NotImplementedError(f"{who}: {name} of dtype {t.dtype} is not supported (torch.float8_e4m3fn expected)")
+        if t.dim() >= 1 and t.shape[-1] != 128:
+            raise NotImplementedError(f"{who}: head_dim {t.shape[-1]} is not supported (128 only)")
+    if out_dtype not in (torch.bfloat16, torch.float16):
+        raise NotImplementedError(f"{who}: out_dtype {out_dtype} is not supported (torch.bfloat16 or torch.float16)")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+        raise RuntimeError(f"{who}: forward only — q, k or v requires grad and the fp8 call has no backward (call it under "
+                           f"torch.no_grad(), or detach the tensors)")
+    import flashattention_lab_cuda as ext
+
+    det = lambda t: t.detach() if isinstance(t, torch.Tensor) else t   # noqa: E731
+    with torch.no_grad():
+        o, lse = ext.fp8_varlen_forward(q.detach(), k.detach(), v.detach(), cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k,
+                                        bool(causal), softmax_scale, det(q_descale), det(k_descale), det(v_descale), out_dtype,
+                                        block_table)
+    return (o, lse) if return_softmax_lse else o

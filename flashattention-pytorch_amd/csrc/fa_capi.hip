@@ -30,7 +30,7 @@ std::vector<hipEvent_t> g_prof_free;
 hipEvent_t g_prof_open[fa::K_COUNT];
 const char* const kKernelNames[fa::K_COUNT] = {"fwd_f32", "bwd_delta", "bwd_dkdv_f32", "bwd_dq_f32", "fwd_mfma",
                                                "bwd_mfma", "bwd_dq_cvt", "bwd_dq_mfma", "fp8_quant", "fwd_fp8", "ex_fwd", "ex_bwd", "kv_group_sum",
-                                               "fp8in_vt", "fp8in_fwd"};
+                                               "fp8in_vt", "fp8in_fwd", "fp8in_vt_varlen", "fp8in_fwd_varlen"};
 
 hipEvent_t prof_get_event() {
     if (!g_prof_free.empty()) { hipEvent_t e = g_prof_free.back(); g_prof_free.pop_back(); return e; }
@@ -2570,6 +2570,167 @@ int fa_fp8_forward(const void* q, const void* k, const void* v, void* o, float* 
     c.dtype = dtype; c.causal = causal; c.scale = softmax_scale;
     c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
     return fp8_forward_impl("fa_fp8_forward", c);
+}
+
+// ---- the packed and the paged form of the fp8 call: see include/fa_mi355x.h
+// One call of fa_fp8_forward_varlen, a family of its own.
+struct Fp8VarCall {
+    const void *q = nullptr, *k = nullptr, *v = nullptr;
+    void* o = nullptr;
+    float* lse = nullptr;
+    const float *q_descale = nullptr, *k_descale = nullptr, *v_descale = nullptr;
+    const int32_t *cu_q = nullptr, *cu_k = nullptr, *block_table = nullptr;
+    int64_t batch = 0, heads_q = 0, heads_kv = 0, total_q = 0, total_k = 0, max_q = 0, max_k = 0, d = 0;
+    int dtype = 0;
+    int64_t q_ts = 0, q_hs = 0, k_ts = 0, k_hs = 0, v_ts = 0, v_hs = 0;
+    int64_t max_blocks = 0, num_blocks = 0, ps = 0, k_ps = 0, v_ps = 0;
+    int64_t qds_bs = 0, kds_bs = 0, vds_bs = 0;
+    int causal = 0;
+    double scale = 0.0;
+    void* workspace = nullptr;
+    size_t workspace_bytes = 0;
+    void* stream = nullptr;
+};
+
+static int fp8_forward_varlen_impl(const char* who, const Fp8VarCall& c) {
+    const bool paged = c.block_table != nullptr;
+    const int64_t kInt = ((int64_t)1 << 31) - 1;
+    // (1) null pointers
+    if (!c.q || !c.k || !c.v || !c.o || !c.lse) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    if (!c.cu_q || !c.cu_k) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null cu_seqlens pointer", who);
+    // (2) dims
+    if (c.batch <= 0 || c.heads_q <= 0 || c.heads_kv <= 0 || c.d <= 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch, heads_q, heads_kv and d must be > 0 (got %lld, %lld, %lld, %lld)", who,
+                    (long long)c.batch, (long long)c.heads_q, (long long)c.heads_kv, (long long)c.d);
+    if (c.total_q < 0 || c.total_k < 0 || c.max_q < 0 || c.max_k < 0 || c.total_q > kInt || c.total_k > kInt || c.max_q > kInt || c.max_k > kInt ||
+        c.batch >= kInt)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: total_q, total_k, max_seqlen_q and max_seqlen_k must lie in [0, 2^31) (got %lld, %lld, %lld, %lld)",
+                    who, (long long)c.total_q, (long long)c.total_k, (long long)c.max_q, (long long)c.max_k);
+    // (3) the head dim
+    if (c.d != 128) return fail(FA_ERR_UNSUPPORTED, "%s: head_dim %lld is not supported (128 only)", who, (long long)c.d);
+    // (4) the heads ratio
+    if (c.heads_q % c.heads_kv != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads_q=%lld must be a multiple of heads_kv=%lld", who, (long long)c.heads_q, (long long)c.heads_kv);
+    // (5) the output dtype, the scale
+    if (c.dtype != FA_DTYPE_F16 && c.dtype != FA_DTYPE_BF16)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: dtype (of o) must be f16 or bf16 (got code %d)", who, c.dtype);
+    if (!(c.scale == c.scale) || !scale_ok(c.scale))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale must be finite and > 0", who);
+    // (6) the pages
+    if (paged) {
+        if (c.ps < 16 || c.ps % 16 != 0 || c.ps > 65536)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: page_block_size must be a multiple of 16 in [16, 65536] (got %lld)", who, (long long)c.ps);
+        if (c.num_blocks < 1 || c.num_blocks > kInt)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_blocks must lie in [1, 2^31) (got %lld)", who, (long long)c.num_blocks);
+        if (c.max_blocks < 0 || c.max_blocks > kInt / c.batch)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch * max_blocks_per_seq must lie in [0, 2^31) (got max_blocks_per_seq=%lld)", who,
+                        (long long)c.max_blocks);
+    } else if (c.max_blocks != 0 || c.num_blocks != 0 || c.ps != 0 || c.k_ps != 0 || c.v_ps != 0) {
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: max_blocks_per_seq, num_blocks, page_block_size and the page strides must be 0 without block_table", who);
+    }
+    // (7) the descale strides
+    const struct { const char* name; const float* p; int64_t bs; } ds[3] = {
+        {"q_descale", c.q_descale, c.qds_bs}, {"k_descale", c.k_descale, c.kds_bs}, {"v_descale", c.v_descale, c.vds_bs}};
+    for (const auto& s : ds) {
+        if (!s.p && s.bs != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: %s_batch_stride must be 0 without %s", who, s.name, s.name);
+        if (s.bs < 0 || (s.bs != 0 && s.bs < c.heads_kv) || s.bs >= ((int64_t)1 << 31) / c.batch)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: %s_batch_stride=%lld must be 0 or >= heads_kv=%lld", who, s.name, (long long)s.bs,
+                        (long long)c.heads_kv);
+        if ((uintptr_t)s.p % 4 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: %s must be 4-byte aligned", who, s.name);
+    }
+    // (8) alignment and strides: 16-byte units, rows that do not overlap
+    if (!aligned16({c.q, c.k, c.v, c.o})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: q, k, v and o must be 16-byte aligned", who);
+    if ((uintptr_t)c.lse % 4 != 0 || (uintptr_t)c.cu_q % 4 != 0 || (uintptr_t)c.cu_k % 4 != 0 || (uintptr_t)c.block_table % 4 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: lse, cu_seqlens_q, cu_seqlens_k and block_table must be 4-byte aligned", who);
+    const int64_t kMaxStride = (int64_t)1 << 44;
+    const struct { const char* name; int64_t ts, hs, heads, ps; } ts[3] = {
+        {"q", c.q_ts, c.q_hs, c.heads_q, 0}, {"k", c.k_ts, c.k_hs, c.heads_kv, c.k_ps}, {"v", c.v_ts, c.v_hs, c.heads_kv, c.v_ps}};
+    for (const auto& t : ts) {
+        const int64_t hs = t.heads > 1 ? t.hs : 0;
+        if (t.ts % 16 != 0 || hs % 16 != 0 || t.ps % 16 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (token %lld, head %lld, page %lld) must be multiples of 16 bytes", who, t.name,
+                        (long long)t.ts, (long long)t.hs, (long long)t.ps);
+        if (t.ts < 128 || hs < 0 || t.ps < 0 || t.ts > kMaxStride || hs > kMaxStride || t.ps > kMaxStride)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (token %lld, head %lld, page %lld) must be >= 0, the token stride >= 128", who,
+                        t.name, (long long)t.ts, (long long)t.hs, (long long)t.ps);
+    }
+    // (9) the span limits: q, packed k and one page are read through 32-bit buffer descriptors and offsets
+    const int64_t kSpan = ((int64_t)1 << 31) - 1;
+    const int64_t q_span = (c.max_q + 255) / 256 * 256 * c.q_ts;
+    if (q_span > kSpan)
+        return fail(FA_ERR_UNSUPPORTED, "%s: span limit: round_up(max_seqlen_q, 256) * token stride of q is %lld bytes, at or above 2^31", who,
+                    (long long)q_span);
+    const int64_t cap = paged ? std::min(c.max_k, c.max_blocks * c.ps) : c.max_k;
+    if (paged) {
+        const int64_t kp = c.ps * c.k_ts, vp = c.ps * c.v_ts;
+        if (kp > kSpan || vp > kSpan)
+            return fail(FA_ERR_UNSUPPORTED, "%s: span limit: page_block_size * token stride of %s is %lld bytes, at or above 2^31", who,
+                        kp > kSpan ? "k" : "v", (long long)(kp > kSpan ? kp : vp));
+        if (cap >= ((int64_t)1 << 24))
+            return fail(FA_ERR_UNSUPPORTED, "%s: span limit: min(max_seqlen_k, max_blocks_per_seq * page_block_size) = %lld is at or above 2^24", who,
+                        (long long)cap);
+    } else {
+        const int64_t k_span = (c.max_k + 255) / 256 * 256 * c.k_ts;
+        if (k_span > kSpan)
+            return fail(FA_ERR_UNSUPPORTED, "%s: span limit: round_up(max_seqlen_k, 256) * token stride of k is %lld bytes, at or above 2^31", who,
+                        (long long)k_span);
+    }
+    fa::Fp8InVarArgs a;
+    a.batch = c.batch; a.heads_q = c.heads_q; a.heads_kv = c.heads_kv; a.total_q = c.total_q; a.total_k = paged ? 0 : c.total_k;
+    a.max_q = c.max_q; a.max_k = c.max_k; a.max_blocks = c.max_blocks; a.num_blocks = c.num_blocks; a.page_size = c.ps;
+    const int64_t nqt = (c.max_q + 255) / 256, nbmax = (cap + 63) / 64, tiles = fa::fp8in_varlen_workspace_bytes(a) / 16384;
+    if ((nqt > 0 && c.batch * c.heads_q >= ((int64_t)1 << 31) / nqt) || (nbmax > 0 && c.batch * c.heads_kv >= ((int64_t)1 << 31) / nbmax) ||
+        tiles >= ((int64_t)1 << 31))
+        return fail(FA_ERR_UNSUPPORTED, "%s: span limit: batch * heads * tiles too large for one launch", who);
+    // (10) the workspace
+    const size_t need = fa::fp8in_varlen_workspace_bytes(a);
+    if (!c.workspace || c.workspace_bytes < need)
+        return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes is too small (need %zu: fa_fp8_forward_varlen_workspace_bytes)", who,
+                    c.workspace ? c.workspace_bytes : (size_t)0, need);
+    if ((uintptr_t)c.workspace % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
+
+    a.q = c.q; a.k = c.k; a.v = c.v; a.o = c.o; a.lse = c.lse;
+    a.q_descale = c.q_descale; a.k_descale = c.k_descale; a.v_descale = c.v_descale;
+    a.qds_bs = c.qds_bs; a.kds_bs = c.kds_bs; a.vds_bs = c.vds_bs;
+    a.cu_q = c.cu_q; a.cu_k = c.cu_k; a.block_table = c.block_table;
+    a.dtype = c.dtype;
+    a.q_ts = c.q_ts; a.q_hs = c.heads_q > 1 ? c.q_hs : 0; a.k_ts = c.k_ts; a.k_hs = c.heads_kv > 1 ? c.k_hs : 0;
+    a.v_ts = c.v_ts; a.v_hs = c.heads_kv > 1 ? c.v_hs : 0; a.k_ps = c.k_ps; a.v_ps = c.v_ps;
+    a.causal = c.causal != 0; a.scale = (float)c.scale; a.workspace = c.workspace;
+    return launched(who, fa::launch_fp8_inputs_varlen(a, reinterpret_cast<hipStream_t>(c.stream)));
+}
+
+size_t fa_fp8_forward_varlen_workspace_bytes(int64_t batch, int64_t heads_kv, int64_t total_k, int64_t max_seqlen_k, int64_t max_blocks_per_seq,
+                                             int64_t page_block_size, int64_t d) {
+    const int64_t kInt = ((int64_t)1 << 31) - 1;
+    if (batch <= 0 || heads_kv <= 0 || total_k < 0 || max_seqlen_k < 0 || max_blocks_per_seq < 0 || page_block_size < 0 || d != 128) return 0;
+    if (batch > kInt || total_k > kInt || max_seqlen_k > kInt || max_blocks_per_seq > kInt || page_block_size > 65536) return 0;
+    if (page_block_size % 16 != 0) return 0;
+    fa::Fp8InVarArgs a;
+    a.batch = batch; a.heads_kv = heads_kv; a.total_k = page_block_size ? 0 : total_k; a.max_k = max_seqlen_k;
+    a.max_blocks = page_block_size ? max_blocks_per_seq : 0; a.page_size = page_block_size;
+    return fa::fp8in_varlen_workspace_bytes(a);
+}
+
+int fa_fp8_forward_varlen(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
+                          const float* v_descale, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, const int32_t* block_table,
+                          int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q,
+                          int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_token_stride, int64_t q_head_stride, int64_t k_token_stride,
+                          int64_t k_head_stride, int64_t v_token_stride, int64_t v_head_stride, int64_t max_blocks_per_seq, int64_t num_blocks,
+                          int64_t page_block_size, int64_t k_page_stride, int64_t v_page_stride, int64_t q_descale_batch_stride,
+                          int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    Fp8VarCall c;
+    c.q = q; c.k = k; c.v = v; c.o = o; c.lse = lse; c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
+    c.cu_q = cu_seqlens_q; c.cu_k = cu_seqlens_k; c.block_table = block_table;
+    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.total_q = total_q; c.total_k = total_k; c.max_q = max_seqlen_q;
+    c.max_k = max_seqlen_k; c.d = d; c.dtype = dtype;
+    c.q_ts = q_token_stride; c.q_hs = q_head_stride; c.k_ts = k_token_stride; c.k_hs = k_head_stride; c.v_ts = v_token_stride;
+    c.v_hs = v_head_stride;
+    c.max_blocks = max_blocks_per_seq; c.num_blocks = num_blocks; c.ps = page_block_size; c.k_ps = k_page_stride; c.v_ps = v_page_stride;
+    c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
+    c.causal = causal; c.scale = softmax_scale; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    return fp8_forward_varlen_impl("fa_fp8_forward_varlen", c);
 }
 
 size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {

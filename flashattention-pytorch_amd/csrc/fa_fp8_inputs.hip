@@ -34,7 +34,13 @@
 //
 // Span limit: q and k are addressed through 32-bit buffer descriptors and 32-bit offsets per (batch, head) unit, so
 // round_up(rows, 256) * token_stride_bytes must stay below 2^31 for both (fa_capi.hip checks it; batch and head offsets are 64-bit).
+//
+// The packed and the paged form of the call (fa_fp8_forward_varlen) follow the padded one below: fp8in_vt_varlen_kernel,
+// fwd_fp8in_varlen_kernel.
+#include <algorithm>
+
 #include "fa_common.h"
+#include "fa_ex_common.h"
 #include "fa_kernels.h"
 
 namespace fa {
@@ -288,6 +294,356 @@ hipError_t launch_fp8_inputs(const Fp8InArgs& c, hipStream_t st) {
     };
     if (c.dtype == 2) return c.causal ? launch(fwd_fp8in_kernel<bf16_tag, true>) : launch(fwd_fp8in_kernel<bf16_tag, false>);
     return c.causal ? launch(fwd_fp8in_kernel<f16_tag, true>) : launch(fwd_fp8in_kernel<f16_tag, false>);
+}
+
+// ---- The packed and the paged form (include/fa_mi355x.h: fa_fp8_forward_varlen) --------------------------
+// q is (total_q, H_q, 128) packed by cu_seqlens_q; k and v are (total_k, H_kv, 128) packed by cu_seqlens_k, or, with a block
+// table, pools (num_blocks, ps, H_kv, 128) in which key t of sequence b is row t % ps of page table[b][t / ps].  Every sequence
+// gets the bits of fa_fp8_forward on that sequence alone: the loop below is fwd_fp8in_kernel's text from the first `stage` call to
+// the epilogue, DUPLICATED rather than shared (a shared device function must not change fwd_fp8in_kernel's instructions, and the
+// two kernels differ in every value that text closes over), and the transposer writes fp8in_vt_kernel's image per sequence.
+//
+// The V^T workspace is [K/V head][tile][d row][128 key bytes] with `nt_head` tiles a head.  Sequence b's tiles start at
+//   packed   floor(start_b / 128) + b      start_b its clamped first key; floor((s + l) / 128) - floor(s / 128) + 1 >= ceil(l / 128), so
+//                                          the regions of consecutive sequences do not overlap and end inside
+//                                          nt_head = floor(total_k / 128) + B tiles
+//   paged    b * nt_seq                    nt_seq = ceil(cap / 128), cap = min(max_seqlen_k, max_blocks * ps); nt_head = B * nt_seq
+// both computable on the device from the offsets alone, and the size on the host from shapes alone.
+// Offsets and table are untrusted: lengths are clamped (seq_span / paged_len, fa_ex_common.h), a page outside [0, num_blocks) reads
+// as zero bytes for K and V, and no table entry past ceil(len_k / ps) is read.
+struct Fp8InVarKernelArgs {
+    const uint8_t *q, *k, *v8t;
+    uint16_t* o;
+    float* lse;                            // (H_q, total_q)
+    const float *qds, *kds, *vds;          // (B, H_kv) descales at their batch strides; null: 1
+    int qds_bs, kds_bs, vds_bs;
+    const int *cu_q, *cu_k;                // [B + 1] untrusted offsets
+    int total_q, total_k, max_q, max_k;    // max_k: the cap on a sequence's keys (paged: min(max_seqlen_k, max_blocks * ps))
+    int hq, hkv, group, nqt, nt_head, nt_seq;
+    int q_ts, k_ts, o_ts;                  // token strides: q and k in bytes, o in elements
+    long long q_hs, k_hs, o_hs;
+    ExPage pg;                             // PAGED: table, K page stride in kps (bytes); vps is not used here
+    float c_log2;
+};
+
+// tiles before sequence b's in a head's part of the workspace; ks: its clamped first key (packed)
+template <bool PAGED> __device__ __forceinline__ int fp8in_tile_start(int b, int ks, int nt_seq) {
+    return PAGED ? b * nt_seq : (ks >> 7) + b;
+}
+
+// one workgroup = one 64-key block of one (sequence, K/V head); the grid is padded to the cap on a sequence's keys, and a block
+// past its sequence's last one has no tile half of its own to write (the last block zeroes the other half of an odd last tile)
+template <bool PAGED>
+__global__ __launch_bounds__(256) void fp8in_vt_varlen_kernel(const uint8_t* __restrict__ v, uint8_t* __restrict__ v8t,
+                                                              const int* __restrict__ cu_k, int total_k, int max_k, int nbmax,
+                                                              int nt_head, int nt_seq, int hkv, long long v_hs, long long v_ts,
+                                                              const ExPage pg) {
+    constexpr int D = 128, CPR = D / 16, PER = (64 * CPR) / 256;   // 16-byte chunks per row / per thread
+    __shared__ __attribute__((aligned(16))) uint8_t tr[D * 64];   // [d row][permuted key position]
+    const int unit = blockIdx.x / nbmax, blk = blockIdx.x - unit * nbmax, row0 = blk * 64;
+    const int b = unit / hkv, hk = unit - b * hkv;
+    int ks = 0, nk;
+    if (PAGED) nk = paged_len(cu_k, b, max_k);
+    else seq_span(cu_k, b, total_k, max_k, ks, nk);
+    const int nb = (nk + 63) >> 6;
+    if (blk >= nb) return;
+    const uint8_t* src = v + (size_t)hk * v_hs + (PAGED ? (size_t)0 : (size_t)ks * v_ts);
+    [[maybe_unused]] const int* trow = PAGED ? pg.table + (size_t)b * pg.max_blocks : nullptr;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const int c = threadIdx.x + 256 * i, key = c / CPR, ch = c % CPR;   // key within the 64-key block
+        u32x4 x = u32x4{0u, 0u, 0u, 0u};
+        if (row0 + key < nk) {
+            if (PAGED) {
+                // a 16-key group never straddles a page (ps % 16 == 0): one entry serves it, and key < nk keeps the slot below
+                // ceil(nk / ps)
+                const int slot = pg_slot(pg, row0 + key), page = trow[slot];
+                if ((unsigned)page < (unsigned)pg.num_blocks)
+                    x = *reinterpret_cast<const u32x4*>(src + (size_t)page * pg.vps + (size_t)(row0 + key - slot * pg.ps) * v_ts + 16 * ch);
+            } else {
+                x = *reinterpret_cast<const u32x4*>(src + (size_t)(row0 + key) * v_ts + 16 * ch);
+            }
+        }
+        const int wlo = key & 31, pos = 32 * (key >> 5) + 16 * ((wlo >> 2) & 1) + (wlo & 3) + 4 * (wlo >> 3);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) tr[(16 * ch + j) * 64 + pos] = (uint8_t)((x[j >> 2] >> (8 * (j & 3))) & 0xff);
+    }
+    __syncthreads();
+    const int r = threadIdx.x >> 1, half = threadIdx.x & 1;
+    const size_t tile = (size_t)hk * nt_head + fp8in_tile_start<PAGED>(b, ks, nt_seq) + (blk >> 1);
+    uint8_t* dst = v8t + (tile * D + r) * 128 + 64 * (blk & 1) + 32 * half;
+    const u32x4* s4 = reinterpret_cast<const u32x4*>(tr + r * 64 + 32 * half);
+    reinterpret_cast<u32x4*>(dst)[0] = s4[0];
+    reinterpret_cast<u32x4*>(dst)[1] = s4[1];
+    if ((nb & 1) && blk == nb - 1) {
+        reinterpret_cast<u32x4*>(dst + 64)[0] = u32x4{0u, 0u, 0u, 0u};
+        reinterpret_cast<u32x4*>(dst + 64)[1] = u32x4{0u, 0u, 0u, 0u};
+    }
+}
+
+// One K tile of a paged call: dma_stage_kv_paged's pieces (fa_ex_common.h) for K alone, with e4m3 rows.  A 1-KiB piece is 8 rows,
+// 8 | 16 | ps, so a piece lies inside one page and one wave-uniform table entry serves it.  Each piece gets a descriptor of its
+// own in SGPRs: the 64-bit address of its first row and as num_records the bytes of its rows below nk, 0 for a piece past the end
+// or on a page outside the pool (every lane fails the range check and lands as zero).  No branch around the DMA: the image is
+// always fully written.  make_rsrc_s's v_readfirstlane writes stand right before dma16_issue, whose s_mov m0 + s_nop 3 are the
+// wait states the buffer instruction needs after them.  The table is not written while the kernel runs, and its entry is read
+// through the constant address space so that it is a scalar load: as a plain global pointer it became a vector load (the DMA's
+// asm statements clobber memory, so hipcc does not prove the table unchanged) whose whole latency stood in front of every tile
+// (profiles/fp8_varlen.md).
+typedef const int __attribute__((address_space(4)))* fp8in_const_int_p;
+__device__ __forceinline__ void fp8in_stage_k_paged(const ExPage& pg, const int* __restrict__ trow, int last, const uint8_t* kh, char* ktile,
+                                                    int row0, int nk, int voff_k, int w, int k_ts) {
+    const unsigned tk = lds_addr_of(ktile);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int pc = w + 8 * j;
+        const int key = __builtin_amdgcn_readfirstlane(row0 + 8 * pc);
+        const int rows = min(8, nk - key);               // <= 0: the piece lies past the sequence
+        const int slot = min(pg_slot(pg, key), last);    // no entry past ceil(nk / ps) is read
+        const int page = ((fp8in_const_int_p)trow)[slot];
+        const bool ok = rows > 0 && (unsigned)page < (unsigned)pg.num_blocks;
+        const long long ko = ok ? (long long)page * pg.kps + (long long)(key - slot * pg.ps) * k_ts : 0ll;
+        dma16_issue(make_rsrc_s(kh + ko, ok ? (unsigned)(rows - 1) * (unsigned)k_ts + 128u : 0u), tk + pc * 1024, voff_k, 0);
+    }
+}
+
+template <typename Tag, bool CAUSAL, bool PAGED>
+__global__ __launch_bounds__(512, 2) void fwd_fp8in_varlen_kernel(const Fp8InVarKernelArgs a) {
+    constexpr int D = 128, BM = 256, BN = 128, KB = 4, NM = D / 32, NDV = D / 32;
+    constexpr int TILE = BN * D;                         // bytes of a K tile and of a V^T tile alike
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // [2 buffers][K8 tile | V8^T tile]
+    typedef int i32x8_t __attribute__((ext_vector_type(8)));
+
+    const int L = xcd_remap(blockIdx.x, gridDim.x);
+    const int bh = L / a.nqt;                            // b * H_q + head
+    int qt = L - bh * a.nqt;
+    if (CAUSAL) qt = a.nqt - 1 - qt;
+    const int b = bh / a.hq, hd = bh - b * a.hq, hk = hd / a.group;
+    int qs, nq, ks = 0, nk;                              // this sequence's clamped spans
+    seq_span(a.cu_q, b, a.total_q, a.max_q, qs, nq);
+    if (PAGED) nk = paged_len(a.cu_k, b, a.max_k);
+    else seq_span(a.cu_k, b, a.total_k, a.max_k, ks, nk);
+    const int q0 = qt * BM;
+    if (q0 >= nq) return;                                // the padded grid: no row of this tile belongs to the sequence
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const int qrow = q0 + 32 * w + r;
+    const int shift = nk - nq;                           // row i sees key j <= i + shift
+
+    const buf_rsrc_t q_rs = make_rsrc(a.q + (size_t)qs * a.q_ts + (size_t)hd * a.q_hs, (unsigned)(nq - 1) * (unsigned)a.q_ts + D);
+    u32x4 qf[NM];
+#pragma unroll
+    for (int m = 0; m < NM; ++m) qf[m] = __builtin_amdgcn_raw_buffer_load_b128(q_rs, qrow * a.q_ts + 32 * m + 16 * h, 0, 0);
+    const float qd = a.qds ? a.qds[(size_t)b * a.qds_bs + hk] : 1.f;
+    const float kd = a.kds ? a.kds[(size_t)b * a.kds_bs + hk] : 1.f;
+    const float vd = a.vds ? a.vds[(size_t)b * a.vds_bs + hk] : 1.f;
+    const float f = (a.c_log2 * qd) * kd;                // the one score factor of this workgroup, > 0
+
+    const int kend = CAUSAL ? max(0, min(nk, q0 + BM + shift)) : nk;
+    const int ntiles = (kend + BN - 1) / BN;             // 0: no row of this tile sees a key
+    const int ntile_b = (nk + BN - 1) / BN;              // this sequence's V^T tiles
+    const uint8_t* kh = a.k + (size_t)hk * a.k_hs + (PAGED ? (size_t)0 : (size_t)ks * a.k_ts);
+    [[maybe_unused]] const rsrc_s_t k_rs = make_rsrc_s(kh, nk > 0 ? (unsigned)(nk - 1) * (unsigned)a.k_ts + D : 0u);
+    const rsrc_s_t v_rs = make_rsrc_s(a.v8t + ((size_t)hk * a.nt_head + fp8in_tile_start<PAGED>(b, ks, a.nt_seq)) * TILE,
+                                      (unsigned)ntile_b * TILE);
+    const int kstride = a.k_ts >> 1;                     // the STRIDED helpers count 2-byte elements
+    const int voff_k = dma_lane_voff<64, true>(lane, w, 64, kstride);   // 128-byte rows: the geometry of a 16-bit d = 64 tile
+    const int voff_v = dma_lane_voff<64>(lane, w);
+    [[maybe_unused]] const int* trow = PAGED ? a.pg.table + (size_t)b * a.pg.max_blocks : nullptr;
+    [[maybe_unused]] const int pg_last = PAGED ? pg_slot(a.pg, max(nk - 1, 0)) : 0;   // no entry past ceil(nk / ps) is read
+    auto stage = [&](int buf, int t) {
+        char* b_ = smem + buf * 2 * TILE;
+        if constexpr (PAGED) {
+            fp8in_stage_k_paged(a.pg, trow, pg_last, kh, b_, t * BN, nk, voff_k, w, a.k_ts);
+        } else {
+            dma_stage_tile<64, BN, 8, true>(k_rs, b_, t * BN, voff_k, w, 64, 0, kstride);
+        }
+        dma_stage_tile<64, BN, 8>(v_rs, b_ + TILE, t * BN, voff_v, w);   // V^T tile t = rows 128 t .. of the [tile][d row] matrix
+    };
+
+    // ---- from here to the stores: fwd_fp8in_kernel's text
+    f32x16 oacc[NDV];
+#pragma unroll
+    for (int t = 0; t < NDV; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) oacc[t][i] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;                // running max in log2 units of the scaled score
+
+    if (ntiles > 0) {
+        stage(0, 0);
+        dma_wait_all();
+        __syncthreads();
+    }
+    const int last_w = q0 + 32 * w + 31 + shift;         // the last key the wave's last row sees under the mask
+    const int ntiles_w = CAUSAL ? (last_w < 0 ? 0 : min(ntiles, last_w / BN + 1)) : ntiles;
+
+    for (int t = 0; t < ntiles_w; ++t) {
+        const int k0 = t * BN, cur = t & 1;
+        if (t + 1 < ntiles) stage(cur ^ 1, t + 1);
+        const char* Kt = smem + cur * 2 * TILE;
+        const char* Vt = Kt + TILE;
+        f32x16 sacc[KB];
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) sacc[kb][i] = 0.f;
+#pragma unroll
+            for (int M = 0; M < NM / 2; ++M) {
+                const u32x4 a0 = *reinterpret_cast<const u32x4*>(Kt + TileSwz<64>::off(32 * kb + r, 4 * M + h));
+                const u32x4 a1 = *reinterpret_cast<const u32x4*>(Kt + TileSwz<64>::off(32 * kb + r, 4 * M + 2 + h));
+                const i32x8_t ka = {(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], (int)a1[0], (int)a1[1], (int)a1[2], (int)a1[3]};
+                const u32x4 b0_ = qf[2 * M], b1_ = qf[2 * M + 1];
+                const i32x8_t qb = {(int)b0_[0], (int)b0_[1], (int)b0_[2], (int)b0_[3], (int)b1_[0], (int)b1_[1], (int)b1_[2], (int)b1_[3]};
+                sacc[kb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ka, qb, sacc[kb], 0, 0, 0, 127, 0, 127);
+            }
+        }
+        const bool need_mask = (CAUSAL && (k0 + BN - 1 > q0 + 32 * w + shift)) || (k0 + BN > nk);
+        const int lim = CAUSAL ? min(qrow + shift, nk - 1) : nk - 1;   // (negative: the row sees no key)
+        float mx = -INFINITY;
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) {
+            if (need_mask) {
+                const int thr = lim - (k0 + 32 * kb + 4 * h);
+#pragma unroll
+                for (int i = 0; i < 16; ++i)
+                    if ((i & 3) + 8 * (i >> 2) > thr) sacc[kb][i] = -INFINITY;
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) mx = fmaxf(mx, sacc[kb][i]);
+        }
+        mx = mx * f;
+        mx = fmaxf(mx, wave_half_swap(mx));
+        const float m_new = fmaxf(m_run, mx);
+        float m_use;
+        if (__any(m_new - m_run > 8.0f) != 0) {   // lazy rescale; a row's first visible key: inf > 8
+            m_use = m_new;
+            const float alpha = __builtin_amdgcn_exp2f(m_run - ((m_new == -INFINITY) ? 0.f : m_new));
+            m_run = m_new;
+            l_run *= alpha;
+#pragma unroll
+            for (int t2 = 0; t2 < NDV; ++t2)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) oacc[t2][i] *= alpha;
+        } else {
+            m_use = m_run;
+        }
+        if (m_use == -INFINITY) m_use = 0.f;      // a row without a visible key so far: p = exp2(-inf) = 0, not exp2(-inf + inf)
+        float rs = 0.f;
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            i32x8_t pb;
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {
+                const int kb = 2 * g + kk;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float p = __builtin_amdgcn_exp2f(fmaf(sacc[kb][i], f, -m_use));   // (-inf stays -inf: f > 0)
+                    sacc[kb][i] = p;
+                    rs += p;
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    int wd = 0;
+                    wd = __builtin_amdgcn_cvt_pk_fp8_f32(sacc[kb][4 * j + 0], sacc[kb][4 * j + 1], wd, false);
+                    wd = __builtin_amdgcn_cvt_pk_fp8_f32(sacc[kb][4 * j + 2], sacc[kb][4 * j + 3], wd, true);
+                    pb[4 * kk + j] = wd;
+                }
+            }
+#pragma unroll
+            for (int dvb = 0; dvb < NDV; ++dvb) {
+                const u32x4 a0 = *reinterpret_cast<const u32x4*>(Vt + TileSwz<64>::off(32 * dvb + r, 4 * g + h));
+                const u32x4 a1 = *reinterpret_cast<const u32x4*>(Vt + TileSwz<64>::off(32 * dvb + r, 4 * g + 2 + h));
+                const i32x8_t va = {(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], (int)a1[0], (int)a1[1], (int)a1[2], (int)a1[3]};
+                oacc[dvb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(va, pb, oacc[dvb], 0, 0, 0, 127, 0, 127);
+            }
+        }
+        l_run += rs;
+        dma_wait_all();
+        __syncthreads();
+    }
+    for (int t = ntiles_w; t < ntiles; ++t) {
+        if (t + 1 < ntiles) stage((t & 1) ^ 1, t + 1);
+        dma_wait_all();
+        __syncthreads();
+    }
+
+    const float l_tot = l_run + wave_half_swap(l_run);
+    const bool dead = l_tot == 0.f;                      // no visible key: o = 0, lse = -inf (a NaN l is not dead: it propagates)
+    const float inv = vd * (1.f / l_tot);                // v_descale once, with 1 / l
+    u32x2 vals[NDV * 4];
+#pragma unroll
+    for (int dvb = 0; dvb < NDV; ++dvb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            float y[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) y[j] = dead ? 0.f : oacc[dvb][4 * g + j] * inv;
+            vals[4 * dvb + g][0] = pack2_rn<Tag>(y[0], y[1]);
+            vals[4 * dvb + g][1] = pack2_rn<Tag>(y[2], y[3]);
+        }
+    // the sequence's rows of o (total_q, H_q, 128) and of lse (H_q, total_q): rows >= nq are not stored
+    store_rows_via_lds<D, true>(smem + w * 32 * D * 2, vals, a.o + (size_t)qs * a.o_ts + (size_t)hd * a.o_hs, q0 + 32 * w, nq, lane, D, -1,
+                                a.o_ts);
+    if (qrow < nq && h == 0) a.lse[(size_t)hd * a.total_q + qs + qrow] = dead ? -INFINITY : (m_run + log2f(l_tot)) * 0.6931471805599453f;
+}
+
+int64_t fp8in_varlen_tiles_per_head(const Fp8InVarArgs& c) {
+    if (c.page_size > 0) return c.batch * ((std::min(c.max_k, c.max_blocks * c.page_size) + 127) / 128);   // (0: the packed form)
+    return c.total_k / 128 + c.batch;
+}
+
+size_t fp8in_varlen_workspace_bytes(const Fp8InVarArgs& c) {
+    return (size_t)c.heads_kv * (size_t)fp8in_varlen_tiles_per_head(c) * 128 * 128 + 256;   // V^T tiles and a pad
+}
+
+template <bool PAGED> static hipError_t launch_fp8_inputs_varlen_t(const Fp8InVarArgs& c, hipStream_t st) {
+    const int64_t cap = PAGED ? std::min(c.max_k, c.max_blocks * c.page_size) : c.max_k;
+    if (c.max_q == 0) return hipSuccess;                 // no sequence has a query: nothing is written
+    const int nbmax = (int)((cap + 63) / 64), nqt = (int)((c.max_q + 255) / 256);
+    const int nt_head = (int)fp8in_varlen_tiles_per_head(c), nt_seq = (int)((cap + 127) / 128);
+    ExPage pg{};
+    if (PAGED) {
+        pg.table = c.block_table; pg.kps = c.k_ps; pg.vps = c.v_ps;
+        pg.max_blocks = (int)c.max_blocks; pg.num_blocks = (int)c.num_blocks; pg.ps = (int)c.page_size;
+        pg.ps16m = kv_magic((int)(c.page_size / 16));
+    }
+    if (nbmax > 0) {
+        ProfScope ps(K_FP8IN_VT_VARLEN, st);
+        hipLaunchKernelGGL(fp8in_vt_varlen_kernel<PAGED>, dim3((unsigned)(c.batch * c.heads_kv * nbmax)), dim3(256), 0, st,
+                           (const uint8_t*)c.v, (uint8_t*)c.workspace, c.cu_k, (int)c.total_k, (int)cap, nbmax, nt_head, nt_seq,
+                           (int)c.heads_kv, (long long)c.v_hs, (long long)c.v_ts, pg);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    Fp8InVarKernelArgs a;
+    a.q = (const uint8_t*)c.q; a.k = (const uint8_t*)c.k; a.v8t = (const uint8_t*)c.workspace;
+    a.o = (uint16_t*)c.o; a.lse = c.lse;
+    a.qds = c.q_descale; a.kds = c.k_descale; a.vds = c.v_descale;
+    a.qds_bs = (int)c.qds_bs; a.kds_bs = (int)c.kds_bs; a.vds_bs = (int)c.vds_bs;
+    a.cu_q = c.cu_q; a.cu_k = c.cu_k;
+    a.total_q = (int)c.total_q; a.total_k = (int)c.total_k; a.max_q = (int)c.max_q; a.max_k = (int)cap;
+    a.hq = (int)c.heads_q; a.hkv = (int)c.heads_kv; a.group = (int)(c.heads_q / c.heads_kv);
+    a.nqt = nqt; a.nt_head = nt_head; a.nt_seq = nt_seq;
+    a.q_ts = (int)c.q_ts; a.k_ts = (int)c.k_ts; a.o_ts = (int)(c.heads_q * 128);
+    a.q_hs = c.q_hs; a.k_hs = c.k_hs; a.o_hs = 128;
+    a.pg = pg;
+    a.c_log2 = c.scale * 1.4426950408889634f;
+    const size_t smem = 2 * 2 * 128 * 128;
+    const unsigned grid = (unsigned)(c.batch * c.heads_q * nqt);
+    ProfScope ps(K_FP8IN_FWD_VARLEN, st);
+    auto launch = [&](auto kern) -> hipError_t {
+        hipError_t e2 = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
+        if (e2 != hipSuccess) return e2;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, st, a);
+        return hipGetLastError();
+    };
+    if (c.dtype == 2)
+        return c.causal ? launch(fwd_fp8in_varlen_kernel<bf16_tag, true, PAGED>) : launch(fwd_fp8in_varlen_kernel<bf16_tag, false, PAGED>);
+    return c.causal ? launch(fwd_fp8in_varlen_kernel<f16_tag, true, PAGED>) : launch(fwd_fp8in_varlen_kernel<f16_tag, false, PAGED>);
+}
+
+hipError_t launch_fp8_inputs_varlen(const Fp8InVarArgs& c, hipStream_t st) {
+    return c.block_table ? launch_fp8_inputs_varlen_t<true>(c, st) : launch_fp8_inputs_varlen_t<false>(c, st);
 }
 
 }  // namespace fa

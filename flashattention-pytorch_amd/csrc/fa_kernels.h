@@ -42,7 +42,8 @@ struct BwdArgs {
 // Optional per-kernel timing with HIP events recorded on the launch stream (used by bench.py for the
 // roofline figure; off by default, costs nothing when off).
 enum KernelId { K_FWD_F32 = 0, K_BWD_DELTA, K_BWD_DKDV_F32, K_BWD_DQ_F32, K_FWD_MFMA, K_BWD_MFMA, K_BWD_DQ_CVT, K_BWD_DQ_MFMA,
-                K_FP8_QUANT, K_FWD_FP8, K_EX_FWD, K_EX_BWD, K_KV_GROUP_SUM, K_FP8IN_VT, K_FP8IN_FWD, K_COUNT };
+                K_FP8_QUANT, K_FWD_FP8, K_EX_FWD, K_EX_BWD, K_KV_GROUP_SUM, K_FP8IN_VT, K_FP8IN_FWD, K_FP8IN_VT_VARLEN,
+                K_FP8IN_FWD_VARLEN, K_COUNT };
 void prof_begin(int id, hipStream_t st);
 void prof_end(int id, hipStream_t st);
 struct ProfScope {
@@ -385,5 +386,27 @@ struct Fp8InArgs {
 };
 size_t fp8in_workspace_bytes(int64_t units_kv, int64_t nk);
 hipError_t launch_fp8_inputs(const Fp8InArgs& a, hipStream_t st);
+
+// The packed and the paged form (fa_fp8_forward_varlen): q (total_q, heads_q, 128) and o, lse as the varlen calls lay them out;
+// k, v (total_k, heads_kv, 128), or with block_table the pools (num_blocks, page_size, heads_kv, 128).  Strides in bytes.
+struct Fp8InVarArgs {
+    const void *q = nullptr, *k = nullptr, *v = nullptr;
+    void* o = nullptr;                                      // (total_q, heads_q, 128) contiguous
+    float* lse = nullptr;                                   // (heads_q, total_q) contiguous
+    const float *q_descale = nullptr, *k_descale = nullptr, *v_descale = nullptr;   // (batch, heads_kv) device floats; null: 1
+    int64_t qds_bs = 0, kds_bs = 0, vds_bs = 0;
+    const int *cu_q = nullptr, *cu_k = nullptr;             // [batch + 1] untrusted device offsets
+    const int* block_table = nullptr;                       // (batch, max_blocks) untrusted page numbers; null: the packed form
+    int64_t batch = 0, heads_q = 0, heads_kv = 0, total_q = 0, total_k = 0, max_q = 0, max_k = 0;
+    int dtype = 0;                                          // of o: FA_DTYPE_F16 / FA_DTYPE_BF16
+    int64_t q_ts = 0, q_hs = 0, k_ts = 0, k_hs = 0, v_ts = 0, v_hs = 0;
+    int64_t max_blocks = 0, num_blocks = 0, page_size = 0, k_ps = 0, v_ps = 0;   // the pools: page strides
+    int causal = 0;
+    float scale = 0.f;
+    void* workspace = nullptr;                              // fp8in_varlen_workspace_bytes
+};
+// from batch, heads_kv, total_k (packed: page_size == 0) or max_k, max_blocks, page_size (paged) alone
+size_t fp8in_varlen_workspace_bytes(const Fp8InVarArgs& a);
+hipError_t launch_fp8_inputs_varlen(const Fp8InVarArgs& a, hipStream_t st);
 
 }  // namespace fa

@@ -56,6 +56,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_ex_forward_vdim", "fa_ex_backward_vdim", "fa_ex_forward_varlen_vdim", "fa_ex_backward_varlen_vdim",
     "fa_ex_forward_bias", "fa_ex_backward_bias", "fa_ex_backward_workspace_bytes_bias",
     "fa_fp8_forward", "fa_fp8_forward_workspace_bytes",
+    "fa_fp8_forward_varlen", "fa_fp8_forward_varlen_workspace_bytes",
 )
 
 
@@ -198,6 +199,13 @@ _sig("fa_fp8_forward", _fields("p:q,k,v,o,lse,q_descale,k_descale,v_descale i:ba
                                "v_head_stride,v_token_stride,o_batch_stride,o_head_stride,o_token_stride,q_descale_batch_stride,"
                                "k_descale_batch_stride,v_descale_batch_stride c:causal d:softmax_scale") + _WS)
 _sig("fa_fp8_forward_workspace_bytes", _fields("i:batch,heads_kv,seqlen_k,d"), _SIZE)
+_sig("fa_fp8_forward_varlen", _fields(
+    "p:q,k,v,o,lse,q_descale,k_descale,v_descale,cu_seqlens_q,cu_seqlens_k,block_table "
+    "i:batch,heads_q,heads_kv,total_q,total_k,max_seqlen_q,max_seqlen_k,d c:dtype "
+    "i:q_token_stride,q_head_stride,k_token_stride,k_head_stride,v_token_stride,v_head_stride,max_blocks_per_seq,num_blocks,"
+    "page_block_size,k_page_stride,v_page_stride,q_descale_batch_stride,k_descale_batch_stride,v_descale_batch_stride "
+    "c:causal d:softmax_scale") + _WS)
+_sig("fa_fp8_forward_varlen_workspace_bytes", _fields("i:batch,heads_kv,total_k,max_seqlen_k,max_blocks_per_seq,page_block_size,d"), _SIZE)
 _KVWSV = _fields("i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,d,num_splits c:with_sinks")
 _sig("fa_ex_kvcache_workspace_bytes_varlen", _KVWSV, _SIZE)
 _sig("fa_ex_kvcache_workspace_bytes_qv", _KVWSV + _fields("i:d_v"), _SIZE)
@@ -250,6 +258,7 @@ _family("fa_mla_sparse_forward", [])
 _family("fa_mla_fp8_forward", [])
 _family("fa_mla_fp8_pack", [])
 _family("fa_fp8_forward", [])
+_family("fa_fp8_forward_varlen", [])
 _family("fa_ex_forward_kvcache_qv", ["fa_ex_forward_kvcache" + _suffix for _suffix in ("", "_paged", "_rotary", "_fp8", "_sink", "_varlen")])
 
 
@@ -1887,5 +1896,107 @@ def fp8_forward(q, k, v, causal, softmax_scale, q_descale=None, k_descale=None, 
         _call("fa_fp8_forward", (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp, b, hq, hkv, nq, nk,
                                  128, _DTYPE_CODE[out_dtype], *sq, *sk, *sv, *so, qds, kds, vds, int(bool(causal)), scale, ws.data_ptr(),
                                  ws.numel(), _stream_ptr(q.device)))
+    del keep_q, keep_k, keep_v
+    return o, lse
+
+
+def _fp8_rows(who, name, t, heads):
+    """(token stride, head stride) in bytes of an e4m3 (.., heads, 128) tensor's last three dims; ValueError on a view the kernels
+    cannot address without a copy"""
+    if t.stride(-1) != 1:
+        raise ValueError(f"{who}: {name} must have a contiguous last dim (a view that would need a copy)")
+    n = t.shape[-3]
+    ts = t.stride(-3) if n > 1 else max(t.stride(-3), 128)
+    hs = t.stride(-2) if heads > 1 else 0
+    if t.numel() and (t.data_ptr() % 16 != 0 or ts % 16 != 0 or hs % 16 != 0 or ts < 128 or hs < 0):
+        raise ValueError(f"{who}: {name} is a view the kernel cannot address: a 16-byte aligned start and non-negative strides that are "
+                         f"multiples of 16 bytes are needed (token stride {ts}, head stride {hs})")
+    return ts, hs
+
+
+def fp8_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, q_descale=None,
+                       k_descale=None, v_descale=None, out_dtype=torch.bfloat16, block_table=None):
+    """(o, lse) of the packed / paged fp8 call (fa_fp8_forward_varlen): q (total_q, H_q, 128) in torch.float8_e4m3fn at its own token
+    and head strides; k and v (total_k, H_kv, 128) e4m3, or with block_table (int32 (B, max_blocks_per_seq)) the pools
+    (num_blocks, ps, H_kv, 128) at their own page and token strides; nothing is copied.  cu_seqlens_* int32 (B + 1,) on the device;
+    descales float32 (B, H_kv) or (H_kv,), None = 1.  o (total_q, H_q, 128) in out_dtype, lse float32 (H_q, total_q); rows no
+    sequence owns hold unspecified values.  Nothing is read on the host; the V^T workspace is the shim's persistent one."""
+    who = "fp8_varlen_forward"
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float8_e4m3fn:
+            dt = t.dtype if isinstance(t, torch.Tensor) else type(t).__name__
+            raise NotImplementedError(f"{who}: {name} of dtype {dt} is not supported (torch.float8_e4m3fn expected; 16-bit tensors go to "
+                                      f"flash_attention_varlen)")
+    if out_dtype not in (torch.bfloat16, torch.float16):
+        raise NotImplementedError(f"{who}: out_dtype {out_dtype} is not supported (torch.bfloat16 or torch.float16)")
+    paged = block_table is not None
+    if paged and not (isinstance(block_table, torch.Tensor) and block_table.dtype == torch.int32):
+        dt = block_table.dtype if isinstance(block_table, torch.Tensor) else type(block_table).__name__
+        raise NotImplementedError(f"{who}: block_table of dtype {dt} is not supported (int32 tensor expected)")
+    kdim = 4 if paged else 3
+    if q.dim() != 3 or k.dim() != kdim or v.shape != k.shape:
+        raise RuntimeError(f"{who}: q must be (total_q, H_q, 128) and k, v " +
+                           ("pools (num_blocks, page_block_size, H_kv, 128)" if paged else "(total_k, H_kv, 128)") +
+                           f"; got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.shape[-1] != 128:
+            raise NotImplementedError(f"{who}: head_dim {t.shape[-1]} is not supported (128 only); got {name} of shape {tuple(t.shape)}")
+    tensors = (q, k, v, cu_seqlens_q, cu_seqlens_k) + ((block_table,) if paged else ())
+    for t in tensors:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{who}: tensors must be on the GPU (HIP device); there is no CPU path")
+    if len({t.device for t in tensors}) != 1:
+        raise RuntimeError(f"{who}: all tensors must be on one device")
+    for name, c in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if c.dtype != torch.int32 or c.dim() != 1 or c.shape[0] < 2:
+            raise RuntimeError(f"{who}: {name} must be a 1-D int32 tensor of batch + 1 >= 2 offsets")
+    if cu_seqlens_q.shape != cu_seqlens_k.shape:
+        raise RuntimeError(f"{who}: cu_seqlens_q and cu_seqlens_k must have the same length (batch + 1)")
+    b = cu_seqlens_q.shape[0] - 1
+    total_q, hq = q.shape[0], q.shape[1]
+    hkv = k.shape[-2]
+    if hkv == 0 or hq == 0 or hq % hkv != 0:
+        raise RuntimeError(f"{who}: H_q = {hq} must be a multiple of H_kv = {hkv}")
+    mq, mk = operator.index(max_seqlen_q), operator.index(max_seqlen_k)
+    if mq < 0 or mk < 0:
+        raise RuntimeError(f"{who}: max_seqlen_q, max_seqlen_k must be >= 0")
+    scale = 128 ** -0.5 if softmax_scale is None else float(softmax_scale)
+    if not (math.isfinite(scale) and scale > 0.0):
+        raise RuntimeError(f"{who}: softmax_scale must be finite and > 0 (got {scale})")
+    qts, qhs = _fp8_rows(who, "q", q, hq)
+    kts, khs = _fp8_rows(who, "k", k, hkv)
+    vts, vhs = _fp8_rows(who, "v", v, hkv)
+    if paged:
+        nblk, ps = k.shape[0], k.shape[1]
+        if ps < 16 or ps % 16 != 0:
+            raise RuntimeError(f"{who}: page_block_size must be a positive multiple of 16, got {ps}")
+        if block_table.dim() != 2 or block_table.shape[0] != b:
+            raise RuntimeError(f"{who}: block_table must be an int32 (batch, max_blocks_per_seq) tensor, batch = {b}; got "
+                               f"{tuple(block_table.shape)}")
+        if nblk < 1:
+            raise RuntimeError(f"{who}: the pools must hold at least one page")
+        block_table = block_table.contiguous()
+        mblk = block_table.shape[1]
+        kps, vps = (t.stride(0) if nblk > 1 else max(t.stride(0), 0) for t in (k, v))
+        if kps % 16 != 0 or vps % 16 != 0 or kps < 0 or vps < 0:
+            raise ValueError(f"{who}: the page strides of k, v ({kps}, {vps}) must be non-negative multiples of 16 bytes")
+        total_k, pages = 0, (mblk, nblk, ps, kps, vps)
+    else:
+        total_k, mblk, ps, pages = k.shape[0], 0, 0, (0, 0, 0, 0, 0)
+    cu_q, cu_k = cu_seqlens_q.contiguous(), cu_seqlens_k.contiguous()
+    qdp, qds, keep_q = _kv_descale(who, "q_descale", q_descale, q, b, hkv)
+    kdp, kds, keep_k = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
+    vdp, vds, keep_v = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
+    with torch.cuda.device(q.device):
+        o = torch.empty((total_q, hq, 128), dtype=out_dtype, device=q.device)
+        lse = torch.empty((hq, total_q), dtype=torch.float32, device=q.device)
+        if total_q == 0:
+            return o, lse
+        need = int(_lib.fa_fp8_forward_varlen_workspace_bytes(b, hkv, total_k, mk, mblk, ps, 128))
+        ws = _workspace(q.device, need)
+        _call("fa_fp8_forward_varlen", (
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp, cu_q.data_ptr(), cu_k.data_ptr(),
+            block_table.data_ptr() if paged else 0, b, hq, hkv, total_q, total_k, mq, mk, 128, _DTYPE_CODE[out_dtype], qts, qhs, kts, khs,
+            vts, vhs, *pages, qds, kds, vds, int(bool(causal)), scale, ws.data_ptr(), ws.numel(), _stream_ptr(q.device)))
     del keep_q, keep_k, keep_v
     return o, lse

@@ -1056,6 +1056,51 @@ int fa_fp8_forward(const void* q, const void* k, const void* v, void* o, float* 
                    double softmax_scale, void* workspace, size_t workspace_bytes, void* stream);
 size_t fa_fp8_forward_workspace_bytes(int64_t batch, int64_t heads_kv, int64_t seqlen_k, int64_t d);
 
+/* --- The packed and the paged form of the fp8 call (FlashAttention-3's flash_attn_varlen_func with q_descale / k_descale /
+ * v_descale).  Forward only; a call family of its own.  Every sequence gets the bits of fa_fp8_forward on that sequence alone.
+ * q is (total_q, heads_q, 128) raw e4m3 bytes packed by cu_seqlens_q (batch + 1 int32 device offsets), at its token and head
+ * strides (a slice of a fused projection needs no copy).  Without block_table (NULL: the packed form) k and v are
+ * (total_k, heads_kv, 128) packed by cu_seqlens_k, and max_blocks_per_seq, num_blocks, page_block_size and both page strides are 0.
+ * With block_table, an int32 (batch, max_blocks_per_seq) device tensor, k and v are pools (num_blocks, page_block_size, heads_kv,
+ * 128) with their own page and token strides; key t of sequence b is row t % page_block_size of page
+ * block_table[b][t / page_block_size], and len_k[b] = cu_seqlens_k[b + 1] - cu_seqlens_k[b] clamped on the device to
+ * [0, min(max_seqlen_k, max_blocks_per_seq * page_block_size)] (total_k is not used).  All strides are in bytes.
+ * Descales as in fa_fp8_forward, (batch, heads_kv) with batch the number of sequences.  Query head h reads K/V head
+ * h / (heads_q / heads_kv).  The causal diagonal is bottom-right aligned per sequence: j <= i + len_k[b] - len_q[b].
+ * o is (total_q, heads_q, 128) contiguous in `dtype` (f16 / bf16), lse float32 (heads_q, total_q) contiguous, natural log.  A row
+ * without a visible key (an empty key sequence, a causal row above the diagonal) gives o = 0, lse = -inf; rows of o and lse that
+ * belong to no sequence are not written.
+ * Nothing is read on the host: no synchronisation, and a captured call replays after the offsets, the table and the descale values
+ * changed in place.  Offsets and table are untrusted: starts are clamped to [0, total], lengths to [0, max_seqlen_*]; a page
+ * outside [0, num_blocks) reads as zero bytes for K and V; no table entry past ceil(len_k / page_block_size) is read; page offsets
+ * are 64-bit and pages may be shared.
+ * Span limits (FA_ERR_UNSUPPORTED, "span limit"): round_up(max_seqlen_q, 256) * q_token_stride below 2^31; packed,
+ * round_up(max_seqlen_k, 256) * k_token_stride below 2^31; paged, page_block_size * token stride below 2^31 for both pools and
+ * min(max_seqlen_k, max_blocks_per_seq * page_block_size) below 2^24.  Sequence, head and page offsets are 64-bit.
+ * Workspace: the caller's, fa_fp8_forward_varlen_workspace_bytes(...) bytes, a function of host-known sizes only: V^T tiles of
+ * 16384 bytes, heads_kv * (total_k / 128 + batch) of them packed (sequence b's start at tile cu_seqlens_k[b] / 128 + b of its
+ * head), heads_kv * batch * ceil(min(max_seqlen_k, max_blocks_per_seq * page_block_size) / 128) paged (page_block_size > 0 selects
+ * that form; sequence b's start at b * ceil(.. / 128)), plus 256; 0 for arguments the call would refuse.  Two launches on `stream`.
+ * Checked before any HIP call, the first broken rule named in fa_last_error(), in this order: (1) q, k, v, o, lse, cu_seqlens_q,
+ * cu_seqlens_k non-null; (2) batch, heads_q, heads_kv, d > 0, total_q, total_k, max_seqlen_q, max_seqlen_k in [0, 2^31); (3) d ==
+ * 128, else FA_ERR_UNSUPPORTED; (4) heads_q % heads_kv == 0; (5) dtype f16 or bf16, softmax_scale finite and > 0; (6) with
+ * block_table page_block_size a multiple of 16 in [16, 65536], num_blocks in [1, 2^31), batch * max_blocks_per_seq in [0, 2^31),
+ * without it the five page arguments 0; (7) a descale stride 0 or >= heads_kv (0 with a NULL descale), descales 4-byte aligned; (8) q,
+ * k, v, o 16-byte aligned, lse, offsets and table 4-byte aligned, every stride >= 0 and a multiple of 16 bytes, token strides >= 128;
+ * (9) the span limits, and batch * heads * tiles below 2^31 (FA_ERR_UNSUPPORTED); (10) workspace non-null with workspace_bytes >=
+ * the need (FA_ERR_WORKSPACE), 16-byte aligned.  Everything else is FA_ERR_INVALID_ARGUMENT. */
+int fa_fp8_forward_varlen(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale,
+                          const float* k_descale, const float* v_descale, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k,
+                          const int32_t* block_table, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
+                          int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_token_stride,
+                          int64_t q_head_stride, int64_t k_token_stride, int64_t k_head_stride, int64_t v_token_stride,
+                          int64_t v_head_stride, int64_t max_blocks_per_seq, int64_t num_blocks, int64_t page_block_size,
+                          int64_t k_page_stride, int64_t v_page_stride, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
+                          int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace, size_t workspace_bytes,
+                          void* stream);
+size_t fa_fp8_forward_varlen_workspace_bytes(int64_t batch, int64_t heads_kv, int64_t total_k, int64_t max_seqlen_k,
+                                             int64_t max_blocks_per_seq, int64_t page_block_size, int64_t d);
+
 /* --- support entry points (no reference counterpart: the reference allocates inside the callee) --- */
 /* bytes for the CURRENT kernel mode: two float row constants per query row (+ an fp32 dQ scratch of bh*n*d floats in
  * FA_MODE_BWD_ATOMIC only); ask again after changing the mode */

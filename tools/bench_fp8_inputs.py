@@ -5,7 +5,10 @@ per (batch, K/V head)).  HIP-event kernel times per call from the library's prof
 rows: GQA (H_q = 32, H_kv = 8, N = 8192), chunked prefill (Nq = 2048, Nk = 16384, causal) against the bf16 extended forward, and the
 V transposer's time over its byte floor (2 * units * Nk * 128 bytes at the 8 TB/s HBM peak).
 `--accuracy`: max |o - fp64| over the sweep of tests/fp8_inputs_cases.py, rows seeing < 256 keys and the rest, beside the 16-bit
-extended forward on the dequantised tensors, and the kernel / baseline error ratio of every case."""
+extended forward on the dequantised tensors, and the kernel / baseline error ratio of every case.
+`--varlen`: the packed and the paged form (flash_attention_fp8_varlen / fa_fp8_forward_varlen, section 9y) — uniform lengths against
+the padded call on the same tokens with that call's round-to-round spread, chunked prefill over an e4m3 paged cache against the
+widening 16-bit call of section 9n, and a ragged batch against the uniform one of the same total."""
 import argparse
 import json
 import os
@@ -21,6 +24,7 @@ import flashattention_lab_cuda as ext  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--accuracy", action="store_true")
+ap.add_argument("--varlen", action="store_true", help="the packed and the paged form (flash_attention_fp8_varlen, DESIGN.md section 9y)")
 args = ap.parse_args()
 D, CALLS, HBM_PEAK = 128, 10, 8.0e12
 E4M3 = torch.float8_e4m3fn
@@ -141,6 +145,107 @@ def accuracy_rows():
     return {"max_abs_err_vs_fp64": worst, "kernel_over_baseline": ratios}
 
 
-out = accuracy_rows() if args.accuracy else time_rows()
+def varlen_problem(lens_q, lens_k, hq, hkv, seed):
+    """packed e4m3 q, k, v of the sequences, their offsets and (B, H_kv) descales"""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    mk = lambda n, h: torch.randn((n, h, D), device="cuda", dtype=torch.bfloat16, generator=g).to(E4M3)   # noqa: E731
+    q, k, v = mk(sum(lens_q), hq), mk(sum(lens_k), hkv), mk(sum(lens_k), hkv)
+    cu = lambda lens: torch.tensor([0] + torch.tensor(lens).cumsum(0).tolist(), dtype=torch.int32, device="cuda")   # noqa: E731
+    ds = [torch.full((len(lens_q), hkv), x, dtype=torch.float32, device="cuda") for x in (0.5, 0.75, 1.25)]
+    return q, k, v, cu(lens_q), cu(lens_k), ds
+
+
+def paged_from(k, v, lens_k, ps, seed):
+    """the pools (num_blocks, ps, H_kv, d) and a shuffled table that hold the packed tokens"""
+    need = [(n + ps - 1) // ps for n in lens_k]
+    nblk, mblk = sum(need), max(need)
+    perm = torch.randperm(nblk, generator=torch.Generator().manual_seed(seed))
+    table = torch.zeros((len(lens_k), mblk), dtype=torch.int32)
+    pk, pv = (torch.zeros((nblk, ps) + tuple(t.shape[1:]), dtype=torch.uint8, device="cuda") for t in (k, v))
+    start, used = 0, 0
+    for b, n in enumerate(lens_k):
+        pages = perm[used:used + need[b]]
+        table[b, :need[b]] = pages.to(torch.int32)
+        for src, pool in ((k, pk), (v, pv)):
+            pad = torch.zeros((need[b] * ps,) + tuple(src.shape[1:]), dtype=torch.uint8, device="cuda")
+            pad[:n] = src[start:start + n].view(torch.uint8)
+            pool[pages.cuda()] = pad.reshape(need[b], ps, *src.shape[1:])
+        start, used = start + n, used + need[b]
+    return pk.view(E4M3), pv.view(E4M3), table.cuda()
+
+
+def varlen_flops(lens_q, lens_k, hq, causal):
+    return sum(flops(1, hq, a, b, causal) for a, b in zip(lens_q, lens_k))
+
+
+def varlen_rows():
+    """the packed and the paged call against the padded call on the same tokens (uniform lengths), against the widening 16-bit prefill
+    over an e4m3 paged cache (chunked prefill), and a ragged batch against the uniform one of the same total"""
+    res = {}
+
+    def uniform(b, h, n, causal, seed):
+        lens = [n] * b
+        q, k, v, cu_q, cu_k, ds = varlen_problem(lens, lens, h, h, seed)
+        qp, kp, vp = (t.reshape(b, n, h, D) for t in (q, k, v))
+        variants = {
+            "padded": lambda: ext.fp8_forward(qp, kp, vp, causal, D ** -0.5, *ds, torch.bfloat16, "bnhd"),
+            "packed": lambda: ext.fp8_varlen_forward(q, k, v, cu_q, cu_k, n, n, causal, D ** -0.5, *ds),
+        }
+        for ps in (16, 256):
+            pk, pv, table = paged_from(k, v, lens, ps, seed)
+            variants[f"paged_ps{ps}"] = (lambda pk=pk, pv=pv, table=table:
+                                         ext.fp8_varlen_forward(q, pk, pv, cu_q, cu_k, n, n, causal, D ** -0.5, *ds, block_table=table))
+        r = interleave(variants)
+        base = r["padded"]
+        for name, x in r.items():
+            x["tflops"] = varlen_flops(lens, lens, h, causal) / x["median_ms"] / 1e9
+            x["over_padded"] = x["median_ms"] / base["median_ms"]
+        r["padded_spread"] = (base["max_ms"] - base["min_ms"]) / base["median_ms"]
+        return r
+
+    for n in (16384, 8192):
+        for causal in (False, True):
+            res[f"uniform_b2_h8_n{n}_{'causal' if causal else 'full'}"] = uniform(2, 8, n, causal, n + causal)
+    # chunked prefill: 2048 new queries against 16384 cached keys, GQA 32 / 8, an e4m3 paged cache
+    hq, hkv, nq, nk, ps = 32, 8, 2048, 16384, 256
+    q, k, v, cu_q, cu_k, ds = varlen_problem([nq], [nk], hq, hkv, 5)
+    pk, pv, table = paged_from(k, v, [nk], ps, 5)
+    q16 = q.to(torch.bfloat16)
+    r = interleave({
+        "bf16_widening": lambda: ext.ex_varlen_forward(q16, pk, pv, cu_q, cu_k, nq, nk, True, D ** -0.5, block_table=table, k_descale=ds[1],
+                                                       v_descale=ds[2]),
+        "fp8_paged": lambda: ext.fp8_varlen_forward(q, pk, pv, cu_q, cu_k, nq, nk, True, D ** -0.5, *ds, block_table=table),
+    })
+    for x in r.values():
+        x["tflops"] = flops(1, hq, nq, nk, True) / x["median_ms"] / 1e9
+    r["speedup"] = r["bf16_widening"]["median_ms"] / r["fp8_paged"]["median_ms"]
+    res["chunked_prefill_2048_16384_causal_gqa_32_8_ps256"] = r
+    # a ragged batch: 8 sequences, the total of 8 x 4096, lengths drawn once
+    b, h, n = 8, 2, 4096
+    cuts = sorted(torch.randint(1, b * n // 64, (b - 1,), generator=torch.Generator().manual_seed(11)).mul(64).tolist())
+    ragged = [hi - lo for lo, hi in zip([0] + cuts, cuts + [b * n])]
+    for causal in (False, True):
+        row = {}
+        for name, lens in (("uniform", [n] * b), ("ragged", ragged)):
+            q, k, v, cu_q, cu_k, ds = varlen_problem(lens, lens, h, h, 9)
+            pk, pv, table = paged_from(k, v, lens, 256, 9)
+            m = max(lens)
+            row[name] = (lens, {
+                f"{name}_packed": lambda q=q, k=k, v=v, cu_q=cu_q, cu_k=cu_k, ds=ds, m=m: ext.fp8_varlen_forward(q, k, v, cu_q, cu_k, m, m, causal, D ** -0.5, *ds),
+                f"{name}_paged_ps256": lambda q=q, pk=pk, pv=pv, cu_q=cu_q, cu_k=cu_k, ds=ds, m=m, table=table:
+                    ext.fp8_varlen_forward(q, pk, pv, cu_q, cu_k, m, m, causal, D ** -0.5, *ds, block_table=table),
+            })
+        r = interleave({**row["uniform"][1], **row["ragged"][1]})
+        for name, x in r.items():
+            lens = row[name.split("_")[0]][0]
+            x["tflops"] = varlen_flops(lens, lens, h, causal) / x["median_ms"] / 1e9
+            x["grid_tiles"] = b * h * ((max(lens) + 255) // 256)
+            x["live_tiles"] = h * sum((n_ + 255) // 256 for n_ in lens)
+        r["lengths"] = ragged
+        res[f"ragged_b8_h2_total{b * n}_{'causal' if causal else 'full'}"] = r
+    return res
+
+
+out = accuracy_rows() if args.accuracy else varlen_rows() if args.varlen else time_rows()
 print(json.dumps({"config": f"d={D}, median of {args.rounds} interleaved rounds x {CALLS} calls" if not args.accuracy else "sweep of tests/fp8_inputs_cases.py",
                   "results": out}, indent=1))
