@@ -30,7 +30,8 @@ std::vector<hipEvent_t> g_prof_free;
 hipEvent_t g_prof_open[fa::K_COUNT];
 const char* const kKernelNames[fa::K_COUNT] = {"fwd_f32", "bwd_delta", "bwd_dkdv_f32", "bwd_dq_f32", "fwd_mfma",
                                                "bwd_mfma", "bwd_dq_cvt", "bwd_dq_mfma", "fp8_quant", "fwd_fp8", "ex_fwd", "ex_bwd", "kv_group_sum",
-                                               "fp8in_vt", "fp8in_fwd", "fp8in_vt_varlen", "fp8in_fwd_varlen"};
+                                               "fp8in_vt", "fp8in_fwd", "fp8in_vt_varlen", "fp8in_fwd_varlen", "idx_pack", "idx_logits",
+                                               "idx_topk"};
 
 hipEvent_t prof_get_event() {
     if (!g_prof_free.empty()) { hipEvent_t e = g_prof_free.back(); g_prof_free.pop_back(); return e; }
@@ -2227,6 +2228,222 @@ int fa_mla_fp8_pack(const void* latent_new, const void* rope_new, void* kv_cache
     a.table_row_stride = block_table_row_stride; a.num_blocks = num_blocks; a.page_size = page_block_size; a.max_blocks = max_blocks_per_seq;
     a.scale_pow2 = scale_pow2;
     return launched(who, fa::launch_mla_f8_pack(a, reinterpret_cast<hipStream_t>(stream)));
+}
+
+// ---- the lightning indexer (fa_indexer_pack, fa_indexer_logits, fa_indexer_topk): see include/fa_mi355x.h.  One record a call, a
+// field per argument under its name in the header.
+static const int64_t kIdxTokenBytes = 132;
+
+// the rules of an index-key pool's geometry that the append and the logits share: the two byte strides, then the address
+static int indexer_pool_ok(const char* who, const void* pool, int64_t page_stride_bytes, int64_t token_stride_bytes, int64_t page_block_size) {
+    if (token_stride_bytes < kIdxTokenBytes || token_stride_bytes % 16 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: token_stride_bytes must be >= 132 and a multiple of 16 (got %lld)", who,
+                    (long long)token_stride_bytes);
+    if (token_stride_bytes >= ((int64_t)1 << 31))
+        return fail(FA_ERR_UNSUPPORTED, "%s: token_stride_bytes = %lld is beyond 32-bit offsets", who, (long long)token_stride_bytes);
+    const int64_t span = (page_block_size > 0 ? page_block_size - 1 : 0) * token_stride_bytes + kIdxTokenBytes;
+    if (page_stride_bytes < span || page_stride_bytes % 16 != 0 || page_stride_bytes > ((int64_t)1 << 44))
+        return fail(FA_ERR_INVALID_ARGUMENT,
+                    "%s: page_stride_bytes must be >= (page_block_size - 1) * token_stride_bytes + 132 = %lld and a multiple of 16 (got %lld)", who,
+                    (long long)span, (long long)page_stride_bytes);
+    if (!aligned16({pool})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_cache must be 16-byte aligned", who);
+    return FA_OK;
+}
+
+struct IndexerPackCall {
+    const void* k_new = nullptr;
+    void* k_cache = nullptr;
+    const int32_t *cache_seqlens = nullptr, *block_table = nullptr;
+    int64_t batch = 0, seqlen_new = 0, d = 0, k_new_batch_stride = 0, k_new_token_stride = 0, page_stride_bytes = 0, token_stride_bytes = 0,
+            block_table_row_stride = 0, num_blocks = 0, page_block_size = 0, max_blocks_per_seq = 0;
+    int scale_pow2 = 0;
+    void* stream = nullptr;
+};
+
+static int indexer_pack_impl(const char* who, const IndexerPackCall& c) {
+    if (c.batch < 0 || c.seqlen_new < 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch and seqlen_new must be >= 0 (got %lld, %lld)", who, (long long)c.batch,
+                    (long long)c.seqlen_new);
+    if (c.batch == 0 || c.seqlen_new == 0) return FA_OK;   // no token: no launch
+    // (1)
+    if (!c.k_new || !c.k_cache || !c.cache_seqlens || !c.block_table) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    // (2)
+    if (c.d != 128) return fail(FA_ERR_UNSUPPORTED, "%s: supported for head_dim = 128 only (got %lld)", who, (long long)c.d);
+    if (c.batch > 0x7fffffff / c.seqlen_new) return fail(FA_ERR_UNSUPPORTED, "%s: problem too large for one launch", who);
+    // (3)
+    const int64_t span = (c.seqlen_new - 1) * c.k_new_token_stride + c.d;
+    if (c.k_new_token_stride < c.d || (c.batch > 1 && c.k_new_batch_stride < span) || c.k_new_batch_stride < 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of k_new too small (batch %lld, token %lld; need token >= %lld, batch >= %lld)", who,
+                    (long long)c.k_new_batch_stride, (long long)c.k_new_token_stride, (long long)c.d, (long long)span);
+    if (c.k_new_token_stride % 8 != 0 || c.k_new_batch_stride % 8 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of k_new must be multiples of 8 elements", who);
+    if (c.k_new_token_stride > ((int64_t)1 << 31) || c.k_new_batch_stride > ((int64_t)1 << 44))
+        return fail(FA_ERR_UNSUPPORTED, "%s: strides of k_new beyond 2^31 (token) or 2^44 (batch) elements", who);
+    if (int rc = indexer_pool_ok(who, c.k_cache, c.page_stride_bytes, c.token_stride_bytes, c.page_block_size)) return rc;
+    if (!aligned16({c.k_new})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_new must be 16-byte aligned", who);
+    if ((uintptr_t)c.cache_seqlens % 4 != 0 || (uintptr_t)c.block_table % 4 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_seqlens and block_table must be 4-byte aligned", who);
+    // (4)
+    if (int rc = mla_fp8_pages_ok(who, c.block_table_row_stride, c.num_blocks, c.page_block_size, c.max_blocks_per_seq)) return rc;
+    fa::IndexerPackArgs a{};
+    a.k_new = c.k_new; a.pool = c.k_cache; a.cache_seqlens = c.cache_seqlens; a.block_table = c.block_table;
+    a.batch = c.batch; a.seqlen_new = c.seqlen_new; a.k_bs = c.k_new_batch_stride; a.k_ts = c.k_new_token_stride;
+    a.page_sb = c.page_stride_bytes; a.tok_sb = c.token_stride_bytes; a.table_row_stride = c.block_table_row_stride;
+    a.num_blocks = c.num_blocks; a.page_size = c.page_block_size; a.max_blocks = c.max_blocks_per_seq; a.scale_pow2 = c.scale_pow2;
+    return launched(who, fa::launch_indexer_pack(a, reinterpret_cast<hipStream_t>(c.stream)));
+}
+
+int fa_indexer_pack(const void* k_new, void* k_cache, const int32_t* cache_seqlens, const int32_t* block_table, int64_t batch,
+                    int64_t seqlen_new, int64_t d, int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t page_stride_bytes,
+                    int64_t token_stride_bytes, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
+                    int64_t max_blocks_per_seq, int scale_pow2, void* stream) {
+    IndexerPackCall c;
+    c.k_new = k_new; c.k_cache = k_cache; c.cache_seqlens = cache_seqlens; c.block_table = block_table;
+    c.batch = batch; c.seqlen_new = seqlen_new; c.d = d; c.k_new_batch_stride = k_new_batch_stride; c.k_new_token_stride = k_new_token_stride;
+    c.page_stride_bytes = page_stride_bytes; c.token_stride_bytes = token_stride_bytes; c.block_table_row_stride = block_table_row_stride;
+    c.num_blocks = num_blocks; c.page_block_size = page_block_size; c.max_blocks_per_seq = max_blocks_per_seq;
+    c.scale_pow2 = scale_pow2; c.stream = stream;
+    return indexer_pack_impl("fa_indexer_pack", c);
+}
+
+static const int64_t kIdxWidthMax = (int64_t)1 << 28, kIdxTopkMax = (int64_t)1 << 20;
+
+// the rules of a (batch, seqlen_q, width) float32 logits tensor that the logits and the selection share
+static int indexer_logits_ok(const char* who, const void* logits, int64_t batch, int64_t seqlen_q, int64_t width, int64_t bs, int64_t rs) {
+    const int64_t kMax = (int64_t)1 << 44, seq = (seqlen_q - 1) * rs + width;
+    if ((seqlen_q > 1 && rs < width) || rs < 0 || rs > kMax || (batch > 1 && bs < seq) || bs < 0 || bs > kMax)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of logits (batch %lld, row %lld): row >= width = %lld, batch >= %lld (each <= 2^44)", who,
+                    (long long)bs, (long long)rs, (long long)width, (long long)seq);
+    if ((uintptr_t)logits % 4 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: logits must be 4-byte aligned", who);
+    return FA_OK;
+}
+
+struct IndexerLogitsCall {
+    const void *q = nullptr, *k_cache = nullptr;
+    const float* weights = nullptr;
+    const int32_t *cache_seqlens = nullptr, *block_table = nullptr;
+    float* logits = nullptr;
+    int64_t batch = 0, seqlen_q = 0, heads = 0, d = 0, width = 0, q_batch_stride = 0, q_token_stride = 0, q_head_stride = 0,
+            weights_batch_stride = 0, weights_token_stride = 0, logits_batch_stride = 0, logits_row_stride = 0, page_stride_bytes = 0,
+            token_stride_bytes = 0, block_table_row_stride = 0, num_blocks = 0, page_block_size = 0, max_blocks_per_seq = 0;
+    int causal = 0;
+    void* stream = nullptr;
+};
+
+static int indexer_logits_impl(const char* who, const IndexerLogitsCall& c) {
+    if (c.batch < 0 || c.seqlen_q < 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch and seqlen_q must be >= 0 (got %lld, %lld)", who, (long long)c.batch, (long long)c.seqlen_q);
+    if (c.batch == 0 || c.seqlen_q == 0) return FA_OK;   // no row: no launch
+    // (1)
+    if (!c.q || !c.weights || !c.k_cache || !c.cache_seqlens || !c.block_table || !c.logits)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    // (2)
+    if (c.d != 128) return fail(FA_ERR_UNSUPPORTED, "%s: supported for head_dim = 128 only (got %lld)", who, (long long)c.d);
+    if (c.heads != 32 && c.heads != 64)
+        return fail(FA_ERR_UNSUPPORTED, "%s: supported for 32 or 64 index heads only (got %lld)", who, (long long)c.heads);
+    // (3)
+    if (c.width < 1 || c.width > kIdxWidthMax)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: width must lie in [1, 2^28] (got %lld)", who, (long long)c.width);
+    if (c.batch > 65535 || c.seqlen_q > ((int64_t)1 << 22)) return fail(FA_ERR_UNSUPPORTED, "%s: problem too large for one launch", who);
+    // (4) q in bytes, weights and logits in elements
+    if (c.q_head_stride < c.d || c.q_head_stride > ((int64_t)1 << 20))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: head stride of q must lie in [128, 2^20] (got %lld)", who, (long long)c.q_head_stride);
+    const int64_t qtok = (c.heads - 1) * c.q_head_stride + c.d, qspan = (c.seqlen_q - 1) * c.q_token_stride + qtok;
+    if (c.q_token_stride < qtok || (c.batch > 1 && c.q_batch_stride < qspan) || c.q_batch_stride < 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of q too small (batch %lld, token %lld; need token >= %lld, batch >= %lld)", who,
+                    (long long)c.q_batch_stride, (long long)c.q_token_stride, (long long)qtok, (long long)qspan);
+    if (c.q_head_stride % 16 != 0 || c.q_token_stride % 16 != 0 || c.q_batch_stride % 16 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of q must be multiples of 16 bytes", who);
+    if (c.q_token_stride > ((int64_t)1 << 31) || c.q_batch_stride > ((int64_t)1 << 44))
+        return fail(FA_ERR_UNSUPPORTED, "%s: strides of q beyond 2^31 (token) or 2^44 (batch) bytes", who);
+    const int64_t wspan = (c.seqlen_q - 1) * c.weights_token_stride + c.heads;
+    if (c.weights_token_stride < c.heads || (c.batch > 1 && c.weights_batch_stride < wspan) || c.weights_batch_stride < 0 ||
+        c.weights_token_stride > ((int64_t)1 << 31) || c.weights_batch_stride > ((int64_t)1 << 44))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of weights (batch %lld, token %lld): token >= heads = %lld, batch >= %lld", who,
+                    (long long)c.weights_batch_stride, (long long)c.weights_token_stride, (long long)c.heads, (long long)wspan);
+    if (int rc = indexer_logits_ok(who, c.logits, c.batch, c.seqlen_q, c.width, c.logits_batch_stride, c.logits_row_stride)) return rc;
+    if (int rc = indexer_pool_ok(who, c.k_cache, c.page_stride_bytes, c.token_stride_bytes, c.page_block_size)) return rc;
+    if (!aligned16({c.q})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: q must be 16-byte aligned", who);
+    if ((uintptr_t)c.weights % 4 != 0 || (uintptr_t)c.cache_seqlens % 4 != 0 || (uintptr_t)c.block_table % 4 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: weights, cache_seqlens and block_table must be 4-byte aligned", who);
+    // (5)
+    if (int rc = mla_fp8_pages_ok(who, c.block_table_row_stride, c.num_blocks, c.page_block_size, c.max_blocks_per_seq)) return rc;
+    fa::IndexerLogitsArgs a{};
+    a.q = c.q; a.pool = c.k_cache; a.weights = c.weights; a.cache_seqlens = c.cache_seqlens; a.block_table = c.block_table; a.logits = c.logits;
+    a.batch = c.batch; a.seqlen_q = c.seqlen_q; a.heads = c.heads; a.width = c.width;
+    a.q_bs = c.q_batch_stride; a.q_ts = c.q_token_stride; a.q_hs = c.q_head_stride; a.w_bs = c.weights_batch_stride; a.w_ts = c.weights_token_stride;
+    a.lg_bs = c.logits_batch_stride; a.lg_rs = c.logits_row_stride; a.page_sb = c.page_stride_bytes; a.tok_sb = c.token_stride_bytes;
+    a.table_row_stride = c.block_table_row_stride; a.num_blocks = c.num_blocks; a.page_size = c.page_block_size;
+    a.max_blocks = c.max_blocks_per_seq; a.causal = c.causal ? 1 : 0;
+    return launched(who, fa::launch_indexer_logits(a, reinterpret_cast<hipStream_t>(c.stream)));
+}
+
+int fa_indexer_logits(const void* q, const float* weights, const void* k_cache, const int32_t* cache_seqlens, const int32_t* block_table,
+                      float* logits, int64_t batch, int64_t seqlen_q, int64_t heads, int64_t d, int64_t width, int64_t q_batch_stride,
+                      int64_t q_token_stride, int64_t q_head_stride, int64_t weights_batch_stride, int64_t weights_token_stride,
+                      int64_t logits_batch_stride, int64_t logits_row_stride, int64_t page_stride_bytes, int64_t token_stride_bytes,
+                      int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq, int causal,
+                      void* stream) {
+    IndexerLogitsCall c;
+    c.q = q; c.weights = weights; c.k_cache = k_cache; c.cache_seqlens = cache_seqlens; c.block_table = block_table; c.logits = logits;
+    c.batch = batch; c.seqlen_q = seqlen_q; c.heads = heads; c.d = d; c.width = width;
+    c.q_batch_stride = q_batch_stride; c.q_token_stride = q_token_stride; c.q_head_stride = q_head_stride;
+    c.weights_batch_stride = weights_batch_stride; c.weights_token_stride = weights_token_stride;
+    c.logits_batch_stride = logits_batch_stride; c.logits_row_stride = logits_row_stride;
+    c.page_stride_bytes = page_stride_bytes; c.token_stride_bytes = token_stride_bytes; c.block_table_row_stride = block_table_row_stride;
+    c.num_blocks = num_blocks; c.page_block_size = page_block_size; c.max_blocks_per_seq = max_blocks_per_seq;
+    c.causal = causal; c.stream = stream;
+    return indexer_logits_impl("fa_indexer_logits", c);
+}
+
+struct IndexerTopkCall {
+    const float* logits = nullptr;
+    const int32_t* cache_seqlens = nullptr;
+    int32_t* indices = nullptr;
+    int64_t batch = 0, seqlen_q = 0, width = 0, topk = 0, logits_batch_stride = 0, logits_row_stride = 0, indices_batch_stride = 0,
+            indices_token_stride = 0;
+    int causal = 0;
+    void* stream = nullptr;
+};
+
+static int indexer_topk_impl(const char* who, const IndexerTopkCall& c) {
+    if (c.batch < 0 || c.seqlen_q < 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch and seqlen_q must be >= 0 (got %lld, %lld)", who, (long long)c.batch, (long long)c.seqlen_q);
+    if (c.batch == 0 || c.seqlen_q == 0) return FA_OK;   // no row: no launch
+    // (1)
+    if (!c.logits || !c.cache_seqlens || !c.indices) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    // (2)
+    if (c.topk < 1 || c.topk > kIdxTopkMax) return fail(FA_ERR_INVALID_ARGUMENT, "%s: topk must lie in [1, 2^20] (got %lld)", who, (long long)c.topk);
+    if (c.width < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: width must be >= 1 (got %lld)", who, (long long)c.width);
+    if (c.width > kIdxWidthMax) return fail(FA_ERR_UNSUPPORTED, "%s: width = %lld is beyond 2^28 keys a row", who, (long long)c.width);
+    if (c.batch > 65535 || c.seqlen_q > 0x7fffffff) return fail(FA_ERR_UNSUPPORTED, "%s: problem too large for one launch", who);
+    // (3)
+    if (int rc = indexer_logits_ok(who, c.logits, c.batch, c.seqlen_q, c.width, c.logits_batch_stride, c.logits_row_stride)) return rc;
+    const int64_t kIxMax = (int64_t)1 << 40, ix_seq = (c.seqlen_q - 1) * c.indices_token_stride + c.topk;
+    if ((c.seqlen_q > 1 && c.indices_token_stride < c.topk) || c.indices_token_stride < 0 || c.indices_token_stride > kIxMax ||
+        (c.batch > 1 && c.indices_batch_stride < ix_seq) || c.indices_batch_stride < 0 || c.indices_batch_stride > kIxMax)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: strides of indices (batch %lld, token %lld): token >= topk = %lld, batch >= %lld (each <= 2^40)",
+                    who, (long long)c.indices_batch_stride, (long long)c.indices_token_stride, (long long)c.topk, (long long)ix_seq);
+    if ((uintptr_t)c.indices % 4 != 0 || (uintptr_t)c.cache_seqlens % 4 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: indices and cache_seqlens must be 4-byte aligned", who);
+    fa::IndexerTopkArgs a{};
+    a.logits = c.logits; a.cache_seqlens = c.cache_seqlens; a.indices = c.indices;
+    a.batch = c.batch; a.seqlen_q = c.seqlen_q; a.width = c.width; a.topk = c.topk;
+    a.lg_bs = c.logits_batch_stride; a.lg_rs = c.logits_row_stride; a.ix_bs = c.indices_batch_stride; a.ix_ts = c.indices_token_stride;
+    a.causal = c.causal ? 1 : 0;
+    return launched(who, fa::launch_indexer_topk(a, reinterpret_cast<hipStream_t>(c.stream)));
+}
+
+int fa_indexer_topk(const float* logits, const int32_t* cache_seqlens, int32_t* indices, int64_t batch, int64_t seqlen_q, int64_t width,
+                    int64_t topk, int64_t logits_batch_stride, int64_t logits_row_stride, int64_t indices_batch_stride,
+                    int64_t indices_token_stride, int causal, void* stream) {
+    IndexerTopkCall c;
+    c.logits = logits; c.cache_seqlens = cache_seqlens; c.indices = indices;
+    c.batch = batch; c.seqlen_q = seqlen_q; c.width = width; c.topk = topk;
+    c.logits_batch_stride = logits_batch_stride; c.logits_row_stride = logits_row_stride;
+    c.indices_batch_stride = indices_batch_stride; c.indices_token_stride = indices_token_stride;
+    c.causal = causal; c.stream = stream;
+    return indexer_topk_impl("fa_indexer_topk", c);
 }
 
 // One call of the fa_rotary_apply family, a field per argument under its name in the header.  Defaults: "argument absent".

@@ -43,7 +43,7 @@ struct BwdArgs {
 // roofline figure; off by default, costs nothing when off).
 enum KernelId { K_FWD_F32 = 0, K_BWD_DELTA, K_BWD_DKDV_F32, K_BWD_DQ_F32, K_FWD_MFMA, K_BWD_MFMA, K_BWD_DQ_CVT, K_BWD_DQ_MFMA,
                 K_FP8_QUANT, K_FWD_FP8, K_EX_FWD, K_EX_BWD, K_KV_GROUP_SUM, K_FP8IN_VT, K_FP8IN_FWD, K_FP8IN_VT_VARLEN,
-                K_FP8IN_FWD_VARLEN, K_COUNT };
+                K_FP8IN_FWD_VARLEN, K_IDX_PACK, K_IDX_LOGITS, K_IDX_TOPK, K_COUNT };
 void prof_begin(int id, hipStream_t st);
 void prof_end(int id, hipStream_t st);
 struct ProfScope {
@@ -325,6 +325,39 @@ struct MlaF8PackArgs {
     int scale_pow2;
 };
 hipError_t launch_mla_f8_pack(const MlaF8PackArgs& a, hipStream_t st);
+
+// The lightning indexer (fa_indexer.hip; fa_indexer_pack, fa_indexer_logits, fa_indexer_topk): the index-key cache is a paged pool of
+// 132-byte tokens [128 e4m3 | 1 float32 scale], token slot of page pg at pool + pg * page_sb + slot * tok_sb bytes; lengths and
+// table are untrusted as for MlaF8PackArgs.  The append: k_new (batch, seqlen_new, 128) bf16 at its strides in elements.
+struct IndexerPackArgs {
+    const void* k_new;
+    void* pool;
+    const int *cache_seqlens, *block_table;
+    int64_t batch, seqlen_new, k_bs, k_ts, page_sb, tok_sb, table_row_stride, num_blocks, page_size, max_blocks;
+    int scale_pow2;
+};
+hipError_t launch_indexer_pack(const IndexerPackArgs& a, hipStream_t st);
+// the logits: q (batch, seqlen_q, heads, 128) e4m3 at byte strides, weights (batch, seqlen_q, heads) and logits (batch, seqlen_q,
+// width) float32 at element strides; heads 32 | 64.  Only the entries a token sees are written.
+struct IndexerLogitsArgs {
+    const void *q, *pool;
+    const float* weights;
+    const int *cache_seqlens, *block_table;
+    float* logits;
+    int64_t batch, seqlen_q, heads, width, q_bs, q_ts, q_hs, w_bs, w_ts, lg_bs, lg_rs, page_sb, tok_sb, table_row_stride, num_blocks,
+        page_size, max_blocks;
+    int causal;
+};
+hipError_t launch_indexer_logits(const IndexerLogitsArgs& a, hipStream_t st);
+// the selection: per row the topk largest visible logits' positions, ascending, then -1
+struct IndexerTopkArgs {
+    const float* logits;
+    const int* cache_seqlens;
+    int* indices;
+    int64_t batch, seqlen_q, width, topk, lg_bs, lg_rs, ix_bs, ix_ts;
+    int causal;
+};
+hipError_t launch_indexer_topk(const IndexerTopkArgs& a, hipStream_t st);
 
 // Rotary embedding for training and prefill (fa_rotary.hip; fa_rotary_apply).  16-bit x, y (batch, seqlen, heads, d), heads at
 // stride d, strides multiples of 8 elements, 16-byte aligned; y == x (with x's strides) is the in-place form.  Tables as KvArgs'.

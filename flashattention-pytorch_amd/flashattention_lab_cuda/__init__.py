@@ -53,6 +53,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_ex_backward_dlse", "fa_ex_backward_varlen_dlse", "fa_merge_states", "fa_merge_states_backward",
     "fa_mla_sparse_forward", "fa_mla_sparse_workspace_bytes",
     "fa_mla_fp8_forward", "fa_mla_fp8_workspace_bytes", "fa_mla_fp8_pack",
+    "fa_indexer_pack", "fa_indexer_logits", "fa_indexer_topk",
     "fa_ex_forward_vdim", "fa_ex_backward_vdim", "fa_ex_forward_varlen_vdim", "fa_ex_backward_varlen_vdim",
     "fa_ex_forward_bias", "fa_ex_backward_bias", "fa_ex_backward_workspace_bytes_bias",
     "fa_fp8_forward", "fa_fp8_forward_workspace_bytes",
@@ -194,6 +195,13 @@ _sig("fa_mla_fp8_workspace_bytes", _fields("i:batch,heads_q,heads_kv,seqlen_q,ca
 _sig("fa_mla_fp8_pack", _fields(
     "p:latent_new,rope_new,kv_cache,cache_seqlens,block_table i:batch,seqlen_new,latent_batch_stride,latent_token_stride,"
     "rope_batch_stride,rope_token_stride") + _F8POOL + _F8PAGES + _fields("c:scale_pow2") + _STREAM)
+_sig("fa_indexer_pack", _fields("p:k_new,k_cache,cache_seqlens,block_table i:batch,seqlen_new,d,k_new_batch_stride,k_new_token_stride") +
+     _F8POOL + _F8PAGES + _fields("c:scale_pow2") + _STREAM)
+_sig("fa_indexer_logits", _fields(
+    "p:q,weights,k_cache,cache_seqlens,block_table,logits i:batch,seqlen_q,heads,d,width,q_batch_stride,q_token_stride,q_head_stride,"
+    "weights_batch_stride,weights_token_stride,logits_batch_stride,logits_row_stride") + _F8POOL + _F8PAGES + _fields("c:causal") + _STREAM)
+_sig("fa_indexer_topk", _fields("p:logits,cache_seqlens,indices i:batch,seqlen_q,width,topk,logits_batch_stride,logits_row_stride,"
+                                "indices_batch_stride,indices_token_stride c:causal") + _STREAM)
 _sig("fa_fp8_forward", _fields("p:q,k,v,o,lse,q_descale,k_descale,v_descale i:batch,heads_q,heads_kv,seqlen_q,seqlen_k,d c:dtype "
                                "i:q_batch_stride,q_head_stride,q_token_stride,k_batch_stride,k_head_stride,k_token_stride,v_batch_stride,"
                                "v_head_stride,v_token_stride,o_batch_stride,o_head_stride,o_token_stride,q_descale_batch_stride,"
@@ -257,6 +265,9 @@ _family("fa_merge_states_backward", [])
 _family("fa_mla_sparse_forward", [])
 _family("fa_mla_fp8_forward", [])
 _family("fa_mla_fp8_pack", [])
+_family("fa_indexer_pack", [])
+_family("fa_indexer_logits", [])
+_family("fa_indexer_topk", [])
 _family("fa_fp8_forward", [])
 _family("fa_fp8_forward_varlen", [])
 _family("fa_ex_forward_kvcache_qv", ["fa_ex_forward_kvcache" + _suffix for _suffix in ("", "_paged", "_rotary", "_fp8", "_sink", "_varlen")])
@@ -1611,6 +1622,199 @@ def ex_mla_fp8_pack(latent_new, rope_new, kv_cache, cache_seqlens, block_table, 
         _call("fa_mla_fp8_pack", (
             latent_new.data_ptr(), rope_new.data_ptr(), kv_cache.data_ptr(), cache_seqlens.data_ptr(), block_table.data_ptr(), b, nnew,
             lb, lt, rb, rt, psb, tsb, trs, nblk, ps, mb, int(bool(scale_pow2)), _stream_ptr(dev)))
+
+
+# ---- the lightning indexer (include/fa_mi355x.h: fa_indexer_pack, fa_indexer_logits, fa_indexer_topk) ----
+INDEXER_TOKEN_BYTES = 132   # 128 e4m3 | 1 float32 scale
+INDEXER_DIM = 128
+
+
+def _idx_pool(who, k_cache, device):
+    """(page stride, token stride, num_blocks, page_block_size) in bytes of a (num_blocks, page_block_size, 1, W >= 132) uint8 /
+    float8_e4m3fn index-key pool; a view of a wider allocation keeps its strides, nothing is copied"""
+    if not isinstance(k_cache, torch.Tensor) or k_cache.dtype not in (torch.uint8, torch.float8_e4m3fn):
+        dt = k_cache.dtype if isinstance(k_cache, torch.Tensor) else type(k_cache).__name__
+        raise NotImplementedError(f"{who}: k_cache of dtype {dt} is not supported (torch.uint8 or torch.float8_e4m3fn bytes expected)")
+    if not k_cache.is_cuda or k_cache.device != device:
+        raise RuntimeError(f"{who}: k_cache must be a GPU (HIP device) tensor on the other tensors' device; there is no CPU path")
+    if k_cache.dim() != 4 or k_cache.shape[2] != 1 or k_cache.shape[3] < INDEXER_TOKEN_BYTES or k_cache.shape[0] == 0:
+        raise RuntimeError(f"{who}: k_cache must be (num_blocks, page_block_size, 1, W >= {INDEXER_TOKEN_BYTES}), got {tuple(k_cache.shape)}")
+    nblk, ps = k_cache.shape[:2]
+    if ps < 16 or ps % 16 != 0:
+        raise RuntimeError(f"{who}: page_block_size (k_cache.shape[1]) must be a positive multiple of 16, got {ps}")
+    tsb = k_cache.stride(1)
+    psb = k_cache.stride(0) if nblk > 1 else max(k_cache.stride(0), ((ps - 1) * tsb + INDEXER_TOKEN_BYTES + 15) // 16 * 16)
+    if k_cache.stride(3) != 1 or tsb < INDEXER_TOKEN_BYTES or tsb % 16 or psb % 16 or psb < (ps - 1) * tsb + INDEXER_TOKEN_BYTES or \
+            k_cache.data_ptr() % 16:
+        raise ValueError(f"{who}: k_cache must have contiguous 132-byte tokens at a stride that is a multiple of 16, pages that do not "
+                         f"overlap at a stride that is a multiple of 16, and a 16-byte aligned address (got strides "
+                         f"{tuple(k_cache.stride())}); it is never copied")
+    return psb, tsb, nblk, ps
+
+
+def _idx_lens(who, cache_seqlens, b, device):
+    if isinstance(cache_seqlens, numbers.Integral):
+        return
+    if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32:
+        dt = cache_seqlens.dtype if isinstance(cache_seqlens, torch.Tensor) else type(cache_seqlens).__name__
+        raise NotImplementedError(f"{who}: cache_seqlens of dtype {dt} is not supported (int32 tensor or int expected)")
+    if cache_seqlens.device != device or cache_seqlens.shape != (b,):
+        raise RuntimeError(f"{who}: cache_seqlens must be an int32 ({b},) tensor on the other tensors' device, or an int")
+
+
+def _idx_out(who, name, out, shape, dtype, device):
+    """a caller's output: the right shape, dtype and device, last dim contiguous; its (batch, row) strides"""
+    if not isinstance(out, torch.Tensor) or out.dtype != dtype:
+        dt = out.dtype if isinstance(out, torch.Tensor) else type(out).__name__
+        raise NotImplementedError(f"{who}: {name} of dtype {dt} is not supported ({dtype} expected)")
+    if out.device != device or tuple(out.shape) != tuple(shape):
+        raise RuntimeError(f"{who}: {name} must be a {tuple(shape)} tensor on {device}, got {tuple(out.shape)} on {out.device}")
+    b, n, w = shape
+    rs = out.stride(1) if n > 1 else max(out.stride(1), w)
+    bs = out.stride(0) if b > 1 else max(out.stride(0), (n - 1) * rs + w)
+    if (w > 1 and out.stride(2) != 1) or rs < w or bs < (n - 1) * rs + w:
+        raise ValueError(f"{who}: {name} must have a contiguous last dim and rows that do not overlap (got strides {tuple(out.stride())}); "
+                         f"it is never copied")
+    return bs, rs
+
+
+def ex_indexer_pack(k_new, k_cache, cache_seqlens, block_table, scale_pow2=False):
+    """Quantise and append new index keys to an fp8 index-key pool, in place (fa_indexer_pack): k_new (B, N_new, 128) bfloat16 on the
+    GPU goes to positions cache_seqlens[b] .. + N_new of sequence b (int32 (B,) lengths before the append, or an int) through
+    block_table; a token whose position or page falls outside the table or the pool is dropped.  Returns None."""
+    who = "ex_indexer_pack"
+    if not isinstance(k_new, torch.Tensor) or not k_new.is_cuda:
+        raise RuntimeError(f"{who}: k_new must be a GPU (HIP device) tensor; there is no CPU path")
+    if k_new.dtype != torch.bfloat16:
+        raise NotImplementedError(f"{who}: k_new of dtype {k_new.dtype} is not supported (torch.bfloat16 expected)")
+    if k_new.dim() != 3:
+        raise RuntimeError(f"{who}: k_new must be (B, N_new, 128), got {tuple(k_new.shape)}")
+    if k_new.shape[2] != INDEXER_DIM:
+        raise NotImplementedError(f"{who}: k_new of width {k_new.shape[2]} is not supported (128 expected)")
+    b, nnew = k_new.shape[:2]
+    dev = k_new.device
+    psb, tsb, nblk, ps = _idx_pool(who, k_cache, dev)
+    _f8_table(who, block_table, cache_seqlens, b, dev, True)
+    k_new, kb, kt, _h = _f8_rows(who, "k_new", k_new.unsqueeze(2), 1, INDEXER_DIM)
+    with torch.cuda.device(dev):
+        cache_seqlens, block_table, trs, mb = _f8_table_args(block_table, cache_seqlens, b, dev)
+        _call("fa_indexer_pack", (
+            k_new.data_ptr(), k_cache.data_ptr(), cache_seqlens.data_ptr(), block_table.data_ptr(), b, nnew, INDEXER_DIM, kb, kt, psb, tsb,
+            trs, nblk, ps, mb, int(bool(scale_pow2)), _stream_ptr(dev)))
+
+
+def _idx_q(who, q, weights):
+    """q as bytes with its (batch, token, head) byte strides, weights with its (batch, token) strides; what the call cannot
+    address is copied (both are only read)"""
+    if not isinstance(q, torch.Tensor) or not q.is_cuda:
+        raise RuntimeError(f"{who}: q must be a GPU (HIP device) tensor; there is no CPU path")
+    if q.dtype not in (torch.float8_e4m3fn, torch.uint8):
+        raise NotImplementedError(f"{who}: q of dtype {q.dtype} is not supported (torch.float8_e4m3fn, or its bytes as torch.uint8, expected: "
+                                  f"the caller quantises q)")
+    if q.dim() != 4:
+        raise RuntimeError(f"{who}: q must be 4-D (B, Nq, H_I, 128), got {tuple(q.shape)}")
+    b, nq, h, d = q.shape
+    if d != INDEXER_DIM:
+        raise NotImplementedError(f"{who}: q of width {d} is not supported (128 expected)")
+    if h not in (32, 64):
+        raise NotImplementedError(f"{who}: q with {h} index heads is not supported (32 or 64 expected)")
+    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32:
+        dt = weights.dtype if isinstance(weights, torch.Tensor) else type(weights).__name__
+        raise NotImplementedError(f"{who}: weights of dtype {dt} is not supported (torch.float32 expected)")
+    if weights.device != q.device or tuple(weights.shape) != (b, nq, h):
+        raise RuntimeError(f"{who}: weights must be a (B, Nq, H_I) = ({b}, {nq}, {h}) tensor on q's device, got {tuple(weights.shape)} on "
+                           f"{weights.device}")
+
+    def ok(t):
+        hs = t.stride(2)
+        tok = (h - 1) * hs + d
+        ts = t.stride(1) if nq > 1 else max(t.stride(1), tok)
+        bs = t.stride(0) if b > 1 else max(t.stride(0), (nq - 1) * ts + tok)
+        good = t.stride(3) == 1 and hs >= d and ts >= tok and bs >= (nq - 1) * ts + tok and not (hs % 16 or ts % 16 or bs % 16 or t.data_ptr() % 16)
+        return good, bs, ts, hs
+    good, qb, qt, qh = ok(q)
+    if not good:
+        q = q.contiguous()
+        good, qb, qt, qh = ok(q)
+    if weights.stride(2) != 1 or (nq > 1 and weights.stride(1) < h) or (b > 1 and weights.stride(0) < (nq - 1) * weights.stride(1) + h):
+        weights = weights.contiguous()
+    wt = weights.stride(1) if nq > 1 else max(weights.stride(1), h)
+    wb = weights.stride(0) if b > 1 else max(weights.stride(0), (nq - 1) * wt + h)
+    return q, qb, qt, qh, weights, wb, wt
+
+
+def ex_indexer_logits(q, weights, k_cache, cache_seqlens, block_table, causal=True, out=None, width=None):
+    """The index logits (fa_indexer_logits): q (B, Nq, H_I, 128) e4m3, weights (B, Nq, H_I) float32, k_cache the index-key pool;
+    returns float32 (B, Nq, width), width defaulting to max_blocks_per_seq * page_block_size.  Only visible entries are written: a
+    fresh result is torch.empty elsewhere."""
+    who = "ex_indexer_logits"
+    q, qb, qt, qh, weights, wb, wt = _idx_q(who, q, weights)
+    b, nq, h, d = q.shape
+    dev = q.device
+    psb, tsb, nblk, ps = _idx_pool(who, k_cache, dev)
+    _f8_table(who, block_table, cache_seqlens, b, dev, True)
+    width = block_table.shape[1] * ps if width is None else operator.index(width)
+    if width < 1:
+        raise RuntimeError(f"{who}: width must be >= 1, got {width}")
+    with torch.cuda.device(dev):
+        cache_seqlens, block_table, trs, mb = _f8_table_args(block_table, cache_seqlens, b, dev)
+        if out is None:
+            out = torch.empty((b, nq, width), dtype=torch.float32, device=dev)
+        lb, lr = _idx_out(who, "out", out, (b, nq, width), torch.float32, dev)
+        _call("fa_indexer_logits", (
+            q.data_ptr(), weights.data_ptr(), k_cache.data_ptr(), cache_seqlens.data_ptr(), block_table.data_ptr(), out.data_ptr(),
+            b, nq, h, d, width, qb, qt, qh, wb, wt, lb, lr, psb, tsb, trs, nblk, ps, mb, int(bool(causal)), _stream_ptr(dev)))
+    return out
+
+
+def ex_indexer_topk(logits, cache_seqlens, topk, seqlen_q=None, causal=True, out=None):
+    """The selection (fa_indexer_topk): logits float32 (B, Nq, width); returns int32 (B, Nq, topk), per row the positions of the
+    topk largest visible logits in ascending order, then -1."""
+    who = "ex_indexer_topk"
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda:
+        raise RuntimeError(f"{who}: logits must be a GPU (HIP device) tensor; there is no CPU path")
+    if logits.dtype != torch.float32:
+        raise NotImplementedError(f"{who}: logits of dtype {logits.dtype} is not supported (torch.float32 expected)")
+    if logits.dim() != 3 or logits.shape[2] < 1:
+        raise RuntimeError(f"{who}: logits must be (B, Nq, width >= 1), got {tuple(logits.shape)}")
+    b, nq, width = logits.shape
+    if seqlen_q is not None and operator.index(seqlen_q) != nq:
+        raise RuntimeError(f"{who}: seqlen_q = {seqlen_q} is not logits.shape[1] = {nq}")
+    topk = operator.index(topk)
+    if topk < 1 or topk > 1 << 20:
+        raise RuntimeError(f"{who}: topk must lie in [1, 2^20], got {topk}")
+    dev = logits.device
+    _idx_lens(who, cache_seqlens, b, dev)
+    lb, lr = _idx_out(who, "logits", logits, (b, nq, width), torch.float32, dev)
+    with torch.cuda.device(dev):
+        if not isinstance(cache_seqlens, torch.Tensor):
+            cache_seqlens = torch.full((b,), operator.index(cache_seqlens), dtype=torch.int32, device=dev)
+        cache_seqlens = cache_seqlens.contiguous()
+        if out is None:
+            out = torch.empty((b, nq, topk), dtype=torch.int32, device=dev)
+        ib, it = _idx_out(who, "out", out, (b, nq, topk), torch.int32, dev)
+        _call("fa_indexer_topk", (
+            logits.data_ptr(), cache_seqlens.data_ptr(), out.data_ptr(), b, nq, width, topk, lb, lr, ib, it, int(bool(causal)),
+            _stream_ptr(dev)))
+    return out
+
+
+def ex_lightning_indexer(q, weights, k_cache, cache_seqlens, block_table, topk, causal=True):
+    """ex_indexer_topk(ex_indexer_logits(..)) with the logits in the shim's workspace: no allocation but the result's after the
+    first call of a shape."""
+    who = "ex_lightning_indexer"
+    _idx_q(who, q, weights)                                   # (the refusals first: nothing has run yet)
+    _idx_pool(who, k_cache, q.device)
+    b, nq = q.shape[:2]
+    _f8_table(who, block_table, cache_seqlens, b, q.device, True)
+    width = block_table.shape[1] * k_cache.shape[1]
+    if b * nq == 0:
+        return ex_indexer_topk(ex_indexer_logits(q, weights, k_cache, cache_seqlens, block_table, causal), cache_seqlens, topk, None, causal)
+    with torch.cuda.device(q.device):
+        ws = _workspace(q.device, b * nq * width * 4)
+    logits = ws[:b * nq * width * 4].view(torch.float32).view(b, nq, width)
+    ex_indexer_logits(q, weights, k_cache, cache_seqlens, block_table, causal, logits, width)
+    return ex_indexer_topk(logits, cache_seqlens, topk, nq, causal)
 
 
 # ---- rotary embedding for training and prefill (include/fa_mi355x.h: fa_rotary_apply) ----

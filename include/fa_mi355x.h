@@ -927,6 +927,83 @@ int fa_mla_fp8_pack(const void* latent_new, const void* rope_new, void* kv_cache
                     int64_t token_stride_bytes, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
                     int64_t max_blocks_per_seq, int scale_pow2, void* stream);
 
+/* --- The lightning indexer (DeepSeek-V3.2): the step that makes the token lists fa_mla_sparse_forward and fa_mla_fp8_forward take as
+ * `indices`.  A call family of its own; three launches, each usable alone.  For query token i and cached token j of sequence b
+ *     I[b, i, j] = sum_h  w[b, i, h] * max(0, q[b, i, h] . k8[j]) * k_scale[j]
+ * over `heads` = 32 or 64 index heads, 128 wide, and per token the topk largest I among the tokens it sees.
+ * The index-key cache is a paged pool, one key a token.  A cached token is 132 bytes:
+ *     byte   0 .. 127   128 e4m3 (OCP, torch.float8_e4m3fn)   the index key, quantised as one 128-wide tile
+ *     byte 128 .. 131   1 float32                             its scale
+ * slot s of page p starts at k_cache + p * page_stride_bytes + s * token_stride_bytes (64-bit arithmetic); token_stride_bytes >= 132
+ * and a multiple of 16 (144: the dense form); bytes of a token's stride past its 132 are never written and never read.
+ * block_table, cache_seqlens, num_blocks, page_block_size, max_blocks_per_seq and block_table_row_stride mean what they mean for
+ * fa_mla_fp8_forward (the same table serves both pools); cache_seqlens is required.  Paged only: a contiguous cache is an identity
+ * table.  Both device arrays are untrusted: a length is clamped on the device to [0, min(max_blocks_per_seq * page_block_size,
+ * width)] (fa_indexer_topk, which takes no table: [0, width]); no table entry past ceil(len / page_block_size) is read; a page
+ * outside [0, num_blocks) is not fetched.  Nothing allocates, synchronises or reads device memory on the host: every call can be
+ * captured in a graph and replayed after lengths, table, cache bytes and weights changed in place.  No workspace.
+ * Visibility (fa_mla_sparse_forward's rule): key j is visible to token i of sequence b iff 0 <= j < len_b and, with causal != 0,
+ * j <= len_b - seqlen_q + i; len_b counts the seqlen_q new tokens.
+ *
+ * fa_indexer_pack quantises and appends: k_new (batch, seqlen_new, 128) bf16 at its batch / token strides (elements); token i of
+ * sequence b goes to position cache_seqlens[b] + i (the lengths before the append; not modified) through block_table.
+ * fa_mla_fp8_pack's rule on the one tile, in fp32 from the exact bf16 values:
+ *     amax = max |x|;   scale = amax > 0 ? amax / 448 : 1   (scale_pow2 != 0: rounded up to the next power of two);
+ *     byte = e4m3_rne(clamp(x / scale, -448, 448))
+ * with both divisions IEEE-rounded, and the same things outside the contract (a NaN or an infinity in the tile, a subnormal scale,
+ * one in the top binade).  A negative length, a position at or beyond max_blocks_per_seq * page_block_size, or a page outside
+ * [0, num_blocks) drops that token and nothing of it is written.  Two tokens mapped to one slot: undefined.  Checked before any HIP
+ * call, the first broken rule named in fa_last_error(), in this order: batch, seqlen_new >= 0 (one of them 0: FA_OK, no launch);
+ * (1) the four pointers non-null; (2) d = 128 (FA_ERR_UNSUPPORTED, with the number), batch * seqlen_new < 2^31 (FA_ERR_UNSUPPORTED);
+ * (3) token stride >= 128, with batch > 1 batch stride >= (seqlen_new - 1) * token stride + 128, multiples of 8, at most 2^31 / 2^44
+ * (FA_ERR_UNSUPPORTED); token_stride_bytes >= 132 and a multiple of 16 (below 2^31: FA_ERR_UNSUPPORTED); page_stride_bytes >=
+ * (page_block_size - 1) * token_stride_bytes + 132 and a multiple of 16; k_cache 16-byte aligned; k_new 16-byte, cache_seqlens and
+ * block_table 4-byte aligned; (4) the page geometry: page_block_size a positive multiple of 16, num_blocks in [1, 2^31),
+ * max_blocks_per_seq >= 1 with a capacity <= 2^28 tokens (FA_ERR_UNSUPPORTED), block_table_row_stride >= max_blocks_per_seq.
+ *
+ * fa_indexer_logits: q (batch, seqlen_q, heads, 128) e4m3 bytes at its batch / token / head strides (bytes = elements); weights
+ * (batch, seqlen_q, heads) float32 at its batch / token strides (elements) -- the caller folds the query's own quantisation scale and
+ * the heads^-1/2 * d^-1/2 factors into it; there is no scale argument.  logits (batch, seqlen_q, width) float32 at 64-bit batch / row
+ * strides (elements); batch * seqlen_q * width may exceed 2^31.  For a visible key the value above is written: the dot products on
+ * v_mfma_scale_f32_32x32x64_f8f6f4 with unit scales (two instructions a product), ReLU, weight and head sum in fp32 in the order
+ * csrc/fa_indexer.hip and tests/indexer_ref.py document, k_scale applied once after the head sum.  A visible key on a page outside
+ * the pool reads as a zero row with scale 0: its logit is 0, and it takes part in the selection.  ENTRIES THAT ARE NOT VISIBLE ARE
+ * NOT WRITTEN: the row keeps its bytes there, and fa_indexer_topk never reads them.  e4m3 NaN codes in a visible q or key propagate.
+ * Checked in this order: batch, seqlen_q >= 0 (one of them 0: FA_OK, no launch); (1) the six pointers non-null; (2) d = 128, then
+ * heads 32 or 64 (each FA_ERR_UNSUPPORTED, with the number); (3) width in [1, 2^28]; batch <= 65535 and seqlen_q <= 2^22
+ * (FA_ERR_UNSUPPORTED); (4) q: head stride in [128, 2^20], token stride >= (heads - 1) * head stride + 128, with batch > 1 batch
+ * stride >= (seqlen_q - 1) * token stride + a token's heads, multiples of 16, at most 2^31 / 2^44 (FA_ERR_UNSUPPORTED); weights: token
+ * stride >= heads, with batch > 1 batch stride >= a sequence's rows; logits: with seqlen_q > 1 row stride >= width, with batch > 1
+ * batch stride >= (seqlen_q - 1) * row stride + width, none negative, each <= 2^44, 4-byte aligned; the rules of token_stride_bytes,
+ * page_stride_bytes and k_cache above; q 16-byte, weights, cache_seqlens and block_table 4-byte aligned; (5) the page geometry.
+ *
+ * fa_indexer_topk: logits as above, from any source.  Per row (b, i) with n visible keys (the positions 0 .. n - 1):
+ *     key(x) = bits(x) ^ (sign(x) ? 0xFFFFFFFF : 0x80000000), compared as unsigned: a total order on bit patterns (-0 < +0, a positive
+ *     NaN above +inf, -inf an ordinary small value);
+ *     selected: the min(topk, n) visible positions largest by (key descending, position ascending): among equal keys the lowest
+ *     positions win;
+ *     indices[b, i, :]: the selected positions in ASCENDING position order, then -1 in the remaining topk - min(topk, n) entries.
+ * A pure function of the logits' bits.  With n <= topk the row is 0 .. n - 1 and padding and the logits are not read.  indices
+ * (batch, seqlen_q, topk) int32 at its batch / token strides (elements), the list fa_mla_sparse_forward (indices_head_stride 0) and
+ * fa_mla_fp8_forward take.  Checked in this order: batch, seqlen_q >= 0 (one of them 0: FA_OK, no launch); (1) the three pointers
+ * non-null; (2) topk in [1, 2^20]; width >= 1, and <= 2^28 (FA_ERR_UNSUPPORTED); batch <= 65535, seqlen_q < 2^31 (FA_ERR_UNSUPPORTED);
+ * (3) the rules of logits above; with seqlen_q > 1 indices_token_stride >= topk, with batch > 1 indices_batch_stride >= a sequence's
+ * lists, none negative, each <= 2^40; indices and cache_seqlens 4-byte aligned. */
+int fa_indexer_pack(const void* k_new, void* k_cache, const int32_t* cache_seqlens, const int32_t* block_table, int64_t batch,
+                    int64_t seqlen_new, int64_t d, int64_t k_new_batch_stride, int64_t k_new_token_stride,
+                    int64_t page_stride_bytes, int64_t token_stride_bytes, int64_t block_table_row_stride, int64_t num_blocks,
+                    int64_t page_block_size, int64_t max_blocks_per_seq, int scale_pow2, void* stream);
+int fa_indexer_logits(const void* q, const float* weights, const void* k_cache, const int32_t* cache_seqlens,
+                      const int32_t* block_table, float* logits, int64_t batch, int64_t seqlen_q, int64_t heads, int64_t d,
+                      int64_t width, int64_t q_batch_stride, int64_t q_token_stride, int64_t q_head_stride,
+                      int64_t weights_batch_stride, int64_t weights_token_stride, int64_t logits_batch_stride,
+                      int64_t logits_row_stride, int64_t page_stride_bytes, int64_t token_stride_bytes,
+                      int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t max_blocks_per_seq,
+                      int causal, void* stream);
+int fa_indexer_topk(const float* logits, const int32_t* cache_seqlens, int32_t* indices, int64_t batch, int64_t seqlen_q,
+                    int64_t width, int64_t topk, int64_t logits_batch_stride, int64_t logits_row_stride,
+                    int64_t indices_batch_stride, int64_t indices_token_stride, int causal, void* stream);
+
 /* --- Rotary position embedding for training and prefill (FlashAttention's flash_attn.layers.rotary: apply_rotary_emb,
  * apply_rotary_emb_qkv_), forward and backward.  One memory-bound launch on `stream` rotates the first rotary_dim head dims of
  * every head of one 16-bit tensor: x -> y, both (batch, seqlen, heads, d) with the heads adjacent at stride d, the last dim
