@@ -819,3 +819,67 @@ def flash_attention_fp8_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q
                                         bool(causal), softmax_scale, det(q_descale), det(k_descale), det(v_descale), out_dtype,
                                         block_table)
     return (o, lse) if return_softmax_lse else o
+
+
+_FP8_KVCACHE_REFUSED = ("k", "v", "rotary_cos", "rotary_sin", "rotary_interleaved", "window_size", "softcap", "alibi_slopes", "sinks",
+                        "cache_leftpad", "cu_seqlens_q", "max_seqlen_q", "cu_seqlens_k_new", "qv", "attn_bias", "mask", "dropout_p")
+
+
+def flash_attention_fp8_kvcache(q, k_cache, v_cache, *, cache_seqlens=None, block_table=None, cache_batch_idx=None, q_descale=None,
+                                k_descale=None, v_descale=None, softmax_scale=None, causal=False, num_splits=0,
+                                out_dtype=torch.bfloat16, return_softmax_lse=False, **unsupported):
+    """fp8 KV-cache decoding with split-KV: an e4m3 q over the e4m3 cache that flash_attn_with_kvcache(..., k_descale=, v_descale=)
+    writes, both products on the e4m3 matrix instruction (FlashAttention-3's fp8 contract in the decode loop).
+        s[i, j] = softmax_scale * q_descale * k_descale * (q8[i] . k8[j]),   o[i] = sum_j softmax(s)[i, j] * v8[j] * v_descale
+    q (B, Nq, H_q, 128) in torch.float8_e4m3fn; a token- or batch-strided view is used without a copy (contiguous last dim, 16-byte
+    aligned).  k_cache, v_cache: contiguous form (B_cache, cache_len, H_kv, 128) e4m3, or with block_table (int32 (B,
+    max_blocks_per_seq) on the device) the pools (num_blocks, ps, H_kv, 128), ps a positive multiple of 16.  Both forms keep their own
+    batch / page and token strides (64-bit page offsets; views such as pool.unbind(1) are never copied).  H_q % H_kv == 0; query head
+    h reads K/V head h // (H_q // H_kv).  cache_seqlens: int32 (B,) on the device, an int, or None (full); len_b =
+    clamp(cache_seqlens[b], 0, capacity), capacity = cache_len or max_blocks_per_seq * ps.  cache_batch_idx: int32 (B,), contiguous
+    form only; an index outside [0, B_cache) gives an empty sequence.  Descales: float32 (B, H_kv) or (H_kv,), q_descale included;
+    None = 1; read on the device only (finite, > 0).  softmax_scale defaults to 128 ** -0.5.  causal is bottom-right aligned: key j
+    is visible to token i iff j <= len_b - Nq + i.  A row without a visible key gives o = 0 and lse = -inf.  P is rounded to e4m3 on
+    every row; l and lse come from the unrounded p.
+    Lengths, table, indices and descales are untrusted device memory, never read on the host: a captured call replays after they
+    change in place.  A page outside [0, num_blocks) reads as zero K and V and takes part with score 0; no table entry past
+    ceil(len_b / ps) is read; cache bytes that no live token owns never reach a result.
+    num_splits: 0 = the library's rule, else 1 .. 256; the result's bits depend on it and on nothing else of the launch.
+    Refused by name before anything runs (NotImplementedError): a 16-bit q (flash_attn_with_kvcache takes it), a 16-bit or other
+    8-bit cache, head dims other than 128, new tokens k / v (fill the cache with flash_attn_with_kvcache's append), rotary,
+    window_size, softcap, alibi_slopes, sinks, cache_leftpad, cu_seqlens_q, qv, block_table together with cache_batch_idx, out_dtype
+    other than bfloat16 / float16.
+    Returns o (B, Nq, H_q, 128) in out_dtype, and with return_softmax_lse also lse float32 (B, H_q, Nq).  No gradient."""
+    who = "flash_attention_fp8_kvcache"
+    for name, val in unsupported.items():
+        if name in _FP8_KVCACHE_REFUSED:
+            if val is None or val is False or (name == "window_size" and tuple(val) == (-1, -1)) or \
+                    (name in ("softcap", "dropout_p") and val == 0.0) or (name == "max_seqlen_q" and val == 0):
+                continue
+            hint = " (the cache is filled by flash_attn_with_kvcache's append, or by the caller)" if name in ("k", "v") else ""
+            raise NotImplementedError(f"{who}: {name} is not supported by the fp8 decode call{hint}")
+        raise TypeError(f"{who}() got an unexpected keyword argument {name!r}")
+    if not isinstance(q, torch.Tensor):
+        raise RuntimeError(f"{who}: q must be a tensor, got {type(q).__name__}")
+    if q.dtype in (torch.float16, torch.bfloat16, torch.float32):
+        raise NotImplementedError(f"{who}: q of dtype {q.dtype} is not supported: torch.float8_e4m3fn expected (a 16-bit q over an e4m3 "
+                                  f"cache is flash_attn_with_kvcache(..., k_descale=, v_descale=))")
+    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
+        if t.dtype != torch.float8_e4m3fn:
+            raise NotImplementedError(f"{who}: {name} of dtype {t.dtype} is not supported (torch.float8_e4m3fn expected)")
+        if t.dim() >= 1 and t.shape[-1] != 128:
+            raise NotImplementedError(f"{who}: head_dim {t.shape[-1]} is not supported (128 only); got {name} of shape {tuple(t.shape)}")
+    if block_table is not None and cache_batch_idx is not None:
+        raise NotImplementedError(f"{who}: block_table together with cache_batch_idx is not supported (a table row is the indirection)")
+    if out_dtype not in (torch.bfloat16, torch.float16):
+        raise NotImplementedError(f"{who}: out_dtype {out_dtype} is not supported (torch.bfloat16 or torch.float16)")
+    import flashattention_lab_cuda as ext
+
+    det = lambda t: t.detach() if isinstance(t, torch.Tensor) else t   # noqa: E731
+    with torch.no_grad():
+        o, lse = ext.fp8_kvcache_forward(q.detach(), k_cache.detach(), v_cache.detach(), cache_seqlens, block_table, cache_batch_idx,
+                                         det(q_descale), det(k_descale), det(v_descale), softmax_scale, bool(causal), num_splits,
+                                         out_dtype)
+    return (o, lse) if return_softmax_lse else o

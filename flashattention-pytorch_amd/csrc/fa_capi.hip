@@ -31,7 +31,7 @@ hipEvent_t g_prof_open[fa::K_COUNT];
 const char* const kKernelNames[fa::K_COUNT] = {"fwd_f32", "bwd_delta", "bwd_dkdv_f32", "bwd_dq_f32", "fwd_mfma",
                                                "bwd_mfma", "bwd_dq_cvt", "bwd_dq_mfma", "fp8_quant", "fwd_fp8", "ex_fwd", "ex_bwd", "kv_group_sum",
                                                "fp8in_vt", "fp8in_fwd", "fp8in_vt_varlen", "fp8in_fwd_varlen", "idx_pack", "idx_logits",
-                                               "idx_topk"};
+                                               "idx_topk", "fp8kv_split"};
 
 hipEvent_t prof_get_event() {
     if (!g_prof_free.empty()) { hipEvent_t e = g_prof_free.back(); g_prof_free.pop_back(); return e; }
@@ -2948,6 +2948,177 @@ int fa_fp8_forward_varlen(const void* q, const void* k, const void* v, void* o, 
     c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
     c.causal = causal; c.scale = softmax_scale; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
     return fp8_forward_varlen_impl("fa_fp8_forward_varlen", c);
+}
+
+// ---- fp8 KV-cache decoding with split-KV (e4m3 q over an e4m3 cache): see include/fa_mi355x.h
+// One call of fa_fp8_forward_kvcache, a family of its own.
+struct Fp8KvCall {
+    const void *q = nullptr, *k_cache = nullptr, *v_cache = nullptr;
+    void* o = nullptr;
+    float* lse = nullptr;
+    const float *q_descale = nullptr, *k_descale = nullptr, *v_descale = nullptr;
+    const int32_t *cache_seqlens = nullptr, *block_table = nullptr, *cache_batch_idx = nullptr;
+    int64_t batch = 0, heads_q = 0, heads_kv = 0, seqlen_q = 0, cache_len = 0, cache_batch = 0, d = 0;
+    int dtype = 0, q_dtype = 0, cache_dtype = 0;
+    int64_t q_bs = 0, q_ts = 0, k_bs = 0, k_ts = 0, v_bs = 0, v_ts = 0;
+    int64_t table_rs = 0, num_blocks = 0, ps = 0;
+    int64_t qds_bs = 0, kds_bs = 0, vds_bs = 0;
+    int causal = 0;
+    double scale = 0.0;
+    int64_t num_splits = 0;
+    void* workspace = nullptr;
+    size_t workspace_bytes = 0;
+    void* stream = nullptr;
+};
+
+static int64_t fp8_kv_splits(int64_t batch, int64_t hq, int64_t hkv, int64_t nq, int64_t cache_len, int64_t num_splits) {
+    if (num_splits > 0) return num_splits;
+    return fa::fp8kv_num_splits(batch, hq, hkv, nq, cache_len);
+}
+
+static int fp8_kvcache_impl(const char* who, const Fp8KvCall& c) {
+    const bool paged = c.block_table != nullptr;
+    const int64_t kInt = ((int64_t)1 << 31) - 1;
+    // (0) the empty call
+    if (c.batch == 0 || c.seqlen_q == 0) return FA_OK;
+    // (1) null pointers
+    if (!c.q || !c.k_cache || !c.v_cache || !c.o || !c.lse) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    // (2) the head dim and the dtypes
+    if (c.d != 128) return fail(FA_ERR_UNSUPPORTED, "%s: head_dim %lld is not supported (128 only)", who, (long long)c.d);
+    if (c.q_dtype != FA_DTYPE_E4M3)
+        return fail(FA_ERR_UNSUPPORTED, "%s: q_dtype must be FA_DTYPE_E4M3 (got code %d; a 16-bit q is fa_ex_forward_kvcache_fp8's)", who,
+                    c.q_dtype);
+    if (c.cache_dtype != FA_DTYPE_E4M3)
+        return fail(FA_ERR_UNSUPPORTED, "%s: cache_dtype must be FA_DTYPE_E4M3 (got code %d)", who, c.cache_dtype);
+    if (c.dtype != FA_DTYPE_F16 && c.dtype != FA_DTYPE_BF16)
+        return fail(FA_ERR_UNSUPPORTED, "%s: dtype (of o) must be f16 or bf16 (got code %d)", who, c.dtype);
+    // (3) the heads ratio
+    if (c.heads_kv < 1 || c.heads_q < 1 || c.heads_q % c.heads_kv != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads_q=%lld must be a positive multiple of heads_kv=%lld", who, (long long)c.heads_q,
+                    (long long)c.heads_kv);
+    // (4) ranges
+    if (c.batch < 1 || c.batch > 65535) return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch must lie in [1, 65535] (got %lld)", who, (long long)c.batch);
+    if (c.seqlen_q < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_q must be >= 1 (got %lld)", who, (long long)c.seqlen_q);
+    if (c.cache_len < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_len must be >= 1 (got %lld)", who, (long long)c.cache_len);
+    if (c.heads_q > ((int64_t)1 << 20) || c.seqlen_q > ((int64_t)1 << 20) || (c.heads_q / c.heads_kv) * c.seqlen_q > ((int64_t)1 << 20))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: (heads_q / heads_kv) * seqlen_q = %lld * %lld must be <= 2^20", who,
+                    (long long)(c.heads_q / c.heads_kv), (long long)c.seqlen_q);
+    if (!(c.scale == c.scale) || !scale_ok(c.scale))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale must be finite and > 0", who);
+    if (c.cache_batch_idx) {
+        if (c.cache_batch < 1 || c.cache_batch > kInt)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_batch must lie in [1, 2^31) with cache_batch_idx (got %lld)", who,
+                        (long long)c.cache_batch);
+    } else if (c.cache_batch != 0) {
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_batch must be 0 without cache_batch_idx (got %lld)", who, (long long)c.cache_batch);
+    }
+    // (5) alignment and strides
+    if (!aligned16({c.q, c.k_cache, c.v_cache, c.o})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: q, k_cache, v_cache and o must be 16-byte aligned", who);
+    if ((uintptr_t)c.lse % 4 != 0 || (uintptr_t)c.cache_seqlens % 4 != 0 || (uintptr_t)c.block_table % 4 != 0 || (uintptr_t)c.cache_batch_idx % 4 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: lse, cache_seqlens, block_table and cache_batch_idx must be 4-byte aligned", who);
+    const int64_t kMaxStride = (int64_t)1 << 44;
+    const struct { const char* name; int64_t bs, ts, heads; } ts[3] = {
+        {"q", c.q_bs, c.q_ts, c.heads_q}, {"k_cache", c.k_bs, c.k_ts, c.heads_kv}, {"v_cache", c.v_bs, c.v_ts, c.heads_kv}};
+    for (const auto& t : ts) {
+        if (t.ts % 16 != 0 || t.bs % 16 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (batch %lld, token %lld) must be multiples of 16 bytes", who, t.name,
+                        (long long)t.bs, (long long)t.ts);
+        if (t.ts < t.heads * 128 || t.ts > kMaxStride || t.bs < 0 || t.bs > kMaxStride)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (batch %lld, token %lld) must be >= 0, the token stride >= heads * 128 = %lld",
+                        who, t.name, (long long)t.bs, (long long)t.ts, (long long)(t.heads * 128));
+    }
+    // (6) the descale strides
+    const struct { const char* name; const float* p; int64_t bs; } ds[3] = {
+        {"q_descale", c.q_descale, c.qds_bs}, {"k_descale", c.k_descale, c.kds_bs}, {"v_descale", c.v_descale, c.vds_bs}};
+    for (const auto& s : ds) {
+        if (!s.p && s.bs != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: %s_batch_stride must be 0 without %s", who, s.name, s.name);
+        if (s.bs < 0 || (s.bs != 0 && s.bs < c.heads_kv) || s.bs >= ((int64_t)1 << 31) / c.batch)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: %s_batch_stride=%lld must be 0 or >= heads_kv=%lld", who, s.name, (long long)s.bs,
+                        (long long)c.heads_kv);
+        if ((uintptr_t)s.p % 4 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: %s must be 4-byte aligned", who, s.name);
+    }
+    // (7) the pages
+    if (paged) {
+        if (c.cache_batch_idx) return fail(FA_ERR_INVALID_ARGUMENT, "%s: block_table cannot be combined with cache_batch_idx", who);
+        if (c.ps < 16 || c.ps % 16 != 0 || c.ps > 65536)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: page_block_size must be a multiple of 16 in [16, 65536] (got %lld)", who, (long long)c.ps);
+        if (c.cache_len % c.ps != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_len=%lld (the capacity) must be a multiple of page_block_size=%lld", who,
+                        (long long)c.cache_len, (long long)c.ps);
+        if (c.num_blocks < 1 || c.num_blocks > kInt)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_blocks must lie in [1, 2^31) (got %lld)", who, (long long)c.num_blocks);
+        if (c.table_rs < c.cache_len / c.ps || c.table_rs > ((int64_t)1 << 40))
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: block_table_row_stride=%lld must be >= max_blocks_per_seq=%lld (and <= 2^40)", who,
+                        (long long)c.table_rs, (long long)(c.cache_len / c.ps));
+    } else if (c.table_rs != 0 || c.num_blocks != 0 || c.ps != 0) {
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: block_table_row_stride, num_blocks and page_block_size must be 0 without block_table", who);
+    }
+    // (8) the span limits: 32-bit byte offsets inside one batch element or page
+    const int64_t kSpan = ((int64_t)1 << 31) - 1;
+    const int64_t c_n = paged ? c.ps : c.cache_len;
+    const int64_t q_span = c.seqlen_q * c.q_ts, k_span = c_n * c.k_ts, v_span = c_n * c.v_ts;
+    if (q_span > kSpan || k_span > kSpan || v_span > kSpan)
+        return fail(FA_ERR_UNSUPPORTED, "%s: span limit: tokens * token stride of %s is %lld bytes, at or above 2^31", who,
+                    q_span > kSpan ? "q" : k_span > kSpan ? "k_cache" : "v_cache", (long long)(q_span > kSpan ? q_span : k_span > kSpan ? k_span : v_span));
+    if (c.cache_len >= ((int64_t)1 << 28))
+        return fail(FA_ERR_UNSUPPORTED, "%s: span limit: cache_len = %lld (the capacity) is at or above 2^28", who, (long long)c.cache_len);
+    const int64_t row_tiles = ((c.heads_q / c.heads_kv) * c.seqlen_q + 31) / 32;
+    if (row_tiles * c.heads_kv > 65535)
+        return fail(FA_ERR_UNSUPPORTED, "%s: span limit: row tiles * heads_kv = %lld is beyond 65535 for one launch", who,
+                    (long long)(row_tiles * c.heads_kv));
+    // (9) the splits
+    if (c.num_splits < 0 || c.num_splits > 256)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_splits must lie in [0, 256] (got %lld)", who, (long long)c.num_splits);
+    const int64_t S = fp8_kv_splits(c.batch, c.heads_q, c.heads_kv, c.seqlen_q, c.cache_len, c.num_splits);
+    // (10) the workspace
+    const size_t need = fa::kv_workspace_bytes(c.batch, c.heads_q, c.seqlen_q, 128, (int)S);
+    if (need > 0) {
+        if (!c.workspace || c.workspace_bytes < need)
+            return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes is too small (need %zu: fa_fp8_forward_kvcache_workspace_bytes)", who,
+                        c.workspace ? c.workspace_bytes : (size_t)0, need);
+        if ((uintptr_t)c.workspace % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
+    }
+
+    fa::Fp8KvArgs a;
+    a.q = c.q; a.k_cache = c.k_cache; a.v_cache = c.v_cache; a.o = c.o; a.lse = c.lse;
+    a.q_descale = c.q_descale; a.k_descale = c.k_descale; a.v_descale = c.v_descale;
+    a.qds_bs = c.qds_bs; a.kds_bs = c.kds_bs; a.vds_bs = c.vds_bs;
+    a.cache_seqlens = c.cache_seqlens; a.block_table = c.block_table; a.cache_batch_idx = c.cache_batch_idx;
+    a.batch = c.batch; a.heads_q = c.heads_q; a.heads_kv = c.heads_kv; a.seqlen_q = c.seqlen_q; a.cache_len = c.cache_len;
+    a.cache_batch = c.cache_batch; a.dtype = c.dtype;
+    a.q_bs = c.q_bs; a.q_ts = c.q_ts; a.kc_bs = c.k_bs; a.kc_ts = c.k_ts; a.vc_bs = c.v_bs; a.vc_ts = c.v_ts;
+    a.table_row_stride = c.table_rs; a.num_blocks = c.num_blocks; a.page_size = c.ps;
+    a.causal = c.causal != 0; a.scale = (float)c.scale; a.num_splits = S; a.workspace = c.workspace;
+    return launched(who, fa::launch_fp8_kvcache(a, reinterpret_cast<hipStream_t>(c.stream)));
+}
+
+size_t fa_fp8_forward_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t d,
+                                              int64_t num_splits) {
+    if (!kv_ws_args_ok(batch, heads_q, heads_kv, seqlen_q, cache_len, d, num_splits) || d != 128) return 0;
+    return fa::kv_workspace_bytes(batch, heads_q, seqlen_q, 128, (int)fp8_kv_splits(batch, heads_q, heads_kv, seqlen_q, cache_len, num_splits));
+}
+
+int fa_fp8_forward_kvcache(const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const float* q_descale,
+                           const float* k_descale, const float* v_descale, const int32_t* cache_seqlens, const int32_t* block_table,
+                           const int32_t* cache_batch_idx, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
+                           int64_t cache_batch, int64_t d, int dtype, int q_dtype, int cache_dtype, int64_t q_batch_stride, int64_t q_token_stride,
+                           int64_t k_batch_stride, int64_t k_token_stride, int64_t v_batch_stride, int64_t v_token_stride,
+                           int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t q_descale_batch_stride,
+                           int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, int64_t num_splits,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    Fp8KvCall c;
+    c.q = q; c.k_cache = k_cache; c.v_cache = v_cache; c.o = o; c.lse = lse;
+    c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
+    c.cache_seqlens = cache_seqlens; c.block_table = block_table; c.cache_batch_idx = cache_batch_idx;
+    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.seqlen_q = seqlen_q; c.cache_len = cache_len; c.cache_batch = cache_batch;
+    c.d = d; c.dtype = dtype; c.q_dtype = q_dtype; c.cache_dtype = cache_dtype;
+    c.q_bs = q_batch_stride; c.q_ts = q_token_stride; c.k_bs = k_batch_stride; c.k_ts = k_token_stride; c.v_bs = v_batch_stride;
+    c.v_ts = v_token_stride;
+    c.table_rs = block_table_row_stride; c.num_blocks = num_blocks; c.ps = page_block_size;
+    c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
+    c.causal = causal; c.scale = softmax_scale; c.num_splits = num_splits;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    return fp8_kvcache_impl("fa_fp8_forward_kvcache", c);
 }
 
 size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {

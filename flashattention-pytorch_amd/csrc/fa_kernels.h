@@ -43,7 +43,7 @@ struct BwdArgs {
 // roofline figure; off by default, costs nothing when off).
 enum KernelId { K_FWD_F32 = 0, K_BWD_DELTA, K_BWD_DKDV_F32, K_BWD_DQ_F32, K_FWD_MFMA, K_BWD_MFMA, K_BWD_DQ_CVT, K_BWD_DQ_MFMA,
                 K_FP8_QUANT, K_FWD_FP8, K_EX_FWD, K_EX_BWD, K_KV_GROUP_SUM, K_FP8IN_VT, K_FP8IN_FWD, K_FP8IN_VT_VARLEN,
-                K_FP8IN_FWD_VARLEN, K_IDX_PACK, K_IDX_LOGITS, K_IDX_TOPK, K_COUNT };
+                K_FP8IN_FWD_VARLEN, K_IDX_PACK, K_IDX_LOGITS, K_IDX_TOPK, K_FP8KV_SPLIT, K_COUNT };
 void prof_begin(int id, hipStream_t st);
 void prof_end(int id, hipStream_t st);
 struct ProfScope {
@@ -441,5 +441,30 @@ struct Fp8InVarArgs {
 // from batch, heads_kv, total_k (packed: page_size == 0) or max_k, max_blocks, page_size (paged) alone
 size_t fp8in_varlen_workspace_bytes(const Fp8InVarArgs& a);
 hipError_t launch_fp8_inputs_varlen(const Fp8InVarArgs& a, hipStream_t st);
+
+// fp8 KV-cache decoding (fa_fp8_decode.hip; fa_fp8_forward_kvcache): e4m3 q (batch, seqlen_q, heads_q, 128) over an e4m3 cache
+// (cache_batch, cache_len, heads_kv, 128), or with block_table the pools (num_blocks, page_size, heads_kv, 128).  Strides in bytes;
+// o (batch, seqlen_q, heads_q, 128) and lse (batch, heads_q, seqlen_q) contiguous.
+struct Fp8KvArgs {
+    const void *q = nullptr, *k_cache = nullptr, *v_cache = nullptr;
+    void* o = nullptr;
+    float* lse = nullptr;
+    const float *q_descale = nullptr, *k_descale = nullptr, *v_descale = nullptr;   // (batch, heads_kv) device floats; null: 1
+    int64_t qds_bs = 0, kds_bs = 0, vds_bs = 0;
+    const int *cache_seqlens = nullptr, *block_table = nullptr, *cache_batch_idx = nullptr;   // untrusted device memory, or null
+    int64_t batch = 0, heads_q = 0, heads_kv = 0, seqlen_q = 0, cache_len = 0, cache_batch = 0;   // cache_len: the capacity
+    int dtype = 0;                                          // of o: FA_DTYPE_F16 / FA_DTYPE_BF16
+    int64_t q_bs = 0, q_ts = 0, kc_bs = 0, kc_ts = 0, vc_bs = 0, vc_ts = 0;   // kc_bs / vc_bs: the batch or the page stride
+    int64_t table_row_stride = 0, num_blocks = 0, page_size = 0;
+    int causal = 0;
+    float scale = 0.f;
+    int64_t num_splits = 1;                                 // >= 1 (the C layer resolves 0 through fp8kv_num_splits)
+    void* workspace = nullptr;                              // kv_workspace_bytes(batch, heads_q, seqlen_q, 128, num_splits)
+};
+int fp8kv_num_splits(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len);
+hipError_t launch_fp8_kvcache(const Fp8KvArgs& a, hipStream_t st);
+// kv_combine_kernel<Tag, false> (fa_decode.hip) over partials in kv_workspace_bytes' layout, for a caller outside that file
+hipError_t launch_kv_combine(void* o, float* lse, float* po, float* plse, int64_t batch, int64_t heads_q, int64_t seqlen_q, int64_t d,
+                             int dtype, int splits, hipStream_t st);
 
 }  // namespace fa

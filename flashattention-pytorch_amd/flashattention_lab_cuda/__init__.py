@@ -58,6 +58,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_ex_forward_bias", "fa_ex_backward_bias", "fa_ex_backward_workspace_bytes_bias",
     "fa_fp8_forward", "fa_fp8_forward_workspace_bytes",
     "fa_fp8_forward_varlen", "fa_fp8_forward_varlen_workspace_bytes",
+    "fa_fp8_forward_kvcache", "fa_fp8_forward_kvcache_workspace_bytes",
 )
 
 
@@ -214,6 +215,12 @@ _sig("fa_fp8_forward_varlen", _fields(
     "page_block_size,k_page_stride,v_page_stride,q_descale_batch_stride,k_descale_batch_stride,v_descale_batch_stride "
     "c:causal d:softmax_scale") + _WS)
 _sig("fa_fp8_forward_varlen_workspace_bytes", _fields("i:batch,heads_kv,total_k,max_seqlen_k,max_blocks_per_seq,page_block_size,d"), _SIZE)
+_sig("fa_fp8_forward_kvcache", _fields(
+    "p:q,k_cache,v_cache,o,lse,q_descale,k_descale,v_descale,cache_seqlens,block_table,cache_batch_idx "
+    "i:batch,heads_q,heads_kv,seqlen_q,cache_len,cache_batch,d c:dtype,q_dtype,cache_dtype "
+    "i:q_batch_stride,q_token_stride,k_batch_stride,k_token_stride,v_batch_stride,v_token_stride,block_table_row_stride,num_blocks,"
+    "page_block_size,q_descale_batch_stride,k_descale_batch_stride,v_descale_batch_stride c:causal d:softmax_scale i:num_splits") + _WS)
+_sig("fa_fp8_forward_kvcache_workspace_bytes", _KVWS, _SIZE)
 _KVWSV = _fields("i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,d,num_splits c:with_sinks")
 _sig("fa_ex_kvcache_workspace_bytes_varlen", _KVWSV, _SIZE)
 _sig("fa_ex_kvcache_workspace_bytes_qv", _KVWSV + _fields("i:d_v"), _SIZE)
@@ -270,6 +277,7 @@ _family("fa_indexer_logits", [])
 _family("fa_indexer_topk", [])
 _family("fa_fp8_forward", [])
 _family("fa_fp8_forward_varlen", [])
+_family("fa_fp8_forward_kvcache", [])
 _family("fa_ex_forward_kvcache_qv", ["fa_ex_forward_kvcache" + _suffix for _suffix in ("", "_paged", "_rotary", "_fp8", "_sink", "_varlen")])
 
 
@@ -2202,5 +2210,117 @@ def fp8_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_se
             q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp, cu_q.data_ptr(), cu_k.data_ptr(),
             block_table.data_ptr() if paged else 0, b, hq, hkv, total_q, total_k, mq, mk, 128, _DTYPE_CODE[out_dtype], qts, qhs, kts, khs,
             vts, vhs, *pages, qds, kds, vds, int(bool(causal)), scale, ws.data_ptr(), ws.numel(), _stream_ptr(q.device)))
+    del keep_q, keep_k, keep_v
+    return o, lse
+
+
+def fp8_kvcache_forward(q, k_cache, v_cache, cache_seqlens=None, block_table=None, cache_batch_idx=None, q_descale=None, k_descale=None,
+                        v_descale=None, softmax_scale=None, causal=False, num_splits=0, out_dtype=torch.bfloat16):
+    """(o, lse) of fp8 KV-cache decoding (fa_fp8_forward_kvcache): q (B, Nq, H_q, 128) in torch.float8_e4m3fn at its own batch and
+    token strides over the e4m3 caches (B_cache, cache_len, H_kv, 128), or with block_table (int32 (B, max_blocks_per_seq)) the pools
+    (num_blocks, ps, H_kv, 128), at their own batch / page and token strides; nothing is copied.  cache_seqlens int32 (B,) on the
+    device, an int, or None (full); cache_batch_idx int32 (B,), contiguous form only; descales float32 (B, H_kv) or (H_kv,), None =
+    1.  o (B, Nq, H_q, 128) in out_dtype, lse float32 (B, H_q, Nq).  Nothing is read on the host; the partials live in the shim's
+    persistent workspace."""
+    who = "fp8_kvcache_forward"
+    if isinstance(q, torch.Tensor) and q.dtype in (torch.float16, torch.bfloat16):
+        raise NotImplementedError(f"{who}: q of dtype {q.dtype} is not supported (torch.float8_e4m3fn expected; a 16-bit q over an e4m3 "
+                                  f"cache is flash_attn_with_kvcache(..., k_descale=, v_descale=))")
+    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float8_e4m3fn:
+            dt = t.dtype if isinstance(t, torch.Tensor) else type(t).__name__
+            raise NotImplementedError(f"{who}: {name} of dtype {dt} is not supported (torch.float8_e4m3fn expected)")
+    if out_dtype not in (torch.bfloat16, torch.float16):
+        raise NotImplementedError(f"{who}: out_dtype {out_dtype} is not supported (torch.bfloat16 or torch.float16)")
+    paged = block_table is not None
+    if paged and cache_batch_idx is not None:
+        raise NotImplementedError(f"{who}: block_table together with cache_batch_idx is not supported (a table row is the indirection)")
+    for name, t in (("block_table", block_table), ("cache_batch_idx", cache_batch_idx)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.int32):
+            dt = t.dtype if isinstance(t, torch.Tensor) else type(t).__name__
+            raise NotImplementedError(f"{who}: {name} of dtype {dt} is not supported (int32 tensor expected)")
+    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
+        raise RuntimeError(f"{who}: q must be (B, Nq, H_q, 128) and k_cache, v_cache " +
+                           ("pools (num_blocks, page_block_size, H_kv, 128)" if paged else "(B_cache, cache_len, H_kv, 128)") +
+                           f" of one shape; got {tuple(q.shape)}, {tuple(k_cache.shape)}, {tuple(v_cache.shape)}")
+    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.shape[-1] != 128:
+            raise NotImplementedError(f"{who}: head_dim {t.shape[-1]} is not supported (128 only); got {name} of shape {tuple(t.shape)}")
+    b, nq, hq = q.shape[0], q.shape[1], q.shape[2]
+    hkv = k_cache.shape[2]
+    if hkv == 0 or hq == 0 or hq % hkv != 0:
+        raise RuntimeError(f"{who}: H_q = {hq} must be a multiple of H_kv = {hkv}")
+    if isinstance(cache_seqlens, int) and not isinstance(cache_seqlens, bool):
+        cache_seqlens = torch.full((b,), cache_seqlens, dtype=torch.int32, device=q.device)
+    if cache_seqlens is not None and not (isinstance(cache_seqlens, torch.Tensor) and cache_seqlens.dtype == torch.int32 and
+                                          cache_seqlens.shape == (b,)):
+        raise RuntimeError(f"{who}: cache_seqlens must be an int32 tensor of shape (B,) = ({b},), an int or None")
+    tensors = [t for t in (q, k_cache, v_cache, cache_seqlens, block_table, cache_batch_idx) if t is not None]
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: tensors must be on the GPU (HIP device); there is no CPU path")
+    if len({t.device for t in tensors}) != 1:
+        raise RuntimeError(f"{who}: all tensors must be on one device")
+    scale = 128 ** -0.5 if softmax_scale is None else float(softmax_scale)
+    if not (math.isfinite(scale) and scale > 0.0):
+        raise RuntimeError(f"{who}: softmax_scale must be finite and > 0 (got {scale})")
+    ns = operator.index(num_splits)
+    if ns < 0 or ns > 256:
+        raise RuntimeError(f"{who}: num_splits must lie in [0, 256] (got {ns})")
+    for name, t, heads in (("q", q, hq), ("k_cache", k_cache, hkv), ("v_cache", v_cache, hkv)):
+        if t.numel() and ((heads > 1 and t.stride(2) != 128) or t.stride(3) != 1):
+            raise ValueError(f"{who}: {name} must have adjacent heads with a contiguous last dim (strides {t.stride()})")
+        if t.numel() and (t.data_ptr() % 16 != 0 or t.stride(0) % 16 != 0 or t.stride(1) % 16 != 0 or t.stride(0) < 0 or
+                          (t.shape[1] > 1 and t.stride(1) < heads * 128)):
+            raise ValueError(f"{who}: {name} is a view the kernel cannot address: a 16-byte aligned start, batch and token strides that "
+                             f"are multiples of 16 bytes and rows that do not overlap are needed (strides {t.stride()})")
+    tstride = lambda t, heads: t.stride(1) if t.shape[1] > 1 else heads * 128   # noqa: E731
+    if paged:
+        nblk, ps = k_cache.shape[0], k_cache.shape[1]
+        if ps < 16 or ps % 16 != 0:
+            raise RuntimeError(f"{who}: page_block_size must be a positive multiple of 16, got {ps}")
+        if block_table.dim() != 2 or block_table.shape[0] != b or block_table.shape[1] < 1:
+            raise RuntimeError(f"{who}: block_table must be an int32 (B, max_blocks_per_seq >= 1) tensor, B = {b}; got "
+                               f"{tuple(block_table.shape)}")
+        if nblk < 1:
+            raise RuntimeError(f"{who}: the pools must hold at least one page")
+        if block_table.stride(1) != 1 and block_table.shape[1] > 1:
+            block_table = block_table.contiguous()
+        cap, cbatch = block_table.shape[1] * ps, 0
+        pages = (max(block_table.stride(0), block_table.shape[1]), nblk, ps)
+    else:
+        cap = k_cache.shape[1]
+        if cap < 1:
+            raise RuntimeError(f"{who}: the caches must hold at least one token")
+        if cache_batch_idx is not None:
+            if cache_batch_idx.shape != (b,):
+                raise RuntimeError(f"{who}: cache_batch_idx must be an int32 tensor of shape (B,) = ({b},)")
+            cache_batch_idx = cache_batch_idx.contiguous()
+            cbatch = k_cache.shape[0]
+        elif k_cache.shape[0] != b:
+            raise RuntimeError(f"{who}: the caches hold {k_cache.shape[0]} rows for a batch of {b} (pass cache_batch_idx to select rows)")
+        else:
+            cbatch = 0
+        pages = (0, 0, 0)
+    if cache_seqlens is not None:
+        cache_seqlens = cache_seqlens.contiguous()
+    qdp, qds, keep_q = _kv_descale(who, "q_descale", q_descale, q, b, hkv)
+    kdp, kds, keep_k = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
+    vdp, vds, keep_v = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
+    with torch.cuda.device(q.device):
+        o = torch.empty((b, nq, hq, 128), dtype=out_dtype, device=q.device)
+        lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)
+        if b == 0 or nq == 0:
+            return o, lse
+        need = int(_lib.fa_fp8_forward_kvcache_workspace_bytes(b, hq, hkv, nq, cap, 128, ns))
+        ws = _workspace(q.device, need)
+        _call("fa_fp8_forward_kvcache", (
+            q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp,
+            cache_seqlens.data_ptr() if cache_seqlens is not None else 0, block_table.data_ptr() if paged else 0,
+            cache_batch_idx.data_ptr() if cache_batch_idx is not None else 0, b, hq, hkv, nq, cap, cbatch, 128, _DTYPE_CODE[out_dtype],
+            _E4M3_CODE, _E4M3_CODE, max(q.stride(0), 0) if b > 1 else 0, tstride(q, hq),
+            k_cache.stride(0) if k_cache.shape[0] > 1 else 0, tstride(k_cache, hkv),
+            v_cache.stride(0) if v_cache.shape[0] > 1 else 0, tstride(v_cache, hkv), *pages, qds, kds, vds, int(bool(causal)), scale, ns,
+            ws.data_ptr() if need else 0, ws.numel() if need else 0, _stream_ptr(q.device)))
     del keep_q, keep_k, keep_v
     return o, lse

@@ -1178,6 +1178,55 @@ int fa_fp8_forward_varlen(const void* q, const void* k, const void* v, void* o, 
 size_t fa_fp8_forward_varlen_workspace_bytes(int64_t batch, int64_t heads_kv, int64_t total_k, int64_t max_seqlen_k,
                                              int64_t max_blocks_per_seq, int64_t page_block_size, int64_t d);
 
+/* --- fp8 KV-cache decoding with split-KV: an e4m3 q over the e4m3 cache that fa_ex_forward_kvcache_fp8 writes.
+ * Forward only; a call family of its own.  Both products run on the e4m3 matrix instruction:
+ *     s[i, j] = softmax_scale * q_descale * k_descale * (q8[i] . k8[j]),   o[i] = sum_j softmax(s)[i, j] * v8[j] * v_descale
+ * P is rounded to e4m3 on every row; l and lse come from the unrounded p.
+ * q is (batch, seqlen_q, heads_q, 128) raw e4m3 bytes at its batch and token strides (heads adjacent, 128 bytes each).  Without
+ * block_table the caches are (cache_batch or batch, cache_len, heads_kv, 128) e4m3 at their batch and token strides; with
+ * block_table, an int32 (batch, cache_len / page_block_size) device tensor at block_table_row_stride, they are pools (num_blocks,
+ * page_block_size, heads_kv, 128), k_batch_stride / v_batch_stride are the page strides and cache_len is the capacity
+ * max_blocks_per_seq * page_block_size, as fa_ex_kvcache_workspace_bytes documents.  All strides are in bytes.  q_dtype and
+ * cache_dtype must be FA_DTYPE_E4M3 (a 16-bit q is fa_ex_forward_kvcache_fp8's call); dtype names o's type, f16 or bf16.
+ * len[b] = clamp(cache_seqlens[b], 0, cache_len) on the device (NULL: cache_len).  cache_batch_idx (contiguous form only; then
+ * cache_batch > 0 is the caches' row count, else 0): sequence b lives in row cache_batch_idx[b]; an index outside [0, cache_batch)
+ * gives an empty sequence.  Query head h reads K/V head h / (heads_q / heads_kv).  causal is bottom-right aligned: key j is visible
+ * to token i iff j <= len[b] - seqlen_q + i.  Descales: float32 (batch, heads_kv) device tensors at their batch strides (0: one row
+ * for every batch element), NULL = 1; finite and > 0 is the caller's contract.
+ * o is (batch, seqlen_q, heads_q, 128) contiguous in dtype, lse float32 (batch, heads_q, seqlen_q) contiguous, natural log.  A row
+ * without a visible key gives o = 0, lse = -inf.
+ * Nothing is read on the host: lengths, table, indices and descales are untrusted device memory, and a captured call replays after
+ * they changed in place.  A page outside [0, num_blocks) reads as zero K and zero V and takes part with score 0; no table entry
+ * past ceil(len[b] / page_block_size) is read; bytes of the caches that no live token owns never reach a result.
+ * num_splits: 0 = the library's rule (kv_num_splits' constants over 32-row tiles), else 1 .. 256.  Workspace: the caller's,
+ * fa_fp8_forward_kvcache_workspace_bytes(...) bytes (0 for one split): fp32 partials in fa_ex_kvcache_workspace_bytes' layout.  One
+ * launch, or two with more than one split.
+ * Span limits (FA_ERR_UNSUPPORTED, "span limit"): seqlen_q * q_token_stride, and cache_len * token stride (contiguous) or
+ * page_block_size * token stride (paged) of both caches, below 2^31; cache_len below 2^28.  Batch and page offsets are 64-bit.
+ * Checked before any HIP call, the first broken rule named in fa_last_error(), in this order: (0) batch == 0 or seqlen_q == 0 is the
+ * empty call, FA_OK; (1) q, k_cache, v_cache, o, lse non-null; (2) d == 128, q_dtype and cache_dtype FA_DTYPE_E4M3, dtype f16 or
+ * bf16, else FA_ERR_UNSUPPORTED; (3) heads_q, heads_kv > 0 and heads_q % heads_kv == 0; (4) batch in [1, 65535], seqlen_q >= 1,
+ * cache_len >= 1, (heads_q / heads_kv) * seqlen_q <= 2^20, softmax_scale finite and > 0, cache_batch in [1, 2^31) with
+ * cache_batch_idx and 0 without; (5) q, k_cache, v_cache, o 16-byte aligned, lse, cache_seqlens, block_table and cache_batch_idx
+ * 4-byte aligned, token strides multiples of 16 and >= heads * 128, batch / page strides multiples of 16, >= 0 and <= 2^44; (6) a
+ * descale stride 0 or >= heads_kv (0 with a NULL descale), descales 4-byte aligned; (7) with block_table no cache_batch_idx,
+ * page_block_size a multiple of 16 in [16, 65536] that divides cache_len, num_blocks in [1, 2^31), block_table_row_stride >=
+ * cache_len / page_block_size, without it the three page arguments 0; (8) the span limits (FA_ERR_UNSUPPORTED); (9) num_splits in
+ * [0, 256]; (10) with more than one split workspace non-null with workspace_bytes >= the need (FA_ERR_WORKSPACE), 16-byte aligned.
+ * Everything else is FA_ERR_INVALID_ARGUMENT. */
+int fa_fp8_forward_kvcache(const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const float* q_descale,
+                           const float* k_descale, const float* v_descale, const int32_t* cache_seqlens, const int32_t* block_table,
+                           const int32_t* cache_batch_idx, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q,
+                           int64_t cache_len, int64_t cache_batch, int64_t d, int dtype, int q_dtype, int cache_dtype,
+                           int64_t q_batch_stride, int64_t q_token_stride, int64_t k_batch_stride, int64_t k_token_stride,
+                           int64_t v_batch_stride, int64_t v_token_stride, int64_t block_table_row_stride, int64_t num_blocks,
+                           int64_t page_block_size, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
+                           int64_t v_descale_batch_stride, int causal, double softmax_scale, int64_t num_splits, void* workspace,
+                           size_t workspace_bytes, void* stream);
+/* cache_len: the capacity (paged: max_blocks_per_seq * page_block_size); 0 for arguments the call would refuse */
+size_t fa_fp8_forward_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
+                                              int64_t d, int64_t num_splits);
+
 /* --- support entry points (no reference counterpart: the reference allocates inside the callee) --- */
 /* bytes for the CURRENT kernel mode: two float row constants per query row (+ an fp32 dQ scratch of bh*n*d floats in
  * FA_MODE_BWD_ATOMIC only); ask again after changing the mode */

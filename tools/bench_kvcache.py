@@ -59,6 +59,10 @@ and V are then 1 an element.  ex_forward and the unfused rotation keep the 16-bi
   tokens read per second in each format, and the ratio packed / 16-bit.  Then the append (ex_mla_fp8_pack) of 1, 512 and 8192 new
   tokens to each of 32 sequences, with and without power-of-two scales, against the bytes it moves (1152 read + 656 written a
   token): eager calls, and the same calls replayed from one captured graph (without the wrapper and the launch path).
+`--fp8-q`: fp8 KV-cache decoding (fp8_kvcache_forward: e4m3 q on the e4m3 matrix instruction) against the yardstick, the e4m3-cache
+  call with a 16-bit q on the same cache, interleaved in one process: B 32 / H 32:8 / L 8192 / Nq 1, B 1 / L 65536, B 8 / Nq 4 causal /
+  L 4096, each contiguous and paged with ps 16 and 256.  Per row the median of `--rounds` (at least 5) interleaved rounds of both
+  calls, the yardstick's own spread over its rounds, and the cache bytes moved over the time against the copy rate.
 Timing: HIP events around `--iters` back-to-back calls after `--warmup` calls; the median of `--reps` such groups."""
 import argparse
 import json
@@ -510,6 +514,46 @@ def mla_fp8_rows(args):
     return rows
 
 
+def fp8q_rows(args, dtype):
+    """--fp8-q: see the module docstring"""
+    dev, rounds = "cuda", max(args.rounds, 5)
+    rows = []
+    for b, nq, L, causal in ((32, 1, 8192, False), (1, 1, 65536, False), (8, 4, 4096, True)):
+        hq, hkv = 32, 8
+        q16 = torch.randn((b, nq, hq, 128), device=dev, dtype=dtype)
+        (kc, kd), (vc, vd) = (quantise(torch.randn((b, L, hkv, 128), device=dev, dtype=dtype)) for _ in range(2))
+        q8 = q16.float().clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+        qd = torch.ones((b, hkv), dtype=torch.float32, device=dev)
+        sl = torch.full((b,), L, dtype=torch.int32, device=dev)
+        nbytes = 2 * b * L * hkv * 128
+        for ps in (0, 16, 256):
+            if ps:
+                nblk = b * L // ps
+                perm = torch.randperm(nblk, device=dev)
+                table = perm.view(b, L // ps).to(torch.int32)
+                kk, vv = torch.empty_like(kc).view(nblk, ps, hkv, 128), torch.empty_like(vc).view(nblk, ps, hkv, 128)
+                kk[perm] = kc.view(nblk, ps, hkv, 128)
+                vv[perm] = vc.view(nblk, ps, hkv, 128)
+            else:
+                table, kk, vv = None, kc, vc
+            old = lambda: ext.ex_kvcache_forward(q16, kk, vv, None, None, sl, causal, None, block_table=table, k_descale=kd,   # noqa: E731
+                                                 v_descale=vd)
+            new = lambda: ext.fp8_kvcache_forward(q8, kk, vv, sl, table, None, qd, kd, vd, None, causal, 0, dtype)   # noqa: E731
+            t_old, t_new = [], []
+            for _ in range(rounds):
+                t_old.append(timed(old, args.warmup, args.iters, 1))
+                t_new.append(timed(new, args.warmup, args.iters, 1))
+            m_old, m_new = statistics.median(t_old), statistics.median(t_new)
+            rows.append(dict(b=b, nq=nq, L=L, causal=causal, page_size=ps, yardstick_us=round(m_old, 2), fp8q_us=round(m_new, 2),
+                             ratio=round(m_new / m_old, 3), yardstick_spread=round((max(t_old) - min(t_old)) / m_old, 3),
+                             fp8q_spread=round((max(t_new) - min(t_new)) / m_new, 3),
+                             yardstick_TBps=round(nbytes / m_old / 1e6, 3), fp8q_TBps=round(nbytes / m_new / 1e6, 3),
+                             fp8q_of_copy_rate=round(nbytes / m_new * 1e6 / COPY_RATE, 3)))
+            print(json.dumps(rows[-1]), flush=True)
+        del kc, vc
+    return rows
+
+
 def parent_check(args, dtype):
     dev, b, h, n, d = "cuda", 2, 32, 4096, 128
     q, k, v = (torch.randn((b * n, h, d), device=dev, dtype=dtype) for _ in range(3))
@@ -548,6 +592,7 @@ def main():
     ap.add_argument("--mla", action="store_true", help="time the call with qv (64 + 512 head dims): see the module docstring")
     ap.add_argument("--mla-sparse", action="store_true", help="time the sparse MLA call against the dense qv call at equal keys: see the module docstring")
     ap.add_argument("--mla-fp8", action="store_true", help="time the packed 8-bit latent cache against the 16-bit paged call, and the append: see the module docstring")
+    ap.add_argument("--fp8-q", action="store_true", help="time fp8 KV-cache decoding (e4m3 q) against the e4m3-cache call with a 16-bit q: see the module docstring")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     args.chunks = [int(x) for x in args.chunks.split(",")]
@@ -562,6 +607,12 @@ def main():
         ext.ex_kvcache_forward(wq, wk, wk, None, None, wl, True, None)
     torch.cuda.synchronize()
     del wq, wk
+    if args.fp8_q:
+        rows = fp8q_rows(args, dtype)
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(dict(fp8_q=True, dtype=args.dtype, version=ext.version(), copy_rate_TBps=COPY_RATE / 1e12, rows=rows), f, indent=1)
+        return
     if args.mla_fp8:
         rows = mla_fp8_rows(args)
         if args.json:
