@@ -60,6 +60,13 @@ namespace fa {
             asm volatile("ds_read_b128 %0, %2 offset:%5\n\t" WAIT("%6") OPC " %1, %3, %4, %1"             \
                          : "=&v"(r0), "+a"(c) : "v"(qa), "v"(a), "v"(b), "n"(OFF), "n"(N));                             \
         }                                                                                                               \
+        /* lean form, k-step 0 of a chain pair: C (the row constants, loaded once) and D (key block 1's accumulator) are   */ \
+        /* different registers; the next MFMA accumulates key block 0 into C's registers in place (one in-order matrix pipe: */ \
+        /* this MFMA has read C before that one writes it)                                                                  */ \
+        template <int N, int OFF> static __device__ __forceinline__ void fb_vcd(unsigned qa, s16x8& r0, s16x8 a, s16x8 b, const f32x16& c, f32x16& d) { \
+            asm volatile("ds_read_b128 %0, %2 offset:%6\n\t" WAIT("%7") OPC " %1, %3, %4, %5"             \
+                         : "=&v"(r0), "=&v"(d) : "v"(qa), "v"(a), "v"(b), "v"(c), "n"(OFF), "n"(N));                     \
+        }                                                                                                               \
         template <int N, int OFF> static __device__ __forceinline__ void ft_v(unsigned lo_a, unsigned hi_a, s16x4& lo, s16x4& hi, s16x8 a, s16x8 b, f32x16& c) { \
             asm volatile("ds_read_b64_tr_b16 %0, %3 offset:%7\n\tds_read_b64_tr_b16 %1, %4 offset:%7\n\t" WAIT("%8") OPC " %2, %5, %6, %2" \
                          : "=&v"(lo), "=&v"(hi), "+v"(c) : "v"(lo_a), "v"(hi_a), "v"(a), "v"(b), "n"(OFF), "n"(N));     \
@@ -208,6 +215,84 @@ constexpr Op kSched[64][kWidth] = {
 };
 }  // namespace w4sched
 
+// The table of the LEAN form (template flag LEAN = 3, below): a launch no block of which can need the mask loads the row
+// constants ONCE per block (ACC(0) -> S'[0], ACC(2) -> dP'[0]; k-step 0 of key block 1 takes them as its C operand) and reads its
+// operands through immediates of a block body per tile buffer: no QADDR / TADDR.  Its dS stores are in the table too.
+namespace w4lean {
+using w4sched::Op; using w4sched::MUL; using w4sched::EXP; using w4sched::PC; using w4sched::SU; using w4sched::ACC; using w4sched::DMA; using w4sched::LADDR;
+constexpr unsigned char OP_DSST = 10;
+constexpr Op DSST(int kb, int half) { return {OP_DSST, (unsigned char)kb, (unsigned char)half}; }
+// generated by tools/gen_dkdv_schedule.py --lean --ds: 0 cycles over budget in 0 gaps
+// slice S (after MFMA S): up to 5 operations
+constexpr Op kSched[64][w4sched::kWidth] = {
+    /*  0 (24) */ {DMA(0)},
+    /*  1 ( 8) */ {LADDR},
+    /*  2 (24) */ {DMA(1)},
+    /*  3 ( 8) */ {},
+    /*  4 (24) */ {DMA(2)},
+    /*  5 ( 8) */ {},
+    /*  6 (24) */ {DMA(3)},
+    /*  7 ( 8) */ {},
+    /*  8 (24) */ {DMA(4)},
+    /*  9 (16) */ {},
+    /* 10 (24) */ {},
+    /* 11 (16) */ {},
+    /* 12 (24) */ {},
+    /* 13 (16) */ {},
+    /* 14 (24) */ {},
+    /* 15 (16) */ {},
+    /* 16 (24) */ {MUL(0,0), EXP(0,0), MUL(0,1), EXP(0,1)},
+    /* 17 (16) */ {MUL(0,2), EXP(0,2), MUL(0,3)},
+    /* 18 (24) */ {EXP(0,3), MUL(0,4), EXP(0,4), MUL(0,5)},
+    /* 19 (16) */ {EXP(0,5), MUL(0,6), MUL(0,7)},
+    /* 20 (24) */ {EXP(0,6), EXP(0,7), PC(0,0), PC(0,1)},
+    /* 21 (16) */ {PC(0,2), PC(0,3), MUL(1,0), MUL(1,1)},
+    /* 22 (24) */ {EXP(1,0), EXP(1,1), MUL(1,2), MUL(1,3)},
+    /* 23 (16) */ {EXP(1,2), EXP(1,3)},
+    /* 24 (24) */ {MUL(1,4), EXP(1,4), MUL(1,5), EXP(1,5)},
+    /* 25 (12) */ {MUL(1,6), EXP(1,6)},
+    /* 26 (24) */ {MUL(1,7), EXP(1,7), PC(1,0), PC(1,1), PC(1,2)},
+    /* 27 (12) */ {PC(1,3), MUL(0,8), MUL(0,9)},
+    /* 28 (24) */ {EXP(0,8), EXP(0,9), MUL(0,10), MUL(0,11)},
+    /* 29 (12) */ {EXP(0,10), MUL(0,12)},
+    /* 30 (24) */ {EXP(0,11), EXP(0,12), MUL(0,13), MUL(0,14)},
+    /* 31 (12) */ {EXP(0,13), MUL(0,15)},
+    /* 32 (24) */ {EXP(0,14), EXP(0,15), PC(0,4), PC(0,5)},
+    /* 33 (12) */ {PC(0,6), PC(0,7), MUL(1,8)},
+    /* 34 (24) */ {EXP(1,8), MUL(1,9), EXP(1,9), MUL(1,10)},
+    /* 35 (12) */ {EXP(1,10), MUL(1,11)},
+    /* 36 (24) */ {EXP(1,11), MUL(1,12), EXP(1,12), MUL(1,13)},
+    /* 37 (12) */ {EXP(1,13), MUL(1,14)},
+    /* 38 (24) */ {EXP(1,14), MUL(1,15), EXP(1,15), PC(1,4)},
+    /* 39 (12) */ {PC(1,5), PC(1,6), PC(1,7)},
+    /* 40 (24) */ {SU(0,0), SU(0,1)},
+    /* 41 (12) */ {SU(0,2)},
+    /* 42 (24) */ {SU(0,3), SU(1,0)},
+    /* 43 (12) */ {SU(1,1)},
+    /* 44 (24) */ {SU(1,2), SU(1,3)},
+    /* 45 (12) */ {SU(0,4)},
+    /* 46 (24) */ {SU(0,5), SU(0,6)},
+    /* 47 (12) */ {SU(0,7)},
+    /* 48 (24) */ {SU(1,4), SU(1,5)},
+    /* 49 (12) */ {SU(1,6)},
+    /* 50 (24) */ {SU(1,7), DSST(0,0)},
+    /* 51 (12) */ {DSST(0,1)},
+    /* 52 (24) */ {ACC(0), DSST(1,0)},
+    /* 53 (12) */ {DSST(1,1)},
+    /* 54 (24) */ {ACC(2)},
+    /* 55 (12) */ {},
+    /* 56 (24) */ {},
+    /* 57 ( 8) */ {},
+    /* 58 (24) */ {},
+    /* 59 ( 8) */ {},
+    /* 60 (24) */ {},
+    /* 61 ( 8) */ {},
+    /* 62 (24) */ {},
+    /* 63 ( 8) */ {},
+};
+}  // namespace w4lean
+constexpr w4sched::Op w4_op(int lean, int S, int j) { return lean == 3 ? w4lean::kSched[S][j] : w4sched::kSched[S][j]; }
+
 // DS: the variant that hands dS to the dQ product kernel (fa_bwd_dq_ds.hip) instead of leaving dQ to a pass that recomputes S
 // and dP.  The packed dS of a block — already the B operand of the dK^T products, 4 x 16 bytes per lane — is stored as it
 // is: tile (b,h; 32-query block qb; 32-key block kb) of 2 KiB at ds + (((b,h) nqb + qb) nkb32 + kb) 2048 bytes, inside it
@@ -219,7 +304,18 @@ constexpr Op kSched[64][kWidth] = {
 // S' groups request fewer fragments, so there is room for all of them: KR = 1 key block 0 (2 fragments per S' group, 10-slot ring),
 // 2 + four fragments of block 1 (12 slots), 3 every K fragment (Q rows only, 8 slots): 32 operand fragments per block from LDS
 // instead of 48 (0.5 KB per MFMA instead of 0.75), 250 - 252 VGPRs, no scratch.
-template <typename Tag, bool CAUSAL, int ABL = 0, int TPW = (CAUSAL ? 2 : 1), bool DS = false, int KR = 0>
+// LEAN (DS, KR = 3, no mask; the launcher picks it when no block of the launch can need one: non-causal and nk a multiple of the
+// 256-key tile — query rows past n need no condition of their own: their Q, dO and row constants read as 0 through the buffer
+// bounds, so P = 1, dP' = 0, dS = 0 and they add nothing to dK or dV, here as in the masked form): what one block body for masked
+// and unmasked launches alike costs the unmasked ones, taken out.  Bit 0: the row constants are read once per block — the two key
+// blocks of a wave see the same 32 queries; the second copy exists for mask_init's per-key-block patterns — into S'[0] / dP'[0], and
+// k-step 0 of key block 1 issues first, with them as its C operand and S'[1] / dP'[1] as its D (fb_vcd above); key block 0 then
+// accumulates in place.  Every chain keeps its order: dK, dV and dS are bitwise the masked form's.  Bit 1: the block loop is
+// unrolled by the NBUF tile buffers and the buffer's offset sits in the offset: field of every operand request (3 BUF + QT + 4096 =
+// 64512 fits its 16 bits): 16 of the 17 address updates per block and their select go; the row-constant address (its last offset
+// would be 68960) stays a register.  Both bits drop mask_init and its compare from the loop.  LEAN = 3 takes its placement from
+// w4lean::kSched; 1 and 2 (A/B of one piece, option dkdv_lean) take the table above with the dead operations' slots left empty.
+template <typename Tag, bool CAUSAL, int ABL = 0, int TPW = (CAUSAL ? 2 : 1), bool DS = false, int KR = 0, int LEAN = 0>
 __global__ __launch_bounds__(256, 1) void bwd_dkdv_w4_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                              const uint16_t* __restrict__ v,
                                                              const uint16_t* __restrict__ dout,
@@ -233,6 +329,8 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv_w4_kernel(const uint16_t* __r
     // operand groups requested ahead of use (6 MFMAs).  4 live groups x 3 fragments = 12 ring slots; with 16 a request
     // never lands on a fragment the two MFMAs just issued are still reading (hipcc would pad that hazard with an s_nop)
     constexpr int AHEAD = 3;
+    constexpr bool ONCE = (LEAN & 1) != 0, FIXED = (LEAN & 2) != 0;   // row constants once / operand addresses fixed (offsets immediate)
+    static_assert(!LEAN || (DS && KR == 3 && !CAUSAL && TPW == 1 && !(ABL & ~32)), "the lean form: unmasked dS-storing launches, every K fragment in registers");
     constexpr int K_BYTES = BK * D * 2;          // 64 KiB: the workgroup's K rows (B operand of S)
     constexpr int QT = BQ * D * 2;               // 8 KiB: one 32-row tile of Q (or dO)
     constexpr int BUF = 2 * QT + 1024;           // Q | dO | 64 x -lse/scale | 64 x -delta | 2 x 64 unused (see dma_piece)
@@ -272,10 +370,10 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv_w4_kernel(const uint16_t* __r
     int qs_first = 0, nblk = 0;                  // first query of the current tile's sweep, 32-query blocks in it
     const unsigned bbase = lds_addr_of(Bs);
     // one LDS-DMA piece (1 KiB = 4 rows) of tile t: J = 0, 1 -> Q, J = 2, 3 -> dO, J = 4 -> the wave's row constants
-    auto dma_piece = [&](auto jc, int t) {
+    auto dma_piece = [&](auto jc, int t, int buf = -1 /* FIXED: t % NBUF as the block body knows it */) {
         constexpr int J = decltype(jc)::value;
         const int qs = qs_first + BQ * t;
-        const unsigned b = bbase + (t & (NBUF - 1)) * BUF;
+        const unsigned b = bbase + (buf >= 0 ? buf : (t & (NBUF - 1))) * BUF;
         if constexpr (J < 4) {
             const int pc = w + 4 * (J & 1);
             dma16_issue_s(J < 2 ? q_rs : o_rs, b + (J < 2 ? 0 : QT) + pc * 1024, dma_voff, (qs + 4 * pc) * 2 * D);
@@ -369,8 +467,9 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv_w4_kernel(const uint16_t* __r
             }
         }
     };
-    auto block = [&](int blk) {
-        const int dlt = ((blk + 1) & (NBUF - 1)) ? BUF : -(NBUF - 1) * BUF;   // to the next tile's buffer
+    auto block = [&](int blk, auto bic) {
+        constexpr int BI = decltype(bic)::value;   // FIXED: the tile buffer of this block, blk % NBUF, known to the body (else 0, unused)
+        const int dlt = FIXED ? (BI == NBUF - 1 ? -(NBUF - 1) * BUF : BUF) : (((blk + 1) & (NBUF - 1)) ? BUF : -(NBUF - 1) * BUF);   // to the next tile's buffer
         // Vector work, cut into single instructions' worth and placed by the table above (w4sched::kSched): MUL + EXP: one
         // element of S' -> P = exp2(c S') in place (the f32 P is what dS is made from, as in the dQ kernel);  PC: one packed
         // dword of P from two finished elements (at least one gap behind its exp2's: no dependency stall, no hazard nop);
@@ -401,23 +500,26 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv_w4_kernel(const uint16_t* __r
         };
         auto slice = [&](auto sc) {
             constexpr int S = decltype(sc)::value;
+            if constexpr (LEAN != 3) {   // (w4lean::kSched places the stores itself)
             if constexpr (DS && !(ABL & 64) && S >= 52 && S < 56) DSST(integral_constant<int, ((S - 52) / 2)>{}, integral_constant<int, ((S - 52) % 2)>{});
+            }
             {   // ABL bits: see the kernel's header comment
                 for_each_const([&](auto jc) {
-                    constexpr w4sched::Op o = w4sched::kSched[S][decltype(jc)::value];
+                    constexpr w4sched::Op o = w4_op(LEAN, S, decltype(jc)::value);
                     constexpr int a = o.a, b = o.b;
                     if constexpr (o.op == w4sched::OP_MUL && !(ABL & 1)) sacc[a][b] *= c_log2;
                     else if constexpr (o.op == w4sched::OP_EXP && !(ABL & 1)) sacc[a][b] = __builtin_amdgcn_exp2f(sacc[a][b]);
                     else if constexpr (o.op == w4sched::OP_PC && !(ABL & 1)) PC(integral_constant<int, a>{}, integral_constant<int, b>{});
                     else if constexpr (o.op == w4sched::OP_SU && !(ABL & 1)) SU(integral_constant<int, a>{}, integral_constant<int, b>{});
-                    else if constexpr (o.op == w4sched::OP_ACC && !(ABL & 8)) {
+                    else if constexpr (o.op == w4sched::OP_ACC && !(ABL & 8) && !(ONCE && (a & 1))) {
                         if constexpr (a < 2) lds_acc_init_asm<0>(laddr, sacc[a]);
                         else lds_acc_init_asm<256>(laddr, pacc[a - 2]);
                     }
-                    else if constexpr (o.op == w4sched::OP_DMA && !(ABL & 2)) dma_piece(integral_constant<int, a>{}, blk + 3);
+                    else if constexpr (o.op == w4sched::OP_DMA && !(ABL & 2)) dma_piece(integral_constant<int, a>{}, blk + 3, FIXED ? (BI + 3) % NBUF : -1);
                     else if constexpr (o.op == w4sched::OP_LADDR && !(ABL & 16)) laddr += dlt;
-                    else if constexpr (o.op == w4sched::OP_QADDR && !(ABL & 16)) qaddr[a] += dlt;
-                    else if constexpr (o.op == w4sched::OP_TADDR && !(ABL & 16)) { tlo[a] += dlt; thi[a] += dlt; }
+                    else if constexpr (o.op == w4sched::OP_QADDR && !(ABL & 16) && !FIXED) qaddr[a] += dlt;
+                    else if constexpr (o.op == w4sched::OP_TADDR && !(ABL & 16) && !FIXED) { tlo[a] += dlt; thi[a] += dlt; }
+                    else if constexpr (o.op == w4lean::OP_DSST) DSST(integral_constant<int, a>{}, integral_constant<int, b>{});
                 }, std::make_integer_sequence<int, w4sched::kWidth>{});
             }
         };
@@ -433,9 +535,11 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv_w4_kernel(const uint16_t* __r
                 int c = 0;
                 for (int S = 2 * g - 4; S <= 2 * g - 1; ++S)
                     for (int j = 0; j < w4sched::kWidth; ++j)
-                        if (w4sched::kSched[(S + 64) % 64][j].op == w4sched::OP_ACC) c += 4;
+                        if (w4_op(LEAN, (S + 64) % 64, j).op == w4sched::OP_ACC && !(ONCE && (w4_op(LEAN, (S + 64) % 64, j).a & 1))) c += 4;
                 return c;
             }();
+            // FIXED: the buffer of the group requested here (groups 29 .. 31 request the next block's groups 0 .. 2) as an immediate
+            constexpr int BO = FIXED ? ((BI + (g + AHEAD >= 32 ? 1 : 0)) % NBUF) * BUF : 0;
             constexpr int NWAIT = G::reads(g + 2) + G::reads(g + 3) + ((ABL & 8) ? 0 : ACCS);
             using M = W4Stream<Tag, WAITS>;
             constexpr int g2 = (g + AHEAD) % 32, ph2 = g2 / 8, i2 = g2 % 8, t0 = G::slot(g2);   // the group requested here
@@ -451,12 +555,17 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv_w4_kernel(const uint16_t* __r
             else { opb0 = *reinterpret_cast<s16x8*>(&sp[0][i / 4]); opb1 = *reinterpret_cast<s16x8*>(&sp[1][i / 4]); }
             f32x16& acc0 = ph == 0 ? sacc[0] : (ph == 1 ? pacc[0] : (ph == 2 ? dva[0][i % 4] : dka[0][i % 4]));
             f32x16& acc1 = ph == 0 ? sacc[1] : (ph == 1 ? pacc[1] : (ph == 2 ? dva[1][i % 4] : dka[1][i % 4]));
-            if constexpr (ABL & 4) {
+            // ONCE, k-step 0 of the S' and of the dP' chains: key block 1 first, C = the row constants in acc0, D = acc1
+            constexpr bool CD = ONCE && ph < 2 && i == 0;
+            if constexpr (CD) {
+                static_assert(ph2 < 2 && (ph2 == 1 || i2 < K1R), "groups 0 and 8 request one row fragment");
+                M::template fb_vcd<NWAIT, BO + (ph2 == 1 ? QT : 0)>(qaddr[i2], ring[t0], opa, opb1, acc0, acc1);
+            } else if constexpr (ABL & 4) {
                 if constexpr (ph < 2) M::v(opa, opb0, acc0);
                 else M::a(opa, opb0, acc0);
             } else if constexpr (ph2 == 0 && i2 < K1R) {   // Q rows only
-                if constexpr (ph < 2) M::template fb_v<NWAIT, 0>(qaddr[i2], ring[t0], opa, opb0, acc0);
-                else M::template fb_a<NWAIT, 0>(qaddr[i2], ring[t0], opa, opb0, acc0);
+                if constexpr (ph < 2) M::template fb_v<NWAIT, BO>(qaddr[i2], ring[t0], opa, opb0, acc0);
+                else M::template fb_a<NWAIT, BO>(qaddr[i2], ring[t0], opa, opb0, acc0);
             } else if constexpr (ph2 == 0 && KR) {
                 if constexpr (ph < 2) M::template f2_v<NWAIT>(qaddr[i2], kaddr[i2], ring[t0], ring[(t0 + 1) % RS], opa, opb0, acc0);
                 else M::template f2_a<NWAIT>(qaddr[i2], kaddr[i2], ring[t0], ring[(t0 + 1) % RS], opa, opb0, acc0);
@@ -465,9 +574,10 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv_w4_kernel(const uint16_t* __r
                 else M::template fa_a<NWAIT>(qaddr[i2], kaddr[i2], ring[t0], ring[(t0 + 1) % RS], ring[(t0 + 2) % RS], opa, opb0, acc0);
             } else if constexpr (ph2 == 1) {
                 static_assert(ph < 2, "dO rows are requested during the S' and dP' chains");
-                M::template fb_v<NWAIT, QT>(qaddr[i2], ring[t0], opa, opb0, acc0);
+                M::template fb_v<NWAIT, BO + QT>(qaddr[i2], ring[t0], opa, opb0, acc0);
             } else {
-                constexpr int off = (ph2 == 2 ? QT : 0) + (i2 / 4) * 16 * 2 * D;
+                constexpr int off = BO + (ph2 == 2 ? QT : 0) + (i2 / 4) * 16 * 2 * D;
+                static_assert(off < 65536, "offset: field of the LDS read");
                 s16x4 lo, hi;
                 if constexpr (ph < 2) M::template ft_v<NWAIT, off>(tlo[i2 % 4], thi[i2 % 4], lo, hi, opa, opb0, acc0);
                 else M::template ft_a<NWAIT, off>(tlo[i2 % 4], thi[i2 % 4], lo, hi, opa, opb0, acc0);
@@ -476,7 +586,8 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv_w4_kernel(const uint16_t* __r
             __builtin_amdgcn_sched_barrier(0);
             slice(integral_constant<int, 2 * g>{});
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (ph < 2) M::v(opa, opb1, acc1);
+            if constexpr (CD) M::v(opa, opb0, acc0);   // key block 0, in place over the row constants
+            else if constexpr (ph < 2) M::v(opa, opb1, acc1);
             else M::a(opa, opb1, acc1);
             __builtin_amdgcn_sched_barrier(0);
             slice(integral_constant<int, 2 * g + 1>{});
@@ -568,10 +679,10 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv_w4_kernel(const uint16_t* __r
         if (last && fb < nblk) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // nothing older may sit in the LDS queue: the counts are exact
             lds_acc_init<0>(laddr, sacc[0]);
-            lds_acc_init<0>(laddr, sacc[1]);
-            mask_init(fb);
+            if constexpr (!ONCE) lds_acc_init<0>(laddr, sacc[1]);
+            if constexpr (!LEAN) mask_init(fb);
             lds_acc_init<256>(laddr, pacc[0]);
-            lds_acc_init<256>(laddr, pacc[1]);
+            if constexpr (!ONCE) lds_acc_init<256>(laddr, pacc[1]);
             fetch(std::integral_constant<int, 0>{});
             fetch(std::integral_constant<int, 1>{});
             fetch(std::integral_constant<int, 2>{});
@@ -586,9 +697,36 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv_w4_kernel(const uint16_t* __r
         __builtin_amdgcn_sched_barrier(0);
         unsigned long long t_begin = 0;
         if (ABL & 32) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_begin)::"memory");
+        if constexpr (LEAN) {
+            // no mask branch; FIXED: a block body per tile buffer (fb = 0: block blk streams from buffer blk % NBUF), left at the
+            // seam behind the last block — the remainder of nblk / NBUF needs no bodies of its own
+            auto seam = [&](int blk) {
+                dsp += (unsigned long long)nkb32 * 2048;
+                wait_tiles(blk == 0);
+                __builtin_amdgcn_s_barrier();
+            };
+            int blk = 0;
+#pragma unroll 1
+            for (;;) {
+                block(blk, std::integral_constant<int, 0>{});
+                seam(blk);
+                if (++blk >= nblk) break;
+                if constexpr (FIXED) {
+                    block(blk, std::integral_constant<int, 1>{});
+                    seam(blk);
+                    if (++blk >= nblk) break;
+                    block(blk, std::integral_constant<int, 2>{});
+                    seam(blk);
+                    if (++blk >= nblk) break;
+                    block(blk, std::integral_constant<int, 3>{});
+                    seam(blk);
+                    if (++blk >= nblk) break;
+                }
+            }
+        } else {
 #pragma unroll 1
         for (int blk = fb; blk < nblk; ++blk) {
-            block(blk);
+            block(blk, std::integral_constant<int, 0>{});
             if (DS && (ABL & 32) && L == 0 && blk < 24) {   // per-wave stamps of blocks 0 .. 23 of workgroup 0's last tile: own work done, dk[32 + 64 w + 2 blk]
                 unsigned long long t_now;
                 asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_now)::"memory");
@@ -605,6 +743,7 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv_w4_kernel(const uint16_t* __r
                 asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_now)::"memory");
                 if (lane == 0) reinterpret_cast<unsigned*>(dk)[32 + 64 * w + 2 * blk + 1] = (unsigned)t_now;
             }
+        }
         }
         if (ABL & 32) {
             unsigned long long t_end;
@@ -680,6 +819,20 @@ static hipError_t launch_dkdv_w4_t(const BwdArgs& a, const float* nlse, const fl
     // Option dkdv_kreg: 2 = none (the round-2 form), 3 = key block 0 only, 4 = block 0 + four fragments of block 1.
     const int kro = option(OPT_DKDV_KREG);
     const int kr = kro == 2 ? 0 : (kro == 3 ? 1 : (kro == 4 ? 2 : 3));
+    // The lean form: no block of the launch can need the mask — non-causal, and every wave's 64 keys exist (nk a multiple of the
+    // workgroup's 256-key tile; query rows past n need no condition: the kernel's header comment) — and every K fragment is in
+    // registers.  Option dkdv_lean: 2 = the general form (A/B runs), 3 = row constants once only, 4 = fixed addresses only.
+    const int lo = option(OPT_DKDV_LEAN);
+    if (ds && !a.causal && nk % BK == 0 && kr == 3 && lo != 2 && (option(OPT_DKDV_ABL) == 0 || option(OPT_DKDV_ABL) == 32)) {
+        route_hit(ROUTE_DKDV_LEAN);
+        if constexpr (std::is_same<Tag, bf16_tag>::value) {
+            if (option(OPT_DKDV_ABL) == 32) return launch(bwd_dkdv_w4_kernel<Tag, false, 32, 1, true, 3, 3>);   // stamps (tools/w4_cycles.py)
+            if (lo == 3) return launch(bwd_dkdv_w4_kernel<Tag, false, 0, 1, true, 3, 1>);
+            if (lo == 4) return launch(bwd_dkdv_w4_kernel<Tag, false, 0, 1, true, 3, 2>);
+        }
+        return launch(bwd_dkdv_w4_kernel<Tag, false, 0, 1, true, 3, 3>);
+    }
+    if (ds) route_hit(ROUTE_DKDV_STREAM);
     if (ds && option(OPT_DKDV_ABL) >= 32) {
         if constexpr (std::is_same<Tag, bf16_tag>::value) switch (option(OPT_DKDV_ABL)) {
             case 64: return a.causal ? launch(bwd_dkdv_w4_kernel<Tag, true, 64, 2, true, 3>) : launch(bwd_dkdv_w4_kernel<Tag, false, 64, 1, true, 3>);
@@ -690,6 +843,9 @@ static hipError_t launch_dkdv_w4_t(const BwdArgs& a, const float* nlse, const fl
             case 608: if (a.causal) return launch(bwd_dkdv_w4_kernel<Tag, true, 96, 1, true, 3>); break;
             case 2080: if (a.causal) return launch(bwd_dkdv_w4_kernel<Tag, true, 2080, 2, true, 3>); break;   // stamps, no mask branch in the loop
             case 512: if (a.causal) return launch(bwd_dkdv_w4_kernel<Tag, true, 0, 1, true, 3>); break;
+            // stamps + no row constants / no address updates: what the lean form can at most return (profiles/dkdv_lean.md)
+            case 40: if (!a.causal) return launch(bwd_dkdv_w4_kernel<Tag, false, 40, 1, true, 3>); break;
+            case 48: if (!a.causal) return launch(bwd_dkdv_w4_kernel<Tag, false, 48, 1, true, 3>); break;
             default: break;
         }
     }

@@ -41,8 +41,8 @@ hipEvent_t prof_get_event() {
 }
 
 // ---- tuning knobs ---------------------------------------------------------------------------------
-constexpr const char* kOptNames[fa::OPT_COUNT] = {"fwd_kb", "fwd_stag", "dkdv", "dq_kt", "fwd_rs", "dkdv_kreg", "fwd_eager", "fwd_hs", "fwd_tpw", "dq_tpw", "dkdv_tpw", "dq_nlf", "dq_w4", "fwd_abl", "small_grid", "fp8_rot", "dkdv_stg", "dkdv_abl", "dq", "dq_abl", "ex_path", "ds_chunk_mb", "fp8_pv", "fwd_rd", "fwd_w2"};
-constexpr const char* kOptEnv[fa::OPT_COUNT] = {"FA_FWD_KB", "FA_FWD_STAG", "FA_DKDV", "FA_DQ_KT", "FA_FWD_RS", "FA_DKDV_KREG", "FA_FWD_EAGER", "FA_FWD_HS", "FA_FWD_TPW", "FA_DQ_TPW", "FA_DKDV_TPW", "FA_DQ_NLF", "FA_DQ_W4", "FA_FWD_ABL", "FA_SMALL_GRID", "FA_FP8_ROT", "FA_DKDV_STG", "FA_DKDV_ABL", "FA_DQ", "FA_DQ_ABL", "FA_EX_PATH", "FA_DS_CHUNK_MB", "FA_FP8_PV", "FA_FWD_RD", "FA_FWD_W2"};
+constexpr const char* kOptNames[fa::OPT_COUNT] = {"fwd_kb", "fwd_stag", "dkdv", "dq_kt", "fwd_rs", "dkdv_kreg", "fwd_eager", "fwd_hs", "fwd_tpw", "dq_tpw", "dkdv_tpw", "dq_nlf", "dq_w4", "fwd_abl", "small_grid", "fp8_rot", "dkdv_stg", "dkdv_abl", "dq", "dq_abl", "ex_path", "ds_chunk_mb", "fp8_pv", "fwd_rd", "fwd_w2", "dkdv_lean"};
+constexpr const char* kOptEnv[fa::OPT_COUNT] = {"FA_FWD_KB", "FA_FWD_STAG", "FA_DKDV", "FA_DQ_KT", "FA_FWD_RS", "FA_DKDV_KREG", "FA_FWD_EAGER", "FA_FWD_HS", "FA_FWD_TPW", "FA_DQ_TPW", "FA_DKDV_TPW", "FA_DQ_NLF", "FA_DQ_W4", "FA_FWD_ABL", "FA_SMALL_GRID", "FA_FP8_ROT", "FA_DKDV_STG", "FA_DKDV_ABL", "FA_DQ", "FA_DQ_ABL", "FA_EX_PATH", "FA_DS_CHUNK_MB", "FA_FP8_PV", "FA_FWD_RD", "FA_FWD_W2", "FA_DKDV_LEAN"};
 // a name added to OptionId without its two strings here would leave a null at the end of a table
 template <size_t N> constexpr bool all_set(const char* const (&t)[N]) {
     for (size_t i = 0; i < N; ++i)
@@ -172,6 +172,14 @@ int set_option(const char* name, int value) {
     std::call_once(g_opts_once, init_opts);
     for (int i = 0; i < OPT_COUNT; ++i)
         if (!strcmp(name, kOptNames[i])) { g_opts[i].store(value); return 0; }
+    return -1;
+}
+std::atomic<long long> g_route_hits[ROUTE_COUNT];
+constexpr const char* kRouteNames[ROUTE_COUNT] = {"dkdv_stream", "dkdv_lean"};
+void route_hit(int id) { g_route_hits[id].fetch_add(1, std::memory_order_relaxed); }
+long long route_count(const char* name) {
+    for (int i = 0; i < ROUTE_COUNT; ++i)
+        if (!strcmp(name, kRouteNames[i])) return g_route_hits[i].load(std::memory_order_relaxed);
     return -1;
 }
 void prof_begin(int id, hipStream_t st) {
@@ -3174,6 +3182,12 @@ int fa_debug_trace_buffer(void* device_ptr) {
 int fa_set_option(const char* name, int value) {
     if (!name || fa::set_option(name, value) != 0) return fail(FA_ERR_INVALID_ARGUMENT, "fa_set_option: unknown option '%s'", name ? name : "(null)");
     return FA_OK;
+}
+
+int64_t fa_route_count(const char* name) {
+    const long long c = name ? fa::route_count(name) : -1;
+    if (c < 0) return fail(FA_ERR_INVALID_ARGUMENT, "fa_route_count: unknown route '%s'", name ? name : "(null)");
+    return c;
 }
 
 const char* fa_last_error(void) { return g_err; }

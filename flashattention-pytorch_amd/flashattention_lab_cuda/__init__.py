@@ -36,7 +36,7 @@ _DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 EXPORTED_C_SYMBOLS = (
     "fa1_forward", "fa1_backward", "fa2_forward", "fa2_backward", "fa3_forward", "fa3_backward",
     "fa_backward_workspace_bytes", "fa_backward_workspace_bytes_fast", "fa3_forward_workspace_bytes", "fa3_backward_workspace_bytes", "fa_last_error", "fa_version",
-    "fa_set_kernel_mode", "fa_set_option", "fa_debug_trace_buffer", "fa_device_is_gfx950", "fa_profile_enable", "fa_profile_report",
+    "fa_set_kernel_mode", "fa_set_option", "fa_debug_trace_buffer", "fa_device_is_gfx950", "fa_profile_enable", "fa_profile_report", "fa_route_count",
     "fa_ex_forward", "fa_ex_backward", "fa_ex_backward_workspace_bytes", "fa_ex_backward_workspace_bytes_fast",
     "fa_ex_forward_grouped", "fa_ex_backward_grouped", "fa_ex_backward_workspace_bytes_grouped",
     "fa_ex_backward_workspace_bytes_fast_grouped", "fa_ex_forward_window", "fa_ex_backward_window",
@@ -145,6 +145,7 @@ _sig("fa_debug_trace_buffer", _fields("p:device_ptr"))
 _sig("fa_device_is_gfx950", _fields("c:device"))
 _sig("fa_profile_enable", _fields("c:on"))
 _sig("fa_profile_report", _fields("s:buf z:cap"))
+_sig("fa_route_count", _fields("s:name"), ctypes.c_int64)
 for _dir, _ptrs, _tail, _ds in (("forward", _FWD, _STREAM, ()), ("backward", _BWD, _WS, _DSINK)):
     _sig(f"fa_ex_{_dir}", _ex_sig(_ptrs, _tail))
     _sig(f"fa_ex_{_dir}_grouped", _ex_sig(_ptrs, _tail, _GROUP))
@@ -316,6 +317,14 @@ def profile_report() -> dict:
         name, cnt, ms = line.split()
         out[name] = (int(cnt), float(ms))
     return out
+
+
+def route_count(name: str) -> int:
+    """Launches of the named kernel route since the library was loaded ("dkdv_stream", "dkdv_lean": include/fa_mi355x.h)."""
+    n = _lib.fa_route_count(name.encode())
+    if n < 0:
+        raise RuntimeError(_lib.fa_last_error().decode())
+    return n
 
 
 def _check(rc: int) -> None:

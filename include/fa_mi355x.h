@@ -1253,6 +1253,10 @@ int fa_device_is_gfx950(int device);   /* 1 if `device` reports gcnArchName gfx9
  * writes one "kernel_name launches total_ms" line per kernel; returns bytes written or a negative code. */
 int fa_profile_enable(int on);
 int fa_profile_report(char* buf, size_t cap);
+/* Which form a launcher took: the number of launches of the named route since the library was loaded, negative for an unknown
+ * name.  "dkdv_stream": the dS-storing dK/dV stream kernel in its general form; "dkdv_lean": its lean form (non-causal launches
+ * whose key count is a multiple of 256; option dkdv_lean = 2 forces the general form). */
+int64_t fa_route_count(const char* name);
 
 #ifdef __cplusplus
 }

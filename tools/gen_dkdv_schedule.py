@@ -18,6 +18,8 @@ A gap that is over its budget stretches by the excess (tools/asm_gaps.py measure
 script packs the work greedily, earliest deadline first, and prints the table as C++.
 
     python tools/gen_dkdv_schedule.py [--prescaled] [--ds]    # --prescaled: no MUL (K tile already multiplied by c)
+    python tools/gen_dkdv_schedule.py --lean --ds             # w4lean::kSched, the table of the lean form (unmasked launches):
+                                                              # two ACC instead of four, no QADDR / TADDR
 """
 import argparse
 
@@ -41,6 +43,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--prescaled", action="store_true")
     ap.add_argument("--ds", action="store_true")
+    ap.add_argument("--lean", action="store_true")
     args = ap.parse_args()
     ops = []   # name, cost, earliest slice, deadline slice, deps (names that must sit in an EARLIER slice), same-slice deps
 
@@ -63,17 +66,24 @@ def main():
             dl = (46 if m < 4 else 54) + kb
             add(f"SU({kb},{m})", 12, 32 + kb, dl, before=(f"EXP({kb},{2 * m})", f"EXP({kb},{2 * m + 1})"))
     # initial accumulators of the next block: S'[kb] / dP'[kb] are free once every SU of kb is behind
-    for kb in (0, 1):
-        sus = tuple(f"SU({kb},{m})" for m in range(8))
-        add(f"ACC({kb})", 16, 40, 61, before=sus + ("LADDR",))        # S'[kb]
-        add(f"ACC({2 + kb})", 16, 40, 61, before=sus + ("LADDR",))    # dP'[kb]
+    if args.lean:
+        # the lean form loads S'[0] / dP'[0] only: k-step 0 of key block 1 takes them as its C operand and writes S'[1] / dP'[1]
+        sus = tuple(f"SU({kb},{m})" for kb in (0, 1) for m in range(8))
+        add("ACC(0)", 16, 40, 61, before=sus + ("LADDR",))
+        add("ACC(2)", 16, 40, 61, before=sus + ("LADDR",))
+    else:
+        for kb in (0, 1):
+            sus = tuple(f"SU({kb},{m})" for m in range(8))
+            add(f"ACC({kb})", 16, 40, 61, before=sus + ("LADDR",))        # S'[kb]
+            add(f"ACC({2 + kb})", 16, 40, 61, before=sus + ("LADDR",))    # dP'[kb]
     add("LADDR", 4, 1, 60)                       # the row constants of this block were read before its first MFMA
     for j in range(5):
         add(f"DMA({j})", 16, 0, 40)              # the target buffer was last read in the previous block
-    for i in range(8):
-        add(f"QADDR({i})", 4, 10 + 2 * i, 56)    # Q rows / dO rows: last requested in front of MFMA 10 + 2 i; group 0 of the next block is requested in front of MFMA 58
-    for j in range(4):
-        add(f"TADDR({j})", 8, 56, 63)            # two addresses; last transposed request in front of MFMA 56
+    if not args.lean:                            # (lean: the buffer offsets are immediates of a block body per buffer)
+        for i in range(8):
+            add(f"QADDR({i})", 4, 10 + 2 * i, 56)    # Q rows / dO rows: last requested in front of MFMA 10 + 2 i; group 0 of the next block is requested in front of MFMA 58
+        for j in range(4):
+            add(f"TADDR({j})", 8, 56, 63)            # two addresses; last transposed request in front of MFMA 56
 
     if args.ds:
         for kb in (0, 1):
@@ -101,7 +111,7 @@ def main():
                     break
     assert not pending, pending
     over = sum(-v for v in left.values() if v < 0)
-    print(f"// generated by tools/gen_dkdv_schedule.py{' --prescaled' if args.prescaled else ''}{' --ds' if args.ds else ''}: {over} cycles over budget in "
+    print(f"// generated by tools/gen_dkdv_schedule.py{' --prescaled' if args.prescaled else ''}{' --lean' if args.lean else ''}{' --ds' if args.ds else ''}: {over} cycles over budget in "
           f"{sum(1 for v in left.values() if v < 0)} gaps")
     width = max(len(v) for v in placed.values())
     print(f"// slice S (after MFMA S): up to {width} operations")

@@ -2,6 +2,8 @@
 (option dkdv_abl with bit 5 set: the kernel stamps its block loop and leaves (cycles, blocks) in dk[0..7]).
 
     python tools/w4_cycles.py [--abl 32 33 34 36 40 59 63]
+    python tools/w4_cycles.py --ds --abl 32 40 48 [--lean 2]   # the dS-storing kernel of the hand-over (the default backward);
+                                                               # --lean: option dkdv_lean (2 = the general form; 40 / 48 always are)
 """
 import argparse
 import sys
@@ -11,7 +13,7 @@ import torch
 import flashattention_lab_cuda as ext
 
 NAMES = {32: "full", 33: "no vector slices", 34: "no DMA / wait / barrier", 36: "no operand requests", 40: "no row constants",
-         59: "requests + MFMAs only", 63: "MFMAs only"}
+         48: "no address updates", 59: "requests + MFMAs only", 63: "MFMAs only"}
 
 
 def main():
@@ -20,6 +22,8 @@ def main():
     ap.add_argument("--abl", type=int, nargs="+", default=None)
     ap.add_argument("--bh", type=int, default=256)
     ap.add_argument("--seqlen", type=int, default=4096)
+    ap.add_argument("--ds", action="store_true", help="dkdv: leave the backward on the dS hand-over (stamps of its dS-storing kernel)")
+    ap.add_argument("--lean", type=int, default=0, help="option dkdv_lean during the runs")
     args = ap.parse_args()
     dq_mode = args.kernel == "dq"
     if args.abl is None:
@@ -31,8 +35,9 @@ def main():
     g = torch.Generator(device="cuda").manual_seed(0)
     q, k, v, do = (torch.randn((bh, n, d), device="cuda", dtype=torch.bfloat16, generator=g) for _ in range(4))
     o, lse = ext.forward(q, k, v, False, d ** -0.5, 64, 128)
-    ext.set_option(opt, 5)
-    print(f"{args.kernel} stream kernel, bh={bh} N={n} d={d}: {mfmas} MFMAs per stamped unit")
+    ext.set_option(opt, 0 if args.ds and not dq_mode else 5)
+    ext.set_option("dkdv_lean", args.lean)
+    print(f"{args.kernel} stream kernel{' (dS-storing, dkdv_lean = %d)' % args.lean if args.ds else ''}, bh={bh} N={n} d={d}: {mfmas} MFMAs per stamped unit")
     print("| variant | cycles / unit | cycles / MFMA | kernel ms | clock GHz (cycles x 16 WG per CU / time; loop only) |")
     print("|---|---|---|---|---|")
     try:
@@ -54,6 +59,7 @@ def main():
     finally:
         ext.set_option(abl_opt, 0)
         ext.set_option(opt, 0)
+        ext.set_option("dkdv_lean", 0)
 
 
 if __name__ == "__main__":
