@@ -883,3 +883,58 @@ def flash_attention_fp8_kvcache(q, k_cache, v_cache, *, cache_seqlens=None, bloc
                                          det(q_descale), det(k_descale), det(v_descale), softmax_scale, bool(causal), num_splits,
                                          out_dtype)
     return (o, lse) if return_softmax_lse else o
+
+
+def quantize_fp8(x, heads_per_scale=1, descale=None, layout="bnhd", out=None, out_layout=None, descale_out=None, scale_pow2=False,
+                 cu_seqlens=None, max_seqlen=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, seqlen_offsets=0):
+    """The producer of the fp8 calls' inputs: a float16 / bfloat16 tensor as torch.float8_e4m3fn codes plus the float32 descales
+    (B, H / heads_per_scale) that flash_attention_fp8 / _varlen / _kvcache and the e4m3 cache of flash_attn_with_kvcache read
+    (fa_fp8_quantize, include/fa_mi355x.h).  Returns (x8, descale).
+    x: (B, N, H, d) with layout="bnhd", (B, H, N, d) with "bhnd", packed (total, H, d) with "thd" plus cu_seqlens (int32 (B + 1,))
+    and max_seqlen; d a multiple of 16 in [16, 256].  A view with a contiguous last dim, a 16-byte aligned start and strides that are
+    multiples of 8 elements, such as qkv[:, :, :H_q] of a fused projection, is read in place.  One descale covers heads_per_scale
+    adjacent heads x all tokens of a sequence x d: H_q // H_kv for q under grouped-query attention, 1 for k and v.
+    descale=None (dynamic): descale = amax / 448 over the unit, 1 for an all-zero or empty unit; scale_pow2 rounds it up to a power
+    of two.  descale given (float32 (B, H / g) or (H / g,), positive and finite, read on the device only): the static mode, one
+    launch, and the tensor itself is returned.  Codes: e4m3 round-to-nearest-even of clamp(x * (1 / descale), +-448), the arithmetic
+    of the e4m3 cache append, so quantize_fp8(k_new, descale=k_descale) has the bytes flash_attn_with_kvcache(k=k_new,
+    k_descale=k_descale) stores.  NaN and infinity in x are outside the contract.
+    out: an e4m3 tensor in out_layout (default: layout) at its own strides (multiples of 16 bytes), e.g. cache[:, :N] of a
+    (B, capacity, H, d) cache; bytes outside the addressed rows are never written, nor are packed tokens no sequence owns.
+    rotary_cos / rotary_sin: (seqlen_ro, rotary_dim / 2) tables in x's dtype rotate the first rotary_dim head dims on the way, by
+    common.rotary.apply_rotary_emb's rules and with its bits (rotary_interleaved; seqlen_offsets an int or int32 (B,); a token
+    outside the table passes through): the call equals itself on the rotated tensor, in every byte and descale.
+    Nothing is read on the host, so projection -> quantise -> fp8 attention captures into one graph and replays after x, descale,
+    cu_seqlens and the offsets change in place; two runs give the same bits.  NotImplementedError for other dtypes and head dims,
+    ValueError for views that would need a copy.  Nothing is recorded by autograd."""
+    import flashattention_lab_cuda as ext
+
+    det = lambda t: t.detach() if isinstance(t, torch.Tensor) else t   # noqa: E731
+    with torch.no_grad():
+        return ext.fp8_quantize(det(x), heads_per_scale, det(descale), layout, det(out), out_layout, det(descale_out), scale_pow2,
+                                cu_seqlens, max_seqlen, det(rotary_cos), det(rotary_sin), rotary_interleaved, seqlen_offsets)
+
+
+def quantize_fp8_qkv(q, k, v, *, layout="bnhd", q_descale=None, k_descale=None, v_descale=None, scale_pow2=False, rotary_cos=None,
+                     rotary_sin=None, rotary_interleaved=False, seqlen_offsets=0, cu_seqlens_q=None, cu_seqlens_k=None,
+                     max_seqlen_q=None, max_seqlen_k=None):
+    """quantize_fp8 on q, k and v with the scale units of the fp8 calls: (q8, k8, v8, q_descale, k_descale, v_descale), every
+    descale float32 (B, H_kv).  q takes heads_per_scale = H_q // H_kv, k and v take 1; the tables rotate q and k and never v.
+    A descale that is given makes that tensor's call static.  layout as quantize_fp8's; "thd" takes cu_seqlens_q / max_seqlen_q for
+    q and cu_seqlens_k / max_seqlen_k for k and v.  The results go straight into flash_attention_fp8(layout=layout),
+    flash_attention_fp8_varlen and flash_attention_fp8_kvcache."""
+    who = "quantize_fp8_qkv"
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
+    hdim = 1 if layout == "bhnd" else -2
+    if q.dim() < 3 or k.dim() != q.dim() or v.dim() != q.dim():
+        raise RuntimeError(f"{who}: q, k, v must share the layout {layout!r}; got q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}")
+    hq, hkv = q.shape[hdim], k.shape[hdim]
+    if v.shape[hdim] != hkv or hkv < 1 or hq % hkv != 0:
+        raise RuntimeError(f"{who}: H_q = {hq} must be a multiple of H_kv = {hkv}, shared by k and v (v has {v.shape[hdim]})")
+    rot = dict(rotary_cos=rotary_cos, rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved, seqlen_offsets=seqlen_offsets)
+    q8, qd = quantize_fp8(q, hq // hkv, q_descale, layout, scale_pow2=scale_pow2, cu_seqlens=cu_seqlens_q, max_seqlen=max_seqlen_q, **rot)
+    k8, kd = quantize_fp8(k, 1, k_descale, layout, scale_pow2=scale_pow2, cu_seqlens=cu_seqlens_k, max_seqlen=max_seqlen_k, **rot)
+    v8, vd = quantize_fp8(v, 1, v_descale, layout, scale_pow2=scale_pow2, cu_seqlens=cu_seqlens_k, max_seqlen=max_seqlen_k)
+    return q8, k8, v8, qd, kd, vd

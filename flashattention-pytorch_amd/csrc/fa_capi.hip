@@ -31,7 +31,7 @@ hipEvent_t g_prof_open[fa::K_COUNT];
 const char* const kKernelNames[fa::K_COUNT] = {"fwd_f32", "bwd_delta", "bwd_dkdv_f32", "bwd_dq_f32", "fwd_mfma",
                                                "bwd_mfma", "bwd_dq_cvt", "bwd_dq_mfma", "fp8_quant", "fwd_fp8", "ex_fwd", "ex_bwd", "kv_group_sum",
                                                "fp8in_vt", "fp8in_fwd", "fp8in_vt_varlen", "fp8in_fwd_varlen", "idx_pack", "idx_logits",
-                                               "idx_topk", "fp8kv_split"};
+                                               "idx_topk", "fp8kv_split", "fp8q_amax", "fp8q_quant", "fp8q_fused"};
 
 hipEvent_t prof_get_event() {
     if (!g_prof_free.empty()) { hipEvent_t e = g_prof_free.back(); g_prof_free.pop_back(); return e; }
@@ -175,7 +175,7 @@ int set_option(const char* name, int value) {
     return -1;
 }
 std::atomic<long long> g_route_hits[ROUTE_COUNT];
-constexpr const char* kRouteNames[ROUTE_COUNT] = {"dkdv_stream", "dkdv_lean"};
+constexpr const char* kRouteNames[ROUTE_COUNT] = {"dkdv_stream", "dkdv_lean", "fp8_quant_fused", "fp8_quant_two_pass", "fp8_quant_static"};
 void route_hit(int id) { g_route_hits[id].fetch_add(1, std::memory_order_relaxed); }
 long long route_count(const char* name) {
     for (int i = 0; i < ROUTE_COUNT; ++i)
@@ -2559,6 +2559,170 @@ int fa_rotary_apply(const void* x, void* y, int64_t batch, int64_t seqlen, int64
     c.conjugate = conjugate; c.seqlen_offset = seqlen_offset; c.seqlen_offsets = seqlen_offsets;
     c.cu_seqlens = cu_seqlens; c.total = total; c.max_seqlen = max_seqlen; c.stream = stream;
     return rotary_impl("fa_rotary_apply", c);
+}
+
+// ---- the fp8 quantiser: see include/fa_mi355x.h
+// One call of the fa_fp8_quantize family, a field per argument under its name in the header.  Defaults: "argument absent".
+struct Fp8QuantCall {
+    const void* x = nullptr;
+    void* out = nullptr;
+    const float* descale = nullptr;
+    float* descale_out = nullptr;
+    const int32_t* cu_seqlens = nullptr;
+    // _rotary
+    const void *rotary_cos = nullptr, *rotary_sin = nullptr;
+    int64_t rotary_cos_row_stride = 0, rotary_sin_row_stride = 0, seqlen_ro = 0, rotary_dim = 0;
+    int rotary_interleaved = 0;
+    int64_t seqlen_offset = 0;
+    const int32_t* seqlen_offsets = nullptr;
+    int64_t batch = 0, heads = 0, seqlen = 0, d = 0, heads_per_scale = 0, total = 0, max_seqlen = 0;
+    int dtype = 0;
+    int64_t x_batch_stride = 0, x_head_stride = 0, x_token_stride = 0, out_batch_stride = 0, out_head_stride = 0, out_token_stride = 0,
+            descale_batch_stride = 0;
+    int scale_pow2 = 0;
+    void* workspace = nullptr;
+    size_t workspace_bytes = 0;
+    void* stream = nullptr;
+};
+
+static int fp8_quantize_impl(const char* who, const Fp8QuantCall& c) {
+    const int64_t kSpan = (int64_t)1 << 58, kStrideMax = (int64_t)1 << 31;
+    if (c.dtype != FA_DTYPE_F16 && c.dtype != FA_DTYPE_BF16)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: dtype must be f16 or bf16 (got code %d)", who, c.dtype);
+    if (c.d < 16 || c.d > 256 || c.d % 16 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: head_dim must be a multiple of 16 in [16, 256] (got %lld)", who, (long long)c.d);
+    if (c.batch < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch must be >= 1 (got %lld)", who, (long long)c.batch);
+    if (c.heads < 1 || c.heads > 0x7fffffff / c.d)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads must be >= 1 with heads * head_dim < 2^31 (got %lld)", who, (long long)c.heads);
+    if (c.heads_per_scale < 1 || c.heads % c.heads_per_scale != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads_per_scale must be >= 1 and divide heads = %lld (got %lld)", who, (long long)c.heads,
+                    (long long)c.heads_per_scale);
+    const int64_t nj = c.heads / c.heads_per_scale;
+    if (c.batch > 0x7fffffff / nj)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch * heads / heads_per_scale must be < 2^31 (got %lld * %lld)", who, (long long)c.batch,
+                    (long long)nj);
+    if (c.seqlen < 0 || c.seqlen > 0x7fffffff)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen must lie in [0, 2^31) (got %lld)", who, (long long)c.seqlen);
+    if (!c.x || !c.out) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    if ((uintptr_t)c.x % 16 != 0 || (uintptr_t)c.out % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: x and out must be 16-byte aligned", who);
+    if ((uintptr_t)c.descale % 4 != 0 || (uintptr_t)c.descale_out % 4 != 0 || (uintptr_t)c.cu_seqlens % 4 != 0 ||
+        (uintptr_t)c.seqlen_offsets % 4 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: descale, descale_out, cu_seqlens and seqlen_offsets must be 4-byte aligned", who);
+    if (!c.descale && !c.descale_out)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: dynamic mode (descale == NULL) needs descale_out", who);
+    const bool packed = c.cu_seqlens != nullptr;
+    if (packed) {
+        if (c.total < 0 || c.total > 0x7fffffff)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: total must lie in [0, 2^31) (got %lld)", who, (long long)c.total);
+        if (c.max_seqlen < 0 || c.max_seqlen > c.total)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: max_seqlen=%lld must lie in [0, total=%lld]", who, (long long)c.max_seqlen,
+                        (long long)c.total);
+        if (c.seqlen != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen must be 0 with cu_seqlens (got %lld)", who, (long long)c.seqlen);
+    } else if (c.total != 0 || c.max_seqlen != 0) {
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: total and max_seqlen must be 0 without cu_seqlens (got %lld, %lld)", who,
+                    (long long)c.total, (long long)c.max_seqlen);
+    }
+    const bool batch_strides = !packed && c.batch > 1;   // the only form that addresses with them
+    const int64_t tokens = packed ? c.total : c.seqlen;
+    const int64_t ext[3] = {batch_strides ? c.batch : 1, c.heads, tokens};
+    const int64_t xs[3] = {c.x_batch_stride, c.x_head_stride, c.x_token_stride};
+    const int64_t os[3] = {c.out_batch_stride, c.out_head_stride, c.out_token_stride};
+    for (int j = 0; j < 3; ++j)
+        if (ext[j] > 1 && (xs[j] < 0 || xs[j] % 8 != 0 || xs[j] > kSpan / (ext[j] - 1)))
+            return fail(FA_ERR_INVALID_ARGUMENT,
+                        "%s: the strides of x (batch %lld, head %lld, token %lld) must be >= 0 and multiples of 8 elements with (extent - 1) * "
+                        "stride <= 2^58", who, (long long)xs[0], (long long)xs[1], (long long)xs[2]);
+    for (int j = 0; j < 3; ++j)
+        if (ext[j] > 1 && (os[j] < 0 || os[j] % 16 != 0 || os[j] > kSpan / (ext[j] - 1)))
+            return fail(FA_ERR_INVALID_ARGUMENT,
+                        "%s: the strides of out (batch %lld, head %lld, token %lld) must be >= 0 and multiples of 16 bytes with (extent - 1) * "
+                        "stride <= 2^58", who, (long long)os[0], (long long)os[1], (long long)os[2]);
+    {   // two addressed rows of out never overlap
+        const int64_t hspan = c.heads > 1 ? (c.heads - 1) * c.out_head_stride : 0, tspan = tokens > 1 ? (tokens - 1) * c.out_token_stride : 0;
+        const bool heads_inner = (c.heads == 1 || c.out_head_stride >= c.d) && (tokens <= 1 || c.out_token_stride >= hspan + c.d);
+        const bool tokens_inner = (tokens <= 1 || c.out_token_stride >= c.d) && (c.heads == 1 || c.out_head_stride >= tspan + c.d);
+        if (!heads_inner && !tokens_inner)
+            return fail(FA_ERR_INVALID_ARGUMENT,
+                        "%s: rows of out overlap: head stride %lld >= head_dim and token stride %lld >= (heads - 1) * head stride + head_dim, or "
+                        "the two the other way round", who, (long long)c.out_head_stride, (long long)c.out_token_stride);
+        if (batch_strides && c.out_batch_stride < hspan + tspan + c.d)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: out's batch stride %lld must cover one batch element (%lld bytes)", who,
+                        (long long)c.out_batch_stride, (long long)(hspan + tspan + c.d));
+    }
+    if (c.descale && c.descale_batch_stride != 0 && (c.descale_batch_stride < nj || c.descale_batch_stride > ((int64_t)1 << 40)))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: descale_batch_stride must be 0 or lie in [heads / heads_per_scale = %lld, 2^40] (got %lld)",
+                    who, (long long)nj, (long long)c.descale_batch_stride);
+    const bool rot = c.rotary_cos || c.rotary_sin;
+    if (rot) {
+        if (!c.rotary_cos || !c.rotary_sin) return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary_cos and rotary_sin must both be given", who);
+        if ((uintptr_t)c.rotary_cos % 4 != 0 || (uintptr_t)c.rotary_sin % 4 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary_cos and rotary_sin must be 4-byte aligned", who);
+        if (c.rotary_dim < 16 || c.rotary_dim > c.d || c.rotary_dim % 16 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary_dim must be a multiple of 16 in [16, head_dim=%lld] (got %lld)", who,
+                        (long long)c.d, (long long)c.rotary_dim);
+        if (c.rotary_cos_row_stride < c.rotary_dim / 2 || c.rotary_sin_row_stride < c.rotary_dim / 2 ||
+            c.rotary_cos_row_stride > kStrideMax || c.rotary_sin_row_stride > kStrideMax)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary row strides (%lld, %lld) must be >= rotary_dim / 2 = %lld (and <= 2^31)", who,
+                        (long long)c.rotary_cos_row_stride, (long long)c.rotary_sin_row_stride, (long long)(c.rotary_dim / 2));
+        if (c.rotary_cos_row_stride % 2 != 0 || c.rotary_sin_row_stride % 2 != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary row strides (%lld, %lld) must be even", who,
+                        (long long)c.rotary_cos_row_stride, (long long)c.rotary_sin_row_stride);
+        if (c.seqlen_ro < 1 || c.seqlen_ro > 0x7fffffff)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_ro must lie in [1, 2^31) (got %lld)", who, (long long)c.seqlen_ro);
+        if (c.seqlen_offset <= -((int64_t)1 << 31) || c.seqlen_offset >= ((int64_t)1 << 31))
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: |seqlen_offset| must be < 2^31 (got %lld)", who, (long long)c.seqlen_offset);
+    }
+    fa::Fp8QuantArgs a;
+    a.x = c.x; a.out = c.out; a.descale = c.descale; a.descale_out = c.descale_out; a.cu_seqlens = c.cu_seqlens;
+    if (rot) {
+        a.rotary_cos = c.rotary_cos; a.rotary_sin = c.rotary_sin; a.rotary_cos_rs = c.rotary_cos_row_stride;
+        a.rotary_sin_rs = c.rotary_sin_row_stride; a.seqlen_ro = c.seqlen_ro; a.rotary_dim = c.rotary_dim;
+        a.rotary_interleaved = c.rotary_interleaved ? 1 : 0; a.seqlen_offset = c.seqlen_offset; a.seqlen_offsets = c.seqlen_offsets;
+    }
+    a.batch = c.batch; a.heads = c.heads; a.seqlen = c.seqlen; a.d = c.d; a.heads_per_scale = c.heads_per_scale; a.total = c.total;
+    a.max_seqlen = c.max_seqlen; a.dtype = c.dtype;
+    a.x_bs = batch_strides ? c.x_batch_stride : 0; a.x_hs = c.heads > 1 ? c.x_head_stride : 0; a.x_ts = tokens > 1 ? c.x_token_stride : 0;
+    a.o_bs = batch_strides ? c.out_batch_stride : 0; a.o_hs = c.heads > 1 ? c.out_head_stride : 0; a.o_ts = tokens > 1 ? c.out_token_stride : 0;
+    a.descale_bs = c.descale_batch_stride; a.scale_pow2 = c.scale_pow2 ? 1 : 0;
+    if (fa::fp8_quant_unit_items(a) > 0x7fffffff)
+        return fail(FA_ERR_UNSUPPORTED, "%s: a scale unit of %lld 16-byte chunks is beyond 2^31", who, (long long)fa::fp8_quant_unit_items(a));
+    if (fa::fp8_quant_two_pass(a)) {
+        const size_t need = fa::fp8_quant_workspace_bytes(c.batch, c.heads, c.heads_per_scale);
+        if (!c.workspace || c.workspace_bytes < need)
+            return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, need, c.workspace ? c.workspace_bytes : (size_t)0);
+        if ((uintptr_t)c.workspace % 16 != 0) return fail(FA_ERR_WORKSPACE, "%s: the workspace must be 16-byte aligned", who);
+        if ((void*)c.descale_out == c.workspace) return fail(FA_ERR_WORKSPACE, "%s: the workspace must not be descale_out", who);
+        a.workspace = c.workspace;
+    }
+    if ((packed ? c.max_seqlen : c.seqlen) == 0 && c.descale && !c.descale_out) return FA_OK;   // nothing to write: no launch
+    return launched(who, fa::launch_fp8_quantize(a, reinterpret_cast<hipStream_t>(c.stream)));
+}
+
+int fa_fp8_quantize(const void* x, void* out, const float* descale, float* descale_out, const int32_t* cu_seqlens, const void* rotary_cos,
+                    const void* rotary_sin, int64_t rotary_cos_row_stride, int64_t rotary_sin_row_stride, int64_t seqlen_ro,
+                    int64_t rotary_dim, int rotary_interleaved, int64_t seqlen_offset, const int32_t* seqlen_offsets, int64_t batch,
+                    int64_t heads, int64_t seqlen, int64_t d, int64_t heads_per_scale, int64_t total, int64_t max_seqlen, int dtype,
+                    int64_t x_batch_stride, int64_t x_head_stride, int64_t x_token_stride, int64_t out_batch_stride,
+                    int64_t out_head_stride, int64_t out_token_stride, int64_t descale_batch_stride, int scale_pow2, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+    Fp8QuantCall c;
+    c.x = x; c.out = out; c.descale = descale; c.descale_out = descale_out; c.cu_seqlens = cu_seqlens;
+    c.rotary_cos = rotary_cos; c.rotary_sin = rotary_sin; c.rotary_cos_row_stride = rotary_cos_row_stride;
+    c.rotary_sin_row_stride = rotary_sin_row_stride; c.seqlen_ro = seqlen_ro; c.rotary_dim = rotary_dim; c.rotary_interleaved = rotary_interleaved;
+    c.seqlen_offset = seqlen_offset; c.seqlen_offsets = seqlen_offsets;
+    c.batch = batch; c.heads = heads; c.seqlen = seqlen; c.d = d; c.heads_per_scale = heads_per_scale; c.total = total;
+    c.max_seqlen = max_seqlen; c.dtype = dtype;
+    c.x_batch_stride = x_batch_stride; c.x_head_stride = x_head_stride; c.x_token_stride = x_token_stride;
+    c.out_batch_stride = out_batch_stride; c.out_head_stride = out_head_stride; c.out_token_stride = out_token_stride;
+    c.descale_batch_stride = descale_batch_stride; c.scale_pow2 = scale_pow2;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    return fp8_quantize_impl("fa_fp8_quantize", c);
+}
+
+size_t fa_fp8_quantize_workspace_bytes(int64_t batch, int64_t heads, int64_t heads_per_scale) {
+    if (batch < 1 || heads < 1 || heads_per_scale < 1 || heads % heads_per_scale != 0 || batch > 0x7fffffff / (heads / heads_per_scale))
+        return 0;
+    return fa::fp8_quant_workspace_bytes(batch, heads, heads_per_scale);
 }
 
 // ---- merge of two partial attention results: see include/fa_mi355x.h

@@ -43,7 +43,7 @@ struct BwdArgs {
 // roofline figure; off by default, costs nothing when off).
 enum KernelId { K_FWD_F32 = 0, K_BWD_DELTA, K_BWD_DKDV_F32, K_BWD_DQ_F32, K_FWD_MFMA, K_BWD_MFMA, K_BWD_DQ_CVT, K_BWD_DQ_MFMA,
                 K_FP8_QUANT, K_FWD_FP8, K_EX_FWD, K_EX_BWD, K_KV_GROUP_SUM, K_FP8IN_VT, K_FP8IN_FWD, K_FP8IN_VT_VARLEN,
-                K_FP8IN_FWD_VARLEN, K_IDX_PACK, K_IDX_LOGITS, K_IDX_TOPK, K_FP8KV_SPLIT, K_COUNT };
+                K_FP8IN_FWD_VARLEN, K_IDX_PACK, K_IDX_LOGITS, K_IDX_TOPK, K_FP8KV_SPLIT, K_FP8Q_AMAX, K_FP8Q_QUANT, K_FP8Q_FUSED, K_COUNT };
 void prof_begin(int id, hipStream_t st);
 void prof_end(int id, hipStream_t st);
 struct ProfScope {
@@ -64,8 +64,9 @@ int option(int id);
 int set_option(const char* name, int value);   // returns 0, or -1 for an unknown name
 
 // Which form a launcher took, counted since the library was loaded and read back through fa_route_count(): a test asks the
-// library, it does not guess from timing.  "dkdv_stream": the dS-storing dK/dV stream kernel, "dkdv_lean": its lean form.
-enum RouteId { ROUTE_DKDV_STREAM = 0, ROUTE_DKDV_LEAN, ROUTE_COUNT };
+// library, it does not guess from timing.  "dkdv_stream": the dS-storing dK/dV stream kernel, "dkdv_lean": its lean form;
+// "fp8_quant_fused", "fp8_quant_two_pass", "fp8_quant_static": the routes of the fp8 quantiser (fa_fp8_quantize.hip).
+enum RouteId { ROUTE_DKDV_STREAM = 0, ROUTE_DKDV_LEAN, ROUTE_FP8Q_FUSED, ROUTE_FP8Q_TWO_PASS, ROUTE_FP8Q_STATIC, ROUTE_COUNT };
 void route_hit(int id);
 
 // exact-f32 kernels (fa_generic.hip): any dtype, d <= 256
@@ -381,6 +382,33 @@ struct RotaryArgs {
     int64_t total, max_seqlen;
 };
 hipError_t launch_rotary(const RotaryArgs& a, hipStream_t st);
+
+// The fp8 quantiser (fa_fp8_quantize.hip; fa_fp8_quantize): 16-bit x -> e4m3 out with one float32 descale per (batch, group of
+// heads_per_scale heads).  x strides in elements, out strides in bytes; tables and positions as RotaryArgs' (rotary_cos null: none).
+struct Fp8QuantArgs {
+    const void* x = nullptr;
+    void* out = nullptr;
+    const float* descale = nullptr;      // static mode: (batch, heads / heads_per_scale) at descale_bs (0: one row); null: dynamic
+    float* descale_out = nullptr;        // (batch, heads / heads_per_scale) contiguous; may be null in static mode
+    const int* cu_seqlens = nullptr;     // (batch + 1,) untrusted device offsets of a packed (total, heads, d) x, or null
+    const void *rotary_cos = nullptr, *rotary_sin = nullptr;
+    int64_t rotary_cos_rs = 0, rotary_sin_rs = 0, seqlen_ro = 0, rotary_dim = 0;
+    int rotary_interleaved = 0;
+    int64_t seqlen_offset = 0;
+    const int* seqlen_offsets = nullptr;
+    int64_t batch = 0, heads = 0, seqlen = 0, d = 0, heads_per_scale = 1, total = 0, max_seqlen = 0;
+    int dtype = 0;
+    int64_t x_bs = 0, x_hs = 0, x_ts = 0, o_bs = 0, o_hs = 0, o_ts = 0, descale_bs = 0;
+    int scale_pow2 = 0;
+    void* workspace = nullptr;           // fp8_quant_workspace_bytes, the two-pass route only
+};
+// work items (one 16-byte chunk, or a non-interleaved rotary pair of them) of the largest unit; at most kFp8QuantFused of them:
+// the dynamic call is one launch that holds the unit in registers
+constexpr int64_t kFp8QuantFused = 1024;
+int64_t fp8_quant_unit_items(const Fp8QuantArgs& a);
+inline bool fp8_quant_two_pass(const Fp8QuantArgs& a) { return !a.descale && fp8_quant_unit_items(a) > kFp8QuantFused; }
+size_t fp8_quant_workspace_bytes(int64_t batch, int64_t heads, int64_t heads_per_scale);
+hipError_t launch_fp8_quantize(const Fp8QuantArgs& a, hipStream_t st);
 
 // Merge of two partial attention results over disjoint key sets (fa_merge.hip; fa_merge_states / fa_merge_states_backward).  Every
 // tensor is addressed by (batch, head, row) through a stride triple in elements; the d elements of an o-like row are contiguous.

@@ -59,6 +59,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_fp8_forward", "fa_fp8_forward_workspace_bytes",
     "fa_fp8_forward_varlen", "fa_fp8_forward_varlen_workspace_bytes",
     "fa_fp8_forward_kvcache", "fa_fp8_forward_kvcache_workspace_bytes",
+    "fa_fp8_quantize", "fa_fp8_quantize_workspace_bytes",
 )
 
 
@@ -222,6 +223,11 @@ _sig("fa_fp8_forward_kvcache", _fields(
     "i:q_batch_stride,q_token_stride,k_batch_stride,k_token_stride,v_batch_stride,v_token_stride,block_table_row_stride,num_blocks,"
     "page_block_size,q_descale_batch_stride,k_descale_batch_stride,v_descale_batch_stride c:causal d:softmax_scale i:num_splits") + _WS)
 _sig("fa_fp8_forward_kvcache_workspace_bytes", _KVWS, _SIZE)
+_sig("fa_fp8_quantize", _fields("p:x,out,descale,descale_out,cu_seqlens") + _ROTARY + _fields(
+    "i:seqlen_offset p:seqlen_offsets i:batch,heads,seqlen,d,heads_per_scale,total,max_seqlen c:dtype "
+    "i:x_batch_stride,x_head_stride,x_token_stride,out_batch_stride,out_head_stride,out_token_stride,descale_batch_stride "
+    "c:scale_pow2") + _WS)
+_sig("fa_fp8_quantize_workspace_bytes", _fields("i:batch,heads,heads_per_scale"), _SIZE)
 _KVWSV = _fields("i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,d,num_splits c:with_sinks")
 _sig("fa_ex_kvcache_workspace_bytes_varlen", _KVWSV, _SIZE)
 _sig("fa_ex_kvcache_workspace_bytes_qv", _KVWSV + _fields("i:d_v"), _SIZE)
@@ -279,6 +285,7 @@ _family("fa_indexer_topk", [])
 _family("fa_fp8_forward", [])
 _family("fa_fp8_forward_varlen", [])
 _family("fa_fp8_forward_kvcache", [])
+_family("fa_fp8_quantize", [])
 _family("fa_ex_forward_kvcache_qv", ["fa_ex_forward_kvcache" + _suffix for _suffix in ("", "_paged", "_rotary", "_fp8", "_sink", "_varlen")])
 
 
@@ -1928,6 +1935,137 @@ def rotary_apply(x, cos, sin, out=None, interleaved=False, conjugate=False, seql
         _call("fa_rotary_apply", (x.data_ptr(), out.data_ptr(), b, seqlen, heads, d, _DTYPE_CODE[x.dtype], xb, xt, yb, yt, *rotary,
                                   int(bool(conjugate)), off0, _ptr(offs), _ptr(cu), total, mx, _stream_ptr(x.device)))
     return out
+
+
+# ---- the fp8 quantiser (include/fa_mi355x.h: fa_fp8_quantize) ----
+
+FP8_QUANT_LAYOUTS = ("bhnd", "bnhd", "thd")
+
+
+def _fp8_quant_view(who, name, t, layout, unit):
+    """(batch, heads, tokens, d, (batch, head, token) strides) of x or out under `layout`: (B, H, N, d), (B, N, H, d) or packed
+    (total, H, d).  Strides in elements of t (out: bytes), each a multiple of `unit` (16 bytes), the start 16-byte aligned, the last
+    dim contiguous; the stride of an extent-1 dim is handed on as 0.  ValueError for a view that would need a copy: it is never
+    copied (out is the target of the call)."""
+    want = 3 if layout == "thd" else 4
+    if t.dim() != want:
+        shape = {"bhnd": "(B, H, N, d)", "bnhd": "(B, N, H, d)", "thd": "(total, H, d) with cu_seqlens"}[layout]
+        raise RuntimeError(f"{who}: {name} must be {want}-D {shape} under layout {layout!r}, got {tuple(t.shape)}")
+    d = t.shape[-1]
+    if layout == "thd":
+        b, h, n, st = 1, t.shape[1], t.shape[0], (0, t.stride(1), t.stride(0))
+    elif layout == "bhnd":
+        b, h, n, st = t.shape[0], t.shape[1], t.shape[2], (t.stride(0), t.stride(1), t.stride(2))
+    else:
+        b, h, n, st = t.shape[0], t.shape[2], t.shape[1], (t.stride(0), t.stride(2), t.stride(1))
+    st = tuple(s if e > 1 else 0 for s, e in zip(st, (b, h, n)))
+    if t.numel() and (t.stride(-1) != 1 or t.data_ptr() % 16 != 0 or any(s % unit != 0 or s < 0 for s in st)):
+        raise ValueError(f"{who}: {name} is a view the kernel cannot address: a contiguous last dim, a 16-byte aligned start and "
+                         f"non-negative strides that are multiples of 16 bytes are needed (strides {tuple(t.stride())}); it is never copied")
+    return b, h, n, d, st
+
+
+def fp8_quantize(x, heads_per_scale=1, descale=None, layout="bnhd", out=None, out_layout=None, descale_out=None, scale_pow2=False,
+                 cu_seqlens=None, max_seqlen=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, seqlen_offsets=0):
+    """(x8, descale): a float16 / bfloat16 tensor as torch.float8_e4m3fn codes plus the float32 descales (B, H / heads_per_scale) the
+    fp8 calls read (fa_fp8_quantize), on the shim's persistent workspace.  x: (B, N, H, d) under layout "bnhd", (B, H, N, d) under
+    "bhnd", packed (total, H, d) under "thd" with cu_seqlens (int32 (B + 1,) on x's device) and max_seqlen; d a multiple of 16 in
+    [16, 256]; any view with a contiguous last dim and strides that are multiples of 8 is addressed as it is (a slice of a fused qkv
+    projection).  One descale covers heads_per_scale adjacent heads, all tokens of a sequence and all of d: H_q / H_kv for q, 1 for k
+    and v.  descale None: amax / 448 per unit (scale_pow2: rounded up to a power of two), 1 for an all-zero or empty unit.  descale
+    given (float32 (B, H / g) or (H / g,), read on the device only): the static mode, one launch; the returned descale is that
+    tensor.  Codes: e4m3_rne(clamp(x / descale, +-448)) by the e4m3 cache append's arithmetic, so with the same descale the bytes
+    are the cache's.  out: an e4m3 tensor in out_layout (default: layout) at its own strides (multiples of 16 bytes), e.g. the
+    [:, :N] prefix of a (B, capacity, H, d) cache; None allocates a dense one.  descale_out: float32 (B, H / g) contiguous, or None.
+    rotary_cos / rotary_sin (seqlen_ro, rotary_dim / 2) in x's dtype rotate the first rotary_dim head dims first, by rotary_apply's
+    rules (rotary_interleaved, seqlen_offsets an int or int32 (B,)), with rotary_apply's bits.  Nothing is read on the host: the
+    call can be captured and replayed.  NotImplementedError for dtypes and head dims, ValueError for views that would need a copy."""
+    who = "fp8_quantize"
+    if layout not in FP8_QUANT_LAYOUTS:
+        raise ValueError(f"{who}: layout must be one of {FP8_QUANT_LAYOUTS}, got {layout!r}")
+    out_layout = layout if out_layout is None else out_layout
+    if out_layout not in FP8_QUANT_LAYOUTS or (out_layout == "thd") != (layout == "thd"):
+        raise ValueError(f"{who}: out_layout must be one of {FP8_QUANT_LAYOUTS} and packed exactly when layout is, got {out_layout!r} "
+                         f"for layout {layout!r}")
+    if not isinstance(x, torch.Tensor) or x.dtype not in (torch.float16, torch.bfloat16):
+        dt = x.dtype if isinstance(x, torch.Tensor) else type(x).__name__
+        raise NotImplementedError(f"{who}: x of dtype {dt} is not supported (torch.float16 or torch.bfloat16)")
+    if x.dim() >= 1 and (x.shape[-1] % 16 != 0 or not 16 <= x.shape[-1] <= 256):
+        raise NotImplementedError(f"{who}: head_dim {x.shape[-1]} is not supported (a multiple of 16 in [16, 256])")
+    if not x.is_cuda:
+        raise RuntimeError(f"{who}: x must be on the GPU (HIP device); there is no CPU path")
+    packed = layout == "thd"
+    if packed != (cu_seqlens is not None):
+        raise ValueError(f"{who}: layout 'thd' and cu_seqlens go together")
+    if max_seqlen is not None and not packed:
+        raise ValueError(f"{who}: max_seqlen needs cu_seqlens")
+    b, heads, n, d, sx = _fp8_quant_view(who, "x", x, layout, 8)
+    total = mx = 0
+    if packed:
+        if max_seqlen is None:
+            raise ValueError(f"{who}: cu_seqlens needs max_seqlen")
+        if not isinstance(cu_seqlens, torch.Tensor) or cu_seqlens.dtype != torch.int32:
+            dt = cu_seqlens.dtype if isinstance(cu_seqlens, torch.Tensor) else type(cu_seqlens).__name__
+            raise NotImplementedError(f"{who}: cu_seqlens of dtype {dt} is not supported (int32 tensor expected)")
+        if cu_seqlens.device != x.device or cu_seqlens.dim() != 1 or cu_seqlens.shape[0] < 2:
+            raise RuntimeError(f"{who}: cu_seqlens must be an int32 (B + 1,) tensor on x's device, B >= 1")
+        b, total, n, mx = cu_seqlens.shape[0] - 1, n, 0, operator.index(max_seqlen)
+        if mx < 0 or mx > total:
+            raise ValueError(f"{who}: max_seqlen = {mx} must lie in [0, total = {total}]")
+    g = operator.index(heads_per_scale)
+    if b < 1 or heads < 1:
+        raise RuntimeError(f"{who}: x needs at least one batch element and one head, got {tuple(x.shape)}")
+    if g < 1 or heads % g != 0:
+        raise RuntimeError(f"{who}: heads_per_scale = {g} must be >= 1 and divide H = {heads}")
+    nj = heads // g
+    rdim = 0
+    if (rotary_cos is None) != (rotary_sin is None):
+        raise RuntimeError(f"{who}: rotary_cos and rotary_sin must both be given")
+    off0, offs = 0, None
+    if rotary_cos is not None:
+        for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+            if not isinstance(t, torch.Tensor) or t.dtype != x.dtype or t.device != x.device or t.dim() != 2 or \
+                    t.shape != rotary_cos.shape or t.numel() == 0:
+                raise RuntimeError(f"{who}: {name} must be a (seqlen_ro, rotary_dim / 2) tensor of x's dtype on x's device, cos and "
+                                   f"sin of one shape")
+        rdim = 2 * rotary_cos.shape[1]
+        if rdim % 16 != 0 or not 16 <= rdim <= d:
+            raise RuntimeError(f"{who}: rotary_dim = 2 * rotary_cos.shape[1] must be a multiple of 16 in [16, d = {d}], got {rdim}")
+        if isinstance(seqlen_offsets, torch.Tensor):
+            if seqlen_offsets.dtype != torch.int32 or seqlen_offsets.device != x.device or seqlen_offsets.shape != (b,):
+                raise RuntimeError(f"{who}: seqlen_offsets must be an int, or an int32 ({b},) tensor on x's device")
+            offs = seqlen_offsets.contiguous()
+        else:
+            off0 = operator.index(seqlen_offsets)
+            if abs(off0) >= 2 ** 31:
+                raise ValueError(f"{who}: |seqlen_offsets| must be < 2^31, got {off0}")
+    dp, dbs, keep = _kv_descale(who, "descale", descale, x, b, nj)
+    with torch.cuda.device(x.device):
+        shape_out = (total, heads, d) if packed else (b, heads, n, d) if out_layout == "bhnd" else (b, n, heads, d)
+        if out is None:
+            out = torch.empty(shape_out, dtype=torch.float8_e4m3fn, device=x.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.float8_e4m3fn:
+            dt = out.dtype if isinstance(out, torch.Tensor) else type(out).__name__
+            raise NotImplementedError(f"{who}: out of dtype {dt} is not supported (torch.float8_e4m3fn expected)")
+        elif tuple(out.shape) != shape_out or out.device != x.device:
+            raise RuntimeError(f"{who}: out must have shape {shape_out} under layout {out_layout!r} on x's device, got {tuple(out.shape)}")
+        _b, _h, _n, _d, so = _fp8_quant_view(who, "out", out, out_layout, 16)
+        if descale_out is not None:
+            if not isinstance(descale_out, torch.Tensor) or descale_out.dtype != torch.float32 or descale_out.device != x.device or \
+                    tuple(descale_out.shape) != (b, nj) or not descale_out.is_contiguous():
+                raise RuntimeError(f"{who}: descale_out must be a contiguous float32 ({b}, {nj}) tensor on x's device")
+        elif descale is None:
+            descale_out = torch.empty((b, nj), dtype=torch.float32, device=x.device)
+        _tabs, rotary = _rotary_tables(rotary_cos, rotary_sin, rdim, rotary_interleaved)
+        cu = cu_seqlens.contiguous() if packed else None
+        need = int(_lib.fa_fp8_quantize_workspace_bytes(b, heads, g))
+        ws = _workspace(x.device, need)
+        # a tensor without elements has no address: the call addresses nothing of it then, and any aligned pointer stands in
+        _call("fa_fp8_quantize", (x.data_ptr() or ws.data_ptr(), out.data_ptr() or ws.data_ptr(), dp, _ptr(descale_out), _ptr(cu), *rotary, off0, _ptr(offs), b, heads, n,
+                                  d, g, total, mx, _DTYPE_CODE[x.dtype], *sx, *so, dbs, int(bool(scale_pow2)), ws.data_ptr(), ws.numel(),
+                                  _stream_ptr(x.device)))
+    del keep
+    return out, (descale if descale is not None else descale_out)
 
 
 # ---- merge of two partial attention results (include/fa_mi355x.h: fa_merge_states / fa_merge_states_backward) ----

@@ -1227,6 +1227,71 @@ int fa_fp8_forward_kvcache(const void* q, const void* k_cache, const void* v_cac
 size_t fa_fp8_forward_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
                                               int64_t d, int64_t num_splits);
 
+/* --- The fp8 quantiser: one 16-bit tensor x -> e4m3 codes plus float32 descales of the shape the fp8 calls above read (the
+ * producer of fa_fp8_forward / _varlen / _kvcache and of the e4m3 cache).  One call covers one tensor, addressed through its own
+ * strides like fa_rotary_apply's, so a slice of a fused qkv projection goes in without a copy.
+ * x: f16 or bf16, element (b, h, i, e) at x[b * x_batch_stride + h * x_head_stride + i * x_token_stride + e], the d elements of a
+ * head row contiguous; d a multiple of 16 in [16, 256]; strides in elements, multiples of 8, the base 16-byte aligned; offsets are
+ * 64-bit.  (B, H, N, d) and (B, N, H, d) differ in their strides only.  Packed form: cu_seqlens int32 (batch + 1,) device memory, x
+ * (total, heads, d) at its token and head strides, seqlen == 0 and the batch strides unused; sequence b owns the tokens of
+ * fa_ex_forward_varlen's clamp (start = clamp(cu[b], 0, total), end = clamp(cu[b + 1], start, total), len = min(end - start,
+ * max_seqlen)), so decreasing or oversized offsets address nothing outside x and out.
+ * Scale units: heads_per_scale = g divides heads; unit (b, j) is heads [j g, (j + 1) g) x all tokens of sequence b x all of d.  For
+ * q under grouped-query attention g = H_q / H_kv gives the (batch, H_kv) descales of the fp8 calls; for k and v g = 1.
+ * Dynamic mode (descale == NULL): amax[b, j] = max |float(x)| over the unit (exact: a maximum does not depend on the order);
+ *     descale[b, j] = amax > 0 ? amax / 448 : 1        (the division IEEE-rounded, __fdiv_rn)
+ * and with scale_pow2 != 0 rounded up to a power of two by fa_mla_fp8_pack's rule: taken in the bit pattern, a mantissa that is
+ * not zero goes to the next exponent (exact for every normal descale below 2^127).  It is written to descale_out, float32 (batch,
+ * heads / g) contiguous, which must be given.  A sequence of length 0 writes descale 1.
+ * Static mode (descale given): float32, unit (b, j) reads descale[b * descale_batch_stride + j]; descale_batch_stride == 0 shares
+ * one (heads / g,) row among the batch.  Read on the device only; positive and finite by contract.  descale_out may be NULL; given,
+ * it receives a copy.  One launch, no workspace.
+ * Codes, both modes: inv = 1 / descale (IEEE-rounded), y = min(max(float(x) * inv, -448), 448), then rounded to nearest even to
+ * OCP e4m3 (v_cvt_pk_fp8_f32).  That is the arithmetic of the e4m3 cache append (fa_ex_forward_kvcache_fp8), so with the same
+ * descale the bytes are the ones the append stores.  NaN and infinity in x are outside the contract.
+ * out: e4m3 bytes, element (b, h, i, e) at out[b * out_batch_stride + h * out_head_stride + i * out_token_stride + e] with its own
+ * strides in bytes, each a multiple of 16, the base 16-byte aligned: (B, H, N, d) -> (B, N, H, d) costs nothing, and out may be
+ * the [:, :N] prefix of a larger (B, capacity, H, d) e4m3 cache.  The strides must not let two addressed rows overlap.  Bytes of
+ * out outside the addressed rows are never written, nor are the rows of packed tokens that no sequence owns.
+ * Optional fused rotary (for q and k): rotary_cos / rotary_sin non-NULL are fa_rotary_apply's tables, to the letter: (seqlen_ro,
+ * rotary_dim / 2) in x's dtype, rows at even strides, 4-byte aligned, rotary_dim a multiple of 16 in [16, d], rotary_interleaved
+ * selecting the pairing, token i of sequence b at pos = seqlen_offset + (seqlen_offsets ? seqlen_offsets[b] : 0) + i, formed in 64
+ * bits, rotated iff 0 <= pos < seqlen_ro and passed through otherwise.  The rotated value is formed in fp32 and rounded ONCE to
+ * x's dtype (fp32 sum, then nearest even), the rule fa_rotary_apply states; amax and codes are taken from that 16-bit value.  So
+ * this call with tables equals this call without them on fa_rotary_apply's result, in every byte and every descale, wherever
+ * fa_rotary_apply rounds through fp32 too: always for bf16; for f16 its compiled code rounds one slot of the interleaved pairing
+ * from the exact sum instead, which moves a 16-bit value by one step where the fp32 sum is an f16 tie (about 1 value in 3 * 10^4;
+ * DESIGN 9zb).  Both tables NULL: no rotation, and the other rotary arguments are not looked at.
+ * Kernels: static mode is one launch (route "fp8_quant_static").  Dynamic mode on a unit of at most 1024 chunks of 16 bytes of
+ * work per workgroup (seqlen * g * d / 8 <= 1024, max_seqlen for seqlen in the packed form; with non-interleaved rotary a chunk
+ * pair counts once) is one launch of one workgroup per unit that holds the unit in registers (route "fp8_quant_fused", no
+ * workspace: the decode step's q is such a unit); larger units take an amax launch, whose workgroups meet in an atomic maximum on
+ * an amax scratch in the workspace (zeroed by a small kernel on the stream first), and a quantise launch (route "fp8_quant_two_pass").  Every
+ * route gives the same bits, and two runs give the same bits.  fa_fp8_quantize_workspace_bytes sizes the scratch: 4 bytes a unit,
+ * rounded up to 256; 0 for arguments the call would refuse.  The workspace is 16-byte aligned and is not descale_out.
+ * Nothing allocates, synchronises or reads device memory on the host: a captured call replays after x, descale, cu_seqlens, the
+ * offsets and the tables' contents change in place (shapes, strides and seqlen_offset are fixed by the capture).
+ * Checked before any HIP call (the first broken rule named in fa_last_error(), FA_ERR_INVALID_ARGUMENT unless said otherwise),
+ * in this order: dtype f16 or bf16; d a multiple of 16 in [16, 256]; batch >= 1, heads >= 1 with heads * d < 2^31; heads_per_scale
+ * >= 1 dividing heads; batch * heads / heads_per_scale < 2^31; seqlen in [0, 2^31); x and out non-null and 16-byte aligned;
+ * descale, descale_out, cu_seqlens, seqlen_offsets 4-byte aligned; dynamic mode needs descale_out; with cu_seqlens 0 <= max_seqlen
+ * <= total < 2^31 and seqlen == 0, without it total == max_seqlen == 0; x's strides >= 0, multiples of 8, every (extent - 1) *
+ * stride <= 2^58; out's strides >= 0, multiples of 16, every (extent - 1) * stride <= 2^58; out's rows do not overlap: head stride
+ * >= d and token stride >= (heads - 1) * head stride + d, or token stride >= d and head stride >= (tokens - 1) * token stride + d,
+ * and with batch > 1 in the padded form the batch stride covers one batch element; static mode: descale_batch_stride == 0 or in
+ * [heads / g, 2^40]; with tables: both given and 4-byte aligned, rotary_dim a multiple of 16 in [16, d], row strides >=
+ * rotary_dim / 2 (and <= 2^31) and even, seqlen_ro in [1, 2^31), |seqlen_offset| < 2^31; a unit of seqlen * g * d / 8 >= 2^31
+ * chunks is FA_ERR_UNSUPPORTED; the two-pass route needs the workspace (FA_ERR_WORKSPACE).  A static call without tokens and
+ * without descale_out returns FA_OK without a launch. */
+int fa_fp8_quantize(const void* x, void* out, const float* descale, float* descale_out, const int32_t* cu_seqlens,
+                    const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride, int64_t rotary_sin_row_stride,
+                    int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved, int64_t seqlen_offset,
+                    const int32_t* seqlen_offsets, int64_t batch, int64_t heads, int64_t seqlen, int64_t d, int64_t heads_per_scale,
+                    int64_t total, int64_t max_seqlen, int dtype, int64_t x_batch_stride, int64_t x_head_stride,
+                    int64_t x_token_stride, int64_t out_batch_stride, int64_t out_head_stride, int64_t out_token_stride,
+                    int64_t descale_batch_stride, int scale_pow2, void* workspace, size_t workspace_bytes, void* stream);
+size_t fa_fp8_quantize_workspace_bytes(int64_t batch, int64_t heads, int64_t heads_per_scale);
+
 /* --- support entry points (no reference counterpart: the reference allocates inside the callee) --- */
 /* bytes for the CURRENT kernel mode: two float row constants per query row (+ an fp32 dQ scratch of bh*n*d floats in
  * FA_MODE_BWD_ATOMIC only); ask again after changing the mode */
@@ -1255,7 +1320,8 @@ int fa_profile_enable(int on);
 int fa_profile_report(char* buf, size_t cap);
 /* Which form a launcher took: the number of launches of the named route since the library was loaded, negative for an unknown
  * name.  "dkdv_stream": the dS-storing dK/dV stream kernel in its general form; "dkdv_lean": its lean form (non-causal launches
- * whose key count is a multiple of 256; option dkdv_lean = 2 forces the general form). */
+ * whose key count is a multiple of 256; option dkdv_lean = 2 forces the general form).  "fp8_quant_fused", "fp8_quant_two_pass",
+ * "fp8_quant_static": the three routes of fa_fp8_quantize, one count a call that launched. */
 int64_t fa_route_count(const char* name);
 
 #ifdef __cplusplus
