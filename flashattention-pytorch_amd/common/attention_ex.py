@@ -712,6 +712,43 @@ _FP8_REFUSED = ("window_size", "softcap", "alibi_slopes", "sinks", "attn_bias", 
                 "cu_seqlens_k", "block_table", "rotary_cos", "rotary_sin")
 
 
+_FP8_MOD_ARGS = ("window_size", "softcap", "sinks")   # what the flash_attn_fp8_* functions take and the older wrappers refuse
+
+
+def _fp8_mod_args(who, window_size, softcap, sinks):
+    """window_size, softcap and sinks of the flash_attn_fp8_* functions as the shim takes them (the shim and the library check
+    the rest: the sinks' shape and device against q)"""
+    try:
+        left, right = window_size
+        if isinstance(left, bool) or isinstance(right, bool):
+            raise TypeError
+        left, right = operator.index(left), operator.index(right)
+    except (TypeError, ValueError):
+        raise RuntimeError(f"{who}: window_size must be a pair (left, right) of ints, got {window_size!r}") from None
+    if left < -1 or right < -1:
+        raise RuntimeError(f"{who}: window ({left}, {right}): each bound must be >= 0, or -1 for unbounded")
+    if isinstance(softcap, bool) or not isinstance(softcap, (int, float)) or not math.isfinite(softcap) or softcap < 0:
+        raise RuntimeError(f"{who}: softcap must be a finite number >= 0 (got {softcap!r})")
+    if sinks is not None and not (isinstance(sinks, torch.Tensor) and sinks.dtype == torch.float32):
+        raise RuntimeError(f"{who}: sinks must be a float32 tensor (pass a 16-bit parameter as p.float())")
+    return dict(window=(left, right), softcap=float(softcap), sinks=None if sinks is None else sinks.detach())
+
+
+def _fp8_refuse(who, refused, unsupported, what, hint_to=None):
+    """The refusals by name of the fp8 wrappers: an argument of `refused` at its neutral value passes, at any other it is a
+    NotImplementedError (hint_to: the function that takes window_size / softcap / sinks), an unknown name a TypeError."""
+    for name, val in unsupported.items():
+        if name in refused:
+            if val is None or val is False or (name == "window_size" and tuple(val) == (-1, -1)) or \
+                    (name in ("softcap", "dropout_p") and val == 0.0) or (name == "max_seqlen_q" and val == 0 and "max_seqlen_q" in refused):
+                continue
+            hint = " (the cache is filled by flash_attn_with_kvcache's append, or by the caller)" if name in ("k", "v") and "k" in refused else ""
+            if hint_to and name in _FP8_MOD_ARGS:
+                hint = f" ({hint_to} takes it)"
+            raise NotImplementedError(f"{who}: {name} is not supported by the fp8 {what}{hint}")
+        raise TypeError(f"{who}() got an unexpected keyword argument {name!r}")
+
+
 def flash_attention_fp8(q, k, v, *, q_descale=None, k_descale=None, v_descale=None, softmax_scale=None, causal=False,
                         out_dtype=torch.bfloat16, layout="bhnd", return_lse=False, **unsupported):
     """FlashAttention-3's fp8 call: attention over q, k, v that are ALREADY torch.float8_e4m3fn, with one float32 descale per
@@ -730,14 +767,32 @@ def flash_attention_fp8(q, k, v, *, q_descale=None, k_descale=None, v_descale=No
     dropout, packed or paged forms, head dims other than 128, 16-bit q / k / v (fa3_attention(fp8=True) and flash_attention_ex take
     those), out_dtype other than bfloat16 / float16.  Wrong shapes and devices raise RuntimeError, a view that would need a copy
     ValueError.  Returns o in `layout` and out_dtype, and with return_lse also lse (B, H_q, Nq) float32.  No gradient."""
-    who = "flash_attention_fp8"
-    for name, val in unsupported.items():
-        if name in _FP8_REFUSED:
-            if val is None or val is False or (name == "window_size" and tuple(val) == (-1, -1)) or \
-                    (name in ("softcap", "dropout_p") and val == 0.0):
-                continue
-            raise NotImplementedError(f"{who}: {name} is not supported by the fp8 call")
-        raise TypeError(f"{who}() got an unexpected keyword argument {name!r}")
+    _fp8_refuse("flash_attention_fp8", _FP8_REFUSED, unsupported, "call", "flash_attn_fp8_func")
+    return _fp8_func("flash_attention_fp8", q, k, v, q_descale, k_descale, v_descale, softmax_scale, causal, out_dtype, layout,
+                     return_lse, {})
+
+
+def flash_attn_fp8_func(q, k, v, *, q_descale=None, k_descale=None, v_descale=None, softmax_scale=None, causal=False,
+                        window_size=(-1, -1), softcap=0.0, sinks=None, out_dtype=torch.bfloat16, layout="bhnd", return_lse=False,
+                        **unsupported):
+    """flash_attention_fp8 with a sliding window, a softcap and attention sinks (FlashAttention-3's flash_attn_func arguments of
+    those names), composing with each other and with everything flash_attention_fp8 takes; its docstring holds for the rest.
+      window_size  (left, right) ints >= -1, -1 = unbounded; causal=True sets right = 0.  Bottom-right aligned: row i sits at
+                   pos = i + Nk - Nq and sees key j iff pos - left <= j <= pos + right and 0 <= j < Nk.  The kernel walks only the
+                   key tiles a workgroup's rows see: O(N w) work.
+      softcap      C > 0: s~ = C tanh(s / C) of s = softmax_scale q_descale k_descale (q8 . k8), before the mask; 0 = off.
+      sinks        float32 (H_q,) on q's device in natural-log units, one per QUERY head, read on the device only: an extra softmax
+                   column with a zero value (lse contains it), never capped, masked or windowed.  A head at -inf gives the bits
+                   of the call without sinks.
+    A row that sees no key gives o = 0 and lse = -inf, with sinks lse = sink.  With all three at their defaults the call IS
+    flash_attention_fp8 (the same kernels).  Everything else flash_attention_fp8 refuses is refused here by name."""
+    who = "flash_attn_fp8_func"
+    _fp8_refuse(who, tuple(n for n in _FP8_REFUSED if n not in _FP8_MOD_ARGS), unsupported, "call")
+    return _fp8_func(who, q, k, v, q_descale, k_descale, v_descale, softmax_scale, causal, out_dtype, layout, return_lse,
+                     _fp8_mod_args(who, window_size, softcap, sinks))
+
+
+def _fp8_func(who, q, k, v, q_descale, k_descale, v_descale, softmax_scale, causal, out_dtype, layout, return_lse, mod):
     for name, t in (("q", q), ("k", k), ("v", v)):
         if not isinstance(t, torch.Tensor):
             raise RuntimeError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
@@ -757,7 +812,7 @@ def flash_attention_fp8(q, k, v, *, q_descale=None, k_descale=None, v_descale=No
                                  None if q_descale is None else q_descale.detach() if isinstance(q_descale, torch.Tensor) else q_descale,
                                  None if k_descale is None else k_descale.detach() if isinstance(k_descale, torch.Tensor) else k_descale,
                                  None if v_descale is None else v_descale.detach() if isinstance(v_descale, torch.Tensor) else v_descale,
-                                 out_dtype, layout)
+                                 out_dtype, layout, **mod)
     return (o, lse) if return_lse else o
 
 
@@ -788,14 +843,27 @@ def flash_attention_fp8_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q
     (flash_attention_varlen takes those), out_dtype other than bfloat16 / float16.
     Returns o (total_q, H_q, 128) in out_dtype, and with return_softmax_lse also lse float32 (H_q, total_q), the layout of
     flash_attention_varlen(return_softmax_lse=True)."""
-    who = "flash_attention_fp8_varlen"
-    for name, val in unsupported.items():
-        if name in _FP8_VARLEN_REFUSED:
-            if val is None or val is False or (name == "window_size" and tuple(val) == (-1, -1)) or \
-                    (name in ("softcap", "dropout_p") and val == 0.0):
-                continue
-            raise NotImplementedError(f"{who}: {name} is not supported by the fp8 call")
-        raise TypeError(f"{who}() got an unexpected keyword argument {name!r}")
+    _fp8_refuse("flash_attention_fp8_varlen", _FP8_VARLEN_REFUSED, unsupported, "call", "flash_attn_fp8_varlen_func")
+    return _fp8_varlen_func("flash_attention_fp8_varlen", q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, block_table,
+                            q_descale, k_descale, v_descale, softmax_scale, causal, out_dtype, return_softmax_lse, {})
+
+
+def flash_attn_fp8_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, *, block_table=None, q_descale=None,
+                               k_descale=None, v_descale=None, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
+                               sinks=None, out_dtype=torch.bfloat16, return_softmax_lse=False, **unsupported):
+    """flash_attention_fp8_varlen with a sliding window, a softcap and attention sinks, packed or paged; its docstring holds for the
+    rest, and window_size, softcap and sinks are flash_attn_fp8_func's, per sequence (pos = i + len_k[b] - len_q[b]; sinks float32
+    (H_q,)).  Every sequence has the bits of flash_attn_fp8_func on that sequence alone with the same window, cap and sinks.  With
+    all three at their defaults the call IS flash_attention_fp8_varlen.  Everything else that one refuses is refused here."""
+    who = "flash_attn_fp8_varlen_func"
+    _fp8_refuse(who, tuple(n for n in _FP8_VARLEN_REFUSED if n not in _FP8_MOD_ARGS), unsupported, "call")
+    return _fp8_varlen_func(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, block_table, q_descale, k_descale,
+                            v_descale, softmax_scale, causal, out_dtype, return_softmax_lse,
+                            _fp8_mod_args(who, window_size, softcap, sinks))
+
+
+def _fp8_varlen_func(who, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, block_table, q_descale, k_descale, v_descale,
+                     softmax_scale, causal, out_dtype, return_softmax_lse, mod):
     for name, t in (("q", q), ("k", k), ("v", v)):
         if not isinstance(t, torch.Tensor):
             raise RuntimeError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
@@ -817,7 +885,7 @@ def flash_attention_fp8_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q
     with torch.no_grad():
         o, lse = ext.fp8_varlen_forward(q.detach(), k.detach(), v.detach(), cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k,
                                         bool(causal), softmax_scale, det(q_descale), det(k_descale), det(v_descale), out_dtype,
-                                        block_table)
+                                        block_table, **mod)
     return (o, lse) if return_softmax_lse else o
 
 
@@ -850,15 +918,35 @@ def flash_attention_fp8_kvcache(q, k_cache, v_cache, *, cache_seqlens=None, bloc
     window_size, softcap, alibi_slopes, sinks, cache_leftpad, cu_seqlens_q, qv, block_table together with cache_batch_idx, out_dtype
     other than bfloat16 / float16.
     Returns o (B, Nq, H_q, 128) in out_dtype, and with return_softmax_lse also lse float32 (B, H_q, Nq).  No gradient."""
-    who = "flash_attention_fp8_kvcache"
-    for name, val in unsupported.items():
-        if name in _FP8_KVCACHE_REFUSED:
-            if val is None or val is False or (name == "window_size" and tuple(val) == (-1, -1)) or \
-                    (name in ("softcap", "dropout_p") and val == 0.0) or (name == "max_seqlen_q" and val == 0):
-                continue
-            hint = " (the cache is filled by flash_attn_with_kvcache's append, or by the caller)" if name in ("k", "v") else ""
-            raise NotImplementedError(f"{who}: {name} is not supported by the fp8 decode call{hint}")
-        raise TypeError(f"{who}() got an unexpected keyword argument {name!r}")
+    _fp8_refuse("flash_attention_fp8_kvcache", _FP8_KVCACHE_REFUSED, unsupported, "decode call", "flash_attn_fp8_with_kvcache")
+    return _fp8_kvcache_func("flash_attention_fp8_kvcache", q, k_cache, v_cache, cache_seqlens, block_table, cache_batch_idx, q_descale,
+                             k_descale, v_descale, softmax_scale, causal, num_splits, out_dtype, return_softmax_lse, {})
+
+
+def flash_attn_fp8_with_kvcache(q, k_cache, v_cache, *, cache_seqlens=None, block_table=None, cache_batch_idx=None, q_descale=None,
+                                k_descale=None, v_descale=None, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
+                                sinks=None, num_splits=0, out_dtype=torch.bfloat16, return_softmax_lse=False, **unsupported):
+    """flash_attention_fp8_kvcache with a sliding window, a softcap and attention sinks; its docstring holds for the rest.
+      window_size  (left, right) ints >= -1, -1 = unbounded; causal=True sets right = 0.  Token i of a sequence of len_b cached
+                   keys sits at pos = len_b - Nq + i and sees key j iff pos - left <= j <= pos + right and 0 <= j < len_b: the
+                   visible set of flash_attn_with_kvcache given the same arguments.  The splits cut only the keys from the
+                   first 64-key tile some row of a 32-row tile sees; no table entry and no cache byte below it is read.  The
+                   split rule (num_splits=0) takes min(capacity, left + max(right, 0) + Nq) for the capacity when left >= 0.
+      softcap      C > 0: s~ = C tanh(s / C), before the mask; 0 = off.
+      sinks        float32 (H_q,) on q's device in natural-log units, one per QUERY head, read on the device only (a captured call
+                   replays with changed values).  The sink joins in the combine, once per row, so such a call runs at least two
+                   splits (num_splits=1 is raised to 2).  A row without a visible key gives o = 0, lse = sink.
+    The result's bits depend on num_splits, the window and nothing else of the launch.  With all three at their defaults the call
+    IS flash_attention_fp8_kvcache.  Everything else that one refuses is refused here by name."""
+    who = "flash_attn_fp8_with_kvcache"
+    _fp8_refuse(who, tuple(n for n in _FP8_KVCACHE_REFUSED if n not in _FP8_MOD_ARGS), unsupported, "decode call")
+    return _fp8_kvcache_func(who, q, k_cache, v_cache, cache_seqlens, block_table, cache_batch_idx, q_descale, k_descale, v_descale,
+                             softmax_scale, causal, num_splits, out_dtype, return_softmax_lse,
+                             _fp8_mod_args(who, window_size, softcap, sinks))
+
+
+def _fp8_kvcache_func(who, q, k_cache, v_cache, cache_seqlens, block_table, cache_batch_idx, q_descale, k_descale, v_descale,
+                      softmax_scale, causal, num_splits, out_dtype, return_softmax_lse, mod):
     if not isinstance(q, torch.Tensor):
         raise RuntimeError(f"{who}: q must be a tensor, got {type(q).__name__}")
     if q.dtype in (torch.float16, torch.bfloat16, torch.float32):
@@ -881,7 +969,7 @@ def flash_attention_fp8_kvcache(q, k_cache, v_cache, *, cache_seqlens=None, bloc
     with torch.no_grad():
         o, lse = ext.fp8_kvcache_forward(q.detach(), k_cache.detach(), v_cache.detach(), cache_seqlens, block_table, cache_batch_idx,
                                          det(q_descale), det(k_descale), det(v_descale), softmax_scale, bool(causal), num_splits,
-                                         out_dtype)
+                                         out_dtype, **mod)
     return (o, lse) if return_softmax_lse else o
 
 

@@ -31,7 +31,8 @@ hipEvent_t g_prof_open[fa::K_COUNT];
 const char* const kKernelNames[fa::K_COUNT] = {"fwd_f32", "bwd_delta", "bwd_dkdv_f32", "bwd_dq_f32", "fwd_mfma",
                                                "bwd_mfma", "bwd_dq_cvt", "bwd_dq_mfma", "fp8_quant", "fwd_fp8", "ex_fwd", "ex_bwd", "kv_group_sum",
                                                "fp8in_vt", "fp8in_fwd", "fp8in_vt_varlen", "fp8in_fwd_varlen", "idx_pack", "idx_logits",
-                                               "idx_topk", "fp8kv_split", "fp8q_amax", "fp8q_quant", "fp8q_fused"};
+                                               "idx_topk", "fp8kv_split", "fp8q_amax", "fp8q_quant", "fp8q_fused", "fp8in_fwd_mod",
+                                               "fp8in_fwd_varlen_mod", "fp8kv_split_mod"};
 
 hipEvent_t prof_get_event() {
     if (!g_prof_free.empty()) { hipEvent_t e = g_prof_free.back(); g_prof_free.pop_back(); return e; }
@@ -175,7 +176,8 @@ int set_option(const char* name, int value) {
     return -1;
 }
 std::atomic<long long> g_route_hits[ROUTE_COUNT];
-constexpr const char* kRouteNames[ROUTE_COUNT] = {"dkdv_stream", "dkdv_lean", "fp8_quant_fused", "fp8_quant_two_pass", "fp8_quant_static"};
+constexpr const char* kRouteNames[ROUTE_COUNT] = {"dkdv_stream", "dkdv_lean", "fp8_quant_fused", "fp8_quant_two_pass", "fp8_quant_static",
+                                                   "fp8in_fwd_mod", "fp8in_fwd_varlen_mod", "fp8kv_split_mod"};
 void route_hit(int id) { g_route_hits[id].fetch_add(1, std::memory_order_relaxed); }
 long long route_count(const char* name) {
     for (int i = 0; i < ROUTE_COUNT; ++i)
@@ -2854,7 +2856,27 @@ struct Fp8Tensor {
     const void* p = nullptr;
     int64_t bs = 0, hs = 0, ts = 0;
 };
+// What the _mod entry points of the three fp8 calls add, checked by name: window bounds >= -1, a finite softcap >= 0, one sink
+// per query head.  The parents' entry points leave Fp8Mod at its defaults, which is no feature.
+static int fp8_mod_check(const char* who, const fa::Fp8Mod& m, int64_t heads_q) {
+    if (m.window_left < -1 || m.window_right < -1)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: window (%lld, %lld): each bound must be >= 0, or -1 for unbounded", who,
+                    (long long)m.window_left, (long long)m.window_right);
+    if (!(m.softcap == m.softcap) || m.softcap < 0.0 || m.softcap > 3.0e38)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: softcap must be a finite number >= 0 (got %g)", who, m.softcap);
+    if (m.sinks) {
+        if (m.sink_heads != heads_q)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: sink_heads=%lld must be heads_q=%lld (one sink per query head)", who,
+                        (long long)m.sink_heads, (long long)heads_q);
+        if ((uintptr_t)m.sinks % 4 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: sinks must be 4-byte aligned", who);
+    } else if (m.sink_heads != 0) {
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: sink_heads must be 0 without sinks (got %lld)", who, (long long)m.sink_heads);
+    }
+    return FA_OK;
+}
+
 struct Fp8Call {
+    fa::Fp8Mod mod;
     Fp8Tensor q, k, v, o;
     float* lse = nullptr;
     const float *q_descale = nullptr, *k_descale = nullptr, *v_descale = nullptr;
@@ -2893,6 +2915,7 @@ static int fp8_forward_impl(const char* who, const Fp8Call& c) {
                         (long long)c.heads_kv);
         if ((uintptr_t)s.p % 4 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: %s must be 4-byte aligned", who, s.name);
     }
+    if (const int rc = fp8_mod_check(who, c.mod, c.heads_q)) return rc;
     // (6) alignment and strides: 16-byte units (q, k, v in bytes, o in 16-bit elements), rows that do not overlap
     if (!aligned16({c.q.p, c.k.p, c.v.p, c.o.p})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: q, k, v and o must be 16-byte aligned", who);
     if ((uintptr_t)c.lse % 4 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: lse must be 4-byte aligned", who);
@@ -2933,7 +2956,7 @@ static int fp8_forward_impl(const char* who, const Fp8Call& c) {
     a.v_bs = c.batch > 1 ? c.v.bs : 0; a.v_hs = c.heads_kv > 1 ? c.v.hs : 0; a.v_ts = c.nk > 1 ? c.v.ts : 128;
     a.o_bs = c.batch > 1 ? c.o.bs : 0; a.o_hs = c.heads_q > 1 ? c.o.hs : 0; a.o_ts = c.nq > 1 ? c.o.ts : 128;
     a.causal = c.causal != 0; a.scale = (float)c.scale; a.workspace = c.workspace;
-    return launched(who, fa::launch_fp8_inputs(a, reinterpret_cast<hipStream_t>(c.stream)));
+    return launched(who, fa::launch_fp8_inputs_mod(a, c.mod, reinterpret_cast<hipStream_t>(c.stream)));
 }
 
 size_t fa_fp8_forward_workspace_bytes(int64_t batch, int64_t heads_kv, int64_t seqlen_k, int64_t d) {
@@ -2961,9 +2984,33 @@ int fa_fp8_forward(const void* q, const void* k, const void* v, void* o, float* 
     return fp8_forward_impl("fa_fp8_forward", c);
 }
 
+int fa_fp8_forward_mod(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
+                       const float* v_descale, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_k, int64_t d,
+                       int dtype, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_token_stride, int64_t k_batch_stride,
+                       int64_t k_head_stride, int64_t k_token_stride, int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride,
+                       int64_t o_batch_stride, int64_t o_head_stride, int64_t o_token_stride, int64_t q_descale_batch_stride,
+                       int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace,
+                       size_t workspace_bytes, void* stream, int64_t window_left, int64_t window_right, double softcap, const float* sinks,
+                       int64_t sink_heads) {
+    Fp8Call c;
+    c.q.p = q; c.q.bs = q_batch_stride; c.q.hs = q_head_stride; c.q.ts = q_token_stride;
+    c.k.p = k; c.k.bs = k_batch_stride; c.k.hs = k_head_stride; c.k.ts = k_token_stride;
+    c.v.p = v; c.v.bs = v_batch_stride; c.v.hs = v_head_stride; c.v.ts = v_token_stride;
+    c.o.p = o; c.o.bs = o_batch_stride; c.o.hs = o_head_stride; c.o.ts = o_token_stride;
+    c.lse = lse; c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
+    c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
+    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.nq = seqlen_q; c.nk = seqlen_k; c.d = d;
+    c.dtype = dtype; c.causal = causal; c.scale = softmax_scale;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    c.mod.window_left = window_left; c.mod.window_right = window_right; c.mod.softcap = softcap; c.mod.sinks = sinks;
+    c.mod.sink_heads = sink_heads;
+    return fp8_forward_impl("fa_fp8_forward_mod", c);
+}
+
 // ---- the packed and the paged form of the fp8 call: see include/fa_mi355x.h
 // One call of fa_fp8_forward_varlen, a family of its own.
 struct Fp8VarCall {
+    fa::Fp8Mod mod;
     const void *q = nullptr, *k = nullptr, *v = nullptr;
     void* o = nullptr;
     float* lse = nullptr;
@@ -3005,6 +3052,7 @@ static int fp8_forward_varlen_impl(const char* who, const Fp8VarCall& c) {
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: dtype (of o) must be f16 or bf16 (got code %d)", who, c.dtype);
     if (!(c.scale == c.scale) || !scale_ok(c.scale))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale must be finite and > 0", who);
+    if (const int rc = fp8_mod_check(who, c.mod, c.heads_q)) return rc;
     // (6) the pages
     if (paged) {
         if (c.ps < 16 || c.ps % 16 != 0 || c.ps > 65536)
@@ -3086,7 +3134,7 @@ static int fp8_forward_varlen_impl(const char* who, const Fp8VarCall& c) {
     a.q_ts = c.q_ts; a.q_hs = c.heads_q > 1 ? c.q_hs : 0; a.k_ts = c.k_ts; a.k_hs = c.heads_kv > 1 ? c.k_hs : 0;
     a.v_ts = c.v_ts; a.v_hs = c.heads_kv > 1 ? c.v_hs : 0; a.k_ps = c.k_ps; a.v_ps = c.v_ps;
     a.causal = c.causal != 0; a.scale = (float)c.scale; a.workspace = c.workspace;
-    return launched(who, fa::launch_fp8_inputs_varlen(a, reinterpret_cast<hipStream_t>(c.stream)));
+    return launched(who, fa::launch_fp8_inputs_varlen_mod(a, c.mod, reinterpret_cast<hipStream_t>(c.stream)));
 }
 
 size_t fa_fp8_forward_varlen_workspace_bytes(int64_t batch, int64_t heads_kv, int64_t total_k, int64_t max_seqlen_k, int64_t max_blocks_per_seq,
@@ -3122,9 +3170,35 @@ int fa_fp8_forward_varlen(const void* q, const void* k, const void* v, void* o, 
     return fp8_forward_varlen_impl("fa_fp8_forward_varlen", c);
 }
 
+int fa_fp8_forward_varlen_mod(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
+                              const float* v_descale, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, const int32_t* block_table,
+                              int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q,
+                              int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_token_stride, int64_t q_head_stride,
+                              int64_t k_token_stride, int64_t k_head_stride, int64_t v_token_stride, int64_t v_head_stride,
+                              int64_t max_blocks_per_seq, int64_t num_blocks, int64_t page_block_size, int64_t k_page_stride,
+                              int64_t v_page_stride, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
+                              int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace, size_t workspace_bytes,
+                              void* stream, int64_t window_left, int64_t window_right, double softcap, const float* sinks,
+                              int64_t sink_heads) {
+    Fp8VarCall c;
+    c.q = q; c.k = k; c.v = v; c.o = o; c.lse = lse; c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
+    c.cu_q = cu_seqlens_q; c.cu_k = cu_seqlens_k; c.block_table = block_table;
+    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.total_q = total_q; c.total_k = total_k; c.max_q = max_seqlen_q;
+    c.max_k = max_seqlen_k; c.d = d; c.dtype = dtype;
+    c.q_ts = q_token_stride; c.q_hs = q_head_stride; c.k_ts = k_token_stride; c.k_hs = k_head_stride; c.v_ts = v_token_stride;
+    c.v_hs = v_head_stride;
+    c.max_blocks = max_blocks_per_seq; c.num_blocks = num_blocks; c.ps = page_block_size; c.k_ps = k_page_stride; c.v_ps = v_page_stride;
+    c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
+    c.causal = causal; c.scale = softmax_scale; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    c.mod.window_left = window_left; c.mod.window_right = window_right; c.mod.softcap = softcap; c.mod.sinks = sinks;
+    c.mod.sink_heads = sink_heads;
+    return fp8_forward_varlen_impl("fa_fp8_forward_varlen_mod", c);
+}
+
 // ---- fp8 KV-cache decoding with split-KV (e4m3 q over an e4m3 cache): see include/fa_mi355x.h
 // One call of fa_fp8_forward_kvcache, a family of its own.
 struct Fp8KvCall {
+    fa::Fp8Mod mod;
     const void *q = nullptr, *k_cache = nullptr, *v_cache = nullptr;
     void* o = nullptr;
     float* lse = nullptr;
@@ -3146,6 +3220,14 @@ struct Fp8KvCall {
 static int64_t fp8_kv_splits(int64_t batch, int64_t hq, int64_t hkv, int64_t nq, int64_t cache_len, int64_t num_splits) {
     if (num_splits > 0) return num_splits;
     return fa::fp8kv_num_splits(batch, hq, hkv, nq, cache_len);
+}
+
+// the featured call: the rule sees the keys a window can show instead of the capacity, and sinks raise 1 split to 2 (the sink
+// joins in the combine, which such a call always runs)
+static int64_t fp8_kv_splits_mod(int64_t batch, int64_t hq, int64_t hkv, int64_t nq, int64_t cache_len, int64_t num_splits, int causal,
+                                 const fa::Fp8Mod& m) {
+    const int64_t S = fp8_kv_splits(batch, hq, hkv, nq, fa::fp8kv_split_len(cache_len, nq, causal, m), num_splits);
+    return m.sinks && S < 2 ? 2 : S;
 }
 
 static int fp8_kvcache_impl(const char* who, const Fp8KvCall& c) {
@@ -3241,13 +3323,14 @@ static int fp8_kvcache_impl(const char* who, const Fp8KvCall& c) {
     // (9) the splits
     if (c.num_splits < 0 || c.num_splits > 256)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_splits must lie in [0, 256] (got %lld)", who, (long long)c.num_splits);
-    const int64_t S = fp8_kv_splits(c.batch, c.heads_q, c.heads_kv, c.seqlen_q, c.cache_len, c.num_splits);
+    if (const int rc = fp8_mod_check(who, c.mod, c.heads_q)) return rc;
+    const int64_t S = fp8_kv_splits_mod(c.batch, c.heads_q, c.heads_kv, c.seqlen_q, c.cache_len, c.num_splits, c.causal, c.mod);
     // (10) the workspace
     const size_t need = fa::kv_workspace_bytes(c.batch, c.heads_q, c.seqlen_q, 128, (int)S);
     if (need > 0) {
         if (!c.workspace || c.workspace_bytes < need)
-            return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes is too small (need %zu: fa_fp8_forward_kvcache_workspace_bytes)", who,
-                        c.workspace ? c.workspace_bytes : (size_t)0, need);
+            return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes is too small (need %zu: fa_fp8_forward_kvcache_workspace_bytes%s)", who,
+                        c.workspace ? c.workspace_bytes : (size_t)0, need, c.mod.any() ? "_mod" : "");
         if ((uintptr_t)c.workspace % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
     }
 
@@ -3261,7 +3344,7 @@ static int fp8_kvcache_impl(const char* who, const Fp8KvCall& c) {
     a.q_bs = c.q_bs; a.q_ts = c.q_ts; a.kc_bs = c.k_bs; a.kc_ts = c.k_ts; a.vc_bs = c.v_bs; a.vc_ts = c.v_ts;
     a.table_row_stride = c.table_rs; a.num_blocks = c.num_blocks; a.page_size = c.ps;
     a.causal = c.causal != 0; a.scale = (float)c.scale; a.num_splits = S; a.workspace = c.workspace;
-    return launched(who, fa::launch_fp8_kvcache(a, reinterpret_cast<hipStream_t>(c.stream)));
+    return launched(who, fa::launch_fp8_kvcache_mod(a, c.mod, reinterpret_cast<hipStream_t>(c.stream)));
 }
 
 size_t fa_fp8_forward_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t d,
@@ -3291,6 +3374,45 @@ int fa_fp8_forward_kvcache(const void* q, const void* k_cache, const void* v_cac
     c.causal = causal; c.scale = softmax_scale; c.num_splits = num_splits;
     c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
     return fp8_kvcache_impl("fa_fp8_forward_kvcache", c);
+}
+
+size_t fa_fp8_forward_kvcache_workspace_bytes_mod(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
+                                                  int64_t d, int64_t num_splits, int causal, int64_t window_left, int64_t window_right,
+                                                  int with_sinks) {
+    if (!kv_ws_args_ok(batch, heads_q, heads_kv, seqlen_q, cache_len, d, num_splits) || d != 128 || window_left < -1 || window_right < -1)
+        return 0;
+    fa::Fp8Mod m;
+    m.window_left = window_left; m.window_right = window_right;
+    int64_t S = fp8_kv_splits(batch, heads_q, heads_kv, seqlen_q, fa::fp8kv_split_len(cache_len, seqlen_q, causal, m), num_splits);
+    if (with_sinks && S < 2) S = 2;
+    return fa::kv_workspace_bytes(batch, heads_q, seqlen_q, 128, (int)S);
+}
+
+int fa_fp8_forward_kvcache_mod(const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const float* q_descale,
+                               const float* k_descale, const float* v_descale, const int32_t* cache_seqlens, const int32_t* block_table,
+                               const int32_t* cache_batch_idx, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q,
+                               int64_t cache_len, int64_t cache_batch, int64_t d, int dtype, int q_dtype, int cache_dtype,
+                               int64_t q_batch_stride, int64_t q_token_stride, int64_t k_batch_stride, int64_t k_token_stride,
+                               int64_t v_batch_stride, int64_t v_token_stride, int64_t block_table_row_stride, int64_t num_blocks,
+                               int64_t page_block_size, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
+                               int64_t v_descale_batch_stride, int causal, double softmax_scale, int64_t num_splits, void* workspace,
+                               size_t workspace_bytes, void* stream, int64_t window_left, int64_t window_right, double softcap,
+                               const float* sinks, int64_t sink_heads) {
+    Fp8KvCall c;
+    c.q = q; c.k_cache = k_cache; c.v_cache = v_cache; c.o = o; c.lse = lse;
+    c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
+    c.cache_seqlens = cache_seqlens; c.block_table = block_table; c.cache_batch_idx = cache_batch_idx;
+    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.seqlen_q = seqlen_q; c.cache_len = cache_len; c.cache_batch = cache_batch;
+    c.d = d; c.dtype = dtype; c.q_dtype = q_dtype; c.cache_dtype = cache_dtype;
+    c.q_bs = q_batch_stride; c.q_ts = q_token_stride; c.k_bs = k_batch_stride; c.k_ts = k_token_stride; c.v_bs = v_batch_stride;
+    c.v_ts = v_token_stride;
+    c.table_rs = block_table_row_stride; c.num_blocks = num_blocks; c.ps = page_block_size;
+    c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
+    c.causal = causal; c.scale = softmax_scale; c.num_splits = num_splits;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    c.mod.window_left = window_left; c.mod.window_right = window_right; c.mod.softcap = softcap; c.mod.sinks = sinks;
+    c.mod.sink_heads = sink_heads;
+    return fp8_kvcache_impl("fa_fp8_forward_kvcache_mod", c);
 }
 
 size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {

@@ -9,6 +9,8 @@
 //                       the G = H_q / H_kv query heads that share a K/V head, times the Nq query tokens, are packed into 32-row tiles
 //                       (row = token * G + head in the group), and each wave reads its cache bytes exactly once.
 //   kv_combine_kernel<Tag, false>   fa_decode.hip's combine, unchanged, over fp32 partials in kv_workspace_bytes' layout.
+// fa_fp8_forward_kvcache_mod (a sliding window, a softcap, attention sinks) launches fp8kv_split_mod_kernel
+// instead, and with sinks kv_combine_kernel<Tag, true>; a call without the three launches the two above as before.
 //
 // One 64-key tile of a wave, lane l = (r = l & 31, h = l >> 5):
 //   S^T = K Q^T     A = K as it lies in memory: key k0 + 32 kb + r, head-dim bytes 64 M + 32 h .. + 31 (two 16-byte loads), B = the
@@ -322,6 +324,285 @@ __global__ __launch_bounds__(64, 2) void fp8kv_split_kernel(const Fp8KvParams p)
     }
 }
 
+
+// What fp8kv_split_mod_kernel takes beside Fp8KvParams (fa_fp8_forward_kvcache_mod)
+struct Fp8KvMod {
+    int wl, wr;                           // token i sees keys [i + coff - wl, i + coff + wr]; kWinNone: unbounded, wr = 0 if causal
+    float cap_k, cap2;                    // 2 / softcap, softcap * log2(e); cap2 == 0: no softcap
+};
+
+// fp8kv_split_kernel's text (DUPLICATED rather than shared: as one body with the features in discarded `if constexpr` branches
+// fp8kv_split_kernel's instructions changed) with, as wave-uniform run-time switches:
+//   window   the tile's keys are [lo, hi) with lo the first 64-key tile some row of the 32 sees, and the splits cut [lo, hi): no
+//            table entry, K byte or V byte below lo is read.  The mask takes the row's lower bound beside its upper one on a
+//            tile that bound crosses.
+//   softcap  fwd_fp8in_mod_kernel's (fa_fp8_inputs.hip): the capped score, in log2 units, replaces the raw product before the
+//            mask, and the factor of what follows is 1.
+// Sinks are not this kernel's: they join in kv_combine_kernel<Tag, true>, once per row.
+template <typename Tag, bool PAGED>
+__global__ __launch_bounds__(64, 2) void fp8kv_split_mod_kernel(const Fp8KvParams p, const Fp8KvMod md) {
+    constexpr int D = 128, KT = 64, NDV = D / 32;
+    __shared__ __attribute__((aligned(16))) char vt[kVtBytes];   // V^T tile, [head dim][64 key bytes in P's key order]
+    const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
+    const int s = blockIdx.x, S = gridDim.x;
+    const int hk = blockIdx.y % p.hkv, rt = blockIdx.y / p.hkv, b = blockIdx.z;
+    const int nq = p.nq, rows = p.rows, G = p.G;
+    const int pr0 = 32 * rt, pr = pr0 + r;                        // (the grid has ceil(rows / 32) row tiles: pr0 < rows)
+
+    // the sequence: its length, and the cache row its keys lie in (contiguous)
+    int lk = p.seqlens ? min(max(p.seqlens[b], 0), p.cap) : p.cap;
+    long long crow = b;
+    if (!PAGED && p.bidx) {
+        const int ix = p.bidx[b];
+        crow = ix;
+        if ((unsigned)ix >= (unsigned)p.bcache) { crow = 0; lk = 0; }   // an index outside the cache: an empty sequence
+    }
+    const int coff = lk - nq;                                     // causal: token i sees key j <= i + coff
+    const int qlo = pr0 / G, qhi = (min(pr0 + 32, rows) - 1) / G;
+    // the split's keys [kbeg, kend): the tile's visible keys [0, hi) cut into 64-key tiles, tiles [s nt / S, (s + 1) nt / S)
+    const int hi = max(0, min(lk, qhi + coff + md.wr + 1));
+    const int lo = max(0, qlo + coff - md.wl) & ~(KT - 1);       // the first 64-key tile some row sees (whole 16-key groups)
+    const int nt = hi > lo ? (hi - lo + KT - 1) / KT : 0;
+    const int t0 = (int)((long long)s * nt / S), t1 = (int)((long long)(s + 1) * nt / S);
+    const int kbeg = lo + t0 * KT, kend = min(hi, lo + t1 * KT);
+
+    // this lane's query row: token qi, query head hd; its last visible key rhi (padding rows of the tile: none)
+    const bool valid = pr < rows;
+    // (a padding row takes the tile's first token: its scores are masked like a real row's, and nothing of it is stored)
+    const int qi = valid ? pr / G : qlo, hd = hk * G + (valid ? pr - qi * G : 0);
+    const int rhi = min(min(qi + coff + md.wr, lk - 1), kend - 1), rlo = qi + coff - md.wl;   // the row sees keys [rlo, rhi]
+
+    i32x8_t qb[2];
+    {
+        const uint8_t* qp = p.q + (long long)b * p.q_bs + (long long)qi * p.q_ts + hd * D + 32 * h;
+#pragma unroll
+        for (int M = 0; M < 2; ++M) {
+            const u32x4 a0 = *reinterpret_cast<const u32x4*>(qp + 64 * M), a1 = *reinterpret_cast<const u32x4*>(qp + 64 * M + 16);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                qb[M][i] = valid ? (int)a0[i] : 0;
+                qb[M][4 + i] = valid ? (int)a1[i] : 0;
+            }
+        }
+    }
+    const float qd = p.qds ? p.qds[b * p.qds_bs + hk] : 1.f;
+    const float kd = p.kds ? p.kds[b * p.kds_bs + hk] : 1.f;
+    const float vd = p.vds ? p.vds[b * p.vds_bs + hk] : 1.f;
+    const float f = (p.c_log2 * qd) * kd;                         // the one score factor of this wave, > 0
+    const bool capped = md.cap2 != 0.f;
+    const float ck = f * md.cap_k;
+    const float fe = capped ? 1.f : f;                            // the factor of what the accumulators hold after the cap
+
+    // byte offsets of the first token of the 16-key groups of the tile at k0 in the two caches, -1: the group reads as zeros
+    const int* tbl = PAGED ? p.table + b * p.tbl_rs : nullptr;
+    auto group_bases = [&](int k0, i64x4_t& kb_, i64x4_t& vb_) {
+        int j0 = 0, s0 = 0;
+        if (PAGED) { j0 = k0 / p.ps; s0 = k0 - j0 * p.ps; }
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+            const int key0 = k0 + 16 * g4;
+            kb_[g4] = -1; vb_[g4] = -1;
+            if (key0 < kend) {
+                if (PAGED) {
+                    int j = j0, sl = s0 + 16 * g4;
+#pragma unroll
+                    for (int i = 0; i < 3; ++i)
+                        if (sl >= p.ps) { sl -= p.ps; ++j; }
+                    const int pg = tbl[j];
+                    if ((unsigned)pg < (unsigned)p.nblk) {
+                        kb_[g4] = pg * p.kc_bs + (long long)sl * p.kc_ts;
+                        vb_[g4] = pg * p.vc_bs + (long long)sl * p.vc_ts;
+                    }
+                } else {
+                    kb_[g4] = crow * p.kc_bs + (long long)key0 * p.kc_ts;
+                    vb_[g4] = crow * p.vc_bs + (long long)key0 * p.vc_ts;
+                }
+            }
+        }
+    };
+
+    f32x16 oacc[NDV];
+#pragma unroll
+    for (int t = 0; t < NDV; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) oacc[t][i] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;                         // running max in log2 units of the scaled score
+    const uint8_t* nowhere = p.q;                                 // readable, for a load whose value is selected away
+
+    for (int k0 = kbeg; k0 < kend; k0 += KT) {
+        i64x4_t kbase, vbase;
+        group_bases(k0, kbase, vbase);
+
+        // a whole tile below the split's end on pages inside the pool: no lane needs a select on its addresses or its bytes
+        // (wave-uniform; the general form below is the same text with them)
+        const bool full = k0 + KT <= kend && kbase[0] >= 0 && kbase[1] >= 0 && kbase[2] >= 0 && kbase[3] >= 0;
+        f32x16 sacc[2];
+        auto front = [&](auto full_c) {
+        constexpr bool FULL = decltype(full_c)::value;
+        // ---- S^T = K Q^T: K rows as they lie in memory
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+            const long long base_lo = kbase[2 * kb], base_hi = kbase[2 * kb + 1];
+            const long long base = (r >> 4) ? base_hi : base_lo;
+            const bool ok = FULL || (base >= 0 && k0 + 32 * kb + r < kend);
+            const uint8_t* kp = ok ? p.kc + base + (r & 15) * p.kc_ts + hk * D + 32 * h : nowhere;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) sacc[kb][i] = 0.f;
+#pragma unroll
+            for (int M = 0; M < 2; ++M) {
+                const u32x4 a0 = *reinterpret_cast<const u32x4*>(kp + 64 * M), a1 = *reinterpret_cast<const u32x4*>(kp + 64 * M + 16);
+                i32x8_t ka;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    ka[i] = ok ? (int)a0[i] : 0;
+                    ka[4 + i] = ok ? (int)a1[i] : 0;
+                }
+                sacc[kb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ka, qb[M], sacc[kb], 0, 0, 0, 127, 0, 127);
+            }
+        }
+
+        // ---- V -> V^T through registers: 16 keys x 4 head dims a lane and key block, four 4 x 4 byte transposes, one 16-byte chunk
+        // a head dim (the previous tile's operand reads were issued before these writes: one wave, LDS in order)
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+            uint32_t t[4][4];                                     // [j][dd]: head dim 4 r + dd of keys 32 kb + 4 h + 8 j + (0 .. 3)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const long long base = vbase[2 * kb + (j >> 1)];  // wave-uniform
+                uint32_t x[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int pos = 4 * h + 8 * (j & 1) + c;      // the key's place in its 16-key group
+                    const bool ok = FULL || (base >= 0 && k0 + 32 * kb + 16 * (j >> 1) + pos < kend);
+                    const uint8_t* vp = ok ? p.vc + base + pos * p.vc_ts + hk * D + 4 * r : nowhere;
+                    const uint32_t y = *reinterpret_cast<const uint32_t*>(vp);
+                    x[c] = ok ? y : 0u;
+                }
+                transpose4x4(x, t[j]);
+            }
+#pragma unroll
+            for (int dd = 0; dd < 4; ++dd)
+                *reinterpret_cast<u32x4*>(vt + vt_off(4 * r + dd, 2 * h + kb)) = u32x4{t[0][dd], t[1][dd], t[2][dd], t[3][dd]};
+        }
+        };
+        if (full) front(std::true_type{});
+        else front(std::false_type{});
+
+        // ---- mask and row maximum on the RAW products; f > 0 goes to the maximum once and to every element inside the exp2's fma
+        // (the mask only where a row of the tile can end inside this key tile: wave-uniform)
+        if (capped) {                             // the softcap first (before the mask): one exp2 and one rcp an element
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float rr = __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(sacc[kb][i] * ck) + 1.f);
+                    sacc[kb][i] = fmaf(rr, -2.f * md.cap2, md.cap2);
+                }
+        }
+        const bool need_mask = !full || k0 + KT - 1 > qlo + coff + md.wr;
+        const bool need_lo = k0 < qhi + coff - md.wl;   // some row's lower bound lies inside or past this tile
+        float mx = -INFINITY;
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+            if (need_mask) {
+                const int thr = rhi - (k0 + 32 * kb + 4 * h);
+#pragma unroll
+                for (int i = 0; i < 16; ++i)
+                    if ((i & 3) + 8 * (i >> 2) > thr) sacc[kb][i] = -INFINITY;
+            }
+            if (need_lo) {
+                const int thr = rlo - (k0 + 32 * kb + 4 * h);
+#pragma unroll
+                for (int i = 0; i < 16; ++i)
+                    if ((i & 3) + 8 * (i >> 2) < thr) sacc[kb][i] = -INFINITY;
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) mx = fmaxf(mx, sacc[kb][i]);
+        }
+        mx = mx * fe;
+        mx = fmaxf(mx, wave_half_swap(mx));
+        const float m_new = fmaxf(m_run, mx);
+        float m_use;
+        if (__any(valid && m_new - m_run > 8.0f) != 0) {   // lazy rescale (fwd_fp8in_kernel) on the real rows; a row's first visible key: inf > 8
+            m_use = m_new;
+            const float alpha = __builtin_amdgcn_exp2f(m_run - ((m_new == -INFINITY) ? 0.f : m_new));
+            m_run = m_new;
+            l_run *= alpha;
+#pragma unroll
+            for (int t2 = 0; t2 < NDV; ++t2)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) oacc[t2][i] *= alpha;
+        } else {
+            m_use = m_run;
+        }
+        if (m_use == -INFINITY) m_use = 0.f;      // a row without a visible key so far: p = exp2(-inf) = 0, not exp2(-inf + inf)
+        float rs = 0.f;
+        i32x8_t pb;                               // P^T as the accumulators hold it, rounded to e4m3 (RNE)
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const float pe = __builtin_amdgcn_exp2f(fmaf(sacc[kb][i], fe, -m_use));   // (-inf stays -inf: fe > 0)
+                sacc[kb][i] = pe;
+                rs += pe;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                int wd = 0;
+                wd = __builtin_amdgcn_cvt_pk_fp8_f32(sacc[kb][4 * j + 0], sacc[kb][4 * j + 1], wd, false);
+                wd = __builtin_amdgcn_cvt_pk_fp8_f32(sacc[kb][4 * j + 2], sacc[kb][4 * j + 3], wd, true);
+                pb[4 * kb + j] = wd;
+            }
+        }
+        l_run += rs;
+
+        // ---- O^T = V^T P^T: the lane's 32 key bytes of head dim 32 dvb + r
+#pragma unroll
+        for (int dvb = 0; dvb < NDV; ++dvb) {
+            const u32x4 a0 = *reinterpret_cast<const u32x4*>(vt + vt_off(32 * dvb + r, 2 * h));
+            const u32x4 a1 = *reinterpret_cast<const u32x4*>(vt + vt_off(32 * dvb + r, 2 * h + 1));
+            const i32x8_t va = {(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], (int)a1[0], (int)a1[1], (int)a1[2], (int)a1[3]};
+            oacc[dvb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(va, pb, oacc[dvb], 0, 0, 0, 127, 0, 127);
+        }
+    }
+
+    // ---- epilogue: O^T register i of block dvb is head dim 32 dvb + 4 h + (i & 3) + 8 (i >> 2) of the lane's query row
+    const float l_tot = l_run + wave_half_swap(l_run);
+    if (!valid) return;
+    const bool dead = l_tot == 0.f;                      // no visible key: o = 0, lse = -inf (a NaN l is not dead: it propagates)
+    const float inv = vd * (1.f / l_tot);                // v_descale once, with 1 / l
+    const float lse_v = dead ? -INFINITY : (m_run + log2f(l_tot)) * 0.6931471805599453f;
+    const size_t row_id = ((size_t)b * p.hq + hd) * nq + qi;
+    if (S == 1) {
+        uint16_t* orow = p.o + (((size_t)b * nq + qi) * p.hq + hd) * D;
+#pragma unroll
+        for (int dvb = 0; dvb < NDV; ++dvb)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                float y[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) y[j] = dead ? 0.f : oacc[dvb][4 * g + j] * inv;
+                u32x2 v;
+                v[0] = pack2_rn<Tag>(y[0], y[1]);
+                v[1] = pack2_rn<Tag>(y[2], y[3]);
+                *reinterpret_cast<u32x2*>(orow + 32 * dvb + 8 * g + 4 * h) = v;
+            }
+        if (h == 0) p.lse[row_id] = lse_v;
+    } else {
+        float* prow = p.po + (row_id * S + s) * D;
+#pragma unroll
+        for (int dvb = 0; dvb < NDV; ++dvb)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                f32x4 y;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) y[j] = dead ? 0.f : oacc[dvb][4 * g + j] * inv;
+                *reinterpret_cast<f32x4*>(prow + 32 * dvb + 8 * g + 4 * h) = y;
+            }
+        if (h == 0) p.plse[row_id * S + s] = lse_v;
+    }
+}
+
 }  // namespace
 
 int fp8kv_row_tiles(int64_t heads_q, int64_t heads_kv, int64_t seqlen_q) { return (int)(((heads_q / heads_kv) * seqlen_q + 31) / 32); }
@@ -331,7 +612,14 @@ int fp8kv_num_splits(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t s
     return kv_num_splits(batch, heads_kv, fp8kv_row_tiles(heads_q, heads_kv, seqlen_q), cache_len);
 }
 
-hipError_t launch_fp8_kvcache(const Fp8KvArgs& a, hipStream_t st) {
+int64_t fp8kv_split_len(int64_t cache_len, int64_t seqlen_q, int causal, const Fp8Mod& m) {
+    if (m.window_left < 0) return cache_len;
+    const int64_t right = causal || m.window_right < 0 ? 0 : m.window_right;
+    return std::min(cache_len, std::min<int64_t>(m.window_left, kWinNone) + std::min<int64_t>(right, kWinNone) + seqlen_q);
+}
+
+// md: null for fa_fp8_forward_kvcache; else the featured call's kernel arguments, with its sinks (null: none)
+static hipError_t launch_fp8_kvcache_t(const Fp8KvArgs& a, const Fp8KvMod* md, const float* sinks, int sink_heads, hipStream_t st) {
     Fp8KvParams p;
     p.q = (const uint8_t*)a.q; p.kc = (const uint8_t*)a.k_cache; p.vc = (const uint8_t*)a.v_cache;
     p.o = (uint16_t*)a.o; p.lse = a.lse;
@@ -350,7 +638,18 @@ hipError_t launch_fp8_kvcache(const Fp8KvArgs& a, hipStream_t st) {
     p.po = (float*)a.workspace;
     p.plse = S > 1 ? (float*)((char*)a.workspace + ((q_rows * S * 128 * 4 + 255) & ~(size_t)255)) : nullptr;
     const dim3 grid((unsigned)S, (unsigned)(fp8kv_row_tiles(a.heads_q, a.heads_kv, a.seqlen_q) * p.hkv), (unsigned)a.batch);
-    {
+    if (md) {
+        route_hit(ROUTE_FP8KV_SPLIT_MOD);
+        ProfScope ps(K_FP8KV_SPLIT_MOD, st);
+        const bool paged = a.block_table != nullptr;
+        if (a.dtype == 2) {
+            if (paged) hipLaunchKernelGGL((fp8kv_split_mod_kernel<bf16_tag, true>), grid, dim3(64), 0, st, p, *md);
+            else hipLaunchKernelGGL((fp8kv_split_mod_kernel<bf16_tag, false>), grid, dim3(64), 0, st, p, *md);
+        } else {
+            if (paged) hipLaunchKernelGGL((fp8kv_split_mod_kernel<f16_tag, true>), grid, dim3(64), 0, st, p, *md);
+            else hipLaunchKernelGGL((fp8kv_split_mod_kernel<f16_tag, false>), grid, dim3(64), 0, st, p, *md);
+        }
+    } else {
         ProfScope ps(K_FP8KV_SPLIT, st);
         const bool paged = a.block_table != nullptr;
         if (a.dtype == 2) {
@@ -363,7 +662,21 @@ hipError_t launch_fp8_kvcache(const Fp8KvArgs& a, hipStream_t st) {
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || S == 1) return e;
+    if (sinks) return launch_kv_combine_sink(a.o, a.lse, p.po, p.plse, a.batch, a.heads_q, a.seqlen_q, 128, a.dtype, S, sinks, sink_heads, st);
     return launch_kv_combine(a.o, a.lse, p.po, p.plse, a.batch, a.heads_q, a.seqlen_q, 128, a.dtype, S, st);
+}
+
+hipError_t launch_fp8_kvcache(const Fp8KvArgs& a, hipStream_t st) { return launch_fp8_kvcache_t(a, nullptr, nullptr, 0, st); }
+
+hipError_t launch_fp8_kvcache_mod(const Fp8KvArgs& a, const Fp8Mod& m, hipStream_t st) {
+    if (!m.any()) return launch_fp8_kvcache(a, st);     // the parent call, launch for launch
+    if (m.sinks && a.num_splits < 2) return hipErrorInvalidValue;   // (the C layer raises a sink call's S to 2: the sink joins in the combine)
+    Fp8KvMod md;
+    md.wl = m.window_left >= 0 ? (int)std::min<int64_t>(m.window_left, kWinNone) : kWinNone;
+    md.wr = a.causal ? 0 : (m.window_right >= 0 ? (int)std::min<int64_t>(m.window_right, kWinNone) : kWinNone);
+    md.cap_k = m.softcap > 0.0 ? (float)(2.0 / m.softcap) : 0.f;
+    md.cap2 = m.softcap > 0.0 ? (float)(m.softcap * 1.4426950408889634) : 0.f;
+    return launch_fp8_kvcache_t(a, &md, m.sinks, (int)(m.sink_heads > 0 ? m.sink_heads : 1), st);
 }
 
 }  // namespace fa

@@ -37,6 +37,9 @@
 //
 // The packed and the paged form of the call (fa_fp8_forward_varlen) follow the padded one below: fp8in_vt_varlen_kernel,
 // fwd_fp8in_varlen_kernel.
+// A sliding window, a softcap and attention sinks (fa_fp8_forward_mod, fa_fp8_forward_varlen_mod) are a
+// kernel of their own at the end of the file, fwd_fp8in_mod_kernel, for all three forms: a call without them launches the kernels
+// above as before.
 #include <algorithm>
 
 #include "fa_common.h"
@@ -263,28 +266,38 @@ size_t fp8in_workspace_bytes(int64_t units_kv, int64_t nk) {
     return (size_t)units_kv * (size_t)((nk + 127) / 128) * 128 * 128 + 256;   // V^T tiles and a pad
 }
 
-hipError_t launch_fp8_inputs(const Fp8InArgs& c, hipStream_t st) {
-    const int nb = (int)((c.nk + 63) / 64), ntile = (int)((c.nk + 127) / 128), nqt = (int)((c.nq + 255) / 256);
+// the transposer's launch and the attention kernel's arguments: what fa_fp8_forward and fa_fp8_forward_mod share on the host
+static hipError_t fp8in_launch_vt(const Fp8InArgs& c, hipStream_t st) {
+    const int nb = (int)((c.nk + 63) / 64), ntile = (int)((c.nk + 127) / 128);
     const int64_t units_kv = c.batch * c.heads_kv;
     {
         ProfScope ps(K_FP8IN_VT, st);
         hipLaunchKernelGGL(fp8in_vt_kernel, dim3((unsigned)(units_kv * nb)), dim3(256), 0, st, (const uint8_t*)c.v, (uint8_t*)c.workspace,
                            (int)c.nk, nb, ntile, (int)c.heads_kv, (long long)c.v_bs, (long long)c.v_hs, (long long)c.v_ts);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    return hipGetLastError();
+}
+
+static Fp8InKernelArgs fp8in_kernel_args(const Fp8InArgs& c) {
     Fp8InKernelArgs a;
     a.q = (const uint8_t*)c.q; a.k = (const uint8_t*)c.k; a.v8t = (const uint8_t*)c.workspace;
     a.o = (uint16_t*)c.o; a.lse = c.lse;
     a.qds = c.q_descale; a.kds = c.k_descale; a.vds = c.v_descale;
     a.qds_bs = (int)c.qds_bs; a.kds_bs = (int)c.kds_bs; a.vds_bs = (int)c.vds_bs;
     a.nq = (int)c.nq; a.nk = (int)c.nk; a.hq = (int)c.heads_q; a.hkv = (int)c.heads_kv; a.group = (int)(c.heads_q / c.heads_kv);
-    a.nqt = nqt; a.ntile = ntile;
+    a.nqt = (int)((c.nq + 255) / 256); a.ntile = (int)((c.nk + 127) / 128);
     a.q_ts = (int)c.q_ts; a.k_ts = (int)c.k_ts; a.o_ts = (int)c.o_ts;
     a.q_bs = c.q_bs; a.q_hs = c.q_hs; a.k_bs = c.k_bs; a.k_hs = c.k_hs; a.o_bs = c.o_bs; a.o_hs = c.o_hs;
     a.c_log2 = c.scale * 1.4426950408889634f;
+    return a;
+}
+
+hipError_t launch_fp8_inputs(const Fp8InArgs& c, hipStream_t st) {
+    const hipError_t e = fp8in_launch_vt(c, st);
+    if (e != hipSuccess) return e;
+    const Fp8InKernelArgs a = fp8in_kernel_args(c);
     const size_t smem = 2 * 2 * 128 * 128;
-    const unsigned grid = (unsigned)(c.batch * c.heads_q * nqt);
+    const unsigned grid = (unsigned)(c.batch * c.heads_q * a.nqt);
     ProfScope ps(K_FP8IN_FWD, st);
     auto launch = [&](auto kern) -> hipError_t {
         hipError_t e2 = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
@@ -596,9 +609,10 @@ size_t fp8in_varlen_workspace_bytes(const Fp8InVarArgs& c) {
     return (size_t)c.heads_kv * (size_t)fp8in_varlen_tiles_per_head(c) * 128 * 128 + 256;   // V^T tiles and a pad
 }
 
-template <bool PAGED> static hipError_t launch_fp8_inputs_varlen_t(const Fp8InVarArgs& c, hipStream_t st) {
+// the transposer's launch and the attention kernel's arguments: what fa_fp8_forward_varlen and fa_fp8_forward_varlen_mod share
+// on the host (c.max_q > 0)
+template <bool PAGED> static hipError_t fp8in_varlen_front(const Fp8InVarArgs& c, hipStream_t st, Fp8InVarKernelArgs& a) {
     const int64_t cap = PAGED ? std::min(c.max_k, c.max_blocks * c.page_size) : c.max_k;
-    if (c.max_q == 0) return hipSuccess;                 // no sequence has a query: nothing is written
     const int nbmax = (int)((cap + 63) / 64), nqt = (int)((c.max_q + 255) / 256);
     const int nt_head = (int)fp8in_varlen_tiles_per_head(c), nt_seq = (int)((cap + 127) / 128);
     ExPage pg{};
@@ -615,7 +629,6 @@ template <bool PAGED> static hipError_t launch_fp8_inputs_varlen_t(const Fp8InVa
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    Fp8InVarKernelArgs a;
     a.q = (const uint8_t*)c.q; a.k = (const uint8_t*)c.k; a.v8t = (const uint8_t*)c.workspace;
     a.o = (uint16_t*)c.o; a.lse = c.lse;
     a.qds = c.q_descale; a.kds = c.k_descale; a.vds = c.v_descale;
@@ -628,8 +641,16 @@ template <bool PAGED> static hipError_t launch_fp8_inputs_varlen_t(const Fp8InVa
     a.q_hs = c.q_hs; a.k_hs = c.k_hs; a.o_hs = 128;
     a.pg = pg;
     a.c_log2 = c.scale * 1.4426950408889634f;
+    return hipSuccess;
+}
+
+template <bool PAGED> static hipError_t launch_fp8_inputs_varlen_t(const Fp8InVarArgs& c, hipStream_t st) {
+    if (c.max_q == 0) return hipSuccess;                 // no sequence has a query: nothing is written
+    Fp8InVarKernelArgs a;
+    const hipError_t e = fp8in_varlen_front<PAGED>(c, st, a);
+    if (e != hipSuccess) return e;
     const size_t smem = 2 * 2 * 128 * 128;
-    const unsigned grid = (unsigned)(c.batch * c.heads_q * nqt);
+    const unsigned grid = (unsigned)(c.batch * c.heads_q * a.nqt);
     ProfScope ps(K_FP8IN_FWD_VARLEN, st);
     auto launch = [&](auto kern) -> hipError_t {
         hipError_t e2 = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
@@ -644,6 +665,318 @@ template <bool PAGED> static hipError_t launch_fp8_inputs_varlen_t(const Fp8InVa
 
 hipError_t launch_fp8_inputs_varlen(const Fp8InVarArgs& c, hipStream_t st) {
     return c.block_table ? launch_fp8_inputs_varlen_t<true>(c, st) : launch_fp8_inputs_varlen_t<false>(c, st);
+}
+
+// ---- A sliding window, a softcap and sinks (fa_fp8_forward_mod, fa_fp8_forward_varlen_mod) -------------
+// One kernel of its own for the padded (MODE 0), the packed (1) and the paged (2) form, so that a call without the three
+// features launches fwd_fp8in_kernel / fwd_fp8in_varlen_kernel as before.  The three features are wave-uniform run-time
+// switches.  The transposers are the ones above and still transpose every key of a sequence.
+//   window   row i of a sequence sits at pos = i + len_k - len_q and sees key j iff pos - wl <= j <= pos + wr and 0 <= j < len_k
+//            (kWinNone: unbounded; causal is wr = 0).  The workgroup's tile loop, with its double-buffered staging, runs over
+//            the 128-key tiles [t_lo, t_hi) that some row of its 256 sees: O(N w) work.  A wave computes on the tiles
+//            [tw_lo, tw_hi) some row of its 32 sees and only takes part in the barriers of the others.  The mask compares
+//            with an upper and a lower threshold, each only on a tile that edge crosses.
+//   softcap  s~ = C tanh(s / C) with s = softmax_scale q_descale k_descale (q8 . k8), BEFORE the mask, as mod_softcap has it:
+//            in log2 units s~ = cap2 (1 - 2 r), r = 1 / (2^(ck raw) + 1), ck = f (2 / C), cap2 = C log2(e), f the workgroup's
+//            score factor.  The capped score replaces the raw product in the accumulator and the factor of what follows is 1.
+//   sinks    one float32 per QUERY head in natural-log units, an extra softmax column with a zero value, never capped or
+//            masked.  It enters in the epilogue after the half-wave sum of l, by ex_sink_norm (finite at +-1e4).  A row
+//            without a visible key gives o = 0, lse = sink; a head at -inf takes the epilogue of a call without sinks.
+struct Fp8InModKernelArgs {
+    Fp8InKernelArgs pad;                   // MODE 0
+    Fp8InVarKernelArgs var;                // MODE 1, 2
+    int wl, wr;                            // kWinNone: unbounded
+    int rev;                               // causal: the long query tiles first
+    float cap_k, cap2;                     // 2 / softcap, softcap * log2(e); cap2 == 0: no softcap
+    const float* sinks;                    // (H_q,) or null
+};
+
+template <typename Tag, int MODE>
+__global__ __launch_bounds__(512, 2) void fwd_fp8in_mod_kernel(const Fp8InModKernelArgs am) {
+    constexpr bool VAR = MODE != 0, PAGED = MODE == 2;
+    constexpr int D = 128, BM = 256, BN = 128, KB = 4, NM = D / 32, NDV = D / 32;
+    constexpr int TILE = BN * D;                         // bytes of a K tile and of a V^T tile alike
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // [2 buffers][K8 tile | V8^T tile]
+    typedef int i32x8_t __attribute__((ext_vector_type(8)));
+
+    // ---- the sequence and its tensors: fwd_fp8in_kernel's (MODE 0) or fwd_fp8in_varlen_kernel's prologue
+    const int nqt = VAR ? am.var.nqt : am.pad.nqt, hq = VAR ? am.var.hq : am.pad.hq, group = VAR ? am.var.group : am.pad.group;
+    const int L = xcd_remap(blockIdx.x, gridDim.x);
+    const int bh = L / nqt;                              // b * H_q + head
+    int qt = L - bh * nqt;
+    if (am.rev) qt = nqt - 1 - qt;
+    const int b = bh / hq, hd = bh - b * hq, hk = hd / group;
+    const int q0 = qt * BM;
+    int nq, nk, qs = 0, ks = 0;
+    if constexpr (VAR) {
+        seq_span(am.var.cu_q, b, am.var.total_q, am.var.max_q, qs, nq);
+        if (PAGED) nk = paged_len(am.var.cu_k, b, am.var.max_k);
+        else seq_span(am.var.cu_k, b, am.var.total_k, am.var.max_k, ks, nk);
+        if (q0 >= nq) return;                            // the padded grid: no row of this tile belongs to the sequence
+    } else {
+        nq = am.pad.nq; nk = am.pad.nk;
+    }
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const int qrow = q0 + 32 * w + r;
+    const int shift = nk - nq;                           // row i sits at key position i + shift
+    const int q_ts = VAR ? am.var.q_ts : am.pad.q_ts, k_ts = VAR ? am.var.k_ts : am.pad.k_ts, o_ts = VAR ? am.var.o_ts : am.pad.o_ts;
+    const uint8_t* qbase;
+    const uint8_t* kh;                                   // the K rows of this K/V head (PAGED: of page 0)
+    const uint8_t* vbase;
+    uint16_t* obase;
+    const float *qds, *kds, *vds;
+    int qds_bs, kds_bs, vds_bs, ntile_b;
+    if constexpr (VAR) {
+        qbase = am.var.q + (size_t)qs * q_ts + (size_t)hd * am.var.q_hs;
+        kh = am.var.k + (size_t)hk * am.var.k_hs + (PAGED ? (size_t)0 : (size_t)ks * k_ts);
+        ntile_b = (nk + BN - 1) / BN;
+        vbase = am.var.v8t + ((size_t)hk * am.var.nt_head + fp8in_tile_start<PAGED>(b, ks, am.var.nt_seq)) * TILE;
+        obase = am.var.o + (size_t)qs * o_ts + (size_t)hd * am.var.o_hs;
+        qds = am.var.qds; kds = am.var.kds; vds = am.var.vds;
+        qds_bs = am.var.qds_bs; kds_bs = am.var.kds_bs; vds_bs = am.var.vds_bs;
+    } else {
+        qbase = am.pad.q + (size_t)b * am.pad.q_bs + (size_t)hd * am.pad.q_hs;
+        kh = am.pad.k + (size_t)b * am.pad.k_bs + (size_t)hk * am.pad.k_hs;
+        ntile_b = am.pad.ntile;
+        vbase = am.pad.v8t + (size_t)(b * am.pad.hkv + hk) * am.pad.ntile * TILE;
+        obase = am.pad.o + (size_t)b * am.pad.o_bs + (size_t)hd * am.pad.o_hs;
+        qds = am.pad.qds; kds = am.pad.kds; vds = am.pad.vds;
+        qds_bs = am.pad.qds_bs; kds_bs = am.pad.kds_bs; vds_bs = am.pad.vds_bs;
+    }
+
+    // q rows >= nq and k rows >= nk lie outside the descriptors: they read as zeros, whatever the memory behind them holds
+    const buf_rsrc_t q_rs = make_rsrc(qbase, (unsigned)(nq - 1) * (unsigned)q_ts + D);
+    u32x4 qf[NM];
+#pragma unroll
+    for (int m = 0; m < NM; ++m) qf[m] = __builtin_amdgcn_raw_buffer_load_b128(q_rs, qrow * q_ts + 32 * m + 16 * h, 0, 0);
+    const float qd = qds ? qds[(size_t)b * qds_bs + hk] : 1.f;
+    const float kd = kds ? kds[(size_t)b * kds_bs + hk] : 1.f;
+    const float vd = vds ? vds[(size_t)b * vds_bs + hk] : 1.f;
+    const float f = ((VAR ? am.var.c_log2 : am.pad.c_log2) * qd) * kd;   // the one score factor of this workgroup, > 0
+    const bool capped = am.cap2 != 0.f;
+    const float ck = f * am.cap_k, cap2 = am.cap2;
+    const float fe = capped ? 1.f : f;                   // the factor of what the accumulators hold after the cap
+
+    // the 128-key tiles [t_lo, t_hi) some row of the workgroup sees, from its first row's lower and its last row's upper bound
+    const int wl = am.wl, wr = am.wr;
+    const int kfirst = max(0, q0 + shift - wl), kend = max(0, min(nk, q0 + BM + shift + wr));
+    const int t_lo = kfirst / BN, t_hi = kend > kfirst ? (kend + BN - 1) / BN : t_lo;
+    [[maybe_unused]] const rsrc_s_t k_rs = make_rsrc_s(kh, nk > 0 ? (unsigned)(nk - 1) * (unsigned)k_ts + D : 0u);
+    const rsrc_s_t v_rs = make_rsrc_s(vbase, (unsigned)ntile_b * TILE);
+    const int kstride = k_ts >> 1;                       // the STRIDED helpers count 2-byte elements
+    const int voff_k = dma_lane_voff<64, true>(lane, w, 64, kstride);   // 128-byte rows: the geometry of a 16-bit d = 64 tile
+    const int voff_v = dma_lane_voff<64>(lane, w);
+    [[maybe_unused]] const int* trow = PAGED ? am.var.pg.table + (size_t)b * am.var.pg.max_blocks : nullptr;
+    [[maybe_unused]] const int pg_last = PAGED ? pg_slot(am.var.pg, max(nk - 1, 0)) : 0;   // no entry past ceil(nk / ps) is read
+    auto stage = [&](int buf, int t) {
+        char* b_ = smem + buf * 2 * TILE;
+        if constexpr (PAGED) {
+            fp8in_stage_k_paged(am.var.pg, trow, pg_last, kh, b_, t * BN, nk, voff_k, w, k_ts);
+        } else {
+            dma_stage_tile<64, BN, 8, true>(k_rs, b_, t * BN, voff_k, w, 64, 0, kstride);
+        }
+        dma_stage_tile<64, BN, 8>(v_rs, b_ + TILE, t * BN, voff_v, w);   // V^T tile t = rows 128 t .. of the [tile][d row] matrix
+    };
+
+    f32x16 oacc[NDV];
+#pragma unroll
+    for (int t = 0; t < NDV; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) oacc[t][i] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;                // running max in log2 units of the (capped) scaled score
+
+    if (t_hi > t_lo) {
+        stage(0, t_lo);
+        dma_wait_all();
+        __syncthreads();
+    }
+    // the tiles some row of the wave sees: its first row's lower bound, its last row's upper bound
+    const int pos_w = q0 + 32 * w + shift;               // the position of the wave's first row
+    const int last_w = pos_w + 31 + wr;
+    const int tw_lo = max(t_lo, max(0, pos_w - wl) / BN), tw_hi = last_w < 0 ? t_lo : min(t_hi, last_w / BN + 1);
+    const int lim_hi = min(qrow + shift + wr, nk - 1), lim_lo = qrow + shift - wl;   // this row sees keys [lim_lo, lim_hi]
+
+    for (int t = t_lo; t < t_hi; ++t) {
+        const int k0 = t * BN, cur = (t - t_lo) & 1;
+        if (t + 1 < t_hi) stage(cur ^ 1, t + 1);
+        if (t >= tw_lo && t < tw_hi) {                   // (wave-uniform)
+        const char* Kt = smem + cur * 2 * TILE;
+        const char* Vt = Kt + TILE;
+        f32x16 sacc[KB];
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) sacc[kb][i] = 0.f;
+#pragma unroll
+            for (int M = 0; M < NM / 2; ++M) {
+                const u32x4 a0 = *reinterpret_cast<const u32x4*>(Kt + TileSwz<64>::off(32 * kb + r, 4 * M + h));
+                const u32x4 a1 = *reinterpret_cast<const u32x4*>(Kt + TileSwz<64>::off(32 * kb + r, 4 * M + 2 + h));
+                const i32x8_t ka = {(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], (int)a1[0], (int)a1[1], (int)a1[2], (int)a1[3]};
+                const u32x4 b0_ = qf[2 * M], b1_ = qf[2 * M + 1];
+                const i32x8_t qb = {(int)b0_[0], (int)b0_[1], (int)b0_[2], (int)b0_[3], (int)b1_[0], (int)b1_[1], (int)b1_[2], (int)b1_[3]};
+                sacc[kb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ka, qb, sacc[kb], 0, 0, 0, 127, 0, 127);
+            }
+        }
+        // the softcap first (before the mask), in log2 units: one exp2 and one rcp an element
+        if (capped) {
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float rr = __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(sacc[kb][i] * ck) + 1.f);
+                    sacc[kb][i] = fmaf(rr, -2.f * cap2, cap2);
+                }
+        }
+        // the mask, only where a band edge or the end of the keys crosses this tile for some row of the wave
+        const bool need_hi = (k0 + BN - 1 > pos_w + wr) || (k0 + BN > nk);
+        const bool need_lo = k0 < pos_w + 31 - wl;
+        float mx = -INFINITY;
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) {
+            if (need_hi) {
+                const int thr = lim_hi - (k0 + 32 * kb + 4 * h);
+#pragma unroll
+                for (int i = 0; i < 16; ++i)
+                    if ((i & 3) + 8 * (i >> 2) > thr) sacc[kb][i] = -INFINITY;
+            }
+            if (need_lo) {
+                const int thr = lim_lo - (k0 + 32 * kb + 4 * h);
+#pragma unroll
+                for (int i = 0; i < 16; ++i)
+                    if ((i & 3) + 8 * (i >> 2) < thr) sacc[kb][i] = -INFINITY;
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) mx = fmaxf(mx, sacc[kb][i]);
+        }
+        mx = mx * fe;
+        mx = fmaxf(mx, wave_half_swap(mx));
+        const float m_new = fmaxf(m_run, mx);
+        float m_use;
+        if (__any(m_new - m_run > 8.0f) != 0) {   // lazy rescale (fwd_fp8in_kernel); a row's first visible key: inf > 8
+            m_use = m_new;
+            const float alpha = __builtin_amdgcn_exp2f(m_run - ((m_new == -INFINITY) ? 0.f : m_new));
+            m_run = m_new;
+            l_run *= alpha;
+#pragma unroll
+            for (int t2 = 0; t2 < NDV; ++t2)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) oacc[t2][i] *= alpha;
+        } else {
+            m_use = m_run;
+        }
+        if (m_use == -INFINITY) m_use = 0.f;      // a row without a visible key so far: p = exp2(-inf) = 0, not exp2(-inf + inf)
+        float rs = 0.f;
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            i32x8_t pb;
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {
+                const int kb = 2 * g + kk;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float p = __builtin_amdgcn_exp2f(fmaf(sacc[kb][i], fe, -m_use));   // (-inf stays -inf: fe > 0)
+                    sacc[kb][i] = p;
+                    rs += p;
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    int wd = 0;
+                    wd = __builtin_amdgcn_cvt_pk_fp8_f32(sacc[kb][4 * j + 0], sacc[kb][4 * j + 1], wd, false);
+                    wd = __builtin_amdgcn_cvt_pk_fp8_f32(sacc[kb][4 * j + 2], sacc[kb][4 * j + 3], wd, true);
+                    pb[4 * kk + j] = wd;
+                }
+            }
+#pragma unroll
+            for (int dvb = 0; dvb < NDV; ++dvb) {
+                const u32x4 a0 = *reinterpret_cast<const u32x4*>(Vt + TileSwz<64>::off(32 * dvb + r, 4 * g + h));
+                const u32x4 a1 = *reinterpret_cast<const u32x4*>(Vt + TileSwz<64>::off(32 * dvb + r, 4 * g + 2 + h));
+                const i32x8_t va = {(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], (int)a1[0], (int)a1[1], (int)a1[2], (int)a1[3]};
+                oacc[dvb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(va, pb, oacc[dvb], 0, 0, 0, 127, 0, 127);
+            }
+        }
+        l_run += rs;
+        }
+        dma_wait_all();
+        __syncthreads();
+    }
+
+    // every wave is past the last barrier: the K / V buffers are dead (fwd_fp8in_kernel's epilogue).  The sink joins here.
+    const float l_tot = l_run + wave_half_swap(l_run);
+    const float snk = am.sinks ? am.sinks[hd] : -INFINITY;   // (workgroup-uniform)
+    bool dead;
+    float inv, lse_v;
+    if (snk != -INFINITY) {
+        float iv;
+        ex_sink_norm(m_run * 0.6931471805599453f, l_tot, snk, iv, lse_v);
+        dead = false;                                    // (no visible key: iv = 0, lse = sink)
+        inv = vd * iv;
+    } else {
+        dead = l_tot == 0.f;                             // no visible key: o = 0, lse = -inf (a NaN l is not dead: it propagates)
+        inv = vd * (1.f / l_tot);                        // v_descale once, with 1 / l
+        lse_v = dead ? -INFINITY : (m_run + log2f(l_tot)) * 0.6931471805599453f;
+    }
+    u32x2 vals[NDV * 4];
+#pragma unroll
+    for (int dvb = 0; dvb < NDV; ++dvb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            float y[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) y[j] = dead ? 0.f : oacc[dvb][4 * g + j] * inv;
+            vals[4 * dvb + g][0] = pack2_rn<Tag>(y[0], y[1]);
+            vals[4 * dvb + g][1] = pack2_rn<Tag>(y[2], y[3]);
+        }
+    store_rows_via_lds<D, true>(smem + w * 32 * D * 2, vals, obase, q0 + 32 * w, nq, lane, D, -1, o_ts);
+    if (qrow < nq && h == 0) {
+        if constexpr (VAR) am.var.lse[(size_t)hd * am.var.total_q + qs + qrow] = lse_v;
+        else am.pad.lse[(size_t)bh * nq + qrow] = lse_v;
+    }
+}
+
+static void fp8in_mod_fill(Fp8InModKernelArgs& a, const Fp8Mod& m, bool causal) {
+    a.wl = m.window_left >= 0 ? (int)std::min<int64_t>(m.window_left, kWinNone) : kWinNone;
+    a.wr = causal ? 0 : (m.window_right >= 0 ? (int)std::min<int64_t>(m.window_right, kWinNone) : kWinNone);
+    a.rev = causal;
+    a.cap_k = m.softcap > 0.0 ? (float)(2.0 / m.softcap) : 0.f;
+    a.cap2 = m.softcap > 0.0 ? (float)(m.softcap * 1.4426950408889634) : 0.f;
+    a.sinks = m.sinks;
+}
+
+template <int MODE> static hipError_t launch_fp8in_mod(const Fp8InModKernelArgs& a, int dtype, unsigned grid, hipStream_t st) {
+    const size_t smem = 2 * 2 * 128 * 128;
+    auto launch = [&](auto kern) -> hipError_t {
+        hipError_t e2 = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
+        if (e2 != hipSuccess) return e2;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, st, a);
+        return hipGetLastError();
+    };
+    return dtype == 2 ? launch(fwd_fp8in_mod_kernel<bf16_tag, MODE>) : launch(fwd_fp8in_mod_kernel<f16_tag, MODE>);
+}
+
+hipError_t launch_fp8_inputs_mod(const Fp8InArgs& c, const Fp8Mod& m, hipStream_t st) {
+    if (!m.any()) return launch_fp8_inputs(c, st);       // the parent call, launch for launch
+    const hipError_t e = fp8in_launch_vt(c, st);
+    if (e != hipSuccess) return e;
+    Fp8InModKernelArgs a{};
+    a.pad = fp8in_kernel_args(c);
+    fp8in_mod_fill(a, m, c.causal != 0);
+    route_hit(ROUTE_FP8IN_FWD_MOD);
+    ProfScope ps(K_FP8IN_FWD_MOD, st);
+    return launch_fp8in_mod<0>(a, c.dtype, (unsigned)(c.batch * c.heads_q * a.pad.nqt), st);
+}
+
+hipError_t launch_fp8_inputs_varlen_mod(const Fp8InVarArgs& c, const Fp8Mod& m, hipStream_t st) {
+    if (!m.any()) return launch_fp8_inputs_varlen(c, st);
+    if (c.max_q == 0) return hipSuccess;                 // no sequence has a query: nothing is written
+    Fp8InModKernelArgs a{};
+    const hipError_t e = c.block_table ? fp8in_varlen_front<true>(c, st, a.var) : fp8in_varlen_front<false>(c, st, a.var);
+    if (e != hipSuccess) return e;
+    fp8in_mod_fill(a, m, c.causal != 0);
+    route_hit(ROUTE_FP8IN_FWD_VARLEN_MOD);
+    ProfScope ps(K_FP8IN_FWD_VARLEN_MOD, st);
+    const unsigned grid = (unsigned)(c.batch * c.heads_q * a.var.nqt);
+    return c.block_table ? launch_fp8in_mod<2>(a, c.dtype, grid, st) : launch_fp8in_mod<1>(a, c.dtype, grid, st);
 }
 
 }  // namespace fa

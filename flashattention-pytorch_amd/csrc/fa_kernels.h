@@ -43,7 +43,8 @@ struct BwdArgs {
 // roofline figure; off by default, costs nothing when off).
 enum KernelId { K_FWD_F32 = 0, K_BWD_DELTA, K_BWD_DKDV_F32, K_BWD_DQ_F32, K_FWD_MFMA, K_BWD_MFMA, K_BWD_DQ_CVT, K_BWD_DQ_MFMA,
                 K_FP8_QUANT, K_FWD_FP8, K_EX_FWD, K_EX_BWD, K_KV_GROUP_SUM, K_FP8IN_VT, K_FP8IN_FWD, K_FP8IN_VT_VARLEN,
-                K_FP8IN_FWD_VARLEN, K_IDX_PACK, K_IDX_LOGITS, K_IDX_TOPK, K_FP8KV_SPLIT, K_FP8Q_AMAX, K_FP8Q_QUANT, K_FP8Q_FUSED, K_COUNT };
+                K_FP8IN_FWD_VARLEN, K_IDX_PACK, K_IDX_LOGITS, K_IDX_TOPK, K_FP8KV_SPLIT, K_FP8Q_AMAX, K_FP8Q_QUANT, K_FP8Q_FUSED,
+                K_FP8IN_FWD_MOD, K_FP8IN_FWD_VARLEN_MOD, K_FP8KV_SPLIT_MOD, K_COUNT };
 void prof_begin(int id, hipStream_t st);
 void prof_end(int id, hipStream_t st);
 struct ProfScope {
@@ -65,8 +66,10 @@ int set_option(const char* name, int value);   // returns 0, or -1 for an unknow
 
 // Which form a launcher took, counted since the library was loaded and read back through fa_route_count(): a test asks the
 // library, it does not guess from timing.  "dkdv_stream": the dS-storing dK/dV stream kernel, "dkdv_lean": its lean form;
-// "fp8_quant_fused", "fp8_quant_two_pass", "fp8_quant_static": the routes of the fp8 quantiser (fa_fp8_quantize.hip).
-enum RouteId { ROUTE_DKDV_STREAM = 0, ROUTE_DKDV_LEAN, ROUTE_FP8Q_FUSED, ROUTE_FP8Q_TWO_PASS, ROUTE_FP8Q_STATIC, ROUTE_COUNT };
+// "fp8_quant_fused", "fp8_quant_two_pass", "fp8_quant_static": the routes of the fp8 quantiser (fa_fp8_quantize.hip);
+// "fp8in_fwd_mod", "fp8in_fwd_varlen_mod", "fp8kv_split_mod": the featured kernels of the fp8 calls (window, softcap, sinks).
+enum RouteId { ROUTE_DKDV_STREAM = 0, ROUTE_DKDV_LEAN, ROUTE_FP8Q_FUSED, ROUTE_FP8Q_TWO_PASS, ROUTE_FP8Q_STATIC, ROUTE_FP8IN_FWD_MOD,
+               ROUTE_FP8IN_FWD_VARLEN_MOD, ROUTE_FP8KV_SPLIT_MOD, ROUTE_COUNT };
 void route_hit(int id);
 
 // exact-f32 kernels (fa_generic.hip): any dtype, d <= 256
@@ -453,6 +456,19 @@ struct Fp8InArgs {
 size_t fp8in_workspace_bytes(int64_t units_kv, int64_t nk);
 hipError_t launch_fp8_inputs(const Fp8InArgs& a, hipStream_t st);
 
+// What the _mod entry points of the three fp8 calls add (fa_fp8_forward_mod, fa_fp8_forward_varlen_mod,
+// fa_fp8_forward_kvcache_mod): a sliding window (-1: unbounded; causal sets the right bound to 0), a softcap (0: off) and one
+// sink logit per query head (device float32, natural-log units; null: none).  A call whose Fp8Mod is not any() is its parent
+// call, launch for launch; any other takes the featured kernels (fwd_fp8in_mod_kernel, fp8kv_split_mod_kernel).
+struct Fp8Mod {
+    int64_t window_left = -1, window_right = -1;
+    double softcap = 0.0;
+    const float* sinks = nullptr;
+    int64_t sink_heads = 0;
+    bool any() const { return window_left >= 0 || window_right >= 0 || softcap > 0.0 || sinks != nullptr; }
+};
+hipError_t launch_fp8_inputs_mod(const Fp8InArgs& a, const Fp8Mod& m, hipStream_t st);
+
 // The packed and the paged form (fa_fp8_forward_varlen): q (total_q, heads_q, 128) and o, lse as the varlen calls lay them out;
 // k, v (total_k, heads_kv, 128), or with block_table the pools (num_blocks, page_size, heads_kv, 128).  Strides in bytes.
 struct Fp8InVarArgs {
@@ -474,6 +490,7 @@ struct Fp8InVarArgs {
 // from batch, heads_kv, total_k (packed: page_size == 0) or max_k, max_blocks, page_size (paged) alone
 size_t fp8in_varlen_workspace_bytes(const Fp8InVarArgs& a);
 hipError_t launch_fp8_inputs_varlen(const Fp8InVarArgs& a, hipStream_t st);
+hipError_t launch_fp8_inputs_varlen_mod(const Fp8InVarArgs& a, const Fp8Mod& m, hipStream_t st);
 
 // fp8 KV-cache decoding (fa_fp8_decode.hip; fa_fp8_forward_kvcache): e4m3 q (batch, seqlen_q, heads_q, 128) over an e4m3 cache
 // (cache_batch, cache_len, heads_kv, 128), or with block_table the pools (num_blocks, page_size, heads_kv, 128).  Strides in bytes;
@@ -496,8 +513,17 @@ struct Fp8KvArgs {
 };
 int fp8kv_num_splits(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len);
 hipError_t launch_fp8_kvcache(const Fp8KvArgs& a, hipStream_t st);
+// The featured call.  The keys a window of `window_left` lets the rows of one tile see are at most window_left + max(window_right,
+// 0) + seqlen_q, whatever the lengths: fp8kv_split_len is what the split rule takes for cache_len then (the host cannot see the
+// lengths, and a short window over a long capacity would be cut into splits of under one tile).  With sinks num_splits >= 2:
+// the sink joins in the combine, which such a call always runs.
+int64_t fp8kv_split_len(int64_t cache_len, int64_t seqlen_q, int causal, const Fp8Mod& m);
+hipError_t launch_fp8_kvcache_mod(const Fp8KvArgs& a, const Fp8Mod& m, hipStream_t st);
 // kv_combine_kernel<Tag, false> (fa_decode.hip) over partials in kv_workspace_bytes' layout, for a caller outside that file
 hipError_t launch_kv_combine(void* o, float* lse, float* po, float* plse, int64_t batch, int64_t heads_q, int64_t seqlen_q, int64_t d,
                              int dtype, int splits, hipStream_t st);
+// kv_combine_kernel<Tag, true>: the same with the sink column of head h, sinks[h % sink_heads]
+hipError_t launch_kv_combine_sink(void* o, float* lse, float* po, float* plse, int64_t batch, int64_t heads_q, int64_t seqlen_q, int64_t d,
+                                  int dtype, int splits, const float* sinks, int sink_heads, hipStream_t st);
 
 }  // namespace fa

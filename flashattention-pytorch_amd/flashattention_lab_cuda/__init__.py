@@ -59,6 +59,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_fp8_forward", "fa_fp8_forward_workspace_bytes",
     "fa_fp8_forward_varlen", "fa_fp8_forward_varlen_workspace_bytes",
     "fa_fp8_forward_kvcache", "fa_fp8_forward_kvcache_workspace_bytes",
+    "fa_fp8_forward_mod", "fa_fp8_forward_varlen_mod", "fa_fp8_forward_kvcache_mod", "fa_fp8_forward_kvcache_workspace_bytes_mod",
     "fa_fp8_quantize", "fa_fp8_quantize_workspace_bytes",
 )
 
@@ -223,6 +224,11 @@ _sig("fa_fp8_forward_kvcache", _fields(
     "i:q_batch_stride,q_token_stride,k_batch_stride,k_token_stride,v_batch_stride,v_token_stride,block_table_row_stride,num_blocks,"
     "page_block_size,q_descale_batch_stride,k_descale_batch_stride,v_descale_batch_stride c:causal d:softmax_scale i:num_splits") + _WS)
 _sig("fa_fp8_forward_kvcache_workspace_bytes", _KVWS, _SIZE)
+# a window, a softcap and sinks on the three fp8 calls: the parent's arguments, then one more group
+_FP8MOD = _WINDOW + _fields("d:softcap") + _SINK
+for _name in ("fa_fp8_forward", "fa_fp8_forward_varlen", "fa_fp8_forward_kvcache"):
+    _sig(_name + "_mod", _SIGNATURES[_name][1] + _FP8MOD)
+_sig("fa_fp8_forward_kvcache_workspace_bytes_mod", _KVWS + _fields("c:causal") + _WINDOW + _fields("c:with_sinks"), _SIZE)
 _sig("fa_fp8_quantize", _fields("p:x,out,descale,descale_out,cu_seqlens") + _ROTARY + _fields(
     "i:seqlen_offset p:seqlen_offsets i:batch,heads,seqlen,d,heads_per_scale,total,max_seqlen c:dtype "
     "i:x_batch_stride,x_head_stride,x_token_stride,out_batch_stride,out_head_stride,out_token_stride,descale_batch_stride "
@@ -285,6 +291,9 @@ _family("fa_indexer_topk", [])
 _family("fa_fp8_forward", [])
 _family("fa_fp8_forward_varlen", [])
 _family("fa_fp8_forward_kvcache", [])
+# a window, a softcap and sinks: each entry point takes its parent's arguments plus one group and is called with exactly its own
+for _name in ("fa_fp8_forward_mod", "fa_fp8_forward_varlen_mod", "fa_fp8_forward_kvcache_mod"):
+    _family(_name, [])
 _family("fa_fp8_quantize", [])
 _family("fa_ex_forward_kvcache_qv", ["fa_ex_forward_kvcache" + _suffix for _suffix in ("", "_paged", "_rotary", "_fp8", "_sink", "_varlen")])
 
@@ -2211,11 +2220,43 @@ def _fp8_view(who, name, t, layout):
     return b, h, n, st
 
 
-def fp8_forward(q, k, v, causal, softmax_scale, q_descale=None, k_descale=None, v_descale=None, out_dtype=torch.bfloat16, layout="bhnd"):
+def _fp8_mod(who, q, hq, window, softcap, sinks):
+    """(the entry point's suffix, its trailing (window_left, window_right, softcap, sinks, sink_heads), the tensor to keep alive) of
+    a window, a softcap and sinks on an fp8 call with hq query heads; ("", (), None) when none of the three is given: such a call
+    goes through its parent entry point with the parent's arguments"""
+    try:
+        wl, wr = window
+        if isinstance(wl, bool) or isinstance(wr, bool):
+            raise TypeError
+        wl, wr = operator.index(wl), operator.index(wr)
+    except (TypeError, ValueError):
+        raise RuntimeError(f"{who}: window must be a pair (left, right) of ints, got {window!r}") from None
+    if wl < -1 or wr < -1:
+        raise RuntimeError(f"{who}: window ({wl}, {wr}): each bound must be >= 0, or -1 for unbounded")
+    cap = float(softcap)
+    if not (math.isfinite(cap) and cap >= 0.0):
+        raise RuntimeError(f"{who}: softcap must be a finite number >= 0 (got {cap})")
+    if sinks is not None:
+        if not isinstance(sinks, torch.Tensor) or sinks.dtype != torch.float32:
+            dt = sinks.dtype if isinstance(sinks, torch.Tensor) else type(sinks).__name__
+            raise RuntimeError(f"{who}: sinks of dtype {dt} is not supported (a float32 tensor expected; pass a 16-bit parameter as p.float())")
+        if tuple(sinks.shape) != (hq,):
+            raise RuntimeError(f"{who}: sinks must be (H_q,) = ({hq},), one per query head, got {tuple(sinks.shape)}")
+        if sinks.device != q.device:
+            raise RuntimeError(f"{who}: sinks must be on q's device ({q.device}), got {sinks.device}")
+        sinks = sinks.contiguous()
+    featured = wl >= 0 or wr >= 0 or cap > 0.0 or sinks is not None
+    return ("_mod", (wl, wr, cap, _ptr(sinks), hq if sinks is not None else 0), sinks) if featured else ("", (), None)
+
+
+def fp8_forward(q, k, v, causal, softmax_scale, q_descale=None, k_descale=None, v_descale=None, out_dtype=torch.bfloat16, layout="bhnd",
+                *, window=(-1, -1), softcap=0.0, sinks=None):
     """(o, lse) of FlashAttention-3's fp8 call (fa_fp8_forward): q (B, H_q, Nq, 128), k and v (B, H_kv, Nk, 128) in torch.float8_e4m3fn
     (layout "bnhd": (B, N, H, 128)), used at their own strides, never copied; q_descale, k_descale, v_descale float32 (B, H_kv) or
     (H_kv,) on q's device, None = 1.  o comes back contiguous in `layout` and out_dtype (bfloat16 / float16), lse float32
-    (B, H_q, Nq).  The V^T workspace is the shim's persistent one.  Nothing is recorded by autograd."""
+    (B, H_q, Nq).  The V^T workspace is the shim's persistent one.  Nothing is recorded by autograd.
+    window (left, right; -1 = unbounded), softcap (0 = off) and sinks (float32 (H_q,) on q's device) are fa_fp8_forward_mod's; a call
+    with none of them goes through fa_fp8_forward."""
     who = "fp8_forward"
     if layout not in FP8_LAYOUTS:
         raise ValueError(f"{who}: layout must be one of {FP8_LAYOUTS}, got {layout!r}")
@@ -2246,16 +2287,17 @@ def fp8_forward(q, k, v, causal, softmax_scale, q_descale=None, k_descale=None, 
     qdp, qds, keep_q = _kv_descale(who, "q_descale", q_descale, q, b, hkv)
     kdp, kds, keep_k = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
     vdp, vds, keep_v = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
+    mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks)
     with torch.cuda.device(q.device):
         o = torch.empty((b, hq, nq, 128) if layout == "bhnd" else (b, nq, hq, 128), dtype=out_dtype, device=q.device)
         lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)
         _b, _h, _n, so = _fp8_view(who, "o", o, layout)
         need = int(_lib.fa_fp8_forward_workspace_bytes(b, hkv, nk, 128))
         ws = _workspace(q.device, need)
-        _call("fa_fp8_forward", (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp, b, hq, hkv, nq, nk,
-                                 128, _DTYPE_CODE[out_dtype], *sq, *sk, *sv, *so, qds, kds, vds, int(bool(causal)), scale, ws.data_ptr(),
-                                 ws.numel(), _stream_ptr(q.device)))
-    del keep_q, keep_k, keep_v
+        _call("fa_fp8_forward" + mod, (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp, b, hq, hkv, nq,
+                                       nk, 128, _DTYPE_CODE[out_dtype], *sq, *sk, *sv, *so, qds, kds, vds, int(bool(causal)), scale,
+                                       ws.data_ptr(), ws.numel(), _stream_ptr(q.device), *tail))
+    del keep_q, keep_k, keep_v, keep_s
     return o, lse
 
 
@@ -2274,12 +2316,15 @@ def _fp8_rows(who, name, t, heads):
 
 
 def fp8_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, q_descale=None,
-                       k_descale=None, v_descale=None, out_dtype=torch.bfloat16, block_table=None):
+                       k_descale=None, v_descale=None, out_dtype=torch.bfloat16, block_table=None, *, window=(-1, -1), softcap=0.0,
+                       sinks=None):
     """(o, lse) of the packed / paged fp8 call (fa_fp8_forward_varlen): q (total_q, H_q, 128) in torch.float8_e4m3fn at its own token
     and head strides; k and v (total_k, H_kv, 128) e4m3, or with block_table (int32 (B, max_blocks_per_seq)) the pools
     (num_blocks, ps, H_kv, 128) at their own page and token strides; nothing is copied.  cu_seqlens_* int32 (B + 1,) on the device;
     descales float32 (B, H_kv) or (H_kv,), None = 1.  o (total_q, H_q, 128) in out_dtype, lse float32 (H_q, total_q); rows no
-    sequence owns hold unspecified values.  Nothing is read on the host; the V^T workspace is the shim's persistent one."""
+    sequence owns hold unspecified values.  Nothing is read on the host; the V^T workspace is the shim's persistent one.
+    window, softcap and sinks (float32 (H_q,)) are fa_fp8_forward_varlen_mod's; a call with none of them goes through
+    fa_fp8_forward_varlen."""
     who = "fp8_varlen_forward"
     for name, t in (("q", q), ("k", k), ("v", v)):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float8_e4m3fn:
@@ -2346,6 +2391,7 @@ def fp8_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_se
     qdp, qds, keep_q = _kv_descale(who, "q_descale", q_descale, q, b, hkv)
     kdp, kds, keep_k = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
     vdp, vds, keep_v = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
+    mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks)
     with torch.cuda.device(q.device):
         o = torch.empty((total_q, hq, 128), dtype=out_dtype, device=q.device)
         lse = torch.empty((hq, total_q), dtype=torch.float32, device=q.device)
@@ -2353,22 +2399,24 @@ def fp8_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_se
             return o, lse
         need = int(_lib.fa_fp8_forward_varlen_workspace_bytes(b, hkv, total_k, mk, mblk, ps, 128))
         ws = _workspace(q.device, need)
-        _call("fa_fp8_forward_varlen", (
+        _call("fa_fp8_forward_varlen" + mod, (
             q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp, cu_q.data_ptr(), cu_k.data_ptr(),
             block_table.data_ptr() if paged else 0, b, hq, hkv, total_q, total_k, mq, mk, 128, _DTYPE_CODE[out_dtype], qts, qhs, kts, khs,
-            vts, vhs, *pages, qds, kds, vds, int(bool(causal)), scale, ws.data_ptr(), ws.numel(), _stream_ptr(q.device)))
-    del keep_q, keep_k, keep_v
+            vts, vhs, *pages, qds, kds, vds, int(bool(causal)), scale, ws.data_ptr(), ws.numel(), _stream_ptr(q.device), *tail))
+    del keep_q, keep_k, keep_v, keep_s
     return o, lse
 
 
 def fp8_kvcache_forward(q, k_cache, v_cache, cache_seqlens=None, block_table=None, cache_batch_idx=None, q_descale=None, k_descale=None,
-                        v_descale=None, softmax_scale=None, causal=False, num_splits=0, out_dtype=torch.bfloat16):
+                        v_descale=None, softmax_scale=None, causal=False, num_splits=0, out_dtype=torch.bfloat16, *, window=(-1, -1),
+                        softcap=0.0, sinks=None):
     """(o, lse) of fp8 KV-cache decoding (fa_fp8_forward_kvcache): q (B, Nq, H_q, 128) in torch.float8_e4m3fn at its own batch and
     token strides over the e4m3 caches (B_cache, cache_len, H_kv, 128), or with block_table (int32 (B, max_blocks_per_seq)) the pools
     (num_blocks, ps, H_kv, 128), at their own batch / page and token strides; nothing is copied.  cache_seqlens int32 (B,) on the
     device, an int, or None (full); cache_batch_idx int32 (B,), contiguous form only; descales float32 (B, H_kv) or (H_kv,), None =
     1.  o (B, Nq, H_q, 128) in out_dtype, lse float32 (B, H_q, Nq).  Nothing is read on the host; the partials live in the shim's
-    persistent workspace."""
+    persistent workspace.  window, softcap and sinks (float32 (H_q,)) are fa_fp8_forward_kvcache_mod's; a call with none of them goes
+    through fa_fp8_forward_kvcache."""
     who = "fp8_kvcache_forward"
     if isinstance(q, torch.Tensor) and q.dtype in (torch.float16, torch.bfloat16):
         raise NotImplementedError(f"{who}: q of dtype {q.dtype} is not supported (torch.float8_e4m3fn expected; a 16-bit q over an e4m3 "
@@ -2454,20 +2502,25 @@ def fp8_kvcache_forward(q, k_cache, v_cache, cache_seqlens=None, block_table=Non
     qdp, qds, keep_q = _kv_descale(who, "q_descale", q_descale, q, b, hkv)
     kdp, kds, keep_k = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
     vdp, vds, keep_v = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
+    mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks)
     with torch.cuda.device(q.device):
         o = torch.empty((b, nq, hq, 128), dtype=out_dtype, device=q.device)
         lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)
         if b == 0 or nq == 0:
             return o, lse
-        need = int(_lib.fa_fp8_forward_kvcache_workspace_bytes(b, hq, hkv, nq, cap, 128, ns))
+        if mod:
+            need = int(_lib.fa_fp8_forward_kvcache_workspace_bytes_mod(b, hq, hkv, nq, cap, 128, ns, int(bool(causal)), tail[0], tail[1],
+                                                                       int(sinks is not None)))
+        else:
+            need = int(_lib.fa_fp8_forward_kvcache_workspace_bytes(b, hq, hkv, nq, cap, 128, ns))
         ws = _workspace(q.device, need)
-        _call("fa_fp8_forward_kvcache", (
+        _call("fa_fp8_forward_kvcache" + mod, (
             q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp,
             cache_seqlens.data_ptr() if cache_seqlens is not None else 0, block_table.data_ptr() if paged else 0,
             cache_batch_idx.data_ptr() if cache_batch_idx is not None else 0, b, hq, hkv, nq, cap, cbatch, 128, _DTYPE_CODE[out_dtype],
             _E4M3_CODE, _E4M3_CODE, max(q.stride(0), 0) if b > 1 else 0, tstride(q, hq),
             k_cache.stride(0) if k_cache.shape[0] > 1 else 0, tstride(k_cache, hkv),
             v_cache.stride(0) if v_cache.shape[0] > 1 else 0, tstride(v_cache, hkv), *pages, qds, kds, vds, int(bool(causal)), scale, ns,
-            ws.data_ptr() if need else 0, ws.numel() if need else 0, _stream_ptr(q.device)))
-    del keep_q, keep_k, keep_v
+            ws.data_ptr() if need else 0, ws.numel() if need else 0, _stream_ptr(q.device), *tail))
+    del keep_q, keep_k, keep_v, keep_s
     return o, lse

@@ -1227,6 +1227,65 @@ int fa_fp8_forward_kvcache(const void* q, const void* k_cache, const void* v_cac
 size_t fa_fp8_forward_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
                                               int64_t d, int64_t num_splits);
 
+/* --- A sliding window, a softcap and attention sinks on the three fp8 calls above.  Each _mod entry point takes its parent's
+ * arguments followed by (window_left, window_right, softcap, sinks, sink_heads) and, given (-1, -1, 0.0, NULL, 0), IS its parent:
+ * the same checks, the same launches of the same kernels.  Any other call launches kernels of its own (fwd_fp8in_mod_kernel,
+ * fp8kv_split_mod_kernel; routes "fp8in_fwd_mod", "fp8in_fwd_varlen_mod", "fp8kv_split_mod" of fa_route_count) after the same
+ * transposer.  The semantics are those of the 16-bit calls (fa_ex_forward_window / _scoremod / _sink, fa_ex_forward_kvcache*):
+ *   window   (window_left, window_right), each >= 0 or -1 for unbounded; causal != 0 sets the right bound to 0.  Bottom-right
+ *            aligned: row i of a sequence with len_q queries and len_k keys sits at pos = i + len_k - len_q and sees key j iff
+ *            pos - window_left <= j <= pos + window_right and 0 <= j < len_k (the decode call: len_k = the clamped cache length,
+ *            len_q = seqlen_q).  The prefill kernels walk only the 128-key tiles some row of a 256-row workgroup sees, the decode
+ *            kernel cuts [lo, hi) into its splits, lo the first 64-key tile some row of the 32-row tile sees, and reads no table
+ *            entry, K byte or V byte below lo.  The transposers of the prefill calls still transpose every key.
+ *   softcap  >= 0, 0 = off: s~ = softcap * tanh(s / softcap) with s = softmax_scale * q_descale * k_descale * (q8 . k8), applied
+ *            before the mask.
+ *   sinks    NULL, or sink_heads == heads_q float32 on the device in natural-log units, one per QUERY head, read on the device
+ *            only: an extra softmax column with a zero value (l += exp(sink - m), lse contains it), never capped, masked or
+ *            windowed.  A row without a visible key gives o = 0 and lse = sink (without sinks: -inf); a head at -inf gives the
+ *            bits of the call without sinks (prefill calls); +-1e4 stay finite.  The decode call joins the sink in the combine,
+ *            once per row, so with sinks it runs at least two splits (num_splits 1 is raised to 2).
+ * The decode call's split rule (num_splits = 0) takes min(cache_len, window_left + max(window_right, 0) + seqlen_q) for
+ * cache_len when window_left >= 0 (causal: window_right counts as 0): the host cannot see the lengths, and the capacity would cut
+ * a short window into splits of under one tile.  The result's bits depend on num_splits, the window and nothing else of the
+ * launch.  fa_fp8_forward_kvcache_workspace_bytes_mod is that call's need (with_sinks: sinks != NULL); the parents' workspace
+ * functions serve the other two.
+ * Checked beside the parent's rules, by name (FA_ERR_INVALID_ARGUMENT): the window bounds >= -1; softcap finite and >= 0;
+ * sink_heads == heads_q with sinks and 0 without, sinks 4-byte aligned. */
+int fa_fp8_forward_mod(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
+                       const float* v_descale, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_k,
+                       int64_t d, int dtype, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_token_stride,
+                       int64_t k_batch_stride, int64_t k_head_stride, int64_t k_token_stride, int64_t v_batch_stride,
+                       int64_t v_head_stride, int64_t v_token_stride, int64_t o_batch_stride, int64_t o_head_stride,
+                       int64_t o_token_stride, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
+                       int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace, size_t workspace_bytes,
+                       void* stream, int64_t window_left, int64_t window_right, double softcap, const float* sinks,
+                       int64_t sink_heads);
+int fa_fp8_forward_varlen_mod(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale,
+                              const float* k_descale, const float* v_descale, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k,
+                              const int32_t* block_table, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
+                              int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype,
+                              int64_t q_token_stride, int64_t q_head_stride, int64_t k_token_stride, int64_t k_head_stride,
+                              int64_t v_token_stride, int64_t v_head_stride, int64_t max_blocks_per_seq, int64_t num_blocks,
+                              int64_t page_block_size, int64_t k_page_stride, int64_t v_page_stride, int64_t q_descale_batch_stride,
+                              int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale,
+                              void* workspace, size_t workspace_bytes, void* stream, int64_t window_left, int64_t window_right,
+                              double softcap, const float* sinks, int64_t sink_heads);
+int fa_fp8_forward_kvcache_mod(const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const float* q_descale,
+                               const float* k_descale, const float* v_descale, const int32_t* cache_seqlens, const int32_t* block_table,
+                               const int32_t* cache_batch_idx, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q,
+                               int64_t cache_len, int64_t cache_batch, int64_t d, int dtype, int q_dtype, int cache_dtype,
+                               int64_t q_batch_stride, int64_t q_token_stride, int64_t k_batch_stride, int64_t k_token_stride,
+                               int64_t v_batch_stride, int64_t v_token_stride, int64_t block_table_row_stride, int64_t num_blocks,
+                               int64_t page_block_size, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
+                               int64_t v_descale_batch_stride, int causal, double softmax_scale, int64_t num_splits, void* workspace,
+                               size_t workspace_bytes, void* stream, int64_t window_left, int64_t window_right, double softcap,
+                               const float* sinks, int64_t sink_heads);
+/* 0 for arguments the call would refuse */
+size_t fa_fp8_forward_kvcache_workspace_bytes_mod(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
+                                                  int64_t d, int64_t num_splits, int causal, int64_t window_left, int64_t window_right,
+                                                  int with_sinks);
+
 /* --- The fp8 quantiser: one 16-bit tensor x -> e4m3 codes plus float32 descales of the shape the fp8 calls above read (the
  * producer of fa_fp8_forward / _varlen / _kvcache and of the e4m3 cache).  One call covers one tensor, addressed through its own
  * strides like fa_rotary_apply's, so a slice of a fused qkv projection goes in without a copy.
@@ -1321,7 +1380,9 @@ int fa_profile_report(char* buf, size_t cap);
 /* Which form a launcher took: the number of launches of the named route since the library was loaded, negative for an unknown
  * name.  "dkdv_stream": the dS-storing dK/dV stream kernel in its general form; "dkdv_lean": its lean form (non-causal launches
  * whose key count is a multiple of 256; option dkdv_lean = 2 forces the general form).  "fp8_quant_fused", "fp8_quant_two_pass",
- * "fp8_quant_static": the three routes of fa_fp8_quantize, one count a call that launched. */
+ * "fp8_quant_static": the three routes of fa_fp8_quantize, one count a call that launched.  "fp8in_fwd_mod",
+ * "fp8in_fwd_varlen_mod", "fp8kv_split_mod": the featured kernels of fa_fp8_forward_mod, fa_fp8_forward_varlen_mod and
+ * fa_fp8_forward_kvcache_mod, one count a call that launched one (a _mod call with default trailing arguments counts none). */
 int64_t fa_route_count(const char* name);
 
 #ifdef __cplusplus

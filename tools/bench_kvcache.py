@@ -63,7 +63,11 @@ and V are then 1 an element.  ex_forward and the unfused rotation keep the 16-bi
   call with a 16-bit q on the same cache, interleaved in one process: B 32 / H 32:8 / L 8192 / Nq 1, B 1 / L 65536, B 8 / Nq 4 causal /
   L 4096, each contiguous and paged with ps 16 and 256.  Per row the median of `--rounds` (at least 5) interleaved rounds of both
   calls, the yardstick's own spread over its rounds, and the cache bytes moved over the time against the copy rate.
-Timing: HIP events around `--iters` back-to-back calls after `--warmup` calls; the median of `--reps` such groups."""
+Timing: HIP events around `--iters` back-to-back calls after `--warmup` calls; the median of `--reps` such groups.
+`--fp8-mod`: the featured fp8 decode call (a window, a softcap, sinks: DESIGN.md section 9zc) at B 32, H_q 32, H_kv 8, Nq 1, interleaved
+rounds: a causal window of 1023 over 32768 cached keys against its floor (the unwindowed fp8 call over a 1024-key cache: the same
+visible keys) and against the 16-bit-q call with the same window on the same e4m3 cache; then the cost of a softcap and of sinks on the
+unwindowed 32768-key row."""
 import argparse
 import json
 import os
@@ -554,6 +558,39 @@ def fp8q_rows(args, dtype):
     return rows
 
 
+def fp8_mod_rows(args, dtype):
+    """--fp8-mod: see the module docstring"""
+    dev, rounds = "cuda", max(args.rounds, 5)
+    b, hq, hkv, L, w = 32, 32, 8, 32768, 1023
+    q16 = torch.randn((b, 1, hq, 128), device=dev, dtype=dtype)
+    (kc, kd), (vc, vd) = (quantise(torch.randn((b, L, hkv, 128), device=dev, dtype=dtype)) for _ in range(2))
+    q8 = q16.float().clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+    qd = torch.ones((b, hkv), dtype=torch.float32, device=dev)
+    sl, sl_short = (torch.full((b,), n, dtype=torch.int32, device=dev) for n in (L, w + 1))
+    sinks = torch.randn((hq,), dtype=torch.float32, device=dev)
+    ks, vs = kc[:, :w + 1].contiguous(), vc[:, :w + 1].contiguous()          # the floor: the same visible keys in a 1024-key cache
+    fp8 = lambda k_, v_, s_, **kw: ext.fp8_kvcache_forward(q8, k_, v_, s_, None, None, qd, kd, vd, None, True, 0, dtype, **kw)   # noqa: E731
+    variants = {
+        "fp8_window_1023_of_32768": lambda: fp8(kc, vc, sl, window=(w, -1)),
+        "fp8_floor_1024_keys": lambda: fp8(ks, vs, sl_short),
+        "q16_window_1023_of_32768": lambda: ext.ex_kvcache_forward(q16, kc, vc, None, None, sl, True, None, window=(w, -1), k_descale=kd,
+                                                                   v_descale=vd),
+        "fp8_unwindowed_32768": lambda: fp8(kc, vc, sl),
+        "fp8_unwindowed_32768_softcap": lambda: fp8(kc, vc, sl, softcap=30.0),
+        "fp8_unwindowed_32768_sinks": lambda: fp8(kc, vc, sl, sinks=sinks),
+    }
+    ts = {n: [] for n in variants}
+    for _ in range(rounds):
+        for n, fn in variants.items():
+            ts[n].append(timed(fn, args.warmup, args.iters, 1))
+    rows = []
+    for n, t in ts.items():
+        m = statistics.median(t)
+        rows.append(dict(kind="fp8_mod", b=b, hq=hq, hkv=hkv, variant=n, us=round(m, 2), spread=round((max(t) - min(t)) / m, 3)))
+        print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
 def parent_check(args, dtype):
     dev, b, h, n, d = "cuda", 2, 32, 4096, 128
     q, k, v = (torch.randn((b * n, h, d), device=dev, dtype=dtype) for _ in range(3))
@@ -593,6 +630,7 @@ def main():
     ap.add_argument("--mla-sparse", action="store_true", help="time the sparse MLA call against the dense qv call at equal keys: see the module docstring")
     ap.add_argument("--mla-fp8", action="store_true", help="time the packed 8-bit latent cache against the 16-bit paged call, and the append: see the module docstring")
     ap.add_argument("--fp8-q", action="store_true", help="time fp8 KV-cache decoding (e4m3 q) against the e4m3-cache call with a 16-bit q: see the module docstring")
+    ap.add_argument("--fp8-mod", action="store_true", help="time the windowed fp8 decode call, its floor and the 16-bit-q call with the same window: see the module docstring")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     args.chunks = [int(x) for x in args.chunks.split(",")]
@@ -607,6 +645,12 @@ def main():
         ext.ex_kvcache_forward(wq, wk, wk, None, None, wl, True, None)
     torch.cuda.synchronize()
     del wq, wk
+    if args.fp8_mod:
+        rows = fp8_mod_rows(args, dtype)
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(dict(fp8_mod=True, dtype=args.dtype, version=ext.version(), rows=rows), f, indent=1)
+        return
     if args.fp8_q:
         rows = fp8q_rows(args, dtype)
         if args.json:
