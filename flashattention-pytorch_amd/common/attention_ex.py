@@ -973,6 +973,79 @@ def _fp8_kvcache_func(who, q, k_cache, v_cache, cache_seqlens, block_table, cach
     return (o, lse) if return_softmax_lse else o
 
 
+_FP8_STEP_REFUSED = ("cache_leftpad", "cu_seqlens_q", "max_seqlen_q", "cu_seqlens_k_new", "qv", "alibi_slopes", "attn_bias", "mask",
+                     "dropout_p")
+
+
+def flash_attn_fp8_kvcache_step(q, k_cache, v_cache, k, v, *, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, cache_seqlens,
+                                block_table=None, cache_batch_idx=None, q_descale=None, k_descale=None, v_descale=None,
+                                softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0, sinks=None, num_splits=0,
+                                out_dtype=None, q8_out=None, return_softmax_lse=False, **unsupported):
+    """One decode step on the e4m3 matrix instruction in one call: append the new tokens k, v (B, N_new, H_kv, 128) to the e4m3
+    cache, rotate and quantise q (B, Nq, H_q, 128), and attend with flash_attn_fp8_with_kvcache's kernels; FlashAttention-3's
+    flash_attn_with_kvcache(q, k_cache, v_cache, k=, v=, rotary_cos=, rotary_sin=, q_descale=, k_descale=, v_descale=).
+    cache_seqlens (required; int32 (B,) on the device, or an int) holds the lengths BEFORE the append.  With
+    L_b = clamp(cache_seqlens[b], 0, capacity - N_new), hk = h // (H_q // H_kv) and len_b = L_b + N_new:
+      16-bit mode  q, k, v all float16 or all bfloat16.
+        1. Token n of sequence b goes to position L_b + n of cache row cache_batch_idx[b] (or b), or through block_table to
+           pool[table[b, pos // ps], pos % ps].  k is rotated at table row L_b + n when rotary_cos / rotary_sin ((seqlen_ro,
+           rotary_dim / 2) in q's dtype, rotary_dim a multiple of 16 up to 128; rotary_interleaved as flash_attn_with_kvcache) are
+           given, and rounded once to its dtype.  The stored bytes are clamp(x * (1 / descale[b, hk]), +-448) rounded to nearest
+           even: the bytes flash_attn_with_kvcache(..., k=, v=, k_descale=, v_descale=) stores.  A cache row outside [0, B_cache)
+           or a page outside the pool drops the token; no other byte of the caches is written.
+        2. q token i is rotated at L_b + i when causal or a window bound is given, otherwise every token at L_b
+           (flash_attn_with_kvcache's rule), rounded once to its dtype and quantised with 1 / q_descale[b, hk].  The codes go into
+           q8_out, a torch.float8_e4m3fn tensor of q's shape, when one is passed, else into the call's workspace.
+        3. o, lse are, bit for bit, flash_attn_fp8_with_kvcache(q8, k_cache, v_cache, cache_seqlens=len_b, ...) with the same
+           descales, causal, window_size, softcap, sinks and num_splits on the caches as step 1 left them.
+      e4m3 mode    q, k, v all torch.float8_e4m3fn: the new bytes are scattered as they are and q is used in place; rotary and
+                   q8_out are refused.  Mixed dtypes are refused.
+    Descales: float32 (B, H_kv) or (H_kv,), static, None = 1.  out_dtype defaults to q's dtype, bfloat16 in e4m3 mode.  Lengths,
+    table, row indices, descales and rotary tables are read on the device only, the first three clamped as above, so the call
+    captures into a graph and replays after any of them change in place; seqlen_ro >= capacity + max(0, Nq - N_new) is checked on
+    the host.  Two sequences appending to one page and duplicate cache_batch_idx rows are undefined.
+    Refused by name before anything runs (NotImplementedError): cache_leftpad, cu_seqlens_q, cu_seqlens_k_new, qv, alibi_slopes,
+    attn_bias, dropout_p, head dims other than 128, block_table together with cache_batch_idx, and k / v missing (attention alone
+    is flash_attn_fp8_with_kvcache).  Dynamic q scales are quantize_fp8's, in front of flash_attn_fp8_with_kvcache.
+    Returns o (B, Nq, H_q, 128) in out_dtype, and with return_softmax_lse also lse float32 (B, H_q, Nq).  No gradient."""
+    who = "flash_attn_fp8_kvcache_step"
+    _fp8_refuse(who, _FP8_STEP_REFUSED, unsupported, "decode step")
+    if k is None or v is None:
+        raise NotImplementedError(f"{who}: k / v missing: the step appends new tokens (attention over the cache as it is: "
+                                  f"flash_attn_fp8_with_kvcache)")
+    for name, t in (("q", q), ("k", k), ("v", v), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
+        if t.dim() >= 1 and t.shape[-1] != 128:
+            raise NotImplementedError(f"{who}: head_dim {t.shape[-1]} is not supported (128 only); got {name} of shape {tuple(t.shape)}")
+    if q.dtype not in (torch.float16, torch.bfloat16, torch.float8_e4m3fn):
+        raise NotImplementedError(f"{who}: q of dtype {q.dtype} is not supported (float16, bfloat16 or torch.float8_e4m3fn)")
+    if k.dtype != q.dtype or v.dtype != q.dtype:
+        raise NotImplementedError(f"{who}: mixed dtypes are not supported: q, k, v must be all float16, all bfloat16 or all "
+                                  f"torch.float8_e4m3fn (got {q.dtype}, {k.dtype}, {v.dtype})")
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.dtype != torch.float8_e4m3fn:
+            raise NotImplementedError(f"{who}: {name} of dtype {t.dtype} is not supported (torch.float8_e4m3fn expected)")
+    if q.dtype == torch.float8_e4m3fn:
+        for name, val in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin), ("q8_out", q8_out)):
+            if val is not None:
+                raise NotImplementedError(f"{who}: {name} is not supported with torch.float8_e4m3fn q, k, v (the codes are used as they are)")
+    if block_table is not None and cache_batch_idx is not None:
+        raise NotImplementedError(f"{who}: block_table together with cache_batch_idx is not supported (a table row is the indirection)")
+    if out_dtype is not None and out_dtype not in (torch.bfloat16, torch.float16):
+        raise NotImplementedError(f"{who}: out_dtype {out_dtype} is not supported (torch.bfloat16 or torch.float16)")
+    mod = _fp8_mod_args(who, window_size, softcap, sinks)
+    import flashattention_lab_cuda as ext
+
+    det = lambda t: t.detach() if isinstance(t, torch.Tensor) else t   # noqa: E731
+    with torch.no_grad():
+        o, lse = ext.fp8_kvcache_step(q.detach(), k_cache.detach(), v_cache.detach(), k.detach(), v.detach(), cache_seqlens, block_table,
+                                      cache_batch_idx, det(q_descale), det(k_descale), det(v_descale), softmax_scale, bool(causal),
+                                      num_splits, out_dtype, rotary_cos=det(rotary_cos), rotary_sin=det(rotary_sin),
+                                      rotary_interleaved=bool(rotary_interleaved), q8_out=det(q8_out), **mod)
+    return (o, lse) if return_softmax_lse else o
+
+
 def quantize_fp8(x, heads_per_scale=1, descale=None, layout="bnhd", out=None, out_layout=None, descale_out=None, scale_pow2=False,
                  cu_seqlens=None, max_seqlen=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, seqlen_offsets=0):
     """The producer of the fp8 calls' inputs: a float16 / bfloat16 tensor as torch.float8_e4m3fn codes plus the float32 descales

@@ -32,7 +32,7 @@ const char* const kKernelNames[fa::K_COUNT] = {"fwd_f32", "bwd_delta", "bwd_dkdv
                                                "bwd_mfma", "bwd_dq_cvt", "bwd_dq_mfma", "fp8_quant", "fwd_fp8", "ex_fwd", "ex_bwd", "kv_group_sum",
                                                "fp8in_vt", "fp8in_fwd", "fp8in_vt_varlen", "fp8in_fwd_varlen", "idx_pack", "idx_logits",
                                                "idx_topk", "fp8kv_split", "fp8q_amax", "fp8q_quant", "fp8q_fused", "fp8in_fwd_mod",
-                                               "fp8in_fwd_varlen_mod", "fp8kv_split_mod"};
+                                               "fp8in_fwd_varlen_mod", "fp8kv_split_mod", "fp8kv_step_prep"};
 
 hipEvent_t prof_get_event() {
     if (!g_prof_free.empty()) { hipEvent_t e = g_prof_free.back(); g_prof_free.pop_back(); return e; }
@@ -177,7 +177,7 @@ int set_option(const char* name, int value) {
 }
 std::atomic<long long> g_route_hits[ROUTE_COUNT];
 constexpr const char* kRouteNames[ROUTE_COUNT] = {"dkdv_stream", "dkdv_lean", "fp8_quant_fused", "fp8_quant_two_pass", "fp8_quant_static",
-                                                   "fp8in_fwd_mod", "fp8in_fwd_varlen_mod", "fp8kv_split_mod"};
+                                                   "fp8in_fwd_mod", "fp8in_fwd_varlen_mod", "fp8kv_split_mod", "fp8kv_step_prep"};
 void route_hit(int id) { g_route_hits[id].fetch_add(1, std::memory_order_relaxed); }
 long long route_count(const char* name) {
     for (int i = 0; i < ROUTE_COUNT; ++i)
@@ -3230,16 +3230,45 @@ static int64_t fp8_kv_splits_mod(int64_t batch, int64_t hq, int64_t hkv, int64_t
     return m.sinks && S < 2 ? 2 : S;
 }
 
-static int fp8_kvcache_impl(const char* who, const Fp8KvCall& c) {
+// What fa_fp8_kvcache_step adds to fa_fp8_forward_kvcache_mod's arguments: the new tokens, the q8 buffer and the rotary tables
+struct Fp8StepCall {
+    const void *k_new = nullptr, *v_new = nullptr;
+    int64_t seqlen_new = 0, kn_bs = 0, kn_ts = 0, vn_bs = 0, vn_ts = 0;
+    int in_dtype = 0;
+    void* q8_out = nullptr;
+    int64_t q8_bs = 0, q8_ts = 0;
+    const void *rotary_cos = nullptr, *rotary_sin = nullptr;
+    int64_t cos_rs = 0, sin_rs = 0, seqlen_ro = 0, rotary_dim = 0;
+    int rotary_interleaved = 0;
+};
+
+// The rules of fa_fp8_forward_kvcache[_mod] (st == null) and of fa_fp8_kvcache_step (st: what it adds), in the header's order.
+// FA_OK: `empty` says that there is nothing to launch; otherwise S is the number of splits and need the workspace's bytes.
+static int fp8_kvcache_check(const char* who, const Fp8KvCall& c, const Fp8StepCall* st, bool& empty, int64_t& S, size_t& need) {
     const bool paged = c.block_table != nullptr;
     const int64_t kInt = ((int64_t)1 << 31) - 1;
+    const int64_t kMaxStride = (int64_t)1 << 44;
+    const int64_t qe = st && c.q_dtype != FA_DTYPE_E4M3 ? 2 : 1;   // bytes an element of q (and of k_new, v_new)
+    empty = false;
     // (0) the empty call
-    if (c.batch == 0 || c.seqlen_q == 0) return FA_OK;
+    if (c.batch == 0 || (!st && c.seqlen_q == 0)) {
+        empty = true;
+        return FA_OK;
+    }
     // (1) null pointers
     if (!c.q || !c.k_cache || !c.v_cache || !c.o || !c.lse) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    if (st && (!st->k_new || !st->v_new)) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer (k_new, v_new)", who);
+    if (st && !c.cache_seqlens)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_seqlens is required (the lengths before the append)", who);
     // (2) the head dim and the dtypes
     if (c.d != 128) return fail(FA_ERR_UNSUPPORTED, "%s: head_dim %lld is not supported (128 only)", who, (long long)c.d);
-    if (c.q_dtype != FA_DTYPE_E4M3)
+    if (st) {
+        if (c.q_dtype != FA_DTYPE_F16 && c.q_dtype != FA_DTYPE_BF16 && c.q_dtype != FA_DTYPE_E4M3)
+            return fail(FA_ERR_UNSUPPORTED, "%s: q_dtype must be f16, bf16 or FA_DTYPE_E4M3 (got code %d)", who, c.q_dtype);
+        if (st->in_dtype != c.q_dtype)
+            return fail(FA_ERR_UNSUPPORTED, "%s: mixed dtypes: q, k_new and v_new must be all f16, all bf16 or all e4m3 (q_dtype code %d, "
+                        "in_dtype code %d)", who, c.q_dtype, st->in_dtype);
+    } else if (c.q_dtype != FA_DTYPE_E4M3)
         return fail(FA_ERR_UNSUPPORTED, "%s: q_dtype must be FA_DTYPE_E4M3 (got code %d; a 16-bit q is fa_ex_forward_kvcache_fp8's)", who,
                     c.q_dtype);
     if (c.cache_dtype != FA_DTYPE_E4M3)
@@ -3254,6 +3283,9 @@ static int fp8_kvcache_impl(const char* who, const Fp8KvCall& c) {
     if (c.batch < 1 || c.batch > 65535) return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch must lie in [1, 65535] (got %lld)", who, (long long)c.batch);
     if (c.seqlen_q < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_q must be >= 1 (got %lld)", who, (long long)c.seqlen_q);
     if (c.cache_len < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_len must be >= 1 (got %lld)", who, (long long)c.cache_len);
+    if (st && (st->seqlen_new < 1 || st->seqlen_new > c.cache_len))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_new=%lld must lie in [1, cache_len=%lld]", who, (long long)st->seqlen_new,
+                    (long long)c.cache_len);
     if (c.heads_q > ((int64_t)1 << 20) || c.seqlen_q > ((int64_t)1 << 20) || (c.heads_q / c.heads_kv) * c.seqlen_q > ((int64_t)1 << 20))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: (heads_q / heads_kv) * seqlen_q = %lld * %lld must be <= 2^20", who,
                     (long long)(c.heads_q / c.heads_kv), (long long)c.seqlen_q);
@@ -3270,16 +3302,29 @@ static int fp8_kvcache_impl(const char* who, const Fp8KvCall& c) {
     if (!aligned16({c.q, c.k_cache, c.v_cache, c.o})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: q, k_cache, v_cache and o must be 16-byte aligned", who);
     if ((uintptr_t)c.lse % 4 != 0 || (uintptr_t)c.cache_seqlens % 4 != 0 || (uintptr_t)c.block_table % 4 != 0 || (uintptr_t)c.cache_batch_idx % 4 != 0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: lse, cache_seqlens, block_table and cache_batch_idx must be 4-byte aligned", who);
-    const int64_t kMaxStride = (int64_t)1 << 44;
-    const struct { const char* name; int64_t bs, ts, heads; } ts[3] = {
-        {"q", c.q_bs, c.q_ts, c.heads_q}, {"k_cache", c.k_bs, c.k_ts, c.heads_kv}, {"v_cache", c.v_bs, c.v_ts, c.heads_kv}};
-    for (const auto& t : ts) {
+    if (st && !aligned16({st->k_new, st->v_new})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_new and v_new must be 16-byte aligned", who);
+    // (heads: the elements of a token's heads over 128, in bytes for a 16-bit q, k_new, v_new)
+    const struct { const char* name; int64_t bs, ts, heads; } ts[5] = {
+        {"q", c.q_bs, c.q_ts, c.heads_q * qe}, {"k_cache", c.k_bs, c.k_ts, c.heads_kv}, {"v_cache", c.v_bs, c.v_ts, c.heads_kv},
+        {"k_new", st ? st->kn_bs : 0, st ? st->kn_ts : 0, c.heads_kv * qe}, {"v_new", st ? st->vn_bs : 0, st ? st->vn_ts : 0, c.heads_kv * qe}};
+    for (int i = 0; i < (st ? 5 : 3); ++i) {
+        const auto& t = ts[i];
         if (t.ts % 16 != 0 || t.bs % 16 != 0)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (batch %lld, token %lld) must be multiples of 16 bytes", who, t.name,
                         (long long)t.bs, (long long)t.ts);
         if (t.ts < t.heads * 128 || t.ts > kMaxStride || t.bs < 0 || t.bs > kMaxStride)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (batch %lld, token %lld) must be >= 0, the token stride >= heads * 128 = %lld",
                         who, t.name, (long long)t.bs, (long long)t.ts, (long long)(t.heads * 128));
+    }
+    if (st && st->q8_out) {
+        if (qe == 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: q8_out goes with a 16-bit q only (an e4m3 q is used in place)", who);
+        if (!aligned16({st->q8_out})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: q8_out must be 16-byte aligned", who);
+        if (st->q8_ts % 16 != 0 || st->q8_bs % 16 != 0 || st->q8_ts < c.heads_q * 128 || st->q8_ts > kMaxStride || st->q8_bs < 0 ||
+            st->q8_bs > kMaxStride)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of q8_out (batch %lld, token %lld) must be multiples of 16 bytes and >= 0, "
+                        "the token stride >= heads_q * 128 = %lld", who, (long long)st->q8_bs, (long long)st->q8_ts, (long long)(c.heads_q * 128));
+    } else if (st && (st->q8_bs != 0 || st->q8_ts != 0)) {
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: q8_batch_stride and q8_token_stride must be 0 without q8_out", who);
     }
     // (6) the descale strides
     const struct { const char* name; const float* p; int64_t bs; } ds[3] = {
@@ -3320,20 +3365,58 @@ static int fp8_kvcache_impl(const char* who, const Fp8KvCall& c) {
     if (row_tiles * c.heads_kv > 65535)
         return fail(FA_ERR_UNSUPPORTED, "%s: span limit: row tiles * heads_kv = %lld is beyond 65535 for one launch", who,
                     (long long)(row_tiles * c.heads_kv));
+    if (st) {
+        const int64_t kn_span = st->seqlen_new * st->kn_ts, vn_span = st->seqlen_new * st->vn_ts, q8_span = c.seqlen_q * st->q8_ts;
+        if (kn_span > kSpan || vn_span > kSpan || q8_span > kSpan)
+            return fail(FA_ERR_UNSUPPORTED, "%s: span limit: tokens * token stride of %s is %lld bytes, at or above 2^31", who,
+                        kn_span > kSpan ? "k_new" : vn_span > kSpan ? "v_new" : "q8_out",
+                        (long long)(kn_span > kSpan ? kn_span : vn_span > kSpan ? vn_span : q8_span));
+        // the rotary tables (the step's rule (9)): read on the device without a check, so every position a clamped length can give
+        // (new key n at L_b + n, q token i at L_b + i, L_b <= cache_len - seqlen_new) must be a table row
+        if ((st->rotary_cos != nullptr) != (st->rotary_sin != nullptr))
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary_cos and rotary_sin must be given together", who);
+        if (st->rotary_cos) {
+            if (qe == 1)
+                return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary_cos / rotary_sin go with 16-bit q, k_new, v_new only (e4m3 codes cannot be rotated)", who);
+            if (st->rotary_dim < 16 || st->rotary_dim > 128 || st->rotary_dim % 16 != 0)
+                return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary_dim must be a multiple of 16 in [16, 128] (got %lld)", who, (long long)st->rotary_dim);
+            const int64_t ro_need = c.cache_len + (c.seqlen_q > st->seqlen_new ? c.seqlen_q - st->seqlen_new : 0);
+            if (st->seqlen_ro < ro_need)
+                return fail(FA_ERR_INVALID_ARGUMENT,
+                            "%s: seqlen_ro=%lld must be >= capacity + max(0, seqlen_q - seqlen_new) = %lld (the tables are not bounds-checked on the device)",
+                            who, (long long)st->seqlen_ro, (long long)ro_need);
+            if (st->cos_rs < st->rotary_dim / 2 || st->sin_rs < st->rotary_dim / 2 || st->cos_rs > ((int64_t)1 << 40) || st->sin_rs > ((int64_t)1 << 40))
+                return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary row strides (%lld, %lld) must be >= rotary_dim / 2 = %lld (and <= 2^40)", who,
+                            (long long)st->cos_rs, (long long)st->sin_rs, (long long)(st->rotary_dim / 2));
+            if (st->cos_rs % 2 != 0 || st->sin_rs % 2 != 0)
+                return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary row strides (%lld, %lld) must be even", who, (long long)st->cos_rs,
+                            (long long)st->sin_rs);
+            if ((uintptr_t)st->rotary_cos % 4 != 0 || (uintptr_t)st->rotary_sin % 4 != 0)
+                return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary_cos and rotary_sin must be 4-byte aligned", who);
+        } else if (st->cos_rs != 0 || st->sin_rs != 0 || st->seqlen_ro != 0 || st->rotary_dim != 0 || st->rotary_interleaved != 0) {
+            return fail(FA_ERR_INVALID_ARGUMENT,
+                        "%s: the rotary row strides, seqlen_ro, rotary_dim and rotary_interleaved must be 0 without rotary_cos / rotary_sin", who);
+        }
+    }
     // (9) the splits
     if (c.num_splits < 0 || c.num_splits > 256)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_splits must lie in [0, 256] (got %lld)", who, (long long)c.num_splits);
     if (const int rc = fp8_mod_check(who, c.mod, c.heads_q)) return rc;
-    const int64_t S = fp8_kv_splits_mod(c.batch, c.heads_q, c.heads_kv, c.seqlen_q, c.cache_len, c.num_splits, c.causal, c.mod);
+    S = fp8_kv_splits_mod(c.batch, c.heads_q, c.heads_kv, c.seqlen_q, c.cache_len, c.num_splits, c.causal, c.mod);
     // (10) the workspace
-    const size_t need = fa::kv_workspace_bytes(c.batch, c.heads_q, c.seqlen_q, 128, (int)S);
+    need = fa::kv_workspace_bytes(c.batch, c.heads_q, c.seqlen_q, 128, (int)S);
+    if (st) need += fa::fp8kv_step_prep_bytes(c.batch, c.heads_q, c.seqlen_q, qe == 2 && !st->q8_out);
     if (need > 0) {
         if (!c.workspace || c.workspace_bytes < need)
-            return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes is too small (need %zu: fa_fp8_forward_kvcache_workspace_bytes%s)", who,
-                        c.workspace ? c.workspace_bytes : (size_t)0, need, c.mod.any() ? "_mod" : "");
+            return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes is too small (need %zu: %s%s)", who,
+                        c.workspace ? c.workspace_bytes : (size_t)0, need,
+                        st ? "fa_fp8_kvcache_step_workspace_bytes" : "fa_fp8_forward_kvcache_workspace_bytes", !st && c.mod.any() ? "_mod" : "");
         if ((uintptr_t)c.workspace % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
     }
+    return FA_OK;
+}
 
+static fa::Fp8KvArgs fp8_kvcache_args(const Fp8KvCall& c, int64_t S) {
     fa::Fp8KvArgs a;
     a.q = c.q; a.k_cache = c.k_cache; a.v_cache = c.v_cache; a.o = c.o; a.lse = c.lse;
     a.q_descale = c.q_descale; a.k_descale = c.k_descale; a.v_descale = c.v_descale;
@@ -3344,7 +3427,16 @@ static int fp8_kvcache_impl(const char* who, const Fp8KvCall& c) {
     a.q_bs = c.q_bs; a.q_ts = c.q_ts; a.kc_bs = c.k_bs; a.kc_ts = c.k_ts; a.vc_bs = c.v_bs; a.vc_ts = c.v_ts;
     a.table_row_stride = c.table_rs; a.num_blocks = c.num_blocks; a.page_size = c.ps;
     a.causal = c.causal != 0; a.scale = (float)c.scale; a.num_splits = S; a.workspace = c.workspace;
-    return launched(who, fa::launch_fp8_kvcache_mod(a, c.mod, reinterpret_cast<hipStream_t>(c.stream)));
+    return a;
+}
+
+static int fp8_kvcache_impl(const char* who, const Fp8KvCall& c) {
+    bool empty;
+    int64_t S = 1;
+    size_t need = 0;
+    if (const int rc = fp8_kvcache_check(who, c, nullptr, empty, S, need)) return rc;
+    if (empty) return FA_OK;
+    return launched(who, fa::launch_fp8_kvcache_mod(fp8_kvcache_args(c, S), c.mod, reinterpret_cast<hipStream_t>(c.stream)));
 }
 
 size_t fa_fp8_forward_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t d,
@@ -3413,6 +3505,70 @@ int fa_fp8_forward_kvcache_mod(const void* q, const void* k_cache, const void* v
     c.mod.window_left = window_left; c.mod.window_right = window_right; c.mod.softcap = softcap; c.mod.sinks = sinks;
     c.mod.sink_heads = sink_heads;
     return fp8_kvcache_impl("fa_fp8_forward_kvcache_mod", c);
+}
+
+// ---- the fp8 decode step (append, rotary and q quantise in front of fa_fp8_forward_kvcache_mod): see include/fa_mi355x.h
+size_t fa_fp8_kvcache_step_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t d,
+                                           int64_t num_splits, int causal, int64_t window_left, int64_t window_right, int with_sinks,
+                                           int in_dtype, int with_q8_out) {
+    if (!kv_ws_args_ok(batch, heads_q, heads_kv, seqlen_q, cache_len, d, num_splits) || d != 128 || window_left < -1 || window_right < -1)
+        return 0;
+    const bool e4m3 = in_dtype == FA_DTYPE_E4M3;
+    if ((!e4m3 && in_dtype != FA_DTYPE_F16 && in_dtype != FA_DTYPE_BF16) || (e4m3 && with_q8_out)) return 0;
+    return fa::fp8kv_step_prep_bytes(batch, heads_q, seqlen_q, !e4m3 && !with_q8_out) +
+           fa_fp8_forward_kvcache_workspace_bytes_mod(batch, heads_q, heads_kv, seqlen_q, cache_len, d, num_splits, causal, window_left,
+                                                      window_right, with_sinks);
+}
+
+int fa_fp8_kvcache_step(const void* q, void* k_cache, void* v_cache, void* o, float* lse, const float* q_descale, const float* k_descale,
+                        const float* v_descale, const int32_t* cache_seqlens, const int32_t* block_table, const int32_t* cache_batch_idx,
+                        int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t cache_batch, int64_t d,
+                        int dtype, int q_dtype, int cache_dtype, int64_t q_batch_stride, int64_t q_token_stride, int64_t k_batch_stride,
+                        int64_t k_token_stride, int64_t v_batch_stride, int64_t v_token_stride, int64_t block_table_row_stride,
+                        int64_t num_blocks, int64_t page_block_size, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
+                        int64_t v_descale_batch_stride, int causal, double softmax_scale, int64_t num_splits, void* workspace,
+                        size_t workspace_bytes, void* stream, int64_t window_left, int64_t window_right, double softcap, const float* sinks,
+                        int64_t sink_heads, const void* k_new, const void* v_new, int64_t seqlen_new, int64_t k_new_batch_stride,
+                        int64_t k_new_token_stride, int64_t v_new_batch_stride, int64_t v_new_token_stride, int in_dtype, void* q8_out,
+                        int64_t q8_batch_stride, int64_t q8_token_stride, const void* rotary_cos, const void* rotary_sin,
+                        int64_t rotary_cos_row_stride, int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim,
+                        int rotary_interleaved) {
+    const char* who = "fa_fp8_kvcache_step";
+    Fp8KvCall c;
+    c.q = q; c.k_cache = k_cache; c.v_cache = v_cache; c.o = o; c.lse = lse;
+    c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
+    c.cache_seqlens = cache_seqlens; c.block_table = block_table; c.cache_batch_idx = cache_batch_idx;
+    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.seqlen_q = seqlen_q; c.cache_len = cache_len; c.cache_batch = cache_batch;
+    c.d = d; c.dtype = dtype; c.q_dtype = q_dtype; c.cache_dtype = cache_dtype;
+    c.q_bs = q_batch_stride; c.q_ts = q_token_stride; c.k_bs = k_batch_stride; c.k_ts = k_token_stride; c.v_bs = v_batch_stride;
+    c.v_ts = v_token_stride;
+    c.table_rs = block_table_row_stride; c.num_blocks = num_blocks; c.ps = page_block_size;
+    c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
+    c.causal = causal; c.scale = softmax_scale; c.num_splits = num_splits;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    c.mod.window_left = window_left; c.mod.window_right = window_right; c.mod.softcap = softcap; c.mod.sinks = sinks;
+    c.mod.sink_heads = sink_heads;
+    Fp8StepCall t;
+    t.k_new = k_new; t.v_new = v_new; t.seqlen_new = seqlen_new; t.kn_bs = k_new_batch_stride; t.kn_ts = k_new_token_stride;
+    t.vn_bs = v_new_batch_stride; t.vn_ts = v_new_token_stride; t.in_dtype = in_dtype;
+    t.q8_out = q8_out; t.q8_bs = q8_batch_stride; t.q8_ts = q8_token_stride;
+    t.rotary_cos = rotary_cos; t.rotary_sin = rotary_sin; t.cos_rs = rotary_cos_row_stride; t.sin_rs = rotary_sin_row_stride;
+    t.seqlen_ro = seqlen_ro; t.rotary_dim = rotary_dim; t.rotary_interleaved = rotary_interleaved;
+    bool empty;
+    int64_t S = 1;
+    size_t need = 0;
+    if (const int rc = fp8_kvcache_check(who, c, &t, empty, S, need)) return rc;
+    if (empty) return FA_OK;
+    fa::Fp8StepArgs s;
+    s.kv = fp8_kvcache_args(c, S);
+    s.in_dtype = in_dtype; s.k_new = k_new; s.v_new = v_new; s.seqlen_new = seqlen_new;
+    s.kn_bs = t.kn_bs; s.kn_ts = t.kn_ts; s.vn_bs = t.vn_bs; s.vn_ts = t.vn_ts;
+    s.q8_out = q8_out; s.q8_bs = t.q8_bs; s.q8_ts = t.q8_ts;
+    s.rotary_cos = rotary_cos; s.rotary_sin = rotary_sin; s.rotary_cos_rs = t.cos_rs; s.rotary_sin_rs = t.sin_rs; s.rotary_dim = rotary_dim;
+    s.rotary_interleaved = rotary_interleaved ? 1 : 0;
+    // q token i is rotated at its own position when causal or a window bound was given (fa_ex_forward_kvcache_rotary's rule)
+    s.rotary_q_per_token = (causal || window_left >= 0 || window_right >= 0) ? 1 : 0;
+    return launched(who, fa::launch_fp8_kvcache_step(s, c.mod, reinterpret_cast<hipStream_t>(stream)));
 }
 
 size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {

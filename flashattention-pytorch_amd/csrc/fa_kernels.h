@@ -44,7 +44,7 @@ struct BwdArgs {
 enum KernelId { K_FWD_F32 = 0, K_BWD_DELTA, K_BWD_DKDV_F32, K_BWD_DQ_F32, K_FWD_MFMA, K_BWD_MFMA, K_BWD_DQ_CVT, K_BWD_DQ_MFMA,
                 K_FP8_QUANT, K_FWD_FP8, K_EX_FWD, K_EX_BWD, K_KV_GROUP_SUM, K_FP8IN_VT, K_FP8IN_FWD, K_FP8IN_VT_VARLEN,
                 K_FP8IN_FWD_VARLEN, K_IDX_PACK, K_IDX_LOGITS, K_IDX_TOPK, K_FP8KV_SPLIT, K_FP8Q_AMAX, K_FP8Q_QUANT, K_FP8Q_FUSED,
-                K_FP8IN_FWD_MOD, K_FP8IN_FWD_VARLEN_MOD, K_FP8KV_SPLIT_MOD, K_COUNT };
+                K_FP8IN_FWD_MOD, K_FP8IN_FWD_VARLEN_MOD, K_FP8KV_SPLIT_MOD, K_FP8KV_STEP_PREP, K_COUNT };
 void prof_begin(int id, hipStream_t st);
 void prof_end(int id, hipStream_t st);
 struct ProfScope {
@@ -67,9 +67,10 @@ int set_option(const char* name, int value);   // returns 0, or -1 for an unknow
 // Which form a launcher took, counted since the library was loaded and read back through fa_route_count(): a test asks the
 // library, it does not guess from timing.  "dkdv_stream": the dS-storing dK/dV stream kernel, "dkdv_lean": its lean form;
 // "fp8_quant_fused", "fp8_quant_two_pass", "fp8_quant_static": the routes of the fp8 quantiser (fa_fp8_quantize.hip);
-// "fp8in_fwd_mod", "fp8in_fwd_varlen_mod", "fp8kv_split_mod": the featured kernels of the fp8 calls (window, softcap, sinks).
+// "fp8in_fwd_mod", "fp8in_fwd_varlen_mod", "fp8kv_split_mod": the featured kernels of the fp8 calls (window, softcap, sinks);
+// "fp8kv_step_prep": the append / rotary / q quantise launch of the fp8 decode step (fa_fp8_step.hip).
 enum RouteId { ROUTE_DKDV_STREAM = 0, ROUTE_DKDV_LEAN, ROUTE_FP8Q_FUSED, ROUTE_FP8Q_TWO_PASS, ROUTE_FP8Q_STATIC, ROUTE_FP8IN_FWD_MOD,
-               ROUTE_FP8IN_FWD_VARLEN_MOD, ROUTE_FP8KV_SPLIT_MOD, ROUTE_COUNT };
+               ROUTE_FP8IN_FWD_VARLEN_MOD, ROUTE_FP8KV_SPLIT_MOD, ROUTE_FP8KV_STEP_PREP, ROUTE_COUNT };
 void route_hit(int id);
 
 // exact-f32 kernels (fa_generic.hip): any dtype, d <= 256
@@ -519,6 +520,24 @@ hipError_t launch_fp8_kvcache(const Fp8KvArgs& a, hipStream_t st);
 // the sink joins in the combine, which such a call always runs.
 int64_t fp8kv_split_len(int64_t cache_len, int64_t seqlen_q, int causal, const Fp8Mod& m);
 hipError_t launch_fp8_kvcache_mod(const Fp8KvArgs& a, const Fp8Mod& m, hipStream_t st);
+// The fp8 decode step (fa_fp8_step.hip; fa_fp8_kvcache_step): one launch of fp8kv_step_prep_kernel appends the new tokens to the
+// e4m3 cache, rotates and quantises q into a q8 buffer and writes len_eff[b] = L_b + seqlen_new; then launch_fp8_kvcache_mod runs
+// on kv with q = the q8 buffer and cache_seqlens = len_eff.  kv.q / kv.q_bs / kv.q_ts describe the caller's q (bytes), in in_dtype;
+// kv.cache_seqlens holds the lengths BEFORE the append (non-null); kv.workspace is the whole workspace, laid out
+// [len_eff | q8 (16-bit mode without q8_out) | the attention call's partials], each part rounded up to 256 bytes.
+struct Fp8StepArgs {
+    Fp8KvArgs kv;
+    int in_dtype = 0;                                       // of q, k_new, v_new: 1 = f16, 2 = bf16 (quantised here), 3 = e4m3 (copied)
+    const void *k_new = nullptr, *v_new = nullptr;          // (batch, seqlen_new, heads_kv, 128)
+    int64_t seqlen_new = 0, kn_bs = 0, kn_ts = 0, vn_bs = 0, vn_ts = 0;   // strides in bytes
+    void* q8_out = nullptr;                                 // 16-bit mode: the caller's (batch, seqlen_q, heads_q, 128) e4m3 buffer, or null
+    int64_t q8_bs = 0, q8_ts = 0;                           // its strides in bytes
+    const void *rotary_cos = nullptr, *rotary_sin = nullptr;   // 16-bit mode only; rows in in_dtype at strides in elements
+    int64_t rotary_cos_rs = 0, rotary_sin_rs = 0, rotary_dim = 0;
+    int rotary_interleaved = 0, rotary_q_per_token = 0;
+};
+size_t fp8kv_step_prep_bytes(int64_t batch, int64_t heads_q, int64_t seqlen_q, bool q8_in_workspace);   // the first two parts
+hipError_t launch_fp8_kvcache_step(const Fp8StepArgs& s, const Fp8Mod& m, hipStream_t st);
 // kv_combine_kernel<Tag, false> (fa_decode.hip) over partials in kv_workspace_bytes' layout, for a caller outside that file
 hipError_t launch_kv_combine(void* o, float* lse, float* po, float* plse, int64_t batch, int64_t heads_q, int64_t seqlen_q, int64_t d,
                              int dtype, int splits, hipStream_t st);

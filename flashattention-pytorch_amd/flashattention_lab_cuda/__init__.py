@@ -61,6 +61,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_fp8_forward_kvcache", "fa_fp8_forward_kvcache_workspace_bytes",
     "fa_fp8_forward_mod", "fa_fp8_forward_varlen_mod", "fa_fp8_forward_kvcache_mod", "fa_fp8_forward_kvcache_workspace_bytes_mod",
     "fa_fp8_quantize", "fa_fp8_quantize_workspace_bytes",
+    "fa_fp8_kvcache_step", "fa_fp8_kvcache_step_workspace_bytes",
 )
 
 
@@ -234,6 +235,11 @@ _sig("fa_fp8_quantize", _fields("p:x,out,descale,descale_out,cu_seqlens") + _ROT
     "i:x_batch_stride,x_head_stride,x_token_stride,out_batch_stride,out_head_stride,out_token_stride,descale_batch_stride "
     "c:scale_pow2") + _WS)
 _sig("fa_fp8_quantize_workspace_bytes", _fields("i:batch,heads,heads_per_scale"), _SIZE)
+# the fp8 decode step: fa_fp8_forward_kvcache_mod's arguments, then the new tokens, in_dtype, the q8 buffer and the rotary group
+_sig("fa_fp8_kvcache_step", _SIGNATURES["fa_fp8_forward_kvcache_mod"][1] + _fields(
+    "p:k_new,v_new i:seqlen_new,k_new_batch_stride,k_new_token_stride,v_new_batch_stride,v_new_token_stride c:in_dtype "
+    "p:q8_out i:q8_batch_stride,q8_token_stride") + _ROTARY)
+_sig("fa_fp8_kvcache_step_workspace_bytes", _KVWS + _fields("c:causal") + _WINDOW + _fields("c:with_sinks,in_dtype,with_q8_out"), _SIZE)
 _KVWSV = _fields("i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,d,num_splits c:with_sinks")
 _sig("fa_ex_kvcache_workspace_bytes_varlen", _KVWSV, _SIZE)
 _sig("fa_ex_kvcache_workspace_bytes_qv", _KVWSV + _fields("i:d_v"), _SIZE)
@@ -295,6 +301,7 @@ _family("fa_fp8_forward_kvcache", [])
 for _name in ("fa_fp8_forward_mod", "fa_fp8_forward_varlen_mod", "fa_fp8_forward_kvcache_mod"):
     _family(_name, [])
 _family("fa_fp8_quantize", [])
+_family("fa_fp8_kvcache_step", [])
 _family("fa_ex_forward_kvcache_qv", ["fa_ex_forward_kvcache" + _suffix for _suffix in ("", "_paged", "_rotary", "_fp8", "_sink", "_varlen")])
 
 
@@ -2523,4 +2530,167 @@ def fp8_kvcache_forward(q, k_cache, v_cache, cache_seqlens=None, block_table=Non
             v_cache.stride(0) if v_cache.shape[0] > 1 else 0, tstride(v_cache, hkv), *pages, qds, kds, vds, int(bool(causal)), scale, ns,
             ws.data_ptr() if need else 0, ws.numel() if need else 0, _stream_ptr(q.device), *tail))
     del keep_q, keep_k, keep_v, keep_s
+    return o, lse
+
+
+def fp8_kvcache_step(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table=None, cache_batch_idx=None, q_descale=None,
+                     k_descale=None, v_descale=None, softmax_scale=None, causal=False, num_splits=0, out_dtype=None, *, window=(-1, -1),
+                     softcap=0.0, sinks=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q8_out=None):
+    """(o, lse) of the fp8 decode step (fa_fp8_kvcache_step): the new tokens k_new, v_new (B, N_new, H_kv, 128) are appended to the
+    e4m3 caches at cache_seqlens[b] (the lengths BEFORE the append: int32 (B,) on the device, or an int), q (B, Nq, H_q, 128) is
+    rotated and quantised, and fp8_kvcache_forward's attention runs over the caches with the new tokens in them.  q, k_new, v_new are
+    all float16, all bfloat16 (quantised with 1 / descale; k_new and q rotated when rotary_cos / rotary_sin, (seqlen_ro, rotary_dim / 2)
+    in their dtype, are given) or all torch.float8_e4m3fn (copied and used as they are; no rotary, no q8_out).  q and the caches follow
+    fp8_kvcache_forward's view rules (their own strides, never copied), the new tokens and the tables ex_kvcache_forward's (a dense
+    copy where the kernel cannot address them).  q8_out: an e4m3 (B, Nq, H_q, 128) tensor that receives q's codes (16-bit mode),
+    else they stay in the workspace.  out_dtype defaults to q's dtype, bfloat16 for an e4m3 q.  Nothing is read on the host."""
+    who = "fp8_kvcache_step"
+    for name, t in (("q", q), ("k", k_new), ("v", v_new), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
+    if q.dtype not in (torch.float16, torch.bfloat16, torch.float8_e4m3fn):
+        raise NotImplementedError(f"{who}: q of dtype {q.dtype} is not supported (float16, bfloat16 or torch.float8_e4m3fn)")
+    if k_new.dtype != q.dtype or v_new.dtype != q.dtype:
+        raise NotImplementedError(f"{who}: mixed dtypes are not supported: q, k, v must be all float16, all bfloat16 or all "
+                                  f"torch.float8_e4m3fn (got {q.dtype}, {k_new.dtype}, {v_new.dtype})")
+    e4 = q.dtype == torch.float8_e4m3fn
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.dtype != torch.float8_e4m3fn:
+            raise NotImplementedError(f"{who}: {name} of dtype {t.dtype} is not supported (torch.float8_e4m3fn expected)")
+    if e4 and (rotary_cos is not None or rotary_sin is not None):
+        raise NotImplementedError(f"{who}: rotary_cos / rotary_sin are not supported with torch.float8_e4m3fn q, k, v (codes cannot be rotated)")
+    if e4 and q8_out is not None:
+        raise NotImplementedError(f"{who}: q8_out is not supported with a torch.float8_e4m3fn q (it is used in place)")
+    if out_dtype is None:
+        out_dtype = torch.bfloat16 if e4 else q.dtype
+    if out_dtype not in (torch.bfloat16, torch.float16):
+        raise NotImplementedError(f"{who}: out_dtype {out_dtype} is not supported (torch.bfloat16 or torch.float16)")
+    paged = block_table is not None
+    if paged and cache_batch_idx is not None:
+        raise NotImplementedError(f"{who}: block_table together with cache_batch_idx is not supported (a table row is the indirection)")
+    for name, t in (("block_table", block_table), ("cache_batch_idx", cache_batch_idx)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.int32):
+            dt = t.dtype if isinstance(t, torch.Tensor) else type(t).__name__
+            raise NotImplementedError(f"{who}: {name} of dtype {dt} is not supported (int32 tensor expected)")
+    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
+        raise RuntimeError(f"{who}: q must be (B, Nq, H_q, 128) and k_cache, v_cache " +
+                           ("pools (num_blocks, page_block_size, H_kv, 128)" if paged else "(B_cache, cache_len, H_kv, 128)") +
+                           f" of one shape; got {tuple(q.shape)}, {tuple(k_cache.shape)}, {tuple(v_cache.shape)}")
+    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache), ("k", k_new), ("v", v_new)):
+        if t.shape[-1] != 128:
+            raise NotImplementedError(f"{who}: head_dim {t.shape[-1]} is not supported (128 only); got {name} of shape {tuple(t.shape)}")
+    b, nq, hq = q.shape[0], q.shape[1], q.shape[2]
+    hkv = k_cache.shape[2]
+    if hkv == 0 or hq == 0 or hq % hkv != 0:
+        raise RuntimeError(f"{who}: H_q = {hq} must be a multiple of H_kv = {hkv}")
+    if k_new.dim() != 4 or k_new.shape[0] != b or k_new.shape[1] < 1 or k_new.shape[2] != hkv or v_new.shape != k_new.shape:
+        raise RuntimeError(f"{who}: k and v must be (B, N_new >= 1, H_kv, 128) = ({b}, ., {hkv}, 128) tensors of one shape; got "
+                           f"{tuple(k_new.shape)}, {tuple(v_new.shape)}")
+    nnew = k_new.shape[1]
+    if cache_seqlens is None:
+        raise RuntimeError(f"{who}: cache_seqlens is required (the lengths before the append: an int32 (B,) tensor or an int)")
+    if isinstance(cache_seqlens, int) and not isinstance(cache_seqlens, bool):
+        cache_seqlens = torch.full((b,), cache_seqlens, dtype=torch.int32, device=q.device)
+    if not (isinstance(cache_seqlens, torch.Tensor) and cache_seqlens.dtype == torch.int32 and cache_seqlens.shape == (b,)):
+        raise RuntimeError(f"{who}: cache_seqlens must be an int32 tensor of shape (B,) = ({b},) or an int")
+    rot = rotary_cos is not None or rotary_sin is not None
+    rdim = 0
+    if rot:
+        if rotary_cos is None or rotary_sin is None:
+            raise RuntimeError(f"{who}: rotary_cos and rotary_sin must be given together")
+        for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+            if not isinstance(t, torch.Tensor) or t.dtype != q.dtype or t.dim() != 2 or t.shape != rotary_cos.shape or t.numel() == 0:
+                raise RuntimeError(f"{who}: {name} must be a (seqlen_ro, rotary_dim / 2) tensor of q's dtype, rotary_cos and rotary_sin of "
+                                   f"one shape")
+        rdim = 2 * rotary_cos.shape[1]
+        if rdim % 16 != 0 or not 16 <= rdim <= 128:
+            raise RuntimeError(f"{who}: rotary_dim = 2 * rotary_cos.shape[1] must be a multiple of 16 in [16, 128], got {rdim}")
+    if q8_out is not None and not (isinstance(q8_out, torch.Tensor) and q8_out.dtype == torch.float8_e4m3fn and q8_out.shape == q.shape):
+        raise RuntimeError(f"{who}: q8_out must be a torch.float8_e4m3fn tensor of q's shape {tuple(q.shape)}")
+    tensors = [t for t in (q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, cache_batch_idx, rotary_cos, rotary_sin, q8_out)
+               if t is not None]
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: tensors must be on the GPU (HIP device); there is no CPU path")
+    if len({t.device for t in tensors}) != 1:
+        raise RuntimeError(f"{who}: all tensors must be on one device")
+    scale = 128 ** -0.5 if softmax_scale is None else float(softmax_scale)
+    if not (math.isfinite(scale) and scale > 0.0):
+        raise RuntimeError(f"{who}: softmax_scale must be finite and > 0 (got {scale})")
+    ns = operator.index(num_splits)
+    if ns < 0 or ns > 256:
+        raise RuntimeError(f"{who}: num_splits must lie in [0, 256] (got {ns})")
+    views = [("q", q, hq), ("k_cache", k_cache, hkv), ("v_cache", v_cache, hkv)] + ([("q8_out", q8_out, hq)] if q8_out is not None else [])
+    for name, t, heads in views:
+        unit = 16 // t.element_size()
+        if t.numel() and ((heads > 1 and t.stride(2) != 128) or t.stride(3) != 1):
+            raise ValueError(f"{who}: {name} must have adjacent heads with a contiguous last dim (strides {t.stride()})")
+        if t.numel() and (t.data_ptr() % 16 != 0 or t.stride(0) % unit != 0 or t.stride(1) % unit != 0 or t.stride(0) < 0 or
+                          (t.shape[1] > 1 and t.stride(1) < heads * 128)):
+            raise ValueError(f"{who}: {name} is a view the kernel cannot address: a 16-byte aligned start, batch and token strides that "
+                             f"are multiples of 16 bytes and rows that do not overlap are needed (strides {t.stride()})")
+    # (batch stride, token stride) in bytes of a view checked above
+    bstride = lambda t: (max(t.stride(0), 0) if t.shape[0] > 1 else 0) * t.element_size()   # noqa: E731
+    tstride = lambda t, heads: (t.stride(1) if t.shape[1] > 1 else heads * 128) * t.element_size()   # noqa: E731
+    if paged:
+        nblk, ps = k_cache.shape[0], k_cache.shape[1]
+        if ps < 16 or ps % 16 != 0:
+            raise RuntimeError(f"{who}: page_block_size must be a positive multiple of 16, got {ps}")
+        if block_table.dim() != 2 or block_table.shape[0] != b or block_table.shape[1] < 1:
+            raise RuntimeError(f"{who}: block_table must be an int32 (B, max_blocks_per_seq >= 1) tensor, B = {b}; got "
+                               f"{tuple(block_table.shape)}")
+        if nblk < 1:
+            raise RuntimeError(f"{who}: the pools must hold at least one page")
+        if block_table.stride(1) != 1 and block_table.shape[1] > 1:
+            block_table = block_table.contiguous()
+        cap, cbatch = block_table.shape[1] * ps, 0
+        pages = (max(block_table.stride(0), block_table.shape[1]), nblk, ps)
+    else:
+        cap = k_cache.shape[1]
+        if cap < 1:
+            raise RuntimeError(f"{who}: the caches must hold at least one token")
+        if cache_batch_idx is not None:
+            if cache_batch_idx.shape != (b,):
+                raise RuntimeError(f"{who}: cache_batch_idx must be an int32 tensor of shape (B,) = ({b},)")
+            cache_batch_idx = cache_batch_idx.contiguous()
+            cbatch = k_cache.shape[0]
+        elif k_cache.shape[0] != b:
+            raise RuntimeError(f"{who}: the caches hold {k_cache.shape[0]} rows for a batch of {b} (pass cache_batch_idx to select rows)")
+        else:
+            cbatch = 0
+        pages = (0, 0, 0)
+    if nnew > cap:
+        raise RuntimeError(f"{who}: N_new = {nnew} new tokens do not fit the capacity {cap}")
+    if rot and rotary_cos.shape[0] < cap + max(0, nq - nnew):
+        raise RuntimeError(f"{who}: rotary_cos / rotary_sin have {rotary_cos.shape[0]} rows; the capacity {cap} + max(0, Nq - N_new) = "
+                           f"{cap + max(0, nq - nnew)} are needed")
+    cache_seqlens = cache_seqlens.contiguous()
+    k_new, v_new = k_new.contiguous(), v_new.contiguous()
+    esz = q.element_size()
+    knb, knt = (x * esz for x in _kv_strides(who, "k", k_new, hkv, 128, False))
+    vnb, vnt = (x * esz for x in _kv_strides(who, "v", v_new, hkv, 128, False))
+    qdp, qds, keep_q = _kv_descale(who, "q_descale", q_descale, q, b, hkv)
+    kdp, kds, keep_k = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
+    vdp, vds, keep_v = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
+    mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks)
+    if not mod:
+        tail = (-1, -1, 0.0, 0, 0)
+    code = _E4M3_CODE if e4 else _DTYPE_CODE[q.dtype]
+    with torch.cuda.device(q.device):
+        o = torch.empty((b, nq, hq, 128), dtype=out_dtype, device=q.device)
+        lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)
+        if b == 0:
+            return o, lse
+        _tabs, rotary = _rotary_tables(rotary_cos, rotary_sin, rdim, rotary_interleaved)
+        need = int(_lib.fa_fp8_kvcache_step_workspace_bytes(b, hq, hkv, nq, cap, 128, ns, int(bool(causal)), tail[0], tail[1],
+                                                            int(sinks is not None), code, int(q8_out is not None)))
+        ws = _workspace(q.device, need)
+        q8 = (q8_out.data_ptr(), bstride(q8_out), tstride(q8_out, hq)) if q8_out is not None else (0, 0, 0)
+        _call("fa_fp8_kvcache_step", (
+            q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp, cache_seqlens.data_ptr(),
+            block_table.data_ptr() if paged else 0, cache_batch_idx.data_ptr() if cache_batch_idx is not None else 0, b, hq, hkv, nq, cap,
+            cbatch, 128, _DTYPE_CODE[out_dtype], code, _E4M3_CODE, bstride(q), tstride(q, hq), bstride(k_cache), tstride(k_cache, hkv),
+            bstride(v_cache), tstride(v_cache, hkv), *pages, qds, kds, vds, int(bool(causal)), scale, ns, ws.data_ptr(), ws.numel(),
+            _stream_ptr(q.device), *tail, k_new.data_ptr(), v_new.data_ptr(), nnew, knb, knt, vnb, vnt, code, *q8, *rotary))
+    del keep_q, keep_k, keep_v, keep_s, _tabs
     return o, lse

@@ -1351,6 +1351,65 @@ int fa_fp8_quantize(const void* x, void* out, const float* descale, float* desca
                     int64_t descale_batch_stride, int scale_pow2, void* workspace, size_t workspace_bytes, void* stream);
 size_t fa_fp8_quantize_workspace_bytes(int64_t batch, int64_t heads, int64_t heads_per_scale);
 
+/* --- The fp8 decode step: append the new tokens to the e4m3 cache, rotate and quantise q, and attend, in one
+ * call; a family of its own.  It takes fa_fp8_forward_kvcache_mod's arguments, which keep their meaning except where said here,
+ * followed by the new-token group (k_new .. v_new_token_stride), in_dtype, the q8 group and the rotary group as
+ * fa_ex_forward_kvcache_rotary spells it.  All strides are in bytes, but the rotary row strides, which count elements.
+ * cache_seqlens (required) holds the lengths BEFORE the append: L_b = clamp(cache_seqlens[b], 0, cache_len - seqlen_new),
+ * hk = h / (heads_q / heads_kv), len_b = L_b + seqlen_new.  q_dtype names the type of q and in_dtype that of k_new and v_new
+ * (batch, seqlen_new, heads_kv, 128); they must be equal.
+ * 16-bit mode (FA_DTYPE_F16 or FA_DTYPE_BF16):
+ *   1. Append.  Token n of sequence b goes to position L_b + n of cache row cache_batch_idx[b] (or b), or through the table to
+ *      pool[block_table[b, pos / page_block_size], pos % page_block_size].  k_new is rotated at table row L_b + n when tables are
+ *      given, in fp32 from the 16-bit inputs, and rounded once to in_dtype; v_new is taken as it is.  The stored bytes are
+ *      clamp(float(x) * (1.0f / descale[b, hk]), -448, 448) rounded to nearest even: the bytes fa_ex_forward_kvcache_fp8 stores,
+ *      by the same device functions.  A row index outside [0, cache_batch) or a page outside [0, num_blocks) drops the token.  No
+ *      other byte of the caches is written.
+ *   2. q.  Token i is rotated by fa_ex_forward_kvcache_rotary's rule: at table row L_b + i when causal is set or a window bound
+ *      is given (>= 0 as passed), otherwise every token at L_b; rounded once to in_dtype; then quantised with
+ *      1.0f / q_descale[b, hk] by the append's arithmetic.  The codes go to q8_out, e4m3 (batch, seqlen_q, heads_q, 128) at
+ *      q8_batch_stride / q8_token_stride, or with q8_out NULL (both strides 0) into the workspace.  q is not modified.
+ *   3. Attention.  o and lse are, bit for bit, fa_fp8_forward_kvcache_mod on those codes and the caches as step 1 left them with
+ *      cache_seqlens = len_b and the same descales, causal, window, softcap, sinks and num_splits.
+ * e4m3 mode (FA_DTYPE_E4M3, FlashAttention-3's form): the new bytes are scattered as they are, q is used in place, q8_out and
+ * the rotary tables must be NULL.
+ * Kernels: one launch of fp8kv_step_prep_kernel (route and profile scope "fp8kv_step_prep") does steps 1 and 2 and writes len_b
+ * for every sequence; then the launches of fa_fp8_forward_kvcache_mod, unchanged.  Nothing is read on the host: lengths, table,
+ * indices, descales and tables are device memory, the first three untrusted and clamped as above, so a captured call replays
+ * after any of them changed in place.  Two sequences that append to one page, and a duplicate cache_batch_idx, are undefined.
+ * Workspace: fa_fp8_kvcache_step_workspace_bytes(...) bytes, always > 0: [len_b, int32 | the q codes, 16-bit mode without q8_out |
+ * fa_fp8_forward_kvcache_workspace_bytes_mod's partials], each part rounded up to 256 bytes; 0 for arguments the call would refuse.
+ * Checked before any HIP call, the first broken rule named in fa_last_error(), in this order: (0) batch == 0 is the empty call,
+ * FA_OK; (1) q, k_cache, v_cache, o, lse, k_new, v_new, cache_seqlens non-null; (2) d == 128, q_dtype f16, bf16 or e4m3, in_dtype
+ * == q_dtype ("mixed"), cache_dtype FA_DTYPE_E4M3, dtype f16 or bf16, else FA_ERR_UNSUPPORTED; (3), (4) the parent's, and 1 <=
+ * seqlen_new <= cache_len; (5) the parent's with q's token stride >= heads_q * 128 elements of q_dtype, and k_new, v_new 16-byte
+ * aligned with strides that are multiples of 16, the token stride >= heads_kv * 128 elements and <= 2^44; q8_out only in 16-bit
+ * mode, 16-byte aligned, its strides multiples of 16, the token stride >= heads_q * 128, and both 0 without it; (6), (7) the
+ * parent's; (8) the parent's span limits, and seqlen_new * token stride of k_new and v_new and seqlen_q * q8_token_stride below
+ * 2^31 (FA_ERR_UNSUPPORTED); (9) rotary: only in 16-bit mode; both tables or none; rotary_dim a multiple of 16 in [16, 128];
+ * seqlen_ro >= cache_len + max(0, seqlen_q - seqlen_new) (the tables are not bounds-checked on the device); row strides >=
+ * rotary_dim / 2, even and <= 2^40; tables 4-byte aligned; the five integers 0 without tables; (10) num_splits in [0, 256] and the
+ * window, softcap and sinks rules of the _mod calls; (11) workspace non-null with workspace_bytes >= the need (FA_ERR_WORKSPACE),
+ * 16-byte aligned.  Everything else is FA_ERR_INVALID_ARGUMENT. */
+int fa_fp8_kvcache_step(const void* q, void* k_cache, void* v_cache, void* o, float* lse, const float* q_descale,
+                        const float* k_descale, const float* v_descale, const int32_t* cache_seqlens, const int32_t* block_table,
+                        const int32_t* cache_batch_idx, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q,
+                        int64_t cache_len, int64_t cache_batch, int64_t d, int dtype, int q_dtype, int cache_dtype,
+                        int64_t q_batch_stride, int64_t q_token_stride, int64_t k_batch_stride, int64_t k_token_stride,
+                        int64_t v_batch_stride, int64_t v_token_stride, int64_t block_table_row_stride, int64_t num_blocks,
+                        int64_t page_block_size, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
+                        int64_t v_descale_batch_stride, int causal, double softmax_scale, int64_t num_splits, void* workspace,
+                        size_t workspace_bytes, void* stream, int64_t window_left, int64_t window_right, double softcap,
+                        const float* sinks, int64_t sink_heads, const void* k_new, const void* v_new, int64_t seqlen_new,
+                        int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t v_new_batch_stride,
+                        int64_t v_new_token_stride, int in_dtype, void* q8_out, int64_t q8_batch_stride, int64_t q8_token_stride,
+                        const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride,
+                        int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved);
+/* with_q8_out: q8_out != NULL; 0 for arguments the call would refuse */
+size_t fa_fp8_kvcache_step_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
+                                           int64_t d, int64_t num_splits, int causal, int64_t window_left, int64_t window_right,
+                                           int with_sinks, int in_dtype, int with_q8_out);
+
 /* --- support entry points (no reference counterpart: the reference allocates inside the callee) --- */
 /* bytes for the CURRENT kernel mode: two float row constants per query row (+ an fp32 dQ scratch of bh*n*d floats in
  * FA_MODE_BWD_ATOMIC only); ask again after changing the mode */
@@ -1382,7 +1441,8 @@ int fa_profile_report(char* buf, size_t cap);
  * whose key count is a multiple of 256; option dkdv_lean = 2 forces the general form).  "fp8_quant_fused", "fp8_quant_two_pass",
  * "fp8_quant_static": the three routes of fa_fp8_quantize, one count a call that launched.  "fp8in_fwd_mod",
  * "fp8in_fwd_varlen_mod", "fp8kv_split_mod": the featured kernels of fa_fp8_forward_mod, fa_fp8_forward_varlen_mod and
- * fa_fp8_forward_kvcache_mod, one count a call that launched one (a _mod call with default trailing arguments counts none). */
+ * fa_fp8_forward_kvcache_mod, one count a call that launched one (a _mod call with default trailing arguments counts none).
+ * "fp8kv_step_prep": the append / rotary / quantise launch of fa_fp8_kvcache_step, one count a call. */
 int64_t fa_route_count(const char* name);
 
 #ifdef __cplusplus

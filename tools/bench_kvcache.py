@@ -67,7 +67,12 @@ Timing: HIP events around `--iters` back-to-back calls after `--warmup` calls; t
 `--fp8-mod`: the featured fp8 decode call (a window, a softcap, sinks: DESIGN.md section 9zc) at B 32, H_q 32, H_kv 8, Nq 1, interleaved
 rounds: a causal window of 1023 over 32768 cached keys against its floor (the unwindowed fp8 call over a 1024-key cache: the same
 visible keys) and against the 16-bit-q call with the same window on the same e4m3 cache; then the cost of a softcap and of sinks on the
-unwindowed 32768-key row."""
+unwindowed 32768-key row.
+`--fp8-step`: the fp8 decode step (fp8_kvcache_step: append, rotary-free q quantise and attention in one call)
+at B 1 and 32, H 32:8, Nq = N_new = 1 over 8192 cached keys, contiguous and paged (ps 16), interleaved rounds: the step; its parent,
+fp8_kvcache_forward alone on the pre-filled cache (the difference is the prep launch); what gives the same effect without the step,
+the e4m3-cache call with a 16-bit q and the append; and the prep launch by its own profile scope against the bytes it moves.
+`--md PATH` writes the table as markdown."""
 import argparse
 import json
 import os
@@ -591,6 +596,83 @@ def fp8_mod_rows(args, dtype):
     return rows
 
 
+def fp8_step_rows(args, dtype):
+    """--fp8-step: see the module docstring"""
+    dev, rounds = "cuda", max(args.rounds, 5)
+    hq, hkv, L, cap = 32, 8, 8192, 8192 + 256
+    rows = []
+    for b in (1, 32):
+        q16 = torch.randn((b, 1, hq, 128), device=dev, dtype=dtype)
+        kn, vn = (torch.randn((b, 1, hkv, 128), device=dev, dtype=dtype) for _ in range(2))
+        (kc, kd), (vc, vd) = (quantise(torch.randn((b, cap, hkv, 128), device=dev, dtype=dtype)) for _ in range(2))
+        qd = torch.full((b, hkv), 2.0 ** -5, dtype=torch.float32, device=dev)
+        q8 = (q16.float() * 32.0).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+        sl, sl1 = (torch.full((b,), n, dtype=torch.int32, device=dev) for n in (L, L + 1))
+        # the prep launch: q and the new tokens in, their codes and the lengths out
+        prep_bytes = b * (hq * 128 * (2 + 1) + 2 * hkv * 128 * (2 + 1) + 8)
+        for ps in (0, 16):
+            if ps:
+                nblk = b * cap // ps
+                perm = torch.randperm(nblk, device=dev)
+                table = perm.view(b, cap // ps).to(torch.int32)
+                kk, vv = torch.empty_like(kc).view(nblk, ps, hkv, 128), torch.empty_like(vc).view(nblk, ps, hkv, 128)
+                kk[perm] = kc.view(nblk, ps, hkv, 128)
+                vv[perm] = vc.view(nblk, ps, hkv, 128)
+            else:
+                table, kk, vv = None, kc, vc
+            variants = {
+                "step": lambda: ext.fp8_kvcache_step(q16, kk, vv, kn, vn, sl, table, None, qd, kd, vd, None, False, 0, dtype),
+                "parent_fp8_decode": lambda: ext.fp8_kvcache_forward(q8, kk, vv, sl1, table, None, qd, kd, vd, None, False, 0, dtype),
+                "q16_call_with_append": lambda: ext.ex_kvcache_forward(q16, kk, vv, kn, vn, sl, False, None, block_table=table, k_descale=kd,
+                                                                       v_descale=vd),
+            }
+            ts = {n: [] for n in variants}
+            for _ in range(rounds):
+                for n, fn in variants.items():
+                    ts[n].append(timed(fn, args.warmup, args.iters, 1))
+            # the same calls replayed from one captured graph each: the device's time without the wrapper and the launch path
+            graphed = {}
+            for n in ("step", "parent_fp8_decode"):
+                gr = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gr):
+                    for _ in range(args.iters):
+                        variants[n]()
+                graphed[n] = statistics.median([timed(gr.replay, 1, 1, 1) / args.iters for _ in range(rounds)])
+            ext.profile_enable(True)
+            for _ in range(args.iters):
+                variants["step"]()
+            torch.cuda.synchronize()
+            count, ms = ext.profile_report().get("fp8kv_step_prep", (0, 0.0))
+            ext.profile_enable(False)
+            med = {n: statistics.median(t) for n, t in ts.items()}
+            prep_us = ms * 1e3 / max(count, 1)
+            rows.append(dict(kind="fp8_step", b=b, hq=hq, hkv=hkv, L=L, page_size=ps, step_us=round(med["step"], 2),
+                             parent_us=round(med["parent_fp8_decode"], 2), step_minus_parent_us=round(med["step"] - med["parent_fp8_decode"], 2),
+                             q16_append_us=round(med["q16_call_with_append"], 2), step_graph_us=round(graphed["step"], 2),
+                             parent_graph_us=round(graphed["parent_fp8_decode"], 2),
+                             spread={n: round((max(t) - min(t)) / med[n], 3) for n, t in ts.items()}, prep_kernel_us=round(prep_us, 2),
+                             prep_bytes=prep_bytes, prep_floor_us=round(prep_bytes / COPY_RATE * 1e6, 4)))
+            print(json.dumps(rows[-1]), flush=True)
+        del kc, vc
+    return rows
+
+
+def fp8_step_markdown(rows, args):
+    out = ["# The fp8 decode step: measured on an MI355X", "",
+           f"`tools/bench_kvcache.py --fp8-step --dtype {args.dtype}`: H 32 / 8, Nq = N_new = 1, 8192 cached keys, num_splits by the rule; the median "
+           f"of {max(args.rounds, 5)} interleaved rounds of {args.iters} back-to-back calls (microseconds a call, host path included); the prep "
+           "kernel by its own profile scope (events on the stream, which cost about as much as the kernel); its floor is its bytes at the copy rate.  "
+           "`graph`: the same calls replayed from one captured graph, the device's time without the wrapper and the launch path.", "",
+           "| B | layout | step | fp8 decode alone | step - alone | 16-bit q call + append | step, graph | alone, graph | prep kernel | prep bytes | prep floor |",
+           "|---|---|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        out.append(f"| {r['b']} | {'ps ' + str(r['page_size']) if r['page_size'] else 'contiguous'} | {r['step_us']} | {r['parent_us']} | "
+                   f"{r['step_minus_parent_us']} | {r['q16_append_us']} | {r['step_graph_us']} | {r['parent_graph_us']} | {r['prep_kernel_us']} | {r['prep_bytes']} | {r['prep_floor_us']} |")
+    out += ["", "Spread of the rounds (max - min over the median): " +
+            "; ".join(f"B {r['b']} {'ps16' if r['page_size'] else 'contig'} " + ", ".join(f"{k} {v}" for k, v in r["spread"].items()) for r in rows), ""]
+    return "\n".join(out)
+
+
 def parent_check(args, dtype):
     dev, b, h, n, d = "cuda", 2, 32, 4096, 128
     q, k, v = (torch.randn((b * n, h, d), device=dev, dtype=dtype) for _ in range(3))
@@ -631,6 +713,8 @@ def main():
     ap.add_argument("--mla-fp8", action="store_true", help="time the packed 8-bit latent cache against the 16-bit paged call, and the append: see the module docstring")
     ap.add_argument("--fp8-q", action="store_true", help="time fp8 KV-cache decoding (e4m3 q) against the e4m3-cache call with a 16-bit q: see the module docstring")
     ap.add_argument("--fp8-mod", action="store_true", help="time the windowed fp8 decode call, its floor and the 16-bit-q call with the same window: see the module docstring")
+    ap.add_argument("--fp8-step", action="store_true", help="time the fp8 decode step against its parent and the 16-bit-q call with the append: see the module docstring")
+    ap.add_argument("--md", default=None, help="--fp8-step: write the table as markdown to this path")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     args.chunks = [int(x) for x in args.chunks.split(",")]
@@ -645,6 +729,15 @@ def main():
         ext.ex_kvcache_forward(wq, wk, wk, None, None, wl, True, None)
     torch.cuda.synchronize()
     del wq, wk
+    if args.fp8_step:
+        rows = fp8_step_rows(args, dtype)
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(dict(fp8_step=True, dtype=args.dtype, version=ext.version(), copy_rate_TBps=COPY_RATE / 1e12, rows=rows), f, indent=1)
+        if args.md:
+            with open(args.md, "w") as f:
+                f.write(fp8_step_markdown(rows, args))
+        return
     if args.fp8_mod:
         rows = fp8_mod_rows(args, dtype)
         if args.json:
