@@ -1099,3 +1099,16 @@ def quantize_fp8_qkv(q, k, v, *, layout="bnhd", q_descale=None, k_descale=None, 
     k8, kd = quantize_fp8(k, 1, k_descale, layout, scale_pow2=scale_pow2, cu_seqlens=cu_seqlens_k, max_seqlen=max_seqlen_k, **rot)
     v8, vd = quantize_fp8(v, 1, v_descale, layout, scale_pow2=scale_pow2, cu_seqlens=cu_seqlens_k, max_seqlen=max_seqlen_k)
     return q8, k8, v8, qd, kd, vd
+
+
+# The fp8 calls at head dims 64, 128 and 256 live in a module of their own (common/fp8_attention.py, which imports this one); they are
+# reachable from here too, where their namesakes are.
+_FP8_HDIM_FUNCS = ("fp8_attn_func", "fp8_attn_varlen_func", "fp8_attn_with_kvcache")
+
+
+def __getattr__(name):
+    if name in _FP8_HDIM_FUNCS:
+        from common import fp8_attention
+
+        return getattr(fp8_attention, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

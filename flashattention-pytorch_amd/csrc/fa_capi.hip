@@ -32,7 +32,8 @@ const char* const kKernelNames[fa::K_COUNT] = {"fwd_f32", "bwd_delta", "bwd_dkdv
                                                "bwd_mfma", "bwd_dq_cvt", "bwd_dq_mfma", "fp8_quant", "fwd_fp8", "ex_fwd", "ex_bwd", "kv_group_sum",
                                                "fp8in_vt", "fp8in_fwd", "fp8in_vt_varlen", "fp8in_fwd_varlen", "idx_pack", "idx_logits",
                                                "idx_topk", "fp8kv_split", "fp8q_amax", "fp8q_quant", "fp8q_fused", "fp8in_fwd_mod",
-                                               "fp8in_fwd_varlen_mod", "fp8kv_split_mod", "fp8kv_step_prep"};
+                                               "fp8in_fwd_varlen_mod", "fp8kv_split_mod", "fp8kv_step_prep", "fp8in_fwd_hdim",
+    "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim"};
 
 hipEvent_t prof_get_event() {
     if (!g_prof_free.empty()) { hipEvent_t e = g_prof_free.back(); g_prof_free.pop_back(); return e; }
@@ -177,7 +178,8 @@ int set_option(const char* name, int value) {
 }
 std::atomic<long long> g_route_hits[ROUTE_COUNT];
 constexpr const char* kRouteNames[ROUTE_COUNT] = {"dkdv_stream", "dkdv_lean", "fp8_quant_fused", "fp8_quant_two_pass", "fp8_quant_static",
-                                                   "fp8in_fwd_mod", "fp8in_fwd_varlen_mod", "fp8kv_split_mod", "fp8kv_step_prep"};
+                                                   "fp8in_fwd_mod", "fp8in_fwd_varlen_mod", "fp8kv_split_mod", "fp8kv_step_prep", "fp8in_fwd_hdim",
+                                                   "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim"};
 void route_hit(int id) { g_route_hits[id].fetch_add(1, std::memory_order_relaxed); }
 long long route_count(const char* name) {
     for (int i = 0; i < ROUTE_COUNT; ++i)
@@ -2875,7 +2877,16 @@ static int fp8_mod_check(const char* who, const fa::Fp8Mod& m, int64_t heads_q) 
     return FA_OK;
 }
 
+// The head dim of an fp8 call: 128 through the entry points up to _mod, 64 / 128 / 256 through the _hdim ones (`hdim`).
+static int fp8_head_dim_check(const char* who, int64_t d, bool hdim) {
+    if (hdim ? (d != 64 && d != 128 && d != 256) : d != 128)
+        return fail(FA_ERR_UNSUPPORTED, hdim ? "%s: head_dim %lld is not supported (64, 128 or 256)" : "%s: head_dim %lld is not supported (128 only)",
+                    who, (long long)d);
+    return FA_OK;
+}
+
 struct Fp8Call {
+    bool hdim = false;                     // the _hdim entry point: d in {64, 128, 256}, and d bounds what 128 bounds elsewhere
     fa::Fp8Mod mod;
     Fp8Tensor q, k, v, o;
     float* lse = nullptr;
@@ -2897,7 +2908,8 @@ static int fp8_forward_impl(const char* who, const Fp8Call& c) {
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch, heads_q, heads_kv, seqlen_q, seqlen_k and d must be > 0 (got %lld, %lld, %lld, %lld, %lld, %lld)",
                     who, (long long)c.batch, (long long)c.heads_q, (long long)c.heads_kv, (long long)c.nq, (long long)c.nk, (long long)c.d);
     // (3) the head dim
-    if (c.d != 128) return fail(FA_ERR_UNSUPPORTED, "%s: head_dim %lld is not supported (128 only)", who, (long long)c.d);
+    if (const int rc = fp8_head_dim_check(who, c.d, c.hdim)) return rc;
+    const int64_t d = c.d;
     // (4) the heads ratio
     if (c.heads_q % c.heads_kv != 0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads_q=%lld must be a multiple of heads_kv=%lld", who, (long long)c.heads_q, (long long)c.heads_kv);
@@ -2923,27 +2935,27 @@ static int fp8_forward_impl(const char* who, const Fp8Call& c) {
         {"q", &c.q, 16, c.heads_q, c.nq}, {"k", &c.k, 16, c.heads_kv, c.nk}, {"v", &c.v, 16, c.heads_kv, c.nk}, {"o", &c.o, 8, c.heads_q, c.nq}};
     const int64_t kMaxStride = (int64_t)1 << 44;
     for (const auto& t : ts) {
-        const int64_t bs = c.batch > 1 ? t.t->bs : 0, hs = t.heads > 1 ? t.t->hs : 0, tk = t.rows > 1 ? t.t->ts : 128;
+        const int64_t bs = c.batch > 1 ? t.t->bs : 0, hs = t.heads > 1 ? t.t->hs : 0, tk = t.rows > 1 ? t.t->ts : d;
         if (bs % t.unit != 0 || hs % t.unit != 0 || tk % t.unit != 0)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (%lld, %lld, %lld) must be multiples of %lld elements (16 bytes)", who,
                         t.name, (long long)t.t->bs, (long long)t.t->hs, (long long)t.t->ts, (long long)t.unit);
-        if (bs < 0 || hs < 0 || tk < 128 || bs > kMaxStride || hs > kMaxStride || tk > kMaxStride)
-            return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (%lld, %lld, %lld) must be >= 0, the token stride >= 128", who, t.name,
-                        (long long)t.t->bs, (long long)t.t->hs, (long long)t.t->ts);
+        if (bs < 0 || hs < 0 || tk < d || bs > kMaxStride || hs > kMaxStride || tk > kMaxStride)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (%lld, %lld, %lld) must be >= 0, the token stride >= %lld", who, t.name,
+                        (long long)t.t->bs, (long long)t.t->hs, (long long)t.t->ts, (long long)d);
     }
     // (7) the span limit: q and k are read through 32-bit buffer descriptors and offsets per (batch, head) unit
     const int64_t kSpan = ((int64_t)1 << 31) - 1;
-    const int64_t q_span = (c.nq + 255) / 256 * 256 * (c.nq > 1 ? c.q.ts : 128), k_span = (c.nk + 255) / 256 * 256 * (c.nk > 1 ? c.k.ts : 128);
+    const int64_t q_span = (c.nq + 255) / 256 * 256 * (c.nq > 1 ? c.q.ts : d), k_span = (c.nk + 255) / 256 * 256 * (c.nk > 1 ? c.k.ts : d);
     if (q_span > kSpan || k_span > kSpan)
         return fail(FA_ERR_UNSUPPORTED, "%s: span limit: round_up(rows, 256) * token stride of %s is %lld bytes, at or above 2^31", who,
                     q_span > kSpan ? "q" : "k", (long long)(q_span > kSpan ? q_span : k_span));
     if (c.batch * c.heads_q >= ((int64_t)1 << 31) / ((c.nq + 255) / 256) || c.batch * c.heads_kv >= ((int64_t)1 << 31) / ((c.nk + 63) / 64))
         return fail(FA_ERR_UNSUPPORTED, "%s: span limit: batch * heads * tiles too large for one launch", who);
     // (8) the workspace
-    const size_t need = fa::fp8in_workspace_bytes(c.batch * c.heads_kv, c.nk);
+    const size_t need = fa::fp8in_workspace_bytes(c.batch * c.heads_kv, c.nk, d);
     if (!c.workspace || c.workspace_bytes < need)
-        return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes is too small (need %zu: fa_fp8_forward_workspace_bytes)", who,
-                    c.workspace ? c.workspace_bytes : (size_t)0, need);
+        return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes is too small (need %zu: fa_fp8_forward%s_workspace_bytes)", who,
+                    c.workspace ? c.workspace_bytes : (size_t)0, need, c.hdim ? "_hdim" : "");
     if ((uintptr_t)c.workspace % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
 
     fa::Fp8InArgs a;
@@ -2951,17 +2963,23 @@ static int fp8_forward_impl(const char* who, const Fp8Call& c) {
     a.q_descale = c.q_descale; a.k_descale = c.k_descale; a.v_descale = c.v_descale;
     a.qds_bs = c.qds_bs; a.kds_bs = c.kds_bs; a.vds_bs = c.vds_bs;
     a.batch = c.batch; a.heads_q = c.heads_q; a.heads_kv = c.heads_kv; a.nq = c.nq; a.nk = c.nk; a.dtype = c.dtype;
-    a.q_bs = c.batch > 1 ? c.q.bs : 0; a.q_hs = c.heads_q > 1 ? c.q.hs : 0; a.q_ts = c.nq > 1 ? c.q.ts : 128;
-    a.k_bs = c.batch > 1 ? c.k.bs : 0; a.k_hs = c.heads_kv > 1 ? c.k.hs : 0; a.k_ts = c.nk > 1 ? c.k.ts : 128;
-    a.v_bs = c.batch > 1 ? c.v.bs : 0; a.v_hs = c.heads_kv > 1 ? c.v.hs : 0; a.v_ts = c.nk > 1 ? c.v.ts : 128;
-    a.o_bs = c.batch > 1 ? c.o.bs : 0; a.o_hs = c.heads_q > 1 ? c.o.hs : 0; a.o_ts = c.nq > 1 ? c.o.ts : 128;
-    a.causal = c.causal != 0; a.scale = (float)c.scale; a.workspace = c.workspace;
-    return launched(who, fa::launch_fp8_inputs_mod(a, c.mod, reinterpret_cast<hipStream_t>(c.stream)));
+    a.q_bs = c.batch > 1 ? c.q.bs : 0; a.q_hs = c.heads_q > 1 ? c.q.hs : 0; a.q_ts = c.nq > 1 ? c.q.ts : d;
+    a.k_bs = c.batch > 1 ? c.k.bs : 0; a.k_hs = c.heads_kv > 1 ? c.k.hs : 0; a.k_ts = c.nk > 1 ? c.k.ts : d;
+    a.v_bs = c.batch > 1 ? c.v.bs : 0; a.v_hs = c.heads_kv > 1 ? c.v.hs : 0; a.v_ts = c.nk > 1 ? c.v.ts : d;
+    a.o_bs = c.batch > 1 ? c.o.bs : 0; a.o_hs = c.heads_q > 1 ? c.o.hs : 0; a.o_ts = c.nq > 1 ? c.o.ts : d;
+    a.causal = c.causal != 0; a.scale = (float)c.scale; a.workspace = c.workspace; a.d = d;
+    return launched(who, fa::launch_fp8_inputs_hdim(a, c.mod, reinterpret_cast<hipStream_t>(c.stream)));   // (d == 128: launch_fp8_inputs_mod)
 }
 
 size_t fa_fp8_forward_workspace_bytes(int64_t batch, int64_t heads_kv, int64_t seqlen_k, int64_t d) {
     if (batch <= 0 || heads_kv <= 0 || seqlen_k <= 0 || d != 128) return 0;
     return fa::fp8in_workspace_bytes(batch * heads_kv, seqlen_k);
+}
+
+// the parent's size at d = 128; the V^T image is units_kv * tiles * d * 128 + 256 bytes
+size_t fa_fp8_forward_hdim_workspace_bytes(int64_t batch, int64_t heads_kv, int64_t seqlen_k, int64_t head_dim) {
+    if (batch <= 0 || heads_kv <= 0 || seqlen_k <= 0 || (head_dim != 64 && head_dim != 128 && head_dim != 256)) return 0;
+    return fa::fp8in_workspace_bytes(batch * heads_kv, seqlen_k, head_dim);
 }
 
 int fa_fp8_forward(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
@@ -2984,15 +3002,17 @@ int fa_fp8_forward(const void* q, const void* k, const void* v, void* o, float* 
     return fp8_forward_impl("fa_fp8_forward", c);
 }
 
-int fa_fp8_forward_mod(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
-                       const float* v_descale, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_k, int64_t d,
-                       int dtype, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_token_stride, int64_t k_batch_stride,
-                       int64_t k_head_stride, int64_t k_token_stride, int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride,
-                       int64_t o_batch_stride, int64_t o_head_stride, int64_t o_token_stride, int64_t q_descale_batch_stride,
-                       int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace,
-                       size_t workspace_bytes, void* stream, int64_t window_left, int64_t window_right, double softcap, const float* sinks,
-                       int64_t sink_heads) {
+// the arguments of fa_fp8_forward_mod and fa_fp8_forward_hdim alike (hdim: the head dims 64, 128 and 256)
+static int fp8_forward_mod_entry(const char* who, bool hdim, const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
+        const float* v_descale, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_k, int64_t d,
+        int dtype, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_token_stride, int64_t k_batch_stride,
+        int64_t k_head_stride, int64_t k_token_stride, int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride,
+        int64_t o_batch_stride, int64_t o_head_stride, int64_t o_token_stride, int64_t q_descale_batch_stride,
+        int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace,
+        size_t workspace_bytes, void* stream, int64_t window_left, int64_t window_right, double softcap, const float* sinks,
+        int64_t sink_heads) {
     Fp8Call c;
+    c.hdim = hdim;
     c.q.p = q; c.q.bs = q_batch_stride; c.q.hs = q_head_stride; c.q.ts = q_token_stride;
     c.k.p = k; c.k.bs = k_batch_stride; c.k.hs = k_head_stride; c.k.ts = k_token_stride;
     c.v.p = v; c.v.bs = v_batch_stride; c.v.hs = v_head_stride; c.v.ts = v_token_stride;
@@ -3004,12 +3024,43 @@ int fa_fp8_forward_mod(const void* q, const void* k, const void* v, void* o, flo
     c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
     c.mod.window_left = window_left; c.mod.window_right = window_right; c.mod.softcap = softcap; c.mod.sinks = sinks;
     c.mod.sink_heads = sink_heads;
-    return fp8_forward_impl("fa_fp8_forward_mod", c);
+    return fp8_forward_impl(who, c);
+}
+
+int fa_fp8_forward_mod(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
+        const float* v_descale, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_k, int64_t d,
+        int dtype, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_token_stride, int64_t k_batch_stride,
+        int64_t k_head_stride, int64_t k_token_stride, int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride,
+        int64_t o_batch_stride, int64_t o_head_stride, int64_t o_token_stride, int64_t q_descale_batch_stride,
+        int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace,
+        size_t workspace_bytes, void* stream, int64_t window_left, int64_t window_right, double softcap, const float* sinks,
+        int64_t sink_heads) {
+    return fp8_forward_mod_entry("fa_fp8_forward_mod", false, q, k, v, o, lse, q_descale, k_descale, v_descale, batch, heads_q,
+           heads_kv, seqlen_q, seqlen_k, d, dtype, q_batch_stride, q_head_stride, q_token_stride, k_batch_stride, k_head_stride,
+           k_token_stride, v_batch_stride, v_head_stride, v_token_stride, o_batch_stride, o_head_stride, o_token_stride,
+           q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale, workspace, workspace_bytes,
+           stream, window_left, window_right, softcap, sinks, sink_heads);
+}
+
+int fa_fp8_forward_hdim(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
+        const float* v_descale, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_k, int64_t head_dim,
+        int dtype, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_token_stride, int64_t k_batch_stride,
+        int64_t k_head_stride, int64_t k_token_stride, int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride,
+        int64_t o_batch_stride, int64_t o_head_stride, int64_t o_token_stride, int64_t q_descale_batch_stride,
+        int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace,
+        size_t workspace_bytes, void* stream, int64_t window_left, int64_t window_right, double softcap, const float* sinks,
+        int64_t sink_heads) {
+    return fp8_forward_mod_entry("fa_fp8_forward_hdim", true, q, k, v, o, lse, q_descale, k_descale, v_descale, batch, heads_q,
+           heads_kv, seqlen_q, seqlen_k, head_dim, dtype, q_batch_stride, q_head_stride, q_token_stride, k_batch_stride, k_head_stride,
+           k_token_stride, v_batch_stride, v_head_stride, v_token_stride, o_batch_stride, o_head_stride, o_token_stride,
+           q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale, workspace, workspace_bytes,
+           stream, window_left, window_right, softcap, sinks, sink_heads);
 }
 
 // ---- the packed and the paged form of the fp8 call: see include/fa_mi355x.h
 // One call of fa_fp8_forward_varlen, a family of its own.
 struct Fp8VarCall {
+    bool hdim = false;                     // as Fp8Call's
     fa::Fp8Mod mod;
     const void *q = nullptr, *k = nullptr, *v = nullptr;
     void* o = nullptr;
@@ -3043,7 +3094,8 @@ static int fp8_forward_varlen_impl(const char* who, const Fp8VarCall& c) {
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: total_q, total_k, max_seqlen_q and max_seqlen_k must lie in [0, 2^31) (got %lld, %lld, %lld, %lld)",
                     who, (long long)c.total_q, (long long)c.total_k, (long long)c.max_q, (long long)c.max_k);
     // (3) the head dim
-    if (c.d != 128) return fail(FA_ERR_UNSUPPORTED, "%s: head_dim %lld is not supported (128 only)", who, (long long)c.d);
+    if (const int rc = fp8_head_dim_check(who, c.d, c.hdim)) return rc;
+    const int64_t d = c.d;
     // (4) the heads ratio
     if (c.heads_q % c.heads_kv != 0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads_q=%lld must be a multiple of heads_kv=%lld", who, (long long)c.heads_q, (long long)c.heads_kv);
@@ -3087,9 +3139,9 @@ static int fp8_forward_varlen_impl(const char* who, const Fp8VarCall& c) {
         if (t.ts % 16 != 0 || hs % 16 != 0 || t.ps % 16 != 0)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (token %lld, head %lld, page %lld) must be multiples of 16 bytes", who, t.name,
                         (long long)t.ts, (long long)t.hs, (long long)t.ps);
-        if (t.ts < 128 || hs < 0 || t.ps < 0 || t.ts > kMaxStride || hs > kMaxStride || t.ps > kMaxStride)
-            return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (token %lld, head %lld, page %lld) must be >= 0, the token stride >= 128", who,
-                        t.name, (long long)t.ts, (long long)t.hs, (long long)t.ps);
+        if (t.ts < d || hs < 0 || t.ps < 0 || t.ts > kMaxStride || hs > kMaxStride || t.ps > kMaxStride)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (token %lld, head %lld, page %lld) must be >= 0, the token stride >= %lld", who,
+                        t.name, (long long)t.ts, (long long)t.hs, (long long)t.ps, (long long)d);
     }
     // (9) the span limits: q, packed k and one page are read through 32-bit buffer descriptors and offsets
     const int64_t kSpan = ((int64_t)1 << 31) - 1;
@@ -3114,16 +3166,16 @@ static int fp8_forward_varlen_impl(const char* who, const Fp8VarCall& c) {
     }
     fa::Fp8InVarArgs a;
     a.batch = c.batch; a.heads_q = c.heads_q; a.heads_kv = c.heads_kv; a.total_q = c.total_q; a.total_k = paged ? 0 : c.total_k;
-    a.max_q = c.max_q; a.max_k = c.max_k; a.max_blocks = c.max_blocks; a.num_blocks = c.num_blocks; a.page_size = c.ps;
-    const int64_t nqt = (c.max_q + 255) / 256, nbmax = (cap + 63) / 64, tiles = fa::fp8in_varlen_workspace_bytes(a) / 16384;
+    a.max_q = c.max_q; a.max_k = c.max_k; a.max_blocks = c.max_blocks; a.num_blocks = c.num_blocks; a.page_size = c.ps; a.d = d;
+    const int64_t nqt = (c.max_q + 255) / 256, nbmax = (cap + 63) / 64, tiles = fa::fp8in_varlen_workspace_bytes(a) / (128 * d);
     if ((nqt > 0 && c.batch * c.heads_q >= ((int64_t)1 << 31) / nqt) || (nbmax > 0 && c.batch * c.heads_kv >= ((int64_t)1 << 31) / nbmax) ||
         tiles >= ((int64_t)1 << 31))
         return fail(FA_ERR_UNSUPPORTED, "%s: span limit: batch * heads * tiles too large for one launch", who);
     // (10) the workspace
     const size_t need = fa::fp8in_varlen_workspace_bytes(a);
     if (!c.workspace || c.workspace_bytes < need)
-        return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes is too small (need %zu: fa_fp8_forward_varlen_workspace_bytes)", who,
-                    c.workspace ? c.workspace_bytes : (size_t)0, need);
+        return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes is too small (need %zu: fa_fp8_forward_varlen%s_workspace_bytes)", who,
+                    c.workspace ? c.workspace_bytes : (size_t)0, need, c.hdim ? "_hdim" : "");
     if ((uintptr_t)c.workspace % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
 
     a.q = c.q; a.k = c.k; a.v = c.v; a.o = c.o; a.lse = c.lse;
@@ -3134,19 +3186,30 @@ static int fp8_forward_varlen_impl(const char* who, const Fp8VarCall& c) {
     a.q_ts = c.q_ts; a.q_hs = c.heads_q > 1 ? c.q_hs : 0; a.k_ts = c.k_ts; a.k_hs = c.heads_kv > 1 ? c.k_hs : 0;
     a.v_ts = c.v_ts; a.v_hs = c.heads_kv > 1 ? c.v_hs : 0; a.k_ps = c.k_ps; a.v_ps = c.v_ps;
     a.causal = c.causal != 0; a.scale = (float)c.scale; a.workspace = c.workspace;
-    return launched(who, fa::launch_fp8_inputs_varlen_mod(a, c.mod, reinterpret_cast<hipStream_t>(c.stream)));
+    return launched(who, fa::launch_fp8_inputs_varlen_hdim(a, c.mod, reinterpret_cast<hipStream_t>(c.stream)));   // (d == 128: .._varlen_mod)
 }
 
-size_t fa_fp8_forward_varlen_workspace_bytes(int64_t batch, int64_t heads_kv, int64_t total_k, int64_t max_seqlen_k, int64_t max_blocks_per_seq,
-                                             int64_t page_block_size, int64_t d) {
+static size_t fp8_varlen_ws(int64_t batch, int64_t heads_kv, int64_t total_k, int64_t max_seqlen_k, int64_t max_blocks_per_seq,
+                            int64_t page_block_size, int64_t d, bool hdim) {
     const int64_t kInt = ((int64_t)1 << 31) - 1;
-    if (batch <= 0 || heads_kv <= 0 || total_k < 0 || max_seqlen_k < 0 || max_blocks_per_seq < 0 || page_block_size < 0 || d != 128) return 0;
+    if (batch <= 0 || heads_kv <= 0 || total_k < 0 || max_seqlen_k < 0 || max_blocks_per_seq < 0 || page_block_size < 0) return 0;
+    if (hdim ? (d != 64 && d != 128 && d != 256) : d != 128) return 0;
     if (batch > kInt || total_k > kInt || max_seqlen_k > kInt || max_blocks_per_seq > kInt || page_block_size > 65536) return 0;
     if (page_block_size % 16 != 0) return 0;
     fa::Fp8InVarArgs a;
     a.batch = batch; a.heads_kv = heads_kv; a.total_k = page_block_size ? 0 : total_k; a.max_k = max_seqlen_k;
-    a.max_blocks = page_block_size ? max_blocks_per_seq : 0; a.page_size = page_block_size;
+    a.max_blocks = page_block_size ? max_blocks_per_seq : 0; a.page_size = page_block_size; a.d = d;
     return fa::fp8in_varlen_workspace_bytes(a);
+}
+
+size_t fa_fp8_forward_varlen_workspace_bytes(int64_t batch, int64_t heads_kv, int64_t total_k, int64_t max_seqlen_k, int64_t max_blocks_per_seq,
+                                             int64_t page_block_size, int64_t d) {
+    return fp8_varlen_ws(batch, heads_kv, total_k, max_seqlen_k, max_blocks_per_seq, page_block_size, d, false);
+}
+
+size_t fa_fp8_forward_varlen_hdim_workspace_bytes(int64_t batch, int64_t heads_kv, int64_t total_k, int64_t max_seqlen_k,
+                                                  int64_t max_blocks_per_seq, int64_t page_block_size, int64_t head_dim) {
+    return fp8_varlen_ws(batch, heads_kv, total_k, max_seqlen_k, max_blocks_per_seq, page_block_size, head_dim, true);
 }
 
 int fa_fp8_forward_varlen(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
@@ -3170,17 +3233,17 @@ int fa_fp8_forward_varlen(const void* q, const void* k, const void* v, void* o, 
     return fp8_forward_varlen_impl("fa_fp8_forward_varlen", c);
 }
 
-int fa_fp8_forward_varlen_mod(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
-                              const float* v_descale, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, const int32_t* block_table,
-                              int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q,
-                              int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_token_stride, int64_t q_head_stride,
-                              int64_t k_token_stride, int64_t k_head_stride, int64_t v_token_stride, int64_t v_head_stride,
-                              int64_t max_blocks_per_seq, int64_t num_blocks, int64_t page_block_size, int64_t k_page_stride,
-                              int64_t v_page_stride, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
-                              int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace, size_t workspace_bytes,
-                              void* stream, int64_t window_left, int64_t window_right, double softcap, const float* sinks,
-                              int64_t sink_heads) {
+// the arguments of fa_fp8_forward_varlen_mod and fa_fp8_forward_varlen_hdim alike (hdim: the head dims 64, 128 and 256)
+static int fp8_forward_varlen_mod_entry(const char* who, bool hdim, const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
+        const float* v_descale, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, const int32_t* block_table, int64_t batch,
+        int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d,
+        int dtype, int64_t q_token_stride, int64_t q_head_stride, int64_t k_token_stride, int64_t k_head_stride,
+        int64_t v_token_stride, int64_t v_head_stride, int64_t max_blocks_per_seq, int64_t num_blocks, int64_t page_block_size,
+        int64_t k_page_stride, int64_t v_page_stride, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
+        int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace, size_t workspace_bytes, void* stream,
+        int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads) {
     Fp8VarCall c;
+    c.hdim = hdim;
     c.q = q; c.k = k; c.v = v; c.o = o; c.lse = lse; c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
     c.cu_q = cu_seqlens_q; c.cu_k = cu_seqlens_k; c.block_table = block_table;
     c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.total_q = total_q; c.total_k = total_k; c.max_q = max_seqlen_q;
@@ -3192,12 +3255,44 @@ int fa_fp8_forward_varlen_mod(const void* q, const void* k, const void* v, void*
     c.causal = causal; c.scale = softmax_scale; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
     c.mod.window_left = window_left; c.mod.window_right = window_right; c.mod.softcap = softcap; c.mod.sinks = sinks;
     c.mod.sink_heads = sink_heads;
-    return fp8_forward_varlen_impl("fa_fp8_forward_varlen_mod", c);
+    return fp8_forward_varlen_impl(who, c);
+}
+
+int fa_fp8_forward_varlen_mod(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
+        const float* v_descale, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, const int32_t* block_table, int64_t batch,
+        int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d,
+        int dtype, int64_t q_token_stride, int64_t q_head_stride, int64_t k_token_stride, int64_t k_head_stride,
+        int64_t v_token_stride, int64_t v_head_stride, int64_t max_blocks_per_seq, int64_t num_blocks, int64_t page_block_size,
+        int64_t k_page_stride, int64_t v_page_stride, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
+        int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace, size_t workspace_bytes, void* stream,
+        int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads) {
+    return fp8_forward_varlen_mod_entry("fa_fp8_forward_varlen_mod", false, q, k, v, o, lse, q_descale, k_descale, v_descale,
+           cu_seqlens_q, cu_seqlens_k, block_table, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype,
+           q_token_stride, q_head_stride, k_token_stride, k_head_stride, v_token_stride, v_head_stride, max_blocks_per_seq, num_blocks,
+           page_block_size, k_page_stride, v_page_stride, q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride,
+           causal, softmax_scale, workspace, workspace_bytes, stream, window_left, window_right, softcap, sinks, sink_heads);
+}
+
+int fa_fp8_forward_varlen_hdim(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
+        const float* v_descale, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, const int32_t* block_table, int64_t batch,
+        int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k,
+        int64_t head_dim, int dtype, int64_t q_token_stride, int64_t q_head_stride, int64_t k_token_stride, int64_t k_head_stride,
+        int64_t v_token_stride, int64_t v_head_stride, int64_t max_blocks_per_seq, int64_t num_blocks, int64_t page_block_size,
+        int64_t k_page_stride, int64_t v_page_stride, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
+        int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace, size_t workspace_bytes, void* stream,
+        int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads) {
+    return fp8_forward_varlen_mod_entry("fa_fp8_forward_varlen_hdim", true, q, k, v, o, lse, q_descale, k_descale, v_descale,
+           cu_seqlens_q, cu_seqlens_k, block_table, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, head_dim,
+           dtype, q_token_stride, q_head_stride, k_token_stride, k_head_stride, v_token_stride, v_head_stride, max_blocks_per_seq,
+           num_blocks, page_block_size, k_page_stride, v_page_stride, q_descale_batch_stride, k_descale_batch_stride,
+           v_descale_batch_stride, causal, softmax_scale, workspace, workspace_bytes, stream, window_left, window_right, softcap, sinks,
+           sink_heads);
 }
 
 // ---- fp8 KV-cache decoding with split-KV (e4m3 q over an e4m3 cache): see include/fa_mi355x.h
 // One call of fa_fp8_forward_kvcache, a family of its own.
 struct Fp8KvCall {
+    bool hdim = false;                     // as Fp8Call's
     fa::Fp8Mod mod;
     const void *q = nullptr, *k_cache = nullptr, *v_cache = nullptr;
     void* o = nullptr;
@@ -3261,7 +3356,8 @@ static int fp8_kvcache_check(const char* who, const Fp8KvCall& c, const Fp8StepC
     if (st && !c.cache_seqlens)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_seqlens is required (the lengths before the append)", who);
     // (2) the head dim and the dtypes
-    if (c.d != 128) return fail(FA_ERR_UNSUPPORTED, "%s: head_dim %lld is not supported (128 only)", who, (long long)c.d);
+    if (const int rc = fp8_head_dim_check(who, c.d, c.hdim)) return rc;
+    const int64_t d = c.d;
     if (st) {
         if (c.q_dtype != FA_DTYPE_F16 && c.q_dtype != FA_DTYPE_BF16 && c.q_dtype != FA_DTYPE_E4M3)
             return fail(FA_ERR_UNSUPPORTED, "%s: q_dtype must be f16, bf16 or FA_DTYPE_E4M3 (got code %d)", who, c.q_dtype);
@@ -3303,7 +3399,7 @@ static int fp8_kvcache_check(const char* who, const Fp8KvCall& c, const Fp8StepC
     if ((uintptr_t)c.lse % 4 != 0 || (uintptr_t)c.cache_seqlens % 4 != 0 || (uintptr_t)c.block_table % 4 != 0 || (uintptr_t)c.cache_batch_idx % 4 != 0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: lse, cache_seqlens, block_table and cache_batch_idx must be 4-byte aligned", who);
     if (st && !aligned16({st->k_new, st->v_new})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_new and v_new must be 16-byte aligned", who);
-    // (heads: the elements of a token's heads over 128, in bytes for a 16-bit q, k_new, v_new)
+    // (heads: the elements of a token's heads over d, in bytes for a 16-bit q, k_new, v_new)
     const struct { const char* name; int64_t bs, ts, heads; } ts[5] = {
         {"q", c.q_bs, c.q_ts, c.heads_q * qe}, {"k_cache", c.k_bs, c.k_ts, c.heads_kv}, {"v_cache", c.v_bs, c.v_ts, c.heads_kv},
         {"k_new", st ? st->kn_bs : 0, st ? st->kn_ts : 0, c.heads_kv * qe}, {"v_new", st ? st->vn_bs : 0, st ? st->vn_ts : 0, c.heads_kv * qe}};
@@ -3312,9 +3408,9 @@ static int fp8_kvcache_check(const char* who, const Fp8KvCall& c, const Fp8StepC
         if (t.ts % 16 != 0 || t.bs % 16 != 0)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (batch %lld, token %lld) must be multiples of 16 bytes", who, t.name,
                         (long long)t.bs, (long long)t.ts);
-        if (t.ts < t.heads * 128 || t.ts > kMaxStride || t.bs < 0 || t.bs > kMaxStride)
-            return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (batch %lld, token %lld) must be >= 0, the token stride >= heads * 128 = %lld",
-                        who, t.name, (long long)t.bs, (long long)t.ts, (long long)(t.heads * 128));
+        if (t.ts < t.heads * d || t.ts > kMaxStride || t.bs < 0 || t.bs > kMaxStride)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (batch %lld, token %lld) must be >= 0, the token stride >= heads * %lld = %lld",
+                        who, t.name, (long long)t.bs, (long long)t.ts, (long long)d, (long long)(t.heads * d));
     }
     if (st && st->q8_out) {
         if (qe == 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: q8_out goes with a 16-bit q only (an e4m3 q is used in place)", who);
@@ -3404,13 +3500,14 @@ static int fp8_kvcache_check(const char* who, const Fp8KvCall& c, const Fp8StepC
     if (const int rc = fp8_mod_check(who, c.mod, c.heads_q)) return rc;
     S = fp8_kv_splits_mod(c.batch, c.heads_q, c.heads_kv, c.seqlen_q, c.cache_len, c.num_splits, c.causal, c.mod);
     // (10) the workspace
-    need = fa::kv_workspace_bytes(c.batch, c.heads_q, c.seqlen_q, 128, (int)S);
+    need = fa::kv_workspace_bytes(c.batch, c.heads_q, c.seqlen_q, d, (int)S);
     if (st) need += fa::fp8kv_step_prep_bytes(c.batch, c.heads_q, c.seqlen_q, qe == 2 && !st->q8_out);
     if (need > 0) {
         if (!c.workspace || c.workspace_bytes < need)
             return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes is too small (need %zu: %s%s)", who,
                         c.workspace ? c.workspace_bytes : (size_t)0, need,
-                        st ? "fa_fp8_kvcache_step_workspace_bytes" : "fa_fp8_forward_kvcache_workspace_bytes", !st && c.mod.any() ? "_mod" : "");
+                        st ? "fa_fp8_kvcache_step_workspace_bytes" : c.hdim ? "fa_fp8_forward_kvcache_hdim_workspace_bytes" : "fa_fp8_forward_kvcache_workspace_bytes",
+                        !st && !c.hdim && c.mod.any() ? "_mod" : "");
         if ((uintptr_t)c.workspace % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
     }
     return FA_OK;
@@ -3426,7 +3523,7 @@ static fa::Fp8KvArgs fp8_kvcache_args(const Fp8KvCall& c, int64_t S) {
     a.cache_batch = c.cache_batch; a.dtype = c.dtype;
     a.q_bs = c.q_bs; a.q_ts = c.q_ts; a.kc_bs = c.k_bs; a.kc_ts = c.k_ts; a.vc_bs = c.v_bs; a.vc_ts = c.v_ts;
     a.table_row_stride = c.table_rs; a.num_blocks = c.num_blocks; a.page_size = c.ps;
-    a.causal = c.causal != 0; a.scale = (float)c.scale; a.num_splits = S; a.workspace = c.workspace;
+    a.causal = c.causal != 0; a.scale = (float)c.scale; a.num_splits = S; a.workspace = c.workspace; a.d = c.d;
     return a;
 }
 
@@ -3436,7 +3533,7 @@ static int fp8_kvcache_impl(const char* who, const Fp8KvCall& c) {
     size_t need = 0;
     if (const int rc = fp8_kvcache_check(who, c, nullptr, empty, S, need)) return rc;
     if (empty) return FA_OK;
-    return launched(who, fa::launch_fp8_kvcache_mod(fp8_kvcache_args(c, S), c.mod, reinterpret_cast<hipStream_t>(c.stream)));
+    return launched(who, fa::launch_fp8_kvcache_hdim(fp8_kvcache_args(c, S), c.mod, reinterpret_cast<hipStream_t>(c.stream)));   // (d == 128: .._mod)
 }
 
 size_t fa_fp8_forward_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t d,
@@ -3471,26 +3568,35 @@ int fa_fp8_forward_kvcache(const void* q, const void* k_cache, const void* v_cac
 size_t fa_fp8_forward_kvcache_workspace_bytes_mod(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
                                                   int64_t d, int64_t num_splits, int causal, int64_t window_left, int64_t window_right,
                                                   int with_sinks) {
-    if (!kv_ws_args_ok(batch, heads_q, heads_kv, seqlen_q, cache_len, d, num_splits) || d != 128 || window_left < -1 || window_right < -1)
-        return 0;
+    if (d != 128) return 0;
+    return fa_fp8_forward_kvcache_hdim_workspace_bytes(batch, heads_q, heads_kv, seqlen_q, cache_len, d, num_splits, causal, window_left,
+                                                       window_right, with_sinks);
+}
+
+// the decode partials follow kv_workspace_bytes at the head dim; the split rule counts keys and is the same at every head dim
+size_t fa_fp8_forward_kvcache_hdim_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
+                                                   int64_t head_dim, int64_t num_splits, int causal, int64_t window_left,
+                                                   int64_t window_right, int with_sinks) {
+    if (!kv_ws_args_ok(batch, heads_q, heads_kv, seqlen_q, cache_len, head_dim, num_splits) || window_left < -1 || window_right < -1) return 0;
+    if (head_dim != 64 && head_dim != 128 && head_dim != 256) return 0;
     fa::Fp8Mod m;
     m.window_left = window_left; m.window_right = window_right;
     int64_t S = fp8_kv_splits(batch, heads_q, heads_kv, seqlen_q, fa::fp8kv_split_len(cache_len, seqlen_q, causal, m), num_splits);
     if (with_sinks && S < 2) S = 2;
-    return fa::kv_workspace_bytes(batch, heads_q, seqlen_q, 128, (int)S);
+    return fa::kv_workspace_bytes(batch, heads_q, seqlen_q, head_dim, (int)S);
 }
 
-int fa_fp8_forward_kvcache_mod(const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const float* q_descale,
-                               const float* k_descale, const float* v_descale, const int32_t* cache_seqlens, const int32_t* block_table,
-                               const int32_t* cache_batch_idx, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q,
-                               int64_t cache_len, int64_t cache_batch, int64_t d, int dtype, int q_dtype, int cache_dtype,
-                               int64_t q_batch_stride, int64_t q_token_stride, int64_t k_batch_stride, int64_t k_token_stride,
-                               int64_t v_batch_stride, int64_t v_token_stride, int64_t block_table_row_stride, int64_t num_blocks,
-                               int64_t page_block_size, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
-                               int64_t v_descale_batch_stride, int causal, double softmax_scale, int64_t num_splits, void* workspace,
-                               size_t workspace_bytes, void* stream, int64_t window_left, int64_t window_right, double softcap,
-                               const float* sinks, int64_t sink_heads) {
+// the arguments of fa_fp8_forward_kvcache_mod and fa_fp8_forward_kvcache_hdim alike (hdim: the head dims 64, 128 and 256)
+static int fp8_forward_kvcache_mod_entry(const char* who, bool hdim, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const float* q_descale, const float* k_descale,
+        const float* v_descale, const int32_t* cache_seqlens, const int32_t* block_table, const int32_t* cache_batch_idx,
+        int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t cache_batch, int64_t d,
+        int dtype, int q_dtype, int cache_dtype, int64_t q_batch_stride, int64_t q_token_stride, int64_t k_batch_stride,
+        int64_t k_token_stride, int64_t v_batch_stride, int64_t v_token_stride, int64_t block_table_row_stride, int64_t num_blocks,
+        int64_t page_block_size, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride, int64_t v_descale_batch_stride,
+        int causal, double softmax_scale, int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream,
+        int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads) {
     Fp8KvCall c;
+    c.hdim = hdim;
     c.q = q; c.k_cache = k_cache; c.v_cache = v_cache; c.o = o; c.lse = lse;
     c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
     c.cache_seqlens = cache_seqlens; c.block_table = block_table; c.cache_batch_idx = cache_batch_idx;
@@ -3504,7 +3610,39 @@ int fa_fp8_forward_kvcache_mod(const void* q, const void* k_cache, const void* v
     c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
     c.mod.window_left = window_left; c.mod.window_right = window_right; c.mod.softcap = softcap; c.mod.sinks = sinks;
     c.mod.sink_heads = sink_heads;
-    return fp8_kvcache_impl("fa_fp8_forward_kvcache_mod", c);
+    return fp8_kvcache_impl(who, c);
+}
+
+int fa_fp8_forward_kvcache_mod(const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const float* q_descale, const float* k_descale,
+        const float* v_descale, const int32_t* cache_seqlens, const int32_t* block_table, const int32_t* cache_batch_idx,
+        int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t cache_batch, int64_t d,
+        int dtype, int q_dtype, int cache_dtype, int64_t q_batch_stride, int64_t q_token_stride, int64_t k_batch_stride,
+        int64_t k_token_stride, int64_t v_batch_stride, int64_t v_token_stride, int64_t block_table_row_stride, int64_t num_blocks,
+        int64_t page_block_size, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride, int64_t v_descale_batch_stride,
+        int causal, double softmax_scale, int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream,
+        int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads) {
+    return fp8_forward_kvcache_mod_entry("fa_fp8_forward_kvcache_mod", false, q, k_cache, v_cache, o, lse, q_descale, k_descale,
+           v_descale, cache_seqlens, block_table, cache_batch_idx, batch, heads_q, heads_kv, seqlen_q, cache_len, cache_batch, d, dtype,
+           q_dtype, cache_dtype, q_batch_stride, q_token_stride, k_batch_stride, k_token_stride, v_batch_stride, v_token_stride,
+           block_table_row_stride, num_blocks, page_block_size, q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride,
+           causal, softmax_scale, num_splits, workspace, workspace_bytes, stream, window_left, window_right, softcap, sinks,
+           sink_heads);
+}
+
+int fa_fp8_forward_kvcache_hdim(const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const float* q_descale, const float* k_descale,
+        const float* v_descale, const int32_t* cache_seqlens, const int32_t* block_table, const int32_t* cache_batch_idx,
+        int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t cache_batch, int64_t head_dim,
+        int dtype, int q_dtype, int cache_dtype, int64_t q_batch_stride, int64_t q_token_stride, int64_t k_batch_stride,
+        int64_t k_token_stride, int64_t v_batch_stride, int64_t v_token_stride, int64_t block_table_row_stride, int64_t num_blocks,
+        int64_t page_block_size, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride, int64_t v_descale_batch_stride,
+        int causal, double softmax_scale, int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream,
+        int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads) {
+    return fp8_forward_kvcache_mod_entry("fa_fp8_forward_kvcache_hdim", true, q, k_cache, v_cache, o, lse, q_descale, k_descale,
+           v_descale, cache_seqlens, block_table, cache_batch_idx, batch, heads_q, heads_kv, seqlen_q, cache_len, cache_batch, head_dim,
+           dtype, q_dtype, cache_dtype, q_batch_stride, q_token_stride, k_batch_stride, k_token_stride, v_batch_stride, v_token_stride,
+           block_table_row_stride, num_blocks, page_block_size, q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride,
+           causal, softmax_scale, num_splits, workspace, workspace_bytes, stream, window_left, window_right, softcap, sinks,
+           sink_heads);
 }
 
 // ---- the fp8 decode step (append, rotary and q quantise in front of fa_fp8_forward_kvcache_mod): see include/fa_mi355x.h

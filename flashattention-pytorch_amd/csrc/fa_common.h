@@ -142,6 +142,11 @@ template <> struct TileSwz<256> {   // 512-byte rows: the bank of a chunk is its
 template <> struct TileSwz<64> {
     static __device__ __forceinline__ int off(int row, int ch) { return 128 * row + 16 * (ch ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3))); }
 };
+// 64-byte rows (the e4m3 K tile of head dim 64): four rows share a 256-byte bank line, so the chunk index turns with row / 4 and
+// the 16 rows of a row-wise ds_read_b128 quarter (rows r, r + 4, r + 8, r + 12 in one line position) land on four different chunks
+template <> struct TileSwz<32> {
+    static __device__ __forceinline__ int off(int row, int ch) { return 64 * row + 16 * (ch ^ ((row >> 2) & 3)); }
+};
 typedef short lds_s16x4_t __attribute__((ext_vector_type(4)));
 // ds_read_b64_tr_b16: per 16-lane group a 4-row x 16-column block of 16-bit elements, delivered column-major
 // (lane i of the group gets column i of the 4 rows; lane 4q+p supplies the address of row q, columns 4p..4p+3).

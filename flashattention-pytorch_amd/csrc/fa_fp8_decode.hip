@@ -77,7 +77,10 @@ __device__ __forceinline__ void transpose4x4(const uint32_t (&x)[4], uint32_t (&
 }
 
 // byte offset of 16-byte chunk ch of head-dim row `row` in the V^T image: 64-byte rows, 16 bytes of padding after every four
-constexpr int kVtBytes = 128 * 64 + 32 * 16;
+// Head dims 64 and 256 (fp8kv_split_mod_kernel<Tag, PAGED, D>) KEEP this padding rule: the image is D such
+// rows, the d = 64 lanes write 8-byte halves of a chunk and the d = 256 lanes two rows 128 apart, both at the same row offsets.
+constexpr int kVtRowBytes = 64 + 4;                      // a head dim's share of the image: D rows take kVtRowBytes * D bytes
+constexpr int kVtBytes = kVtRowBytes * 128;
 __device__ __forceinline__ int vt_off(int row, int ch) { return 64 * row + 16 * (row >> 2) + 16 * ch; }
 
 template <typename Tag, bool PAGED>
@@ -339,10 +342,10 @@ struct Fp8KvMod {
 //   softcap  fwd_fp8in_mod_kernel's (fa_fp8_inputs.hip): the capped score, in log2 units, replaces the raw product before the
 //            mask, and the factor of what follows is 1.
 // Sinks are not this kernel's: they join in kv_combine_kernel<Tag, true>, once per row.
-template <typename Tag, bool PAGED>
-__global__ __launch_bounds__(64, 2) void fp8kv_split_mod_kernel(const Fp8KvParams p, const Fp8KvMod md) {
-    constexpr int D = 128, KT = 64, NDV = D / 32;
-    __shared__ __attribute__((aligned(16))) char vt[kVtBytes];   // V^T tile, [head dim][64 key bytes in P's key order]
+template <typename Tag, bool PAGED, int D = 128>
+__global__ __launch_bounds__(64, D == 256 ? 1 : 2) void fp8kv_split_mod_kernel(const Fp8KvParams p, const Fp8KvMod md) {
+    constexpr int KT = 64, NDV = D / 32, NMQ = D / 64;
+    __shared__ __attribute__((aligned(16))) char vt[kVtRowBytes * D];   // V^T tile, [head dim][64 key bytes in P's key order]
     const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
     const int s = blockIdx.x, S = gridDim.x;
     const int hk = blockIdx.y % p.hkv, rt = blockIdx.y / p.hkv, b = blockIdx.z;
@@ -372,11 +375,11 @@ __global__ __launch_bounds__(64, 2) void fp8kv_split_mod_kernel(const Fp8KvParam
     const int qi = valid ? pr / G : qlo, hd = hk * G + (valid ? pr - qi * G : 0);
     const int rhi = min(min(qi + coff + md.wr, lk - 1), kend - 1), rlo = qi + coff - md.wl;   // the row sees keys [rlo, rhi]
 
-    i32x8_t qb[2];
+    i32x8_t qb[NMQ];
     {
         const uint8_t* qp = p.q + (long long)b * p.q_bs + (long long)qi * p.q_ts + hd * D + 32 * h;
 #pragma unroll
-        for (int M = 0; M < 2; ++M) {
+        for (int M = 0; M < NMQ; ++M) {
             const u32x4 a0 = *reinterpret_cast<const u32x4*>(qp + 64 * M), a1 = *reinterpret_cast<const u32x4*>(qp + 64 * M + 16);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -449,7 +452,7 @@ __global__ __launch_bounds__(64, 2) void fp8kv_split_mod_kernel(const Fp8KvParam
 #pragma unroll
             for (int i = 0; i < 16; ++i) sacc[kb][i] = 0.f;
 #pragma unroll
-            for (int M = 0; M < 2; ++M) {
+            for (int M = 0; M < NMQ; ++M) {
                 const u32x4 a0 = *reinterpret_cast<const u32x4*>(kp + 64 * M), a1 = *reinterpret_cast<const u32x4*>(kp + 64 * M + 16);
                 i32x8_t ka;
 #pragma unroll
@@ -462,27 +465,38 @@ __global__ __launch_bounds__(64, 2) void fp8kv_split_mod_kernel(const Fp8KvParam
         }
 
         // ---- V -> V^T through registers: 16 keys x 4 head dims a lane and key block, four 4 x 4 byte transposes, one 16-byte chunk
-        // a head dim (the previous tile's operand reads were issued before these writes: one wave, LDS in order)
+        // a head dim (the previous tile's operand reads were issued before these writes: one wave, LDS in order).
+        // D = 256: 32 lanes cover half a key row, so a lane takes the dwords at head dims 4 r and 128 + 4 r (DW = 2 rounds).
+        // D = 64: 16 lanes cover a key row; lane r takes head dims 4 (r & 15) of the key groups j = 2 (r >> 4), 2 (r >> 4) + 1
+        // only, and writes that half (8 bytes) of the head dim's chunk: all 64 lanes load, no key byte twice.
+        constexpr int DW = D == 256 ? 2 : 1, NJ = D == 64 ? 2 : 4;
+        const int rd = D == 64 ? (r & 15) : r, j0 = D == 64 ? 2 * (r >> 4) : 0;
+#pragma unroll
+        for (int dw = 0; dw < DW; ++dw)
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
-            uint32_t t[4][4];                                     // [j][dd]: head dim 4 r + dd of keys 32 kb + 4 h + 8 j + (0 .. 3)
+            uint32_t t[NJ][4];                                    // [j][dd]: head dim 128 dw + 4 rd + dd of keys 32 kb + 4 h + 8 (j0 + j) + (0 .. 3)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const long long base = vbase[2 * kb + (j >> 1)];  // wave-uniform
+            for (int jj = 0; jj < NJ; ++jj) {
+                const int j = j0 + jj;
+                const long long base = D == 64 ? ((j >> 1) ? vbase[2 * kb + 1] : vbase[2 * kb]) : vbase[2 * kb + (jj >> 1)];   // (D != 64: wave-uniform)
                 uint32_t x[4];
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     const int pos = 4 * h + 8 * (j & 1) + c;      // the key's place in its 16-key group
                     const bool ok = FULL || (base >= 0 && k0 + 32 * kb + 16 * (j >> 1) + pos < kend);
-                    const uint8_t* vp = ok ? p.vc + base + pos * p.vc_ts + hk * D + 4 * r : nowhere;
+                    const uint8_t* vp = ok ? p.vc + base + pos * p.vc_ts + hk * D + 128 * dw + 4 * rd : nowhere;
                     const uint32_t y = *reinterpret_cast<const uint32_t*>(vp);
                     x[c] = ok ? y : 0u;
                 }
-                transpose4x4(x, t[j]);
+                transpose4x4(x, t[jj]);
             }
 #pragma unroll
-            for (int dd = 0; dd < 4; ++dd)
-                *reinterpret_cast<u32x4*>(vt + vt_off(4 * r + dd, 2 * h + kb)) = u32x4{t[0][dd], t[1][dd], t[2][dd], t[3][dd]};
+            for (int dd = 0; dd < 4; ++dd) {
+                char* chunk = vt + vt_off(128 * dw + 4 * rd + dd, 2 * h + kb);
+                if constexpr (D == 64) *reinterpret_cast<u32x2*>(chunk + 4 * j0) = u32x2{t[0][dd], t[1][dd]};
+                else *reinterpret_cast<u32x4*>(chunk) = u32x4{t[0][dd], t[1][dd], t[2][dd], t[3][dd]};
+            }
         }
         };
         if (full) front(std::true_type{});
@@ -636,9 +650,25 @@ static hipError_t launch_fp8_kvcache_t(const Fp8KvArgs& a, const Fp8KvMod* md, c
     // workspace (S > 1): the O partials, then the lse partials, each rounded up to 256 bytes (kv_workspace_bytes)
     const size_t q_rows = (size_t)a.batch * a.heads_q * a.seqlen_q;
     p.po = (float*)a.workspace;
-    p.plse = S > 1 ? (float*)((char*)a.workspace + ((q_rows * S * 128 * 4 + 255) & ~(size_t)255)) : nullptr;
+    p.plse = S > 1 ? (float*)((char*)a.workspace + ((q_rows * S * (size_t)a.d * 4 + 255) & ~(size_t)255)) : nullptr;
     const dim3 grid((unsigned)S, (unsigned)(fp8kv_row_tiles(a.heads_q, a.heads_kv, a.seqlen_q) * p.hkv), (unsigned)a.batch);
-    if (md) {
+    if (a.d != 128) {                                    // launch_fp8_kvcache_hdim: md is never null here
+        route_hit(ROUTE_FP8KV_SPLIT_HDIM);
+        ProfScope ps(K_FP8KV_SPLIT_HDIM, st);
+        const bool paged = a.block_table != nullptr;
+        auto launch = [&](auto d_c) {
+            constexpr int DD = decltype(d_c)::value;
+            if (a.dtype == 2) {
+                if (paged) hipLaunchKernelGGL((fp8kv_split_mod_kernel<bf16_tag, true, DD>), grid, dim3(64), 0, st, p, *md);
+                else hipLaunchKernelGGL((fp8kv_split_mod_kernel<bf16_tag, false, DD>), grid, dim3(64), 0, st, p, *md);
+            } else {
+                if (paged) hipLaunchKernelGGL((fp8kv_split_mod_kernel<f16_tag, true, DD>), grid, dim3(64), 0, st, p, *md);
+                else hipLaunchKernelGGL((fp8kv_split_mod_kernel<f16_tag, false, DD>), grid, dim3(64), 0, st, p, *md);
+            }
+        };
+        if (a.d == 64) launch(std::integral_constant<int, 64>{});
+        else launch(std::integral_constant<int, 256>{});
+    } else if (md) {
         route_hit(ROUTE_FP8KV_SPLIT_MOD);
         ProfScope ps(K_FP8KV_SPLIT_MOD, st);
         const bool paged = a.block_table != nullptr;
@@ -662,20 +692,35 @@ static hipError_t launch_fp8_kvcache_t(const Fp8KvArgs& a, const Fp8KvMod* md, c
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || S == 1) return e;
-    if (sinks) return launch_kv_combine_sink(a.o, a.lse, p.po, p.plse, a.batch, a.heads_q, a.seqlen_q, 128, a.dtype, S, sinks, sink_heads, st);
-    return launch_kv_combine(a.o, a.lse, p.po, p.plse, a.batch, a.heads_q, a.seqlen_q, 128, a.dtype, S, st);
+    if (sinks) return launch_kv_combine_sink(a.o, a.lse, p.po, p.plse, a.batch, a.heads_q, a.seqlen_q, a.d, a.dtype, S, sinks, sink_heads, st);
+    return launch_kv_combine(a.o, a.lse, p.po, p.plse, a.batch, a.heads_q, a.seqlen_q, a.d, a.dtype, S, st);
 }
 
 hipError_t launch_fp8_kvcache(const Fp8KvArgs& a, hipStream_t st) { return launch_fp8_kvcache_t(a, nullptr, nullptr, 0, st); }
 
-hipError_t launch_fp8_kvcache_mod(const Fp8KvArgs& a, const Fp8Mod& m, hipStream_t st) {
-    if (!m.any()) return launch_fp8_kvcache(a, st);     // the parent call, launch for launch
-    if (m.sinks && a.num_splits < 2) return hipErrorInvalidValue;   // (the C layer raises a sink call's S to 2: the sink joins in the combine)
+// the featured kernel's arguments of an Fp8Mod (one that is not any(): no window, no cap)
+static Fp8KvMod fp8kv_mod_args(const Fp8KvArgs& a, const Fp8Mod& m) {
     Fp8KvMod md;
     md.wl = m.window_left >= 0 ? (int)std::min<int64_t>(m.window_left, kWinNone) : kWinNone;
     md.wr = a.causal ? 0 : (m.window_right >= 0 ? (int)std::min<int64_t>(m.window_right, kWinNone) : kWinNone);
     md.cap_k = m.softcap > 0.0 ? (float)(2.0 / m.softcap) : 0.f;
     md.cap2 = m.softcap > 0.0 ? (float)(m.softcap * 1.4426950408889634) : 0.f;
+    return md;
+}
+
+hipError_t launch_fp8_kvcache_mod(const Fp8KvArgs& a, const Fp8Mod& m, hipStream_t st) {
+    if (!m.any()) return launch_fp8_kvcache(a, st);     // the parent call, launch for launch
+    if (m.sinks && a.num_splits < 2) return hipErrorInvalidValue;   // (the C layer raises a sink call's S to 2: the sink joins in the combine)
+    const Fp8KvMod md = fp8kv_mod_args(a, m);
+    return launch_fp8_kvcache_t(a, &md, m.sinks, (int)(m.sink_heads > 0 ? m.sink_heads : 1), st);
+}
+
+// Head dims 64 and 256 (fa_fp8_forward_kvcache_hdim): every such call, featured or not, runs
+// fp8kv_split_mod_kernel<Tag, PAGED, D>, then kv_combine_kernel at d.  d = 128 is the call above.
+hipError_t launch_fp8_kvcache_hdim(const Fp8KvArgs& a, const Fp8Mod& m, hipStream_t st) {
+    if (a.d == 128) return launch_fp8_kvcache_mod(a, m, st);
+    if (m.sinks && a.num_splits < 2) return hipErrorInvalidValue;
+    const Fp8KvMod md = fp8kv_mod_args(a, m);
     return launch_fp8_kvcache_t(a, &md, m.sinks, (int)(m.sink_heads > 0 ? m.sink_heads : 1), st);
 }
 

@@ -38,8 +38,10 @@
 // The packed and the paged form of the call (fa_fp8_forward_varlen) follow the padded one below: fp8in_vt_varlen_kernel,
 // fwd_fp8in_varlen_kernel.
 // A sliding window, a softcap and attention sinks (fa_fp8_forward_mod, fa_fp8_forward_varlen_mod) are a
-// kernel of their own at the end of the file, fwd_fp8in_mod_kernel, for all three forms: a call without them launches the kernels
+// kernel of their own after those, fwd_fp8in_mod_kernel, for all three forms: a call without them launches the kernels
 // above as before.
+// Head dims 64 and 256 (fa_fp8_forward_hdim, fa_fp8_forward_varlen_hdim) are the last part of the file:
+// fwd_fp8in_hdim_kernel and fp8in_vt_hdim_kernel serve every call at those widths; everything before them stays d = 128.
 #include <algorithm>
 
 #include "fa_common.h"
@@ -262,8 +264,8 @@ __global__ __launch_bounds__(512, 2) void fwd_fp8in_kernel(const Fp8InKernelArgs
     if (qrow < nq && h == 0) a.lse[(size_t)bh * nq + qrow] = dead ? -INFINITY : (m_run + log2f(l_tot)) * 0.6931471805599453f;
 }
 
-size_t fp8in_workspace_bytes(int64_t units_kv, int64_t nk) {
-    return (size_t)units_kv * (size_t)((nk + 127) / 128) * 128 * 128 + 256;   // V^T tiles and a pad
+size_t fp8in_workspace_bytes(int64_t units_kv, int64_t nk, int64_t d) {
+    return (size_t)units_kv * (size_t)((nk + 127) / 128) * (size_t)d * 128 + 256;   // V^T tiles (d rows of 128 key bytes) and a pad
 }
 
 // the transposer's launch and the attention kernel's arguments: what fa_fp8_forward and fa_fp8_forward_mod share on the host
@@ -403,20 +405,24 @@ __global__ __launch_bounds__(256) void fp8in_vt_varlen_kernel(const uint8_t* __r
 // through the constant address space so that it is a scalar load: as a plain global pointer it became a vector load (the DMA's
 // asm statements clobber memory, so hipcc does not prove the table unchanged) whose whole latency stood in front of every tile
 // (profiles/fp8_varlen.md).
+// Head dim D (fwd_fp8in_mod_kernel at 64 and 256): a piece is RPP = 1024 / D rows, 16 or 4, which still divide 16 | ps, and a
+// wave issues D / 64 of them; the pieces of a wave lie 8 RPP rows apart, a multiple of 16, so one voff_k serves them all.
 typedef const int __attribute__((address_space(4)))* fp8in_const_int_p;
+template <int D = 128>
 __device__ __forceinline__ void fp8in_stage_k_paged(const ExPage& pg, const int* __restrict__ trow, int last, const uint8_t* kh, char* ktile,
                                                     int row0, int nk, int voff_k, int w, int k_ts) {
+    constexpr int RPP = 1024 / D;
     const unsigned tk = lds_addr_of(ktile);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
+    for (int j = 0; j < D / 64; ++j) {
         const int pc = w + 8 * j;
-        const int key = __builtin_amdgcn_readfirstlane(row0 + 8 * pc);
-        const int rows = min(8, nk - key);               // <= 0: the piece lies past the sequence
+        const int key = __builtin_amdgcn_readfirstlane(row0 + RPP * pc);
+        const int rows = min(RPP, nk - key);             // <= 0: the piece lies past the sequence
         const int slot = min(pg_slot(pg, key), last);    // no entry past ceil(nk / ps) is read
         const int page = ((fp8in_const_int_p)trow)[slot];
         const bool ok = rows > 0 && (unsigned)page < (unsigned)pg.num_blocks;
         const long long ko = ok ? (long long)page * pg.kps + (long long)(key - slot * pg.ps) * k_ts : 0ll;
-        dma16_issue(make_rsrc_s(kh + ko, ok ? (unsigned)(rows - 1) * (unsigned)k_ts + 128u : 0u), tk + pc * 1024, voff_k, 0);
+        dma16_issue(make_rsrc_s(kh + ko, ok ? (unsigned)(rows - 1) * (unsigned)k_ts + (unsigned)D : 0u), tk + pc * 1024, voff_k, 0);
     }
 }
 
@@ -606,8 +612,20 @@ int64_t fp8in_varlen_tiles_per_head(const Fp8InVarArgs& c) {
 }
 
 size_t fp8in_varlen_workspace_bytes(const Fp8InVarArgs& c) {
-    return (size_t)c.heads_kv * (size_t)fp8in_varlen_tiles_per_head(c) * 128 * 128 + 256;   // V^T tiles and a pad
+    return (size_t)c.heads_kv * (size_t)fp8in_varlen_tiles_per_head(c) * (size_t)c.d * 128 + 256;   // V^T tiles and a pad
 }
+
+// the transposer of the head dims 64 and 256 (at the end of the file)
+struct Fp8InVtArgs {
+    const uint8_t* v;
+    uint8_t* v8t;
+    const int* cu_k;
+    int nk, total_k, max_k, nb, ntile, nt_head, nt_seq, hkv;   // nb: the grid's 64-key blocks a (sequence, K/V head)
+    long long v_bs, v_hs, v_ts;
+    ExPage pg;
+};
+static Fp8InVtArgs fp8in_vt_hdim_args(const Fp8InVarArgs& c, const ExPage& pg, int cap, int nbmax, int nt_head, int nt_seq);
+template <int MODE> static hipError_t fp8in_launch_vt_hdim(const Fp8InVtArgs& a, int d, unsigned grid, hipStream_t st);
 
 // the transposer's launch and the attention kernel's arguments: what fa_fp8_forward_varlen and fa_fp8_forward_varlen_mod share
 // on the host (c.max_q > 0)
@@ -621,7 +639,11 @@ template <bool PAGED> static hipError_t fp8in_varlen_front(const Fp8InVarArgs& c
         pg.max_blocks = (int)c.max_blocks; pg.num_blocks = (int)c.num_blocks; pg.ps = (int)c.page_size;
         pg.ps16m = kv_magic((int)(c.page_size / 16));
     }
-    if (nbmax > 0) {
+    if (nbmax > 0 && c.d != 128) {                        // (fa_fp8_forward_varlen_hdim: the transposer at the end of the file)
+        const hipError_t e = fp8in_launch_vt_hdim<PAGED ? 2 : 1>(fp8in_vt_hdim_args(c, pg, (int)cap, nbmax, nt_head, nt_seq), (int)c.d,
+                                                                 (unsigned)(c.batch * c.heads_kv * nbmax), st);
+        if (e != hipSuccess) return e;
+    } else if (nbmax > 0) {
         ProfScope ps(K_FP8IN_VT_VARLEN, st);
         hipLaunchKernelGGL(fp8in_vt_varlen_kernel<PAGED>, dim3((unsigned)(c.batch * c.heads_kv * nbmax)), dim3(256), 0, st,
                            (const uint8_t*)c.v, (uint8_t*)c.workspace, c.cu_k, (int)c.total_k, (int)cap, nbmax, nt_head, nt_seq,
@@ -637,8 +659,8 @@ template <bool PAGED> static hipError_t fp8in_varlen_front(const Fp8InVarArgs& c
     a.total_q = (int)c.total_q; a.total_k = (int)c.total_k; a.max_q = (int)c.max_q; a.max_k = (int)cap;
     a.hq = (int)c.heads_q; a.hkv = (int)c.heads_kv; a.group = (int)(c.heads_q / c.heads_kv);
     a.nqt = nqt; a.nt_head = nt_head; a.nt_seq = nt_seq;
-    a.q_ts = (int)c.q_ts; a.k_ts = (int)c.k_ts; a.o_ts = (int)(c.heads_q * 128);
-    a.q_hs = c.q_hs; a.k_hs = c.k_hs; a.o_hs = 128;
+    a.q_ts = (int)c.q_ts; a.k_ts = (int)c.k_ts; a.o_ts = (int)(c.heads_q * c.d);
+    a.q_hs = c.q_hs; a.k_hs = c.k_hs; a.o_hs = c.d;
     a.pg = pg;
     a.c_log2 = c.scale * 1.4426950408889634f;
     return hipSuccess;
@@ -977,6 +999,375 @@ hipError_t launch_fp8_inputs_varlen_mod(const Fp8InVarArgs& c, const Fp8Mod& m, 
     ProfScope ps(K_FP8IN_FWD_VARLEN_MOD, st);
     const unsigned grid = (unsigned)(c.batch * c.heads_q * a.var.nqt);
     return c.block_table ? launch_fp8in_mod<2>(a, c.dtype, grid, st) : launch_fp8in_mod<1>(a, c.dtype, grid, st);
+}
+
+// ---- Head dims 64 and 256 (fa_fp8_forward_hdim, fa_fp8_forward_varlen_hdim) --------------------------------
+// Every call at d = 64 / 256, with or without a window, a softcap or sinks, runs fwd_fp8in_hdim_kernel<Tag, MODE, D>:
+// fwd_fp8in_mod_kernel's text (DUPLICATED rather than given a head-dim parameter: as one template its d = 128 instantiation kept
+// its instructions but not their order, and d = 128 runs the code it ran) with NM = NDV = D / 32 fragments and accumulators, D / 64 score instructions a 32-key block in ascending head-dim order,
+// a K tile of 128 rows of D bytes (TileSwz<D / 2> and the LDS-DMA geometry of a 16-bit tile of D / 2 elements) and a V^T tile of D
+// rows of 128 key bytes, in which the key permutation of a row is what it is at 128.  Two buffers of both are 32 KiB at 64 and
+// 128 KiB at 256: one workgroup a CU there, which the registers ask for as well (eight waves a workgroup are two a SIMD, 256
+// registers each).  At 256 the 128 output accumulators, 64 score accumulators and 32 q registers do not fit them (68 bytes of
+// scratch), so the softmax step is a 64-key half of the staged tile (KBS = 2: 32 score accumulators, no scratch); the
+// arithmetic is that of a 64-key tile (profiles/fp8_hdim.md has the register report of both choices).
+// The transposer is one kernel for the three forms: fp8in_vt_kernel's / fp8in_vt_varlen_kernel's loads and key permutation, D
+// rows in LDS, and the block's D x 64 bytes leave as 4 D 16-byte chunks over the 256 threads.
+template <typename Tag, int MODE, int D>
+__global__ __launch_bounds__(512, 2) void fwd_fp8in_hdim_kernel(const Fp8InModKernelArgs am) {
+    constexpr bool VAR = MODE != 0, PAGED = MODE == 2;
+    constexpr int BM = 256, BN = 128, KB = 4, NM = D / 32, NDV = D / 32;
+    constexpr int KBS = D == 256 ? 2 : KB, BNS = 32 * KBS;   // key blocks and keys of a softmax step
+    constexpr int TILE = BN * D;                         // bytes of a K tile and of a V^T tile alike
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // [2 buffers][K8 tile | V8^T tile]
+    typedef int i32x8_t __attribute__((ext_vector_type(8)));
+
+    // ---- the sequence and its tensors: fwd_fp8in_kernel's (MODE 0) or fwd_fp8in_varlen_kernel's prologue
+    const int nqt = VAR ? am.var.nqt : am.pad.nqt, hq = VAR ? am.var.hq : am.pad.hq, group = VAR ? am.var.group : am.pad.group;
+    const int L = xcd_remap(blockIdx.x, gridDim.x);
+    const int bh = L / nqt;                              // b * H_q + head
+    int qt = L - bh * nqt;
+    if (am.rev) qt = nqt - 1 - qt;
+    const int b = bh / hq, hd = bh - b * hq, hk = hd / group;
+    const int q0 = qt * BM;
+    int nq, nk, qs = 0, ks = 0;
+    if constexpr (VAR) {
+        seq_span(am.var.cu_q, b, am.var.total_q, am.var.max_q, qs, nq);
+        if (PAGED) nk = paged_len(am.var.cu_k, b, am.var.max_k);
+        else seq_span(am.var.cu_k, b, am.var.total_k, am.var.max_k, ks, nk);
+        if (q0 >= nq) return;                            // the padded grid: no row of this tile belongs to the sequence
+    } else {
+        nq = am.pad.nq; nk = am.pad.nk;
+    }
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const int qrow = q0 + 32 * w + r;
+    const int shift = nk - nq;                           // row i sits at key position i + shift
+    const int q_ts = VAR ? am.var.q_ts : am.pad.q_ts, k_ts = VAR ? am.var.k_ts : am.pad.k_ts, o_ts = VAR ? am.var.o_ts : am.pad.o_ts;
+    const uint8_t* qbase;
+    const uint8_t* kh;                                   // the K rows of this K/V head (PAGED: of page 0)
+    const uint8_t* vbase;
+    uint16_t* obase;
+    const float *qds, *kds, *vds;
+    int qds_bs, kds_bs, vds_bs, ntile_b;
+    if constexpr (VAR) {
+        qbase = am.var.q + (size_t)qs * q_ts + (size_t)hd * am.var.q_hs;
+        kh = am.var.k + (size_t)hk * am.var.k_hs + (PAGED ? (size_t)0 : (size_t)ks * k_ts);
+        ntile_b = (nk + BN - 1) / BN;
+        vbase = am.var.v8t + ((size_t)hk * am.var.nt_head + fp8in_tile_start<PAGED>(b, ks, am.var.nt_seq)) * TILE;
+        obase = am.var.o + (size_t)qs * o_ts + (size_t)hd * am.var.o_hs;
+        qds = am.var.qds; kds = am.var.kds; vds = am.var.vds;
+        qds_bs = am.var.qds_bs; kds_bs = am.var.kds_bs; vds_bs = am.var.vds_bs;
+    } else {
+        qbase = am.pad.q + (size_t)b * am.pad.q_bs + (size_t)hd * am.pad.q_hs;
+        kh = am.pad.k + (size_t)b * am.pad.k_bs + (size_t)hk * am.pad.k_hs;
+        ntile_b = am.pad.ntile;
+        vbase = am.pad.v8t + (size_t)(b * am.pad.hkv + hk) * am.pad.ntile * TILE;
+        obase = am.pad.o + (size_t)b * am.pad.o_bs + (size_t)hd * am.pad.o_hs;
+        qds = am.pad.qds; kds = am.pad.kds; vds = am.pad.vds;
+        qds_bs = am.pad.qds_bs; kds_bs = am.pad.kds_bs; vds_bs = am.pad.vds_bs;
+    }
+
+    // q rows >= nq and k rows >= nk lie outside the descriptors: they read as zeros, whatever the memory behind them holds
+    const buf_rsrc_t q_rs = make_rsrc(qbase, (unsigned)(nq - 1) * (unsigned)q_ts + D);
+    u32x4 qf[NM];
+#pragma unroll
+    for (int m = 0; m < NM; ++m) qf[m] = __builtin_amdgcn_raw_buffer_load_b128(q_rs, qrow * q_ts + 32 * m + 16 * h, 0, 0);
+    const float qd = qds ? qds[(size_t)b * qds_bs + hk] : 1.f;
+    const float kd = kds ? kds[(size_t)b * kds_bs + hk] : 1.f;
+    const float vd = vds ? vds[(size_t)b * vds_bs + hk] : 1.f;
+    const float f = ((VAR ? am.var.c_log2 : am.pad.c_log2) * qd) * kd;   // the one score factor of this workgroup, > 0
+    const bool capped = am.cap2 != 0.f;
+    const float ck = f * am.cap_k, cap2 = am.cap2;
+    const float fe = capped ? 1.f : f;                   // the factor of what the accumulators hold after the cap
+
+    // the 128-key tiles [t_lo, t_hi) some row of the workgroup sees, from its first row's lower and its last row's upper bound
+    const int wl = am.wl, wr = am.wr;
+    const int kfirst = max(0, q0 + shift - wl), kend = max(0, min(nk, q0 + BM + shift + wr));
+    const int t_lo = kfirst / BN, t_hi = kend > kfirst ? (kend + BN - 1) / BN : t_lo;
+    [[maybe_unused]] const rsrc_s_t k_rs = make_rsrc_s(kh, nk > 0 ? (unsigned)(nk - 1) * (unsigned)k_ts + D : 0u);
+    const rsrc_s_t v_rs = make_rsrc_s(vbase, (unsigned)ntile_b * TILE);
+    const int kstride = k_ts >> 1;                       // the STRIDED helpers count 2-byte elements
+    const int voff_k = dma_lane_voff<D / 2, true>(lane, w, D / 2, kstride);   // D-byte rows: the geometry of a 16-bit d = D / 2 tile
+    const int voff_v = dma_lane_voff<64>(lane, w);
+    [[maybe_unused]] const int* trow = PAGED ? am.var.pg.table + (size_t)b * am.var.pg.max_blocks : nullptr;
+    [[maybe_unused]] const int pg_last = PAGED ? pg_slot(am.var.pg, max(nk - 1, 0)) : 0;   // no entry past ceil(nk / ps) is read
+    auto stage = [&](int buf, int t) {
+        char* b_ = smem + buf * 2 * TILE;
+        if constexpr (PAGED) {
+            fp8in_stage_k_paged<D>(am.var.pg, trow, pg_last, kh, b_, t * BN, nk, voff_k, w, k_ts);
+        } else {
+            dma_stage_tile<D / 2, BN, 8, true>(k_rs, b_, t * BN, voff_k, w, D / 2, 0, kstride);
+        }
+        dma_stage_tile<64, D, 8>(v_rs, b_ + TILE, t * D, voff_v, w);   // V^T tile t = rows D t .. of the [tile][d row] matrix
+    };
+
+    f32x16 oacc[NDV];
+#pragma unroll
+    for (int t = 0; t < NDV; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) oacc[t][i] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;                // running max in log2 units of the (capped) scaled score
+
+    if (t_hi > t_lo) {
+        stage(0, t_lo);
+        dma_wait_all();
+        __syncthreads();
+    }
+    // the tiles some row of the wave sees: its first row's lower bound, its last row's upper bound
+    const int pos_w = q0 + 32 * w + shift;               // the position of the wave's first row
+    const int last_w = pos_w + 31 + wr;
+    const int tw_lo = max(t_lo, max(0, pos_w - wl) / BN), tw_hi = last_w < 0 ? t_lo : min(t_hi, last_w / BN + 1);
+    const int lim_hi = min(qrow + shift + wr, nk - 1), lim_lo = qrow + shift - wl;   // this row sees keys [lim_lo, lim_hi]
+
+    for (int t = t_lo; t < t_hi; ++t) {
+        const int k0 = t * BN, cur = (t - t_lo) & 1;
+        if (t + 1 < t_hi) stage(cur ^ 1, t + 1);
+        if (t >= tw_lo && t < tw_hi) {                   // (wave-uniform)
+        const char* Kt = smem + cur * 2 * TILE;
+        const char* Vt = Kt + TILE;
+        // the softmax step: the whole staged tile (KBS = KB, one trip), at D = 256 its two 64-key halves one after the other
+        // (kept a loop: unrolled, hipcc hoists the second half's operand reads over the first and spills 448 bytes)
+#pragma nounroll
+        for (int sub = 0; sub < KB / KBS; ++sub) {
+        const int kbo = KBS * sub, k0s = k0 + 32 * kbo;  // the step's first key block and first key
+        f32x16 sacc[KBS];
+#pragma unroll
+        for (int kb = 0; kb < KBS; ++kb) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) sacc[kb][i] = 0.f;
+#pragma unroll
+            for (int M = 0; M < NM / 2; ++M) {
+                const u32x4 a0 = *reinterpret_cast<const u32x4*>(Kt + TileSwz<D / 2>::off(32 * (kbo + kb) + r, 4 * M + h));
+                const u32x4 a1 = *reinterpret_cast<const u32x4*>(Kt + TileSwz<D / 2>::off(32 * (kbo + kb) + r, 4 * M + 2 + h));
+                const i32x8_t ka = {(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], (int)a1[0], (int)a1[1], (int)a1[2], (int)a1[3]};
+                const u32x4 b0_ = qf[2 * M], b1_ = qf[2 * M + 1];
+                const i32x8_t qb = {(int)b0_[0], (int)b0_[1], (int)b0_[2], (int)b0_[3], (int)b1_[0], (int)b1_[1], (int)b1_[2], (int)b1_[3]};
+                sacc[kb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ka, qb, sacc[kb], 0, 0, 0, 127, 0, 127);
+            }
+        }
+        // the softcap first (before the mask), in log2 units: one exp2 and one rcp an element
+        if (capped) {
+#pragma unroll
+            for (int kb = 0; kb < KBS; ++kb)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float rr = __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(sacc[kb][i] * ck) + 1.f);
+                    sacc[kb][i] = fmaf(rr, -2.f * cap2, cap2);
+                }
+        }
+        // the mask, only where a band edge or the end of the keys crosses this tile for some row of the wave
+        const bool need_hi = (k0s + BNS - 1 > pos_w + wr) || (k0s + BNS > nk);
+        const bool need_lo = k0s < pos_w + 31 - wl;
+        float mx = -INFINITY;
+#pragma unroll
+        for (int kb = 0; kb < KBS; ++kb) {
+            if (need_hi) {
+                const int thr = lim_hi - (k0s + 32 * kb + 4 * h);
+#pragma unroll
+                for (int i = 0; i < 16; ++i)
+                    if ((i & 3) + 8 * (i >> 2) > thr) sacc[kb][i] = -INFINITY;
+            }
+            if (need_lo) {
+                const int thr = lim_lo - (k0s + 32 * kb + 4 * h);
+#pragma unroll
+                for (int i = 0; i < 16; ++i)
+                    if ((i & 3) + 8 * (i >> 2) < thr) sacc[kb][i] = -INFINITY;
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) mx = fmaxf(mx, sacc[kb][i]);
+        }
+        mx = mx * fe;
+        mx = fmaxf(mx, wave_half_swap(mx));
+        const float m_new = fmaxf(m_run, mx);
+        float m_use;
+        if (__any(m_new - m_run > 8.0f) != 0) {   // lazy rescale (fwd_fp8in_kernel); a row's first visible key: inf > 8
+            m_use = m_new;
+            const float alpha = __builtin_amdgcn_exp2f(m_run - ((m_new == -INFINITY) ? 0.f : m_new));
+            m_run = m_new;
+            l_run *= alpha;
+#pragma unroll
+            for (int t2 = 0; t2 < NDV; ++t2)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) oacc[t2][i] *= alpha;
+        } else {
+            m_use = m_run;
+        }
+        if (m_use == -INFINITY) m_use = 0.f;      // a row without a visible key so far: p = exp2(-inf) = 0, not exp2(-inf + inf)
+        float rs = 0.f;
+#pragma unroll
+        for (int g = 0; g < KBS / 2; ++g) {
+            const int gt = kbo / 2 + g;                  // the 64-key group of the staged tile
+            i32x8_t pb;
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {
+                const int kb = 2 * g + kk;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float p = __builtin_amdgcn_exp2f(fmaf(sacc[kb][i], fe, -m_use));   // (-inf stays -inf: fe > 0)
+                    sacc[kb][i] = p;
+                    rs += p;
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    int wd = 0;
+                    wd = __builtin_amdgcn_cvt_pk_fp8_f32(sacc[kb][4 * j + 0], sacc[kb][4 * j + 1], wd, false);
+                    wd = __builtin_amdgcn_cvt_pk_fp8_f32(sacc[kb][4 * j + 2], sacc[kb][4 * j + 3], wd, true);
+                    pb[4 * kk + j] = wd;
+                }
+            }
+#pragma unroll
+            for (int dvb = 0; dvb < NDV; ++dvb) {
+                const u32x4 a0 = *reinterpret_cast<const u32x4*>(Vt + TileSwz<64>::off(32 * dvb + r, 4 * gt + h));
+                const u32x4 a1 = *reinterpret_cast<const u32x4*>(Vt + TileSwz<64>::off(32 * dvb + r, 4 * gt + 2 + h));
+                const i32x8_t va = {(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], (int)a1[0], (int)a1[1], (int)a1[2], (int)a1[3]};
+                oacc[dvb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(va, pb, oacc[dvb], 0, 0, 0, 127, 0, 127);
+            }
+        }
+        l_run += rs;
+        }
+        }
+        dma_wait_all();
+        __syncthreads();
+    }
+
+    // every wave is past the last barrier: the K / V buffers are dead (fwd_fp8in_mod_kernel's epilogue).  The sink joins here.
+    const float l_tot = l_run + wave_half_swap(l_run);
+    const float snk = am.sinks ? am.sinks[hd] : -INFINITY;   // (workgroup-uniform)
+    bool dead;
+    float inv, lse_v;
+    if (snk != -INFINITY) {
+        float iv;
+        ex_sink_norm(m_run * 0.6931471805599453f, l_tot, snk, iv, lse_v);
+        dead = false;                                    // (no visible key: iv = 0, lse = sink)
+        inv = vd * iv;
+    } else {
+        dead = l_tot == 0.f;                             // no visible key: o = 0, lse = -inf (a NaN l is not dead: it propagates)
+        inv = vd * (1.f / l_tot);                        // v_descale once, with 1 / l
+        lse_v = dead ? -INFINITY : (m_run + log2f(l_tot)) * 0.6931471805599453f;
+    }
+    u32x2 vals[NDV * 4];
+#pragma unroll
+    for (int dvb = 0; dvb < NDV; ++dvb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            float y[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) y[j] = dead ? 0.f : oacc[dvb][4 * g + j] * inv;
+            vals[4 * dvb + g][0] = pack2_rn<Tag>(y[0], y[1]);
+            vals[4 * dvb + g][1] = pack2_rn<Tag>(y[2], y[3]);
+        }
+    store_rows_via_lds<D, true>(smem + w * 32 * D * 2, vals, obase, q0 + 32 * w, nq, lane, D, -1, o_ts);
+    if (qrow < nq && h == 0) {
+        if constexpr (VAR) am.var.lse[(size_t)hd * am.var.total_q + qs + qrow] = lse_v;
+        else am.pad.lse[(size_t)bh * nq + qrow] = lse_v;
+    }
+}
+
+template <int MODE, int D>
+static hipError_t launch_fp8in_hdim(const Fp8InModKernelArgs& a, int dtype, unsigned grid, hipStream_t st) {
+    const size_t smem = 2 * 2 * 128 * D;
+    auto launch = [&](auto kern) -> hipError_t {
+        hipError_t e2 = ensure_dynamic_smem(reinterpret_cast<const void*>(kern), (int)smem);
+        if (e2 != hipSuccess) return e2;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, st, a);
+        return hipGetLastError();
+    };
+    return dtype == 2 ? launch(fwd_fp8in_hdim_kernel<bf16_tag, MODE, D>) : launch(fwd_fp8in_hdim_kernel<f16_tag, MODE, D>);
+}
+
+template <int D, int MODE>
+__global__ __launch_bounds__(256) void fp8in_vt_hdim_kernel(const Fp8InVtArgs a) {
+    constexpr bool VAR = MODE != 0, PAGED = MODE == 2;
+    constexpr int CPR = D / 16, PER = (64 * CPR) / 256;   // 16-byte chunks per row / per thread
+    __shared__ __attribute__((aligned(16))) uint8_t tr[D * 64];   // [d row][permuted key position]
+    const int unit = blockIdx.x / a.nb, blk = blockIdx.x - unit * a.nb, row0 = blk * 64;
+    const int b = unit / a.hkv, hk = unit - b * a.hkv;
+    int ks = 0, nk = a.nk;
+    if constexpr (VAR) {
+        if (PAGED) nk = paged_len(a.cu_k, b, a.max_k);
+        else seq_span(a.cu_k, b, a.total_k, a.max_k, ks, nk);
+    }
+    const int nb = (nk + 63) >> 6;
+    if (blk >= nb) return;                               // (the padded grid of the packed and the paged form)
+    const uint8_t* src = a.v + (size_t)hk * a.v_hs + (VAR ? (PAGED ? (size_t)0 : (size_t)ks * a.v_ts) : (size_t)b * a.v_bs);
+    [[maybe_unused]] const int* trow = PAGED ? a.pg.table + (size_t)b * a.pg.max_blocks : nullptr;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const int c = threadIdx.x + 256 * i, key = c / CPR, ch = c % CPR;   // key within the 64-key block
+        u32x4 x = u32x4{0u, 0u, 0u, 0u};
+        if (row0 + key < nk) {
+            if constexpr (PAGED) {
+                // a 16-key group never straddles a page (ps % 16 == 0), and key < nk keeps the slot below ceil(nk / ps)
+                const int slot = pg_slot(a.pg, row0 + key), page = trow[slot];
+                if ((unsigned)page < (unsigned)a.pg.num_blocks)
+                    x = *reinterpret_cast<const u32x4*>(src + (size_t)page * a.pg.vps + (size_t)(row0 + key - slot * a.pg.ps) * a.v_ts + 16 * ch);
+            } else {
+                x = *reinterpret_cast<const u32x4*>(src + (size_t)(row0 + key) * a.v_ts + 16 * ch);
+            }
+        }
+        const int wlo = key & 31, pos = 32 * (key >> 5) + 16 * ((wlo >> 2) & 1) + (wlo & 3) + 4 * (wlo >> 3);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) tr[(16 * ch + j) * 64 + pos] = (uint8_t)((x[j >> 2] >> (8 * (j & 3))) & 0xff);
+    }
+    __syncthreads();
+    const size_t tile = VAR ? (size_t)hk * a.nt_head + fp8in_tile_start<PAGED>(b, ks, a.nt_seq) + (blk >> 1)
+                            : (size_t)unit * a.ntile + (blk >> 1);
+#pragma unroll
+    for (int i = 0; i < D / 64; ++i) {
+        const int c = threadIdx.x + 256 * i, r = c >> 2, q4 = c & 3;   // d row r, 16-byte quarter q4 of its 64 key bytes
+        uint8_t* dst = a.v8t + (tile * D + r) * 128 + 64 * (blk & 1) + 16 * q4;
+        *reinterpret_cast<u32x4*>(dst) = *reinterpret_cast<const u32x4*>(tr + r * 64 + 16 * q4);
+        // an odd block count leaves the second half of the last tile unwritten by any block: zero it (those keys lie past nk)
+        if ((nb & 1) && blk == nb - 1) *reinterpret_cast<u32x4*>(dst + 64) = u32x4{0u, 0u, 0u, 0u};
+    }
+}
+
+static Fp8InVtArgs fp8in_vt_hdim_args(const Fp8InVarArgs& c, const ExPage& pg, int cap, int nbmax, int nt_head, int nt_seq) {
+    Fp8InVtArgs a{};
+    a.v = (const uint8_t*)c.v; a.v8t = (uint8_t*)c.workspace; a.cu_k = c.cu_k;
+    a.total_k = (int)c.total_k; a.max_k = cap; a.nb = nbmax; a.nt_head = nt_head; a.nt_seq = nt_seq; a.hkv = (int)c.heads_kv;
+    a.v_hs = c.v_hs; a.v_ts = c.v_ts; a.pg = pg;
+    return a;
+}
+
+template <int MODE> static hipError_t fp8in_launch_vt_hdim(const Fp8InVtArgs& a, int d, unsigned grid, hipStream_t st) {
+    ProfScope ps(MODE == 0 ? K_FP8IN_VT : K_FP8IN_VT_VARLEN, st);
+    if (d == 64) hipLaunchKernelGGL((fp8in_vt_hdim_kernel<64, MODE>), dim3(grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((fp8in_vt_hdim_kernel<256, MODE>), dim3(grid), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_fp8_inputs_hdim(const Fp8InArgs& c, const Fp8Mod& m, hipStream_t st) {
+    if (c.d == 128) return launch_fp8_inputs_mod(c, m, st);   // the parent call, launch for launch
+    const int nb = (int)((c.nk + 63) / 64);
+    Fp8InVtArgs v{};
+    v.v = (const uint8_t*)c.v; v.v8t = (uint8_t*)c.workspace;
+    v.nk = (int)c.nk; v.nb = nb; v.ntile = (int)((c.nk + 127) / 128); v.hkv = (int)c.heads_kv;
+    v.v_bs = c.v_bs; v.v_hs = c.v_hs; v.v_ts = c.v_ts;
+    const hipError_t e = fp8in_launch_vt_hdim<0>(v, (int)c.d, (unsigned)(c.batch * c.heads_kv * nb), st);
+    if (e != hipSuccess) return e;
+    Fp8InModKernelArgs a{};
+    a.pad = fp8in_kernel_args(c);
+    fp8in_mod_fill(a, m, c.causal != 0);
+    route_hit(ROUTE_FP8IN_FWD_HDIM);
+    ProfScope ps(K_FP8IN_FWD_HDIM, st);
+    const unsigned grid = (unsigned)(c.batch * c.heads_q * a.pad.nqt);
+    return c.d == 64 ? launch_fp8in_hdim<0, 64>(a, c.dtype, grid, st) : launch_fp8in_hdim<0, 256>(a, c.dtype, grid, st);
+}
+
+hipError_t launch_fp8_inputs_varlen_hdim(const Fp8InVarArgs& c, const Fp8Mod& m, hipStream_t st) {
+    if (c.d == 128) return launch_fp8_inputs_varlen_mod(c, m, st);
+    if (c.max_q == 0) return hipSuccess;                 // no sequence has a query: nothing is written
+    Fp8InModKernelArgs a{};
+    const hipError_t e = c.block_table ? fp8in_varlen_front<true>(c, st, a.var) : fp8in_varlen_front<false>(c, st, a.var);
+    if (e != hipSuccess) return e;
+    fp8in_mod_fill(a, m, c.causal != 0);
+    route_hit(ROUTE_FP8IN_FWD_VARLEN_HDIM);
+    ProfScope ps(K_FP8IN_FWD_VARLEN_HDIM, st);
+    const unsigned grid = (unsigned)(c.batch * c.heads_q * a.var.nqt);
+    if (c.d == 64) return c.block_table ? launch_fp8in_hdim<2, 64>(a, c.dtype, grid, st) : launch_fp8in_hdim<1, 64>(a, c.dtype, grid, st);
+    return c.block_table ? launch_fp8in_hdim<2, 256>(a, c.dtype, grid, st) : launch_fp8in_hdim<1, 256>(a, c.dtype, grid, st);
 }
 
 }  // namespace fa

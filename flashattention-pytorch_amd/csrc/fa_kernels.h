@@ -44,7 +44,8 @@ struct BwdArgs {
 enum KernelId { K_FWD_F32 = 0, K_BWD_DELTA, K_BWD_DKDV_F32, K_BWD_DQ_F32, K_FWD_MFMA, K_BWD_MFMA, K_BWD_DQ_CVT, K_BWD_DQ_MFMA,
                 K_FP8_QUANT, K_FWD_FP8, K_EX_FWD, K_EX_BWD, K_KV_GROUP_SUM, K_FP8IN_VT, K_FP8IN_FWD, K_FP8IN_VT_VARLEN,
                 K_FP8IN_FWD_VARLEN, K_IDX_PACK, K_IDX_LOGITS, K_IDX_TOPK, K_FP8KV_SPLIT, K_FP8Q_AMAX, K_FP8Q_QUANT, K_FP8Q_FUSED,
-                K_FP8IN_FWD_MOD, K_FP8IN_FWD_VARLEN_MOD, K_FP8KV_SPLIT_MOD, K_FP8KV_STEP_PREP, K_COUNT };
+                K_FP8IN_FWD_MOD, K_FP8IN_FWD_VARLEN_MOD, K_FP8KV_SPLIT_MOD, K_FP8KV_STEP_PREP, K_FP8IN_FWD_HDIM,
+                K_FP8IN_FWD_VARLEN_HDIM, K_FP8KV_SPLIT_HDIM, K_COUNT };
 void prof_begin(int id, hipStream_t st);
 void prof_end(int id, hipStream_t st);
 struct ProfScope {
@@ -68,9 +69,11 @@ int set_option(const char* name, int value);   // returns 0, or -1 for an unknow
 // library, it does not guess from timing.  "dkdv_stream": the dS-storing dK/dV stream kernel, "dkdv_lean": its lean form;
 // "fp8_quant_fused", "fp8_quant_two_pass", "fp8_quant_static": the routes of the fp8 quantiser (fa_fp8_quantize.hip);
 // "fp8in_fwd_mod", "fp8in_fwd_varlen_mod", "fp8kv_split_mod": the featured kernels of the fp8 calls (window, softcap, sinks);
-// "fp8kv_step_prep": the append / rotary / q quantise launch of the fp8 decode step (fa_fp8_step.hip).
+// "fp8kv_step_prep": the append / rotary / q quantise launch of the fp8 decode step (fa_fp8_step.hip);
+// "fp8in_fwd_hdim", "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim": the fp8 calls at head dim 64 or 256 (the _hdim entry points).
 enum RouteId { ROUTE_DKDV_STREAM = 0, ROUTE_DKDV_LEAN, ROUTE_FP8Q_FUSED, ROUTE_FP8Q_TWO_PASS, ROUTE_FP8Q_STATIC, ROUTE_FP8IN_FWD_MOD,
-               ROUTE_FP8IN_FWD_VARLEN_MOD, ROUTE_FP8KV_SPLIT_MOD, ROUTE_FP8KV_STEP_PREP, ROUTE_COUNT };
+               ROUTE_FP8IN_FWD_VARLEN_MOD, ROUTE_FP8KV_SPLIT_MOD, ROUTE_FP8KV_STEP_PREP, ROUTE_FP8IN_FWD_HDIM,
+               ROUTE_FP8IN_FWD_VARLEN_HDIM, ROUTE_FP8KV_SPLIT_HDIM, ROUTE_COUNT };
 void route_hit(int id);
 
 // exact-f32 kernels (fa_generic.hip): any dtype, d <= 256
@@ -452,9 +455,10 @@ struct Fp8InArgs {
     int64_t q_bs = 0, q_hs = 0, q_ts = 0, k_bs = 0, k_hs = 0, k_ts = 0, v_bs = 0, v_hs = 0, v_ts = 0, o_bs = 0, o_hs = 0, o_ts = 0;
     int causal = 0;
     float scale = 0.f;
-    void* workspace = nullptr;                              // fp8in_workspace_bytes(batch * heads_kv, nk)
+    void* workspace = nullptr;                              // fp8in_workspace_bytes(batch * heads_kv, nk, d)
+    int64_t d = 128;                                        // the head dim: 128, or 64 / 256 through launch_fp8_inputs_hdim alone
 };
-size_t fp8in_workspace_bytes(int64_t units_kv, int64_t nk);
+size_t fp8in_workspace_bytes(int64_t units_kv, int64_t nk, int64_t d = 128);
 hipError_t launch_fp8_inputs(const Fp8InArgs& a, hipStream_t st);
 
 // What the _mod entry points of the three fp8 calls add (fa_fp8_forward_mod, fa_fp8_forward_varlen_mod,
@@ -469,6 +473,10 @@ struct Fp8Mod {
     bool any() const { return window_left >= 0 || window_right >= 0 || softcap > 0.0 || sinks != nullptr; }
 };
 hipError_t launch_fp8_inputs_mod(const Fp8InArgs& a, const Fp8Mod& m, hipStream_t st);
+// The _hdim entry points of the three fp8 calls (fa_fp8_forward_hdim, fa_fp8_forward_varlen_hdim, fa_fp8_forward_kvcache_hdim):
+// a.d in {64, 128, 256}.  a.d == 128 is the _mod launcher above, launch for launch; 64 and 256 run the head-dim instantiations of
+// the featured kernels (fwd_fp8in_hdim_kernel<.., D>, fp8kv_split_mod_kernel<.., D>) whether or not the Fp8Mod is any().
+hipError_t launch_fp8_inputs_hdim(const Fp8InArgs& a, const Fp8Mod& m, hipStream_t st);
 
 // The packed and the paged form (fa_fp8_forward_varlen): q (total_q, heads_q, 128) and o, lse as the varlen calls lay them out;
 // k, v (total_k, heads_kv, 128), or with block_table the pools (num_blocks, page_size, heads_kv, 128).  Strides in bytes.
@@ -487,11 +495,13 @@ struct Fp8InVarArgs {
     int causal = 0;
     float scale = 0.f;
     void* workspace = nullptr;                              // fp8in_varlen_workspace_bytes
+    int64_t d = 128;                                        // the head dim: 128, or 64 / 256 through launch_fp8_inputs_varlen_hdim alone
 };
 // from batch, heads_kv, total_k (packed: page_size == 0) or max_k, max_blocks, page_size (paged) alone
 size_t fp8in_varlen_workspace_bytes(const Fp8InVarArgs& a);
 hipError_t launch_fp8_inputs_varlen(const Fp8InVarArgs& a, hipStream_t st);
 hipError_t launch_fp8_inputs_varlen_mod(const Fp8InVarArgs& a, const Fp8Mod& m, hipStream_t st);
+hipError_t launch_fp8_inputs_varlen_hdim(const Fp8InVarArgs& a, const Fp8Mod& m, hipStream_t st);
 
 // fp8 KV-cache decoding (fa_fp8_decode.hip; fa_fp8_forward_kvcache): e4m3 q (batch, seqlen_q, heads_q, 128) over an e4m3 cache
 // (cache_batch, cache_len, heads_kv, 128), or with block_table the pools (num_blocks, page_size, heads_kv, 128).  Strides in bytes;
@@ -510,7 +520,8 @@ struct Fp8KvArgs {
     int causal = 0;
     float scale = 0.f;
     int64_t num_splits = 1;                                 // >= 1 (the C layer resolves 0 through fp8kv_num_splits)
-    void* workspace = nullptr;                              // kv_workspace_bytes(batch, heads_q, seqlen_q, 128, num_splits)
+    void* workspace = nullptr;                              // kv_workspace_bytes(batch, heads_q, seqlen_q, d, num_splits)
+    int64_t d = 128;                                        // the head dim: 128, or 64 / 256 through launch_fp8_kvcache_hdim alone
 };
 int fp8kv_num_splits(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len);
 hipError_t launch_fp8_kvcache(const Fp8KvArgs& a, hipStream_t st);
@@ -520,6 +531,7 @@ hipError_t launch_fp8_kvcache(const Fp8KvArgs& a, hipStream_t st);
 // the sink joins in the combine, which such a call always runs.
 int64_t fp8kv_split_len(int64_t cache_len, int64_t seqlen_q, int causal, const Fp8Mod& m);
 hipError_t launch_fp8_kvcache_mod(const Fp8KvArgs& a, const Fp8Mod& m, hipStream_t st);
+hipError_t launch_fp8_kvcache_hdim(const Fp8KvArgs& a, const Fp8Mod& m, hipStream_t st);
 // The fp8 decode step (fa_fp8_step.hip; fa_fp8_kvcache_step): one launch of fp8kv_step_prep_kernel appends the new tokens to the
 // e4m3 cache, rotates and quantises q into a q8 buffer and writes len_eff[b] = L_b + seqlen_new; then launch_fp8_kvcache_mod runs
 // on kv with q = the q8 buffer and cache_seqlens = len_eff.  kv.q / kv.q_bs / kv.q_ts describe the caller's q (bytes), in in_dtype;

@@ -62,6 +62,8 @@ EXPORTED_C_SYMBOLS = (
     "fa_fp8_forward_mod", "fa_fp8_forward_varlen_mod", "fa_fp8_forward_kvcache_mod", "fa_fp8_forward_kvcache_workspace_bytes_mod",
     "fa_fp8_quantize", "fa_fp8_quantize_workspace_bytes",
     "fa_fp8_kvcache_step", "fa_fp8_kvcache_step_workspace_bytes",
+    "fa_fp8_forward_hdim", "fa_fp8_forward_varlen_hdim", "fa_fp8_forward_kvcache_hdim",
+    "fa_fp8_forward_hdim_workspace_bytes", "fa_fp8_forward_varlen_hdim_workspace_bytes", "fa_fp8_forward_kvcache_hdim_workspace_bytes",
 )
 
 
@@ -240,6 +242,16 @@ _sig("fa_fp8_kvcache_step", _SIGNATURES["fa_fp8_forward_kvcache_mod"][1] + _fiel
     "p:k_new,v_new i:seqlen_new,k_new_batch_stride,k_new_token_stride,v_new_batch_stride,v_new_token_stride c:in_dtype "
     "p:q8_out i:q8_batch_stride,q8_token_stride") + _ROTARY)
 _sig("fa_fp8_kvcache_step_workspace_bytes", _KVWS + _fields("c:causal") + _WINDOW + _fields("c:with_sinks,in_dtype,with_q8_out"), _SIZE)
+# head dims 64 / 128 / 256: each _mod entry point's list (and the workspace functions' lists) with d under the name head_dim
+def _hdim_fields(fields):
+    return tuple(("head_dim" if field == "d" else field, ctype) for field, ctype in fields)
+
+
+for _name in ("fa_fp8_forward", "fa_fp8_forward_varlen", "fa_fp8_forward_kvcache"):
+    _sig(_name + "_hdim", _hdim_fields(_SIGNATURES[_name + "_mod"][1]))
+_sig("fa_fp8_forward_hdim_workspace_bytes", _hdim_fields(_SIGNATURES["fa_fp8_forward_workspace_bytes"][1]), _SIZE)
+_sig("fa_fp8_forward_varlen_hdim_workspace_bytes", _hdim_fields(_SIGNATURES["fa_fp8_forward_varlen_workspace_bytes"][1]), _SIZE)
+_sig("fa_fp8_forward_kvcache_hdim_workspace_bytes", _hdim_fields(_SIGNATURES["fa_fp8_forward_kvcache_workspace_bytes_mod"][1]), _SIZE)
 _KVWSV = _fields("i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,d,num_splits c:with_sinks")
 _sig("fa_ex_kvcache_workspace_bytes_varlen", _KVWSV, _SIZE)
 _sig("fa_ex_kvcache_workspace_bytes_qv", _KVWSV + _fields("i:d_v"), _SIZE)
@@ -299,6 +311,9 @@ _family("fa_fp8_forward_varlen", [])
 _family("fa_fp8_forward_kvcache", [])
 # a window, a softcap and sinks: each entry point takes its parent's arguments plus one group and is called with exactly its own
 for _name in ("fa_fp8_forward_mod", "fa_fp8_forward_varlen_mod", "fa_fp8_forward_kvcache_mod"):
+    _family(_name, [])
+# head dims 64 / 128 / 256: again a family of one each
+for _name in ("fa_fp8_forward_hdim", "fa_fp8_forward_varlen_hdim", "fa_fp8_forward_kvcache_hdim"):
     _family(_name, [])
 _family("fa_fp8_quantize", [])
 _family("fa_fp8_kvcache_step", [])
@@ -2208,18 +2223,36 @@ def merge_states_backward(o_a, lse_a, o_b, lse_b, do_, dlse=None, layout="bhnd")
 FP8_LAYOUTS = ("bhnd", "bnhd")
 
 
-def _fp8_view(who, name, t, layout):
-    """(batch, heads, rows, (batch, head, token) strides in elements) of a 4-D (.., 128) tensor under `layout`; a stride of an extent-1
-    dim is handed on as 0 (token: 128), so that the C layer's rules see only the strides that address"""
-    if t.dim() != 4 or t.shape[3] != 128:
+FP8_HEAD_DIMS = (64, 128, 256)   # of the _hdim entry points (hdim=True below); every other call: 128
+
+
+def _fp8_head_dim(who, hdim, **tensors):
+    """The head dim of an fp8 call: 128 (the callers' own checks refuse the rest), or with hdim the one last extent of all
+    `tensors`, 64, 128 or 256: RuntimeError names tensors that disagree, NotImplementedError any other width."""
+    if not hdim:
+        return 128
+    dims = {name: t.shape[-1] for name, t in tensors.items() if t.dim() >= 1}
+    if len(set(dims.values())) > 1:
+        raise RuntimeError(f"{who}: mixed head dims: " + ", ".join(f"{name} has {d}" for name, d in dims.items()) +
+                           " (q, k and v must agree in their last extent)")
+    d = next(iter(dims.values()), 128)
+    if d not in FP8_HEAD_DIMS:
+        raise NotImplementedError(f"{who}: head_dim {d} is not supported (64, 128 or 256)")
+    return d
+
+
+def _fp8_view(who, name, t, layout, d=128):
+    """(batch, heads, rows, (batch, head, token) strides in elements) of a 4-D (.., d) tensor under `layout`; a stride of an extent-1
+    dim is handed on as 0 (token: d), so that the C layer's rules see only the strides that address"""
+    if t.dim() != 4 or t.shape[3] != d:
         if t.dim() == 4:
             raise NotImplementedError(f"{who}: head_dim {t.shape[3]} is not supported (128 only); got {name} of shape {tuple(t.shape)}")
-        raise RuntimeError(f"{who}: {name} must be 4-D ({'B, H, N, 128' if layout == 'bhnd' else 'B, N, H, 128'}), got {tuple(t.shape)}")
+        raise RuntimeError(f"{who}: {name} must be 4-D ({f'B, H, N, {d}' if layout == 'bhnd' else f'B, N, H, {d}'}), got {tuple(t.shape)}")
     if t.stride(3) != 1:
         raise ValueError(f"{who}: {name} must have a contiguous last dim (a view that would need a copy)")
     b, h, n = (t.shape[0], t.shape[1], t.shape[2]) if layout == "bhnd" else (t.shape[0], t.shape[2], t.shape[1])
     hs, ts = (t.stride(1), t.stride(2)) if layout == "bhnd" else (t.stride(2), t.stride(1))
-    st = (t.stride(0) if b > 1 else 0, hs if h > 1 else 0, ts if n > 1 else 128)
+    st = (t.stride(0) if b > 1 else 0, hs if h > 1 else 0, ts if n > 1 else d)
     unit = 16 // t.element_size()
     if t.numel() and (t.data_ptr() % 16 != 0 or any(x % unit != 0 or x < 0 for x in st)):
         raise ValueError(f"{who}: {name} is a view the kernel cannot address: a 16-byte aligned start and non-negative strides that are "
@@ -2227,10 +2260,11 @@ def _fp8_view(who, name, t, layout):
     return b, h, n, st
 
 
-def _fp8_mod(who, q, hq, window, softcap, sinks):
+def _fp8_mod(who, q, hq, window, softcap, sinks, hdim=False):
     """(the entry point's suffix, its trailing (window_left, window_right, softcap, sinks, sink_heads), the tensor to keep alive) of
     a window, a softcap and sinks on an fp8 call with hq query heads; ("", (), None) when none of the three is given: such a call
-    goes through its parent entry point with the parent's arguments"""
+    goes through its parent entry point with the parent's arguments.  hdim: the suffix is "_hdim" and the trailing group is always
+    there (the _hdim entry points take it; at its defaults it is no feature)"""
     try:
         wl, wr = window
         if isinstance(wl, bool) or isinstance(wr, bool):
@@ -2253,17 +2287,20 @@ def _fp8_mod(who, q, hq, window, softcap, sinks):
             raise RuntimeError(f"{who}: sinks must be on q's device ({q.device}), got {sinks.device}")
         sinks = sinks.contiguous()
     featured = wl >= 0 or wr >= 0 or cap > 0.0 or sinks is not None
+    if hdim:
+        return "_hdim", (wl, wr, cap, _ptr(sinks), hq if sinks is not None else 0), sinks
     return ("_mod", (wl, wr, cap, _ptr(sinks), hq if sinks is not None else 0), sinks) if featured else ("", (), None)
 
 
 def fp8_forward(q, k, v, causal, softmax_scale, q_descale=None, k_descale=None, v_descale=None, out_dtype=torch.bfloat16, layout="bhnd",
-                *, window=(-1, -1), softcap=0.0, sinks=None):
+                *, window=(-1, -1), softcap=0.0, sinks=None, hdim=False):
     """(o, lse) of FlashAttention-3's fp8 call (fa_fp8_forward): q (B, H_q, Nq, 128), k and v (B, H_kv, Nk, 128) in torch.float8_e4m3fn
     (layout "bnhd": (B, N, H, 128)), used at their own strides, never copied; q_descale, k_descale, v_descale float32 (B, H_kv) or
     (H_kv,) on q's device, None = 1.  o comes back contiguous in `layout` and out_dtype (bfloat16 / float16), lse float32
     (B, H_q, Nq).  The V^T workspace is the shim's persistent one.  Nothing is recorded by autograd.
     window (left, right; -1 = unbounded), softcap (0 = off) and sinks (float32 (H_q,) on q's device) are fa_fp8_forward_mod's; a call
-    with none of them goes through fa_fp8_forward."""
+    with none of them goes through fa_fp8_forward.  hdim=True: the call goes through fa_fp8_forward_hdim, whatever its other arguments,
+    and the last extent of q, k, v may be 64, 128 or 256 (softmax_scale None: d ** -0.5); at 128 that entry point is fa_fp8_forward_mod."""
     who = "fp8_forward"
     if layout not in FP8_LAYOUTS:
         raise ValueError(f"{who}: layout must be one of {FP8_LAYOUTS}, got {layout!r}")
@@ -2279,44 +2316,45 @@ def fp8_forward(q, k, v, causal, softmax_scale, q_descale=None, k_descale=None, 
             raise RuntimeError(f"{who}: tensors must be on the GPU (HIP device); there is no CPU path")
         if t.device != q.device:
             raise RuntimeError(f"{who}: q, k, v must be on one device ({name} is on {t.device}, q on {q.device})")
-    b, hq, nq, sq = _fp8_view(who, "q", q, layout)
-    bk, hkv, nk, sk = _fp8_view(who, "k", k, layout)
-    bv, hv, nv, sv = _fp8_view(who, "v", v, layout)
+    d = _fp8_head_dim(who, hdim, q=q, k=k, v=v)
+    b, hq, nq, sq = _fp8_view(who, "q", q, layout, d)
+    bk, hkv, nk, sk = _fp8_view(who, "k", k, layout, d)
+    bv, hv, nv, sv = _fp8_view(who, "v", v, layout, d)
     if (bk, bv) != (b, b) or (hv, nv) != (hkv, nk):
         raise RuntimeError(f"{who}: k and v must share (B, H_kv, Nk) and q's batch; got q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}")
     if min(b, hq, hkv, nq, nk) < 1:
         raise RuntimeError(f"{who}: empty tensors are not supported (q {tuple(q.shape)}, k {tuple(k.shape)})")
     if hq % hkv != 0:
         raise RuntimeError(f"{who}: H_q = {hq} must be a multiple of H_kv = {hkv}")
-    scale = 128 ** -0.5 if softmax_scale is None else float(softmax_scale)
+    scale = d ** -0.5 if softmax_scale is None else float(softmax_scale)
     if not (math.isfinite(scale) and scale > 0.0):
         raise RuntimeError(f"{who}: softmax_scale must be finite and > 0 (got {scale})")
     qdp, qds, keep_q = _kv_descale(who, "q_descale", q_descale, q, b, hkv)
     kdp, kds, keep_k = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
     vdp, vds, keep_v = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
-    mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks)
+    mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks, hdim)
     with torch.cuda.device(q.device):
-        o = torch.empty((b, hq, nq, 128) if layout == "bhnd" else (b, nq, hq, 128), dtype=out_dtype, device=q.device)
+        o = torch.empty((b, hq, nq, d) if layout == "bhnd" else (b, nq, hq, d), dtype=out_dtype, device=q.device)
         lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)
-        _b, _h, _n, so = _fp8_view(who, "o", o, layout)
-        need = int(_lib.fa_fp8_forward_workspace_bytes(b, hkv, nk, 128))
+        _b, _h, _n, so = _fp8_view(who, "o", o, layout, d)
+        need = int((_lib.fa_fp8_forward_hdim_workspace_bytes if hdim else _lib.fa_fp8_forward_workspace_bytes)(b, hkv, nk, d))
         ws = _workspace(q.device, need)
         _call("fa_fp8_forward" + mod, (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp, b, hq, hkv, nq,
-                                       nk, 128, _DTYPE_CODE[out_dtype], *sq, *sk, *sv, *so, qds, kds, vds, int(bool(causal)), scale,
+                                       nk, d, _DTYPE_CODE[out_dtype], *sq, *sk, *sv, *so, qds, kds, vds, int(bool(causal)), scale,
                                        ws.data_ptr(), ws.numel(), _stream_ptr(q.device), *tail))
     del keep_q, keep_k, keep_v, keep_s
     return o, lse
 
 
-def _fp8_rows(who, name, t, heads):
-    """(token stride, head stride) in bytes of an e4m3 (.., heads, 128) tensor's last three dims; ValueError on a view the kernels
+def _fp8_rows(who, name, t, heads, d=128):
+    """(token stride, head stride) in bytes of an e4m3 (.., heads, d) tensor's last three dims; ValueError on a view the kernels
     cannot address without a copy"""
     if t.stride(-1) != 1:
         raise ValueError(f"{who}: {name} must have a contiguous last dim (a view that would need a copy)")
     n = t.shape[-3]
-    ts = t.stride(-3) if n > 1 else max(t.stride(-3), 128)
+    ts = t.stride(-3) if n > 1 else max(t.stride(-3), d)
     hs = t.stride(-2) if heads > 1 else 0
-    if t.numel() and (t.data_ptr() % 16 != 0 or ts % 16 != 0 or hs % 16 != 0 or ts < 128 or hs < 0):
+    if t.numel() and (t.data_ptr() % 16 != 0 or ts % 16 != 0 or hs % 16 != 0 or ts < d or hs < 0):
         raise ValueError(f"{who}: {name} is a view the kernel cannot address: a 16-byte aligned start and non-negative strides that are "
                          f"multiples of 16 bytes are needed (token stride {ts}, head stride {hs})")
     return ts, hs
@@ -2324,14 +2362,14 @@ def _fp8_rows(who, name, t, heads):
 
 def fp8_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, q_descale=None,
                        k_descale=None, v_descale=None, out_dtype=torch.bfloat16, block_table=None, *, window=(-1, -1), softcap=0.0,
-                       sinks=None):
+                       sinks=None, hdim=False):
     """(o, lse) of the packed / paged fp8 call (fa_fp8_forward_varlen): q (total_q, H_q, 128) in torch.float8_e4m3fn at its own token
     and head strides; k and v (total_k, H_kv, 128) e4m3, or with block_table (int32 (B, max_blocks_per_seq)) the pools
     (num_blocks, ps, H_kv, 128) at their own page and token strides; nothing is copied.  cu_seqlens_* int32 (B + 1,) on the device;
     descales float32 (B, H_kv) or (H_kv,), None = 1.  o (total_q, H_q, 128) in out_dtype, lse float32 (H_q, total_q); rows no
     sequence owns hold unspecified values.  Nothing is read on the host; the V^T workspace is the shim's persistent one.
     window, softcap and sinks (float32 (H_q,)) are fa_fp8_forward_varlen_mod's; a call with none of them goes through
-    fa_fp8_forward_varlen."""
+    fa_fp8_forward_varlen.  hdim=True: through fa_fp8_forward_varlen_hdim, with a last extent of 64, 128 or 256 (fp8_forward has the rest)."""
     who = "fp8_varlen_forward"
     for name, t in (("q", q), ("k", k), ("v", v)):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float8_e4m3fn:
@@ -2349,8 +2387,9 @@ def fp8_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_se
         raise RuntimeError(f"{who}: q must be (total_q, H_q, 128) and k, v " +
                            ("pools (num_blocks, page_block_size, H_kv, 128)" if paged else "(total_k, H_kv, 128)") +
                            f"; got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    d = _fp8_head_dim(who, hdim, q=q, k=k, v=v)
     for name, t in (("q", q), ("k", k), ("v", v)):
-        if t.shape[-1] != 128:
+        if t.shape[-1] != d:
             raise NotImplementedError(f"{who}: head_dim {t.shape[-1]} is not supported (128 only); got {name} of shape {tuple(t.shape)}")
     tensors = (q, k, v, cu_seqlens_q, cu_seqlens_k) + ((block_table,) if paged else ())
     for t in tensors:
@@ -2371,12 +2410,12 @@ def fp8_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_se
     mq, mk = operator.index(max_seqlen_q), operator.index(max_seqlen_k)
     if mq < 0 or mk < 0:
         raise RuntimeError(f"{who}: max_seqlen_q, max_seqlen_k must be >= 0")
-    scale = 128 ** -0.5 if softmax_scale is None else float(softmax_scale)
+    scale = d ** -0.5 if softmax_scale is None else float(softmax_scale)
     if not (math.isfinite(scale) and scale > 0.0):
         raise RuntimeError(f"{who}: softmax_scale must be finite and > 0 (got {scale})")
-    qts, qhs = _fp8_rows(who, "q", q, hq)
-    kts, khs = _fp8_rows(who, "k", k, hkv)
-    vts, vhs = _fp8_rows(who, "v", v, hkv)
+    qts, qhs = _fp8_rows(who, "q", q, hq, d)
+    kts, khs = _fp8_rows(who, "k", k, hkv, d)
+    vts, vhs = _fp8_rows(who, "v", v, hkv, d)
     if paged:
         nblk, ps = k.shape[0], k.shape[1]
         if ps < 16 or ps % 16 != 0:
@@ -2398,17 +2437,18 @@ def fp8_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_se
     qdp, qds, keep_q = _kv_descale(who, "q_descale", q_descale, q, b, hkv)
     kdp, kds, keep_k = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
     vdp, vds, keep_v = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
-    mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks)
+    mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks, hdim)
     with torch.cuda.device(q.device):
-        o = torch.empty((total_q, hq, 128), dtype=out_dtype, device=q.device)
+        o = torch.empty((total_q, hq, d), dtype=out_dtype, device=q.device)
         lse = torch.empty((hq, total_q), dtype=torch.float32, device=q.device)
         if total_q == 0:
             return o, lse
-        need = int(_lib.fa_fp8_forward_varlen_workspace_bytes(b, hkv, total_k, mk, mblk, ps, 128))
+        need = int((_lib.fa_fp8_forward_varlen_hdim_workspace_bytes if hdim else _lib.fa_fp8_forward_varlen_workspace_bytes)(
+            b, hkv, total_k, mk, mblk, ps, d))
         ws = _workspace(q.device, need)
         _call("fa_fp8_forward_varlen" + mod, (
             q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp, cu_q.data_ptr(), cu_k.data_ptr(),
-            block_table.data_ptr() if paged else 0, b, hq, hkv, total_q, total_k, mq, mk, 128, _DTYPE_CODE[out_dtype], qts, qhs, kts, khs,
+            block_table.data_ptr() if paged else 0, b, hq, hkv, total_q, total_k, mq, mk, d, _DTYPE_CODE[out_dtype], qts, qhs, kts, khs,
             vts, vhs, *pages, qds, kds, vds, int(bool(causal)), scale, ws.data_ptr(), ws.numel(), _stream_ptr(q.device), *tail))
     del keep_q, keep_k, keep_v, keep_s
     return o, lse
@@ -2416,14 +2456,15 @@ def fp8_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_se
 
 def fp8_kvcache_forward(q, k_cache, v_cache, cache_seqlens=None, block_table=None, cache_batch_idx=None, q_descale=None, k_descale=None,
                         v_descale=None, softmax_scale=None, causal=False, num_splits=0, out_dtype=torch.bfloat16, *, window=(-1, -1),
-                        softcap=0.0, sinks=None):
+                        softcap=0.0, sinks=None, hdim=False):
     """(o, lse) of fp8 KV-cache decoding (fa_fp8_forward_kvcache): q (B, Nq, H_q, 128) in torch.float8_e4m3fn at its own batch and
     token strides over the e4m3 caches (B_cache, cache_len, H_kv, 128), or with block_table (int32 (B, max_blocks_per_seq)) the pools
     (num_blocks, ps, H_kv, 128), at their own batch / page and token strides; nothing is copied.  cache_seqlens int32 (B,) on the
     device, an int, or None (full); cache_batch_idx int32 (B,), contiguous form only; descales float32 (B, H_kv) or (H_kv,), None =
     1.  o (B, Nq, H_q, 128) in out_dtype, lse float32 (B, H_q, Nq).  Nothing is read on the host; the partials live in the shim's
     persistent workspace.  window, softcap and sinks (float32 (H_q,)) are fa_fp8_forward_kvcache_mod's; a call with none of them goes
-    through fa_fp8_forward_kvcache."""
+    through fa_fp8_forward_kvcache.  hdim=True: through fa_fp8_forward_kvcache_hdim, with a last extent of 64, 128 or 256 (fp8_forward
+    has the rest)."""
     who = "fp8_kvcache_forward"
     if isinstance(q, torch.Tensor) and q.dtype in (torch.float16, torch.bfloat16):
         raise NotImplementedError(f"{who}: q of dtype {q.dtype} is not supported (torch.float8_e4m3fn expected; a 16-bit q over an e4m3 "
@@ -2445,8 +2486,9 @@ def fp8_kvcache_forward(q, k_cache, v_cache, cache_seqlens=None, block_table=Non
         raise RuntimeError(f"{who}: q must be (B, Nq, H_q, 128) and k_cache, v_cache " +
                            ("pools (num_blocks, page_block_size, H_kv, 128)" if paged else "(B_cache, cache_len, H_kv, 128)") +
                            f" of one shape; got {tuple(q.shape)}, {tuple(k_cache.shape)}, {tuple(v_cache.shape)}")
+    d = _fp8_head_dim(who, hdim, q=q, k_cache=k_cache, v_cache=v_cache)
     for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
-        if t.shape[-1] != 128:
+        if t.shape[-1] != d:
             raise NotImplementedError(f"{who}: head_dim {t.shape[-1]} is not supported (128 only); got {name} of shape {tuple(t.shape)}")
     b, nq, hq = q.shape[0], q.shape[1], q.shape[2]
     hkv = k_cache.shape[2]
@@ -2463,20 +2505,20 @@ def fp8_kvcache_forward(q, k_cache, v_cache, cache_seqlens=None, block_table=Non
             raise RuntimeError(f"{who}: tensors must be on the GPU (HIP device); there is no CPU path")
     if len({t.device for t in tensors}) != 1:
         raise RuntimeError(f"{who}: all tensors must be on one device")
-    scale = 128 ** -0.5 if softmax_scale is None else float(softmax_scale)
+    scale = d ** -0.5 if softmax_scale is None else float(softmax_scale)
     if not (math.isfinite(scale) and scale > 0.0):
         raise RuntimeError(f"{who}: softmax_scale must be finite and > 0 (got {scale})")
     ns = operator.index(num_splits)
     if ns < 0 or ns > 256:
         raise RuntimeError(f"{who}: num_splits must lie in [0, 256] (got {ns})")
     for name, t, heads in (("q", q, hq), ("k_cache", k_cache, hkv), ("v_cache", v_cache, hkv)):
-        if t.numel() and ((heads > 1 and t.stride(2) != 128) or t.stride(3) != 1):
+        if t.numel() and ((heads > 1 and t.stride(2) != d) or t.stride(3) != 1):
             raise ValueError(f"{who}: {name} must have adjacent heads with a contiguous last dim (strides {t.stride()})")
         if t.numel() and (t.data_ptr() % 16 != 0 or t.stride(0) % 16 != 0 or t.stride(1) % 16 != 0 or t.stride(0) < 0 or
-                          (t.shape[1] > 1 and t.stride(1) < heads * 128)):
+                          (t.shape[1] > 1 and t.stride(1) < heads * d)):
             raise ValueError(f"{who}: {name} is a view the kernel cannot address: a 16-byte aligned start, batch and token strides that "
                              f"are multiples of 16 bytes and rows that do not overlap are needed (strides {t.stride()})")
-    tstride = lambda t, heads: t.stride(1) if t.shape[1] > 1 else heads * 128   # noqa: E731
+    tstride = lambda t, heads: t.stride(1) if t.shape[1] > 1 else heads * d   # noqa: E731
     if paged:
         nblk, ps = k_cache.shape[0], k_cache.shape[1]
         if ps < 16 or ps % 16 != 0:
@@ -2509,13 +2551,16 @@ def fp8_kvcache_forward(q, k_cache, v_cache, cache_seqlens=None, block_table=Non
     qdp, qds, keep_q = _kv_descale(who, "q_descale", q_descale, q, b, hkv)
     kdp, kds, keep_k = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
     vdp, vds, keep_v = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
-    mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks)
+    mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks, hdim)
     with torch.cuda.device(q.device):
-        o = torch.empty((b, nq, hq, 128), dtype=out_dtype, device=q.device)
+        o = torch.empty((b, nq, hq, d), dtype=out_dtype, device=q.device)
         lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)
         if b == 0 or nq == 0:
             return o, lse
-        if mod:
+        if hdim:
+            need = int(_lib.fa_fp8_forward_kvcache_hdim_workspace_bytes(b, hq, hkv, nq, cap, d, ns, int(bool(causal)), tail[0], tail[1],
+                                                                        int(sinks is not None)))
+        elif mod:
             need = int(_lib.fa_fp8_forward_kvcache_workspace_bytes_mod(b, hq, hkv, nq, cap, 128, ns, int(bool(causal)), tail[0], tail[1],
                                                                        int(sinks is not None)))
         else:
@@ -2524,7 +2569,7 @@ def fp8_kvcache_forward(q, k_cache, v_cache, cache_seqlens=None, block_table=Non
         _call("fa_fp8_forward_kvcache" + mod, (
             q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp,
             cache_seqlens.data_ptr() if cache_seqlens is not None else 0, block_table.data_ptr() if paged else 0,
-            cache_batch_idx.data_ptr() if cache_batch_idx is not None else 0, b, hq, hkv, nq, cap, cbatch, 128, _DTYPE_CODE[out_dtype],
+            cache_batch_idx.data_ptr() if cache_batch_idx is not None else 0, b, hq, hkv, nq, cap, cbatch, d, _DTYPE_CODE[out_dtype],
             _E4M3_CODE, _E4M3_CODE, max(q.stride(0), 0) if b > 1 else 0, tstride(q, hq),
             k_cache.stride(0) if k_cache.shape[0] > 1 else 0, tstride(k_cache, hkv),
             v_cache.stride(0) if v_cache.shape[0] > 1 else 0, tstride(v_cache, hkv), *pages, qds, kds, vds, int(bool(causal)), scale, ns,

@@ -1286,6 +1286,59 @@ size_t fa_fp8_forward_kvcache_workspace_bytes_mod(int64_t batch, int64_t heads_q
                                                   int64_t d, int64_t num_splits, int causal, int64_t window_left, int64_t window_right,
                                                   int with_sinks);
 
+/* --- Head dims 64 and 256 beside 128 on the three fp8 calls.  Each _hdim entry point takes its _mod parent's argument list (the
+ * head dim is named head_dim here) and the same rules in the same order, with two changes: head_dim may be 64, 128 or 256 (any other
+ * value: FA_ERR_UNSUPPORTED, "head_dim N is not supported (64, 128 or 256)", where the parent checks d == 128), and head_dim
+ * stands where the parent's rules say 128: the least token stride (heads * head_dim for the decode call), the stride handed on for
+ * a single row, the spans.  The entry points above keep refusing everything but 128.
+ * head_dim == 128 IS the _mod call: the same launches of the same kernels, the same routes counted, the same workspace size.
+ * head_dim 64 and 256 run instantiations of the featured kernels at that width (routes "fp8in_fwd_hdim", "fp8in_fwd_varlen_hdim",
+ * "fp8kv_split_hdim" of fa_route_count, one count a call that launched), with or without a window, a softcap or sinks, and
+ * everything documented for 128 holds: GQA, seqlen_q != seqlen_k with the bottom-right diagonal, strided views, untrusted
+ * lengths, tables and indices, graph replay, f16 / bf16 o.  The arithmetic is that of 128 with head_dim / 64 score instructions
+ * a 32-key block accumulated in ascending head-dim order; at 256 the prefill kernels take the softmax step (maximum, lazy
+ * rescale, e4m3 P) over 64 keys instead of 128.
+ * Workspace: the V^T image of the prefill calls is units_kv * tiles * head_dim * 128 + 256 bytes (tiles as the parents count
+ * them); the decode partials follow fa_fp8_forward_kvcache_workspace_bytes_mod at head_dim (the split rule counts keys, not bytes).
+ * Not here: fa_fp8_kvcache_step (128 only; a 64 / 256 cache is filled by fa_ex_forward_kvcache_fp8's append and q comes from
+ * fa_fp8_quantize), head dims 96 and 192, fa3_forward(fp8 = 1), the MLA and indexer families. */
+int fa_fp8_forward_hdim(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
+                       const float* v_descale, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_k,
+                       int64_t head_dim, int dtype, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_token_stride,
+                       int64_t k_batch_stride, int64_t k_head_stride, int64_t k_token_stride, int64_t v_batch_stride,
+                       int64_t v_head_stride, int64_t v_token_stride, int64_t o_batch_stride, int64_t o_head_stride,
+                       int64_t o_token_stride, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
+                       int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace, size_t workspace_bytes,
+                       void* stream, int64_t window_left, int64_t window_right, double softcap, const float* sinks,
+                       int64_t sink_heads);
+int fa_fp8_forward_varlen_hdim(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale,
+                              const float* k_descale, const float* v_descale, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k,
+                              const int32_t* block_table, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q,
+                              int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t head_dim, int dtype,
+                              int64_t q_token_stride, int64_t q_head_stride, int64_t k_token_stride, int64_t k_head_stride,
+                              int64_t v_token_stride, int64_t v_head_stride, int64_t max_blocks_per_seq, int64_t num_blocks,
+                              int64_t page_block_size, int64_t k_page_stride, int64_t v_page_stride, int64_t q_descale_batch_stride,
+                              int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale,
+                              void* workspace, size_t workspace_bytes, void* stream, int64_t window_left, int64_t window_right,
+                              double softcap, const float* sinks, int64_t sink_heads);
+int fa_fp8_forward_kvcache_hdim(const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const float* q_descale,
+                               const float* k_descale, const float* v_descale, const int32_t* cache_seqlens, const int32_t* block_table,
+                               const int32_t* cache_batch_idx, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q,
+                               int64_t cache_len, int64_t cache_batch, int64_t head_dim, int dtype, int q_dtype, int cache_dtype,
+                               int64_t q_batch_stride, int64_t q_token_stride, int64_t k_batch_stride, int64_t k_token_stride,
+                               int64_t v_batch_stride, int64_t v_token_stride, int64_t block_table_row_stride, int64_t num_blocks,
+                               int64_t page_block_size, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
+                               int64_t v_descale_batch_stride, int causal, double softmax_scale, int64_t num_splits, void* workspace,
+                               size_t workspace_bytes, void* stream, int64_t window_left, int64_t window_right, double softcap,
+                               const float* sinks, int64_t sink_heads);
+/* the three needs; 0 for arguments the call would refuse (head_dim outside {64, 128, 256} among them) */
+size_t fa_fp8_forward_hdim_workspace_bytes(int64_t batch, int64_t heads_kv, int64_t seqlen_k, int64_t head_dim);
+size_t fa_fp8_forward_varlen_hdim_workspace_bytes(int64_t batch, int64_t heads_kv, int64_t total_k, int64_t max_seqlen_k,
+                                                  int64_t max_blocks_per_seq, int64_t page_block_size, int64_t head_dim);
+size_t fa_fp8_forward_kvcache_hdim_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
+                                                  int64_t head_dim, int64_t num_splits, int causal, int64_t window_left, int64_t window_right,
+                                                  int with_sinks);
+
 /* --- The fp8 quantiser: one 16-bit tensor x -> e4m3 codes plus float32 descales of the shape the fp8 calls above read (the
  * producer of fa_fp8_forward / _varlen / _kvcache and of the e4m3 cache).  One call covers one tensor, addressed through its own
  * strides like fa_rotary_apply's, so a slice of a fused qkv projection goes in without a copy.
@@ -1442,7 +1495,9 @@ int fa_profile_report(char* buf, size_t cap);
  * "fp8_quant_static": the three routes of fa_fp8_quantize, one count a call that launched.  "fp8in_fwd_mod",
  * "fp8in_fwd_varlen_mod", "fp8kv_split_mod": the featured kernels of fa_fp8_forward_mod, fa_fp8_forward_varlen_mod and
  * fa_fp8_forward_kvcache_mod, one count a call that launched one (a _mod call with default trailing arguments counts none).
- * "fp8kv_step_prep": the append / rotary / quantise launch of fa_fp8_kvcache_step, one count a call. */
+ * "fp8kv_step_prep": the append / rotary / quantise launch of fa_fp8_kvcache_step, one count a call.  "fp8in_fwd_hdim",
+ * "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim": the head dim 64 / 256 kernels of fa_fp8_forward_hdim, fa_fp8_forward_varlen_hdim and
+ * fa_fp8_forward_kvcache_hdim, one count a call that launched one (head_dim 128 counts what the _mod call counts). */
 int64_t fa_route_count(const char* name);
 
 #ifdef __cplusplus
