@@ -1103,7 +1103,8 @@ def quantize_fp8_qkv(q, k, v, *, layout="bnhd", q_descale=None, k_descale=None, 
 
 # The fp8 calls at head dims 64, 128 and 256 live in a module of their own (common/fp8_attention.py, which imports this one); they are
 # reachable from here too, where their namesakes are.
-_FP8_HDIM_FUNCS = ("fp8_attn_func", "fp8_attn_varlen_func", "fp8_attn_with_kvcache")
+_FP8_HDIM_FUNCS = ("fp8_attn_func", "fp8_attn_varlen_func", "fp8_attn_with_kvcache", "fp8_attn_with_kvcache_varlen",
+                   "fp8_attn_kvcache_step")
 
 
 def __getattr__(name):

@@ -33,7 +33,7 @@ const char* const kKernelNames[fa::K_COUNT] = {"fwd_f32", "bwd_delta", "bwd_dkdv
                                                "fp8in_vt", "fp8in_fwd", "fp8in_vt_varlen", "fp8in_fwd_varlen", "idx_pack", "idx_logits",
                                                "idx_topk", "fp8kv_split", "fp8q_amax", "fp8q_quant", "fp8q_fused", "fp8in_fwd_mod",
                                                "fp8in_fwd_varlen_mod", "fp8kv_split_mod", "fp8kv_step_prep", "fp8in_fwd_hdim",
-    "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim"};
+    "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim", "fp8kv_split_varlen", "fp8kv_step_prep_varlen"};
 
 hipEvent_t prof_get_event() {
     if (!g_prof_free.empty()) { hipEvent_t e = g_prof_free.back(); g_prof_free.pop_back(); return e; }
@@ -179,7 +179,8 @@ int set_option(const char* name, int value) {
 std::atomic<long long> g_route_hits[ROUTE_COUNT];
 constexpr const char* kRouteNames[ROUTE_COUNT] = {"dkdv_stream", "dkdv_lean", "fp8_quant_fused", "fp8_quant_two_pass", "fp8_quant_static",
                                                    "fp8in_fwd_mod", "fp8in_fwd_varlen_mod", "fp8kv_split_mod", "fp8kv_step_prep", "fp8in_fwd_hdim",
-                                                   "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim"};
+                                                   "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim", "fp8kv_split_varlen",
+                                                   "fp8kv_step_prep_varlen"};
 void route_hit(int id) { g_route_hits[id].fetch_add(1, std::memory_order_relaxed); }
 long long route_count(const char* name) {
     for (int i = 0; i < ROUTE_COUNT; ++i)
@@ -3310,6 +3311,10 @@ struct Fp8KvCall {
     void* workspace = nullptr;
     size_t workspace_bytes = 0;
     void* stream = nullptr;
+    // the _varlen entry points (varlen: one of them was called; its packed group, all null / 0: the padded call)
+    bool varlen = false;
+    const int32_t* cu_seqlens_q = nullptr;
+    int64_t total_q = 0, max_seqlen_q = 0;
 };
 
 static int64_t fp8_kv_splits(int64_t batch, int64_t hq, int64_t hkv, int64_t nq, int64_t cache_len, int64_t num_splits) {
@@ -3335,18 +3340,25 @@ struct Fp8StepCall {
     const void *rotary_cos = nullptr, *rotary_sin = nullptr;
     int64_t cos_rs = 0, sin_rs = 0, seqlen_ro = 0, rotary_dim = 0;
     int rotary_interleaved = 0;
+    const int32_t* cu_seqlens_k_new = nullptr;   // fa_fp8_kvcache_step_varlen
+    int64_t total_k_new = 0;
 };
 
 // The rules of fa_fp8_forward_kvcache[_mod] (st == null) and of fa_fp8_kvcache_step (st: what it adds), in the header's order.
+// With packed queries (c.cu_seqlens_q; the _varlen entry points) seqlen_q and q's batch stride are not looked at, nor seqlen_new
+// and the batch strides of k_new / v_new with cu_seqlens_k_new; the rules of the packed group follow the parents' (9).
 // FA_OK: `empty` says that there is nothing to launch; otherwise S is the number of splits and need the workspace's bytes.
 static int fp8_kvcache_check(const char* who, const Fp8KvCall& c, const Fp8StepCall* st, bool& empty, int64_t& S, size_t& need) {
     const bool paged = c.block_table != nullptr;
     const int64_t kInt = ((int64_t)1 << 31) - 1;
     const int64_t kMaxStride = (int64_t)1 << 44;
     const int64_t qe = st && c.q_dtype != FA_DTYPE_E4M3 ? 2 : 1;   // bytes an element of q (and of k_new, v_new)
+    const bool packed = c.cu_seqlens_q != nullptr, packed_kn = st && st->cu_seqlens_k_new != nullptr;
+    const int64_t q_bs = packed ? 0 : c.q_bs;                      // (packed: not used)
+    const int64_t nq = packed ? c.max_seqlen_q : c.seqlen_q;       // the most query tokens a sequence has
     empty = false;
     // (0) the empty call
-    if (c.batch == 0 || (!st && c.seqlen_q == 0)) {
+    if (c.batch == 0 || (!st && !packed && c.seqlen_q == 0) || (!st && packed && (c.total_q == 0 || c.max_seqlen_q == 0))) {
         empty = true;
         return FA_OK;
     }
@@ -3377,12 +3389,12 @@ static int fp8_kvcache_check(const char* who, const Fp8KvCall& c, const Fp8StepC
                     (long long)c.heads_kv);
     // (4) ranges
     if (c.batch < 1 || c.batch > 65535) return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch must lie in [1, 65535] (got %lld)", who, (long long)c.batch);
-    if (c.seqlen_q < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_q must be >= 1 (got %lld)", who, (long long)c.seqlen_q);
+    if (!packed && c.seqlen_q < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_q must be >= 1 (got %lld)", who, (long long)c.seqlen_q);
     if (c.cache_len < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_len must be >= 1 (got %lld)", who, (long long)c.cache_len);
-    if (st && (st->seqlen_new < 1 || st->seqlen_new > c.cache_len))
+    if (st && !packed_kn && (st->seqlen_new < 1 || st->seqlen_new > c.cache_len))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_new=%lld must lie in [1, cache_len=%lld]", who, (long long)st->seqlen_new,
                     (long long)c.cache_len);
-    if (c.heads_q > ((int64_t)1 << 20) || c.seqlen_q > ((int64_t)1 << 20) || (c.heads_q / c.heads_kv) * c.seqlen_q > ((int64_t)1 << 20))
+    if (c.heads_q > ((int64_t)1 << 20) || (!packed && (c.seqlen_q > ((int64_t)1 << 20) || (c.heads_q / c.heads_kv) * c.seqlen_q > ((int64_t)1 << 20))))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: (heads_q / heads_kv) * seqlen_q = %lld * %lld must be <= 2^20", who,
                     (long long)(c.heads_q / c.heads_kv), (long long)c.seqlen_q);
     if (!(c.scale == c.scale) || !scale_ok(c.scale))
@@ -3401,8 +3413,9 @@ static int fp8_kvcache_check(const char* who, const Fp8KvCall& c, const Fp8StepC
     if (st && !aligned16({st->k_new, st->v_new})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_new and v_new must be 16-byte aligned", who);
     // (heads: the elements of a token's heads over d, in bytes for a 16-bit q, k_new, v_new)
     const struct { const char* name; int64_t bs, ts, heads; } ts[5] = {
-        {"q", c.q_bs, c.q_ts, c.heads_q * qe}, {"k_cache", c.k_bs, c.k_ts, c.heads_kv}, {"v_cache", c.v_bs, c.v_ts, c.heads_kv},
-        {"k_new", st ? st->kn_bs : 0, st ? st->kn_ts : 0, c.heads_kv * qe}, {"v_new", st ? st->vn_bs : 0, st ? st->vn_ts : 0, c.heads_kv * qe}};
+        {"q", q_bs, c.q_ts, c.heads_q * qe}, {"k_cache", c.k_bs, c.k_ts, c.heads_kv}, {"v_cache", c.v_bs, c.v_ts, c.heads_kv},
+        {"k_new", st && !packed_kn ? st->kn_bs : 0, st ? st->kn_ts : 0, c.heads_kv * qe},
+        {"v_new", st && !packed_kn ? st->vn_bs : 0, st ? st->vn_ts : 0, c.heads_kv * qe}};
     for (int i = 0; i < (st ? 5 : 3); ++i) {
         const auto& t = ts[i];
         if (t.ts % 16 != 0 || t.bs % 16 != 0)
@@ -3415,10 +3428,11 @@ static int fp8_kvcache_check(const char* who, const Fp8KvCall& c, const Fp8StepC
     if (st && st->q8_out) {
         if (qe == 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: q8_out goes with a 16-bit q only (an e4m3 q is used in place)", who);
         if (!aligned16({st->q8_out})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: q8_out must be 16-byte aligned", who);
-        if (st->q8_ts % 16 != 0 || st->q8_bs % 16 != 0 || st->q8_ts < c.heads_q * 128 || st->q8_ts > kMaxStride || st->q8_bs < 0 ||
-            st->q8_bs > kMaxStride)
+        const int64_t q8_bs = packed ? 0 : st->q8_bs;              // (packed: not used)
+        if (st->q8_ts % 16 != 0 || q8_bs % 16 != 0 || st->q8_ts < c.heads_q * d || st->q8_ts > kMaxStride || q8_bs < 0 || q8_bs > kMaxStride)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of q8_out (batch %lld, token %lld) must be multiples of 16 bytes and >= 0, "
-                        "the token stride >= heads_q * 128 = %lld", who, (long long)st->q8_bs, (long long)st->q8_ts, (long long)(c.heads_q * 128));
+                        "the token stride >= heads_q * %lld = %lld", who, (long long)q8_bs, (long long)st->q8_ts, (long long)d,
+                        (long long)(c.heads_q * d));
     } else if (st && (st->q8_bs != 0 || st->q8_ts != 0)) {
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: q8_batch_stride and q8_token_stride must be 0 without q8_out", who);
     }
@@ -3451,18 +3465,20 @@ static int fp8_kvcache_check(const char* who, const Fp8KvCall& c, const Fp8StepC
     // (8) the span limits: 32-bit byte offsets inside one batch element or page
     const int64_t kSpan = ((int64_t)1 << 31) - 1;
     const int64_t c_n = paged ? c.ps : c.cache_len;
-    const int64_t q_span = c.seqlen_q * c.q_ts, k_span = c_n * c.k_ts, v_span = c_n * c.v_ts;
+    const int64_t q_span = packed ? 0 : c.seqlen_q * c.q_ts, k_span = c_n * c.k_ts, v_span = c_n * c.v_ts;   // (packed: rule (P5))
     if (q_span > kSpan || k_span > kSpan || v_span > kSpan)
         return fail(FA_ERR_UNSUPPORTED, "%s: span limit: tokens * token stride of %s is %lld bytes, at or above 2^31", who,
                     q_span > kSpan ? "q" : k_span > kSpan ? "k_cache" : "v_cache", (long long)(q_span > kSpan ? q_span : k_span > kSpan ? k_span : v_span));
     if (c.cache_len >= ((int64_t)1 << 28))
         return fail(FA_ERR_UNSUPPORTED, "%s: span limit: cache_len = %lld (the capacity) is at or above 2^28", who, (long long)c.cache_len);
-    const int64_t row_tiles = ((c.heads_q / c.heads_kv) * c.seqlen_q + 31) / 32;
+    const int64_t row_tiles = packed ? 0 : ((c.heads_q / c.heads_kv) * c.seqlen_q + 31) / 32;   // (packed: rule (P6))
     if (row_tiles * c.heads_kv > 65535)
         return fail(FA_ERR_UNSUPPORTED, "%s: span limit: row tiles * heads_kv = %lld is beyond 65535 for one launch", who,
                     (long long)(row_tiles * c.heads_kv));
     if (st) {
-        const int64_t kn_span = st->seqlen_new * st->kn_ts, vn_span = st->seqlen_new * st->vn_ts, q8_span = c.seqlen_q * st->q8_ts;
+        // (packed new keys: the kernel addresses their rows in 64 bits; packed queries: rule (P5))
+        const int64_t kn_span = packed_kn ? 0 : st->seqlen_new * st->kn_ts, vn_span = packed_kn ? 0 : st->seqlen_new * st->vn_ts;
+        const int64_t q8_span = packed ? 0 : c.seqlen_q * st->q8_ts;
         if (kn_span > kSpan || vn_span > kSpan || q8_span > kSpan)
             return fail(FA_ERR_UNSUPPORTED, "%s: span limit: tokens * token stride of %s is %lld bytes, at or above 2^31", who,
                         kn_span > kSpan ? "k_new" : vn_span > kSpan ? "v_new" : "q8_out",
@@ -3474,10 +3490,11 @@ static int fp8_kvcache_check(const char* who, const Fp8KvCall& c, const Fp8StepC
         if (st->rotary_cos) {
             if (qe == 1)
                 return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary_cos / rotary_sin go with 16-bit q, k_new, v_new only (e4m3 codes cannot be rotated)", who);
-            if (st->rotary_dim < 16 || st->rotary_dim > 128 || st->rotary_dim % 16 != 0)
-                return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary_dim must be a multiple of 16 in [16, 128] (got %lld)", who, (long long)st->rotary_dim);
+            if (st->rotary_dim < 16 || st->rotary_dim > d || st->rotary_dim % 16 != 0)
+                return fail(FA_ERR_INVALID_ARGUMENT, "%s: rotary_dim must be a multiple of 16 in [16, %lld] (got %lld)", who, (long long)d,
+                            (long long)st->rotary_dim);
             const int64_t ro_need = c.cache_len + (c.seqlen_q > st->seqlen_new ? c.seqlen_q - st->seqlen_new : 0);
-            if (st->seqlen_ro < ro_need)
+            if (!packed && st->seqlen_ro < ro_need)
                 return fail(FA_ERR_INVALID_ARGUMENT,
                             "%s: seqlen_ro=%lld must be >= capacity + max(0, seqlen_q - seqlen_new) = %lld (the tables are not bounds-checked on the device)",
                             who, (long long)st->seqlen_ro, (long long)ro_need);
@@ -3498,14 +3515,55 @@ static int fp8_kvcache_check(const char* who, const Fp8KvCall& c, const Fp8StepC
     if (c.num_splits < 0 || c.num_splits > 256)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_splits must lie in [0, 256] (got %lld)", who, (long long)c.num_splits);
     if (const int rc = fp8_mod_check(who, c.mod, c.heads_q)) return rc;
-    S = fp8_kv_splits_mod(c.batch, c.heads_q, c.heads_kv, c.seqlen_q, c.cache_len, c.num_splits, c.causal, c.mod);
+    // (P) the packed group of the _varlen entry points (every other entry point hands nulls and zeros on)
+    // (P1) no extent without its array
+    if (!packed && (c.total_q != 0 || c.max_seqlen_q != 0))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: total_q and max_seqlen_q must be 0 without cu_seqlens_q (got %lld, %lld)", who,
+                    (long long)c.total_q, (long long)c.max_seqlen_q);
+    if (st && !packed_kn && st->total_k_new != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: total_k_new must be 0 without cu_seqlens_k_new (got %lld)", who, (long long)st->total_k_new);
+    // (P2) packed new keys go with packed queries
+    if (packed_kn && !packed) return fail(FA_ERR_INVALID_ARGUMENT, "%s: cu_seqlens_k_new needs cu_seqlens_q (packed new keys go with packed queries)", who);
+    if (packed) {
+        // (P3), (P4) the extents
+        if (c.max_seqlen_q < 0 || c.max_seqlen_q > c.total_q)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: max_seqlen_q=%lld must lie in [0, total_q=%lld]", who, (long long)c.max_seqlen_q,
+                        (long long)c.total_q);
+        if (c.total_q > kInt || (st && (st->total_k_new < 0 || st->total_k_new > kInt)))
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: total_q=%lld and total_k_new=%lld must lie in [0, 2^31)", who, (long long)c.total_q,
+                        (long long)(st ? st->total_k_new : 0));
+        // (P5) the span limit of one sequence's tokens
+        const int64_t pq_span = c.max_seqlen_q * c.q_ts, pq8_span = st ? c.max_seqlen_q * st->q8_ts : 0;
+        if (pq_span > kSpan || pq8_span > kSpan)
+            return fail(FA_ERR_UNSUPPORTED, "%s: span limit: max_seqlen_q * token stride of %s is %lld bytes, at or above 2^31", who,
+                        pq_span > kSpan ? "q" : "q8_out", (long long)(pq_span > kSpan ? pq_span : pq8_span));
+        // (P6) the rows of one sequence
+        if (c.max_seqlen_q > ((int64_t)1 << 20) || (c.heads_q / c.heads_kv) * c.max_seqlen_q > ((int64_t)1 << 20))
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: (heads_q / heads_kv) * max_seqlen_q = %lld * %lld must be <= 2^20", who,
+                        (long long)(c.heads_q / c.heads_kv), (long long)c.max_seqlen_q);
+        const int64_t prow_tiles = ((c.heads_q / c.heads_kv) * c.max_seqlen_q + 31) / 32;
+        if (prow_tiles * c.heads_kv > 65535)
+            return fail(FA_ERR_UNSUPPORTED, "%s: span limit: row tiles * heads_kv = %lld is beyond 65535 for one launch", who,
+                        (long long)(prow_tiles * c.heads_kv));
+        // (P7) the rotary tables: q token i of a sequence sits at L_b + i, L_b <= cache_len
+        if (st && st->rotary_cos && st->seqlen_ro < c.cache_len + c.max_seqlen_q)
+            return fail(FA_ERR_INVALID_ARGUMENT,
+                        "%s: seqlen_ro=%lld must be >= capacity + max_seqlen_q = %lld (the tables are not bounds-checked on the device)", who,
+                        (long long)st->seqlen_ro, (long long)(c.cache_len + c.max_seqlen_q));
+        // (P8) alignment
+        if ((uintptr_t)c.cu_seqlens_q % 4 != 0 || (st && (uintptr_t)st->cu_seqlens_k_new % 4 != 0))
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: cu_seqlens_q and cu_seqlens_k_new must be 4-byte aligned", who);
+    }
+    S = fp8_kv_splits_mod(c.batch, c.heads_q, c.heads_kv, nq, c.cache_len, c.num_splits, c.causal, c.mod);
     // (10) the workspace
-    need = fa::kv_workspace_bytes(c.batch, c.heads_q, c.seqlen_q, d, (int)S);
-    if (st) need += fa::fp8kv_step_prep_bytes(c.batch, c.heads_q, c.seqlen_q, qe == 2 && !st->q8_out);
+    need = packed ? fa::kv_workspace_bytes(1, c.heads_q, c.total_q, d, (int)S) : fa::kv_workspace_bytes(c.batch, c.heads_q, c.seqlen_q, d, (int)S);
+    if (st && c.varlen) need += fa::fp8kv_step_prep_bytes_varlen(c.batch, packed ? c.total_q : c.batch * c.seqlen_q, c.heads_q, d, qe == 2 && !st->q8_out);
+    else if (st) need += fa::fp8kv_step_prep_bytes(c.batch, c.heads_q, c.seqlen_q, qe == 2 && !st->q8_out);
     if (need > 0) {
         if (!c.workspace || c.workspace_bytes < need)
             return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes is too small (need %zu: %s%s)", who,
                         c.workspace ? c.workspace_bytes : (size_t)0, need,
+                        c.varlen ? (st ? "fa_fp8_kvcache_step_varlen_workspace_bytes" : "fa_fp8_forward_kvcache_varlen_workspace_bytes") :
                         st ? "fa_fp8_kvcache_step_workspace_bytes" : c.hdim ? "fa_fp8_forward_kvcache_hdim_workspace_bytes" : "fa_fp8_forward_kvcache_workspace_bytes",
                         !st && !c.hdim && c.mod.any() ? "_mod" : "");
         if ((uintptr_t)c.workspace % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
@@ -3524,6 +3582,7 @@ static fa::Fp8KvArgs fp8_kvcache_args(const Fp8KvCall& c, int64_t S) {
     a.q_bs = c.q_bs; a.q_ts = c.q_ts; a.kc_bs = c.k_bs; a.kc_ts = c.k_ts; a.vc_bs = c.v_bs; a.vc_ts = c.v_ts;
     a.table_row_stride = c.table_rs; a.num_blocks = c.num_blocks; a.page_size = c.ps;
     a.causal = c.causal != 0; a.scale = (float)c.scale; a.num_splits = S; a.workspace = c.workspace; a.d = c.d;
+    a.cu_seqlens_q = c.cu_seqlens_q; a.total_q = c.total_q; a.max_seqlen_q = c.max_seqlen_q;
     return a;
 }
 
@@ -3533,7 +3592,9 @@ static int fp8_kvcache_impl(const char* who, const Fp8KvCall& c) {
     size_t need = 0;
     if (const int rc = fp8_kvcache_check(who, c, nullptr, empty, S, need)) return rc;
     if (empty) return FA_OK;
-    return launched(who, fa::launch_fp8_kvcache_hdim(fp8_kvcache_args(c, S), c.mod, reinterpret_cast<hipStream_t>(c.stream)));   // (d == 128: .._mod)
+    // (d == 128: .._mod; packed queries: launch_fp8_kvcache_varlen)
+    if (c.cu_seqlens_q) return launched(who, fa::launch_fp8_kvcache_varlen(fp8_kvcache_args(c, S), c.mod, reinterpret_cast<hipStream_t>(c.stream)));
+    return launched(who, fa::launch_fp8_kvcache_hdim(fp8_kvcache_args(c, S), c.mod, reinterpret_cast<hipStream_t>(c.stream)));
 }
 
 size_t fa_fp8_forward_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t d,
@@ -3707,6 +3768,144 @@ int fa_fp8_kvcache_step(const void* q, void* k_cache, void* v_cache, void* o, fl
     // q token i is rotated at its own position when causal or a window bound was given (fa_ex_forward_kvcache_rotary's rule)
     s.rotary_q_per_token = (causal || window_left >= 0 || window_right >= 0) ? 1 : 0;
     return launched(who, fa::launch_fp8_kvcache_step(s, c.mod, reinterpret_cast<hipStream_t>(stream)));
+}
+
+// ---- packed queries and new keys on the fp8 decode call and the step, and the step at head dims 64 / 256: see include/fa_mi355x.h
+// the splits of a packed call: the rule over max_seqlen_q (the most rows a sequence has), as the call's rule (9) takes them
+static int64_t fp8_kv_splits_varlen(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t max_seqlen_q, int64_t cache_len,
+                                    int64_t num_splits, int causal, int64_t window_left, int64_t window_right, int with_sinks) {
+    fa::Fp8Mod m;
+    m.window_left = window_left; m.window_right = window_right;
+    int64_t S = fp8_kv_splits(batch, heads_q, heads_kv, max_seqlen_q, fa::fp8kv_split_len(cache_len, max_seqlen_q, causal, m), num_splits);
+    if (with_sinks && S < 2) S = 2;
+    return S;
+}
+
+static bool fp8_varlen_ws_args_ok(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t max_seqlen_q, int64_t cache_len,
+                                  int64_t head_dim, int64_t num_splits, int64_t window_left, int64_t window_right) {
+    const int64_t kInt = ((int64_t)1 << 31) - 1;
+    return batch > 0 && batch <= 65535 && heads_q > 0 && heads_kv > 0 && heads_q % heads_kv == 0 && total_q >= 0 && total_q <= kInt &&
+           max_seqlen_q >= 0 && max_seqlen_q <= total_q && (heads_q / heads_kv) * max_seqlen_q <= ((int64_t)1 << 20) && cache_len >= 1 &&
+           num_splits >= 0 && num_splits <= 256 && window_left >= -1 && window_right >= -1 &&
+           (head_dim == 64 || head_dim == 128 || head_dim == 256);
+}
+
+size_t fa_fp8_forward_kvcache_varlen_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t max_seqlen_q,
+                                                     int64_t cache_len, int64_t head_dim, int64_t num_splits, int causal,
+                                                     int64_t window_left, int64_t window_right, int with_sinks) {
+    if (!fp8_varlen_ws_args_ok(batch, heads_q, heads_kv, total_q, max_seqlen_q, cache_len, head_dim, num_splits, window_left, window_right))
+        return 0;
+    if (total_q == 0 || max_seqlen_q == 0) return 0;
+    const int64_t S = fp8_kv_splits_varlen(batch, heads_q, heads_kv, max_seqlen_q, cache_len, num_splits, causal, window_left, window_right, with_sinks);
+    return fa::kv_workspace_bytes(1, heads_q, total_q, head_dim, (int)S);
+}
+
+int fa_fp8_forward_kvcache_varlen(const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const float* q_descale, const float* k_descale,
+        const float* v_descale, const int32_t* cache_seqlens, const int32_t* block_table, const int32_t* cache_batch_idx,
+        int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t cache_batch, int64_t head_dim,
+        int dtype, int q_dtype, int cache_dtype, int64_t q_batch_stride, int64_t q_token_stride, int64_t k_batch_stride,
+        int64_t k_token_stride, int64_t v_batch_stride, int64_t v_token_stride, int64_t block_table_row_stride, int64_t num_blocks,
+        int64_t page_block_size, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride, int64_t v_descale_batch_stride,
+        int causal, double softmax_scale, int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream,
+        int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads,
+        const int32_t* cu_seqlens_q, int64_t total_q, int64_t max_seqlen_q) {
+    Fp8KvCall c;
+    c.hdim = true; c.varlen = true;
+    c.q = q; c.k_cache = k_cache; c.v_cache = v_cache; c.o = o; c.lse = lse;
+    c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
+    c.cache_seqlens = cache_seqlens; c.block_table = block_table; c.cache_batch_idx = cache_batch_idx;
+    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.seqlen_q = seqlen_q; c.cache_len = cache_len; c.cache_batch = cache_batch;
+    c.d = head_dim; c.dtype = dtype; c.q_dtype = q_dtype; c.cache_dtype = cache_dtype;
+    c.q_bs = q_batch_stride; c.q_ts = q_token_stride; c.k_bs = k_batch_stride; c.k_ts = k_token_stride; c.v_bs = v_batch_stride;
+    c.v_ts = v_token_stride;
+    c.table_rs = block_table_row_stride; c.num_blocks = num_blocks; c.ps = page_block_size;
+    c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
+    c.causal = causal; c.scale = softmax_scale; c.num_splits = num_splits;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    c.mod.window_left = window_left; c.mod.window_right = window_right; c.mod.softcap = softcap; c.mod.sinks = sinks;
+    c.mod.sink_heads = sink_heads;
+    c.cu_seqlens_q = cu_seqlens_q; c.total_q = total_q; c.max_seqlen_q = max_seqlen_q;
+    return fp8_kvcache_impl("fa_fp8_forward_kvcache_varlen", c);
+}
+
+size_t fa_fp8_kvcache_step_varlen_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
+                                                  int64_t head_dim, int64_t num_splits, int causal, int64_t window_left, int64_t window_right,
+                                                  int with_sinks, int in_dtype, int with_q8_out, int64_t total_q, int64_t max_seqlen_q) {
+    const bool e4m3 = in_dtype == FA_DTYPE_E4M3;
+    if ((!e4m3 && in_dtype != FA_DTYPE_F16 && in_dtype != FA_DTYPE_BF16) || (e4m3 && with_q8_out)) return 0;
+    if (seqlen_q != 0) {   // the padded step at head_dim (a packed call is asked about with seqlen_q == 0)
+        if (total_q != 0 || max_seqlen_q != 0) return 0;
+        if (head_dim == 128)
+            return fa_fp8_kvcache_step_workspace_bytes(batch, heads_q, heads_kv, seqlen_q, cache_len, 128, num_splits, causal, window_left,
+                                                       window_right, with_sinks, in_dtype, with_q8_out);
+        const size_t att = fa_fp8_forward_kvcache_hdim_workspace_bytes(batch, heads_q, heads_kv, seqlen_q, cache_len, head_dim, num_splits, causal,
+                                                                       window_left, window_right, with_sinks);
+        if (!kv_ws_args_ok(batch, heads_q, heads_kv, seqlen_q, cache_len, head_dim, num_splits) || window_left < -1 || window_right < -1 ||
+            (head_dim != 64 && head_dim != 256))
+            return 0;
+        return fa::fp8kv_step_prep_bytes_varlen(batch, batch * seqlen_q, heads_q, head_dim, !e4m3 && !with_q8_out) + att;
+    }
+    if (!fp8_varlen_ws_args_ok(batch, heads_q, heads_kv, total_q, max_seqlen_q, cache_len, head_dim, num_splits, window_left, window_right))
+        return 0;
+    const int64_t S = fp8_kv_splits_varlen(batch, heads_q, heads_kv, max_seqlen_q, cache_len, num_splits, causal, window_left, window_right, with_sinks);
+    return fa::fp8kv_step_prep_bytes_varlen(batch, total_q, heads_q, head_dim, !e4m3 && !with_q8_out) +
+           fa::kv_workspace_bytes(1, heads_q, total_q, head_dim, (int)S);
+}
+
+int fa_fp8_kvcache_step_varlen(const void* q, void* k_cache, void* v_cache, void* o, float* lse, const float* q_descale, const float* k_descale,
+                               const float* v_descale, const int32_t* cache_seqlens, const int32_t* block_table, const int32_t* cache_batch_idx,
+                               int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t cache_batch,
+                               int64_t head_dim, int dtype, int q_dtype, int cache_dtype, int64_t q_batch_stride, int64_t q_token_stride,
+                               int64_t k_batch_stride, int64_t k_token_stride, int64_t v_batch_stride, int64_t v_token_stride,
+                               int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t q_descale_batch_stride,
+                               int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale,
+                               int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream, int64_t window_left,
+                               int64_t window_right, double softcap, const float* sinks, int64_t sink_heads, const void* k_new,
+                               const void* v_new, int64_t seqlen_new, int64_t k_new_batch_stride, int64_t k_new_token_stride,
+                               int64_t v_new_batch_stride, int64_t v_new_token_stride, int in_dtype, void* q8_out, int64_t q8_batch_stride,
+                               int64_t q8_token_stride, const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride,
+                               int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
+                               const int32_t* cu_seqlens_q, int64_t total_q, int64_t max_seqlen_q, const int32_t* cu_seqlens_k_new,
+                               int64_t total_k_new) {
+    const char* who = "fa_fp8_kvcache_step_varlen";
+    Fp8KvCall c;
+    c.hdim = true; c.varlen = true;
+    c.q = q; c.k_cache = k_cache; c.v_cache = v_cache; c.o = o; c.lse = lse;
+    c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
+    c.cache_seqlens = cache_seqlens; c.block_table = block_table; c.cache_batch_idx = cache_batch_idx;
+    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.seqlen_q = seqlen_q; c.cache_len = cache_len; c.cache_batch = cache_batch;
+    c.d = head_dim; c.dtype = dtype; c.q_dtype = q_dtype; c.cache_dtype = cache_dtype;
+    c.q_bs = q_batch_stride; c.q_ts = q_token_stride; c.k_bs = k_batch_stride; c.k_ts = k_token_stride; c.v_bs = v_batch_stride;
+    c.v_ts = v_token_stride;
+    c.table_rs = block_table_row_stride; c.num_blocks = num_blocks; c.ps = page_block_size;
+    c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
+    c.causal = causal; c.scale = softmax_scale; c.num_splits = num_splits;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    c.mod.window_left = window_left; c.mod.window_right = window_right; c.mod.softcap = softcap; c.mod.sinks = sinks;
+    c.mod.sink_heads = sink_heads;
+    c.cu_seqlens_q = cu_seqlens_q; c.total_q = total_q; c.max_seqlen_q = max_seqlen_q;
+    Fp8StepCall t;
+    t.k_new = k_new; t.v_new = v_new; t.seqlen_new = seqlen_new; t.kn_bs = k_new_batch_stride; t.kn_ts = k_new_token_stride;
+    t.vn_bs = v_new_batch_stride; t.vn_ts = v_new_token_stride; t.in_dtype = in_dtype;
+    t.q8_out = q8_out; t.q8_bs = q8_batch_stride; t.q8_ts = q8_token_stride;
+    t.rotary_cos = rotary_cos; t.rotary_sin = rotary_sin; t.cos_rs = rotary_cos_row_stride; t.sin_rs = rotary_sin_row_stride;
+    t.seqlen_ro = seqlen_ro; t.rotary_dim = rotary_dim; t.rotary_interleaved = rotary_interleaved;
+    t.cu_seqlens_k_new = cu_seqlens_k_new; t.total_k_new = total_k_new;
+    bool empty;
+    int64_t S = 1;
+    size_t need = 0;
+    if (const int rc = fp8_kvcache_check(who, c, &t, empty, S, need)) return rc;
+    if (empty) return FA_OK;
+    fa::Fp8StepArgs s;
+    s.kv = fp8_kvcache_args(c, S);
+    s.in_dtype = in_dtype; s.k_new = k_new; s.v_new = v_new; s.seqlen_new = seqlen_new;
+    s.kn_bs = t.kn_bs; s.kn_ts = t.kn_ts; s.vn_bs = t.vn_bs; s.vn_ts = t.vn_ts;
+    s.q8_out = q8_out; s.q8_bs = t.q8_bs; s.q8_ts = t.q8_ts;
+    s.rotary_cos = rotary_cos; s.rotary_sin = rotary_sin; s.rotary_cos_rs = t.cos_rs; s.rotary_sin_rs = t.sin_rs; s.rotary_dim = rotary_dim;
+    s.rotary_interleaved = rotary_interleaved ? 1 : 0;
+    s.rotary_q_per_token = (causal || window_left >= 0 || window_right >= 0) ? 1 : 0;   // the step's rule
+    s.cu_seqlens_k_new = cu_seqlens_k_new; s.total_k_new = total_k_new;
+    return launched(who, fa::launch_fp8_kvcache_step_varlen(s, c.mod, reinterpret_cast<hipStream_t>(stream)));
 }
 
 size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {

@@ -247,6 +247,27 @@ hipError_t launch_kv_combine_sink(void* o, float* lse, float* po, float* plse, i
     return hipGetLastError();
 }
 
+hipError_t launch_kv_combine_packed(void* o, float* lse, float* po, float* plse, const int* cu_seqlens_q, int64_t heads_q, int64_t total_q,
+                                    int64_t d, int dtype, int splits, const float* sinks, int sink_heads, hipStream_t st) {
+    KvParams p{};
+    p.o = (uint16_t*)o; p.lse = lse; p.po = po; p.plse = plse;
+    p.hq = (int)heads_q; p.d = (int)d;
+    p.cu_q = cu_seqlens_q; p.total_q = (int)total_q;   // (the combine tests cu_q against null and never reads it)
+    const long long nrows = (long long)total_q * heads_q;
+    const dim3 grid((unsigned)((nrows + 3) / 4));
+    if (sinks) {
+        if (dtype == 1) {
+            auto kernel = kv_combine_kernel<f16_tag, true, const float* __restrict__, int>;
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, p, splits, nrows, sinks, sink_heads);
+        } else {
+            auto kernel = kv_combine_kernel<bf16_tag, true, const float* __restrict__, int>;
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, p, splits, nrows, sinks, sink_heads);
+        }
+    } else if (dtype == 1) hipLaunchKernelGGL((kv_combine_kernel<f16_tag, false>), grid, dim3(256), 0, st, p, splits, nrows);
+    else hipLaunchKernelGGL((kv_combine_kernel<bf16_tag, false>), grid, dim3(256), 0, st, p, splits, nrows);
+    return hipGetLastError();
+}
+
 hipError_t launch_kvcache(const KvArgs& a, hipStream_t st) {
     if (a.qv) return launch_kvcache_mla(a, st);   // K and V of different widths with a second query operand: fa_mla.hip
     KvParams p = kv_make_params(a);

@@ -11,6 +11,10 @@
 //   kv_combine_kernel<Tag, false>   fa_decode.hip's combine, unchanged, over fp32 partials in kv_workspace_bytes' layout.
 // fa_fp8_forward_kvcache_mod (a sliding window, a softcap, attention sinks) launches fp8kv_split_mod_kernel
 // instead, and with sinks kv_combine_kernel<Tag, true>; a call without the three launches the two above as before.
+// fa_fp8_forward_kvcache_varlen (packed queries, cu_seqlens_q) launches fp8kv_split_mod_kernel's packed
+// instantiation (one more kernel argument, Fp8KvPacked) at every head dim, featured or not: sequence b owns the tokens kv_cu_range
+// gives it, rows = G nq_b, and a wave whose row tile lies past them leaves before its first load; for S > 1 a memset of the lse
+// partials (kPlseFill) and kv_combine_kernel in its packed mode, which leaves the rows that no sequence owns unwritten.
 //
 // One 64-key tile of a wave, lane l = (r = l & 31, h = l >> 5):
 //   S^T = K Q^T     A = K as it lies in memory: key k0 + 32 kb + r, head-dim bytes 64 M + 32 h .. + 31 (two 16-byte loads), B = the
@@ -27,7 +31,7 @@
 //                   banks.  The A operand of d block dvb is then the lane's 32 contiguous bytes at row 32 dvb + r, byte 32 h.
 //   v_descale enters once, in the epilogue, with 1 / l.  A row without a visible key gives o = 0, lse = -inf (l == 0).
 //
-// What is untrusted: cache_seqlens, block_table, cache_batch_idx and the descales are read on the device only.  len_b =
+// What is untrusted: cache_seqlens, block_table, cache_batch_idx, cu_seqlens_q and the descales are read on the device only.  len_b =
 // clamp(cache_seqlens[b], 0, capacity); a cache_batch_idx outside [0, B_cache) makes the sequence empty; a page outside
 // [0, num_blocks) reads as zero K and zero V and takes part with score 0; no table entry past ceil(len_b / ps) is read (a 16-key
 // group never straddles a page, ps % 16 == 0, and a group is looked up only if its first key lies below the split's end).  Bytes
@@ -42,6 +46,7 @@
 #include "fa_common.h"
 #include "fa_ex_common.h"
 #include "fa_kernels.h"
+#include "fa_decode_common.h"   // kv_cu_range, kPlseFill: the packed calls
 
 namespace fa {
 
@@ -342,15 +347,40 @@ struct Fp8KvMod {
 //   softcap  fwd_fp8in_mod_kernel's (fa_fp8_inputs.hip): the capped score, in log2 units, replaces the raw product before the
 //            mask, and the factor of what follows is 1.
 // Sinks are not this kernel's: they join in kv_combine_kernel<Tag, true>, once per row.
-template <typename Tag, bool PAGED, int D = 128>
-__global__ __launch_bounds__(64, D == 256 ? 1 : 2) void fp8kv_split_mod_kernel(const Fp8KvParams p, const Fp8KvMod md) {
+//
+// PACKED (fa_fp8_forward_kvcache_varlen): the kernel takes one more argument, Packed = (Fp8KvPacked), and
+// PACKED is "that argument is there" (an argument pack, as kv_combine_kernel's Sink: the padded instantiations keep their argument
+// list, and with it their instructions).  q and o are (total_q, H_q, D), lse and the partials (H_q, total_q)-major; sequence b owns
+// the nq_b tokens from tok0 that kv_cu_range gives it, and is the padded call on b alone: rows = G nq_b, coff = len_b - nq_b.  The
+// grid is sized for max_seqlen_q; a wave whose row tile starts at or past rows leaves before its first load.  Wave-uniform scalars.
+struct Fp8KvPacked {
+    const int* cu_q;                      // (B + 1,) untrusted device offsets
+    int total_q, max_q;
+};
+
+template <typename Tag, bool PAGED, int D = 128, typename... Packed>
+__global__ __launch_bounds__(64, D == 256 ? 1 : 2) void fp8kv_split_mod_kernel(const Fp8KvParams p, const Fp8KvMod md, const Packed... pk) {
+    constexpr bool PACKED = sizeof...(Packed) != 0;
+    static_assert(sizeof...(Packed) <= 1, "PACKED: (Fp8KvPacked) follows");
     constexpr int KT = 64, NDV = D / 32, NMQ = D / 64;
     __shared__ __attribute__((aligned(16))) char vt[kVtRowBytes * D];   // V^T tile, [head dim][64 key bytes in P's key order]
     const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
     const int s = blockIdx.x, S = gridDim.x;
     const int hk = blockIdx.y % p.hkv, rt = blockIdx.y / p.hkv, b = blockIdx.z;
-    const int nq = p.nq, rows = p.rows, G = p.G;
+    int nq = p.nq, rows = p.rows;
+    const int G = p.G;
     const int pr0 = 32 * rt, pr = pr0 + r;                        // (the grid has ceil(rows / 32) row tiles: pr0 < rows)
+    [[maybe_unused]] long long tok0 = 0;                          // PACKED: the sequence's first token of q, o and lse
+    [[maybe_unused]] int total_q = 0;
+    if constexpr (PACKED) {
+        const Fp8KvPacked& pq = (pk, ...);
+        int st;
+        nq = kv_cu_range(pq.cu_q, b, pq.total_q, pq.max_q, st);
+        tok0 = st;
+        total_q = pq.total_q;
+        rows = G * nq;
+        if (pr0 >= rows) return;                                  // (wave-uniform) a tile past the sequence's rows: nothing loaded, nothing stored
+    }
 
     // the sequence: its length, and the cache row its keys lie in (contiguous)
     int lk = p.seqlens ? min(max(p.seqlens[b], 0), p.cap) : p.cap;
@@ -377,7 +407,7 @@ __global__ __launch_bounds__(64, D == 256 ? 1 : 2) void fp8kv_split_mod_kernel(c
 
     i32x8_t qb[NMQ];
     {
-        const uint8_t* qp = p.q + (long long)b * p.q_bs + (long long)qi * p.q_ts + hd * D + 32 * h;
+        const uint8_t* qp = p.q + (PACKED ? tok0 * p.q_ts : (long long)b * p.q_bs) + (long long)qi * p.q_ts + hd * D + 32 * h;
 #pragma unroll
         for (int M = 0; M < NMQ; ++M) {
             const u32x4 a0 = *reinterpret_cast<const u32x4*>(qp + 64 * M), a1 = *reinterpret_cast<const u32x4*>(qp + 64 * M + 16);
@@ -586,9 +616,10 @@ __global__ __launch_bounds__(64, D == 256 ? 1 : 2) void fp8kv_split_mod_kernel(c
     const bool dead = l_tot == 0.f;                      // no visible key: o = 0, lse = -inf (a NaN l is not dead: it propagates)
     const float inv = vd * (1.f / l_tot);                // v_descale once, with 1 / l
     const float lse_v = dead ? -INFINITY : (m_run + log2f(l_tot)) * 0.6931471805599453f;
-    const size_t row_id = ((size_t)b * p.hq + hd) * nq + qi;
+    // (PACKED: kv_combine_row's packed layout, row = h * total_q + packed token)
+    const size_t row_id = PACKED ? (size_t)hd * total_q + (size_t)(tok0 + qi) : ((size_t)b * p.hq + hd) * nq + qi;
     if (S == 1) {
-        uint16_t* orow = p.o + (((size_t)b * nq + qi) * p.hq + hd) * D;
+        uint16_t* orow = p.o + (PACKED ? (size_t)(tok0 + qi) * p.hq + hd : ((size_t)b * nq + qi) * p.hq + hd) * D;
 #pragma unroll
         for (int dvb = 0; dvb < NDV; ++dvb)
 #pragma unroll
@@ -722,6 +753,63 @@ hipError_t launch_fp8_kvcache_hdim(const Fp8KvArgs& a, const Fp8Mod& m, hipStrea
     if (m.sinks && a.num_splits < 2) return hipErrorInvalidValue;
     const Fp8KvMod md = fp8kv_mod_args(a, m);
     return launch_fp8_kvcache_t(a, &md, m.sinks, (int)(m.sink_heads > 0 ? m.sink_heads : 1), st);
+}
+
+// Packed queries (fa_fp8_forward_kvcache_varlen): a.cu_seqlens_q non-null, q / o (total_q, H_q, d), lse
+// (H_q, total_q).  Every call, featured or not, at every head dim runs fp8kv_split_mod_kernel<Tag, PAGED, D, Fp8KvPacked> on a grid
+// sized for max_seqlen_q; for S > 1 the lse partials are filled with kPlseFill bytes first (a memset node: rows that no sequence
+// owns keep it) and kv_combine_kernel runs in its packed mode.  The workspace is kv_workspace_bytes(1, H_q, total_q, d, S).
+hipError_t launch_fp8_kvcache_varlen(const Fp8KvArgs& a, const Fp8Mod& m, hipStream_t st) {
+    if (!a.cu_seqlens_q) return launch_fp8_kvcache_hdim(a, m, st);
+    if (a.total_q <= 0 || a.max_seqlen_q <= 0) return hipSuccess;
+    const int S = (int)a.num_splits;
+    if (m.sinks && S < 2) return hipErrorInvalidValue;
+    Fp8KvArgs pa = a;
+    pa.seqlen_q = a.max_seqlen_q;                        // what the window's right bound is canonicalised against (fp8kv_mod_args)
+    const Fp8KvMod md = fp8kv_mod_args(pa, m);
+    Fp8KvParams p;
+    p.q = (const uint8_t*)a.q; p.kc = (const uint8_t*)a.k_cache; p.vc = (const uint8_t*)a.v_cache;
+    p.o = (uint16_t*)a.o; p.lse = a.lse;
+    p.qds = a.q_descale; p.kds = a.k_descale; p.vds = a.v_descale;
+    p.qds_bs = a.qds_bs; p.kds_bs = a.kds_bs; p.vds_bs = a.vds_bs;
+    p.seqlens = a.cache_seqlens; p.table = a.block_table; p.bidx = a.cache_batch_idx;
+    p.tbl_rs = a.table_row_stride; p.nblk = (int)a.num_blocks; p.ps = (int)a.page_size; p.bcache = (int)a.cache_batch;
+    p.q_bs = 0; p.kc_bs = a.kc_bs; p.vc_bs = a.vc_bs;
+    p.q_ts = (int)a.q_ts; p.kc_ts = (int)a.kc_ts; p.vc_ts = (int)a.vc_ts;
+    p.hq = (int)a.heads_q; p.hkv = (int)a.heads_kv; p.G = (int)(a.heads_q / a.heads_kv);
+    p.nq = (int)a.max_seqlen_q; p.cap = (int)a.cache_len; p.rows = p.G * p.nq; p.causal = a.causal != 0;   // (nq, rows: the kernel takes its own)
+    p.c_log2 = a.scale * 1.4426950408889634f;
+    const size_t q_rows = (size_t)a.total_q * a.heads_q;
+    p.po = (float*)a.workspace;
+    p.plse = S > 1 ? (float*)((char*)a.workspace + ((q_rows * S * (size_t)a.d * 4 + 255) & ~(size_t)255)) : nullptr;
+    const Fp8KvPacked pk{a.cu_seqlens_q, (int)a.total_q, (int)a.max_seqlen_q};
+    if (S > 1) {
+        const hipError_t e = hipMemsetAsync(p.plse, kPlseFill, q_rows * S * 4, st);
+        if (e != hipSuccess) return e;
+    }
+    const dim3 grid((unsigned)S, (unsigned)(fp8kv_row_tiles(a.heads_q, a.heads_kv, a.max_seqlen_q) * p.hkv), (unsigned)a.batch);
+    {
+        route_hit(ROUTE_FP8KV_SPLIT_VARLEN);
+        ProfScope ps(K_FP8KV_SPLIT_VARLEN, st);
+        const bool paged = a.block_table != nullptr;
+        auto launch = [&](auto d_c) {
+            constexpr int DD = decltype(d_c)::value;
+            if (a.dtype == 2) {
+                if (paged) hipLaunchKernelGGL((fp8kv_split_mod_kernel<bf16_tag, true, DD, Fp8KvPacked>), grid, dim3(64), 0, st, p, md, pk);
+                else hipLaunchKernelGGL((fp8kv_split_mod_kernel<bf16_tag, false, DD, Fp8KvPacked>), grid, dim3(64), 0, st, p, md, pk);
+            } else {
+                if (paged) hipLaunchKernelGGL((fp8kv_split_mod_kernel<f16_tag, true, DD, Fp8KvPacked>), grid, dim3(64), 0, st, p, md, pk);
+                else hipLaunchKernelGGL((fp8kv_split_mod_kernel<f16_tag, false, DD, Fp8KvPacked>), grid, dim3(64), 0, st, p, md, pk);
+            }
+        };
+        if (a.d == 64) launch(std::integral_constant<int, 64>{});
+        else if (a.d == 128) launch(std::integral_constant<int, 128>{});
+        else launch(std::integral_constant<int, 256>{});
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || S == 1) return e;
+    return launch_kv_combine_packed(a.o, a.lse, p.po, p.plse, a.cu_seqlens_q, a.heads_q, a.total_q, a.d, a.dtype, S, m.sinks,
+                                    (int)(m.sink_heads > 0 ? m.sink_heads : 1), st);
 }
 
 }  // namespace fa

@@ -45,7 +45,7 @@ enum KernelId { K_FWD_F32 = 0, K_BWD_DELTA, K_BWD_DKDV_F32, K_BWD_DQ_F32, K_FWD_
                 K_FP8_QUANT, K_FWD_FP8, K_EX_FWD, K_EX_BWD, K_KV_GROUP_SUM, K_FP8IN_VT, K_FP8IN_FWD, K_FP8IN_VT_VARLEN,
                 K_FP8IN_FWD_VARLEN, K_IDX_PACK, K_IDX_LOGITS, K_IDX_TOPK, K_FP8KV_SPLIT, K_FP8Q_AMAX, K_FP8Q_QUANT, K_FP8Q_FUSED,
                 K_FP8IN_FWD_MOD, K_FP8IN_FWD_VARLEN_MOD, K_FP8KV_SPLIT_MOD, K_FP8KV_STEP_PREP, K_FP8IN_FWD_HDIM,
-                K_FP8IN_FWD_VARLEN_HDIM, K_FP8KV_SPLIT_HDIM, K_COUNT };
+                K_FP8IN_FWD_VARLEN_HDIM, K_FP8KV_SPLIT_HDIM, K_FP8KV_SPLIT_VARLEN, K_FP8KV_STEP_PREP_VARLEN, K_COUNT };
 void prof_begin(int id, hipStream_t st);
 void prof_end(int id, hipStream_t st);
 struct ProfScope {
@@ -70,10 +70,12 @@ int set_option(const char* name, int value);   // returns 0, or -1 for an unknow
 // "fp8_quant_fused", "fp8_quant_two_pass", "fp8_quant_static": the routes of the fp8 quantiser (fa_fp8_quantize.hip);
 // "fp8in_fwd_mod", "fp8in_fwd_varlen_mod", "fp8kv_split_mod": the featured kernels of the fp8 calls (window, softcap, sinks);
 // "fp8kv_step_prep": the append / rotary / q quantise launch of the fp8 decode step (fa_fp8_step.hip);
-// "fp8in_fwd_hdim", "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim": the fp8 calls at head dim 64 or 256 (the _hdim entry points).
+// "fp8in_fwd_hdim", "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim": the fp8 calls at head dim 64 or 256 (the _hdim entry points);
+// "fp8kv_split_varlen": the packed-query split kernel of fa_fp8_forward_kvcache_varlen / fa_fp8_kvcache_step_varlen;
+// "fp8kv_step_prep_varlen": the prep launch of fa_fp8_kvcache_step_varlen with packed tokens or at head dim 64 / 256.
 enum RouteId { ROUTE_DKDV_STREAM = 0, ROUTE_DKDV_LEAN, ROUTE_FP8Q_FUSED, ROUTE_FP8Q_TWO_PASS, ROUTE_FP8Q_STATIC, ROUTE_FP8IN_FWD_MOD,
                ROUTE_FP8IN_FWD_VARLEN_MOD, ROUTE_FP8KV_SPLIT_MOD, ROUTE_FP8KV_STEP_PREP, ROUTE_FP8IN_FWD_HDIM,
-               ROUTE_FP8IN_FWD_VARLEN_HDIM, ROUTE_FP8KV_SPLIT_HDIM, ROUTE_COUNT };
+               ROUTE_FP8IN_FWD_VARLEN_HDIM, ROUTE_FP8KV_SPLIT_HDIM, ROUTE_FP8KV_SPLIT_VARLEN, ROUTE_FP8KV_STEP_PREP_VARLEN, ROUTE_COUNT };
 void route_hit(int id);
 
 // exact-f32 kernels (fa_generic.hip): any dtype, d <= 256
@@ -522,6 +524,10 @@ struct Fp8KvArgs {
     int64_t num_splits = 1;                                 // >= 1 (the C layer resolves 0 through fp8kv_num_splits)
     void* workspace = nullptr;                              // kv_workspace_bytes(batch, heads_q, seqlen_q, d, num_splits)
     int64_t d = 128;                                        // the head dim: 128, or 64 / 256 through launch_fp8_kvcache_hdim alone
+    // launch_fp8_kvcache_varlen (null: the padded call): q and o (total_q, heads_q, d), lse (heads_q, total_q); sequence b owns the
+    // tokens kv_cu_range (fa_decode_common.h) gives it from the untrusted device offsets, at most max_seqlen_q; seqlen_q, q_bs unused
+    const int* cu_seqlens_q = nullptr;
+    int64_t total_q = 0, max_seqlen_q = 0;
 };
 int fp8kv_num_splits(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len);
 hipError_t launch_fp8_kvcache(const Fp8KvArgs& a, hipStream_t st);
@@ -532,6 +538,9 @@ hipError_t launch_fp8_kvcache(const Fp8KvArgs& a, hipStream_t st);
 int64_t fp8kv_split_len(int64_t cache_len, int64_t seqlen_q, int causal, const Fp8Mod& m);
 hipError_t launch_fp8_kvcache_mod(const Fp8KvArgs& a, const Fp8Mod& m, hipStream_t st);
 hipError_t launch_fp8_kvcache_hdim(const Fp8KvArgs& a, const Fp8Mod& m, hipStream_t st);
+// a.cu_seqlens_q == null: launch_fp8_kvcache_hdim.  Else the packed split kernel at a.d in {64, 128, 256}, a memset of the lse
+// partials and the packed combine for num_splits > 1; workspace: kv_workspace_bytes(1, heads_q, total_q, d, num_splits)
+hipError_t launch_fp8_kvcache_varlen(const Fp8KvArgs& a, const Fp8Mod& m, hipStream_t st);
 // The fp8 decode step (fa_fp8_step.hip; fa_fp8_kvcache_step): one launch of fp8kv_step_prep_kernel appends the new tokens to the
 // e4m3 cache, rotates and quantises q into a q8 buffer and writes len_eff[b] = L_b + seqlen_new; then launch_fp8_kvcache_mod runs
 // on kv with q = the q8 buffer and cache_seqlens = len_eff.  kv.q / kv.q_bs / kv.q_ts describe the caller's q (bytes), in in_dtype;
@@ -547,14 +556,26 @@ struct Fp8StepArgs {
     const void *rotary_cos = nullptr, *rotary_sin = nullptr;   // 16-bit mode only; rows in in_dtype at strides in elements
     int64_t rotary_cos_rs = 0, rotary_sin_rs = 0, rotary_dim = 0;
     int rotary_interleaved = 0, rotary_q_per_token = 0;
+    // launch_fp8_kvcache_step_varlen: k_new / v_new (total_k_new, heads_kv, d) by untrusted device offsets (null: padded, seqlen_new)
+    const int* cu_seqlens_k_new = nullptr;
+    int64_t total_k_new = 0;
 };
 size_t fp8kv_step_prep_bytes(int64_t batch, int64_t heads_q, int64_t seqlen_q, bool q8_in_workspace);   // the first two parts
 hipError_t launch_fp8_kvcache_step(const Fp8StepArgs& s, const Fp8Mod& m, hipStream_t st);
+// The step with packed q (kv.cu_seqlens_q), packed or padded new keys, at kv.d in {64, 128, 256} (fa_fp8_kvcache_step_varlen):
+// fp8kv_step_prep_varlen_kernel, then launch_fp8_kvcache_varlen on the q8 buffer and len_eff.  The workspace's first two parts:
+// len_eff (batch int32) and, with q8_in_workspace, q_tokens * heads_q * d code bytes (q_tokens: total_q, or batch * seqlen_q)
+size_t fp8kv_step_prep_bytes_varlen(int64_t batch, int64_t q_tokens, int64_t heads_q, int64_t d, bool q8_in_workspace);
+hipError_t launch_fp8_kvcache_step_varlen(const Fp8StepArgs& s, const Fp8Mod& m, hipStream_t st);
 // kv_combine_kernel<Tag, false> (fa_decode.hip) over partials in kv_workspace_bytes' layout, for a caller outside that file
 hipError_t launch_kv_combine(void* o, float* lse, float* po, float* plse, int64_t batch, int64_t heads_q, int64_t seqlen_q, int64_t d,
                              int dtype, int splits, hipStream_t st);
 // kv_combine_kernel<Tag, true>: the same with the sink column of head h, sinks[h % sink_heads]
 hipError_t launch_kv_combine_sink(void* o, float* lse, float* po, float* plse, int64_t batch, int64_t heads_q, int64_t seqlen_q, int64_t d,
                                   int dtype, int splits, const float* sinks, int sink_heads, hipStream_t st);
+// kv_combine_kernel in its packed mode (kv_combine_row: row = h * total_q + packed token; a row whose first lse partial still holds
+// the kPlseFill bytes belongs to no sequence and is left unwritten); sinks null: kv_combine_kernel<Tag, false>
+hipError_t launch_kv_combine_packed(void* o, float* lse, float* po, float* plse, const int* cu_seqlens_q, int64_t heads_q, int64_t total_q,
+                                    int64_t d, int dtype, int splits, const float* sinks, int sink_heads, hipStream_t st);
 
 }  // namespace fa

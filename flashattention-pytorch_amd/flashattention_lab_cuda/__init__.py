@@ -64,6 +64,8 @@ EXPORTED_C_SYMBOLS = (
     "fa_fp8_kvcache_step", "fa_fp8_kvcache_step_workspace_bytes",
     "fa_fp8_forward_hdim", "fa_fp8_forward_varlen_hdim", "fa_fp8_forward_kvcache_hdim",
     "fa_fp8_forward_hdim_workspace_bytes", "fa_fp8_forward_varlen_hdim_workspace_bytes", "fa_fp8_forward_kvcache_hdim_workspace_bytes",
+    "fa_fp8_forward_kvcache_varlen", "fa_fp8_forward_kvcache_varlen_workspace_bytes",
+    "fa_fp8_kvcache_step_varlen", "fa_fp8_kvcache_step_varlen_workspace_bytes",
 )
 
 
@@ -252,6 +254,14 @@ for _name in ("fa_fp8_forward", "fa_fp8_forward_varlen", "fa_fp8_forward_kvcache
 _sig("fa_fp8_forward_hdim_workspace_bytes", _hdim_fields(_SIGNATURES["fa_fp8_forward_workspace_bytes"][1]), _SIZE)
 _sig("fa_fp8_forward_varlen_hdim_workspace_bytes", _hdim_fields(_SIGNATURES["fa_fp8_forward_varlen_workspace_bytes"][1]), _SIZE)
 _sig("fa_fp8_forward_kvcache_hdim_workspace_bytes", _hdim_fields(_SIGNATURES["fa_fp8_forward_kvcache_workspace_bytes_mod"][1]), _SIZE)
+# packed queries (and new keys) on the fp8 decode call and the step: the _hdim / step list with head_dim, then the packed group
+_sig("fa_fp8_forward_kvcache_varlen", _SIGNATURES["fa_fp8_forward_kvcache_hdim"][1] + _fields("p:cu_seqlens_q i:total_q,max_seqlen_q"))
+_sig("fa_fp8_forward_kvcache_varlen_workspace_bytes",
+     _fields("i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,head_dim,num_splits c:causal") + _WINDOW + _fields("c:with_sinks"), _SIZE)
+_sig("fa_fp8_kvcache_step_varlen", _hdim_fields(_SIGNATURES["fa_fp8_kvcache_step"][1]) +
+     _fields("p:cu_seqlens_q i:total_q,max_seqlen_q p:cu_seqlens_k_new i:total_k_new"))
+_sig("fa_fp8_kvcache_step_varlen_workspace_bytes",
+     _hdim_fields(_SIGNATURES["fa_fp8_kvcache_step_workspace_bytes"][1]) + _fields("i:total_q,max_seqlen_q"), _SIZE)
 _KVWSV = _fields("i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,d,num_splits c:with_sinks")
 _sig("fa_ex_kvcache_workspace_bytes_varlen", _KVWSV, _SIZE)
 _sig("fa_ex_kvcache_workspace_bytes_qv", _KVWSV + _fields("i:d_v"), _SIZE)
@@ -317,6 +327,9 @@ for _name in ("fa_fp8_forward_hdim", "fa_fp8_forward_varlen_hdim", "fa_fp8_forwa
     _family(_name, [])
 _family("fa_fp8_quantize", [])
 _family("fa_fp8_kvcache_step", [])
+# packed queries / new keys and the step at 64 / 256: a family of one each, called with exactly its own arguments
+_family("fa_fp8_forward_kvcache_varlen", [])
+_family("fa_fp8_kvcache_step_varlen", [])
 _family("fa_ex_forward_kvcache_qv", ["fa_ex_forward_kvcache" + _suffix for _suffix in ("", "_paged", "_rotary", "_fp8", "_sink", "_varlen")])
 
 
@@ -2456,7 +2469,7 @@ def fp8_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_se
 
 def fp8_kvcache_forward(q, k_cache, v_cache, cache_seqlens=None, block_table=None, cache_batch_idx=None, q_descale=None, k_descale=None,
                         v_descale=None, softmax_scale=None, causal=False, num_splits=0, out_dtype=torch.bfloat16, *, window=(-1, -1),
-                        softcap=0.0, sinks=None, hdim=False):
+                        softcap=0.0, sinks=None, hdim=False, cu_seqlens_q=None, max_seqlen_q=None):
     """(o, lse) of fp8 KV-cache decoding (fa_fp8_forward_kvcache): q (B, Nq, H_q, 128) in torch.float8_e4m3fn at its own batch and
     token strides over the e4m3 caches (B_cache, cache_len, H_kv, 128), or with block_table (int32 (B, max_blocks_per_seq)) the pools
     (num_blocks, ps, H_kv, 128), at their own batch / page and token strides; nothing is copied.  cache_seqlens int32 (B,) on the
@@ -2464,8 +2477,13 @@ def fp8_kvcache_forward(q, k_cache, v_cache, cache_seqlens=None, block_table=Non
     1.  o (B, Nq, H_q, 128) in out_dtype, lse float32 (B, H_q, Nq).  Nothing is read on the host; the partials live in the shim's
     persistent workspace.  window, softcap and sinks (float32 (H_q,)) are fa_fp8_forward_kvcache_mod's; a call with none of them goes
     through fa_fp8_forward_kvcache.  hdim=True: through fa_fp8_forward_kvcache_hdim, with a last extent of 64, 128 or 256 (fp8_forward
-    has the rest)."""
+    has the rest).  cu_seqlens_q (int32 (B + 1,) on the device, never read on the host) with max_seqlen_q (an int): packed queries
+    through fa_fp8_forward_kvcache_varlen under the hdim rules; q is (total_q, H_q, d), o likewise and lse (H_q, total_q)."""
     who = "fp8_kvcache_forward"
+    if cu_seqlens_q is not None or max_seqlen_q is not None:
+        return _fp8_kvcache_packed(who, q, k_cache, v_cache, None, None, cache_seqlens, block_table, cache_batch_idx, q_descale, k_descale,
+                                   v_descale, softmax_scale, causal, num_splits, out_dtype, window, softcap, sinks, cu_seqlens_q,
+                                   max_seqlen_q, None, None, None, False, None)
     if isinstance(q, torch.Tensor) and q.dtype in (torch.float16, torch.bfloat16):
         raise NotImplementedError(f"{who}: q of dtype {q.dtype} is not supported (torch.float8_e4m3fn expected; a 16-bit q over an e4m3 "
                                   f"cache is flash_attn_with_kvcache(..., k_descale=, v_descale=))")
@@ -2580,7 +2598,8 @@ def fp8_kvcache_forward(q, k_cache, v_cache, cache_seqlens=None, block_table=Non
 
 def fp8_kvcache_step(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table=None, cache_batch_idx=None, q_descale=None,
                      k_descale=None, v_descale=None, softmax_scale=None, causal=False, num_splits=0, out_dtype=None, *, window=(-1, -1),
-                     softcap=0.0, sinks=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q8_out=None):
+                     softcap=0.0, sinks=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q8_out=None, cu_seqlens_q=None,
+                     max_seqlen_q=None, cu_seqlens_k_new=None, hdim=False):
     """(o, lse) of the fp8 decode step (fa_fp8_kvcache_step): the new tokens k_new, v_new (B, N_new, H_kv, 128) are appended to the
     e4m3 caches at cache_seqlens[b] (the lengths BEFORE the append: int32 (B,) on the device, or an int), q (B, Nq, H_q, 128) is
     rotated and quantised, and fp8_kvcache_forward's attention runs over the caches with the new tokens in them.  q, k_new, v_new are
@@ -2588,8 +2607,16 @@ def fp8_kvcache_step(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_tab
     in their dtype, are given) or all torch.float8_e4m3fn (copied and used as they are; no rotary, no q8_out).  q and the caches follow
     fp8_kvcache_forward's view rules (their own strides, never copied), the new tokens and the tables ex_kvcache_forward's (a dense
     copy where the kernel cannot address them).  q8_out: an e4m3 (B, Nq, H_q, 128) tensor that receives q's codes (16-bit mode),
-    else they stay in the workspace.  out_dtype defaults to q's dtype, bfloat16 for an e4m3 q.  Nothing is read on the host."""
+    else they stay in the workspace.  out_dtype defaults to q's dtype, bfloat16 for an e4m3 q.  Nothing is read on the host.
+    cu_seqlens_q with max_seqlen_q, cu_seqlens_k_new (int32 (B + 1,) device tensors, never read on the host) or hdim=True: through
+    fa_fp8_kvcache_step_varlen, at a last extent of 64, 128 or 256; with cu_seqlens_q q is packed (total_q, H_q, d), o and q8_out
+    likewise, lse (H_q, total_q); with cu_seqlens_k_new the new tokens are packed (total_k_new, H_kv, d).  Without any of the four the
+    function is what it was."""
     who = "fp8_kvcache_step"
+    if cu_seqlens_q is not None or max_seqlen_q is not None or cu_seqlens_k_new is not None or hdim:
+        return _fp8_kvcache_packed(who, q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, cache_batch_idx, q_descale, k_descale,
+                                   v_descale, softmax_scale, causal, num_splits, out_dtype, window, softcap, sinks, cu_seqlens_q,
+                                   max_seqlen_q, cu_seqlens_k_new, rotary_cos, rotary_sin, rotary_interleaved, q8_out)
     for name, t in (("q", q), ("k", k_new), ("v", v_new), ("k_cache", k_cache), ("v_cache", v_cache)):
         if not isinstance(t, torch.Tensor):
             raise RuntimeError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
@@ -2738,4 +2765,217 @@ def fp8_kvcache_step(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_tab
             bstride(v_cache), tstride(v_cache, hkv), *pages, qds, kds, vds, int(bool(causal)), scale, ns, ws.data_ptr(), ws.numel(),
             _stream_ptr(q.device), *tail, k_new.data_ptr(), v_new.data_ptr(), nnew, knb, knt, vnb, vnt, code, *q8, *rotary))
     del keep_q, keep_k, keep_v, keep_s, _tabs
+    return o, lse
+
+
+def _fp8_kvcache_packed(who, q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, cache_batch_idx, q_descale, k_descale, v_descale,
+                        softmax_scale, causal, num_splits, out_dtype, window, softcap, sinks, cu_seqlens_q, max_seqlen_q, cu_seqlens_k_new,
+                        rotary_cos, rotary_sin, rotary_interleaved, q8_out):
+    """fp8_kvcache_forward (k_new is None) and fp8_kvcache_step through the _varlen entry points: packed queries (cu_seqlens_q), packed
+    or padded new keys, head dims 64 / 128 / 256.  The offsets are int32 (B + 1,) device tensors and are never read on the host."""
+    step = k_new is not None
+    tensors = [("q", q), ("k_cache", k_cache), ("v_cache", v_cache)] + ([("k", k_new), ("v", v_new)] if step else [])
+    for name, t in tensors:
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
+    packed = cu_seqlens_q is not None
+    if max_seqlen_q is not None and not packed:
+        raise RuntimeError(f"{who}: max_seqlen_q goes with cu_seqlens_q")
+    if cu_seqlens_k_new is not None and not packed:
+        raise RuntimeError(f"{who}: cu_seqlens_k_new needs cu_seqlens_q (packed new keys go with packed queries)")
+    if packed and (isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int)):
+        raise RuntimeError(f"{who}: max_seqlen_q (an int, the most query tokens of one sequence) is required with cu_seqlens_q")
+    if step:
+        if q.dtype not in (torch.float16, torch.bfloat16, torch.float8_e4m3fn):
+            raise NotImplementedError(f"{who}: q of dtype {q.dtype} is not supported (float16, bfloat16 or torch.float8_e4m3fn)")
+        if k_new.dtype != q.dtype or v_new.dtype != q.dtype:
+            raise NotImplementedError(f"{who}: mixed dtypes are not supported: q, k, v must be all float16, all bfloat16 or all "
+                                      f"torch.float8_e4m3fn (got {q.dtype}, {k_new.dtype}, {v_new.dtype})")
+    elif q.dtype != torch.float8_e4m3fn:
+        raise NotImplementedError(f"{who}: q of dtype {q.dtype} is not supported (torch.float8_e4m3fn expected)")
+    e4 = q.dtype == torch.float8_e4m3fn
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.dtype != torch.float8_e4m3fn:
+            raise NotImplementedError(f"{who}: {name} of dtype {t.dtype} is not supported (torch.float8_e4m3fn expected)")
+    if e4 and (rotary_cos is not None or rotary_sin is not None):
+        raise NotImplementedError(f"{who}: rotary_cos / rotary_sin are not supported with torch.float8_e4m3fn q, k, v (codes cannot be rotated)")
+    if e4 and q8_out is not None:
+        raise NotImplementedError(f"{who}: q8_out is not supported with a torch.float8_e4m3fn q (it is used in place)")
+    if out_dtype is None:
+        out_dtype = torch.bfloat16 if e4 else q.dtype
+    if out_dtype not in (torch.bfloat16, torch.float16):
+        raise NotImplementedError(f"{who}: out_dtype {out_dtype} is not supported (torch.bfloat16 or torch.float16)")
+    paged = block_table is not None
+    if paged and cache_batch_idx is not None:
+        raise NotImplementedError(f"{who}: block_table together with cache_batch_idx is not supported (a table row is the indirection)")
+    for name, t in (("block_table", block_table), ("cache_batch_idx", cache_batch_idx), ("cu_seqlens_q", cu_seqlens_q),
+                    ("cu_seqlens_k_new", cu_seqlens_k_new)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.int32):
+            dt = t.dtype if isinstance(t, torch.Tensor) else type(t).__name__
+            raise NotImplementedError(f"{who}: {name} of dtype {dt} is not supported (int32 tensor expected)")
+    qdim = 3 if packed else 4
+    if q.dim() != qdim or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
+        raise RuntimeError(f"{who}: q must be " + ("packed (total_q, H_q, d)" if packed else "(B, Nq, H_q, d)") + " and k_cache, v_cache " +
+                           ("pools (num_blocks, page_block_size, H_kv, d)" if paged else "(B_cache, cache_len, H_kv, d)") +
+                           f" of one shape; got {tuple(q.shape)}, {tuple(k_cache.shape)}, {tuple(v_cache.shape)}")
+    d = _fp8_head_dim(who, True, **dict(tensors))
+    hq, hkv = q.shape[-2], k_cache.shape[2]
+    if hkv == 0 or hq == 0 or hq % hkv != 0:
+        raise RuntimeError(f"{who}: H_q = {hq} must be a multiple of H_kv = {hkv}")
+    if packed:
+        if cu_seqlens_q.dim() != 1 or cu_seqlens_q.shape[0] < 1:
+            raise RuntimeError(f"{who}: cu_seqlens_q must be an int32 (B + 1,) tensor, got {tuple(cu_seqlens_q.shape)}")
+        b, total_q, nq = cu_seqlens_q.shape[0] - 1, q.shape[0], 0
+        if max_seqlen_q < 0 or max_seqlen_q > total_q:
+            raise RuntimeError(f"{who}: max_seqlen_q = {max_seqlen_q} must lie in [0, total_q = {total_q}]")
+    else:
+        b, total_q, nq, max_seqlen_q = q.shape[0], 0, q.shape[1], 0
+    packed_kn = cu_seqlens_k_new is not None
+    nnew = total_kn = 0
+    if step:
+        if packed_kn:
+            if cu_seqlens_k_new.shape != (b + 1,):
+                raise RuntimeError(f"{who}: cu_seqlens_k_new must be an int32 (B + 1,) = ({b + 1},) tensor, got {tuple(cu_seqlens_k_new.shape)}")
+            if k_new.dim() != 3 or k_new.shape[1] != hkv or v_new.shape != k_new.shape:
+                raise RuntimeError(f"{who}: k and v must be packed (total_k_new, H_kv, d) = (., {hkv}, {d}) tensors of one shape; got "
+                                   f"{tuple(k_new.shape)}, {tuple(v_new.shape)}")
+            total_kn = k_new.shape[0]
+        else:
+            if k_new.dim() != 4 or k_new.shape[0] != b or k_new.shape[1] < 1 or k_new.shape[2] != hkv or v_new.shape != k_new.shape:
+                raise RuntimeError(f"{who}: k and v must be (B, N_new >= 1, H_kv, d) = ({b}, ., {hkv}, {d}) tensors of one shape; got "
+                                   f"{tuple(k_new.shape)}, {tuple(v_new.shape)}")
+            nnew = k_new.shape[1]
+        if cache_seqlens is None:
+            raise RuntimeError(f"{who}: cache_seqlens is required (the lengths before the append: an int32 (B,) tensor or an int)")
+    if isinstance(cache_seqlens, int) and not isinstance(cache_seqlens, bool):
+        cache_seqlens = torch.full((b,), cache_seqlens, dtype=torch.int32, device=q.device)
+    if cache_seqlens is not None and not (isinstance(cache_seqlens, torch.Tensor) and cache_seqlens.dtype == torch.int32 and
+                                          cache_seqlens.shape == (b,)):
+        raise RuntimeError(f"{who}: cache_seqlens must be an int32 tensor of shape (B,) = ({b},), an int or None")
+    rot = rotary_cos is not None or rotary_sin is not None
+    rdim = 0
+    if rot:
+        if rotary_cos is None or rotary_sin is None:
+            raise RuntimeError(f"{who}: rotary_cos and rotary_sin must be given together")
+        for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+            if not isinstance(t, torch.Tensor) or t.dtype != q.dtype or t.dim() != 2 or t.shape != rotary_cos.shape or t.numel() == 0:
+                raise RuntimeError(f"{who}: {name} must be a (seqlen_ro, rotary_dim / 2) tensor of q's dtype, rotary_cos and rotary_sin of "
+                                   f"one shape")
+        rdim = 2 * rotary_cos.shape[1]
+        if rdim % 16 != 0 or not 16 <= rdim <= d:
+            raise RuntimeError(f"{who}: rotary_dim = 2 * rotary_cos.shape[1] must be a multiple of 16 in [16, {d}], got {rdim}")
+    if q8_out is not None and not (isinstance(q8_out, torch.Tensor) and q8_out.dtype == torch.float8_e4m3fn and q8_out.shape == q.shape):
+        raise RuntimeError(f"{who}: q8_out must be a torch.float8_e4m3fn tensor of q's shape {tuple(q.shape)}")
+    every = [t for t in (q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, cache_batch_idx, cu_seqlens_q, cu_seqlens_k_new,
+                         rotary_cos, rotary_sin, q8_out) if t is not None]
+    for t in every:
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: tensors must be on the GPU (HIP device); there is no CPU path")
+    if len({t.device for t in every}) != 1:
+        raise RuntimeError(f"{who}: all tensors must be on one device")
+    scale = d ** -0.5 if softmax_scale is None else float(softmax_scale)
+    if not (math.isfinite(scale) and scale > 0.0):
+        raise RuntimeError(f"{who}: softmax_scale must be finite and > 0 (got {scale})")
+    ns = operator.index(num_splits)
+    if ns < 0 or ns > 256:
+        raise RuntimeError(f"{who}: num_splits must lie in [0, 256] (got {ns})")
+    # views: (tensor, heads, the dim of its tokens); a batch dim, where there is one, is dim 0
+    views = [("q", q, hq, qdim - 3), ("k_cache", k_cache, hkv, 1), ("v_cache", v_cache, hkv, 1)]
+    if q8_out is not None:
+        views.append(("q8_out", q8_out, hq, qdim - 3))
+    for name, t, heads, tdim in views:
+        unit = 16 // t.element_size()
+        if t.numel() and ((heads > 1 and t.stride(-2) != d) or t.stride(-1) != 1):
+            raise ValueError(f"{who}: {name} must have adjacent heads with a contiguous last dim (strides {t.stride()})")
+        if t.numel() and (t.data_ptr() % 16 != 0 or any(t.stride(i) % unit != 0 or t.stride(i) < 0 for i in range(tdim + 1)) or
+                          (t.shape[tdim] > 1 and t.stride(tdim) < heads * d)):
+            raise ValueError(f"{who}: {name} is a view the kernel cannot address: a 16-byte aligned start, batch and token strides that "
+                             f"are multiples of 16 bytes and rows that do not overlap are needed (strides {t.stride()})")
+    bstride = lambda t: (max(t.stride(0), 0) if t.dim() == 4 and t.shape[0] > 1 else 0) * t.element_size()   # noqa: E731
+    tstride = lambda t, heads: (t.stride(-3) if t.shape[-3] > 1 else heads * d) * t.element_size()   # noqa: E731
+    if paged:
+        nblk, ps = k_cache.shape[0], k_cache.shape[1]
+        if ps < 16 or ps % 16 != 0:
+            raise RuntimeError(f"{who}: page_block_size must be a positive multiple of 16, got {ps}")
+        if block_table.dim() != 2 or block_table.shape[0] != b or block_table.shape[1] < 1:
+            raise RuntimeError(f"{who}: block_table must be an int32 (B, max_blocks_per_seq >= 1) tensor, B = {b}; got "
+                               f"{tuple(block_table.shape)}")
+        if nblk < 1:
+            raise RuntimeError(f"{who}: the pools must hold at least one page")
+        if block_table.stride(1) != 1 and block_table.shape[1] > 1:
+            block_table = block_table.contiguous()
+        cap, cbatch = block_table.shape[1] * ps, 0
+        pages = (max(block_table.stride(0), block_table.shape[1]), nblk, ps)
+    else:
+        cap = k_cache.shape[1]
+        if cap < 1:
+            raise RuntimeError(f"{who}: the caches must hold at least one token")
+        if cache_batch_idx is not None:
+            if cache_batch_idx.shape != (b,):
+                raise RuntimeError(f"{who}: cache_batch_idx must be an int32 tensor of shape (B,) = ({b},)")
+            cache_batch_idx = cache_batch_idx.contiguous()
+            cbatch = k_cache.shape[0]
+        elif k_cache.shape[0] != b:
+            raise RuntimeError(f"{who}: the caches hold {k_cache.shape[0]} rows for a batch of {b} (pass cache_batch_idx to select rows)")
+        else:
+            cbatch = 0
+        pages = (0, 0, 0)
+    if step and not packed_kn and nnew > cap:
+        raise RuntimeError(f"{who}: N_new = {nnew} new tokens do not fit the capacity {cap}")
+    ro_need = cap + (max_seqlen_q if packed else max(0, nq - nnew))
+    if rot and rotary_cos.shape[0] < ro_need:
+        raise RuntimeError(f"{who}: rotary_cos / rotary_sin have {rotary_cos.shape[0]} rows; the capacity {cap} + " +
+                           ("max_seqlen_q" if packed else "max(0, Nq - N_new)") + f" = {ro_need} are needed")
+    if cache_seqlens is not None:
+        cache_seqlens = cache_seqlens.contiguous()
+    if packed:
+        cu_seqlens_q = cu_seqlens_q.contiguous()
+    if packed_kn:
+        cu_seqlens_k_new = cu_seqlens_k_new.contiguous()
+    qdp, qds, keep_q = _kv_descale(who, "q_descale", q_descale, q, b, hkv)
+    kdp, kds, keep_k = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
+    vdp, vds, keep_v = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
+    _mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks, True)
+    code = _E4M3_CODE if e4 else _DTYPE_CODE[q.dtype]
+    with torch.cuda.device(q.device):
+        o = torch.empty((total_q, hq, d) if packed else (b, nq, hq, d), dtype=out_dtype, device=q.device)
+        lse = torch.empty((hq, total_q) if packed else (b, hq, nq), dtype=torch.float32, device=q.device)
+        if b == 0 or (not step and (total_q == 0 or max_seqlen_q == 0 if packed else nq == 0)):
+            return o, lse
+        head = (q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp,
+                cache_seqlens.data_ptr() if cache_seqlens is not None else 0, block_table.data_ptr() if paged else 0,
+                cache_batch_idx.data_ptr() if cache_batch_idx is not None else 0, b, hq, hkv, nq, cap, cbatch, d, _DTYPE_CODE[out_dtype], code,
+                _E4M3_CODE, bstride(q), tstride(q, hq), bstride(k_cache), tstride(k_cache, hkv), bstride(v_cache), tstride(v_cache, hkv),
+                *pages, qds, kds, vds, int(bool(causal)), scale, ns)
+        group = (cu_seqlens_q.data_ptr() if packed else 0, total_q, max_seqlen_q)
+        if not step:
+            if packed:
+                need = int(_lib.fa_fp8_forward_kvcache_varlen_workspace_bytes(b, hq, hkv, total_q, max_seqlen_q, cap, d, ns, int(bool(causal)),
+                                                                              tail[0], tail[1], int(sinks is not None)))
+            else:
+                need = int(_lib.fa_fp8_forward_kvcache_hdim_workspace_bytes(b, hq, hkv, nq, cap, d, ns, int(bool(causal)), tail[0], tail[1],
+                                                                            int(sinks is not None)))
+            ws = _workspace(q.device, need)
+            _call("fa_fp8_forward_kvcache_varlen", (*head, ws.data_ptr() if need else 0, ws.numel() if need else 0, _stream_ptr(q.device),
+                                                    *tail, *group))
+        else:
+            k_new, v_new = k_new.contiguous(), v_new.contiguous()
+            esz = q.element_size()
+            if packed_kn:
+                knb = vnb = 0
+                knt = vnt = hkv * d * esz
+            else:
+                knb, knt = (x * esz for x in _kv_strides(who, "k", k_new, hkv, d, False))
+                vnb, vnt = (x * esz for x in _kv_strides(who, "v", v_new, hkv, d, False))
+            _tabs, rotary = _rotary_tables(rotary_cos, rotary_sin, rdim, rotary_interleaved)
+            need = int(_lib.fa_fp8_kvcache_step_varlen_workspace_bytes(b, hq, hkv, nq, cap, d, ns, int(bool(causal)), tail[0], tail[1],
+                                                                       int(sinks is not None), code, int(q8_out is not None), total_q,
+                                                                       max_seqlen_q))
+            ws = _workspace(q.device, need)
+            q8 = (q8_out.data_ptr(), bstride(q8_out), tstride(q8_out, hq)) if q8_out is not None else (0, 0, 0)
+            _call("fa_fp8_kvcache_step_varlen", (*head, ws.data_ptr(), ws.numel(), _stream_ptr(q.device), *tail, k_new.data_ptr(),
+                                                 v_new.data_ptr(), nnew, knb, knt, vnb, vnt, code, *q8, *rotary, *group,
+                                                 cu_seqlens_k_new.data_ptr() if packed_kn else 0, total_kn))
+            del _tabs
+    del keep_q, keep_k, keep_v, keep_s
     return o, lse

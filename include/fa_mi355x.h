@@ -1463,6 +1463,85 @@ size_t fa_fp8_kvcache_step_workspace_bytes(int64_t batch, int64_t heads_q, int64
                                            int64_t d, int64_t num_splits, int causal, int64_t window_left, int64_t window_right,
                                            int with_sinks, int in_dtype, int with_q8_out);
 
+/* --- Packed queries and new keys on the fp8 decode call and the fp8 decode step, and the step at head dims 64 / 256 (DESIGN.md
+ * 9zf): FlashAttention-3's cu_seqlens_q / cu_seqlens_k_new / max_seqlen_q as fa_ex_forward_kvcache_varlen states them.  Two
+ * families of one, each with its size function.
+ * fa_fp8_forward_kvcache_varlen takes fa_fp8_forward_kvcache_hdim's list followed by cu_seqlens_q, total_q, max_seqlen_q.  With
+ * NULL, 0, 0 it IS the _hdim call: the same checks, launches and routes.  With cu_seqlens_q (int32 (batch + 1,) device memory) q is
+ * packed (total_q, heads_q, head_dim) at q_token_stride, o is dense (total_q, heads_q, head_dim), lse (heads_q, total_q); seqlen_q
+ * and q_batch_stride are not used.  Sequence b owns the tokens [start, start + nq_b) with start = clamp(cu[b], 0, total_q) and nq_b
+ * = clamp(cu[b + 1] - cu[b], 0, min(max_seqlen_q, total_q - start)) (kv_cu_range, csrc/fa_decode_common.h): whatever the array
+ * holds, nothing outside q is read and nothing outside o, lse and the workspace written.  Every sequence gets, bit for bit, what the
+ * padded call returns for it alone (batch 1, its own tokens, its cache row / table row / cache_batch_idx entry / descale row, the
+ * same num_splits, window, softcap and sinks): len_b = clamp(cache_seqlens[b], 0, cache_len), the causal diagonal is len_b - nq_b.
+ * nq_b == 0 writes nothing; rows of o / lse that no sequence owns keep their contents.  total_q == 0 or max_seqlen_q == 0 is the
+ * empty call (FA_OK).
+ * Kernels: fp8kv_split_mod_kernel's packed instantiation on the grid (S, ceil(max_seqlen_q * G / 32) * heads_kv, batch), route and
+ * profile scope "fp8kv_split_varlen", one count a call, at every head dim and with or without a window, a softcap or sinks; for S >
+ * 1 a memset of the lse partials (a graph node) and kv_combine_kernel in its packed mode.  num_splits == 0 takes the parents' rule
+ * over ceil(max_seqlen_q * G / 32) row tiles, and a window is measured against max_seqlen_q.  Nothing is read on the host; a
+ * captured call replays after offsets, lengths, table and descales changed in place (total_q, max_seqlen_q fixed by the capture).
+ * fa_fp8_forward_kvcache_varlen_workspace_bytes: S * total_q * heads_q * (head_dim + 1) floats for S > 1, each of the two parts
+ * rounded up to 256 bytes; sinks raise S to at least 2; 0 for one split and for arguments the call would refuse.
+ *
+ * fa_fp8_kvcache_step_varlen takes fa_fp8_kvcache_step's list with head_dim in {64, 128, 256}, followed by cu_seqlens_q, total_q,
+ * max_seqlen_q, cu_seqlens_k_new, total_k_new.  With the five NULL / 0 and head_dim == 128 it IS fa_fp8_kvcache_step, launch for
+ * launch; with the five NULL / 0 at 64 / 256 it is the padded step at that width.  With cu_seqlens_q, q is packed as above and
+ * q8_out is (total_q, heads_q, head_dim) at q8_token_stride (q8_batch_stride unused).  The new keys are packed (total_k_new,
+ * heads_kv, head_dim) by cu_seqlens_k_new (clamped likewise, the bound being cache_len; seqlen_new and the batch strides of k_new,
+ * v_new unused), or padded (batch, seqlen_new, heads_kv, head_dim) when that array is NULL.  Per sequence: L_b =
+ * clamp(cache_seqlens[b], 0, cache_len - nnew_b), len_b = L_b + nnew_b, new key n is rotated at L_b + n, q token i at L_b + i when
+ * causal or a window bound >= 0 is given, else at L_b; nq_b == 0 still appends, nnew_b == 0 appends nothing.  The cache bytes, the
+ * q codes and o / lse are those of the padded step on the sequence alone.  Kernels: fp8kv_step_prep_varlen_kernel (route
+ * "fp8kv_step_prep_varlen", one count a call; every packed call and every call at 64 / 256), then the launches above on the q codes
+ * and len_b; total_q == 0 or max_seqlen_q == 0 launches the prep only.  Workspace: [len_b, batch int32 | the q codes, total_q *
+ * heads_q * head_dim bytes (batch * seqlen_q * .. padded), 16-bit mode without q8_out | the decode call's partials], each part
+ * rounded up to 256 bytes.  fa_fp8_kvcache_step_varlen_workspace_bytes: the step's list with head_dim, plus total_q, max_seqlen_q;
+ * seqlen_q == 0 asks about a packed call, seqlen_q != 0 (with total_q == max_seqlen_q == 0) about the padded one.
+ *
+ * Rules, both entry points: the parents' rules in the parents' order up to and including the window / softcap / sinks rules, with
+ * head_dim wherever a rule says 128 (token strides >= heads * head_dim elements, rotary_dim <= head_dim, head_dim outside {64, 128,
+ * 256}: FA_ERR_UNSUPPORTED "(64, 128 or 256)"), and with cu_seqlens_q without the rules on seqlen_q and q_batch_stride (with
+ * cu_seqlens_k_new: on seqlen_new and the batch strides of k_new / v_new).  Then the packed group, in this order: (P1) total_q and
+ * max_seqlen_q are 0 without cu_seqlens_q, total_k_new is 0 without cu_seqlens_k_new; (P2) cu_seqlens_k_new needs cu_seqlens_q;
+ * (P3) 0 <= max_seqlen_q <= total_q; (P4) total_q and total_k_new in [0, 2^31); (P5) max_seqlen_q * token stride of q and of
+ * q8_out below 2^31 bytes (FA_ERR_UNSUPPORTED, "span limit"); (P6) (heads_q / heads_kv) * max_seqlen_q <= 2^20, and the row tiles
+ * * heads_kv fit one launch (FA_ERR_UNSUPPORTED); (P7) with rotary tables seqlen_ro >= cache_len + max_seqlen_q; (P8) both arrays
+ * 4-byte aligned.  Last the parents' workspace rule.  Still refused: head dims 96 / 192 and block_table with cache_batch_idx. */
+int fa_fp8_forward_kvcache_varlen(const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const float* q_descale,
+                                 const float* k_descale, const float* v_descale, const int32_t* cache_seqlens, const int32_t* block_table,
+                                 const int32_t* cache_batch_idx, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q,
+                                 int64_t cache_len, int64_t cache_batch, int64_t head_dim, int dtype, int q_dtype, int cache_dtype,
+                                 int64_t q_batch_stride, int64_t q_token_stride, int64_t k_batch_stride, int64_t k_token_stride,
+                                 int64_t v_batch_stride, int64_t v_token_stride, int64_t block_table_row_stride, int64_t num_blocks,
+                                 int64_t page_block_size, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
+                                 int64_t v_descale_batch_stride, int causal, double softmax_scale, int64_t num_splits, void* workspace,
+                                 size_t workspace_bytes, void* stream, int64_t window_left, int64_t window_right, double softcap,
+                                 const float* sinks, int64_t sink_heads, const int32_t* cu_seqlens_q, int64_t total_q,
+                                 int64_t max_seqlen_q);
+size_t fa_fp8_forward_kvcache_varlen_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t max_seqlen_q,
+                                                     int64_t cache_len, int64_t head_dim, int64_t num_splits, int causal,
+                                                     int64_t window_left, int64_t window_right, int with_sinks);
+int fa_fp8_kvcache_step_varlen(const void* q, void* k_cache, void* v_cache, void* o, float* lse, const float* q_descale,
+                               const float* k_descale, const float* v_descale, const int32_t* cache_seqlens, const int32_t* block_table,
+                               const int32_t* cache_batch_idx, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q,
+                               int64_t cache_len, int64_t cache_batch, int64_t head_dim, int dtype, int q_dtype, int cache_dtype,
+                               int64_t q_batch_stride, int64_t q_token_stride, int64_t k_batch_stride, int64_t k_token_stride,
+                               int64_t v_batch_stride, int64_t v_token_stride, int64_t block_table_row_stride, int64_t num_blocks,
+                               int64_t page_block_size, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
+                               int64_t v_descale_batch_stride, int causal, double softmax_scale, int64_t num_splits, void* workspace,
+                               size_t workspace_bytes, void* stream, int64_t window_left, int64_t window_right, double softcap,
+                               const float* sinks, int64_t sink_heads, const void* k_new, const void* v_new, int64_t seqlen_new,
+                               int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t v_new_batch_stride,
+                               int64_t v_new_token_stride, int in_dtype, void* q8_out, int64_t q8_batch_stride, int64_t q8_token_stride,
+                               const void* rotary_cos, const void* rotary_sin, int64_t rotary_cos_row_stride,
+                               int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
+                               const int32_t* cu_seqlens_q, int64_t total_q, int64_t max_seqlen_q, const int32_t* cu_seqlens_k_new,
+                               int64_t total_k_new);
+size_t fa_fp8_kvcache_step_varlen_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
+                                                  int64_t head_dim, int64_t num_splits, int causal, int64_t window_left, int64_t window_right,
+                                                  int with_sinks, int in_dtype, int with_q8_out, int64_t total_q, int64_t max_seqlen_q);
+
 /* --- support entry points (no reference counterpart: the reference allocates inside the callee) --- */
 /* bytes for the CURRENT kernel mode: two float row constants per query row (+ an fp32 dQ scratch of bh*n*d floats in
  * FA_MODE_BWD_ATOMIC only); ask again after changing the mode */
@@ -1497,7 +1576,10 @@ int fa_profile_report(char* buf, size_t cap);
  * fa_fp8_forward_kvcache_mod, one count a call that launched one (a _mod call with default trailing arguments counts none).
  * "fp8kv_step_prep": the append / rotary / quantise launch of fa_fp8_kvcache_step, one count a call.  "fp8in_fwd_hdim",
  * "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim": the head dim 64 / 256 kernels of fa_fp8_forward_hdim, fa_fp8_forward_varlen_hdim and
- * fa_fp8_forward_kvcache_hdim, one count a call that launched one (head_dim 128 counts what the _mod call counts). */
+ * fa_fp8_forward_kvcache_hdim, one count a call that launched one (head_dim 128 counts what the _mod call counts).
+ * "fp8kv_split_varlen": the packed split kernel of fa_fp8_forward_kvcache_varlen and fa_fp8_kvcache_step_varlen;
+ * "fp8kv_step_prep_varlen": the prep launch of fa_fp8_kvcache_step_varlen with packed tokens or at head dim 64 / 256; one count a
+ * call that launched one (null packed groups count what the parent calls count). */
 int64_t fa_route_count(const char* name);
 
 #ifdef __cplusplus

@@ -72,7 +72,13 @@ unwindowed 32768-key row.
 at B 1 and 32, H 32:8, Nq = N_new = 1 over 8192 cached keys, contiguous and paged (ps 16), interleaved rounds: the step; its parent,
 fp8_kvcache_forward alone on the pre-filled cache (the difference is the prep launch); what gives the same effect without the step,
 the e4m3-cache call with a 16-bit q and the append; and the prep launch by its own profile scope against the bytes it moves.
-`--md PATH` writes the table as markdown."""
+`--md PATH` writes the table as markdown.
+`--fp8-varlen`: packed queries on the fp8 decode call and the step, H 32:8, 8192 cached keys, contiguous e4m3
+caches, interleaved rounds, three row kinds: `uniform`, the packed call on B = 32 sequences of Nq = 1 and of Nq = 4 tokens against
+the padded call on the same tokens (d = 128); `mixed`, one step of 63 one-token sequences plus one chunk of 128 tokens, as one packed
+fp8 step (num_splits by the rule, and 8) against the two padded fp8 steps that serve it today (d = 128); `step_hdim`, the fused step at d = 64 and 256 (B = 32, Nq =
+N_new = 1) against the three calls that served these widths: the e4m3-cache call with a 16-bit q and k=, v= (the only append there
+was; its own attention comes with it), quantize_fp8 on q, the fp8 decode call."""
 import argparse
 import json
 import os
@@ -673,6 +679,88 @@ def fp8_step_markdown(rows, args):
     return "\n".join(out)
 
 
+def fp8_varlen_rows(args, dtype):
+    """--fp8-varlen: see the module docstring"""
+    dev, rounds = "cuda", max(args.rounds, 5)
+    hq, hkv, L, cap = 32, 8, 8192, 8192 + 256
+    rows = []
+
+    def measure(kind, variants, **what):
+        ts = {n: [] for n in variants}
+        for _ in range(rounds):
+            for n, fn in variants.items():
+                ts[n].append(timed(fn, args.warmup, args.iters, 1))
+        med = {n: statistics.median(t) for n, t in ts.items()}
+        rows.append(dict(kind=kind, hq=hq, hkv=hkv, L=L, **what, us={n: round(v, 2) for n, v in med.items()},
+                         spread={n: round((max(t) - min(t)) / med[n], 3) for n, t in ts.items()}))
+        print(json.dumps(rows[-1]), flush=True)
+
+    def caches(b, d):
+        (kc, kd), (vc, vd) = (quantise(torch.randn((b, cap, hkv, d), device=dev, dtype=dtype)) for _ in range(2))
+        return kc, vc, kd, vd, torch.full((b, hkv), 2.0 ** -5, dtype=torch.float32, device=dev)
+
+    def codes(x):
+        return (x.float() * 32.0).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+
+    # uniform lengths: the packed call against the padded call on the same tokens
+    b, d = 32, 128
+    kc, vc, kd, vd, qd = caches(b, d)
+    sl = torch.full((b,), L, dtype=torch.int32, device=dev)
+    for nq in (1, 4):
+        q8 = codes(torch.randn((b, nq, hq, d), device=dev, dtype=dtype))
+        qp = q8.view(b * nq, hq, d)
+        cu = torch.arange(0, b * nq + 1, nq, dtype=torch.int32, device=dev)
+        measure("uniform", {
+            "padded": lambda: ext.fp8_kvcache_forward(q8, kc, vc, sl, None, None, qd, kd, vd, None, True, 0, dtype),
+            "packed": lambda: ext.fp8_kvcache_forward(qp, kc, vc, sl, None, None, qd, kd, vd, None, True, 0, dtype, cu_seqlens_q=cu,
+                                                      max_seqlen_q=nq)}, b=b, nq=nq, d=d)
+    del kc, vc
+    # the mixed step: 63 one-token decodes and one chunk of 128 tokens, one packed step against two padded steps
+    b, chunk = 64, 128
+    kc, vc, kd, vd, qd = caches(b, d)
+    sl = torch.full((b,), L, dtype=torch.int32, device=dev)
+    total = b - 1 + chunk
+    q16, kn, vn = (torch.randn((total, h, d), device=dev, dtype=dtype) for h in (hq, hkv, hkv))
+    cu = torch.tensor(list(range(b)) + [total], dtype=torch.int32, device=dev)
+    idx1, idx2 = torch.arange(b - 1, dtype=torch.int32, device=dev), torch.full((1,), b - 1, dtype=torch.int32, device=dev)
+    q1, k1, v1 = (t[:b - 1].view(b - 1, 1, -1, d) for t in (q16, kn, vn))
+    q2, k2, v2 = (t[b - 1:].view(1, chunk, -1, d) for t in (q16, kn, vn))
+
+    def two_padded():
+        ext.fp8_kvcache_step(q1, kc, vc, k1, v1, sl[:b - 1], None, idx1, qd[:b - 1], kd[:b - 1], vd[:b - 1], None, True, 0, dtype)
+        ext.fp8_kvcache_step(q2, kc, vc, k2, v2, sl[b - 1:], None, idx2, qd[b - 1:], kd[b - 1:], vd[b - 1:], None, True, 0, dtype)
+
+    measure("mixed", {
+        "two_padded_steps": two_padded,
+        "one_packed_step": lambda: ext.fp8_kvcache_step(q16, kc, vc, kn, vn, sl, None, None, qd, kd, vd, None, True, 0, dtype, cu_seqlens_q=cu,
+                                                        max_seqlen_q=chunk, cu_seqlens_k_new=cu),
+        # the rule counts the dense grid (B x ceil(max_seqlen_q G / 32) row tiles, most of which leave at once) and gives one split here
+        "one_packed_step_8_splits": lambda: ext.fp8_kvcache_step(q16, kc, vc, kn, vn, sl, None, None, qd, kd, vd, None, True, 8, dtype,
+                                                                 cu_seqlens_q=cu, max_seqlen_q=chunk, cu_seqlens_k_new=cu)},
+        b=b, chunk=chunk, d=d)
+    del kc, vc
+    # the fused step at 64 / 256 against the three calls that served these widths
+    b = 32
+    for d in (64, 256):
+        kc, vc, kd, vd, qd = caches(b, d)
+        sl, sl1 = (torch.full((b,), n, dtype=torch.int32, device=dev) for n in (L, L + 1))
+        q16 = torch.randn((b, 1, hq, d), device=dev, dtype=dtype)
+        kn, vn = (torch.randn((b, 1, hkv, d), device=dev, dtype=dtype) for _ in range(2))
+        q8 = torch.empty((b, 1, hq, d), dtype=torch.float8_e4m3fn, device=dev)
+
+        def chain():
+            ext.ex_kvcache_forward(q16, kc, vc, kn, vn, sl, False, None, k_descale=kd, v_descale=vd)   # (the append's call)
+            ext.fp8_quantize(q16, hq // hkv, qd, "bnhd", q8)
+            ext.fp8_kvcache_forward(q8, kc, vc, sl1, None, None, qd, kd, vd, None, False, 0, dtype, hdim=True)
+
+        measure("step_hdim", {
+            "append_quantize_decode": chain,
+            "fused_step": lambda: ext.fp8_kvcache_step(q16, kc, vc, kn, vn, sl, None, None, qd, kd, vd, None, False, 0, dtype, hdim=True)},
+            b=b, nq=1, d=d)
+        del kc, vc
+    return rows
+
+
 def parent_check(args, dtype):
     dev, b, h, n, d = "cuda", 2, 32, 4096, 128
     q, k, v = (torch.randn((b * n, h, d), device=dev, dtype=dtype) for _ in range(3))
@@ -714,6 +802,7 @@ def main():
     ap.add_argument("--fp8-q", action="store_true", help="time fp8 KV-cache decoding (e4m3 q) against the e4m3-cache call with a 16-bit q: see the module docstring")
     ap.add_argument("--fp8-mod", action="store_true", help="time the windowed fp8 decode call, its floor and the 16-bit-q call with the same window: see the module docstring")
     ap.add_argument("--fp8-step", action="store_true", help="time the fp8 decode step against its parent and the 16-bit-q call with the append: see the module docstring")
+    ap.add_argument("--fp8-varlen", action="store_true", help="time the packed fp8 decode call and step, and the step at d 64 / 256: see the module docstring")
     ap.add_argument("--md", default=None, help="--fp8-step: write the table as markdown to this path")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
@@ -729,6 +818,12 @@ def main():
         ext.ex_kvcache_forward(wq, wk, wk, None, None, wl, True, None)
     torch.cuda.synchronize()
     del wq, wk
+    if args.fp8_varlen:
+        rows = fp8_varlen_rows(args, dtype)
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(dict(fp8_varlen=True, dtype=args.dtype, version=ext.version(), rows=rows), f, indent=1)
+        return
     if args.fp8_step:
         rows = fp8_step_rows(args, dtype)
         if args.json:
