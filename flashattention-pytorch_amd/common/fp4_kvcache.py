@@ -1,0 +1,74 @@
+"""An MXFP4 KV cache under an fp8 query (C ABI: fa_fp4_kvcache_append, fa_fp4_forward_kvcache): half the
+bytes of the e4m3 cache per cached token, read by the matrix instruction in its own format.
+
+    mxfp4_kvcache_append           16-bit k, v -> e2m1 codes and E8M0 scales at cache_seqlens[b] + i, in place
+    fp8_attn_with_mxfp4_kvcache    e4m3 q over that cache: split-KV decoding, fp8_attn_with_kvcache's contract
+
+The cache, per K/V head at d = 128:
+    k_cache  uint8 (B_cache, cap, H_kv, 64), or a pool (num_blocks, ps, H_kv, 64): two e2m1 codes a byte, the low nibble the even
+             channel; code s eem, magnitudes 0, .5, 1, 1.5, 2, 3, 4, 6
+    k_scale  uint8 (.., H_kv, 4): one E8M0 byte per 32 channels (an OCP MX block), value 2^(byte - 127)
+    v_cache  as k_cache;  v_scale uint8 (.., H_kv): one E8M0 byte per (token, head)
+torch.float4_e2m1fn_x2 / torch.float8_e8m0fnu tensors are taken as well where torch has them.  Views at any batch / page / token
+strides are used in place (code rows 16-byte aligned, k_scale rows 4-byte aligned).  k_descale / v_descale (and q_descale) are the
+float32 (B, H_kv) or (H_kv,) scales of the fp8 calls and carry the global magnitude: value = code * 2^(scale byte - 127) * descale.
+
+Lengths, block_table and cache_batch_idx are untrusted device memory, never read on the host: a captured append + decode replays
+after they changed in place.  Refused by name (NotImplementedError): window_size, softcap, sinks, cu_seqlens_q / max_seqlen_q
+(packed queries), cache_leftpad, qv, rotary tables, head dims other than 128, 16-bit q, block_table with cache_batch_idx.  No
+gradient."""
+from __future__ import annotations
+
+import torch
+
+_REFUSED = dict(
+    window_size="a sliding window", softcap="a softcap", sinks="attention sinks", cu_seqlens_q="packed queries",
+    max_seqlen_q="packed queries", cu_seqlens_k_new="packed new keys", cache_leftpad="cache_leftpad", qv="qv (MLA)",
+    rotary_cos="rotary embedding", rotary_sin="rotary embedding", alibi_slopes="ALiBi", attn_bias="an additive bias")
+
+
+def _refuse(who, unsupported):
+    for name, val in unsupported.items():
+        if name not in _REFUSED:
+            raise TypeError(f"{who}() got an unexpected keyword argument '{name}'")
+        if isinstance(val, torch.Tensor) or val not in (None, False, 0, 0.0, (-1, -1), (None, None)):
+            raise NotImplementedError(f"{who}: {name} is not supported: the MXFP4 cache calls take no {_REFUSED[name]} (the e4m3 cache "
+                                      f"calls of common.fp8_attention do)")
+
+
+def _det(t):
+    return t.detach() if isinstance(t, torch.Tensor) else t
+
+
+def mxfp4_kvcache_append(k, v, k_cache, k_scale, v_cache, v_scale, *, cache_seqlens, block_table=None, cache_batch_idx=None,
+                         k_descale=None, v_descale=None, **unsupported):
+    """Append k, v (B, N_new, H_kv, 128) float16 / bfloat16 to the MXFP4 cache at positions cache_seqlens[b] + i (the lengths BEFORE
+    the append: int32 (B,) on the device or an int; clamped to [0, capacity] there and not modified).  Per block (32 channels of K,
+    the 128 of V) with x' = x * (1 / descale) in float32: e = the smallest integer with 6 * 2^e >= max |x'| in [-64, 64] (0 for an
+    all-zero block), scale byte e + 127, code = x' * 2^-e rounded to e2m1 (nearest, ties to the even code).  A token whose position,
+    page or cache row falls outside the cache is dropped.  Returns None; the four arrays are written in place."""
+    who = "mxfp4_kvcache_append"
+    _refuse(who, unsupported)
+    import flashattention_lab_cuda as ext
+
+    with torch.no_grad():
+        ext.fp4_kvcache_append(_det(k), _det(v), k_cache, k_scale, v_cache, v_scale, cache_seqlens, block_table, cache_batch_idx,
+                               _det(k_descale), _det(v_descale))
+
+
+def fp8_attn_with_mxfp4_kvcache(q, k_cache, k_scale, v_cache, v_scale, *, cache_seqlens=None, block_table=None, cache_batch_idx=None,
+                                q_descale=None, k_descale=None, v_descale=None, softmax_scale=None, causal=False, num_splits=0,
+                                out_dtype=torch.bfloat16, return_softmax_lse=False, **unsupported):
+    """o = softmax(softmax_scale q_descale k_descale q8 (k4 2^ek)^T [causal, bottom-right]) (v4 2^ev v_descale): q (B, Nq, H_q, 128)
+    torch.float8_e4m3fn over the MXFP4 cache.  GQA, cache_seqlens (None: full), block_table (ps % 16 == 0) or cache_batch_idx,
+    num_splits (0: the library's rule) as in fp8_attn_with_kvcache.  Returns o (B, Nq, H_q, 128) in out_dtype, with
+    return_softmax_lse also lse (B, H_q, Nq) float32.  A row without a visible key gives o = 0, lse = -inf."""
+    who = "fp8_attn_with_mxfp4_kvcache"
+    _refuse(who, unsupported)
+    import flashattention_lab_cuda as ext
+
+    with torch.no_grad():
+        o, lse = ext.fp4_kvcache_forward(_det(q), k_cache, k_scale, v_cache, v_scale, cache_seqlens, block_table, cache_batch_idx,
+                                         _det(q_descale), _det(k_descale), _det(v_descale), softmax_scale, bool(causal), num_splits,
+                                         out_dtype)
+    return (o, lse) if return_softmax_lse else o

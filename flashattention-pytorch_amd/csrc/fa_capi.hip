@@ -33,7 +33,7 @@ const char* const kKernelNames[fa::K_COUNT] = {"fwd_f32", "bwd_delta", "bwd_dkdv
                                                "fp8in_vt", "fp8in_fwd", "fp8in_vt_varlen", "fp8in_fwd_varlen", "idx_pack", "idx_logits",
                                                "idx_topk", "fp8kv_split", "fp8q_amax", "fp8q_quant", "fp8q_fused", "fp8in_fwd_mod",
                                                "fp8in_fwd_varlen_mod", "fp8kv_split_mod", "fp8kv_step_prep", "fp8in_fwd_hdim",
-    "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim", "fp8kv_split_varlen", "fp8kv_step_prep_varlen"};
+    "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim", "fp8kv_split_varlen", "fp8kv_step_prep_varlen", "fp4kv_append", "fp4kv_split"};
 
 hipEvent_t prof_get_event() {
     if (!g_prof_free.empty()) { hipEvent_t e = g_prof_free.back(); g_prof_free.pop_back(); return e; }
@@ -180,7 +180,7 @@ std::atomic<long long> g_route_hits[ROUTE_COUNT];
 constexpr const char* kRouteNames[ROUTE_COUNT] = {"dkdv_stream", "dkdv_lean", "fp8_quant_fused", "fp8_quant_two_pass", "fp8_quant_static",
                                                    "fp8in_fwd_mod", "fp8in_fwd_varlen_mod", "fp8kv_split_mod", "fp8kv_step_prep", "fp8in_fwd_hdim",
                                                    "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim", "fp8kv_split_varlen",
-                                                   "fp8kv_step_prep_varlen"};
+                                                   "fp8kv_step_prep_varlen", "fp4kv_append", "fp4kv_split"};
 void route_hit(int id) { g_route_hits[id].fetch_add(1, std::memory_order_relaxed); }
 long long route_count(const char* name) {
     for (int i = 0; i < ROUTE_COUNT; ++i)
@@ -3952,6 +3952,193 @@ size_t fa3_forward_workspace_bytes(int64_t bh, int64_t n, int64_t d, int dtype, 
     if (!fp8 || bh <= 0 || n <= 0 || d <= 0 || !fa::fwd_mfma_supported(dtype, d) || !fa::bwd_mfma_supported(dtype, d)) return 0;
     if (fa::fwd_fp8_supported(dtype, d)) return slab_bytes(bh, n, d) + fa::fwd_fp8_workspace_bytes(bh, n, d);
     return 3 * slab_bytes(bh, n, d);
+}
+
+// ---- the MXFP4 KV cache (fa_fp4_kvcache_append, fa_fp4_forward_kvcache): see include/fa_mi355x.h
+// What the two entry points share: the cache (fa::Fp4Cache), the batch, the head dim, the 16-bit dtype and the descales.
+struct Fp4Call {
+    fa::Fp4Cache c;
+    int64_t batch = 0, d = 0;
+    int dtype = 0;
+    const float *q_descale = nullptr, *k_descale = nullptr, *v_descale = nullptr;
+    int64_t qds_bs = 0, kds_bs = 0, vds_bs = 0;
+};
+
+// The rules both entry points share, in the header's order from (2) on: the head dim, the dtype, the cache's extents, alignment and
+// strides, the descales (nd of them), the pages, the span limits.
+static int fp4_cache_check(const char* who, const Fp4Call& k, int nd) {
+    const fa::Fp4Cache& c = k.c;
+    const bool paged = c.block_table != nullptr;
+    const int64_t kInt = ((int64_t)1 << 31) - 1, kMaxStride = (int64_t)1 << 44;
+    if (k.d != 128)
+        return fail(FA_ERR_UNSUPPORTED, "%s: head_dim %lld is not supported by the MXFP4 cache (128 only)", who, (long long)k.d);
+    if (k.dtype != FA_DTYPE_F16 && k.dtype != FA_DTYPE_BF16)
+        return fail(FA_ERR_UNSUPPORTED, "%s: dtype must be f16 or bf16 (got code %d)", who, k.dtype);
+    if (c.heads_kv < 1 || c.heads_kv > ((int64_t)1 << 20))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads_kv must lie in [1, 2^20] (got %lld)", who, (long long)c.heads_kv);
+    if (k.batch < 1 || k.batch > 65535) return fail(FA_ERR_INVALID_ARGUMENT, "%s: batch must lie in [1, 65535] (got %lld)", who, (long long)k.batch);
+    if (c.cache_len < 1) return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_len must be >= 1 (got %lld)", who, (long long)c.cache_len);
+    if (c.cache_batch_idx) {
+        if (c.cache_batch < 1 || c.cache_batch > kInt)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_batch must lie in [1, 2^31) with cache_batch_idx (got %lld)", who,
+                        (long long)c.cache_batch);
+    } else if (c.cache_batch != 0) {
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_batch must be 0 without cache_batch_idx (got %lld)", who, (long long)c.cache_batch);
+    }
+    if (!aligned16({c.k_cache, c.v_cache})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_cache and v_cache must be 16-byte aligned", who);
+    if ((uintptr_t)c.k_scale % 4 != 0 || (uintptr_t)c.cache_seqlens % 4 != 0 || (uintptr_t)c.block_table % 4 != 0 || (uintptr_t)c.cache_batch_idx % 4 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_scale, cache_seqlens, block_table and cache_batch_idx must be 4-byte aligned", who);
+    // (unit: what a stride must be a multiple of; least: the bytes of a token's heads)
+    const struct { const char* name; int64_t bs, ts, unit, least; } ts[4] = {
+        {"k_cache", c.kc_bs, c.kc_ts, 16, c.heads_kv * 64}, {"k_scale", c.ks_bs, c.ks_ts, 4, c.heads_kv * 4},
+        {"v_cache", c.vc_bs, c.vc_ts, 16, c.heads_kv * 64}, {"v_scale", c.vs_bs, c.vs_ts, 1, c.heads_kv}};
+    for (const auto& t : ts)
+        if (t.ts % t.unit != 0 || t.bs % t.unit != 0 || t.ts < t.least || t.ts > kMaxStride || t.bs < 0 || t.bs > kMaxStride)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (batch %lld, token %lld) must be multiples of %lld bytes and >= 0, "
+                        "the token stride >= %lld", who, t.name, (long long)t.bs, (long long)t.ts, (long long)t.unit, (long long)t.least);
+    const struct { const char* name; const float* p; int64_t bs; } ds[3] = {
+        {"k_descale", k.k_descale, k.kds_bs}, {"v_descale", k.v_descale, k.vds_bs}, {"q_descale", k.q_descale, k.qds_bs}};
+    for (int i = 0; i < nd; ++i) {
+        const auto& s = ds[i];
+        if (!s.p && s.bs != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: %s_batch_stride must be 0 without %s", who, s.name, s.name);
+        if (s.bs < 0 || (s.bs != 0 && s.bs < c.heads_kv) || s.bs >= ((int64_t)1 << 31) / k.batch)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: %s_batch_stride=%lld must be 0 or >= heads_kv=%lld", who, s.name, (long long)s.bs,
+                        (long long)c.heads_kv);
+        if ((uintptr_t)s.p % 4 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: %s must be 4-byte aligned", who, s.name);
+    }
+    if (paged) {
+        if (c.cache_batch_idx) return fail(FA_ERR_INVALID_ARGUMENT, "%s: block_table cannot be combined with cache_batch_idx", who);
+        if (c.page_size < 16 || c.page_size % 16 != 0 || c.page_size > 65536)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: page_block_size must be a multiple of 16 in [16, 65536] (got %lld)", who, (long long)c.page_size);
+        if (c.cache_len % c.page_size != 0)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_len=%lld (the capacity) must be a multiple of page_block_size=%lld", who,
+                        (long long)c.cache_len, (long long)c.page_size);
+        if (c.num_blocks < 1 || c.num_blocks > kInt)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_blocks must lie in [1, 2^31) (got %lld)", who, (long long)c.num_blocks);
+        if (c.table_row_stride < c.cache_len / c.page_size || c.table_row_stride > ((int64_t)1 << 40))
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: block_table_row_stride=%lld must be >= max_blocks_per_seq=%lld (and <= 2^40)", who,
+                        (long long)c.table_row_stride, (long long)(c.cache_len / c.page_size));
+    } else if (c.table_row_stride != 0 || c.num_blocks != 0 || c.page_size != 0) {
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: block_table_row_stride, num_blocks and page_block_size must be 0 without block_table", who);
+    }
+    const int64_t c_n = paged ? c.page_size : c.cache_len;
+    for (const auto& t : ts)
+        if (c_n * t.ts > kInt)
+            return fail(FA_ERR_UNSUPPORTED, "%s: span limit: tokens * token stride of %s is %lld bytes, at or above 2^31", who, t.name,
+                        (long long)(c_n * t.ts));
+    if (c.cache_len >= ((int64_t)1 << 28))
+        return fail(FA_ERR_UNSUPPORTED, "%s: span limit: cache_len = %lld (the capacity) is at or above 2^28", who, (long long)c.cache_len);
+    return FA_OK;
+}
+
+int fa_fp4_kvcache_append(const void* k_new, const void* v_new, void* k_cache, void* k_scale, void* v_cache, void* v_scale,
+                          const int32_t* cache_seqlens, const int32_t* block_table, const int32_t* cache_batch_idx, const float* k_descale,
+                          const float* v_descale, int64_t batch, int64_t heads_kv, int64_t seqlen_new, int64_t cache_len, int64_t cache_batch,
+                          int64_t d, int dtype, int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t v_new_batch_stride,
+                          int64_t v_new_token_stride, int64_t k_batch_stride, int64_t k_token_stride, int64_t k_scale_batch_stride,
+                          int64_t k_scale_token_stride, int64_t v_batch_stride, int64_t v_token_stride, int64_t v_scale_batch_stride,
+                          int64_t v_scale_token_stride, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
+                          int64_t descale_batch_stride, void* stream) {
+    const char* who = "fa_fp4_kvcache_append";
+    Fp4Call k;
+    k.c.k_cache = k_cache; k.c.k_scale = k_scale; k.c.v_cache = v_cache; k.c.v_scale = v_scale;
+    k.c.cache_seqlens = cache_seqlens; k.c.block_table = block_table; k.c.cache_batch_idx = cache_batch_idx;
+    k.c.heads_kv = heads_kv; k.c.cache_len = cache_len; k.c.cache_batch = cache_batch;
+    k.c.kc_bs = k_batch_stride; k.c.kc_ts = k_token_stride; k.c.ks_bs = k_scale_batch_stride; k.c.ks_ts = k_scale_token_stride;
+    k.c.vc_bs = v_batch_stride; k.c.vc_ts = v_token_stride; k.c.vs_bs = v_scale_batch_stride; k.c.vs_ts = v_scale_token_stride;
+    k.c.table_row_stride = block_table_row_stride; k.c.num_blocks = num_blocks; k.c.page_size = page_block_size;
+    k.batch = batch; k.d = d; k.dtype = dtype; k.k_descale = k_descale; k.v_descale = v_descale;
+    k.kds_bs = k_descale ? descale_batch_stride : 0; k.vds_bs = v_descale ? descale_batch_stride : 0;   // (one stride for both)
+    if (batch == 0 || seqlen_new == 0) return FA_OK;
+    if (!k_descale && !v_descale && descale_batch_stride != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: descale_batch_stride must be 0 without k_descale and v_descale", who);
+    if (!k_new || !v_new || !k_cache || !k_scale || !v_cache || !v_scale) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    if (!cache_seqlens) return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_seqlens is required (the lengths before the append)", who);
+    if (const int rc = fp4_cache_check(who, k, 2)) return rc;
+    if (seqlen_new < 1 || seqlen_new > ((int64_t)1 << 24))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_new must lie in [1, 2^24] (got %lld)", who, (long long)seqlen_new);
+    if (!aligned16({k_new, v_new})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_new and v_new must be 16-byte aligned", who);
+    const struct { const char* name; int64_t bs, ts; } ns[2] = {{"k_new", k_new_batch_stride, k_new_token_stride},
+                                                                 {"v_new", v_new_batch_stride, v_new_token_stride}};
+    for (const auto& t : ns)
+        if (t.ts % 16 != 0 || t.bs % 16 != 0 || t.ts < heads_kv * 256 || t.ts > ((int64_t)1 << 44) || t.bs < 0 || t.bs > ((int64_t)1 << 44))
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (batch %lld, token %lld) must be multiples of 16 bytes and >= 0, "
+                        "the token stride >= heads_kv * 256 = %lld", who, t.name, (long long)t.bs, (long long)t.ts, (long long)(heads_kv * 256));
+    if (seqlen_new * heads_kv * 8 > ((int64_t)1 << 31) - 256)
+        return fail(FA_ERR_UNSUPPORTED, "%s: span limit: seqlen_new * heads_kv = %lld is beyond one launch", who, (long long)(seqlen_new * heads_kv));
+    fa::Fp4AppendArgs a;
+    a.c = k.c; a.k_new = k_new; a.v_new = v_new; a.k_descale = k_descale; a.v_descale = v_descale;
+    a.kds_bs = k.kds_bs; a.vds_bs = k.vds_bs; a.batch = batch; a.seqlen_new = seqlen_new;
+    a.kn_bs = k_new_batch_stride; a.kn_ts = k_new_token_stride; a.vn_bs = v_new_batch_stride; a.vn_ts = v_new_token_stride;
+    a.dtype = dtype;
+    return launched(who, fa::launch_fp4_kvcache_append(a, reinterpret_cast<hipStream_t>(stream)));
+}
+
+// the e4m3 decode call's layout and split rule (the kernels share the 32-row tile and the combine)
+size_t fa_fp4_forward_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t d,
+                                              int64_t num_splits) {
+    return fa_fp8_forward_kvcache_workspace_bytes(batch, heads_q, heads_kv, seqlen_q, cache_len, d, num_splits);
+}
+
+int fa_fp4_forward_kvcache(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o, float* lse,
+                           const float* q_descale, const float* k_descale, const float* v_descale, const int32_t* cache_seqlens,
+                           const int32_t* block_table, const int32_t* cache_batch_idx, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                           int64_t seqlen_q, int64_t cache_len, int64_t cache_batch, int64_t d, int dtype, int64_t q_batch_stride,
+                           int64_t q_token_stride, int64_t k_batch_stride, int64_t k_token_stride, int64_t k_scale_batch_stride,
+                           int64_t k_scale_token_stride, int64_t v_batch_stride, int64_t v_token_stride, int64_t v_scale_batch_stride,
+                           int64_t v_scale_token_stride, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
+                           int64_t q_descale_batch_stride, int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal,
+                           double softmax_scale, int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "fa_fp4_forward_kvcache";
+    Fp4Call k;
+    k.c.k_cache = const_cast<void*>(k_cache); k.c.k_scale = const_cast<void*>(k_scale);
+    k.c.v_cache = const_cast<void*>(v_cache); k.c.v_scale = const_cast<void*>(v_scale);
+    k.c.cache_seqlens = cache_seqlens; k.c.block_table = block_table; k.c.cache_batch_idx = cache_batch_idx;
+    k.c.heads_kv = heads_kv; k.c.cache_len = cache_len; k.c.cache_batch = cache_batch;
+    k.c.kc_bs = k_batch_stride; k.c.kc_ts = k_token_stride; k.c.ks_bs = k_scale_batch_stride; k.c.ks_ts = k_scale_token_stride;
+    k.c.vc_bs = v_batch_stride; k.c.vc_ts = v_token_stride; k.c.vs_bs = v_scale_batch_stride; k.c.vs_ts = v_scale_token_stride;
+    k.c.table_row_stride = block_table_row_stride; k.c.num_blocks = num_blocks; k.c.page_size = page_block_size;
+    k.batch = batch; k.d = d; k.dtype = dtype; k.q_descale = q_descale; k.k_descale = k_descale; k.v_descale = v_descale;
+    k.qds_bs = q_descale_batch_stride; k.kds_bs = k_descale_batch_stride; k.vds_bs = v_descale_batch_stride;
+    if (batch == 0 || seqlen_q == 0) return FA_OK;
+    if (!q || !k_cache || !k_scale || !v_cache || !v_scale || !o || !lse) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    if (const int rc = fp4_cache_check(who, k, 3)) return rc;
+    if (heads_q < 1 || heads_q % heads_kv != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads_q=%lld must be a positive multiple of heads_kv=%lld", who, (long long)heads_q,
+                    (long long)heads_kv);
+    if (seqlen_q < 1 || heads_q > ((int64_t)1 << 20) || seqlen_q > ((int64_t)1 << 20) || (heads_q / heads_kv) * seqlen_q > ((int64_t)1 << 20))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: seqlen_q >= 1 and (heads_q / heads_kv) * seqlen_q = %lld * %lld <= 2^20 are needed", who,
+                    (long long)(heads_q / heads_kv), (long long)seqlen_q);
+    if (!(softmax_scale == softmax_scale) || !scale_ok(softmax_scale))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale must be finite and > 0", who);
+    if (!aligned16({q, o}) || (uintptr_t)lse % 4 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: q and o must be 16-byte aligned, lse 4-byte aligned", who);
+    if (q_token_stride % 16 != 0 || q_batch_stride % 16 != 0 || q_token_stride < heads_q * 128 || q_token_stride > ((int64_t)1 << 44) ||
+        q_batch_stride < 0 || q_batch_stride > ((int64_t)1 << 44))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of q (batch %lld, token %lld) must be multiples of 16 bytes and >= 0, the token "
+                    "stride >= heads_q * 128 = %lld", who, (long long)q_batch_stride, (long long)q_token_stride, (long long)(heads_q * 128));
+    if (seqlen_q * q_token_stride > ((int64_t)1 << 31) - 1)
+        return fail(FA_ERR_UNSUPPORTED, "%s: span limit: tokens * token stride of q is %lld bytes, at or above 2^31", who,
+                    (long long)(seqlen_q * q_token_stride));
+    const int64_t row_tiles = ((heads_q / heads_kv) * seqlen_q + 31) / 32;
+    if (row_tiles * heads_kv > 65535)
+        return fail(FA_ERR_UNSUPPORTED, "%s: span limit: row tiles * heads_kv = %lld is beyond 65535 for one launch", who,
+                    (long long)(row_tiles * heads_kv));
+    if (num_splits < 0 || num_splits > 256)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_splits must lie in [0, 256] (got %lld)", who, (long long)num_splits);
+    const int64_t S = fp8_kv_splits(batch, heads_q, heads_kv, seqlen_q, cache_len, num_splits);
+    const size_t need = fa::kv_workspace_bytes(batch, heads_q, seqlen_q, 128, (int)S);
+    if (need > 0) {
+        if (!workspace || workspace_bytes < need)
+            return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes is too small (need %zu: fa_fp4_forward_kvcache_workspace_bytes)", who,
+                        workspace ? workspace_bytes : (size_t)0, need);
+        if ((uintptr_t)workspace % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
+    }
+    fa::Fp4KvArgs a;
+    a.c = k.c; a.q = q; a.o = o; a.lse = lse; a.q_descale = q_descale; a.k_descale = k_descale; a.v_descale = v_descale;
+    a.qds_bs = k.qds_bs; a.kds_bs = k.kds_bs; a.vds_bs = k.vds_bs;
+    a.batch = batch; a.heads_q = heads_q; a.seqlen_q = seqlen_q; a.q_bs = q_batch_stride; a.q_ts = q_token_stride;
+    a.dtype = dtype; a.causal = causal != 0; a.scale = (float)softmax_scale; a.num_splits = S; a.workspace = workspace;
+    return launched(who, fa::launch_fp4_kvcache(a, reinterpret_cast<hipStream_t>(stream)));
 }
 
 int fa_debug_trace_buffer(void* device_ptr) {

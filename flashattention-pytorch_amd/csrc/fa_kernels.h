@@ -45,7 +45,7 @@ enum KernelId { K_FWD_F32 = 0, K_BWD_DELTA, K_BWD_DKDV_F32, K_BWD_DQ_F32, K_FWD_
                 K_FP8_QUANT, K_FWD_FP8, K_EX_FWD, K_EX_BWD, K_KV_GROUP_SUM, K_FP8IN_VT, K_FP8IN_FWD, K_FP8IN_VT_VARLEN,
                 K_FP8IN_FWD_VARLEN, K_IDX_PACK, K_IDX_LOGITS, K_IDX_TOPK, K_FP8KV_SPLIT, K_FP8Q_AMAX, K_FP8Q_QUANT, K_FP8Q_FUSED,
                 K_FP8IN_FWD_MOD, K_FP8IN_FWD_VARLEN_MOD, K_FP8KV_SPLIT_MOD, K_FP8KV_STEP_PREP, K_FP8IN_FWD_HDIM,
-                K_FP8IN_FWD_VARLEN_HDIM, K_FP8KV_SPLIT_HDIM, K_FP8KV_SPLIT_VARLEN, K_FP8KV_STEP_PREP_VARLEN, K_COUNT };
+                K_FP8IN_FWD_VARLEN_HDIM, K_FP8KV_SPLIT_HDIM, K_FP8KV_SPLIT_VARLEN, K_FP8KV_STEP_PREP_VARLEN, K_FP4KV_APPEND, K_FP4KV_SPLIT, K_COUNT };
 void prof_begin(int id, hipStream_t st);
 void prof_end(int id, hipStream_t st);
 struct ProfScope {
@@ -72,10 +72,12 @@ int set_option(const char* name, int value);   // returns 0, or -1 for an unknow
 // "fp8kv_step_prep": the append / rotary / q quantise launch of the fp8 decode step (fa_fp8_step.hip);
 // "fp8in_fwd_hdim", "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim": the fp8 calls at head dim 64 or 256 (the _hdim entry points);
 // "fp8kv_split_varlen": the packed-query split kernel of fa_fp8_forward_kvcache_varlen / fa_fp8_kvcache_step_varlen;
-// "fp8kv_step_prep_varlen": the prep launch of fa_fp8_kvcache_step_varlen with packed tokens or at head dim 64 / 256.
+// "fp8kv_step_prep_varlen": the prep launch of fa_fp8_kvcache_step_varlen with packed tokens or at head dim 64 / 256;
+// "fp4kv_append", "fp4kv_split": the two kernels of the MXFP4 KV cache (fa_fp4_decode.hip).
 enum RouteId { ROUTE_DKDV_STREAM = 0, ROUTE_DKDV_LEAN, ROUTE_FP8Q_FUSED, ROUTE_FP8Q_TWO_PASS, ROUTE_FP8Q_STATIC, ROUTE_FP8IN_FWD_MOD,
                ROUTE_FP8IN_FWD_VARLEN_MOD, ROUTE_FP8KV_SPLIT_MOD, ROUTE_FP8KV_STEP_PREP, ROUTE_FP8IN_FWD_HDIM,
-               ROUTE_FP8IN_FWD_VARLEN_HDIM, ROUTE_FP8KV_SPLIT_HDIM, ROUTE_FP8KV_SPLIT_VARLEN, ROUTE_FP8KV_STEP_PREP_VARLEN, ROUTE_COUNT };
+               ROUTE_FP8IN_FWD_VARLEN_HDIM, ROUTE_FP8KV_SPLIT_HDIM, ROUTE_FP8KV_SPLIT_VARLEN, ROUTE_FP8KV_STEP_PREP_VARLEN, ROUTE_FP4KV_APPEND,
+               ROUTE_FP4KV_SPLIT, ROUTE_COUNT };
 void route_hit(int id);
 
 // exact-f32 kernels (fa_generic.hip): any dtype, d <= 256
@@ -577,5 +579,40 @@ hipError_t launch_kv_combine_sink(void* o, float* lse, float* po, float* plse, i
 // the kPlseFill bytes belongs to no sequence and is left unwritten); sinks null: kv_combine_kernel<Tag, false>
 hipError_t launch_kv_combine_packed(void* o, float* lse, float* po, float* plse, const int* cu_seqlens_q, int64_t heads_q, int64_t total_q,
                                     int64_t d, int dtype, int splits, const float* sinks, int sink_heads, hipStream_t st);
+
+// The MXFP4 KV cache (fa_fp4_decode.hip; fa_fp4_kvcache_append, fa_fp4_forward_kvcache): e2m1 codes, two a byte, (cache_batch,
+// cache_len, heads_kv, 64), with E8M0 scale bytes, k_scale (.., heads_kv, 4) and v_scale (.., heads_kv); with block_table the four
+// are pools (num_blocks, page_size, ..).  Each array has its own batch (or page) and token stride, in bytes.  Fp4Cache is what
+// the append and the decode call share.
+struct Fp4Cache {
+    void *k_cache = nullptr, *k_scale = nullptr, *v_cache = nullptr, *v_scale = nullptr;
+    const int *cache_seqlens = nullptr, *block_table = nullptr, *cache_batch_idx = nullptr;   // untrusted device memory, or null
+    int64_t heads_kv = 0, cache_len = 0, cache_batch = 0;   // cache_len: the capacity
+    int64_t kc_bs = 0, kc_ts = 0, ks_bs = 0, ks_ts = 0, vc_bs = 0, vc_ts = 0, vs_bs = 0, vs_ts = 0;
+    int64_t table_row_stride = 0, num_blocks = 0, page_size = 0;
+};
+struct Fp4AppendArgs {
+    Fp4Cache c;                                             // c.cache_seqlens: the lengths before the append (non-null)
+    const void *k_new = nullptr, *v_new = nullptr;          // (batch, seqlen_new, heads_kv, 128) in dtype; strides in bytes
+    const float *k_descale = nullptr, *v_descale = nullptr; // (batch, heads_kv) device floats; null: 1
+    int64_t kds_bs = 0, vds_bs = 0;
+    int64_t batch = 0, seqlen_new = 0, kn_bs = 0, kn_ts = 0, vn_bs = 0, vn_ts = 0;
+    int dtype = 0;                                          // FA_DTYPE_F16 / FA_DTYPE_BF16
+};
+hipError_t launch_fp4_kvcache_append(const Fp4AppendArgs& a, hipStream_t st);
+struct Fp4KvArgs {
+    Fp4Cache c;
+    const void* q = nullptr;                                // e4m3 (batch, seqlen_q, heads_q, 128); strides in bytes
+    void* o = nullptr;                                      // (batch, seqlen_q, heads_q, 128) contiguous in dtype
+    float* lse = nullptr;                                   // (batch, heads_q, seqlen_q) contiguous
+    const float *q_descale = nullptr, *k_descale = nullptr, *v_descale = nullptr;
+    int64_t qds_bs = 0, kds_bs = 0, vds_bs = 0;
+    int64_t batch = 0, heads_q = 0, seqlen_q = 0, q_bs = 0, q_ts = 0;
+    int dtype = 0, causal = 0;
+    float scale = 0.f;
+    int64_t num_splits = 1;                                 // >= 1 (the C layer resolves 0 through fp8kv_num_splits)
+    void* workspace = nullptr;                              // kv_workspace_bytes(batch, heads_q, seqlen_q, 128, num_splits)
+};
+hipError_t launch_fp4_kvcache(const Fp4KvArgs& a, hipStream_t st);
 
 }  // namespace fa

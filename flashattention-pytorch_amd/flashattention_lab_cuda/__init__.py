@@ -66,6 +66,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_fp8_forward_hdim_workspace_bytes", "fa_fp8_forward_varlen_hdim_workspace_bytes", "fa_fp8_forward_kvcache_hdim_workspace_bytes",
     "fa_fp8_forward_kvcache_varlen", "fa_fp8_forward_kvcache_varlen_workspace_bytes",
     "fa_fp8_kvcache_step_varlen", "fa_fp8_kvcache_step_varlen_workspace_bytes",
+    "fa_fp4_kvcache_append", "fa_fp4_forward_kvcache", "fa_fp4_forward_kvcache_workspace_bytes",
 )
 
 
@@ -262,6 +263,19 @@ _sig("fa_fp8_kvcache_step_varlen", _hdim_fields(_SIGNATURES["fa_fp8_kvcache_step
      _fields("p:cu_seqlens_q i:total_q,max_seqlen_q p:cu_seqlens_k_new i:total_k_new"))
 _sig("fa_fp8_kvcache_step_varlen_workspace_bytes",
      _hdim_fields(_SIGNATURES["fa_fp8_kvcache_step_workspace_bytes"][1]) + _fields("i:total_q,max_seqlen_q"), _SIZE)
+# the MXFP4 KV cache: four arrays (codes and scale bytes of K and of V), each with a batch / page and a token stride of its own
+_FP4STRIDES = _fields("i:k_batch_stride,k_token_stride,k_scale_batch_stride,k_scale_token_stride,v_batch_stride,v_token_stride,"
+                      "v_scale_batch_stride,v_scale_token_stride,block_table_row_stride,num_blocks,page_block_size")
+_sig("fa_fp4_kvcache_append", _fields(
+    "p:k_new,v_new,k_cache,k_scale,v_cache,v_scale,cache_seqlens,block_table,cache_batch_idx,k_descale,v_descale "
+    "i:batch,heads_kv,seqlen_new,cache_len,cache_batch,d c:dtype "
+    "i:k_new_batch_stride,k_new_token_stride,v_new_batch_stride,v_new_token_stride") + _FP4STRIDES +
+    _fields("i:descale_batch_stride") + _STREAM)
+_sig("fa_fp4_forward_kvcache", _fields(
+    "p:q,k_cache,k_scale,v_cache,v_scale,o,lse,q_descale,k_descale,v_descale,cache_seqlens,block_table,cache_batch_idx "
+    "i:batch,heads_q,heads_kv,seqlen_q,cache_len,cache_batch,d c:dtype i:q_batch_stride,q_token_stride") + _FP4STRIDES +
+    _fields("i:q_descale_batch_stride,k_descale_batch_stride,v_descale_batch_stride c:causal d:softmax_scale i:num_splits") + _WS)
+_sig("fa_fp4_forward_kvcache_workspace_bytes", _KVWS, _SIZE)
 _KVWSV = _fields("i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,d,num_splits c:with_sinks")
 _sig("fa_ex_kvcache_workspace_bytes_varlen", _KVWSV, _SIZE)
 _sig("fa_ex_kvcache_workspace_bytes_qv", _KVWSV + _fields("i:d_v"), _SIZE)
@@ -330,6 +344,9 @@ _family("fa_fp8_kvcache_step", [])
 # packed queries / new keys and the step at 64 / 256: a family of one each, called with exactly its own arguments
 _family("fa_fp8_forward_kvcache_varlen", [])
 _family("fa_fp8_kvcache_step_varlen", [])
+# the MXFP4 KV cache: the append and the decode call, a family of one each
+_family("fa_fp4_kvcache_append", [])
+_family("fa_fp4_forward_kvcache", [])
 _family("fa_ex_forward_kvcache_qv", ["fa_ex_forward_kvcache" + _suffix for _suffix in ("", "_paged", "_rotary", "_fp8", "_sink", "_varlen")])
 
 
@@ -2978,4 +2995,187 @@ def _fp8_kvcache_packed(who, q, k_cache, v_cache, k_new, v_new, cache_seqlens, b
                                                  cu_seqlens_k_new.data_ptr() if packed_kn else 0, total_kn))
             del _tabs
     del keep_q, keep_k, keep_v, keep_s
+    return o, lse
+
+
+# ---- the MXFP4 KV cache (fa_fp4_kvcache_append, fa_fp4_forward_kvcache)
+def _fp4_u8(who, name, t, typed):
+    """t as uint8: uint8 itself, or a view of the torch dtype `typed` names (where this torch has it); nothing is copied"""
+    if isinstance(t, torch.Tensor) and t.dtype == torch.uint8:
+        return t
+    dt = getattr(torch, typed, None)
+    if isinstance(t, torch.Tensor) and dt is not None and t.dtype == dt:
+        return t.view(torch.uint8)
+    got = t.dtype if isinstance(t, torch.Tensor) else type(t).__name__
+    raise NotImplementedError(f"{who}: {name} of dtype {got} is not supported (torch.uint8 or torch.{typed} expected)")
+
+
+def _fp4_cache(who, k_cache, k_scale, v_cache, v_scale, block_table, cache_batch_idx, b):
+    """The four arrays of an MXFP4 cache as uint8 views with their geometry: (arrays, H_kv, capacity, cache_batch, the eight byte
+    strides in the C order, (block_table_row_stride, num_blocks, page_block_size), block_table, cache_batch_idx)."""
+    kc, vc = (_fp4_u8(who, n, t, "float4_e2m1fn_x2") for n, t in (("k_cache", k_cache), ("v_cache", v_cache)))
+    ks, vs = (_fp4_u8(who, n, t, "float8_e8m0fnu") for n, t in (("k_scale", k_scale), ("v_scale", v_scale)))
+    paged = block_table is not None
+    if paged and cache_batch_idx is not None:
+        raise NotImplementedError(f"{who}: block_table together with cache_batch_idx is not supported (a table row is the indirection)")
+    for name, t in (("block_table", block_table), ("cache_batch_idx", cache_batch_idx)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.int32):
+            dt = t.dtype if isinstance(t, torch.Tensor) else type(t).__name__
+            raise NotImplementedError(f"{who}: {name} of dtype {dt} is not supported (int32 tensor expected)")
+    if kc.dim() != 4:
+        raise RuntimeError(f"{who}: k_cache must be (B_cache, cache_len, H_kv, 64) code bytes or a pool (num_blocks, page_block_size, "
+                           f"H_kv, 64); got {tuple(kc.shape)}")
+    if kc.shape[3] != 64:
+        raise NotImplementedError(f"{who}: head_dim {2 * kc.shape[3]} is not supported (128 only: 64 code bytes a head); got k_cache "
+                                  f"of shape {tuple(kc.shape)}")
+    lead, hkv = tuple(kc.shape[:2]), kc.shape[2]
+    want = dict(k_scale=(*lead, hkv, 4), v_cache=(*lead, hkv, 64), v_scale=(*lead, hkv))
+    for name, t in (("k_scale", ks), ("v_cache", vc), ("v_scale", vs)):
+        if tuple(t.shape) != want[name]:
+            raise RuntimeError(f"{who}: {name} of shape {tuple(t.shape)} does not match k_cache {tuple(kc.shape)}: {want[name]} expected "
+                               f"(k_scale one byte per 32 channels, v_scale one byte per token and head)")
+    if hkv < 1 or lead[0] < 1 or lead[1] < 1:
+        raise RuntimeError(f"{who}: the caches must hold at least one token and one head; got k_cache of shape {tuple(kc.shape)}")
+    strides = []
+    for name, t, width in (("k_cache", kc, 64), ("k_scale", ks, 4), ("v_cache", vc, 64), ("v_scale", vs, 1)):
+        if (t.dim() == 4 and t.stride(3) != 1) or (hkv > 1 and t.stride(2) != width):
+            raise ValueError(f"{who}: {name} must have adjacent heads with a contiguous last dim (strides {t.stride()})")
+        strides += [t.stride(0) if lead[0] > 1 else 0, t.stride(1) if lead[1] > 1 else hkv * width]
+    if paged:
+        if block_table.dim() != 2 or block_table.shape[0] != b or block_table.shape[1] < 1:
+            raise RuntimeError(f"{who}: block_table must be an int32 (B, max_blocks_per_seq >= 1) tensor, B = {b}; got "
+                               f"{tuple(block_table.shape)}")
+        if lead[1] % 16 != 0:
+            raise RuntimeError(f"{who}: page_block_size must be a positive multiple of 16, got {lead[1]}")
+        if block_table.stride(1) != 1 and block_table.shape[1] > 1:
+            block_table = block_table.contiguous()
+        cap, cbatch = block_table.shape[1] * lead[1], 0
+        pages = (max(block_table.stride(0), block_table.shape[1]), lead[0], lead[1])
+    else:
+        cap, cbatch, pages = lead[1], 0, (0, 0, 0)
+        if cache_batch_idx is not None:
+            if cache_batch_idx.shape != (b,):
+                raise RuntimeError(f"{who}: cache_batch_idx must be an int32 tensor of shape (B,) = ({b},)")
+            cache_batch_idx, cbatch = cache_batch_idx.contiguous(), lead[0]
+        elif lead[0] != b:
+            raise RuntimeError(f"{who}: the caches hold {lead[0]} rows for a batch of {b} (pass cache_batch_idx to select rows)")
+    return (kc, ks, vc, vs), hkv, cap, cbatch, strides, pages, block_table, cache_batch_idx
+
+
+def _fp4_lens(who, cache_seqlens, b, device, required):
+    if isinstance(cache_seqlens, int) and not isinstance(cache_seqlens, bool):
+        cache_seqlens = torch.full((b,), cache_seqlens, dtype=torch.int32, device=device)
+    if cache_seqlens is None and not required:
+        return None
+    if not (isinstance(cache_seqlens, torch.Tensor) and cache_seqlens.dtype == torch.int32 and cache_seqlens.shape == (b,)):
+        raise RuntimeError(f"{who}: cache_seqlens must be an int32 tensor of shape (B,) = ({b},) or an int" +
+                           (" (required: the lengths before the append)" if required else " or None"))
+    return cache_seqlens.contiguous()
+
+
+def _fp4_one_device(who, *tensors):
+    tensors = [t for t in tensors if t is not None]
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: tensors must be on the GPU (HIP device); there is no CPU path")
+    if len({t.device for t in tensors}) != 1:
+        raise RuntimeError(f"{who}: all tensors must be on one device")
+
+
+def fp4_kvcache_append(k_new, v_new, k_cache, k_scale, v_cache, v_scale, cache_seqlens, block_table=None, cache_batch_idx=None,
+                       k_descale=None, v_descale=None):
+    """Quantise new tokens to MXFP4 and append them to the cache, in place (fa_fp4_kvcache_append): k_new, v_new (B, N_new, H_kv, 128)
+    float16 / bfloat16 views at their own batch and token strides go to positions cache_seqlens[b] + i (int32 (B,) on the device, or an
+    int: the lengths before the append, clamped to [0, capacity] there, not modified).  k_cache / v_cache: uint8 (or
+    torch.float4_e2m1fn_x2) (B_cache, cap, H_kv, 64), k_scale uint8 (or torch.float8_e8m0fnu) (B_cache, cap, H_kv, 4), v_scale
+    (B_cache, cap, H_kv), or with block_table pools (num_blocks, ps, ..); each at its own strides, never copied.  A token whose
+    position, page or cache row lies outside the cache is dropped.  k_descale / v_descale float32 (B, H_kv) or (H_kv,), None = 1.
+    The arithmetic is include/fa_mi355x.h's, exact.  Nothing is read on the host.  Returns None."""
+    who = "fp4_kvcache_append"
+    for name, t in (("k_new", k_new), ("v_new", v_new)):
+        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float16, torch.bfloat16):
+            dt = t.dtype if isinstance(t, torch.Tensor) else type(t).__name__
+            raise NotImplementedError(f"{who}: {name} of dtype {dt} is not supported (torch.float16 or torch.bfloat16)")
+    if k_new.dim() != 4 or v_new.shape != k_new.shape or v_new.dtype != k_new.dtype:
+        raise RuntimeError(f"{who}: k_new and v_new must be (B, N_new, H_kv, 128) of one shape and dtype; got {tuple(k_new.shape)} "
+                           f"{k_new.dtype}, {tuple(v_new.shape)} {v_new.dtype}")
+    if k_new.shape[3] != 128:
+        raise NotImplementedError(f"{who}: head_dim {k_new.shape[3]} is not supported (128 only)")
+    b, nnew = k_new.shape[0], k_new.shape[1]
+    arrays, hkv, cap, cbatch, strides, pages, block_table, cache_batch_idx = _fp4_cache(who, k_cache, k_scale, v_cache, v_scale, block_table,
+                                                                                        cache_batch_idx, b)
+    if k_new.shape[2] != hkv:
+        raise RuntimeError(f"{who}: k_new has {k_new.shape[2]} heads, the caches {hkv}")
+    cache_seqlens = _fp4_lens(who, cache_seqlens, b, k_new.device, True)
+    _fp4_one_device(who, k_new, v_new, *arrays, cache_seqlens, block_table, cache_batch_idx)
+    new = []
+    for name, t in (("k_new", k_new), ("v_new", v_new)):
+        if t.numel() and ((hkv > 1 and t.stride(2) != 128) or t.stride(3) != 1):
+            raise ValueError(f"{who}: {name} must have adjacent heads with a contiguous last dim (strides {t.stride()})")
+        new += [2 * t.stride(0) if b > 1 else 0, 2 * t.stride(1) if nnew > 1 else 2 * hkv * 128]
+    kdp, vdp, dss, keep = _kv_descales(who, k_descale, v_descale, k_new, b, hkv)
+    if b == 0 or nnew == 0:
+        return
+    with torch.cuda.device(k_new.device):
+        _call("fa_fp4_kvcache_append", (
+            k_new.data_ptr(), v_new.data_ptr(), *(t.data_ptr() for t in arrays), cache_seqlens.data_ptr(), _ptr(block_table),
+            _ptr(cache_batch_idx), kdp, vdp, b, hkv, nnew, cap, cbatch, 128, _DTYPE_CODE[k_new.dtype], *new, *strides, *pages, dss,
+            _stream_ptr(k_new.device)))
+    del keep
+
+
+def fp4_kvcache_forward(q, k_cache, k_scale, v_cache, v_scale, cache_seqlens=None, block_table=None, cache_batch_idx=None, q_descale=None,
+                        k_descale=None, v_descale=None, softmax_scale=None, causal=False, num_splits=0, out_dtype=torch.bfloat16, out=None):
+    """(o, lse) of decoding over an MXFP4 KV cache (fa_fp4_forward_kvcache): q (B, Nq, H_q, 128) torch.float8_e4m3fn at its own batch
+    and token strides over the cache fp4_kvcache_append fills (its docstring has the four arrays); cache_seqlens int32 (B,) on the
+    device, an int, or None (full); descales float32 (B, H_kv) or (H_kv,), None = 1.  o (B, Nq, H_q, 128) in out_dtype, lse float32
+    (B, H_q, Nq).  Nothing is copied or read on the host; the partials live in the shim's persistent workspace.  out: an (o, lse) pair
+    of contiguous tensors of those shapes and dtypes to write into (16- and 4-byte aligned), instead of fresh ones."""
+    who = "fp4_kvcache_forward"
+    if not isinstance(q, torch.Tensor) or q.dtype != torch.float8_e4m3fn:
+        dt = q.dtype if isinstance(q, torch.Tensor) else type(q).__name__
+        raise NotImplementedError(f"{who}: q of dtype {dt} is not supported (torch.float8_e4m3fn expected: quantize_fp8)")
+    if out_dtype not in (torch.bfloat16, torch.float16):
+        raise NotImplementedError(f"{who}: out_dtype {out_dtype} is not supported (torch.bfloat16 or torch.float16)")
+    if q.dim() != 4:
+        raise RuntimeError(f"{who}: q must be (B, Nq, H_q, 128), got {tuple(q.shape)}")
+    if q.shape[3] != 128:
+        raise NotImplementedError(f"{who}: head_dim {q.shape[3]} is not supported (128 only); got q of shape {tuple(q.shape)}")
+    b, nq, hq = q.shape[0], q.shape[1], q.shape[2]
+    arrays, hkv, cap, cbatch, strides, pages, block_table, cache_batch_idx = _fp4_cache(who, k_cache, k_scale, v_cache, v_scale, block_table,
+                                                                                        cache_batch_idx, b)
+    if hq == 0 or hq % hkv != 0:
+        raise RuntimeError(f"{who}: H_q = {hq} must be a multiple of H_kv = {hkv}")
+    cache_seqlens = _fp4_lens(who, cache_seqlens, b, q.device, False)
+    _fp4_one_device(who, q, *arrays, cache_seqlens, block_table, cache_batch_idx)
+    scale = 128 ** -0.5 if softmax_scale is None else float(softmax_scale)
+    if not (math.isfinite(scale) and scale > 0.0):
+        raise RuntimeError(f"{who}: softmax_scale must be finite and > 0 (got {scale})")
+    ns = operator.index(num_splits)
+    if ns < 0 or ns > 256:
+        raise RuntimeError(f"{who}: num_splits must lie in [0, 256] (got {ns})")
+    if q.numel() and ((hq > 1 and q.stride(2) != 128) or q.stride(3) != 1):
+        raise ValueError(f"{who}: q must have adjacent heads with a contiguous last dim (strides {q.stride()})")
+    qdp, qds, keep_q = _kv_descale(who, "q_descale", q_descale, q, b, hkv)
+    kdp, kds, keep_k = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
+    vdp, vds, keep_v = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
+    with torch.cuda.device(q.device):
+        if out is not None:
+            o, lse = out
+            if (tuple(o.shape), o.dtype, tuple(lse.shape), lse.dtype) != ((b, nq, hq, 128), out_dtype, (b, hq, nq), torch.float32) or \
+                    not (o.is_contiguous() and lse.is_contiguous() and o.device == q.device and lse.device == q.device):
+                raise RuntimeError(f"{who}: out must be contiguous (o ({b}, {nq}, {hq}, 128) {out_dtype}, lse ({b}, {hq}, {nq}) float32) on q's device")
+        else:
+            o = torch.empty((b, nq, hq, 128), dtype=out_dtype, device=q.device)
+            lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)
+        if b == 0 or nq == 0:
+            return o, lse
+        need = int(_lib.fa_fp4_forward_kvcache_workspace_bytes(b, hq, hkv, nq, cap, 128, ns))
+        ws = _workspace(q.device, need)
+        _call("fa_fp4_forward_kvcache", (
+            q.data_ptr(), *(t.data_ptr() for t in arrays), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp, _ptr(cache_seqlens),
+            _ptr(block_table), _ptr(cache_batch_idx), b, hq, hkv, nq, cap, cbatch, 128, _DTYPE_CODE[out_dtype],
+            q.stride(0) if b > 1 else 0, q.stride(1) if nq > 1 else hq * 128, *strides, *pages, qds, kds, vds, int(bool(causal)), scale, ns,
+            ws.data_ptr() if need else 0, ws.numel() if need else 0, _stream_ptr(q.device)))
+    del keep_q, keep_k, keep_v
     return o, lse

@@ -1556,6 +1556,61 @@ size_t fa_backward_workspace_bytes(int64_t bh, int64_t n, int64_t d, int dtype);
 size_t fa_backward_workspace_bytes_fast(int64_t bh, int64_t n, int64_t d, int dtype, int causal);
 size_t fa3_forward_workspace_bytes(int64_t bh, int64_t n, int64_t d, int dtype, int fp8);
 size_t fa3_backward_workspace_bytes(int64_t bh, int64_t n, int64_t d, int dtype, int fp8);
+/* --- An MXFP4 KV cache: the append kernel and split-KV decoding on the fp4 form of the matrix instruction.
+ * Forward only; a call family of its own.  Per K/V head at d = 128 (any other head dim: FA_ERR_UNSUPPORTED):
+ *     k_cache (.., heads_kv, 64) bytes   two OCP e2m1 codes a byte, the low nibble the even channel; code s eem, magnitudes
+ *                                        0, .5, 1, 1.5, 2, 3, 4, 6
+ *     k_scale (.., heads_kv, 4)  bytes   one E8M0 byte per 32 channels (an OCP MX block), value 2^(byte - 127)
+ *     v_cache as k_cache;  v_scale (.., heads_kv) bytes: one E8M0 byte per (token, head)
+ * 133 bytes a token and head against 256 in e4m3.  "..": (cache_batch or batch, cache_len) tokens, or with block_table pools
+ * (num_blocks, page_block_size); each of the four arrays has its own batch (page) and token stride, in bytes: multiples of 16 for the
+ * codes (16-byte aligned), of 4 for k_scale (4-byte aligned), any for v_scale.  Lengths, table, indices and descales are as in
+ * fa_fp8_forward_kvcache: untrusted device memory, never read on the host; q_descale / k_descale / v_descale float32 (batch,
+ * heads_kv) at their batch strides, NULL = 1, carry the global magnitude.
+ *
+ * fa_fp4_kvcache_append: k_new, v_new (batch, seqlen_new, heads_kv, 128) in dtype (f16 / bf16) at their strides in bytes (16-byte
+ * aligned, multiples of 16) go to positions len[b] + i, len[b] = clamp(cache_seqlens[b], 0, cache_len) (cache_seqlens required, not
+ * modified); k_descale and v_descale share descale_batch_stride, as in fa_ex_forward_kvcache_fp8.  A position >= cache_len, a page outside [0, num_blocks) or a cache_batch_idx outside [0, cache_batch) drops the token.
+ * Per block (32 channels of K, the 128 of V), x' = x * (1 / descale) in float32: amax = max |x'|, e = the smallest integer with
+ * 6 * 2^e >= amax clamped to [-64, 64] (amax = 0: e = 0), the scale byte e + 127, the code x' * 2^-e rounded to e2m1, nearest, a tie
+ * to the even code, saturating at 6 under the clamp.  Non-finite inputs give unspecified codes inside the token.  One launch.
+ *
+ * fa_fp4_forward_kvcache: q is e4m3 as in fa_fp8_forward_kvcache, o (batch, seqlen_q, heads_q, 128) in dtype, lse float32;
+ *     s[i, j] = softmax_scale * q_descale * k_descale * (q8[i] . (k4[j] * 2^ek[j])),  o[i] = sum_j softmax(s)[i, j] * v4[j] * 2^ev[j]
+ *               * v_descale
+ * K's block scales are the instruction's E8M0 operand; V's token scale joins the softmax exponent, P' = exp2(s f + ev - M) with M
+ * the running maximum of s f + ev is rounded to e4m3 and meets the raw v4 codes, l sums the unscaled exp2(s f - M).  GQA, causal
+ * (bottom-right), cache_seqlens, block_table (page_block_size % 16 == 0) or cache_batch_idx, num_splits, the workspace layout, the
+ * combine, the trust rules and graph replay are fa_fp8_forward_kvcache's; fa_fp4_forward_kvcache_workspace_bytes is its function.  A
+ * page outside the pool reads as zero codes with unit scales (score 0, value 0); keys at or past len[b] are never loaded; any
+ * scale byte in memory (0xFF included) may give any number for its key and never an address.
+ * Checks, the first broken rule named in fa_last_error(): the empty call (batch == 0, or seqlen_new / seqlen_q == 0) is FA_OK; null
+ * pointers; d == 128 and dtype f16 / bf16 (FA_ERR_UNSUPPORTED); the extents; alignment and strides; the descale strides; the page
+ * arguments; the span limits (FA_ERR_UNSUPPORTED: tokens * token stride of an array below 2^31, cache_len below 2^28); then what
+ * the call adds (the append: seqlen_new, k_new / v_new; the decode call: heads_q, seqlen_q, softmax_scale, q, num_splits in [0, 256],
+ * the workspace, FA_ERR_WORKSPACE). */
+int fa_fp4_kvcache_append(const void* k_new, const void* v_new, void* k_cache, void* k_scale, void* v_cache, void* v_scale,
+                          const int32_t* cache_seqlens, const int32_t* block_table, const int32_t* cache_batch_idx,
+                          const float* k_descale, const float* v_descale, int64_t batch, int64_t heads_kv, int64_t seqlen_new,
+                          int64_t cache_len, int64_t cache_batch, int64_t d, int dtype, int64_t k_new_batch_stride,
+                          int64_t k_new_token_stride, int64_t v_new_batch_stride, int64_t v_new_token_stride, int64_t k_batch_stride,
+                          int64_t k_token_stride, int64_t k_scale_batch_stride, int64_t k_scale_token_stride, int64_t v_batch_stride,
+                          int64_t v_token_stride, int64_t v_scale_batch_stride, int64_t v_scale_token_stride,
+                          int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t descale_batch_stride,
+                          void* stream);
+int fa_fp4_forward_kvcache(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o,
+                           float* lse, const float* q_descale, const float* k_descale, const float* v_descale,
+                           const int32_t* cache_seqlens, const int32_t* block_table, const int32_t* cache_batch_idx, int64_t batch,
+                           int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t cache_batch, int64_t d,
+                           int dtype, int64_t q_batch_stride, int64_t q_token_stride, int64_t k_batch_stride, int64_t k_token_stride,
+                           int64_t k_scale_batch_stride, int64_t k_scale_token_stride, int64_t v_batch_stride, int64_t v_token_stride,
+                           int64_t v_scale_batch_stride, int64_t v_scale_token_stride, int64_t block_table_row_stride,
+                           int64_t num_blocks, int64_t page_block_size, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
+                           int64_t v_descale_batch_stride, int causal, double softmax_scale, int64_t num_splits, void* workspace,
+                           size_t workspace_bytes, void* stream);
+size_t fa_fp4_forward_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
+                                              int64_t d, int64_t num_splits);
+
 const char* fa_last_error(void);
 const char* fa_version(void);
 int fa_set_kernel_mode(int mode);      /* FA_MODE_*; returns the previous mode */
@@ -1579,7 +1634,8 @@ int fa_profile_report(char* buf, size_t cap);
  * fa_fp8_forward_kvcache_hdim, one count a call that launched one (head_dim 128 counts what the _mod call counts).
  * "fp8kv_split_varlen": the packed split kernel of fa_fp8_forward_kvcache_varlen and fa_fp8_kvcache_step_varlen;
  * "fp8kv_step_prep_varlen": the prep launch of fa_fp8_kvcache_step_varlen with packed tokens or at head dim 64 / 256; one count a
- * call that launched one (null packed groups count what the parent calls count). */
+ * call that launched one (null packed groups count what the parent calls count).  "fp4kv_append", "fp4kv_split": the kernels of
+ * fa_fp4_kvcache_append and fa_fp4_forward_kvcache, one count a call that launched. */
 int64_t fa_route_count(const char* name);
 
 #ifdef __cplusplus

@@ -78,7 +78,12 @@ caches, interleaved rounds, three row kinds: `uniform`, the packed call on B = 3
 the padded call on the same tokens (d = 128); `mixed`, one step of 63 one-token sequences plus one chunk of 128 tokens, as one packed
 fp8 step (num_splits by the rule, and 8) against the two padded fp8 steps that serve it today (d = 128); `step_hdim`, the fused step at d = 64 and 256 (B = 32, Nq =
 N_new = 1) against the three calls that served these widths: the e4m3-cache call with a 16-bit q and k=, v= (the only append there
-was; its own attention comes with it), quantize_fp8 on q, the fp8 decode call."""
+was; its own attention comes with it), quantize_fp8 on q, the fp8 decode call.
+`--fp4`: decoding over the MXFP4 cache (fp4_kvcache_forward) against the e4m3 decode call on the same tokens
+widened exactly to e4m3, interleaved rounds: H 32:8, Nq 1, B 8 and 64, 4096 and 32768 cached keys, contiguous and paged (ps 16,
+shuffled); per row both times, their ratio, and the cache bytes (133 against 256 a token and head) over the time.  Then the append
+of one token a sequence at B 64 by the kernels' own profile scopes: fp4kv_append against the e4m3 step's prep launch (its append plus
+the q quantise)."""
 import argparse
 import json
 import os
@@ -569,6 +574,75 @@ def fp8q_rows(args, dtype):
     return rows
 
 
+def fp4_rows(args, dtype):
+    """--fp4: see the module docstring"""
+    dev, rounds, hq, hkv = "cuda", max(args.rounds, 5), 32, 8
+    mags = torch.tensor([0, .5, 1, 1.5, 2, 3, 4, 6, -0., -.5, -1, -1.5, -2, -3, -4, -6], dtype=torch.float32, device=dev)
+    rows = []
+    for b in (8, 64):
+        for L in (4096, 32768):
+            kc, vc = (torch.randint(0, 256, (b, L, hkv, 64), device=dev, dtype=torch.uint8) for _ in range(2))
+            ks = torch.randint(124, 131, (b, L, hkv, 4), device=dev, dtype=torch.uint8)
+            vs = torch.randint(124, 131, (b, L, hkv), device=dev, dtype=torch.uint8)
+            k8, v8 = (torch.empty((b, L, hkv, 128), device=dev, dtype=torch.float8_e4m3fn) for _ in range(2))
+            for bb in range(b):   # the same values in e4m3 (exact), one batch element at a time
+                for c4, sc, out in ((kc, ks, k8), (vc, vs, v8)):
+                    x = mags[torch.stack((c4[bb] & 15, c4[bb] >> 4), -1).flatten(-2).long()]
+                    e = torch.exp2(sc[bb].float() - 127.0).reshape(L, hkv, -1)
+                    out[bb] = (x * e.repeat_interleave(128 // e.shape[-1], -1)).to(torch.float8_e4m3fn)
+            q8 = torch.randn((b, 1, hq, 128), device=dev).to(torch.float8_e4m3fn)
+            qd, kd, vd = (torch.full((b, hkv), x, dtype=torch.float32, device=dev) for x in (0.25, 0.0625, 0.5))
+            sl = torch.full((b,), L, dtype=torch.int32, device=dev)
+            for ps in (0, 16):
+                if ps:
+                    nblk = b * L // ps
+                    perm = torch.randperm(nblk, device=dev)
+                    table = perm.view(b, L // ps).to(torch.int32)
+                    paged = []
+                    for t in (kc, ks, vc, vs, k8.view(torch.uint8), v8.view(torch.uint8)):
+                        pt = torch.empty_like(t).view(nblk, ps, *t.shape[2:])
+                        pt[perm] = t.view(nblk, ps, *t.shape[2:])
+                        paged.append(pt)
+                    a4, (a8k, a8v) = paged[:4], (paged[4].view(torch.float8_e4m3fn), paged[5].view(torch.float8_e4m3fn))
+                else:
+                    table, a4, a8k, a8v = None, [kc, ks, vc, vs], k8, v8
+                fp4 = lambda: ext.fp4_kvcache_forward(q8, *a4, sl, table, None, qd, kd, vd, None, False, 0, dtype)   # noqa: E731
+                fp8 = lambda: ext.fp8_kvcache_forward(q8, a8k, a8v, sl, table, None, qd, kd, vd, None, False, 0, dtype)   # noqa: E731
+                torch.testing.assert_close(fp4()[0].float(), fp8()[0].float(), rtol=5e-2, atol=5e-2)
+                t4, t8 = [], []
+                for _ in range(rounds):
+                    t8.append(timed(fp8, args.warmup, args.iters, 1))
+                    t4.append(timed(fp4, args.warmup, args.iters, 1))
+                m4, m8 = statistics.median(t4), statistics.median(t8)
+                n4, n8 = b * L * hkv * 133, b * L * hkv * 256
+                rows.append(dict(kind="fp4", b=b, L=L, page_size=ps, e4m3_us=round(m8, 2), fp4_us=round(m4, 2), ratio=round(m4 / m8, 3),
+                                 e4m3_spread=round((max(t8) - min(t8)) / m8, 3), fp4_spread=round((max(t4) - min(t4)) / m4, 3),
+                                 e4m3_TBps=round(n8 / m8 / 1e6, 3), fp4_TBps=round(n4 / m4 / 1e6, 3), byte_ratio=round(133 / 256, 3)))
+                print(json.dumps(rows[-1]), flush=True)
+                del a4, a8k, a8v
+            del kc, vc, ks, vs, k8, v8
+            torch.cuda.empty_cache()
+    # the append of one token a sequence: the kernels by their own profile scopes
+    b, cap = 64, 4096
+    kn, vn, q16 = (torch.randn((b, 1, h_, 128), device=dev, dtype=dtype) for h_ in (hkv, hkv, hq))
+    c4 = [torch.zeros((b, cap, hkv, w), device=dev, dtype=torch.uint8) for w in (64, 4, 64)] + [torch.zeros((b, cap, hkv), device=dev, dtype=torch.uint8)]
+    c8k, c8v = (torch.zeros((b, cap, hkv, 128), device=dev, dtype=torch.float8_e4m3fn) for _ in range(2))
+    sl = torch.full((b,), cap // 2, dtype=torch.int32, device=dev)
+    ext.profile_enable(True)
+    for _ in range(args.iters * rounds):
+        ext.fp4_kvcache_append(kn, vn, *c4, sl)
+        ext.fp8_kvcache_step(q16, c8k, c8v, kn, vn, sl, None, None, None, None, None, None, False, 0, dtype)
+    torch.cuda.synchronize()
+    rep = ext.profile_report()
+    ext.profile_enable(False)
+    us = {n: rep[n][1] * 1e3 / max(rep[n][0], 1) for n in ("fp4kv_append", "fp8kv_step_prep") if n in rep}
+    rows.append(dict(kind="fp4_append", b=b, n_new=1, fp4_append_us=round(us.get("fp4kv_append", 0.0), 2),
+                     e4m3_step_prep_us=round(us.get("fp8kv_step_prep", 0.0), 2), fp4_bytes=b * hkv * (2 * 256 + 133),
+                     e4m3_bytes=b * hkv * (2 * 256 + 256) + b * hq * 384))
+    print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
 def fp8_mod_rows(args, dtype):
     """--fp8-mod: see the module docstring"""
     dev, rounds = "cuda", max(args.rounds, 5)
@@ -803,6 +877,7 @@ def main():
     ap.add_argument("--fp8-mod", action="store_true", help="time the windowed fp8 decode call, its floor and the 16-bit-q call with the same window: see the module docstring")
     ap.add_argument("--fp8-step", action="store_true", help="time the fp8 decode step against its parent and the 16-bit-q call with the append: see the module docstring")
     ap.add_argument("--fp8-varlen", action="store_true", help="time the packed fp8 decode call and step, and the step at d 64 / 256: see the module docstring")
+    ap.add_argument("--fp4", action="store_true", help="time decoding over the MXFP4 cache against the e4m3 decode call, and the append: see the module docstring")
     ap.add_argument("--md", default=None, help="--fp8-step: write the table as markdown to this path")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
@@ -818,6 +893,12 @@ def main():
         ext.ex_kvcache_forward(wq, wk, wk, None, None, wl, True, None)
     torch.cuda.synchronize()
     del wq, wk
+    if args.fp4:
+        rows = fp4_rows(args, dtype)
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(dict(fp4=True, dtype=args.dtype, version=ext.version(), copy_rate_TBps=COPY_RATE / 1e12, rows=rows), f, indent=1)
+        return
     if args.fp8_varlen:
         rows = fp8_varlen_rows(args, dtype)
         if args.json:
