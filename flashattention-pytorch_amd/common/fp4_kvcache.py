@@ -1,8 +1,10 @@
-"""An MXFP4 KV cache under an fp8 query (C ABI: fa_fp4_kvcache_append, fa_fp4_forward_kvcache): half the
-bytes of the e4m3 cache per cached token, read by the matrix instruction in its own format.
+"""An MXFP4 KV cache under an fp8 query (C ABI: fa_fp4_kvcache_append, fa_fp4_forward_kvcache, fa_fp4_forward_varlen; DESIGN.md
+sections 9zg and 9zh): half the bytes of the e4m3 cache per cached token, read by the matrix instruction in its own format.
 
-    mxfp4_kvcache_append           16-bit k, v -> e2m1 codes and E8M0 scales at cache_seqlens[b] + i, in place
-    fp8_attn_with_mxfp4_kvcache    e4m3 q over that cache: split-KV decoding, fp8_attn_with_kvcache's contract
+    mxfp4_kvcache_append                  16-bit k, v -> e2m1 codes and E8M0 scales at cache_seqlens[b] + i, in place
+    fp8_attn_with_mxfp4_kvcache           e4m3 q over that cache: split-KV decoding, fp8_attn_with_kvcache's contract
+    fp8_attn_varlen_with_mxfp4_kvcache    packed e4m3 q over the paged cache: chunked prefill, fp8_attn_varlen_func(block_table=)'s
+                                          contract, a workgroup of four waves sharing each key tile
 
 The cache, per K/V head at d = 128:
     k_cache  uint8 (B_cache, cap, H_kv, 64), or a pool (num_blocks, ps, H_kv, 64): two e2m1 codes a byte, the low nibble the even
@@ -14,9 +16,10 @@ strides are used in place (code rows 16-byte aligned, k_scale rows 4-byte aligne
 float32 (B, H_kv) or (H_kv,) scales of the fp8 calls and carry the global magnitude: value = code * 2^(scale byte - 127) * descale.
 
 Lengths, block_table and cache_batch_idx are untrusted device memory, never read on the host: a captured append + decode replays
-after they changed in place.  Refused by name (NotImplementedError): window_size, softcap, sinks, cu_seqlens_q / max_seqlen_q
-(packed queries), cache_leftpad, qv, rotary tables, head dims other than 128, 16-bit q, block_table with cache_batch_idx.  No
-gradient."""
+after they changed in place.  Refused by name (NotImplementedError) by all three: window_size, softcap, sinks, cache_leftpad,
+qv, rotary tables, ALiBi, a bias, head dims other than 128, 16-bit q.  The decode call also refuses cu_seqlens_q / max_seqlen_q
+(packed queries are fp8_attn_varlen_with_mxfp4_kvcache's) and block_table with cache_batch_idx; the packed call refuses
+cache_batch_idx and cache_seqlens (its lengths are cu_seqlens_k) and needs block_table.  No gradient."""
 from __future__ import annotations
 
 import torch
@@ -24,7 +27,8 @@ import torch
 _REFUSED = dict(
     window_size="a sliding window", softcap="a softcap", sinks="attention sinks", cu_seqlens_q="packed queries",
     max_seqlen_q="packed queries", cu_seqlens_k_new="packed new keys", cache_leftpad="cache_leftpad", qv="qv (MLA)",
-    rotary_cos="rotary embedding", rotary_sin="rotary embedding", alibi_slopes="ALiBi", attn_bias="an additive bias")
+    rotary_cos="rotary embedding", rotary_sin="rotary embedding", alibi_slopes="ALiBi", attn_bias="an additive bias",
+    cache_batch_idx="cache_batch_idx", cache_seqlens="cache_seqlens")
 
 
 def _refuse(who, unsupported):
@@ -32,6 +36,9 @@ def _refuse(who, unsupported):
         if name not in _REFUSED:
             raise TypeError(f"{who}() got an unexpected keyword argument '{name}'")
         if isinstance(val, torch.Tensor) or val not in (None, False, 0, 0.0, (-1, -1), (None, None)):
+            if _REFUSED[name] == "packed queries":
+                raise NotImplementedError(f"{who}: {name} is not supported: packed queries over the MXFP4 cache are "
+                                          f"fp8_attn_varlen_with_mxfp4_kvcache's (chunked prefill over the paged cache)")
             raise NotImplementedError(f"{who}: {name} is not supported: the MXFP4 cache calls take no {_REFUSED[name]} (the e4m3 cache "
                                       f"calls of common.fp8_attention do)")
 
@@ -71,4 +78,27 @@ def fp8_attn_with_mxfp4_kvcache(q, k_cache, k_scale, v_cache, v_scale, *, cache_
         o, lse = ext.fp4_kvcache_forward(_det(q), k_cache, k_scale, v_cache, v_scale, cache_seqlens, block_table, cache_batch_idx,
                                          _det(q_descale), _det(k_descale), _det(v_descale), softmax_scale, bool(causal), num_splits,
                                          out_dtype)
+    return (o, lse) if return_softmax_lse else o
+
+
+def fp8_attn_varlen_with_mxfp4_kvcache(q, k_cache, k_scale, v_cache, v_scale, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, *,
+                                       block_table, q_descale=None, k_descale=None, v_descale=None, softmax_scale=None, causal=False,
+                                       out_dtype=torch.bfloat16, return_softmax_lse=False, **unsupported):
+    """Chunked prefill over the paged MXFP4 cache, one launch: q (total_q, H_q, 128) torch.float8_e4m3fn packed by cu_seqlens_q (a
+    view such as qkv8[:, 0] is used in place) over the pools (num_blocks, ps, H_kv, ..) mxfp4_kvcache_append fills, under block_table
+    int32 (B, max_blocks), ps % 16 == 0.  Sequence b has cu_seqlens_q[b + 1] - cu_seqlens_q[b] queries and cu_seqlens_k[b + 1] -
+    cu_seqlens_k[b] keys (slots 0 .. of its pages), both clamped on the device; causal is the bottom-right diagonal of that sequence
+    alone; sequences may be empty.  Returns o (total_q, H_q, 128) in out_dtype, with return_softmax_lse also lse (H_q, total_q)
+    float32; a row without a visible key gives o = 0, lse = -inf, a row of no sequence is not written.  A contiguous (B, cap, H_kv, ..)
+    cache with cap % ps == 0 is already such a pool: pass its arrays as .view(B * cap // ps, ps, H_kv, -1) with block_table =
+    arange(B * cap // ps).view(B, -1).  Below about 32 / (H_q / H_kv) query tokens a sequence fp8_attn_with_mxfp4_kvcache, which
+    splits the keys, is the faster call."""
+    who = "fp8_attn_varlen_with_mxfp4_kvcache"
+    _refuse(who, unsupported)
+    import flashattention_lab_cuda as ext
+
+    with torch.no_grad():
+        o, lse = ext.fp4_varlen_forward(_det(q), k_cache, k_scale, v_cache, v_scale, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k,
+                                        block_table, _det(q_descale), _det(k_descale), _det(v_descale), softmax_scale, bool(causal),
+                                        out_dtype)
     return (o, lse) if return_softmax_lse else o

@@ -33,7 +33,8 @@ const char* const kKernelNames[fa::K_COUNT] = {"fwd_f32", "bwd_delta", "bwd_dkdv
                                                "fp8in_vt", "fp8in_fwd", "fp8in_vt_varlen", "fp8in_fwd_varlen", "idx_pack", "idx_logits",
                                                "idx_topk", "fp8kv_split", "fp8q_amax", "fp8q_quant", "fp8q_fused", "fp8in_fwd_mod",
                                                "fp8in_fwd_varlen_mod", "fp8kv_split_mod", "fp8kv_step_prep", "fp8in_fwd_hdim",
-    "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim", "fp8kv_split_varlen", "fp8kv_step_prep_varlen", "fp4kv_append", "fp4kv_split"};
+    "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim", "fp8kv_split_varlen", "fp8kv_step_prep_varlen", "fp4kv_append", "fp4kv_split",
+    "fp4kv_prefill"};
 
 hipEvent_t prof_get_event() {
     if (!g_prof_free.empty()) { hipEvent_t e = g_prof_free.back(); g_prof_free.pop_back(); return e; }
@@ -180,7 +181,8 @@ std::atomic<long long> g_route_hits[ROUTE_COUNT];
 constexpr const char* kRouteNames[ROUTE_COUNT] = {"dkdv_stream", "dkdv_lean", "fp8_quant_fused", "fp8_quant_two_pass", "fp8_quant_static",
                                                    "fp8in_fwd_mod", "fp8in_fwd_varlen_mod", "fp8kv_split_mod", "fp8kv_step_prep", "fp8in_fwd_hdim",
                                                    "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim", "fp8kv_split_varlen",
-                                                   "fp8kv_step_prep_varlen", "fp4kv_append", "fp4kv_split"};
+                                                   "fp8kv_step_prep_varlen", "fp4kv_append", "fp4kv_split",
+    "fp4kv_prefill"};
 void route_hit(int id) { g_route_hits[id].fetch_add(1, std::memory_order_relaxed); }
 long long route_count(const char* name) {
     for (int i = 0; i < ROUTE_COUNT; ++i)
@@ -4139,6 +4141,58 @@ int fa_fp4_forward_kvcache(const void* q, const void* k_cache, const void* k_sca
     a.batch = batch; a.heads_q = heads_q; a.seqlen_q = seqlen_q; a.q_bs = q_batch_stride; a.q_ts = q_token_stride;
     a.dtype = dtype; a.causal = causal != 0; a.scale = (float)softmax_scale; a.num_splits = S; a.workspace = workspace;
     return launched(who, fa::launch_fp4_kvcache(a, reinterpret_cast<hipStream_t>(stream)));
+}
+
+// Chunked prefill over the paged MXFP4 cache: packed queries, one launch, no workspace (fa_fp4_prefill.hip)
+int fa_fp4_forward_varlen(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o, float* lse,
+                          const float* q_descale, const float* k_descale, const float* v_descale, const int32_t* cu_seqlens_q,
+                          const int32_t* cu_seqlens_k, const int32_t* block_table, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                          int64_t total_q, int64_t max_seqlen_q, int64_t cache_len, int64_t d, int dtype, int64_t q_token_stride,
+                          int64_t k_batch_stride, int64_t k_token_stride, int64_t k_scale_batch_stride, int64_t k_scale_token_stride,
+                          int64_t v_batch_stride, int64_t v_token_stride, int64_t v_scale_batch_stride, int64_t v_scale_token_stride,
+                          int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t q_descale_batch_stride,
+                          int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* stream) {
+    const char* who = "fa_fp4_forward_varlen";
+    Fp4Call k;
+    k.c.k_cache = const_cast<void*>(k_cache); k.c.k_scale = const_cast<void*>(k_scale);
+    k.c.v_cache = const_cast<void*>(v_cache); k.c.v_scale = const_cast<void*>(v_scale);
+    k.c.block_table = block_table; k.c.heads_kv = heads_kv; k.c.cache_len = cache_len;
+    k.c.kc_bs = k_batch_stride; k.c.kc_ts = k_token_stride; k.c.ks_bs = k_scale_batch_stride; k.c.ks_ts = k_scale_token_stride;
+    k.c.vc_bs = v_batch_stride; k.c.vc_ts = v_token_stride; k.c.vs_bs = v_scale_batch_stride; k.c.vs_ts = v_scale_token_stride;
+    k.c.table_row_stride = block_table_row_stride; k.c.num_blocks = num_blocks; k.c.page_size = page_block_size;
+    k.batch = batch; k.d = d; k.dtype = dtype; k.q_descale = q_descale; k.k_descale = k_descale; k.v_descale = v_descale;
+    k.qds_bs = q_descale_batch_stride; k.kds_bs = k_descale_batch_stride; k.vds_bs = v_descale_batch_stride;
+    if (batch == 0 || total_q == 0 || max_seqlen_q == 0) return FA_OK;
+    if (!q || !k_cache || !k_scale || !v_cache || !v_scale || !o || !lse) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    if (!cu_seqlens_q || !cu_seqlens_k) return fail(FA_ERR_INVALID_ARGUMENT, "%s: cu_seqlens_q and cu_seqlens_k are required", who);
+    if (!block_table)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: block_table is required (the cache is a pool of pages; a contiguous cache is one under "
+                    "an arange table)", who);
+    if (const int rc = fp4_cache_check(who, k, 3)) return rc;
+    if (heads_q < 1 || heads_q % heads_kv != 0 || heads_q > ((int64_t)1 << 20))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads_q=%lld must be a positive multiple of heads_kv=%lld (at most 2^20)", who,
+                    (long long)heads_q, (long long)heads_kv);
+    if (total_q < 1 || max_seqlen_q < 1 || total_q > ((int64_t)1 << 28) || max_seqlen_q > total_q)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: 1 <= max_seqlen_q <= total_q <= 2^28 is needed (got max_seqlen_q=%lld, total_q=%lld)", who,
+                    (long long)max_seqlen_q, (long long)total_q);
+    if (!(softmax_scale == softmax_scale) || !scale_ok(softmax_scale))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale must be finite and > 0", who);
+    if (!aligned16({q, o}) || (uintptr_t)lse % 4 != 0 || (uintptr_t)cu_seqlens_q % 4 != 0 || (uintptr_t)cu_seqlens_k % 4 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: q and o must be 16-byte aligned, lse, cu_seqlens_q and cu_seqlens_k 4-byte aligned", who);
+    if (q_token_stride % 16 != 0 || q_token_stride < heads_q * 128 || q_token_stride > ((int64_t)1 << 44))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: the token stride of q (%lld) must be a multiple of 16 bytes and >= heads_q * 128 = %lld", who,
+                    (long long)q_token_stride, (long long)(heads_q * 128));
+    if (total_q * heads_q > ((int64_t)1 << 31) - 1)
+        return fail(FA_ERR_UNSUPPORTED, "%s: span limit: total_q * heads_q = %lld is at or above 2^31", who, (long long)(total_q * heads_q));
+    if (heads_kv > 65535 || (max_seqlen_q * (heads_q / heads_kv) + 127) / 128 > ((int64_t)1 << 31) - 1)
+        return fail(FA_ERR_UNSUPPORTED, "%s: span limit: heads_kv = %lld (at most 65535) or the row tiles of max_seqlen_q are beyond one launch",
+                    who, (long long)heads_kv);
+    fa::Fp4VarlenArgs a;
+    a.c = k.c; a.q = q; a.o = o; a.lse = lse; a.q_descale = q_descale; a.k_descale = k_descale; a.v_descale = v_descale;
+    a.qds_bs = k.qds_bs; a.kds_bs = k.kds_bs; a.vds_bs = k.vds_bs; a.cu_seqlens_q = cu_seqlens_q; a.cu_seqlens_k = cu_seqlens_k;
+    a.batch = batch; a.heads_q = heads_q; a.total_q = total_q; a.max_seqlen_q = max_seqlen_q; a.q_ts = q_token_stride;
+    a.dtype = dtype; a.causal = causal != 0; a.scale = (float)softmax_scale;
+    return launched(who, fa::launch_fp4_prefill(a, reinterpret_cast<hipStream_t>(stream)));
 }
 
 int fa_debug_trace_buffer(void* device_ptr) {

@@ -1,0 +1,351 @@
+// Chunked prefill over the paged MXFP4 KV cache for gfx950 (fa_fp4_forward_varlen; include/fa_mi355x.h):
+// packed e4m3 queries (total_q, H_q, 128) over the four pool arrays fa_fp4_kvcache_append fills, per sequence, with the bottom-right
+// causal diagonal of that sequence alone, in one launch and without a workspace.
+//
+//     o[i] = sum_j softmax_j(softmax_scale q_descale k_descale q8[i] . (k4[j] 2^ek[j])) v4[j] 2^ev[j] v_descale
+//
+// The decode kernel (fa_fp4_decode.hip) reads every visible key once per WAVE of 32 rows.  Here a workgroup of four waves owns 128
+// rows and reads a cache byte from memory once: the 64-key tile goes through LDS.
+//
+//   rows and waves   row = token * G + head in the group (the decode kernel's packing), a workgroup takes 128 consecutive rows of
+//                    one (sequence, K/V head), wave w rows 32 w .. 32 w + 31.  Any G works the same way, the whole group shares the
+//                    staged tile, and the four waves end within 96 / G tokens of each other under the causal mask: no wave
+//                    idles through a quarter of the diagonal as it would with one head a wave.  The grid is (row tiles of
+//                    max_seqlen_q, H_kv, B), the heaviest (last) row tile first; a workgroup past its sequence's rows returns.
+//   the tile ring    tile t is computed from LDS stage t & 1 while tile t + 1 lies in the other stage and tile t + 2 is in flight
+//                    in 9 registers a lane (three tiles deep); the table entry of tile t + 3 is fetched at the same time.  One
+//                    barrier a tile: a stage is rewritten at the top of iteration t + 1, after the barrier that ended its last reader.
+//   the loader       wave w moves the tile's 16-key group w (ps % 16 == 0: one page, one wave-uniform table entry):
+//                      K      lane (kk = l >> 2, c = l & 3): 16 code bytes of key kk -> row 80 (16 w + kk) + 16 c of the K stage
+//                      scales lanes 0 .. 15 the k_scale dword of key l -> byte 64 of the key's row; lanes 16 .. 31 the v_scale
+//                             byte of key l - 16 -> evs[key] = byte - 127
+//                      V      lane (rd = l & 15, hv = (l >> 4) & 1, jl = l >> 5): the dwords at channels 8 rd .. + 7 of the four
+//                             keys pos = 4 hv + 8 jl + c of the group (a row of 16 lanes reads a key's 64 bytes), the decode kernel's
+//                             nibble transpose cut to four keys (mask / shift / or, then 4 v_perm_b32), and eight 2-byte writes into
+//                             the V^T image: channel 8 rd + 2 m (+ 1), byte 16 h + 8 hv + 2 j with h = w >> 1, j = 2 (w & 1) + jl.
+//                    So V is transposed ONCE a workgroup and tile, out of the registers the load landed in; the raw codes never
+//                    lie in LDS.  A key at or past the workgroup's last visible key or on a page outside [0, num_blocks) is not
+//                    loaded: zero codes, scale bytes 127, ev = 0.  A group whole below that bound on a valid page skips the
+//                    per-lane compares (wave-uniform).
+//   LDS              K stage: 64 rows of 80 bytes (64 codes, 4 scale bytes, 12 unused): the 16-byte operand reads of 16 lanes land
+//                    at 80 r mod 256 = sixteen different multiples of 16, every bank once.  V^T stage: vt4_off's padded image of
+//                    the decode kernel, 4352 bytes.  evs: 64 ints.  2 x 9728 = 19456 bytes.
+//   a wave's tile    the decode kernel's arithmetic with its operand orders (the header of fa_fp4_decode.hip): S^T = K Q^T with K
+//                    in fp4 as operand A and the lane's k_scale byte on the instruction, q at channels 64 M + 16 h and 64 M + 32 +
+//                    16 h; t = fma(s, f, ev) under the joint running maximum with the lazy rescale; P' rounded to e4m3; l from the
+//                    unrounded ldexp(P', -ev); O^T = V^T P'^T with V^T in fp4 from the image.  The mask (a select on the scores) only
+//                    where the tile holds the sequence's end or a row's diagonal: wave-uniform.  A wave skips the tiles past its own
+//                    rows' last key but keeps loading and meeting the barrier.
+//
+// What is untrusted: cu_seqlens_q, cu_seqlens_k, block_table, the descales and every cache byte, read on the device only.  (start,
+// nq_b) = kv_cu_range(cu_seqlens_q, b, total_q, max_seqlen_q); nk_b = kv_cu_range(cu_seqlens_k, b, 2^31 - 1, capacity).  A scale
+// byte is only ever an operand of arithmetic.  Rows of no sequence are not written.
+#include <algorithm>
+#include <climits>
+
+#include "fa_decode_common.h"
+
+namespace fa {
+
+namespace {
+
+typedef int i32x4_t __attribute__((ext_vector_type(4)));
+typedef int i32x8_t __attribute__((ext_vector_type(8)));
+
+constexpr int kFp4 = 4;                                  // the instruction's format selector of e2m1 (0: e4m3)
+constexpr int kKRow = 80;                                // bytes of a key's row in the K stage
+constexpr int kKBytes = 64 * kKRow;
+constexpr int kVt4Bytes = 32 * 128 + 16 * 16;            // the V^T image of fa_fp4_decode.hip
+__device__ __forceinline__ int vt4_off(int row) { return 32 * row + 16 * (row >> 3); }
+
+struct Fp4PrefillParams {
+    const uint8_t *q, *kc, *ksc, *vc, *vsc;
+    uint16_t* o;
+    float* lse;
+    const float *qds, *kds, *vds;         // (B, H_kv) descales at their batch strides; null: 1
+    long long qds_bs, kds_bs, vds_bs;
+    const int *cu_q, *cu_k, *table;       // untrusted device memory
+    long long tbl_rs;
+    int nblk, ps, cap;
+    long long q_ts, kc_bs, ks_bs, vc_bs, vs_bs;   // q's token stride and the page strides in bytes
+    int kc_ts, ks_ts, vc_ts, vs_ts;               // token strides in bytes
+    int hq, G, total_q, max_q, causal;
+    float c_log2;                         // float(softmax_scale) * log2(e)
+};
+
+// what a lane holds of a tile in flight
+struct Fp4Staged {
+    u32x4 k;
+    uint32_t v[4];
+    uint32_t s;
+};
+
+template <typename Tag>
+__global__ __launch_bounds__(256, 2) void fp4kv_prefill_kernel(const Fp4PrefillParams p) {
+    constexpr int D = 128, KT = 64, NDV = D / 32, HB = D / 2;     // HB: code bytes a head
+    __shared__ __attribute__((aligned(16))) char kt[2][kKBytes];  // K stages: [key][64 code bytes, 4 scale bytes, pad]
+    __shared__ __attribute__((aligned(16))) char vt[2][kVt4Bytes];   // V^T stages, [channel][32 key bytes in P's key order]
+    __shared__ __attribute__((aligned(16))) int evs[2][KT];       // the tiles' V exponents, by key
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int rt = gridDim.x - 1 - blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
+    const int G = p.G;
+
+    int qstart, kdummy;
+    const int nq = kv_cu_range(p.cu_q, b, p.total_q, p.max_q, qstart);
+    const int nk = kv_cu_range(p.cu_k, b, INT_MAX, p.cap, kdummy);
+    const int rows = nq * G, pr0 = 128 * rt;
+    if (pr0 >= rows) return;                                      // (the whole workgroup)
+    const int coff = nk - nq;                                     // causal: token i sees key j <= i + coff
+    // the workgroup's keys [0, kend), the wave's [0, whi)
+    const int wr0 = pr0 + 32 * w;
+    const bool wave_on = wr0 < rows;
+    const int qlo = (wave_on ? wr0 : pr0) / G, qhi = (min(wr0 + 32, rows) - 1) / G, qhi_wg = (min(pr0 + 128, rows) - 1) / G;
+    const int kend = p.causal ? max(0, min(nk, qhi_wg + coff + 1)) : nk;
+    const int whi = !wave_on ? 0 : p.causal ? max(0, min(nk, qhi + coff + 1)) : nk;
+    const int nt = (kend + KT - 1) / KT;
+
+    // this lane's query row: token qi, query head hd; its last visible key rhi
+    const int pr = wr0 + r;
+    const bool valid = pr < rows;
+    // (a padding row takes the wave's first token: its scores are masked like a real row's, and nothing of it is stored)
+    const int qi = valid ? pr / G : qlo, hd = hk * G + (valid ? pr - qi * G : 0);
+    const int rhi = min(p.causal ? qi + coff : nk - 1, kend - 1);
+
+    i32x8_t qb[2];
+    {
+        // (an 8-bit operand's byte 16 g + x of lane half h is k = 32 g + 16 h + x: the two 16-byte halves lie 32 channels apart)
+        const uint8_t* qp = p.q + (long long)(qstart + qi) * p.q_ts + hd * D + 16 * h;
+#pragma unroll
+        for (int M = 0; M < 2; ++M) {
+            const u32x4 a0 = *reinterpret_cast<const u32x4*>(qp + 64 * M), a1 = *reinterpret_cast<const u32x4*>(qp + 64 * M + 32);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                qb[M][i] = valid ? (int)a0[i] : 0;
+                qb[M][4 + i] = valid ? (int)a1[i] : 0;
+            }
+        }
+    }
+    const float qd = p.qds ? p.qds[b * p.qds_bs + hk] : 1.f;
+    const float kd = p.kds ? p.kds[b * p.kds_bs + hk] : 1.f;
+    const float vd = p.vds ? p.vds[b * p.vds_bs + hk] : 1.f;
+    const float f = (p.c_log2 * qd) * kd;                         // the one score factor of this workgroup, > 0
+
+    // ---- the loader: this wave's 16-key group of a tile
+    const int* tbl = p.table + b * p.tbl_rs;
+    const int kk = lane >> 2, kch = lane & 3;                     // K: key of the group, 16-byte chunk
+    const int rd = lane & 15, hv = (lane >> 4) & 1, jl = lane >> 5;   // V: channels 8 rd .., keys 4 hv + 8 jl + c of the group
+    // the group's table entry, -1 where the group starts at or past kend (no entry is read there)
+    auto fetch_page = [&](int t) -> int {
+        const int key0 = t * KT + 16 * w;
+        return key0 < kend ? tbl[key0 / p.ps] : -1;
+    };
+    auto load_tile = [&](int t, int pg) -> Fp4Staged {
+        Fp4Staged st;
+        st.k = u32x4{0u, 0u, 0u, 0u};
+        st.v[0] = st.v[1] = st.v[2] = st.v[3] = 0u;
+        st.s = lane < 16 ? 0x7f7f7f7fu : 127u;
+        const int key0 = t * KT + 16 * w;
+        if (key0 >= kend || (unsigned)pg >= (unsigned)p.nblk) return st;      // (wave-uniform)
+        const long long sl = key0 % p.ps;
+        const uint8_t* kp = p.kc + pg * p.kc_bs + sl * p.kc_ts + hk * HB;
+        const uint8_t* vp = p.vc + pg * p.vc_bs + sl * p.vc_ts + hk * HB + 4 * rd;
+        const uint8_t* sp = p.ksc + pg * p.ks_bs + sl * p.ks_ts + hk * 4;
+        const uint8_t* ep = p.vsc + pg * p.vs_bs + sl * p.vs_ts + hk;
+        const bool full = key0 + 16 <= kend;                     // no lane needs a compare
+        if (full || key0 + kk < kend) st.k = *reinterpret_cast<const u32x4*>(kp + kk * p.kc_ts + 16 * kch);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int pos = 4 * hv + 8 * jl + c;
+            if (full || key0 + pos < kend) st.v[c] = *reinterpret_cast<const uint32_t*>(vp + pos * p.vc_ts);
+        }
+        if (lane < 16) {
+            if (full || key0 + lane < kend) st.s = *reinterpret_cast<const uint32_t*>(sp + lane * p.ks_ts);
+        } else if (lane < 32) {
+            if (full || key0 + lane - 16 < kend) st.s = ep[(lane - 16) * p.vs_ts];
+        }
+        return st;
+    };
+    auto store_tile = [&](const Fp4Staged& st, int buf) {
+        *reinterpret_cast<u32x4*>(kt[buf] + kKRow * (16 * w + kk) + 16 * kch) = st.k;
+        if (lane < 16) *reinterpret_cast<uint32_t*>(kt[buf] + kKRow * (16 * w + lane) + 64) = st.s;
+        else if (lane < 32) evs[buf][16 * w + lane - 16] = (int)st.s - 127;
+        // V -> V^T: four keys x eight channels a lane; the even (odd) channels of key pairs (0, 1) and (2, 3) in a byte each
+        constexpr uint32_t LO = 0x0f0f0f0fu;
+        const uint32_t ea = (st.v[0] & LO) | ((st.v[1] & LO) << 4), eb = (st.v[2] & LO) | ((st.v[3] & LO) << 4);
+        const uint32_t oa = ((st.v[0] >> 4) & LO) | (st.v[1] & ~LO), ob = ((st.v[2] >> 4) & LO) | (st.v[3] & ~LO);
+        // bytes {a.m, b.m} side by side: channel pair m = 0, 1 in the first word's halves, m = 2, 3 in the second's
+        const uint32_t e01 = __builtin_amdgcn_perm(eb, ea, 0x05010400u), e23 = __builtin_amdgcn_perm(eb, ea, 0x07030602u);
+        const uint32_t o01 = __builtin_amdgcn_perm(ob, oa, 0x05010400u), o23 = __builtin_amdgcn_perm(ob, oa, 0x07030602u);
+        char* base = vt[buf] + 16 * (w >> 1) + 8 * hv + 2 * (2 * (w & 1) + jl);
+        *reinterpret_cast<uint16_t*>(base + vt4_off(8 * rd + 0)) = (uint16_t)e01;
+        *reinterpret_cast<uint16_t*>(base + vt4_off(8 * rd + 1)) = (uint16_t)o01;
+        *reinterpret_cast<uint16_t*>(base + vt4_off(8 * rd + 2)) = (uint16_t)(e01 >> 16);
+        *reinterpret_cast<uint16_t*>(base + vt4_off(8 * rd + 3)) = (uint16_t)(o01 >> 16);
+        *reinterpret_cast<uint16_t*>(base + vt4_off(8 * rd + 4)) = (uint16_t)e23;
+        *reinterpret_cast<uint16_t*>(base + vt4_off(8 * rd + 5)) = (uint16_t)o23;
+        *reinterpret_cast<uint16_t*>(base + vt4_off(8 * rd + 6)) = (uint16_t)(e23 >> 16);
+        *reinterpret_cast<uint16_t*>(base + vt4_off(8 * rd + 7)) = (uint16_t)(o23 >> 16);
+    };
+
+    f32x16 oacc[NDV];
+#pragma unroll
+    for (int t = 0; t < NDV; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) oacc[t][i] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;                         // running max of t, in log2 units
+
+    // ---- one 64-key tile of this wave out of stage buf
+    auto compute = [&](int k0, int buf) {
+        const char* ktb = kt[buf];
+        const char* vtb = vt[buf];
+        const int* evb = evs[buf];
+        f32x16 sacc[2];
+        // S^T = K Q^T: K codes as they lie in memory, the lane's MX block scale on the instruction
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+            const char* row = ktb + kKRow * (32 * kb + r);
+            const u32x4 a0 = *reinterpret_cast<const u32x4*>(row + 16 * h), a1 = *reinterpret_cast<const u32x4*>(row + 32 + 16 * h);
+            const uint32_t ws = *reinterpret_cast<const uint32_t*>(row + 64);
+            const int sc0 = (int)((ws >> (8 * h)) & 0xffu), sc1 = (int)((ws >> (16 + 8 * h)) & 0xffu);
+            const i32x8_t k0a = {(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], 0, 0, 0, 0};
+            const i32x8_t k1a = {(int)a1[0], (int)a1[1], (int)a1[2], (int)a1[3], 0, 0, 0, 0};
+#pragma unroll
+            for (int i = 0; i < 16; ++i) sacc[kb][i] = 0.f;
+            sacc[kb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(k0a, qb[0], sacc[kb], kFp4, 0, 0, sc0, 0, 127);
+            sacc[kb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(k1a, qb[1], sacc[kb], kFp4, 0, 0, sc1, 0, 127);
+        }
+
+        // t = s f + ev, the mask, the row maximum over t
+        // (the mask only where the sequence or a row of the wave can end inside this key tile: wave-uniform)
+        const bool need_mask = k0 + KT > kend || (p.causal && k0 + KT - 1 > qlo + coff);
+        int ev[2][16];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const i32x4_t e4 = *reinterpret_cast<const i32x4_t*>(evb + 32 * kb + 4 * h + 8 * j);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) ev[kb][4 * j + c] = e4[c];
+            }
+            if (need_mask) {
+                const int thr = rhi - (k0 + 32 * kb + 4 * h);
+#pragma unroll
+                for (int i = 0; i < 16; ++i)
+                    if ((i & 3) + 8 * (i >> 2) > thr) sacc[kb][i] = -INFINITY;
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                sacc[kb][i] = fmaf(sacc[kb][i], f, (float)ev[kb][i]);    // (-inf stays -inf: f > 0)
+                mx = fmaxf(mx, sacc[kb][i]);
+            }
+        }
+        mx = fmaxf(mx, wave_half_swap(mx));
+        const float m_new = fmaxf(m_run, mx);
+        float m_use;
+        if (__any(valid && m_new - m_run > 8.0f) != 0) {   // lazy rescale on the real rows; a row's first visible key: inf > 8
+            m_use = m_new;
+            const float alpha = __builtin_amdgcn_exp2f(m_run - ((m_new == -INFINITY) ? 0.f : m_new));
+            m_run = m_new;
+            l_run *= alpha;
+#pragma unroll
+            for (int t2 = 0; t2 < NDV; ++t2)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) oacc[t2][i] *= alpha;
+        } else {
+            m_use = m_run;
+        }
+        if (m_use == -INFINITY) m_use = 0.f;      // a row without a visible key so far: p = exp2(-inf) = 0, not exp2(-inf + inf)
+        float rs = 0.f;
+        i32x8_t pb;                               // P'^T as the accumulators hold it, rounded to e4m3 (RNE)
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const float pe = __builtin_amdgcn_exp2f(sacc[kb][i] - m_use);
+                sacc[kb][i] = pe;
+                rs += __builtin_ldexpf(pe, -ev[kb][i]);          // the key's share of l: exp2(s f - M), V's scale taken out again
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                int wd = 0;
+                wd = __builtin_amdgcn_cvt_pk_fp8_f32(sacc[kb][4 * j + 0], sacc[kb][4 * j + 1], wd, false);
+                wd = __builtin_amdgcn_cvt_pk_fp8_f32(sacc[kb][4 * j + 2], sacc[kb][4 * j + 3], wd, true);
+                pb[4 * kb + j] = wd;
+            }
+        }
+        l_run += rs;
+
+        // O^T = V^T P'^T: the lane's 16 key bytes (32 keys) of channel 32 dvb + r
+#pragma unroll
+        for (int dvb = 0; dvb < NDV; ++dvb) {
+            const u32x4 a0 = *reinterpret_cast<const u32x4*>(vtb + vt4_off(32 * dvb + r) + 16 * h);
+            const i32x8_t va = {(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], 0, 0, 0, 0};
+            oacc[dvb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(va, pb, oacc[dvb], kFp4, 0, 0, 127, 0, 127);
+        }
+    };
+
+    // ---- the ring: tile t in stage t & 1, tile t + 1 in the other, tile t + 2 in st, the table entry of tile t + 3 in pg
+    Fp4Staged st = load_tile(0, fetch_page(0));
+    int pg = fetch_page(1);
+    store_tile(st, 0);
+    st = load_tile(1, pg);
+    pg = fetch_page(2);
+    __syncthreads();
+    for (int t = 0; t < nt; ++t) {
+        store_tile(st, (t + 1) & 1);              // (its last readers, of tile t - 1, are behind the barrier)
+        st = load_tile(t + 2, pg);
+        pg = fetch_page(t + 3);
+        if (t * KT < whi) compute(t * KT, t & 1);
+        __syncthreads();
+    }
+
+    // ---- epilogue: O^T register i of block dvb is channel 32 dvb + 4 h + (i & 3) + 8 (i >> 2) of the lane's query row
+    const float l_tot = l_run + wave_half_swap(l_run);
+    if (!valid) return;
+    const bool dead = l_tot == 0.f;                      // no visible key: o = 0, lse = -inf (a NaN l is not dead: it propagates)
+    const float inv = vd * (1.f / l_tot);                // v_descale once, with 1 / l
+    const float lse_v = dead ? -INFINITY : (m_run + log2f(l_tot)) * 0.6931471805599453f;
+    uint16_t* orow = p.o + ((size_t)(qstart + qi) * p.hq + hd) * D;
+#pragma unroll
+    for (int dvb = 0; dvb < NDV; ++dvb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            float y[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) y[j] = dead ? 0.f : oacc[dvb][4 * g + j] * inv;
+            u32x2 v;
+            v[0] = pack2_rn<Tag>(y[0], y[1]);
+            v[1] = pack2_rn<Tag>(y[2], y[3]);
+            *reinterpret_cast<u32x2*>(orow + 32 * dvb + 8 * g + 4 * h) = v;
+        }
+    if (h == 0) p.lse[(size_t)hd * p.total_q + qstart + qi] = lse_v;
+}
+
+}  // namespace
+
+hipError_t launch_fp4_prefill(const Fp4VarlenArgs& a, hipStream_t st) {
+    Fp4PrefillParams p;
+    p.q = (const uint8_t*)a.q; p.kc = (const uint8_t*)a.c.k_cache; p.ksc = (const uint8_t*)a.c.k_scale;
+    p.vc = (const uint8_t*)a.c.v_cache; p.vsc = (const uint8_t*)a.c.v_scale;
+    p.o = (uint16_t*)a.o; p.lse = a.lse;
+    p.qds = a.q_descale; p.kds = a.k_descale; p.vds = a.v_descale;
+    p.qds_bs = a.qds_bs; p.kds_bs = a.kds_bs; p.vds_bs = a.vds_bs;
+    p.cu_q = a.cu_seqlens_q; p.cu_k = a.cu_seqlens_k; p.table = a.c.block_table;
+    p.tbl_rs = a.c.table_row_stride; p.nblk = (int)a.c.num_blocks; p.ps = (int)a.c.page_size; p.cap = (int)a.c.cache_len;
+    p.q_ts = a.q_ts; p.kc_bs = a.c.kc_bs; p.ks_bs = a.c.ks_bs; p.vc_bs = a.c.vc_bs; p.vs_bs = a.c.vs_bs;
+    p.kc_ts = (int)a.c.kc_ts; p.ks_ts = (int)a.c.ks_ts; p.vc_ts = (int)a.c.vc_ts; p.vs_ts = (int)a.c.vs_ts;
+    p.hq = (int)a.heads_q; p.G = (int)(a.heads_q / a.c.heads_kv);
+    p.total_q = (int)a.total_q; p.max_q = (int)a.max_seqlen_q; p.causal = a.causal != 0;
+    p.c_log2 = a.scale * 1.4426950408889634f;
+    const unsigned row_tiles = (unsigned)((a.max_seqlen_q * p.G + 127) / 128);
+    const dim3 grid(row_tiles, (unsigned)a.c.heads_kv, (unsigned)a.batch);
+    route_hit(ROUTE_FP4KV_PREFILL);
+    ProfScope ps(K_FP4KV_PREFILL, st);
+    if (a.dtype == 2) hipLaunchKernelGGL((fp4kv_prefill_kernel<bf16_tag>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((fp4kv_prefill_kernel<f16_tag>), grid, dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+
+}  // namespace fa

@@ -66,7 +66,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_fp8_forward_hdim_workspace_bytes", "fa_fp8_forward_varlen_hdim_workspace_bytes", "fa_fp8_forward_kvcache_hdim_workspace_bytes",
     "fa_fp8_forward_kvcache_varlen", "fa_fp8_forward_kvcache_varlen_workspace_bytes",
     "fa_fp8_kvcache_step_varlen", "fa_fp8_kvcache_step_varlen_workspace_bytes",
-    "fa_fp4_kvcache_append", "fa_fp4_forward_kvcache", "fa_fp4_forward_kvcache_workspace_bytes",
+    "fa_fp4_kvcache_append", "fa_fp4_forward_kvcache", "fa_fp4_forward_kvcache_workspace_bytes", "fa_fp4_forward_varlen",
 )
 
 
@@ -276,6 +276,10 @@ _sig("fa_fp4_forward_kvcache", _fields(
     "i:batch,heads_q,heads_kv,seqlen_q,cache_len,cache_batch,d c:dtype i:q_batch_stride,q_token_stride") + _FP4STRIDES +
     _fields("i:q_descale_batch_stride,k_descale_batch_stride,v_descale_batch_stride c:causal d:softmax_scale i:num_splits") + _WS)
 _sig("fa_fp4_forward_kvcache_workspace_bytes", _KVWS, _SIZE)
+_sig("fa_fp4_forward_varlen", _fields(
+    "p:q,k_cache,k_scale,v_cache,v_scale,o,lse,q_descale,k_descale,v_descale,cu_seqlens_q,cu_seqlens_k,block_table "
+    "i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,d c:dtype i:q_token_stride") + _FP4STRIDES +
+    _fields("i:q_descale_batch_stride,k_descale_batch_stride,v_descale_batch_stride c:causal d:softmax_scale") + _STREAM)
 _KVWSV = _fields("i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,d,num_splits c:with_sinks")
 _sig("fa_ex_kvcache_workspace_bytes_varlen", _KVWSV, _SIZE)
 _sig("fa_ex_kvcache_workspace_bytes_qv", _KVWSV + _fields("i:d_v"), _SIZE)
@@ -347,6 +351,7 @@ _family("fa_fp8_kvcache_step_varlen", [])
 # the MXFP4 KV cache: the append and the decode call, a family of one each
 _family("fa_fp4_kvcache_append", [])
 _family("fa_fp4_forward_kvcache", [])
+_family("fa_fp4_forward_varlen", [])
 _family("fa_ex_forward_kvcache_qv", ["fa_ex_forward_kvcache" + _suffix for _suffix in ("", "_paged", "_rotary", "_fp8", "_sink", "_varlen")])
 
 
@@ -3177,5 +3182,69 @@ def fp4_kvcache_forward(q, k_cache, k_scale, v_cache, v_scale, cache_seqlens=Non
             _ptr(block_table), _ptr(cache_batch_idx), b, hq, hkv, nq, cap, cbatch, 128, _DTYPE_CODE[out_dtype],
             q.stride(0) if b > 1 else 0, q.stride(1) if nq > 1 else hq * 128, *strides, *pages, qds, kds, vds, int(bool(causal)), scale, ns,
             ws.data_ptr() if need else 0, ws.numel() if need else 0, _stream_ptr(q.device)))
+    del keep_q, keep_k, keep_v
+    return o, lse
+
+
+def fp4_varlen_forward(q, k_cache, k_scale, v_cache, v_scale, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, block_table,
+                       q_descale=None, k_descale=None, v_descale=None, softmax_scale=None, causal=False, out_dtype=torch.bfloat16, out=None):
+    """(o, lse) of chunked prefill over the paged MXFP4 KV cache (fa_fp4_forward_varlen): q (total_q, H_q, 128)
+    torch.float8_e4m3fn at its own token stride (a view such as qkv8[:, 0] is used in place) over the pools fp4_kvcache_append fills
+    (its docstring has the four arrays) under block_table int32 (B, max_blocks); cu_seqlens_q / cu_seqlens_k int32 (B + 1,) on the
+    device, clamped there (nq_b to max_seqlen_q and the tokens left in q, nk_b to max_blocks * ps) and never read on the host;
+    max_seqlen_k is checked and otherwise unused.  Per sequence, causal on its own bottom-right diagonal.  Descales float32 (B, H_kv)
+    or (H_kv,), None = 1.  o (total_q, H_q, 128) in out_dtype, lse float32 (H_q, total_q); rows of no sequence keep their contents
+    (a fresh output is uninitialised there).  One launch, no workspace.  out: an (o, lse) pair of contiguous tensors to write into."""
+    who = "fp4_varlen_forward"
+    if not isinstance(q, torch.Tensor) or q.dtype != torch.float8_e4m3fn:
+        dt = q.dtype if isinstance(q, torch.Tensor) else type(q).__name__
+        raise NotImplementedError(f"{who}: q of dtype {dt} is not supported (torch.float8_e4m3fn expected: quantize_fp8)")
+    if out_dtype not in (torch.bfloat16, torch.float16):
+        raise NotImplementedError(f"{who}: out_dtype {out_dtype} is not supported (torch.bfloat16 or torch.float16)")
+    if q.dim() != 3:
+        raise RuntimeError(f"{who}: q must be packed (total_q, H_q, 128), got {tuple(q.shape)}")
+    if q.shape[2] != 128:
+        raise NotImplementedError(f"{who}: head_dim {q.shape[2]} is not supported (128 only); got q of shape {tuple(q.shape)}")
+    if block_table is None:
+        raise RuntimeError(f"{who}: block_table is required (a contiguous (B, cap, H_kv, ..) cache is a pool of B * cap / ps pages "
+                           f"under an arange table)")
+    for name, t in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.dim() == 1 and t.shape[0] >= 2):
+            raise RuntimeError(f"{who}: {name} must be an int32 tensor of shape (B + 1,)")
+    b, total_q, hq = cu_seqlens_q.shape[0] - 1, q.shape[0], q.shape[1]
+    if cu_seqlens_k.shape[0] != b + 1:
+        raise RuntimeError(f"{who}: cu_seqlens_q and cu_seqlens_k must both be (B + 1,); got {tuple(cu_seqlens_q.shape)}, {tuple(cu_seqlens_k.shape)}")
+    max_q, max_k = operator.index(max_seqlen_q), operator.index(max_seqlen_k)
+    if max_q < 0 or max_k < 0:
+        raise RuntimeError(f"{who}: max_seqlen_q and max_seqlen_k must be >= 0 (got {max_q}, {max_k})")
+    arrays, hkv, cap, _cbatch, strides, pages, block_table, _ = _fp4_cache(who, k_cache, k_scale, v_cache, v_scale, block_table, None, b)
+    if hq == 0 or hq % hkv != 0:
+        raise RuntimeError(f"{who}: H_q = {hq} must be a multiple of H_kv = {hkv}")
+    _fp4_one_device(who, q, *arrays, cu_seqlens_q, cu_seqlens_k, block_table)
+    scale = 128 ** -0.5 if softmax_scale is None else float(softmax_scale)
+    if not (math.isfinite(scale) and scale > 0.0):
+        raise RuntimeError(f"{who}: softmax_scale must be finite and > 0 (got {scale})")
+    if q.numel() and ((hq > 1 and q.stride(1) != 128) or q.stride(2) != 1):
+        raise ValueError(f"{who}: q must have adjacent heads with a contiguous last dim (strides {q.stride()})")
+    qdp, qds, keep_q = _kv_descale(who, "q_descale", q_descale, q, b, hkv)
+    kdp, kds, keep_k = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
+    vdp, vds, keep_v = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
+    cu_seqlens_q, cu_seqlens_k = cu_seqlens_q.contiguous(), cu_seqlens_k.contiguous()
+    with torch.cuda.device(q.device):
+        if out is not None:
+            o, lse = out
+            if (tuple(o.shape), o.dtype, tuple(lse.shape), lse.dtype) != ((total_q, hq, 128), out_dtype, (hq, total_q), torch.float32) or \
+                    not (o.is_contiguous() and lse.is_contiguous() and o.device == q.device and lse.device == q.device):
+                raise RuntimeError(f"{who}: out must be contiguous (o ({total_q}, {hq}, 128) {out_dtype}, lse ({hq}, {total_q}) float32) on q's device")
+        else:
+            o = torch.empty((total_q, hq, 128), dtype=out_dtype, device=q.device)
+            lse = torch.empty((hq, total_q), dtype=torch.float32, device=q.device)
+        max_q = min(max_q, total_q)
+        if b == 0 or total_q == 0 or max_q == 0:
+            return o, lse
+        _call("fa_fp4_forward_varlen", (
+            q.data_ptr(), *(t.data_ptr() for t in arrays), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp, cu_seqlens_q.data_ptr(),
+            cu_seqlens_k.data_ptr(), block_table.data_ptr(), b, hq, hkv, total_q, max_q, cap, 128, _DTYPE_CODE[out_dtype],
+            q.stride(0) if total_q > 1 else hq * 128, *strides, *pages, qds, kds, vds, int(bool(causal)), scale, _stream_ptr(q.device)))
     del keep_q, keep_k, keep_v
     return o, lse

@@ -1610,6 +1610,36 @@ int fa_fp4_forward_kvcache(const void* q, const void* k_cache, const void* k_sca
                            size_t workspace_bytes, void* stream);
 size_t fa_fp4_forward_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
                                               int64_t d, int64_t num_splits);
+/* --- Chunked prefill over the paged MXFP4 cache: packed e4m3 queries, one launch, no workspace.  Forward only; a
+ * call family of its own.  q (total_q, heads_q, 128) e4m3 at q_token_stride bytes (heads adjacent), o (total_q, heads_q, 128) in dtype
+ * and lse (heads_q, total_q) float32, both contiguous.  The cache is the four pool arrays of fa_fp4_kvcache_append, (num_blocks,
+ * page_block_size, heads_kv, ..) at their page ("batch") and token strides, under block_table (batch, max_blocks_per_seq) at
+ * block_table_row_stride; cache_len = max_blocks_per_seq * page_block_size is the capacity of a sequence.  A contiguous (B, cap, ..)
+ * cache with cap % 16 == 0 is such a pool under an arange table.  Per sequence b, on the device (kv_cu_range), from untrusted offsets:
+ *     start_b = clamp(cu_seqlens_q[b], 0, total_q), nq_b = clamp(cu_seqlens_q[b + 1] - cu_seqlens_q[b], 0, min(max_seqlen_q, total_q - start_b)),
+ *     nk_b = clamp(cu_seqlens_k[b + 1] - cu_seqlens_k[b], 0, cache_len)   (cu_seqlens_k gives lengths only: key j of b is slot j of b's pages)
+ *     s[i, j] = softmax_scale * q_descale * k_descale * (q8[start_b + i] . (k4[j] * 2^ek[j])),  j < nk_b, with causal j <= i + nk_b - nq_b
+ *     o[start_b + i] = sum_j softmax(s)[i, j] * v4[j] * 2^ev[j] * v_descale
+ * with fa_fp4_forward_kvcache's arithmetic (P' = exp2(s f + ev - M) in e4m3 over the raw v4 codes, l from the unrounded values).  A row
+ * without a visible key gives o = 0, lse = -inf; rows of no sequence are not written; sequences may be empty.  Nothing is read on the
+ * host: a captured call replays after offsets, table, descales and cache bytes changed in place.  A page outside [0, num_blocks)
+ * reads as zero codes with unit scales; keys at or past nk_b are never loaded; a scale byte is only ever an operand of arithmetic.
+ * A workgroup of four waves shares each 64-key tile through LDS and transposes V once (fa_fp4_prefill.hip); below about 32 /
+ * (heads_q / heads_kv) rows a sequence fa_fp4_forward_kvcache, which splits the keys, stays the faster call.
+ * Checks, the first broken rule named in fa_last_error(): the empty call (batch, total_q or max_seqlen_q == 0) is FA_OK; null tensor
+ * pointers, null cu_seqlens_q / cu_seqlens_k, null block_table; then fa_fp4_forward_kvcache's rules in its order (d == 128 and the
+ * dtype: FA_ERR_UNSUPPORTED; extents; alignment and strides; descale strides; page arguments; span limits); then heads_q, 1 <=
+ * max_seqlen_q <= total_q <= 2^28, softmax_scale, the alignment of q, o, lse and the offsets, q_token_stride, and the span limits of
+ * this call (FA_ERR_UNSUPPORTED: total_q * heads_q below 2^31, heads_kv at most 65535). */
+int fa_fp4_forward_varlen(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o,
+                          float* lse, const float* q_descale, const float* k_descale, const float* v_descale,
+                          const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, const int32_t* block_table, int64_t batch,
+                          int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t max_seqlen_q, int64_t cache_len, int64_t d,
+                          int dtype, int64_t q_token_stride, int64_t k_batch_stride, int64_t k_token_stride,
+                          int64_t k_scale_batch_stride, int64_t k_scale_token_stride, int64_t v_batch_stride, int64_t v_token_stride,
+                          int64_t v_scale_batch_stride, int64_t v_scale_token_stride, int64_t block_table_row_stride,
+                          int64_t num_blocks, int64_t page_block_size, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
+                          int64_t v_descale_batch_stride, int causal, double softmax_scale, void* stream);
 
 const char* fa_last_error(void);
 const char* fa_version(void);
@@ -1635,7 +1665,8 @@ int fa_profile_report(char* buf, size_t cap);
  * "fp8kv_split_varlen": the packed split kernel of fa_fp8_forward_kvcache_varlen and fa_fp8_kvcache_step_varlen;
  * "fp8kv_step_prep_varlen": the prep launch of fa_fp8_kvcache_step_varlen with packed tokens or at head dim 64 / 256; one count a
  * call that launched one (null packed groups count what the parent calls count).  "fp4kv_append", "fp4kv_split": the kernels of
- * fa_fp4_kvcache_append and fa_fp4_forward_kvcache, one count a call that launched. */
+ * fa_fp4_kvcache_append and fa_fp4_forward_kvcache, one count a call that launched.  "fp4kv_prefill": the kernel of
+ * fa_fp4_forward_varlen, one count a call that launched. */
 int64_t fa_route_count(const char* name);
 
 #ifdef __cplusplus

@@ -83,7 +83,11 @@ was; its own attention comes with it), quantize_fp8 on q, the fp8 decode call.
 widened exactly to e4m3, interleaved rounds: H 32:8, Nq 1, B 8 and 64, 4096 and 32768 cached keys, contiguous and paged (ps 16,
 shuffled); per row both times, their ratio, and the cache bytes (133 against 256 a token and head) over the time.  Then the append
 of one token a sequence at B 64 by the kernels' own profile scopes: fp4kv_append against the e4m3 step's prep launch (its append plus
-the q quantise)."""
+the q quantise).
+`--fp4-prefill`: one causal prefill chunk at the end of a paged MXFP4 cache (ps 16, shuffled; H 32:8; chunks of 512 and 2048 tokens,
+8192 and 32768 keys, B 1 and 8), interleaved rounds of three calls on the same tokens: fp4_varlen_forward,
+the decode call fp4_kvcache_forward with Nq = chunk (the only way to serve the shape before), and fp8_varlen_forward(block_table=) on
+the pool widened exactly to e4m3; per row the three medians, their spreads ((max - min) / median) and the two ratios."""
 import argparse
 import json
 import os
@@ -574,6 +578,52 @@ def fp8q_rows(args, dtype):
     return rows
 
 
+def fp4_prefill_rows(args, dtype):
+    """--fp4-prefill: see the module docstring"""
+    dev, rounds, hq, hkv, ps = "cuda", max(args.rounds, 5), 32, 8, 16
+    mags = torch.tensor([0, .5, 1, 1.5, 2, 3, 4, 6, -0., -.5, -1, -1.5, -2, -3, -4, -6], dtype=torch.float32, device=dev)
+    rows = []
+    for b in (1, 8):
+        for L in (8192, 32768):
+            nblk = b * L // ps
+            kc, vc = (torch.randint(0, 256, (nblk, ps, hkv, 64), device=dev, dtype=torch.uint8) for _ in range(2))
+            ks = torch.randint(124, 131, (nblk, ps, hkv, 4), device=dev, dtype=torch.uint8)
+            vs = torch.randint(124, 131, (nblk, ps, hkv), device=dev, dtype=torch.uint8)
+            k8, v8 = (torch.empty((nblk, ps, hkv, 128), device=dev, dtype=torch.float8_e4m3fn) for _ in range(2))
+            for lo in range(0, nblk, 4096):   # the same values in e4m3 (exact), 4096 pages at a time
+                for c4, sc, out in ((kc, ks, k8), (vc, vs, v8)):
+                    x = mags[torch.stack((c4[lo:lo + 4096] & 15, c4[lo:lo + 4096] >> 4), -1).flatten(-2).long()]
+                    e = torch.exp2(sc[lo:lo + 4096].float() - 127.0).reshape(*x.shape[:3], -1)
+                    out[lo:lo + 4096] = (x * e.repeat_interleave(128 // e.shape[-1], -1)).to(torch.float8_e4m3fn)
+            table = torch.randperm(nblk, device=dev).view(b, L // ps).to(torch.int32)
+            qd, kd, vd = (torch.full((b, hkv), x, dtype=torch.float32, device=dev) for x in (0.25, 0.0625, 0.5))
+            sl = torch.full((b,), L, dtype=torch.int32, device=dev)
+            for n in (512, 2048):
+                q8 = torch.randn((b, n, hq, 128), device=dev).to(torch.float8_e4m3fn)
+                qp = q8.view(b * n, hq, 128)
+                cu_q = torch.arange(b + 1, dtype=torch.int32, device=dev) * n
+                cu_k = torch.arange(b + 1, dtype=torch.int32, device=dev) * L
+                new = lambda: ext.fp4_varlen_forward(qp, kc, ks, vc, vs, cu_q, cu_k, n, L, table, qd, kd, vd, None, True, dtype)   # noqa: E731
+                dec = lambda: ext.fp4_kvcache_forward(q8, kc, ks, vc, vs, sl, table, None, qd, kd, vd, None, True, 0, dtype)   # noqa: E731
+                e4 = lambda: ext.fp8_varlen_forward(qp, k8, v8, cu_q, cu_k, n, L, True, None, qd, kd, vd, dtype, table)   # noqa: E731
+                torch.testing.assert_close(new()[0].float(), dec()[0].view(b * n, hq, 128).float(), rtol=5e-2, atol=5e-2)
+                tn, td, t8 = [], [], []
+                for _ in range(rounds):
+                    td.append(timed(dec, 1, max(args.iters // 3, 2), 1))
+                    t8.append(timed(e4, args.warmup, args.iters, 1))
+                    tn.append(timed(new, args.warmup, args.iters, 1))
+                mn, md, m8 = (statistics.median(t) for t in (tn, td, t8))
+                spread = lambda t, m: round((max(t) - min(t)) / m, 3)   # noqa: E731
+                flops = 4.0 * b * hq * 128 * n * (L - n / 2.0)
+                rows.append(dict(kind="fp4_prefill", b=b, L=L, chunk=n, new_us=round(mn, 1), decode_us=round(md, 1), e4m3_varlen_us=round(m8, 1),
+                                 new_spread=spread(tn, mn), decode_spread=spread(td, md), e4m3_spread=spread(t8, m8),
+                                 decode_over_new=round(md / mn, 2), new_over_e4m3=round(mn / m8, 3), new_TFLOPs=round(flops / mn / 1e6, 1)))
+                print(json.dumps(rows[-1]), flush=True)
+            del kc, vc, ks, vs, k8, v8
+            torch.cuda.empty_cache()
+    return rows
+
+
 def fp4_rows(args, dtype):
     """--fp4: see the module docstring"""
     dev, rounds, hq, hkv = "cuda", max(args.rounds, 5), 32, 8
@@ -878,6 +928,7 @@ def main():
     ap.add_argument("--fp8-step", action="store_true", help="time the fp8 decode step against its parent and the 16-bit-q call with the append: see the module docstring")
     ap.add_argument("--fp8-varlen", action="store_true", help="time the packed fp8 decode call and step, and the step at d 64 / 256: see the module docstring")
     ap.add_argument("--fp4", action="store_true", help="time decoding over the MXFP4 cache against the e4m3 decode call, and the append: see the module docstring")
+    ap.add_argument("--fp4-prefill", action="store_true", help="time chunked prefill over the MXFP4 cache against the decode call and the e4m3 packed call: see the module docstring")
     ap.add_argument("--md", default=None, help="--fp8-step: write the table as markdown to this path")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
@@ -893,6 +944,12 @@ def main():
         ext.ex_kvcache_forward(wq, wk, wk, None, None, wl, True, None)
     torch.cuda.synchronize()
     del wq, wk
+    if args.fp4_prefill:
+        rows = fp4_prefill_rows(args, dtype)
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(dict(fp4_prefill=True, dtype=args.dtype, version=ext.version(), rows=rows), f, indent=1)
+        return
     if args.fp4:
         rows = fp4_rows(args, dtype)
         if args.json:
