@@ -34,7 +34,7 @@ const char* const kKernelNames[fa::K_COUNT] = {"fwd_f32", "bwd_delta", "bwd_dkdv
                                                "idx_topk", "fp8kv_split", "fp8q_amax", "fp8q_quant", "fp8q_fused", "fp8in_fwd_mod",
                                                "fp8in_fwd_varlen_mod", "fp8kv_split_mod", "fp8kv_step_prep", "fp8in_fwd_hdim",
     "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim", "fp8kv_split_varlen", "fp8kv_step_prep_varlen", "fp4kv_append", "fp4kv_split",
-    "fp4kv_prefill"};
+    "fp4kv_prefill", "fp4kv_split_mod", "fp4kv_prefill_mod"};
 
 hipEvent_t prof_get_event() {
     if (!g_prof_free.empty()) { hipEvent_t e = g_prof_free.back(); g_prof_free.pop_back(); return e; }
@@ -182,7 +182,7 @@ constexpr const char* kRouteNames[ROUTE_COUNT] = {"dkdv_stream", "dkdv_lean", "f
                                                    "fp8in_fwd_mod", "fp8in_fwd_varlen_mod", "fp8kv_split_mod", "fp8kv_step_prep", "fp8in_fwd_hdim",
                                                    "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim", "fp8kv_split_varlen",
                                                    "fp8kv_step_prep_varlen", "fp4kv_append", "fp4kv_split",
-    "fp4kv_prefill"};
+    "fp4kv_prefill", "fp4kv_split_mod", "fp4kv_prefill_mod"};
 void route_hit(int id) { g_route_hits[id].fetch_add(1, std::memory_order_relaxed); }
 long long route_count(const char* name) {
     for (int i = 0; i < ROUTE_COUNT; ++i)
@@ -4076,13 +4076,40 @@ int fa_fp4_kvcache_append(const void* k_new, const void* v_new, void* k_cache, v
     return launched(who, fa::launch_fp4_kvcache_append(a, reinterpret_cast<hipStream_t>(stream)));
 }
 
+// What the _mod entry points of the two MXFP4 cache readers add (fp8_mod_check's rules and words; a sink array of one logit for
+// every head is taken as well: the combine and the prefill epilogue read sinks[h % sink_heads])
+static int fp4_mod_check(const char* who, const fa::Fp8Mod& m, int64_t heads_q) {
+    if (m.window_left < -1 || m.window_right < -1)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: window (%lld, %lld): each bound must be >= 0, or -1 for unbounded", who,
+                    (long long)m.window_left, (long long)m.window_right);
+    if (!(m.softcap == m.softcap) || m.softcap < 0.0 || m.softcap > 3.0e38)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: softcap must be a finite number >= 0 (got %g)", who, m.softcap);
+    if (m.sinks) {
+        if (m.sink_heads != 1 && m.sink_heads != heads_q)
+            return fail(FA_ERR_INVALID_ARGUMENT, "%s: sink_heads=%lld must be 1 or heads_q=%lld (one sink per query head)", who,
+                        (long long)m.sink_heads, (long long)heads_q);
+        if ((uintptr_t)m.sinks % 4 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: sinks must be 4-byte aligned", who);
+    } else if (m.sink_heads != 0) {
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: sink_heads must be 0 without sinks (got %lld)", who, (long long)m.sink_heads);
+    }
+    return FA_OK;
+}
+
 // the e4m3 decode call's layout and split rule (the kernels share the 32-row tile and the combine)
+size_t fa_fp4_forward_kvcache_workspace_bytes_mod(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
+                                                  int64_t d, int64_t num_splits, int causal, int64_t window_left, int64_t window_right,
+                                                  int with_sinks) {
+    return fa_fp8_forward_kvcache_workspace_bytes_mod(batch, heads_q, heads_kv, seqlen_q, cache_len, d, num_splits, causal, window_left,
+                                                      window_right, with_sinks);
+}
+
 size_t fa_fp4_forward_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t d,
                                               int64_t num_splits) {
     return fa_fp8_forward_kvcache_workspace_bytes(batch, heads_q, heads_kv, seqlen_q, cache_len, d, num_splits);
 }
 
-int fa_fp4_forward_kvcache(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o, float* lse,
+// fa_fp4_forward_kvcache (m at its defaults) and fa_fp4_forward_kvcache_mod
+static int fp4_forward_kvcache_entry(const char* who, const fa::Fp8Mod& m, const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o, float* lse,
                            const float* q_descale, const float* k_descale, const float* v_descale, const int32_t* cache_seqlens,
                            const int32_t* block_table, const int32_t* cache_batch_idx, int64_t batch, int64_t heads_q, int64_t heads_kv,
                            int64_t seqlen_q, int64_t cache_len, int64_t cache_batch, int64_t d, int dtype, int64_t q_batch_stride,
@@ -4091,7 +4118,6 @@ int fa_fp4_forward_kvcache(const void* q, const void* k_cache, const void* k_sca
                            int64_t v_scale_token_stride, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
                            int64_t q_descale_batch_stride, int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal,
                            double softmax_scale, int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "fa_fp4_forward_kvcache";
     Fp4Call k;
     k.c.k_cache = const_cast<void*>(k_cache); k.c.k_scale = const_cast<void*>(k_scale);
     k.c.v_cache = const_cast<void*>(v_cache); k.c.v_scale = const_cast<void*>(v_scale);
@@ -4127,12 +4153,14 @@ int fa_fp4_forward_kvcache(const void* q, const void* k_cache, const void* k_sca
                     (long long)(row_tiles * heads_kv));
     if (num_splits < 0 || num_splits > 256)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_splits must lie in [0, 256] (got %lld)", who, (long long)num_splits);
-    const int64_t S = fp8_kv_splits(batch, heads_q, heads_kv, seqlen_q, cache_len, num_splits);
+    if (const int rc = fp4_mod_check(who, m, heads_q)) return rc;
+    // (the featured call: the rule sees the keys a window can show, and sinks raise 1 split to 2; not any(): the parent's rule)
+    const int64_t S = fp8_kv_splits_mod(batch, heads_q, heads_kv, seqlen_q, cache_len, num_splits, causal, m);
     const size_t need = fa::kv_workspace_bytes(batch, heads_q, seqlen_q, 128, (int)S);
     if (need > 0) {
         if (!workspace || workspace_bytes < need)
-            return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes is too small (need %zu: fa_fp4_forward_kvcache_workspace_bytes)", who,
-                        workspace ? workspace_bytes : (size_t)0, need);
+            return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes is too small (need %zu: fa_fp4_forward_kvcache_workspace_bytes%s)", who,
+                        workspace ? workspace_bytes : (size_t)0, need, m.any() ? "_mod" : "");
         if ((uintptr_t)workspace % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
     }
     fa::Fp4KvArgs a;
@@ -4140,11 +4168,49 @@ int fa_fp4_forward_kvcache(const void* q, const void* k_cache, const void* k_sca
     a.qds_bs = k.qds_bs; a.kds_bs = k.kds_bs; a.vds_bs = k.vds_bs;
     a.batch = batch; a.heads_q = heads_q; a.seqlen_q = seqlen_q; a.q_bs = q_batch_stride; a.q_ts = q_token_stride;
     a.dtype = dtype; a.causal = causal != 0; a.scale = (float)softmax_scale; a.num_splits = S; a.workspace = workspace;
-    return launched(who, fa::launch_fp4_kvcache(a, reinterpret_cast<hipStream_t>(stream)));
+    return launched(who, fa::launch_fp4_kvcache_mod(a, m, reinterpret_cast<hipStream_t>(stream)));
+}
+
+int fa_fp4_forward_kvcache(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o, float* lse,
+                           const float* q_descale, const float* k_descale, const float* v_descale, const int32_t* cache_seqlens,
+                           const int32_t* block_table, const int32_t* cache_batch_idx, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                           int64_t seqlen_q, int64_t cache_len, int64_t cache_batch, int64_t d, int dtype, int64_t q_batch_stride,
+                           int64_t q_token_stride, int64_t k_batch_stride, int64_t k_token_stride, int64_t k_scale_batch_stride,
+                           int64_t k_scale_token_stride, int64_t v_batch_stride, int64_t v_token_stride, int64_t v_scale_batch_stride,
+                           int64_t v_scale_token_stride, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
+                           int64_t q_descale_batch_stride, int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal,
+                           double softmax_scale, int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream) {
+    return fp4_forward_kvcache_entry("fa_fp4_forward_kvcache", fa::Fp8Mod(), q, k_cache, k_scale, v_cache, v_scale, o, lse, q_descale, k_descale,
+           v_descale, cache_seqlens, block_table, cache_batch_idx, batch, heads_q, heads_kv, seqlen_q, cache_len, cache_batch, d, dtype,
+           q_batch_stride, q_token_stride, k_batch_stride, k_token_stride, k_scale_batch_stride, k_scale_token_stride, v_batch_stride,
+           v_token_stride, v_scale_batch_stride, v_scale_token_stride, block_table_row_stride, num_blocks, page_block_size,
+           q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale, num_splits, workspace,
+           workspace_bytes, stream);
+}
+
+int fa_fp4_forward_kvcache_mod(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o, float* lse,
+                           const float* q_descale, const float* k_descale, const float* v_descale, const int32_t* cache_seqlens,
+                           const int32_t* block_table, const int32_t* cache_batch_idx, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                           int64_t seqlen_q, int64_t cache_len, int64_t cache_batch, int64_t d, int dtype, int64_t q_batch_stride,
+                           int64_t q_token_stride, int64_t k_batch_stride, int64_t k_token_stride, int64_t k_scale_batch_stride,
+                           int64_t k_scale_token_stride, int64_t v_batch_stride, int64_t v_token_stride, int64_t v_scale_batch_stride,
+                           int64_t v_scale_token_stride, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
+                           int64_t q_descale_batch_stride, int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal,
+                           double softmax_scale, int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream,
+                           int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads) {
+    fa::Fp8Mod m;
+    m.window_left = window_left; m.window_right = window_right; m.softcap = softcap; m.sinks = sinks; m.sink_heads = sink_heads;
+    return fp4_forward_kvcache_entry("fa_fp4_forward_kvcache_mod", m, q, k_cache, k_scale, v_cache, v_scale, o, lse, q_descale, k_descale,
+           v_descale, cache_seqlens, block_table, cache_batch_idx, batch, heads_q, heads_kv, seqlen_q, cache_len, cache_batch, d, dtype,
+           q_batch_stride, q_token_stride, k_batch_stride, k_token_stride, k_scale_batch_stride, k_scale_token_stride, v_batch_stride,
+           v_token_stride, v_scale_batch_stride, v_scale_token_stride, block_table_row_stride, num_blocks, page_block_size,
+           q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale, num_splits, workspace,
+           workspace_bytes, stream);
 }
 
 // Chunked prefill over the paged MXFP4 cache: packed queries, one launch, no workspace (fa_fp4_prefill.hip)
-int fa_fp4_forward_varlen(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o, float* lse,
+// fa_fp4_forward_varlen (m at its defaults) and fa_fp4_forward_varlen_mod
+static int fp4_forward_varlen_entry(const char* who, const fa::Fp8Mod& m, const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o, float* lse,
                           const float* q_descale, const float* k_descale, const float* v_descale, const int32_t* cu_seqlens_q,
                           const int32_t* cu_seqlens_k, const int32_t* block_table, int64_t batch, int64_t heads_q, int64_t heads_kv,
                           int64_t total_q, int64_t max_seqlen_q, int64_t cache_len, int64_t d, int dtype, int64_t q_token_stride,
@@ -4152,7 +4218,6 @@ int fa_fp4_forward_varlen(const void* q, const void* k_cache, const void* k_scal
                           int64_t v_batch_stride, int64_t v_token_stride, int64_t v_scale_batch_stride, int64_t v_scale_token_stride,
                           int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t q_descale_batch_stride,
                           int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* stream) {
-    const char* who = "fa_fp4_forward_varlen";
     Fp4Call k;
     k.c.k_cache = const_cast<void*>(k_cache); k.c.k_scale = const_cast<void*>(k_scale);
     k.c.v_cache = const_cast<void*>(v_cache); k.c.v_scale = const_cast<void*>(v_scale);
@@ -4187,12 +4252,46 @@ int fa_fp4_forward_varlen(const void* q, const void* k_cache, const void* k_scal
     if (heads_kv > 65535 || (max_seqlen_q * (heads_q / heads_kv) + 127) / 128 > ((int64_t)1 << 31) - 1)
         return fail(FA_ERR_UNSUPPORTED, "%s: span limit: heads_kv = %lld (at most 65535) or the row tiles of max_seqlen_q are beyond one launch",
                     who, (long long)heads_kv);
+    if (const int rc = fp4_mod_check(who, m, heads_q)) return rc;
     fa::Fp4VarlenArgs a;
     a.c = k.c; a.q = q; a.o = o; a.lse = lse; a.q_descale = q_descale; a.k_descale = k_descale; a.v_descale = v_descale;
     a.qds_bs = k.qds_bs; a.kds_bs = k.kds_bs; a.vds_bs = k.vds_bs; a.cu_seqlens_q = cu_seqlens_q; a.cu_seqlens_k = cu_seqlens_k;
     a.batch = batch; a.heads_q = heads_q; a.total_q = total_q; a.max_seqlen_q = max_seqlen_q; a.q_ts = q_token_stride;
     a.dtype = dtype; a.causal = causal != 0; a.scale = (float)softmax_scale;
-    return launched(who, fa::launch_fp4_prefill(a, reinterpret_cast<hipStream_t>(stream)));
+    return launched(who, fa::launch_fp4_prefill_mod(a, m, reinterpret_cast<hipStream_t>(stream)));
+}
+
+int fa_fp4_forward_varlen(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o, float* lse,
+                          const float* q_descale, const float* k_descale, const float* v_descale, const int32_t* cu_seqlens_q,
+                          const int32_t* cu_seqlens_k, const int32_t* block_table, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                          int64_t total_q, int64_t max_seqlen_q, int64_t cache_len, int64_t d, int dtype, int64_t q_token_stride,
+                          int64_t k_batch_stride, int64_t k_token_stride, int64_t k_scale_batch_stride, int64_t k_scale_token_stride,
+                          int64_t v_batch_stride, int64_t v_token_stride, int64_t v_scale_batch_stride, int64_t v_scale_token_stride,
+                          int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t q_descale_batch_stride,
+                          int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* stream) {
+    return fp4_forward_varlen_entry("fa_fp4_forward_varlen", fa::Fp8Mod(), q, k_cache, k_scale, v_cache, v_scale, o, lse, q_descale, k_descale,
+           v_descale, cu_seqlens_q, cu_seqlens_k, block_table, batch, heads_q, heads_kv, total_q, max_seqlen_q, cache_len, d, dtype,
+           q_token_stride, k_batch_stride, k_token_stride, k_scale_batch_stride, k_scale_token_stride, v_batch_stride, v_token_stride,
+           v_scale_batch_stride, v_scale_token_stride, block_table_row_stride, num_blocks, page_block_size, q_descale_batch_stride,
+           k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale, stream);
+}
+
+int fa_fp4_forward_varlen_mod(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o, float* lse,
+                          const float* q_descale, const float* k_descale, const float* v_descale, const int32_t* cu_seqlens_q,
+                          const int32_t* cu_seqlens_k, const int32_t* block_table, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                          int64_t total_q, int64_t max_seqlen_q, int64_t cache_len, int64_t d, int dtype, int64_t q_token_stride,
+                          int64_t k_batch_stride, int64_t k_token_stride, int64_t k_scale_batch_stride, int64_t k_scale_token_stride,
+                          int64_t v_batch_stride, int64_t v_token_stride, int64_t v_scale_batch_stride, int64_t v_scale_token_stride,
+                          int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t q_descale_batch_stride,
+                          int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* stream,
+                          int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads) {
+    fa::Fp8Mod m;
+    m.window_left = window_left; m.window_right = window_right; m.softcap = softcap; m.sinks = sinks; m.sink_heads = sink_heads;
+    return fp4_forward_varlen_entry("fa_fp4_forward_varlen_mod", m, q, k_cache, k_scale, v_cache, v_scale, o, lse, q_descale, k_descale,
+           v_descale, cu_seqlens_q, cu_seqlens_k, block_table, batch, heads_q, heads_kv, total_q, max_seqlen_q, cache_len, d, dtype,
+           q_token_stride, k_batch_stride, k_token_stride, k_scale_batch_stride, k_scale_token_stride, v_batch_stride, v_token_stride,
+           v_scale_batch_stride, v_scale_token_stride, block_table_row_stride, num_blocks, page_block_size, q_descale_batch_stride,
+           k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale, stream);
 }
 
 int fa_debug_trace_buffer(void* device_ptr) {

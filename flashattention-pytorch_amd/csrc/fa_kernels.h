@@ -45,7 +45,8 @@ enum KernelId { K_FWD_F32 = 0, K_BWD_DELTA, K_BWD_DKDV_F32, K_BWD_DQ_F32, K_FWD_
                 K_FP8_QUANT, K_FWD_FP8, K_EX_FWD, K_EX_BWD, K_KV_GROUP_SUM, K_FP8IN_VT, K_FP8IN_FWD, K_FP8IN_VT_VARLEN,
                 K_FP8IN_FWD_VARLEN, K_IDX_PACK, K_IDX_LOGITS, K_IDX_TOPK, K_FP8KV_SPLIT, K_FP8Q_AMAX, K_FP8Q_QUANT, K_FP8Q_FUSED,
                 K_FP8IN_FWD_MOD, K_FP8IN_FWD_VARLEN_MOD, K_FP8KV_SPLIT_MOD, K_FP8KV_STEP_PREP, K_FP8IN_FWD_HDIM,
-                K_FP8IN_FWD_VARLEN_HDIM, K_FP8KV_SPLIT_HDIM, K_FP8KV_SPLIT_VARLEN, K_FP8KV_STEP_PREP_VARLEN, K_FP4KV_APPEND, K_FP4KV_SPLIT, K_FP4KV_PREFILL, K_COUNT };
+                K_FP8IN_FWD_VARLEN_HDIM, K_FP8KV_SPLIT_HDIM, K_FP8KV_SPLIT_VARLEN, K_FP8KV_STEP_PREP_VARLEN, K_FP4KV_APPEND, K_FP4KV_SPLIT, K_FP4KV_PREFILL,
+                K_FP4KV_SPLIT_MOD, K_FP4KV_PREFILL_MOD, K_COUNT };
 void prof_begin(int id, hipStream_t st);
 void prof_end(int id, hipStream_t st);
 struct ProfScope {
@@ -74,11 +75,12 @@ int set_option(const char* name, int value);   // returns 0, or -1 for an unknow
 // "fp8kv_split_varlen": the packed-query split kernel of fa_fp8_forward_kvcache_varlen / fa_fp8_kvcache_step_varlen;
 // "fp8kv_step_prep_varlen": the prep launch of fa_fp8_kvcache_step_varlen with packed tokens or at head dim 64 / 256;
 // "fp4kv_append", "fp4kv_split": the two kernels of the MXFP4 KV cache (fa_fp4_decode.hip);
-// "fp4kv_prefill": the packed-query prefill kernel over the paged MXFP4 cache (fa_fp4_prefill.hip).
+// "fp4kv_prefill": the packed-query prefill kernel over the paged MXFP4 cache (fa_fp4_prefill.hip);
+// "fp4kv_split_mod", "fp4kv_prefill_mod": the featured kernels of the two MXFP4 cache readers (window, softcap, sinks).
 enum RouteId { ROUTE_DKDV_STREAM = 0, ROUTE_DKDV_LEAN, ROUTE_FP8Q_FUSED, ROUTE_FP8Q_TWO_PASS, ROUTE_FP8Q_STATIC, ROUTE_FP8IN_FWD_MOD,
                ROUTE_FP8IN_FWD_VARLEN_MOD, ROUTE_FP8KV_SPLIT_MOD, ROUTE_FP8KV_STEP_PREP, ROUTE_FP8IN_FWD_HDIM,
                ROUTE_FP8IN_FWD_VARLEN_HDIM, ROUTE_FP8KV_SPLIT_HDIM, ROUTE_FP8KV_SPLIT_VARLEN, ROUTE_FP8KV_STEP_PREP_VARLEN, ROUTE_FP4KV_APPEND,
-               ROUTE_FP4KV_SPLIT, ROUTE_FP4KV_PREFILL, ROUTE_COUNT };
+               ROUTE_FP4KV_SPLIT, ROUTE_FP4KV_PREFILL, ROUTE_FP4KV_SPLIT_MOD, ROUTE_FP4KV_PREFILL_MOD, ROUTE_COUNT };
 void route_hit(int id);
 
 // exact-f32 kernels (fa_generic.hip): any dtype, d <= 256
@@ -615,6 +617,10 @@ struct Fp4KvArgs {
     void* workspace = nullptr;                              // kv_workspace_bytes(batch, heads_q, seqlen_q, 128, num_splits)
 };
 hipError_t launch_fp4_kvcache(const Fp4KvArgs& a, hipStream_t st);
+// The featured call (fa_fp4_forward_kvcache_mod): Fp8Mod's window, softcap and sinks over the MXFP4 cache.  A
+// call whose Fp8Mod is not any() is launch_fp4_kvcache; any other runs fp4kv_split_mod_kernel, and with sinks num_splits >= 2 (the
+// sink joins in launch_kv_combine_sink).  fp8kv_split_len is the length the split rule takes.
+hipError_t launch_fp4_kvcache_mod(const Fp4KvArgs& a, const Fp8Mod& m, hipStream_t st);
 // Chunked prefill over the paged cache (fa_fp4_prefill.hip; fa_fp4_forward_varlen): packed e4m3 queries, one launch, no workspace.
 // c.block_table is non-null, c.cache_len = max_blocks_per_seq * page_size, c.cache_seqlens and c.cache_batch_idx are null.
 struct Fp4VarlenArgs {
@@ -630,5 +636,8 @@ struct Fp4VarlenArgs {
     float scale = 0.f;
 };
 hipError_t launch_fp4_prefill(const Fp4VarlenArgs& a, hipStream_t st);
+// The featured call (fa_fp4_forward_varlen_mod): not any() is launch_fp4_prefill; any other runs fp4kv_prefill_mod_kernel, which walks
+// the key tiles of each workgroup's band alone and takes the sink in its epilogue (no workspace).
+hipError_t launch_fp4_prefill_mod(const Fp4VarlenArgs& a, const Fp8Mod& m, hipStream_t st);
 
 }  // namespace fa

@@ -67,6 +67,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_fp8_forward_kvcache_varlen", "fa_fp8_forward_kvcache_varlen_workspace_bytes",
     "fa_fp8_kvcache_step_varlen", "fa_fp8_kvcache_step_varlen_workspace_bytes",
     "fa_fp4_kvcache_append", "fa_fp4_forward_kvcache", "fa_fp4_forward_kvcache_workspace_bytes", "fa_fp4_forward_varlen",
+    "fa_fp4_forward_kvcache_mod", "fa_fp4_forward_kvcache_workspace_bytes_mod", "fa_fp4_forward_varlen_mod",
 )
 
 
@@ -280,6 +281,10 @@ _sig("fa_fp4_forward_varlen", _fields(
     "p:q,k_cache,k_scale,v_cache,v_scale,o,lse,q_descale,k_descale,v_descale,cu_seqlens_q,cu_seqlens_k,block_table "
     "i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,d c:dtype i:q_token_stride") + _FP4STRIDES +
     _fields("i:q_descale_batch_stride,k_descale_batch_stride,v_descale_batch_stride c:causal d:softmax_scale") + _STREAM)
+# a window, a softcap and sinks on the two MXFP4 cache readers: the parent's arguments, then the fp8 calls' group
+for _name in ("fa_fp4_forward_kvcache", "fa_fp4_forward_varlen"):
+    _sig(_name + "_mod", _SIGNATURES[_name][1] + _FP8MOD)
+_sig("fa_fp4_forward_kvcache_workspace_bytes_mod", _SIGNATURES["fa_fp8_forward_kvcache_workspace_bytes_mod"][1], _SIZE)
 _KVWSV = _fields("i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,d,num_splits c:with_sinks")
 _sig("fa_ex_kvcache_workspace_bytes_varlen", _KVWSV, _SIZE)
 _sig("fa_ex_kvcache_workspace_bytes_qv", _KVWSV + _fields("i:d_v"), _SIZE)
@@ -352,6 +357,8 @@ _family("fa_fp8_kvcache_step_varlen", [])
 _family("fa_fp4_kvcache_append", [])
 _family("fa_fp4_forward_kvcache", [])
 _family("fa_fp4_forward_varlen", [])
+for _name in ("fa_fp4_forward_kvcache_mod", "fa_fp4_forward_varlen_mod"):
+    _family(_name, [])
 _family("fa_ex_forward_kvcache_qv", ["fa_ex_forward_kvcache" + _suffix for _suffix in ("", "_paged", "_rotary", "_fp8", "_sink", "_varlen")])
 
 
@@ -3130,12 +3137,15 @@ def fp4_kvcache_append(k_new, v_new, k_cache, k_scale, v_cache, v_scale, cache_s
 
 
 def fp4_kvcache_forward(q, k_cache, k_scale, v_cache, v_scale, cache_seqlens=None, block_table=None, cache_batch_idx=None, q_descale=None,
-                        k_descale=None, v_descale=None, softmax_scale=None, causal=False, num_splits=0, out_dtype=torch.bfloat16, out=None):
+                        k_descale=None, v_descale=None, softmax_scale=None, causal=False, num_splits=0, out_dtype=torch.bfloat16, out=None,
+                        *, window=(-1, -1), softcap=0.0, sinks=None):
     """(o, lse) of decoding over an MXFP4 KV cache (fa_fp4_forward_kvcache): q (B, Nq, H_q, 128) torch.float8_e4m3fn at its own batch
     and token strides over the cache fp4_kvcache_append fills (its docstring has the four arrays); cache_seqlens int32 (B,) on the
     device, an int, or None (full); descales float32 (B, H_kv) or (H_kv,), None = 1.  o (B, Nq, H_q, 128) in out_dtype, lse float32
     (B, H_q, Nq).  Nothing is copied or read on the host; the partials live in the shim's persistent workspace.  out: an (o, lse) pair
-    of contiguous tensors of those shapes and dtypes to write into (16- and 4-byte aligned), instead of fresh ones."""
+    of contiguous tensors of those shapes and dtypes to write into (16- and 4-byte aligned), instead of fresh ones.  window (left,
+    right; -1 = unbounded), softcap (0 = off) and sinks (float32 (H_q,) on q's device) are fa_fp4_forward_kvcache_mod's; a call with
+    none of them goes through fa_fp4_forward_kvcache."""
     who = "fp4_kvcache_forward"
     if not isinstance(q, torch.Tensor) or q.dtype != torch.float8_e4m3fn:
         dt = q.dtype if isinstance(q, torch.Tensor) else type(q).__name__
@@ -3164,6 +3174,7 @@ def fp4_kvcache_forward(q, k_cache, k_scale, v_cache, v_scale, cache_seqlens=Non
     qdp, qds, keep_q = _kv_descale(who, "q_descale", q_descale, q, b, hkv)
     kdp, kds, keep_k = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
     vdp, vds, keep_v = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
+    mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks)
     with torch.cuda.device(q.device):
         if out is not None:
             o, lse = out
@@ -3175,26 +3186,33 @@ def fp4_kvcache_forward(q, k_cache, k_scale, v_cache, v_scale, cache_seqlens=Non
             lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)
         if b == 0 or nq == 0:
             return o, lse
-        need = int(_lib.fa_fp4_forward_kvcache_workspace_bytes(b, hq, hkv, nq, cap, 128, ns))
+        if mod:
+            need = int(_lib.fa_fp4_forward_kvcache_workspace_bytes_mod(b, hq, hkv, nq, cap, 128, ns, int(bool(causal)), tail[0], tail[1],
+                                                                       int(sinks is not None)))
+        else:
+            need = int(_lib.fa_fp4_forward_kvcache_workspace_bytes(b, hq, hkv, nq, cap, 128, ns))
         ws = _workspace(q.device, need)
-        _call("fa_fp4_forward_kvcache", (
+        _call("fa_fp4_forward_kvcache" + mod, (
             q.data_ptr(), *(t.data_ptr() for t in arrays), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp, _ptr(cache_seqlens),
             _ptr(block_table), _ptr(cache_batch_idx), b, hq, hkv, nq, cap, cbatch, 128, _DTYPE_CODE[out_dtype],
             q.stride(0) if b > 1 else 0, q.stride(1) if nq > 1 else hq * 128, *strides, *pages, qds, kds, vds, int(bool(causal)), scale, ns,
-            ws.data_ptr() if need else 0, ws.numel() if need else 0, _stream_ptr(q.device)))
-    del keep_q, keep_k, keep_v
+            ws.data_ptr() if need else 0, ws.numel() if need else 0, _stream_ptr(q.device), *tail))
+    del keep_q, keep_k, keep_v, keep_s
     return o, lse
 
 
 def fp4_varlen_forward(q, k_cache, k_scale, v_cache, v_scale, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, block_table,
-                       q_descale=None, k_descale=None, v_descale=None, softmax_scale=None, causal=False, out_dtype=torch.bfloat16, out=None):
+                       q_descale=None, k_descale=None, v_descale=None, softmax_scale=None, causal=False, out_dtype=torch.bfloat16, out=None,
+                       *, window=(-1, -1), softcap=0.0, sinks=None):
     """(o, lse) of chunked prefill over the paged MXFP4 KV cache (fa_fp4_forward_varlen): q (total_q, H_q, 128)
     torch.float8_e4m3fn at its own token stride (a view such as qkv8[:, 0] is used in place) over the pools fp4_kvcache_append fills
     (its docstring has the four arrays) under block_table int32 (B, max_blocks); cu_seqlens_q / cu_seqlens_k int32 (B + 1,) on the
     device, clamped there (nq_b to max_seqlen_q and the tokens left in q, nk_b to max_blocks * ps) and never read on the host;
     max_seqlen_k is checked and otherwise unused.  Per sequence, causal on its own bottom-right diagonal.  Descales float32 (B, H_kv)
     or (H_kv,), None = 1.  o (total_q, H_q, 128) in out_dtype, lse float32 (H_q, total_q); rows of no sequence keep their contents
-    (a fresh output is uninitialised there).  One launch, no workspace.  out: an (o, lse) pair of contiguous tensors to write into."""
+    (a fresh output is uninitialised there).  One launch, no workspace.  out: an (o, lse) pair of contiguous tensors to write into.
+    window, softcap and sinks (float32 (H_q,)) are fa_fp4_forward_varlen_mod's; a call with none of them goes through
+    fa_fp4_forward_varlen."""
     who = "fp4_varlen_forward"
     if not isinstance(q, torch.Tensor) or q.dtype != torch.float8_e4m3fn:
         dt = q.dtype if isinstance(q, torch.Tensor) else type(q).__name__
@@ -3230,6 +3248,7 @@ def fp4_varlen_forward(q, k_cache, k_scale, v_cache, v_scale, cu_seqlens_q, cu_s
     kdp, kds, keep_k = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
     vdp, vds, keep_v = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
     cu_seqlens_q, cu_seqlens_k = cu_seqlens_q.contiguous(), cu_seqlens_k.contiguous()
+    mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks)
     with torch.cuda.device(q.device):
         if out is not None:
             o, lse = out
@@ -3242,9 +3261,10 @@ def fp4_varlen_forward(q, k_cache, k_scale, v_cache, v_scale, cu_seqlens_q, cu_s
         max_q = min(max_q, total_q)
         if b == 0 or total_q == 0 or max_q == 0:
             return o, lse
-        _call("fa_fp4_forward_varlen", (
+        _call("fa_fp4_forward_varlen" + mod, (
             q.data_ptr(), *(t.data_ptr() for t in arrays), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp, cu_seqlens_q.data_ptr(),
             cu_seqlens_k.data_ptr(), block_table.data_ptr(), b, hq, hkv, total_q, max_q, cap, 128, _DTYPE_CODE[out_dtype],
-            q.stride(0) if total_q > 1 else hq * 128, *strides, *pages, qds, kds, vds, int(bool(causal)), scale, _stream_ptr(q.device)))
-    del keep_q, keep_k, keep_v
+            q.stride(0) if total_q > 1 else hq * 128, *strides, *pages, qds, kds, vds, int(bool(causal)), scale, _stream_ptr(q.device),
+            *tail))
+    del keep_q, keep_k, keep_v, keep_s
     return o, lse

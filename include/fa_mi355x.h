@@ -1640,6 +1640,50 @@ int fa_fp4_forward_varlen(const void* q, const void* k_cache, const void* k_scal
                           int64_t v_scale_batch_stride, int64_t v_scale_token_stride, int64_t block_table_row_stride,
                           int64_t num_blocks, int64_t page_block_size, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
                           int64_t v_descale_batch_stride, int causal, double softmax_scale, void* stream);
+/* --- A sliding window, a softcap and attention sinks on the two MXFP4 cache readers: each call is its parent's
+ * argument list followed by (window_left, window_right, softcap, sinks, sink_heads), with fa_fp8_forward_kvcache_mod's semantics at
+ * d = 128, forward only.  With -1, -1, 0.0, NULL, 0 each is its parent call, launch for launch.
+ *     window   key j is visible to query token i of a sequence iff i + (nk - nq) - window_left <= j <= i + (nk - nq) + window_right
+ *              (bottom-right aligned per sequence; -1 = unbounded; causal sets the right bound to 0)
+ *     softcap  s' = softcap * tanh(s / softcap) on the scaled score s = softmax_scale * q_descale * k_descale * (q8 . k4 2^ek), before
+ *              the mask (0 = off); in the kernels' exponent t = softcap log2(e) tanh(s / softcap) + ev
+ *     sinks    float32 device logits in natural-log units, sinks[h % sink_heads] for query head h (sink_heads 1 or heads_q): one more
+ *              softmax column with a zero value, never capped or masked.  lse contains it; a row without a visible key gives o = 0,
+ *              lse = sink; a head at -inf gives the bits of the call without sinks; +-1e4 stays finite.
+ * A masked key's V exponent never reaches the joint maximum.  fa_fp4_forward_kvcache_mod runs fp4kv_split_mod_kernel: a wave's keys
+ * are [lo, hi), lo the first 64-key tile one of its 32 rows sees and hi its last visible key + 1, the splits cut that range, and
+ * nothing outside it is loaded (no code, scale or table entry).  The split rule counts the keys a window can show
+ * (fa_fp4_forward_kvcache_workspace_bytes_mod, which is fa_fp8_forward_kvcache_workspace_bytes_mod); with sinks the call runs at
+ * least 2 splits, the sink joins in the combine.  fa_fp4_forward_varlen_mod runs fp4kv_prefill_mod_kernel: a workgroup walks the key
+ * tiles of its 128 rows' band alone, the sink joins in its epilogue, no workspace.  Trust rules and graph replay are the parents';
+ * the sink values are read on the device only.
+ * Checks: the parent's, in its order, up to num_splits (decode) or the span limits (prefill); then window bounds >= -1, softcap finite
+ * and >= 0, sink_heads 1 or heads_q with sinks and 0 without, sinks 4-byte aligned; then (decode) the workspace. */
+int fa_fp4_forward_kvcache_mod(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o,
+                               float* lse, const float* q_descale, const float* k_descale, const float* v_descale,
+                               const int32_t* cache_seqlens, const int32_t* block_table, const int32_t* cache_batch_idx, int64_t batch,
+                               int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t cache_batch, int64_t d,
+                               int dtype, int64_t q_batch_stride, int64_t q_token_stride, int64_t k_batch_stride, int64_t k_token_stride,
+                               int64_t k_scale_batch_stride, int64_t k_scale_token_stride, int64_t v_batch_stride,
+                               int64_t v_token_stride, int64_t v_scale_batch_stride, int64_t v_scale_token_stride,
+                               int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
+                               int64_t q_descale_batch_stride, int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal,
+                               double softmax_scale, int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream,
+                               int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads);
+size_t fa_fp4_forward_kvcache_workspace_bytes_mod(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
+                                                  int64_t d, int64_t num_splits, int causal, int64_t window_left, int64_t window_right,
+                                                  int with_sinks);
+int fa_fp4_forward_varlen_mod(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o,
+                              float* lse, const float* q_descale, const float* k_descale, const float* v_descale,
+                              const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, const int32_t* block_table, int64_t batch,
+                              int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t max_seqlen_q, int64_t cache_len, int64_t d,
+                              int dtype, int64_t q_token_stride, int64_t k_batch_stride, int64_t k_token_stride,
+                              int64_t k_scale_batch_stride, int64_t k_scale_token_stride, int64_t v_batch_stride, int64_t v_token_stride,
+                              int64_t v_scale_batch_stride, int64_t v_scale_token_stride, int64_t block_table_row_stride,
+                              int64_t num_blocks, int64_t page_block_size, int64_t q_descale_batch_stride,
+                              int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale,
+                              void* stream, int64_t window_left, int64_t window_right, double softcap, const float* sinks,
+                              int64_t sink_heads);
 
 const char* fa_last_error(void);
 const char* fa_version(void);
@@ -1666,7 +1710,9 @@ int fa_profile_report(char* buf, size_t cap);
  * "fp8kv_step_prep_varlen": the prep launch of fa_fp8_kvcache_step_varlen with packed tokens or at head dim 64 / 256; one count a
  * call that launched one (null packed groups count what the parent calls count).  "fp4kv_append", "fp4kv_split": the kernels of
  * fa_fp4_kvcache_append and fa_fp4_forward_kvcache, one count a call that launched.  "fp4kv_prefill": the kernel of
- * fa_fp4_forward_varlen, one count a call that launched. */
+ * fa_fp4_forward_varlen, one count a call that launched.  "fp4kv_split_mod", "fp4kv_prefill_mod": the featured kernels of
+ * fa_fp4_forward_kvcache_mod and fa_fp4_forward_varlen_mod, one count a call that launched one (a _mod call with default trailing
+ * arguments counts its parent's route and not these). */
 int64_t fa_route_count(const char* name);
 
 #ifdef __cplusplus

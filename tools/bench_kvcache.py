@@ -87,7 +87,13 @@ the q quantise).
 `--fp4-prefill`: one causal prefill chunk at the end of a paged MXFP4 cache (ps 16, shuffled; H 32:8; chunks of 512 and 2048 tokens,
 8192 and 32768 keys, B 1 and 8), interleaved rounds of three calls on the same tokens: fp4_varlen_forward,
 the decode call fp4_kvcache_forward with Nq = chunk (the only way to serve the shape before), and fp8_varlen_forward(block_table=) on
-the pool widened exactly to e4m3; per row the three medians, their spreads ((max - min) / median) and the two ratios."""
+the pool widened exactly to e4m3; per row the three medians, their spreads ((max - min) / median) and the two ratios.
+`--fp4-mod`: a sliding window, a softcap and sinks over the MXFP4 cache, H 32:8, interleaved rounds, medians
+with spreads.  `fp4_mod_decode`: Nq 1, 32768 cached keys, B 8 and 64, causal windows of 128 and 4096 keys: the windowed call, the
+parent call on a cache cut to the window's keys (the work a windowed call should do) and the e4m3 decode call with the same window.
+`fp4_mod_prefill`: a 2048-token chunk at the end of 32768 keys (paged, ps 16, B 8), windows 1024 and 4096: the windowed call, the
+parent call without a window and fp8_varlen_forward(block_table=, window=); the tile count of the walk over the unwindowed one.
+`fp4_mod_alone`: softcap 30 alone and sinks alone on the unwindowed B 64 decode row and the B 8 prefill row against the parent."""
 import argparse
 import json
 import os
@@ -624,6 +630,94 @@ def fp4_prefill_rows(args, dtype):
     return rows
 
 
+def fp4_mod_rows(args, dtype):
+    """--fp4-mod: see the module docstring"""
+    dev, rounds, hq, hkv, ps, L, n = "cuda", max(args.rounds, 5), 32, 8, 16, 32768, 2048
+    mags = torch.tensor([0, .5, 1, 1.5, 2, 3, 4, 6, -0., -.5, -1, -1.5, -2, -3, -4, -6], dtype=torch.float32, device=dev)
+    rows = []
+
+    def widen(c4, sc, out, step):   # the same values in e4m3 (exact), `step` leading entries at a time
+        for lo in range(0, c4.shape[0], step):
+            x = mags[torch.stack((c4[lo:lo + step] & 15, c4[lo:lo + step] >> 4), -1).flatten(-2).long()]
+            e = torch.exp2(sc[lo:lo + step].float() - 127.0).reshape(*x.shape[:3], -1)
+            out[lo:lo + step] = (x * e.repeat_interleave(128 // e.shape[-1], -1)).to(torch.float8_e4m3fn)
+
+    def race(calls):                # {name: call} -> {name: (median us, spread)} over interleaved rounds
+        t = {k: [] for k in calls}
+        for _ in range(rounds):
+            for k, fn in calls.items():
+                t[k].append(timed(fn, args.warmup, args.iters, 1))
+        return {k: (statistics.median(v), round((max(v) - min(v)) / statistics.median(v), 3)) for k, v in t.items()}
+
+    def row(kind, res, base, **more):
+        out = dict(kind=kind, **more)
+        for k, (m, sp) in res.items():
+            out[k + "_us"], out[k + "_spread"] = round(m, 1), sp
+        for k in res:
+            if k != base:
+                out[f"{base}_over_{k}"] = round(res[base][0] / res[k][0], 3)
+        rows.append(out)
+        print(json.dumps(out), flush=True)
+
+    for b in (8, 64):               # ---- decode, contiguous
+        kc, vc = (torch.randint(0, 256, (b, L, hkv, 64), device=dev, dtype=torch.uint8) for _ in range(2))
+        ks = torch.randint(124, 131, (b, L, hkv, 4), device=dev, dtype=torch.uint8)
+        vs = torch.randint(124, 131, (b, L, hkv), device=dev, dtype=torch.uint8)
+        k8, v8 = (torch.empty((b, L, hkv, 128), device=dev, dtype=torch.float8_e4m3fn) for _ in range(2))
+        widen(kc, ks, k8, 1), widen(vc, vs, v8, 1)
+        q8 = (torch.randn((b, 1, hq, 128), device=dev) * 0.25).to(torch.float8_e4m3fn)
+        qd, kd, vd = (torch.full((b, hkv), x, dtype=torch.float32, device=dev) for x in (0.25, 0.0625, 0.5))
+        sl = torch.full((b,), L, dtype=torch.int32, device=dev)
+        sinks = torch.randn(hq, device=dev)
+        for w in (128, 4096):
+            cut = (w + 1 + 63) // 64 * 64                         # a cache that holds the window's w + 1 keys alone (whole tiles of capacity)
+            cl = torch.full((b,), w + 1, dtype=torch.int32, device=dev)
+            calls = dict(
+                win=lambda: ext.fp4_kvcache_forward(q8, kc, ks, vc, vs, sl, None, None, qd, kd, vd, None, True, 0, dtype, window=(w, -1)),
+                cut=lambda: ext.fp4_kvcache_forward(q8, kc[:, L - cut:], ks[:, L - cut:], vc[:, L - cut:], vs[:, L - cut:], cl, None, None, qd, kd,
+                                                    vd, None, True, 0, dtype),
+                e4m3=lambda: ext.fp8_kvcache_forward(q8, k8, v8, sl, None, None, qd, kd, vd, None, True, 0, dtype, window=(w, -1)))
+            # (both kernels round P to e4m3, 2^-4 a key, and a short window averages few keys: two such roundings of the largest |o|)
+            ref = calls["e4m3"]()[0].float()
+            torch.testing.assert_close(calls["win"]()[0].float(), ref, rtol=0.0, atol=0.125 * float(ref.abs().max()))
+            row("fp4_mod_decode", race(calls), "win", b=b, L=L, window=w)
+        if b == 64:
+            calls = dict(parent=lambda: ext.fp4_kvcache_forward(q8, kc, ks, vc, vs, sl, None, None, qd, kd, vd, None, True, 0, dtype),
+                         softcap=lambda: ext.fp4_kvcache_forward(q8, kc, ks, vc, vs, sl, None, None, qd, kd, vd, None, True, 0, dtype, softcap=30.0),
+                         sinks=lambda: ext.fp4_kvcache_forward(q8, kc, ks, vc, vs, sl, None, None, qd, kd, vd, None, True, 0, dtype, sinks=sinks))
+            for k in ("softcap", "sinks"):
+                row("fp4_mod_alone", race(dict(parent=calls["parent"], **{k: calls[k]})), k, call="decode", b=b, L=L)
+        del kc, vc, ks, vs, k8, v8
+        torch.cuda.empty_cache()
+
+    b = 8                           # ---- prefill, paged
+    nblk = b * L // ps
+    kc, vc = (torch.randint(0, 256, (nblk, ps, hkv, 64), device=dev, dtype=torch.uint8) for _ in range(2))
+    ks = torch.randint(124, 131, (nblk, ps, hkv, 4), device=dev, dtype=torch.uint8)
+    vs = torch.randint(124, 131, (nblk, ps, hkv), device=dev, dtype=torch.uint8)
+    k8, v8 = (torch.empty((nblk, ps, hkv, 128), device=dev, dtype=torch.float8_e4m3fn) for _ in range(2))
+    widen(kc, ks, k8, 4096), widen(vc, vs, v8, 4096)
+    table = torch.randperm(nblk, device=dev).view(b, L // ps).to(torch.int32)
+    qd, kd, vd = (torch.full((b, hkv), x, dtype=torch.float32, device=dev) for x in (0.25, 0.0625, 0.5))
+    qp = (torch.randn((b * n, hq, 128), device=dev) * 0.25).to(torch.float8_e4m3fn)
+    cu_q = torch.arange(b + 1, dtype=torch.int32, device=dev) * n
+    cu_k = torch.arange(b + 1, dtype=torch.int32, device=dev) * L
+    sinks = torch.randn(hq, device=dev)
+    new = lambda **kw: ext.fp4_varlen_forward(qp, kc, ks, vc, vs, cu_q, cu_k, n, L, table, qd, kd, vd, None, True, dtype, **kw)   # noqa: E731
+    for w in (1024, 4096):
+        calls = dict(win=lambda: new(window=(w, -1)), parent=lambda: new(),
+                     e4m3=lambda: ext.fp8_varlen_forward(qp, k8, v8, cu_q, cu_k, n, L, True, None, qd, kd, vd, dtype, table, window=(w, -1)))
+        ref = calls["e4m3"]()[0].float()
+        torch.testing.assert_close(calls["win"]()[0].float(), ref, rtol=0.0, atol=0.125 * float(ref.abs().max()))
+        # the tiles a workgroup of 128 / G tokens walks, summed over the chunk's workgroups, over the unwindowed walk's
+        tok = 128 // (hq // hkv)
+        tiles = lambda left: sum((L - n + t0 + tok + 63) // 64 - max(0, L - n + t0 - left) // 64 for t0 in range(0, n, tok))   # noqa: E731
+        row("fp4_mod_prefill", race(calls), "win", b=b, L=L, chunk=n, window=w, tile_share=round(tiles(w) / tiles(1 << 30), 4))
+    for k, kw in (("softcap", dict(softcap=30.0)), ("sinks", dict(sinks=sinks))):
+        row("fp4_mod_alone", race(dict(parent=lambda: new(), **{k: lambda: new(**kw)})), k, call="prefill", b=b, L=L, chunk=n)
+    return rows
+
+
 def fp4_rows(args, dtype):
     """--fp4: see the module docstring"""
     dev, rounds, hq, hkv = "cuda", max(args.rounds, 5), 32, 8
@@ -929,6 +1023,7 @@ def main():
     ap.add_argument("--fp8-varlen", action="store_true", help="time the packed fp8 decode call and step, and the step at d 64 / 256: see the module docstring")
     ap.add_argument("--fp4", action="store_true", help="time decoding over the MXFP4 cache against the e4m3 decode call, and the append: see the module docstring")
     ap.add_argument("--fp4-prefill", action="store_true", help="time chunked prefill over the MXFP4 cache against the decode call and the e4m3 packed call: see the module docstring")
+    ap.add_argument("--fp4-mod", action="store_true", help="time a window, a softcap and sinks over the MXFP4 cache against the parent calls and the e4m3 calls: see the module docstring")
     ap.add_argument("--md", default=None, help="--fp8-step: write the table as markdown to this path")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
@@ -944,6 +1039,12 @@ def main():
         ext.ex_kvcache_forward(wq, wk, wk, None, None, wl, True, None)
     torch.cuda.synchronize()
     del wq, wk
+    if args.fp4_mod:
+        rows = fp4_mod_rows(args, dtype)
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(dict(fp4_mod=True, dtype=args.dtype, version=ext.version(), rows=rows), f, indent=1)
+        return
     if args.fp4_prefill:
         rows = fp4_prefill_rows(args, dtype)
         if args.json:
