@@ -12,8 +12,9 @@
 //                                   6 * 2^e >= amax over the block (32 channels for K, 128 for V: a maximum over the four lanes of
 //                                   a head), clamped to [-64, 64], 0 for amax = 0, read off amax's exponent and mantissa; the code
 //                                   is x' * 2^-e (exact) rounded to e2m1, nearest, ties to the even code, by seven compares.
-//   fp4kv_split_kernel<Tag, PAGED>  fp8kv_split_kernel's mapping (fa_fp8_decode.hip): one wave per (split, 32-row tile x K/V head,
-//                                   sequence), row = token * G + head in the group, 64-key tiles, every cache byte read once.
+//   fp4kv_split_kernel<Tag, PAGED, Mod...>  fp8kv_split_kernel's mapping (fa_fp8_decode.hip): one wave per (split, 32-row tile x
+//                                   K/V head, sequence), row = token * G + head in the group, 64-key tiles, every cache byte read
+//                                   once.  Mod...: nothing, or (KvqMod) for the featured call below.
 //   kv_combine_kernel<Tag, false>   fa_decode.hip's combine, unchanged, for S > 1 (kv_workspace_bytes' layout).
 //
 // One 64-key tile of a wave, lane l = (r = l & 31, h = l >> 5):
@@ -52,21 +53,17 @@
 // codes read as zero, scale bytes as 127, the score is masked by a select.  A scale byte is only ever an operand of arithmetic
 // (0xFF is a NaN to the instruction and ev = 128 to the softmax): it can make a key's share any number, never an address.
 // A tile whole below the split's end on pages inside the pool takes the wave-uniform path without the selects, as in the e4m3 kernel.
-#include <algorithm>
-
-#include "fa_common.h"
-#include "fa_ex_common.h"
-#include "fa_kernels.h"
+//
+// fa_fp4_forward_kvcache_mod (a sliding window, a softcap, attention sinks) launches the featured
+// instantiation fp4kv_split_kernel<Tag, PAGED, KvqMod>: the same text with one more kernel argument (fa_kvq_common.h) and the three
+// features as wave-uniform run-time switches, noted at the sites they change.  The bounds live in SGPRs (md is a kernel argument);
+// a lane's lower bound is recomputed from its token where it is needed.  Sinks are not this kernel's: they join in
+// kv_combine_kernel<Tag, true>, once per row.
+#include "fa_kvq_common.h"
 
 namespace fa {
 
 namespace {
-
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-typedef int i32x8_t __attribute__((ext_vector_type(8)));
-typedef long long i64x4_t __attribute__((ext_vector_type(4)));   // four group bases, held as values
-
-constexpr int kFp4 = 4;                                  // the instruction's format selector of e2m1 (0: e4m3)
 
 struct Fp4KvParams {
     const uint8_t *q, *kc, *ksc, *vc, *vsc;
@@ -83,22 +80,11 @@ struct Fp4KvParams {
     float c_log2;                         // float(softmax_scale) * log2(e)
 };
 
-// 4 x 4 byte transpose (fa_fp8_decode.hip's): t[dd] gets byte dd of x[0 .. 3], x[0]'s in the low byte
-__device__ __forceinline__ void transpose4x4(const uint32_t (&x)[4], uint32_t (&t)[4]) {
-    const uint32_t lo01 = __builtin_amdgcn_perm(x[1], x[0], 0x05010400u), hi01 = __builtin_amdgcn_perm(x[1], x[0], 0x07030602u);
-    const uint32_t lo23 = __builtin_amdgcn_perm(x[3], x[2], 0x05010400u), hi23 = __builtin_amdgcn_perm(x[3], x[2], 0x07030602u);
-    t[0] = __builtin_amdgcn_perm(lo23, lo01, 0x05040100u);
-    t[1] = __builtin_amdgcn_perm(lo23, lo01, 0x07060302u);
-    t[2] = __builtin_amdgcn_perm(hi23, hi01, 0x05040100u);
-    t[3] = __builtin_amdgcn_perm(hi23, hi01, 0x07060302u);
-}
-
-// the V^T image: 32 key bytes a channel row, 16 bytes of padding after every eight rows (the bank argument: the file header)
-constexpr int kVt4Bytes = 32 * 128 + 16 * 16;
-__device__ __forceinline__ int vt4_off(int row) { return 32 * row + 16 * (row >> 3); }
-
-template <typename Tag, bool PAGED>
-__global__ __launch_bounds__(64, 2) void fp4kv_split_kernel(const Fp4KvParams p) {
+template <typename Tag, bool PAGED, typename... Mod>
+__global__ __launch_bounds__(64, 2) void fp4kv_split_kernel(const Fp4KvParams p, const Mod... mod) {
+    constexpr bool MOD = sizeof...(Mod) != 0;                     // the featured instantiation: (KvqMod) follows p
+    static_assert(sizeof...(Mod) <= 1, "Mod...: nothing, or (KvqMod)");
+    const KvqMod md = kvq_mod_of<KvqMod>(mod...);
     constexpr int D = 128, KT = 64, NDV = D / 32, HB = D / 2;     // HB: code bytes a head
     __shared__ __attribute__((aligned(16))) char vt[kVt4Bytes];   // V^T tile, [channel][32 key bytes in P's key order]
     __shared__ __attribute__((aligned(16))) int evs[KT];          // the tile's V exponents, by key
@@ -116,314 +102,23 @@ __global__ __launch_bounds__(64, 2) void fp4kv_split_kernel(const Fp4KvParams p)
         crow = ix;
         if ((unsigned)ix >= (unsigned)p.bcache) { crow = 0; lk = 0; }   // an index outside the cache: an empty sequence
     }
-    const int coff = lk - nq;                                     // causal: token i sees key j <= i + coff
-    const int qlo = pr0 / G, qhi = (min(pr0 + 32, rows) - 1) / G;
-    // the split's keys [kbeg, kend): the tile's visible keys [0, hi) cut into 64-key tiles, tiles [s nt / S, (s + 1) nt / S)
-    const int hi = p.causal ? max(0, min(lk, qhi + coff + 1)) : lk;
-    const int nt = (hi + KT - 1) / KT;
-    const int t0 = (int)((long long)s * nt / S), t1 = (int)((long long)(s + 1) * nt / S);
-    const int kbeg = t0 * KT, kend = min(hi, t1 * KT);
-
-    // this lane's query row: token qi, query head hd; its last visible key rhi
-    const bool valid = pr < rows;
-    // (a padding row takes the tile's first token: its scores are masked like a real row's, and nothing of it is stored)
-    const int qi = valid ? pr / G : qlo, hd = hk * G + (valid ? pr - qi * G : 0);
-    const int rhi = min(p.causal ? qi + coff : lk - 1, kend - 1);
-
-    i32x8_t qb[2];
-    {
-        // (an 8-bit operand's byte 16 g + x of lane half h is k = 32 g + 16 h + x: the two 16-byte halves lie 32 channels apart)
-        const uint8_t* qp = p.q + (long long)b * p.q_bs + (long long)qi * p.q_ts + hd * D + 16 * h;
-#pragma unroll
-        for (int M = 0; M < 2; ++M) {
-            const u32x4 a0 = *reinterpret_cast<const u32x4*>(qp + 64 * M), a1 = *reinterpret_cast<const u32x4*>(qp + 64 * M + 32);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                qb[M][i] = valid ? (int)a0[i] : 0;
-                qb[M][4 + i] = valid ? (int)a1[i] : 0;
-            }
-        }
-    }
-    const float qd = p.qds ? p.qds[b * p.qds_bs + hk] : 1.f;
-    const float kd = p.kds ? p.kds[b * p.kds_bs + hk] : 1.f;
-    const float vd = p.vds ? p.vds[b * p.vds_bs + hk] : 1.f;
-    const float f = (p.c_log2 * qd) * kd;                         // the one score factor of this wave, > 0
-
-    // byte offsets of the first token of the tile's four 16-key groups in the four arrays (wave-uniform); kB < 0: the group
-    // reads as zero codes with unit scales (past the split's end, or a page outside the pool)
-    const int* tbl = PAGED ? p.table + b * p.tbl_rs : nullptr;
-    auto group_bases = [&](int k0, i64x4_t& kB, i64x4_t& sB, i64x4_t& vB, i64x4_t& eB) {
-        int j0 = 0, s0 = 0;
-        if (PAGED) { j0 = k0 / p.ps; s0 = k0 - j0 * p.ps; }
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const int key0 = k0 + 16 * g4;
-            kB[g4] = -1; sB[g4] = 0; vB[g4] = 0; eB[g4] = 0;
-            if (key0 < kend) {
-                long long pg = crow, sl = key0;
-                if (PAGED) {
-                    int j = j0, sj = s0 + 16 * g4;
-#pragma unroll
-                    for (int i = 0; i < 3; ++i)
-                        if (sj >= p.ps) { sj -= p.ps; ++j; }
-                    pg = tbl[j]; sl = sj;
-                    if ((unsigned long long)pg >= (unsigned long long)p.nblk) continue;
-                }
-                kB[g4] = pg * p.kc_bs + sl * p.kc_ts; sB[g4] = pg * p.ks_bs + sl * p.ks_ts;
-                vB[g4] = pg * p.vc_bs + sl * p.vc_ts; eB[g4] = pg * p.vs_bs + sl * p.vs_ts;
-            }
-        }
-    };
-
-    f32x16 oacc[NDV];
-#pragma unroll
-    for (int t = 0; t < NDV; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) oacc[t][i] = 0.f;
-    float m_run = -INFINITY, l_run = 0.f;                         // running max of t, in log2 units
-    const uint8_t* nowhere = p.q;                                 // readable and 16-byte aligned, for a load whose value is selected away
-    const int rd = r & 15, hv = r >> 4;                           // the lane's place in the V transpose: channels 8 rd .., keys 32 h + 4 hv + ..
-    const bool up = hv != 0;                                      // K: the lane's key lies in the block's second 16-key group
-
-    for (int k0 = kbeg; k0 < kend; k0 += KT) {
-        i64x4_t kB, sB, vB, eB;
-        group_bases(k0, kB, sB, vB, eB);
-
-        // a whole tile below the split's end on pages inside the pool: no lane needs a select on its addresses or its bytes
-        const bool full = k0 + KT <= kend && kB[0] >= 0 && kB[1] >= 0 && kB[2] >= 0 && kB[3] >= 0;
-        f32x16 sacc[2];
-        auto front = [&](auto full_c) {
-        constexpr bool FULL = decltype(full_c)::value;
-        // ---- S^T = K Q^T: K codes as they lie in memory, the lane's MX block scale on the instruction
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            const long long bk = up ? kB[2 * kb + 1] : kB[2 * kb], bs = up ? sB[2 * kb + 1] : sB[2 * kb];
-            const bool ok = FULL || (bk >= 0 && k0 + 32 * kb + r < kend);
-            const uint8_t* kp = ok ? p.kc + bk + rd * p.kc_ts + hk * HB + 16 * h : nowhere;
-            const uint8_t* sp = ok ? p.ksc + bs + rd * p.ks_ts + hk * 4 : nowhere;
-            const u32x4 a0 = *reinterpret_cast<const u32x4*>(kp), a1 = *reinterpret_cast<const u32x4*>(kp + 32);
-            uint32_t w = *reinterpret_cast<const uint32_t*>(sp);
-            if (!ok) w = 0x7f7f7f7fu;
-            const int sc0 = (int)((w >> (8 * h)) & 0xffu), sc1 = (int)((w >> (16 + 8 * h)) & 0xffu);
-            i32x8_t k0a = {0, 0, 0, 0, 0, 0, 0, 0}, k1a = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                k0a[i] = ok ? (int)a0[i] : 0;
-                k1a[i] = ok ? (int)a1[i] : 0;
-            }
-#pragma unroll
-            for (int i = 0; i < 16; ++i) sacc[kb][i] = 0.f;
-            sacc[kb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(k0a, qb[0], sacc[kb], kFp4, 0, 0, sc0, 0, 127);
-            sacc[kb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(k1a, qb[1], sacc[kb], kFp4, 0, 0, sc1, 0, 127);
-        }
-
-        // ---- the tile's V exponents: key k0 + lane on this lane, through LDS to the lanes that hold its scores
-        {
-            const int g4 = lane >> 4;
-            const long long bkk = g4 == 0 ? kB[0] : g4 == 1 ? kB[1] : g4 == 2 ? kB[2] : kB[3];
-            const long long be = g4 == 0 ? eB[0] : g4 == 1 ? eB[1] : g4 == 2 ? eB[2] : eB[3];
-            const bool ok = FULL || (bkk >= 0 && k0 + lane < kend);
-            const uint8_t* ep = ok ? p.vsc + be + (lane & 15) * p.vs_ts + hk : nowhere;
-            const int byte = *ep;
-            evs[lane] = ok ? byte - 127 : 0;
-        }
-
-        // ---- V -> V^T: 16 keys x 8 channels a lane, the nibble transpose, 8 bytes a channel into the image
-        // (the previous tile's operand reads were issued before these writes: one wave, LDS in order)
-        {
-            uint32_t te[2][4], to[2][4];                          // [jp][m]: channels 8 rd + 2 m and + 2 m + 1 of keys j = 2 jp, 2 jp + 1
-#pragma unroll
-            for (int jp = 0; jp < 2; ++jp) {
-                const long long bv = h ? vB[2 + jp] : vB[jp], bkk = h ? kB[2 + jp] : kB[jp];   // (wave halves: group 2 h + jp)
-                uint32_t ein[4], oin[4];
-#pragma unroll
-                for (int jj = 0; jj < 2; ++jj) {
-                    uint32_t x[4];
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        const int pos = 4 * hv + 8 * jj + c;      // the key's place in its 16-key group
-                        const bool ok = FULL || (bkk >= 0 && k0 + 32 * h + 16 * jp + pos < kend);
-                        const uint8_t* vp = ok ? p.vc + bv + pos * p.vc_ts + hk * HB + 4 * rd : nowhere;
-                        const uint32_t y = *reinterpret_cast<const uint32_t*>(vp);
-                        x[c] = ok ? y : 0u;
-                    }
-                    constexpr uint32_t LO = 0x0f0f0f0fu;
-                    ein[2 * jj] = (x[0] & LO) | ((x[1] & LO) << 4);
-                    oin[2 * jj] = ((x[0] >> 4) & LO) | (x[1] & ~LO);
-                    ein[2 * jj + 1] = (x[2] & LO) | ((x[3] & LO) << 4);
-                    oin[2 * jj + 1] = ((x[2] >> 4) & LO) | (x[3] & ~LO);
-                }
-                transpose4x4(ein, te[jp]);
-                transpose4x4(oin, to[jp]);
-            }
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                *reinterpret_cast<u32x2*>(vt + vt4_off(8 * rd + 2 * m) + 16 * h + 8 * hv) = u32x2{te[0][m], te[1][m]};
-                *reinterpret_cast<u32x2*>(vt + vt4_off(8 * rd + 2 * m + 1) + 16 * h + 8 * hv) = u32x2{to[0][m], to[1][m]};
-            }
-        }
-        };
-        if (full) front(std::true_type{});
-        else front(std::false_type{});
-
-        // ---- t = s f + ev, the mask, the row maximum over t
-        // (the mask only where a row of the tile can end inside this key tile: wave-uniform)
-        const bool need_mask = !full || (p.causal && k0 + KT - 1 > qlo + coff);
-        int ev[2][16];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const i32x4_t e4 = *reinterpret_cast<const i32x4_t*>(evs + 32 * kb + 4 * h + 8 * j);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) ev[kb][4 * j + c] = e4[c];
-            }
-            if (need_mask) {
-                const int thr = rhi - (k0 + 32 * kb + 4 * h);
-#pragma unroll
-                for (int i = 0; i < 16; ++i)
-                    if ((i & 3) + 8 * (i >> 2) > thr) sacc[kb][i] = -INFINITY;
-            }
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                sacc[kb][i] = fmaf(sacc[kb][i], f, (float)ev[kb][i]);    // (-inf stays -inf: f > 0)
-                mx = fmaxf(mx, sacc[kb][i]);
-            }
-        }
-        mx = fmaxf(mx, wave_half_swap(mx));
-        const float m_new = fmaxf(m_run, mx);
-        float m_use;
-        if (__any(valid && m_new - m_run > 8.0f) != 0) {   // lazy rescale on the real rows; a row's first visible key: inf > 8
-            m_use = m_new;
-            const float alpha = __builtin_amdgcn_exp2f(m_run - ((m_new == -INFINITY) ? 0.f : m_new));
-            m_run = m_new;
-            l_run *= alpha;
-#pragma unroll
-            for (int t2 = 0; t2 < NDV; ++t2)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) oacc[t2][i] *= alpha;
-        } else {
-            m_use = m_run;
-        }
-        if (m_use == -INFINITY) m_use = 0.f;      // a row without a visible key so far: p = exp2(-inf) = 0, not exp2(-inf + inf)
-        float rs = 0.f;
-        i32x8_t pb;                               // P'^T as the accumulators hold it, rounded to e4m3 (RNE)
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const float pe = __builtin_amdgcn_exp2f(sacc[kb][i] - m_use);
-                sacc[kb][i] = pe;
-                rs += __builtin_ldexpf(pe, -ev[kb][i]);          // the key's share of l: exp2(s f - M), V's scale taken out again
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                int wd = 0;
-                wd = __builtin_amdgcn_cvt_pk_fp8_f32(sacc[kb][4 * j + 0], sacc[kb][4 * j + 1], wd, false);
-                wd = __builtin_amdgcn_cvt_pk_fp8_f32(sacc[kb][4 * j + 2], sacc[kb][4 * j + 3], wd, true);
-                pb[4 * kb + j] = wd;
-            }
-        }
-        l_run += rs;
-
-        // ---- O^T = V^T P'^T: the lane's 16 key bytes (32 keys) of channel 32 dvb + r
-#pragma unroll
-        for (int dvb = 0; dvb < NDV; ++dvb) {
-            const u32x4 a0 = *reinterpret_cast<const u32x4*>(vt + vt4_off(32 * dvb + r) + 16 * h);
-            const i32x8_t va = {(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], 0, 0, 0, 0};
-            oacc[dvb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(va, pb, oacc[dvb], kFp4, 0, 0, 127, 0, 127);
-        }
-    }
-
-    // ---- epilogue: O^T register i of block dvb is channel 32 dvb + 4 h + (i & 3) + 8 (i >> 2) of the lane's query row
-    const float l_tot = l_run + wave_half_swap(l_run);
-    if (!valid) return;
-    const bool dead = l_tot == 0.f;                      // no visible key: o = 0, lse = -inf (a NaN l is not dead: it propagates)
-    const float inv = vd * (1.f / l_tot);                // v_descale once, with 1 / l
-    const float lse_v = dead ? -INFINITY : (m_run + log2f(l_tot)) * 0.6931471805599453f;
-    const size_t row_id = ((size_t)b * p.hq + hd) * nq + qi;
-    if (S == 1) {
-        uint16_t* orow = p.o + (((size_t)b * nq + qi) * p.hq + hd) * D;
-#pragma unroll
-        for (int dvb = 0; dvb < NDV; ++dvb)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float y[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) y[j] = dead ? 0.f : oacc[dvb][4 * g + j] * inv;
-                u32x2 v;
-                v[0] = pack2_rn<Tag>(y[0], y[1]);
-                v[1] = pack2_rn<Tag>(y[2], y[3]);
-                *reinterpret_cast<u32x2*>(orow + 32 * dvb + 8 * g + 4 * h) = v;
-            }
-        if (h == 0) p.lse[row_id] = lse_v;
-    } else {
-        float* prow = p.po + (row_id * S + s) * D;
-#pragma unroll
-        for (int dvb = 0; dvb < NDV; ++dvb)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4 y;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) y[j] = dead ? 0.f : oacc[dvb][4 * g + j] * inv;
-                *reinterpret_cast<f32x4*>(prow + 32 * dvb + 8 * g + 4 * h) = y;
-            }
-        if (h == 0) p.plse[row_id * S + s] = lse_v;
-    }
-}
-
-// What fp4kv_split_mod_kernel takes beside Fp4KvParams (fa_fp4_forward_kvcache_mod)
-struct Fp4KvMod {
-    int wl, wr;                           // token i sees keys [i + coff - wl, i + coff + wr]; kWinNone: unbounded, wr = 0 if causal
-    float cap_k, cap2;                    // 2 / softcap, softcap * log2(e); cap2 == 0: no softcap
-};
-
-// fp4kv_split_kernel's text (DUPLICATED rather than shared, as fp8kv_split_mod_kernel's is: the unfeatured kernel keeps its
-// instructions) with, as wave-uniform run-time switches:
-//   window   the wave's keys are [lo, hi): lo the first 64-key tile some row of the 32 sees, hi the last visible key + 1.  The
-//            splits cut [lo, hi): no table entry, code byte or scale byte below lo or at / past hi is read.  A tile inside every
-//            row's band on valid pages takes the fast path; the selects (row's upper bound, row's lower bound) run only on a tile
-//            that holds a band edge or the end.
-//   softcap  the capped score in log2 units, cap2 (1 - 2 r) with r = 1 / (2^(ck s) + 1), ck = f cap_k, replaces s f: one exp2 and
-//            one rcp an element, before the mask.  Then t = capped + ev.
-//   masked   a masked key's score is -inf BEFORE ev is added: its ev never reaches the joint maximum.
-// The bounds live in SGPRs (md is a kernel argument); a lane's lower bound rlo is recomputed from its token where it is needed.
-// Sinks are not this kernel's: they join in kv_combine_kernel<Tag, true>, once per row.
-template <typename Tag, bool PAGED>
-__global__ __launch_bounds__(64, 2) void fp4kv_split_mod_kernel(const Fp4KvParams p, const Fp4KvMod md) {
-    constexpr int D = 128, KT = 64, NDV = D / 32, HB = D / 2;     // HB: code bytes a head
-    __shared__ __attribute__((aligned(16))) char vt[kVt4Bytes];   // V^T tile, [channel][32 key bytes in P's key order]
-    __shared__ __attribute__((aligned(16))) int evs[KT];          // the tile's V exponents, by key
-    const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
-    const int s = blockIdx.x, S = gridDim.x;
-    const int hk = blockIdx.y % p.hkv, rt = blockIdx.y / p.hkv, b = blockIdx.z;
-    const int nq = p.nq, rows = p.rows, G = p.G;
-    const int pr0 = 32 * rt, pr = pr0 + r;                        // (the grid has ceil(rows / 32) row tiles: pr0 < rows)
-
-    // the sequence: its length, and the cache row its keys lie in (contiguous)
-    int lk = p.seqlens ? min(max(p.seqlens[b], 0), p.cap) : p.cap;
-    long long crow = b;
-    if (!PAGED && p.bidx) {
-        const int ix = p.bidx[b];
-        crow = ix;
-        if ((unsigned)ix >= (unsigned)p.bcache) { crow = 0; lk = 0; }   // an index outside the cache: an empty sequence
-    }
-    const int coff = lk - nq;                                     // token i sees keys [i + coff - wl, i + coff + wr]
+    const int coff = lk - nq;                                     // causal: token i sees key j <= i + coff; MOD: [i + coff - wl, i + coff + wr]
     const int qlo = pr0 / G, qhi = (min(pr0 + 32, rows) - 1) / G;
     // the split's keys [kbeg, kend): the tile's visible keys [lo, hi) cut into 64-key tiles, tiles [s nt / S, (s + 1) nt / S)
+    // window: lo is the first 64-key tile some row of the 32 sees (whole 16-key groups), hi the last visible key + 1.  The splits
+    // cut [lo, hi): no table entry, code byte or scale byte below lo or at / past hi is read.
     // (wl, wr <= 2^30, coff < 2^28, a token < 2^20: the sums stay inside an int)
-    const int hi = max(0, min(lk, qhi + coff + md.wr + 1));
-    const int lo = max(0, qlo + coff - md.wl) & ~(KT - 1);       // the first 64-key tile some row sees (whole 16-key groups)
-    const int nt = hi > lo ? (hi - lo + KT - 1) / KT : 0;
+    const int hi = MOD ? max(0, min(lk, qhi + coff + md.wr + 1)) : p.causal ? max(0, min(lk, qhi + coff + 1)) : lk;
+    const int lo = MOD ? max(0, qlo + coff - md.wl) & ~(KT - 1) : 0;
+    const int nt = MOD ? (hi > lo ? (hi - lo + KT - 1) / KT : 0) : (hi + KT - 1) / KT;
     const int t0 = (int)((long long)s * nt / S), t1 = (int)((long long)(s + 1) * nt / S);
     const int kbeg = lo + t0 * KT, kend = min(hi, lo + t1 * KT);
 
-    // this lane's query row: token qi, query head hd; it sees keys [qi + coff - wl, rhi]
+    // this lane's query row: token qi, query head hd; its last visible key rhi (MOD: it sees keys [qi + coff - wl, rhi])
     const bool valid = pr < rows;
     // (a padding row takes the tile's first token: its scores are masked like a real row's, and nothing of it is stored)
     const int qi = valid ? pr / G : qlo, hd = hk * G + (valid ? pr - qi * G : 0);
-    const int rhi = min(min(qi + coff + md.wr, lk - 1), kend - 1);
+    const int rhi = MOD ? min(min(qi + coff + md.wr, lk - 1), kend - 1) : min(p.causal ? qi + coff : lk - 1, kend - 1);
 
     i32x8_t qb[2];
     {
@@ -443,7 +138,7 @@ __global__ __launch_bounds__(64, 2) void fp4kv_split_mod_kernel(const Fp4KvParam
     const float kd = p.kds ? p.kds[b * p.kds_bs + hk] : 1.f;
     const float vd = p.vds ? p.vds[b * p.vds_bs + hk] : 1.f;
     const float f = (p.c_log2 * qd) * kd;                         // the one score factor of this wave, > 0
-    const bool capped = md.cap2 != 0.f;
+    const bool capped = MOD && md.cap2 != 0.f;
     const float ck = f * md.cap_k;
     const float fe = capped ? 1.f : f;                            // the factor of what the accumulators hold after the cap
 
@@ -564,7 +259,8 @@ __global__ __launch_bounds__(64, 2) void fp4kv_split_mod_kernel(const Fp4KvParam
         if (full) front(std::true_type{});
         else front(std::false_type{});
 
-        // ---- the softcap (before the mask): the capped score in log2 units, one exp2 and one rcp an element
+        // ---- softcap (before the mask): the capped score in log2 units, cap2 (1 - 2 r) with r = 1 / (2^(ck s) + 1), ck = f cap_k,
+        // replaces s f: one exp2 and one rcp an element
         if (capped) {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
@@ -575,9 +271,10 @@ __global__ __launch_bounds__(64, 2) void fp4kv_split_mod_kernel(const Fp4KvParam
                 }
         }
         // ---- the mask, t = (s f or the capped score) + ev, the row maximum over t
-        // (the selects only where a row's upper bound, the end, or a row's lower bound lies inside this key tile: wave-uniform)
-        const bool need_mask = !full || k0 + KT - 1 > qlo + coff + md.wr;
-        const bool need_lo = k0 < qhi + coff - md.wl;             // some row's lower bound lies inside or past this tile
+        // (the selects only where a row's upper bound, the end, or with a window a row's lower bound lies inside this key tile:
+        // wave-uniform.  A masked key's score is -inf BEFORE ev is added: its ev never reaches the joint maximum.)
+        const bool need_mask = !full || (MOD ? k0 + KT - 1 > qlo + coff + md.wr : p.causal && k0 + KT - 1 > qlo + coff);
+        const bool need_lo = MOD && k0 < qhi + coff - md.wl;      // some row's lower bound lies inside or past this tile
         int ev[2][16];
         float mx = -INFINITY;
 #pragma unroll
@@ -796,7 +493,7 @@ hipError_t launch_fp4_kvcache_append(const Fp4AppendArgs& a, hipStream_t st) {
 }
 
 // md: null for fa_fp4_forward_kvcache; else the featured call's kernel arguments, with its sinks (null: none)
-static hipError_t launch_fp4_kvcache_t(const Fp4KvArgs& a, const Fp4KvMod* md, const float* sinks, int sink_heads, hipStream_t st) {
+static hipError_t launch_fp4_kvcache_t(const Fp4KvArgs& a, const KvqMod* md, const float* sinks, int sink_heads, hipStream_t st) {
     Fp4KvParams p;
     p.q = (const uint8_t*)a.q; p.kc = (const uint8_t*)a.c.k_cache; p.ksc = (const uint8_t*)a.c.k_scale;
     p.vc = (const uint8_t*)a.c.v_cache; p.vsc = (const uint8_t*)a.c.v_scale;
@@ -817,28 +514,16 @@ static hipError_t launch_fp4_kvcache_t(const Fp4KvArgs& a, const Fp4KvMod* md, c
     p.plse = S > 1 ? (float*)((char*)a.workspace + ((q_rows * S * (size_t)128 * 4 + 255) & ~(size_t)255)) : nullptr;
     const int row_tiles = (int)((p.rows + 31) / 32);
     const dim3 grid((unsigned)S, (unsigned)(row_tiles * p.hkv), (unsigned)a.batch);
-    if (md) {
-        route_hit(ROUTE_FP4KV_SPLIT_MOD);
-        ProfScope ps(K_FP4KV_SPLIT_MOD, st);
-        const bool paged = a.c.block_table != nullptr;
-        if (a.dtype == 2) {
-            if (paged) hipLaunchKernelGGL((fp4kv_split_mod_kernel<bf16_tag, true>), grid, dim3(64), 0, st, p, *md);
-            else hipLaunchKernelGGL((fp4kv_split_mod_kernel<bf16_tag, false>), grid, dim3(64), 0, st, p, *md);
-        } else {
-            if (paged) hipLaunchKernelGGL((fp4kv_split_mod_kernel<f16_tag, true>), grid, dim3(64), 0, st, p, *md);
-            else hipLaunchKernelGGL((fp4kv_split_mod_kernel<f16_tag, false>), grid, dim3(64), 0, st, p, *md);
-        }
-    } else {
-        route_hit(ROUTE_FP4KV_SPLIT);
-        ProfScope ps(K_FP4KV_SPLIT, st);
-        const bool paged = a.c.block_table != nullptr;
-        if (a.dtype == 2) {
-            if (paged) hipLaunchKernelGGL((fp4kv_split_kernel<bf16_tag, true>), grid, dim3(64), 0, st, p);
-            else hipLaunchKernelGGL((fp4kv_split_kernel<bf16_tag, false>), grid, dim3(64), 0, st, p);
-        } else {
-            if (paged) hipLaunchKernelGGL((fp4kv_split_kernel<f16_tag, true>), grid, dim3(64), 0, st, p);
-            else hipLaunchKernelGGL((fp4kv_split_kernel<f16_tag, false>), grid, dim3(64), 0, st, p);
-        }
+    route_hit(md ? ROUTE_FP4KV_SPLIT_MOD : ROUTE_FP4KV_SPLIT);
+    {
+        ProfScope ps(md ? K_FP4KV_SPLIT_MOD : K_FP4KV_SPLIT, st);
+        auto launch = [&](auto... mod) {
+            kvq_dispatch(a.dtype, a.c.block_table != nullptr, [&](auto tag, auto paged) {
+                hipLaunchKernelGGL((fp4kv_split_kernel<decltype(tag), decltype(paged)::value, decltype(mod)...>), grid, dim3(64), 0, st, p, mod...);
+            });
+        };
+        if (md) launch(*md);
+        else launch();
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || S == 1) return e;
@@ -851,11 +536,7 @@ hipError_t launch_fp4_kvcache(const Fp4KvArgs& a, hipStream_t st) { return launc
 hipError_t launch_fp4_kvcache_mod(const Fp4KvArgs& a, const Fp8Mod& m, hipStream_t st) {
     if (!m.any()) return launch_fp4_kvcache(a, st);     // the parent call, launch for launch
     if (m.sinks && a.num_splits < 2) return hipErrorInvalidValue;   // (the C layer raises a sink call's S to 2: the sink joins in the combine)
-    Fp4KvMod md;
-    md.wl = m.window_left >= 0 ? (int)std::min<int64_t>(m.window_left, kWinNone) : kWinNone;
-    md.wr = a.causal ? 0 : (m.window_right >= 0 ? (int)std::min<int64_t>(m.window_right, kWinNone) : kWinNone);
-    md.cap_k = m.softcap > 0.0 ? (float)(2.0 / m.softcap) : 0.f;
-    md.cap2 = m.softcap > 0.0 ? (float)(m.softcap * 1.4426950408889634) : 0.f;
+    const KvqMod md = kvq_mod_args(m, a.causal != 0);
     return launch_fp4_kvcache_t(a, &md, m.sinks, (int)(m.sink_heads > 0 ? m.sink_heads : 1), st);
 }
 

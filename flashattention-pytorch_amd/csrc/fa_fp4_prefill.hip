@@ -40,23 +40,20 @@
 // What is untrusted: cu_seqlens_q, cu_seqlens_k, block_table, the descales and every cache byte, read on the device only.  (start,
 // nq_b) = kv_cu_range(cu_seqlens_q, b, total_q, max_seqlen_q); nk_b = kv_cu_range(cu_seqlens_k, b, 2^31 - 1, capacity).  A scale
 // byte is only ever an operand of arithmetic.  Rows of no sequence are not written.
-#include <algorithm>
+//
+// fa_fp4_forward_varlen_mod (a sliding window, a softcap, attention sinks) launches the featured
+// instantiation fp4kv_prefill_kernel<Tag, KvqModSinks>: the same text with one more kernel argument (fa_kvq_common.h) and the
+// features as run-time switches, noted at the sites they change.
 #include <climits>
 
-#include "fa_decode_common.h"
+#include "fa_kvq_common.h"
 
 namespace fa {
 
 namespace {
 
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-typedef int i32x8_t __attribute__((ext_vector_type(8)));
-
-constexpr int kFp4 = 4;                                  // the instruction's format selector of e2m1 (0: e4m3)
 constexpr int kKRow = 80;                                // bytes of a key's row in the K stage
 constexpr int kKBytes = 64 * kKRow;
-constexpr int kVt4Bytes = 32 * 128 + 16 * 16;            // the V^T image of fa_fp4_decode.hip
-__device__ __forceinline__ int vt4_off(int row) { return 32 * row + 16 * (row >> 3); }
 
 struct Fp4PrefillParams {
     const uint8_t *q, *kc, *ksc, *vc, *vsc;
@@ -80,8 +77,11 @@ struct Fp4Staged {
     uint32_t s;
 };
 
-template <typename Tag>
-__global__ __launch_bounds__(256, 2) void fp4kv_prefill_kernel(const Fp4PrefillParams p) {
+template <typename Tag, typename... Mod>
+__global__ __launch_bounds__(256, 2) void fp4kv_prefill_kernel(const Fp4PrefillParams p, const Mod... mod) {
+    constexpr bool MOD = sizeof...(Mod) != 0;                     // the featured instantiation: (KvqModSinks) follows p
+    static_assert(sizeof...(Mod) <= 1, "Mod...: nothing, or (KvqModSinks)");
+    const KvqModSinks md = kvq_mod_of<KvqModSinks>(mod...);
     constexpr int D = 128, KT = 64, NDV = D / 32, HB = D / 2;     // HB: code bytes a head
     __shared__ __attribute__((aligned(16))) char kt[2][kKBytes];  // K stages: [key][64 code bytes, 4 scale bytes, pad]
     __shared__ __attribute__((aligned(16))) char vt[2][kVt4Bytes];   // V^T stages, [channel][32 key bytes in P's key order]
@@ -96,286 +96,31 @@ __global__ __launch_bounds__(256, 2) void fp4kv_prefill_kernel(const Fp4PrefillP
     const int nk = kv_cu_range(p.cu_k, b, INT_MAX, p.cap, kdummy);
     const int rows = nq * G, pr0 = 128 * rt;
     if (pr0 >= rows) return;                                      // (the whole workgroup)
-    const int coff = nk - nq;                                     // causal: token i sees key j <= i + coff
-    // the workgroup's keys [0, kend), the wave's [0, whi)
-    const int wr0 = pr0 + 32 * w;
-    const bool wave_on = wr0 < rows;
-    const int qlo = (wave_on ? wr0 : pr0) / G, qhi = (min(wr0 + 32, rows) - 1) / G, qhi_wg = (min(pr0 + 128, rows) - 1) / G;
-    const int kend = p.causal ? max(0, min(nk, qhi_wg + coff + 1)) : nk;
-    const int whi = !wave_on ? 0 : p.causal ? max(0, min(nk, qhi + coff + 1)) : nk;
-    const int nt = (kend + KT - 1) / KT;
-
-    // this lane's query row: token qi, query head hd; its last visible key rhi
-    const int pr = wr0 + r;
-    const bool valid = pr < rows;
-    // (a padding row takes the wave's first token: its scores are masked like a real row's, and nothing of it is stored)
-    const int qi = valid ? pr / G : qlo, hd = hk * G + (valid ? pr - qi * G : 0);
-    const int rhi = min(p.causal ? qi + coff : nk - 1, kend - 1);
-
-    i32x8_t qb[2];
-    {
-        // (an 8-bit operand's byte 16 g + x of lane half h is k = 32 g + 16 h + x: the two 16-byte halves lie 32 channels apart)
-        const uint8_t* qp = p.q + (long long)(qstart + qi) * p.q_ts + hd * D + 16 * h;
-#pragma unroll
-        for (int M = 0; M < 2; ++M) {
-            const u32x4 a0 = *reinterpret_cast<const u32x4*>(qp + 64 * M), a1 = *reinterpret_cast<const u32x4*>(qp + 64 * M + 32);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                qb[M][i] = valid ? (int)a0[i] : 0;
-                qb[M][4 + i] = valid ? (int)a1[i] : 0;
-            }
-        }
-    }
-    const float qd = p.qds ? p.qds[b * p.qds_bs + hk] : 1.f;
-    const float kd = p.kds ? p.kds[b * p.kds_bs + hk] : 1.f;
-    const float vd = p.vds ? p.vds[b * p.vds_bs + hk] : 1.f;
-    const float f = (p.c_log2 * qd) * kd;                         // the one score factor of this workgroup, > 0
-
-    // ---- the loader: this wave's 16-key group of a tile
-    const int* tbl = p.table + b * p.tbl_rs;
-    const int kk = lane >> 2, kch = lane & 3;                     // K: key of the group, 16-byte chunk
-    const int rd = lane & 15, hv = (lane >> 4) & 1, jl = lane >> 5;   // V: channels 8 rd .., keys 4 hv + 8 jl + c of the group
-    // the group's table entry, -1 where the group starts at or past kend (no entry is read there)
-    auto fetch_page = [&](int t) -> int {
-        const int key0 = t * KT + 16 * w;
-        return key0 < kend ? tbl[key0 / p.ps] : -1;
-    };
-    auto load_tile = [&](int t, int pg) -> Fp4Staged {
-        Fp4Staged st;
-        st.k = u32x4{0u, 0u, 0u, 0u};
-        st.v[0] = st.v[1] = st.v[2] = st.v[3] = 0u;
-        st.s = lane < 16 ? 0x7f7f7f7fu : 127u;
-        const int key0 = t * KT + 16 * w;
-        if (key0 >= kend || (unsigned)pg >= (unsigned)p.nblk) return st;      // (wave-uniform)
-        const long long sl = key0 % p.ps;
-        const uint8_t* kp = p.kc + pg * p.kc_bs + sl * p.kc_ts + hk * HB;
-        const uint8_t* vp = p.vc + pg * p.vc_bs + sl * p.vc_ts + hk * HB + 4 * rd;
-        const uint8_t* sp = p.ksc + pg * p.ks_bs + sl * p.ks_ts + hk * 4;
-        const uint8_t* ep = p.vsc + pg * p.vs_bs + sl * p.vs_ts + hk;
-        const bool full = key0 + 16 <= kend;                     // no lane needs a compare
-        if (full || key0 + kk < kend) st.k = *reinterpret_cast<const u32x4*>(kp + kk * p.kc_ts + 16 * kch);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int pos = 4 * hv + 8 * jl + c;
-            if (full || key0 + pos < kend) st.v[c] = *reinterpret_cast<const uint32_t*>(vp + pos * p.vc_ts);
-        }
-        if (lane < 16) {
-            if (full || key0 + lane < kend) st.s = *reinterpret_cast<const uint32_t*>(sp + lane * p.ks_ts);
-        } else if (lane < 32) {
-            if (full || key0 + lane - 16 < kend) st.s = ep[(lane - 16) * p.vs_ts];
-        }
-        return st;
-    };
-    auto store_tile = [&](const Fp4Staged& st, int buf) {
-        *reinterpret_cast<u32x4*>(kt[buf] + kKRow * (16 * w + kk) + 16 * kch) = st.k;
-        if (lane < 16) *reinterpret_cast<uint32_t*>(kt[buf] + kKRow * (16 * w + lane) + 64) = st.s;
-        else if (lane < 32) evs[buf][16 * w + lane - 16] = (int)st.s - 127;
-        // V -> V^T: four keys x eight channels a lane; the even (odd) channels of key pairs (0, 1) and (2, 3) in a byte each
-        constexpr uint32_t LO = 0x0f0f0f0fu;
-        const uint32_t ea = (st.v[0] & LO) | ((st.v[1] & LO) << 4), eb = (st.v[2] & LO) | ((st.v[3] & LO) << 4);
-        const uint32_t oa = ((st.v[0] >> 4) & LO) | (st.v[1] & ~LO), ob = ((st.v[2] >> 4) & LO) | (st.v[3] & ~LO);
-        // bytes {a.m, b.m} side by side: channel pair m = 0, 1 in the first word's halves, m = 2, 3 in the second's
-        const uint32_t e01 = __builtin_amdgcn_perm(eb, ea, 0x05010400u), e23 = __builtin_amdgcn_perm(eb, ea, 0x07030602u);
-        const uint32_t o01 = __builtin_amdgcn_perm(ob, oa, 0x05010400u), o23 = __builtin_amdgcn_perm(ob, oa, 0x07030602u);
-        char* base = vt[buf] + 16 * (w >> 1) + 8 * hv + 2 * (2 * (w & 1) + jl);
-        *reinterpret_cast<uint16_t*>(base + vt4_off(8 * rd + 0)) = (uint16_t)e01;
-        *reinterpret_cast<uint16_t*>(base + vt4_off(8 * rd + 1)) = (uint16_t)o01;
-        *reinterpret_cast<uint16_t*>(base + vt4_off(8 * rd + 2)) = (uint16_t)(e01 >> 16);
-        *reinterpret_cast<uint16_t*>(base + vt4_off(8 * rd + 3)) = (uint16_t)(o01 >> 16);
-        *reinterpret_cast<uint16_t*>(base + vt4_off(8 * rd + 4)) = (uint16_t)e23;
-        *reinterpret_cast<uint16_t*>(base + vt4_off(8 * rd + 5)) = (uint16_t)o23;
-        *reinterpret_cast<uint16_t*>(base + vt4_off(8 * rd + 6)) = (uint16_t)(e23 >> 16);
-        *reinterpret_cast<uint16_t*>(base + vt4_off(8 * rd + 7)) = (uint16_t)(o23 >> 16);
-    };
-
-    f32x16 oacc[NDV];
-#pragma unroll
-    for (int t = 0; t < NDV; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) oacc[t][i] = 0.f;
-    float m_run = -INFINITY, l_run = 0.f;                         // running max of t, in log2 units
-
-    // ---- one 64-key tile of this wave out of stage buf
-    auto compute = [&](int k0, int buf) {
-        const char* ktb = kt[buf];
-        const char* vtb = vt[buf];
-        const int* evb = evs[buf];
-        f32x16 sacc[2];
-        // S^T = K Q^T: K codes as they lie in memory, the lane's MX block scale on the instruction
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            const char* row = ktb + kKRow * (32 * kb + r);
-            const u32x4 a0 = *reinterpret_cast<const u32x4*>(row + 16 * h), a1 = *reinterpret_cast<const u32x4*>(row + 32 + 16 * h);
-            const uint32_t ws = *reinterpret_cast<const uint32_t*>(row + 64);
-            const int sc0 = (int)((ws >> (8 * h)) & 0xffu), sc1 = (int)((ws >> (16 + 8 * h)) & 0xffu);
-            const i32x8_t k0a = {(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], 0, 0, 0, 0};
-            const i32x8_t k1a = {(int)a1[0], (int)a1[1], (int)a1[2], (int)a1[3], 0, 0, 0, 0};
-#pragma unroll
-            for (int i = 0; i < 16; ++i) sacc[kb][i] = 0.f;
-            sacc[kb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(k0a, qb[0], sacc[kb], kFp4, 0, 0, sc0, 0, 127);
-            sacc[kb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(k1a, qb[1], sacc[kb], kFp4, 0, 0, sc1, 0, 127);
-        }
-
-        // t = s f + ev, the mask, the row maximum over t
-        // (the mask only where the sequence or a row of the wave can end inside this key tile: wave-uniform)
-        const bool need_mask = k0 + KT > kend || (p.causal && k0 + KT - 1 > qlo + coff);
-        int ev[2][16];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const i32x4_t e4 = *reinterpret_cast<const i32x4_t*>(evb + 32 * kb + 4 * h + 8 * j);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) ev[kb][4 * j + c] = e4[c];
-            }
-            if (need_mask) {
-                const int thr = rhi - (k0 + 32 * kb + 4 * h);
-#pragma unroll
-                for (int i = 0; i < 16; ++i)
-                    if ((i & 3) + 8 * (i >> 2) > thr) sacc[kb][i] = -INFINITY;
-            }
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                sacc[kb][i] = fmaf(sacc[kb][i], f, (float)ev[kb][i]);    // (-inf stays -inf: f > 0)
-                mx = fmaxf(mx, sacc[kb][i]);
-            }
-        }
-        mx = fmaxf(mx, wave_half_swap(mx));
-        const float m_new = fmaxf(m_run, mx);
-        float m_use;
-        if (__any(valid && m_new - m_run > 8.0f) != 0) {   // lazy rescale on the real rows; a row's first visible key: inf > 8
-            m_use = m_new;
-            const float alpha = __builtin_amdgcn_exp2f(m_run - ((m_new == -INFINITY) ? 0.f : m_new));
-            m_run = m_new;
-            l_run *= alpha;
-#pragma unroll
-            for (int t2 = 0; t2 < NDV; ++t2)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) oacc[t2][i] *= alpha;
-        } else {
-            m_use = m_run;
-        }
-        if (m_use == -INFINITY) m_use = 0.f;      // a row without a visible key so far: p = exp2(-inf) = 0, not exp2(-inf + inf)
-        float rs = 0.f;
-        i32x8_t pb;                               // P'^T as the accumulators hold it, rounded to e4m3 (RNE)
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const float pe = __builtin_amdgcn_exp2f(sacc[kb][i] - m_use);
-                sacc[kb][i] = pe;
-                rs += __builtin_ldexpf(pe, -ev[kb][i]);          // the key's share of l: exp2(s f - M), V's scale taken out again
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                int wd = 0;
-                wd = __builtin_amdgcn_cvt_pk_fp8_f32(sacc[kb][4 * j + 0], sacc[kb][4 * j + 1], wd, false);
-                wd = __builtin_amdgcn_cvt_pk_fp8_f32(sacc[kb][4 * j + 2], sacc[kb][4 * j + 3], wd, true);
-                pb[4 * kb + j] = wd;
-            }
-        }
-        l_run += rs;
-
-        // O^T = V^T P'^T: the lane's 16 key bytes (32 keys) of channel 32 dvb + r
-#pragma unroll
-        for (int dvb = 0; dvb < NDV; ++dvb) {
-            const u32x4 a0 = *reinterpret_cast<const u32x4*>(vtb + vt4_off(32 * dvb + r) + 16 * h);
-            const i32x8_t va = {(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], 0, 0, 0, 0};
-            oacc[dvb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(va, pb, oacc[dvb], kFp4, 0, 0, 127, 0, 127);
-        }
-    };
-
-    // ---- the ring: tile t in stage t & 1, tile t + 1 in the other, tile t + 2 in st, the table entry of tile t + 3 in pg
-    Fp4Staged st = load_tile(0, fetch_page(0));
-    int pg = fetch_page(1);
-    store_tile(st, 0);
-    st = load_tile(1, pg);
-    pg = fetch_page(2);
-    __syncthreads();
-    for (int t = 0; t < nt; ++t) {
-        store_tile(st, (t + 1) & 1);              // (its last readers, of tile t - 1, are behind the barrier)
-        st = load_tile(t + 2, pg);
-        pg = fetch_page(t + 3);
-        if (t * KT < whi) compute(t * KT, t & 1);
-        __syncthreads();
-    }
-
-    // ---- epilogue: O^T register i of block dvb is channel 32 dvb + 4 h + (i & 3) + 8 (i >> 2) of the lane's query row
-    const float l_tot = l_run + wave_half_swap(l_run);
-    if (!valid) return;
-    const bool dead = l_tot == 0.f;                      // no visible key: o = 0, lse = -inf (a NaN l is not dead: it propagates)
-    const float inv = vd * (1.f / l_tot);                // v_descale once, with 1 / l
-    const float lse_v = dead ? -INFINITY : (m_run + log2f(l_tot)) * 0.6931471805599453f;
-    uint16_t* orow = p.o + ((size_t)(qstart + qi) * p.hq + hd) * D;
-#pragma unroll
-    for (int dvb = 0; dvb < NDV; ++dvb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float y[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) y[j] = dead ? 0.f : oacc[dvb][4 * g + j] * inv;
-            u32x2 v;
-            v[0] = pack2_rn<Tag>(y[0], y[1]);
-            v[1] = pack2_rn<Tag>(y[2], y[3]);
-            *reinterpret_cast<u32x2*>(orow + 32 * dvb + 8 * g + 4 * h) = v;
-        }
-    if (h == 0) p.lse[(size_t)hd * p.total_q + qstart + qi] = lse_v;
-}
-
-// What fp4kv_prefill_mod_kernel takes beside Fp4PrefillParams (fa_fp4_forward_varlen_mod)
-struct Fp4PfMod {
-    int wl, wr;                           // token i sees keys [i + coff - wl, i + coff + wr]; kWinNone: unbounded, wr = 0 if causal
-    float cap_k, cap2;                    // 2 / softcap, softcap * log2(e); cap2 == 0: no softcap
-    const float* sinks;                   // one logit a query head (natural-log units), sinks[h % sink_heads]; null: none
-    int sink_heads;
-};
-
-// fp4kv_prefill_kernel's text (DUPLICATED rather than shared: the unfeatured kernel keeps its instructions) with, as run-time switches:
-//   window   the workgroup's keys are [klo, kend): klo the smallest lower bound of its 128 rows, kend its largest upper bound + 1
-//            (the sequence's end at most).  The ring walks tiles [t_lo, t_hi) = [klo / 64, ceil(kend / 64)) alone, O(N w) tiles a
-//            sequence; prologue, stage parity, the tile in flight and the table entry of t + 3 all count from t_lo.  The loader
-//            reads no table entry, code or scale byte of a 16-key group outside [klo, kend).  A wave computes the tiles that meet
-//            its own rows' band [wlo, whi) and only loads and meets the barrier on the others.  The selects (upper bound / end,
-//            lower bound) run on the tiles that hold one of the wave's band edges or the end: wave-uniform.
-//   softcap  fp4kv_split_mod_kernel's: the capped score in log2 units replaces s f before the mask, then t = capped + ev.
-//   masked   a masked key's score is -inf before ev is added: its ev never reaches the joint maximum.
-//   sinks    in the epilogue by ex_sink_norm (finite at +-1e4): a row without a visible key gives o = 0, lse = sink.
-template <typename Tag>
-__global__ __launch_bounds__(256, 2) void fp4kv_prefill_mod_kernel(const Fp4PrefillParams p, const Fp4PfMod md) {
-    constexpr int D = 128, KT = 64, NDV = D / 32, HB = D / 2;     // HB: code bytes a head
-    __shared__ __attribute__((aligned(16))) char kt[2][kKBytes];  // K stages: [key][64 code bytes, 4 scale bytes, pad]
-    __shared__ __attribute__((aligned(16))) char vt[2][kVt4Bytes];   // V^T stages, [channel][32 key bytes in P's key order]
-    __shared__ __attribute__((aligned(16))) int evs[2][KT];       // the tiles' V exponents, by key
-    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int rt = gridDim.x - 1 - blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
-    const int G = p.G;
-
-    int qstart, kdummy;
-    const int nq = kv_cu_range(p.cu_q, b, p.total_q, p.max_q, qstart);
-    const int nk = kv_cu_range(p.cu_k, b, INT_MAX, p.cap, kdummy);
-    const int rows = nq * G, pr0 = 128 * rt;
-    if (pr0 >= rows) return;                                      // (the whole workgroup)
-    const int coff = nk - nq;                                     // token i sees keys [i + coff - wl, i + coff + wr]
-    // the workgroup's keys [klo, kend) in tiles [t_lo, t_hi), the wave's [wlo, whi)
+    const int coff = nk - nq;                                     // causal: token i sees key j <= i + coff; MOD: [i + coff - wl, i + coff + wr]
+    // the workgroup's keys [klo, kend) in tiles [t_lo, t_hi), the wave's [wlo, whi); without a window klo = wlo = t_lo = 0
+    // window: klo is the smallest lower bound of the workgroup's 128 rows, kend its largest upper bound + 1 (the sequence's end at
+    // most).  The ring walks tiles [klo / 64, ceil(kend / 64)) alone, O(N w) tiles a sequence; prologue, stage parity, the tile in
+    // flight and the table entry of t + 3 all count from t_lo.  The loader reads no table entry, code or scale byte of a 16-key
+    // group outside [klo, kend).  A wave computes the tiles that meet its own rows' band [wlo, whi) and only loads and meets the
+    // barrier on the others.
     // (wl, wr <= 2^30, coff < 2^28, a token < 2^28: the sums stay inside an int)
     const int wr0 = pr0 + 32 * w;
     const bool wave_on = wr0 < rows;
     const int qlo = (wave_on ? wr0 : pr0) / G, qhi = (min(wr0 + 32, rows) - 1) / G;
     const int qlo_wg = pr0 / G, qhi_wg = (min(pr0 + 128, rows) - 1) / G;
-    const int kend = max(0, min(nk, qhi_wg + coff + md.wr + 1));
-    const int klo = max(0, qlo_wg + coff - md.wl);
-    const int whi = !wave_on ? 0 : max(0, min(nk, qhi + coff + md.wr + 1));
-    const int wlo = max(0, qlo + coff - md.wl);
+    const int kend = MOD ? max(0, min(nk, qhi_wg + coff + md.wr + 1)) : p.causal ? max(0, min(nk, qhi_wg + coff + 1)) : nk;
+    const int klo = MOD ? max(0, qlo_wg + coff - md.wl) : 0;
+    const int whi = !wave_on ? 0 : MOD ? max(0, min(nk, qhi + coff + md.wr + 1)) : p.causal ? max(0, min(nk, qhi + coff + 1)) : nk;
+    const int wlo = MOD ? max(0, qlo + coff - md.wl) : 0;
     const int t_lo = klo / KT, t_hi = (kend + KT - 1) / KT;      // (t_hi <= t_lo: no visible key, the ring below runs no tile)
 
-    // this lane's query row: token qi, query head hd; it sees keys [rlo, rhi]
+    // this lane's query row: token qi, query head hd; it sees keys [rlo, rhi] (rlo: MOD alone)
     const int pr = wr0 + r;
     const bool valid = pr < rows;
     // (a padding row takes the wave's first token: its scores are masked like a real row's, and nothing of it is stored)
     const int qi = valid ? pr / G : qlo, hd = hk * G + (valid ? pr - qi * G : 0);
-    const int rhi = min(min(qi + coff + md.wr, nk - 1), kend - 1), rlo = qi + coff - md.wl;
+    const int rhi = MOD ? min(min(qi + coff + md.wr, nk - 1), kend - 1) : min(p.causal ? qi + coff : nk - 1, kend - 1);
+    const int rlo = qi + coff - md.wl;
 
     i32x8_t qb[2];
     {
@@ -395,7 +140,7 @@ __global__ __launch_bounds__(256, 2) void fp4kv_prefill_mod_kernel(const Fp4Pref
     const float kd = p.kds ? p.kds[b * p.kds_bs + hk] : 1.f;
     const float vd = p.vds ? p.vds[b * p.vds_bs + hk] : 1.f;
     const float f = (p.c_log2 * qd) * kd;                         // the one score factor of this workgroup, > 0
-    const bool capped = md.cap2 != 0.f;
+    const bool capped = MOD && md.cap2 != 0.f;
     const float ck = f * md.cap_k;
     const float fe = capped ? 1.f : f;                            // the factor of what the accumulators hold after the cap
 
@@ -406,7 +151,7 @@ __global__ __launch_bounds__(256, 2) void fp4kv_prefill_mod_kernel(const Fp4Pref
     // the group's table entry, -1 where the group lies outside [klo, kend) (no entry is read there)
     auto fetch_page = [&](int t) -> int {
         const int key0 = t * KT + 16 * w;
-        return key0 < kend && key0 + 16 > klo ? tbl[key0 / p.ps] : -1;
+        return key0 < kend && (!MOD || key0 + 16 > klo) ? tbl[key0 / p.ps] : -1;
     };
     auto load_tile = [&](int t, int pg) -> Fp4Staged {
         Fp4Staged st;
@@ -414,7 +159,7 @@ __global__ __launch_bounds__(256, 2) void fp4kv_prefill_mod_kernel(const Fp4Pref
         st.v[0] = st.v[1] = st.v[2] = st.v[3] = 0u;
         st.s = lane < 16 ? 0x7f7f7f7fu : 127u;
         const int key0 = t * KT + 16 * w;
-        if (key0 >= kend || key0 + 16 <= klo || (unsigned)pg >= (unsigned)p.nblk) return st;      // (wave-uniform)
+        if (key0 >= kend || (MOD && key0 + 16 <= klo) || (unsigned)pg >= (unsigned)p.nblk) return st;      // (wave-uniform)
         const long long sl = key0 % p.ps;
         const uint8_t* kp = p.kc + pg * p.kc_bs + sl * p.kc_ts + hk * HB;
         const uint8_t* vp = p.vc + pg * p.vc_bs + sl * p.vc_ts + hk * HB + 4 * rd;
@@ -484,7 +229,7 @@ __global__ __launch_bounds__(256, 2) void fp4kv_prefill_mod_kernel(const Fp4Pref
             sacc[kb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(k1a, qb[1], sacc[kb], kFp4, 0, 0, sc1, 0, 127);
         }
 
-        // the softcap (before the mask): the capped score in log2 units, one exp2 and one rcp an element
+        // softcap (before the mask), as in fp4kv_split_kernel: the capped score in log2 units replaces s f, one exp2 and one rcp an element
         if (capped) {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
@@ -495,9 +240,10 @@ __global__ __launch_bounds__(256, 2) void fp4kv_prefill_mod_kernel(const Fp4Pref
                 }
         }
         // the mask, t = (s f or the capped score) + ev, the row maximum over t
-        // (the selects only where the sequence's end, a row's upper bound or a row's lower bound lies inside this key tile: wave-uniform)
-        const bool need_mask = k0 + KT > kend || k0 + KT - 1 > qlo + coff + md.wr;
-        const bool need_lo = k0 < qhi + coff - md.wl;
+        // (the selects only where the sequence's end, a row's upper bound or with a window a row's lower bound lies inside this key
+        // tile: wave-uniform.  A masked key's score is -inf before ev is added: its ev never reaches the joint maximum.)
+        const bool need_mask = k0 + KT > kend || (MOD ? k0 + KT - 1 > qlo + coff + md.wr : p.causal && k0 + KT - 1 > qlo + coff);
+        const bool need_lo = MOD && k0 < qhi + coff - md.wl;
         int ev[2][16];
         float mx = -INFINITY;
 #pragma unroll
@@ -583,18 +329,19 @@ __global__ __launch_bounds__(256, 2) void fp4kv_prefill_mod_kernel(const Fp4Pref
         store_tile(st, (t + 1) & 1);              // (its last readers, of tile t - 1, are behind the barrier)
         st = load_tile(t + 2, pg);
         pg = fetch_page(t + 3);
-        if (t * KT < whi && (t + 1) * KT > wlo) compute(t * KT, t & 1);   // (a tile wholly left or right of the wave's band: skipped)
+        // (a tile wholly right or, with a window, left of the wave's band: skipped)
+        if (t * KT < whi && (!MOD || (t + 1) * KT > wlo)) compute(t * KT, t & 1);
         __syncthreads();
     }
 
     // ---- epilogue: O^T register i of block dvb is channel 32 dvb + 4 h + (i & 3) + 8 (i >> 2) of the lane's query row
     const float l_tot = l_run + wave_half_swap(l_run);
     if (!valid) return;
-    // the sink joins here, once per row, after the last tile: a softmax column with a zero value (it multiplies no V)
-    const float snk = md.sinks ? md.sinks[hd % md.sink_heads] : -INFINITY;
+    // sinks: the sink joins here, once per row, after the last tile: a softmax column with a zero value (it multiplies no V)
+    const float snk = MOD && md.sinks ? md.sinks[hd % md.sink_heads] : -INFINITY;
     bool dead;
     float inv, lse_v;
-    if (snk != -INFINITY) {
+    if (snk != -INFINITY) {                              // ex_sink_norm is finite at +-1e4
         float iv;
         ex_sink_norm(m_run * 0.6931471805599453f, l_tot, snk, iv, lse_v);
         dead = false;                                    // (no visible key: iv = 0, lse = sink)
@@ -623,7 +370,7 @@ __global__ __launch_bounds__(256, 2) void fp4kv_prefill_mod_kernel(const Fp4Pref
 }  // namespace
 
 // md: null for fa_fp4_forward_varlen; else the featured call's kernel arguments
-static hipError_t launch_fp4_prefill_t(const Fp4VarlenArgs& a, const Fp4PfMod* md, hipStream_t st) {
+static hipError_t launch_fp4_prefill_t(const Fp4VarlenArgs& a, const KvqModSinks* md, hipStream_t st) {
     Fp4PrefillParams p;
     p.q = (const uint8_t*)a.q; p.kc = (const uint8_t*)a.c.k_cache; p.ksc = (const uint8_t*)a.c.k_scale;
     p.vc = (const uint8_t*)a.c.v_cache; p.vsc = (const uint8_t*)a.c.v_scale;
@@ -639,17 +386,14 @@ static hipError_t launch_fp4_prefill_t(const Fp4VarlenArgs& a, const Fp4PfMod* m
     p.c_log2 = a.scale * 1.4426950408889634f;
     const unsigned row_tiles = (unsigned)((a.max_seqlen_q * p.G + 127) / 128);
     const dim3 grid(row_tiles, (unsigned)a.c.heads_kv, (unsigned)a.batch);
-    if (md) {
-        route_hit(ROUTE_FP4KV_PREFILL_MOD);
-        ProfScope ps(K_FP4KV_PREFILL_MOD, st);
-        if (a.dtype == 2) hipLaunchKernelGGL((fp4kv_prefill_mod_kernel<bf16_tag>), grid, dim3(256), 0, st, p, *md);
-        else hipLaunchKernelGGL((fp4kv_prefill_mod_kernel<f16_tag>), grid, dim3(256), 0, st, p, *md);
-        return hipGetLastError();
-    }
-    route_hit(ROUTE_FP4KV_PREFILL);
-    ProfScope ps(K_FP4KV_PREFILL, st);
-    if (a.dtype == 2) hipLaunchKernelGGL((fp4kv_prefill_kernel<bf16_tag>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((fp4kv_prefill_kernel<f16_tag>), grid, dim3(256), 0, st, p);
+    route_hit(md ? ROUTE_FP4KV_PREFILL_MOD : ROUTE_FP4KV_PREFILL);
+    ProfScope ps(md ? K_FP4KV_PREFILL_MOD : K_FP4KV_PREFILL, st);
+    auto launch = [&](auto... mod) {
+        if (a.dtype == 2) hipLaunchKernelGGL((fp4kv_prefill_kernel<bf16_tag, decltype(mod)...>), grid, dim3(256), 0, st, p, mod...);
+        else hipLaunchKernelGGL((fp4kv_prefill_kernel<f16_tag, decltype(mod)...>), grid, dim3(256), 0, st, p, mod...);
+    };
+    if (md) launch(*md);
+    else launch();
     return hipGetLastError();
 }
 
@@ -657,13 +401,7 @@ hipError_t launch_fp4_prefill(const Fp4VarlenArgs& a, hipStream_t st) { return l
 
 hipError_t launch_fp4_prefill_mod(const Fp4VarlenArgs& a, const Fp8Mod& m, hipStream_t st) {
     if (!m.any()) return launch_fp4_prefill(a, st);      // the parent call, launch for launch
-    Fp4PfMod md;
-    md.wl = m.window_left >= 0 ? (int)std::min<int64_t>(m.window_left, kWinNone) : kWinNone;
-    md.wr = a.causal ? 0 : (m.window_right >= 0 ? (int)std::min<int64_t>(m.window_right, kWinNone) : kWinNone);
-    md.cap_k = m.softcap > 0.0 ? (float)(2.0 / m.softcap) : 0.f;
-    md.cap2 = m.softcap > 0.0 ? (float)(m.softcap * 1.4426950408889634) : 0.f;
-    md.sinks = m.sinks;
-    md.sink_heads = (int)(m.sink_heads > 0 ? m.sink_heads : 1);
+    const KvqModSinks md{kvq_mod_args(m, a.causal != 0), m.sinks, (int)(m.sink_heads > 0 ? m.sink_heads : 1)};
     return launch_fp4_prefill_t(a, &md, st);
 }
 

@@ -41,19 +41,11 @@
 // Addressing: 64-bit bases per 16-key group (batch element or page, first token of the group), 32-bit offsets inside them.
 // A tile that lies whole below the split's end on pages inside the pool takes a wave-uniform path without the per-lane selects and
 // without the mask: with them on every tile the loads of a tile were not issued together (profiles/fp8_kvcache.md, 2.6 x the time).
-#include <algorithm>
-
-#include "fa_common.h"
-#include "fa_ex_common.h"
-#include "fa_kernels.h"
-#include "fa_decode_common.h"   // kv_cu_range, kPlseFill: the packed calls
+#include "fa_kvq_common.h"   // the vector types, transpose4x4, KvqMod and its fill, the launch ladder
 
 namespace fa {
 
 namespace {
-
-typedef int i32x8_t __attribute__((ext_vector_type(8)));
-typedef long long i64x4_t __attribute__((ext_vector_type(4)));   // four group bases, held as values (an array becomes an indexed scratch slot)
 
 struct Fp8KvParams {
     const uint8_t *q, *kc, *vc;
@@ -69,17 +61,6 @@ struct Fp8KvParams {
     int hq, hkv, G, nq, cap, rows, causal;
     float c_log2;                         // float(softmax_scale) * log2(e)
 };
-
-// 4 x 4 byte transpose: x[c] holds bytes (d0, d1, d2, d3) of key c; t[dd] gets byte dd of keys 0 .. 3 (key 0 in the low byte).
-// v_perm_b32 selects bytes 0 .. 3 from its second source and 4 .. 7 from its first.
-__device__ __forceinline__ void transpose4x4(const uint32_t (&x)[4], uint32_t (&t)[4]) {
-    const uint32_t lo01 = __builtin_amdgcn_perm(x[1], x[0], 0x05010400u), hi01 = __builtin_amdgcn_perm(x[1], x[0], 0x07030602u);
-    const uint32_t lo23 = __builtin_amdgcn_perm(x[3], x[2], 0x05010400u), hi23 = __builtin_amdgcn_perm(x[3], x[2], 0x07030602u);
-    t[0] = __builtin_amdgcn_perm(lo23, lo01, 0x05040100u);
-    t[1] = __builtin_amdgcn_perm(lo23, lo01, 0x07060302u);
-    t[2] = __builtin_amdgcn_perm(hi23, hi01, 0x05040100u);
-    t[3] = __builtin_amdgcn_perm(hi23, hi01, 0x07060302u);
-}
 
 // byte offset of 16-byte chunk ch of head-dim row `row` in the V^T image: 64-byte rows, 16 bytes of padding after every four
 // Head dims 64 and 256 (fp8kv_split_mod_kernel<Tag, PAGED, D>) KEEP this padding rule: the image is D such
@@ -333,14 +314,13 @@ __global__ __launch_bounds__(64, 2) void fp8kv_split_kernel(const Fp8KvParams p)
 }
 
 
-// What fp8kv_split_mod_kernel takes beside Fp8KvParams (fa_fp8_forward_kvcache_mod)
-struct Fp8KvMod {
-    int wl, wr;                           // token i sees keys [i + coff - wl, i + coff + wr]; kWinNone: unbounded, wr = 0 if causal
-    float cap_k, cap2;                    // 2 / softcap, softcap * log2(e); cap2 == 0: no softcap
-};
-
-// fp8kv_split_kernel's text (DUPLICATED rather than shared: as one body with the features in discarded `if constexpr` branches
-// fp8kv_split_kernel's instructions changed) with, as wave-uniform run-time switches:
+// fp8kv_split_kernel's text with KvqMod (fa_kvq_common.h; fa_fp8_forward_kvcache_mod) as a second kernel
+// argument.  DUPLICATED: one template fp8kv_split_kernel<Tag, PAGED, D, Mod...> with the plain instantiation's argument list kept by
+// an argument pack, as the MXFP4 readers are merged, was tried, and tools/kernel_diff.py --census showed 24 identical, 4 differ: the
+// four plain kernels at equal instruction counts (2162 / 2315 / 2305 / 2457), registers (226 / 225 VGPRs) and hot loop (1005 / 1226
+// instructions, 12 MFMAs), with a dozen address instructions of the prologue in another order.  The cause is the one-round
+// `for (dw)` loop of the V transpose: without it the plain kernels are identical and the head-dim ones (d = 64, 256) differ, and
+// no single text gave both (profiles/kvq_merge.md).  The features, as wave-uniform run-time switches:
 //   window   the tile's keys are [lo, hi) with lo the first 64-key tile some row of the 32 sees, and the splits cut [lo, hi): no
 //            table entry, K byte or V byte below lo is read.  The mask takes the row's lower bound beside its upper one on a
 //            tile that bound crosses.
@@ -359,7 +339,7 @@ struct Fp8KvPacked {
 };
 
 template <typename Tag, bool PAGED, int D = 128, typename... Packed>
-__global__ __launch_bounds__(64, D == 256 ? 1 : 2) void fp8kv_split_mod_kernel(const Fp8KvParams p, const Fp8KvMod md, const Packed... pk) {
+__global__ __launch_bounds__(64, D == 256 ? 1 : 2) void fp8kv_split_mod_kernel(const Fp8KvParams p, const KvqMod md, const Packed... pk) {
     constexpr bool PACKED = sizeof...(Packed) != 0;
     static_assert(sizeof...(Packed) <= 1, "PACKED: (Fp8KvPacked) follows");
     constexpr int KT = 64, NDV = D / 32, NMQ = D / 64;
@@ -663,8 +643,9 @@ int64_t fp8kv_split_len(int64_t cache_len, int64_t seqlen_q, int causal, const F
     return std::min(cache_len, std::min<int64_t>(m.window_left, kWinNone) + std::min<int64_t>(right, kWinNone) + seqlen_q);
 }
 
-// md: null for fa_fp8_forward_kvcache; else the featured call's kernel arguments, with its sinks (null: none)
-static hipError_t launch_fp8_kvcache_t(const Fp8KvArgs& a, const Fp8KvMod* md, const float* sinks, int sink_heads, hipStream_t st) {
+// The kernel parameters of a call.  packed (cu_seqlens_q): o has total_q * H_q rows, q no batch stride, and nq is the host's bound
+// on a sequence's tokens (the kernel takes its own nq and rows).
+static Fp8KvParams fp8kv_make_params(const Fp8KvArgs& a, bool packed) {
     Fp8KvParams p;
     p.q = (const uint8_t*)a.q; p.kc = (const uint8_t*)a.k_cache; p.vc = (const uint8_t*)a.v_cache;
     p.o = (uint16_t*)a.o; p.lse = a.lse;
@@ -672,54 +653,46 @@ static hipError_t launch_fp8_kvcache_t(const Fp8KvArgs& a, const Fp8KvMod* md, c
     p.qds_bs = a.qds_bs; p.kds_bs = a.kds_bs; p.vds_bs = a.vds_bs;
     p.seqlens = a.cache_seqlens; p.table = a.block_table; p.bidx = a.cache_batch_idx;
     p.tbl_rs = a.table_row_stride; p.nblk = (int)a.num_blocks; p.ps = (int)a.page_size; p.bcache = (int)a.cache_batch;
-    p.q_bs = a.q_bs; p.kc_bs = a.kc_bs; p.vc_bs = a.vc_bs;
+    p.q_bs = packed ? 0 : a.q_bs; p.kc_bs = a.kc_bs; p.vc_bs = a.vc_bs;
     p.q_ts = (int)a.q_ts; p.kc_ts = (int)a.kc_ts; p.vc_ts = (int)a.vc_ts;
     p.hq = (int)a.heads_q; p.hkv = (int)a.heads_kv; p.G = (int)(a.heads_q / a.heads_kv);
-    p.nq = (int)a.seqlen_q; p.cap = (int)a.cache_len; p.rows = p.G * p.nq; p.causal = a.causal != 0;
+    p.nq = (int)(packed ? a.max_seqlen_q : a.seqlen_q); p.cap = (int)a.cache_len; p.rows = p.G * p.nq; p.causal = a.causal != 0;
     p.c_log2 = a.scale * 1.4426950408889634f;
-    const int S = (int)a.num_splits;
     // workspace (S > 1): the O partials, then the lse partials, each rounded up to 256 bytes (kv_workspace_bytes)
-    const size_t q_rows = (size_t)a.batch * a.heads_q * a.seqlen_q;
+    const size_t q_rows = packed ? (size_t)a.total_q * a.heads_q : (size_t)a.batch * a.heads_q * a.seqlen_q, S = (size_t)a.num_splits;
     p.po = (float*)a.workspace;
     p.plse = S > 1 ? (float*)((char*)a.workspace + ((q_rows * S * (size_t)a.d * 4 + 255) & ~(size_t)255)) : nullptr;
+    return p;
+}
+
+// one launch of fp8kv_split_mod_kernel<o's dtype, paged, a.d, Packed...>
+template <typename... Packed>
+static void fp8kv_launch_mod(const Fp8KvArgs& a, const dim3 grid, hipStream_t st, const Fp8KvParams& p, const KvqMod& md, const Packed&... pk) {
+    auto launch = [&](auto d_c) {
+        kvq_dispatch(a.dtype, a.block_table != nullptr, [&](auto tag, auto paged) {
+            hipLaunchKernelGGL((fp8kv_split_mod_kernel<decltype(tag), decltype(paged)::value, decltype(d_c)::value, Packed...>), grid, dim3(64), 0, st,
+                               p, md, pk...);
+        });
+    };
+    if (a.d == 64) launch(std::integral_constant<int, 64>{});
+    else if (a.d == 128) launch(std::integral_constant<int, 128>{});
+    else launch(std::integral_constant<int, 256>{});
+}
+
+// md: null for fa_fp8_forward_kvcache; else the featured call's kernel arguments, with its sinks (null: none)
+static hipError_t launch_fp8_kvcache_t(const Fp8KvArgs& a, const KvqMod* md, const float* sinks, int sink_heads, hipStream_t st) {
+    const Fp8KvParams p = fp8kv_make_params(a, false);
+    const int S = (int)a.num_splits;
     const dim3 grid((unsigned)S, (unsigned)(fp8kv_row_tiles(a.heads_q, a.heads_kv, a.seqlen_q) * p.hkv), (unsigned)a.batch);
-    if (a.d != 128) {                                    // launch_fp8_kvcache_hdim: md is never null here
-        route_hit(ROUTE_FP8KV_SPLIT_HDIM);
-        ProfScope ps(K_FP8KV_SPLIT_HDIM, st);
-        const bool paged = a.block_table != nullptr;
-        auto launch = [&](auto d_c) {
-            constexpr int DD = decltype(d_c)::value;
-            if (a.dtype == 2) {
-                if (paged) hipLaunchKernelGGL((fp8kv_split_mod_kernel<bf16_tag, true, DD>), grid, dim3(64), 0, st, p, *md);
-                else hipLaunchKernelGGL((fp8kv_split_mod_kernel<bf16_tag, false, DD>), grid, dim3(64), 0, st, p, *md);
-            } else {
-                if (paged) hipLaunchKernelGGL((fp8kv_split_mod_kernel<f16_tag, true, DD>), grid, dim3(64), 0, st, p, *md);
-                else hipLaunchKernelGGL((fp8kv_split_mod_kernel<f16_tag, false, DD>), grid, dim3(64), 0, st, p, *md);
-            }
-        };
-        if (a.d == 64) launch(std::integral_constant<int, 64>{});
-        else launch(std::integral_constant<int, 256>{});
-    } else if (md) {
-        route_hit(ROUTE_FP8KV_SPLIT_MOD);
-        ProfScope ps(K_FP8KV_SPLIT_MOD, st);
-        const bool paged = a.block_table != nullptr;
-        if (a.dtype == 2) {
-            if (paged) hipLaunchKernelGGL((fp8kv_split_mod_kernel<bf16_tag, true>), grid, dim3(64), 0, st, p, *md);
-            else hipLaunchKernelGGL((fp8kv_split_mod_kernel<bf16_tag, false>), grid, dim3(64), 0, st, p, *md);
-        } else {
-            if (paged) hipLaunchKernelGGL((fp8kv_split_mod_kernel<f16_tag, true>), grid, dim3(64), 0, st, p, *md);
-            else hipLaunchKernelGGL((fp8kv_split_mod_kernel<f16_tag, false>), grid, dim3(64), 0, st, p, *md);
-        }
+    if (md) {                                            // (launch_fp8_kvcache_hdim, a.d != 128: md is never null)
+        route_hit(a.d != 128 ? ROUTE_FP8KV_SPLIT_HDIM : ROUTE_FP8KV_SPLIT_MOD);
+        ProfScope ps(a.d != 128 ? K_FP8KV_SPLIT_HDIM : K_FP8KV_SPLIT_MOD, st);
+        fp8kv_launch_mod(a, grid, st, p, *md);
     } else {
         ProfScope ps(K_FP8KV_SPLIT, st);
-        const bool paged = a.block_table != nullptr;
-        if (a.dtype == 2) {
-            if (paged) hipLaunchKernelGGL((fp8kv_split_kernel<bf16_tag, true>), grid, dim3(64), 0, st, p);
-            else hipLaunchKernelGGL((fp8kv_split_kernel<bf16_tag, false>), grid, dim3(64), 0, st, p);
-        } else {
-            if (paged) hipLaunchKernelGGL((fp8kv_split_kernel<f16_tag, true>), grid, dim3(64), 0, st, p);
-            else hipLaunchKernelGGL((fp8kv_split_kernel<f16_tag, false>), grid, dim3(64), 0, st, p);
-        }
+        kvq_dispatch(a.dtype, a.block_table != nullptr, [&](auto tag, auto paged) {
+            hipLaunchKernelGGL((fp8kv_split_kernel<decltype(tag), decltype(paged)::value>), grid, dim3(64), 0, st, p);
+        });
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || S == 1) return e;
@@ -729,20 +702,10 @@ static hipError_t launch_fp8_kvcache_t(const Fp8KvArgs& a, const Fp8KvMod* md, c
 
 hipError_t launch_fp8_kvcache(const Fp8KvArgs& a, hipStream_t st) { return launch_fp8_kvcache_t(a, nullptr, nullptr, 0, st); }
 
-// the featured kernel's arguments of an Fp8Mod (one that is not any(): no window, no cap)
-static Fp8KvMod fp8kv_mod_args(const Fp8KvArgs& a, const Fp8Mod& m) {
-    Fp8KvMod md;
-    md.wl = m.window_left >= 0 ? (int)std::min<int64_t>(m.window_left, kWinNone) : kWinNone;
-    md.wr = a.causal ? 0 : (m.window_right >= 0 ? (int)std::min<int64_t>(m.window_right, kWinNone) : kWinNone);
-    md.cap_k = m.softcap > 0.0 ? (float)(2.0 / m.softcap) : 0.f;
-    md.cap2 = m.softcap > 0.0 ? (float)(m.softcap * 1.4426950408889634) : 0.f;
-    return md;
-}
-
 hipError_t launch_fp8_kvcache_mod(const Fp8KvArgs& a, const Fp8Mod& m, hipStream_t st) {
     if (!m.any()) return launch_fp8_kvcache(a, st);     // the parent call, launch for launch
     if (m.sinks && a.num_splits < 2) return hipErrorInvalidValue;   // (the C layer raises a sink call's S to 2: the sink joins in the combine)
-    const Fp8KvMod md = fp8kv_mod_args(a, m);
+    const KvqMod md = kvq_mod_args(m, a.causal != 0);
     return launch_fp8_kvcache_t(a, &md, m.sinks, (int)(m.sink_heads > 0 ? m.sink_heads : 1), st);
 }
 
@@ -751,7 +714,7 @@ hipError_t launch_fp8_kvcache_mod(const Fp8KvArgs& a, const Fp8Mod& m, hipStream
 hipError_t launch_fp8_kvcache_hdim(const Fp8KvArgs& a, const Fp8Mod& m, hipStream_t st) {
     if (a.d == 128) return launch_fp8_kvcache_mod(a, m, st);
     if (m.sinks && a.num_splits < 2) return hipErrorInvalidValue;
-    const Fp8KvMod md = fp8kv_mod_args(a, m);
+    const KvqMod md = kvq_mod_args(m, a.causal != 0);
     return launch_fp8_kvcache_t(a, &md, m.sinks, (int)(m.sink_heads > 0 ? m.sink_heads : 1), st);
 }
 
@@ -764,47 +727,18 @@ hipError_t launch_fp8_kvcache_varlen(const Fp8KvArgs& a, const Fp8Mod& m, hipStr
     if (a.total_q <= 0 || a.max_seqlen_q <= 0) return hipSuccess;
     const int S = (int)a.num_splits;
     if (m.sinks && S < 2) return hipErrorInvalidValue;
-    Fp8KvArgs pa = a;
-    pa.seqlen_q = a.max_seqlen_q;                        // what the window's right bound is canonicalised against (fp8kv_mod_args)
-    const Fp8KvMod md = fp8kv_mod_args(pa, m);
-    Fp8KvParams p;
-    p.q = (const uint8_t*)a.q; p.kc = (const uint8_t*)a.k_cache; p.vc = (const uint8_t*)a.v_cache;
-    p.o = (uint16_t*)a.o; p.lse = a.lse;
-    p.qds = a.q_descale; p.kds = a.k_descale; p.vds = a.v_descale;
-    p.qds_bs = a.qds_bs; p.kds_bs = a.kds_bs; p.vds_bs = a.vds_bs;
-    p.seqlens = a.cache_seqlens; p.table = a.block_table; p.bidx = a.cache_batch_idx;
-    p.tbl_rs = a.table_row_stride; p.nblk = (int)a.num_blocks; p.ps = (int)a.page_size; p.bcache = (int)a.cache_batch;
-    p.q_bs = 0; p.kc_bs = a.kc_bs; p.vc_bs = a.vc_bs;
-    p.q_ts = (int)a.q_ts; p.kc_ts = (int)a.kc_ts; p.vc_ts = (int)a.vc_ts;
-    p.hq = (int)a.heads_q; p.hkv = (int)a.heads_kv; p.G = (int)(a.heads_q / a.heads_kv);
-    p.nq = (int)a.max_seqlen_q; p.cap = (int)a.cache_len; p.rows = p.G * p.nq; p.causal = a.causal != 0;   // (nq, rows: the kernel takes its own)
-    p.c_log2 = a.scale * 1.4426950408889634f;
-    const size_t q_rows = (size_t)a.total_q * a.heads_q;
-    p.po = (float*)a.workspace;
-    p.plse = S > 1 ? (float*)((char*)a.workspace + ((q_rows * S * (size_t)a.d * 4 + 255) & ~(size_t)255)) : nullptr;
+    const KvqMod md = kvq_mod_args(m, a.causal != 0);
+    const Fp8KvParams p = fp8kv_make_params(a, true);
     const Fp8KvPacked pk{a.cu_seqlens_q, (int)a.total_q, (int)a.max_seqlen_q};
     if (S > 1) {
-        const hipError_t e = hipMemsetAsync(p.plse, kPlseFill, q_rows * S * 4, st);
+        const hipError_t e = hipMemsetAsync(p.plse, kPlseFill, (size_t)a.total_q * a.heads_q * S * 4, st);
         if (e != hipSuccess) return e;
     }
     const dim3 grid((unsigned)S, (unsigned)(fp8kv_row_tiles(a.heads_q, a.heads_kv, a.max_seqlen_q) * p.hkv), (unsigned)a.batch);
     {
         route_hit(ROUTE_FP8KV_SPLIT_VARLEN);
         ProfScope ps(K_FP8KV_SPLIT_VARLEN, st);
-        const bool paged = a.block_table != nullptr;
-        auto launch = [&](auto d_c) {
-            constexpr int DD = decltype(d_c)::value;
-            if (a.dtype == 2) {
-                if (paged) hipLaunchKernelGGL((fp8kv_split_mod_kernel<bf16_tag, true, DD, Fp8KvPacked>), grid, dim3(64), 0, st, p, md, pk);
-                else hipLaunchKernelGGL((fp8kv_split_mod_kernel<bf16_tag, false, DD, Fp8KvPacked>), grid, dim3(64), 0, st, p, md, pk);
-            } else {
-                if (paged) hipLaunchKernelGGL((fp8kv_split_mod_kernel<f16_tag, true, DD, Fp8KvPacked>), grid, dim3(64), 0, st, p, md, pk);
-                else hipLaunchKernelGGL((fp8kv_split_mod_kernel<f16_tag, false, DD, Fp8KvPacked>), grid, dim3(64), 0, st, p, md, pk);
-            }
-        };
-        if (a.d == 64) launch(std::integral_constant<int, 64>{});
-        else if (a.d == 128) launch(std::integral_constant<int, 128>{});
-        else launch(std::integral_constant<int, 256>{});
+        fp8kv_launch_mod(a, grid, st, p, md, pk);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || S == 1) return e;
@@ -813,3 +747,4 @@ hipError_t launch_fp8_kvcache_varlen(const Fp8KvArgs& a, const Fp8Mod& m, hipStr
 }
 
 }  // namespace fa
+

@@ -618,7 +618,7 @@ struct Fp4KvArgs {
 };
 hipError_t launch_fp4_kvcache(const Fp4KvArgs& a, hipStream_t st);
 // The featured call (fa_fp4_forward_kvcache_mod): Fp8Mod's window, softcap and sinks over the MXFP4 cache.  A
-// call whose Fp8Mod is not any() is launch_fp4_kvcache; any other runs fp4kv_split_mod_kernel, and with sinks num_splits >= 2 (the
+// call whose Fp8Mod is not any() is launch_fp4_kvcache; any other runs fp4kv_split_kernel<.., KvqMod>, and with sinks num_splits >= 2 (the
 // sink joins in launch_kv_combine_sink).  fp8kv_split_len is the length the split rule takes.
 hipError_t launch_fp4_kvcache_mod(const Fp4KvArgs& a, const Fp8Mod& m, hipStream_t st);
 // Chunked prefill over the paged cache (fa_fp4_prefill.hip; fa_fp4_forward_varlen): packed e4m3 queries, one launch, no workspace.
@@ -636,7 +636,7 @@ struct Fp4VarlenArgs {
     float scale = 0.f;
 };
 hipError_t launch_fp4_prefill(const Fp4VarlenArgs& a, hipStream_t st);
-// The featured call (fa_fp4_forward_varlen_mod): not any() is launch_fp4_prefill; any other runs fp4kv_prefill_mod_kernel, which walks
+// The featured call (fa_fp4_forward_varlen_mod): not any() is launch_fp4_prefill; any other runs fp4kv_prefill_kernel<.., KvqModSinks>, which walks
 // the key tiles of each workgroup's band alone and takes the sink in its epilogue (no workspace).
 hipError_t launch_fp4_prefill_mod(const Fp4VarlenArgs& a, const Fp8Mod& m, hipStream_t st);
 

@@ -1650,11 +1650,11 @@ int fa_fp4_forward_varlen(const void* q, const void* k_cache, const void* k_scal
  *     sinks    float32 device logits in natural-log units, sinks[h % sink_heads] for query head h (sink_heads 1 or heads_q): one more
  *              softmax column with a zero value, never capped or masked.  lse contains it; a row without a visible key gives o = 0,
  *              lse = sink; a head at -inf gives the bits of the call without sinks; +-1e4 stays finite.
- * A masked key's V exponent never reaches the joint maximum.  fa_fp4_forward_kvcache_mod runs fp4kv_split_mod_kernel: a wave's keys
+ * A masked key's V exponent never reaches the joint maximum.  fa_fp4_forward_kvcache_mod runs fp4kv_split_kernel<.., KvqMod>: a wave's keys
  * are [lo, hi), lo the first 64-key tile one of its 32 rows sees and hi its last visible key + 1, the splits cut that range, and
  * nothing outside it is loaded (no code, scale or table entry).  The split rule counts the keys a window can show
  * (fa_fp4_forward_kvcache_workspace_bytes_mod, which is fa_fp8_forward_kvcache_workspace_bytes_mod); with sinks the call runs at
- * least 2 splits, the sink joins in the combine.  fa_fp4_forward_varlen_mod runs fp4kv_prefill_mod_kernel: a workgroup walks the key
+ * least 2 splits, the sink joins in the combine.  fa_fp4_forward_varlen_mod runs fp4kv_prefill_kernel<.., KvqModSinks>: a workgroup walks the key
  * tiles of its 128 rows' band alone, the sink joins in its epilogue, no workspace.  Trust rules and graph replay are the parents';
  * the sink values are read on the device only.
  * Checks: the parent's, in its order, up to num_splits (decode) or the span limits (prefill); then window bounds >= -1, softcap finite
