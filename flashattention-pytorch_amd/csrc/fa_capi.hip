@@ -2861,18 +2861,20 @@ struct Fp8Tensor {
     const void* p = nullptr;
     int64_t bs = 0, hs = 0, ts = 0;
 };
-// What the _mod entry points of the three fp8 calls add, checked by name: window bounds >= -1, a finite softcap >= 0, one sink
-// per query head.  The parents' entry points leave Fp8Mod at its defaults, which is no feature.
-static int fp8_mod_check(const char* who, const fa::Fp8Mod& m, int64_t heads_q) {
+// What the _mod entry points of the fp8 calls and of the two MXFP4 cache readers add, checked by name: window bounds >= -1, a finite
+// softcap >= 0, one sink per query head.  one_sink_ok (the MXFP4 readers): a sink array of one logit for every head is taken as
+// well (the combine and the prefill epilogue read sinks[h % sink_heads]).  The parents' entry points leave Fp8Mod at its defaults,
+// which is no feature.
+static int mod_check(const char* who, const fa::Fp8Mod& m, int64_t heads_q, bool one_sink_ok) {
     if (m.window_left < -1 || m.window_right < -1)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: window (%lld, %lld): each bound must be >= 0, or -1 for unbounded", who,
                     (long long)m.window_left, (long long)m.window_right);
     if (!(m.softcap == m.softcap) || m.softcap < 0.0 || m.softcap > 3.0e38)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: softcap must be a finite number >= 0 (got %g)", who, m.softcap);
     if (m.sinks) {
-        if (m.sink_heads != heads_q)
-            return fail(FA_ERR_INVALID_ARGUMENT, "%s: sink_heads=%lld must be heads_q=%lld (one sink per query head)", who,
-                        (long long)m.sink_heads, (long long)heads_q);
+        if (m.sink_heads != heads_q && !(one_sink_ok && m.sink_heads == 1))
+            return fail(FA_ERR_INVALID_ARGUMENT, one_sink_ok ? "%s: sink_heads=%lld must be 1 or heads_q=%lld (one sink per query head)" :
+                        "%s: sink_heads=%lld must be heads_q=%lld (one sink per query head)", who, (long long)m.sink_heads, (long long)heads_q);
         if ((uintptr_t)m.sinks % 4 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: sinks must be 4-byte aligned", who);
     } else if (m.sink_heads != 0) {
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: sink_heads must be 0 without sinks (got %lld)", who, (long long)m.sink_heads);
@@ -2880,9 +2882,19 @@ static int fp8_mod_check(const char* who, const fa::Fp8Mod& m, int64_t heads_q) 
     return FA_OK;
 }
 
+// the trailing group of every _mod / _hdim / _varlen entry point
+static fa::Fp8Mod fp8_mod(int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads) {
+    fa::Fp8Mod m;
+    m.window_left = window_left; m.window_right = window_right; m.softcap = softcap; m.sinks = sinks; m.sink_heads = sink_heads;
+    return m;
+}
+
+// the head dims of the _hdim (and _varlen) entry points: false for 64, 128 and 256
+static bool fp8_hdim_unsupported(int64_t d) { return d != 64 && d != 128 && d != 256; }
+
 // The head dim of an fp8 call: 128 through the entry points up to _mod, 64 / 128 / 256 through the _hdim ones (`hdim`).
 static int fp8_head_dim_check(const char* who, int64_t d, bool hdim) {
-    if (hdim ? (d != 64 && d != 128 && d != 256) : d != 128)
+    if (hdim ? fp8_hdim_unsupported(d) : d != 128)
         return fail(FA_ERR_UNSUPPORTED, hdim ? "%s: head_dim %lld is not supported (64, 128 or 256)" : "%s: head_dim %lld is not supported (128 only)",
                     who, (long long)d);
     return FA_OK;
@@ -2930,7 +2942,7 @@ static int fp8_forward_impl(const char* who, const Fp8Call& c) {
                         (long long)c.heads_kv);
         if ((uintptr_t)s.p % 4 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: %s must be 4-byte aligned", who, s.name);
     }
-    if (const int rc = fp8_mod_check(who, c.mod, c.heads_q)) return rc;
+    if (const int rc = mod_check(who, c.mod, c.heads_q, false)) return rc;
     // (6) alignment and strides: 16-byte units (q, k, v in bytes, o in 16-bit elements), rows that do not overlap
     if (!aligned16({c.q.p, c.k.p, c.v.p, c.o.p})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: q, k, v and o must be 16-byte aligned", who);
     if ((uintptr_t)c.lse % 4 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: lse must be 4-byte aligned", who);
@@ -2981,8 +2993,29 @@ size_t fa_fp8_forward_workspace_bytes(int64_t batch, int64_t heads_kv, int64_t s
 
 // the parent's size at d = 128; the V^T image is units_kv * tiles * d * 128 + 256 bytes
 size_t fa_fp8_forward_hdim_workspace_bytes(int64_t batch, int64_t heads_kv, int64_t seqlen_k, int64_t head_dim) {
-    if (batch <= 0 || heads_kv <= 0 || seqlen_k <= 0 || (head_dim != 64 && head_dim != 128 && head_dim != 256)) return 0;
+    if (batch <= 0 || heads_kv <= 0 || seqlen_k <= 0 || fp8_hdim_unsupported(head_dim)) return 0;
     return fa::fp8in_workspace_bytes(batch * heads_kv, seqlen_k, head_dim);
+}
+
+// the arguments every fa_fp8_forward* has (ex_call's pattern: an entry point fills the record once and sets its own group)
+static Fp8Call fp8_call(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
+                        const float* v_descale, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_k, int64_t d,
+                        int dtype, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_token_stride, int64_t k_batch_stride,
+                        int64_t k_head_stride, int64_t k_token_stride, int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride,
+                        int64_t o_batch_stride, int64_t o_head_stride, int64_t o_token_stride, int64_t q_descale_batch_stride,
+                        int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    Fp8Call c;
+    c.q.p = q; c.q.bs = q_batch_stride; c.q.hs = q_head_stride; c.q.ts = q_token_stride;
+    c.k.p = k; c.k.bs = k_batch_stride; c.k.hs = k_head_stride; c.k.ts = k_token_stride;
+    c.v.p = v; c.v.bs = v_batch_stride; c.v.hs = v_head_stride; c.v.ts = v_token_stride;
+    c.o.p = o; c.o.bs = o_batch_stride; c.o.hs = o_head_stride; c.o.ts = o_token_stride;
+    c.lse = lse; c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
+    c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
+    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.nq = seqlen_q; c.nk = seqlen_k; c.d = d;
+    c.dtype = dtype; c.causal = causal; c.scale = softmax_scale;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    return c;
 }
 
 int fa_fp8_forward(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
@@ -2992,42 +3025,10 @@ int fa_fp8_forward(const void* q, const void* k, const void* v, void* o, float* 
                    int64_t o_batch_stride, int64_t o_head_stride, int64_t o_token_stride, int64_t q_descale_batch_stride,
                    int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace,
                    size_t workspace_bytes, void* stream) {
-    Fp8Call c;
-    c.q.p = q; c.q.bs = q_batch_stride; c.q.hs = q_head_stride; c.q.ts = q_token_stride;
-    c.k.p = k; c.k.bs = k_batch_stride; c.k.hs = k_head_stride; c.k.ts = k_token_stride;
-    c.v.p = v; c.v.bs = v_batch_stride; c.v.hs = v_head_stride; c.v.ts = v_token_stride;
-    c.o.p = o; c.o.bs = o_batch_stride; c.o.hs = o_head_stride; c.o.ts = o_token_stride;
-    c.lse = lse; c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
-    c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
-    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.nq = seqlen_q; c.nk = seqlen_k; c.d = d;
-    c.dtype = dtype; c.causal = causal; c.scale = softmax_scale;
-    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
-    return fp8_forward_impl("fa_fp8_forward", c);
-}
-
-// the arguments of fa_fp8_forward_mod and fa_fp8_forward_hdim alike (hdim: the head dims 64, 128 and 256)
-static int fp8_forward_mod_entry(const char* who, bool hdim, const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
-        const float* v_descale, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t seqlen_k, int64_t d,
-        int dtype, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_token_stride, int64_t k_batch_stride,
-        int64_t k_head_stride, int64_t k_token_stride, int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride,
-        int64_t o_batch_stride, int64_t o_head_stride, int64_t o_token_stride, int64_t q_descale_batch_stride,
-        int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace,
-        size_t workspace_bytes, void* stream, int64_t window_left, int64_t window_right, double softcap, const float* sinks,
-        int64_t sink_heads) {
-    Fp8Call c;
-    c.hdim = hdim;
-    c.q.p = q; c.q.bs = q_batch_stride; c.q.hs = q_head_stride; c.q.ts = q_token_stride;
-    c.k.p = k; c.k.bs = k_batch_stride; c.k.hs = k_head_stride; c.k.ts = k_token_stride;
-    c.v.p = v; c.v.bs = v_batch_stride; c.v.hs = v_head_stride; c.v.ts = v_token_stride;
-    c.o.p = o; c.o.bs = o_batch_stride; c.o.hs = o_head_stride; c.o.ts = o_token_stride;
-    c.lse = lse; c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
-    c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
-    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.nq = seqlen_q; c.nk = seqlen_k; c.d = d;
-    c.dtype = dtype; c.causal = causal; c.scale = softmax_scale;
-    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
-    c.mod.window_left = window_left; c.mod.window_right = window_right; c.mod.softcap = softcap; c.mod.sinks = sinks;
-    c.mod.sink_heads = sink_heads;
-    return fp8_forward_impl(who, c);
+    return fp8_forward_impl("fa_fp8_forward", fp8_call(q, k, v, o, lse, q_descale, k_descale, v_descale, batch, heads_q, heads_kv, seqlen_q,
+           seqlen_k, d, dtype, q_batch_stride, q_head_stride, q_token_stride, k_batch_stride, k_head_stride, k_token_stride, v_batch_stride,
+           v_head_stride, v_token_stride, o_batch_stride, o_head_stride, o_token_stride, q_descale_batch_stride, k_descale_batch_stride,
+           v_descale_batch_stride, causal, softmax_scale, workspace, workspace_bytes, stream));
 }
 
 int fa_fp8_forward_mod(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
@@ -3038,11 +3039,12 @@ int fa_fp8_forward_mod(const void* q, const void* k, const void* v, void* o, flo
         int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace,
         size_t workspace_bytes, void* stream, int64_t window_left, int64_t window_right, double softcap, const float* sinks,
         int64_t sink_heads) {
-    return fp8_forward_mod_entry("fa_fp8_forward_mod", false, q, k, v, o, lse, q_descale, k_descale, v_descale, batch, heads_q,
-           heads_kv, seqlen_q, seqlen_k, d, dtype, q_batch_stride, q_head_stride, q_token_stride, k_batch_stride, k_head_stride,
-           k_token_stride, v_batch_stride, v_head_stride, v_token_stride, o_batch_stride, o_head_stride, o_token_stride,
-           q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale, workspace, workspace_bytes,
-           stream, window_left, window_right, softcap, sinks, sink_heads);
+    Fp8Call c = fp8_call(q, k, v, o, lse, q_descale, k_descale, v_descale, batch, heads_q, heads_kv, seqlen_q, seqlen_k, d, dtype,
+           q_batch_stride, q_head_stride, q_token_stride, k_batch_stride, k_head_stride, k_token_stride, v_batch_stride, v_head_stride,
+           v_token_stride, o_batch_stride, o_head_stride, o_token_stride, q_descale_batch_stride, k_descale_batch_stride,
+           v_descale_batch_stride, causal, softmax_scale, workspace, workspace_bytes, stream);
+    c.mod = fp8_mod(window_left, window_right, softcap, sinks, sink_heads);
+    return fp8_forward_impl("fa_fp8_forward_mod", c);
 }
 
 int fa_fp8_forward_hdim(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
@@ -3053,11 +3055,12 @@ int fa_fp8_forward_hdim(const void* q, const void* k, const void* v, void* o, fl
         int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace,
         size_t workspace_bytes, void* stream, int64_t window_left, int64_t window_right, double softcap, const float* sinks,
         int64_t sink_heads) {
-    return fp8_forward_mod_entry("fa_fp8_forward_hdim", true, q, k, v, o, lse, q_descale, k_descale, v_descale, batch, heads_q,
-           heads_kv, seqlen_q, seqlen_k, head_dim, dtype, q_batch_stride, q_head_stride, q_token_stride, k_batch_stride, k_head_stride,
-           k_token_stride, v_batch_stride, v_head_stride, v_token_stride, o_batch_stride, o_head_stride, o_token_stride,
-           q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale, workspace, workspace_bytes,
-           stream, window_left, window_right, softcap, sinks, sink_heads);
+    Fp8Call c = fp8_call(q, k, v, o, lse, q_descale, k_descale, v_descale, batch, heads_q, heads_kv, seqlen_q, seqlen_k, head_dim, dtype,
+           q_batch_stride, q_head_stride, q_token_stride, k_batch_stride, k_head_stride, k_token_stride, v_batch_stride, v_head_stride,
+           v_token_stride, o_batch_stride, o_head_stride, o_token_stride, q_descale_batch_stride, k_descale_batch_stride,
+           v_descale_batch_stride, causal, softmax_scale, workspace, workspace_bytes, stream);
+    c.hdim = true; c.mod = fp8_mod(window_left, window_right, softcap, sinks, sink_heads);
+    return fp8_forward_impl("fa_fp8_forward_hdim", c);
 }
 
 // ---- the packed and the paged form of the fp8 call: see include/fa_mi355x.h
@@ -3107,7 +3110,7 @@ static int fp8_forward_varlen_impl(const char* who, const Fp8VarCall& c) {
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: dtype (of o) must be f16 or bf16 (got code %d)", who, c.dtype);
     if (!(c.scale == c.scale) || !scale_ok(c.scale))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale must be finite and > 0", who);
-    if (const int rc = fp8_mod_check(who, c.mod, c.heads_q)) return rc;
+    if (const int rc = mod_check(who, c.mod, c.heads_q, false)) return rc;
     // (6) the pages
     if (paged) {
         if (c.ps < 16 || c.ps % 16 != 0 || c.ps > 65536)
@@ -3196,7 +3199,7 @@ static size_t fp8_varlen_ws(int64_t batch, int64_t heads_kv, int64_t total_k, in
                             int64_t page_block_size, int64_t d, bool hdim) {
     const int64_t kInt = ((int64_t)1 << 31) - 1;
     if (batch <= 0 || heads_kv <= 0 || total_k < 0 || max_seqlen_k < 0 || max_blocks_per_seq < 0 || page_block_size < 0) return 0;
-    if (hdim ? (d != 64 && d != 128 && d != 256) : d != 128) return 0;
+    if (hdim ? fp8_hdim_unsupported(d) : d != 128) return 0;
     if (batch > kInt || total_k > kInt || max_seqlen_k > kInt || max_blocks_per_seq > kInt || page_block_size > 65536) return 0;
     if (page_block_size % 16 != 0) return 0;
     fa::Fp8InVarArgs a;
@@ -3215,6 +3218,29 @@ size_t fa_fp8_forward_varlen_hdim_workspace_bytes(int64_t batch, int64_t heads_k
     return fp8_varlen_ws(batch, heads_kv, total_k, max_seqlen_k, max_blocks_per_seq, page_block_size, head_dim, true);
 }
 
+// the arguments every fa_fp8_forward_varlen* has
+static Fp8VarCall fp8_var_call(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale,
+                               const float* k_descale, const float* v_descale, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k,
+                               const int32_t* block_table, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k,
+                               int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d, int dtype, int64_t q_token_stride, int64_t q_head_stride,
+                               int64_t k_token_stride, int64_t k_head_stride, int64_t v_token_stride, int64_t v_head_stride,
+                               int64_t max_blocks_per_seq, int64_t num_blocks, int64_t page_block_size, int64_t k_page_stride,
+                               int64_t v_page_stride, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
+                               int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    Fp8VarCall c;
+    c.q = q; c.k = k; c.v = v; c.o = o; c.lse = lse; c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
+    c.cu_q = cu_seqlens_q; c.cu_k = cu_seqlens_k; c.block_table = block_table;
+    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.total_q = total_q; c.total_k = total_k; c.max_q = max_seqlen_q;
+    c.max_k = max_seqlen_k; c.d = d; c.dtype = dtype;
+    c.q_ts = q_token_stride; c.q_hs = q_head_stride; c.k_ts = k_token_stride; c.k_hs = k_head_stride; c.v_ts = v_token_stride;
+    c.v_hs = v_head_stride;
+    c.max_blocks = max_blocks_per_seq; c.num_blocks = num_blocks; c.ps = page_block_size; c.k_ps = k_page_stride; c.v_ps = v_page_stride;
+    c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
+    c.causal = causal; c.scale = softmax_scale; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+    return c;
+}
+
 int fa_fp8_forward_varlen(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
                           const float* v_descale, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, const int32_t* block_table,
                           int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q,
@@ -3223,42 +3249,11 @@ int fa_fp8_forward_varlen(const void* q, const void* k, const void* v, void* o, 
                           int64_t page_block_size, int64_t k_page_stride, int64_t v_page_stride, int64_t q_descale_batch_stride,
                           int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace,
                           size_t workspace_bytes, void* stream) {
-    Fp8VarCall c;
-    c.q = q; c.k = k; c.v = v; c.o = o; c.lse = lse; c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
-    c.cu_q = cu_seqlens_q; c.cu_k = cu_seqlens_k; c.block_table = block_table;
-    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.total_q = total_q; c.total_k = total_k; c.max_q = max_seqlen_q;
-    c.max_k = max_seqlen_k; c.d = d; c.dtype = dtype;
-    c.q_ts = q_token_stride; c.q_hs = q_head_stride; c.k_ts = k_token_stride; c.k_hs = k_head_stride; c.v_ts = v_token_stride;
-    c.v_hs = v_head_stride;
-    c.max_blocks = max_blocks_per_seq; c.num_blocks = num_blocks; c.ps = page_block_size; c.k_ps = k_page_stride; c.v_ps = v_page_stride;
-    c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
-    c.causal = causal; c.scale = softmax_scale; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
-    return fp8_forward_varlen_impl("fa_fp8_forward_varlen", c);
-}
-
-// the arguments of fa_fp8_forward_varlen_mod and fa_fp8_forward_varlen_hdim alike (hdim: the head dims 64, 128 and 256)
-static int fp8_forward_varlen_mod_entry(const char* who, bool hdim, const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
-        const float* v_descale, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, const int32_t* block_table, int64_t batch,
-        int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t total_k, int64_t max_seqlen_q, int64_t max_seqlen_k, int64_t d,
-        int dtype, int64_t q_token_stride, int64_t q_head_stride, int64_t k_token_stride, int64_t k_head_stride,
-        int64_t v_token_stride, int64_t v_head_stride, int64_t max_blocks_per_seq, int64_t num_blocks, int64_t page_block_size,
-        int64_t k_page_stride, int64_t v_page_stride, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
-        int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace, size_t workspace_bytes, void* stream,
-        int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads) {
-    Fp8VarCall c;
-    c.hdim = hdim;
-    c.q = q; c.k = k; c.v = v; c.o = o; c.lse = lse; c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
-    c.cu_q = cu_seqlens_q; c.cu_k = cu_seqlens_k; c.block_table = block_table;
-    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.total_q = total_q; c.total_k = total_k; c.max_q = max_seqlen_q;
-    c.max_k = max_seqlen_k; c.d = d; c.dtype = dtype;
-    c.q_ts = q_token_stride; c.q_hs = q_head_stride; c.k_ts = k_token_stride; c.k_hs = k_head_stride; c.v_ts = v_token_stride;
-    c.v_hs = v_head_stride;
-    c.max_blocks = max_blocks_per_seq; c.num_blocks = num_blocks; c.ps = page_block_size; c.k_ps = k_page_stride; c.v_ps = v_page_stride;
-    c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
-    c.causal = causal; c.scale = softmax_scale; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
-    c.mod.window_left = window_left; c.mod.window_right = window_right; c.mod.softcap = softcap; c.mod.sinks = sinks;
-    c.mod.sink_heads = sink_heads;
-    return fp8_forward_varlen_impl(who, c);
+    return fp8_forward_varlen_impl("fa_fp8_forward_varlen", fp8_var_call(q, k, v, o, lse, q_descale, k_descale, v_descale, cu_seqlens_q,
+           cu_seqlens_k, block_table, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype, q_token_stride,
+           q_head_stride, k_token_stride, k_head_stride, v_token_stride, v_head_stride, max_blocks_per_seq, num_blocks, page_block_size,
+           k_page_stride, v_page_stride, q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale,
+           workspace, workspace_bytes, stream));
 }
 
 int fa_fp8_forward_varlen_mod(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
@@ -3269,11 +3264,12 @@ int fa_fp8_forward_varlen_mod(const void* q, const void* k, const void* v, void*
         int64_t k_page_stride, int64_t v_page_stride, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
         int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace, size_t workspace_bytes, void* stream,
         int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads) {
-    return fp8_forward_varlen_mod_entry("fa_fp8_forward_varlen_mod", false, q, k, v, o, lse, q_descale, k_descale, v_descale,
-           cu_seqlens_q, cu_seqlens_k, block_table, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype,
-           q_token_stride, q_head_stride, k_token_stride, k_head_stride, v_token_stride, v_head_stride, max_blocks_per_seq, num_blocks,
-           page_block_size, k_page_stride, v_page_stride, q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride,
-           causal, softmax_scale, workspace, workspace_bytes, stream, window_left, window_right, softcap, sinks, sink_heads);
+    Fp8VarCall c = fp8_var_call(q, k, v, o, lse, q_descale, k_descale, v_descale, cu_seqlens_q, cu_seqlens_k, block_table, batch, heads_q,
+           heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, d, dtype, q_token_stride, q_head_stride, k_token_stride, k_head_stride,
+           v_token_stride, v_head_stride, max_blocks_per_seq, num_blocks, page_block_size, k_page_stride, v_page_stride,
+           q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale, workspace, workspace_bytes, stream);
+    c.mod = fp8_mod(window_left, window_right, softcap, sinks, sink_heads);
+    return fp8_forward_varlen_impl("fa_fp8_forward_varlen_mod", c);
 }
 
 int fa_fp8_forward_varlen_hdim(const void* q, const void* k, const void* v, void* o, float* lse, const float* q_descale, const float* k_descale,
@@ -3284,12 +3280,12 @@ int fa_fp8_forward_varlen_hdim(const void* q, const void* k, const void* v, void
         int64_t k_page_stride, int64_t v_page_stride, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride,
         int64_t v_descale_batch_stride, int causal, double softmax_scale, void* workspace, size_t workspace_bytes, void* stream,
         int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads) {
-    return fp8_forward_varlen_mod_entry("fa_fp8_forward_varlen_hdim", true, q, k, v, o, lse, q_descale, k_descale, v_descale,
-           cu_seqlens_q, cu_seqlens_k, block_table, batch, heads_q, heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, head_dim,
-           dtype, q_token_stride, q_head_stride, k_token_stride, k_head_stride, v_token_stride, v_head_stride, max_blocks_per_seq,
-           num_blocks, page_block_size, k_page_stride, v_page_stride, q_descale_batch_stride, k_descale_batch_stride,
-           v_descale_batch_stride, causal, softmax_scale, workspace, workspace_bytes, stream, window_left, window_right, softcap, sinks,
-           sink_heads);
+    Fp8VarCall c = fp8_var_call(q, k, v, o, lse, q_descale, k_descale, v_descale, cu_seqlens_q, cu_seqlens_k, block_table, batch, heads_q,
+           heads_kv, total_q, total_k, max_seqlen_q, max_seqlen_k, head_dim, dtype, q_token_stride, q_head_stride, k_token_stride,
+           k_head_stride, v_token_stride, v_head_stride, max_blocks_per_seq, num_blocks, page_block_size, k_page_stride, v_page_stride,
+           q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale, workspace, workspace_bytes, stream);
+    c.hdim = true; c.mod = fp8_mod(window_left, window_right, softcap, sinks, sink_heads);
+    return fp8_forward_varlen_impl("fa_fp8_forward_varlen_hdim", c);
 }
 
 // ---- fp8 KV-cache decoding with split-KV (e4m3 q over an e4m3 cache): see include/fa_mi355x.h
@@ -3325,11 +3321,18 @@ static int64_t fp8_kv_splits(int64_t batch, int64_t hq, int64_t hkv, int64_t nq,
 }
 
 // the featured call: the rule sees the keys a window can show instead of the capacity, and sinks raise 1 split to 2 (the sink
-// joins in the combine, which such a call always runs)
+// joins in the combine, which such a call always runs).  nq: of a packed call, max_seqlen_q (the most rows a sequence has)
 static int64_t fp8_kv_splits_mod(int64_t batch, int64_t hq, int64_t hkv, int64_t nq, int64_t cache_len, int64_t num_splits, int causal,
                                  const fa::Fp8Mod& m) {
     const int64_t S = fp8_kv_splits(batch, hq, hkv, nq, fa::fp8kv_split_len(cache_len, nq, causal, m), num_splits);
     return m.sinks && S < 2 ? 2 : S;
+}
+// ... as every featured workspace-size function asks it: by the window bounds and whether there are sinks
+static int64_t fp8_kv_splits_ws(int64_t batch, int64_t hq, int64_t hkv, int64_t nq, int64_t cache_len, int64_t num_splits, int causal,
+                                int64_t window_left, int64_t window_right, int with_sinks) {
+    static const float kSomeSink = 0.0f;   // (the rule asks only whether m.sinks is set)
+    return fp8_kv_splits_mod(batch, hq, hkv, nq, cache_len, num_splits, causal,
+                             fp8_mod(window_left, window_right, 0.0, with_sinks ? &kSomeSink : nullptr, 0));
 }
 
 // What fa_fp8_kvcache_step adds to fa_fp8_forward_kvcache_mod's arguments: the new tokens, the q8 buffer and the rotary tables
@@ -3516,7 +3519,7 @@ static int fp8_kvcache_check(const char* who, const Fp8KvCall& c, const Fp8StepC
     // (9) the splits
     if (c.num_splits < 0 || c.num_splits > 256)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_splits must lie in [0, 256] (got %lld)", who, (long long)c.num_splits);
-    if (const int rc = fp8_mod_check(who, c.mod, c.heads_q)) return rc;
+    if (const int rc = mod_check(who, c.mod, c.heads_q, false)) return rc;
     // (P) the packed group of the _varlen entry points (every other entry point hands nulls and zeros on)
     // (P1) no extent without its array
     if (!packed && (c.total_q != 0 || c.max_seqlen_q != 0))
@@ -3605,14 +3608,15 @@ size_t fa_fp8_forward_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, in
     return fa::kv_workspace_bytes(batch, heads_q, seqlen_q, 128, (int)fp8_kv_splits(batch, heads_q, heads_kv, seqlen_q, cache_len, num_splits));
 }
 
-int fa_fp8_forward_kvcache(const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const float* q_descale,
-                           const float* k_descale, const float* v_descale, const int32_t* cache_seqlens, const int32_t* block_table,
-                           const int32_t* cache_batch_idx, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
-                           int64_t cache_batch, int64_t d, int dtype, int q_dtype, int cache_dtype, int64_t q_batch_stride, int64_t q_token_stride,
-                           int64_t k_batch_stride, int64_t k_token_stride, int64_t v_batch_stride, int64_t v_token_stride,
-                           int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t q_descale_batch_stride,
-                           int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, int64_t num_splits,
-                           void* workspace, size_t workspace_bytes, void* stream) {
+// the arguments every fa_fp8_forward_kvcache* and both steps have
+static Fp8KvCall fp8_kv_call(const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const float* q_descale,
+                             const float* k_descale, const float* v_descale, const int32_t* cache_seqlens, const int32_t* block_table,
+                             const int32_t* cache_batch_idx, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q,
+                             int64_t cache_len, int64_t cache_batch, int64_t d, int dtype, int q_dtype, int cache_dtype, int64_t q_batch_stride,
+                             int64_t q_token_stride, int64_t k_batch_stride, int64_t k_token_stride, int64_t v_batch_stride,
+                             int64_t v_token_stride, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
+                             int64_t q_descale_batch_stride, int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal,
+                             double softmax_scale, int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream) {
     Fp8KvCall c;
     c.q = q; c.k_cache = k_cache; c.v_cache = v_cache; c.o = o; c.lse = lse;
     c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
@@ -3625,7 +3629,22 @@ int fa_fp8_forward_kvcache(const void* q, const void* k_cache, const void* v_cac
     c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
     c.causal = causal; c.scale = softmax_scale; c.num_splits = num_splits;
     c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
-    return fp8_kvcache_impl("fa_fp8_forward_kvcache", c);
+    return c;
+}
+
+int fa_fp8_forward_kvcache(const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const float* q_descale,
+                           const float* k_descale, const float* v_descale, const int32_t* cache_seqlens, const int32_t* block_table,
+                           const int32_t* cache_batch_idx, int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
+                           int64_t cache_batch, int64_t d, int dtype, int q_dtype, int cache_dtype, int64_t q_batch_stride, int64_t q_token_stride,
+                           int64_t k_batch_stride, int64_t k_token_stride, int64_t v_batch_stride, int64_t v_token_stride,
+                           int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t q_descale_batch_stride,
+                           int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, int64_t num_splits,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    return fp8_kvcache_impl("fa_fp8_forward_kvcache", fp8_kv_call(q, k_cache, v_cache, o, lse, q_descale, k_descale, v_descale, cache_seqlens,
+           block_table, cache_batch_idx, batch, heads_q, heads_kv, seqlen_q, cache_len, cache_batch, d, dtype, q_dtype, cache_dtype,
+           q_batch_stride, q_token_stride, k_batch_stride, k_token_stride, v_batch_stride, v_token_stride, block_table_row_stride, num_blocks,
+           page_block_size, q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale, num_splits,
+           workspace, workspace_bytes, stream));
 }
 
 size_t fa_fp8_forward_kvcache_workspace_bytes_mod(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
@@ -3641,39 +3660,9 @@ size_t fa_fp8_forward_kvcache_hdim_workspace_bytes(int64_t batch, int64_t heads_
                                                    int64_t head_dim, int64_t num_splits, int causal, int64_t window_left,
                                                    int64_t window_right, int with_sinks) {
     if (!kv_ws_args_ok(batch, heads_q, heads_kv, seqlen_q, cache_len, head_dim, num_splits) || window_left < -1 || window_right < -1) return 0;
-    if (head_dim != 64 && head_dim != 128 && head_dim != 256) return 0;
-    fa::Fp8Mod m;
-    m.window_left = window_left; m.window_right = window_right;
-    int64_t S = fp8_kv_splits(batch, heads_q, heads_kv, seqlen_q, fa::fp8kv_split_len(cache_len, seqlen_q, causal, m), num_splits);
-    if (with_sinks && S < 2) S = 2;
+    if (fp8_hdim_unsupported(head_dim)) return 0;
+    const int64_t S = fp8_kv_splits_ws(batch, heads_q, heads_kv, seqlen_q, cache_len, num_splits, causal, window_left, window_right, with_sinks);
     return fa::kv_workspace_bytes(batch, heads_q, seqlen_q, head_dim, (int)S);
-}
-
-// the arguments of fa_fp8_forward_kvcache_mod and fa_fp8_forward_kvcache_hdim alike (hdim: the head dims 64, 128 and 256)
-static int fp8_forward_kvcache_mod_entry(const char* who, bool hdim, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const float* q_descale, const float* k_descale,
-        const float* v_descale, const int32_t* cache_seqlens, const int32_t* block_table, const int32_t* cache_batch_idx,
-        int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t cache_batch, int64_t d,
-        int dtype, int q_dtype, int cache_dtype, int64_t q_batch_stride, int64_t q_token_stride, int64_t k_batch_stride,
-        int64_t k_token_stride, int64_t v_batch_stride, int64_t v_token_stride, int64_t block_table_row_stride, int64_t num_blocks,
-        int64_t page_block_size, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride, int64_t v_descale_batch_stride,
-        int causal, double softmax_scale, int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream,
-        int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads) {
-    Fp8KvCall c;
-    c.hdim = hdim;
-    c.q = q; c.k_cache = k_cache; c.v_cache = v_cache; c.o = o; c.lse = lse;
-    c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
-    c.cache_seqlens = cache_seqlens; c.block_table = block_table; c.cache_batch_idx = cache_batch_idx;
-    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.seqlen_q = seqlen_q; c.cache_len = cache_len; c.cache_batch = cache_batch;
-    c.d = d; c.dtype = dtype; c.q_dtype = q_dtype; c.cache_dtype = cache_dtype;
-    c.q_bs = q_batch_stride; c.q_ts = q_token_stride; c.k_bs = k_batch_stride; c.k_ts = k_token_stride; c.v_bs = v_batch_stride;
-    c.v_ts = v_token_stride;
-    c.table_rs = block_table_row_stride; c.num_blocks = num_blocks; c.ps = page_block_size;
-    c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
-    c.causal = causal; c.scale = softmax_scale; c.num_splits = num_splits;
-    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
-    c.mod.window_left = window_left; c.mod.window_right = window_right; c.mod.softcap = softcap; c.mod.sinks = sinks;
-    c.mod.sink_heads = sink_heads;
-    return fp8_kvcache_impl(who, c);
 }
 
 int fa_fp8_forward_kvcache_mod(const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const float* q_descale, const float* k_descale,
@@ -3684,12 +3673,12 @@ int fa_fp8_forward_kvcache_mod(const void* q, const void* k_cache, const void* v
         int64_t page_block_size, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride, int64_t v_descale_batch_stride,
         int causal, double softmax_scale, int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream,
         int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads) {
-    return fp8_forward_kvcache_mod_entry("fa_fp8_forward_kvcache_mod", false, q, k_cache, v_cache, o, lse, q_descale, k_descale,
-           v_descale, cache_seqlens, block_table, cache_batch_idx, batch, heads_q, heads_kv, seqlen_q, cache_len, cache_batch, d, dtype,
-           q_dtype, cache_dtype, q_batch_stride, q_token_stride, k_batch_stride, k_token_stride, v_batch_stride, v_token_stride,
-           block_table_row_stride, num_blocks, page_block_size, q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride,
-           causal, softmax_scale, num_splits, workspace, workspace_bytes, stream, window_left, window_right, softcap, sinks,
-           sink_heads);
+    Fp8KvCall c = fp8_kv_call(q, k_cache, v_cache, o, lse, q_descale, k_descale, v_descale, cache_seqlens, block_table, cache_batch_idx, batch,
+           heads_q, heads_kv, seqlen_q, cache_len, cache_batch, d, dtype, q_dtype, cache_dtype, q_batch_stride, q_token_stride, k_batch_stride,
+           k_token_stride, v_batch_stride, v_token_stride, block_table_row_stride, num_blocks, page_block_size, q_descale_batch_stride,
+           k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale, num_splits, workspace, workspace_bytes, stream);
+    c.mod = fp8_mod(window_left, window_right, softcap, sinks, sink_heads);
+    return fp8_kvcache_impl("fa_fp8_forward_kvcache_mod", c);
 }
 
 int fa_fp8_forward_kvcache_hdim(const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const float* q_descale, const float* k_descale,
@@ -3700,12 +3689,13 @@ int fa_fp8_forward_kvcache_hdim(const void* q, const void* k_cache, const void* 
         int64_t page_block_size, int64_t q_descale_batch_stride, int64_t k_descale_batch_stride, int64_t v_descale_batch_stride,
         int causal, double softmax_scale, int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream,
         int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads) {
-    return fp8_forward_kvcache_mod_entry("fa_fp8_forward_kvcache_hdim", true, q, k_cache, v_cache, o, lse, q_descale, k_descale,
-           v_descale, cache_seqlens, block_table, cache_batch_idx, batch, heads_q, heads_kv, seqlen_q, cache_len, cache_batch, head_dim,
-           dtype, q_dtype, cache_dtype, q_batch_stride, q_token_stride, k_batch_stride, k_token_stride, v_batch_stride, v_token_stride,
-           block_table_row_stride, num_blocks, page_block_size, q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride,
-           causal, softmax_scale, num_splits, workspace, workspace_bytes, stream, window_left, window_right, softcap, sinks,
-           sink_heads);
+    Fp8KvCall c = fp8_kv_call(q, k_cache, v_cache, o, lse, q_descale, k_descale, v_descale, cache_seqlens, block_table, cache_batch_idx, batch,
+           heads_q, heads_kv, seqlen_q, cache_len, cache_batch, head_dim, dtype, q_dtype, cache_dtype, q_batch_stride, q_token_stride,
+           k_batch_stride, k_token_stride, v_batch_stride, v_token_stride, block_table_row_stride, num_blocks, page_block_size,
+           q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale, num_splits, workspace,
+           workspace_bytes, stream);
+    c.hdim = true; c.mod = fp8_mod(window_left, window_right, softcap, sinks, sink_heads);
+    return fp8_kvcache_impl("fa_fp8_forward_kvcache_hdim", c);
 }
 
 // ---- the fp8 decode step (append, rotary and q quantise in front of fa_fp8_forward_kvcache_mod): see include/fa_mi355x.h
@@ -3721,6 +3711,42 @@ size_t fa_fp8_kvcache_step_workspace_bytes(int64_t batch, int64_t heads_q, int64
                                                       window_right, with_sinks);
 }
 
+// what both steps add to the decode call's arguments (fa_fp8_kvcache_step_varlen then sets its packed new keys)
+static Fp8StepCall fp8_step_call(const void* k_new, const void* v_new, int64_t seqlen_new, int64_t k_new_batch_stride,
+                                 int64_t k_new_token_stride, int64_t v_new_batch_stride, int64_t v_new_token_stride, int in_dtype,
+                                 void* q8_out, int64_t q8_batch_stride, int64_t q8_token_stride, const void* rotary_cos,
+                                 const void* rotary_sin, int64_t rotary_cos_row_stride, int64_t rotary_sin_row_stride, int64_t seqlen_ro,
+                                 int64_t rotary_dim, int rotary_interleaved) {
+    Fp8StepCall t;
+    t.k_new = k_new; t.v_new = v_new; t.seqlen_new = seqlen_new; t.kn_bs = k_new_batch_stride; t.kn_ts = k_new_token_stride;
+    t.vn_bs = v_new_batch_stride; t.vn_ts = v_new_token_stride; t.in_dtype = in_dtype;
+    t.q8_out = q8_out; t.q8_bs = q8_batch_stride; t.q8_ts = q8_token_stride;
+    t.rotary_cos = rotary_cos; t.rotary_sin = rotary_sin; t.cos_rs = rotary_cos_row_stride; t.sin_rs = rotary_sin_row_stride;
+    t.seqlen_ro = seqlen_ro; t.rotary_dim = rotary_dim; t.rotary_interleaved = rotary_interleaved;
+    return t;
+}
+
+// fa_fp8_kvcache_step and (c.varlen) fa_fp8_kvcache_step_varlen
+static int fp8_step_impl(const char* who, const Fp8KvCall& c, const Fp8StepCall& t) {
+    bool empty;
+    int64_t S = 1;
+    size_t need = 0;
+    if (const int rc = fp8_kvcache_check(who, c, &t, empty, S, need)) return rc;
+    if (empty) return FA_OK;
+    fa::Fp8StepArgs s;
+    s.kv = fp8_kvcache_args(c, S);
+    s.in_dtype = t.in_dtype; s.k_new = t.k_new; s.v_new = t.v_new; s.seqlen_new = t.seqlen_new;
+    s.kn_bs = t.kn_bs; s.kn_ts = t.kn_ts; s.vn_bs = t.vn_bs; s.vn_ts = t.vn_ts;
+    s.q8_out = t.q8_out; s.q8_bs = t.q8_bs; s.q8_ts = t.q8_ts;
+    s.rotary_cos = t.rotary_cos; s.rotary_sin = t.rotary_sin; s.rotary_cos_rs = t.cos_rs; s.rotary_sin_rs = t.sin_rs;
+    s.rotary_dim = t.rotary_dim; s.rotary_interleaved = t.rotary_interleaved ? 1 : 0;
+    // q token i is rotated at its own position when causal or a window bound was given (fa_ex_forward_kvcache_rotary's rule)
+    s.rotary_q_per_token = (c.causal || c.mod.window_left >= 0 || c.mod.window_right >= 0) ? 1 : 0;
+    s.cu_seqlens_k_new = t.cu_seqlens_k_new; s.total_k_new = t.total_k_new;   // (the padded step: null and 0)
+    const hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+    return launched(who, c.varlen ? fa::launch_fp8_kvcache_step_varlen(s, c.mod, st) : fa::launch_fp8_kvcache_step(s, c.mod, st));
+}
+
 int fa_fp8_kvcache_step(const void* q, void* k_cache, void* v_cache, void* o, float* lse, const float* q_descale, const float* k_descale,
                         const float* v_descale, const int32_t* cache_seqlens, const int32_t* block_table, const int32_t* cache_batch_idx,
                         int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t cache_batch, int64_t d,
@@ -3734,54 +3760,17 @@ int fa_fp8_kvcache_step(const void* q, void* k_cache, void* v_cache, void* o, fl
                         int64_t q8_batch_stride, int64_t q8_token_stride, const void* rotary_cos, const void* rotary_sin,
                         int64_t rotary_cos_row_stride, int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim,
                         int rotary_interleaved) {
-    const char* who = "fa_fp8_kvcache_step";
-    Fp8KvCall c;
-    c.q = q; c.k_cache = k_cache; c.v_cache = v_cache; c.o = o; c.lse = lse;
-    c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
-    c.cache_seqlens = cache_seqlens; c.block_table = block_table; c.cache_batch_idx = cache_batch_idx;
-    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.seqlen_q = seqlen_q; c.cache_len = cache_len; c.cache_batch = cache_batch;
-    c.d = d; c.dtype = dtype; c.q_dtype = q_dtype; c.cache_dtype = cache_dtype;
-    c.q_bs = q_batch_stride; c.q_ts = q_token_stride; c.k_bs = k_batch_stride; c.k_ts = k_token_stride; c.v_bs = v_batch_stride;
-    c.v_ts = v_token_stride;
-    c.table_rs = block_table_row_stride; c.num_blocks = num_blocks; c.ps = page_block_size;
-    c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
-    c.causal = causal; c.scale = softmax_scale; c.num_splits = num_splits;
-    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
-    c.mod.window_left = window_left; c.mod.window_right = window_right; c.mod.softcap = softcap; c.mod.sinks = sinks;
-    c.mod.sink_heads = sink_heads;
-    Fp8StepCall t;
-    t.k_new = k_new; t.v_new = v_new; t.seqlen_new = seqlen_new; t.kn_bs = k_new_batch_stride; t.kn_ts = k_new_token_stride;
-    t.vn_bs = v_new_batch_stride; t.vn_ts = v_new_token_stride; t.in_dtype = in_dtype;
-    t.q8_out = q8_out; t.q8_bs = q8_batch_stride; t.q8_ts = q8_token_stride;
-    t.rotary_cos = rotary_cos; t.rotary_sin = rotary_sin; t.cos_rs = rotary_cos_row_stride; t.sin_rs = rotary_sin_row_stride;
-    t.seqlen_ro = seqlen_ro; t.rotary_dim = rotary_dim; t.rotary_interleaved = rotary_interleaved;
-    bool empty;
-    int64_t S = 1;
-    size_t need = 0;
-    if (const int rc = fp8_kvcache_check(who, c, &t, empty, S, need)) return rc;
-    if (empty) return FA_OK;
-    fa::Fp8StepArgs s;
-    s.kv = fp8_kvcache_args(c, S);
-    s.in_dtype = in_dtype; s.k_new = k_new; s.v_new = v_new; s.seqlen_new = seqlen_new;
-    s.kn_bs = t.kn_bs; s.kn_ts = t.kn_ts; s.vn_bs = t.vn_bs; s.vn_ts = t.vn_ts;
-    s.q8_out = q8_out; s.q8_bs = t.q8_bs; s.q8_ts = t.q8_ts;
-    s.rotary_cos = rotary_cos; s.rotary_sin = rotary_sin; s.rotary_cos_rs = t.cos_rs; s.rotary_sin_rs = t.sin_rs; s.rotary_dim = rotary_dim;
-    s.rotary_interleaved = rotary_interleaved ? 1 : 0;
-    // q token i is rotated at its own position when causal or a window bound was given (fa_ex_forward_kvcache_rotary's rule)
-    s.rotary_q_per_token = (causal || window_left >= 0 || window_right >= 0) ? 1 : 0;
-    return launched(who, fa::launch_fp8_kvcache_step(s, c.mod, reinterpret_cast<hipStream_t>(stream)));
+    Fp8KvCall c = fp8_kv_call(q, k_cache, v_cache, o, lse, q_descale, k_descale, v_descale, cache_seqlens, block_table, cache_batch_idx, batch,
+           heads_q, heads_kv, seqlen_q, cache_len, cache_batch, d, dtype, q_dtype, cache_dtype, q_batch_stride, q_token_stride, k_batch_stride,
+           k_token_stride, v_batch_stride, v_token_stride, block_table_row_stride, num_blocks, page_block_size, q_descale_batch_stride,
+           k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale, num_splits, workspace, workspace_bytes, stream);
+    c.mod = fp8_mod(window_left, window_right, softcap, sinks, sink_heads);
+    return fp8_step_impl("fa_fp8_kvcache_step", c, fp8_step_call(k_new, v_new, seqlen_new, k_new_batch_stride, k_new_token_stride,
+           v_new_batch_stride, v_new_token_stride, in_dtype, q8_out, q8_batch_stride, q8_token_stride, rotary_cos, rotary_sin,
+           rotary_cos_row_stride, rotary_sin_row_stride, seqlen_ro, rotary_dim, rotary_interleaved));
 }
 
 // ---- packed queries and new keys on the fp8 decode call and the step, and the step at head dims 64 / 256: see include/fa_mi355x.h
-// the splits of a packed call: the rule over max_seqlen_q (the most rows a sequence has), as the call's rule (9) takes them
-static int64_t fp8_kv_splits_varlen(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t max_seqlen_q, int64_t cache_len,
-                                    int64_t num_splits, int causal, int64_t window_left, int64_t window_right, int with_sinks) {
-    fa::Fp8Mod m;
-    m.window_left = window_left; m.window_right = window_right;
-    int64_t S = fp8_kv_splits(batch, heads_q, heads_kv, max_seqlen_q, fa::fp8kv_split_len(cache_len, max_seqlen_q, causal, m), num_splits);
-    if (with_sinks && S < 2) S = 2;
-    return S;
-}
 
 static bool fp8_varlen_ws_args_ok(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t max_seqlen_q, int64_t cache_len,
                                   int64_t head_dim, int64_t num_splits, int64_t window_left, int64_t window_right) {
@@ -3789,7 +3778,7 @@ static bool fp8_varlen_ws_args_ok(int64_t batch, int64_t heads_q, int64_t heads_
     return batch > 0 && batch <= 65535 && heads_q > 0 && heads_kv > 0 && heads_q % heads_kv == 0 && total_q >= 0 && total_q <= kInt &&
            max_seqlen_q >= 0 && max_seqlen_q <= total_q && (heads_q / heads_kv) * max_seqlen_q <= ((int64_t)1 << 20) && cache_len >= 1 &&
            num_splits >= 0 && num_splits <= 256 && window_left >= -1 && window_right >= -1 &&
-           (head_dim == 64 || head_dim == 128 || head_dim == 256);
+           !fp8_hdim_unsupported(head_dim);
 }
 
 size_t fa_fp8_forward_kvcache_varlen_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t max_seqlen_q,
@@ -3798,7 +3787,7 @@ size_t fa_fp8_forward_kvcache_varlen_workspace_bytes(int64_t batch, int64_t head
     if (!fp8_varlen_ws_args_ok(batch, heads_q, heads_kv, total_q, max_seqlen_q, cache_len, head_dim, num_splits, window_left, window_right))
         return 0;
     if (total_q == 0 || max_seqlen_q == 0) return 0;
-    const int64_t S = fp8_kv_splits_varlen(batch, heads_q, heads_kv, max_seqlen_q, cache_len, num_splits, causal, window_left, window_right, with_sinks);
+    const int64_t S = fp8_kv_splits_ws(batch, heads_q, heads_kv, max_seqlen_q, cache_len, num_splits, causal, window_left, window_right, with_sinks);
     return fa::kv_workspace_bytes(1, heads_q, total_q, head_dim, (int)S);
 }
 
@@ -3811,21 +3800,12 @@ int fa_fp8_forward_kvcache_varlen(const void* q, const void* k_cache, const void
         int causal, double softmax_scale, int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream,
         int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads,
         const int32_t* cu_seqlens_q, int64_t total_q, int64_t max_seqlen_q) {
-    Fp8KvCall c;
-    c.hdim = true; c.varlen = true;
-    c.q = q; c.k_cache = k_cache; c.v_cache = v_cache; c.o = o; c.lse = lse;
-    c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
-    c.cache_seqlens = cache_seqlens; c.block_table = block_table; c.cache_batch_idx = cache_batch_idx;
-    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.seqlen_q = seqlen_q; c.cache_len = cache_len; c.cache_batch = cache_batch;
-    c.d = head_dim; c.dtype = dtype; c.q_dtype = q_dtype; c.cache_dtype = cache_dtype;
-    c.q_bs = q_batch_stride; c.q_ts = q_token_stride; c.k_bs = k_batch_stride; c.k_ts = k_token_stride; c.v_bs = v_batch_stride;
-    c.v_ts = v_token_stride;
-    c.table_rs = block_table_row_stride; c.num_blocks = num_blocks; c.ps = page_block_size;
-    c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
-    c.causal = causal; c.scale = softmax_scale; c.num_splits = num_splits;
-    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
-    c.mod.window_left = window_left; c.mod.window_right = window_right; c.mod.softcap = softcap; c.mod.sinks = sinks;
-    c.mod.sink_heads = sink_heads;
+    Fp8KvCall c = fp8_kv_call(q, k_cache, v_cache, o, lse, q_descale, k_descale, v_descale, cache_seqlens, block_table, cache_batch_idx, batch,
+           heads_q, heads_kv, seqlen_q, cache_len, cache_batch, head_dim, dtype, q_dtype, cache_dtype, q_batch_stride, q_token_stride,
+           k_batch_stride, k_token_stride, v_batch_stride, v_token_stride, block_table_row_stride, num_blocks, page_block_size,
+           q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale, num_splits, workspace,
+           workspace_bytes, stream);
+    c.hdim = true; c.varlen = true; c.mod = fp8_mod(window_left, window_right, softcap, sinks, sink_heads);
     c.cu_seqlens_q = cu_seqlens_q; c.total_q = total_q; c.max_seqlen_q = max_seqlen_q;
     return fp8_kvcache_impl("fa_fp8_forward_kvcache_varlen", c);
 }
@@ -3843,13 +3823,13 @@ size_t fa_fp8_kvcache_step_varlen_workspace_bytes(int64_t batch, int64_t heads_q
         const size_t att = fa_fp8_forward_kvcache_hdim_workspace_bytes(batch, heads_q, heads_kv, seqlen_q, cache_len, head_dim, num_splits, causal,
                                                                        window_left, window_right, with_sinks);
         if (!kv_ws_args_ok(batch, heads_q, heads_kv, seqlen_q, cache_len, head_dim, num_splits) || window_left < -1 || window_right < -1 ||
-            (head_dim != 64 && head_dim != 256))
+            fp8_hdim_unsupported(head_dim))   // (128 went above)
             return 0;
         return fa::fp8kv_step_prep_bytes_varlen(batch, batch * seqlen_q, heads_q, head_dim, !e4m3 && !with_q8_out) + att;
     }
     if (!fp8_varlen_ws_args_ok(batch, heads_q, heads_kv, total_q, max_seqlen_q, cache_len, head_dim, num_splits, window_left, window_right))
         return 0;
-    const int64_t S = fp8_kv_splits_varlen(batch, heads_q, heads_kv, max_seqlen_q, cache_len, num_splits, causal, window_left, window_right, with_sinks);
+    const int64_t S = fp8_kv_splits_ws(batch, heads_q, heads_kv, max_seqlen_q, cache_len, num_splits, causal, window_left, window_right, with_sinks);
     return fa::fp8kv_step_prep_bytes_varlen(batch, total_q, heads_q, head_dim, !e4m3 && !with_q8_out) +
            fa::kv_workspace_bytes(1, heads_q, total_q, head_dim, (int)S);
 }
@@ -3869,45 +3849,18 @@ int fa_fp8_kvcache_step_varlen(const void* q, void* k_cache, void* v_cache, void
                                int64_t rotary_sin_row_stride, int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved,
                                const int32_t* cu_seqlens_q, int64_t total_q, int64_t max_seqlen_q, const int32_t* cu_seqlens_k_new,
                                int64_t total_k_new) {
-    const char* who = "fa_fp8_kvcache_step_varlen";
-    Fp8KvCall c;
-    c.hdim = true; c.varlen = true;
-    c.q = q; c.k_cache = k_cache; c.v_cache = v_cache; c.o = o; c.lse = lse;
-    c.q_descale = q_descale; c.k_descale = k_descale; c.v_descale = v_descale;
-    c.cache_seqlens = cache_seqlens; c.block_table = block_table; c.cache_batch_idx = cache_batch_idx;
-    c.batch = batch; c.heads_q = heads_q; c.heads_kv = heads_kv; c.seqlen_q = seqlen_q; c.cache_len = cache_len; c.cache_batch = cache_batch;
-    c.d = head_dim; c.dtype = dtype; c.q_dtype = q_dtype; c.cache_dtype = cache_dtype;
-    c.q_bs = q_batch_stride; c.q_ts = q_token_stride; c.k_bs = k_batch_stride; c.k_ts = k_token_stride; c.v_bs = v_batch_stride;
-    c.v_ts = v_token_stride;
-    c.table_rs = block_table_row_stride; c.num_blocks = num_blocks; c.ps = page_block_size;
-    c.qds_bs = q_descale_batch_stride; c.kds_bs = k_descale_batch_stride; c.vds_bs = v_descale_batch_stride;
-    c.causal = causal; c.scale = softmax_scale; c.num_splits = num_splits;
-    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
-    c.mod.window_left = window_left; c.mod.window_right = window_right; c.mod.softcap = softcap; c.mod.sinks = sinks;
-    c.mod.sink_heads = sink_heads;
+    Fp8KvCall c = fp8_kv_call(q, k_cache, v_cache, o, lse, q_descale, k_descale, v_descale, cache_seqlens, block_table, cache_batch_idx, batch,
+           heads_q, heads_kv, seqlen_q, cache_len, cache_batch, head_dim, dtype, q_dtype, cache_dtype, q_batch_stride, q_token_stride,
+           k_batch_stride, k_token_stride, v_batch_stride, v_token_stride, block_table_row_stride, num_blocks, page_block_size,
+           q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale, num_splits, workspace,
+           workspace_bytes, stream);
+    c.hdim = true; c.varlen = true; c.mod = fp8_mod(window_left, window_right, softcap, sinks, sink_heads);
     c.cu_seqlens_q = cu_seqlens_q; c.total_q = total_q; c.max_seqlen_q = max_seqlen_q;
-    Fp8StepCall t;
-    t.k_new = k_new; t.v_new = v_new; t.seqlen_new = seqlen_new; t.kn_bs = k_new_batch_stride; t.kn_ts = k_new_token_stride;
-    t.vn_bs = v_new_batch_stride; t.vn_ts = v_new_token_stride; t.in_dtype = in_dtype;
-    t.q8_out = q8_out; t.q8_bs = q8_batch_stride; t.q8_ts = q8_token_stride;
-    t.rotary_cos = rotary_cos; t.rotary_sin = rotary_sin; t.cos_rs = rotary_cos_row_stride; t.sin_rs = rotary_sin_row_stride;
-    t.seqlen_ro = seqlen_ro; t.rotary_dim = rotary_dim; t.rotary_interleaved = rotary_interleaved;
+    Fp8StepCall t = fp8_step_call(k_new, v_new, seqlen_new, k_new_batch_stride, k_new_token_stride, v_new_batch_stride, v_new_token_stride,
+           in_dtype, q8_out, q8_batch_stride, q8_token_stride, rotary_cos, rotary_sin, rotary_cos_row_stride, rotary_sin_row_stride,
+           seqlen_ro, rotary_dim, rotary_interleaved);
     t.cu_seqlens_k_new = cu_seqlens_k_new; t.total_k_new = total_k_new;
-    bool empty;
-    int64_t S = 1;
-    size_t need = 0;
-    if (const int rc = fp8_kvcache_check(who, c, &t, empty, S, need)) return rc;
-    if (empty) return FA_OK;
-    fa::Fp8StepArgs s;
-    s.kv = fp8_kvcache_args(c, S);
-    s.in_dtype = in_dtype; s.k_new = k_new; s.v_new = v_new; s.seqlen_new = seqlen_new;
-    s.kn_bs = t.kn_bs; s.kn_ts = t.kn_ts; s.vn_bs = t.vn_bs; s.vn_ts = t.vn_ts;
-    s.q8_out = q8_out; s.q8_bs = t.q8_bs; s.q8_ts = t.q8_ts;
-    s.rotary_cos = rotary_cos; s.rotary_sin = rotary_sin; s.rotary_cos_rs = t.cos_rs; s.rotary_sin_rs = t.sin_rs; s.rotary_dim = rotary_dim;
-    s.rotary_interleaved = rotary_interleaved ? 1 : 0;
-    s.rotary_q_per_token = (causal || window_left >= 0 || window_right >= 0) ? 1 : 0;   // the step's rule
-    s.cu_seqlens_k_new = cu_seqlens_k_new; s.total_k_new = total_k_new;
-    return launched(who, fa::launch_fp8_kvcache_step_varlen(s, c.mod, reinterpret_cast<hipStream_t>(stream)));
+    return fp8_step_impl("fa_fp8_kvcache_step_varlen", c, t);
 }
 
 size_t fa_ex_backward_workspace_bytes_grouped(int64_t bh, int64_t kv_group, int64_t nq, int64_t nk, int64_t d, int dtype) {
@@ -4033,6 +3986,27 @@ static int fp4_cache_check(const char* who, const Fp4Call& k, int nd) {
     return FA_OK;
 }
 
+// the cache arguments the append and both readers have: the four arrays, their eight strides, the page triple, the three descales
+static Fp4Call fp4_cache_call(const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, const int32_t* cache_seqlens,
+                              const int32_t* block_table, const int32_t* cache_batch_idx, int64_t batch, int64_t heads_kv, int64_t cache_len,
+                              int64_t cache_batch, int64_t d, int dtype, int64_t k_batch_stride, int64_t k_token_stride,
+                              int64_t k_scale_batch_stride, int64_t k_scale_token_stride, int64_t v_batch_stride, int64_t v_token_stride,
+                              int64_t v_scale_batch_stride, int64_t v_scale_token_stride, int64_t block_table_row_stride, int64_t num_blocks,
+                              int64_t page_block_size, const float* q_descale, const float* k_descale, const float* v_descale,
+                              int64_t q_descale_batch_stride, int64_t k_descale_batch_stride, int64_t v_descale_batch_stride) {
+    Fp4Call k;
+    k.c.k_cache = const_cast<void*>(k_cache); k.c.k_scale = const_cast<void*>(k_scale);
+    k.c.v_cache = const_cast<void*>(v_cache); k.c.v_scale = const_cast<void*>(v_scale);
+    k.c.cache_seqlens = cache_seqlens; k.c.block_table = block_table; k.c.cache_batch_idx = cache_batch_idx;
+    k.c.heads_kv = heads_kv; k.c.cache_len = cache_len; k.c.cache_batch = cache_batch;
+    k.c.kc_bs = k_batch_stride; k.c.kc_ts = k_token_stride; k.c.ks_bs = k_scale_batch_stride; k.c.ks_ts = k_scale_token_stride;
+    k.c.vc_bs = v_batch_stride; k.c.vc_ts = v_token_stride; k.c.vs_bs = v_scale_batch_stride; k.c.vs_ts = v_scale_token_stride;
+    k.c.table_row_stride = block_table_row_stride; k.c.num_blocks = num_blocks; k.c.page_size = page_block_size;
+    k.batch = batch; k.d = d; k.dtype = dtype; k.q_descale = q_descale; k.k_descale = k_descale; k.v_descale = v_descale;
+    k.qds_bs = q_descale_batch_stride; k.kds_bs = k_descale_batch_stride; k.vds_bs = v_descale_batch_stride;
+    return k;
+}
+
 int fa_fp4_kvcache_append(const void* k_new, const void* v_new, void* k_cache, void* k_scale, void* v_cache, void* v_scale,
                           const int32_t* cache_seqlens, const int32_t* block_table, const int32_t* cache_batch_idx, const float* k_descale,
                           const float* v_descale, int64_t batch, int64_t heads_kv, int64_t seqlen_new, int64_t cache_len, int64_t cache_batch,
@@ -4042,15 +4016,11 @@ int fa_fp4_kvcache_append(const void* k_new, const void* v_new, void* k_cache, v
                           int64_t v_scale_token_stride, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
                           int64_t descale_batch_stride, void* stream) {
     const char* who = "fa_fp4_kvcache_append";
-    Fp4Call k;
-    k.c.k_cache = k_cache; k.c.k_scale = k_scale; k.c.v_cache = v_cache; k.c.v_scale = v_scale;
-    k.c.cache_seqlens = cache_seqlens; k.c.block_table = block_table; k.c.cache_batch_idx = cache_batch_idx;
-    k.c.heads_kv = heads_kv; k.c.cache_len = cache_len; k.c.cache_batch = cache_batch;
-    k.c.kc_bs = k_batch_stride; k.c.kc_ts = k_token_stride; k.c.ks_bs = k_scale_batch_stride; k.c.ks_ts = k_scale_token_stride;
-    k.c.vc_bs = v_batch_stride; k.c.vc_ts = v_token_stride; k.c.vs_bs = v_scale_batch_stride; k.c.vs_ts = v_scale_token_stride;
-    k.c.table_row_stride = block_table_row_stride; k.c.num_blocks = num_blocks; k.c.page_size = page_block_size;
-    k.batch = batch; k.d = d; k.dtype = dtype; k.k_descale = k_descale; k.v_descale = v_descale;
-    k.kds_bs = k_descale ? descale_batch_stride : 0; k.vds_bs = v_descale ? descale_batch_stride : 0;   // (one stride for both)
+    // (no q_descale, and one stride for both others)
+    const Fp4Call k = fp4_cache_call(k_cache, k_scale, v_cache, v_scale, cache_seqlens, block_table, cache_batch_idx, batch, heads_kv, cache_len,
+           cache_batch, d, dtype, k_batch_stride, k_token_stride, k_scale_batch_stride, k_scale_token_stride, v_batch_stride, v_token_stride,
+           v_scale_batch_stride, v_scale_token_stride, block_table_row_stride, num_blocks, page_block_size, nullptr, k_descale, v_descale, 0,
+           k_descale ? descale_batch_stride : 0, v_descale ? descale_batch_stride : 0);
     if (batch == 0 || seqlen_new == 0) return FA_OK;
     if (!k_descale && !v_descale && descale_batch_stride != 0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: descale_batch_stride must be 0 without k_descale and v_descale", who);
@@ -4076,25 +4046,6 @@ int fa_fp4_kvcache_append(const void* k_new, const void* v_new, void* k_cache, v
     return launched(who, fa::launch_fp4_kvcache_append(a, reinterpret_cast<hipStream_t>(stream)));
 }
 
-// What the _mod entry points of the two MXFP4 cache readers add (fp8_mod_check's rules and words; a sink array of one logit for
-// every head is taken as well: the combine and the prefill epilogue read sinks[h % sink_heads])
-static int fp4_mod_check(const char* who, const fa::Fp8Mod& m, int64_t heads_q) {
-    if (m.window_left < -1 || m.window_right < -1)
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: window (%lld, %lld): each bound must be >= 0, or -1 for unbounded", who,
-                    (long long)m.window_left, (long long)m.window_right);
-    if (!(m.softcap == m.softcap) || m.softcap < 0.0 || m.softcap > 3.0e38)
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: softcap must be a finite number >= 0 (got %g)", who, m.softcap);
-    if (m.sinks) {
-        if (m.sink_heads != 1 && m.sink_heads != heads_q)
-            return fail(FA_ERR_INVALID_ARGUMENT, "%s: sink_heads=%lld must be 1 or heads_q=%lld (one sink per query head)", who,
-                        (long long)m.sink_heads, (long long)heads_q);
-        if ((uintptr_t)m.sinks % 4 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: sinks must be 4-byte aligned", who);
-    } else if (m.sink_heads != 0) {
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: sink_heads must be 0 without sinks (got %lld)", who, (long long)m.sink_heads);
-    }
-    return FA_OK;
-}
-
 // the e4m3 decode call's layout and split rule (the kernels share the 32-row tile and the combine)
 size_t fa_fp4_forward_kvcache_workspace_bytes_mod(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
                                                   int64_t d, int64_t num_splits, int causal, int64_t window_left, int64_t window_right,
@@ -4108,28 +4059,13 @@ size_t fa_fp4_forward_kvcache_workspace_bytes(int64_t batch, int64_t heads_q, in
     return fa_fp8_forward_kvcache_workspace_bytes(batch, heads_q, heads_kv, seqlen_q, cache_len, d, num_splits);
 }
 
-// fa_fp4_forward_kvcache (m at its defaults) and fa_fp4_forward_kvcache_mod
-static int fp4_forward_kvcache_entry(const char* who, const fa::Fp8Mod& m, const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o, float* lse,
-                           const float* q_descale, const float* k_descale, const float* v_descale, const int32_t* cache_seqlens,
-                           const int32_t* block_table, const int32_t* cache_batch_idx, int64_t batch, int64_t heads_q, int64_t heads_kv,
-                           int64_t seqlen_q, int64_t cache_len, int64_t cache_batch, int64_t d, int dtype, int64_t q_batch_stride,
-                           int64_t q_token_stride, int64_t k_batch_stride, int64_t k_token_stride, int64_t k_scale_batch_stride,
-                           int64_t k_scale_token_stride, int64_t v_batch_stride, int64_t v_token_stride, int64_t v_scale_batch_stride,
-                           int64_t v_scale_token_stride, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
-                           int64_t q_descale_batch_stride, int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal,
-                           double softmax_scale, int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream) {
-    Fp4Call k;
-    k.c.k_cache = const_cast<void*>(k_cache); k.c.k_scale = const_cast<void*>(k_scale);
-    k.c.v_cache = const_cast<void*>(v_cache); k.c.v_scale = const_cast<void*>(v_scale);
-    k.c.cache_seqlens = cache_seqlens; k.c.block_table = block_table; k.c.cache_batch_idx = cache_batch_idx;
-    k.c.heads_kv = heads_kv; k.c.cache_len = cache_len; k.c.cache_batch = cache_batch;
-    k.c.kc_bs = k_batch_stride; k.c.kc_ts = k_token_stride; k.c.ks_bs = k_scale_batch_stride; k.c.ks_ts = k_scale_token_stride;
-    k.c.vc_bs = v_batch_stride; k.c.vc_ts = v_token_stride; k.c.vs_bs = v_scale_batch_stride; k.c.vs_ts = v_scale_token_stride;
-    k.c.table_row_stride = block_table_row_stride; k.c.num_blocks = num_blocks; k.c.page_size = page_block_size;
-    k.batch = batch; k.d = d; k.dtype = dtype; k.q_descale = q_descale; k.k_descale = k_descale; k.v_descale = v_descale;
-    k.qds_bs = q_descale_batch_stride; k.kds_bs = k_descale_batch_stride; k.vds_bs = v_descale_batch_stride;
+// fa_fp4_forward_kvcache (m at its defaults) and fa_fp4_forward_kvcache_mod: k is the cache's record, the rest the query's side
+static int fp4_forward_kvcache_impl(const char* who, const fa::Fp8Mod& m, const Fp4Call& k, const void* q, void* o, float* lse, int64_t heads_q,
+                                    int64_t seqlen_q, int64_t q_batch_stride, int64_t q_token_stride, int causal, double softmax_scale,
+                                    int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream) {
+    const int64_t batch = k.batch, heads_kv = k.c.heads_kv, cache_len = k.c.cache_len;
     if (batch == 0 || seqlen_q == 0) return FA_OK;
-    if (!q || !k_cache || !k_scale || !v_cache || !v_scale || !o || !lse) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    if (!q || !k.c.k_cache || !k.c.k_scale || !k.c.v_cache || !k.c.v_scale || !o || !lse) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
     if (const int rc = fp4_cache_check(who, k, 3)) return rc;
     if (heads_q < 1 || heads_q % heads_kv != 0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: heads_q=%lld must be a positive multiple of heads_kv=%lld", who, (long long)heads_q,
@@ -4153,7 +4089,7 @@ static int fp4_forward_kvcache_entry(const char* who, const fa::Fp8Mod& m, const
                     (long long)(row_tiles * heads_kv));
     if (num_splits < 0 || num_splits > 256)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: num_splits must lie in [0, 256] (got %lld)", who, (long long)num_splits);
-    if (const int rc = fp4_mod_check(who, m, heads_q)) return rc;
+    if (const int rc = mod_check(who, m, heads_q, true)) return rc;
     // (the featured call: the rule sees the keys a window can show, and sinks raise 1 split to 2; not any(): the parent's rule)
     const int64_t S = fp8_kv_splits_mod(batch, heads_q, heads_kv, seqlen_q, cache_len, num_splits, causal, m);
     const size_t need = fa::kv_workspace_bytes(batch, heads_q, seqlen_q, 128, (int)S);
@@ -4164,10 +4100,10 @@ static int fp4_forward_kvcache_entry(const char* who, const fa::Fp8Mod& m, const
         if ((uintptr_t)workspace % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
     }
     fa::Fp4KvArgs a;
-    a.c = k.c; a.q = q; a.o = o; a.lse = lse; a.q_descale = q_descale; a.k_descale = k_descale; a.v_descale = v_descale;
+    a.c = k.c; a.q = q; a.o = o; a.lse = lse; a.q_descale = k.q_descale; a.k_descale = k.k_descale; a.v_descale = k.v_descale;
     a.qds_bs = k.qds_bs; a.kds_bs = k.kds_bs; a.vds_bs = k.vds_bs;
     a.batch = batch; a.heads_q = heads_q; a.seqlen_q = seqlen_q; a.q_bs = q_batch_stride; a.q_ts = q_token_stride;
-    a.dtype = dtype; a.causal = causal != 0; a.scale = (float)softmax_scale; a.num_splits = S; a.workspace = workspace;
+    a.dtype = k.dtype; a.causal = causal != 0; a.scale = (float)softmax_scale; a.num_splits = S; a.workspace = workspace;
     return launched(who, fa::launch_fp4_kvcache_mod(a, m, reinterpret_cast<hipStream_t>(stream)));
 }
 
@@ -4180,12 +4116,12 @@ int fa_fp4_forward_kvcache(const void* q, const void* k_cache, const void* k_sca
                            int64_t v_scale_token_stride, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
                            int64_t q_descale_batch_stride, int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal,
                            double softmax_scale, int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream) {
-    return fp4_forward_kvcache_entry("fa_fp4_forward_kvcache", fa::Fp8Mod(), q, k_cache, k_scale, v_cache, v_scale, o, lse, q_descale, k_descale,
-           v_descale, cache_seqlens, block_table, cache_batch_idx, batch, heads_q, heads_kv, seqlen_q, cache_len, cache_batch, d, dtype,
-           q_batch_stride, q_token_stride, k_batch_stride, k_token_stride, k_scale_batch_stride, k_scale_token_stride, v_batch_stride,
-           v_token_stride, v_scale_batch_stride, v_scale_token_stride, block_table_row_stride, num_blocks, page_block_size,
-           q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale, num_splits, workspace,
-           workspace_bytes, stream);
+    const Fp4Call k = fp4_cache_call(k_cache, k_scale, v_cache, v_scale, cache_seqlens, block_table, cache_batch_idx, batch, heads_kv, cache_len,
+           cache_batch, d, dtype, k_batch_stride, k_token_stride, k_scale_batch_stride, k_scale_token_stride, v_batch_stride, v_token_stride,
+           v_scale_batch_stride, v_scale_token_stride, block_table_row_stride, num_blocks, page_block_size, q_descale, k_descale, v_descale,
+           q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride);
+    return fp4_forward_kvcache_impl("fa_fp4_forward_kvcache", fa::Fp8Mod(), k, q, o, lse, heads_q, seqlen_q, q_batch_stride, q_token_stride, causal,
+                                    softmax_scale, num_splits, workspace, workspace_bytes, stream);
 }
 
 int fa_fp4_forward_kvcache_mod(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o, float* lse,
@@ -4198,39 +4134,25 @@ int fa_fp4_forward_kvcache_mod(const void* q, const void* k_cache, const void* k
                            int64_t q_descale_batch_stride, int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal,
                            double softmax_scale, int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream,
                            int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads) {
-    fa::Fp8Mod m;
-    m.window_left = window_left; m.window_right = window_right; m.softcap = softcap; m.sinks = sinks; m.sink_heads = sink_heads;
-    return fp4_forward_kvcache_entry("fa_fp4_forward_kvcache_mod", m, q, k_cache, k_scale, v_cache, v_scale, o, lse, q_descale, k_descale,
-           v_descale, cache_seqlens, block_table, cache_batch_idx, batch, heads_q, heads_kv, seqlen_q, cache_len, cache_batch, d, dtype,
-           q_batch_stride, q_token_stride, k_batch_stride, k_token_stride, k_scale_batch_stride, k_scale_token_stride, v_batch_stride,
-           v_token_stride, v_scale_batch_stride, v_scale_token_stride, block_table_row_stride, num_blocks, page_block_size,
-           q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale, num_splits, workspace,
-           workspace_bytes, stream);
+    const Fp4Call k = fp4_cache_call(k_cache, k_scale, v_cache, v_scale, cache_seqlens, block_table, cache_batch_idx, batch, heads_kv, cache_len,
+           cache_batch, d, dtype, k_batch_stride, k_token_stride, k_scale_batch_stride, k_scale_token_stride, v_batch_stride, v_token_stride,
+           v_scale_batch_stride, v_scale_token_stride, block_table_row_stride, num_blocks, page_block_size, q_descale, k_descale, v_descale,
+           q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride);
+    return fp4_forward_kvcache_impl("fa_fp4_forward_kvcache_mod", fp8_mod(window_left, window_right, softcap, sinks, sink_heads), k, q, o, lse,
+                                    heads_q, seqlen_q, q_batch_stride, q_token_stride, causal, softmax_scale, num_splits, workspace,
+                                    workspace_bytes, stream);
 }
 
 // Chunked prefill over the paged MXFP4 cache: packed queries, one launch, no workspace (fa_fp4_prefill.hip)
-// fa_fp4_forward_varlen (m at its defaults) and fa_fp4_forward_varlen_mod
-static int fp4_forward_varlen_entry(const char* who, const fa::Fp8Mod& m, const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o, float* lse,
-                          const float* q_descale, const float* k_descale, const float* v_descale, const int32_t* cu_seqlens_q,
-                          const int32_t* cu_seqlens_k, const int32_t* block_table, int64_t batch, int64_t heads_q, int64_t heads_kv,
-                          int64_t total_q, int64_t max_seqlen_q, int64_t cache_len, int64_t d, int dtype, int64_t q_token_stride,
-                          int64_t k_batch_stride, int64_t k_token_stride, int64_t k_scale_batch_stride, int64_t k_scale_token_stride,
-                          int64_t v_batch_stride, int64_t v_token_stride, int64_t v_scale_batch_stride, int64_t v_scale_token_stride,
-                          int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t q_descale_batch_stride,
-                          int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* stream) {
-    Fp4Call k;
-    k.c.k_cache = const_cast<void*>(k_cache); k.c.k_scale = const_cast<void*>(k_scale);
-    k.c.v_cache = const_cast<void*>(v_cache); k.c.v_scale = const_cast<void*>(v_scale);
-    k.c.block_table = block_table; k.c.heads_kv = heads_kv; k.c.cache_len = cache_len;
-    k.c.kc_bs = k_batch_stride; k.c.kc_ts = k_token_stride; k.c.ks_bs = k_scale_batch_stride; k.c.ks_ts = k_scale_token_stride;
-    k.c.vc_bs = v_batch_stride; k.c.vc_ts = v_token_stride; k.c.vs_bs = v_scale_batch_stride; k.c.vs_ts = v_scale_token_stride;
-    k.c.table_row_stride = block_table_row_stride; k.c.num_blocks = num_blocks; k.c.page_size = page_block_size;
-    k.batch = batch; k.d = d; k.dtype = dtype; k.q_descale = q_descale; k.k_descale = k_descale; k.v_descale = v_descale;
-    k.qds_bs = q_descale_batch_stride; k.kds_bs = k_descale_batch_stride; k.vds_bs = v_descale_batch_stride;
+// fa_fp4_forward_varlen (m at its defaults) and fa_fp4_forward_varlen_mod: k is the cache's record (no lengths, no row indirection)
+static int fp4_forward_varlen_impl(const char* who, const fa::Fp8Mod& m, const Fp4Call& k, const void* q, void* o, float* lse,
+                                   const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t heads_q, int64_t total_q,
+                                   int64_t max_seqlen_q, int64_t q_token_stride, int causal, double softmax_scale, void* stream) {
+    const int64_t batch = k.batch, heads_kv = k.c.heads_kv;
     if (batch == 0 || total_q == 0 || max_seqlen_q == 0) return FA_OK;
-    if (!q || !k_cache || !k_scale || !v_cache || !v_scale || !o || !lse) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
+    if (!q || !k.c.k_cache || !k.c.k_scale || !k.c.v_cache || !k.c.v_scale || !o || !lse) return fail(FA_ERR_INVALID_ARGUMENT, "%s: null tensor pointer", who);
     if (!cu_seqlens_q || !cu_seqlens_k) return fail(FA_ERR_INVALID_ARGUMENT, "%s: cu_seqlens_q and cu_seqlens_k are required", who);
-    if (!block_table)
+    if (!k.c.block_table)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: block_table is required (the cache is a pool of pages; a contiguous cache is one under "
                     "an arange table)", who);
     if (const int rc = fp4_cache_check(who, k, 3)) return rc;
@@ -4252,12 +4174,12 @@ static int fp4_forward_varlen_entry(const char* who, const fa::Fp8Mod& m, const 
     if (heads_kv > 65535 || (max_seqlen_q * (heads_q / heads_kv) + 127) / 128 > ((int64_t)1 << 31) - 1)
         return fail(FA_ERR_UNSUPPORTED, "%s: span limit: heads_kv = %lld (at most 65535) or the row tiles of max_seqlen_q are beyond one launch",
                     who, (long long)heads_kv);
-    if (const int rc = fp4_mod_check(who, m, heads_q)) return rc;
+    if (const int rc = mod_check(who, m, heads_q, true)) return rc;
     fa::Fp4VarlenArgs a;
-    a.c = k.c; a.q = q; a.o = o; a.lse = lse; a.q_descale = q_descale; a.k_descale = k_descale; a.v_descale = v_descale;
+    a.c = k.c; a.q = q; a.o = o; a.lse = lse; a.q_descale = k.q_descale; a.k_descale = k.k_descale; a.v_descale = k.v_descale;
     a.qds_bs = k.qds_bs; a.kds_bs = k.kds_bs; a.vds_bs = k.vds_bs; a.cu_seqlens_q = cu_seqlens_q; a.cu_seqlens_k = cu_seqlens_k;
     a.batch = batch; a.heads_q = heads_q; a.total_q = total_q; a.max_seqlen_q = max_seqlen_q; a.q_ts = q_token_stride;
-    a.dtype = dtype; a.causal = causal != 0; a.scale = (float)softmax_scale;
+    a.dtype = k.dtype; a.causal = causal != 0; a.scale = (float)softmax_scale;
     return launched(who, fa::launch_fp4_prefill_mod(a, m, reinterpret_cast<hipStream_t>(stream)));
 }
 
@@ -4269,11 +4191,12 @@ int fa_fp4_forward_varlen(const void* q, const void* k_cache, const void* k_scal
                           int64_t v_batch_stride, int64_t v_token_stride, int64_t v_scale_batch_stride, int64_t v_scale_token_stride,
                           int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t q_descale_batch_stride,
                           int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* stream) {
-    return fp4_forward_varlen_entry("fa_fp4_forward_varlen", fa::Fp8Mod(), q, k_cache, k_scale, v_cache, v_scale, o, lse, q_descale, k_descale,
-           v_descale, cu_seqlens_q, cu_seqlens_k, block_table, batch, heads_q, heads_kv, total_q, max_seqlen_q, cache_len, d, dtype,
-           q_token_stride, k_batch_stride, k_token_stride, k_scale_batch_stride, k_scale_token_stride, v_batch_stride, v_token_stride,
-           v_scale_batch_stride, v_scale_token_stride, block_table_row_stride, num_blocks, page_block_size, q_descale_batch_stride,
-           k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale, stream);
+    const Fp4Call k = fp4_cache_call(k_cache, k_scale, v_cache, v_scale, nullptr, block_table, nullptr, batch, heads_kv, cache_len, 0, d, dtype,
+           k_batch_stride, k_token_stride, k_scale_batch_stride, k_scale_token_stride, v_batch_stride, v_token_stride, v_scale_batch_stride,
+           v_scale_token_stride, block_table_row_stride, num_blocks, page_block_size, q_descale, k_descale, v_descale, q_descale_batch_stride,
+           k_descale_batch_stride, v_descale_batch_stride);
+    return fp4_forward_varlen_impl("fa_fp4_forward_varlen", fa::Fp8Mod(), k, q, o, lse, cu_seqlens_q, cu_seqlens_k, heads_q, total_q, max_seqlen_q,
+                                   q_token_stride, causal, softmax_scale, stream);
 }
 
 int fa_fp4_forward_varlen_mod(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o, float* lse,
@@ -4285,13 +4208,12 @@ int fa_fp4_forward_varlen_mod(const void* q, const void* k_cache, const void* k_
                           int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t q_descale_batch_stride,
                           int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* stream,
                           int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads) {
-    fa::Fp8Mod m;
-    m.window_left = window_left; m.window_right = window_right; m.softcap = softcap; m.sinks = sinks; m.sink_heads = sink_heads;
-    return fp4_forward_varlen_entry("fa_fp4_forward_varlen_mod", m, q, k_cache, k_scale, v_cache, v_scale, o, lse, q_descale, k_descale,
-           v_descale, cu_seqlens_q, cu_seqlens_k, block_table, batch, heads_q, heads_kv, total_q, max_seqlen_q, cache_len, d, dtype,
-           q_token_stride, k_batch_stride, k_token_stride, k_scale_batch_stride, k_scale_token_stride, v_batch_stride, v_token_stride,
-           v_scale_batch_stride, v_scale_token_stride, block_table_row_stride, num_blocks, page_block_size, q_descale_batch_stride,
-           k_descale_batch_stride, v_descale_batch_stride, causal, softmax_scale, stream);
+    const Fp4Call k = fp4_cache_call(k_cache, k_scale, v_cache, v_scale, nullptr, block_table, nullptr, batch, heads_kv, cache_len, 0, d, dtype,
+           k_batch_stride, k_token_stride, k_scale_batch_stride, k_scale_token_stride, v_batch_stride, v_token_stride, v_scale_batch_stride,
+           v_scale_token_stride, block_table_row_stride, num_blocks, page_block_size, q_descale, k_descale, v_descale, q_descale_batch_stride,
+           k_descale_batch_stride, v_descale_batch_stride);
+    return fp4_forward_varlen_impl("fa_fp4_forward_varlen_mod", fp8_mod(window_left, window_right, softcap, sinks, sink_heads), k, q, o, lse,
+                                   cu_seqlens_q, cu_seqlens_k, heads_q, total_q, max_seqlen_q, q_token_stride, causal, softmax_scale, stream);
 }
 
 int fa_debug_trace_buffer(void* device_ptr) {

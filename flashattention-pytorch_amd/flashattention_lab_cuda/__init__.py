@@ -2496,6 +2496,43 @@ def fp8_varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_se
     return o, lse
 
 
+def _fp8_cache_geometry(who, k_cache, block_table, cache_batch_idx, b):
+    """(block_table, cache_batch_idx, capacity, cache_batch, (block_table_row_stride, num_blocks, page_block_size)) of an e4m3 cache
+    (B_cache, cache_len, H_kv, d), or with block_table of the pools (num_blocks, page_block_size, H_kv, d), for a batch of b: the rules
+    of the three fp8 KV-cache functions, in their order; the two index tensors come back in the form the C call takes"""
+    if block_table is not None:
+        nblk, ps = k_cache.shape[0], k_cache.shape[1]
+        if ps < 16 or ps % 16 != 0:
+            raise RuntimeError(f"{who}: page_block_size must be a positive multiple of 16, got {ps}")
+        if block_table.dim() != 2 or block_table.shape[0] != b or block_table.shape[1] < 1:
+            raise RuntimeError(f"{who}: block_table must be an int32 (B, max_blocks_per_seq >= 1) tensor, B = {b}; got "
+                               f"{tuple(block_table.shape)}")
+        if nblk < 1:
+            raise RuntimeError(f"{who}: the pools must hold at least one page")
+        if block_table.stride(1) != 1 and block_table.shape[1] > 1:
+            block_table = block_table.contiguous()
+        return block_table, cache_batch_idx, block_table.shape[1] * ps, 0, (max(block_table.stride(0), block_table.shape[1]), nblk, ps)
+    cap, cbatch = k_cache.shape[1], 0
+    if cap < 1:
+        raise RuntimeError(f"{who}: the caches must hold at least one token")
+    if cache_batch_idx is not None:
+        if cache_batch_idx.shape != (b,):
+            raise RuntimeError(f"{who}: cache_batch_idx must be an int32 tensor of shape (B,) = ({b},)")
+        cache_batch_idx, cbatch = cache_batch_idx.contiguous(), k_cache.shape[0]
+    elif k_cache.shape[0] != b:
+        raise RuntimeError(f"{who}: the caches hold {k_cache.shape[0]} rows for a batch of {b} (pass cache_batch_idx to select rows)")
+    return block_table, cache_batch_idx, cap, cbatch, (0, 0, 0)
+
+
+def _one_device(who, *tensors):
+    tensors = [t for t in tensors if t is not None]
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: tensors must be on the GPU (HIP device); there is no CPU path")
+    if len({t.device for t in tensors}) != 1:
+        raise RuntimeError(f"{who}: all tensors must be on one device")
+
+
 def fp8_kvcache_forward(q, k_cache, v_cache, cache_seqlens=None, block_table=None, cache_batch_idx=None, q_descale=None, k_descale=None,
                         v_descale=None, softmax_scale=None, causal=False, num_splits=0, out_dtype=torch.bfloat16, *, window=(-1, -1),
                         softcap=0.0, sinks=None, hdim=False, cu_seqlens_q=None, max_seqlen_q=None):
@@ -2509,120 +2546,20 @@ def fp8_kvcache_forward(q, k_cache, v_cache, cache_seqlens=None, block_table=Non
     has the rest).  cu_seqlens_q (int32 (B + 1,) on the device, never read on the host) with max_seqlen_q (an int): packed queries
     through fa_fp8_forward_kvcache_varlen under the hdim rules; q is (total_q, H_q, d), o likewise and lse (H_q, total_q)."""
     who = "fp8_kvcache_forward"
-    if cu_seqlens_q is not None or max_seqlen_q is not None:
-        return _fp8_kvcache_packed(who, q, k_cache, v_cache, None, None, cache_seqlens, block_table, cache_batch_idx, q_descale, k_descale,
-                                   v_descale, softmax_scale, causal, num_splits, out_dtype, window, softcap, sinks, cu_seqlens_q,
-                                   max_seqlen_q, None, None, None, False, None)
-    if isinstance(q, torch.Tensor) and q.dtype in (torch.float16, torch.bfloat16):
-        raise NotImplementedError(f"{who}: q of dtype {q.dtype} is not supported (torch.float8_e4m3fn expected; a 16-bit q over an e4m3 "
-                                  f"cache is flash_attn_with_kvcache(..., k_descale=, v_descale=))")
-    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float8_e4m3fn:
-            dt = t.dtype if isinstance(t, torch.Tensor) else type(t).__name__
-            raise NotImplementedError(f"{who}: {name} of dtype {dt} is not supported (torch.float8_e4m3fn expected)")
-    if out_dtype not in (torch.bfloat16, torch.float16):
-        raise NotImplementedError(f"{who}: out_dtype {out_dtype} is not supported (torch.bfloat16 or torch.float16)")
-    paged = block_table is not None
-    if paged and cache_batch_idx is not None:
-        raise NotImplementedError(f"{who}: block_table together with cache_batch_idx is not supported (a table row is the indirection)")
-    for name, t in (("block_table", block_table), ("cache_batch_idx", cache_batch_idx)):
-        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.int32):
-            dt = t.dtype if isinstance(t, torch.Tensor) else type(t).__name__
-            raise NotImplementedError(f"{who}: {name} of dtype {dt} is not supported (int32 tensor expected)")
-    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
-        raise RuntimeError(f"{who}: q must be (B, Nq, H_q, 128) and k_cache, v_cache " +
-                           ("pools (num_blocks, page_block_size, H_kv, 128)" if paged else "(B_cache, cache_len, H_kv, 128)") +
-                           f" of one shape; got {tuple(q.shape)}, {tuple(k_cache.shape)}, {tuple(v_cache.shape)}")
-    d = _fp8_head_dim(who, hdim, q=q, k_cache=k_cache, v_cache=v_cache)
-    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
-        if t.shape[-1] != d:
-            raise NotImplementedError(f"{who}: head_dim {t.shape[-1]} is not supported (128 only); got {name} of shape {tuple(t.shape)}")
-    b, nq, hq = q.shape[0], q.shape[1], q.shape[2]
-    hkv = k_cache.shape[2]
-    if hkv == 0 or hq == 0 or hq % hkv != 0:
-        raise RuntimeError(f"{who}: H_q = {hq} must be a multiple of H_kv = {hkv}")
-    if isinstance(cache_seqlens, int) and not isinstance(cache_seqlens, bool):
-        cache_seqlens = torch.full((b,), cache_seqlens, dtype=torch.int32, device=q.device)
-    if cache_seqlens is not None and not (isinstance(cache_seqlens, torch.Tensor) and cache_seqlens.dtype == torch.int32 and
-                                          cache_seqlens.shape == (b,)):
-        raise RuntimeError(f"{who}: cache_seqlens must be an int32 tensor of shape (B,) = ({b},), an int or None")
-    tensors = [t for t in (q, k_cache, v_cache, cache_seqlens, block_table, cache_batch_idx) if t is not None]
-    for t in tensors:
-        if not t.is_cuda:
-            raise RuntimeError(f"{who}: tensors must be on the GPU (HIP device); there is no CPU path")
-    if len({t.device for t in tensors}) != 1:
-        raise RuntimeError(f"{who}: all tensors must be on one device")
-    scale = d ** -0.5 if softmax_scale is None else float(softmax_scale)
-    if not (math.isfinite(scale) and scale > 0.0):
-        raise RuntimeError(f"{who}: softmax_scale must be finite and > 0 (got {scale})")
-    ns = operator.index(num_splits)
-    if ns < 0 or ns > 256:
-        raise RuntimeError(f"{who}: num_splits must lie in [0, 256] (got {ns})")
-    for name, t, heads in (("q", q, hq), ("k_cache", k_cache, hkv), ("v_cache", v_cache, hkv)):
-        if t.numel() and ((heads > 1 and t.stride(2) != d) or t.stride(3) != 1):
-            raise ValueError(f"{who}: {name} must have adjacent heads with a contiguous last dim (strides {t.stride()})")
-        if t.numel() and (t.data_ptr() % 16 != 0 or t.stride(0) % 16 != 0 or t.stride(1) % 16 != 0 or t.stride(0) < 0 or
-                          (t.shape[1] > 1 and t.stride(1) < heads * d)):
-            raise ValueError(f"{who}: {name} is a view the kernel cannot address: a 16-byte aligned start, batch and token strides that "
-                             f"are multiples of 16 bytes and rows that do not overlap are needed (strides {t.stride()})")
-    tstride = lambda t, heads: t.stride(1) if t.shape[1] > 1 else heads * d   # noqa: E731
-    if paged:
-        nblk, ps = k_cache.shape[0], k_cache.shape[1]
-        if ps < 16 or ps % 16 != 0:
-            raise RuntimeError(f"{who}: page_block_size must be a positive multiple of 16, got {ps}")
-        if block_table.dim() != 2 or block_table.shape[0] != b or block_table.shape[1] < 1:
-            raise RuntimeError(f"{who}: block_table must be an int32 (B, max_blocks_per_seq >= 1) tensor, B = {b}; got "
-                               f"{tuple(block_table.shape)}")
-        if nblk < 1:
-            raise RuntimeError(f"{who}: the pools must hold at least one page")
-        if block_table.stride(1) != 1 and block_table.shape[1] > 1:
-            block_table = block_table.contiguous()
-        cap, cbatch = block_table.shape[1] * ps, 0
-        pages = (max(block_table.stride(0), block_table.shape[1]), nblk, ps)
-    else:
-        cap = k_cache.shape[1]
-        if cap < 1:
-            raise RuntimeError(f"{who}: the caches must hold at least one token")
-        if cache_batch_idx is not None:
-            if cache_batch_idx.shape != (b,):
-                raise RuntimeError(f"{who}: cache_batch_idx must be an int32 tensor of shape (B,) = ({b},)")
-            cache_batch_idx = cache_batch_idx.contiguous()
-            cbatch = k_cache.shape[0]
-        elif k_cache.shape[0] != b:
-            raise RuntimeError(f"{who}: the caches hold {k_cache.shape[0]} rows for a batch of {b} (pass cache_batch_idx to select rows)")
-        else:
-            cbatch = 0
-        pages = (0, 0, 0)
-    if cache_seqlens is not None:
-        cache_seqlens = cache_seqlens.contiguous()
-    qdp, qds, keep_q = _kv_descale(who, "q_descale", q_descale, q, b, hkv)
-    kdp, kds, keep_k = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
-    vdp, vds, keep_v = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
-    mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks, hdim)
-    with torch.cuda.device(q.device):
-        o = torch.empty((b, nq, hq, d), dtype=out_dtype, device=q.device)
-        lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)
-        if b == 0 or nq == 0:
-            return o, lse
-        if hdim:
-            need = int(_lib.fa_fp8_forward_kvcache_hdim_workspace_bytes(b, hq, hkv, nq, cap, d, ns, int(bool(causal)), tail[0], tail[1],
-                                                                        int(sinks is not None)))
-        elif mod:
-            need = int(_lib.fa_fp8_forward_kvcache_workspace_bytes_mod(b, hq, hkv, nq, cap, 128, ns, int(bool(causal)), tail[0], tail[1],
-                                                                       int(sinks is not None)))
-        else:
-            need = int(_lib.fa_fp8_forward_kvcache_workspace_bytes(b, hq, hkv, nq, cap, 128, ns))
-        ws = _workspace(q.device, need)
-        _call("fa_fp8_forward_kvcache" + mod, (
-            q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp,
-            cache_seqlens.data_ptr() if cache_seqlens is not None else 0, block_table.data_ptr() if paged else 0,
-            cache_batch_idx.data_ptr() if cache_batch_idx is not None else 0, b, hq, hkv, nq, cap, cbatch, d, _DTYPE_CODE[out_dtype],
-            _E4M3_CODE, _E4M3_CODE, max(q.stride(0), 0) if b > 1 else 0, tstride(q, hq),
-            k_cache.stride(0) if k_cache.shape[0] > 1 else 0, tstride(k_cache, hkv),
-            v_cache.stride(0) if v_cache.shape[0] > 1 else 0, tstride(v_cache, hkv), *pages, qds, kds, vds, int(bool(causal)), scale, ns,
-            ws.data_ptr() if need else 0, ws.numel() if need else 0, _stream_ptr(q.device), *tail))
-    del keep_q, keep_k, keep_v, keep_s
-    return o, lse
+    if cu_seqlens_q is None and max_seqlen_q is None:
+        # the padded call's own first rules (the packed form has the front's: a q that is no tensor, a default out_dtype)
+        if isinstance(q, torch.Tensor) and q.dtype in (torch.float16, torch.bfloat16):
+            raise NotImplementedError(f"{who}: q of dtype {q.dtype} is not supported (torch.float8_e4m3fn expected; a 16-bit q over an "
+                                      f"e4m3 cache is flash_attn_with_kvcache(..., k_descale=, v_descale=))")
+        for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float8_e4m3fn:
+                dt = t.dtype if isinstance(t, torch.Tensor) else type(t).__name__
+                raise NotImplementedError(f"{who}: {name} of dtype {dt} is not supported (torch.float8_e4m3fn expected)")
+        if out_dtype not in (torch.bfloat16, torch.float16):
+            raise NotImplementedError(f"{who}: out_dtype {out_dtype} is not supported (torch.bfloat16 or torch.float16)")
+    return _fp8_kvcache_run(who, q, k_cache, v_cache, None, None, cache_seqlens, block_table, cache_batch_idx, q_descale, k_descale,
+                            v_descale, softmax_scale, causal, num_splits, out_dtype, window, softcap, sinks, hdim, cu_seqlens_q,
+                            max_seqlen_q, None, None, None, False, None)
 
 
 def fp8_kvcache_step(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table=None, cache_batch_idx=None, q_descale=None,
@@ -2642,171 +2579,32 @@ def fp8_kvcache_step(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_tab
     likewise, lse (H_q, total_q); with cu_seqlens_k_new the new tokens are packed (total_k_new, H_kv, d).  Without any of the four the
     function is what it was."""
     who = "fp8_kvcache_step"
-    if cu_seqlens_q is not None or max_seqlen_q is not None or cu_seqlens_k_new is not None or hdim:
-        return _fp8_kvcache_packed(who, q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, cache_batch_idx, q_descale, k_descale,
-                                   v_descale, softmax_scale, causal, num_splits, out_dtype, window, softcap, sinks, cu_seqlens_q,
-                                   max_seqlen_q, cu_seqlens_k_new, rotary_cos, rotary_sin, rotary_interleaved, q8_out)
-    for name, t in (("q", q), ("k", k_new), ("v", v_new), ("k_cache", k_cache), ("v_cache", v_cache)):
-        if not isinstance(t, torch.Tensor):
-            raise RuntimeError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
-    if q.dtype not in (torch.float16, torch.bfloat16, torch.float8_e4m3fn):
-        raise NotImplementedError(f"{who}: q of dtype {q.dtype} is not supported (float16, bfloat16 or torch.float8_e4m3fn)")
-    if k_new.dtype != q.dtype or v_new.dtype != q.dtype:
-        raise NotImplementedError(f"{who}: mixed dtypes are not supported: q, k, v must be all float16, all bfloat16 or all "
-                                  f"torch.float8_e4m3fn (got {q.dtype}, {k_new.dtype}, {v_new.dtype})")
-    e4 = q.dtype == torch.float8_e4m3fn
-    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
-        if t.dtype != torch.float8_e4m3fn:
-            raise NotImplementedError(f"{who}: {name} of dtype {t.dtype} is not supported (torch.float8_e4m3fn expected)")
-    if e4 and (rotary_cos is not None or rotary_sin is not None):
-        raise NotImplementedError(f"{who}: rotary_cos / rotary_sin are not supported with torch.float8_e4m3fn q, k, v (codes cannot be rotated)")
-    if e4 and q8_out is not None:
-        raise NotImplementedError(f"{who}: q8_out is not supported with a torch.float8_e4m3fn q (it is used in place)")
-    if out_dtype is None:
-        out_dtype = torch.bfloat16 if e4 else q.dtype
-    if out_dtype not in (torch.bfloat16, torch.float16):
-        raise NotImplementedError(f"{who}: out_dtype {out_dtype} is not supported (torch.bfloat16 or torch.float16)")
-    paged = block_table is not None
-    if paged and cache_batch_idx is not None:
-        raise NotImplementedError(f"{who}: block_table together with cache_batch_idx is not supported (a table row is the indirection)")
-    for name, t in (("block_table", block_table), ("cache_batch_idx", cache_batch_idx)):
-        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.int32):
-            dt = t.dtype if isinstance(t, torch.Tensor) else type(t).__name__
-            raise NotImplementedError(f"{who}: {name} of dtype {dt} is not supported (int32 tensor expected)")
-    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
-        raise RuntimeError(f"{who}: q must be (B, Nq, H_q, 128) and k_cache, v_cache " +
-                           ("pools (num_blocks, page_block_size, H_kv, 128)" if paged else "(B_cache, cache_len, H_kv, 128)") +
-                           f" of one shape; got {tuple(q.shape)}, {tuple(k_cache.shape)}, {tuple(v_cache.shape)}")
-    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache), ("k", k_new), ("v", v_new)):
-        if t.shape[-1] != 128:
-            raise NotImplementedError(f"{who}: head_dim {t.shape[-1]} is not supported (128 only); got {name} of shape {tuple(t.shape)}")
-    b, nq, hq = q.shape[0], q.shape[1], q.shape[2]
-    hkv = k_cache.shape[2]
-    if hkv == 0 or hq == 0 or hq % hkv != 0:
-        raise RuntimeError(f"{who}: H_q = {hq} must be a multiple of H_kv = {hkv}")
-    if k_new.dim() != 4 or k_new.shape[0] != b or k_new.shape[1] < 1 or k_new.shape[2] != hkv or v_new.shape != k_new.shape:
-        raise RuntimeError(f"{who}: k and v must be (B, N_new >= 1, H_kv, 128) = ({b}, ., {hkv}, 128) tensors of one shape; got "
-                           f"{tuple(k_new.shape)}, {tuple(v_new.shape)}")
-    nnew = k_new.shape[1]
-    if cache_seqlens is None:
-        raise RuntimeError(f"{who}: cache_seqlens is required (the lengths before the append: an int32 (B,) tensor or an int)")
-    if isinstance(cache_seqlens, int) and not isinstance(cache_seqlens, bool):
-        cache_seqlens = torch.full((b,), cache_seqlens, dtype=torch.int32, device=q.device)
-    if not (isinstance(cache_seqlens, torch.Tensor) and cache_seqlens.dtype == torch.int32 and cache_seqlens.shape == (b,)):
-        raise RuntimeError(f"{who}: cache_seqlens must be an int32 tensor of shape (B,) = ({b},) or an int")
-    rot = rotary_cos is not None or rotary_sin is not None
-    rdim = 0
-    if rot:
-        if rotary_cos is None or rotary_sin is None:
-            raise RuntimeError(f"{who}: rotary_cos and rotary_sin must be given together")
-        for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
-            if not isinstance(t, torch.Tensor) or t.dtype != q.dtype or t.dim() != 2 or t.shape != rotary_cos.shape or t.numel() == 0:
-                raise RuntimeError(f"{who}: {name} must be a (seqlen_ro, rotary_dim / 2) tensor of q's dtype, rotary_cos and rotary_sin of "
-                                   f"one shape")
-        rdim = 2 * rotary_cos.shape[1]
-        if rdim % 16 != 0 or not 16 <= rdim <= 128:
-            raise RuntimeError(f"{who}: rotary_dim = 2 * rotary_cos.shape[1] must be a multiple of 16 in [16, 128], got {rdim}")
-    if q8_out is not None and not (isinstance(q8_out, torch.Tensor) and q8_out.dtype == torch.float8_e4m3fn and q8_out.shape == q.shape):
-        raise RuntimeError(f"{who}: q8_out must be a torch.float8_e4m3fn tensor of q's shape {tuple(q.shape)}")
-    tensors = [t for t in (q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, cache_batch_idx, rotary_cos, rotary_sin, q8_out)
-               if t is not None]
-    for t in tensors:
-        if not t.is_cuda:
-            raise RuntimeError(f"{who}: tensors must be on the GPU (HIP device); there is no CPU path")
-    if len({t.device for t in tensors}) != 1:
-        raise RuntimeError(f"{who}: all tensors must be on one device")
-    scale = 128 ** -0.5 if softmax_scale is None else float(softmax_scale)
-    if not (math.isfinite(scale) and scale > 0.0):
-        raise RuntimeError(f"{who}: softmax_scale must be finite and > 0 (got {scale})")
-    ns = operator.index(num_splits)
-    if ns < 0 or ns > 256:
-        raise RuntimeError(f"{who}: num_splits must lie in [0, 256] (got {ns})")
-    views = [("q", q, hq), ("k_cache", k_cache, hkv), ("v_cache", v_cache, hkv)] + ([("q8_out", q8_out, hq)] if q8_out is not None else [])
-    for name, t, heads in views:
-        unit = 16 // t.element_size()
-        if t.numel() and ((heads > 1 and t.stride(2) != 128) or t.stride(3) != 1):
-            raise ValueError(f"{who}: {name} must have adjacent heads with a contiguous last dim (strides {t.stride()})")
-        if t.numel() and (t.data_ptr() % 16 != 0 or t.stride(0) % unit != 0 or t.stride(1) % unit != 0 or t.stride(0) < 0 or
-                          (t.shape[1] > 1 and t.stride(1) < heads * 128)):
-            raise ValueError(f"{who}: {name} is a view the kernel cannot address: a 16-byte aligned start, batch and token strides that "
-                             f"are multiples of 16 bytes and rows that do not overlap are needed (strides {t.stride()})")
-    # (batch stride, token stride) in bytes of a view checked above
-    bstride = lambda t: (max(t.stride(0), 0) if t.shape[0] > 1 else 0) * t.element_size()   # noqa: E731
-    tstride = lambda t, heads: (t.stride(1) if t.shape[1] > 1 else heads * 128) * t.element_size()   # noqa: E731
-    if paged:
-        nblk, ps = k_cache.shape[0], k_cache.shape[1]
-        if ps < 16 or ps % 16 != 0:
-            raise RuntimeError(f"{who}: page_block_size must be a positive multiple of 16, got {ps}")
-        if block_table.dim() != 2 or block_table.shape[0] != b or block_table.shape[1] < 1:
-            raise RuntimeError(f"{who}: block_table must be an int32 (B, max_blocks_per_seq >= 1) tensor, B = {b}; got "
-                               f"{tuple(block_table.shape)}")
-        if nblk < 1:
-            raise RuntimeError(f"{who}: the pools must hold at least one page")
-        if block_table.stride(1) != 1 and block_table.shape[1] > 1:
-            block_table = block_table.contiguous()
-        cap, cbatch = block_table.shape[1] * ps, 0
-        pages = (max(block_table.stride(0), block_table.shape[1]), nblk, ps)
-    else:
-        cap = k_cache.shape[1]
-        if cap < 1:
-            raise RuntimeError(f"{who}: the caches must hold at least one token")
-        if cache_batch_idx is not None:
-            if cache_batch_idx.shape != (b,):
-                raise RuntimeError(f"{who}: cache_batch_idx must be an int32 tensor of shape (B,) = ({b},)")
-            cache_batch_idx = cache_batch_idx.contiguous()
-            cbatch = k_cache.shape[0]
-        elif k_cache.shape[0] != b:
-            raise RuntimeError(f"{who}: the caches hold {k_cache.shape[0]} rows for a batch of {b} (pass cache_batch_idx to select rows)")
-        else:
-            cbatch = 0
-        pages = (0, 0, 0)
-    if nnew > cap:
-        raise RuntimeError(f"{who}: N_new = {nnew} new tokens do not fit the capacity {cap}")
-    if rot and rotary_cos.shape[0] < cap + max(0, nq - nnew):
-        raise RuntimeError(f"{who}: rotary_cos / rotary_sin have {rotary_cos.shape[0]} rows; the capacity {cap} + max(0, Nq - N_new) = "
-                           f"{cap + max(0, nq - nnew)} are needed")
-    cache_seqlens = cache_seqlens.contiguous()
-    k_new, v_new = k_new.contiguous(), v_new.contiguous()
-    esz = q.element_size()
-    knb, knt = (x * esz for x in _kv_strides(who, "k", k_new, hkv, 128, False))
-    vnb, vnt = (x * esz for x in _kv_strides(who, "v", v_new, hkv, 128, False))
-    qdp, qds, keep_q = _kv_descale(who, "q_descale", q_descale, q, b, hkv)
-    kdp, kds, keep_k = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
-    vdp, vds, keep_v = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
-    mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks)
-    if not mod:
-        tail = (-1, -1, 0.0, 0, 0)
-    code = _E4M3_CODE if e4 else _DTYPE_CODE[q.dtype]
-    with torch.cuda.device(q.device):
-        o = torch.empty((b, nq, hq, 128), dtype=out_dtype, device=q.device)
-        lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)
-        if b == 0:
-            return o, lse
-        _tabs, rotary = _rotary_tables(rotary_cos, rotary_sin, rdim, rotary_interleaved)
-        need = int(_lib.fa_fp8_kvcache_step_workspace_bytes(b, hq, hkv, nq, cap, 128, ns, int(bool(causal)), tail[0], tail[1],
-                                                            int(sinks is not None), code, int(q8_out is not None)))
-        ws = _workspace(q.device, need)
-        q8 = (q8_out.data_ptr(), bstride(q8_out), tstride(q8_out, hq)) if q8_out is not None else (0, 0, 0)
-        _call("fa_fp8_kvcache_step", (
-            q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp, cache_seqlens.data_ptr(),
-            block_table.data_ptr() if paged else 0, cache_batch_idx.data_ptr() if cache_batch_idx is not None else 0, b, hq, hkv, nq, cap,
-            cbatch, 128, _DTYPE_CODE[out_dtype], code, _E4M3_CODE, bstride(q), tstride(q, hq), bstride(k_cache), tstride(k_cache, hkv),
-            bstride(v_cache), tstride(v_cache, hkv), *pages, qds, kds, vds, int(bool(causal)), scale, ns, ws.data_ptr(), ws.numel(),
-            _stream_ptr(q.device), *tail, k_new.data_ptr(), v_new.data_ptr(), nnew, knb, knt, vnb, vnt, code, *q8, *rotary))
-    del keep_q, keep_k, keep_v, keep_s, _tabs
-    return o, lse
+    if cu_seqlens_q is None and max_seqlen_q is None and cu_seqlens_k_new is None and not hdim:
+        # the padded step at 128 names what is no tensor in its own order: the new tokens before the caches
+        for name, t in (("q", q), ("k", k_new), ("v", v_new), ("k_cache", k_cache), ("v_cache", v_cache)):
+            if not isinstance(t, torch.Tensor):
+                raise RuntimeError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
+    return _fp8_kvcache_run(who, q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, cache_batch_idx, q_descale, k_descale,
+                            v_descale, softmax_scale, causal, num_splits, out_dtype, window, softcap, sinks, hdim, cu_seqlens_q,
+                            max_seqlen_q, cu_seqlens_k_new, rotary_cos, rotary_sin, rotary_interleaved, q8_out)
 
 
-def _fp8_kvcache_packed(who, q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, cache_batch_idx, q_descale, k_descale, v_descale,
-                        softmax_scale, causal, num_splits, out_dtype, window, softcap, sinks, cu_seqlens_q, max_seqlen_q, cu_seqlens_k_new,
-                        rotary_cos, rotary_sin, rotary_interleaved, q8_out):
-    """fp8_kvcache_forward (k_new is None) and fp8_kvcache_step through the _varlen entry points: packed queries (cu_seqlens_q), packed
-    or padded new keys, head dims 64 / 128 / 256.  The offsets are int32 (B + 1,) device tensors and are never read on the host."""
+def _fp8_kvcache_run(who, q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, cache_batch_idx, q_descale, k_descale, v_descale,
+                     softmax_scale, causal, num_splits, out_dtype, window, softcap, sinks, hdim, cu_seqlens_q, max_seqlen_q,
+                     cu_seqlens_k_new, rotary_cos, rotary_sin, rotary_interleaved, q8_out):
+    """Every form of fp8_kvcache_forward (k_new is None) and of fp8_kvcache_step: the rules in their one order, and the entry point.
+    varlen (packed queries or new keys, whose offsets are int32 (B + 1,) device tensors never read on the host, or the step under
+    hdim): the _varlen entry points, head dims 64 / 128 / 256, and `d` where the padded forms' messages say `128`.  The padded decode
+    call goes through fa_fp8_forward_kvcache, _mod (a feature) or _hdim (hdim), the padded step at 128 through fa_fp8_kvcache_step."""
     step = k_new is not None
+    varlen = cu_seqlens_q is not None or max_seqlen_q is not None or cu_seqlens_k_new is not None or (step and hdim)
+    wide = hdim or varlen                      # the head dims 64 / 128 / 256, and the trailing group always there
+    dn = "d" if varlen else "128"
     tensors = [("q", q), ("k_cache", k_cache), ("v_cache", v_cache)] + ([("k", k_new), ("v", v_new)] if step else [])
-    for name, t in tensors:
-        if not isinstance(t, torch.Tensor):
-            raise RuntimeError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
+    if varlen:                                 # (a padded call has named what is no tensor in its own words)
+        for name, t in tensors:
+            if not isinstance(t, torch.Tensor):
+                raise RuntimeError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
     packed = cu_seqlens_q is not None
     if max_seqlen_q is not None and not packed:
         raise RuntimeError(f"{who}: max_seqlen_q goes with cu_seqlens_q")
@@ -2814,26 +2612,29 @@ def _fp8_kvcache_packed(who, q, k_cache, v_cache, k_new, v_new, cache_seqlens, b
         raise RuntimeError(f"{who}: cu_seqlens_k_new needs cu_seqlens_q (packed new keys go with packed queries)")
     if packed and (isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int)):
         raise RuntimeError(f"{who}: max_seqlen_q (an int, the most query tokens of one sequence) is required with cu_seqlens_q")
-    if step:
-        if q.dtype not in (torch.float16, torch.bfloat16, torch.float8_e4m3fn):
-            raise NotImplementedError(f"{who}: q of dtype {q.dtype} is not supported (float16, bfloat16 or torch.float8_e4m3fn)")
-        if k_new.dtype != q.dtype or v_new.dtype != q.dtype:
-            raise NotImplementedError(f"{who}: mixed dtypes are not supported: q, k, v must be all float16, all bfloat16 or all "
-                                      f"torch.float8_e4m3fn (got {q.dtype}, {k_new.dtype}, {v_new.dtype})")
-    elif q.dtype != torch.float8_e4m3fn:
-        raise NotImplementedError(f"{who}: q of dtype {q.dtype} is not supported (torch.float8_e4m3fn expected)")
-    e4 = q.dtype == torch.float8_e4m3fn
-    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
-        if t.dtype != torch.float8_e4m3fn:
-            raise NotImplementedError(f"{who}: {name} of dtype {t.dtype} is not supported (torch.float8_e4m3fn expected)")
-    if e4 and (rotary_cos is not None or rotary_sin is not None):
-        raise NotImplementedError(f"{who}: rotary_cos / rotary_sin are not supported with torch.float8_e4m3fn q, k, v (codes cannot be rotated)")
-    if e4 and q8_out is not None:
-        raise NotImplementedError(f"{who}: q8_out is not supported with a torch.float8_e4m3fn q (it is used in place)")
-    if out_dtype is None:
-        out_dtype = torch.bfloat16 if e4 else q.dtype
-    if out_dtype not in (torch.bfloat16, torch.float16):
-        raise NotImplementedError(f"{who}: out_dtype {out_dtype} is not supported (torch.bfloat16 or torch.float16)")
+    if step or varlen:
+        if step:
+            if q.dtype not in (torch.float16, torch.bfloat16, torch.float8_e4m3fn):
+                raise NotImplementedError(f"{who}: q of dtype {q.dtype} is not supported (float16, bfloat16 or torch.float8_e4m3fn)")
+            if k_new.dtype != q.dtype or v_new.dtype != q.dtype:
+                raise NotImplementedError(f"{who}: mixed dtypes are not supported: q, k, v must be all float16, all bfloat16 or all "
+                                          f"torch.float8_e4m3fn (got {q.dtype}, {k_new.dtype}, {v_new.dtype})")
+        elif q.dtype != torch.float8_e4m3fn:
+            raise NotImplementedError(f"{who}: q of dtype {q.dtype} is not supported (torch.float8_e4m3fn expected)")
+        e4 = q.dtype == torch.float8_e4m3fn
+        for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+            if t.dtype != torch.float8_e4m3fn:
+                raise NotImplementedError(f"{who}: {name} of dtype {t.dtype} is not supported (torch.float8_e4m3fn expected)")
+        if e4 and (rotary_cos is not None or rotary_sin is not None):
+            raise NotImplementedError(f"{who}: rotary_cos / rotary_sin are not supported with torch.float8_e4m3fn q, k, v (codes cannot be rotated)")
+        if e4 and q8_out is not None:
+            raise NotImplementedError(f"{who}: q8_out is not supported with a torch.float8_e4m3fn q (it is used in place)")
+        if out_dtype is None:
+            out_dtype = torch.bfloat16 if e4 else q.dtype
+        if out_dtype not in (torch.bfloat16, torch.float16):
+            raise NotImplementedError(f"{who}: out_dtype {out_dtype} is not supported (torch.bfloat16 or torch.float16)")
+    else:
+        e4 = True                              # (the padded decode call has held q, the caches and out_dtype to its own rules)
     paged = block_table is not None
     if paged and cache_batch_idx is not None:
         raise NotImplementedError(f"{who}: block_table together with cache_batch_idx is not supported (a table row is the indirection)")
@@ -2844,10 +2645,16 @@ def _fp8_kvcache_packed(who, q, k_cache, v_cache, k_new, v_new, cache_seqlens, b
             raise NotImplementedError(f"{who}: {name} of dtype {dt} is not supported (int32 tensor expected)")
     qdim = 3 if packed else 4
     if q.dim() != qdim or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
-        raise RuntimeError(f"{who}: q must be " + ("packed (total_q, H_q, d)" if packed else "(B, Nq, H_q, d)") + " and k_cache, v_cache " +
-                           ("pools (num_blocks, page_block_size, H_kv, d)" if paged else "(B_cache, cache_len, H_kv, d)") +
+        raise RuntimeError(f"{who}: q must be " + ("packed (total_q, H_q, d)" if packed else f"(B, Nq, H_q, {dn})") + " and k_cache, v_cache " +
+                           (f"pools (num_blocks, page_block_size, H_kv, {dn})" if paged else f"(B_cache, cache_len, H_kv, {dn})") +
                            f" of one shape; got {tuple(q.shape)}, {tuple(k_cache.shape)}, {tuple(v_cache.shape)}")
-    d = _fp8_head_dim(who, True, **dict(tensors))
+    if wide:
+        d = _fp8_head_dim(who, True, **dict(tensors))
+    else:
+        d = 128
+        for name, t in tensors:
+            if t.shape[-1] != 128:
+                raise NotImplementedError(f"{who}: head_dim {t.shape[-1]} is not supported (128 only); got {name} of shape {tuple(t.shape)}")
     hq, hkv = q.shape[-2], k_cache.shape[2]
     if hkv == 0 or hq == 0 or hq % hkv != 0:
         raise RuntimeError(f"{who}: H_q = {hq} must be a multiple of H_kv = {hkv}")
@@ -2871,7 +2678,7 @@ def _fp8_kvcache_packed(who, q, k_cache, v_cache, k_new, v_new, cache_seqlens, b
             total_kn = k_new.shape[0]
         else:
             if k_new.dim() != 4 or k_new.shape[0] != b or k_new.shape[1] < 1 or k_new.shape[2] != hkv or v_new.shape != k_new.shape:
-                raise RuntimeError(f"{who}: k and v must be (B, N_new >= 1, H_kv, d) = ({b}, ., {hkv}, {d}) tensors of one shape; got "
+                raise RuntimeError(f"{who}: k and v must be (B, N_new >= 1, H_kv, {dn}) = ({b}, ., {hkv}, {d}) tensors of one shape; got "
                                    f"{tuple(k_new.shape)}, {tuple(v_new.shape)}")
             nnew = k_new.shape[1]
         if cache_seqlens is None:
@@ -2880,7 +2687,8 @@ def _fp8_kvcache_packed(who, q, k_cache, v_cache, k_new, v_new, cache_seqlens, b
         cache_seqlens = torch.full((b,), cache_seqlens, dtype=torch.int32, device=q.device)
     if cache_seqlens is not None and not (isinstance(cache_seqlens, torch.Tensor) and cache_seqlens.dtype == torch.int32 and
                                           cache_seqlens.shape == (b,)):
-        raise RuntimeError(f"{who}: cache_seqlens must be an int32 tensor of shape (B,) = ({b},), an int or None")
+        raise RuntimeError(f"{who}: cache_seqlens must be an int32 tensor of shape (B,) = ({b},)" +
+                           (" or an int" if step and not varlen else ", an int or None"))
     rot = rotary_cos is not None or rotary_sin is not None
     rdim = 0
     if rot:
@@ -2895,60 +2703,32 @@ def _fp8_kvcache_packed(who, q, k_cache, v_cache, k_new, v_new, cache_seqlens, b
             raise RuntimeError(f"{who}: rotary_dim = 2 * rotary_cos.shape[1] must be a multiple of 16 in [16, {d}], got {rdim}")
     if q8_out is not None and not (isinstance(q8_out, torch.Tensor) and q8_out.dtype == torch.float8_e4m3fn and q8_out.shape == q.shape):
         raise RuntimeError(f"{who}: q8_out must be a torch.float8_e4m3fn tensor of q's shape {tuple(q.shape)}")
-    every = [t for t in (q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, cache_batch_idx, cu_seqlens_q, cu_seqlens_k_new,
-                         rotary_cos, rotary_sin, q8_out) if t is not None]
-    for t in every:
-        if not t.is_cuda:
-            raise RuntimeError(f"{who}: tensors must be on the GPU (HIP device); there is no CPU path")
-    if len({t.device for t in every}) != 1:
-        raise RuntimeError(f"{who}: all tensors must be on one device")
+    _one_device(who, q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, cache_batch_idx, cu_seqlens_q, cu_seqlens_k_new,
+                rotary_cos, rotary_sin, q8_out)
     scale = d ** -0.5 if softmax_scale is None else float(softmax_scale)
     if not (math.isfinite(scale) and scale > 0.0):
         raise RuntimeError(f"{who}: softmax_scale must be finite and > 0 (got {scale})")
     ns = operator.index(num_splits)
     if ns < 0 or ns > 256:
         raise RuntimeError(f"{who}: num_splits must lie in [0, 256] (got {ns})")
-    # views: (tensor, heads, the dim of its tokens); a batch dim, where there is one, is dim 0
+    # views: (tensor, heads, the dim of its tokens); a batch dim, where there is one, is dim 0.  Each tensor's strides are read once;
+    # bytes[name] is its (batch stride, token stride) in bytes as the C call takes them
     views = [("q", q, hq, qdim - 3), ("k_cache", k_cache, hkv, 1), ("v_cache", v_cache, hkv, 1)]
     if q8_out is not None:
         views.append(("q8_out", q8_out, hq, qdim - 3))
+    bytes_ = {}
     for name, t, heads, tdim in views:
-        unit = 16 // t.element_size()
-        if t.numel() and ((heads > 1 and t.stride(-2) != d) or t.stride(-1) != 1):
-            raise ValueError(f"{who}: {name} must have adjacent heads with a contiguous last dim (strides {t.stride()})")
-        if t.numel() and (t.data_ptr() % 16 != 0 or any(t.stride(i) % unit != 0 or t.stride(i) < 0 for i in range(tdim + 1)) or
-                          (t.shape[tdim] > 1 and t.stride(tdim) < heads * d)):
-            raise ValueError(f"{who}: {name} is a view the kernel cannot address: a 16-byte aligned start, batch and token strides that "
-                             f"are multiples of 16 bytes and rows that do not overlap are needed (strides {t.stride()})")
-    bstride = lambda t: (max(t.stride(0), 0) if t.dim() == 4 and t.shape[0] > 1 else 0) * t.element_size()   # noqa: E731
-    tstride = lambda t, heads: (t.stride(-3) if t.shape[-3] > 1 else heads * d) * t.element_size()   # noqa: E731
-    if paged:
-        nblk, ps = k_cache.shape[0], k_cache.shape[1]
-        if ps < 16 or ps % 16 != 0:
-            raise RuntimeError(f"{who}: page_block_size must be a positive multiple of 16, got {ps}")
-        if block_table.dim() != 2 or block_table.shape[0] != b or block_table.shape[1] < 1:
-            raise RuntimeError(f"{who}: block_table must be an int32 (B, max_blocks_per_seq >= 1) tensor, B = {b}; got "
-                               f"{tuple(block_table.shape)}")
-        if nblk < 1:
-            raise RuntimeError(f"{who}: the pools must hold at least one page")
-        if block_table.stride(1) != 1 and block_table.shape[1] > 1:
-            block_table = block_table.contiguous()
-        cap, cbatch = block_table.shape[1] * ps, 0
-        pages = (max(block_table.stride(0), block_table.shape[1]), nblk, ps)
-    else:
-        cap = k_cache.shape[1]
-        if cap < 1:
-            raise RuntimeError(f"{who}: the caches must hold at least one token")
-        if cache_batch_idx is not None:
-            if cache_batch_idx.shape != (b,):
-                raise RuntimeError(f"{who}: cache_batch_idx must be an int32 tensor of shape (B,) = ({b},)")
-            cache_batch_idx = cache_batch_idx.contiguous()
-            cbatch = k_cache.shape[0]
-        elif k_cache.shape[0] != b:
-            raise RuntimeError(f"{who}: the caches hold {k_cache.shape[0]} rows for a batch of {b} (pass cache_batch_idx to select rows)")
-        else:
-            cbatch = 0
-        pages = (0, 0, 0)
+        st, esz = t.stride(), t.element_size()
+        unit = 16 // esz
+        if t.numel():
+            if (heads > 1 and st[-2] != d) or st[-1] != 1:
+                raise ValueError(f"{who}: {name} must have adjacent heads with a contiguous last dim (strides {st})")
+            if t.data_ptr() % 16 != 0 or st[0] % unit != 0 or st[0] < 0 or (tdim == 1 and (st[1] % unit != 0 or st[1] < 0)) or \
+                    (t.shape[tdim] > 1 and st[tdim] < heads * d):
+                raise ValueError(f"{who}: {name} is a view the kernel cannot address: a 16-byte aligned start, batch and token strides that "
+                                 f"are multiples of 16 bytes and rows that do not overlap are needed (strides {st})")
+        bytes_[name] = ((max(st[0], 0) if tdim == 1 and t.shape[0] > 1 else 0) * esz, (st[tdim] if t.shape[tdim] > 1 else heads * d) * esz)
+    block_table, cache_batch_idx, cap, cbatch, pages = _fp8_cache_geometry(who, k_cache, block_table, cache_batch_idx, b)
     if step and not packed_kn and nnew > cap:
         raise RuntimeError(f"{who}: N_new = {nnew} new tokens do not fit the capacity {cap}")
     ro_need = cap + (max_seqlen_q if packed else max(0, nq - nnew))
@@ -2964,8 +2744,9 @@ def _fp8_kvcache_packed(who, q, k_cache, v_cache, k_new, v_new, cache_seqlens, b
     qdp, qds, keep_q = _kv_descale(who, "q_descale", q_descale, q, b, hkv)
     kdp, kds, keep_k = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
     vdp, vds, keep_v = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
-    _mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks, True)
+    mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks, wide)
     code = _E4M3_CODE if e4 else _DTYPE_CODE[q.dtype]
+    cz, sk = int(bool(causal)), int(sinks is not None)
     with torch.cuda.device(q.device):
         o = torch.empty((total_q, hq, d) if packed else (b, nq, hq, d), dtype=out_dtype, device=q.device)
         lse = torch.empty((hq, total_q) if packed else (b, hq, nq), dtype=torch.float32, device=q.device)
@@ -2974,19 +2755,21 @@ def _fp8_kvcache_packed(who, q, k_cache, v_cache, k_new, v_new, cache_seqlens, b
         head = (q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp,
                 cache_seqlens.data_ptr() if cache_seqlens is not None else 0, block_table.data_ptr() if paged else 0,
                 cache_batch_idx.data_ptr() if cache_batch_idx is not None else 0, b, hq, hkv, nq, cap, cbatch, d, _DTYPE_CODE[out_dtype], code,
-                _E4M3_CODE, bstride(q), tstride(q, hq), bstride(k_cache), tstride(k_cache, hkv), bstride(v_cache), tstride(v_cache, hkv),
-                *pages, qds, kds, vds, int(bool(causal)), scale, ns)
-        group = (cu_seqlens_q.data_ptr() if packed else 0, total_q, max_seqlen_q)
+                _E4M3_CODE, *bytes_["q"], *bytes_["k_cache"], *bytes_["v_cache"], *pages, qds, kds, vds, cz, scale, ns)
+        group = (cu_seqlens_q.data_ptr() if packed else 0, total_q, max_seqlen_q) if varlen else ()
         if not step:
-            if packed:
-                need = int(_lib.fa_fp8_forward_kvcache_varlen_workspace_bytes(b, hq, hkv, total_q, max_seqlen_q, cap, d, ns, int(bool(causal)),
-                                                                              tail[0], tail[1], int(sinks is not None)))
+            if varlen:
+                need = int(_lib.fa_fp8_forward_kvcache_varlen_workspace_bytes(b, hq, hkv, total_q, max_seqlen_q, cap, d, ns, cz, tail[0], tail[1],
+                                                                              sk))
+            elif hdim:
+                need = int(_lib.fa_fp8_forward_kvcache_hdim_workspace_bytes(b, hq, hkv, nq, cap, d, ns, cz, tail[0], tail[1], sk))
+            elif mod:
+                need = int(_lib.fa_fp8_forward_kvcache_workspace_bytes_mod(b, hq, hkv, nq, cap, d, ns, cz, tail[0], tail[1], sk))
             else:
-                need = int(_lib.fa_fp8_forward_kvcache_hdim_workspace_bytes(b, hq, hkv, nq, cap, d, ns, int(bool(causal)), tail[0], tail[1],
-                                                                            int(sinks is not None)))
+                need = int(_lib.fa_fp8_forward_kvcache_workspace_bytes(b, hq, hkv, nq, cap, d, ns))
             ws = _workspace(q.device, need)
-            _call("fa_fp8_forward_kvcache_varlen", (*head, ws.data_ptr() if need else 0, ws.numel() if need else 0, _stream_ptr(q.device),
-                                                    *tail, *group))
+            _call("fa_fp8_forward_kvcache" + ("_varlen" if varlen else mod),
+                  (*head, ws.data_ptr() if need else 0, ws.numel() if need else 0, _stream_ptr(q.device), *tail, *group))
         else:
             k_new, v_new = k_new.contiguous(), v_new.contiguous()
             esz = q.element_size()
@@ -2997,14 +2780,19 @@ def _fp8_kvcache_packed(who, q, k_cache, v_cache, k_new, v_new, cache_seqlens, b
                 knb, knt = (x * esz for x in _kv_strides(who, "k", k_new, hkv, d, False))
                 vnb, vnt = (x * esz for x in _kv_strides(who, "v", v_new, hkv, d, False))
             _tabs, rotary = _rotary_tables(rotary_cos, rotary_sin, rdim, rotary_interleaved)
-            need = int(_lib.fa_fp8_kvcache_step_varlen_workspace_bytes(b, hq, hkv, nq, cap, d, ns, int(bool(causal)), tail[0], tail[1],
-                                                                       int(sinks is not None), code, int(q8_out is not None), total_q,
-                                                                       max_seqlen_q))
+            tail = tail or (-1, -1, 0.0, 0, 0)         # (the step's entry points always take the group)
+            if varlen:
+                need = int(_lib.fa_fp8_kvcache_step_varlen_workspace_bytes(b, hq, hkv, nq, cap, d, ns, cz, tail[0], tail[1], sk, code,
+                                                                           int(q8_out is not None), total_q, max_seqlen_q))
+            else:
+                need = int(_lib.fa_fp8_kvcache_step_workspace_bytes(b, hq, hkv, nq, cap, d, ns, cz, tail[0], tail[1], sk, code,
+                                                                    int(q8_out is not None)))
             ws = _workspace(q.device, need)
-            q8 = (q8_out.data_ptr(), bstride(q8_out), tstride(q8_out, hq)) if q8_out is not None else (0, 0, 0)
-            _call("fa_fp8_kvcache_step_varlen", (*head, ws.data_ptr(), ws.numel(), _stream_ptr(q.device), *tail, k_new.data_ptr(),
-                                                 v_new.data_ptr(), nnew, knb, knt, vnb, vnt, code, *q8, *rotary, *group,
-                                                 cu_seqlens_k_new.data_ptr() if packed_kn else 0, total_kn))
+            q8 = (q8_out.data_ptr(), *bytes_["q8_out"]) if q8_out is not None else (0, 0, 0)
+            packed_new = (cu_seqlens_k_new.data_ptr() if packed_kn else 0, total_kn) if varlen else ()
+            _call("fa_fp8_kvcache_step" + ("_varlen" if varlen else ""),
+                  (*head, ws.data_ptr(), ws.numel(), _stream_ptr(q.device), *tail, k_new.data_ptr(), v_new.data_ptr(), nnew, knb, knt, vnb,
+                   vnt, code, *q8, *rotary, *group, *packed_new))
             del _tabs
     del keep_q, keep_k, keep_v, keep_s
     return o, lse
@@ -3085,15 +2873,6 @@ def _fp4_lens(who, cache_seqlens, b, device, required):
     return cache_seqlens.contiguous()
 
 
-def _fp4_one_device(who, *tensors):
-    tensors = [t for t in tensors if t is not None]
-    for t in tensors:
-        if not t.is_cuda:
-            raise RuntimeError(f"{who}: tensors must be on the GPU (HIP device); there is no CPU path")
-    if len({t.device for t in tensors}) != 1:
-        raise RuntimeError(f"{who}: all tensors must be on one device")
-
-
 def fp4_kvcache_append(k_new, v_new, k_cache, k_scale, v_cache, v_scale, cache_seqlens, block_table=None, cache_batch_idx=None,
                        k_descale=None, v_descale=None):
     """Quantise new tokens to MXFP4 and append them to the cache, in place (fa_fp4_kvcache_append): k_new, v_new (B, N_new, H_kv, 128)
@@ -3119,7 +2898,7 @@ def fp4_kvcache_append(k_new, v_new, k_cache, k_scale, v_cache, v_scale, cache_s
     if k_new.shape[2] != hkv:
         raise RuntimeError(f"{who}: k_new has {k_new.shape[2]} heads, the caches {hkv}")
     cache_seqlens = _fp4_lens(who, cache_seqlens, b, k_new.device, True)
-    _fp4_one_device(who, k_new, v_new, *arrays, cache_seqlens, block_table, cache_batch_idx)
+    _one_device(who, k_new, v_new, *arrays, cache_seqlens, block_table, cache_batch_idx)
     new = []
     for name, t in (("k_new", k_new), ("v_new", v_new)):
         if t.numel() and ((hkv > 1 and t.stride(2) != 128) or t.stride(3) != 1):
@@ -3162,7 +2941,7 @@ def fp4_kvcache_forward(q, k_cache, k_scale, v_cache, v_scale, cache_seqlens=Non
     if hq == 0 or hq % hkv != 0:
         raise RuntimeError(f"{who}: H_q = {hq} must be a multiple of H_kv = {hkv}")
     cache_seqlens = _fp4_lens(who, cache_seqlens, b, q.device, False)
-    _fp4_one_device(who, q, *arrays, cache_seqlens, block_table, cache_batch_idx)
+    _one_device(who, q, *arrays, cache_seqlens, block_table, cache_batch_idx)
     scale = 128 ** -0.5 if softmax_scale is None else float(softmax_scale)
     if not (math.isfinite(scale) and scale > 0.0):
         raise RuntimeError(f"{who}: softmax_scale must be finite and > 0 (got {scale})")
@@ -3238,7 +3017,7 @@ def fp4_varlen_forward(q, k_cache, k_scale, v_cache, v_scale, cu_seqlens_q, cu_s
     arrays, hkv, cap, _cbatch, strides, pages, block_table, _ = _fp4_cache(who, k_cache, k_scale, v_cache, v_scale, block_table, None, b)
     if hq == 0 or hq % hkv != 0:
         raise RuntimeError(f"{who}: H_q = {hq} must be a multiple of H_kv = {hkv}")
-    _fp4_one_device(who, q, *arrays, cu_seqlens_q, cu_seqlens_k, block_table)
+    _one_device(who, q, *arrays, cu_seqlens_q, cu_seqlens_k, block_table)
     scale = 128 ** -0.5 if softmax_scale is None else float(softmax_scale)
     if not (math.isfinite(scale) and scale > 0.0):
         raise RuntimeError(f"{who}: softmax_scale must be finite and > 0 (got {scale})")

@@ -226,6 +226,39 @@ def test_the_shim_refuses_by_name():
         ext.fp8_kvcache_forward(q, kc, vc, block_table=torch.zeros((2, 4), dtype=torch.int64))
     with pytest.raises(RuntimeError, match="multiple of H_kv"):
         ext.fp8_kvcache_forward(q[:, :, :3], kc, vc)
+    # every further rule that fires before the device check, in the order the shim states them
+    i32, i64 = (lambda *s: torch.zeros(s, dtype=torch.int32)), (lambda *s: torch.zeros(s, dtype=torch.int64))   # noqa: E731
+    for exc, what, args, kw in (
+            (NotImplementedError, r"q of dtype int is not supported \(torch.float8_e4m3fn expected\)", (3, kc, vc), {}),
+            (NotImplementedError, r"v_cache of dtype NoneType is not supported \(torch.float8_e4m3fn expected\)", (q, kc, None), {}),
+            (NotImplementedError, r"out_dtype torch.float32 is not supported \(torch.bfloat16 or torch.float16\)", (q, kc, vc),
+             dict(out_dtype=torch.float32)),
+            (NotImplementedError, r"block_table together with cache_batch_idx is not supported \(a table row is the indirection\)", (q, kc, vc),
+             dict(block_table=i32(2, 4), cache_batch_idx=i32(2), out_dtype=torch.float16)),
+            (NotImplementedError, r"cache_batch_idx of dtype torch.int64 is not supported \(int32 tensor expected\)", (q, kc, vc),
+             dict(cache_batch_idx=i64(2))),
+            (NotImplementedError, r"block_table of dtype list is not supported \(int32 tensor expected\)", (q, kc, vc), dict(block_table=[[0]])),
+            (RuntimeError, r"q must be \(B, Nq, H_q, 128\) and k_cache, v_cache \(B_cache, cache_len, H_kv, 128\) of one shape; got "
+                           r"\(2, 4, 128\), \(2, 64, 2, 128\), \(2, 64, 2, 128\)", (q[:, 0], kc, vc), {}),
+            (RuntimeError, r"q must be \(B, Nq, H_q, 128\) and k_cache, v_cache pools \(num_blocks, page_block_size, H_kv, 128\) of one shape; got",
+             (q, kc, vc[:, :32]), dict(block_table=i32(2, 4), hdim=True)),
+            (NotImplementedError, r"head_dim 64 is not supported \(128 only\); got q of shape \(2, 1, 4, 64\)", (q[..., :64], kc, vc), {}),
+            (NotImplementedError, r"head_dim 64 is not supported \(128 only\); got k_cache of shape \(2, 64, 2, 64\)", (q, kc[..., :64], vc[..., :64]), {}),
+            (RuntimeError, r"mixed head dims: q has 64, k_cache has 128, v_cache has 128 \(q, k and v must agree", (q[..., :64], kc, vc),
+             dict(hdim=True)),
+            (NotImplementedError, r"head_dim 96 is not supported \(64, 128 or 256\)", (q[..., :96], kc[..., :96], vc[..., :96]), dict(hdim=True)),
+            (RuntimeError, r"H_q = 3 must be a multiple of H_kv = 2", (q[:, :, :3, :64], kc[..., :64], vc[..., :64]), dict(hdim=True)),
+            (RuntimeError, r"cache_seqlens must be an int32 tensor of shape \(B,\) = \(2,\), an int or None", (q, kc, vc),
+             dict(cache_seqlens=i64(2))),
+            (RuntimeError, r"cache_seqlens must be an int32 tensor of shape \(B,\) = \(2,\), an int or None", (q, kc, vc),
+             dict(cache_seqlens=i32(3), hdim=True)),
+            (RuntimeError, r"cache_seqlens must be an int32 tensor of shape \(B,\) = \(2,\), an int or None", (q, kc, vc),
+             dict(cache_seqlens=True)),
+            # what comes after the device check is not looked at: the scale, the splits, the views, the cache's geometry
+            (RuntimeError, "tensors must be on the GPU", (q, kc, vc), dict(cache_seqlens=5, softmax_scale=-1.0, num_splits=999)),
+            (RuntimeError, "tensors must be on the GPU", (q, kc[:1], vc[:1]), dict(hdim=True, block_table=i32(2, 0)))):
+        with pytest.raises(exc, match="fp8_kvcache_forward: " + what):
+            ext.fp8_kvcache_forward(*args, **kw)
     with pytest.raises(RuntimeError, match="must be on the GPU"):
         ext.fp8_kvcache_forward(q, kc, vc)
 

@@ -342,6 +342,170 @@ def test_the_shim_keywords():
         ext.fp8_kvcache_step(bf(2, 1, 2, 64), _f8(2, 16, 2, 64), _f8(2, 16, 2, 64), bf(2, 1, 2, 64), bf(2, 1, 2, 64), 3)
 
 
+def test_the_shim_rules_before_the_device_check_in_their_order():
+    """every rule of fp8_kvcache_step (padded at 128; hdim; packed) and of the packed fp8_kvcache_forward that fires before the device
+    check, by its full words; a row with two faults names the rule that comes first"""
+    import flashattention_lab_cuda as ext
+
+    cu = torch.tensor([0, 1, 4], dtype=torch.int32)
+    bf = lambda *s: torch.zeros(s, dtype=torch.bfloat16)   # noqa: E731
+    hf = lambda *s: torch.zeros(s, dtype=torch.float16)   # noqa: E731
+    i32, i64 = (lambda *s: torch.zeros(s, dtype=torch.int32)), (lambda *s: torch.zeros(s, dtype=torch.int64))   # noqa: E731
+    NI, RT = NotImplementedError, RuntimeError
+
+    # ---- the padded step at 128: (q, k_cache, v_cache, k_new, v_new, cache_seqlens), keywords
+    q, kc, k = bf(2, 1, 4, 128), _f8(2, 16, 2, 128), bf(2, 1, 2, 128)
+    q8, k8 = _f8(2, 1, 4, 128), _f8(2, 1, 2, 128)
+    cos = bf(20, 16)
+    for exc, what, args, kw in (
+            (RT, r"k must be a tensor, got int", (q, 3, kc, 5, k, 3), {}),                      # (the new tokens before the caches)
+            (RT, r"q must be a tensor, got NoneType", (None, kc, kc, k, 5, 3), {}),
+            (RT, r"v_cache must be a tensor, got list", (q, kc, [], k, k, 3), {}),
+            (NI, r"q of dtype torch.float32 is not supported \(float16, bfloat16 or torch.float8_e4m3fn\)", (q.float(), kc, kc, k, k, 3), {}),
+            (NI, r"mixed dtypes are not supported: q, k, v must be all float16, all bfloat16 or all torch.float8_e4m3fn \(got torch.bfloat16, "
+                 r"torch.bfloat16, torch.float16\)", (q, kc, kc, k, k.half(), 3), {}),
+            (NI, r"v_cache of dtype torch.bfloat16 is not supported \(torch.float8_e4m3fn expected\)", (q, kc, bf(2, 16, 2, 128), k, k, 3), {}),
+            (NI, r"rotary_cos / rotary_sin are not supported with torch.float8_e4m3fn q, k, v \(codes cannot be rotated\)",
+             (q8, kc, kc, k8, k8, 3), dict(rotary_sin=cos, q8_out=q8)),
+            (NI, r"q8_out is not supported with a torch.float8_e4m3fn q \(it is used in place\)", (q8, kc, kc, k8, k8, 3),
+             dict(q8_out=q8, out_dtype=torch.float32)),
+            (NI, r"out_dtype torch.float32 is not supported \(torch.bfloat16 or torch.float16\)", (q, kc, kc, k, k, 3),
+             dict(out_dtype=torch.float32, block_table=i32(2, 1), cache_batch_idx=i32(2))),
+            (NI, r"block_table together with cache_batch_idx is not supported \(a table row is the indirection\)", (q, kc, kc, k, k, 3),
+             dict(block_table=i64(2, 1), cache_batch_idx=i32(2))),
+            (NI, r"cache_batch_idx of dtype torch.int64 is not supported \(int32 tensor expected\)", (q, kc, kc, k, k, 3),
+             dict(cache_batch_idx=i64(2))),
+            (RT, r"q must be \(B, Nq, H_q, 128\) and k_cache, v_cache \(B_cache, cache_len, H_kv, 128\) of one shape; got \(2, 4, 128\), "
+                 r"\(2, 16, 2, 128\), \(2, 16, 2, 128\)", (q[:, 0], kc, kc, k, k, 3), {}),
+            (RT, r"q must be \(B, Nq, H_q, 128\) and k_cache, v_cache pools \(num_blocks, page_block_size, H_kv, 128\) of one shape; got",
+             (q, kc, kc[:1], k, k, 3), dict(block_table=i32(2, 1))),
+            (NI, r"head_dim 64 is not supported \(128 only\); got k_cache of shape \(2, 16, 2, 64\)",
+             (q, kc[..., :64], kc[..., :64], k[..., :64], k, 3), {}),
+            (NI, r"head_dim 64 is not supported \(128 only\); got k of shape \(2, 1, 2, 64\)", (q[:, :, :3], kc, kc, k[..., :64], k, 3), {}),
+            (RT, r"H_q = 3 must be a multiple of H_kv = 2", (q[:, :, :3], kc, kc, k[0], k, None), {}),
+            (RT, r"k and v must be \(B, N_new >= 1, H_kv, 128\) = \(2, ., 2, 128\) tensors of one shape; got \(1, 2, 128\), \(2, 1, 2, 128\)",
+             (q, kc, kc, k[0], k, None), {}),
+            (RT, r"k and v must be \(B, N_new >= 1, H_kv, 128\) = \(2, ., 2, 128\) tensors of one shape; got \(2, 0, 2, 128\)",
+             (q, kc, kc, k[:, :0], k[:, :0], 3), {}),
+            (RT, r"k and v must be \(B, N_new >= 1, H_kv, 128\)", (q, kc, kc, k, bf(2, 2, 2, 128), 3), {}),
+            (RT, r"cache_seqlens is required \(the lengths before the append: an int32 \(B,\) tensor or an int\)", (q, kc, kc, k, k, None),
+             dict(rotary_cos=cos)),
+            (RT, r"cache_seqlens must be an int32 tensor of shape \(B,\) = \(2,\) or an int$", (q, kc, kc, k, k, i64(2)), dict(rotary_cos=cos)),
+            (RT, r"cache_seqlens must be an int32 tensor of shape \(B,\) = \(2,\) or an int$", (q, kc, kc, k, k, True), {}),
+            (RT, r"rotary_cos and rotary_sin must be given together", (q, kc, kc, k, k, 3), dict(rotary_cos=cos, q8_out=q8[:1])),
+            (RT, r"rotary_sin must be a \(seqlen_ro, rotary_dim / 2\) tensor of q's dtype, rotary_cos and rotary_sin of one shape",
+             (q, kc, kc, k, k, 3), dict(rotary_cos=cos, rotary_sin=bf(20, 8))),
+            (RT, r"rotary_cos must be a \(seqlen_ro, rotary_dim / 2\) tensor of q's dtype", (q, kc, kc, k, k, 3),
+             dict(rotary_cos=hf(20, 16), rotary_sin=hf(20, 16))),
+            (RT, r"rotary_dim = 2 \* rotary_cos.shape\[1\] must be a multiple of 16 in \[16, 128\], got 144", (q, kc, kc, k, k, 3),
+             dict(rotary_cos=bf(20, 72), rotary_sin=bf(20, 72))),
+            (RT, r"rotary_dim = 2 \* rotary_cos.shape\[1\] must be a multiple of 16 in \[16, 128\], got 8", (q, kc, kc, k, k, 3),
+             dict(rotary_cos=bf(20, 4), rotary_sin=bf(20, 4))),
+            (RT, r"q8_out must be a torch.float8_e4m3fn tensor of q's shape \(2, 1, 4, 128\)", (q, kc, kc, k, k, 3), dict(q8_out=q8[:1])),
+            (RT, r"q8_out must be a torch.float8_e4m3fn tensor of q's shape", (q, kc, kc, k, k, 3), dict(q8_out=q)),
+            # what comes after the device check is not looked at: the scale, the splits, the views, the geometry, the tables' rows
+            (RT, r"tensors must be on the GPU \(HIP device\); there is no CPU path", (q, kc, kc, bf(2, 99, 2, 128), bf(2, 99, 2, 128), 3),
+             dict(softmax_scale=0.0, num_splits=-1, rotary_cos=bf(1, 16), rotary_sin=bf(1, 16), q8_out=q8, window=(3, 0), sinks=5))):
+        with pytest.raises(exc, match="fp8_kvcache_step: " + what):
+            ext.fp8_kvcache_step(*args, **kw)
+
+    # ---- the step through the _varlen route: hdim=True (padded, 64 wide) and packed
+    q, kc, k = bf(2, 1, 4, 64), _f8(2, 16, 2, 64), bf(2, 1, 2, 64)
+    pq, pk, pq8 = bf(4, 4, 64), bf(3, 2, 64), _f8(4, 4, 64)
+    H, PK, PQ = dict(hdim=True), dict(cu_seqlens_q=cu, max_seqlen_q=3, cu_seqlens_k_new=cu), dict(cu_seqlens_q=cu, max_seqlen_q=3)
+    for exc, what, args, kw in (
+            (RT, r"k_cache must be a tensor, got int", (q, 3, kc, 5, k, 3), H),                  # (the caches before the new tokens)
+            (RT, r"k must be a tensor, got int", (q, kc, kc, 5, None, 3), H),
+            (RT, r"max_seqlen_q goes with cu_seqlens_q", (q.float(), kc, kc, k, k, 3), dict(max_seqlen_q=3, cu_seqlens_k_new=cu)),
+            (RT, r"cu_seqlens_k_new needs cu_seqlens_q \(packed new keys go with packed queries\)", (q.float(), kc, kc, k, k, 3),
+             dict(cu_seqlens_k_new=cu)),
+            (RT, r"max_seqlen_q \(an int, the most query tokens of one sequence\) is required with cu_seqlens_q", (pq.float(), kc, kc, pk, pk, 3),
+             dict(cu_seqlens_q=cu, max_seqlen_q=True)),
+            (NI, r"q of dtype torch.float32 is not supported \(float16, bfloat16 or torch.float8_e4m3fn\)", (q.float(), kc, kc, k, k, 3), H),
+            (NI, r"mixed dtypes are not supported: q, k, v must be all float16, all bfloat16 or all torch.float8_e4m3fn \(got torch.bfloat16, "
+                 r"torch.float16, torch.bfloat16\)", (pq, kc, kc, pk.half(), pk, 3), PK),
+            (NI, r"k_cache of dtype torch.uint8 is not supported \(torch.float8_e4m3fn expected\)", (q, kc.view(torch.uint8), kc, k, k, 3), H),
+            (NI, r"rotary_cos / rotary_sin are not supported with torch.float8_e4m3fn q, k, v \(codes cannot be rotated\)",
+             (pq8, kc, kc, _f8(3, 2, 64), _f8(3, 2, 64), 3), dict(PK, rotary_cos=bf(20, 16), q8_out=pq8)),
+            (NI, r"q8_out is not supported with a torch.float8_e4m3fn q \(it is used in place\)", (pq8, kc, kc, _f8(3, 2, 64), _f8(3, 2, 64), 3),
+             dict(PK, q8_out=pq8, out_dtype=torch.float32)),
+            (NI, r"out_dtype torch.float32 is not supported \(torch.bfloat16 or torch.float16\)", (q, kc, kc, k, k, 3),
+             dict(H, out_dtype=torch.float32, block_table=i32(2, 1), cache_batch_idx=i32(2))),
+            (NI, r"block_table together with cache_batch_idx is not supported \(a table row is the indirection\)", (q, kc, kc, k, k, 3),
+             dict(H, block_table=i64(2, 1), cache_batch_idx=i32(2))),
+            (NI, r"block_table of dtype torch.int64 is not supported \(int32 tensor expected\)", (pq, kc, kc, pk, pk, 3),
+             dict(PK, block_table=i64(2, 1), cu_seqlens_q=cu.long())),
+            (NI, r"cu_seqlens_q of dtype torch.int64 is not supported \(int32 tensor expected\)", (pq, kc, kc, pk, pk, 3),
+             dict(PK, cu_seqlens_q=cu.long(), cu_seqlens_k_new=cu.long())),
+            (NI, r"cu_seqlens_k_new of dtype list is not supported \(int32 tensor expected\)", (pq, kc, kc, pk, pk, 3),
+             dict(PK, cu_seqlens_k_new=[0, 1, 4])),
+            (RT, r"q must be \(B, Nq, H_q, d\) and k_cache, v_cache \(B_cache, cache_len, H_kv, d\) of one shape; got \(4, 4, 64\), "
+                 r"\(2, 16, 2, 64\), \(2, 16, 2, 64\)", (pq, kc, kc, k, k, 3), H),
+            (RT, r"q must be packed \(total_q, H_q, d\) and k_cache, v_cache pools \(num_blocks, page_block_size, H_kv, d\) of one shape; got "
+                 r"\(2, 1, 4, 64\)", (q, kc, kc, pk, pk, 3), dict(PK, block_table=i32(2, 1))),
+            (RT, r"mixed head dims: q has 64, k_cache has 64, v_cache has 64, k has 128, v has 64 \(q, k and v must agree in their last extent\)",
+             (q, kc, kc, bf(2, 1, 2, 128), k, 3), H),
+            (NI, r"head_dim 32 is not supported \(64, 128 or 256\)", (q[..., :32], kc[..., :32], kc[..., :32], k[..., :32], k[..., :32], 3), H),
+            (RT, r"H_q = 3 must be a multiple of H_kv = 2", (pq[:, :3], kc, kc, pk, pk, None), dict(PK, cu_seqlens_q=cu[None])),
+            (RT, r"cu_seqlens_q must be an int32 \(B \+ 1,\) tensor, got \(1, 3\)", (pq, kc, kc, pk, pk, None),
+             dict(PK, cu_seqlens_q=cu[None], max_seqlen_q=9)),
+            (RT, r"cu_seqlens_q must be an int32 \(B \+ 1,\) tensor, got \(0,\)", (pq, kc, kc, pk, pk, None), dict(PK, cu_seqlens_q=cu[:0])),
+            (RT, r"max_seqlen_q = 5 must lie in \[0, total_q = 4\]", (pq, kc, kc, pk, pk, None), dict(PK, max_seqlen_q=5, cu_seqlens_k_new=cu[:2])),
+            (RT, r"max_seqlen_q = -1 must lie in \[0, total_q = 4\]", (pq, kc, kc, pk, pk, None), dict(PK, max_seqlen_q=-1)),
+            (RT, r"cu_seqlens_k_new must be an int32 \(B \+ 1,\) = \(3,\) tensor, got \(2,\)", (pq, kc, kc, k, k, None),
+             dict(PK, cu_seqlens_k_new=cu[:2])),
+            (RT, r"k and v must be packed \(total_k_new, H_kv, d\) = \(., 2, 64\) tensors of one shape; got \(2, 1, 2, 64\), \(2, 1, 2, 64\)",
+             (pq, kc, kc, k, k, None), PK),
+            (RT, r"k and v must be packed \(total_k_new, H_kv, d\)", (pq, kc, kc, pk, bf(5, 2, 64), None), PK),
+            (RT, r"k and v must be \(B, N_new >= 1, H_kv, d\) = \(2, ., 2, 64\) tensors of one shape; got \(3, 2, 64\), \(3, 2, 64\)",
+             (pq, kc, kc, pk, pk, None), PQ),
+            (RT, r"k and v must be \(B, N_new >= 1, H_kv, d\) = \(2, ., 2, 64\) tensors of one shape; got \(2, 0, 2, 64\)",
+             (q, kc, kc, k[:, :0], k[:, :0], None), H),
+            (RT, r"cache_seqlens is required \(the lengths before the append: an int32 \(B,\) tensor or an int\)", (pq, kc, kc, pk, pk, None),
+             dict(PK, rotary_cos=bf(20, 16))),
+            (RT, r"cache_seqlens must be an int32 tensor of shape \(B,\) = \(2,\), an int or None", (q, kc, kc, k, k, i32(3)),
+             dict(H, rotary_cos=bf(20, 16))),
+            (RT, r"cache_seqlens must be an int32 tensor of shape \(B,\) = \(2,\), an int or None", (pq, kc, kc, pk, pk, False), PK),
+            (RT, r"rotary_cos and rotary_sin must be given together", (pq, kc, kc, pk, pk, 3), dict(PK, rotary_sin=bf(20, 16), q8_out=pq8[:1])),
+            (RT, r"rotary_cos must be a \(seqlen_ro, rotary_dim / 2\) tensor of q's dtype, rotary_cos and rotary_sin of one shape",
+             (q, kc, kc, k, k, 3), dict(H, rotary_cos=bf(0, 16), rotary_sin=bf(0, 16))),
+            (RT, r"rotary_dim = 2 \* rotary_cos.shape\[1\] must be a multiple of 16 in \[16, 64\], got 96", (pq, kc, kc, pk, pk, 3),
+             dict(PK, rotary_cos=bf(20, 48), rotary_sin=bf(20, 48))),
+            (RT, r"q8_out must be a torch.float8_e4m3fn tensor of q's shape \(4, 4, 64\)", (pq, kc, kc, pk, pk, 3), dict(PK, q8_out=pq8[:2])),
+            (RT, r"q8_out must be a torch.float8_e4m3fn tensor of q's shape \(2, 1, 4, 64\)", (q, kc, kc, k, k, 3), dict(H, q8_out=pq8)),
+            (RT, r"tensors must be on the GPU \(HIP device\); there is no CPU path", (pq, kc, kc, bf(2, 99, 2, 64), bf(2, 99, 2, 64), 3),
+             dict(PQ, softmax_scale=0.0, num_splits=-1, rotary_cos=bf(1, 16), rotary_sin=bf(1, 16), q8_out=pq8, window=(3, 0), sinks=5))):
+        with pytest.raises(exc, match="fp8_kvcache_step: " + what):
+            ext.fp8_kvcache_step(*args, **kw)
+
+    # ---- the packed decode call: (q, k_cache, v_cache), keywords
+    pq = _f8(4, 4, 64)
+    for exc, what, args, kw in (
+            (RT, r"q must be a tensor, got int", (3, kc, kc), PQ),
+            (RT, r"v_cache must be a tensor, got NoneType", (pq.view(torch.uint8), kc, None), PQ),
+            (RT, r"max_seqlen_q \(an int, the most query tokens of one sequence\) is required with cu_seqlens_q", (bf(4, 4, 64), kc, kc),
+             dict(cu_seqlens_q=cu, max_seqlen_q=3.0)),
+            (NI, r"q of dtype torch.bfloat16 is not supported \(torch.float8_e4m3fn expected\)$", (bf(4, 4, 64), kc, kc), PQ),
+            (NI, r"v_cache of dtype torch.float16 is not supported \(torch.float8_e4m3fn expected\)", (pq, kc, hf(2, 16, 2, 64)), PQ),
+            (NI, r"out_dtype torch.float32 is not supported \(torch.bfloat16 or torch.float16\)", (pq, kc, kc), dict(PQ, out_dtype=torch.float32)),
+            (NI, r"block_table together with cache_batch_idx is not supported", (pq, kc, kc), dict(PQ, block_table=3, cache_batch_idx=3)),
+            (NI, r"cache_batch_idx of dtype int is not supported \(int32 tensor expected\)", (pq, kc, kc), dict(PQ, cache_batch_idx=3)),
+            (RT, r"q must be packed \(total_q, H_q, d\) and k_cache, v_cache \(B_cache, cache_len, H_kv, d\) of one shape; got \(1, 4, 4, 64\)",
+             (pq[None], kc, kc), PQ),
+            (RT, r"q must be packed \(total_q, H_q, d\) and k_cache, v_cache \(B_cache, cache_len, H_kv, d\) of one shape; got",
+             (pq, kc, kc[:, :8]), PQ),
+            (RT, r"mixed head dims: q has 64, k_cache has 128, v_cache has 128", (pq, _f8(2, 16, 2, 128), _f8(2, 16, 2, 128)), PQ),
+            (RT, r"H_q = 4 must be a multiple of H_kv = 3", (pq, _f8(2, 16, 3, 64), _f8(2, 16, 3, 64)), PQ),
+            (RT, r"H_q = 4 must be a multiple of H_kv = 0", (pq, _f8(2, 16, 0, 64), _f8(2, 16, 0, 64)), PQ),
+            (RT, r"cu_seqlens_q must be an int32 \(B \+ 1,\) tensor, got \(\)", (pq, kc, kc), dict(PQ, cu_seqlens_q=cu[0])),
+            (RT, r"max_seqlen_q = 5 must lie in \[0, total_q = 4\]", (pq, kc, kc), dict(PQ, max_seqlen_q=5, cache_seqlens=i64(2))),
+            (RT, r"cache_seqlens must be an int32 tensor of shape \(B,\) = \(2,\), an int or None", (pq, kc, kc), dict(PQ, cache_seqlens=i64(2))),
+            (RT, r"tensors must be on the GPU \(HIP device\); there is no CPU path", (pq, kc, kc),
+             dict(PQ, cache_seqlens=2, softmax_scale=0.0, num_splits=-1, window=(3, 0), sinks=5))):
+        with pytest.raises(exc, match="fp8_kvcache_forward: " + what):
+            ext.fp8_kvcache_forward(*args, **kw)
+
+
 def test_the_older_wrappers_still_refuse_the_three_names():
     from common.attention_ex import flash_attention_fp8_kvcache, flash_attn_fp8_kvcache_step, flash_attn_fp8_with_kvcache
     from common.fp8_attention import fp8_attn_with_kvcache
