@@ -34,7 +34,7 @@ const char* const kKernelNames[fa::K_COUNT] = {"fwd_f32", "bwd_delta", "bwd_dkdv
                                                "idx_topk", "fp8kv_split", "fp8q_amax", "fp8q_quant", "fp8q_fused", "fp8in_fwd_mod",
                                                "fp8in_fwd_varlen_mod", "fp8kv_split_mod", "fp8kv_step_prep", "fp8in_fwd_hdim",
     "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim", "fp8kv_split_varlen", "fp8kv_step_prep_varlen", "fp4kv_append", "fp4kv_split",
-    "fp4kv_prefill", "fp4kv_split_mod", "fp4kv_prefill_mod"};
+    "fp4kv_prefill", "fp4kv_split_mod", "fp4kv_prefill_mod", "fp4kv_append_hdim", "fp4kv_split_hdim", "fp4kv_prefill_hdim"};
 
 hipEvent_t prof_get_event() {
     if (!g_prof_free.empty()) { hipEvent_t e = g_prof_free.back(); g_prof_free.pop_back(); return e; }
@@ -182,7 +182,7 @@ constexpr const char* kRouteNames[ROUTE_COUNT] = {"dkdv_stream", "dkdv_lean", "f
                                                    "fp8in_fwd_mod", "fp8in_fwd_varlen_mod", "fp8kv_split_mod", "fp8kv_step_prep", "fp8in_fwd_hdim",
                                                    "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim", "fp8kv_split_varlen",
                                                    "fp8kv_step_prep_varlen", "fp4kv_append", "fp4kv_split",
-    "fp4kv_prefill", "fp4kv_split_mod", "fp4kv_prefill_mod"};
+    "fp4kv_prefill", "fp4kv_split_mod", "fp4kv_prefill_mod", "fp4kv_append_hdim", "fp4kv_split_hdim", "fp4kv_prefill_hdim"};
 void route_hit(int id) { g_route_hits[id].fetch_add(1, std::memory_order_relaxed); }
 long long route_count(const char* name) {
     for (int i = 0; i < ROUTE_COUNT; ++i)
@@ -3917,6 +3917,7 @@ struct Fp4Call {
     int dtype = 0;
     const float *q_descale = nullptr, *k_descale = nullptr, *v_descale = nullptr;
     int64_t qds_bs = 0, kds_bs = 0, vds_bs = 0;
+    bool hdim = false;                     // an _hdim entry point: d in {64, 128, 256}, and d / 2, d / 32 bound what 64, 4 bound elsewhere
 };
 
 // The rules both entry points share, in the header's order from (2) on: the head dim, the dtype, the cache's extents, alignment and
@@ -3925,8 +3926,10 @@ static int fp4_cache_check(const char* who, const Fp4Call& k, int nd) {
     const fa::Fp4Cache& c = k.c;
     const bool paged = c.block_table != nullptr;
     const int64_t kInt = ((int64_t)1 << 31) - 1, kMaxStride = (int64_t)1 << 44;
-    if (k.d != 128)
-        return fail(FA_ERR_UNSUPPORTED, "%s: head_dim %lld is not supported by the MXFP4 cache (128 only)", who, (long long)k.d);
+    if (k.hdim ? fp8_hdim_unsupported(k.d) : k.d != 128)
+        return fail(FA_ERR_UNSUPPORTED, k.hdim ? "%s: head_dim %lld is not supported (64, 128 or 256)"
+                                               : "%s: head_dim %lld is not supported by the MXFP4 cache (128 only)", who, (long long)k.d);
+    const int64_t hb = k.d / 2, sb = k.d / 32;          // code bytes and k_scale bytes a key and head
     if (k.dtype != FA_DTYPE_F16 && k.dtype != FA_DTYPE_BF16)
         return fail(FA_ERR_UNSUPPORTED, "%s: dtype must be f16 or bf16 (got code %d)", who, k.dtype);
     if (c.heads_kv < 1 || c.heads_kv > ((int64_t)1 << 20))
@@ -3941,12 +3944,13 @@ static int fp4_cache_check(const char* who, const Fp4Call& k, int nd) {
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: cache_batch must be 0 without cache_batch_idx (got %lld)", who, (long long)c.cache_batch);
     }
     if (!aligned16({c.k_cache, c.v_cache})) return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_cache and v_cache must be 16-byte aligned", who);
-    if ((uintptr_t)c.k_scale % 4 != 0 || (uintptr_t)c.cache_seqlens % 4 != 0 || (uintptr_t)c.block_table % 4 != 0 || (uintptr_t)c.cache_batch_idx % 4 != 0)
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_scale, cache_seqlens, block_table and cache_batch_idx must be 4-byte aligned", who);
+    if ((uintptr_t)c.k_scale % sb != 0 || (uintptr_t)c.cache_seqlens % 4 != 0 || (uintptr_t)c.block_table % 4 != 0 || (uintptr_t)c.cache_batch_idx % 4 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: k_scale%s, cache_seqlens, block_table and cache_batch_idx must be 4-byte aligned", who,
+                    sb == 4 ? "" : sb == 2 ? " (2-byte)" : " (8-byte)");
     // (unit: what a stride must be a multiple of; least: the bytes of a token's heads)
     const struct { const char* name; int64_t bs, ts, unit, least; } ts[4] = {
-        {"k_cache", c.kc_bs, c.kc_ts, 16, c.heads_kv * 64}, {"k_scale", c.ks_bs, c.ks_ts, 4, c.heads_kv * 4},
-        {"v_cache", c.vc_bs, c.vc_ts, 16, c.heads_kv * 64}, {"v_scale", c.vs_bs, c.vs_ts, 1, c.heads_kv}};
+        {"k_cache", c.kc_bs, c.kc_ts, 16, c.heads_kv * hb}, {"k_scale", c.ks_bs, c.ks_ts, sb, c.heads_kv * sb},
+        {"v_cache", c.vc_bs, c.vc_ts, 16, c.heads_kv * hb}, {"v_scale", c.vs_bs, c.vs_ts, 1, c.heads_kv}};
     for (const auto& t : ts)
         if (t.ts % t.unit != 0 || t.bs % t.unit != 0 || t.ts < t.least || t.ts > kMaxStride || t.bs < 0 || t.bs > kMaxStride)
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (batch %lld, token %lld) must be multiples of %lld bytes and >= 0, "
@@ -4007,20 +4011,21 @@ static Fp4Call fp4_cache_call(const void* k_cache, const void* k_scale, const vo
     return k;
 }
 
-int fa_fp4_kvcache_append(const void* k_new, const void* v_new, void* k_cache, void* k_scale, void* v_cache, void* v_scale,
-                          const int32_t* cache_seqlens, const int32_t* block_table, const int32_t* cache_batch_idx, const float* k_descale,
+// fa_fp4_kvcache_append and fa_fp4_kvcache_append_hdim (`hdim`)
+static int fp4_kvcache_append_impl(const char* who, bool hdim, const void* k_new, const void* v_new, void* k_cache, void* k_scale, void* v_cache,
+                          void* v_scale, const int32_t* cache_seqlens, const int32_t* block_table, const int32_t* cache_batch_idx, const float* k_descale,
                           const float* v_descale, int64_t batch, int64_t heads_kv, int64_t seqlen_new, int64_t cache_len, int64_t cache_batch,
                           int64_t d, int dtype, int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t v_new_batch_stride,
                           int64_t v_new_token_stride, int64_t k_batch_stride, int64_t k_token_stride, int64_t k_scale_batch_stride,
                           int64_t k_scale_token_stride, int64_t v_batch_stride, int64_t v_token_stride, int64_t v_scale_batch_stride,
                           int64_t v_scale_token_stride, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
                           int64_t descale_batch_stride, void* stream) {
-    const char* who = "fa_fp4_kvcache_append";
     // (no q_descale, and one stride for both others)
-    const Fp4Call k = fp4_cache_call(k_cache, k_scale, v_cache, v_scale, cache_seqlens, block_table, cache_batch_idx, batch, heads_kv, cache_len,
+    Fp4Call k = fp4_cache_call(k_cache, k_scale, v_cache, v_scale, cache_seqlens, block_table, cache_batch_idx, batch, heads_kv, cache_len,
            cache_batch, d, dtype, k_batch_stride, k_token_stride, k_scale_batch_stride, k_scale_token_stride, v_batch_stride, v_token_stride,
            v_scale_batch_stride, v_scale_token_stride, block_table_row_stride, num_blocks, page_block_size, nullptr, k_descale, v_descale, 0,
            k_descale ? descale_batch_stride : 0, v_descale ? descale_batch_stride : 0);
+    k.hdim = hdim;
     if (batch == 0 || seqlen_new == 0) return FA_OK;
     if (!k_descale && !v_descale && descale_batch_stride != 0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: descale_batch_stride must be 0 without k_descale and v_descale", who);
@@ -4033,18 +4038,49 @@ int fa_fp4_kvcache_append(const void* k_new, const void* v_new, void* k_cache, v
     const struct { const char* name; int64_t bs, ts; } ns[2] = {{"k_new", k_new_batch_stride, k_new_token_stride},
                                                                  {"v_new", v_new_batch_stride, v_new_token_stride}};
     for (const auto& t : ns)
-        if (t.ts % 16 != 0 || t.bs % 16 != 0 || t.ts < heads_kv * 256 || t.ts > ((int64_t)1 << 44) || t.bs < 0 || t.bs > ((int64_t)1 << 44))
+        if (t.ts % 16 != 0 || t.bs % 16 != 0 || t.ts < heads_kv * 2 * d || t.ts > ((int64_t)1 << 44) || t.bs < 0 || t.bs > ((int64_t)1 << 44))
             return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of %s (batch %lld, token %lld) must be multiples of 16 bytes and >= 0, "
-                        "the token stride >= heads_kv * 256 = %lld", who, t.name, (long long)t.bs, (long long)t.ts, (long long)(heads_kv * 256));
-    if (seqlen_new * heads_kv * 8 > ((int64_t)1 << 31) - 256)
+                        "the token stride >= heads_kv * %lld = %lld", who, t.name, (long long)t.bs, (long long)t.ts, (long long)(2 * d),
+                        (long long)(heads_kv * 2 * d));
+    if (seqlen_new * heads_kv * (d / 16) > ((int64_t)1 << 31) - 256)
         return fail(FA_ERR_UNSUPPORTED, "%s: span limit: seqlen_new * heads_kv = %lld is beyond one launch", who, (long long)(seqlen_new * heads_kv));
     fa::Fp4AppendArgs a;
     a.c = k.c; a.k_new = k_new; a.v_new = v_new; a.k_descale = k_descale; a.v_descale = v_descale;
     a.kds_bs = k.kds_bs; a.vds_bs = k.vds_bs; a.batch = batch; a.seqlen_new = seqlen_new;
     a.kn_bs = k_new_batch_stride; a.kn_ts = k_new_token_stride; a.vn_bs = v_new_batch_stride; a.vn_ts = v_new_token_stride;
-    a.dtype = dtype;
-    return launched(who, fa::launch_fp4_kvcache_append(a, reinterpret_cast<hipStream_t>(stream)));
+    a.dtype = dtype; a.d = d;
+    return launched(who, fa::launch_fp4_kvcache_append_hdim(a, reinterpret_cast<hipStream_t>(stream)));   // (d == 128: launch_fp4_kvcache_append)
 }
+
+#define FP4_APPEND_ARGS k_new, v_new, k_cache, k_scale, v_cache, v_scale, cache_seqlens, block_table, cache_batch_idx, k_descale, v_descale, batch, \
+    heads_kv, seqlen_new, cache_len, cache_batch
+#define FP4_APPEND_STRIDES dtype, k_new_batch_stride, k_new_token_stride, v_new_batch_stride, v_new_token_stride, k_batch_stride, k_token_stride, \
+    k_scale_batch_stride, k_scale_token_stride, v_batch_stride, v_token_stride, v_scale_batch_stride, v_scale_token_stride, \
+    block_table_row_stride, num_blocks, page_block_size, descale_batch_stride, stream
+
+int fa_fp4_kvcache_append(const void* k_new, const void* v_new, void* k_cache, void* k_scale, void* v_cache, void* v_scale,
+                          const int32_t* cache_seqlens, const int32_t* block_table, const int32_t* cache_batch_idx, const float* k_descale,
+                          const float* v_descale, int64_t batch, int64_t heads_kv, int64_t seqlen_new, int64_t cache_len, int64_t cache_batch,
+                          int64_t d, int dtype, int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t v_new_batch_stride,
+                          int64_t v_new_token_stride, int64_t k_batch_stride, int64_t k_token_stride, int64_t k_scale_batch_stride,
+                          int64_t k_scale_token_stride, int64_t v_batch_stride, int64_t v_token_stride, int64_t v_scale_batch_stride,
+                          int64_t v_scale_token_stride, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
+                          int64_t descale_batch_stride, void* stream) {
+    return fp4_kvcache_append_impl("fa_fp4_kvcache_append", false, FP4_APPEND_ARGS, d, FP4_APPEND_STRIDES);
+}
+
+int fa_fp4_kvcache_append_hdim(const void* k_new, const void* v_new, void* k_cache, void* k_scale, void* v_cache, void* v_scale,
+                          const int32_t* cache_seqlens, const int32_t* block_table, const int32_t* cache_batch_idx, const float* k_descale,
+                          const float* v_descale, int64_t batch, int64_t heads_kv, int64_t seqlen_new, int64_t cache_len, int64_t cache_batch,
+                          int64_t head_dim, int dtype, int64_t k_new_batch_stride, int64_t k_new_token_stride, int64_t v_new_batch_stride,
+                          int64_t v_new_token_stride, int64_t k_batch_stride, int64_t k_token_stride, int64_t k_scale_batch_stride,
+                          int64_t k_scale_token_stride, int64_t v_batch_stride, int64_t v_token_stride, int64_t v_scale_batch_stride,
+                          int64_t v_scale_token_stride, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
+                          int64_t descale_batch_stride, void* stream) {
+    return fp4_kvcache_append_impl("fa_fp4_kvcache_append_hdim", true, FP4_APPEND_ARGS, head_dim, FP4_APPEND_STRIDES);
+}
+#undef FP4_APPEND_ARGS
+#undef FP4_APPEND_STRIDES
 
 // the e4m3 decode call's layout and split rule (the kernels share the 32-row tile and the combine)
 size_t fa_fp4_forward_kvcache_workspace_bytes_mod(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
@@ -4076,10 +4112,11 @@ static int fp4_forward_kvcache_impl(const char* who, const fa::Fp8Mod& m, const 
     if (!(softmax_scale == softmax_scale) || !scale_ok(softmax_scale))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale must be finite and > 0", who);
     if (!aligned16({q, o}) || (uintptr_t)lse % 4 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: q and o must be 16-byte aligned, lse 4-byte aligned", who);
-    if (q_token_stride % 16 != 0 || q_batch_stride % 16 != 0 || q_token_stride < heads_q * 128 || q_token_stride > ((int64_t)1 << 44) ||
+    if (q_token_stride % 16 != 0 || q_batch_stride % 16 != 0 || q_token_stride < heads_q * k.d || q_token_stride > ((int64_t)1 << 44) ||
         q_batch_stride < 0 || q_batch_stride > ((int64_t)1 << 44))
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: the strides of q (batch %lld, token %lld) must be multiples of 16 bytes and >= 0, the token "
-                    "stride >= heads_q * 128 = %lld", who, (long long)q_batch_stride, (long long)q_token_stride, (long long)(heads_q * 128));
+                    "stride >= heads_q * %lld = %lld", who, (long long)q_batch_stride, (long long)q_token_stride, (long long)k.d,
+                    (long long)(heads_q * k.d));
     if (seqlen_q * q_token_stride > ((int64_t)1 << 31) - 1)
         return fail(FA_ERR_UNSUPPORTED, "%s: span limit: tokens * token stride of q is %lld bytes, at or above 2^31", who,
                     (long long)(seqlen_q * q_token_stride));
@@ -4092,19 +4129,19 @@ static int fp4_forward_kvcache_impl(const char* who, const fa::Fp8Mod& m, const 
     if (const int rc = mod_check(who, m, heads_q, true)) return rc;
     // (the featured call: the rule sees the keys a window can show, and sinks raise 1 split to 2; not any(): the parent's rule)
     const int64_t S = fp8_kv_splits_mod(batch, heads_q, heads_kv, seqlen_q, cache_len, num_splits, causal, m);
-    const size_t need = fa::kv_workspace_bytes(batch, heads_q, seqlen_q, 128, (int)S);
+    const size_t need = fa::kv_workspace_bytes(batch, heads_q, seqlen_q, k.d, (int)S);
     if (need > 0) {
         if (!workspace || workspace_bytes < need)
-            return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes is too small (need %zu: fa_fp4_forward_kvcache_workspace_bytes%s)", who,
-                        workspace ? workspace_bytes : (size_t)0, need, m.any() ? "_mod" : "");
+            return fail(FA_ERR_WORKSPACE, "%s: workspace of %zu bytes is too small (need %zu: fa_fp4_forward_kvcache_%sworkspace_bytes%s)", who,
+                        workspace ? workspace_bytes : (size_t)0, need, k.hdim ? "hdim_" : "", k.hdim ? "" : m.any() ? "_mod" : "");
         if ((uintptr_t)workspace % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
     }
     fa::Fp4KvArgs a;
     a.c = k.c; a.q = q; a.o = o; a.lse = lse; a.q_descale = k.q_descale; a.k_descale = k.k_descale; a.v_descale = k.v_descale;
     a.qds_bs = k.qds_bs; a.kds_bs = k.kds_bs; a.vds_bs = k.vds_bs;
     a.batch = batch; a.heads_q = heads_q; a.seqlen_q = seqlen_q; a.q_bs = q_batch_stride; a.q_ts = q_token_stride;
-    a.dtype = k.dtype; a.causal = causal != 0; a.scale = (float)softmax_scale; a.num_splits = S; a.workspace = workspace;
-    return launched(who, fa::launch_fp4_kvcache_mod(a, m, reinterpret_cast<hipStream_t>(stream)));
+    a.dtype = k.dtype; a.causal = causal != 0; a.scale = (float)softmax_scale; a.num_splits = S; a.workspace = workspace; a.d = k.d;
+    return launched(who, fa::launch_fp4_kvcache_hdim(a, m, reinterpret_cast<hipStream_t>(stream)));   // (d == 128: launch_fp4_kvcache_mod)
 }
 
 int fa_fp4_forward_kvcache(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o, float* lse,
@@ -4143,6 +4180,33 @@ int fa_fp4_forward_kvcache_mod(const void* q, const void* k_cache, const void* k
                                     workspace_bytes, stream);
 }
 
+int fa_fp4_forward_kvcache_hdim(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o, float* lse,
+                           const float* q_descale, const float* k_descale, const float* v_descale, const int32_t* cache_seqlens,
+                           const int32_t* block_table, const int32_t* cache_batch_idx, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                           int64_t seqlen_q, int64_t cache_len, int64_t cache_batch, int64_t head_dim, int dtype, int64_t q_batch_stride,
+                           int64_t q_token_stride, int64_t k_batch_stride, int64_t k_token_stride, int64_t k_scale_batch_stride,
+                           int64_t k_scale_token_stride, int64_t v_batch_stride, int64_t v_token_stride, int64_t v_scale_batch_stride,
+                           int64_t v_scale_token_stride, int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
+                           int64_t q_descale_batch_stride, int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal,
+                           double softmax_scale, int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream,
+                           int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads) {
+    Fp4Call k = fp4_cache_call(k_cache, k_scale, v_cache, v_scale, cache_seqlens, block_table, cache_batch_idx, batch, heads_kv, cache_len,
+           cache_batch, head_dim, dtype, k_batch_stride, k_token_stride, k_scale_batch_stride, k_scale_token_stride, v_batch_stride, v_token_stride,
+           v_scale_batch_stride, v_scale_token_stride, block_table_row_stride, num_blocks, page_block_size, q_descale, k_descale, v_descale,
+           q_descale_batch_stride, k_descale_batch_stride, v_descale_batch_stride);
+    k.hdim = true;
+    return fp4_forward_kvcache_impl("fa_fp4_forward_kvcache_hdim", fp8_mod(window_left, window_right, softcap, sinks, sink_heads), k, q, o, lse,
+                                    heads_q, seqlen_q, q_batch_stride, q_token_stride, causal, softmax_scale, num_splits, workspace,
+                                    workspace_bytes, stream);
+}
+
+size_t fa_fp4_forward_kvcache_hdim_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
+                                                   int64_t head_dim, int64_t num_splits, int causal, int64_t window_left, int64_t window_right,
+                                                   int with_sinks) {
+    return fa_fp8_forward_kvcache_hdim_workspace_bytes(batch, heads_q, heads_kv, seqlen_q, cache_len, head_dim, num_splits, causal, window_left,
+                                                       window_right, with_sinks);
+}
+
 // Chunked prefill over the paged MXFP4 cache: packed queries, one launch, no workspace (fa_fp4_prefill.hip)
 // fa_fp4_forward_varlen (m at its defaults) and fa_fp4_forward_varlen_mod: k is the cache's record (no lengths, no row indirection)
 static int fp4_forward_varlen_impl(const char* who, const fa::Fp8Mod& m, const Fp4Call& k, const void* q, void* o, float* lse,
@@ -4166,9 +4230,9 @@ static int fp4_forward_varlen_impl(const char* who, const fa::Fp8Mod& m, const F
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: softmax_scale must be finite and > 0", who);
     if (!aligned16({q, o}) || (uintptr_t)lse % 4 != 0 || (uintptr_t)cu_seqlens_q % 4 != 0 || (uintptr_t)cu_seqlens_k % 4 != 0)
         return fail(FA_ERR_INVALID_ARGUMENT, "%s: q and o must be 16-byte aligned, lse, cu_seqlens_q and cu_seqlens_k 4-byte aligned", who);
-    if (q_token_stride % 16 != 0 || q_token_stride < heads_q * 128 || q_token_stride > ((int64_t)1 << 44))
-        return fail(FA_ERR_INVALID_ARGUMENT, "%s: the token stride of q (%lld) must be a multiple of 16 bytes and >= heads_q * 128 = %lld", who,
-                    (long long)q_token_stride, (long long)(heads_q * 128));
+    if (q_token_stride % 16 != 0 || q_token_stride < heads_q * k.d || q_token_stride > ((int64_t)1 << 44))
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: the token stride of q (%lld) must be a multiple of 16 bytes and >= heads_q * %lld = %lld", who,
+                    (long long)q_token_stride, (long long)k.d, (long long)(heads_q * k.d));
     if (total_q * heads_q > ((int64_t)1 << 31) - 1)
         return fail(FA_ERR_UNSUPPORTED, "%s: span limit: total_q * heads_q = %lld is at or above 2^31", who, (long long)(total_q * heads_q));
     if (heads_kv > 65535 || (max_seqlen_q * (heads_q / heads_kv) + 127) / 128 > ((int64_t)1 << 31) - 1)
@@ -4179,8 +4243,8 @@ static int fp4_forward_varlen_impl(const char* who, const fa::Fp8Mod& m, const F
     a.c = k.c; a.q = q; a.o = o; a.lse = lse; a.q_descale = k.q_descale; a.k_descale = k.k_descale; a.v_descale = k.v_descale;
     a.qds_bs = k.qds_bs; a.kds_bs = k.kds_bs; a.vds_bs = k.vds_bs; a.cu_seqlens_q = cu_seqlens_q; a.cu_seqlens_k = cu_seqlens_k;
     a.batch = batch; a.heads_q = heads_q; a.total_q = total_q; a.max_seqlen_q = max_seqlen_q; a.q_ts = q_token_stride;
-    a.dtype = k.dtype; a.causal = causal != 0; a.scale = (float)softmax_scale;
-    return launched(who, fa::launch_fp4_prefill_mod(a, m, reinterpret_cast<hipStream_t>(stream)));
+    a.dtype = k.dtype; a.causal = causal != 0; a.scale = (float)softmax_scale; a.d = k.d;
+    return launched(who, fa::launch_fp4_prefill_hdim(a, m, reinterpret_cast<hipStream_t>(stream)));   // (d == 128: launch_fp4_prefill_mod)
 }
 
 int fa_fp4_forward_varlen(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o, float* lse,
@@ -4213,6 +4277,24 @@ int fa_fp4_forward_varlen_mod(const void* q, const void* k_cache, const void* k_
            v_scale_token_stride, block_table_row_stride, num_blocks, page_block_size, q_descale, k_descale, v_descale, q_descale_batch_stride,
            k_descale_batch_stride, v_descale_batch_stride);
     return fp4_forward_varlen_impl("fa_fp4_forward_varlen_mod", fp8_mod(window_left, window_right, softcap, sinks, sink_heads), k, q, o, lse,
+                                   cu_seqlens_q, cu_seqlens_k, heads_q, total_q, max_seqlen_q, q_token_stride, causal, softmax_scale, stream);
+}
+
+int fa_fp4_forward_varlen_hdim(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o, float* lse,
+                          const float* q_descale, const float* k_descale, const float* v_descale, const int32_t* cu_seqlens_q,
+                          const int32_t* cu_seqlens_k, const int32_t* block_table, int64_t batch, int64_t heads_q, int64_t heads_kv,
+                          int64_t total_q, int64_t max_seqlen_q, int64_t cache_len, int64_t head_dim, int dtype, int64_t q_token_stride,
+                          int64_t k_batch_stride, int64_t k_token_stride, int64_t k_scale_batch_stride, int64_t k_scale_token_stride,
+                          int64_t v_batch_stride, int64_t v_token_stride, int64_t v_scale_batch_stride, int64_t v_scale_token_stride,
+                          int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t q_descale_batch_stride,
+                          int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale, void* stream,
+                          int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads) {
+    Fp4Call k = fp4_cache_call(k_cache, k_scale, v_cache, v_scale, nullptr, block_table, nullptr, batch, heads_kv, cache_len, 0, head_dim, dtype,
+           k_batch_stride, k_token_stride, k_scale_batch_stride, k_scale_token_stride, v_batch_stride, v_token_stride, v_scale_batch_stride,
+           v_scale_token_stride, block_table_row_stride, num_blocks, page_block_size, q_descale, k_descale, v_descale, q_descale_batch_stride,
+           k_descale_batch_stride, v_descale_batch_stride);
+    k.hdim = true;
+    return fp4_forward_varlen_impl("fa_fp4_forward_varlen_hdim", fp8_mod(window_left, window_right, softcap, sinks, sink_heads), k, q, o, lse,
                                    cu_seqlens_q, cu_seqlens_k, heads_q, total_q, max_seqlen_q, q_token_stride, causal, softmax_scale, stream);
 }
 

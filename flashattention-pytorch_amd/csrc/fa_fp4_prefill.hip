@@ -55,21 +55,6 @@ namespace {
 constexpr int kKRow = 80;                                // bytes of a key's row in the K stage
 constexpr int kKBytes = 64 * kKRow;
 
-struct Fp4PrefillParams {
-    const uint8_t *q, *kc, *ksc, *vc, *vsc;
-    uint16_t* o;
-    float* lse;
-    const float *qds, *kds, *vds;         // (B, H_kv) descales at their batch strides; null: 1
-    long long qds_bs, kds_bs, vds_bs;
-    const int *cu_q, *cu_k, *table;       // untrusted device memory
-    long long tbl_rs;
-    int nblk, ps, cap;
-    long long q_ts, kc_bs, ks_bs, vc_bs, vs_bs;   // q's token stride and the page strides in bytes
-    int kc_ts, ks_ts, vc_ts, vs_ts;               // token strides in bytes
-    int hq, G, total_q, max_q, causal;
-    float c_log2;                         // float(softmax_scale) * log2(e)
-};
-
 // what a lane holds of a tile in flight
 struct Fp4Staged {
     u32x4 k;
@@ -371,19 +356,7 @@ __global__ __launch_bounds__(256, 2) void fp4kv_prefill_kernel(const Fp4PrefillP
 
 // md: null for fa_fp4_forward_varlen; else the featured call's kernel arguments
 static hipError_t launch_fp4_prefill_t(const Fp4VarlenArgs& a, const KvqModSinks* md, hipStream_t st) {
-    Fp4PrefillParams p;
-    p.q = (const uint8_t*)a.q; p.kc = (const uint8_t*)a.c.k_cache; p.ksc = (const uint8_t*)a.c.k_scale;
-    p.vc = (const uint8_t*)a.c.v_cache; p.vsc = (const uint8_t*)a.c.v_scale;
-    p.o = (uint16_t*)a.o; p.lse = a.lse;
-    p.qds = a.q_descale; p.kds = a.k_descale; p.vds = a.v_descale;
-    p.qds_bs = a.qds_bs; p.kds_bs = a.kds_bs; p.vds_bs = a.vds_bs;
-    p.cu_q = a.cu_seqlens_q; p.cu_k = a.cu_seqlens_k; p.table = a.c.block_table;
-    p.tbl_rs = a.c.table_row_stride; p.nblk = (int)a.c.num_blocks; p.ps = (int)a.c.page_size; p.cap = (int)a.c.cache_len;
-    p.q_ts = a.q_ts; p.kc_bs = a.c.kc_bs; p.ks_bs = a.c.ks_bs; p.vc_bs = a.c.vc_bs; p.vs_bs = a.c.vs_bs;
-    p.kc_ts = (int)a.c.kc_ts; p.ks_ts = (int)a.c.ks_ts; p.vc_ts = (int)a.c.vc_ts; p.vs_ts = (int)a.c.vs_ts;
-    p.hq = (int)a.heads_q; p.G = (int)(a.heads_q / a.c.heads_kv);
-    p.total_q = (int)a.total_q; p.max_q = (int)a.max_seqlen_q; p.causal = a.causal != 0;
-    p.c_log2 = a.scale * 1.4426950408889634f;
+    const Fp4PrefillParams p = fp4_prefill_params(a);
     const unsigned row_tiles = (unsigned)((a.max_seqlen_q * p.G + 127) / 128);
     const dim3 grid(row_tiles, (unsigned)a.c.heads_kv, (unsigned)a.batch);
     route_hit(md ? ROUTE_FP4KV_PREFILL_MOD : ROUTE_FP4KV_PREFILL);

@@ -46,7 +46,7 @@ enum KernelId { K_FWD_F32 = 0, K_BWD_DELTA, K_BWD_DKDV_F32, K_BWD_DQ_F32, K_FWD_
                 K_FP8IN_FWD_VARLEN, K_IDX_PACK, K_IDX_LOGITS, K_IDX_TOPK, K_FP8KV_SPLIT, K_FP8Q_AMAX, K_FP8Q_QUANT, K_FP8Q_FUSED,
                 K_FP8IN_FWD_MOD, K_FP8IN_FWD_VARLEN_MOD, K_FP8KV_SPLIT_MOD, K_FP8KV_STEP_PREP, K_FP8IN_FWD_HDIM,
                 K_FP8IN_FWD_VARLEN_HDIM, K_FP8KV_SPLIT_HDIM, K_FP8KV_SPLIT_VARLEN, K_FP8KV_STEP_PREP_VARLEN, K_FP4KV_APPEND, K_FP4KV_SPLIT, K_FP4KV_PREFILL,
-                K_FP4KV_SPLIT_MOD, K_FP4KV_PREFILL_MOD, K_COUNT };
+                K_FP4KV_SPLIT_MOD, K_FP4KV_PREFILL_MOD, K_FP4KV_APPEND_HDIM, K_FP4KV_SPLIT_HDIM, K_FP4KV_PREFILL_HDIM, K_COUNT };
 void prof_begin(int id, hipStream_t st);
 void prof_end(int id, hipStream_t st);
 struct ProfScope {
@@ -76,11 +76,13 @@ int set_option(const char* name, int value);   // returns 0, or -1 for an unknow
 // "fp8kv_step_prep_varlen": the prep launch of fa_fp8_kvcache_step_varlen with packed tokens or at head dim 64 / 256;
 // "fp4kv_append", "fp4kv_split": the two kernels of the MXFP4 KV cache (fa_fp4_decode.hip);
 // "fp4kv_prefill": the packed-query prefill kernel over the paged MXFP4 cache (fa_fp4_prefill.hip);
-// "fp4kv_split_mod", "fp4kv_prefill_mod": the featured kernels of the two MXFP4 cache readers (window, softcap, sinks).
+// "fp4kv_split_mod", "fp4kv_prefill_mod": the featured kernels of the two MXFP4 cache readers (window, softcap, sinks);
+// "fp4kv_append_hdim", "fp4kv_split_hdim", "fp4kv_prefill_hdim": the MXFP4 cache kernels at head dims 64 / 256 (fa_fp4_hdim.hip).
 enum RouteId { ROUTE_DKDV_STREAM = 0, ROUTE_DKDV_LEAN, ROUTE_FP8Q_FUSED, ROUTE_FP8Q_TWO_PASS, ROUTE_FP8Q_STATIC, ROUTE_FP8IN_FWD_MOD,
                ROUTE_FP8IN_FWD_VARLEN_MOD, ROUTE_FP8KV_SPLIT_MOD, ROUTE_FP8KV_STEP_PREP, ROUTE_FP8IN_FWD_HDIM,
                ROUTE_FP8IN_FWD_VARLEN_HDIM, ROUTE_FP8KV_SPLIT_HDIM, ROUTE_FP8KV_SPLIT_VARLEN, ROUTE_FP8KV_STEP_PREP_VARLEN, ROUTE_FP4KV_APPEND,
-               ROUTE_FP4KV_SPLIT, ROUTE_FP4KV_PREFILL, ROUTE_FP4KV_SPLIT_MOD, ROUTE_FP4KV_PREFILL_MOD, ROUTE_COUNT };
+               ROUTE_FP4KV_SPLIT, ROUTE_FP4KV_PREFILL, ROUTE_FP4KV_SPLIT_MOD, ROUTE_FP4KV_PREFILL_MOD,
+               ROUTE_FP4KV_APPEND_HDIM, ROUTE_FP4KV_SPLIT_HDIM, ROUTE_FP4KV_PREFILL_HDIM, ROUTE_COUNT };
 void route_hit(int id);
 
 // exact-f32 kernels (fa_generic.hip): any dtype, d <= 256
@@ -601,6 +603,7 @@ struct Fp4AppendArgs {
     int64_t kds_bs = 0, vds_bs = 0;
     int64_t batch = 0, seqlen_new = 0, kn_bs = 0, kn_ts = 0, vn_bs = 0, vn_ts = 0;
     int dtype = 0;                                          // FA_DTYPE_F16 / FA_DTYPE_BF16
+    int64_t d = 128;                                        // the head dim: 128, or 64 / 256 through launch_fp4_kvcache_append_hdim alone
 };
 hipError_t launch_fp4_kvcache_append(const Fp4AppendArgs& a, hipStream_t st);
 struct Fp4KvArgs {
@@ -614,7 +617,8 @@ struct Fp4KvArgs {
     int dtype = 0, causal = 0;
     float scale = 0.f;
     int64_t num_splits = 1;                                 // >= 1 (the C layer resolves 0 through fp8kv_num_splits)
-    void* workspace = nullptr;                              // kv_workspace_bytes(batch, heads_q, seqlen_q, 128, num_splits)
+    void* workspace = nullptr;                              // kv_workspace_bytes(batch, heads_q, seqlen_q, d, num_splits)
+    int64_t d = 128;                                        // the head dim: 128, or 64 / 256 through launch_fp4_kvcache_hdim alone
 };
 hipError_t launch_fp4_kvcache(const Fp4KvArgs& a, hipStream_t st);
 // The featured call (fa_fp4_forward_kvcache_mod): Fp8Mod's window, softcap and sinks over the MXFP4 cache.  A
@@ -634,10 +638,16 @@ struct Fp4VarlenArgs {
     int64_t batch = 0, heads_q = 0, total_q = 0, max_seqlen_q = 0, q_ts = 0;
     int dtype = 0, causal = 0;
     float scale = 0.f;
+    int64_t d = 128;                                        // the head dim: 128, or 64 / 256 through launch_fp4_prefill_hdim alone
 };
 hipError_t launch_fp4_prefill(const Fp4VarlenArgs& a, hipStream_t st);
 // The featured call (fa_fp4_forward_varlen_mod): not any() is launch_fp4_prefill; any other runs fp4kv_prefill_kernel<.., KvqModSinks>, which walks
 // the key tiles of each workgroup's band alone and takes the sink in its epilogue (no workspace).
 hipError_t launch_fp4_prefill_mod(const Fp4VarlenArgs& a, const Fp8Mod& m, hipStream_t st);
+// The three calls at a.d in {64, 128, 256} (fa_fp4_hdim.hip; the fa_fp4_*_hdim entry points): the cache at width d,
+// codes (.., heads_kv, d / 2), k_scale (.., heads_kv, d / 32), v_scale (.., heads_kv).  d == 128 is the parent launcher above.
+hipError_t launch_fp4_kvcache_append_hdim(const Fp4AppendArgs& a, hipStream_t st);
+hipError_t launch_fp4_kvcache_hdim(const Fp4KvArgs& a, const Fp8Mod& m, hipStream_t st);
+hipError_t launch_fp4_prefill_hdim(const Fp4VarlenArgs& a, const Fp8Mod& m, hipStream_t st);
 
 }  // namespace fa

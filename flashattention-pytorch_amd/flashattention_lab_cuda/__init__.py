@@ -68,6 +68,7 @@ EXPORTED_C_SYMBOLS = (
     "fa_fp8_kvcache_step_varlen", "fa_fp8_kvcache_step_varlen_workspace_bytes",
     "fa_fp4_kvcache_append", "fa_fp4_forward_kvcache", "fa_fp4_forward_kvcache_workspace_bytes", "fa_fp4_forward_varlen",
     "fa_fp4_forward_kvcache_mod", "fa_fp4_forward_kvcache_workspace_bytes_mod", "fa_fp4_forward_varlen_mod",
+    "fa_fp4_kvcache_append_hdim", "fa_fp4_forward_kvcache_hdim", "fa_fp4_forward_kvcache_hdim_workspace_bytes", "fa_fp4_forward_varlen_hdim",
 )
 
 
@@ -285,6 +286,11 @@ _sig("fa_fp4_forward_varlen", _fields(
 for _name in ("fa_fp4_forward_kvcache", "fa_fp4_forward_varlen"):
     _sig(_name + "_mod", _SIGNATURES[_name][1] + _FP8MOD)
 _sig("fa_fp4_forward_kvcache_workspace_bytes_mod", _SIGNATURES["fa_fp8_forward_kvcache_workspace_bytes_mod"][1], _SIZE)
+# head dims 64 / 128 / 256 on the MXFP4 cache: the append's list and the two readers' _mod lists with d under the name head_dim
+_sig("fa_fp4_kvcache_append_hdim", _hdim_fields(_SIGNATURES["fa_fp4_kvcache_append"][1]))
+for _name in ("fa_fp4_forward_kvcache", "fa_fp4_forward_varlen"):
+    _sig(_name + "_hdim", _hdim_fields(_SIGNATURES[_name + "_mod"][1]))
+_sig("fa_fp4_forward_kvcache_hdim_workspace_bytes", _SIGNATURES["fa_fp8_forward_kvcache_hdim_workspace_bytes"][1], _SIZE)
 _KVWSV = _fields("i:batch,heads_q,heads_kv,total_q,max_seqlen_q,cache_len,d,num_splits c:with_sinks")
 _sig("fa_ex_kvcache_workspace_bytes_varlen", _KVWSV, _SIZE)
 _sig("fa_ex_kvcache_workspace_bytes_qv", _KVWSV + _fields("i:d_v"), _SIZE)
@@ -357,7 +363,8 @@ _family("fa_fp8_kvcache_step_varlen", [])
 _family("fa_fp4_kvcache_append", [])
 _family("fa_fp4_forward_kvcache", [])
 _family("fa_fp4_forward_varlen", [])
-for _name in ("fa_fp4_forward_kvcache_mod", "fa_fp4_forward_varlen_mod"):
+for _name in ("fa_fp4_forward_kvcache_mod", "fa_fp4_forward_varlen_mod", "fa_fp4_kvcache_append_hdim", "fa_fp4_forward_kvcache_hdim",
+              "fa_fp4_forward_varlen_hdim"):
     _family(_name, [])
 _family("fa_ex_forward_kvcache_qv", ["fa_ex_forward_kvcache" + _suffix for _suffix in ("", "_paged", "_rotary", "_fp8", "_sink", "_varlen")])
 
@@ -2810,9 +2817,27 @@ def _fp4_u8(who, name, t, typed):
     raise NotImplementedError(f"{who}: {name} of dtype {got} is not supported (torch.uint8 or torch.{typed} expected)")
 
 
-def _fp4_cache(who, k_cache, k_scale, v_cache, v_scale, block_table, cache_batch_idx, b):
-    """The four arrays of an MXFP4 cache as uint8 views with their geometry: (arrays, H_kv, capacity, cache_batch, the eight byte
-    strides in the C order, (block_table_row_stride, num_blocks, page_block_size), block_table, cache_batch_idx)."""
+def _fp4_head_dim(who, hdim, name, t, k_cache, k_scale, v_cache):
+    """The head dim of an MXFP4 call: 128 (the callers' own checks refuse the rest), or with hdim the last extent of `t` (q or k_new),
+    which the code and scale arrays must match and FP8_HEAD_DIMS must hold"""
+    if not hdim:
+        return 128
+    widths = [(name, t.shape[-1] if isinstance(t, torch.Tensor) and t.dim() else None)]
+    widths += [(n, f * c.shape[-1] if isinstance(c, torch.Tensor) and c.dim() else None)
+               for n, f, c in (("k_cache", 2, k_cache), ("k_scale", 32, k_scale), ("v_cache", 2, v_cache))]
+    d = widths[0][1]
+    if any(w != d for _n, w in widths):
+        raise RuntimeError(f"{who}: the tensors do not have one head dim: " + ", ".join(f"{n} {w}" for n, w in widths) +
+                           " (two channels a code byte, 32 a k_scale byte)")
+    if d not in FP8_HEAD_DIMS:
+        raise NotImplementedError(f"{who}: head_dim {d} is not supported (64, 128 or 256)")
+    return d
+
+
+def _fp4_cache(who, k_cache, k_scale, v_cache, v_scale, block_table, cache_batch_idx, b, d=128):
+    """The four arrays of an MXFP4 cache at head dim d as uint8 views with their geometry: (arrays, H_kv, capacity, cache_batch, the
+    eight byte strides in the C order, (block_table_row_stride, num_blocks, page_block_size), block_table, cache_batch_idx)."""
+    hb, sb = d // 2, d // 32
     kc, vc = (_fp4_u8(who, n, t, "float4_e2m1fn_x2") for n, t in (("k_cache", k_cache), ("v_cache", v_cache)))
     ks, vs = (_fp4_u8(who, n, t, "float8_e8m0fnu") for n, t in (("k_scale", k_scale), ("v_scale", v_scale)))
     paged = block_table is not None
@@ -2823,13 +2848,13 @@ def _fp4_cache(who, k_cache, k_scale, v_cache, v_scale, block_table, cache_batch
             dt = t.dtype if isinstance(t, torch.Tensor) else type(t).__name__
             raise NotImplementedError(f"{who}: {name} of dtype {dt} is not supported (int32 tensor expected)")
     if kc.dim() != 4:
-        raise RuntimeError(f"{who}: k_cache must be (B_cache, cache_len, H_kv, 64) code bytes or a pool (num_blocks, page_block_size, "
-                           f"H_kv, 64); got {tuple(kc.shape)}")
-    if kc.shape[3] != 64:
+        raise RuntimeError(f"{who}: k_cache must be (B_cache, cache_len, H_kv, {hb}) code bytes or a pool (num_blocks, page_block_size, "
+                           f"H_kv, {hb}); got {tuple(kc.shape)}")
+    if kc.shape[3] != hb:
         raise NotImplementedError(f"{who}: head_dim {2 * kc.shape[3]} is not supported (128 only: 64 code bytes a head); got k_cache "
                                   f"of shape {tuple(kc.shape)}")
     lead, hkv = tuple(kc.shape[:2]), kc.shape[2]
-    want = dict(k_scale=(*lead, hkv, 4), v_cache=(*lead, hkv, 64), v_scale=(*lead, hkv))
+    want = dict(k_scale=(*lead, hkv, sb), v_cache=(*lead, hkv, hb), v_scale=(*lead, hkv))
     for name, t in (("k_scale", ks), ("v_cache", vc), ("v_scale", vs)):
         if tuple(t.shape) != want[name]:
             raise RuntimeError(f"{who}: {name} of shape {tuple(t.shape)} does not match k_cache {tuple(kc.shape)}: {want[name]} expected "
@@ -2837,7 +2862,7 @@ def _fp4_cache(who, k_cache, k_scale, v_cache, v_scale, block_table, cache_batch
     if hkv < 1 or lead[0] < 1 or lead[1] < 1:
         raise RuntimeError(f"{who}: the caches must hold at least one token and one head; got k_cache of shape {tuple(kc.shape)}")
     strides = []
-    for name, t, width in (("k_cache", kc, 64), ("k_scale", ks, 4), ("v_cache", vc, 64), ("v_scale", vs, 1)):
+    for name, t, width in (("k_cache", kc, hb), ("k_scale", ks, sb), ("v_cache", vc, hb), ("v_scale", vs, 1)):
         if (t.dim() == 4 and t.stride(3) != 1) or (hkv > 1 and t.stride(2) != width):
             raise ValueError(f"{who}: {name} must have adjacent heads with a contiguous last dim (strides {t.stride()})")
         strides += [t.stride(0) if lead[0] > 1 else 0, t.stride(1) if lead[1] > 1 else hkv * width]
@@ -2874,14 +2899,15 @@ def _fp4_lens(who, cache_seqlens, b, device, required):
 
 
 def fp4_kvcache_append(k_new, v_new, k_cache, k_scale, v_cache, v_scale, cache_seqlens, block_table=None, cache_batch_idx=None,
-                       k_descale=None, v_descale=None):
+                       k_descale=None, v_descale=None, *, hdim=False):
     """Quantise new tokens to MXFP4 and append them to the cache, in place (fa_fp4_kvcache_append): k_new, v_new (B, N_new, H_kv, 128)
     float16 / bfloat16 views at their own batch and token strides go to positions cache_seqlens[b] + i (int32 (B,) on the device, or an
     int: the lengths before the append, clamped to [0, capacity] there, not modified).  k_cache / v_cache: uint8 (or
     torch.float4_e2m1fn_x2) (B_cache, cap, H_kv, 64), k_scale uint8 (or torch.float8_e8m0fnu) (B_cache, cap, H_kv, 4), v_scale
     (B_cache, cap, H_kv), or with block_table pools (num_blocks, ps, ..); each at its own strides, never copied.  A token whose
     position, page or cache row lies outside the cache is dropped.  k_descale / v_descale float32 (B, H_kv) or (H_kv,), None = 1.
-    The arithmetic is include/fa_mi355x.h's, exact.  Nothing is read on the host.  Returns None."""
+    The arithmetic is include/fa_mi355x.h's, exact.  Nothing is read on the host.  Returns None.  hdim=True: through
+    fa_fp4_kvcache_append_hdim, whatever the other arguments, with a last extent d of 64, 128 or 256: codes (.., d / 2), k_scale (.., d / 32)."""
     who = "fp4_kvcache_append"
     for name, t in (("k_new", k_new), ("v_new", v_new)):
         if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float16, torch.bfloat16):
@@ -2890,41 +2916,43 @@ def fp4_kvcache_append(k_new, v_new, k_cache, k_scale, v_cache, v_scale, cache_s
     if k_new.dim() != 4 or v_new.shape != k_new.shape or v_new.dtype != k_new.dtype:
         raise RuntimeError(f"{who}: k_new and v_new must be (B, N_new, H_kv, 128) of one shape and dtype; got {tuple(k_new.shape)} "
                            f"{k_new.dtype}, {tuple(v_new.shape)} {v_new.dtype}")
-    if k_new.shape[3] != 128:
+    if not hdim and k_new.shape[3] != 128:
         raise NotImplementedError(f"{who}: head_dim {k_new.shape[3]} is not supported (128 only)")
+    d = _fp4_head_dim(who, hdim, "k_new", k_new, k_cache, k_scale, v_cache)
     b, nnew = k_new.shape[0], k_new.shape[1]
     arrays, hkv, cap, cbatch, strides, pages, block_table, cache_batch_idx = _fp4_cache(who, k_cache, k_scale, v_cache, v_scale, block_table,
-                                                                                        cache_batch_idx, b)
+                                                                                        cache_batch_idx, b, d)
     if k_new.shape[2] != hkv:
         raise RuntimeError(f"{who}: k_new has {k_new.shape[2]} heads, the caches {hkv}")
     cache_seqlens = _fp4_lens(who, cache_seqlens, b, k_new.device, True)
     _one_device(who, k_new, v_new, *arrays, cache_seqlens, block_table, cache_batch_idx)
     new = []
     for name, t in (("k_new", k_new), ("v_new", v_new)):
-        if t.numel() and ((hkv > 1 and t.stride(2) != 128) or t.stride(3) != 1):
+        if t.numel() and ((hkv > 1 and t.stride(2) != d) or t.stride(3) != 1):
             raise ValueError(f"{who}: {name} must have adjacent heads with a contiguous last dim (strides {t.stride()})")
-        new += [2 * t.stride(0) if b > 1 else 0, 2 * t.stride(1) if nnew > 1 else 2 * hkv * 128]
+        new += [2 * t.stride(0) if b > 1 else 0, 2 * t.stride(1) if nnew > 1 else 2 * hkv * d]
     kdp, vdp, dss, keep = _kv_descales(who, k_descale, v_descale, k_new, b, hkv)
     if b == 0 or nnew == 0:
         return
     with torch.cuda.device(k_new.device):
-        _call("fa_fp4_kvcache_append", (
+        _call("fa_fp4_kvcache_append_hdim" if hdim else "fa_fp4_kvcache_append", (
             k_new.data_ptr(), v_new.data_ptr(), *(t.data_ptr() for t in arrays), cache_seqlens.data_ptr(), _ptr(block_table),
-            _ptr(cache_batch_idx), kdp, vdp, b, hkv, nnew, cap, cbatch, 128, _DTYPE_CODE[k_new.dtype], *new, *strides, *pages, dss,
+            _ptr(cache_batch_idx), kdp, vdp, b, hkv, nnew, cap, cbatch, d, _DTYPE_CODE[k_new.dtype], *new, *strides, *pages, dss,
             _stream_ptr(k_new.device)))
     del keep
 
 
 def fp4_kvcache_forward(q, k_cache, k_scale, v_cache, v_scale, cache_seqlens=None, block_table=None, cache_batch_idx=None, q_descale=None,
                         k_descale=None, v_descale=None, softmax_scale=None, causal=False, num_splits=0, out_dtype=torch.bfloat16, out=None,
-                        *, window=(-1, -1), softcap=0.0, sinks=None):
+                        *, window=(-1, -1), softcap=0.0, sinks=None, hdim=False):
     """(o, lse) of decoding over an MXFP4 KV cache (fa_fp4_forward_kvcache): q (B, Nq, H_q, 128) torch.float8_e4m3fn at its own batch
     and token strides over the cache fp4_kvcache_append fills (its docstring has the four arrays); cache_seqlens int32 (B,) on the
     device, an int, or None (full); descales float32 (B, H_kv) or (H_kv,), None = 1.  o (B, Nq, H_q, 128) in out_dtype, lse float32
     (B, H_q, Nq).  Nothing is copied or read on the host; the partials live in the shim's persistent workspace.  out: an (o, lse) pair
     of contiguous tensors of those shapes and dtypes to write into (16- and 4-byte aligned), instead of fresh ones.  window (left,
     right; -1 = unbounded), softcap (0 = off) and sinks (float32 (H_q,) on q's device) are fa_fp4_forward_kvcache_mod's; a call with
-    none of them goes through fa_fp4_forward_kvcache."""
+    none of them goes through fa_fp4_forward_kvcache.  hdim=True: through fa_fp4_forward_kvcache_hdim, whatever the other arguments,
+    with a last extent d of 64, 128 or 256 on q and o over a cache of that width; softmax_scale defaults to d ** -0.5."""
     who = "fp4_kvcache_forward"
     if not isinstance(q, torch.Tensor) or q.dtype != torch.float8_e4m3fn:
         dt = q.dtype if isinstance(q, torch.Tensor) else type(q).__name__
@@ -2933,39 +2961,43 @@ def fp4_kvcache_forward(q, k_cache, k_scale, v_cache, v_scale, cache_seqlens=Non
         raise NotImplementedError(f"{who}: out_dtype {out_dtype} is not supported (torch.bfloat16 or torch.float16)")
     if q.dim() != 4:
         raise RuntimeError(f"{who}: q must be (B, Nq, H_q, 128), got {tuple(q.shape)}")
-    if q.shape[3] != 128:
+    if not hdim and q.shape[3] != 128:
         raise NotImplementedError(f"{who}: head_dim {q.shape[3]} is not supported (128 only); got q of shape {tuple(q.shape)}")
+    d = _fp4_head_dim(who, hdim, "q", q, k_cache, k_scale, v_cache)
     b, nq, hq = q.shape[0], q.shape[1], q.shape[2]
     arrays, hkv, cap, cbatch, strides, pages, block_table, cache_batch_idx = _fp4_cache(who, k_cache, k_scale, v_cache, v_scale, block_table,
-                                                                                        cache_batch_idx, b)
+                                                                                        cache_batch_idx, b, d)
     if hq == 0 or hq % hkv != 0:
         raise RuntimeError(f"{who}: H_q = {hq} must be a multiple of H_kv = {hkv}")
     cache_seqlens = _fp4_lens(who, cache_seqlens, b, q.device, False)
     _one_device(who, q, *arrays, cache_seqlens, block_table, cache_batch_idx)
-    scale = 128 ** -0.5 if softmax_scale is None else float(softmax_scale)
+    scale = d ** -0.5 if softmax_scale is None else float(softmax_scale)
     if not (math.isfinite(scale) and scale > 0.0):
         raise RuntimeError(f"{who}: softmax_scale must be finite and > 0 (got {scale})")
     ns = operator.index(num_splits)
     if ns < 0 or ns > 256:
         raise RuntimeError(f"{who}: num_splits must lie in [0, 256] (got {ns})")
-    if q.numel() and ((hq > 1 and q.stride(2) != 128) or q.stride(3) != 1):
+    if q.numel() and ((hq > 1 and q.stride(2) != d) or q.stride(3) != 1):
         raise ValueError(f"{who}: q must have adjacent heads with a contiguous last dim (strides {q.stride()})")
     qdp, qds, keep_q = _kv_descale(who, "q_descale", q_descale, q, b, hkv)
     kdp, kds, keep_k = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
     vdp, vds, keep_v = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
-    mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks)
+    mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks, hdim)
     with torch.cuda.device(q.device):
         if out is not None:
             o, lse = out
-            if (tuple(o.shape), o.dtype, tuple(lse.shape), lse.dtype) != ((b, nq, hq, 128), out_dtype, (b, hq, nq), torch.float32) or \
+            if (tuple(o.shape), o.dtype, tuple(lse.shape), lse.dtype) != ((b, nq, hq, d), out_dtype, (b, hq, nq), torch.float32) or \
                     not (o.is_contiguous() and lse.is_contiguous() and o.device == q.device and lse.device == q.device):
-                raise RuntimeError(f"{who}: out must be contiguous (o ({b}, {nq}, {hq}, 128) {out_dtype}, lse ({b}, {hq}, {nq}) float32) on q's device")
+                raise RuntimeError(f"{who}: out must be contiguous (o ({b}, {nq}, {hq}, {d}) {out_dtype}, lse ({b}, {hq}, {nq}) float32) on q's device")
         else:
-            o = torch.empty((b, nq, hq, 128), dtype=out_dtype, device=q.device)
+            o = torch.empty((b, nq, hq, d), dtype=out_dtype, device=q.device)
             lse = torch.empty((b, hq, nq), dtype=torch.float32, device=q.device)
         if b == 0 or nq == 0:
             return o, lse
-        if mod:
+        if hdim:
+            need = int(_lib.fa_fp4_forward_kvcache_hdim_workspace_bytes(b, hq, hkv, nq, cap, d, ns, int(bool(causal)), tail[0], tail[1],
+                                                                        int(sinks is not None)))
+        elif mod:
             need = int(_lib.fa_fp4_forward_kvcache_workspace_bytes_mod(b, hq, hkv, nq, cap, 128, ns, int(bool(causal)), tail[0], tail[1],
                                                                        int(sinks is not None)))
         else:
@@ -2973,8 +3005,8 @@ def fp4_kvcache_forward(q, k_cache, k_scale, v_cache, v_scale, cache_seqlens=Non
         ws = _workspace(q.device, need)
         _call("fa_fp4_forward_kvcache" + mod, (
             q.data_ptr(), *(t.data_ptr() for t in arrays), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp, _ptr(cache_seqlens),
-            _ptr(block_table), _ptr(cache_batch_idx), b, hq, hkv, nq, cap, cbatch, 128, _DTYPE_CODE[out_dtype],
-            q.stride(0) if b > 1 else 0, q.stride(1) if nq > 1 else hq * 128, *strides, *pages, qds, kds, vds, int(bool(causal)), scale, ns,
+            _ptr(block_table), _ptr(cache_batch_idx), b, hq, hkv, nq, cap, cbatch, d, _DTYPE_CODE[out_dtype],
+            q.stride(0) if b > 1 else 0, q.stride(1) if nq > 1 else hq * d, *strides, *pages, qds, kds, vds, int(bool(causal)), scale, ns,
             ws.data_ptr() if need else 0, ws.numel() if need else 0, _stream_ptr(q.device), *tail))
     del keep_q, keep_k, keep_v, keep_s
     return o, lse
@@ -2982,7 +3014,7 @@ def fp4_kvcache_forward(q, k_cache, k_scale, v_cache, v_scale, cache_seqlens=Non
 
 def fp4_varlen_forward(q, k_cache, k_scale, v_cache, v_scale, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, block_table,
                        q_descale=None, k_descale=None, v_descale=None, softmax_scale=None, causal=False, out_dtype=torch.bfloat16, out=None,
-                       *, window=(-1, -1), softcap=0.0, sinks=None):
+                       *, window=(-1, -1), softcap=0.0, sinks=None, hdim=False):
     """(o, lse) of chunked prefill over the paged MXFP4 KV cache (fa_fp4_forward_varlen): q (total_q, H_q, 128)
     torch.float8_e4m3fn at its own token stride (a view such as qkv8[:, 0] is used in place) over the pools fp4_kvcache_append fills
     (its docstring has the four arrays) under block_table int32 (B, max_blocks); cu_seqlens_q / cu_seqlens_k int32 (B + 1,) on the
@@ -2991,7 +3023,8 @@ def fp4_varlen_forward(q, k_cache, k_scale, v_cache, v_scale, cu_seqlens_q, cu_s
     or (H_kv,), None = 1.  o (total_q, H_q, 128) in out_dtype, lse float32 (H_q, total_q); rows of no sequence keep their contents
     (a fresh output is uninitialised there).  One launch, no workspace.  out: an (o, lse) pair of contiguous tensors to write into.
     window, softcap and sinks (float32 (H_q,)) are fa_fp4_forward_varlen_mod's; a call with none of them goes through
-    fa_fp4_forward_varlen."""
+    fa_fp4_forward_varlen.  hdim=True: through fa_fp4_forward_varlen_hdim, whatever the other arguments, with a last extent d of 64,
+    128 or 256 on q and o over pools of that width; softmax_scale defaults to d ** -0.5."""
     who = "fp4_varlen_forward"
     if not isinstance(q, torch.Tensor) or q.dtype != torch.float8_e4m3fn:
         dt = q.dtype if isinstance(q, torch.Tensor) else type(q).__name__
@@ -3000,8 +3033,9 @@ def fp4_varlen_forward(q, k_cache, k_scale, v_cache, v_scale, cu_seqlens_q, cu_s
         raise NotImplementedError(f"{who}: out_dtype {out_dtype} is not supported (torch.bfloat16 or torch.float16)")
     if q.dim() != 3:
         raise RuntimeError(f"{who}: q must be packed (total_q, H_q, 128), got {tuple(q.shape)}")
-    if q.shape[2] != 128:
+    if not hdim and q.shape[2] != 128:
         raise NotImplementedError(f"{who}: head_dim {q.shape[2]} is not supported (128 only); got q of shape {tuple(q.shape)}")
+    d = _fp4_head_dim(who, hdim, "q", q, k_cache, k_scale, v_cache)
     if block_table is None:
         raise RuntimeError(f"{who}: block_table is required (a contiguous (B, cap, H_kv, ..) cache is a pool of B * cap / ps pages "
                            f"under an arange table)")
@@ -3014,36 +3048,36 @@ def fp4_varlen_forward(q, k_cache, k_scale, v_cache, v_scale, cu_seqlens_q, cu_s
     max_q, max_k = operator.index(max_seqlen_q), operator.index(max_seqlen_k)
     if max_q < 0 or max_k < 0:
         raise RuntimeError(f"{who}: max_seqlen_q and max_seqlen_k must be >= 0 (got {max_q}, {max_k})")
-    arrays, hkv, cap, _cbatch, strides, pages, block_table, _ = _fp4_cache(who, k_cache, k_scale, v_cache, v_scale, block_table, None, b)
+    arrays, hkv, cap, _cbatch, strides, pages, block_table, _ = _fp4_cache(who, k_cache, k_scale, v_cache, v_scale, block_table, None, b, d)
     if hq == 0 or hq % hkv != 0:
         raise RuntimeError(f"{who}: H_q = {hq} must be a multiple of H_kv = {hkv}")
     _one_device(who, q, *arrays, cu_seqlens_q, cu_seqlens_k, block_table)
-    scale = 128 ** -0.5 if softmax_scale is None else float(softmax_scale)
+    scale = d ** -0.5 if softmax_scale is None else float(softmax_scale)
     if not (math.isfinite(scale) and scale > 0.0):
         raise RuntimeError(f"{who}: softmax_scale must be finite and > 0 (got {scale})")
-    if q.numel() and ((hq > 1 and q.stride(1) != 128) or q.stride(2) != 1):
+    if q.numel() and ((hq > 1 and q.stride(1) != d) or q.stride(2) != 1):
         raise ValueError(f"{who}: q must have adjacent heads with a contiguous last dim (strides {q.stride()})")
     qdp, qds, keep_q = _kv_descale(who, "q_descale", q_descale, q, b, hkv)
     kdp, kds, keep_k = _kv_descale(who, "k_descale", k_descale, q, b, hkv)
     vdp, vds, keep_v = _kv_descale(who, "v_descale", v_descale, q, b, hkv)
     cu_seqlens_q, cu_seqlens_k = cu_seqlens_q.contiguous(), cu_seqlens_k.contiguous()
-    mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks)
+    mod, tail, keep_s = _fp8_mod(who, q, hq, window, softcap, sinks, hdim)
     with torch.cuda.device(q.device):
         if out is not None:
             o, lse = out
-            if (tuple(o.shape), o.dtype, tuple(lse.shape), lse.dtype) != ((total_q, hq, 128), out_dtype, (hq, total_q), torch.float32) or \
+            if (tuple(o.shape), o.dtype, tuple(lse.shape), lse.dtype) != ((total_q, hq, d), out_dtype, (hq, total_q), torch.float32) or \
                     not (o.is_contiguous() and lse.is_contiguous() and o.device == q.device and lse.device == q.device):
-                raise RuntimeError(f"{who}: out must be contiguous (o ({total_q}, {hq}, 128) {out_dtype}, lse ({hq}, {total_q}) float32) on q's device")
+                raise RuntimeError(f"{who}: out must be contiguous (o ({total_q}, {hq}, {d}) {out_dtype}, lse ({hq}, {total_q}) float32) on q's device")
         else:
-            o = torch.empty((total_q, hq, 128), dtype=out_dtype, device=q.device)
+            o = torch.empty((total_q, hq, d), dtype=out_dtype, device=q.device)
             lse = torch.empty((hq, total_q), dtype=torch.float32, device=q.device)
         max_q = min(max_q, total_q)
         if b == 0 or total_q == 0 or max_q == 0:
             return o, lse
         _call("fa_fp4_forward_varlen" + mod, (
             q.data_ptr(), *(t.data_ptr() for t in arrays), o.data_ptr(), lse.data_ptr(), qdp, kdp, vdp, cu_seqlens_q.data_ptr(),
-            cu_seqlens_k.data_ptr(), block_table.data_ptr(), b, hq, hkv, total_q, max_q, cap, 128, _DTYPE_CODE[out_dtype],
-            q.stride(0) if total_q > 1 else hq * 128, *strides, *pages, qds, kds, vds, int(bool(causal)), scale, _stream_ptr(q.device),
+            cu_seqlens_k.data_ptr(), block_table.data_ptr(), b, hq, hkv, total_q, max_q, cap, d, _DTYPE_CODE[out_dtype],
+            q.stride(0) if total_q > 1 else hq * d, *strides, *pages, qds, kds, vds, int(bool(causal)), scale, _stream_ptr(q.device),
             *tail))
     del keep_q, keep_k, keep_v, keep_s
     return o, lse

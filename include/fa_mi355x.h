@@ -1684,6 +1684,53 @@ int fa_fp4_forward_varlen_mod(const void* q, const void* k_cache, const void* k_
                               int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale,
                               void* stream, int64_t window_left, int64_t window_right, double softcap, const float* sinks,
                               int64_t sink_heads);
+/* --- The MXFP4 KV cache at head dims 64 and 256 beside 128 (csrc/fa_fp4_hdim.hip), forward: each call is its parent's
+ * argument list with the head dim under the name head_dim in {64, 128, 256}; the parent of the append is fa_fp4_kvcache_append, the
+ * parents of the two readers are their _mod forms.  Any other head_dim: FA_ERR_UNSUPPORTED, "head_dim N is not supported (64, 128 or
+ * 256)".  At 128 each call IS its parent: the same checks, launches and route counts.  The cache is the parent's rule at width d:
+ *     k_cache, v_cache  uint8 (.., heads_kv, d / 2)   two e2m1 codes a byte, the low nibble the even channel; rows 16-byte aligned
+ *     k_scale           uint8 (.., heads_kv, d / 32)  one E8M0 byte per 32 channels; rows (and the pointer) d / 32-byte aligned
+ *     v_scale           uint8 (.., heads_kv)          ONE E8M0 byte a (token, head): the maximum runs over all d channels
+ * 67 bytes a token and head at d = 64 (128 in e4m3), 265 at d = 256 (512).  q, k_new, v_new and o have d channels a head (the
+ * stride floors of the parents with d in the place of 128).  The exponent and tie rules, the descales, the softmax with V's
+ * exponent in it, the window / softcap / sinks, the split rule, the combine, the trust rules (untrusted lengths, table and
+ * cache_batch_idx, dropped tokens, pages outside the pool as zero codes with byte 127) and graph replay are the parents'.  The
+ * workspace is the parents' layout at d (fa_fp4_forward_kvcache_hdim_workspace_bytes; at 128 it is .._workspace_bytes_mod).
+ * At d = 256 both readers run one wave a SIMD (128 accumulators a lane).  Checks: the parent's, in its order. */
+int fa_fp4_kvcache_append_hdim(const void* k_new, const void* v_new, void* k_cache, void* k_scale, void* v_cache, void* v_scale,
+                          const int32_t* cache_seqlens, const int32_t* block_table, const int32_t* cache_batch_idx,
+                          const float* k_descale, const float* v_descale, int64_t batch, int64_t heads_kv, int64_t seqlen_new,
+                          int64_t cache_len, int64_t cache_batch, int64_t head_dim, int dtype, int64_t k_new_batch_stride,
+                          int64_t k_new_token_stride, int64_t v_new_batch_stride, int64_t v_new_token_stride, int64_t k_batch_stride,
+                          int64_t k_token_stride, int64_t k_scale_batch_stride, int64_t k_scale_token_stride, int64_t v_batch_stride,
+                          int64_t v_token_stride, int64_t v_scale_batch_stride, int64_t v_scale_token_stride,
+                          int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size, int64_t descale_batch_stride,
+                          void* stream);
+int fa_fp4_forward_kvcache_hdim(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o,
+                               float* lse, const float* q_descale, const float* k_descale, const float* v_descale,
+                               const int32_t* cache_seqlens, const int32_t* block_table, const int32_t* cache_batch_idx, int64_t batch,
+                               int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len, int64_t cache_batch, int64_t head_dim,
+                               int dtype, int64_t q_batch_stride, int64_t q_token_stride, int64_t k_batch_stride, int64_t k_token_stride,
+                               int64_t k_scale_batch_stride, int64_t k_scale_token_stride, int64_t v_batch_stride,
+                               int64_t v_token_stride, int64_t v_scale_batch_stride, int64_t v_scale_token_stride,
+                               int64_t block_table_row_stride, int64_t num_blocks, int64_t page_block_size,
+                               int64_t q_descale_batch_stride, int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal,
+                               double softmax_scale, int64_t num_splits, void* workspace, size_t workspace_bytes, void* stream,
+                               int64_t window_left, int64_t window_right, double softcap, const float* sinks, int64_t sink_heads);
+size_t fa_fp4_forward_kvcache_hdim_workspace_bytes(int64_t batch, int64_t heads_q, int64_t heads_kv, int64_t seqlen_q, int64_t cache_len,
+                                                  int64_t head_dim, int64_t num_splits, int causal, int64_t window_left, int64_t window_right,
+                                                  int with_sinks);
+int fa_fp4_forward_varlen_hdim(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o,
+                              float* lse, const float* q_descale, const float* k_descale, const float* v_descale,
+                              const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, const int32_t* block_table, int64_t batch,
+                              int64_t heads_q, int64_t heads_kv, int64_t total_q, int64_t max_seqlen_q, int64_t cache_len, int64_t head_dim,
+                              int dtype, int64_t q_token_stride, int64_t k_batch_stride, int64_t k_token_stride,
+                              int64_t k_scale_batch_stride, int64_t k_scale_token_stride, int64_t v_batch_stride, int64_t v_token_stride,
+                              int64_t v_scale_batch_stride, int64_t v_scale_token_stride, int64_t block_table_row_stride,
+                              int64_t num_blocks, int64_t page_block_size, int64_t q_descale_batch_stride,
+                              int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale,
+                              void* stream, int64_t window_left, int64_t window_right, double softcap, const float* sinks,
+                              int64_t sink_heads);
 
 const char* fa_last_error(void);
 const char* fa_version(void);
@@ -1712,7 +1759,9 @@ int fa_profile_report(char* buf, size_t cap);
  * fa_fp4_kvcache_append and fa_fp4_forward_kvcache, one count a call that launched.  "fp4kv_prefill": the kernel of
  * fa_fp4_forward_varlen, one count a call that launched.  "fp4kv_split_mod", "fp4kv_prefill_mod": the featured kernels of
  * fa_fp4_forward_kvcache_mod and fa_fp4_forward_varlen_mod, one count a call that launched one (a _mod call with default trailing
- * arguments counts its parent's route and not these). */
+ * arguments counts its parent's route and not these).  "fp4kv_append_hdim", "fp4kv_split_hdim", "fp4kv_prefill_hdim": the head dim
+ * 64 / 256 kernels of fa_fp4_kvcache_append_hdim, fa_fp4_forward_kvcache_hdim and fa_fp4_forward_varlen_hdim, one count a call that
+ * launched one (head_dim 128 counts what the parent call counts). */
 int64_t fa_route_count(const char* name);
 
 #ifdef __cplusplus

@@ -93,7 +93,10 @@ with spreads.  `fp4_mod_decode`: Nq 1, 32768 cached keys, B 8 and 64, causal win
 parent call on a cache cut to the window's keys (the work a windowed call should do) and the e4m3 decode call with the same window.
 `fp4_mod_prefill`: a 2048-token chunk at the end of 32768 keys (paged, ps 16, B 8), windows 1024 and 4096: the windowed call, the
 parent call without a window and fp8_varlen_forward(block_table=, window=); the tile count of the walk over the unwindowed one.
-`fp4_mod_alone`: softcap 30 alone and sinks alone on the unwindowed B 64 decode row and the B 8 prefill row against the parent."""
+`fp4_mod_alone`: softcap 30 alone and sinks alone on the unwindowed B 64 decode row and the B 8 prefill row against the parent.
+`--fp4-hdim`: the MXFP4 cache at head dims 64 and 256, H 32:4, interleaved rounds, medians with spreads, each
+against the e4m3 call at the same d on the same tokens.  `fp4_hdim_decode`: Nq 1, B 8 and 64, 4096 / 16384 / 32768 keys.
+`fp4_hdim_prefill`: a 2048-token causal chunk at the end of 16384 keys (paged, ps 16, B 8), plain and with a 1024-key window."""
 import argparse
 import json
 import os
@@ -718,6 +721,65 @@ def fp4_mod_rows(args, dtype):
     return rows
 
 
+def fp4_hdim_rows(args, dtype):
+    """--fp4-hdim: see the module docstring"""
+    dev, rounds, hq, hkv, ps = "cuda", max(args.rounds, 5), 32, 4, 16
+    mags = torch.tensor([0, .5, 1, 1.5, 2, 3, 4, 6, -0., -.5, -1, -1.5, -2, -3, -4, -6], dtype=torch.float32, device=dev)
+    spread = lambda t, m: round((max(t) - min(t)) / m, 3)   # noqa: E731
+
+    def caches(lead, d):
+        """random MXFP4 arrays (*lead, hkv, ..) at width d and the same values in e4m3 (exact), 2^20 tokens at a time"""
+        kc, vc = (torch.randint(0, 256, (*lead, hkv, d // 2), device=dev, dtype=torch.uint8) for _ in range(2))
+        ks = torch.randint(124, 131, (*lead, hkv, d // 32), device=dev, dtype=torch.uint8)
+        vs = torch.randint(124, 131, (*lead, hkv), device=dev, dtype=torch.uint8)
+        k8, v8 = (torch.empty((*lead, hkv, d), device=dev, dtype=torch.float8_e4m3fn) for _ in range(2))
+        for c4, sc, out in ((kc, ks, k8), (vc, vs, v8)):
+            c2, s2, o2 = c4.view(-1, hkv, d // 2), sc.view(lead[0] * lead[1], hkv, -1), out.view(-1, hkv, d)
+            for lo in range(0, c2.shape[0], 1 << 20):
+                x = mags[torch.stack((c2[lo:lo + (1 << 20)] & 15, c2[lo:lo + (1 << 20)] >> 4), -1).flatten(-2).long()]
+                e = torch.exp2(s2[lo:lo + (1 << 20)].float() - 127.0)
+                o2[lo:lo + (1 << 20)] = (x * e.repeat_interleave(d // e.shape[-1], -1)).to(torch.float8_e4m3fn)
+        return (kc, ks, vc, vs), k8, v8
+
+    def race(kind, fp4, fp8, **tags):
+        torch.testing.assert_close(fp4()[0].float(), fp8()[0].float(), rtol=5e-2, atol=5e-2)
+        t4, t8 = [], []
+        for _ in range(rounds):
+            t8.append(timed(fp8, args.warmup, args.iters, 1))
+            t4.append(timed(fp4, args.warmup, args.iters, 1))
+        m4, m8 = statistics.median(t4), statistics.median(t8)
+        row = dict(kind=kind, **tags, e4m3_us=round(m8, 2), fp4_us=round(m4, 2), ratio=round(m4 / m8, 3), e4m3_spread=spread(t8, m8), fp4_spread=spread(t4, m4))
+        print(json.dumps(row), flush=True)
+        return row
+
+    rows = []
+    for d in (64, 256):
+        qd, kd, vd = (torch.full((64, hkv), x, dtype=torch.float32, device=dev) for x in (0.25, 0.0625, 0.5))
+        for b in (8, 64):
+            for L in (4096, 16384, 32768):
+                a4, k8, v8 = caches((b, L), d)
+                q8 = torch.randn((b, 1, hq, d), device=dev).to(torch.float8_e4m3fn)
+                sl = torch.full((b,), L, dtype=torch.int32, device=dev)
+                rows.append(race("fp4_hdim_decode", lambda: ext.fp4_kvcache_forward(q8, *a4, sl, None, None, qd[:b], kd[:b], vd[:b], None, False, 0, dtype, hdim=True),
+                                 lambda: ext.fp8_kvcache_forward(q8, k8, v8, sl, None, None, qd[:b], kd[:b], vd[:b], None, False, 0, dtype, hdim=True),
+                                 d=d, b=b, L=L, byte_ratio=round((d // 2 * 2 + d // 32 + 1) / (2 * d), 3)))
+                del a4, k8, v8
+                torch.cuda.empty_cache()
+        b, L, n = 8, 16384, 2048                                   # one 2048-token chunk at the end of 16384 keys, paged
+        a4, k8, v8 = caches((b * L // ps, ps), d)
+        table = torch.randperm(b * L // ps, device=dev).view(b, L // ps).to(torch.int32)
+        qp = torch.randn((b * n, hq, d), device=dev).to(torch.float8_e4m3fn)
+        cu_q, cu_k = (torch.arange(b + 1, dtype=torch.int32, device=dev) * x for x in (n, L))
+        for w in (-1, 1024):
+            rows.append(race("fp4_hdim_prefill",
+                             lambda: ext.fp4_varlen_forward(qp, *a4, cu_q, cu_k, n, L, table, qd[:b], kd[:b], vd[:b], None, True, dtype, window=(w, -1), hdim=True),
+                             lambda: ext.fp8_varlen_forward(qp, k8, v8, cu_q, cu_k, n, L, True, None, qd[:b], kd[:b], vd[:b], dtype, table, window=(w, -1), hdim=True),
+                             d=d, b=b, L=L, chunk=n, window=w))
+        del a4, k8, v8
+        torch.cuda.empty_cache()
+    return rows
+
+
 def fp4_rows(args, dtype):
     """--fp4: see the module docstring"""
     dev, rounds, hq, hkv = "cuda", max(args.rounds, 5), 32, 8
@@ -1024,6 +1086,7 @@ def main():
     ap.add_argument("--fp4", action="store_true", help="time decoding over the MXFP4 cache against the e4m3 decode call, and the append: see the module docstring")
     ap.add_argument("--fp4-prefill", action="store_true", help="time chunked prefill over the MXFP4 cache against the decode call and the e4m3 packed call: see the module docstring")
     ap.add_argument("--fp4-mod", action="store_true", help="time a window, a softcap and sinks over the MXFP4 cache against the parent calls and the e4m3 calls: see the module docstring")
+    ap.add_argument("--fp4-hdim", action="store_true", help="time the MXFP4 cache calls at head dims 64 / 256 against the e4m3 calls at the same d: see the module docstring")
     ap.add_argument("--md", default=None, help="--fp8-step: write the table as markdown to this path")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
@@ -1039,6 +1102,12 @@ def main():
         ext.ex_kvcache_forward(wq, wk, wk, None, None, wl, True, None)
     torch.cuda.synchronize()
     del wq, wk
+    if args.fp4_hdim:
+        rows = fp4_hdim_rows(args, dtype)
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(dict(fp4_hdim=True, dtype=args.dtype, version=ext.version(), rows=rows), f, indent=1)
+        return
     if args.fp4_mod:
         rows = fp4_mod_rows(args, dtype)
         if args.json:
