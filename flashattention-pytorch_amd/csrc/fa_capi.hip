@@ -4049,7 +4049,7 @@ static int fp4_kvcache_append_impl(const char* who, bool hdim, const void* k_new
     a.kds_bs = k.kds_bs; a.vds_bs = k.vds_bs; a.batch = batch; a.seqlen_new = seqlen_new;
     a.kn_bs = k_new_batch_stride; a.kn_ts = k_new_token_stride; a.vn_bs = v_new_batch_stride; a.vn_ts = v_new_token_stride;
     a.dtype = dtype; a.d = d;
-    return launched(who, fa::launch_fp4_kvcache_append_hdim(a, reinterpret_cast<hipStream_t>(stream)));   // (d == 128: launch_fp4_kvcache_append)
+    return launched(who, fa::launch_fp4_kvcache_append(a, reinterpret_cast<hipStream_t>(stream)));   // (d in {64, 128, 256})
 }
 
 #define FP4_APPEND_ARGS k_new, v_new, k_cache, k_scale, v_cache, v_scale, cache_seqlens, block_table, cache_batch_idx, k_descale, v_descale, batch, \
@@ -4141,7 +4141,7 @@ static int fp4_forward_kvcache_impl(const char* who, const fa::Fp8Mod& m, const 
     a.qds_bs = k.qds_bs; a.kds_bs = k.kds_bs; a.vds_bs = k.vds_bs;
     a.batch = batch; a.heads_q = heads_q; a.seqlen_q = seqlen_q; a.q_bs = q_batch_stride; a.q_ts = q_token_stride;
     a.dtype = k.dtype; a.causal = causal != 0; a.scale = (float)softmax_scale; a.num_splits = S; a.workspace = workspace; a.d = k.d;
-    return launched(who, fa::launch_fp4_kvcache_hdim(a, m, reinterpret_cast<hipStream_t>(stream)));   // (d == 128: launch_fp4_kvcache_mod)
+    return launched(who, fa::launch_fp4_kvcache(a, m, reinterpret_cast<hipStream_t>(stream)));   // (d in {64, 128, 256}; m not any(): the plain kernel)
 }
 
 int fa_fp4_forward_kvcache(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o, float* lse,
@@ -4244,7 +4244,7 @@ static int fp4_forward_varlen_impl(const char* who, const fa::Fp8Mod& m, const F
     a.qds_bs = k.qds_bs; a.kds_bs = k.kds_bs; a.vds_bs = k.vds_bs; a.cu_seqlens_q = cu_seqlens_q; a.cu_seqlens_k = cu_seqlens_k;
     a.batch = batch; a.heads_q = heads_q; a.total_q = total_q; a.max_seqlen_q = max_seqlen_q; a.q_ts = q_token_stride;
     a.dtype = k.dtype; a.causal = causal != 0; a.scale = (float)softmax_scale; a.d = k.d;
-    return launched(who, fa::launch_fp4_prefill_hdim(a, m, reinterpret_cast<hipStream_t>(stream)));   // (d == 128: launch_fp4_prefill_mod)
+    return launched(who, fa::launch_fp4_prefill(a, m, reinterpret_cast<hipStream_t>(stream)));   // (d in {64, 128, 256}; m not any(): the plain kernel)
 }
 
 int fa_fp4_forward_varlen(const void* q, const void* k_cache, const void* k_scale, const void* v_cache, const void* v_scale, void* o, float* lse,

@@ -1,6 +1,8 @@
-// Chunked prefill over the paged MXFP4 KV cache for gfx950 (fa_fp4_forward_varlen; include/fa_mi355x.h):
-// packed e4m3 queries (total_q, H_q, 128) over the four pool arrays fa_fp4_kvcache_append fills, per sequence, with the bottom-right
-// causal diagonal of that sequence alone, in one launch and without a workspace.
+// Chunked prefill over the paged MXFP4 KV cache for gfx950 at head dim d in {64, 128, 256} (fa_fp4_forward_varlen and its _mod /
+// _hdim entry points; include/fa_mi355x.h; DESIGN.md sections 9zh - 9zj): packed e4m3 queries (total_q, H_q, d) over the four pool
+// arrays fa_fp4_kvcache_append fills, per sequence, with the bottom-right causal diagonal of that sequence alone, in one launch and
+// without a workspace.  Two bodies behind one launcher: fp4kv_prefill_kernel<Tag, Mod...> at 128, fp4kv_prefill_hdim_kernel<Tag, D,
+// Mod...> at 64 / 256 on Fp4Hd<D> and the shared tile pieces of fa_fp4_common.h.
 //
 //     o[i] = sum_j softmax_j(softmax_scale q_descale k_descale q8[i] . (k4[j] 2^ek[j])) v4[j] 2^ev[j] v_descale
 //
@@ -13,23 +15,35 @@
 //                    idles through a quarter of the diagonal as it would with one head a wave.  The grid is (row tiles of
 //                    max_seqlen_q, H_kv, B), the heaviest (last) row tile first; a workgroup past its sequence's rows returns.
 //   the tile ring    tile t is computed from LDS stage t & 1 while tile t + 1 lies in the other stage and tile t + 2 is in flight
-//                    in 9 registers a lane (three tiles deep); the table entry of tile t + 3 is fetched at the same time.  One
+//                    in 9 registers a lane at 128 (three tiles deep); the table entry of tile t + 3 is fetched at the same time.  One
 //                    barrier a tile: a stage is rewritten at the top of iteration t + 1, after the barrier that ended its last reader.
 //   the loader       wave w moves the tile's 16-key group w (ps % 16 == 0: one page, one wave-uniform table entry):
-//                      K      lane (kk = l >> 2, c = l & 3): 16 code bytes of key kk -> row 80 (16 w + kk) + 16 c of the K stage
-//                      scales lanes 0 .. 15 the k_scale dword of key l -> byte 64 of the key's row; lanes 16 .. 31 the v_scale
+//                      K      16 keys x D / 32 chunks of 16 code bytes, chunk id = lane + 64 i -> (key id / (D / 32), chunk id %
+//                             (D / 32)) -> row KROW (16 w + key) + 16 chunk of the K stage
+//                      scales lanes 0 .. 15 the k_scale row of key l -> byte D / 2 of the key's row; lanes 16 .. 31 the v_scale
 //                             byte of key l - 16 -> evs[key] = byte - 127
 //                      V      lane (rd = l & 15, hv = (l >> 4) & 1, jl = l >> 5): the dwords at channels 8 rd .. + 7 of the four
-//                             keys pos = 4 hv + 8 jl + c of the group (a row of 16 lanes reads a key's 64 bytes), the decode kernel's
+//                             keys pos = 4 hv + 8 jl + c of the group (a row of 16 lanes reads 64 bytes of a key), the decode kernel's
 //                             nibble transpose cut to four keys (mask / shift / or, then 4 v_perm_b32), and eight 2-byte writes into
 //                             the V^T image: channel 8 rd + 2 m (+ 1), byte 16 h + 8 hv + 2 j with h = w >> 1, j = 2 (w & 1) + jl.
+//                    by width:          D = 64                        D = 128                  D = 256
+//                      K chunks a lane  1, lanes 0 .. 31 alone         1                        2
+//                      k_scale row      a ushort                      a dword                  two dwords
+//                      K stage row      48 bytes                      80                       144
+//                      V                two keys a lane, byte writes  four keys, as above      the 128 map twice (channels 128 pass
+//                                       (below)                                                + 8 rd ..), eight dwords a lane
+//                      LDS, two stages  11008 bytes                   19456                    36352
+//                      V at 64: lane (rd = l & 7, hv = (l >> 3) & 1, jl = (l >> 4) & 1, cc = l >> 5) loads channels 8 rd .. of the TWO
+//                      keys 4 hv + 8 jl + 2 cc (+ 1); mask / shift / or give a byte a channel, written at row byte 16 h + 8 hv + 2 j +
+//                      cc with h = w >> 1, j = 2 (w & 1) + jl.
 //                    So V is transposed ONCE a workgroup and tile, out of the registers the load landed in; the raw codes never
 //                    lie in LDS.  A key at or past the workgroup's last visible key or on a page outside [0, num_blocks) is not
 //                    loaded: zero codes, scale bytes 127, ev = 0.  A group whole below that bound on a valid page skips the
 //                    per-lane compares (wave-uniform).
-//   LDS              K stage: 64 rows of 80 bytes (64 codes, 4 scale bytes, 12 unused): the 16-byte operand reads of 16 lanes land
-//                    at 80 r mod 256 = sixteen different multiples of 16, every bank once.  V^T stage: vt4_off's padded image of
-//                    the decode kernel, 4352 bytes.  evs: 64 ints.  2 x 9728 = 19456 bytes.
+//   LDS              K stage: 64 rows of KROW bytes, D / 2 code bytes + D / 32 scale bytes padded to an ODD multiple of 16 (48 /
+//                    80 / 144), so the 16-byte operand reads of 16 lanes land at sixteen different multiples of 16 mod 256, every
+//                    bank once.  V^T stage: vt4_off's padded image of the decode kernel, 34 D bytes.  evs: 64 ints.  Two stages:
+//                    2 x (64 KROW + 34 D + 256) bytes.
 //   a wave's tile    the decode kernel's arithmetic with its operand orders (the header of fa_fp4_decode.hip): S^T = K Q^T with K
 //                    in fp4 as operand A and the lane's k_scale byte on the instruction, q at channels 64 M + 16 h and 64 M + 32 +
 //                    16 h; t = fma(s, f, ev) under the joint running maximum with the lazy rescale; P' rounded to e4m3; l from the
@@ -42,16 +56,21 @@
 // byte is only ever an operand of arithmetic.  Rows of no sequence are not written.
 //
 // fa_fp4_forward_varlen_mod (a sliding window, a softcap, attention sinks) launches the featured
-// instantiation fp4kv_prefill_kernel<Tag, KvqModSinks>: the same text with one more kernel argument (fa_kvq_common.h) and the
-// features as run-time switches, noted at the sites they change.
+// instantiation, fp4kv_prefill_kernel<Tag, KvqModSinks> at 128 and fp4kv_prefill_hdim_kernel<Tag, D, KvqModSinks> at 64 / 256:
+// the same text with one more kernel argument (fa_kvq_common.h) and the features as run-time switches, noted at the sites
+// they change.
 #include <climits>
 
-#include "fa_kvq_common.h"
+#include "fa_fp4_common.h"
 
 namespace fa {
 
 namespace {
 
+// ---- chunked prefill ------------------------------------------------------------------------------------------------------------
+// Two bodies: the 128 kernel below with its tile softmax inline, and fp4kv_prefill_hdim_kernel<.., D> for D = 64 / 256 on the shared
+// pieces of fa_fp4_common.h.  No one text over the three widths kept the instructions of both (profiles/fp4_merge.md has the
+// forms and their figures).
 constexpr int kKRow = 80;                                // bytes of a key's row in the K stage
 constexpr int kKBytes = 64 * kKRow;
 
@@ -352,30 +371,252 @@ __global__ __launch_bounds__(256, 2) void fp4kv_prefill_kernel(const Fp4PrefillP
     if (h == 0) p.lse[(size_t)hd * p.total_q + qstart + qi] = lse_v;
 }
 
-}  // namespace
+// D = 64 / 256: the same workgroup on Fp4Hd<D> and the shared tile pieces
+// what a lane holds of a tile in flight
+template <int D> struct Fp4hStaged {
+    u32x4 k[D == 256 ? 2 : 1];
+    uint32_t v[D / 32];
+    uint32_t s[2];
+};
 
-// md: null for fa_fp4_forward_varlen; else the featured call's kernel arguments
-static hipError_t launch_fp4_prefill_t(const Fp4VarlenArgs& a, const KvqModSinks* md, hipStream_t st) {
-    const Fp4PrefillParams p = fp4_prefill_params(a);
-    const unsigned row_tiles = (unsigned)((a.max_seqlen_q * p.G + 127) / 128);
-    const dim3 grid(row_tiles, (unsigned)a.c.heads_kv, (unsigned)a.batch);
-    route_hit(md ? ROUTE_FP4KV_PREFILL_MOD : ROUTE_FP4KV_PREFILL);
-    ProfScope ps(md ? K_FP4KV_PREFILL_MOD : K_FP4KV_PREFILL, st);
-    auto launch = [&](auto... mod) {
-        if (a.dtype == 2) hipLaunchKernelGGL((fp4kv_prefill_kernel<bf16_tag, decltype(mod)...>), grid, dim3(256), 0, st, p, mod...);
-        else hipLaunchKernelGGL((fp4kv_prefill_kernel<f16_tag, decltype(mod)...>), grid, dim3(256), 0, st, p, mod...);
+template <typename Tag, int D, typename... Mod>
+__global__ __launch_bounds__(256, Fp4Hd<D>::WAVES) void fp4kv_prefill_hdim_kernel(const Fp4PrefillParams p, const Mod... mod) {
+    constexpr bool MOD = sizeof...(Mod) != 0;                     // the featured instantiation: (KvqModSinks) follows p
+    static_assert(sizeof...(Mod) <= 1, "Mod...: nothing, or (KvqModSinks)");
+    static_assert(D != 128, "128: fp4kv_prefill_kernel");
+    const KvqModSinks md = kvq_mod_of<KvqModSinks>(mod...);
+    using C = Fp4Hd<D>;
+    constexpr int KT = C::KT, NM = C::NM, NDV = C::NDV, HB = C::HB, SB = C::SB, KROW = C::KROW;
+    constexpr int CPK = D / 32, NKC = D == 256 ? 2 : 1;           // 16-byte chunks a key; chunks a lane
+    __shared__ __attribute__((aligned(16))) char kt[2][KT * KROW];   // K stages: [key][D / 2 code bytes, D / 32 scale bytes, pad]
+    __shared__ __attribute__((aligned(16))) char vt[2][C::VT];    // V^T stages, [channel][32 key bytes in P's key order]
+    __shared__ __attribute__((aligned(16))) int evs[2][KT];       // the tiles' V exponents, by key
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int rt = gridDim.x - 1 - blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
+    const int G = p.G;
+
+    int qstart, kdummy;
+    const int nq = kv_cu_range(p.cu_q, b, p.total_q, p.max_q, qstart);
+    const int nk = kv_cu_range(p.cu_k, b, INT_MAX, p.cap, kdummy);
+    const int rows = nq * G, pr0 = 128 * rt;
+    if (pr0 >= rows) return;                                      // (the whole workgroup)
+    const int coff = nk - nq;
+    // the workgroup's keys [klo, kend) in tiles [t_lo, t_hi), the wave's [wlo, whi); without a window klo = wlo = t_lo = 0
+    // window: klo is the smallest lower bound of the workgroup's 128 rows, kend its largest upper bound + 1 (the sequence's end at
+    // most).  The ring walks tiles [klo / 64, ceil(kend / 64)) alone, O(N w) tiles a sequence; prologue, stage parity, the tile in
+    // flight and the table entry of t + 3 all count from t_lo.  The loader reads no table entry, code or scale byte of a 16-key
+    // group outside [klo, kend).  A wave computes the tiles that meet its own rows' band [wlo, whi) and only loads and meets the
+    // barrier on the others.
+    // (wl, wr <= 2^30, coff < 2^28, a token < 2^28: the sums stay inside an int)
+    const int wr0 = pr0 + 32 * w;
+    const bool wave_on = wr0 < rows;
+    const int qlo = (wave_on ? wr0 : pr0) / G, qhi = (min(wr0 + 32, rows) - 1) / G;
+    const int qlo_wg = pr0 / G, qhi_wg = (min(pr0 + 128, rows) - 1) / G;
+    const int kend = MOD ? max(0, min(nk, qhi_wg + coff + md.wr + 1)) : p.causal ? max(0, min(nk, qhi_wg + coff + 1)) : nk;
+    const int klo = MOD ? max(0, qlo_wg + coff - md.wl) : 0;
+    const int whi = !wave_on ? 0 : MOD ? max(0, min(nk, qhi + coff + md.wr + 1)) : p.causal ? max(0, min(nk, qhi + coff + 1)) : nk;
+    const int wlo = MOD ? max(0, qlo + coff - md.wl) : 0;
+    const int t_lo = klo / KT, t_hi = (kend + KT - 1) / KT;       // (t_hi <= t_lo: no visible key, the ring below runs no tile)
+
+    const int pr = wr0 + r;
+    const bool valid = pr < rows;
+    // (a padding row takes the wave's first token: its scores are masked like a real row's, and nothing of it is stored)
+    const int qi = valid ? pr / G : qlo, hd = hk * G + (valid ? pr - qi * G : 0);
+    i32x8_t qb[NM];
+    fp4h_load_q<NM>(p.q + (long long)(qstart + qi) * p.q_ts + hd * D + 16 * h, valid, qb);
+    const float qd = p.qds ? p.qds[b * p.qds_bs + hk] : 1.f;
+    const float kd = p.kds ? p.kds[b * p.kds_bs + hk] : 1.f;
+    const float vd = p.vds ? p.vds[b * p.vds_bs + hk] : 1.f;
+    const float f = (p.c_log2 * qd) * kd;                         // the one score factor of this workgroup, > 0
+    Fp4hRow rw;
+    rw.valid = valid;
+    rw.capped = MOD && md.cap2 != 0.f;
+    rw.rhi = MOD ? min(min(qi + coff + md.wr, nk - 1), kend - 1) : min(p.causal ? qi + coff : nk - 1, kend - 1);
+    rw.rlo = qi + coff - md.wl;
+    rw.ck = f * md.cap_k;
+    rw.cap2 = md.cap2;
+    rw.fe = rw.capped ? 1.f : f;
+
+    // ---- the loader: this wave's 16-key group of a tile (the lane maps: the header)
+    const int* tbl = p.table + b * p.tbl_rs;
+    const int rd = D == 64 ? lane & 7 : lane & 15;                // V: channels 8 rd ..
+    const int hv = (lane >> (D == 64 ? 3 : 4)) & 1;
+    const int jl = D == 64 ? (lane >> 4) & 1 : lane >> 5, cc = lane >> 5;   // (cc: D = 64 alone)
+    constexpr int NVK = D == 64 ? 2 : 4;                          // V: keys a lane (and pass)
+    auto vpos = [&](int c) { return D == 64 ? 4 * hv + 8 * jl + 2 * cc + c : 4 * hv + 8 * jl + c; };
+    // the group's table entry, -1 where the group lies outside [klo, kend) (no entry is read there)
+    auto fetch_page = [&](int t) -> int {
+        const int key0 = t * KT + 16 * w;
+        return key0 < kend && (!MOD || key0 + 16 > klo) ? tbl[key0 / p.ps] : -1;
     };
-    if (md) launch(*md);
-    else launch();
-    return hipGetLastError();
+    auto load_tile = [&](int t, int pg) -> Fp4hStaged<D> {
+        Fp4hStaged<D> st;
+#pragma unroll
+        for (int i = 0; i < NKC; ++i) st.k[i] = u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int i = 0; i < D / 32; ++i) st.v[i] = 0u;
+        st.s[0] = st.s[1] = lane < 16 ? 0x7f7f7f7fu : 127u;
+        const int key0 = t * KT + 16 * w;
+        if (key0 >= kend || (MOD && key0 + 16 <= klo) || (unsigned)pg >= (unsigned)p.nblk) return st;      // (wave-uniform)
+        const long long sl = key0 % p.ps;
+        const uint8_t* kp = p.kc + pg * p.kc_bs + sl * p.kc_ts + hk * HB;
+        const uint8_t* vp = p.vc + pg * p.vc_bs + sl * p.vc_ts + hk * HB + 4 * rd;
+        const uint8_t* sp = p.ksc + pg * p.ks_bs + sl * p.ks_ts + hk * SB;
+        const uint8_t* ep = p.vsc + pg * p.vs_bs + sl * p.vs_ts + hk;
+        const bool full = key0 + 16 <= kend;                     // no lane needs a compare
+#pragma unroll
+        for (int i = 0; i < NKC; ++i) {
+            const int id = lane + 64 * i, kk = id / CPK, kch = id % CPK;
+            if (id < 16 * CPK && (full || key0 + kk < kend)) st.k[i] = *reinterpret_cast<const u32x4*>(kp + kk * p.kc_ts + 16 * kch);
+        }
+#pragma unroll
+        for (int pass = 0; pass < (D == 64 ? 1 : D / 128); ++pass)
+#pragma unroll
+            for (int c = 0; c < NVK; ++c) {
+                const int pos = vpos(c);
+                if (full || key0 + pos < kend) st.v[NVK * pass + c] = *reinterpret_cast<const uint32_t*>(vp + 64 * pass + pos * p.vc_ts);
+            }
+        if (lane < 16) {
+            if (full || key0 + lane < kend) fp4h_scale_row<D>(sp + lane * p.ks_ts, st.s);
+        } else if (lane < 32) {
+            if (full || key0 + lane - 16 < kend) st.s[0] = ep[(lane - 16) * p.vs_ts];
+        }
+        return st;
+    };
+    auto store_tile = [&](const Fp4hStaged<D>& st, int buf) {
+#pragma unroll
+        for (int i = 0; i < NKC; ++i) {
+            const int id = lane + 64 * i, kk = id / CPK, kch = id % CPK;
+            if (id < 16 * CPK) *reinterpret_cast<u32x4*>(kt[buf] + KROW * (16 * w + kk) + 16 * kch) = st.k[i];
+        }
+        if (lane < 16) {
+            char* srow = kt[buf] + KROW * (16 * w + lane) + HB;
+            if constexpr (D == 64) *reinterpret_cast<uint16_t*>(srow) = (uint16_t)st.s[0];
+            else *reinterpret_cast<u32x2*>(srow) = u32x2{st.s[0], st.s[1]};
+        } else if (lane < 32) {
+            evs[buf][16 * w + lane - 16] = (int)st.s[0] - 127;
+        }
+        constexpr uint32_t LO = 0x0f0f0f0fu;
+        if constexpr (D == 64) {
+            // two keys x eight channels a lane: the even (odd) channels of the key pair in a byte each
+            const uint32_t e = (st.v[0] & LO) | ((st.v[1] & LO) << 4), o = ((st.v[0] >> 4) & LO) | (st.v[1] & ~LO);
+            char* base = vt[buf] + 16 * (w >> 1) + 8 * hv + 2 * (2 * (w & 1) + jl) + cc;
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                base[vt4_off(8 * rd + 2 * m)] = (char)(e >> (8 * m));
+                base[vt4_off(8 * rd + 2 * m + 1)] = (char)(o >> (8 * m));
+            }
+        } else {
+            // four keys x eight channels a lane and pass of 128 channels: the even (odd) channels of key pairs (0, 1) and (2, 3) in a byte each
+            char* base = vt[buf] + 16 * (w >> 1) + 8 * hv + 2 * (2 * (w & 1) + jl);
+#pragma unroll
+            for (int pass = 0; pass < D / 128; ++pass) {
+                const uint32_t x[4] = {st.v[4 * pass], st.v[4 * pass + 1], st.v[4 * pass + 2], st.v[4 * pass + 3]};
+                uint32_t ea, oa, eb, ob;
+                fp4h_pair_nibbles(x, ea, oa, eb, ob);
+                // bytes {a.m, b.m} side by side: channel pair m = 0, 1 in the first word's halves, m = 2, 3 in the second's
+                const uint32_t e01 = __builtin_amdgcn_perm(eb, ea, 0x05010400u), e23 = __builtin_amdgcn_perm(eb, ea, 0x07030602u);
+                const uint32_t o01 = __builtin_amdgcn_perm(ob, oa, 0x05010400u), o23 = __builtin_amdgcn_perm(ob, oa, 0x07030602u);
+                const int row0 = 128 * pass + 8 * rd;
+                *reinterpret_cast<uint16_t*>(base + vt4_off(row0 + 0)) = (uint16_t)e01;
+                *reinterpret_cast<uint16_t*>(base + vt4_off(row0 + 1)) = (uint16_t)o01;
+                *reinterpret_cast<uint16_t*>(base + vt4_off(row0 + 2)) = (uint16_t)(e01 >> 16);
+                *reinterpret_cast<uint16_t*>(base + vt4_off(row0 + 3)) = (uint16_t)(o01 >> 16);
+                *reinterpret_cast<uint16_t*>(base + vt4_off(row0 + 4)) = (uint16_t)e23;
+                *reinterpret_cast<uint16_t*>(base + vt4_off(row0 + 5)) = (uint16_t)o23;
+                *reinterpret_cast<uint16_t*>(base + vt4_off(row0 + 6)) = (uint16_t)(e23 >> 16);
+                *reinterpret_cast<uint16_t*>(base + vt4_off(row0 + 7)) = (uint16_t)(o23 >> 16);
+            }
+        }
+    };
+
+    f32x16 oacc[NDV];
+#pragma unroll
+    for (int t = 0; t < NDV; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) oacc[t][i] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;                         // running max of t, in log2 units
+
+    // ---- one 64-key tile of this wave out of stage buf
+    auto compute = [&](int k0, int buf) {
+        f32x16 sacc[2];
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+            const char* row = kt[buf] + KROW * (32 * kb + r);
+            u32x4 a[NM];
+#pragma unroll
+            for (int M = 0; M < NM; ++M) a[M] = *reinterpret_cast<const u32x4*>(row + 32 * M + 16 * h);
+            uint32_t ws[2];
+            fp4h_scale_row<D>(row + HB, ws);
+            sacc[kb] = fp4h_scores<NM>(a, ws, h, qb);
+        }
+        const bool need_mask = k0 + KT > kend || (MOD ? k0 + KT - 1 > qlo + coff + md.wr : p.causal && k0 + KT - 1 > qlo + coff);
+        const bool need_lo = MOD && k0 < qhi + coff - md.wl;
+        fp4h_softmax_pv<D>(sacc, evs[buf], vt[buf], oacc, m_run, l_run, rw, k0, r, h, need_mask, need_lo);
+    };
+
+    // ---- the ring over tiles [t_lo, t_hi): tile t in stage t & 1, tile t + 1 in the other, tile t + 2 in st, the table entry of
+    // tile t + 3 in pg.  Every wave meets the prologue's barrier and one a tile, whatever its own band (an empty range: the one).
+    Fp4hStaged<D> st = load_tile(t_lo, fetch_page(t_lo));
+    int pg = fetch_page(t_lo + 1);
+    store_tile(st, t_lo & 1);
+    st = load_tile(t_lo + 1, pg);
+    pg = fetch_page(t_lo + 2);
+    __syncthreads();
+    for (int t = t_lo; t < t_hi; ++t) {
+        store_tile(st, (t + 1) & 1);              // (its last readers, of tile t - 1, are behind the barrier)
+        st = load_tile(t + 2, pg);
+        pg = fetch_page(t + 3);
+        // (a tile wholly right or, with a window, left of the wave's band: skipped)
+        if (t * KT < whi && (!MOD || (t + 1) * KT > wlo)) compute(t * KT, t & 1);
+        __syncthreads();
+    }
+
+    // ---- epilogue.  sinks: the sink joins here, once per row, after the last tile: a softmax column with a zero value (it multiplies no V)
+    const float l_tot = l_run + wave_half_swap(l_run);
+    if (!valid) return;
+    const float snk = MOD && md.sinks ? md.sinks[hd % md.sink_heads] : -INFINITY;
+    bool dead;
+    float inv, lse_v;
+    if (snk != -INFINITY) {                              // ex_sink_norm is finite at +-1e4
+        float iv;
+        ex_sink_norm(m_run * 0.6931471805599453f, l_tot, snk, iv, lse_v);
+        dead = false;                                    // (no visible key: iv = 0, lse = sink)
+        inv = vd * iv;
+    } else {                                             // a head at -inf: the epilogue of the call without sinks, bit for bit
+        dead = l_tot == 0.f;                             // no visible key: o = 0, lse = -inf (a NaN l is not dead: it propagates)
+        inv = vd * (1.f / l_tot);                        // v_descale once, with 1 / l
+        lse_v = dead ? -INFINITY : (m_run + log2f(l_tot)) * 0.6931471805599453f;
+    }
+    fp4h_store_o<Tag, NDV>(p.o + ((size_t)(qstart + qi) * p.hq + hd) * D, oacc, inv, dead, h);
+    if (h == 0) p.lse[(size_t)hd * p.total_q + qstart + qi] = lse_v;
 }
 
-hipError_t launch_fp4_prefill(const Fp4VarlenArgs& a, hipStream_t st) { return launch_fp4_prefill_t(a, nullptr, st); }
+}  // namespace
 
-hipError_t launch_fp4_prefill_mod(const Fp4VarlenArgs& a, const Fp8Mod& m, hipStream_t st) {
-    if (!m.any()) return launch_fp4_prefill(a, st);      // the parent call, launch for launch
+// (the route and the profiler id: as in launch_fp4_kvcache, fa_fp4_decode.hip)
+hipError_t launch_fp4_prefill(const Fp4VarlenArgs& a, const Fp8Mod& m, hipStream_t st) {
+    if (a.d != 64 && a.d != 128 && a.d != 256) return hipErrorInvalidValue;
+    const Fp4PrefillParams p = fp4_prefill_params(a);
+    const dim3 grid((unsigned)((a.max_seqlen_q * p.G + 127) / 128), (unsigned)a.c.heads_kv, (unsigned)a.batch);
     const KvqModSinks md{kvq_mod_args(m, a.causal != 0), m.sinks, (int)(m.sink_heads > 0 ? m.sink_heads : 1)};
-    return launch_fp4_prefill_t(a, &md, st);
+    route_hit(a.d != 128 ? ROUTE_FP4KV_PREFILL_HDIM : m.any() ? ROUTE_FP4KV_PREFILL_MOD : ROUTE_FP4KV_PREFILL);
+    ProfScope ps(a.d != 128 ? K_FP4KV_PREFILL_HDIM : m.any() ? K_FP4KV_PREFILL_MOD : K_FP4KV_PREFILL, st);
+    fp4h_width(a.d, [&](auto dc) {
+        constexpr int D = decltype(dc)::value;
+        kvq_dispatch(a.dtype, false, [&](auto tag, auto) {
+            using T = decltype(tag);
+            if constexpr (D == 128) {
+                if (m.any()) hipLaunchKernelGGL((fp4kv_prefill_kernel<T, KvqModSinks>), grid, dim3(256), 0, st, p, md);
+                else hipLaunchKernelGGL((fp4kv_prefill_kernel<T>), grid, dim3(256), 0, st, p);
+            } else {
+                if (m.any()) hipLaunchKernelGGL((fp4kv_prefill_hdim_kernel<T, D, KvqModSinks>), grid, dim3(256), 0, st, p, md);
+                else hipLaunchKernelGGL((fp4kv_prefill_hdim_kernel<T, D>), grid, dim3(256), 0, st, p);
+            }
+        });
+    });
+    return hipGetLastError();
 }
 
 }  // namespace fa

@@ -74,10 +74,10 @@ int set_option(const char* name, int value);   // returns 0, or -1 for an unknow
 // "fp8in_fwd_hdim", "fp8in_fwd_varlen_hdim", "fp8kv_split_hdim": the fp8 calls at head dim 64 or 256 (the _hdim entry points);
 // "fp8kv_split_varlen": the packed-query split kernel of fa_fp8_forward_kvcache_varlen / fa_fp8_kvcache_step_varlen;
 // "fp8kv_step_prep_varlen": the prep launch of fa_fp8_kvcache_step_varlen with packed tokens or at head dim 64 / 256;
-// "fp4kv_append", "fp4kv_split": the two kernels of the MXFP4 KV cache (fa_fp4_decode.hip);
-// "fp4kv_prefill": the packed-query prefill kernel over the paged MXFP4 cache (fa_fp4_prefill.hip);
-// "fp4kv_split_mod", "fp4kv_prefill_mod": the featured kernels of the two MXFP4 cache readers (window, softcap, sinks);
-// "fp4kv_append_hdim", "fp4kv_split_hdim", "fp4kv_prefill_hdim": the MXFP4 cache kernels at head dims 64 / 256 (fa_fp4_hdim.hip).
+// "fp4kv_append", "fp4kv_split": the two kernels of the MXFP4 KV cache at head dim 128 (fa_fp4_decode.hip);
+// "fp4kv_prefill": the packed-query prefill kernel over the paged MXFP4 cache at head dim 128 (fa_fp4_prefill.hip);
+// "fp4kv_split_mod", "fp4kv_prefill_mod": the featured instantiations of the two readers at 128 (window, softcap, sinks);
+// "fp4kv_append_hdim", "fp4kv_split_hdim", "fp4kv_prefill_hdim": the three calls at head dims 64 / 256, plain or featured.
 enum RouteId { ROUTE_DKDV_STREAM = 0, ROUTE_DKDV_LEAN, ROUTE_FP8Q_FUSED, ROUTE_FP8Q_TWO_PASS, ROUTE_FP8Q_STATIC, ROUTE_FP8IN_FWD_MOD,
                ROUTE_FP8IN_FWD_VARLEN_MOD, ROUTE_FP8KV_SPLIT_MOD, ROUTE_FP8KV_STEP_PREP, ROUTE_FP8IN_FWD_HDIM,
                ROUTE_FP8IN_FWD_VARLEN_HDIM, ROUTE_FP8KV_SPLIT_HDIM, ROUTE_FP8KV_SPLIT_VARLEN, ROUTE_FP8KV_STEP_PREP_VARLEN, ROUTE_FP4KV_APPEND,
@@ -585,10 +585,11 @@ hipError_t launch_kv_combine_sink(void* o, float* lse, float* po, float* plse, i
 hipError_t launch_kv_combine_packed(void* o, float* lse, float* po, float* plse, const int* cu_seqlens_q, int64_t heads_q, int64_t total_q,
                                     int64_t d, int dtype, int splits, const float* sinks, int sink_heads, hipStream_t st);
 
-// The MXFP4 KV cache (fa_fp4_decode.hip; fa_fp4_kvcache_append, fa_fp4_forward_kvcache): e2m1 codes, two a byte, (cache_batch,
-// cache_len, heads_kv, 64), with E8M0 scale bytes, k_scale (.., heads_kv, 4) and v_scale (.., heads_kv); with block_table the four
-// are pools (num_blocks, page_size, ..).  Each array has its own batch (or page) and token stride, in bytes.  Fp4Cache is what
-// the append and the decode call share.
+// The MXFP4 KV cache at head dim d in {64, 128, 256} (fa_fp4_decode.hip: append and decode, fa_fp4_prefill.hip: chunked prefill;
+// the fa_fp4_* entry points; DESIGN.md sections 9zg - 9zj): e2m1 codes, two a byte, (cache_batch, cache_len, heads_kv, d / 2), with
+// E8M0 scale bytes, k_scale (.., heads_kv, d / 32) and v_scale (.., heads_kv); with block_table the four are pools (num_blocks,
+// page_size, ..).  Each array has its own batch (or page) and token stride, in bytes.  Fp4Cache is what the three calls share.
+// One launcher a call; each refuses any other d with hipErrorInvalidValue.
 struct Fp4Cache {
     void *k_cache = nullptr, *k_scale = nullptr, *v_cache = nullptr, *v_scale = nullptr;
     const int *cache_seqlens = nullptr, *block_table = nullptr, *cache_batch_idx = nullptr;   // untrusted device memory, or null
@@ -603,7 +604,7 @@ struct Fp4AppendArgs {
     int64_t kds_bs = 0, vds_bs = 0;
     int64_t batch = 0, seqlen_new = 0, kn_bs = 0, kn_ts = 0, vn_bs = 0, vn_ts = 0;
     int dtype = 0;                                          // FA_DTYPE_F16 / FA_DTYPE_BF16
-    int64_t d = 128;                                        // the head dim: 128, or 64 / 256 through launch_fp4_kvcache_append_hdim alone
+    int64_t d = 128;                                        // the head dim: 64, 128 or 256
 };
 hipError_t launch_fp4_kvcache_append(const Fp4AppendArgs& a, hipStream_t st);
 struct Fp4KvArgs {
@@ -618,13 +619,13 @@ struct Fp4KvArgs {
     float scale = 0.f;
     int64_t num_splits = 1;                                 // >= 1 (the C layer resolves 0 through fp8kv_num_splits)
     void* workspace = nullptr;                              // kv_workspace_bytes(batch, heads_q, seqlen_q, d, num_splits)
-    int64_t d = 128;                                        // the head dim: 128, or 64 / 256 through launch_fp4_kvcache_hdim alone
+    int64_t d = 128;                                        // the head dim: 64, 128 or 256
 };
-hipError_t launch_fp4_kvcache(const Fp4KvArgs& a, hipStream_t st);
-// The featured call (fa_fp4_forward_kvcache_mod): Fp8Mod's window, softcap and sinks over the MXFP4 cache.  A
-// call whose Fp8Mod is not any() is launch_fp4_kvcache; any other runs fp4kv_split_kernel<.., KvqMod>, and with sinks num_splits >= 2 (the
-// sink joins in launch_kv_combine_sink).  fp8kv_split_len is the length the split rule takes.
-hipError_t launch_fp4_kvcache_mod(const Fp4KvArgs& a, const Fp8Mod& m, hipStream_t st);
+// The decode call with Fp8Mod's window, softcap and sinks.  The kernel is fp4kv_split_kernel at 128 and
+// fp4kv_split_hdim_kernel<.., D> at 64 / 256: its plain instantiation for an Fp8Mod that is not any(), <.., KvqMod> for any
+// other, and with sinks num_splits >= 2 (the sink joins in launch_kv_combine_sink).  fp8kv_split_len is the length the split
+// rule takes.
+hipError_t launch_fp4_kvcache(const Fp4KvArgs& a, const Fp8Mod& m, hipStream_t st);
 // Chunked prefill over the paged cache (fa_fp4_prefill.hip; fa_fp4_forward_varlen): packed e4m3 queries, one launch, no workspace.
 // c.block_table is non-null, c.cache_len = max_blocks_per_seq * page_size, c.cache_seqlens and c.cache_batch_idx are null.
 struct Fp4VarlenArgs {
@@ -638,16 +639,11 @@ struct Fp4VarlenArgs {
     int64_t batch = 0, heads_q = 0, total_q = 0, max_seqlen_q = 0, q_ts = 0;
     int dtype = 0, causal = 0;
     float scale = 0.f;
-    int64_t d = 128;                                        // the head dim: 128, or 64 / 256 through launch_fp4_prefill_hdim alone
+    int64_t d = 128;                                        // the head dim: 64, 128 or 256
 };
-hipError_t launch_fp4_prefill(const Fp4VarlenArgs& a, hipStream_t st);
-// The featured call (fa_fp4_forward_varlen_mod): not any() is launch_fp4_prefill; any other runs fp4kv_prefill_kernel<.., KvqModSinks>, which walks
-// the key tiles of each workgroup's band alone and takes the sink in its epilogue (no workspace).
-hipError_t launch_fp4_prefill_mod(const Fp4VarlenArgs& a, const Fp8Mod& m, hipStream_t st);
-// The three calls at a.d in {64, 128, 256} (fa_fp4_hdim.hip; the fa_fp4_*_hdim entry points): the cache at width d,
-// codes (.., heads_kv, d / 2), k_scale (.., heads_kv, d / 32), v_scale (.., heads_kv).  d == 128 is the parent launcher above.
-hipError_t launch_fp4_kvcache_append_hdim(const Fp4AppendArgs& a, hipStream_t st);
-hipError_t launch_fp4_kvcache_hdim(const Fp4KvArgs& a, const Fp8Mod& m, hipStream_t st);
-hipError_t launch_fp4_prefill_hdim(const Fp4VarlenArgs& a, const Fp8Mod& m, hipStream_t st);
+// The kernel is fp4kv_prefill_kernel at 128 and fp4kv_prefill_hdim_kernel<.., D> at 64 / 256: its plain instantiation for an
+// Fp8Mod that is not any(), <.., KvqModSinks> for any other, which walks the key tiles of each workgroup's band alone and takes
+// the sink in its epilogue (no workspace).
+hipError_t launch_fp4_prefill(const Fp4VarlenArgs& a, const Fp8Mod& m, hipStream_t st);
 
 }  // namespace fa

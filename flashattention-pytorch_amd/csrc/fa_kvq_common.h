@@ -29,8 +29,8 @@ __device__ __forceinline__ void transpose4x4(const uint32_t (&x)[4], uint32_t (&
 }
 
 // the MXFP4 V^T image: 32 key bytes a channel row, 16 bytes of padding after every eight rows (the bank argument: the header of
-// fa_fp4_decode.hip)
-constexpr int kVt4Bytes = 32 * 128 + 16 * 16;
+// fa_fp4_decode.hip; its size at head dim D: Fp4Hd<D>::VT, fa_fp4_common.h)
+constexpr int kVt4Bytes = 32 * 128 + 16 * 16;           // at head dim 128
 __device__ __forceinline__ int vt4_off(int row) { return 32 * row + 16 * (row >> 3); }
 
 // What a featured instantiation takes beside its kernel's parameter block (the _mod calls; DESIGN.md sections 9zc, 9zi).  It is
@@ -59,7 +59,7 @@ inline KvqMod kvq_mod_args(const Fp8Mod& m, bool causal) {
     return md;
 }
 
-// ---- the MXFP4 cache kernels' parameter blocks (fa_fp4_decode.hip, fa_fp4_prefill.hip, fa_fp4_hdim.hip) and what fills them from
+// ---- the MXFP4 cache kernels' parameter blocks (fa_fp4_decode.hip, fa_fp4_prefill.hip) and what fills them from
 // the launch arguments: one definition each, whatever the head dim of the kernel that takes it
 struct Fp4KvParams {
     const uint8_t *q, *kc, *ksc, *vc, *vsc;

@@ -1684,7 +1684,7 @@ int fa_fp4_forward_varlen_mod(const void* q, const void* k_cache, const void* k_
                               int64_t k_descale_batch_stride, int64_t v_descale_batch_stride, int causal, double softmax_scale,
                               void* stream, int64_t window_left, int64_t window_right, double softcap, const float* sinks,
                               int64_t sink_heads);
-/* --- The MXFP4 KV cache at head dims 64 and 256 beside 128 (csrc/fa_fp4_hdim.hip), forward: each call is its parent's
+/* --- The MXFP4 KV cache at head dims 64 and 256 beside 128 (csrc/fa_fp4_decode.hip, csrc/fa_fp4_prefill.hip), forward: each call is its parent's
  * argument list with the head dim under the name head_dim in {64, 128, 256}; the parent of the append is fa_fp4_kvcache_append, the
  * parents of the two readers are their _mod forms.  Any other head_dim: FA_ERR_UNSUPPORTED, "head_dim N is not supported (64, 128 or
  * 256)".  At 128 each call IS its parent: the same checks, launches and route counts.  The cache is the parent's rule at width d:

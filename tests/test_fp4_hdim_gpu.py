@@ -1,4 +1,4 @@
-"""GPU: the MXFP4 KV cache at head dims 64 and 256 (csrc/fa_fp4_hdim.hip) through common.mxfp4_attention.
+"""GPU: the MXFP4 KV cache at head dims 64 and 256 (csrc/fa_fp4_decode.hip, csrc/fa_fp4_prefill.hip) through common.mxfp4_attention.
 
   * the append bit for bit against the rule restated here in torch at width d, untouched bytes included;
   * decode and prefill against fp64 attention on code * 2^e * descale, held to the sharp bar (tests/ex_full_ref.sharp_bar, factor 2)
